@@ -29,6 +29,9 @@ MFMA peak, counted in the reference's direct-conv FLOPs), `cpu_baseline` (the or
 non-keyframe of the same clip: 2 warm-up + 5 timed runs, median), `cpu_baseline_c1` (BASELINE configs[0]: PSPNet-18 HR 720x960 on the
 CPU) and `parity` (max-abs error and argmax agreement of that frame against the oracle).
 
+`--dump-outputs DIR` writes what the last timed step returned (every lane's output, a seeded sample of it when large) to DIR as float32 .npy files,
+so that two builds run with the same arguments can be compared output for output (dump_outputs()).
+
 stdout carries the JSON line and nothing else (file descriptor 1 is pointed at stderr while the bench runs: RCCL prints a banner there).
 ARSEG_RCCL_LOOPBACK=1 (N = 1): the N > 1 step on a one-rank RCCL communicator, the collective really issued -- a check of the exchange path on a
 1-GPU box, marked `rccl_loopback` on the line.  ARSEG_DIST_BACKEND=gloo: rehearsal of an N-rank schedule on fewer GPUs than ranks.
@@ -47,8 +50,9 @@ import torch
 import torch.distributed as dist
 
 GOP = 12
-MIN_TIMED_S = 0.4          # a timed region shorter than this is repeated with a whole multiple of --steps (flagged in `steps_note`); the default
-                           # and the driver's `--steps 20` last longer (a step = `--streams` GOP steps in flight at a time, see the docstring)
+VARIANT_MIN_TIMED_S = 0.12     # a variant line's timed region (--variant-steps) shorter than this is repeated with a whole multiple of its steps;
+                               # the headline line times exactly --steps
+DUMP_BYTES = 60_000_000        # --dump-outputs: the payload of all files together (the contract allows 64 MB)
 # headline workload = BASELINE.json configs[1]; "psp2k" = the same network with the 512x1024 *non-key* reading of the metric
 # (SURVEY.md section 8 preamble); "bise" = configs[2] (BiSeNet-18, Cityscapes sizes) measured in fp32 --
 # the bf16 MFMA conv path that config names is not built yet, so it is an extra, not the headline.
@@ -144,6 +148,29 @@ def build_nets(dev, cfg, to_device=True):
     return hr.to(dev).eval(), lr.to(dev).eval(), sd_hr, sd_lr
 
 
+def dump_outputs(dirname, lane_outs, budget, prefix=""):
+    """--dump-outputs: the output of the last timed step of every lane -- this rank's batch of non-keyframes, log-probabilities [11,n_cls,H,W]
+    (BiSeNet: the fused argmax label maps [11,H,W]) -- as DIR/<prefix>lane<i>.npy in float32.  When the lanes' outputs together exceed
+    `budget` bytes, each file holds the same fixed, seeded sample of elements (flat indices into the output, ascending, saved as
+    DIR/<prefix>sample_index.npy in float64).  The inputs are seeded (synth), so two builds run with the same arguments compare element
+    for element."""
+    import numpy as np
+
+    os.makedirs(dirname, exist_ok=True)
+    numel = lane_outs[0].numel()
+    idx = None
+    if 4 * numel * len(lane_outs) > budget:
+        n = budget // (4 * len(lane_outs) + 8)
+        idx = np.sort(np.random.default_rng(0).choice(numel, n, replace=False))
+        np.save(os.path.join(dirname, f"{prefix}sample_index.npy"), idx.astype(np.float64))
+        idx_d = torch.from_numpy(idx).to(lane_outs[0].device)
+    for i, o in enumerate(lane_outs):
+        a = o.reshape(-1)[idx_d] if idx is not None else o
+        np.save(os.path.join(dirname, f"{prefix}lane{i}.npy"), a.float().cpu().numpy())
+    _log(f"wrote {len(lane_outs)} lane output(s) of shape {list(lane_outs[0].shape)} to {dirname}" +
+         (f" ({len(idx)} sampled elements each)" if idx is not None else ""))
+
+
 def main():
     ap = argparse.ArgumentParser()
     ap.add_argument("--gpus", type=int, default=1)
@@ -167,7 +194,12 @@ def main():
     ap.add_argument("--no-graph", action="store_true", help="enqueue every step eagerly instead of replaying the captured HIP graph (N = 1 only)")
     ap.add_argument("--conv-math", choices=["f16x3", "f32", "f16"], default="f16x3",
                     help="MFMA back end of the fp32 conv GEMMs: f16x3 = split-fp16 emulation (3 fp16 MFMAs, fp32 accumulate), f32 = fp32 MFMA")
+    ap.add_argument("--dump-outputs", metavar="DIR",
+                    help="after the timed steps, write what the last timed step returned (one array per lane) to DIR as float32 .npy; "
+                         "see dump_outputs()")
     args = ap.parse_args()
+    if args.steps < 1:
+        ap.error("--steps must be at least 1")
 
     # The contract is ONE JSON line on stdout.  Libraries write there too (RCCL prints a five-line version banner through C stdio when its first
     # communicator is created, and the buffered text comes out at exit -- after the JSON line, seen with ARSEG_RCCL_LOOPBACK=1): from here on file
@@ -367,17 +399,17 @@ def run_config(args, config, steps, warmup, world, rank, dev, backend, full):
 
     def run_steps(k, step=step):
         """k bench steps = k passes over the batch of L independent GOP clips per rank: one replay of the lane graphs each (N = 1), or L GOP
-        steps rotated over the L streams (eager: N > 1, --no-graph, the comparison plans)."""
-        out = None
+        steps rotated over the L streams (eager: N > 1, --no-graph, the comparison plans).  Returns the last step's outputs, one per lane."""
+        outs = [None] * L
         if gop_graph is not None and step is step_main:
             with torch.cuda.stream(streams[0]):
                 for _ in range(k):
-                    out = gop_graph.replay(join=False)[0]      # (the timed region ends in a device-wide synchronize)
-            return out
+                    outs = gop_graph.replay(join=False)      # (the timed region ends in a device-wide synchronize)
+            return outs
         for i in range(k * L):
             with torch.cuda.stream(streams[i % L]):
-                out = step()
-        return out
+                outs[i % L] = step()
+        return outs
 
     def timed_region(k, step=step):
         torch.cuda.synchronize()
@@ -400,19 +432,12 @@ def run_config(args, config, steps, warmup, world, rank, dev, backend, full):
     _log("warm-up (conv plans are tuned on first use)")
     run_steps(warmup)
     _log("timed region")
-    steps_requested = steps
-    elapsed, outs = timed_region(steps)
-    requested_run = {"steps": steps, "timed_s": elapsed, "value": world * GPR * (GOP - 1) * L * steps / elapsed}      # the run the command line asked for, as timed
-    steps_note = None
-    min_s = MIN_TIMED_S if full else 0.3 * MIN_TIMED_S          # variant lines: a shorter window, still far above launch jitter
-    if elapsed < min_s:
-        # the requested K steps are too short a window to trust (0.12 s at --steps 20): time a whole multiple of K that lasts
-        # >= 1 s instead; the multiple follows from the max-over-ranks time, so every rank runs the same number of steps
-        steps = steps_requested * int(math.ceil(1.05 * min_s / max(elapsed, 1e-6)))
-        elapsed, outs = timed_region(steps)
-        steps_note = (f"--steps {steps_requested} lasted {requested_run['timed_s']:.3f} s ({requested_run['value']:.0f} frames/s, `requested_run`): shorter than the "
-                      f"{min_s:.2f} s this bench trusts, so `value` / `steps` / `ms_per_step` are from a second region of {steps} = {steps // steps_requested} x "
-                      f"{steps_requested} steps, timed the same way (barrier + synchronize on both sides, max over ranks)")
+    elapsed, lane_outs = timed_region(steps)
+    if not full and elapsed < VARIANT_MIN_TIMED_S:
+        # a variant's --variant-steps can be too short a window to trust: time a whole multiple of them instead; the multiple follows from the
+        # max-over-ranks time, so every rank runs the same number of steps
+        steps *= int(math.ceil(1.05 * VARIANT_MIN_TIMED_S / max(elapsed, 1e-6)))
+        elapsed, lane_outs = timed_region(steps)
     # N > 1: the rolling CReFF kernel's persistent workgroups hold EVERY compute unit for ~1.7 ms at a time, and an RCCL kernel that cannot get a
     # compute unit on one GPU keeps its peers' RCCL kernels spinning on theirs.  Whether leaving a few compute units to the collective pays cannot
     # be measured on the 1-GPU boxes this was built on, so the first multi-GPU run decides it by measurement: the same K steps once more with
@@ -427,12 +452,15 @@ def run_config(args, config, steps, warmup, world, rank, dev, backend, full):
         r_el, r_outs = timed_region(steps)
         res_cus = {"creff_max_wgs": max(1, cus - 16), "value": world * GPR * (GOP - 1) * L * steps / r_el, "ms_per_step": 1e3 * r_el / steps}
         if r_el < elapsed:
-            elapsed, outs = r_el, r_outs
+            elapsed, lane_outs = r_el, r_outs
         else:
             ops.configure(creff_max_wgs=0)
         reserve = {"all_compute_units": all_cus, "sixteen_left_to_the_collective": res_cus, "chosen_creff_max_wgs": ops.config.creff_max_wgs,
                    "what": "the mandated exchange plan timed twice with the same K: the CReFF kernel on every compute unit / 16 compute units left free for the RCCL "
                            "kernels; `value` is the faster one"}
+    if full and args.dump_outputs:          # before any other pass: the graph lanes' outputs are static tensors that the next replay overwrites
+        dump_outputs(args.dump_outputs, lane_outs, DUMP_BYTES // world, f"rank{rank}_" if world > 1 else "")
+    outs = lane_outs[0]
     plans = None
     if step_local is not None:
         run_steps(max(1, warmup // 2), step_local)
@@ -487,7 +515,7 @@ def run_config(args, config, steps, warmup, world, rank, dev, backend, full):
                    "bise03_fp16": "non-keyframe frames/sec (backbone+CReFF), BiSeNet-18 1024x2048 / LR 0.3x 307x614, fp16"}[config],
         "value": nonkey_per_step * steps / elapsed,
         "unit": "frames/s",
-        "n_gpus": world, "steps": steps, "steps_requested": steps_requested, "steps_note": steps_note, "requested_run": requested_run, "warmup": warmup, "timed_s": elapsed,
+        "n_gpus": world, "steps": steps, "warmup": warmup, "timed_s": elapsed,
         "ms_per_step": 1e3 * elapsed / steps,
         "higher_is_better": True, "scaling": "weak", "vs_baseline": None,
         "dtype": storage if storage != "f32" else ("f16" if args.conv_math == "f16" else "f32"), "data": "synthetic",

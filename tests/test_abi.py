@@ -217,22 +217,26 @@ def test_synthetic_clip_matches_the_reference_mv_format():
     assert np.array_equal(c["frames"], c2["frames"]) and np.array_equal(mv, c2["mv"])     # seeded
 
 
-def test_reference_attention_imports_with_shim():
-    """INTEGRATION.md level 1: with shims/ in front of sys.path the UNMODIFIED reference model/attention.py imports, its
-    ``from localAttention import ...`` resolving to the HIP-backed shim and its own ``model`` package staying the reference's."""
+def test_reference_attention_imports_with_shim(tmp_path):
+    """INTEGRATION.md level 1: with shims/ in front of sys.path, unmodified reference code imports: a ``model/attention.py`` whose
+    ``from localAttention import ...`` names the five functions the reference's does (model/attention.py:7-11) gets the HIP-backed shim,
+    and its own ``model`` package keeps resolving to the caller's tree (here a stand-in for the reference's, written under tmp_path)."""
     import subprocess
     import sys
 
-    ref = "/root/reference"
-    if not os.path.isdir(os.path.join(ref, "model")):
-        pytest.skip("reference tree not present (GPU box)")
+    ref = tmp_path / "ref"
+    (ref / "model").mkdir(parents=True)
+    (ref / "model" / "__init__.py").write_text("")
+    names = ("similar_forward", "similar_backward", "weighting_forward", "weighting_backward_ori", "weighting_backward_weight")
+    (ref / "model" / "attention.py").write_text(f"from localAttention import {', '.join(names)}\n")
+    ref = str(ref)
     code = (
         "import sys; sys.dont_write_bytecode = True\n"
         f"sys.path.insert(0, {ref!r}); sys.path.insert(0, {os.path.join(ROOT, 'shims')!r})\n"
         "import localAttention, model.attention as A\n"
         f"assert localAttention.__file__.startswith({os.path.join(ROOT, 'shims')!r}), localAttention.__file__\n"
         f"assert A.__file__.startswith({ref!r}), A.__file__\n"
-        "assert A.similar_forward is localAttention.similar_forward and hasattr(A, 'MyAttention')\n"
+        f"assert all(getattr(A, n) is getattr(localAttention, n) for n in {names!r})\n"
         "print('ok')\n")
     r = subprocess.run([sys.executable, "-c", code], capture_output=True, text=True, env={**os.environ, "PYTHONDONTWRITEBYTECODE": "1"})
     assert r.returncode == 0 and "ok" in r.stdout, r.stderr[-2000:]
