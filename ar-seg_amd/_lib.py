@@ -88,6 +88,7 @@ PROTOTYPES = {
     "arseg_maxpool3x3s2_16_fwd": (c_int, [_P, _P, c_int, c_int, c_int, c_int, c_int, _STREAM]),
     "arseg_global_mean16_workspace_bytes": (c_size_t, [c_int, c_int, c_int, c_int]),
     "arseg_global_mean16_fwd": (c_int, [_P, c_int, _P, c_int, c_int, c_int, c_int, c_int, _P, c_size_t, _STREAM]),
+    "arseg_global_max16_fwd": (c_int, [_P, c_int, _P, c_int, c_int, c_int, c_int, c_int, _P, c_size_t, _STREAM]),
     "arseg_resize16_fwd": (c_int, [_P, _P] + [c_int] * 11 + [_STREAM]),
     "arseg_scale_add16_fwd": (c_int, [_P, _P, _P, _P, _P, c_int, c_int, c_int, c_int, _STREAM]),
     "arseg_head16_fwd": (c_int, [_P, c_int, c_int, _P, _P, _P, c_int, c_int, c_int, c_int, c_int, _STREAM]),
@@ -100,6 +101,9 @@ PROTOTYPES = {
     "arseg_psp_pool_matrix_workspace_bytes": (c_size_t, [c_int, c_int, c_int, c_int, c_int, POINTER(c_int)]),
     "arseg_psp_pool_matrix_fwd": (c_int, [_P, c_int, _P, _P, c_size_t, c_int, c_int, c_int, c_int, c_int, POINTER(c_int), _STREAM]),
     "arseg_psp_prior_sum_fwd": (c_int, [_P, _P, c_int, c_int, c_int, c_int, c_int, POINTER(c_int), _STREAM]),
+    "arseg_psp_pool_matrix16_workspace_bytes": (c_size_t, [c_int, c_int, c_int, c_int, c_int, POINTER(c_int)]),
+    "arseg_psp_pool_matrix16_fwd": (c_int, [_P, c_int, _P, c_int, _P, c_size_t, c_int, c_int, c_int, c_int, c_int, POINTER(c_int), _STREAM]),
+    "arseg_psp_prior_sum16_fwd": (c_int, [_P, _P, c_int, c_int, c_int, c_int, c_int, c_int, POINTER(c_int), _STREAM]),
     "arseg_global_reduce_fwd": (c_int, [_P, c_int, _P, c_int, c_int, c_int, c_int, c_int, _STREAM]),
     "arseg_global_reduce_workspace_bytes": (c_size_t, [c_int, c_int, c_int, c_int]),
     "arseg_global_reduce_ws_fwd": (c_int, [_P, c_int, _P, _P, c_size_t, c_int, c_int, c_int, c_int, c_int, _STREAM]),

@@ -259,7 +259,12 @@ __global__ __launch_bounds__(256) void conv16_kernel(const Conv16Params p) {
 // (BN x 64 halves) streams per tap, requested two taps ahead (two register stages + LDS double buffer).  The implicit-GEMM kernel
 // above re-fetches the activation slice of every tap from L2 and has 16 MFMAs per wave between barriers; here the activations are
 // read from L2 once instead of nine times.  D[pixel][co] (A = pixels, B = weights), C/D layout: co = lane & 31.
-template <bool BF, int BN, int WM>      // WM wave rows of 64 output pixels each: BM = 64*WM pixels, 2*WM waves
+//
+// UP2: the conv input is the x2 bilinear (align_corners=False) upsample of `p.in` [N, H/2, W/2, in_ld] (PSPUpsample, model/pspnet.py:43-46),
+// never materialised.  Per chunk the low-resolution window of the tile ((TH/2+2) x (TW/2+2) pixels, a quarter of the patch's bytes) is
+// fetched into registers, stored to LDS, and every patch pixel is interpolated from it with resize16_kernel's source-index helper, fp32
+// expression and single rounding (layers16.hip), so the staged values -- and the conv -- equal resize16 -> conv2d16 bit for bit.  Dilation 1.
+template <bool BF, int BN, int WM, bool UP2>      // WM wave rows of 64 output pixels each: BM = 64*WM pixels, 2*WM waves
 __global__ __launch_bounds__(128 * WM, (BN == 64 ? 4 : 2)) void conv16_patch_kernel(const Conv16Params p) {
     constexpr int ROWB = 144;                          // bytes per LDS row: 64 halves + pad (conflict-free b128 reads)
     constexpr int NT = 128 * WM, BM = 64 * WM;
@@ -270,6 +275,9 @@ __global__ __launch_bounds__(128 * WM, (BN == 64 ? 4 : 2)) void conv16_patch_ker
     const int TH = BM >> log2TW, d = p.dil, PW = TW + 2 * d, PH = TH + 2 * d, npx = PW * PH;
     unsigned char *Ps = smem;                                                  // [npx][ROWB]
     unsigned char *Bs = Ps + ((npx * ROWB + 255) & ~255);                        // [2][BN][ROWB]
+    constexpr int MAXW = UP2 ? (WM == 2 ? 4 : 3) : 1;  // UP2: window items per thread: <= 102 / 136 low-resolution pixels
+    const int WWW = (TW >> 1) + 2, nwin = ((TH >> 1) + 2) * WWW;               // UP2: low-resolution window, WWW pixels per row
+    unsigned char *Ws = Bs + 2 * BN * ROWB;                                      // UP2: [nwin][ROWB]
 
     const int tiles_x = (p.Wo + TW - 1) >> log2TW, tiles_y = (p.Ho + TH - 1) / TH;
     const int nblk = p.tiles_m * p.tiles_co;
@@ -286,13 +294,29 @@ __global__ __launch_bounds__(128 * WM, (BN == 64 ? 4 : 2)) void conv16_patch_ker
     const __amdgpu_buffer_rsrc_t b_rsrc = __builtin_amdgcn_make_buffer_rsrc(const_cast<uint16_t *>(p.w), 0, (int)p.w_bytes, 0x00020000);
     const int tid = threadIdx.x;
 
-    unsigned poff[MAXI];                               // item i = (pixel i/8, piece i%8): global byte offset without the chunk term, or OOB
+    unsigned poff[UP2 ? 1 : MAXI];                     // item i = (pixel i/8, piece i%8): global byte offset without the chunk term, or OOB
+    if constexpr (!UP2) {
 #pragma unroll
-    for (int it = 0; it < MAXI; ++it) {
-        const int i = tid + it * NT, px = i >> 3, py = px / PW, pxx = px - py * PW;
-        const int gy = ty0 - d + py, gx = tx0 - d + pxx;
-        const bool ok = px < npx && (unsigned)gy < (unsigned)p.H && (unsigned)gx < (unsigned)p.W;
-        poff[it] = ok ? (unsigned)((((img * p.H + gy) * p.W + gx) * p.in_ld) * 2 + (i & 7) * 16) : OOB;
+        for (int it = 0; it < MAXI; ++it) {
+            const int i = tid + it * NT, px = i >> 3, py = px / PW, pxx = px - py * PW;
+            const int gy = ty0 - d + py, gx = tx0 - d + pxx;
+            const bool ok = px < npx && (unsigned)gy < (unsigned)p.H && (unsigned)gx < (unsigned)p.W;
+            poff[it] = ok ? (unsigned)((((img * p.H + gy) * p.W + gx) * p.in_ld) * 2 + (i & 7) * 16) : OOB;
+        }
+    }
+    // UP2: window item i = (low-resolution pixel i/8 of the window whose corner is (ty0/2 - 1, tx0/2 - 1), piece i%8).  ty0 and tx0 are even
+    // (TH, TW are), and the source rows of patch rows ty0-1 .. ty0+TH are ty0/2-1 .. ty0/2+TH/2 after clamping: the window holds every
+    // source pixel of the patch; its pixels outside the image load zeros and are never read.
+    const int h = p.H >> 1, w = p.W >> 1, wy0 = (ty0 >> 1) - 1, wx0 = (tx0 >> 1) - 1;
+    unsigned woffl[MAXW];
+    if constexpr (UP2) {
+#pragma unroll
+        for (int it = 0; it < MAXW; ++it) {
+            const int i = tid + it * NT, px = i >> 3, py = px / WWW, pxx = px - py * WWW;
+            const int gy = wy0 + py, gx = wx0 + pxx;
+            const bool ok = px < nwin && (unsigned)gy < (unsigned)h && (unsigned)gx < (unsigned)w;
+            woffl[it] = ok ? (unsigned)((((img * h + gy) * w + gx) * p.in_ld) * 2 + (i & 7) * 16) : OOB;
+        }
     }
     const int chunk = tid & 7, row0 = tid >> 3;
     unsigned woff[RB];
@@ -304,16 +328,58 @@ __global__ __launch_bounds__(128 * WM, (BN == 64 ? 4 : 2)) void conv16_patch_ker
     const int nchunk = p.Cin >> 6;
 
     struct BRegs { u32x4 v[RB]; };
-    u32x4 rp[MAXI];
+    u32x4 rp[UP2 ? MAXW : MAXI];
     auto load_patch = [&](int ck) {
+        if constexpr (UP2) {
 #pragma unroll
-        for (int it = 0; it < MAXI; ++it) rp[it] = __builtin_amdgcn_raw_buffer_load_b128(a_rsrc, poff[it] + (unsigned)(ck * 128), 0, 0);
+            for (int it = 0; it < MAXW; ++it) rp[it] = __builtin_amdgcn_raw_buffer_load_b128(a_rsrc, woffl[it] + (unsigned)(ck * 128), 0, 0);
+        } else {
+#pragma unroll
+            for (int it = 0; it < MAXI; ++it) rp[it] = __builtin_amdgcn_raw_buffer_load_b128(a_rsrc, poff[it] + (unsigned)(ck * 128), 0, 0);
+        }
     };
     auto store_patch = [&]() {
+        if constexpr (UP2) {
 #pragma unroll
-        for (int it = 0; it < MAXI; ++it) {
-            const int i = tid + it * NT, px = i >> 3;
-            if (px < npx) *reinterpret_cast<u32x4 *>(Ps + px * ROWB + (i & 7) * 16) = rp[it];
+            for (int it = 0; it < MAXW; ++it) {
+                const int i = tid + it * NT, px = i >> 3;
+                if (px < nwin) *reinterpret_cast<u32x4 *>(Ws + px * ROWB + (i & 7) * 16) = rp[it];
+            }
+            __syncthreads();                    // (uniform: every caller is) the window is complete
+            const float sy = arseg_resize_scale(h, p.H, false), sx = arseg_resize_scale(w, p.W, false);
+#pragma unroll 1
+            for (int it = 0; it < MAXI; ++it) {                             // (not unrolled: the hoisted LDS reads of 9 items spilled)
+                const int i = tid + it * NT, px = i >> 3, py = px / PW, pxx = px - py * PW, piece = i & 7;
+                if (px >= npx) continue;
+                const int gy = ty0 - 1 + py, gx = tx0 - 1 + pxx;
+                u32x4 o = {0u, 0u, 0u, 0u};                                   // conv padding outside the upsampled image
+                if ((unsigned)gy < (unsigned)p.H && (unsigned)gx < (unsigned)p.W) {
+                    // resize16_kernel (layers16.hip), bilinear, align_corners = 0: the same index helper, clamps, expression and rounding
+                    int y0, y1, x0, x1; float ly, lx;
+                    arseg_src_index(sy, gy, false, h, y0, y1, ly);
+                    arseg_src_index(sx, gx, false, w, x0, x1, lx);
+                    ly = fminf(fmaxf(ly, 0.f), 1.f); lx = fminf(fmaxf(lx, 0.f), 1.f);
+                    const unsigned char *r0 = Ws + ((y0 - wy0) * WWW - wx0) * ROWB + piece * 16, *r1 = Ws + ((y1 - wy0) * WWW - wx0) * ROWB + piece * 16;
+                    const u32x4 va = *reinterpret_cast<const u32x4 *>(r0 + x0 * ROWB), vb = *reinterpret_cast<const u32x4 *>(r0 + x1 * ROWB);
+                    const u32x4 vc = *reinterpret_cast<const u32x4 *>(r1 + x0 * ROWB), vd = *reinterpret_cast<const u32x4 *>(r1 + x1 * ROWB);
+                    uint16_t q[8];
+#pragma unroll
+                    for (int e = 0; e < 8; ++e) {
+                        const int sh = (e & 1) * 16;
+                        const float a = arseg_h2f<BF>((uint16_t)(va[e >> 1] >> sh)), b = arseg_h2f<BF>((uint16_t)(vb[e >> 1] >> sh));
+                        const float cc = arseg_h2f<BF>((uint16_t)(vc[e >> 1] >> sh)), dd = arseg_h2f<BF>((uint16_t)(vd[e >> 1] >> sh));
+                        q[e] = arseg_f2h<BF>((1.f - ly) * ((1.f - lx) * a + lx * b) + ly * ((1.f - lx) * cc + lx * dd));
+                    }
+                    o = u32x4{q[0] | ((unsigned)q[1] << 16), q[2] | ((unsigned)q[3] << 16), q[4] | ((unsigned)q[5] << 16), q[6] | ((unsigned)q[7] << 16)};
+                }
+                *reinterpret_cast<u32x4 *>(Ps + px * ROWB + piece * 16) = o;
+            }
+        } else {
+#pragma unroll
+            for (int it = 0; it < MAXI; ++it) {
+                const int i = tid + it * NT, px = i >> 3;
+                if (px < npx) *reinterpret_cast<u32x4 *>(Ps + px * ROWB + (i & 7) * 16) = rp[it];
+            }
         }
     };
     auto load_b = [&](int ck, int tap, BRegs &r) {
@@ -443,25 +509,30 @@ __global__ __launch_bounds__(128 * WM, (BN == 64 ? 4 : 2)) void conv16_patch_ker
     }
 }
 
-template <bool BF, int BN, int WM>
+template <bool BF, int BN, int WM, bool UP2>
 int launch_patch16(const Conv16Params &p, hipStream_t st) {
     const int th = 64 * WM / p.patch_tw, npx = (th + 2 * p.dil) * (p.patch_tw + 2 * p.dil);
-    const size_t stage = (size_t)((npx * 144 + 255) & ~255) + (size_t)2 * BN * 144, epi = (size_t)128 * (BN + 4) * 4;
+    const int nwin = UP2 ? (th / 2 + 2) * (p.patch_tw / 2 + 2) : 0;          // the low-resolution window (after the weight buffers)
+    const size_t stage = (size_t)((npx * 144 + 255) & ~255) + (size_t)2 * BN * 144 + (size_t)nwin * 144, epi = (size_t)128 * (BN + 4) * 4;
     const size_t smem = stage > epi ? stage : epi;
     static ArsegSmemAttr attr;
-    if (int e = arseg_allow_smem(attr, reinterpret_cast<const void *>(conv16_patch_kernel<BF, BN, WM>), smem)) return e;
-    hipLaunchKernelGGL((conv16_patch_kernel<BF, BN, WM>), dim3(p.tiles_m * p.tiles_co), dim3(128 * WM), smem, st, p);
+    if (int e = arseg_allow_smem(attr, reinterpret_cast<const void *>(conv16_patch_kernel<BF, BN, WM, UP2>), smem)) return e;
+    hipLaunchKernelGGL((conv16_patch_kernel<BF, BN, WM, UP2>), dim3(p.tiles_m * p.tiles_co), dim3(128 * WM), smem, st, p);
     return arseg_launch_status();
 }
-template <bool BF>
+template <bool BF, bool UP2>
 int launch_patch16_cfg(const Conv16Params &p, int cfg, hipStream_t st) {
     switch (cfg) {
-        case 5: return launch_patch16<BF, 64, 2>(p, st);
-        case 6: return launch_patch16<BF, 128, 2>(p, st);
-        case 7: case 10: case 11: return launch_patch16<BF, 64, 4>(p, st);
-        case 13: return launch_patch16<BF, 64, 2>(p, st);
-        default: return launch_patch16<BF, 128, 4>(p, st);      // 8, 12
+        case 5: return launch_patch16<BF, 64, 2, UP2>(p, st);
+        case 6: return launch_patch16<BF, 128, 2, UP2>(p, st);
+        case 7: case 10: case 11: return launch_patch16<BF, 64, 4, UP2>(p, st);
+        case 13: return launch_patch16<BF, 64, 2, UP2>(p, st);
+        default: return launch_patch16<BF, 128, 4, UP2>(p, st);      // 8, 12
     }
+}
+template <bool BF>
+int launch_patch16_any(const Conv16Params &p, int cfg, bool up2, hipStream_t st) {
+    return up2 ? launch_patch16_cfg<BF, true>(p, cfg, st) : launch_patch16_cfg<BF, false>(p, cfg, st);
 }
 
 // ------------------------------------------------------------------------------------------------------------------------------
@@ -653,7 +724,7 @@ bool conv16_wide(const arseg_conv_desc *d, long long M) {
 
 extern "C" size_t arseg_conv2d16_workspace_bytes(const arseg_conv_desc *d) {
     int Ho, Wo;
-    if (!d || arseg_conv_out_hw(d, &Ho, &Wo) != ARSEG_OK) return 0;
+    if (!d || d->upsample2x || arseg_conv_out_hw(d, &Ho, &Wo) != ARSEG_OK) return 0;          // (the fused-upsample plans have no split-K)
     const long long M = (long long)d->N * Ho * Wo;
     const int Kpad = (d->R * d->S * d->Cin + KPAD - 1) / KPAD * KPAD;
     const int ns = conv16_nsplit(d, M, Kpad, conv16_wide(d, M) ? 128 : 64);
@@ -673,7 +744,17 @@ extern "C" int arseg_conv2d16_fwd(const arseg_conv_desc *d, int dtype, const voi
     if (!ARSEG_ALIGNED16(in) || !ARSEG_ALIGNED16(w_packed16) || !ARSEG_ALIGNED16(out) || (residual && !ARSEG_ALIGNED16(residual))) return ARSEG_EINVAL;
     if (d->batch > 1) return ARSEG_EUNSUPPORTED;
     int Ho, Wo;
-    if (int e = arseg_conv_out_hw(d, &Ho, &Wo)) return e;
+    {
+        arseg_conv_desc d0 = *d;                 // (the fp32 plan check of arseg_conv_out_hw refuses upsample2x on plans that are not its own)
+        d0.upsample2x = 0;
+        if (int e = arseg_conv_out_hw(&d0, &Ho, &Wo)) return e;
+    }
+    // upsample2x: `in` is [N, H/2, W/2, in_ld]; only the patch-resident plans (5..8, 10..13; 0 = 7) stage its x2 upsample, for a 3x3 stride-1
+    // pad-1 conv with dil 1 on an even H x W.  Everything else is refused (a plan that ignored the flag would read the small tensor as H x W)
+    const bool up2 = d->upsample2x != 0;
+    if (up2 && ((d->H & 1) || (d->W & 1) || d->dil != 1 || d->R != 3 || d->S != 3 || d->stride != 1 || d->pad != 1 || (d->Cin & 63) ||
+                d->split_k > 1 || d->tile_cfg < 0 || (d->tile_cfg >= 1 && d->tile_cfg <= 4) || d->tile_cfg == 9))
+        return d->tile_cfg < 0 || d->tile_cfg > 13 ? ARSEG_EINVAL : ARSEG_EUNSUPPORTED;
     Conv16Params p;
     p.in = (const uint16_t *)in; p.w = (const uint16_t *)w_packed16; p.res = (const uint16_t *)residual; p.scale = scale; p.bias = bias;
     p.out = (uint16_t *)out;
@@ -685,11 +766,11 @@ extern "C" int arseg_conv2d16_fwd(const arseg_conv_desc *d, int dtype, const voi
     p.inv_S = 65536 / d->S + 1;
     if (d->R * d->S > 64) return ARSEG_EUNSUPPORTED;          // (the multiply-high filter-row decode is exact for taps < 64: up to 7 x 7 and 8 x 8)
     const long long M = (long long)d->N * Ho * Wo;
-    const size_t in_bytes = (size_t)d->N * d->H * d->W * d->in_ld * 2, w_bytes = (size_t)d->Cout * p.Kpad * 2;
+    const size_t in_bytes = (size_t)d->N * (up2 ? (d->H >> 1) * (d->W >> 1) : d->H * d->W) * d->in_ld * 2, w_bytes = (size_t)d->Cout * p.Kpad * 2;
     if (M >= (1ll << 31) || in_bytes >= (1ull << 31) || w_bytes >= (1ull << 31)) return ARSEG_EUNSUPPORTED;       // 32-bit buffer offsets
     p.M = (int)M; p.in_bytes = (unsigned)in_bytes; p.w_bytes = (unsigned)w_bytes;
     // tile_cfg: 0 auto; 1 / 2 = 64- / 128-channel tile with K step 32; 3 / 4 = the same with K step 64
-    const int cfg = d->tile_cfg;
+    const int cfg = up2 && d->tile_cfg == 0 ? 7 : d->tile_cfg;
     if (cfg < 0 || cfg > 13) return ARSEG_EINVAL;
     if (cfg == 9) {          // stem kernel: 7x7 stride-2 pad-3, NHWC8 -> 64 channels, no residual
         if (d->R != 7 || d->S != 7 || d->stride != 2 || d->pad != 3 || d->dil != 1 || d->Cin != 8 || d->Cout != 64 || residual || d->split_k > 1)
@@ -713,7 +794,7 @@ extern "C" int arseg_conv2d16_fwd(const arseg_conv_desc *d, int dtype, const voi
         p.tiles_co = arseg_cdiv(d->Cout, (cfg == 6 || cfg == 8 || cfg == 12) ? 128 : 64); p.tiles_px = 0;
         p.nsplit = 1; p.kt_per_split = 0; p.ws = nullptr;
         hipStream_t st = arseg_stream(stream);
-        return dtype == ARSEG_DT_BF16 ? launch_patch16_cfg<true>(p, cfg, st) : launch_patch16_cfg<false>(p, cfg, st);
+        return dtype == ARSEG_DT_BF16 ? launch_patch16_any<true>(p, cfg, up2, st) : launch_patch16_any<false>(p, cfg, up2, st);
     }
     p.patch_tw = 0; p.patch_l2tw = 0; p.tiles_m = 0;
     // 128-channel tiles when they still give every CU a few workgroups, K step 64 (half the barriers, 74 KB of LDS) for long K loops

@@ -191,6 +191,64 @@ __global__ __launch_bounds__(256) void psp_bins_kernel(const float *__restrict__
     }
 }
 
+// 16-bit twins (the storage path of model/pspnet.py): the same cells and bins, 16-bit input read 4 channels (8 bytes) per lane, fp32 cell sums in
+// the workspace, one rounding per element of the pooled matrix (zeros of the sibling blocks included).
+template <bool BF>
+__global__ __launch_bounds__(256) void psp_cells16_kernel(const uint16_t *__restrict__ in, int in_ld, float *__restrict__ cells, int H, int W, int C, PoolGrid g) {
+    __shared__ f32x4 red[16][17];
+    const int cell = blockIdx.x, cy = cell / g.nx, cx = cell - cy * g.nx, n = blockIdx.z;
+    const int y0 = g.ey[cy], y1 = g.ey[cy + 1], x0 = g.ex[cx], x1 = g.ex[cx + 1];
+    const int cv = threadIdx.x & 15, pl = threadIdx.x >> 4, c = blockIdx.y * 64 + cv * 4;
+    const int ww = x1 - x0, cnt = (y1 - y0) * ww;
+    f32x4 acc = {0.f, 0.f, 0.f, 0.f};
+    if (c < C)
+        for (int i = pl; i < cnt; i += 16) {
+            const int yy = y0 + i / ww, xx = x0 + i % ww;
+            const uint2 v = *reinterpret_cast<const uint2 *>(in + (((size_t)n * H + yy) * W + xx) * in_ld + c);
+            acc += f32x4{arseg_h2f<BF>((uint16_t)(v.x & 0xffffu)), arseg_h2f<BF>((uint16_t)(v.x >> 16)), arseg_h2f<BF>((uint16_t)(v.y & 0xffffu)),
+                         arseg_h2f<BF>((uint16_t)(v.y >> 16))};
+        }
+    red[pl][cv] = acc;
+    __syncthreads();
+#pragma unroll
+    for (int s = 8; s >= 1; s >>= 1) {
+        if (pl < s) red[pl][cv] += red[pl + s][cv];
+        __syncthreads();
+    }
+    if (pl == 0 && c < C) *reinterpret_cast<f32x4 *>(cells + ((size_t)n * g.ny * g.nx + cell) * C + c) = red[0][cv];
+}
+
+template <bool BF>
+__global__ __launch_bounds__(256) void psp_bins16_kernel(const float *__restrict__ cells, uint16_t *__restrict__ out, int H, int W, int C, PoolGrid g) {
+    const int row = blockIdx.x, n = blockIdx.y;
+    int lev = 0;
+    while (lev + 1 < g.nlev && row >= g.off[lev + 1]) ++lev;
+    const int s = g.size[lev], b = row - g.off[lev], by = b / s, bx = b - by * s;
+    const int y0 = (by * H) / s, y1 = ((by + 1) * H + s - 1) / s, x0 = (bx * W) / s, x1 = ((bx + 1) * W + s - 1) / s;
+    const float inv = 1.0f / (float)((y1 - y0) * (x1 - x0));
+    const float *cn = cells + (size_t)n * g.ny * g.nx * C;
+    uint16_t *o = out + ((size_t)n * g.rows + row) * ((size_t)g.nlev * C);
+    int cy0 = 0, cy1 = g.ny, cx0 = 0, cx1 = g.nx;
+    while (g.ey[cy0] < y0) ++cy0;
+    while (g.ey[cy1] > y1) --cy1;
+    while (g.ex[cx0] < x0) ++cx0;
+    while (g.ex[cx1] > x1) --cx1;
+    const int nc = (cy1 - cy0) * (cx1 - cx0), cw = cx1 - cx0;
+    for (int c = threadIdx.x * 4; c < C; c += 1024) {
+        f32x4 a0 = {0.f, 0.f, 0.f, 0.f}, a1 = a0, a2 = a0, a3 = a0;
+        auto cell = [&](int i) { return *reinterpret_cast<const f32x4 *>(cn + (size_t)((cy0 + i / cw) * g.nx + cx0 + i % cw) * C + c); };
+        int i = 0;
+        for (; i + 4 <= nc; i += 4) {
+            const f32x4 v0 = cell(i), v1 = cell(i + 1), v2 = cell(i + 2), v3 = cell(i + 3);
+            a0 += v0; a1 += v1; a2 += v2; a3 += v3;
+        }
+        for (; i < nc; ++i) a0 += cell(i);
+        const f32x4 acc = ((a0 + a1) + (a2 + a3)) * inv;
+        const uint2 v = {arseg_f2h<BF>(acc[0]) | ((unsigned)arseg_f2h<BF>(acc[1]) << 16), arseg_f2h<BF>(acc[2]) | ((unsigned)arseg_f2h<BF>(acc[3]) << 16)};
+        for (int j = 0; j < g.nlev; ++j) *reinterpret_cast<uint2 *>(o + (size_t)j * C + c) = j == lev ? v : uint2{0u, 0u};
+    }
+}
+
 // ------------------------------------------------------------------ resize
 __global__ __launch_bounds__(256) void resize_nhwc_kernel(const float *__restrict__ in, float *__restrict__ out, int N, int C,
                                                           int Hin, int Win, int Hout, int Wout, int mode, int align, int in_ld,
@@ -419,6 +477,45 @@ __global__ __launch_bounds__(256) void psp_prior_sum_px_kernel(const float *__re
             acc += (1.f - ly) * ((1.f - lx) * a + lx * b) + ly * ((1.f - lx) * cc + lx * d);
         }
         *reinterpret_cast<f32x4 *>(out + pix * C + c) = acc;
+    }
+}
+
+// 16-bit pyramid priors: psp_prior_sum_px_kernel with 16-bit maps (8 channels per thread), the same blend per level, the sum over levels in fp32,
+// one rounding at the store (the result is the residual of the bottleneck conv2d16, which applies the ReLU after the add).
+template <bool BF>
+__global__ __launch_bounds__(256) void psp_prior_sum16_kernel(const uint16_t *__restrict__ t, uint16_t *__restrict__ out, int N, int H, int W,
+                                                              int C, PriorSizes ps) {
+    const int c8n = C >> 3;
+    const long long total = (long long)N * H * W * c8n;
+    for (long long idx = (long long)blockIdx.x * blockDim.x + threadIdx.x; idx < total; idx += (long long)gridDim.x * blockDim.x) {
+        const int c = (int)(idx % c8n) * 8;
+        const long long pix = idx / c8n;
+        const int x = (int)(pix % W), y = (int)((pix / W) % H), n = (int)(pix / ((long long)W * H));
+        float acc[8] = {0.f, 0.f, 0.f, 0.f, 0.f, 0.f, 0.f, 0.f};
+        for (int s = 0; s < ps.n; ++s) {
+            const int sz = ps.size[s];
+            const uint16_t *base = t + ((size_t)n * ps.rows + ps.off[s]) * C + c;
+            int y0, y1, x0, x1; float ly, lx;
+            arseg_src_index(arseg_resize_scale(sz, H, false), y, false, sz, y0, y1, ly);
+            arseg_src_index(arseg_resize_scale(sz, W, false), x, false, sz, x0, x1, lx);
+            ly = fminf(fmaxf(ly, 0.f), 1.f); lx = fminf(fmaxf(lx, 0.f), 1.f);
+            const uint4 a = *reinterpret_cast<const uint4 *>(base + (size_t)(y0 * sz + x0) * C);
+            const uint4 b = *reinterpret_cast<const uint4 *>(base + (size_t)(y0 * sz + x1) * C);
+            const uint4 cc = *reinterpret_cast<const uint4 *>(base + (size_t)(y1 * sz + x0) * C);
+            const uint4 d = *reinterpret_cast<const uint4 *>(base + (size_t)(y1 * sz + x1) * C);
+            const unsigned av[4] = {a.x, a.y, a.z, a.w}, bv[4] = {b.x, b.y, b.z, b.w}, cv[4] = {cc.x, cc.y, cc.z, cc.w}, dv[4] = {d.x, d.y, d.z, d.w};
+#pragma unroll
+            for (int e = 0; e < 8; ++e) {
+                const int sh = (e & 1) * 16;
+                const float fa = arseg_h2f<BF>((uint16_t)(av[e >> 1] >> sh)), fb = arseg_h2f<BF>((uint16_t)(bv[e >> 1] >> sh));
+                const float fc = arseg_h2f<BF>((uint16_t)(cv[e >> 1] >> sh)), fd = arseg_h2f<BF>((uint16_t)(dv[e >> 1] >> sh));
+                acc[e] += (1.f - ly) * ((1.f - lx) * fa + lx * fb) + ly * ((1.f - lx) * fc + lx * fd);
+            }
+        }
+        unsigned o[4];
+#pragma unroll
+        for (int e = 0; e < 4; ++e) o[e] = arseg_f2h<BF>(acc[2 * e]) | ((unsigned)arseg_f2h<BF>(acc[2 * e + 1]) << 16);
+        *reinterpret_cast<uint4 *>(out + pix * C + c) = uint4{o[0], o[1], o[2], o[3]};
     }
 }
 
@@ -991,6 +1088,52 @@ extern "C" int arseg_psp_prior_sum_fwd(const float *t, float *out, int N, int H,
     else
         hipLaunchKernelGGL(psp_prior_sum_px_kernel, dim3(grid_for((long long)N * H * W * (C >> 2))), dim3(256), 0, arseg_stream(stream), t, out, N,
                            H, W, C, ps);
+    return arseg_launch_status();
+}
+
+extern "C" size_t arseg_psp_pool_matrix16_workspace_bytes(int N, int H, int W, int C, int n_sizes, const int *sizes) {
+    return arseg_psp_pool_matrix_workspace_bytes(N, H, W, C, n_sizes, sizes);
+}
+
+extern "C" int arseg_psp_pool_matrix16_fwd(const void *in, int in_ld, void *out, int dtype, void *workspace, size_t workspace_bytes, int N, int H,
+                                           int W, int C, int n_sizes, const int *sizes, arseg_stream_t stream) {
+    ARSEG_CHECK_PTR(in); ARSEG_CHECK_PTR(out); ARSEG_CHECK_PTR(workspace); ARSEG_CHECK_PTR(sizes);
+    ARSEG_CHECK_POS(N); ARSEG_CHECK_POS(H); ARSEG_CHECK_POS(W); ARSEG_CHECK_POS(C);
+    if (dtype != ARSEG_DT_F16 && dtype != ARSEG_DT_BF16) return ARSEG_EINVAL;
+    if ((C & 7) || (in_ld & 7) || in_ld < C || !ARSEG_ALIGNED16(in) || !ARSEG_ALIGNED16(out) || !ARSEG_ALIGNED16(workspace) || N > 65535) return ARSEG_EINVAL;
+    PoolGrid g;
+    if (int e = pool_grid(H, W, n_sizes, sizes, &g)) return e;
+    if (workspace_bytes < (size_t)N * g.ny * g.nx * C * sizeof(float)) return ARSEG_EWORKSPACE;
+    hipStream_t hs = arseg_stream(stream);
+    float *cells = reinterpret_cast<float *>(workspace);
+    const dim3 g1(g.ny * g.nx, arseg_cdiv(C, 64), N), g2(g.rows, N);
+    if (dtype == ARSEG_DT_BF16) {
+        hipLaunchKernelGGL(psp_cells16_kernel<true>, g1, dim3(256), 0, hs, (const uint16_t *)in, in_ld, cells, H, W, C, g);
+        hipLaunchKernelGGL(psp_bins16_kernel<true>, g2, dim3(256), 0, hs, cells, (uint16_t *)out, H, W, C, g);
+    } else {
+        hipLaunchKernelGGL(psp_cells16_kernel<false>, g1, dim3(256), 0, hs, (const uint16_t *)in, in_ld, cells, H, W, C, g);
+        hipLaunchKernelGGL(psp_bins16_kernel<false>, g2, dim3(256), 0, hs, cells, (uint16_t *)out, H, W, C, g);
+    }
+    return arseg_launch_status();
+}
+
+extern "C" int arseg_psp_prior_sum16_fwd(const void *t, void *out, int dtype, int N, int H, int W, int C, int n_sizes, const int *sizes,
+                                         arseg_stream_t stream) {
+    ARSEG_CHECK_PTR(t); ARSEG_CHECK_PTR(out); ARSEG_CHECK_PTR(sizes);
+    ARSEG_CHECK_POS(N); ARSEG_CHECK_POS(H); ARSEG_CHECK_POS(W); ARSEG_CHECK_POS(C);
+    if (dtype != ARSEG_DT_F16 && dtype != ARSEG_DT_BF16) return ARSEG_EINVAL;
+    if (n_sizes < 1 || n_sizes > 4 || (C & 7) || !ARSEG_ALIGNED16(t) || !ARSEG_ALIGNED16(out)) return ARSEG_EINVAL;
+    PriorSizes ps;
+    ps.n = n_sizes; ps.rows = 0;
+    for (int i = 0; i < 4; ++i) { ps.size[i] = 1; ps.off[i] = 0; }
+    for (int i = 0; i < n_sizes; ++i) {
+        if (sizes[i] <= 0) return ARSEG_EINVAL;
+        ps.size[i] = sizes[i]; ps.off[i] = ps.rows; ps.rows += sizes[i] * sizes[i];
+    }
+    const dim3 grid(grid_for((long long)N * H * W * (C >> 3)));
+    hipStream_t hs = arseg_stream(stream);
+    if (dtype == ARSEG_DT_BF16) hipLaunchKernelGGL(psp_prior_sum16_kernel<true>, grid, dim3(256), 0, hs, (const uint16_t *)t, (uint16_t *)out, N, H, W, C, ps);
+    else hipLaunchKernelGGL(psp_prior_sum16_kernel<false>, grid, dim3(256), 0, hs, (const uint16_t *)t, (uint16_t *)out, N, H, W, C, ps);
     return arseg_launch_status();
 }
 

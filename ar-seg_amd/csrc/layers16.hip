@@ -467,6 +467,61 @@ static int mean16_slices(int N, int HW, int C) {
     return S > maxS ? maxS : S;
 }
 
+// ------------------------------------------------------------------ max over (H, W) in the same two steps (the PSPNet auxiliary classifier input,
+// model/pspnet.py:92-93): the 16-bit values widen to fp32 exactly and the result narrows back exactly -- it is one of the inputs.  A NaN wins
+// (fmaxf would drop it): m = (f > m || f != f) ? f : m keeps the first NaN met, and no later value replaces it.
+__device__ __forceinline__ float max_nan(float m, float f) { return (f > m || f != f) ? f : m; }
+
+template <bool BF>
+__global__ __launch_bounds__(256) void global_max16_kernel(const uint16_t *__restrict__ in, int in_ld, float *__restrict__ part, int HW, int C, int S) {
+    __shared__ float red[8][32][8];
+    const int n = blockIdx.y, sl = blockIdx.z, cv = blockIdx.x * 32 + (threadIdx.x & 31), pl = threadIdx.x >> 5;
+    const int per = (HW + S - 1) / S, p0 = sl * per, p1 = min(p0 + per, HW);
+    float acc[8];
+#pragma unroll
+    for (int e = 0; e < 8; ++e) acc[e] = -INFINITY;
+    if (cv * 8 < C) {
+        const uint16_t *base = in + (size_t)n * HW * in_ld + cv * 8;
+        for (int px = p0 + pl; px < p1; px += 8) {
+            float f[8];
+            unpack8<BF>(ld8(base + (size_t)px * in_ld), f);
+#pragma unroll
+            for (int e = 0; e < 8; ++e) acc[e] = max_nan(acc[e], f[e]);
+        }
+    }
+#pragma unroll
+    for (int e = 0; e < 8; ++e) red[pl][threadIdx.x & 31][e] = acc[e];
+    __syncthreads();
+    if (pl == 0 && cv * 8 < C) {
+        float *o = part + ((size_t)n * S + sl) * C + cv * 8;
+#pragma unroll
+        for (int e = 0; e < 8; ++e) {
+            float t = -INFINITY;
+#pragma unroll
+            for (int k = 0; k < 8; ++k) t = max_nan(t, red[k][threadIdx.x & 31][e]);
+            o[e] = t;
+        }
+    }
+}
+template <bool BF>
+__global__ __launch_bounds__(256) void global_max_fin16_kernel(const float *__restrict__ part, uint16_t *__restrict__ out, int N, int C, int S) {
+    __shared__ float red[8][32];
+    const int i = blockIdx.x * 32 + (threadIdx.x & 31), k = threadIdx.x >> 5;
+    float t = -INFINITY;
+    if (i < N * C) {
+        const int n = i / C, c = i - n * C;
+        for (int s = k; s < S; s += 8) t = max_nan(t, part[((size_t)n * S + s) * C + c]);
+    }
+    red[k][threadIdx.x & 31] = t;
+    __syncthreads();
+    if (k == 0 && i < N * C) {
+        float a = -INFINITY;
+#pragma unroll
+        for (int j = 0; j < 8; ++j) a = max_nan(a, red[j][threadIdx.x]);
+        out[i] = arseg_f2h<BF>(a);
+    }
+}
+
 extern "C" size_t arseg_global_mean16_workspace_bytes(int N, int H, int W, int C) {
     if (N <= 0 || H <= 0 || W <= 0 || C <= 0) return 0;
     return (size_t)N * mean16_slices(N, H * W, C) * C * sizeof(float);
@@ -490,6 +545,28 @@ extern "C" int arseg_global_mean16_fwd(const void *in, int in_ld, void *out, int
         hipLaunchKernelGGL(global_sum16_kernel<false>, grid, dim3(256), 0, st, (const uint16_t *)in, in_ld, part, H * W, C, S);
         hipLaunchKernelGGL(global_mean_fin16_kernel<false>, dim3(gf), dim3(256), 0, st, part, (uint16_t *)out, N, C, S, inv);
     } else return ARSEG_EINVAL;
+    return arseg_launch_status();
+}
+
+// torch.amax(x, (2,3)) on 16-bit NHWC: the two-step reduction of arseg_global_mean16_fwd with max instead of sum (same slices, same workspace size)
+extern "C" int arseg_global_max16_fwd(const void *in, int in_ld, void *out, int dtype, int N, int H, int W, int C, void *workspace,
+                                      size_t workspace_bytes, arseg_stream_t stream) {
+    ARSEG_CHECK_PTR(in); ARSEG_CHECK_PTR(out); ARSEG_CHECK_POS(N); ARSEG_CHECK_POS(H); ARSEG_CHECK_POS(W); ARSEG_CHECK_POS(C);
+    if ((C & 7) || (in_ld & 7) || in_ld < C || !ARSEG_ALIGNED16(in) || N > 65535) return ARSEG_EINVAL;
+    if (dtype != ARSEG_DT_F16 && dtype != ARSEG_DT_BF16) return ARSEG_EINVAL;
+    const int S = mean16_slices(N, H * W, C);
+    if (!workspace || workspace_bytes < (size_t)N * S * C * sizeof(float)) return ARSEG_EWORKSPACE;
+    const dim3 grid(arseg_cdiv(C, 256), N, S);
+    float *part = (float *)workspace;
+    const int gf = arseg_cdiv((long long)N * C, 32);
+    hipStream_t st = arseg_stream(stream);
+    if (dtype == ARSEG_DT_BF16) {
+        hipLaunchKernelGGL(global_max16_kernel<true>, grid, dim3(256), 0, st, (const uint16_t *)in, in_ld, part, H * W, C, S);
+        hipLaunchKernelGGL(global_max_fin16_kernel<true>, dim3(gf), dim3(256), 0, st, part, (uint16_t *)out, N, C, S);
+    } else {
+        hipLaunchKernelGGL(global_max16_kernel<false>, grid, dim3(256), 0, st, (const uint16_t *)in, in_ld, part, H * W, C, S);
+        hipLaunchKernelGGL(global_max_fin16_kernel<false>, dim3(gf), dim3(256), 0, st, part, (uint16_t *)out, N, C, S);
+    }
     return arseg_launch_status();
 }
 

@@ -31,7 +31,8 @@ class HipModule(nn.Module):
         if dtype not in (torch.float32, torch.float16, torch.bfloat16):
             raise _lib.ArsegError(f"unsupported storage dtype {dtype}")
         if dtype != torch.float32 and not self.SUPPORTS_16BIT:
-            raise _lib.ArsegError(f"{type(self).__name__} has no 16-bit storage path (only the BiSeNet family does); use torch.float32")
+            raise _lib.ArsegError(f"{type(self).__name__} has no 16-bit storage path (only the BiSeNet and CamVid PSPNet families "
+                                  "have one); use torch.float32")
         self.storage_dtype = dtype
         return self
 

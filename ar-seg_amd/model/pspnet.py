@@ -4,6 +4,10 @@ Same class names, constructor keywords, ``forward`` / ``forward_phase1`` / ``for
 signatures and ``state_dict`` keys.  Tensors at the interface are logical NCHW; outputs produced
 here are physically NHWC (``torch.channels_last`` strides), which every entry point also accepts,
 so ``ref_p`` flows HR net -> warpFeature -> forward_phase2 without layout copies.
+
+``set_storage(torch.bfloat16 | torch.float16)`` runs the backbone, pyramid and up-sampling convs on the 16-bit storage path (as BiSeNet does):
+log-probs and the auxiliary logits are fp32, ``p`` of ``forward`` / ``forward_phase1`` is in the storage dtype, ``p`` of phase 2 is fp32
+(the CReFF stage computes in fp32).
 """
 from __future__ import annotations
 
@@ -49,6 +53,7 @@ class PSPModule(HipModule):
                 "feat": PackedConv(w_feat, self.bottleneck.bias, None, act=_lib.ACT_RELU, device=device)}
 
     def forward_nhwc(self, feats):
+        # 16-bit feats: pool matrix, prior conv, prior sum and bottleneck all on the 16-bit path (the gemm_x3 fold is fp32 only)
         pk = self.packed()
         N, h, w, C = feats.shape
         rows = sum(s * s for s in self.sizes)
@@ -77,12 +82,15 @@ class PSPUpsample(HipModule):
 
     def forward_nhwc(self, x, out_split=False):
         # x2 bilinear upsample (F.upsample default) + conv + BN + PReLU.  out_split: the only consumer is another PSPUpsample -- on the split-row
-        # route (x is an ops.SplitRows) the result is written as split rows too; otherwise the flag is ignored
+        # route (x is an ops.SplitRows) the result is written as split rows too; otherwise the flag is ignored (16-bit: always).  16-bit x: the
+        # patch-resident conv interpolates while it stages, or resize16 + conv2d16, whichever the plan cache timed faster for the shape
         return ops.conv2d(x, self.packed(), up2=True, out_split=out_split)
 
 
 class _PSPBase(HipModule):
     """Everything PSPNet and PSPNetWithFuse share (the reference duplicates the code)."""
+
+    SUPPORTS_16BIT = True
 
     def _build(self, input_channel, n_classes, sizes, psp_size, deep_features_size, backend, pretrained):
         self.feats = getattr(extractors, backend)(pretrained, input_channel=input_channel)
@@ -104,7 +112,7 @@ class _PSPBase(HipModule):
     def _trunk_nhwc(self, x):
         """NCHW frame -> (aux logits [N,n_cls], p NHWC [N,H',W',64])."""
         N, C, H, W = x.shape
-        return self.phase1_nhwc4(ops.frame_to_nhwc4(x, H, W))
+        return self.phase1_nhwc4(ops.frame_ingest(x, H, W, self.storage_dtype))
 
     def phase1_nhwc4(self, x4, aux=True):
         """The backbone on an NHWC4 frame (pspnet.py:198-217): -> (aux logits [N,n_cls], p NHWC).  ``aux=False`` (the build's fast paths, which
@@ -118,7 +126,8 @@ class _PSPBase(HipModule):
         if not aux:
             return None, p
         pk = self.packed()
-        aux = ops.global_reduce(class_f, _lib.REDUCE_MAX)
+        # (16-bit: the max is one of the inputs, so its fp32 cast is exact; the two tiny classifier layers then run in fp32 -> fp32 logits)
+        aux = ops.cast(ops.global_reduce(class_f, _lib.REDUCE_MAX), torch.float32)
         aux = ops.conv2d(ops.conv2d(aux, pk["cls0"]), pk["cls2"])
         return aux.reshape(N, -1), p
 
@@ -141,7 +150,7 @@ class _PSPBase(HipModule):
         -> (log-probs NCHW, p NHWC).  Same arithmetic as ``forward``; the training-only auxiliary classifier output is not evaluated."""
         self._check_inference()
         N, C, H, W = x.shape
-        _, p = self.phase1_nhwc4(ops.frame_to_nhwc4(x, H, W), aux=False)
+        _, p = self.phase1_nhwc4(ops.frame_ingest(x, H, W, self.storage_dtype), aux=False)
         return self._final(p, H, W), p
 
 
@@ -193,13 +202,30 @@ class PSPNetWithFuse(_PSPBase):
 
     def phase2_warp(self, p_nhwc, refs_nhwc, mv_q):
         """Phase 2 with the MV warp fused in (fast path): LR feature NHWC, un-warped keyframe features NHWC [Hp,Wp,C] (one per
-        frame), int16 MVs -> (log-probs NCHW, p C8)."""
+        frame), int16 MVs -> (log-probs NCHW, p C8).
+
+        16-bit features at C = 64 with a 7 x 7 window: each distinct keyframe feature of THIS call (the frames of a GOP batch share one) and the
+        LR feature are cast to fp32 once and the fp32 fused warp + CReFF + head kernel runs -- the 16-bit route (ops.creff_warp) writes an fp32
+        C8 copy of the warped keyframe feature per frame and reads it back (measured slower).  The cast is per call: the batched
+        path (alter_res_batch_fast, GopRunner.run_batched) casts the keyframe feature once per GOP, the per-frame path once per frame.
+        Other shapes take the 16-bit route."""
         hd = self.packed()["head"]
-        p_c8, out = self.fuse_attention.fuse_warp(refs_nhwc, mv_q, p_nhwc, head=(hd.wf, hd.bf), log_softmax=True)
+        fa = self.fuse_attention
+        if ops.is16(p_nhwc) and p_nhwc.shape[3] == 64 and fa.kH == 7 and fa.kW == 7:
+            cast = {}
+            for r in refs_nhwc:
+                k = (r.data_ptr(), tuple(r.shape), tuple(r.stride()))
+                if k not in cast:
+                    cast[k] = ops.cast(r, torch.float32)
+            refs_nhwc = [cast[(r.data_ptr(), tuple(r.shape), tuple(r.stride()))] for r in refs_nhwc]
+            p_nhwc = ops.cast(p_nhwc, torch.float32)
+        p_c8, out = fa.fuse_warp(refs_nhwc, mv_q, p_nhwc, head=(hd.wf, hd.bf), log_softmax=True)
         return out, p_c8
 
     def forward_phase2(self, p, ref_p):
         self._check_inference()
+        if ops.is16(p) or ops.is16(ref_p):      # 16-bit storage through the NCHW interface: the CReFF stage itself is fp32
+            p, ref_p = ops.cast(p, torch.float32), ops.cast(ref_p, torch.float32)
         N, C, H, W = ref_p.shape
         ref_c8 = ops.to_c8(ops.to_nhwc(ref_p), _lib.NHWC) if ops.is_nhwc_view(ref_p) else ops.to_c8(ref_p, _lib.NCHW)
         out, p_c8 = self.phase2_c8(ops.to_nhwc(p), ref_c8)

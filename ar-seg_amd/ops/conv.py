@@ -357,13 +357,11 @@ def conv2d(x: torch.Tensor, pc, residual: Optional[torch.Tensor] = None, out: Op
     return out
 
 
-def _conv2d16(x, pc, residual, out, up2, tile_cfg=0, split_k=0):
-    """conv2d on the 16-bit storage path: one MFMA per product (arseg_conv2d16_fwd), fp32 epilogue (pc.scale / pc.bias)."""
-    dt = _need_gpu16(x, residual, out)
-    if up2:
-        n_, h_, w_, c_ = x.shape
-        x = resize_nhwc(x, 2 * h_, 2 * w_, _lib.BILINEAR, False)
+def _desc16(x, pc, residual, out, tile_cfg, split_k, up2=False):
+    """arseg_conv_desc of a 16-bit conv (up2: ``x`` is the half-resolution input) and its output tensor -> (desc, out, N, H, W, Ho, Wo)."""
     N, H, W, Cin = x.shape
+    if up2:
+        H, W = 2 * H, 2 * W
     w16, cin_pad = pc.weights16(x.dtype)
     if Cin != cin_pad:
         raise _lib.ArsegError(f"conv (16-bit) expects {cin_pad} input channels (padded to 8), got {Cin}")
@@ -374,10 +372,10 @@ def _conv2d16(x, pc, residual, out, up2, tile_cfg=0, split_k=0):
     d.act, d.prelu_slope = pc.act, pc.slope
     d.tile_cfg = tile_cfg
     d.out_ld, d.res_ld = pc.cout, pc.cout
-    lib = _lib.load()
     ho, wo = ctypes.c_int(), ctypes.c_int()
-    check(lib.arseg_conv_out_hw(ctypes.byref(d), ctypes.byref(ho), ctypes.byref(wo)), "conv_out_hw")
+    check(_lib.load().arseg_conv_out_hw(ctypes.byref(d), ctypes.byref(ho), ctypes.byref(wo)), "conv_out_hw")
     Ho, Wo = ho.value, wo.value
+    d.upsample2x = 1 if up2 else 0          # (set after the size query: arseg_conv_out_hw checks the fp32 engine's plans)
     cout_ld = (pc.cout + 7) // 8 * 8
     if out is None:
         out = torch.empty((N, Ho, Wo, cout_ld), dtype=x.dtype, device=x.device)[..., :pc.cout]
@@ -389,6 +387,75 @@ def _conv2d16(x, pc, residual, out, up2, tile_cfg=0, split_k=0):
             raise _lib.ArsegError("residual shape mismatch")
         d.res_ld = _nhwc_ld(residual)
     d.split_k = split_k
+    return d, out, N, H, W, Ho, Wo
+
+
+# arseg_conv2d16_fwd's patch-resident plans: the only ones that stage a x2 upsample of their input (upsample2x)
+_PATCH16_CFGS = (5, 6, 7, 8, 10, 11, 12, 13)
+
+
+def _up2_fusable(x_low, pc) -> bool:
+    return pc.R == 3 and pc.S == 3 and pc.stride == 1 and pc.pad == 1 and pc.dil == 1 and x_low.shape[3] % 64 == 0 and _nhwc_ld(x_low) % 8 == 0
+
+
+def _conv2d16_up2(x_low, pc, residual, out, tile_cfg, split_k):
+    """conv2d16 on the x2 bilinear (align_corners=False) upsample of ``x_low`` (PSPUpsample).  The fused form -- a patch plan that interpolates
+    while it stages (upsample2x) -- is timed against resize16 + conv2d16 once per shape and the winner kept.  tile_cfg 5..8 / 10..13 pins a
+    fused plan (ARSEG_EUNSUPPORTED raises if the map is too narrow for it); any other pinned plan, an explicit split_k and the shapes the fused
+    plans refuse take resize16 + conv2d16 with that plan, as before the fused form existed."""
+    dt = _need_gpu16(x_low, residual, out)
+    n_, h_, w_, _ = x_low.shape
+
+    def materialised(o=out, cfg=tile_cfg, sk=split_k):
+        return _conv2d16(resize_nhwc(x_low, 2 * h_, 2 * w_, _lib.BILINEAR, False), pc, residual, o, False, cfg, sk)
+
+    if split_k or (tile_cfg and tile_cfg not in _PATCH16_CFGS) or not _up2_fusable(x_low, pc):
+        return materialised()
+    lib = _lib.load()
+    d, out, N, H, W, Ho, Wo = _desc16(x_low, pc, residual, out, tile_cfg, 0, up2=True)
+    w16, _ = pc.weights16(x_low.dtype)
+
+    def args():
+        return (ctypes.byref(d), dt, _ptr(x_low), _ptr(w16), _ptr(pc.scale), _ptr(pc.bias), _ptr(residual), _ptr(out), None, 0, _stream())
+
+    if tile_cfg == 0 and sw.AUTOTUNE:
+        # the plan key of the materialised conv of the same shape plus an "up2" marker: keys without it keep their meaning
+        key = ("conv16", x_low.device.index, dt, N, H, W, x_low.shape[3], pc.cout, pc.R, pc.S, pc.stride, pc.pad, pc.dil, "up2")
+        plan = _conv_plans.get(key)
+        if plan is None:
+            plan, best_t = "resize", float("inf")
+            for cfg in _PATCH16_CFGS:
+                if cfg in (6, 8, 12) and pc.cout <= 64:
+                    continue
+                d.tile_cfg = cfg
+                try:
+                    t = _time(lambda: check(lib.arseg_conv2d16_fwd(*args()), "conv2d16"))
+                except _lib.ArsegError:
+                    continue
+                if t < best_t:
+                    plan, best_t = (cfg, 0), t
+            materialised(out)                                                  # (tunes the materialised conv's own plan first)
+            if _time(lambda: materialised(out)) < best_t:
+                plan = "resize"
+            _conv_plans[key] = plan
+        if plan == "resize" or not isinstance(plan, (tuple, list)):
+            return materialised(out)
+        d.tile_cfg = plan[0]
+    flops16 = 2 * N * Ho * Wo * pc.cout * pc.R * pc.S * pc.cin
+    with tagged((N, H, W, pc.cin, pc.cout, pc.R, pc.stride, pc.dil, True, "16-bit up2 " + str((d.tile_cfg, 0)), flops16)):
+        launch("conv2d", lib.arseg_conv2d16_fwd, *args(), flops=flops16)
+    return out
+
+
+def _conv2d16(x, pc, residual, out, up2, tile_cfg=0, split_k=0):
+    """conv2d on the 16-bit storage path: one MFMA per product (arseg_conv2d16_fwd), fp32 epilogue (pc.scale / pc.bias)."""
+    if up2:
+        return _conv2d16_up2(x, pc, residual, out, tile_cfg, split_k)
+    dt = _need_gpu16(x, residual, out)
+    d, out, N, H, W, Ho, Wo = _desc16(x, pc, residual, out, tile_cfg, split_k)
+    Cin = x.shape[3]
+    w16, cin_pad = pc.weights16(x.dtype)
+    lib = _lib.load()
 
     def args():
         nbytes = lib.arseg_conv2d16_workspace_bytes(ctypes.byref(d))

@@ -169,7 +169,10 @@ def adaptive_avgpool(x: torch.Tensor, oh: int, ow: int, out: Optional[torch.Tens
 
 def psp_pool_matrix(x: torch.Tensor, sizes) -> torch.Tensor:
     """The folded pyramid's block-structured pooled matrix [N, sum(s^2), 1, len(sizes)*C]: level i's adaptive average pool in columns
-    [i*C, (i+1)*C) of its s_i^2 rows, zeros elsewhere -- written entirely by the pooling launches (no fill)."""
+    [i*C, (i+1)*C) of its s_i^2 rows, zeros elsewhere -- written entirely by the pooling launches (no fill).
+    16-bit input: arseg_psp_pool_matrix16_fwd, the matrix in the storage dtype."""
+    if is16(x):
+        return _psp_pool_matrix16(x, sizes)
     _need_gpu(x)
     N, H, W, C = x.shape
     n, rows = len(sizes), sum(s * s for s in sizes)
@@ -189,8 +192,34 @@ def psp_pool_matrix(x: torch.Tensor, sizes) -> torch.Tensor:
     return out
 
 
+def _psp_pool_matrix16(x, sizes):
+    dt = _need_gpu16(x)
+    N, H, W, C = x.shape
+    n, rows = len(sizes), sum(s * s for s in sizes)
+    out = torch.empty((N, rows, 1, n * C), dtype=x.dtype, device=x.device)
+    lib = _lib.load()
+    arr = (ctypes.c_int * n)(*[int(s) for s in sizes])
+    nb = lib.arseg_psp_pool_matrix16_workspace_bytes(N, H, W, C, n, arr)
+    if not nb:
+        raise _lib.ArsegError(f"psp_pool_matrix (16-bit): pyramid sizes {tuple(sizes)} are not supported (at most 4 levels of size <= 6)")
+    ws = workspace(nb, x.device)
+    launch("adaptive_avgpool", lib.arseg_psp_pool_matrix16_fwd, _ptr(x), _nhwc_ld(x), _ptr(out), dt, _ptr(ws), nb, N, H, W, C, n, arr, _stream())
+    return out
+
+
 def psp_prior_sum(t: torch.Tensor, sizes, H: int, W: int) -> torch.Tensor:
-    """t [N, sum(s^2), C] (per-level maps after the folded 1x1 convs) -> [N,H,W,C] sum of bilinear upsamples."""
+    """t [N, sum(s^2), C] (per-level maps after the folded 1x1 convs) -> [N,H,W,C] sum of bilinear upsamples (16-bit t: in the storage dtype,
+    summed in fp32 and rounded once)."""
+    if is16(t):
+        dt = _need_gpu16(t)
+        t = t.contiguous()
+        N, rows, C = t.shape
+        if rows != sum(s * s for s in sizes):
+            raise _lib.ArsegError("psp_prior_sum: row count does not match the pyramid sizes")
+        out = torch.empty((N, H, W, C), dtype=t.dtype, device=t.device)
+        arr = (ctypes.c_int * len(sizes))(*[int(s) for s in sizes])
+        launch("psp_prior_sum", _lib.load().arseg_psp_prior_sum16_fwd, _ptr(t), _ptr(out), dt, N, H, W, C, len(sizes), arr, _stream())
+        return out
     _need_gpu(t)
     t = t.contiguous()
     N, rows, C = t.shape
@@ -206,13 +235,14 @@ def global_reduce(x: torch.Tensor, op: int) -> torch.Tensor:
     """NHWC -> [N,1,1,C] mean or max over (H,W)."""
     if is16(x):
         dt = _need_gpu16(x)
-        if op != _lib.REDUCE_MEAN:
-            raise _lib.ArsegError("16-bit path: only the mean reduction is built (BiSeNet ARM / FFM / conv_avg)")
+        if op not in (_lib.REDUCE_MEAN, _lib.REDUCE_MAX):
+            raise _lib.ArsegError(f"global_reduce: unknown op {op}")
         N, H, W, C = x.shape
         out = torch.empty((N, 1, 1, C), dtype=x.dtype, device=x.device)
         nb = _lib.load().arseg_global_mean16_workspace_bytes(N, H, W, C)
         ws = workspace(nb, x.device)
-        launch("global_reduce", _lib.load().arseg_global_mean16_fwd, _ptr(x), _nhwc_ld(x), _ptr(out), dt, N, H, W, C, _ptr(ws), nb, _stream())
+        fn = _lib.load().arseg_global_mean16_fwd if op == _lib.REDUCE_MEAN else _lib.load().arseg_global_max16_fwd
+        launch("global_reduce", fn, _ptr(x), _nhwc_ld(x), _ptr(out), dt, N, H, W, C, _ptr(ws), nb, _stream())
         return out
     _need_gpu(x)
     N, H, W, C = x.shape

@@ -199,9 +199,9 @@ typedef struct arseg_conv_desc {
     int math;          /* enum arseg_math: which MFMA back end evaluates the fp32 GEMM (selects the w_packed format too) */
     int upsample2x;    /* 1: `in` is the LOW-resolution tensor [N, H/2, W/2, in_ld] and the conv runs on its x2 bilinear
                           (align_corners=False) upsample, which is never materialised (PSPUpsample, model/pspnet.py:43-46): H, W stay
-                          the conv's input size, both even, dil == 1.  Patch-resident plans only (tile_cfg 13..16; the 16-bit conv
-                          ignores it); ARSEG_EUNSUPPORTED otherwise -- the Winograd route has its own fused form
-                          (arseg_wino43_input_fwd upsample2x). */
+                          the conv's input size, both even, dil == 1.  Patch-resident plans only (tile_cfg 13..16 here; 5..8 and
+                          10..13 of arseg_conv2d16_fwd, whose auto plan 0 is then 7); ARSEG_EUNSUPPORTED otherwise -- the Winograd
+                          route has its own fused form (arseg_wino43_input_fwd upsample2x). */
     void *range_flag;  /* ARSEG_MATH_F16X3 only, may be NULL: a caller-owned, 4-byte aligned device word.  Bit 0 is set (atomic OR, never
                           cleared by the library) when an activation this conv multiplies exceeds range_limit in magnitude, i.e. when
                           the hi/lo fp16 pair starts to lose bits (65504) or clamps (131008): the caller reads the word once per
@@ -428,6 +428,10 @@ int arseg_nhwc_to_nchw_fwd(const float *in, int in_ld, float *out, int N, int C,
  *                       layers of BiSeNet-18 --, >= 1 explicit; deterministic: fp32 partial sums in `workspace`
  *                       (arseg_conv2d16_workspace_bytes(desc) bytes, 0 without split-K), summed in slice order by a second kernel that
  *                       applies the epilogue; split-K needs Cout % 8 == 0, otherwise one slice.  batch unused)
+ *                       upsample2x = 1 (PSPUpsample): `in` is [N, H/2, W/2, in_ld], 3x3 stride-1 pad-1 dil-1, H and W even, Cin % 64 == 0,
+ *                       patch plans 5..8 / 10..13 only (tile_cfg 0 = 7); every other plan and shape -> ARSEG_EUNSUPPORTED.  The patch is
+ *                       interpolated from the low-resolution window while it is staged, with arseg_resize16_fwd's arithmetic and rounding:
+ *                       the result equals arseg_resize16_fwd(2h x 2w, BILINEAR, align_corners 0) -> arseg_conv2d16_fwd, same plan, bit for bit.
  * ------------------------------------------------------------------------------------------- */
 int arseg_packed_k16(int Cin_pad, int R, int S);
 int arseg_pack_conv_weight16_host(const float *w_oihw_host, int Cout, int Cin, int R, int S, int Cin_pad, int dtype, void *out_host);
@@ -446,6 +450,20 @@ int arseg_maxpool3x3s2_16_fwd(const void *in, void *out, int dtype, int N, int H
 size_t arseg_global_mean16_workspace_bytes(int N, int H, int W, int C);      /* fp32 partial sums of pixel slices */
 int arseg_global_mean16_fwd(const void *in, int in_ld, void *out, int dtype, int N, int H, int W, int C, void *workspace,
                             size_t workspace_bytes, arseg_stream_t stream);
+/* torch.amax(x,(2,3)) -> [N][C] in the storage dtype, exact (the result is one of the inputs; a NaN in a channel gives NaN); the workspace of
+ * arseg_global_mean16_workspace_bytes.  PSPNet's auxiliary classifier input (model/pspnet.py:92-93). */
+int arseg_global_max16_fwd(const void *in, int in_ld, void *out, int dtype, int N, int H, int W, int C, void *workspace,
+                           size_t workspace_bytes, arseg_stream_t stream);
+/* The folded PSP pyramid on the 16-bit path, twins of arseg_psp_pool_matrix_fwd / arseg_psp_prior_sum_fwd with the same limits and arithmetic:
+ *   pool_matrix16: 16-bit NHWC in -> [N][rows][n_sizes * C] in the storage dtype (fp32 cell sums in the workspace, one rounding per element,
+ *                  every element written, zeros included); workspace = arseg_psp_pool_matrix16_workspace_bytes (0: shape refused)
+ *   prior_sum16:   t [N][rows][C] 16-bit (the prior 1x1 conv's output) -> [N,H,W,C] 16-bit sum of the levels' bilinear (align_corners=False)
+ *                  upsamples, summed in fp32, rounded once (the residual of the bottleneck conv2d16, whose ReLU follows the add) */
+size_t arseg_psp_pool_matrix16_workspace_bytes(int N, int H, int W, int C, int n_sizes, const int *sizes);
+int arseg_psp_pool_matrix16_fwd(const void *in, int in_ld, void *out, int dtype, void *workspace, size_t workspace_bytes, int N, int H,
+                                int W, int C, int n_sizes, const int *sizes, arseg_stream_t stream);
+int arseg_psp_prior_sum16_fwd(const void *t, void *out, int dtype, int N, int H, int W, int C, int n_sizes, const int *sizes_host,
+                              arseg_stream_t stream);
 int arseg_resize16_fwd(const void *in, void *out, int dtype, int N, int C, int Hin, int Win, int Hout, int Wout, int mode,
                        int align_corners, int in_ld, int out_ld, arseg_stream_t stream);
 int arseg_scale_add16_fwd(const void *x, const void *scale, const void *add_full, const void *add_vec, void *out, int dtype, int N,
