@@ -1,7 +1,7 @@
 #!/usr/bin/env python3
 """bench.py -- AR-Seg LR-branch hot path on MI355X: non-keyframe frames/s on synthetic GOP-12 clips.
 
-    python bench.py --gpus N --steps K --warmup W
+    python bench.py --gpus N --steps K --warmup W [--full]
     (N > 1: python -m torch.distributed.run --nnodes=1 --nproc-per-node N ... bench.py --gpus N ...)
 
 Workload (BASELINE.json configs[1], the configuration the metric is quoted on): PSPNet-18, keyframe HR branch at
@@ -16,14 +16,20 @@ exactly K steps are enqueued and completed inside the timed region (`ms_per_step
 called a step).  All inputs (frames, int16 MV maps, weights) are resident in HBM before the timed region.  `value` counts the non-keyframes only, while
 the keyframe's HR forward (with the keyframe's own segmentation output) and the exchange are inside the timed region.  Not evaluated by default:
 the training-only auxiliary outputs that forward() / forward_phase1() return and evaluation.py:173-174,190-191 discard (PSPNet's aux classifier,
-BiSeNet's two aux heads with their x8 / x16 upsamples); `--reference-outputs` evaluates them too (printed as `value_reference_outputs` on the headline line).
+BiSeNet's two aux heads with their x8 / x16 upsamples); `--reference-outputs` evaluates them too (a `--full` run prints that rate as
+`value_reference_outputs` on the headline line).
 
 Arithmetic: fp32 tensors end to end.  The convolution GEMMs are evaluated on the fp16 matrix cores with every fp32 operand
 split into hi + lo fp16 (22 significant bits) and three MFMAs per product, fp32 accumulation (`--conv-math f16x3`, default;
 measured error vs an fp64 reference 1.5e-6 relative, the fp32 MFMA's is 2.3e-6 -- tests/test_gpu_ops.py); `--conv-math f32`
 runs them on v_mfma_f32_32x32x2_f32 instead.
 
-Extra objects on the JSON line: `roofline` (the dominant kernel of the rocprofv3 kernel stats = the fused MV-warp + CReFF kernel,
+A plain run does what the headline figure needs and no more: it sets up, warms up, times the K steps, writes --dump-outputs and prints the line
+(at N > 1 it also times the CReFF compute-unit reserve below, which decides `value`).  `--full` measures and checks everything else as well: the
+objects listed next, `peaks_measured`, `eager_launches`, the `variants` (other BASELINE shapes, precisions and conv arithmetic, with
+`value_strict_f32` and `value_reference_outputs` at the top level) and, at N > 1, `plans` and `exchange`; `--conv-layers` needs it.
+
+Extra objects on the JSON line under --full: `roofline` (the dominant kernel of the rocprofv3 kernel stats = the fused MV-warp + CReFF kernel,
 against the HBM roofline with the algorithmic bytes of SURVEY.md section 8d), `roofline_conv` (the conv family against the dense fp16
 MFMA peak, counted in the reference's direct-conv FLOPs), `cpu_baseline` (the oracle, i.e. a port, timed on the host cores for one
 non-keyframe of the same clip: 2 warm-up + 5 timed runs, median), `cpu_baseline_c1` (BASELINE configs[0]: PSPNet-18 HR 720x960 on the
@@ -90,7 +96,7 @@ PEAK_HBM_GBS = 8000.0              # MI355X_MICROARCH.md: HBM3E 8 TB/s (spec; ~6
 def measure_peaks(dev):
     """the on-box denominators beside the datasheet ones -- a stream copy (1 GiB, 16-byte accesses, best of 5 launches by
     HIP events: read + write bytes / time) and an MFMA issue loop (every wave of a full-chip launch issues independent v_mfma_f32_32x32x16_f16,
-    no memory traffic; best of 5).  A few milliseconds, once per bench run."""
+    no memory traffic; best of 5).  A few milliseconds, once per --full run."""
     import ctypes
 
     from arseg_amd import _lib
@@ -176,11 +182,15 @@ def main():
     ap.add_argument("--gpus", type=int, default=1)
     ap.add_argument("--steps", type=int, default=20)
     ap.add_argument("--warmup", type=int, default=3)
-    ap.add_argument("--no-cpu-baseline", action="store_true", help="skip the (slow) CPU oracle leg")
-    ap.add_argument("--no-profile", action="store_true", help="skip the per-kernel event pass")
-    ap.add_argument("--no-variants", action="store_true", help="skip the short runs of the other single-GPU BASELINE shapes (psp2k, bise_bf16, bise03_fp16)")
+    ap.add_argument("--full", action="store_true",
+                    help="also measure and check everything beyond the headline figure: the CPU baseline and parity legs, the per-kernel event pass "
+                         "(roofline objects), the on-box peaks, the eager-launch rate, the variant configs and, at N > 1, the comparison plans and "
+                         "the exchange diagnostics.  Default: set up, warm up, time --steps, print the line")
+    ap.add_argument("--no-cpu-baseline", action="store_true", help="--full: skip the (slow) CPU oracle leg")
+    ap.add_argument("--no-profile", action="store_true", help="--full: skip the per-kernel event pass")
+    ap.add_argument("--no-variants", action="store_true", help="--full: skip the short runs of the other single-GPU BASELINE shapes (psp2k, bise_bf16, bise03_fp16)")
     ap.add_argument("--variant-steps", type=int, default=2)
-    ap.add_argument("--conv-layers", metavar="FILE", help="also write the per-layer conv table (shape, plan, us, TFLOP/s, fraction of the MFMA peak) as JSON")
+    ap.add_argument("--conv-layers", metavar="FILE", help="--full: also write the per-layer conv table (shape, plan, us, TFLOP/s, fraction of the MFMA peak) as JSON")
     ap.add_argument("--config", choices=sorted(CONFIGS), default="psp", help="psp = the headline workload (BASELINE configs[1])")
     ap.add_argument("--gops-per-rank", type=int, default=1, help="GOPs per rank per step (experiment: a larger LR batch per launch sequence; 1 = one GOP-12 clip per GPU as BASELINE configs[1] says)")
     ap.add_argument("--plan", choices=["both", "exchange", "local", "neighbor"], default="both",
@@ -200,6 +210,8 @@ def main():
     args = ap.parse_args()
     if args.steps < 1:
         ap.error("--steps must be at least 1")
+    if args.conv_layers and not args.full:
+        ap.error("--conv-layers comes from the per-kernel event pass: it needs --full")
 
     # The contract is ONE JSON line on stdout.  Libraries write there too (RCCL prints a five-line version banner through C stdio when its first
     # communicator is created, and the buffered text comes out at exit -- after the JSON line, seen with ARSEG_RCCL_LOOPBACK=1): from here on file
@@ -235,8 +247,8 @@ def main():
         else:
             dist.init_process_group(backend, rank=rank, world_size=world)
 
-    result = run_config(args, args.config, args.steps, args.warmup, world, rank, dev, backend, full=True)
-    if rank == 0:
+    result = run_config(args, args.config, args.steps, args.warmup, world, rank, dev, backend, headline=True)
+    if rank == 0 and args.full:
         try:
             pk = measure_peaks(dev)
             result["peaks_measured"] = pk
@@ -250,20 +262,20 @@ def main():
         except Exception as exc:          # a measurement aid must never take the line down
             result["peaks_measured"] = {"error": repr(exc)}
     # ---- the other single-GPU BASELINE shapes, driver-timed in the same line (short runs)
-    if world == 1 and args.config == "psp" and not args.no_variants and not args.loopback:
+    if args.full and world == 1 and args.config == "psp" and not args.no_variants and not args.loopback:
         result["variants"] = {}
         for name in ("psp_f32", "psp_reference_outputs", "psp2k", "bise_bf16", "bise03_fp16", "semseg"):      # semseg = SURVEY 8f row 1 (Cityscapes PSPNet-18)
             try:
                 if name == "psp_f32":          # the headline workload with the reference's own arithmetic: fp32 MFMA
                     a32 = argparse.Namespace(**{**vars(args), "conv_math": "f32"})
-                    r = run_config(a32, "psp", args.variant_steps, 1, world, rank, dev, backend, full=False)
+                    r = run_config(a32, "psp", args.variant_steps, 1, world, rank, dev, backend, headline=False)
                 elif name == "psp_reference_outputs":      # the headline workload with the training-only auxiliary outputs evaluated as well
                     if args.reference_outputs:
                         continue
                     aro = argparse.Namespace(**{**vars(args), "reference_outputs": True})
-                    r = run_config(aro, "psp", args.variant_steps, 1, world, rank, dev, backend, full=False)
+                    r = run_config(aro, "psp", args.variant_steps, 1, world, rank, dev, backend, headline=False)
                 else:
-                    r = run_config(args, name, args.variant_steps, 1, world, rank, dev, backend, full=False)
+                    r = run_config(args, name, args.variant_steps, 1, world, rank, dev, backend, headline=False)
                 rc = r.get("roofline_conv", {})
                 result["variants"][name] = {
                     "workload": r["config"]["workload"], "value": r["value"], "unit": r["unit"], "dtype": r["dtype"], "steps": r["steps"],
@@ -299,11 +311,14 @@ def main():
             out.write(json.dumps(result) + "\n")
 
 
-def run_config(args, config, steps, warmup, world, rank, dev, backend, full):
-    """One bench line for `config`.  full = the headline form (CPU baseline, CPU parity at every size, minimum timed duration);
-    otherwise a short variant run (throughput, roofline objects, label agreement against one oracle pass)."""
+def run_config(args, config, steps, warmup, world, rank, dev, backend, headline):
+    """One bench line for `config`.  headline = exactly `steps` timed steps, the --dump-outputs files; under --full also the CPU baseline,
+    the eager-launch rate and, at N > 1, the comparison plans and exchange diagnostics.  Otherwise a short variant run (--full only:
+    throughput, roofline objects, label agreement against one oracle pass, minimum timed duration)."""
     from arseg_amd import _lib, evaluation as ev, ops, synth
     from arseg_amd.gop import GopRunner
+
+    extras = headline and args.full          # what only the headline line of a --full run measures beside its figure
 
     _lib.load()
     ops.set_conv_math(args.conv_math)
@@ -336,7 +351,7 @@ def run_config(args, config, steps, warmup, world, rank, dev, backend, full):
     runner = GopRunner(key_fn, nonkey_fn, n_gops=world * GPR, gop=GOP, loopback=getattr(args, "loopback", False))
     # (round 6) the contiguous-run deal: a rank's frames straddle ONE GOP boundary, one send / receive between ring neighbours instead of the all-gather
     runner_n = None
-    if world > 1 and full and args.plan in ("both", "neighbor"):
+    if world > 1 and extras and args.plan in ("both", "neighbor"):
         runner_n = GopRunner(key_fn, nonkey_fn, n_gops=world * GPR, gop=GOP, deal="neighbor")
     clips = {}
     needed = set(runner.my_gops) | {g for g, _ in runner.plan} | ({g for g, _ in runner_n.plan} if runner_n is not None else set())
@@ -370,7 +385,7 @@ def run_config(args, config, steps, warmup, world, rank, dev, backend, full):
     # SURVEY 8e's comparison line (N > 1): the zero-communication plan -- rank g keeps GOP g whole (its keyframe is the one it owns anyway), no
     # exchange.  Same kernels, same work per rank; timed after the mandated plan with the same K, reported beside it as plans.local
     step_local = None
-    if world > 1 and full and args.plan in ("both", "local"):
+    if world > 1 and extras and args.plan in ("both", "local"):
         runner_l = GopRunner(key_fn, nonkey_fn, n_gops=world * GPR, gop=GOP, local=True)
         fl = torch.cat([torch.from_numpy(clips[g]["frames"][d:d + 1]) for g, d in runner_l.plan]).to(dev)
         ml = torch.cat([torch.from_numpy(clips[g]["mv"][d:d + 1]) for g, d in runner_l.plan]).to(dev)
@@ -433,7 +448,7 @@ def run_config(args, config, steps, warmup, world, rank, dev, backend, full):
     run_steps(warmup)
     _log("timed region")
     elapsed, lane_outs = timed_region(steps)
-    if not full and elapsed < VARIANT_MIN_TIMED_S:
+    if not headline and elapsed < VARIANT_MIN_TIMED_S:
         # a variant's --variant-steps can be too short a window to trust: time a whole multiple of them instead; the multiple follows from the
         # max-over-ranks time, so every rank runs the same number of steps
         steps *= int(math.ceil(1.05 * VARIANT_MIN_TIMED_S / max(elapsed, 1e-6)))
@@ -442,9 +457,9 @@ def run_config(args, config, steps, warmup, world, rank, dev, backend, full):
     # compute unit on one GPU keeps its peers' RCCL kernels spinning on theirs.  Whether leaving a few compute units to the collective pays cannot
     # be measured on the 1-GPU boxes this was built on, so the first multi-GPU run decides it by measurement: the same K steps once more with
     # `creff_max_wgs` = CUs - 16, and the faster of the two IS the configuration (both are printed; the decision uses the max-over-ranks times,
-    # so every rank takes the same one)
+    # so every rank takes the same one; a plain run does this too: it decides `value`)
     reserve = None
-    if world > 1 and full and not fused_tail and ops.config.creff_max_wgs == 0:
+    if world > 1 and headline and not fused_tail and ops.config.creff_max_wgs == 0:
         cus = torch.cuda.get_device_properties(dev).multi_processor_count
         all_cus = {"creff_max_wgs": 0, "value": world * GPR * (GOP - 1) * L * steps / elapsed, "ms_per_step": 1e3 * elapsed / steps}
         ops.configure(creff_max_wgs=max(1, cus - 16))
@@ -458,7 +473,7 @@ def run_config(args, config, steps, warmup, world, rank, dev, backend, full):
         reserve = {"all_compute_units": all_cus, "sixteen_left_to_the_collective": res_cus, "chosen_creff_max_wgs": ops.config.creff_max_wgs,
                    "what": "the mandated exchange plan timed twice with the same K: the CReFF kernel on every compute unit / 16 compute units left free for the RCCL "
                            "kernels; `value` is the faster one"}
-    if full and args.dump_outputs:          # before any other pass: the graph lanes' outputs are static tensors that the next replay overwrites
+    if headline and args.dump_outputs:          # before any other pass: the graph lanes' outputs are static tensors that the next replay overwrites
         dump_outputs(args.dump_outputs, lane_outs, DUMP_BYTES // world, f"rank{rank}_" if world > 1 else "")
     outs = lane_outs[0]
     plans = None
@@ -479,7 +494,7 @@ def run_config(args, config, steps, warmup, world, rank, dev, backend, full):
                                      "sharded over two GPUs, ONE keyframe feature in and one out per rank and step (grouped send / receive between ring neighbours "
                                      "over one xGMI link) instead of the all-gather's world-1; bit-equal outputs"}
     exchange_stats = None
-    if multi and full and not fused_tail:
+    if multi and extras and not fused_tail:
         # self-diagnosing exchange: a few more steps with HIP events around the side-stream collective and around phase 1
         runner.enable_timing()
         run_steps(2)
@@ -495,7 +510,7 @@ def run_config(args, config, steps, warmup, world, rank, dev, backend, full):
     # N = 1 replays a captured HIP graph, N > 1 enqueues eagerly around the RCCL exchange: the eager rate of the same step at N = 1 is
     # timed as well, so that a multi-GPU number can be read against the right single-GPU one
     eager = None
-    if full and gop_graph is not None:
+    if extras and gop_graph is not None:
         g_keep, gop_graph = gop_graph, None
         run_steps(1)
         e_steps = max(1, int(math.ceil(0.5 / max(elapsed / steps, 1e-6))))
@@ -549,8 +564,9 @@ def run_config(args, config, steps, warmup, world, rank, dev, backend, full):
     result["range_guard"] = {"mode": ops.config.conv_range_guard, "tripped": bool(ops.range_tripped())}
 
     # ---- per-kernel timing with HIP events on the launch stream (one extra, instrumented step)
-    _log(f"{result['value']:.1f} frames/s; per-kernel event pass")
-    if rank == 0 and not args.no_profile:
+    _log(f"{result['value']:.1f} frames/s")
+    if rank == 0 and args.full and not args.no_profile:
+        _log("per-kernel event pass")
         g0, d0 = runner.plan[0]
         with torch.no_grad():
             ref_p = key_fn(keyframes[runner.my_gops[0]])
@@ -710,7 +726,7 @@ def run_config(args, config, steps, warmup, world, rank, dev, backend, full):
         }
         result["per_frame_ms"] = {"lr_frame_by_op": {k: v["ms"] / nb for k, v in sorted(nk.items())},
                                   "hr_keyframe_by_op": {k: v["ms"] for k, v in sorted(ky.items())}}
-        if args.conv_layers and full:
+        if args.conv_layers and headline:
             def table(rows, div):
                 for r in rows:
                     r["calls"] = r["calls"] / div
@@ -724,7 +740,7 @@ def run_config(args, config, steps, warmup, world, rank, dev, backend, full):
                            "lr": table(prof_nk.layers(), 3), "hr": table(prof_key.layers(), 1)}, f, indent=1)
 
     # ---- CPU baseline (rank 0, N=1 only): the oracle (a port) on one non-keyframe of the same clip; also the parity check
-    if rank == 0 and world == 1 and not args.no_cpu_baseline:
+    if rank == 0 and world == 1 and args.full and not args.no_cpu_baseline:
         import statistics
 
         _log("CPU oracle leg")
@@ -757,7 +773,7 @@ def run_config(args, config, steps, warmup, world, rank, dev, backend, full):
         # counts: `value` / `cores` = the fastest, `at_all_host_cores` = the os.cpu_count() figure.
         host_cores = os.cpu_count() or 1
         ncores = host_cores if "ARSEG_CPU_THREADS" not in os.environ else min(int(os.environ["ARSEG_CPU_THREADS"]), host_cores)
-        if not full:
+        if not headline:
             ncores = min(32, host_cores)          # a variant line's single oracle pass (parity figures only, never a baseline)
         torch.set_num_threads(ncores)
         cpu_ref.use_c_local_attention(ncores)
@@ -776,7 +792,7 @@ def run_config(args, config, steps, warmup, world, rank, dev, backend, full):
                 keep["r"] = cpu_ref.alter_res_step(cfg["kind"], sd_hr, sd_lr, img, key, cpu_ref.mv_from_int16(mvq), SCALE, ref_p=ref_cpu)
 
             reps = (1, 3) if cfg["H"] * cfg["W"] > 512 * 1024 else (2, 5)         # the 1024x2048 extras: a shorter sample
-            if not full:
+            if not headline:
                 reps = (0, 1)                                                     # a variant line: one oracle pass for the parity figures
             elif ncores > 64:
                 # every host core of a many-core box: torch's CPU ops oversubscribe badly there (r6, 256 threads of an EPYC 9575F: 28 s per frame against
@@ -785,7 +801,7 @@ def run_config(args, config, steps, warmup, world, rank, dev, backend, full):
             cpu_s, samples = timed(one_frame, *reps)
             o_out, o_p, _, _ = keep["r"]
         sweep = {ncores: cpu_s}
-        if full:
+        if headline:
             for nt in (16, 32, 64, 128):
                 if nt < host_cores and nt != ncores:
                     torch.set_num_threads(nt)
@@ -816,9 +832,9 @@ def run_config(args, config, steps, warmup, world, rank, dev, backend, full):
                                   "at_all_host_cores": {"cores": ncores, "seconds": sweep.get(ncores), "value": 1.0 / sweep[ncores] if sweep.get(ncores) else None},
                                   "seconds": cpu_s, "seconds_all": samples,
                                   "thread_sweep_seconds": {str(k): v for k, v in sorted(sweep.items())}}
-        if not full:
+        if not headline:
             del result["cpu_baseline"]          # (a single untimed-quality pass: not a baseline)
-        if cfg["kind"] == "psp" and full:
+        if cfg["kind"] == "psp" and headline:
             # BASELINE configs[0]: PSPNet-18 HR branch on one 720x960 CamVid-sized frame, PyTorch-CPU forward, no CReFF (evaluation.py --mode 1 0 0)
             frame_c1 = torch.from_numpy(synth.make_clip(0, 720, 960, gop=1, mean=mean, std=std)["frames"][0:1])
             with torch.no_grad():

@@ -1,7 +1,7 @@
 #!/bin/bash
 # Collects the round's evidence on the MI355X box (run from the repo root through gpurun):
 #   bash profiles/collect.sh <tag> [config]   -> gpurun_out/<tag>_*   (copy the summaries you keep into profiles/)
-# 1. bench.py with the CPU baseline (the JSON line)           2. rocprofv3 --kernel-trace --stats of the same command
+# 1. bench.py --full with the CPU baseline (the JSON line)    2. rocprofv3 --kernel-trace --stats of the same command
 # 3./4. rocprofv3 --pmc FETCH_SIZE and --pmc WRITE_SIZE in separate passes (no trace domains besides --kernel-trace)
 # 5. rocprofv3 --pmc SQ_VALU_MFMA_BUSY_CYCLES SQ_BUSY_CU_CYCLES SQ_INSTS_VALU_MFMA_MOPS_F16 GRBM_GUI_ACTIVE: matrix-core utilisation per kernel
 #    = MFMA busy cycles (summed over the SIMDs) / (128 SIMDs per XCD x GRBM_GUI_ACTIVE, which rocprofv3 reports summed over the 8 XCDs)
@@ -15,9 +15,9 @@ mkdir -p $OUT
 export ARSEG_CONV_PLAN_FILE=$OUT/${TAG}_plans.json
 rm -f $ARSEG_CONV_PLAN_FILE
 cd $R
-python bench.py --config $CFG --steps 9 --warmup 3 --conv-layers $OUT/${TAG}_conv_layers.json 2> $OUT/${TAG}_bench.err | tail -1 > $OUT/${TAG}_bench.json
+python bench.py --config $CFG --steps 9 --warmup 3 --full --conv-layers $OUT/${TAG}_conv_layers.json 2> $OUT/${TAG}_bench.err | tail -1 > $OUT/${TAG}_bench.json
 cd /tmp && export TMPDIR=/tmp
-BENCH="python $R/bench.py --config $CFG --steps 3 --warmup 2 --no-cpu-baseline --no-variants"
+BENCH="python $R/bench.py --config $CFG --steps 3 --warmup 2 --full --no-cpu-baseline --no-variants"
 rocprofv3 --kernel-trace --stats -d $OUT/${TAG}_stats -o s --output-format csv -- $BENCH > $OUT/${TAG}_bench_under_rocprof.json 2> /dev/null
 rocprofv3 --kernel-trace --pmc FETCH_SIZE -d $OUT/${TAG}_fetch -o f --output-format csv -- $BENCH --no-profile > /dev/null 2>&1
 rocprofv3 --kernel-trace --pmc WRITE_SIZE -d $OUT/${TAG}_write -o w --output-format csv -- $BENCH --no-profile > /dev/null 2>&1

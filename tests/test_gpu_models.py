@@ -743,7 +743,7 @@ def test_bench_multi_rank_path_end_to_end(dev, mode):
     """bench.py's N > 1 code path as the driver launches it, end to end, on the 1-GPU box: (rehearsal2) two ranks under torch.distributed.run that share
     the GPU and exchange over gloo (ARSEG_DIST_BACKEND=gloo) -- every rank-0-only block of the bench must be free of collectives, or this hangs: it
     did, in the in-step profile pass, until round 5 --; (rccl-loopback) one rank on RCCL with the collective issued (ARSEG_RCCL_LOOPBACK=1).  Both must end
-    with exactly ONE line on stdout, the JSON, carrying the exchange diagnostics (RCCL's banner used to land behind it)."""
+    with exactly ONE line on stdout, the JSON, carrying the exchange diagnostics (RCCL's banner used to land behind it; --full prints them)."""
     import json
     import socket
     import subprocess
@@ -760,10 +760,10 @@ def test_bench_multi_rank_path_end_to_end(dev, mode):
     if mode == "rehearsal2":
         env["ARSEG_DIST_BACKEND"] = "gloo"
         cmd = [sys.executable, "-m", "torch.distributed.run", "--nnodes=1", "--nproc-per-node", "2", "--master-addr", "127.0.0.1", "--master-port", str(port),
-               os.path.join(root, "bench.py"), "--gpus", "2", "--steps", "3", "--warmup", "2"]
+               os.path.join(root, "bench.py"), "--gpus", "2", "--steps", "3", "--warmup", "2", "--full"]
     else:
         env.update(ARSEG_RCCL_LOOPBACK="1", MASTER_ADDR="127.0.0.1", MASTER_PORT=str(port))
-        cmd = [sys.executable, os.path.join(root, "bench.py"), "--gpus", "1", "--steps", "6", "--warmup", "2", "--no-cpu-baseline"]
+        cmd = [sys.executable, os.path.join(root, "bench.py"), "--gpus", "1", "--steps", "6", "--warmup", "2", "--full", "--no-cpu-baseline"]
     r = subprocess.run(cmd, cwd=root, env=env, stdout=subprocess.PIPE, stderr=subprocess.PIPE, timeout=420, text=True)
     assert r.returncode == 0, r.stderr[-2000:]
     lines = [ln for ln in r.stdout.splitlines() if ln.strip()]
@@ -776,3 +776,35 @@ def test_bench_multi_rank_path_end_to_end(dev, mode):
         assert d["n_gpus"] == 2 and "rehearsal" in d and d["plans"]["local"]["value"] > 0 and "creff_compute_units" in d
     else:
         assert d["n_gpus"] == 1 and "rccl_loopback" in d and ex["backend"] == "nccl"
+
+
+def test_bench_plain_run_is_lean(dev, tmp_path):
+    """A plain `bench.py --gpus 1` run does what the headline figure needs and nothing else: set-up, warm-up, the timed steps, the
+    --dump-outputs files and one JSON line.  The CPU legs, the per-kernel event pass, the on-box peaks, the eager-launch rate and the
+    variant configs belong to --full; the 90 s bound on the time outside the steps is far above a lean run's and far below a --full one's."""
+    import json
+    import subprocess
+    import sys
+    import time
+
+    root = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
+    env = dict(os.environ)
+    for k in ("RANK", "LOCAL_RANK", "WORLD_SIZE", "ARSEG_RCCL_LOOPBACK", "ARSEG_DIST_BACKEND"):
+        env.pop(k, None)
+    steps, warmup = 2, 1
+    cmd = [sys.executable, os.path.join(root, "bench.py"), "--gpus", "1", "--steps", str(steps), "--warmup", str(warmup),
+           "--dump-outputs", str(tmp_path)]
+    t0 = time.perf_counter()
+    r = subprocess.run(cmd, cwd=root, env=env, stdout=subprocess.PIPE, stderr=subprocess.PIPE, timeout=300, text=True)
+    wall = time.perf_counter() - t0
+    assert r.returncode == 0, r.stderr[-2000:]
+    lines = [ln for ln in r.stdout.splitlines() if ln.strip()]
+    assert len(lines) == 1, r.stdout[-2000:]
+    d = json.loads(lines[0])
+    assert d["value"] > 0 and d["unit"] == "frames/s" and d["higher_is_better"] is True and d["dtype"] == "f32"
+    assert d["steps"] == steps and d["warmup"] == warmup and d["ms_per_step"] > 0 and d["metric"].startswith("non-keyframe frames/sec")
+    assert not {"cpu_baseline", "cpu_baseline_c1", "parity", "roofline", "roofline_conv", "per_frame_ms", "peaks_measured", "eager_launches",
+                "variants", "value_strict_f32", "value_reference_outputs"} & set(d), sorted(d)
+    lanes = {f"lane{i}.npy" for i in range(d["streams"])}
+    assert set(os.listdir(tmp_path)) - {"sample_index.npy"} == lanes, sorted(os.listdir(tmp_path))
+    assert wall - (steps + warmup) * d["ms_per_step"] * 1e-3 < 90, wall
