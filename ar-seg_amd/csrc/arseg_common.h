@@ -51,18 +51,6 @@ __device__ __forceinline__ uint16_t arseg_f2h(float x) {
     if constexpr (BF) return __builtin_bit_cast(uint16_t, (__bf16)x);
     else return __builtin_bit_cast(uint16_t, (_Float16)x);
 }
-// two values -> one packed dword (low half = a): one v_cvt_pk_bf16_f32 / v_cvt_pkrtz-free v_cvt_pk for fp16
-template <bool BF>
-__device__ __forceinline__ unsigned arseg_f2h_pair(float a, float b) {
-    typedef float f32x2_ __attribute__((ext_vector_type(2)));
-    if constexpr (BF) {
-        typedef __bf16 bf16x2_ __attribute__((ext_vector_type(2)));
-        return __builtin_bit_cast(unsigned, __builtin_convertvector(f32x2_{a, b}, bf16x2_));
-    } else {
-        typedef _Float16 h16x2_ __attribute__((ext_vector_type(2)));
-        return __builtin_bit_cast(unsigned, __builtin_convertvector(f32x2_{a, b}, h16x2_));
-    }
-}
 
 // fp32 -> two fp16: x = hi + lo with hi = fp16(x) rounded toward zero (11 significant bits) and lo = fp16(x - hi), 22 bits together.
 // lo is formed from the fp16 value actually stored (v_fma_mix_f32 reads the packed half directly), so

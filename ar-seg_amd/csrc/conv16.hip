@@ -14,12 +14,6 @@
 //   * epilogue through LDS: the fp32 accumulators are transposed into [pixel][co] rows so that scale / bias / residual / activation
 //     run on 8 consecutive channels and the store is a coalesced 16-byte vector of a full NHWC row.
 #include "arseg_common.h"
-#ifndef PATCH_ABL
-#define PATCH_ABL 0         // dev builds (tools/bench_patch16.py): 1 = no epilogue, 2 = one K step instead of nchunk * 9, 4 = fragments read once (no LDS reads in the loop)
-#endif
-#ifndef STEM_ABL
-#define STEM_ABL 0          // dev builds (tools/bench_stem16.py): 1 = no output stores, 2 = one K step instead of 25, 4 = the patch is loaded once
-#endif
 
 namespace {
 
@@ -408,7 +402,7 @@ __global__ __launch_bounds__(128 * WM, (BN == 64 ? 4 : 2)) void conv16_patch_ker
 #pragma unroll
             for (int r = 0; r < 16; ++r) acc[a][b][r] = 0.0f;
 
-    const int nsteps = (PATCH_ABL & 2) ? 1 : nchunk * 9;                     // K steps s = (chunk ck, tap): s = 9*ck + tap
+    const int nsteps = nchunk * 9;                     // K steps s = (chunk ck, tap): s = 9*ck + tap
     BRegs r0, r1;
     load_patch(0);
     load_b(0, 0, r0);
@@ -454,7 +448,6 @@ __global__ __launch_bounds__(128 * WM, (BN == 64 ? 4 : 2)) void conv16_patch_ker
         if (s_ + 1 < nsteps) step(s_ + 1, r0, r1);
     }
 
-    if ((PATCH_ABL & 1) && acc[0][0][0] != 12345.678f) return;
     // epilogue through LDS (the patch and the weight tiles are dead: the last step ended with a barrier): 128 pixels at a time the fp32
     // accumulators are laid out [pixel][co] so that scale / bias / residual / activation run on 8 consecutive channels and the store is a
     // 16-byte vector of an NHWC row.  C/D layout of the 32x32 MFMA: col = lane&31 (co), row = (r&3) + 8*(r>>2) + 4*(lane>>5) (pixel).
@@ -586,7 +579,7 @@ __global__ __launch_bounds__(256, 2) void conv16_stem_kernel(const Conv16Params 
         __syncthreads();                                      // the previous tile's patch is no longer read (and the weights are in place)
         patch_store();
         __syncthreads();
-        if (!(STEM_ABL & 4) && tile + (int)gridDim.x < ntiles) patch_load(tile + gridDim.x);
+        if (tile + (int)gridDim.x < ntiles) patch_load(tile + gridDim.x);
         f32x16 acc[2][2];                                     // [co tile][pixel row of the wave]
 #pragma unroll
         for (int a = 0; a < 2; ++a)
@@ -595,7 +588,7 @@ __global__ __launch_bounds__(256, 2) void conv16_stem_kernel(const Conv16Params 
 #pragma unroll
                 for (int e = 0; e < 16; ++e) acc[a][b][e] = 0.f;
 #pragma unroll 5
-        for (int j = 0; j < ((STEM_ABL & 2) ? 1 : 25); ++j) {
+        for (int j = 0; j < 25; ++j) {
             const int t = 2 * j + lh, tc = min(t, 48), r = (tc * 37) >> 8, sx = tc - 7 * r;      // tap (r, sx); t == 49 multiplies zero weights
             u32x4 a[2], b[2];
 #pragma unroll
@@ -608,7 +601,7 @@ __global__ __launch_bounds__(256, 2) void conv16_stem_kernel(const Conv16Params 
                 for (int k = 0; k < 2; ++k) acc[i][k] = mfma16<BF>(a[i], b[k], acc[i][k]);
         }
         // epilogue: lane = pixel (column li of output row 2*wave + k), accumulator rows = channels (r&3) + 8*(r>>2) + 4*lh (+32 i).
-        // (r6, tools/bench_stem16.py with -DSTEM_ABL: of 124 us per 11-frame batch the MFMA loop was 40 and this epilogue 59 -- its ARITHMETIC, not its
+        // (r6, measured with an ablation build: of 124 us per 11-frame batch the MFMA loop was 40 and this epilogue 59 -- its ARITHMETIC, not its
         // 8-byte stores: a software bf16 rounding (~8 VALU per value) and a four-way activation switch per value.  With v_cvt_pk_bf16_f32 and the
         // branch-free activation: 106-108 us.  Measured and not kept: the same rows laid out in LDS and stored as contiguous 16-byte pieces (108.4 against
         // 109-111 us: the stores were never the cost), barriers that leave the stores in flight (no change).)
@@ -616,7 +609,6 @@ __global__ __launch_bounds__(256, 2) void conv16_stem_kernel(const Conv16Params 
         for (int k = 0; k < 2; ++k) {
             const int oy = ty0 + 2 * wave + k, ox = tx0 + li;
             if (oy >= p.Ho || ox >= p.Wo) continue;
-            if ((STEM_ABL & 1) && acc[0][k][0] != 12345.678f) continue;
             uint16_t *dst = p.out + (((size_t)img * p.Ho + oy) * p.Wo + ox) * p.out_ld;
 #pragma unroll
             for (int i = 0; i < 2; ++i)

@@ -103,20 +103,8 @@ __device__ __forceinline__ void store4_buf(unsigned v, const u32x4 rsrc, unsigne
 }
 __device__ __forceinline__ unsigned lds_addr(const void *p) { return (unsigned)(size_t)(__attribute__((address_space(3))) const void *)p; }
 
-#ifdef MFMA_TIMING
-// dev builds only (tools/time_mfma.py): every wave adds the shader-clock ticks since its previous stamp to its row of a device-global table
-__device__ unsigned long long g_mfma_dbg[16 * 16];
-#define MF_STAMP(i) do { const unsigned long long now_ = __builtin_amdgcn_s_memtime(); tacc_[i] += now_ - tprev_; tprev_ = now_; } while (0)
-#else
-#define MF_STAMP(i) do { } while (0)
-#endif
-
 template <int NB, int TY>      // NB: classifier row blocks of 16 classes (0: no head)
 __global__ __launch_bounds__(64 * TY, 4) void creff_mfma_kernel(const CreffParams p) {
-#ifdef MFMA_TIMING
-    unsigned long long tacc_[15] = {};          // (wave uniform: scalar registers; flushed once per tile at the end of the kernel)
-    unsigned long long tprev_ = __builtin_amdgcn_s_memtime();
-#endif
     constexpr int NBA = NB > 0 ? NB : 1;
     typedef Geo<TY> GE;
     constexpr int NT = GE::NT, HBUF = GE::HBUF, RH = GE::RH, HH = GE::HH, LH = GE::LH, KPLK = GE::KPLK, KPLV = GE::KPLV, HPL = GE::HPL, LPL = GE::LPL;
@@ -249,7 +237,7 @@ __global__ __launch_bounds__(64 * TY, 4) void creff_mfma_kernel(const CreffParam
         // per-lane pointers live across both chunk loops, spills them and reloads them from scratch in every iteration (a vmcnt wait
         // that also waits for the LDS-DMA just issued)
         // (r5) the lr window is requested by the upper half of a 16-wave workgroup and the weights by waves 6 / 7: with everything on the lowest waves,
-        // wave 0 issued twice the requests of the mean wave and every barrier waited for it (tools/time_mfma.py)
+        // wave 0 issued twice the requests of the mean wave and every barrier waited for it
         constexpr int LW0 = NT == 1024 ? 512 : 0, WD0 = NT == 1024 ? 384 : 0;
         int tid = tid_ - LW0; asm volatile("" : "+v"(tid));
         const int wave_l = wave_u - LW0 / 64;
@@ -345,11 +333,8 @@ __global__ __launch_bounds__(64 * TY, 4) void creff_mfma_kernel(const CreffParam
     for (int k = 0; k < CB; ++k) {
         const int buf = k & 1;
         asm volatile("s_waitcnt vmcnt(0)" ::: "memory");      // this thread's share of chunk k has landed
-        MF_STAMP(0);
         __syncthreads();                         // ... everybody's has; everybody is done with the other buffers
-        MF_STAMP(1);
         issue(k + 1 < CB ? k + 1 : 0, buf ^ 1, k + 1 == CB);      // after the last chunk: chunk 0 again, for pass 2
-        MF_STAMP(2);
 #pragma unroll
         for (int it = 0; it < L_NI; ++it) {
             const int code = lrc_[it];
@@ -360,11 +345,8 @@ __global__ __launch_bounds__(64 * TY, 4) void creff_mfma_kernel(const CreffParam
                 Ls[gg * LPL + r * LWD + c] = v;
             }
         }
-        MF_STAMP(3);
         conv_kv(1, buf);
-        MF_STAMP(4);
         __syncthreads();
-        MF_STAMP(5);
         if (HBUF == 1) issue_hr(k + 1 < CB ? k + 1 : 0, 0);      // single hr buffer: free now that the key records are built
         // query conv, lane local: channels 4g..4g+3 of this lane's own pixel
         const f32x4 *w = Wd + (buf * 3 + 0) * 10 * G;
@@ -376,7 +358,6 @@ __global__ __launch_bounds__(64 * TY, 4) void creff_mfma_kernel(const CreffParam
         u32x2 qh, ql;
         split4(qv, qh, ql);
         const u32x6 q6 = pack6(qh, ql);
-        MF_STAMP(6);
         if (k + 1 == CB) load_head(0);
 #pragma unroll
         for (int b = 0; b < 8; ++b) {
@@ -385,7 +366,6 @@ __global__ __launch_bounds__(64 * TY, 4) void creff_mfma_kernel(const CreffParam
             S[b] = __builtin_amdgcn_mfma_f32_16x16x32_f16(a, op_b(q6), S[b], 0, 0, 0);
         }
         if (k + 1 == CB) commit_head(buf ^ 1);
-        MF_STAMP(7);
     }
 
     // ------------------------------------------------------------------ softmax over the 49 taps (padding taps included)
@@ -425,7 +405,6 @@ __global__ __launch_bounds__(64 * TY, 4) void creff_mfma_kernel(const CreffParam
         inv = 1.0f / z;                            // applied to the weighted sum instead of the 128 weights
     }
 
-    MF_STAMP(8);
     f32x4 lg[NBA];
 #pragma unroll
     for (int nb = 0; nb < NBA; ++nb) lg[nb] = f32x4{0.f, 0.f, 0.f, 0.f};
@@ -438,17 +417,13 @@ __global__ __launch_bounds__(64 * TY, 4) void creff_mfma_kernel(const CreffParam
     for (int k = 0; k < CB; ++k) {
         const int buf = (k + CB) & 1;            // continues the alternation of pass 1
         asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
-        MF_STAMP(9);
         __syncthreads();
-        MF_STAMP(10);
         if (k + 1 < CB) issue(k + 1, buf ^ 1, true);
         conv_kv(2, buf);
         int t2 = tid_; asm volatile("" : "+v"(t2));
         const int q2 = t2 & 15, g2 = (t2 >> 4) & 3, w2 = t2 >> 6, pc2 = w2 & 1, pr2 = w2 >> 1;
         const f32x4 lrc = lr_up(Lw + buf * LWCAP, 2 * pr2 + (q2 >> 3) + 1, 8 * pc2 + (q2 & 7) + 1, g2);      // residual term, channels 4g..4g+3 (table rows clamp into the image)
-        MF_STAMP(11);
         __syncthreads();
-        MF_STAMP(12);
         if (HBUF == 1 && k + 1 < CB) issue_hr(k + 1, 0);
         if (k + 1 < CB) load_head(k + 1);
         f32x4 acc = f32x4{0.f, 0.f, 0.f, 0.f};
@@ -479,7 +454,6 @@ __global__ __launch_bounds__(64 * TY, 4) void creff_mfma_kernel(const CreffParam
             }
         }
         if (k + 1 < CB) commit_head(buf ^ 1);
-        MF_STAMP(13);
     }
 
     // ------------------------------------------------------------------ logits: lg[nb][i] = class 16nb + 4g + i of query q
@@ -514,12 +488,6 @@ __global__ __launch_bounds__(64 * TY, 4) void creff_mfma_kernel(const CreffParam
                 store4_buf(__float_as_uint(lg[nb][i]), l_rsrc, (inq && cls < p.n_cls) ? off : OOB);
             }
     }
-    MF_STAMP(14);
-#ifdef MFMA_TIMING
-    if ((threadIdx.x & 63) == 0)
-        for (int i = 0; i < 15; ++i) atomicAdd(&g_mfma_dbg[16 * (threadIdx.x >> 6) + i], tacc_[i]);
-    if (threadIdx.x == 0) atomicAdd(&g_mfma_dbg[15], 1ull);
-#endif
 }
 
 template <int NB, int TY>
@@ -536,14 +504,6 @@ int launch(const CreffParams &p, hipStream_t st) {
 }
 
 }  // namespace
-
-#ifdef MFMA_TIMING
-extern "C" void arseg__mfma_dbg_read(unsigned long long *host, int reset) {
-    (void)hipDeviceSynchronize();
-    if (host) (void)hipMemcpyFromSymbol(host, HIP_SYMBOL(g_mfma_dbg), sizeof(unsigned long long) * 256);
-    if (reset) { static unsigned long long z[256]; (void)hipMemcpyToSymbol(HIP_SYMBOL(g_mfma_dbg), z, sizeof(z)); }
-}
-#endif
 
 int arseg_creff_mfma_launch(const CreffParams &p, hipStream_t st) {
     if (p.C & 15) return ARSEG_EUNSUPPORTED;

@@ -30,26 +30,6 @@
 //
 // Arithmetic contract: as creff.hip (zero-padded unfold: keys / values outside the image are 0 and still take softmax mass).
 #include "creff_params.h"
-#ifndef ROLL_PNT
-#define ROLL_PNT 2            // cache policy of the p / logits stores: 2 = nontemporal
-#endif
-#ifndef ROLL_LRTAB
-#define ROLL_LRTAB 0          // 1: the row taps of the lr_up rows come from a table the tap wave writes (measured slower: an LDS round trip in
-#endif                        // front of the lr loads, and the tap wave is the longest of H2)
-#ifndef ROLL_SPLIT6
-#define ROLL_SPLIT6 0          // 1: lo halves by v_fma_mixlo / mixhi_f16 (6 instead of 8 instructions per 4 values): measured 2 % SLOWER (5685 vs 5572 cycles per step)
-#endif
-#ifndef ROLL_LPRIO
-#define ROLL_LPRIO 0           // 1: raised issue priority while a producer wave requests its taps (and, for key/value waves, runs the value conv):
-#endif                         // zero-sum -- the producers' H1 drops 2600 -> 1900 cycles, the merge waves' rises 2380 -> 3280: a SIMD's H1 is issue-bound
-#ifndef ROLL_CPRIO
-#define ROLL_CPRIO 2          // issue priority of the consumer waves (producers: 0)
-#endif
-#ifndef ROLL_KSLOT5
-#define ROLL_KSLOT5 0         // 1: key ring row r lives in ring slot (5 r) & 7 instead of r & 7 (see kslot below): removes the bank conflicts of the key-block
-                              // reads across a window-row wrap -- measured (r6, same box, tools/ab_roll.sh): 0.1626-0.1627 vs 0.1617-0.1621 ms per frame,
-                              // i.e. 0.4 % SLOWER: those conflicts are not on the critical path of either half step
-#endif
 #include "warp_math.h"
 
 namespace {
@@ -65,6 +45,8 @@ constexpr int SW = 16;                               // query columns of a strip
 constexpr int RW = SW + 6;                           // key / value record columns (22)
 constexpr int GW = SW + 8;                           // warped keyframe columns (24): + 1 for the depthwise convs
 constexpr int LW = SW + 2;                           // lr_up columns (18)
+constexpr int PNT = 2;                               // cache policy of the p / logits stores: nontemporal
+constexpr int CPRIO = 2;                             // issue priority of the consumer waves (producers: 0)
 constexpr int KSLOT = 8, VSLOT = 8;                  // ring rows = the 8 rows under the windows of a row pair: key rows are written in H2 and read
                                                      // in H1, value rows written in H1 and read in H2 -- nobody reads a ring while it is written
 constexpr int KPL = KSLOT * RW;                      // key records per channel-group plane: 176, a multiple of 16 (ds_read_b128 of one key
@@ -85,8 +67,8 @@ constexpr int R_OFF = Q_OFF + 2 * 16 * 16 * 16;      // 120,832  residual record
 constexpr int XB_OFF = R_OFF + 2 * 16 * 16 * 16;     // 129,024  partials of the kh-1 waves [2 patches][4 chunks + {m, z}][64 lanes]
 constexpr int TW_OFF = XB_OFF + 2 * 5 * 64 * 16;     // 139,264  [48] {ex, wx, ey, wy} with the tap validity folded in
 constexpr int TO_OFF = TW_OFF + NGP * 16;            //          [48] byte offsets of the four (clamped) taps of a pixel: NW, NE, SW, SE
-constexpr int LR_OFF = TO_OFF + NGP * 16;            //          [2] lr taps of the two lr_up rows of an iteration {row 0 bytes, row 1 bytes, w0, w1}
-constexpr int WD_OFF = LR_OFF + 2 * 16;              //          depthwise weights [key | value | query][16 groups][9 taps + bias]
+constexpr int WD_OFF = TO_OFF + NGP * 16 + 2 * 16;   //          depthwise weights [key | value | query][16 groups][9 taps + bias]
+                                                     //          (32 bytes of padding in front: the offsets below stay as measured)
 constexpr int WF_OFF = WD_OFF + 3 * 160 * 16;        // 147,904  classifier records [4 chunks][4 groups][32] {4 hi | 4 lo}
 constexpr int BF_OFF = WF_OFF + 4 * 4 * 32 * 16;     // 156,096  classifier bias [32]
 constexpr int SC_OFF = BF_OFF + 32 * 4;              //          this workgroup's list of pieces (struct PieceTab)
@@ -96,13 +78,10 @@ constexpr int MAXN = 32;
 constexpr unsigned OOB = 0xFFFFFFF0u;
 constexpr float LOG2E = 1.44269504088896340736f;
 
-// Ring slot of key row r.  A consumer's ds_read_b128 of one key block takes 16 consecutive window keys e = 2b + q, which wrap from window
-// row b to row b + 1 at e = 14: with the rows in consecutive slots (pitch RW = 22 records) the lanes behind the wrap sit 22 - 14 = 8 records
-// = half a 256-byte bank row away from where a contiguous run would put them and collide with the lanes 8 records further on (2-way
-// conflicts on up to half of the lanes: profiles/r04_v1_pmc_creff_roll.json, SQ_LDS_BANK_CONFLICT = 26 % of the LDS-active cycles).  With
-// consecutive rows 5 slots apart (5 is coprime to 8: still a permutation of the ring) the wrap lands 5 * 22 - 14 = 96 = 0 mod 16 records
-// (or -3 * 22 - 14 = -80) further: the 16 lanes cover the 64 banks exactly once.
-__device__ __forceinline__ int kslot(int r) { return ROLL_KSLOT5 ? (5 * r) & 7 : r & 7; }
+// Ring slot of key row r.  A consumer's ds_read_b128 of one key block wraps from window row b to row b + 1 and conflicts 2-way on up to
+// half of its lanes (profiles/r04_v1_pmc_creff_roll.json).  Rows 5 slots apart remove those conflicts but measured 0.4 % slower (r6,
+// tools/ab_roll.sh): they are not on the critical path of either half step.
+__device__ __forceinline__ int kslot(int r) { return r & 7; }
 
 struct RollParams {
     const float *ref[MAXN];       // un-warped keyframe feature of each frame, NHWC [Hp][Wp][64]
@@ -112,30 +91,14 @@ struct RollParams {
     int N, Hp, Wp, hp, wp, H, W, n_cls, log_softmax, p_layout, nstrips, nseg, seg_rows, balanced;
     unsigned p_bytes, l_bytes, lr_bytes, ref_bytes;      // of ONE frame: every frame has its own buffer descriptor
     float sy, sx;
-    unsigned long long *dbg;
 };
 
-// fp32 -> two fp16 (x = hi + lo, 22 bits together; see arseg_split_f16) in 6 instructions per 4 values: the lo halves are written by
-// v_fma_mixlo / mixhi_f16 straight into their packed register (arseg_split_f16: fp32 differences + a packing convert, 8 instructions).
-// The lo half is rounded to nearest instead of toward zero; beyond |x| = 131008 it becomes Inf instead of clamping -- far outside the
-// features this kernel sees (the tile kernel measured this form 2 % slower; here the VALU issue count is what bounds a half step).
-__device__ __forceinline__ void split4(const f32x4 v, u32x2 &hi, u32x2 &lo) {
-#if ROLL_SPLIT6
-    unsigned h01, h23, l01, l23;
-    asm("v_cvt_pkrtz_f16_f32 %0, %4, %5\n\tv_cvt_pkrtz_f16_f32 %1, %6, %7\n\t"
-        "v_fma_mixlo_f16 %2, %0, -1.0, %4 op_sel_hi:[1,0,0]\n\tv_fma_mixhi_f16 %2, %0, -1.0, %5 op_sel:[1,0,0] op_sel_hi:[1,0,0]\n\t"
-        "v_fma_mixlo_f16 %3, %1, -1.0, %6 op_sel_hi:[1,0,0]\n\tv_fma_mixhi_f16 %3, %1, -1.0, %7 op_sel:[1,0,0] op_sel_hi:[1,0,0]"
-        : "=&v"(h01), "=&v"(h23), "=&v"(l01), "=&v"(l23) : "v"(v[0]), "v"(v[1]), "v"(v[2]), "v"(v[3]));
-#else
+// fp32 -> two fp16 in the record form {4 hi | 4 lo} (arseg_split_f16).  Writing the lo halves by v_fma_mixlo / mixhi_f16 (6 instead of
+// 8 instructions per 4 values) measured 2 % slower (5685 vs 5572 cycles per step).
+__device__ __forceinline__ u32x4 split4r(const f32x4 v) {
     unsigned h01, h23, l01, l23;
     arseg_split_f16(v, h01, h23, l01, l23);
-#endif
-    hi = u32x2{h01, h23}; lo = u32x2{l01, l23};
-}
-__device__ __forceinline__ u32x4 split4r(const f32x4 v) {      // the record form {4 hi | 4 lo}
-    u32x2 hi, lo;
-    split4(v, hi, lo);
-    return u32x4{hi.x, hi.y, lo.x, lo.y};
+    return u32x4{h01, h23, l01, l23};
 }
 __device__ __forceinline__ h16x8 pack8(const u32x2 a, const u32x2 b) { return __builtin_bit_cast(h16x8, u32x4{a.x, a.y, b.x, b.y}); }
 __device__ __forceinline__ u32x2 lds_tr16(const unsigned char *p) {
@@ -171,30 +134,13 @@ __device__ __forceinline__ double uniform_f64(double x) {
 // Workgroup barrier that orders LDS traffic only: global loads requested before it stay in flight across it (the gather of the next
 // row pair travels under the convolutions of this one).
 __device__ __forceinline__ void wg_sync() {
-#ifdef ROLL_FULLSYNC
-    __syncthreads();
-    return;
-#endif
     __builtin_amdgcn_fence(__ATOMIC_RELEASE, "workgroup", "local");
     __builtin_amdgcn_s_barrier();
     __builtin_amdgcn_fence(__ATOMIC_ACQUIRE, "workgroup", "local");
 }
 // 3 x 3 depthwise stencil on 4 channels, two output rows at once: rows r0..r3, each {left, centre, right}; out_a = rows r0..r2, out_b =
-// rows r1..r3; weights w[0..8] + bias w[9] read from LDS one tap at a time (accumulation order of creff_rr.hip / creff.hip)
-__device__ __forceinline__ void stencil2(const f32x4 *w, const f32x4 (&r0)[3], const f32x4 (&r1)[3], const f32x4 (&r2)[3],
-                                         const f32x4 (&r3)[3], f32x4 &oa, f32x4 &ob) {
-    f32x4 a = w[9], b = a;
-#pragma unroll
-    for (int j = 0; j < 3; ++j) { const f32x4 wj = w[j]; a = fma4(wj, r0[j], a); b = fma4(wj, r1[j], b); }
-#pragma unroll
-    for (int j = 0; j < 3; ++j) { const f32x4 wj = w[3 + j]; a = fma4(wj, r1[j], a); b = fma4(wj, r2[j], b); }
-#pragma unroll
-    for (int j = 0; j < 3; ++j) { const f32x4 wj = w[6 + j]; a = fma4(wj, r2[j], a); b = fma4(wj, r3[j], b); }
-    oa = a; ob = b;
-}
-
-// the same with the ten weight vectors already in registers (requested ahead of the barrier in front of the stencil: constants, so
-// their LDS round trip need not sit on the critical path of the half step that uses them)
+// rows r1..r3; weights w[0..8] + bias w[9] (accumulation order of creff_rr.hip / creff.hip), already in registers (requested ahead of the
+// barrier in front of the stencil: constants, so their LDS round trip need not sit on the critical path of the half step that uses them)
 __device__ __forceinline__ void stencil2r(const f32x4 (&w)[10], const f32x4 (&r0)[3], const f32x4 (&r1)[3], const f32x4 (&r2)[3],
                                           const f32x4 (&r3)[3], f32x4 &oa, f32x4 &ob) {
     f32x4 a = w[9], b = a;
@@ -222,31 +168,10 @@ __device__ __forceinline__ void stencil2h(const f32x4 (&wa)[5], const f32x4 *w, 
     oa = a; ob = b;
 }
 
-#ifdef ROLL_TIMING
-// dev builds only: every wave accumulates the shader-clock ticks of its four segments per iteration (H1 work, wait at barrier A, H2 work,
-// wait at barrier B) and adds them to dbg[8 * wave + i] when it is done (tools/time_roll.py)
-#define RT_DECL unsigned long long tacc_[4] = {0ull, 0ull, 0ull, 0ull}, tprev_ = __builtin_amdgcn_s_memtime(), nsteps_ = 0
-#define RT(i) do { const unsigned long long now_ = __builtin_amdgcn_s_memtime(); tacc_[i] += now_ - tprev_; tprev_ = now_; } while (0)
-#define RT_STEPS(n) nsteps_ += (n)
-#define RT_FLUSH() do { if ((tid & 63) == 0 && p.dbg) { for (int i_ = 0; i_ < 4; ++i_) atomicAdd(p.dbg + 8 * wave + i_, tacc_[i_]); \
-        atomicAdd(p.dbg + 8 * wave + 4, nsteps_); } } while (0)
-#elif defined(ROLL_MARK)
-// census builds only: comment markers in the listing at the segment boundaries (tools/roll_census.py --marks)
-#define RT_DECL do { } while (0)
-#define RT(i) asm volatile("; ROLLMARK " #i)
-#define RT_STEPS(n) do { } while (0)
-#define RT_FLUSH() do { } while (0)
-#else
-#define RT_DECL do { } while (0)
-#define RT(i) do { } while (0)
-#define RT_STEPS(n) do { } while (0)
-#define RT_FLUSH() do { } while (0)
-#endif
-
 struct Smem {
     u32x4 *Kr, *Vr, *Qr;
     f32x4 *Ws, *Ls, *Rr, *Xb, *TapW, *Wd, *Wfs;
-    u32x4 *TapO, *LrRow;
+    u32x4 *TapO;
     float *Bfs;
 };
 // This workgroup's pieces of work; a piece = `S` steps (row pairs) of one 16-column strip of one frame from row `ys` on, and costs S + 9
@@ -315,14 +240,12 @@ __device__ __forceinline__ void consumer(const RollParams &p, const Smem &sm, co
     f32x4 bias[NBA];                             // classifier bias of this lane's classes 16nb + 4g .. + 3 (-inf beyond n_cls: such a class
 #pragma unroll                                   // drops out of the log-softmax by itself)
     for (int nb = 0; nb < NBA; ++nb) bias[nb] = KH == 0 && NB > 0 ? *reinterpret_cast<const f32x4 *>(sm.Bfs + nb * 16 + 4 * g) : f32x4{0.f, 0.f, 0.f, 0.f};
-    RT_DECL;
     const int npieces = __builtin_amdgcn_readfirstlane(sc->count);
     for (int piece = 0; piece < npieces; ++piece) {
         const int4 pe = sc->e[piece];      // (read by all lanes, the same entry: readfirstlane keeps it -- and the descriptors built from it -- scalar)
         const int n = __builtin_amdgcn_readfirstlane(pe.x), strip = __builtin_amdgcn_readfirstlane(pe.y);
         const int ys = __builtin_amdgcn_readfirstlane(pe.z), S = __builtin_amdgcn_readfirstlane(pe.w);
         const int x0 = strip * SW;
-        RT_STEPS(S);
         // one descriptor PER FRAME (scalar arithmetic per piece): the 32-bit buffer offsets then only have to span a frame, not the batch
         const __amdgpu_buffer_rsrc_t p_rsrc = __builtin_amdgcn_make_buffer_rsrc(p.p_out + (size_t)n * (size_t)(CH * Hp) * Wp, 0, (int)p.p_bytes, 0x00020000);
         const __amdgpu_buffer_rsrc_t l_rsrc = __builtin_amdgcn_make_buffer_rsrc(p.logits + (size_t)n * (size_t)(p.n_cls * Hp) * Wp, 0, (int)p.l_bytes, 0x00020000);
@@ -369,7 +292,7 @@ __device__ __forceinline__ void consumer(const RollParams &p, const Smem &sm, co
 #pragma unroll
                 for (int c = 0; c < 4; ++c) {
                     const f32x4 o = sm.Rr[(pc * 16 + 4 * c + g) * 16 + q] + (Oh[c] * s0 + xb[c * 64] * s1);      // p[query][16c + 4g .. +3]
-                    if (rowok) __builtin_amdgcn_raw_buffer_store_b128(__builtin_bit_cast(u32x4, o), p_rsrc, vp, p_s + (unsigned)c * p_cstep, ROLL_PNT);
+                    if (rowok) __builtin_amdgcn_raw_buffer_store_b128(__builtin_bit_cast(u32x4, o), p_rsrc, vp, p_s + (unsigned)c * p_cstep, PNT);
                     if (NB > 0) {
                         const u32x4 os = split4r(o);
                         const h16x8 o1 = __builtin_bit_cast(h16x8, os), o2 = __builtin_bit_cast(h16x8, u32x4{os.z, os.w, os.x, os.y});
@@ -432,9 +355,7 @@ __device__ __forceinline__ void consumer(const RollParams &p, const Smem &sm, co
                 }
                 mh = ml; zh = rows_sum(z);
             }
-            RT(0);
             wg_sync();
-            RT(1);
             // ---------------------------------------------------------------- H2 (KH 0 first): log-softmax + logits stores of step s - 1
             if (KH == 0 && NB > 0 && s >= 1) {
                 const bool rowok = qy == 0 || ys + 2 * (s - 1) + 1 < Hp;
@@ -465,7 +386,7 @@ __device__ __forceinline__ void consumer(const RollParams &p, const Smem &sm, co
                     for (int nb = 0; nb < NBA; ++nb)
 #pragma unroll
                         for (int i = 0; i < 4; ++i)
-                            __builtin_amdgcn_raw_buffer_store_b32(__float_as_uint(lg[nb][i]), l_rsrc, vl[nb][i], l_s, ROLL_PNT);
+                            __builtin_amdgcn_raw_buffer_store_b32(__float_as_uint(lg[nb][i]), l_rsrc, vl[nb][i], l_s, PNT);
                 }
             }
             // ---------------------------------------------------------------- H2: P.V over this half's blocks (un-normalised)
@@ -507,12 +428,9 @@ __device__ __forceinline__ void consumer(const RollParams &p, const Smem &sm, co
                     xb[4 * 64] = f32x4{mh, zh, 0.f, 0.f};
                 }
             }
-            RT(2);
             wg_sync();
-            RT(3);
         }
     }
-    RT_FLUSH();
 }
 
 // ============================================================================================== producers (waves 4..15)
@@ -547,7 +465,6 @@ __device__ __forceinline__ void producer(const RollParams &p, const Smem &sm, co
         g_dW = uniform_f64((double)max(Wp - 1, 1)); g_dH = uniform_f64((double)max(Hp - 1, 1));
         g_rW = uniform_f64(1.0 / g_dW); g_rH = uniform_f64(1.0 / g_dH);
     }
-    RT_DECL;
 
     const int npieces = __builtin_amdgcn_readfirstlane(sc->count);
     for (int piece = 0; piece < npieces; ++piece) {
@@ -555,7 +472,6 @@ __device__ __forceinline__ void producer(const RollParams &p, const Smem &sm, co
         const int n = __builtin_amdgcn_readfirstlane(pe.x), strip = __builtin_amdgcn_readfirstlane(pe.y);
         const int ys = __builtin_amdgcn_readfirstlane(pe.z), S = __builtin_amdgcn_readfirstlane(pe.w);
         const int x0 = strip * SW;
-        RT_STEPS(S);
         const __amdgpu_buffer_rsrc_t g_rsrc = __builtin_amdgcn_make_buffer_rsrc(const_cast<float *>(p.ref[n]), 0, (int)p.ref_bytes, 0x00020000);
         const __amdgpu_buffer_rsrc_t lr_rsrc = __builtin_amdgcn_make_buffer_rsrc(const_cast<float *>(p.lr) + (size_t)n * (size_t)(p.hp * p.wp) * CH, 0, (int)p.lr_bytes, 0x00020000);
         const unsigned lr_img = 16u * gcg;           // (the frame is in the descriptor's base)
@@ -596,9 +512,8 @@ __device__ __forceinline__ void producer(const RollParams &p, const Smem &sm, co
         for (int t = T_FIRST; t <= S + 5; ++t) {
             // ================================================================ H1
             f32x4 gv[4];
-#if ROLL_LPRIO
-            __builtin_amdgcn_s_setprio(3);      // every wave's requests leave before anybody's arithmetic (the youngest waves of a SIMD otherwise issue theirs last)
-#endif
+            // (raising the priority while a producer requests its taps is zero-sum: the producers' H1 drops 2600 -> 1900 cycles, the merge
+            // waves' rises 2380 -> 3280 -- a SIMD's H1 is issue-bound)
             if (ROLE == ROLE_KV) {      // two of the four gather taps travel under the value conv (all four: 16 more registers than the conv leaves)
 #pragma unroll
                 for (int k = 0; k < 2; ++k) gv[k] = __builtin_bit_cast(f32x4, __builtin_amdgcn_raw_buffer_load_b128(g_rsrc, go[k] + 16u * gcg, 0, 0));
@@ -627,30 +542,19 @@ __device__ __forceinline__ void producer(const RollParams &p, const Smem &sm, co
             // ---- gather t: the four taps of this lane's pixel (tap offsets read in H1(t-1); the lines were touched by the tap wave in H2(t-2),
             // so these come from the L2: no load of a compute wave is in flight across a barrier -- hipcc's s_waitcnt bookkeeping otherwise
             // makes the LDS reads of H2 wait for them)
-#ifdef ROLL_NOGATHER
-            const bool g_on = false;
-#else
             const bool g_on = t >= 0 && t <= S + 3;
-#endif
 #pragma unroll
             for (int k = ROLE == ROLE_KV ? 2 : 0; k < 4; ++k)      // (outside [0, S+3] the offsets are stale but valid: the values are not used)
                 gv[k] = __builtin_bit_cast(f32x4, __builtin_amdgcn_raw_buffer_load_b128(g_rsrc, go[k] + 16u * gcg, 0, 0));
             // ---- lr_up rows ys + 2t - 7, ys + 2t - 6 (+1 halo column each side): the bilinear taps (lines touched by wave 12 in H2(t-2))
-#ifdef ROLL_NOLR
-            const bool l_on = false;
-#else
             const bool l_on = t >= 3 && t <= S + 3;
-#endif
             f32x4 lv[NLU > 0 ? NLU : 1][4];
             float lwy0[NLU > 0 ? NLU : 1], lwy1[NLU > 0 ? NLU : 1];
             {                                                        // (unconditional: hipcc spills registers that loads define under a branch;
-#pragma unroll                                                       //  outside [3, S+3] the table rows are stale, the values unused)
+#pragma unroll                                                       //  outside [3, S+3] the rows are clamped, the values unused)
                 for (int i = 0; i < NLU; ++i) {
-#if ROLL_LRTAB
-                    const u32x4 rt = sm.LrRow[lrr[i]];              // the row taps of the iteration (tap wave, H2(t-1))
-                    lwy0[i] = __uint_as_float(rt.z); lwy1[i] = __uint_as_float(rt.w);
-                    const unsigned r0 = lr_img + rt.x, r1 = lr_img + rt.y;
-#else
+                    // (the row taps from a table the tap wave writes instead: measured slower -- an LDS round trip in front of the lr loads,
+                    // and the tap wave is the longest of H2)
                     const int gy = ys + 2 * t - 7 + lrr[i];
                     int i0, i1; float l;
                     arseg_src_index(p.sy, min(max(gy, 0), Hp - 1), true, p.hp, i0, i1, l);
@@ -658,16 +562,12 @@ __device__ __forceinline__ void producer(const RollParams &p, const Smem &sm, co
                     const float iny = (unsigned)gy < (unsigned)Hp ? 1.f : 0.f;
                     lwy0[i] = (1.f - l) * iny; lwy1[i] = l * iny;
                     const unsigned r0 = lr_img + (unsigned)(i0 * p.wp) * (CH * 4u), r1 = lr_img + (unsigned)(i1 * p.wp) * (CH * 4u);
-#endif
                     lv[i][0] = __builtin_bit_cast(f32x4, __builtin_amdgcn_raw_buffer_load_b128(lr_rsrc, r0 + lx0[i], 0, 0));
                     lv[i][1] = __builtin_bit_cast(f32x4, __builtin_amdgcn_raw_buffer_load_b128(lr_rsrc, r0 + lx1[i], 0, 0));
                     lv[i][2] = __builtin_bit_cast(f32x4, __builtin_amdgcn_raw_buffer_load_b128(lr_rsrc, r1 + lx0[i], 0, 0));
                     lv[i][3] = __builtin_bit_cast(f32x4, __builtin_amdgcn_raw_buffer_load_b128(lr_rsrc, r1 + lx1[i], 0, 0));
                 }
             }
-#if ROLL_LPRIO
-            __builtin_amdgcn_s_setprio(0);
-#endif
             // ---- sampling position of gather t + 2 (warp rows ys - 4 + 2(t+2), +1), fp64 like the reference; the MV was requested in H2(t-1)
             if (ROLE == ROLE_AUX && tap_lane && t >= -2 && t <= S + 1) {
                 const int gy = ys + 2 * t + trr, gx = x0 - 4 + tcc;
@@ -703,9 +603,7 @@ __device__ __forceinline__ void producer(const RollParams &p, const Smem &sm, co
 #pragma unroll
                 for (int j = 0; j < 5; ++j) wqa[j] = sm.Wd[320 + qcg * 10 + j];
             }
-            RT(0);
             wg_sync();
-            RT(1);
             // ================================================================ H2
             if (ROLE == ROLE_KV) {
                 // ---- key records of rows rho = 2k, 2k + 1 (k = t - 1; image rows ys - 3 + rho); the value records follow in H1(t+1)
@@ -776,15 +674,6 @@ __device__ __forceinline__ void producer(const RollParams &p, const Smem &sm, co
 #pragma unroll
                     for (int i = 0; i < 8; ++i) pft[i] = __builtin_amdgcn_raw_buffer_load_b32(g_rsrc, o[i >> 1] + ((i & 1) ? 128u : 0u), 0, 0);
                 }
-                // ---- lr row taps of iteration t + 1 (lr_up rows ys + 2t - 5, ys + 2t - 4): lanes 48, 49 of the tap wave
-                if (ROLL_LRTAB && wave == 13 && (tl == NGP || tl == NGP + 1) && t >= 2 && t <= S + 2) {
-                    const int gy = ys + 2 * t - 5 + (tl - NGP);
-                    int i0, i1; float l;
-                    arseg_src_index(p.sy, min(max(gy, 0), Hp - 1), true, p.hp, i0, i1, l);
-                    l = fminf(fmaxf(l, 0.f), 1.f);
-                    const float iny = (unsigned)gy < (unsigned)Hp ? 1.f : 0.f;
-                    sm.LrRow[tl - NGP] = u32x4{(unsigned)(i0 * p.wp) * (CH * 4u), (unsigned)(i1 * p.wp) * (CH * 4u), __float_as_uint((1.f - l) * iny), __float_as_uint(l * iny)};
-                }
                 // ---- wave 12 touches the lr pixels under the lr_up rows of iteration t + 2 (rows ys + 2t - 3, ys + 2t - 2): lane = (lr row 0..3 from
                 // the first tap row, lr column 0..15 from the first tap column of the strip), both lines of the pixel
                 if (wave == 12 && t >= 1 && t <= S + 1) {
@@ -801,12 +690,9 @@ __device__ __forceinline__ void producer(const RollParams &p, const Smem &sm, co
                     pft[1] = __builtin_amdgcn_raw_buffer_load_b32(lr_rsrc, off == OOB ? OOB : off + 128u, 0, 0);
                 }
             }
-            RT(2);
             wg_sync();
-            RT(3);
         }
     }
-    RT_FLUSH();
 }
 
 template <int NB>      // NB: classifier row blocks of 16 classes (0: no head)
@@ -818,7 +704,7 @@ __global__ __launch_bounds__(NT) void creff_roll_kernel(const RollParams p) {
     sm.Ws = reinterpret_cast<f32x4 *>(smem + WS_OFF); sm.Ls = reinterpret_cast<f32x4 *>(smem + LS_OFF);
     sm.Qr = reinterpret_cast<u32x4 *>(smem + Q_OFF); sm.Rr = reinterpret_cast<f32x4 *>(smem + R_OFF);
     sm.Xb = reinterpret_cast<f32x4 *>(smem + XB_OFF); sm.TapW = reinterpret_cast<f32x4 *>(smem + TW_OFF);
-    sm.TapO = reinterpret_cast<u32x4 *>(smem + TO_OFF); sm.LrRow = reinterpret_cast<u32x4 *>(smem + LR_OFF);
+    sm.TapO = reinterpret_cast<u32x4 *>(smem + TO_OFF);
     sm.Wd = reinterpret_cast<f32x4 *>(smem + WD_OFF);
     sm.Wfs = reinterpret_cast<f32x4 *>(smem + WF_OFF);        // [4 chunks][4 groups][NBA*16]
     sm.Bfs = reinterpret_cast<float *>(smem + BF_OFF);
@@ -848,16 +734,8 @@ __global__ __launch_bounds__(NT) void creff_roll_kernel(const RollParams p) {
     if (tid == 0) build_pieces(p, sc);
     __syncthreads();
 
-#ifdef ROLL_ONLY      // dev builds only: one role alone, to read ITS register count off -Rpass-analysis=kernel-resource-usage (0 / 1: consumers, 2: key/value, 3: aux, 4: query)
-    if (ROLL_ONLY == 0) consumer<NB, 0>(p, sm, sc, tid, wave);
-    if (ROLL_ONLY == 1) consumer<NB, 1>(p, sm, sc, tid, wave);
-    if (ROLL_ONLY == 2) producer<ROLE_KV>(p, sm, sc, tid, wave);
-    if (ROLL_ONLY == 3) producer<ROLE_AUX>(p, sm, sc, tid, wave);
-    if (ROLL_ONLY == 4) producer<ROLE_Q>(p, sm, sc, tid, wave);
-    return;
-#endif
     if (wave < NCONS) {
-        __builtin_amdgcn_s_setprio(ROLL_CPRIO);       // the consumers are the critical path of both halves of an iteration
+        __builtin_amdgcn_s_setprio(CPRIO);       // the consumers are the critical path of both halves of an iteration
         if (wave < 2) consumer<NB, 0>(p, sm, sc, tid, wave);
         else consumer<NB, 1>(p, sm, sc, tid, wave);
     } else if (wave < 10) {
@@ -886,14 +764,7 @@ int launch(const RollParams &p, int max_wgs, hipStream_t st) {
     return arseg_launch_status();
 }
 
-#ifdef ROLL_TIMING
-unsigned long long *g_roll_dbg = nullptr;
-#endif
 }  // namespace
-
-#ifdef ROLL_TIMING
-extern "C" void arseg__roll_set_dbg(void *ptr) { g_roll_dbg = (unsigned long long *)ptr; }
-#endif
 
 // creff_rr.hip's entry point dispatches here (same argument checks there).
 int arseg_creff_roll_launch(const float *const *ref_nhwc_host, const int16_t *mv_q, int H, int W, const float *lr, const float *wq,
@@ -933,10 +804,6 @@ int arseg_creff_roll_launch(const float *const *ref_nhwc_host, const int16_t *mv
     p.lr_bytes = (unsigned)((size_t)CH * hp * wp * sizeof(float));
     p.ref_bytes = (unsigned)((size_t)CH * Hp * Wp * sizeof(float));
     p.sy = arseg_resize_scale(hp, Hp, true); p.sx = arseg_resize_scale(wp, Wp, true);
-    p.dbg = nullptr;
-#ifdef ROLL_TIMING
-    p.dbg = g_roll_dbg;
-#endif
     if (p.balanced) {      // a workgroup's list of pieces must hold its whole-strip passes + the pieces of its remainder run
         int dev = 0, cus = 256;
         if (hipGetDevice(&dev) != hipSuccess || hipDeviceGetAttribute(&cus, hipDeviceAttributeMultiprocessorCount, dev) != hipSuccess) cus = 256;

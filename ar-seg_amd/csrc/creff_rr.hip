@@ -22,11 +22,6 @@
 //
 // Arithmetic contract: as creff.hip (zero-padded unfold: keys / values outside the image are 0 and still take softmax mass).
 #include "creff_params.h"
-// cache policy of the p / logits stores: 2 = nontemporal (1.7 GB per 11-frame launch that nobody re-reads soon; keeps the XCD's L2 for the
-// overlapping gather of the keyframe feature: 242.4-243.9 -> 241.4 us per frame)
-#ifndef RR_PNT
-#define RR_PNT 2
-#endif
 #include "warp_math.h"
 
 namespace {
@@ -54,15 +49,9 @@ constexpr int SMEM_BYTES = LRT_OFF + 2 * LW * 16;       // 162,368 <= 163,840
 constexpr int MAXN = 32;
 constexpr unsigned OOB = 0xFFFFFFF0u;
 constexpr float LOG2E = 1.44269504088896340736f;
-#ifndef RR_G1
-#define RR_G1 2       // gather units requested ahead of the query conv
-#endif
-#ifndef RR_PEARLY
-#define RR_PEARLY 0   // 1: the single-pixel round is requested ahead of the query conv as well
-#endif
-#ifndef RR_GB
-#define RR_GB 5       // gather units per later batch
-#endif
+// cache policy of the p / logits stores: 2 = nontemporal (1.7 GB per 11-frame launch that nobody re-reads soon; keeps the XCD's L2 for the
+// overlapping gather of the keyframe feature: 242.4-243.9 -> 241.4 us per frame)
+constexpr int PNT = 2;
 
 struct RRParams {
     const float *ref[MAXN];       // un-warped keyframe feature of each frame, NHWC [Hp][Wp][64]
@@ -72,7 +61,6 @@ struct RRParams {
     int N, Hp, Wp, hp, wp, H, W, n_cls, log_softmax, p_layout, tiles_x, tiles_y;
     unsigned p_bytes, l_bytes, lr_bytes;
     float sy, sx;
-    unsigned long long *dbg;
 };
 
 __device__ __forceinline__ void split4(const f32x4 v, u32x2 &hi, u32x2 &lo) {
@@ -142,20 +130,6 @@ __device__ __forceinline__ double uniform_f64(double x) {
 }
 __device__ __forceinline__ int key_rec(int b, int k0, int base0) { return base0 + 24 * b + (k0 >= 14 - 2 * b ? 8 : 0); }
 
-#ifdef RR_TIMING
-// dev builds only: a wave adds the shader-clock ticks since its previous stamp to its dbg row (scalar registers, one atomic)
-// (every wave: dbg[16 * wave + i]; tools/time_phases.py reports wave 0, the mean and the slowest wave of each phase)
-#define RR_STAMP(i) do { const unsigned long long now_ = __builtin_amdgcn_s_memtime(); \
-        if ((tid0 & 63) == 0 && p.dbg) atomicAdd(p.dbg + 16 * (tid0 >> 6) + (i), now_ - tprev_); tprev_ = now_; } while (0)
-#else
-#define RR_STAMP(i) do { } while (0)
-#endif
-#ifdef RR_ABLATE
-#define RR_ON(bit) (!((RR_ABLATE >> (bit)) & 1) || p.N > 1000000)
-#else
-#define RR_ON(bit) true
-#endif
-
 template <int NB>      // NB: classifier row blocks of 16 classes (0: no head)
 __global__ __launch_bounds__(NT) void creff_rr_kernel(const RRParams p) {
     constexpr int NBA = NB > 0 ? NB : 1;
@@ -211,9 +185,6 @@ __global__ __launch_bounds__(NT) void creff_rr_kernel(const RRParams p) {
   for (int tile = t_lo + slot; tile < t_hi; tile += nslot) {
     // Everything derived from the thread id is recomputed per phase from an opaque copy: left alone, LLVM hoists the per-lane
     // constants of all phases (record indices, masks, addresses) to the top of the tile loop where they occupy ~100 registers.
-#ifdef RR_TIMING
-    unsigned long long tprev_ = __builtin_amdgcn_s_memtime();
-#endif
     const int n = tile / per_img, trem = tile - n * per_img;
     const int ty0 = (trem / p.tiles_x) * TY, tx0 = (trem - (trem / p.tiles_x) * p.tiles_x) * TX;
     const int Hp = p.Hp, Wp = p.Wp;
@@ -242,7 +213,7 @@ __global__ __launch_bounds__(NT) void creff_rr_kernel(const RRParams p) {
         const int g16 = t & 15, pl = t >> 4;
         const unsigned mv_cur = t < R4N ? TapO[t] : 0u;
         // window pixels by LDS-DMA: a wave's 64 lanes = 4 pixels x 16 channel groups = 1 KB contiguous in the pixel-major image
-        if (win_lds && RR_ON(2)) {
+        if (win_lds) {
             const unsigned wbase = lds_addr(LwA) + (unsigned)__builtin_amdgcn_readfirstlane(t >> 6) * 1024u;
 #pragma unroll
             for (int k = 0; k < 4; ++k) {
@@ -253,9 +224,7 @@ __global__ __launch_bounds__(NT) void creff_rr_kernel(const RRParams p) {
                 }
             }
         }
-        if (!RR_ON(0)) {
-            if (t < R4N) { TapW[t] = f32x4{0.5f, 0.5f, 0.5f, 0.5f}; TapO[t] = (unsigned)t; }
-        } else if (t < R4N) {
+        if (t < R4N) {
             const int yr = t / R4W, xr = t - yr * R4W;
             const int gy = ty0 - 4 + yr, gx = tx0 - 4 + xr;
             f32x4 w = {0.f, 0.f, 0.f, 0.f};
@@ -292,11 +261,9 @@ __global__ __launch_bounds__(NT) void creff_rr_kernel(const RRParams p) {
             const int mul = 16 * (isx ? 1 : (win_lds ? wx_n : p.wp)), lo = win_lds ? (isx ? wx_lo : wy_lo) : 0;     // in 16-byte units
             LrT[i] = u32x4{(unsigned)((i0 - lo) * mul), (unsigned)((i1 - lo) * mul), __float_as_uint((1.f - l) * in), __float_as_uint(l * in)};
         }
-        RR_STAMP(12);
         asm volatile("s_waitcnt vmcnt(0)" ::: "memory");       // the window has landed (and the motion vector requested ahead of it)
     }
     __syncthreads();
-    RR_STAMP(9);
 
     // ------------------------------------------------------------------ phases 1 + 2: query conv | gather + bilinear warp of the region into LDS
     // Gather unit = (region pixel, channel group): 16 lanes read one whole 256-byte pixel per tap.  The staged region overwrites the
@@ -306,7 +273,8 @@ __global__ __launch_bounds__(NT) void creff_rr_kernel(const RRParams p) {
     // neighbourhood (equal motion vectors -- codec MVs are block constant -- and no clamping at the image border) the block costs 9
     // pixel loads instead of 16: the gather is bound by the bytes the texture path returns (64 B / clk / CU).  Other blocks take
     // the per-pixel path at commit time.
-    constexpr int G1 = RR_G1, GU = 2, BW = R4W / 2;       // 144 blocks: two rounds of 64; the pixels of the last 16 blocks one by one (64 units)
+    constexpr int G1 = 2;                             // gather units requested ahead of the query conv
+    constexpr int GU = 2, BW = R4W / 2;               // 144 blocks: two rounds of 64; the pixels of the last 16 blocks one by one (64 units)
     const float *g_img = p.ref[n];
     const unsigned g_row_off = (unsigned)Wp * CH;
     auto g_prep = [&](int k, const float *&a) -> bool {
@@ -393,13 +361,11 @@ __global__ __launch_bounds__(NT) void creff_rr_kernel(const RRParams p) {
         constexpr int NL = G1 > 0 ? 9 : 0;       // round 0 here (a wave can post ~9 requests before the texture queue stalls it); round 1 ahead of the query conv
 #pragma unroll
         for (int k = 0; k < 6; ++k) {
-            if (RR_ON(1)) {
 #pragma unroll
-                for (int j = k * NL / 6; j < (k + 1) * NL / 6; ++j) gv[0][j] = g_load(ga[0], j);
-            }
+            for (int j = k * NL / 6; j < (k + 1) * NL / 6; ++j) gv[0][j] = g_load(ga[0], j);
             __builtin_amdgcn_sched_barrier(0);
             const int px = pl + 64 * k;
-            if (win_lds && RR_ON(2) && (k < 5 || px < LN)) {
+            if (win_lds && (k < 5 || px < LN)) {
                 const int r = px / LW, c = px - r * LW;
                 const u32x4 rt = LrT[r], ct = LrT[LW + c];
                 const float wy0 = __uint_as_float(rt.z), wy1 = __uint_as_float(rt.w), wx0 = __uint_as_float(ct.z), wx1 = __uint_as_float(ct.w);
@@ -410,7 +376,7 @@ __global__ __launch_bounds__(NT) void creff_rr_kernel(const RRParams p) {
         }
         // without the staged window (other scales): taps from global memory.  A separate loop: with the LDS and the global taps merged
         // into one, hipcc waits for vmcnt(0) -- i.e. for the gather requests in flight -- before every interpolation.
-        if (!win_lds && RR_ON(2)) {
+        if (!win_lds) {
             for (int px = pl; px < LN; px += 64) {
                 const int r = px / LW, c = px - r * LW;
                 const u32x4 rt = LrT[r], ct = LrT[LW + c];
@@ -421,19 +387,12 @@ __global__ __launch_bounds__(NT) void creff_rr_kernel(const RRParams p) {
         }
     }
     __syncthreads();
-    RR_STAMP(1);
 
     // ------------------------------------------------------------------ phase 1: query conv, lane local (channels 16c + 4g .. +3 of the lane's own query)
-    if (RR_ON(1)) {
 #pragma unroll
-        for (int k = 1; k < G1; ++k)
+    for (int k = 1; k < G1; ++k)
 #pragma unroll
-            for (int j = 0; j < 9; ++j) gv[k][j] = g_load(ga[k], j);
-    }
-#if RR_PEARLY
-    f32x4 gx[4];
-    if (RR_ON(1)) p_issue(gx);
-#endif
+        for (int j = 0; j < 9; ++j) gv[k][j] = g_load(ga[k], j);
     u32x2 qh[4], ql[4];
     {
         RR_TID(t);
@@ -441,7 +400,6 @@ __global__ __launch_bounds__(NT) void creff_rr_kernel(const RRParams p) {
         const int yq = 2 * (wave >> 1) + (q >> 3), xq = 8 * (wave & 1) + (q & 7);
 #pragma unroll
         for (int c = 0; c < 4; ++c) { qh[c] = u32x2{(unsigned)t, 0u}; ql[c] = qh[c]; }
-        if (RR_ON(3))
 #pragma unroll
         for (int c = 0; c < 4; ++c) {
             const f32x4 *w = WdQ + c * 40;
@@ -458,31 +416,21 @@ __global__ __launch_bounds__(NT) void creff_rr_kernel(const RRParams p) {
         }
     }
     __syncthreads();
-    RR_STAMP(2);
 
-    if (RR_ON(1)) {
 #pragma unroll
-        for (int k = 0; k < G1; ++k) g_commit(k, gv[k], grigid[k]);
-        __builtin_amdgcn_sched_barrier(0);
-        {       // the remaining rounds in flight together
-            f32x4 v[GU - G1 > 0 ? GU - G1 : 1][9], x[4];
-            bool rg[GU - G1 > 0 ? GU - G1 : 1];
+    for (int k = 0; k < G1; ++k) g_commit(k, gv[k], grigid[k]);
+    __builtin_amdgcn_sched_barrier(0);
+    {       // the remaining rounds in flight together
+        f32x4 v[GU - G1 > 0 ? GU - G1 : 1][9], x[4];
+        bool rg[GU - G1 > 0 ? GU - G1 : 1];
 #pragma unroll
-            for (int k = G1; k < GU; ++k) rg[k - G1] = g_issue(k, v[k - G1]);
-#if RR_PEARLY
-            p_commit(gx);
-#else
-            p_issue(x);
-#endif
+        for (int k = G1; k < GU; ++k) rg[k - G1] = g_issue(k, v[k - G1]);
+        p_issue(x);
 #pragma unroll
-            for (int k = G1; k < GU; ++k) g_commit(k, v[k - G1], rg[k - G1]);
-#if !RR_PEARLY
-            p_commit(x);
-#endif
-        }
+        for (int k = G1; k < GU; ++k) g_commit(k, v[k - G1], rg[k - G1]);
+        p_commit(x);
     }
     __syncthreads();
-    RR_STAMP(3);
 
     // ------------------------------------------------------------------ phase 3: walker columns into registers
     // lane = DPP row r4 (span = r4 & 1, half = r4 >> 1) x 16 columns; channel group = wave
@@ -492,11 +440,10 @@ __global__ __launch_bounds__(NT) void creff_rr_kernel(const RRParams p) {
         const int lane = t & 63, wave = t >> 6, r4 = lane >> 4, xi = lane & 15;
         const int xr = 8 * (r4 & 1) + xi, rb = 11 * (r4 >> 1);
 #pragma unroll
-        for (int j = 0; j < 13; ++j) h[j] = BIGf[wave * HPL + (RR_ON(2) ? (rb + j) * R4W + xr : 0)];
+        for (int j = 0; j < 13; ++j) h[j] = BIGf[wave * HPL + (rb + j) * R4W + xr];
         if (tile + nslot < t_hi) mv_fetch(tile + nslot);       // the tap tables are dead
     }
     __syncthreads();
-    RR_STAMP(4);
 
     // ------------------------------------------------------------------ phases 4 / 6: key (value) records of the whole region
     // Interior tiles (every record of the 22 x 22 region inside the image: all but the frame's border tiles) need no padding mask -- a
@@ -551,10 +498,9 @@ __global__ __launch_bounds__(NT) void creff_rr_kernel(const RRParams p) {
                 if (wr_ok && !(col_in && (unsigned)(gy + j) < (unsigned)Hp)) dst[j * R3W] = u32x4{zz, zz, zz, zz};
         }
     };
-    if (RR_ON(4)) conv_records(p.wk, p.bk, KPLK);
+    conv_records(p.wk, p.bk, KPLK);
     asm volatile("s_waitcnt vmcnt(0)" ::: "memory");           // the next tile's motion vectors have landed long ago
     __syncthreads();
-    RR_STAMP(5);
 
     // ------------------------------------------------------------------ phase 5: scores S[b][i] = q . key(16b + 4g + i), then softmax
     float inv;
@@ -566,24 +512,21 @@ __global__ __launch_bounds__(NT) void creff_rr_kernel(const RRParams p) {
         f32x4 S[7];
 #pragma unroll
         for (int b = 0; b < 7; ++b) S[b] = f32x4{0.f, 0.f, 0.f, 0.f};
-        if (RR_ON(5)) {
-            int krec[7];
+        int krec[7];
 #pragma unroll
-            for (int b = 0; b < 7; ++b) krec[b] = key_rec(b, q, 2 * pr * R3W + 8 * pc + q);
+        for (int b = 0; b < 7; ++b) krec[b] = key_rec(b, q, 2 * pr * R3W + 8 * pc + q);
 #pragma unroll
-            for (int c = 0; c < 4; ++c) {
-                const u32x4 *ka = BIGu + (4 * c + g) * KPLK;
-                const h16x8 b1 = pack8(qh[c], ql[c]), b2 = pack8(ql[c], qh[c]);
+        for (int c = 0; c < 4; ++c) {
+            const u32x4 *ka = BIGu + (4 * c + g) * KPLK;
+            const h16x8 b1 = pack8(qh[c], ql[c]), b2 = pack8(ql[c], qh[c]);
 #pragma unroll
-                for (int b = 0; b < 7; ++b) {
-                    const h16x8 a = __builtin_bit_cast(h16x8, ka[krec[b]]);
-                    S[b] = __builtin_amdgcn_mfma_f32_16x16x32_f16(a, b1, S[b], 0, 0, 0);
-                    S[b] = __builtin_amdgcn_mfma_f32_16x16x32_f16(a, b2, S[b], 0, 0, 0);
-                }
+            for (int b = 0; b < 7; ++b) {
+                const h16x8 a = __builtin_bit_cast(h16x8, ka[krec[b]]);
+                S[b] = __builtin_amdgcn_mfma_f32_16x16x32_f16(a, b1, S[b], 0, 0, 0);
+                S[b] = __builtin_amdgcn_mfma_f32_16x16x32_f16(a, b2, S[b], 0, 0, 0);
             }
         }
             // softmax over the 49 taps (padding taps included)
-        RR_STAMP(10);
         float m = -INFINITY;
 #pragma unroll
         for (int b = 0; b < 7; ++b)
@@ -599,7 +542,7 @@ __global__ __launch_bounds__(NT) void creff_rr_kernel(const RRParams p) {
         for (int b = 0; b < 7; ++b) {
 #pragma unroll
             for (int i = 0; i < 4; ++i) {
-                if (RR_ON(11)) S[b][i] = __builtin_amdgcn_exp2f(fmaf(S[b][i], LOG2E, -ml));     // masked slots: exp2(-inf) = 0
+                S[b][i] = __builtin_amdgcn_exp2f(fmaf(S[b][i], LOG2E, -ml));     // masked slots: exp2(-inf) = 0
                 z += S[b][i];
             }
             u32x2 hi, lo;
@@ -612,10 +555,9 @@ __global__ __launch_bounds__(NT) void creff_rr_kernel(const RRParams p) {
         for (int b = 0; b < 7; ++b) asm volatile("" : "+v"(P[b]));      // finish the softmax here, not behind the value conv
     }
     __syncthreads();
-    RR_STAMP(6);
 
     // ------------------------------------------------------------------ phase 6: value records (the key records are dead)
-    if (RR_ON(6)) conv_records(p.wv, p.bv, KPLV);
+    conv_records(p.wv, p.bv, KPLV);
     // classifier records [chunk][group][class] {4 hi | 4 lo}, behind the value records
     {
         RR_TID(t);
@@ -630,7 +572,6 @@ __global__ __launch_bounds__(NT) void creff_rr_kernel(const RRParams p) {
         if (NB > 0 && t >= 512 && t < 512 + NBA * 16) Bfs[t - 512] = t - 512 < p.n_cls ? p.bf[t - 512] : 0.f;
     }
     __syncthreads();
-    RR_STAMP(7);
 
     // ------------------------------------------------------------------ phase 7: P.V, residual, classifier, stores
     {
@@ -649,7 +590,7 @@ __global__ __launch_bounds__(NT) void creff_rr_kernel(const RRParams p) {
 #pragma unroll
         for (int nb = 0; nb < NBA; ++nb) lg[nb] = f32x4{0.f, 0.f, 0.f, 0.f};
         const __amdgpu_buffer_rsrc_t p_rsrc = __builtin_amdgcn_make_buffer_rsrc(p.p_out, 0, (int)p.p_bytes, 0x00020000);
-        if (RR_ON(7)) {
+        {
             // residual term lr_up(own pixel): bilinear(align_corners=True) taps, coordinates clamped into the image
             int y0, y1, x0, x1; float ly, lx;
             arseg_src_index(p.sy, min(gyq, Hp - 1), true, p.hp, y0, y1, ly);
@@ -661,7 +602,7 @@ __global__ __launch_bounds__(NT) void creff_rr_kernel(const RRParams p) {
             const unsigned lrb = (unsigned)n * (unsigned)(p.hp * p.wp) * (CH * 4u) + 16u * g;
             const unsigned o00 = lrb + (unsigned)(y0 * p.wp + x0) * (CH * 4u), o01 = lrb + (unsigned)(y0 * p.wp + x1) * (CH * 4u);
             const unsigned o10 = lrb + (unsigned)(y1 * p.wp + x0) * (CH * 4u), o11 = lrb + (unsigned)(y1 * p.wp + x1) * (CH * 4u);
-            auto lr_tap = [&](unsigned o, int c) { return RR_ON(8) ? __builtin_bit_cast(f32x4, __builtin_amdgcn_raw_buffer_load_b128(lr_rsrc, o, 64 * c, 0)) : f32x4{(float)o, 0.f, 0.f, 0.f}; };
+            auto lr_tap = [&](unsigned o, int c) { return __builtin_bit_cast(f32x4, __builtin_amdgcn_raw_buffer_load_b128(lr_rsrc, o, 64 * c, 0)); };
             // byte offset of the value record of (block b, this lane's key) in a channel-group plane: vbase + 384 b (+128 where bit b of
             // vsel is set) -- see key_rec; one register pair instead of seven addresses
             const int vk0 = 4 * g + (q >> 2);
@@ -672,8 +613,8 @@ __global__ __launch_bounds__(NT) void creff_rr_kernel(const RRParams p) {
             auto vrec = [&](int b) { return vbase + 384u * b + (((vsel >> b) & 1u) << 7); };
             auto epilogue = [&](int c, const f32x4 o) {       // o = p[query][16c + 4g .. +3]: store, then this chunk's share of the classifier
                 const unsigned off = p_off0 + (unsigned)c * p_step;
-                __builtin_amdgcn_raw_buffer_store_b128(__builtin_bit_cast(u32x4, o), p_rsrc, (inq && RR_ON(9)) ? off : OOB, 0, RR_PNT);
-                if (NB > 0 && RR_ON(13)) {
+                __builtin_amdgcn_raw_buffer_store_b128(__builtin_bit_cast(u32x4, o), p_rsrc, inq ? off : OOB, 0, PNT);
+                if (NB > 0) {
                     u32x2 oh, ol;
                     split4(o, oh, ol);
                     const h16x8 o1 = pack8(oh, ol), o2 = pack8(ol, oh);
@@ -705,7 +646,6 @@ __global__ __launch_bounds__(NT) void creff_rr_kernel(const RRParams p) {
         }
 
         // logits: lg[nb][i] = class 16nb + 4g + i of query q
-        RR_STAMP(11);
         if (NB > 0) {
             const __amdgpu_buffer_rsrc_t l_rsrc = __builtin_amdgcn_make_buffer_rsrc(p.logits, 0, (int)p.l_bytes, 0x00020000);
             float m = -INFINITY;
@@ -735,16 +675,11 @@ __global__ __launch_bounds__(NT) void creff_rr_kernel(const RRParams p) {
                 for (int i = 0; i < 4; ++i) {
                     const int cls = nb * 16 + 4 * g + i;
                     const unsigned off = l_off0 + (unsigned)cls * plane * 4u;
-                    __builtin_amdgcn_raw_buffer_store_b32(__float_as_uint(lg[nb][i]), l_rsrc, (inq && cls < p.n_cls && RR_ON(14)) ? off : OOB, 0, RR_PNT);
+                    __builtin_amdgcn_raw_buffer_store_b32(__float_as_uint(lg[nb][i]), l_rsrc, (inq && cls < p.n_cls) ? off : OOB, 0, PNT);
                 }
         }
     }
-    RR_STAMP(13);
     __syncthreads();          // the next tile's tables / staging overwrite LDS this tile still reads
-    RR_STAMP(8);
-#ifdef RR_TIMING
-    if (tid0 == 0 && p.dbg) atomicAdd(p.dbg + 15, 1ull);
-#endif
   }
 }
 
@@ -760,14 +695,7 @@ int launch(const RRParams &p, hipStream_t st) {
     return arseg_launch_status();
 }
 
-#ifdef RR_TIMING
-unsigned long long *g_rr_dbg = nullptr;
-#endif
 }  // namespace
-
-#ifdef RR_TIMING
-extern "C" void arseg__rr_set_dbg(void *ptr) { g_rr_dbg = (unsigned long long *)ptr; }
-#endif
 
 extern "C" int arseg_creff_warp_fwd_ex(const float *const *ref_nhwc_host, const int16_t *mv_q, int H, int W, const float *lr,
                                        const float *wq, const float *bq, const float *wk, const float *bk, const float *wv,
@@ -816,10 +744,6 @@ extern "C" int arseg_creff_warp_fwd_ex(const float *const *ref_nhwc_host, const 
     p.p_bytes = (unsigned)((size_t)N * C * Hp * Wp * sizeof(float)); p.l_bytes = head ? (unsigned)((size_t)N * n_cls * Hp * Wp * sizeof(float)) : 0u;
     p.lr_bytes = (unsigned)((size_t)N * C * hp * wp * sizeof(float));
     p.sy = arseg_resize_scale(hp, Hp, true); p.sx = arseg_resize_scale(wp, Wp, true);
-    p.dbg = nullptr;
-#ifdef RR_TIMING
-    p.dbg = g_rr_dbg;
-#endif
     hipStream_t st = arseg_stream(stream);
     if (!head) return launch<0>(p, st);
     return n_cls <= 16 ? launch<1>(p, st) : launch<2>(p, st);

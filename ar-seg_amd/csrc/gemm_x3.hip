@@ -82,7 +82,7 @@ __device__ __forceinline__ f32x4 mfma16(const h16x8 a, const h16x8 b, const f32x
 }
 
 // NWM x NWN waves; 16-row fragments per wave: WTM along M (activation rows), WTN along N (weight rows); FMT 0: split rows (f16x3), 1: fp16 rows, 2: bf16 rows
-template <int NWM, int NWN, int WTM, int WTN, int ABL = 0, bool STAG = false, int FMT = 0>
+template <int NWM, int NWN, int WTM, int WTN, bool STAG = false, int FMT = 0>
 __global__ __launch_bounds__(64 * NWM * NWN) void gemm_x3_kernel(const GX3Params p) {
     constexpr unsigned EB = FMT == 0 ? 4u : 2u;           // bytes per operand value
     constexpr int NW = NWM * NWN, BM = 16 * NWM * WTM, BN = 16 * NWN * WTN;
@@ -175,8 +175,6 @@ __global__ __launch_bounds__(64 * NWM * NWN) void gemm_x3_kernel(const GX3Params
 #pragma unroll
         for (int c = 0; c < WTN; ++c) acc[a][c] = f32x4{0.f, 0.f, 0.f, 0.f};
 
-    constexpr int PRIO = (ABL & 4) ? 1 : 0;
-    constexpr bool NOREAD = (ABL & 2) != 0, NODMA = (ABL & 1) != 0;
     constexpr int HM = WTM >= 4 ? WTM / 2 : WTM;         // activation fragments held at a time
     auto mfmas = [&](int h, const h16x8 (&wh)[WTN], const h16x8 (&wl)[WTN], const h16x8 (&xh)[HM], const h16x8 (&xl)[HM]) {
         if constexpr (FMT != 0) {      // 16-bit rows: "h" = k 0..31, "l" = k 32..63 of the step, one product each
@@ -203,17 +201,8 @@ __global__ __launch_bounds__(64 * NWM * NWN) void gemm_x3_kernel(const GX3Params
 #pragma unroll
             for (int c = 0; c < WTN; ++c) acc[h * HM + a][c] = __builtin_amdgcn_mfma_f32_16x16x32_f16(wh[c], xh[a], acc[h * HM + a][c], 0, 0, 0);
     };
-    h16x8 pwh[WTN], pwl[WTN], pxh[HM], pxl[HM];           // (ablation builds: fragments read once)
     auto compute = [&](int st, int kt_next) {       // kt_next >= 0: the next K step's operands are requested into the other buffer on the way
         const unsigned char *base = smem + st * STAGE;
-        if constexpr (NOREAD) {
-#pragma unroll
-            for (int h = 0; h < WTM / HM; ++h) {
-                if (kt_next >= 0) { if (h == 0) issue_x(kt_next, st ^ 1); else if (h == WTM / HM - 1) issue_w(kt_next, st ^ 1); }
-                mfmas(h, pwh, pwl, pxh, pxl);
-            }
-            return;
-        }
         h16x8 wh[WTN], wl[WTN];
 #pragma unroll
         for (int c = 0; c < WTN; ++c) {
@@ -234,7 +223,7 @@ __global__ __launch_bounds__(64 * NWM * NWN) void gemm_x3_kernel(const GX3Params
                 if (h == 0) issue_x(kt_next, st ^ 1);
                 if (h == WTM / HM - 1) issue_w(kt_next, st ^ 1);
             }
-            __builtin_amdgcn_s_setprio(PRIO);
+            __builtin_amdgcn_s_setprio(0);      // (priority 1 around these MFMAs, as in the staggered form below, was tried here and not kept)
             mfmas(h, wh, wl, xh, xl);
             __builtin_amdgcn_s_setprio(0);
         }
@@ -245,18 +234,6 @@ __global__ __launch_bounds__(64 * NWM * NWN) void gemm_x3_kernel(const GX3Params
     issue_w(0, 0);
     asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
     __syncthreads();
-    if constexpr (NOREAD) {
-#pragma unroll
-        for (int c = 0; c < WTN; ++c) {
-            pwh[c] = *reinterpret_cast<const h16x8 *>(smem + wo + c * 2048);
-            pwl[c] = *reinterpret_cast<const h16x8 *>(smem + (wo ^ 64u) + c * 2048);
-        }
-#pragma unroll
-        for (int a = 0; a < HM; ++a) {
-            pxh[a] = *reinterpret_cast<const h16x8 *>(smem + xo + a * 2048);
-            pxl[a] = *reinterpret_cast<const h16x8 *>(smem + (xo ^ 64u) + a * 2048);
-        }
-    }
     if constexpr (STAG) {
         // Two wave groups half a K step apart (each SIMD hosts two waves of either group): a K step is read(half 0) | MFMA(half 0) | read(half 1) |
         // MFMA(half 1), separated by barriers, and group 1 starts one barrier late -- while one group issues MFMAs the other reads fragments and
@@ -315,7 +292,7 @@ __global__ __launch_bounds__(64 * NWM * NWN) void gemm_x3_kernel(const GX3Params
     for (int kt = 0; kt < nk; ++kt) {
         const int cur = kt & 1;
         // (the other buffer is free: everybody finished reading it before the last barrier)
-        compute(NOREAD ? 0 : cur, (kt + 1 < nk && !NODMA) ? kt + 1 : -1);
+        compute(cur, kt + 1 < nk ? kt + 1 : -1);
         asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
         __syncthreads();
     }
@@ -448,43 +425,37 @@ __global__ __launch_bounds__(256) void psp_w2_split_kernel(const float *__restri
     if (range_flag && vmax > range_limit) atomicOr(range_flag, 1u);
 }
 
-template <int NWM, int NWN, int WTM, int WTN, int ABL = 0, bool STAG = false, int FMT = 0>
+template <int NWM, int NWN, int WTM, int WTN, bool STAG = false, int FMT = 0>
 int launch_x3(GX3Params &p, hipStream_t hs) {
     constexpr int BM = 16 * NWM * WTM, BN = 16 * NWN * WTN;
     p.tiles_m = arseg_cdiv(p.M, BM); p.tiles_n = arseg_cdiv(p.N, BN);
     if ((long long)p.tiles_m * p.tiles_n * p.batch >= (1ll << 31)) return ARSEG_EUNSUPPORTED;
     const size_t smem = (size_t)2 * (BM + BN) * 128;
     static ArsegSmemAttr attr;
-    if (int e = arseg_allow_smem(attr, reinterpret_cast<const void *>(gemm_x3_kernel<NWM, NWN, WTM, WTN, ABL, STAG, FMT>), smem)) return e;
-    hipLaunchKernelGGL((gemm_x3_kernel<NWM, NWN, WTM, WTN, ABL, STAG, FMT>), dim3(p.tiles_m * p.tiles_n * p.batch), dim3(64 * NWM * NWN), smem, hs, p);
+    if (int e = arseg_allow_smem(attr, reinterpret_cast<const void *>(gemm_x3_kernel<NWM, NWN, WTM, WTN, STAG, FMT>), smem)) return e;
+    hipLaunchKernelGGL((gemm_x3_kernel<NWM, NWN, WTM, WTN, STAG, FMT>), dim3(p.tiles_m * p.tiles_n * p.batch), dim3(64 * NWM * NWN), smem, hs, p);
     return arseg_launch_status();
 }
 
 // tile_cfg -> tile shape.  0-6: the GEMM shapes of rounds 3-4; 7-10 (r5): narrow / short tiles for the implicit 3x3 convs of the 64- and 128-channel
 // layers (a 64-wide N tile cannot feed 16 waves: 8 rows of weights per DMA instruction)
-template <int ABL, int FMT>
+template <int FMT>
 int launch_cfg(GX3Params &p, int cfg, hipStream_t hs) {
     switch (cfg) {
-        case 0: return launch_x3<2, 4, 8, 4, ABL, false, FMT>(p, hs);      // 256 x 256,  8 waves
-        case 1: return launch_x3<4, 4, 4, 4, ABL, false, FMT>(p, hs);      // 256 x 256, 16 waves
-        case 2: return launch_x3<2, 4, 4, 4, ABL, false, FMT>(p, hs);      // 128 x 256,  8 waves
-        case 3: return launch_x3<2, 4, 4, 2, ABL, false, FMT>(p, hs);      // 128 x 128,  8 waves
-        case 4: return launch_x3<4, 4, 4, 2, ABL, false, FMT>(p, hs);      // 256 x 128, 16 waves
-        case 5: return launch_x3<4, 4, 2, 4, ABL, false, FMT>(p, hs);      // 128 x 256, 16 waves
-        case 6: return launch_x3<4, 4, 4, 4, ABL, true, FMT>(p, hs);       // 256 x 256, 16 waves in two staggered groups
-        default: break;
+        case 0: return launch_x3<2, 4, 8, 4, false, FMT>(p, hs);      // 256 x 256,  8 waves
+        case 1: return launch_x3<4, 4, 4, 4, false, FMT>(p, hs);      // 256 x 256, 16 waves
+        case 2: return launch_x3<2, 4, 4, 4, false, FMT>(p, hs);      // 128 x 256,  8 waves
+        case 3: return launch_x3<2, 4, 4, 2, false, FMT>(p, hs);      // 128 x 128,  8 waves
+        case 4: return launch_x3<4, 4, 4, 2, false, FMT>(p, hs);      // 256 x 128, 16 waves
+        case 5: return launch_x3<4, 4, 2, 4, false, FMT>(p, hs);      // 128 x 256, 16 waves
+        case 6: return launch_x3<4, 4, 4, 4, true, FMT>(p, hs);       // 256 x 256, 16 waves in two staggered groups
+        case 7: return launch_x3<4, 2, 4, 2, false, FMT>(p, hs);      // 256 x  64,  8 waves
+        case 8: return launch_x3<4, 1, 2, 4, false, FMT>(p, hs);      // 128 x  64,  4 waves (three workgroups per compute unit)
+        case 9: return launch_x3<4, 2, 2, 2, false, FMT>(p, hs);      // 128 x  64,  8 waves
+        case 10: return launch_x3<2, 4, 2, 2, false, FMT>(p, hs);     //  64 x 128,  8 waves
+        case 11: return launch_x3<4, 2, 2, 4, false, FMT>(p, hs);     // 128 x 128,  8 waves, 32 x 64 wave tiles
+        default: return ARSEG_EINVAL;
     }
-    if constexpr (ABL == 0) {
-        switch (cfg) {
-            case 7: return launch_x3<4, 2, 4, 2, 0, false, FMT>(p, hs);    // 256 x  64,  8 waves
-            case 8: return launch_x3<4, 1, 2, 4, 0, false, FMT>(p, hs);    // 128 x  64,  4 waves (three workgroups per compute unit)
-            case 9: return launch_x3<4, 2, 2, 2, 0, false, FMT>(p, hs);    // 128 x  64,  8 waves
-            case 10: return launch_x3<2, 4, 2, 2, 0, false, FMT>(p, hs);   //  64 x 128,  8 waves
-            case 11: return launch_x3<4, 2, 2, 4, 0, false, FMT>(p, hs);   // 128 x 128,  8 waves, 32 x 64 wave tiles
-            default: break;
-        }
-    }
-    return ARSEG_EINVAL;
 }
 
 }  // namespace
@@ -542,16 +513,7 @@ static int gemm_x3(const void *x_split, const void *w_split, const void *x2_spli
     p.range_flag = out_split ? reinterpret_cast<unsigned *>(range_flag) : nullptr; p.range_limit = range_limit > 0.0f ? range_limit : 65504.0f;
     p.taps = 1; p.kg = K >> 5; p.pH = p.pW = p.iH = p.iW = 1; p.pad = 0; p.dil = 1; p.out_mode = 0; p.res_rows = nullptr; p.ldx = (unsigned)K * 4u;
     hipStream_t hs = arseg_stream(stream);
-#ifdef ARSEG_GX3_ABLATE      // dev builds (tools/bench_gemm_x3.py): tile_cfg = 16 * ablation + tile; wrong results, same instruction stream otherwise
-    switch (tile_cfg >> 4) {
-        case 1: return launch_cfg<1, 0>(p, tile_cfg & 15, hs);
-        case 2: return launch_cfg<2, 0>(p, tile_cfg & 15, hs);
-        case 3: return launch_cfg<3, 0>(p, tile_cfg & 15, hs);
-        case 4: return launch_cfg<4, 0>(p, tile_cfg & 15, hs);
-        default: break;
-    }
-#endif
-    return launch_cfg<0, 0>(p, tile_cfg, hs);
+    return launch_cfg<0>(p, tile_cfg, hs);
 }
 
 // Implicit 3x3 conv / plain GEMM on rows of any of the three formats (fmt = enum arseg_rows_fmt); see arseg_conv3x3_rows_fwd in the header.
@@ -601,9 +563,9 @@ static int conv_rows(const void *x_rows, const void *w_rows, void *out, int fmt,
     p.out_mode = taps == 1 ? 0 : (padded_out ? 2 : 1); p.ldx = (unsigned)Cin * eb;
     hipStream_t hs = arseg_stream(stream);
     switch (fmt) {
-        case ARSEG_ROWS_X3: return launch_cfg<0, 0>(p, tile_cfg, hs);
-        case ARSEG_ROWS_F16: return launch_cfg<0, 1>(p, tile_cfg, hs);
-        default: return launch_cfg<0, 2>(p, tile_cfg, hs);
+        case ARSEG_ROWS_X3: return launch_cfg<0>(p, tile_cfg, hs);
+        case ARSEG_ROWS_F16: return launch_cfg<1>(p, tile_cfg, hs);
+        default: return launch_cfg<2>(p, tile_cfg, hs);
     }
 }
 

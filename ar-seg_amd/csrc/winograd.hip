@@ -12,9 +12,6 @@
 // tilesY = ceil(ceil(H/d)/4).  Threads run along channels (coalesced 4-byte accesses, 36 registers of patch per thread).
 // fp32 throughout; the transform constants grow the rounding error to ~1e-5 relative (vs 1e-6 for the direct form).
 #include "arseg_common.h"
-#ifndef WINO_NT_LOADS
-#define WINO_NT_LOADS 1
-#endif
 
 namespace {
 
@@ -206,17 +203,12 @@ __global__ __launch_bounds__(256) void wino43_output_kernel(const float *__restr
         const int t = idx / Cv, c = (idx - t * Cv) * VW;
         int n, y0, x0;
         tile_origin(g, t, n, y0, x0);
-        F m[6][6];
+        F m[6][6];      // (M is read exactly once: nontemporal loads leave the L2 / Infinity Cache to the other lanes)
 #pragma unroll
         for (int i = 0; i < 6; ++i)
 #pragma unroll
-            for (int j = 0; j < 6; ++j) {
-#if WINO_NT_LOADS
+            for (int j = 0; j < 6; ++j)
                 m[i][j] = __builtin_nontemporal_load(reinterpret_cast<const F *>(M + ((size_t)(i * 6 + j) * g.T + t) * C + c));
-#else
-                m[i][j] = *reinterpret_cast<const F *>(M + ((size_t)(i * 6 + j) * g.T + t) * C + c);
-#endif
-            }
         F tmp[4][6];
 #pragma unroll
         for (int j = 0; j < 6; ++j) {            // A^T m : columns

@@ -20,7 +20,7 @@ _CHOICES = {
     "conv_range_guard": ("device", "host", "off"),
     "conv_gemm_x3": (True, False, "wino"),
     "conv_igemm3": (True, False),
-    "creff_impl": ("", "mfma", "valu", "fused"),
+    "creff_impl": ("", "mfma", "valu"),
     "creff_tile_rows": (0, 8, 16),
     "creff_warp_impl": ("", "roll", "tiles"),
 }
@@ -47,7 +47,7 @@ class Config:
     conv_range_guard [ARSEG_CONV_RANGE_GUARD = device | host | 0]   operand range of the f16x3 back end: sticky device word read by
                      ops.range_tripped() (default) / amax + host sync per conv with an immediate fp32 fallback / off
     conv_plan_file   [ARSEG_CONV_PLAN_FILE = <json>]            persist the tuned plans
-    creff_impl       [ARSEG_CREFF_IMPL = mfma | valu | fused]   pin one CReFF kernel for C >= 128 (A/B measurements, tests)
+    creff_impl       [ARSEG_CREFF_IMPL = mfma | valu]           pin one CReFF kernel for C >= 128 (A/B measurements, tests)
     creff_tile_rows  [ARSEG_CREFF_TY = 8 | 16]                  pin the tile height of the matrix-core CReFF kernel
     creff_warp_impl  [ARSEG_CREFF_WARP_IMPL = roll | tiles]     fused warp + CReFF kernel for C = 64: the rolling kernel (csrc/creff_roll.hip, default) or
                      the 16 x 16 tile kernel of rounds 2-3 (csrc/creff_rr.hip)

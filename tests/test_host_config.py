@@ -96,12 +96,14 @@ def test_config_validation_is_the_same_for_env_and_configure(monkeypatch):
     from arseg_amd import _lib, ops
 
     for var, bad in (("ARSEG_CREFF_WARP_IMPL", "rol"), ("ARSEG_CONV_WINO_MARGIN", "0"), ("ARSEG_CONV_WINO_MARGIN", "-1"), ("ARSEG_CONV_MATH", "fp32"),
-                     ("ARSEG_CREFF_TY", "12"), ("ARSEG_CONV_RANGE_GUARD", "devcie"), ("ARSEG_CREFF_MAX_WGS", "-3"), ("ARSEG_LR_SUBBATCH", "x")):
+                     ("ARSEG_CREFF_TY", "12"), ("ARSEG_CONV_RANGE_GUARD", "devcie"), ("ARSEG_CREFF_MAX_WGS", "-3"), ("ARSEG_LR_SUBBATCH", "x"),
+                     ("ARSEG_CREFF_IMPL", "fused")):
         monkeypatch.setenv(var, bad)
         with pytest.raises(_lib.ArsegError):
             ops.Config.from_env()
         monkeypatch.delenv(var)
-    for kw in ({"creff_warp_impl": "rol"}, {"conv_wino_margin": 0}, {"conv_math": "fp32"}, {"creff_tile_rows": 12}, {"creff_max_wgs": -1}, {"conv_range_guard": "x"}):
+    for kw in ({"creff_warp_impl": "rol"}, {"conv_wino_margin": 0}, {"conv_math": "fp32"}, {"creff_tile_rows": 12}, {"creff_max_wgs": -1}, {"conv_range_guard": "x"},
+               {"creff_impl": "fused"}):
         with pytest.raises(_lib.ArsegError):
             ops.configure(**kw)
     assert ops.Config.from_env() == ops.Config()

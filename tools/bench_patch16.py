@@ -1,7 +1,6 @@
 #!/usr/bin/env python3
 """The patch-resident 16-bit 3x3 kernel (arseg_conv2d16_fwd, tile_cfg 5..8) on the 3x3 stride-1 layer shapes of the BiSeNet bench
-configurations, every tile_cfg timed alone with HIP events (5..8: the 4 x 64 / 2 x 64 pixel tiles, 10..13: the squarer tiles of round 6; with
-ARSEG_HIP_LIB pointing at a -DPATCH_ABL=<bits> build the ablations that say where the kernel's time goes):
+configurations, every tile_cfg timed alone with HIP events (5..8: the 4 x 64 / 2 x 64 pixel tiles, 10..13: the squarer tiles of round 6):
 
     python tools/bench_patch16.py [--dtype bf16|f16] [--json FILE]
 

@@ -1,6 +1,5 @@
 #!/usr/bin/env python3
-"""The 16-bit stem kernel (conv16_stem_kernel, tile_cfg 9) alone on the two bench shapes (11 x 512 x 1024 LR batch, 1 x 1024 x 2048 keyframe), us per call.
-With ARSEG_HIP_LIB pointing at a -DSTEM_ABL=<bits> build (tools/build_rr_variant.sh, SRC=conv16): the ablations that say where its time goes."""
+"""The 16-bit stem kernel (conv16_stem_kernel, tile_cfg 9) alone on the two bench shapes (11 x 512 x 1024 LR batch, 1 x 1024 x 2048 keyframe), us per call."""
 import json
 import os
 import sys

@@ -4,10 +4,6 @@ for every depth-2 loop (the iteration loop of a role) the instructions between c
 
     hipcc --offload-arch=gfx950 -O3 -std=c++17 -I include -S --cuda-device-only ar-seg_amd/csrc/creff_roll.hip -o /tmp/creff_roll.s
     python tools/roll_census.py /tmp/creff_roll.s creff_roll_kernelILi1E
-
-With --marks (listing built with -DROLL_MARK): the instructions between the "; ROLLMARK i" comments the RT(i) sites leave -- every role,
-also where hipcc peeled or unswitched the iteration loop (the LAST copy of a mark sequence 3 -> 0 -> 1 -> 2 -> 3 of a role is its steady-state
-loop body): segment "3->0" = H1, "1->2" = H2.
 """
 import collections
 import re
@@ -23,24 +19,6 @@ def main():
     start = next(i for i, l in enumerate(lines) if l.startswith("_Z") and key in l and ":" in l.split(";")[0])
     end = next(i for i in range(start + 1, len(lines)) if lines[i].strip().startswith(".Lfunc_end"))
     body = lines[start:end]
-    if "--marks" in sys.argv:
-        marks = [(i, int(l.split("ROLLMARK")[1].split()[0])) for i, l in enumerate(body) if "ROLLMARK" in l]
-        for (i0, m0), (i1, m1) in zip(marks, marks[1:]):
-            if (m0, m1) not in ((3, 0), (1, 2)):
-                continue
-            sg = collections.Counter()
-            for l in body[i0:i1]:
-                t = l.strip()
-                if not t or t.startswith((";", ".")) or t.endswith(":"):
-                    continue
-                cls, cost = classify(t.split()[0], t)
-                sg[cls] += 1
-                sg["_cycles"] += cost
-            valu = sum(v for c, v in sg.items() if c.startswith("valu"))
-            print(f"line {start + i0:6d} {'H1' if m0 == 3 else 'H2'}: valu {valu:4d}  mfma {sg['mfma']:3d}  ds_read {sg['ds_read']:3d}  ds_write {sg['ds_write']:3d}  "
-                  f"vmem {sg['vmem_load'] + sg['vmem_store']:3d}  salu {sg['salu']:3d}  issue~{sg['_cycles']:.0f}   " +
-                  " ".join(f"{c[5:]}={v}" for c, v in sorted(sg.items()) if c.startswith("valu_")))
-        return
     # loop headers at depth 2
     heads = [i for i, l in enumerate(body) if "Inner Loop Header: Depth=2" in l]
     for h in heads:
