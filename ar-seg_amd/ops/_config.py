@@ -16,7 +16,6 @@ from .. import _lib
 MATH_NAMES = {"f32": _lib.MATH_F32, "f16x3": _lib.MATH_F16X3, "f16": _lib.MATH_F16}      # "f16": reduced precision (plain fp16 operands)
 _CHOICES = {
     "conv_math": tuple(MATH_NAMES),
-    "conv_find": ("native", "python"),
     "conv_range_guard": ("device", "host", "off"),
     "conv_gemm_x3": (True, False, "wino"),
     "conv_igemm3": (True, False),
@@ -34,7 +33,6 @@ class Config:
     conv_math        [ARSEG_CONV_MATH = f16x3 | f32 | f16]     MFMA back end of the fp32 conv GEMMs (f16x3: hi/lo split, 3 fp16 MFMAs per
                      product; f32: v_mfma_f32_32x32x2_f32; f16: reduced-precision comparison point)
     conv_autotune    [ARSEG_CONV_AUTOTUNE = 1 | 0]              per-shape plans timed on first use (0: the library's tile heuristic)
-    conv_find        [ARSEG_CONV_FIND = native | python]        who times the candidate plans: arseg_conv2d_find or the host loop
     conv_winograd    [ARSEG_CONV_WINOGRAD = 1 | 0]              let the tuner consider Winograd F(4x4,3x3)
     conv_wino_margin [ARSEG_CONV_WINO_MARGIN = f]              Winograd is taken when f x its time (three launches, 6x the HBM bytes of the direct
                                                                conv) is below the best direct plan's, both timed alone: in a step that shares HBM
@@ -42,8 +40,8 @@ class Config:
     conv_up2_taps    [ARSEG_CONV_UP2_TAPS = 1 | 0]              let the tuner consider the tap decomposition for convs after a x2 upsample
     conv_gemm_x3     [ARSEG_CONV_GEMM_X3 = 1 | wino | 0]        let the tuner consider the LDS-DMA GEMM on pre-split operands (csrc/gemm_x3.hip): for
                      the Winograd GEMMs, the 1x1 convs and the PSP bottleneck -> up_1 chain on split rows (1), the Winograd GEMMs only (wino)
-    conv_igemm3      [ARSEG_CONV_IGEMM3 = 1 | 0]                let 3x3 stride-1 convs run as an implicit GEMM of the LDS-DMA kernel on zero-bordered
-                     ("padded") activations: one K step per (tap, 32-channel group), the tap is a row offset of the DMA source
+    conv_igemm3      [ARSEG_CONV_IGEMM3 = 1 | 0]                let the tuner consider the plain GEMM of the LDS-DMA kernel (gemm_rows16) for the 1x1
+                     stride-1 convs of the 16-bit storage path (the name is historical: the implicit-3x3 route it once switched is gone)
     conv_range_guard [ARSEG_CONV_RANGE_GUARD = device | host | 0]   operand range of the f16x3 back end: sticky device word read by
                      ops.range_tripped() (default) / amax + host sync per conv with an immediate fp32 fallback / off
     conv_plan_file   [ARSEG_CONV_PLAN_FILE = <json>]            persist the tuned plans
@@ -59,7 +57,6 @@ class Config:
     (ARSEG_HIP_LIB = <path> selects an alternative library build; it is read by _lib before anything is loaded.)"""
     conv_math: str = "f16x3"
     conv_autotune: bool = True
-    conv_find: str = "native"
     conv_winograd: bool = True
     conv_wino_margin: float = 1.0
     conv_up2_taps: bool = True
@@ -89,8 +86,7 @@ class Config:
                 raise _lib.ArsegError(f"{name}={raw!r} is not a number") from None
 
         c = cls(conv_math=e("ARSEG_CONV_MATH", "f16x3"), conv_autotune=e("ARSEG_CONV_AUTOTUNE", "1") != "0",
-                conv_find=e("ARSEG_CONV_FIND", "native"), conv_winograd=e("ARSEG_CONV_WINOGRAD", "1") != "0",
-                conv_wino_margin=num("ARSEG_CONV_WINO_MARGIN", float, 1.0),
+                conv_winograd=e("ARSEG_CONV_WINOGRAD", "1") != "0", conv_wino_margin=num("ARSEG_CONV_WINO_MARGIN", float, 1.0),
                 conv_up2_taps=e("ARSEG_CONV_UP2_TAPS", "1") != "0", conv_gemm_x3={"0": False, "wino": "wino"}.get(e("ARSEG_CONV_GEMM_X3", "1"), True),
                 conv_igemm3=e("ARSEG_CONV_IGEMM3", "1") != "0",
                 conv_range_guard={"1": "host", "0": "off"}.get(e("ARSEG_CONV_RANGE_GUARD", "device"), e("ARSEG_CONV_RANGE_GUARD", "device")),
@@ -118,7 +114,7 @@ def validate(kw, source="configure"):
 
 class _Switches:
     """What the hot paths read (attribute lookups at call time, so configure() takes effect at once)."""
-    __slots__ = ("AUTOTUNE", "math", "RANGE_MODE", "RANGE_GUARD", "NATIVE_FIND", "WINOGRAD", "UP2_TAPS", "GEMM_X3", "IGEMM3", "PLAN_FILE")
+    __slots__ = ("AUTOTUNE", "math", "RANGE_MODE", "RANGE_GUARD", "WINOGRAD", "UP2_TAPS", "GEMM_X3", "IGEMM3", "PLAN_FILE")
 
 
 config = Config.from_env()
@@ -136,7 +132,7 @@ def _apply_config():
     sw.AUTOTUNE, sw.math = config.conv_autotune, MATH_NAMES[config.conv_math]
     sw.RANGE_MODE = config.conv_range_guard
     sw.RANGE_GUARD = sw.RANGE_MODE == "host"
-    sw.NATIVE_FIND, sw.WINOGRAD, sw.UP2_TAPS = config.conv_find != "python", config.conv_winograd, config.conv_up2_taps
+    sw.WINOGRAD, sw.UP2_TAPS = config.conv_winograd, config.conv_up2_taps
     sw.GEMM_X3, sw.IGEMM3 = config.conv_gemm_x3, config.conv_igemm3
 
 

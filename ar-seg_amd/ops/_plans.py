@@ -1,4 +1,5 @@
-"""Per-shape launch plans (tile shape, LDS buffering, split-K, route): the cache, its optional JSON mirror, and the timing helpers.
+"""Per-shape launch plans (tile shape, LDS buffering, split-K, route): the cache, its optional JSON mirror, and the one tuner (``tuned``)
+every conv route picks its plan with.
 
 The library's built-in heuristic is good to ~10 %; the first time a conv shape is seen on a device the candidates are timed with HIP
 events and the fastest is cached (what MIOpen calls "find").  ARSEG_CONV_AUTOTUNE=0 keeps the heuristic."""
@@ -77,22 +78,46 @@ def _time(fn, reps=6, rounds=2):
     return best
 
 
-def _tune_conv(launch, pc, m, allow_patch=True):
-    ktiles = (pc.R * pc.S * pc.cin_pad + 31) // 32
-    best, best_t = (0, 0), float("inf")
-    patch_ok = allow_patch and (sw.math == _lib.MATH_F16X3 and pc.R == 3 and pc.S == 3 and pc.stride == 1 and pc.pad == pc.dil == 1 and pc.cin_pad % 32 == 0)
-    for cfg, sk in ([(0, 0)] if allow_patch else []) + _conv_candidates(ktiles, pc.cout, m, patch_ok):
+def _capturing() -> bool:
+    """Is a HIP-graph capture running on the current stream?  (Nothing may be timed inside one.)"""
+    return torch.cuda.is_current_stream_capturing()
+
+
+def _fastest(candidates, run, timer, margin=None):
+    """The candidate whose ``timer(lambda: run(plan))`` (x ``margin[plan]``, default 1) is lowest; the first of equals wins.  A candidate
+    that raises ArsegError is skipped; None if none launched."""
+    best, best_t = None, float("inf")
+    for plan in candidates:
         try:
-            launch(cfg, sk, record=False)                          # warm (also sizes the workspace)
-            s, e = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
-            s.record()
-            for _ in range(3):
-                launch(cfg, sk, record=False)
-            e.record()
-            e.synchronize()
-            t = s.elapsed_time(e)
+            t = timer(lambda: run(plan))
         except _lib.ArsegError:
             continue
+        if margin:
+            t *= margin.get(plan, 1.0)
         if t < best_t:
-            best, best_t = (cfg, sk), t
-    return best if best_t < float("inf") else None          # None: no candidate could be launched (nothing to cache)
+            best, best_t = plan, t
+    return best
+
+
+def tuned(key, candidates, run, *, timer=_time, valid=None, untuned=None, margin=None):
+    """The plan of ``key``: the cached one if ``valid`` accepts it (a rejected one -- a route switched off, a plan of an older round -- is
+    re-tuned); ``untuned``, if given, while the tuner is off or a graph capture runs (not cached); else the fastest of ``candidates``
+    launched by ``run(plan)`` (see _fastest), cached.  None if no candidate launched (never cached)."""
+    plan = _conv_plans.get(key)
+    if plan is not None and (valid is None or valid(plan)):
+        return plan
+    if untuned is not None and (not sw.AUTOTUNE or _capturing()):
+        return untuned
+    plan = _fastest(candidates, run, timer, margin)
+    if plan is not None:
+        _conv_plans[key] = plan
+    return plan
+
+
+def _tune_conv(run, pc, m, allow_patch=True):
+    """The fastest (tile_cfg, split_k) of arseg_conv2d_fwd for ``pc`` on an M = ``m`` GEMM, launched by ``run(plan)``; None if none launched.
+    allow_patch=False: the GEMM-tile plans only (the input of a fused x2 upsample is materialised for them)."""
+    ktiles = (pc.R * pc.S * pc.cin_pad + 31) // 32
+    patch_ok = allow_patch and (sw.math == _lib.MATH_F16X3 and pc.R == 3 and pc.S == 3 and pc.stride == 1 and pc.pad == pc.dil == 1 and pc.cin_pad % 32 == 0)
+    return _fastest(([(0, 0)] if allow_patch else []) + _conv_candidates(ktiles, pc.cout, m, patch_ok), run,
+                    lambda f: _time(f, reps=3, rounds=1))

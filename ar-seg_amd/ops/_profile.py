@@ -64,9 +64,10 @@ class profile:
 layer_tag = None      # set by conv2d while it launches on behalf of one layer (profile.layers())
 
 
-def launch(name, fn, *args, flops=0, nbytes=0):
-    """Every ABI call of the host layer goes through here: status check, and HIP events around it while a profile is active."""
-    if current is None or (current.only is not None and name not in current.only):
+def launch(name, fn, *args, flops=0, nbytes=0, record=True):
+    """Every ABI call of the host layer goes through here: status check, and HIP events around it while a profile is active.
+    record=False: the status check only (the launches the plan tuner times)."""
+    if not record or current is None or (current.only is not None and name not in current.only):
         check(fn(*args), name)
         return
     s, e = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)

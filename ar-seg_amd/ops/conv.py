@@ -11,7 +11,7 @@ from .. import _lib
 from .._lib import ConvDesc, check
 from ._base import RANGE_LIMIT, _arm_range_watch, _need_gpu, _need_gpu16, _nhwc_ld, _ptr, _range_word, _stream, is16, workspace
 from ._config import config, set_conv_math, sw
-from ._plans import _PATCH_CFGS, _conv_candidates, _conv_plans, _time, _tune_conv
+from ._plans import _PATCH_CFGS, _tune_conv, tuned
 from ._profile import launch, tagged
 from .layers import psp_prior_sum, resize_nhwc
 
@@ -35,13 +35,6 @@ class SplitRows:
         return (hl[..., 0, :] + hl[..., 1, :]).reshape(n, h, w, c)
 
 
-def igemm3_enabled(x=None) -> bool:
-    """May the 1x1 convs of the 16-bit storage path run as a plain GEMM of the LDS-DMA kernel (gemm_rows16)?  ``ops.config.conv_igemm3``.
-    (The knob's name is historical: rounds 5's implicit-3x3 route on zero-bordered rows -- arseg_conv3x3_rows_fwd / arseg_pad_rows_fwd -- measured
-    parity with the patch-resident kernels on every bench shape, was never selected, and was removed from the tuner and the ABI in round 6.)"""
-    return bool(sw.IGEMM3)
-
-
 _ROWS_CFGS = (0, 1, 2, 3, 4, 5, 6, 7, 8, 9, 10, 11)
 
 
@@ -63,32 +56,15 @@ def gemm_rows16(x: torch.Tensor, pc, residual=None, out: Optional[torch.Tensor] 
         raise _lib.ArsegError("residual shape mismatch")
     flops = 2 * M * cin * cout
 
-    def run(c, rec):
-        args = (_ptr(x), _ptr(w16), _ptr(out), dt, M, cin, cout, _nhwc_ld(out), _ptr(pc.scale), _ptr(pc.bias), _ptr(residual),
-                _nhwc_ld(residual) if residual is not None else 0, pc.act, pc.slope, c, _stream())
-        if rec:
-            launch("conv2d", lib.arseg_gemm_rows16_fwd, *args, flops=flops)
-        else:
-            check(lib.arseg_gemm_rows16_fwd(*args), "gemm_rows16")
+    def run(c, record=True):
+        launch("conv2d", lib.arseg_gemm_rows16_fwd, _ptr(x), _ptr(w16), _ptr(out), dt, M, cin, cout, _nhwc_ld(out), _ptr(pc.scale), _ptr(pc.bias),
+               _ptr(residual), _nhwc_ld(residual) if residual is not None else 0, pc.act, pc.slope, c, _stream(), flops=flops, record=record)
 
     if cfg is None:
         key = ("gemm16", x.device.index, dt, M, cin, cout, residual is not None)
-        cfg = _conv_plans.get(key)
-        if cfg is None:
-            if not sw.AUTOTUNE or torch.cuda.is_current_stream_capturing():
-                cfg = 9 if cout <= 64 else 3
-            else:
-                best_t = float("inf")
-                for c in _ROWS_CFGS:
-                    try:
-                        tm = _time(lambda: run(c, False))
-                    except _lib.ArsegError:
-                        continue
-                    if tm < best_t:
-                        cfg, best_t = c, tm
-                if cfg is None:          #  every tile refused the shape: the caller keeps its other plan; None is never cached
-                    raise _lib.ArsegError(f"gemm_rows16: no tile configuration accepts M={M} K={cin} N={cout}")
-                _conv_plans[key] = cfg
+        cfg = tuned(key, _ROWS_CFGS, lambda c: run(c, False), untuned=9 if cout <= 64 else 3)
+        if cfg is None:          #  every tile refused the shape: the caller keeps its other plan
+            raise _lib.ArsegError(f"gemm_rows16: no tile configuration accepts M={M} K={cin} N={cout}")
     with tagged(lambda: (n, h, w, pc.cin, cout, 1, 1, 1, False, f"gemm16({cfg})", flops)):
         run(cfg, record)
     return out
@@ -129,40 +105,26 @@ def _conv1x1_x3(x, pc, residual=None, out=None, out_split=False, cfg=None, recor
         out = torch.empty((N, H, W, Cout), dtype=torch.float32, device=dev)
     rw = _range_word(dev) if (out_split and sw.RANGE_MODE == "device") else None
 
-    def run(c, rec):
-        args = (_ptr(xs.t), _ptr(pc.w_h3), _ptr(out), M, Cout, Cin, Cout if out_split else _nhwc_ld(out), 1, 0, 0, 0, _ptr(pc.scale_h3), _ptr(pc.bias),
-                _ptr(residual), _nhwc_ld(residual) if residual is not None else 0, pc.act, pc.slope, 1 if out_split else 0, c, _ptr(rw), 65504.0, _stream())
-        if rec:
-            launch("conv2d", lib.arseg_gemm_x3_fwd, *args, flops=2 * M * Cin * Cout)
-        else:
-            check(lib.arseg_gemm_x3_fwd(*args), "gemm_x3")
+    def run(c, record=True):
+        launch("conv2d", lib.arseg_gemm_x3_fwd, _ptr(xs.t), _ptr(pc.w_h3), _ptr(out), M, Cout, Cin, Cout if out_split else _nhwc_ld(out), 1, 0, 0, 0,
+               _ptr(pc.scale_h3), _ptr(pc.bias), _ptr(residual), _nhwc_ld(residual) if residual is not None else 0, pc.act, pc.slope,
+               1 if out_split else 0, c, _ptr(rw), 65504.0, _stream(), flops=2 * M * Cin * Cout, record=record)
 
     if cfg is None:
         key = ("x3", dev.index, M, Cin, Cout, bool(out_split), residual is not None)
-        cfg = _conv_plans.get(key)
+        cfg = tuned(key, range(7), lambda c: run(c, False), untuned=-1)
         if cfg is None:
-            if not sw.AUTOTUNE or torch.cuda.is_current_stream_capturing():
-                # no timing loop inside a graph capture / with the tuner off: the first tile shape the problem admits, un-timed and not cached
-                # (cfg 0 alone raised for a shape it rejects although another tile takes it)
-                for c in range(7):
-                    try:
-                        run(c, record)
-                        return SplitRows(out) if out_split else out
-                    except _lib.ArsegError as err:
-                        last = err
-                raise last
-            else:
-                best_t = float("inf")
-                for c in range(7):
-                    try:
-                        t = _time(lambda: run(c, False))
-                    except _lib.ArsegError:  # a tile shape this problem does not admit
-                        continue
-                    if t < best_t:
-                        cfg, best_t = c, t
-                if cfg is None:
-                    raise _lib.ArsegError(f"gemm_x3: no tile configuration accepts M={M} K={Cin} N={Cout}")
-                _conv_plans[key] = cfg
+            raise _lib.ArsegError(f"gemm_x3: no tile configuration accepts M={M} K={Cin} N={Cout}")
+    if cfg == -1:
+        # un-timed (tuner off / graph capture): the first tile shape the problem admits; the last one raises its own error (cfg 0
+        # alone raised for a shape it rejects although another tile takes it)
+        for c in range(6):
+            try:
+                run(c, record)
+                return SplitRows(out) if out_split else out
+            except _lib.ArsegError:
+                pass
+        cfg = 6
     run(cfg, record)
     return SplitRows(out) if out_split else out
 
@@ -217,35 +179,24 @@ def conv2d(x: torch.Tensor, pc, residual: Optional[torch.Tensor] = None, out: Op
     N, H, W, Cin = x.shape
     if Cin != pc.cin_pad:
         raise _lib.ArsegError(f"conv expects {pc.cin_pad} input channels (padded), got {Cin}")
-    d = ConvDesc()
     in_ld_hi = Cin if x_low is not None else _nhwc_ld(x)
-    d.N, d.H, d.W, d.Cin, d.in_ld = N, H, W, Cin, in_ld_hi
-    d.Cout = pc.cout
-    d.R, d.S, d.stride, d.pad, d.dil = pc.R, pc.S, pc.stride, pc.pad, pc.dil
-    d.act, d.prelu_slope = pc.act, pc.slope
-    d.tile_cfg, d.split_k = tile_cfg, split_k
-    d.math = math = sw.math
-    _arm_range_watch(d, dev)
+    math = sw.math
+    d, out, Ho, Wo = _conv_desc(pc, N, H, W, Cin, in_ld_hi, tile_cfg, split_k, residual, out, torch.float32, dev, math)
     w_dev, scale_dev = (pc.w_h3, pc.scale_h3) if math != _lib.MATH_F32 else (pc.w, pc.scale)
-    d.out_ld, d.res_ld = pc.cout, pc.cout     # provisional, for the shape query
     lib = _lib.load()
-    ho, wo = ctypes.c_int(), ctypes.c_int()
-    check(lib.arseg_conv_out_hw(ctypes.byref(d), ctypes.byref(ho), ctypes.byref(wo)), "conv_out_hw")
-    Ho, Wo = ho.value, wo.value
-    if out is None:
-        out = torch.empty((N, Ho, Wo, pc.cout), dtype=torch.float32, device=dev)
-    elif tuple(out.shape) != (N, Ho, Wo, pc.cout):
-        raise _lib.ArsegError(f"conv out has shape {tuple(out.shape)}, expected {(N, Ho, Wo, pc.cout)}")
-    d.out_ld = _nhwc_ld(out)
-    if residual is not None:
-        if tuple(residual.shape) != (N, Ho, Wo, pc.cout):
-            raise _lib.ArsegError("residual shape mismatch")
-        d.res_ld = _nhwc_ld(residual)
     flops = 2 * N * Ho * Wo * pc.cout * pc.R * pc.S * pc.cin
 
     up_buf = []
 
-    def run_plan(cfg, sk, record=True):
+    def run(plan, record=True):
+        """Launch any plan: a (tile_cfg, split_k) pair of arseg_conv2d_fwd, or the route "wino", "x3" or "taps"."""
+        if plan == "wino":
+            return _conv_wino(x if x_low is None else x_low, pc, residual, out, N, H, W, record, up2=x_low is not None)
+        if plan == "x3":
+            return _conv1x1_x3(x, pc, residual, out, False, None, record)
+        if plan == "taps":
+            return _conv_up2_taps(x_low, pc, out, record)
+        cfg, sk = plan
         xin = x
         d.upsample2x, d.in_ld = 0, in_ld_hi
         if x_low is not None:
@@ -258,24 +209,15 @@ def conv2d(x: torch.Tensor, pc, residual: Optional[torch.Tensor] = None, out: Op
         d.tile_cfg, d.split_k = cfg, sk
         nbytes = lib.arseg_conv2d_workspace_bytes(ctypes.byref(d))
         ws = workspace(nbytes, out.device) if nbytes else None
-        args = (ctypes.byref(d), _ptr(xin), _ptr(w_dev), _ptr(scale_dev), _ptr(pc.bias), _ptr(residual), _ptr(out), _ptr(ws), nbytes, _stream())
-        if record:
-            launch("conv2d", lib.arseg_conv2d_fwd, *args, flops=flops)
-        else:
-            check(lib.arseg_conv2d_fwd(*args), "conv2d")
+        launch("conv2d", lib.arseg_conv2d_fwd, ctypes.byref(d), _ptr(xin), _ptr(w_dev), _ptr(scale_dev), _ptr(pc.bias), _ptr(residual), _ptr(out),
+               _ptr(ws), nbytes, _stream(), flops=flops, record=record)
 
-    def launch_wino(record=True):
-        _conv_wino(x if x_low is None else x_low, pc, residual, out, N, H, W, record, up2=x_low is not None)
-
-    def launch_taps(record=True):
-        _conv_up2_taps(x_low, pc, out, record)
-
-    def launch_x3(record=True):
-        _conv1x1_x3(x, pc, residual, out, False, None, record)
+    def quiet(plan):
+        run(plan, record=False)
 
     def find_native():
         """Plan selection inside the library (arseg_conv2d_find: every candidate timed with HIP events, no Python in the loop).  With a
-        fused upsample only the patch-resident plans qualify; None = nothing launched (the Python tuner then tries the rest)."""
+        fused upsample only the patch-resident plans qualify; None = nothing launched."""
         xin = x
         d.upsample2x, d.in_ld = 0, in_ld_hi
         if x_low is not None:
@@ -290,71 +232,75 @@ def conv2d(x: torch.Tensor, pc, residual: Optional[torch.Tensor] = None, out: Op
             check(st, "conv2d_find")                                # a HIP error is not "no plan": raise it
         return (cfg.value, sk.value) if st == _lib.ARSEG_OK else None
 
-    if tile_cfg == 0 and split_k == 0 and sw.AUTOTUNE:
-        key = (dev.index, N, H, W, Cin, pc.cout, pc.R, pc.S, pc.stride, pc.pad, pc.dil, x_low is not None, math)
-        wino_ok = getattr(pc, "wino_u", None) is not None and sw.WINOGRAD
-        taps_ok = (x_low is not None and sw.UP2_TAPS and residual is None and pc.R == 3 and pc.S == 3 and pc.stride == 1 and pc.pad == 1
-                   and pc.dil == 1 and pc.cout % 4 == 0)
-        x3_ok = _x3_eligible(pc, Cin, residual, x_low is not None) and not wino_ok
-        plan = _conv_plans.get(key)
-        if ((plan == "wino" and not wino_ok) or (plan == "taps" and not taps_ok) or (plan == "x3" and not x3_ok) or plan in ("rows", "tapsf")):      # a persisted plan whose route is switched off / gone: re-tune
-            plan = None
-        if plan is None:
-            plan = find_native() if sw.NATIVE_FIND else None
-            if plan is None:
-                plan = _tune_conv(run_plan, pc, N * Ho * Wo)
-            elif x_low is not None:
-                # with a fused upsample the library times only the patch-resident plans: also time the GEMM-tile plans on the materialised
-                # upsample and keep the faster
-                alt = _tune_conv(run_plan, pc, N * Ho * Wo, allow_patch=False)
-                if alt is not None and _time(lambda: run_plan(*alt, record=False)) < _time(lambda: run_plan(*plan, record=False)):
-                    plan = alt
-            if plan is None:
-                # nothing could be launched.  The one shape-independent cause is the 2 GiB limit of the kernels' 32-bit buffer
-                # offsets on a large batch: split the batch (as creff does) instead of caching a plan that never ran.
-                if N > 1 and x_low is None and max(x.numel(), out.numel()) * 4 >= (1 << 31):
-                    hN = N // 2
-                    conv2d(x[:hN], pc, None if residual is None else residual[:hN], out[:hN])
-                    conv2d(x[hN:], pc, None if residual is None else residual[hN:], out[hN:])
-                    return out
-                run_plan(0, 0)                                    # raises the library's own error
-            if wino_ok:
+    if tile_cfg or split_k or not sw.AUTOTUNE:
+        run((tile_cfg, split_k))
+        return out
+    wino_ok = getattr(pc, "wino_u", None) is not None and sw.WINOGRAD
+    routes = {"wino": wino_ok, "x3": _x3_eligible(pc, Cin, residual, x_low is not None) and not wino_ok,
+              "taps": (x_low is not None and sw.UP2_TAPS and residual is None and pc.R == 3 and pc.S == 3 and pc.stride == 1 and pc.pad == 1
+                       and pc.dil == 1 and pc.cout % 4 == 0)}
+
+    def candidates():
+        """The library's own pick; the host loop where that launched nothing and, with a fused upsample (the library then times only the
+        patch-resident plans), for the GEMM-tile plans on the materialised upsample.  Then each route outside arseg_conv_desc
+        that applies, launched once first (which tunes its own GEMM)."""
+        base = find_native()
+        alt = _tune_conv(quiet, pc, N * Ho * Wo, allow_patch=base is None) if base is None or x_low is not None else None
+        direct = [p for p in (base, alt) if p is not None]
+        if not direct:
+            return
+        yield from direct
+        for name, ok in routes.items():
+            if ok:
                 try:
-                    t_direct = _time(lambda: run_plan(*plan, record=False))
-                    launch_wino(record=False)                   # tunes the batched GEMM underneath
-                    if _time(lambda: launch_wino(record=False)) * float(config.conv_wino_margin) < t_direct:
-                        plan = "wino"
+                    quiet(name)
                 except _lib.ArsegError:
-                    pass                                        # the Winograd route does not cover this shape: keep the direct plan
-            if x3_ok:                                           # split pre-pass + LDS-DMA GEMM against the best implicit-GEMM plan
-                try:
-                    t_direct = _time(lambda: run_plan(*plan, record=False))
-                    launch_x3(record=False)                     # picks its tile shape
-                    if _time(lambda: launch_x3(record=False)) < t_direct:
-                        plan = "x3"
-                except _lib.ArsegError:
-                    pass
-            if taps_ok:
-                try:
-                    t_best = _time((lambda: launch_wino(record=False)) if plan == "wino" else (lambda: run_plan(*plan, record=False)))
-                    launch_taps(record=False)                   # tunes the low-resolution GEMM underneath
-                    if _time(lambda: launch_taps(record=False)) < t_best:
-                        plan = "taps"
-                except _lib.ArsegError:
-                    pass
-            _conv_plans[key] = plan
-        with tagged((N, H, W, pc.cin, pc.cout, pc.R, pc.stride, pc.dil, x_low is not None, str(plan), flops)):
-            if plan == "wino":
-                launch_wino()
-            elif plan == "taps":
-                launch_taps()
-            elif plan == "x3":
-                launch_x3()
-            else:
-                run_plan(*plan)
-    else:
-        run_plan(tile_cfg, split_k)
+                    continue                                    # the route does not cover this shape
+                yield name
+
+    key = (dev.index, N, H, W, Cin, pc.cout, pc.R, pc.S, pc.stride, pc.pad, pc.dil, x_low is not None, math)
+    plan = tuned(key, candidates(), quiet, valid=lambda p: isinstance(p, tuple) or routes.get(p, False), untuned=(0, 0),
+                 margin={"wino": float(config.conv_wino_margin)})
+    if plan is None:
+        # nothing could be launched.  The one shape-independent cause is the 2 GiB limit of the kernels' 32-bit buffer
+        # offsets on a large batch: split the batch (as creff does) instead of caching a plan that never ran.
+        if N > 1 and x_low is None and max(x.numel(), out.numel()) * 4 >= (1 << 31):
+            hN = N // 2
+            conv2d(x[:hN], pc, None if residual is None else residual[:hN], out[:hN])
+            conv2d(x[hN:], pc, None if residual is None else residual[hN:], out[hN:])
+            return out
+        plan = (0, 0)                                           # raises the library's own error
+    with tagged((N, H, W, pc.cin, pc.cout, pc.R, pc.stride, pc.dil, x_low is not None, str(plan), flops)):
+        run(plan)
     return out
+
+
+def _conv_desc(pc, N, H, W, Cin, in_ld, tile_cfg, split_k, residual, out, dtype, device, math=_lib.MATH_F32):
+    """arseg_conv_desc of ``pc`` on an [N, H, W, Cin] input of row pitch ``in_ld``, and its output tensor: ``out`` (shape checked) or a new one
+    of ``dtype`` (16-bit: row pitch padded to 8 channels) -> (desc, out, Ho, Wo)."""
+    d = ConvDesc()
+    d.N, d.H, d.W, d.Cin, d.in_ld = N, H, W, Cin, in_ld
+    d.Cout = pc.cout
+    d.R, d.S, d.stride, d.pad, d.dil = pc.R, pc.S, pc.stride, pc.pad, pc.dil
+    d.act, d.prelu_slope = pc.act, pc.slope
+    d.tile_cfg, d.split_k = tile_cfg, split_k
+    d.math = math
+    _arm_range_watch(d, device)
+    d.out_ld, d.res_ld = pc.cout, pc.cout     # provisional, for the shape query
+    ho, wo = ctypes.c_int(), ctypes.c_int()
+    check(_lib.load().arseg_conv_out_hw(ctypes.byref(d), ctypes.byref(ho), ctypes.byref(wo)), "conv_out_hw")
+    Ho, Wo = ho.value, wo.value
+    if out is None:
+        ld = pc.cout if dtype == torch.float32 else (pc.cout + 7) // 8 * 8
+        out = torch.empty((N, Ho, Wo, ld), dtype=dtype, device=device)[..., :pc.cout]
+    elif tuple(out.shape) != (N, Ho, Wo, pc.cout):
+        raise _lib.ArsegError(f"conv out has shape {tuple(out.shape)}, expected {(N, Ho, Wo, pc.cout)}")
+    d.out_ld = _nhwc_ld(out)
+    if residual is not None:
+        if tuple(residual.shape) != (N, Ho, Wo, pc.cout):
+            raise _lib.ArsegError("residual shape mismatch")
+        d.res_ld = _nhwc_ld(residual)
+    return d, out, Ho, Wo
 
 
 def _desc16(x, pc, residual, out, tile_cfg, split_k, up2=False):
@@ -365,28 +311,8 @@ def _desc16(x, pc, residual, out, tile_cfg, split_k, up2=False):
     w16, cin_pad = pc.weights16(x.dtype)
     if Cin != cin_pad:
         raise _lib.ArsegError(f"conv (16-bit) expects {cin_pad} input channels (padded to 8), got {Cin}")
-    d = ConvDesc()
-    d.N, d.H, d.W, d.Cin, d.in_ld = N, H, W, Cin, _nhwc_ld(x)
-    d.Cout = pc.cout
-    d.R, d.S, d.stride, d.pad, d.dil = pc.R, pc.S, pc.stride, pc.pad, pc.dil
-    d.act, d.prelu_slope = pc.act, pc.slope
-    d.tile_cfg = tile_cfg
-    d.out_ld, d.res_ld = pc.cout, pc.cout
-    ho, wo = ctypes.c_int(), ctypes.c_int()
-    check(_lib.load().arseg_conv_out_hw(ctypes.byref(d), ctypes.byref(ho), ctypes.byref(wo)), "conv_out_hw")
-    Ho, Wo = ho.value, wo.value
-    d.upsample2x = 1 if up2 else 0          # (set after the size query: arseg_conv_out_hw checks the fp32 engine's plans)
-    cout_ld = (pc.cout + 7) // 8 * 8
-    if out is None:
-        out = torch.empty((N, Ho, Wo, cout_ld), dtype=x.dtype, device=x.device)[..., :pc.cout]
-    elif tuple(out.shape) != (N, Ho, Wo, pc.cout):
-        raise _lib.ArsegError(f"conv out has shape {tuple(out.shape)}, expected {(N, Ho, Wo, pc.cout)}")
-    d.out_ld = _nhwc_ld(out)
-    if residual is not None:
-        if tuple(residual.shape) != (N, Ho, Wo, pc.cout):
-            raise _lib.ArsegError("residual shape mismatch")
-        d.res_ld = _nhwc_ld(residual)
-    d.split_k = split_k
+    d, out, Ho, Wo = _conv_desc(pc, N, H, W, Cin, _nhwc_ld(x), tile_cfg, 0, residual, out, x.dtype, x.device)
+    d.upsample2x, d.split_k = (1 if up2 else 0), split_k          # (set after the size query: arseg_conv_out_hw checks the fp32 engine's plans)
     return d, out, N, H, W, Ho, Wo
 
 
@@ -419,26 +345,21 @@ def _conv2d16_up2(x_low, pc, residual, out, tile_cfg, split_k):
         return (ctypes.byref(d), dt, _ptr(x_low), _ptr(w16), _ptr(pc.scale), _ptr(pc.bias), _ptr(residual), _ptr(out), None, 0, _stream())
 
     if tile_cfg == 0 and sw.AUTOTUNE:
+        def quiet(plan):
+            if plan == "resize":
+                return materialised(out)
+            d.tile_cfg = plan[0]
+            check(lib.arseg_conv2d16_fwd(*args()), "conv2d16")
+
+        def candidates():
+            yield from ((cfg, 0) for cfg in _PATCH16_CFGS if not (cfg in (6, 8, 12) and pc.cout <= 64))
+            materialised(out)                                                  # (tunes the materialised conv's own plan first)
+            yield "resize"
+
         # the plan key of the materialised conv of the same shape plus an "up2" marker: keys without it keep their meaning
         key = ("conv16", x_low.device.index, dt, N, H, W, x_low.shape[3], pc.cout, pc.R, pc.S, pc.stride, pc.pad, pc.dil, "up2")
-        plan = _conv_plans.get(key)
-        if plan is None:
-            plan, best_t = "resize", float("inf")
-            for cfg in _PATCH16_CFGS:
-                if cfg in (6, 8, 12) and pc.cout <= 64:
-                    continue
-                d.tile_cfg = cfg
-                try:
-                    t = _time(lambda: check(lib.arseg_conv2d16_fwd(*args()), "conv2d16"))
-                except _lib.ArsegError:
-                    continue
-                if t < best_t:
-                    plan, best_t = (cfg, 0), t
-            materialised(out)                                                  # (tunes the materialised conv's own plan first)
-            if _time(lambda: materialised(out)) < best_t:
-                plan = "resize"
-            _conv_plans[key] = plan
-        if plan == "resize" or not isinstance(plan, (tuple, list)):
+        plan = tuned(key, candidates(), quiet, valid=lambda p: p == "resize" or isinstance(p, tuple))
+        if plan in (None, "resize"):
             return materialised(out)
         d.tile_cfg = plan[0]
     flops16 = 2 * N * Ho * Wo * pc.cout * pc.R * pc.S * pc.cin
@@ -463,10 +384,13 @@ def _conv2d16(x, pc, residual, out, up2, tile_cfg=0, split_k=0):
         return (ctypes.byref(d), dt, _ptr(x), _ptr(w16), _ptr(pc.scale), _ptr(pc.bias), _ptr(residual), _ptr(out), _ptr(ws), nbytes, _stream())
 
     if tile_cfg == 0 and split_k == 0 and sw.AUTOTUNE:      # per-shape plan: tile / K-step variants x split-K timed once on the device
-        key = ("conv16", x.device.index, dt, N, H, W, Cin, pc.cout, pc.R, pc.S, pc.stride, pc.pad, pc.dil)
-        plan = _conv_plans.get(key)
-        if plan is None:
-            best_t = float("inf")
+        def quiet(plan):
+            if plan == "gemm16":
+                return gemm_rows16(x, pc, residual, out, record=False)
+            d.tile_cfg, d.split_k = plan
+            check(lib.arseg_conv2d16_fwd(*args()), "conv2d16")
+
+        def candidates():
             ktiles = (pc.R * pc.S * Cin + 63) // 64
             # 5..8, 10..13: patch-resident 3x3 plans (10..13: squarer pixel tiles, r6), 9: the 7x7 stem kernel (EUNSUPPORTED for other shapes)
             for cfg in (0, 1, 2, 3, 4, 5, 6, 7, 8, 9, 10, 11, 12, 13):
@@ -475,28 +399,20 @@ def _conv2d16(x, pc, residual, out, up2, tile_cfg=0, split_k=0):
                         continue
                     if cfg >= 5 and (sk == 1 or (cfg in (6, 8, 12) and pc.cout <= 64)):
                         continue
-                    d.tile_cfg, d.split_k = cfg, sk
-                    try:
-                        t = _time(lambda: check(lib.arseg_conv2d16_fwd(*args()), "conv2d16"))
-                    except _lib.ArsegError:
-                        continue
-                    if t < best_t:
-                        plan, best_t = (cfg, sk), t
-            plan = plan or (0, 0)
-            if igemm3_enabled(x) and pc.R == 1 and pc.S == 1 and pc.stride == 1 and pc.pad == 0 and Cin % 64 == 0 and pc.cout % 4 == 0 and d.in_ld == Cin:
+                    yield cfg, sk
+            if sw.IGEMM3 and pc.R == 1 and pc.S == 1 and pc.stride == 1 and pc.pad == 0 and Cin % 64 == 0 and pc.cout % 4 == 0 and d.in_ld == Cin:
                 try:                                                                       # 1x1: the plain GEMM of the LDS-DMA kernel
-                    gemm_rows16(x, pc, residual, out, record=False)
-                    if _time(lambda: gemm_rows16(x, pc, residual, out, record=False)) < best_t:
-                        plan = "gemm16"
+                    gemm_rows16(x, pc, residual, out, record=False)                         # (tunes its tile shape first)
                 except _lib.ArsegError:
-                    pass
-            _conv_plans[key] = plan
+                    return
+                yield "gemm16"
+
+        key = ("conv16", x.device.index, dt, N, H, W, Cin, pc.cout, pc.R, pc.S, pc.stride, pc.pad, pc.dil)
+        plan = tuned(key, candidates(), quiet, valid=lambda p: isinstance(p, tuple) or p == "gemm16", untuned=(0, 0)) or (0, 0)
         #  the plan key holds the shape, not the alignment / row pitch of `out` and `residual`: a later call with a channel-slice
         # view the LDS-DMA kernel refuses (EINVAL) falls back to the library's heuristic instead of raising
-        if plan == "rows":                     # (a plan file of round 5: the route is gone)
-            plan = (0, 0)
         if plan == "gemm16":
-            if igemm3_enabled(x) and d.in_ld == Cin:
+            if sw.IGEMM3 and d.in_ld == Cin:
                 try:
                     return gemm_rows16(x, pc, residual, out)
                 except _lib.ArsegError:
@@ -519,7 +435,6 @@ def _conv_wino(x, pc, residual, out, N, H, W, record=True, up2=False):
     T = lib.arseg_wino43_tiles(N, H, W, dil)
     V = torch.empty((36, T, Cin), dtype=torch.float32, device=x.device)
     M = torch.empty((36, T, Cout), dtype=torch.float32, device=x.device)
-    la = launch if record else (lambda name, fn, *a, **k: check(fn(*a), name))
     # under f16x3 the transformed activations are stored scaled by 2^-4 (exact; undone in the output transform): B^T d B amplifies by up to
     # 100, and unscaled the split-fp16 operand range would be left for |x| >~ 1.3e3
     vs = 2.0 ** -4 if sw.math == _lib.MATH_F16X3 else 1.0
@@ -533,57 +448,41 @@ def _conv_wino(x, pc, residual, out, N, H, W, record=True, up2=False):
     _arm_range_watch(d, x.device)          # the batched GEMM watches the transformed activations it multiplies
     u_dev, scale_dev = (pc.wino_u_h3, pc.wino_scale_h3) if math != _lib.MATH_F32 else (pc.wino_u, pc.scale)
     x3_ok = bool(sw.GEMM_X3) and math == _lib.MATH_F16X3 and Cin % 32 == 0 and Cout % 4 == 0
-    key = ("wino_gemm", x.device.index, T, Cin, Cout, math)
-    plan = _conv_plans.get(key)
-    if plan is not None and plan >= 100 and not x3_ok:
-        plan = None
 
-    def transform(split, la_):
+    def transform(split, record=True):
         if split:      # the transform is the last place that sees the GEMM's fp32 operands: it carries the range watch
-            la_("wino_input", lib.arseg_wino43_input_split_fwd, _ptr(x), _nhwc_ld(x), _ptr(V), N, H, W, Cin, dil, 1 if up2 else 0, vs,
-                ctypes.c_void_p(d.range_flag), 65504.0, _stream())
+            launch("wino_input", lib.arseg_wino43_input_split_fwd, _ptr(x), _nhwc_ld(x), _ptr(V), N, H, W, Cin, dil, 1 if up2 else 0, vs,
+                   ctypes.c_void_p(d.range_flag), 65504.0, _stream(), record=record)
         else:
-            la_("wino_input", lib.arseg_wino43_input_fwd, _ptr(x), _nhwc_ld(x), _ptr(V), N, H, W, Cin, dil, 1 if up2 else 0, vs, _stream())
+            launch("wino_input", lib.arseg_wino43_input_fwd, _ptr(x), _nhwc_ld(x), _ptr(V), N, H, W, Cin, dil, 1 if up2 else 0, vs, _stream(),
+                   record=record)
 
-    def gemm(cfg, rec):
+    def gemm(cfg, record=True):
         if cfg >= 100:
             fn, args = lib.arseg_gemm_x3_fwd, (_ptr(V), _ptr(u_dev), _ptr(M), T, Cout, Cin, Cout, 36, T * Cin * 4, Cout * Cin * 4, T * Cout,
                                                _ptr(None), _ptr(None), _ptr(None), 0, _lib.ACT_NONE, 0.0, 0, cfg - 100, _ptr(None), 0.0, _stream())
         else:
             d.tile_cfg, d.split_k = cfg, 1
             fn, args = lib.arseg_conv2d_fwd, (ctypes.byref(d), _ptr(V), _ptr(u_dev), _ptr(None), _ptr(None), _ptr(None), _ptr(M), _ptr(None), 0, _stream())
-        if rec:
-            launch("conv2d", fn, *args, flops=2 * 36 * T * Cin * Cout)
-        else:
-            check(fn(*args), "conv2d(batched)")
+        launch("conv2d", fn, *args, flops=2 * 36 * T * Cin * Cout, record=record)
 
-    if plan is None:
-        quiet = lambda name, fn, *a, **k: check(fn(*a), name)      # noqa: E731
-        best, best_t = 0, float("inf")
-        transform(False, quiet)
+    def candidates():
+        transform(False, record=False)
         for cfg in (0, 5, 6, 7, 8, 9, 10, 11, 12) + ((17, 18, 19) if math == _lib.MATH_F16X3 else ()):
-            if cfg in (5, 8, 9, 12, 17, 18, 19) and Cout <= 64:
-                continue
-            if cfg in (18, 19) and Cout <= 128:
-                continue
-            t = _time(lambda: gemm(cfg, False))
-            if t < best_t:
-                best, best_t = cfg, t
+            if not ((cfg in (5, 8, 9, 12, 17, 18, 19) and Cout <= 64) or (cfg in (18, 19) and Cout <= 128)):
+                yield cfg
         if x3_ok:
-            transform(True, quiet)
-            for cfg in range(100, 107):
-                t = _time(lambda: gemm(cfg, False))
-                if t < best_t:
-                    best, best_t = cfg, t
-        plan = _conv_plans[key] = best
-    transform(plan >= 100, la)
+            transform(True, record=False)
+            yield from range(100, 107)
+
+    plan = tuned(("wino_gemm", x.device.index, T, Cin, Cout, math), candidates(), lambda c: gemm(c, False), valid=lambda p: p < 100 or x3_ok)
+    if plan is None:
+        raise _lib.ArsegError(f"wino: no batched GEMM configuration accepts T={T} K={Cin} N={Cout}")
+    transform(plan >= 100, record)
     gemm(plan, record)
-    la("wino_output", lib.arseg_wino43_output_fwd, _ptr(M), _ptr(scale_dev), _ptr(pc.bias), _ptr(residual),
-       _nhwc_ld(residual) if residual is not None else 0, _ptr(out), _nhwc_ld(out), N, H, W, Cout, dil, pc.act, pc.slope, 1.0 / vs, _stream())
-
-
-sw.UP2_TAPS = config.conv_up2_taps
-sw.GEMM_X3 = config.conv_gemm_x3
+    launch("wino_output", lib.arseg_wino43_output_fwd, _ptr(M), _ptr(scale_dev), _ptr(pc.bias), _ptr(residual),
+           _nhwc_ld(residual) if residual is not None else 0, _ptr(out), _nhwc_ld(out), N, H, W, Cout, dil, pc.act, pc.slope, 1.0 / vs, _stream(),
+           record=record)
 
 
 def _conv_up2_taps(x_low, pc, out, record=True, out_split=False):
@@ -595,15 +494,11 @@ def _conv_up2_taps(x_low, pc, out, record=True, out_split=False):
     z = conv2d(x_low, pc.taps())
     if out_split:
         rw = _range_word(out.device) if sw.RANGE_MODE == "device" else None
-        fn, name = lib.arseg_upconv3x3_tap_gather_split_fwd, "up2_tap_gather"
-        args = (_ptr(z), 9 * pc.cout, _ptr(pc.scale), _ptr(pc.bias), _ptr(out), n, h, w, pc.cout, pc.act, pc.slope, _ptr(rw), 65504.0, _stream())
+        launch("up2_tap_gather", lib.arseg_upconv3x3_tap_gather_split_fwd, _ptr(z), 9 * pc.cout, _ptr(pc.scale), _ptr(pc.bias), _ptr(out), n, h, w,
+               pc.cout, pc.act, pc.slope, _ptr(rw), 65504.0, _stream(), record=record)
     else:
-        fn, name = lib.arseg_upconv3x3_tap_gather_fwd, "up2_tap_gather"
-        args = (_ptr(z), 9 * pc.cout, _ptr(pc.scale), _ptr(pc.bias), _ptr(out), _nhwc_ld(out), n, h, w, pc.cout, pc.act, pc.slope, _stream())
-    if record:
-        launch(name, fn, *args)
-    else:
-        check(fn(*args), name)
+        launch("up2_tap_gather", lib.arseg_upconv3x3_tap_gather_fwd, _ptr(z), 9 * pc.cout, _ptr(pc.scale), _ptr(pc.bias), _ptr(out), _nhwc_ld(out),
+               n, h, w, pc.cout, pc.act, pc.slope, _stream(), record=record)
 
 
 _psp_interp = {}
@@ -648,23 +543,14 @@ def psp_bottleneck_x3(feats: torch.Tensor, t: torch.Tensor, pc, sizes, out_split
     out = torch.empty((N, H, W, Cout), dtype=torch.float32, device=dev)
     rw = _range_word(dev) if (out_split and sw.RANGE_MODE == "device") else None
 
-    def run(c, rec):
-        args = (_ptr(xs.t), _ptr(pc.w_h3), _ptr(B.t), _ptr(w2s.t), _ptr(out), H * W, Cout, C, 64, Cout, N, H * W * C * 4, 0, 0, Cout * 64 * 4, H * W * Cout,
-                _ptr(pc.scale_h3), _ptr(pc.bias), pc.act, pc.slope, 1 if out_split else 0, c, _ptr(rw), 65504.0, _stream())
-        if rec:
-            launch("conv2d", lib.arseg_gemm_x3_cat_fwd, *args, flops=2 * N * H * W * (C + 64) * Cout)
-        else:
-            check(lib.arseg_gemm_x3_cat_fwd(*args), "gemm_x3_cat")
+    def run(c, record=True):
+        launch("conv2d", lib.arseg_gemm_x3_cat_fwd, _ptr(xs.t), _ptr(pc.w_h3), _ptr(B.t), _ptr(w2s.t), _ptr(out), H * W, Cout, C, 64, Cout, N,
+               H * W * C * 4, 0, 0, Cout * 64 * 4, H * W * Cout, _ptr(pc.scale_h3), _ptr(pc.bias), pc.act, pc.slope, 1 if out_split else 0, c, _ptr(rw),
+               65504.0, _stream(), flops=2 * N * H * W * (C + 64) * Cout, record=record)
 
-    pkey = ("x3cat", dev.index, N, H * W, C, Cout, bool(out_split))
-    cfg = _conv_plans.get(pkey)
+    cfg = tuned(("x3cat", dev.index, N, H * W, C, Cout, bool(out_split)), range(7), lambda c: run(c, False))
     if cfg is None:
-        best_t = float("inf")
-        for c in range(7):
-            tm = _time(lambda: run(c, False))
-            if tm < best_t:
-                cfg, best_t = c, tm
-        _conv_plans[pkey] = cfg
+        raise _lib.ArsegError(f"gemm_x3_cat: no tile configuration accepts M={H * W} K={C + 64} N={Cout}")
     with tagged((N, H, W, C, Cout, 1, 1, 1, False, "x3(cat, split out)", 2 * N * H * W * C * Cout)):
         run(cfg, True)
     return SplitRows(out) if out_split else out

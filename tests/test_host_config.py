@@ -3,15 +3,19 @@ CPU only -- nothing here touches the library."""
 import pytest
 
 
-def test_config_from_env(monkeypatch):
-    from arseg_amd import ops
+def test_config_env_defaults(monkeypatch):
+    from arseg_amd import _lib, ops
 
     for k in list(__import__("os").environ):
         if k.startswith("ARSEG_"):
             monkeypatch.delenv(k)
     d = ops.Config.from_env()
-    assert (d.conv_math, d.conv_autotune, d.conv_find, d.conv_winograd, d.conv_up2_taps, d.conv_range_guard) == ("f16x3", True, "native", True, True, "device")
+    assert (d.conv_math, d.conv_autotune, d.conv_winograd, d.conv_up2_taps, d.conv_range_guard) == ("f16x3", True, True, True, "device")
     assert d.conv_plan_file is None and d.creff_impl == "" and d.creff_tile_rows == 0 and d.lr_subbatch == 0
+    monkeypatch.setenv("ARSEG_CONV_FIND", "python")              # the removed conv_find knob: its variable is no longer read
+    assert not hasattr(ops.Config.from_env(), "conv_find")
+    with pytest.raises(_lib.ArsegError):
+        ops.configure(conv_find="python")
     monkeypatch.setenv("ARSEG_CONV_MATH", "f32")
     monkeypatch.setenv("ARSEG_CONV_AUTOTUNE", "0")
     monkeypatch.setenv("ARSEG_CONV_RANGE_GUARD", "1")          # the round-2 spelling of the host-synchronising mode
