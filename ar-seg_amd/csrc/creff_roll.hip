@@ -35,6 +35,7 @@
 namespace {
 
 typedef _Float16 h16x8 __attribute__((ext_vector_type(8)));
+typedef _Float16 h16x4 __attribute__((ext_vector_type(4)));
 typedef short s16x4 __attribute__((ext_vector_type(4)));
 typedef unsigned u32x2 __attribute__((ext_vector_type(2)));
 typedef unsigned u32x4 __attribute__((ext_vector_type(4)));
@@ -84,14 +85,50 @@ constexpr float LOG2E = 1.44269504088896340736f;
 __device__ __forceinline__ int kslot(int r) { return r & 7; }
 
 struct RollParams {
-    const float *ref[MAXN];       // un-warped keyframe feature of each frame, NHWC [Hp][Wp][64]
+    const void *ref[MAXN];        // un-warped keyframe feature of each frame, NHWC [Hp][Wp][64], in the kernel's input element type DT
     const int16_t *mv;            // [N][H][W][2] quarter-pel
-    const float *lr, *wq, *bq, *wk, *bk, *wv, *bv, *wf, *bf;
+    const void *lr;               // [N][hp][wp][64], element type DT
+    const float *wq, *bq, *wk, *bk, *wv, *bv, *wf, *bf;
     float *p_out, *logits;
     int N, Hp, Wp, hp, wp, H, W, n_cls, log_softmax, p_layout, nstrips, nseg, seg_rows, balanced;
     unsigned p_bytes, l_bytes, lr_bytes, ref_bytes;      // of ONE frame: every frame has its own buffer descriptor
     float sy, sx;
 };
+
+// Input element type DT of the keyframe and LR features (enum arseg_dtype): a producer unit is 4 channels of one pixel -- 16 bytes of fp32,
+// 8 bytes of fp16 / bf16, widened to fp32 in registers.  Both widenings are exact, so every value behind a load is the float the fp32
+// instantiation reads from a tensor cast ahead of the launch: the 16-bit instantiations reproduce that path bit for bit.
+template <int DT> constexpr unsigned ESZ = DT == ARSEG_DT_F32 ? 4u : 2u;
+template <int DT>
+__device__ __forceinline__ f32x4 load_unit(const __amdgpu_buffer_rsrc_t rsrc, const unsigned off) {
+    if constexpr (DT == ARSEG_DT_F32) {
+        return __builtin_bit_cast(f32x4, __builtin_amdgcn_raw_buffer_load_b128(rsrc, off, 0, 0));
+    } else {
+        const u32x2 r = __builtin_bit_cast(u32x2, __builtin_amdgcn_raw_buffer_load_b64(rsrc, off, 0, 0));
+        if constexpr (DT == ARSEG_DT_BF16) {      // bf16 is the upper half of the fp32 pattern: a shift / a mask per value
+            return f32x4{__uint_as_float(r.x << 16), __uint_as_float(r.x & 0xFFFF0000u), __uint_as_float(r.y << 16), __uint_as_float(r.y & 0xFFFF0000u)};
+        } else {
+            const h16x4 h = __builtin_bit_cast(h16x4, r);
+            return f32x4{(float)h[0], (float)h[1], (float)h[2], (float)h[3]};
+        }
+    }
+}
+
+// Bilinear interpolation of the four lr taps of an lr_up unit.  The fp32 instantiation keeps the expression hipcc has always compiled: it
+// contracts the sum of the two row terms as fma(wy1, B, wy0 A).  Behind the widening of a 16-bit instantiation hipcc contracts the same text
+// as fma(wy0, A, wy1 B) -- a last-bit difference wherever the row weights are not powers of two (measured: bit-equal at lr ratios with
+// sy = 1/2 or 1, a few ulp off at 23/47) -- so there the fp32 form of the row sum is written out.  The column sums A, B stay expressions:
+// hipcc contracts them as in the fp32 instantiation (tests/test_gpu_creff16.py holds both to bit equality with the fp32 kernel).
+template <int DT>
+__device__ __forceinline__ f32x4 lr_interp(const float wy0, const float wy1, const float wx0, const float wx1, const f32x4 (&v)[4]) {
+    if constexpr (DT == ARSEG_DT_F32) {
+        return wy0 * (wx0 * v[0] + wx1 * v[1]) + wy1 * (wx0 * v[2] + wx1 * v[3]);
+    } else {
+        const f32x4 y1 = {wy1, wy1, wy1, wy1};
+        const f32x4 a = wx0 * v[0] + wx1 * v[1], b = wx0 * v[2] + wx1 * v[3];
+        return __builtin_elementwise_fma(y1, b, wy0 * a);
+    }
+}
 
 // fp32 -> two fp16 in the record form {4 hi | 4 lo} (arseg_split_f16).  Writing the lo halves by v_fma_mixlo / mixhi_f16 (6 instead of
 // 8 instructions per 4 values) measured 2 % slower (5685 vs 5572 cycles per step).
@@ -443,9 +480,10 @@ __device__ __forceinline__ void consumer(const RollParams &p, const Smem &sm, co
 // H2(j-2)  ->  the four taps requested in H1(j-1), in flight for a whole iteration (the first touch of a keyframe row comes from HBM)  ->
 // blended and staged in H1(j)  ->  consumed by the convs in H2(j).
 enum { ROLE_KV = 0, ROLE_Q = 1, ROLE_AUX = 2 };
-template <int ROLE>
+template <int ROLE, int DT>
 __device__ __forceinline__ void producer(const RollParams &p, const Smem &sm, const PieceTab *sc, const int tid, const int wave) {
     const int Hp = p.Hp, Wp = p.Wp;
+    constexpr unsigned ES = ESZ<DT>, UB = 4u * ES, PXB = CH * ES;      // bytes of an element, of a unit (4 channels), of a pixel
     const int pl = tid - 64 * NCONS;                   // 0 .. 767
     const int gpx = pl >> 4, gcg = pl & 15;            // gather unit: staged warp pixel (row gpx / 24, column gpx % 24), channel group
     const int grr = gpx >= GW ? 1 : 0, gcc = gpx - GW * grr;
@@ -472,9 +510,9 @@ __device__ __forceinline__ void producer(const RollParams &p, const Smem &sm, co
         const int n = __builtin_amdgcn_readfirstlane(pe.x), strip = __builtin_amdgcn_readfirstlane(pe.y);
         const int ys = __builtin_amdgcn_readfirstlane(pe.z), S = __builtin_amdgcn_readfirstlane(pe.w);
         const int x0 = strip * SW;
-        const __amdgpu_buffer_rsrc_t g_rsrc = __builtin_amdgcn_make_buffer_rsrc(const_cast<float *>(p.ref[n]), 0, (int)p.ref_bytes, 0x00020000);
-        const __amdgpu_buffer_rsrc_t lr_rsrc = __builtin_amdgcn_make_buffer_rsrc(const_cast<float *>(p.lr) + (size_t)n * (size_t)(p.hp * p.wp) * CH, 0, (int)p.lr_bytes, 0x00020000);
-        const unsigned lr_img = 16u * gcg;           // (the frame is in the descriptor's base)
+        const __amdgpu_buffer_rsrc_t g_rsrc = __builtin_amdgcn_make_buffer_rsrc(const_cast<void *>(p.ref[n]), 0, (int)p.ref_bytes, 0x00020000);
+        const __amdgpu_buffer_rsrc_t lr_rsrc = __builtin_amdgcn_make_buffer_rsrc(const_cast<unsigned char *>(static_cast<const unsigned char *>(p.lr)) + (size_t)n * (size_t)(p.hp * p.wp) * PXB, 0, (int)p.lr_bytes, 0x00020000);
+        const unsigned lr_img = UB * gcg;            // (the frame is in the descriptor's base)
         const bool x_inner = x0 >= 3 && x0 + SW + 3 <= Wp;      // every record column of the strip inside the image
         // lr_up column taps of this lane's units: the same for every row of the strip
         bool l_lane[NLU > 0 ? NLU : 1];
@@ -492,7 +530,7 @@ __device__ __forceinline__ void producer(const RollParams &p, const Smem &sm, co
             m = fminf(fmaxf(m, 0.f), 1.f);
             const float inx = (unsigned)gx < (unsigned)Wp ? 1.f : 0.f;
             lwx0[i] = (1.f - m) * inx; lwx1[i] = m * inx;
-            lx0[i] = (unsigned)j0 * (CH * 4u); lx1[i] = (unsigned)j1 * (CH * 4u);
+            lx0[i] = (unsigned)j0 * PXB; lx1[i] = (unsigned)j1 * PXB;
             if (!l_lane[i]) { lx0[i] = OOB - lr_img; lx1[i] = OOB - lr_img; }      // (wave 13: no unit -- with the row offset still beyond the buffer)
         }
         // ROLE_KV: the four warp rows under the two record rows being produced (rows 0, 1: the window; 2, 3: staged this iteration);
@@ -516,7 +554,7 @@ __device__ __forceinline__ void producer(const RollParams &p, const Smem &sm, co
             // waves' rises 2380 -> 3280 -- a SIMD's H1 is issue-bound)
             if (ROLE == ROLE_KV) {      // two of the four gather taps travel under the value conv (all four: 16 more registers than the conv leaves)
 #pragma unroll
-                for (int k = 0; k < 2; ++k) gv[k] = __builtin_bit_cast(f32x4, __builtin_amdgcn_raw_buffer_load_b128(g_rsrc, go[k] + 16u * gcg, 0, 0));
+                for (int k = 0; k < 2; ++k) gv[k] = load_unit<DT>(g_rsrc, go[k] + UB * gcg);
             }
             if (ROLE == ROLE_KV) {
                 // ---- value records of rows rho = 2k, 2k + 1 (k = t - 2) from the four warp rows the key conv of H2(t-1) used (weights requested at
@@ -545,7 +583,7 @@ __device__ __forceinline__ void producer(const RollParams &p, const Smem &sm, co
             const bool g_on = t >= 0 && t <= S + 3;
 #pragma unroll
             for (int k = ROLE == ROLE_KV ? 2 : 0; k < 4; ++k)      // (outside [0, S+3] the offsets are stale but valid: the values are not used)
-                gv[k] = __builtin_bit_cast(f32x4, __builtin_amdgcn_raw_buffer_load_b128(g_rsrc, go[k] + 16u * gcg, 0, 0));
+                gv[k] = load_unit<DT>(g_rsrc, go[k] + UB * gcg);
             // ---- lr_up rows ys + 2t - 7, ys + 2t - 6 (+1 halo column each side): the bilinear taps (lines touched by wave 12 in H2(t-2))
             const bool l_on = t >= 3 && t <= S + 3;
             f32x4 lv[NLU > 0 ? NLU : 1][4];
@@ -561,11 +599,11 @@ __device__ __forceinline__ void producer(const RollParams &p, const Smem &sm, co
                     l = fminf(fmaxf(l, 0.f), 1.f);
                     const float iny = (unsigned)gy < (unsigned)Hp ? 1.f : 0.f;
                     lwy0[i] = (1.f - l) * iny; lwy1[i] = l * iny;
-                    const unsigned r0 = lr_img + (unsigned)(i0 * p.wp) * (CH * 4u), r1 = lr_img + (unsigned)(i1 * p.wp) * (CH * 4u);
-                    lv[i][0] = __builtin_bit_cast(f32x4, __builtin_amdgcn_raw_buffer_load_b128(lr_rsrc, r0 + lx0[i], 0, 0));
-                    lv[i][1] = __builtin_bit_cast(f32x4, __builtin_amdgcn_raw_buffer_load_b128(lr_rsrc, r0 + lx1[i], 0, 0));
-                    lv[i][2] = __builtin_bit_cast(f32x4, __builtin_amdgcn_raw_buffer_load_b128(lr_rsrc, r1 + lx0[i], 0, 0));
-                    lv[i][3] = __builtin_bit_cast(f32x4, __builtin_amdgcn_raw_buffer_load_b128(lr_rsrc, r1 + lx1[i], 0, 0));
+                    const unsigned r0 = lr_img + (unsigned)(i0 * p.wp) * PXB, r1 = lr_img + (unsigned)(i1 * p.wp) * PXB;
+                    lv[i][0] = load_unit<DT>(lr_rsrc, r0 + lx0[i]);
+                    lv[i][1] = load_unit<DT>(lr_rsrc, r0 + lx1[i]);
+                    lv[i][2] = load_unit<DT>(lr_rsrc, r1 + lx0[i]);
+                    lv[i][3] = load_unit<DT>(lr_rsrc, r1 + lx1[i]);
                 }
             }
             // ---- sampling position of gather t + 2 (warp rows ys - 4 + 2(t+2), +1), fp64 like the reference; the MV was requested in H2(t-1)
@@ -583,7 +621,7 @@ __device__ __forceinline__ void producer(const RollParams &p, const Smem &sm, co
 #pragma unroll
             for (int i = 0; i < NLU; ++i)
                 if (l_on && l_lane[i])
-                    sm.Ls[(lrr[i] * 16 + gcg) * LPL + lcc[i]] = lwy0[i] * (lwx0[i] * lv[i][0] + lwx1[i] * lv[i][1]) + lwy1[i] * (lwx0[i] * lv[i][2] + lwx1[i] * lv[i][3]);
+                    sm.Ls[(lrr[i] * 16 + gcg) * LPL + lcc[i]] = lr_interp<DT>(lwy0[i], lwy1[i], lwx0[i], lwx1[i], lv[i]);
             // ---- gather t: blend, stage; then the tap offsets / weights of gather t + 1 (table of H2(t-1))
             if (g_on) {
                 f32x4 acc = {0.f, 0.f, 0.f, 0.f};
@@ -665,19 +703,27 @@ __device__ __forceinline__ void producer(const RollParams &p, const Smem &sm, co
                         const Taps tp = make_taps(ngx, ngy, Hp, Wp);
                         const int xa = min(max(tp.x0, 0), Wp - 1), xc = min(max(tp.x0 + 1, 0), Wp - 1);
                         const int ya = min(max(tp.y0, 0), Hp - 1), yc = min(max(tp.y0 + 1, 0), Hp - 1);
-                        o = u32x4{(unsigned)(ya * Wp + xa), (unsigned)(ya * Wp + xc), (unsigned)(yc * Wp + xa), (unsigned)(yc * Wp + xc)} * (CH * 4u);
+                        o = u32x4{(unsigned)(ya * Wp + xa), (unsigned)(ya * Wp + xc), (unsigned)(yc * Wp + xa), (unsigned)(yc * Wp + xc)} * PXB;
                         w = f32x4{tp.vx0 ? tp.ex : 0.f, tp.vx1 ? tp.wx : 0.f, tp.vy0 ? tp.ey : 0.f, tp.vy1 ? tp.wy : 0.f};
                     }
                     sm.TapW[tl] = w; sm.TapO[tl] = o;
-                    // touch the eight 128-byte lines of the four tap pixels: the gather lanes read them one and a half iterations from now
-                    asm volatile("" :: "v"(pft[0]), "v"(pft[1]), "v"(pft[2]), "v"(pft[3]), "v"(pft[4]), "v"(pft[5]), "v"(pft[6]), "v"(pft[7]));
+                    // touch the 128-byte lines of the four tap pixels (fp32: two per pixel, 16-bit: one): the gather lanes read them one and a
+                    // half iterations from now
+                    if constexpr (PXB == 256u) {
+                        asm volatile("" :: "v"(pft[0]), "v"(pft[1]), "v"(pft[2]), "v"(pft[3]), "v"(pft[4]), "v"(pft[5]), "v"(pft[6]), "v"(pft[7]));
 #pragma unroll
-                    for (int i = 0; i < 8; ++i) pft[i] = __builtin_amdgcn_raw_buffer_load_b32(g_rsrc, o[i >> 1] + ((i & 1) ? 128u : 0u), 0, 0);
+                        for (int i = 0; i < 8; ++i) pft[i] = __builtin_amdgcn_raw_buffer_load_b32(g_rsrc, o[i >> 1] + ((i & 1) ? 128u : 0u), 0, 0);
+                    } else {
+                        asm volatile("" :: "v"(pft[0]), "v"(pft[1]), "v"(pft[2]), "v"(pft[3]));
+#pragma unroll
+                        for (int i = 0; i < 4; ++i) pft[i] = __builtin_amdgcn_raw_buffer_load_b32(g_rsrc, o[i], 0, 0);
+                    }
                 }
                 // ---- wave 12 touches the lr pixels under the lr_up rows of iteration t + 2 (rows ys + 2t - 3, ys + 2t - 2): lane = (lr row 0..3 from
-                // the first tap row, lr column 0..15 from the first tap column of the strip), both lines of the pixel
+                // the first tap row, lr column 0..15 from the first tap column of the strip), every line of the pixel (fp32: two, 16-bit: one)
                 if (wave == 12 && t >= 1 && t <= S + 1) {
-                    asm volatile("" :: "v"(pft[0]), "v"(pft[1]));
+                    if constexpr (PXB == 256u) asm volatile("" :: "v"(pft[0]), "v"(pft[1]));
+                    else asm volatile("" :: "v"(pft[0]));
                     const int tq = tid & 63;
                     int i0, i1, ie0, ie1, j0, j1, je0, je1; float l;
                     arseg_src_index(p.sy, min(max(ys + 2 * t - 3, 0), Hp - 1), true, p.hp, i0, i1, l);
@@ -685,9 +731,9 @@ __device__ __forceinline__ void producer(const RollParams &p, const Smem &sm, co
                     arseg_src_index(p.sx, min(max(x0 - 1, 0), Wp - 1), true, p.wp, j0, j1, l);
                     arseg_src_index(p.sx, min(max(x0 + SW, 0), Wp - 1), true, p.wp, je0, je1, l);
                     const int r = i0 + (tq >> 4), c = j0 + (tq & 15);
-                    const unsigned off = r <= ie1 && c <= je1 ? (unsigned)(r * p.wp + c) * (CH * 4u) : OOB;
+                    const unsigned off = r <= ie1 && c <= je1 ? (unsigned)(r * p.wp + c) * PXB : OOB;
                     pft[0] = __builtin_amdgcn_raw_buffer_load_b32(lr_rsrc, off, 0, 0);
-                    pft[1] = __builtin_amdgcn_raw_buffer_load_b32(lr_rsrc, off == OOB ? OOB : off + 128u, 0, 0);
+                    if constexpr (PXB == 256u) pft[1] = __builtin_amdgcn_raw_buffer_load_b32(lr_rsrc, off == OOB ? OOB : off + 128u, 0, 0);
                 }
             }
             wg_sync();
@@ -695,7 +741,7 @@ __device__ __forceinline__ void producer(const RollParams &p, const Smem &sm, co
     }
 }
 
-template <int NB>      // NB: classifier row blocks of 16 classes (0: no head)
+template <int NB, int DT>      // NB: classifier row blocks of 16 classes (0: no head); DT: element type of ref / lr (enum arseg_dtype)
 __global__ __launch_bounds__(NT) void creff_roll_kernel(const RollParams p) {
     constexpr int NBA = NB > 0 ? NB : 1;
     extern __shared__ __attribute__((aligned(16))) unsigned char smem[];
@@ -742,36 +788,38 @@ __global__ __launch_bounds__(NT) void creff_roll_kernel(const RollParams p) {
         // Roles by SIMD (a workgroup's waves go to the four SIMDs cyclically, so waves w and w + 4 share one): every SIMD hosts one
         // consumer and about the same producer VALU work --  SIMD a: 0 C | 4 KV | 8 KV | 12 AUX     SIMD b: 1 C | 5 KV | 9 KV | 13 AUX (taps)
         //                                                 SIMD c: 2 C | 6 KV | 10 Q | 14 Q       SIMD d: 3 C | 7 KV | 11 Q | 15 Q
-        producer<ROLE_KV>(p, sm, sc, tid, wave);
+        producer<ROLE_KV, DT>(p, sm, sc, tid, wave);
     } else if (wave == 12 || wave == 13) {
-        producer<ROLE_AUX>(p, sm, sc, tid, wave);
+        producer<ROLE_AUX, DT>(p, sm, sc, tid, wave);
     } else {
-        producer<ROLE_Q>(p, sm, sc, tid, wave);
+        producer<ROLE_Q, DT>(p, sm, sc, tid, wave);
     }
 }
 
-template <int NB>
+template <int NB, int DT>
 int launch(const RollParams &p, int max_wgs, hipStream_t st) {
     static ArsegSmemAttr attr;
-    if (int e = arseg_allow_smem(attr, reinterpret_cast<const void *>(creff_roll_kernel<NB>), SMEM_BYTES)) return e;
+    if (int e = arseg_allow_smem(attr, reinterpret_cast<const void *>(creff_roll_kernel<NB, DT>), SMEM_BYTES)) return e;
     int dev = 0, cus = 256;
     if (hipGetDevice(&dev) != hipSuccess || hipDeviceGetAttribute(&cus, hipDeviceAttributeMultiprocessorCount, dev) != hipSuccess) cus = 256;
     // workgroups: one per CU; fewer when the launch is small -- mode 0: one per unit, mode 1: at least 16 steps each (a piece costs 9 iterations of fill)
     const long long nunits = p.balanced ? ((long long)p.nstrips * p.N * ((p.Hp + 1) >> 1) + 15) / 16 : (long long)p.nstrips * p.nseg * p.N;
     if (max_wgs > 0 && max_wgs < cus) cus = max_wgs;      // leave compute units to the kernels of other streams (the workgroups are persistent)
     const int grid = (int)(nunits < cus ? nunits : cus);
-    hipLaunchKernelGGL((creff_roll_kernel<NB>), dim3(grid), dim3(NT), SMEM_BYTES, st, p);
+    hipLaunchKernelGGL((creff_roll_kernel<NB, DT>), dim3(grid), dim3(NT), SMEM_BYTES, st, p);
     return arseg_launch_status();
 }
 
 }  // namespace
 
-// creff_rr.hip's entry point dispatches here (same argument checks there).
-int arseg_creff_roll_launch(const float *const *ref_nhwc_host, const int16_t *mv_q, int H, int W, const float *lr, const float *wq,
+// creff_rr.hip's entry points dispatch here (same argument checks there); dtype = element type of ref / lr (enum arseg_dtype).
+int arseg_creff_roll_launch(const void *const *ref_nhwc_host, const int16_t *mv_q, int H, int W, const void *lr, int dtype, const float *wq,
                             const float *bq, const float *wk, const float *bk, const float *wv, const float *bv, float *p_out,
                             int p_layout, const float *wf, const float *bf, int n_cls, float *logits, int log_softmax, int N, int Hp,
                             int Wp, int hp, int wp, int seg_rows, int max_wgs, bool dry_run, hipStream_t st) {
     const bool head = dry_run ? n_cls > 0 : logits != nullptr;
+    if (dtype != ARSEG_DT_F32 && dtype != ARSEG_DT_F16 && dtype != ARSEG_DT_BF16) return ARSEG_EINVAL;
+    const size_t esz = dtype == ARSEG_DT_F32 ? sizeof(float) : 2;
     // one head instantiation: up to 16 classes.  A 17-32-class head (the NB = 2 form of rounds 4) spilled in the merge wave and was never
     // selected by AUTO; such heads run on the tile kernel (creff_rr.hip) -- VERDICT r4 item 6.
     if (head && n_cls > 16) return ARSEG_EUNSUPPORTED;
@@ -801,8 +849,8 @@ int arseg_creff_roll_launch(const float *const *ref_nhwc_host, const int16_t *mv
     }
     p.seg_rows = seg_rows; p.nseg = arseg_cdiv(Hp, seg_rows);
     p.p_bytes = (unsigned)((size_t)CH * Hp * Wp * sizeof(float)); p.l_bytes = head ? (unsigned)((size_t)n_cls * Hp * Wp * sizeof(float)) : 0u;
-    p.lr_bytes = (unsigned)((size_t)CH * hp * wp * sizeof(float));
-    p.ref_bytes = (unsigned)((size_t)CH * Hp * Wp * sizeof(float));
+    p.lr_bytes = (unsigned)((size_t)CH * hp * wp * esz);
+    p.ref_bytes = (unsigned)((size_t)CH * Hp * Wp * esz);
     p.sy = arseg_resize_scale(hp, Hp, true); p.sx = arseg_resize_scale(wp, Wp, true);
     if (p.balanced) {      // a workgroup's list of pieces must hold its whole-strip passes + the pieces of its remainder run
         int dev = 0, cus = 256;
@@ -813,5 +861,7 @@ int arseg_creff_roll_launch(const float *const *ref_nhwc_host, const int16_t *mv
         if (share / g + 3 > MAXPIECES) return ARSEG_EUNSUPPORTED;
     }
     if (dry_run) return ARSEG_OK;
-    return head ? launch<1>(p, max_wgs, st) : launch<0>(p, max_wgs, st);
+    if (dtype == ARSEG_DT_F16) return head ? launch<1, ARSEG_DT_F16>(p, max_wgs, st) : launch<0, ARSEG_DT_F16>(p, max_wgs, st);
+    if (dtype == ARSEG_DT_BF16) return head ? launch<1, ARSEG_DT_BF16>(p, max_wgs, st) : launch<0, ARSEG_DT_BF16>(p, max_wgs, st);
+    return head ? launch<1, ARSEG_DT_F32>(p, max_wgs, st) : launch<0, ARSEG_DT_F32>(p, max_wgs, st);
 }

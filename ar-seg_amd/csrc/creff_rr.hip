@@ -728,7 +728,7 @@ extern "C" int arseg_creff_warp_fwd_ex(const float *const *ref_nhwc_host, const 
     // (creff_roll.hip) serves every launch it admits -- no head or a head of <= 16 classes, a schedule that fits its piece table -- the
     // 16 x 16 tile kernel below the rest (17-32 classes, oversized schedules) and impl = TILES
     if (impl != ARSEG_CREFF_WARP_TILES) {
-        const int e = arseg_creff_roll_launch(ref_nhwc_host, mv_q, H, W, lr, wq, bq, wk, bk, wv, bv, p_out, p_layout, wf, bf, n_cls, logits,
+        const int e = arseg_creff_roll_launch(reinterpret_cast<const void *const *>(ref_nhwc_host), mv_q, H, W, lr, ARSEG_DT_F32, wq, bq, wk, bk, wv, bv, p_out, p_layout, wf, bf, n_cls, logits,
                                               log_softmax, N, Hp, Wp, hp, wp, seg_rows, max_wgs, false, arseg_stream(stream));
         if (e != ARSEG_EUNSUPPORTED || impl == ARSEG_CREFF_WARP_ROLL) return e;
     }
@@ -749,6 +749,37 @@ extern "C" int arseg_creff_warp_fwd_ex(const float *const *ref_nhwc_host, const 
     return n_cls <= 16 ? launch<1>(p, st) : launch<2>(p, st);
 }
 
+extern "C" int arseg_creff_warp16_fwd_ex(const void *const *ref_nhwc_host, const void *lr, int dtype, const int16_t *mv_q, int H, int W,
+                                         const float *wq, const float *bq, const float *wk, const float *bk, const float *wv,
+                                         const float *bv, float *p_out, int p_layout, const float *wf, const float *bf, int n_cls,
+                                         float *logits, int log_softmax, int N, int C, int Hp, int Wp, int hp, int wp, int kH, int kW,
+                                         int seg_rows, int max_wgs, arseg_stream_t stream) {
+    ARSEG_CHECK_PTR(ref_nhwc_host); ARSEG_CHECK_PTR(mv_q); ARSEG_CHECK_PTR(lr); ARSEG_CHECK_PTR(wq); ARSEG_CHECK_PTR(bq); ARSEG_CHECK_PTR(wk);
+    ARSEG_CHECK_PTR(bk); ARSEG_CHECK_PTR(wv); ARSEG_CHECK_PTR(bv); ARSEG_CHECK_PTR(p_out);
+    ARSEG_CHECK_POS(N); ARSEG_CHECK_POS(C); ARSEG_CHECK_POS(Hp); ARSEG_CHECK_POS(Wp); ARSEG_CHECK_POS(hp); ARSEG_CHECK_POS(wp);
+    ARSEG_CHECK_POS(H); ARSEG_CHECK_POS(W);
+    if (dtype != ARSEG_DT_F16 && dtype != ARSEG_DT_BF16) return ARSEG_EINVAL;
+    if (C != CH || kH != 7 || kW != 7 || N > MAXN) return ARSEG_EUNSUPPORTED;
+    if (p_layout != ARSEG_C8 && p_layout != ARSEG_NHWC) return ARSEG_EINVAL;
+    if ((size_t)C * Hp * Wp * sizeof(float) >= (1ull << 31)) return ARSEG_EUNSUPPORTED;       // 32-bit buffer offsets within a frame of p_out
+    if ((size_t)Hp * Wp >= (1u << 30)) return ARSEG_EUNSUPPORTED;
+    if (!ARSEG_ALIGNED16(lr) || !ARSEG_ALIGNED16(p_out) || !ARSEG_ALIGNED16(wq) || !ARSEG_ALIGNED16(wk) || !ARSEG_ALIGNED16(wv) ||
+        !ARSEG_ALIGNED16(bq) || !ARSEG_ALIGNED16(bk) || !ARSEG_ALIGNED16(bv))
+        return ARSEG_EINVAL;
+    const bool head = logits != nullptr;
+    if (head) {
+        if (!wf || !bf || n_cls <= 0) return ARSEG_EINVAL;
+        if (n_cls > 16) return ARSEG_EUNSUPPORTED;                                               // 17-32 classes: the tile kernel, fp32 inputs only
+        if (!ARSEG_ALIGNED16(wf)) return ARSEG_EINVAL;
+    }
+    if (seg_rows < 0 || max_wgs < 0) return ARSEG_EINVAL;
+    for (int i = 0; i < N; ++i)
+        if (!ref_nhwc_host[i] || !ARSEG_ALIGNED16(ref_nhwc_host[i])) return ARSEG_EINVAL;
+    // the rolling kernel or nothing: a launch it does not admit (a schedule beyond its piece table) is refused before anything runs
+    return arseg_creff_roll_launch(ref_nhwc_host, mv_q, H, W, lr, dtype, wq, bq, wk, bk, wv, bv, p_out, p_layout, wf, bf, n_cls, logits,
+                                   log_softmax, N, Hp, Wp, hp, wp, seg_rows, max_wgs, false, arseg_stream(stream));
+}
+
 extern "C" int arseg_creff_warp_select(int N, int C, int Hp, int Wp, int hp, int wp, int kH, int kW, int n_cls, int impl, int seg_rows, int max_wgs) {
     if (N <= 0 || C <= 0 || Hp <= 0 || Wp <= 0 || hp <= 0 || wp <= 0 || n_cls < 0 || seg_rows < 0 || max_wgs < 0) return ARSEG_EINVAL;
     if (impl != ARSEG_CREFF_WARP_AUTO && impl != ARSEG_CREFF_WARP_TILES && impl != ARSEG_CREFF_WARP_ROLL) return ARSEG_EINVAL;
@@ -758,7 +789,7 @@ extern "C" int arseg_creff_warp_select(int N, int C, int Hp, int Wp, int hp, int
     // (the tile kernel: 32-bit offsets over the whole batch; the rolling kernel: over one frame)
     const bool tiles_fit = (size_t)N * C * Hp * Wp * sizeof(float) < (1ull << 31) && (size_t)N * C * hp * wp * sizeof(float) < (1ull << 31);
     if (impl == ARSEG_CREFF_WARP_TILES) return tiles_fit ? ARSEG_CREFF_WARP_TILES : ARSEG_EUNSUPPORTED;
-    const int e = arseg_creff_roll_launch(nullptr, nullptr, 1, 1, nullptr, nullptr, nullptr, nullptr, nullptr, nullptr, nullptr, nullptr, ARSEG_NHWC, nullptr,
+    const int e = arseg_creff_roll_launch(nullptr, nullptr, 1, 1, nullptr, ARSEG_DT_F32, nullptr, nullptr, nullptr, nullptr, nullptr, nullptr, nullptr, ARSEG_NHWC, nullptr,
                                           nullptr, n_cls, nullptr, 0, N, Hp, Wp, hp, wp, seg_rows, max_wgs, true, nullptr);
     if (e == ARSEG_OK) return ARSEG_CREFF_WARP_ROLL;
     if (e != ARSEG_EUNSUPPORTED) return e;

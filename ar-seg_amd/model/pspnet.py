@@ -204,21 +204,12 @@ class PSPNetWithFuse(_PSPBase):
         """Phase 2 with the MV warp fused in (fast path): LR feature NHWC, un-warped keyframe features NHWC [Hp,Wp,C] (one per
         frame), int16 MVs -> (log-probs NCHW, p C8).
 
-        16-bit features at C = 64 with a 7 x 7 window: each distinct keyframe feature of THIS call (the frames of a GOP batch share one) and the
-        LR feature are cast to fp32 once and the fp32 fused warp + CReFF + head kernel runs -- the 16-bit route (ops.creff_warp) writes an fp32
-        C8 copy of the warped keyframe feature per frame and reads it back (measured slower).  The cast is per call: the batched
-        path (alter_res_batch_fast, GopRunner.run_batched) casts the keyframe feature once per GOP, the per-frame path once per frame.
-        Other shapes take the 16-bit route."""
+        16-bit features go to the fused kernel as they are: ops.creff_warp picks the route (``ops.config.creff_warp16``) -- the rolling kernel
+        reading fp16 / bf16 directly, or each distinct keyframe feature of THIS call and the LR batch cast to fp32 once ahead of the fp32
+        kernel (the batched path, alter_res_batch_fast / GopRunner.run_batched, then casts the keyframe feature once per GOP, the per-frame path
+        once per frame).  Same bits on both; p and the log-probs are fp32."""
         hd = self.packed()["head"]
         fa = self.fuse_attention
-        if ops.is16(p_nhwc) and p_nhwc.shape[3] == 64 and fa.kH == 7 and fa.kW == 7:
-            cast = {}
-            for r in refs_nhwc:
-                k = (r.data_ptr(), tuple(r.shape), tuple(r.stride()))
-                if k not in cast:
-                    cast[k] = ops.cast(r, torch.float32)
-            refs_nhwc = [cast[(r.data_ptr(), tuple(r.shape), tuple(r.stride()))] for r in refs_nhwc]
-            p_nhwc = ops.cast(p_nhwc, torch.float32)
         p_c8, out = fa.fuse_warp(refs_nhwc, mv_q, p_nhwc, head=(hd.wf, hd.bf), log_softmax=True)
         return out, p_c8
 

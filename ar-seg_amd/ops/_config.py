@@ -22,7 +22,9 @@ _CHOICES = {
     "creff_impl": ("", "mfma", "valu"),
     "creff_tile_rows": (0, 8, 16),
     "creff_warp_impl": ("", "roll", "tiles"),
+    "creff_warp16": ("", "direct", "cast"),
 }
+WARP16_DEFAULT = "direct"          # what creff_warp16 = "" stands for: the route measured faster
 _NONNEG_INT = ("creff_seg_rows", "creff_max_wgs", "lr_subbatch")
 
 
@@ -49,6 +51,8 @@ class Config:
     creff_tile_rows  [ARSEG_CREFF_TY = 8 | 16]                  pin the tile height of the matrix-core CReFF kernel
     creff_warp_impl  [ARSEG_CREFF_WARP_IMPL = roll | tiles]     fused warp + CReFF kernel for C = 64: the rolling kernel (csrc/creff_roll.hip, default) or
                      the 16 x 16 tile kernel of rounds 2-3 (csrc/creff_rr.hip)
+    creff_warp16     [ARSEG_CREFF_WARP16 = direct | cast]       fp16 / bf16 features on the rolling kernel: read as they are (direct) or cast to fp32 once
+                     per call and run through the fp32 instantiation (cast); the same bits either way.  Default: the faster one (WARP16_DEFAULT below)
     creff_seg_rows   [ARSEG_CREFF_SEG_ROWS = n]                 fixed strip segments of n rows for the rolling kernel (0: its balanced default schedule)
     creff_max_wgs    [ARSEG_CREFF_MAX_WGS = n]                  upper bound on the rolling kernel's persistent workgroups (0: one per compute unit)
     lr_subbatch      [ARSEG_LR_SUBBATCH = n]                    evaluate the LR batch of a GOP in slices of n frames (bounds the working set)
@@ -67,6 +71,7 @@ class Config:
     creff_impl: str = ""
     creff_tile_rows: int = 0
     creff_warp_impl: str = ""
+    creff_warp16: str = ""
     creff_seg_rows: int = 0
     creff_max_wgs: int = 0
     lr_subbatch: int = 0
@@ -91,7 +96,8 @@ class Config:
                 conv_igemm3=e("ARSEG_CONV_IGEMM3", "1") != "0",
                 conv_range_guard={"1": "host", "0": "off"}.get(e("ARSEG_CONV_RANGE_GUARD", "device"), e("ARSEG_CONV_RANGE_GUARD", "device")),
                 conv_plan_file=e("ARSEG_CONV_PLAN_FILE"), creff_impl=e("ARSEG_CREFF_IMPL", ""), creff_tile_rows=num("ARSEG_CREFF_TY", int, 0),
-                creff_warp_impl=e("ARSEG_CREFF_WARP_IMPL", ""), creff_seg_rows=num("ARSEG_CREFF_SEG_ROWS", int, 0),
+                creff_warp_impl=e("ARSEG_CREFF_WARP_IMPL", ""), creff_warp16=e("ARSEG_CREFF_WARP16", ""),
+                creff_seg_rows=num("ARSEG_CREFF_SEG_ROWS", int, 0),
                 creff_max_wgs=num("ARSEG_CREFF_MAX_WGS", int, 0), lr_subbatch=num("ARSEG_LR_SUBBATCH", int, 0),
                 aux_outputs=e("ARSEG_AUX_OUTPUTS", "0") not in ("", "0"))
         validate(dataclasses.asdict(c), source="environment")

@@ -8,7 +8,7 @@ import torch
 
 from .. import _lib
 from ._base import _need_gpu, _need_gpu16, _ptr, _stream, is16
-from ._config import config
+from ._config import WARP16_DEFAULT, config
 from ._profile import launch
 from .layers import cast, from_c8
 
@@ -117,29 +117,37 @@ def creff_warp(refs_nhwc, mv_q: torch.Tensor, lr_nhwc: torch.Tensor, attn, head=
     """MV warp + CReFF + head in one kernel (arseg_creff_warp_fwd).
 
     refs_nhwc: sequence of B un-warped keyframe features, NHWC [Hp,Wp,C] each (frames of one GOP share theirs);
-    mv_q: int16 [B,H,W,2]; lr_nhwc: [B,hp,wp,C].  Returns (p in ``p_layout``, logits NCHW or None).  Shapes the fused
-    kernel does not cover (C != 64, windows other than 7x7) run as arseg_warp_mvq_fwd + arseg_creff_fwd."""
-    if is16(lr_nhwc):
-        # 16-bit storage path: the warp reads the 16-bit keyframe feature directly (fp32 C8 out), the small LR feature is converted,
-        # the CReFF arithmetic itself stays fp32 (split-fp16 matrix cores): p and the logits come back fp32
+    mv_q: int16 [B,H,W,2]; lr_nhwc: [B,hp,wp,C].  Returns (p in ``p_layout``, logits NCHW or None), both fp32.  Shapes the fused
+    kernel does not cover (C != 64, windows other than 7x7) run as arseg_warp_mvq_fwd + arseg_creff_fwd.
+
+    fp16 / bf16 features (refs and lr of ONE 16-bit dtype; anything mixed raises), by shape:
+      * C = 64, 7 x 7 and a launch the rolling kernel admits (``creff_warp_kernel(...) == "roll"``): ``config.creff_warp16`` chooses between
+        "direct" -- the rolling kernel reads the 16-bit tensors as they are (arseg_creff_warp16_fwd_ex: one ``creff_warp`` launch per <= 32
+        frames, no fp32 copies) -- and "cast" -- each distinct keyframe feature of this call and the LR batch are cast to fp32 once
+        (``cast`` launches) and the fp32 fused kernel runs.  The two give the same bits: widening is exact.
+      * C = 64, 7 x 7 otherwise (17-32-class heads, oversized schedules, ``creff_warp_impl="tiles"``): cast once, then the fp32 fused entry point.
+      * every other shape: arseg_warp_mvq16_fwd (fp32 C8 copy of the warped feature) + arseg_creff_fwd."""
+    if is16(lr_nhwc) or any(is16(r) for r in refs_nhwc):
         dt = _need_gpu16(lr_nhwc, *refs_nhwc)
         _need_gpu(mv_q, dtype=torch.int16)
-        mv_q = mv_q.contiguous()
         B, hp, wp, C = lr_nhwc.shape
-        Hp, Wp, _ = refs_nhwc[0].shape
-        _, H, W, _ = mv_q.shape
-        ref_c8 = torch.empty((B, C // 8, Hp, Wp, 8), dtype=torch.float32, device=lr_nhwc.device)
-        refs16 = [r.contiguous() for r in refs_nhwc]
-        if B * C * Hp * Wp * 4 < (1 << 31) and all(r.data_ptr() == refs16[0].data_ptr() for r in refs16):
-            # the non-keyframes of one GOP share the keyframe feature: one launch for the batch (feature stride 0) instead of one per frame
-            launch("warp_mvq", _lib.load().arseg_warp_mvq16_shared_fwd, _ptr(refs16[0]), 0, dt, _ptr(mv_q), _ptr(ref_c8), B, C, Hp, Wp,
-                    H, W, _stream(), nbytes=B * (2 * C * Hp * Wp + 4 * C * Hp * Wp + 4 * H * W))
-        else:
-            for b in range(B):
-                launch("warp_mvq", _lib.load().arseg_warp_mvq16_fwd, _ptr(refs16[b]), dt, _ptr(mv_q[b:b + 1]), _ptr(ref_c8[b:b + 1]), 1, C, Hp, Wp,
-                        H, W, _stream(), nbytes=2 * C * Hp * Wp + 4 * C * Hp * Wp + 4 * H * W)
-        p_c8, logits = creff(ref_c8, cast(lr_nhwc, torch.float32), attn, head, log_softmax, kH, kW)
-        return (p_c8 if p_layout == _lib.C8 else from_c8(p_c8, _lib.NHWC)), logits
+        Hp, Wp, C2 = refs_nhwc[0].shape
+        if len(refs_nhwc) != B or mv_q.shape[0] != B or C2 != C or any(tuple(r.shape) != (Hp, Wp, C) for r in refs_nhwc):
+            raise _lib.ArsegError("creff_warp: refs / mv_q / lr batch or channel mismatch")
+        if not (C == 64 and kH == 7 and kW == 7):
+            return _creff_warp16_two_kernel(dt, refs_nhwc, mv_q, lr_nhwc, attn, head, log_softmax, kH, kW, p_layout)
+        n_cls = 0 if head is None else head[0].shape[0]
+        direct = (config.creff_warp16 or WARP16_DEFAULT) == "direct"
+        if direct and n_cls <= 32 and C * Hp * Wp * 4 < (1 << 31) and creff_warp_kernel(B, C, Hp, Wp, hp, wp, n_cls, kH, kW) == "roll":
+            return _creff_warp16_direct(dt, refs_nhwc, mv_q, lr_nhwc, attn, head, log_softmax, p_layout)
+        # cast once: every distinct keyframe feature of THIS call (the frames of a GOP batch share one) and the LR batch, then the fp32 routes below
+        once = {}
+        for r in refs_nhwc:
+            k = (r.data_ptr(), tuple(r.shape), tuple(r.stride()))
+            if k not in once:
+                once[k] = cast(r, torch.float32)
+        refs_nhwc = [once[(r.data_ptr(), tuple(r.shape), tuple(r.stride()))] for r in refs_nhwc]
+        lr_nhwc = cast(lr_nhwc, torch.float32)
     _need_gpu(lr_nhwc, *refs_nhwc)
     _need_gpu(mv_q, dtype=torch.int16)
     lr_nhwc, mv_q = lr_nhwc.contiguous(), mv_q.contiguous()
@@ -175,6 +183,54 @@ def creff_warp(refs_nhwc, mv_q: torch.Tensor, lr_nhwc: torch.Tensor, attn, head=
                 flops=b * Hp * Wp * C * (250 + 2 * n_cls),
                 nbytes=b * (4 * (2 * C * Hp * Wp + C * hp * wp + n_cls * Hp * Wp) + 4 * H * W))
     return p_out, logits
+
+
+def _creff_warp16_direct(dt, refs_nhwc, mv_q, lr_nhwc, attn, head, log_softmax, p_layout):
+    """The rolling kernel on the 16-bit tensors as they are (C = 64, 7 x 7, a launch it admits: the caller has asked creff_warp_kernel)."""
+    lr_nhwc, mv_q = lr_nhwc.contiguous(), mv_q.contiguous()
+    refs = [r.contiguous() for r in refs_nhwc]
+    B, hp, wp, C = lr_nhwc.shape
+    Hp, Wp, _ = refs[0].shape
+    _, H, W, _ = mv_q.shape
+    n_cls = 0 if head is None else head[0].shape[0]
+    shape = (B, C // 8, Hp, Wp, 8) if p_layout == _lib.C8 else (B, Hp, Wp, C)
+    p_out = torch.empty(shape, dtype=torch.float32, device=lr_nhwc.device)
+    logits, wf, bf = None, None, None
+    if head is not None:
+        wf, bf = head
+        logits = torch.empty((B, n_cls, Hp, Wp), dtype=torch.float32, device=lr_nhwc.device)
+    per = min(B, 32)          # (the rolling kernel addresses every frame through its own descriptors: only the pointer table caps a launch)
+    for i in range(0, B, per):
+        b = min(per, B - i)
+        ptrs = (ctypes.c_void_p * b)(*[r.data_ptr() for r in refs[i:i + b]])
+        launch("creff_warp", _lib.load().arseg_creff_warp16_fwd_ex, ptrs, _ptr(lr_nhwc[i:i + b]), dt, _ptr(mv_q[i:i + b]), H, W, _ptr(attn.wq),
+                _ptr(attn.bq), _ptr(attn.wk), _ptr(attn.bk), _ptr(attn.wv), _ptr(attn.bv), _ptr(p_out[i:i + b]), p_layout, _ptr(wf), _ptr(bf), n_cls,
+                _ptr(None if logits is None else logits[i:i + b]), 1 if log_softmax else 0, b, C, Hp, Wp, hp, wp, 7, 7,
+                max(0, int(config.creff_seg_rows)), max(0, int(config.creff_max_wgs)), _stream(),
+                flops=b * Hp * Wp * C * (250 + 2 * n_cls),
+                nbytes=b * (2 * (C * Hp * Wp + C * hp * wp) + 4 * (C * Hp * Wp + n_cls * Hp * Wp) + 4 * H * W))
+    return p_out, logits
+
+
+def _creff_warp16_two_kernel(dt, refs_nhwc, mv_q, lr_nhwc, attn, head, log_softmax, kH, kW, p_layout):
+    """16-bit features beyond the fused kernel's shapes: the warp reads the 16-bit keyframe feature directly (fp32 C8 out), the small LR
+    feature is converted, the CReFF arithmetic itself stays fp32 (split-fp16 matrix cores): p and the logits come back fp32."""
+    mv_q = mv_q.contiguous()
+    B, hp, wp, C = lr_nhwc.shape
+    Hp, Wp, _ = refs_nhwc[0].shape
+    _, H, W, _ = mv_q.shape
+    ref_c8 = torch.empty((B, C // 8, Hp, Wp, 8), dtype=torch.float32, device=lr_nhwc.device)
+    refs16 = [r.contiguous() for r in refs_nhwc]
+    if B * C * Hp * Wp * 4 < (1 << 31) and all(r.data_ptr() == refs16[0].data_ptr() for r in refs16):
+        # the non-keyframes of one GOP share the keyframe feature: one launch for the batch (feature stride 0) instead of one per frame
+        launch("warp_mvq", _lib.load().arseg_warp_mvq16_shared_fwd, _ptr(refs16[0]), 0, dt, _ptr(mv_q), _ptr(ref_c8), B, C, Hp, Wp,
+                H, W, _stream(), nbytes=B * (2 * C * Hp * Wp + 4 * C * Hp * Wp + 4 * H * W))
+    else:
+        for b in range(B):
+            launch("warp_mvq", _lib.load().arseg_warp_mvq16_fwd, _ptr(refs16[b]), dt, _ptr(mv_q[b:b + 1]), _ptr(ref_c8[b:b + 1]), 1, C, Hp, Wp,
+                    H, W, _stream(), nbytes=2 * C * Hp * Wp + 4 * C * Hp * Wp + 4 * H * W)
+    p_c8, logits = creff(ref_c8, cast(lr_nhwc, torch.float32), attn, head, log_softmax, kH, kW)
+    return (p_c8 if p_layout == _lib.C8 else from_c8(p_c8, _lib.NHWC)), logits
 
 
 def _warp_frames_per_launch(B, C, Hp, Wp, hp, wp, n_cls, kH=7, kW=7) -> int:

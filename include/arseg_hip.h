@@ -153,6 +153,20 @@ int arseg_creff_warp_fwd_ex(const float *const *ref_nhwc_host, const int16_t *mv
  * heads, oversized schedules and impl = TILES.  (bench.py labels its roofline line with this; tests enforce the table.) */
 int arseg_creff_warp_select(int N, int C, int Hp, int Wp, int hp, int wp, int kH, int kW, int n_cls, int impl, int seg_rows, int max_wgs);
 
+/* The rolling kernel on 16-bit features: the keyframe features (ref_nhwc_host: HOST array of N device pointers, NHWC [Hp][Wp][C]) and lr
+ * ([N,hp,wp,C]) are fp16 or bf16 (dtype = ARSEG_DT_F16 | ARSEG_DT_BF16, both the same) and are read as they are -- no fp32 copies; every
+ * element is widened to fp32 in registers (exact) and everything behind the loads is the arithmetic of arseg_creff_warp_fwd_ex, so the
+ * results equal, bit for bit, those of arseg_creff_warp_fwd_ex on the same tensors cast to fp32.  Weights, biases, the classifier, p_out and
+ * logits are fp32; every other argument as arseg_creff_warp_fwd_ex.  It serves exactly the launches for which
+ * arseg_creff_warp_select(..., impl = ARSEG_CREFF_WARP_ROLL, ...) answers ARSEG_CREFF_WARP_ROLL; anything else (C != 64, other windows, more than 16
+ * classes, N > 32, a schedule beyond the piece table) returns ARSEG_EUNSUPPORTED before any launch -- the tile kernel has no 16-bit form
+ * and nothing is computed in part; null pointers, another dtype or bad sizes ARSEG_EINVAL. */
+int arseg_creff_warp16_fwd_ex(const void *const *ref_nhwc_host, const void *lr, int dtype, const int16_t *mv_q, int H, int W,
+                              const float *wq, const float *bq, const float *wk, const float *bk, const float *wv,
+                              const float *bv, float *p_out, int p_layout, const float *wf, const float *bf, int n_cls,
+                              float *logits, int log_softmax, int N, int C, int Hp, int Wp, int hp, int wp, int kH, int kW,
+                              int seg_rows, int max_wgs, arseg_stream_t stream);
+
 /* The same with the kernel choice made explicit (measurements, tests): impl = enum arseg_creff_impl (AUTO: the matrix-core kernel
  * for C >= 128, the VALU kernel otherwise); mfma_tile_rows = 0 (by launch size), 8 or 16.  No environment variables are read. */
 int arseg_creff_fwd_ex(const float *hr, const float *lr, const float *wq, const float *bq, const float *wk,

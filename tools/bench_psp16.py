@@ -3,8 +3,9 @@
 bf16 and fp16 storage, in one process; plus the two measurements the 16-bit path's routing rests on:
   * the x2-upsample convs (up_1 / up_2 / up_3 of the keyframe and of the LR batch): the best fused patch plan against resize16 + conv2d16,
     and which of the two the plan cache keeps;
-  * phase 2 on 16-bit features at the headline shape: cast-once + the fp32 fused warp + CReFF kernel (PSPNetWithFuse.phase2_warp) against
-    the 16-bit route (warp_mvq16 to an fp32 C8 tensor + CReFF).
+  * phase 2 on 16-bit features at the headline shape: the fused warp + CReFF kernel reading the 16-bit tensors directly, cast-once + its
+    fp32 instantiation (PSPNetWithFuse.phase2_warp under creff_warp16 = direct / cast) and the two-kernel 16-bit route (warp_mvq16 to an
+    fp32 C8 tensor + CReFF); the GOP step in bf16 / fp16 is timed under both knob values (variants "bf16" = default, "bf16_cast", ...).
 Variants are alternated (repeats x variants), each timed over windows of >= 0.5 s after >= 2 warm-up steps; the spread over repeats is
 printed with the median.  --profile-step DTYPE: warm up, then run a few steps of that variant only (for rocprofv3 --kernel-trace --stats).
 One JSON line on stdout; the per-layer tables (ops.profile().layers()) with --layers."""
@@ -47,7 +48,7 @@ def main():
     ap.add_argument("--warmup", type=int, default=2)
     ap.add_argument("--window", type=float, default=0.5)
     ap.add_argument("--layers", action="store_true")
-    ap.add_argument("--profile-step", choices=sorted(DT), default=None)
+    ap.add_argument("--profile-step", choices=sorted(DT) + ["bf16_direct", "bf16_cast", "fp16_direct", "fp16_cast"], default=None)
     a = ap.parse_args()
     dev = torch.device("cuda:0")
     H, W = 512, 1024
@@ -61,12 +62,18 @@ def main():
     mvs = torch.from_numpy(clip["mv"]).to(dev)
 
     def step(name):
-        hr.set_storage(DT[name])
-        lr.set_storage(DT[name])
-        _, ref = hr.forward_keyframe(frames[0:1])
-        return ev.alter_res_batch_fast(lr, [ref[0]] * 11, frames[1:12], mvs[1:12], 0.5)
+        # "bf16_direct" / "bf16_cast": the 16-bit step with the phase-2 route pinned (plain "bf16": the default route)
+        name, _, route = name.partition("_")
+        prev = ops.configure(creff_warp16=route)
+        try:
+            hr.set_storage(DT[name])
+            lr.set_storage(DT[name])
+            _, ref = hr.forward_keyframe(frames[0:1])
+            return ev.alter_res_batch_fast(lr, [ref[0]] * 11, frames[1:12], mvs[1:12], 0.5)
+        finally:
+            ops.configure(**prev)
 
-    variants = [a.profile_step] if a.profile_step else ["fp32", "bf16", "fp16"]
+    variants = [a.profile_step] if a.profile_step else ["fp32", "bf16_direct", "bf16_cast", "fp16_direct", "fp16_cast"]
     with torch.no_grad():
         for v in variants:                      # warm-ups (the first also tunes every conv plan of the variant)
             for _ in range(max(2, a.warmup)):
@@ -121,18 +128,39 @@ def main():
                                                "fused_best_us": fused[best], "materialised_us": mat, "plan_cache": ops._conv_plans.get(key)}
         res["up2_convs"] = up
 
-        # phase 2 at the headline shape on 16-bit features: cast-once fp32 fused kernel vs the 16-bit two-kernel route
+        # phase 2 at the headline shape on 16-bit features, three routes alternated (repeats x routes): the rolling kernel reading the 16-bit
+        # tensors directly, cast-once + its fp32 instantiation (both through phase2_warp, pinned by the creff_warp16 knob), and the two-kernel
+        # 16-bit route (warp_mvq16 to an fp32 C8 tensor + CReFF)
+        from arseg_amd.ops.creff import _creff_warp16_two_kernel
+
         p2 = {}
         hd = lr.packed()["head"]
+        pa = lr.fuse_attention.packed()
         for v in ("bf16", "fp16"):
             dt = DT[v]
             feat = torch.randn(11, H // 2, W // 2, 64, device=dev).to(dt)
             ref = torch.randn(H, W, 64, device=dev).to(dt)
             refs = [ref] * 11
-            t_cast = window_ms(lambda: lr.phase2_warp(feat, refs, mvs[1:12]), a.window)
-            t_16 = window_ms(lambda: lr.fuse_attention.fuse_warp(refs, mvs[1:12], feat, head=(hd.wf, hd.bf), log_softmax=True), a.window)
-            p2[v] = {"cast_once_fp32_fused_ms": t_cast, "route16_warp_mvq16_creff_ms": t_16,
-                     "winner": "cast_once" if t_cast < t_16 else "route16"}
+            code = _lib.DT_BF16 if dt == torch.bfloat16 else _lib.DT_F16
+
+            def knob(value):
+                def run():
+                    prev = ops.configure(creff_warp16=value)
+                    try:
+                        lr.phase2_warp(feat, refs, mvs[1:12])
+                    finally:
+                        ops.configure(**prev)
+                return run
+
+            routes = {"direct16_fused_ms": knob("direct"), "cast_once_fp32_fused_ms": knob("cast"),
+                      "route16_warp_mvq16_creff_ms": lambda: _creff_warp16_two_kernel(code, refs, mvs[1:12], feat, pa, (hd.wf, hd.bf), True, 7, 7, _lib.C8)}
+            t = {k: [] for k in routes}
+            for _ in range(a.repeats):
+                for k, fn in routes.items():
+                    t[k].append(window_ms(fn, a.window))
+            p2[v] = {k: statistics.median(x) for k, x in t.items()}
+            p2[v].update({k.replace("_ms", "_min_max_ms"): [min(x), max(x)] for k, x in t.items()})
+            p2[v]["winner"] = min(routes, key=lambda k: p2[v][k])[:-3]
         res["phase2_16bit"] = p2
     print(json.dumps(res))
 
