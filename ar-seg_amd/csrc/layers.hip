@@ -828,44 +828,86 @@ __global__ __launch_bounds__(256) void nhwc_to_nchw_kernel(const float *__restri
 }
 
 // ------------------------------------------------------------------ evaluator tail
+// One workgroup keeps one n_cls x n_cls histogram of 32-bit counters in LDS (n_cls <= 32) and adds its non-zero counters to the int64
+// histogram in memory once, with 64-bit vector atomics.
+__device__ __forceinline__ void lds_hist_clear(unsigned int *lh, int n_cls) {
+    for (int i = threadIdx.x; i < n_cls * n_cls; i += blockDim.x) lh[i] = 0;
+    __syncthreads();
+}
+__device__ __forceinline__ void lds_hist_flush(const unsigned int *lh, unsigned long long *__restrict__ hist, int n_cls) {
+    __syncthreads();
+    for (int i = threadIdx.x; i < n_cls * n_cls; i += blockDim.x)
+        if (lh[i]) atomicAdd(&hist[i], (unsigned long long)lh[i]);
+}
+
+// One output pixel (ox, oy) of frame n: bilinear taps, argmax over the classes, pred store and the LDS count.  Shared by the ungrouped
+// and the grouped kernel, so the two give the same labels bit for bit.
+__device__ __forceinline__ void argmax_pixel(const float *__restrict__ logits, const int64_t *__restrict__ label, int32_t *__restrict__ pred,
+                                             unsigned int *lh, bool count, int n, int oy, int ox, int n_cls, int h, int w, int H, int W,
+                                             int ignore_label, int align, bool same, float sy, float sx) {
+    const long long pix = ((long long)n * H + oy) * W + ox;
+    int y0 = oy, y1 = oy, x0 = ox, x1 = ox; float ly = 0.f, lx = 0.f;
+    if (!same) {
+        arseg_src_index(sy, oy, align != 0, h, y0, y1, ly);
+        arseg_src_index(sx, ox, align != 0, w, x0, x1, lx);
+        ly = fminf(fmaxf(ly, 0.f), 1.f); lx = fminf(fmaxf(lx, 0.f), 1.f);
+    }
+    // torch.argmax semantics: the first maximum wins, a NaN counts as the maximum (the first NaN wins)
+    float best = -INFINITY; int bi = 0; bool best_nan = false;
+    for (int k = 0; k < n_cls; ++k) {
+        const float *b = logits + ((size_t)n * n_cls + k) * h * w;
+        float v;
+        if (same) v = b[(size_t)oy * w + ox];
+        else v = (1.f - ly) * ((1.f - lx) * b[(size_t)y0 * w + x0] + lx * b[(size_t)y0 * w + x1]) +
+                 ly * ((1.f - lx) * b[(size_t)y1 * w + x0] + lx * b[(size_t)y1 * w + x1]);
+        const bool isn = v != v, take = !best_nan & ((v > best) | isn);          // branch free
+        best = take ? v : best; bi = take ? k : bi; best_nan = best_nan | (take & isn);
+    }
+    if (pred) pred[pix] = bi;
+    if (count) {
+        const long long lab = label[pix];
+        if (lab != ignore_label && lab >= 0 && lab < n_cls) atomicAdd(&lh[(int)lab * n_cls + bi], 1u);
+    }
+}
+
 __global__ __launch_bounds__(256) void argmax_confusion_kernel(const float *__restrict__ logits, const int64_t *__restrict__ label,
                                                                int32_t *__restrict__ pred, unsigned long long *__restrict__ hist,
                                                                int N, int n_cls, int h, int w, int H, int W, int ignore_label, int align) {
     __shared__ unsigned int lh[1024];
-    for (int i = threadIdx.x; i < n_cls * n_cls; i += blockDim.x) lh[i] = 0;
-    __syncthreads();
+    lds_hist_clear(lh, n_cls);
     const long long total = (long long)N * H * W;
     const float sy = arseg_resize_scale(h, H, align != 0), sx = arseg_resize_scale(w, W, align != 0);
-    const bool same = (h == H && w == W);
+    const bool same = (h == H && w == W), count = hist && label;
     for (long long pix = (long long)blockIdx.x * blockDim.x + threadIdx.x; pix < total; pix += (long long)gridDim.x * blockDim.x) {
         const int ox = (int)(pix % W), oy = (int)((pix / W) % H), n = (int)(pix / ((long long)W * H));
-        int y0 = oy, y1 = oy, x0 = ox, x1 = ox; float ly = 0.f, lx = 0.f;
-        if (!same) {
-            arseg_src_index(sy, oy, align != 0, h, y0, y1, ly);
-            arseg_src_index(sx, ox, align != 0, w, x0, x1, lx);
-            ly = fminf(fmaxf(ly, 0.f), 1.f); lx = fminf(fmaxf(lx, 0.f), 1.f);
-        }
-        // torch.argmax semantics: the first maximum wins, a NaN counts as the maximum (the first NaN wins)
-        float best = -INFINITY; int bi = 0; bool best_nan = false;
-        for (int k = 0; k < n_cls; ++k) {
-            const float *b = logits + ((size_t)n * n_cls + k) * h * w;
-            float v;
-            if (same) v = b[(size_t)oy * w + ox];
-            else v = (1.f - ly) * ((1.f - lx) * b[(size_t)y0 * w + x0] + lx * b[(size_t)y0 * w + x1]) +
-                     ly * ((1.f - lx) * b[(size_t)y1 * w + x0] + lx * b[(size_t)y1 * w + x1]);
-            const bool isn = v != v, take = !best_nan & ((v > best) | isn);          // branch free
-            best = take ? v : best; bi = take ? k : bi; best_nan = best_nan | (take & isn);
-        }
-        if (pred) pred[pix] = bi;
-        if (hist && label) {
-            const long long lab = label[pix];
-            if (lab != ignore_label && lab >= 0 && lab < n_cls) atomicAdd(&lh[(int)lab * n_cls + bi], 1u);
+        argmax_pixel(logits, label, pred, lh, count, n, oy, ox, n_cls, h, w, H, W, ignore_label, align, same, sy, sx);
+    }
+    if (hist) lds_hist_flush(lh, hist, n_cls);
+}
+
+// The grouped tail (one histogram per keyframe distance): blockIdx.y walks the frames and the grid-stride loop stays inside one frame, so
+// a workgroup's LDS histogram belongs to one group at a time and is flushed once per frame into hist[group[n]].  A frame whose group id
+// is outside [0, n_groups) gets its labels and counts nowhere.
+__global__ __launch_bounds__(256) void argmax_confusion_grouped_kernel(const float *__restrict__ logits, const int64_t *__restrict__ label,
+                                                                       const int32_t *__restrict__ group, int32_t *__restrict__ pred,
+                                                                       unsigned long long *__restrict__ hist, int N, int n_groups, int n_cls,
+                                                                       int h, int w, int H, int W, int ignore_label, int align) {
+    __shared__ unsigned int lh[1024];
+    const long long per = (long long)H * W;
+    const float sy = arseg_resize_scale(h, H, align != 0), sx = arseg_resize_scale(w, W, align != 0);
+    const bool same = (h == H && w == W);
+    for (int n = blockIdx.y; n < N; n += gridDim.y) {
+        const int g = (hist && label) ? group[n] : -1;
+        const bool count = g >= 0 && g < n_groups;          // uniform over the workgroup
+        if (!count && !pred) continue;
+        if (count) lds_hist_clear(lh, n_cls);
+        for (long long p = (long long)blockIdx.x * blockDim.x + threadIdx.x; p < per; p += (long long)gridDim.x * blockDim.x)
+            argmax_pixel(logits, label, pred, lh, count, n, (int)(p / W), (int)(p % W), n_cls, h, w, H, W, ignore_label, align, same, sy, sx);
+        if (count) {
+            lds_hist_flush(lh, hist + (size_t)g * n_cls * n_cls, n_cls);
+            __syncthreads();          // the next frame clears lh
         }
     }
-    __syncthreads();
-    if (hist)
-        for (int i = threadIdx.x; i < n_cls * n_cls; i += blockDim.x)
-            if (lh[i]) atomicAdd(&hist[i], (unsigned long long)lh[i]);
 }
 
 // The same tail for an exact x S bilinear upsample with align_corners=False, S a power of two (BiSeNetOutput's nn.Upsample(x8),
@@ -874,93 +916,124 @@ __global__ __launch_bounds__(256) void argmax_confusion_kernel(const float *__re
 // pixels from registers -- 4 loads per class and run instead of 4 S; the per-pixel kernel above issues 76 scattered loads per output
 // pixel at 19 classes and is bound by the texture path's instruction rate (77 us per 1024x2048 frame; this one: memory-side trivial).
 // Same taps and weights (arseg_src_index) and the same argmax semantics; the blend is regrouped (see below).
+// One run of frame n: output row oy, low-resolution column j (-1 .. w-1).  Shared by the ungrouped and the grouped kernel.
+template <int S>
+__device__ __forceinline__ void argmax_run(const float *__restrict__ logits, const int64_t *__restrict__ label, int32_t *__restrict__ pred,
+                                           unsigned int *lh, bool count, bool pred_vec, float sc, int n, int oy, int j, int n_cls, int h, int w,
+                                           int ignore_label) {
+    const int H = S * h, W = S * w;
+    int y0, y1; float ly;
+    arseg_src_index(sc, oy, false, h, y0, y1, ly);
+    ly = fminf(fmaxf(ly, 0.f), 1.f);
+    const int x0 = max(j, 0), x1 = min(x0 + 1, w - 1), xs = S * j + S / 2;       // first output column of the run (may be negative for j = -1)
+    float lx[S];
+#pragma unroll
+    for (int r = 0; r < S; ++r) {
+        int a, b;
+        arseg_src_index(sc, min(max(xs + r, 0), W - 1), false, w, a, b, lx[r]);
+        lx[r] = fminf(fmaxf(lx[r], 0.f), 1.f);
+    }
+    float best[S]; int bi[S]; bool bn[S];
+#pragma unroll
+    for (int r = 0; r < S; ++r) { best[r] = -INFINITY; bi[r] = 0; bn[r] = false; }
+    const float *b = logits + (size_t)n * n_cls * h * w;
+    const size_t o00 = (size_t)y0 * w + x0, o01 = (size_t)y0 * w + x1, o10 = (size_t)y1 * w + x0, o11 = (size_t)y1 * w + x1, cs = (size_t)h * w;
+    for (int k0 = 0; k0 < n_cls; k0 += 4) {          // four classes' taps in flight (a class at a time is bound by the load latency)
+        float t[4][4];
+#pragma unroll
+        for (int u = 0; u < 4; ++u) {
+            const float *bk = b + (size_t)min(k0 + u, n_cls - 1) * cs;
+            if (x1 > x0) {          // the two taps of a row are neighbours: one 8-byte load (the kernel is bound by the number of load instructions)
+                // (a 4-byte aligned pair type: the address is odd in floats for every other run -- gfx950 global loads take any dword
+                // address, and the reduced alignment makes that a defined access instead of a misaligned float2)
+                typedef float f32x2_a4 __attribute__((ext_vector_type(2), aligned(4)));
+                const f32x2_a4 a01 = *reinterpret_cast<const f32x2_a4 *>(bk + o00), a11 = *reinterpret_cast<const f32x2_a4 *>(bk + o10);
+                t[u][0] = a01.x; t[u][1] = a01.y; t[u][2] = a11.x; t[u][3] = a11.y;
+            } else {
+                t[u][0] = bk[o00]; t[u][1] = bk[o01]; t[u][2] = bk[o10]; t[u][3] = bk[o11];
+            }
+        }
+#pragma unroll
+        for (int u = 0; u < 4; ++u) {
+            if (k0 + u >= n_cls) break;
+            // the bilinear blend is linear in lx along the run: v(r) = a + lx[r] * b -- one FMA per pixel and class (the expanded form,
+            // 6 operations, made this kernel VALU bound); same value up to fp32 rounding of the regrouped sum
+            const float a = (1.f - ly) * t[u][0] + ly * t[u][2];
+            const float b = (1.f - ly) * (t[u][1] - t[u][0]) + ly * (t[u][3] - t[u][2]);
+#pragma unroll
+            for (int r = 0; r < S; ++r) {          // branch free (the short-circuit form compiles to a divergent branch per pixel and class)
+                const float v = fmaf(lx[r], b, a);
+                const bool isn = v != v, take = !bn[r] & ((v > best[r]) | isn);
+                best[r] = take ? v : best[r];
+                bi[r] = take ? k0 + u : bi[r];
+                bn[r] = bn[r] | (take & isn);
+            }
+        }
+    }
+    const long long row = ((long long)n * H + oy) * W;
+    const bool whole = xs >= 0 && xs + S <= W;              // interior run: S consecutive labels, S/2 * 4 bytes aligned (W = S w, xs = S j + S/2)
+    if (pred && whole && S >= 4 && pred_vec) {               // vector stores (scalar ones: 4 bytes per lane at a 4 S byte stride)
+        if constexpr (S == 8) {
+            *reinterpret_cast<int4 *>(pred + row + xs) = int4{bi[0], bi[1], bi[2], bi[3]};
+            *reinterpret_cast<int4 *>(pred + row + xs + 4) = int4{bi[S > 4 ? 4 : 0], bi[S > 5 ? 5 : 0], bi[S > 6 ? 6 : 0], bi[S > 7 ? 7 : 0]};
+        } else {
+            *reinterpret_cast<int2 *>(pred + row + xs) = int2{bi[0], bi[1]};
+            *reinterpret_cast<int2 *>(pred + row + xs + 2) = int2{bi[S > 2 ? 2 : 0], bi[S > 3 ? 3 : 0]};
+        }
+    }
+#pragma unroll
+    for (int r = 0; r < S; ++r) {
+        const int ox = xs + r;
+        if (ox < 0 || ox >= W) continue;
+        if (pred && !(whole && S >= 4 && pred_vec)) pred[row + ox] = bi[r];
+        if (count) {
+            const long long lab = label[row + ox];
+            if (lab != ignore_label && lab >= 0 && lab < n_cls) atomicAdd(&lh[(int)lab * n_cls + bi[r]], 1u);
+        }
+    }
+}
+
 template <int S>
 __global__ __launch_bounds__(256) void argmax_confusion_up_kernel(const float *__restrict__ logits, const int64_t *__restrict__ label,
                                                                   int32_t *__restrict__ pred, unsigned long long *__restrict__ hist,
                                                                   int N, int n_cls, int h, int w, int ignore_label) {
     __shared__ unsigned int lh[1024];
-    for (int i = threadIdx.x; i < n_cls * n_cls; i += blockDim.x) lh[i] = 0;
-    __syncthreads();
-    const int H = S * h, W = S * w, runs = w + 1;
+    lds_hist_clear(lh, n_cls);
+    const int H = S * h, runs = w + 1;
     const long long total = (long long)N * H * runs;
     const bool pred_vec = (reinterpret_cast<uintptr_t>(pred) & 15u) == 0;      // 16 / 8-byte label stores need an aligned base (rows are multiples of S)
     const float sc = arseg_resize_scale(h, H, false);          // = 1 / S exactly
+    const bool count = hist && label;
     for (long long idx = (long long)blockIdx.x * blockDim.x + threadIdx.x; idx < total; idx += (long long)gridDim.x * blockDim.x) {
         const int j = (int)(idx % runs) - 1, oy = (int)((idx / runs) % H), n = (int)(idx / ((long long)runs * H));
-        int y0, y1; float ly;
-        arseg_src_index(sc, oy, false, h, y0, y1, ly);
-        ly = fminf(fmaxf(ly, 0.f), 1.f);
-        const int x0 = max(j, 0), x1 = min(x0 + 1, w - 1), xs = S * j + S / 2;       // first output column of the run (may be negative for j = -1)
-        float lx[S];
-#pragma unroll
-        for (int r = 0; r < S; ++r) {
-            int a, b;
-            arseg_src_index(sc, min(max(xs + r, 0), W - 1), false, w, a, b, lx[r]);
-            lx[r] = fminf(fmaxf(lx[r], 0.f), 1.f);
-        }
-        float best[S]; int bi[S]; bool bn[S];
-#pragma unroll
-        for (int r = 0; r < S; ++r) { best[r] = -INFINITY; bi[r] = 0; bn[r] = false; }
-        const float *b = logits + (size_t)n * n_cls * h * w;
-        const size_t o00 = (size_t)y0 * w + x0, o01 = (size_t)y0 * w + x1, o10 = (size_t)y1 * w + x0, o11 = (size_t)y1 * w + x1, cs = (size_t)h * w;
-        for (int k0 = 0; k0 < n_cls; k0 += 4) {          // four classes' taps in flight (a class at a time is bound by the load latency)
-            float t[4][4];
-#pragma unroll
-            for (int u = 0; u < 4; ++u) {
-                const float *bk = b + (size_t)min(k0 + u, n_cls - 1) * cs;
-                if (x1 > x0) {          // the two taps of a row are neighbours: one 8-byte load (the kernel is bound by the number of load instructions)
-                    // (a 4-byte aligned pair type: the address is odd in floats for every other run -- gfx950 global loads take any dword
-                    // address, and the reduced alignment makes that a defined access instead of a misaligned float2)
-                    typedef float f32x2_a4 __attribute__((ext_vector_type(2), aligned(4)));
-                    const f32x2_a4 a01 = *reinterpret_cast<const f32x2_a4 *>(bk + o00), a11 = *reinterpret_cast<const f32x2_a4 *>(bk + o10);
-                    t[u][0] = a01.x; t[u][1] = a01.y; t[u][2] = a11.x; t[u][3] = a11.y;
-                } else {
-                    t[u][0] = bk[o00]; t[u][1] = bk[o01]; t[u][2] = bk[o10]; t[u][3] = bk[o11];
-                }
-            }
-#pragma unroll
-            for (int u = 0; u < 4; ++u) {
-                if (k0 + u >= n_cls) break;
-                // the bilinear blend is linear in lx along the run: v(r) = a + lx[r] * b -- one FMA per pixel and class (the expanded form,
-                // 6 operations, made this kernel VALU bound); same value up to fp32 rounding of the regrouped sum
-                const float a = (1.f - ly) * t[u][0] + ly * t[u][2];
-                const float b = (1.f - ly) * (t[u][1] - t[u][0]) + ly * (t[u][3] - t[u][2]);
-#pragma unroll
-                for (int r = 0; r < S; ++r) {          // branch free (the short-circuit form compiles to a divergent branch per pixel and class)
-                    const float v = fmaf(lx[r], b, a);
-                    const bool isn = v != v, take = !bn[r] & ((v > best[r]) | isn);
-                    best[r] = take ? v : best[r];
-                    bi[r] = take ? k0 + u : bi[r];
-                    bn[r] = bn[r] | (take & isn);
-                }
-            }
-        }
-        const long long row = ((long long)n * H + oy) * W;
-        const bool whole = xs >= 0 && xs + S <= W;              // interior run: S consecutive labels, S/2 * 4 bytes aligned (W = S w, xs = S j + S/2)
-        if (pred && whole && S >= 4 && pred_vec) {               // vector stores (scalar ones: 4 bytes per lane at a 4 S byte stride)
-            if constexpr (S == 8) {
-                *reinterpret_cast<int4 *>(pred + row + xs) = int4{bi[0], bi[1], bi[2], bi[3]};
-                *reinterpret_cast<int4 *>(pred + row + xs + 4) = int4{bi[S > 4 ? 4 : 0], bi[S > 5 ? 5 : 0], bi[S > 6 ? 6 : 0], bi[S > 7 ? 7 : 0]};
-            } else {
-                *reinterpret_cast<int2 *>(pred + row + xs) = int2{bi[0], bi[1]};
-                *reinterpret_cast<int2 *>(pred + row + xs + 2) = int2{bi[S > 2 ? 2 : 0], bi[S > 3 ? 3 : 0]};
-            }
-        }
-#pragma unroll
-        for (int r = 0; r < S; ++r) {
-            const int ox = xs + r;
-            if (ox < 0 || ox >= W) continue;
-            if (pred && !(whole && S >= 4 && pred_vec)) pred[row + ox] = bi[r];
-            if (hist && label) {
-                const long long lab = label[row + ox];
-                if (lab != ignore_label && lab >= 0 && lab < n_cls) atomicAdd(&lh[(int)lab * n_cls + bi[r]], 1u);
-            }
+        argmax_run<S>(logits, label, pred, lh, count, pred_vec, sc, n, oy, j, n_cls, h, w, ignore_label);
+    }
+    if (hist) lds_hist_flush(lh, hist, n_cls);
+}
+
+// The grouped form of the run kernel: frame-aligned like argmax_confusion_grouped_kernel.
+template <int S>
+__global__ __launch_bounds__(256) void argmax_confusion_up_grouped_kernel(const float *__restrict__ logits, const int64_t *__restrict__ label,
+                                                                          const int32_t *__restrict__ group, int32_t *__restrict__ pred,
+                                                                          unsigned long long *__restrict__ hist, int N, int n_groups, int n_cls,
+                                                                          int h, int w, int ignore_label) {
+    __shared__ unsigned int lh[1024];
+    const int H = S * h, runs = w + 1;
+    const long long per = (long long)H * runs;
+    const bool pred_vec = (reinterpret_cast<uintptr_t>(pred) & 15u) == 0;
+    const float sc = arseg_resize_scale(h, H, false);
+    for (int n = blockIdx.y; n < N; n += gridDim.y) {
+        const int g = (hist && label) ? group[n] : -1;
+        const bool count = g >= 0 && g < n_groups;          // uniform over the workgroup
+        if (!count && !pred) continue;
+        if (count) lds_hist_clear(lh, n_cls);
+        for (long long p = (long long)blockIdx.x * blockDim.x + threadIdx.x; p < per; p += (long long)gridDim.x * blockDim.x)
+            argmax_run<S>(logits, label, pred, lh, count, pred_vec, sc, n, (int)(p / runs), (int)(p % runs) - 1, n_cls, h, w, ignore_label);
+        if (count) {
+            lds_hist_flush(lh, hist + (size_t)g * n_cls * n_cls, n_cls);
+            __syncthreads();
         }
     }
-    __syncthreads();
-    if (hist)
-        for (int i = threadIdx.x; i < n_cls * n_cls; i += blockDim.x)
-            if (lh[i]) atomicAdd(&hist[i], (unsigned long long)lh[i]);
 }
 
 }  // namespace
@@ -1332,5 +1405,31 @@ extern "C" int arseg_argmax_confusion_fwd(const float *logits, const int64_t *la
     }
     hipLaunchKernelGGL(argmax_confusion_kernel, dim3(grid_for((long long)N * H * W, 1024)), dim3(256), 0, arseg_stream(stream), logits,
                        label, pred, hh, N, n_cls, h, w, H, W, ignore_label, align_corners);
+    return arseg_launch_status();
+}
+
+// One histogram per group (keyframe distance): frame n counts into hist[group[n]].  blockIdx.y walks the frames; per frame as many
+// workgroups as the ungrouped launch spends on a frame of the same batch, so the flushes stay few.
+extern "C" int arseg_argmax_confusion_grouped_fwd(const float *logits, const int64_t *label, const int32_t *group, int32_t *pred, int64_t *hist,
+                                                  int N, int n_groups, int n_cls, int h, int w, int H, int W, int ignore_label,
+                                                  int align_corners, arseg_stream_t stream) {
+    ARSEG_CHECK_PTR(logits); ARSEG_CHECK_POS(N); ARSEG_CHECK_POS(n_cls); ARSEG_CHECK_POS(h); ARSEG_CHECK_POS(w); ARSEG_CHECK_POS(H); ARSEG_CHECK_POS(W);
+    if (n_groups < 1 || n_cls > 32) return ARSEG_EINVAL;
+    if (!pred && !(hist && label)) return ARSEG_EINVAL;
+    if (hist && !group) return ARSEG_EINVAL;
+    unsigned long long *hh = reinterpret_cast<unsigned long long *>(hist);
+    hipStream_t st = arseg_stream(stream);
+    const int gy = N < 65535 ? N : 65535, S = H / h;
+    if (!align_corners && S * h == H && S * w == W && (S == 2 || S == 4 || S == 8)) {
+        const int per = grid_for((long long)H * (w + 1), 4096), share = 4096 / gy;
+        const dim3 g(per < share ? per : (share < 1 ? 1 : share), gy);
+        if (S == 8) hipLaunchKernelGGL(argmax_confusion_up_grouped_kernel<8>, g, dim3(256), 0, st, logits, label, group, pred, hh, N, n_groups, n_cls, h, w, ignore_label);
+        else if (S == 4) hipLaunchKernelGGL(argmax_confusion_up_grouped_kernel<4>, g, dim3(256), 0, st, logits, label, group, pred, hh, N, n_groups, n_cls, h, w, ignore_label);
+        else hipLaunchKernelGGL(argmax_confusion_up_grouped_kernel<2>, g, dim3(256), 0, st, logits, label, group, pred, hh, N, n_groups, n_cls, h, w, ignore_label);
+        return arseg_launch_status();
+    }
+    const int per = grid_for((long long)H * W, 1024), share = 1024 / gy;
+    hipLaunchKernelGGL(argmax_confusion_grouped_kernel, dim3(per < share ? per : (share < 1 ? 1 : share), gy), dim3(256), 0, st, logits, label, group,
+                       pred, hh, N, n_groups, n_cls, h, w, H, W, ignore_label, align_corners);
     return arseg_launch_status();
 }

@@ -5,6 +5,8 @@
 * ``EvalConstRes`` / ``EvalAlterRes`` -- evaluation.py:90-144 / 148-215, same call signatures
   (``dl`` is any iterable of the reference's sample tuples).  Networks may be bare modules or
   wrapped in ``nn.DataParallel`` (the reference addresses ``net.module`` on the hot path).
+* ``EvalByDistance`` / ``EvalTable`` / ``table_filename`` -- the reference's result table (mIoU at keyframe distance
+  0 .. GOP-1 and their mean, evaluation.py:272-303, 308-386, 406-439) from ONE pass: one confusion matrix per distance.
 * ``alter_res_step_fast`` -- the same non-keyframe step on the kernel-native layouts (int16 MVs in,
   MV resize + warp + CReFF + head fused), used by the GOP runner and bench.py.
 
@@ -15,6 +17,7 @@ from __future__ import annotations
 
 import os
 
+import numpy as np
 import torch
 import torch.distributed as dist
 
@@ -71,12 +74,13 @@ class EvalConstRes(object):
         return hist
 
 
-def _range_safe(run, dl, n_classes, reset=None):
+def _range_safe_hist(run, dl, reset=None):
     """Runs an evaluation pass (``run()`` returns this rank's confusion matrix); if the split-fp16 convs met an activation outside their
     operand range (the sticky device word of ops.range_tripped -- read once, after the pass, which ends in a host read anyway), the pass is
     repeated on the fp32 matrix-core back end.  With torch.distributed initialised the decision is COLLECTIVE (max of the ranks' flags: a
-    rank that did not trip repeats as well, so every rank issues the same collectives) and the histogram is all-reduced once, on the final
-    pass only (evaluation.py:134-135).  A one-shot iterator cannot be replayed: that raises instead of returning a possibly clamped result."""
+    rank that did not trip repeats as well, so every rank issues the same collectives); the caller all-reduces the histogram once, from
+    the final pass only (evaluation.py:134-135).  A one-shot iterator cannot be replayed: that raises instead of returning a possibly
+    clamped result.  Returns the final pass's histogram of this rank."""
     ops.range_tripped()                      # clear what earlier launches left
     hist = run()
     tripped = bool(ops.range_tripped())
@@ -96,7 +100,11 @@ def _range_safe(run, dl, n_classes, reset=None):
             hist = run()
         finally:
             ops.set_conv_math(prev)
-    return _miou(hist, n_classes)
+    return hist
+
+
+def _range_safe(run, dl, n_classes, reset=None):
+    return _miou(_range_safe_hist(run, dl, reset), n_classes)
 
 
 def _resize_frames(imgs, h, w):
@@ -138,27 +146,152 @@ class EvalAlterRes(object):
     def _run(self, highres_net, net, dl, n_classes):
         hist = torch.zeros((n_classes, n_classes), dtype=torch.int64, device="cuda")
         lr_net = _unwrap(net)
-        last_ref, last_p = None, None
+        cache = [None, None]
         for imgs, label, _, ref_imgs, flow in dl:
             label = label.cuda()
-            imgs = imgs.cuda()
-            flow = flow.cuda()
-            ref_imgs = ref_imgs.cuda()
-            if self.cache_keyframe and last_ref is not None and last_ref.shape == ref_imgs.shape and torch.equal(last_ref, ref_imgs):
-                highres_ref_p = last_p
-            else:
-                highres_ref_p = highres_net(ref_imgs)[-1]                                     # :173-174
-                self.hr_forwards += 1
-                last_ref, last_p = ref_imgs, highres_ref_p
-            flow = resize_flow(flow, highres_ref_p.shape[-2], highres_ref_p.shape[-1])       # :177-180
-            highres_ref_p = warpFeature(highres_ref_p, flow)                                 # :183
-            N, C, H, W = imgs.shape
-            h, w = _downscale_hw(H, W, self.scale)
-            imgs = _resize_frames(imgs, h, w)                                                # :186-188
-            out_p = lr_net.forward_phase1(imgs)[-1]                                          # :190-191
-            out, _ = lr_net.forward_phase2(out_p, highres_ref_p)                             # :193
+            out = self._logits(highres_net, lr_net, imgs, ref_imgs, flow, cache)
             _, hist = ops.argmax_confusion(out, label, label.shape[-2], label.shape[-1], hist, self.ignore_label, want_pred=False)
         return hist
+
+    def _logits(self, highres_net, lr_net, imgs, ref_imgs, flow, cache):
+        """The loop body up to the logits.  ``cache`` = [reference frames, their HR feature] of the previous sample."""
+        imgs = imgs.cuda()
+        flow = flow.cuda()
+        ref_imgs = ref_imgs.cuda()
+        last_ref, last_p = cache
+        if self.cache_keyframe and last_ref is not None and last_ref.shape == ref_imgs.shape and torch.equal(last_ref, ref_imgs):
+            highres_ref_p = last_p
+        else:
+            highres_ref_p = highres_net(ref_imgs)[-1]                                     # :173-174
+            self.hr_forwards += 1
+            cache[0], cache[1] = ref_imgs, highres_ref_p
+        flow = resize_flow(flow, highres_ref_p.shape[-2], highres_ref_p.shape[-1])       # :177-180
+        highres_ref_p = warpFeature(highres_ref_p, flow)                                 # :183
+        N, C, H, W = imgs.shape
+        h, w = _downscale_hw(H, W, self.scale)
+        imgs = _resize_frames(imgs, h, w)                                                # :186-188
+        out_p = lr_net.forward_phase1(imgs)[-1]                                          # :190-191
+        out, _ = lr_net.forward_phase2(out_p, highres_ref_p)                             # :193
+        return out
+
+
+class EvalByDistance(EvalAlterRes):
+    """The reference's result table from one pass: the mIoU at every keyframe distance d = 0 .. gop-1 (its CLI runs one evaluation per
+    distance, evaluation.py:317-376).  ``dl`` yields the reference's sample tuples, of any distance and in any order:
+
+    * ``(imgs, label, _)``: keyframe samples -- through the HR net at scale 1.0 and counted at d = 0 (evaluation.py:358-363);
+    * ``(imgs, label, _, ref_imgs, flow, dist)``: EvalAlterRes' sample with the distance(s) appended, an int or an int tensor [N] with
+      values 1 .. gop-1 -- EvalAlterRes' loop body, counted at ``dist`` (frames of one batch may differ).
+
+    One [gop, n_cls, n_cls] histogram, all-reduced once under torch.distributed; the operand-range fallback of the other evaluators.
+    Returns an ``EvalTable``.  ``cache_keyframe`` / ``hr_forwards`` as in EvalAlterRes (the keyframe feature of non-keyframe samples)."""
+
+    def __init__(self, scale=0.5, ignore_label=255, gop=12, cache_keyframe=False):
+        super().__init__(scale, ignore_label, cache_keyframe)
+        if gop < 1:
+            raise ValueError(f"gop must be positive, got {gop}")
+        self.gop = gop
+
+    def __call__(self, highres_net, net, dl, n_classes):
+        first = self.hr_forwards
+
+        def reset():
+            self.hr_forwards = first
+
+        hist = _range_safe_hist(lambda: self._run(highres_net, net, dl, n_classes), dl, reset)
+        if dist.is_available() and dist.is_initialized():
+            dist.all_reduce(hist, dist.ReduceOp.SUM)                 # integer counts: exact
+        return EvalTable(hist)
+
+    def _groups(self, d, N):
+        if torch.is_tensor(d) and d.is_cuda:                 # stays on the device: no host read (ids outside 0 .. gop-1 count nowhere)
+            return d.reshape(-1).to(torch.int32)
+        ds = [int(v) for v in d.reshape(-1).tolist()] if torch.is_tensor(d) else [int(d)] * N
+        if len(ds) == 1 and N > 1:
+            ds = ds * N
+        if any(not 1 <= v < self.gop for v in ds):
+            raise ValueError(f"keyframe distance of a non-keyframe sample must be in 1 .. {self.gop - 1}, got {ds}")
+        return ds
+
+    def _run(self, highres_net, net, dl, n_classes):
+        hist = torch.zeros((self.gop, n_classes, n_classes), dtype=torch.int64, device="cuda")
+        lr_net = _unwrap(net)
+        cache = [None, None]
+        for sample in dl:
+            label = sample[1].cuda()
+            N = label.shape[0]
+            if len(sample) == 3:
+                out = highres_net(sample[0].cuda())[0]                # EvalConstRes(scale=1.0), evaluation.py:363
+                groups = [0] * N
+            elif len(sample) == 6:
+                imgs, _, _, ref_imgs, flow, d = sample
+                out = self._logits(highres_net, lr_net, imgs, ref_imgs, flow, cache)
+                groups = self._groups(d, N)
+            else:
+                raise ValueError(f"EvalByDistance takes (imgs, label, _) or (imgs, label, _, ref_imgs, flow, dist) samples, got {len(sample)} elements")
+            _, hist = ops.argmax_confusion_grouped(out, label, groups, self.gop, label.shape[-2], label.shape[-1], hist, self.ignore_label,
+                                                   want_pred=False)
+        return hist
+
+
+def table_filename(dataset, backbone, mode, scale, gop, bitrate):
+    """File name of the reference's result tables (evaluation.py:299-301 "HR", :382-384 "AR", :435-437 "LR")."""
+    if mode not in ("HR", "AR", "LR"):
+        raise ValueError(f"mode must be 'HR', 'AR' or 'LR', got {mode!r}")
+    tag = "1.0x" if mode == "HR" else f"AR-{scale}x" if mode == "AR" else f"{scale}x"
+    return f"{dataset}-{backbone}-{tag}-resolution-exp-GOP{gop}-{bitrate}-evaluation.txt"
+
+
+def _ious(hist):
+    """evaluation.py:136 on one confusion matrix, in float32 (a class absent from label and prediction: 0 / 0 = NaN)."""
+    hist = hist.float()
+    return hist.diag() / (hist.sum(dim=0) + hist.sum(dim=1) - hist.diag())
+
+
+class EvalTable(object):
+    """mIoU per group (keyframe distance) from a [G, n_cls, n_cls] confusion histogram -- the 13 numbers of the reference's result files
+    at G = 12.  Plain torch / numpy; works on CPU tensors.
+
+    ``hist`` the histogram; ``iou`` float32 [G, n_cls]; ``miou`` G Python floats, each what EvalConstRes / EvalAlterRes return on that
+    group's samples alone (same float32 arithmetic, NaN where a class is absent from both label and prediction); ``mean`` their float64
+    mean as the reference takes it (np.array(mIoU_list).mean(), evaluation.py:298)."""
+
+    def __init__(self, hist):
+        hist = torch.as_tensor(hist)
+        if hist.dim() != 3 or hist.shape[1] != hist.shape[2]:
+            raise ValueError(f"EvalTable takes a [G, n_cls, n_cls] histogram, got {tuple(hist.shape)}")
+        self.hist = hist
+        ious = [_ious(h) for h in hist]
+        self.miou = [i.mean().item() for i in ious]          # on the histogram's device, as _miou does
+        self.iou = torch.stack(ious).cpu()
+
+    @property
+    def mean(self):
+        return np.array(self.miou).mean()
+
+    def as_array(self):
+        """The G values and their mean: what the reference writes (evaluation.py:298-303)."""
+        return np.array(list(self.miou) + [self.mean])
+
+    def pooled(self, groups=None):
+        """mIoU of the summed histogram (``groups``: only these; default all) -- what EvalAlterRes reports for the same samples."""
+        if self.hist is None:
+            raise ValueError("a table read from a file holds the mIoU values only, not the histogram")
+        h = self.hist if groups is None else self.hist[list(groups)]
+        return _ious(h.sum(dim=0)).mean().item()
+
+    def save(self, path):
+        np.savetxt(path, self.as_array())
+
+    @classmethod
+    def load(cls, path):
+        """A table written by ``save`` or by the reference: the floats only (``hist`` and ``iou`` are None)."""
+        vals = np.atleast_1d(np.loadtxt(path))
+        if vals.ndim != 1 or vals.size < 2:
+            raise ValueError(f"{path}: expected G mIoU values and their mean, one per line")
+        t = cls.__new__(cls)
+        t.hist, t.iou, t.miou = None, None, [float(v) for v in vals[:-1]]
+        return t
 
 
 def alter_res_step_fast(lr_net, ref_p_nhwc, img, mv_q, scale=0.5):
@@ -207,11 +340,15 @@ def alter_res_phase2(lr_net, feat, ref_ps, mv_qs):
     return _unwrap(lr_net).phase2_warp(feat, list(ref_ps), mv_qs)[0]
 
 
-def alter_res_batch_pred(lr_net, ref_ps, imgs, mv_qs, scale=0.5, labels=None, hist=None, ignore_label=255):
+def alter_res_batch_pred(lr_net, ref_ps, imgs, mv_qs, scale=0.5, labels=None, hist=None, ignore_label=255, groups=None, n_groups=None):
     """B non-keyframes through backbone + warp + CReFF + head and the evaluator tail (evaluation.py:201-209) in one go:
     -> (pred int32 [B,H,W], hist int64 [n_cls,n_cls] | None).  For BiSeNet the head's 1/8-resolution logits go straight into
     the argmax (x8 upsample fused); the other networks' logits are resized (align_corners=True,
-    the identity for PSPNet) inside the same argmax kernel."""
+    the identity for PSPNet) inside the same argmax kernel.  ``groups`` (one id per frame, e.g. the keyframe distances
+    ``range(1, 12)`` of a GOP; see ops.argmax_confusion_grouped) with ``n_groups``: hist is [n_groups,n_cls,n_cls], frame b counts into
+    hist[groups[b]]; pred is unchanged."""
+    if groups is not None and n_groups is None:
+        raise ValueError("groups needs n_groups (the number of histograms)")
     lr_net = _unwrap(lr_net)
     B, _, H, W = imgs.shape
     h, w = _downscale_hw(H, W, scale)
@@ -223,4 +360,6 @@ def alter_res_batch_pred(lr_net, ref_ps, imgs, mv_qs, scale=0.5, labels=None, hi
             lo, fused_up = ops.resize_nchw(lo, 8 * lo.shape[-2], 8 * lo.shape[-1], _lib.BILINEAR, False), False
     else:
         lo, _ = lr_net.phase2_warp(feat, list(ref_ps), mv_qs)
+    if groups is not None:
+        return ops.argmax_confusion_grouped(lo, labels, groups, n_groups, H, W, hist, ignore_label, align_corners=not fused_up)
     return ops.argmax_confusion(lo, labels, H, W, hist, ignore_label, align_corners=not fused_up)

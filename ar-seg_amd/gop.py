@@ -70,6 +70,13 @@ def neighbor_plan(n_gops: int, gop: int, world: int) -> List[List[Tuple[int, int
     return plan
 
 
+def plan_groups(plan) -> List[int]:
+    """Histogram group (= keyframe distance d) of every frame of a rank's plan, in plan order: the ``groups`` argument of
+    ops.argmax_confusion_grouped / evaluation.alter_res_batch_pred for the batch ``run_batched`` / ``run_overlapped`` process.  ``plan``: a
+    GopRunner or its ``plan`` list; the same for every deal."""
+    return [d for (_, d) in getattr(plan, "plan", plan)]
+
+
 class GopRunner:
     """key_fn(keyframe) -> ref_p tensor; nonkey_fn(ref_p, frame, mv) -> output.
 

@@ -381,3 +381,60 @@ def argmax_confusion(logits: torch.Tensor, label: Optional[torch.Tensor], H: int
     launch("argmax_confusion", _lib.load().arseg_argmax_confusion_fwd, _ptr(logits), _ptr(label), _ptr(pred), _ptr(hist if label is not None else None), N,
                                                  n_cls, h, w, H, W, ignore_label, 1 if align_corners else 0, _stream())
     return pred, hist
+
+
+_group_uploads = {}          # (group ids, device) -> int32 device tensor: a replayed GOP step uploads nothing
+
+
+def _group_ids(groups, n_groups: int):
+    """A Python sequence of group ids, range-checked on the host -> tuple; a tensor -> None (never read here)."""
+    if n_groups < 1:
+        raise ValueError(f"n_groups must be positive, got {n_groups}")
+    if torch.is_tensor(groups):
+        return None
+    ids = tuple(int(g) for g in groups)
+    bad = [g for g in ids if not 0 <= g < n_groups]
+    if bad:
+        raise ValueError(f"group id {bad[0]} is outside [0, {n_groups})")
+    return ids
+
+
+def _groups_tensor(groups, ids, N: int, device) -> torch.Tensor:
+    if ids is None:                      # a tensor is taken as is: no host read, ids outside [0, n_groups) count nowhere
+        if not groups.is_cuda or groups.dtype != torch.int32 or groups.dim() != 1 or groups.shape[0] != N:
+            raise _lib.ArsegError(f"groups: expected an int32 GPU tensor [{N}], got {groups.dtype} {tuple(groups.shape)} on {groups.device}")
+        return groups.contiguous()
+    if len(ids) != N:
+        raise ValueError(f"groups names {len(ids)} frames, the batch has {N}")
+    key = (ids, str(device))
+    t = _group_uploads.get(key)
+    if t is None:
+        if len(_group_uploads) >= 256:
+            _group_uploads.clear()
+        t = _group_uploads[key] = torch.tensor(ids, dtype=torch.int32, device=device)
+    return t
+
+
+def argmax_confusion_grouped(logits: torch.Tensor, label: Optional[torch.Tensor], groups, n_groups: int, H: int, W: int,
+                             hist: Optional[torch.Tensor] = None, ignore_label: int = 255, want_pred: bool = True, align_corners: bool = True):
+    """The evaluator tail with one confusion matrix per group of frames (the reference reports the mIoU per keyframe distance,
+    evaluation.py:272-303): frame n counts into hist[groups[n]].  Returns (pred int32 [N,H,W] or None, hist int64 [n_groups,n_cls,n_cls]
+    or None); pred is bit-equal to ``argmax_confusion``'s.  ``groups``: an int32 GPU tensor [N] (taken as is; a frame whose id is outside
+    [0, n_groups) is labelled and counted nowhere) or a sequence of ints (range-checked here, uploaded once per distinct sequence)."""
+    ids = _group_ids(groups, n_groups)
+    _need_gpu(logits)
+    logits = logits.contiguous()
+    N, n_cls, h, w = logits.shape
+    pred = torch.empty((N, H, W), dtype=torch.int32, device=logits.device) if want_pred else None
+    grp = None
+    if label is not None:
+        _need_gpu(label, dtype=torch.int64)
+        label = label.contiguous()
+        grp = _groups_tensor(groups, ids, N, logits.device)
+        if hist is None:
+            hist = torch.zeros((n_groups, n_cls, n_cls), dtype=torch.int64, device=logits.device)
+        elif tuple(hist.shape) != (n_groups, n_cls, n_cls) or hist.dtype != torch.int64 or not hist.is_cuda or not hist.is_contiguous():
+            raise _lib.ArsegError(f"hist: expected a contiguous int64 GPU tensor [{n_groups},{n_cls},{n_cls}], got {hist.dtype} {tuple(hist.shape)}")
+    launch("argmax_confusion_grouped", _lib.load().arseg_argmax_confusion_grouped_fwd, _ptr(logits), _ptr(label), _ptr(grp), _ptr(pred),
+           _ptr(hist if label is not None else None), N, n_groups, n_cls, h, w, H, W, ignore_label, 1 if align_corners else 0, _stream())
+    return pred, hist

@@ -507,6 +507,16 @@ int arseg_warp_mvq16_shared_fwd(const void *feature, long long feat_n_stride, in
 int arseg_argmax_confusion_fwd(const float *logits, const int64_t *label, int32_t *pred, int64_t *hist, int N,
                                int n_cls, int h, int w, int H, int W, int ignore_label, int align_corners, arseg_stream_t stream);
 
+/* The same tail with one histogram per group of frames (the reference's result table is the mIoU per keyframe distance,
+ * evaluation.py:272-303, 308-386): group = int32 [N] on the device, frame n counts into hist[group[n]]; hist: int64
+ * [n_groups][n_cls*n_cls], accumulated.  A frame whose group id is outside [0, n_groups) gets its pred and counts nowhere.
+ * pred is bit-equal to arseg_argmax_confusion_fwd's on the same input (same taps, blend order and argmax rule, both the per-pixel route
+ * and the x2 / x4 / x8 align_corners == 0 run route).  pred or hist/label may be NULL; hist without group, n_groups < 1 and
+ * n_cls > 32 are ARSEG_EINVAL. */
+int arseg_argmax_confusion_grouped_fwd(const float *logits, const int64_t *label, const int32_t *group, int32_t *pred, int64_t *hist,
+                                       int N, int n_groups, int n_cls, int h, int w, int H, int W, int ignore_label, int align_corners,
+                                       arseg_stream_t stream);
+
 /* ---------------------------------------------------------------------------------------------
  * Measurement aids (no reference counterpart; BASELINE.md section 3: roofline fractions are reported against the datasheet peaks AND
  * against on-box micro-benchmarks).  bench.py times each with HIP events and prints `peaks_measured`.
