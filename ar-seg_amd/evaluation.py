@@ -112,6 +112,13 @@ def _resize_frames(imgs, h, w):
     return ops.resize_nchw(imgs, h, w, _lib.BILINEAR, True)
 
 
+def _same_frames(a, b):
+    """torch.equal for float frames; ingest.DecodedFrames compare their planes (both on the GPU, one host read as before)."""
+    if torch.is_tensor(a) and torch.is_tensor(b):
+        return torch.equal(a, b)
+    return type(a) is type(b) and not torch.is_tensor(a) and a.equal(b)
+
+
 def _miou(hist, n_classes):
     hist = hist.float()
     if dist.is_available() and dist.is_initialized():
@@ -159,7 +166,7 @@ class EvalAlterRes(object):
         flow = flow.cuda()
         ref_imgs = ref_imgs.cuda()
         last_ref, last_p = cache
-        if self.cache_keyframe and last_ref is not None and last_ref.shape == ref_imgs.shape and torch.equal(last_ref, ref_imgs):
+        if self.cache_keyframe and last_ref is not None and last_ref.shape == ref_imgs.shape and _same_frames(last_ref, ref_imgs):
             highres_ref_p = last_p
         else:
             highres_ref_p = highres_net(ref_imgs)[-1]                                     # :173-174
@@ -169,8 +176,11 @@ class EvalAlterRes(object):
         highres_ref_p = warpFeature(highres_ref_p, flow)                                 # :183
         N, C, H, W = imgs.shape
         h, w = _downscale_hw(H, W, self.scale)
-        imgs = _resize_frames(imgs, h, w)                                                # :186-188
-        out_p = lr_net.forward_phase1(imgs)[-1]                                          # :190-191
+        if torch.is_tensor(imgs):
+            imgs = _resize_frames(imgs, h, w)                                            # :186-188
+            out_p = lr_net.forward_phase1(imgs)[-1]                                      # :190-191
+        else:                                                                            # 8-bit decoder frames: downscale fused into the ingest
+            out_p = ops.as_nchw(lr_net.phase1_nhwc4(ops.ingest_input(imgs, h, w, lr_net.storage_dtype), aux=ops.config.aux_outputs)[-1])
         out, _ = lr_net.forward_phase2(out_p, highres_ref_p)                             # :193
         return out
 
@@ -304,7 +314,7 @@ def alter_res_step_fast(lr_net, ref_p_nhwc, img, mv_q, scale=0.5):
     lr_net = _unwrap(lr_net)
     N, C, H, W = img.shape
     h, w = _downscale_hw(H, W, scale)
-    feat = lr_net.phase1_nhwc4(ops.frame_ingest(img, h, w, lr_net.storage_dtype), aux=ops.config.aux_outputs)[-1]     # a3 + phase 1
+    feat = lr_net.phase1_nhwc4(ops.ingest_input(img, h, w, lr_net.storage_dtype), aux=ops.config.aux_outputs)[-1]     # a3 + phase 1
     return lr_net.phase2_warp(feat, [ref_p_nhwc[i] for i in range(N)], mv_q)      # a2 + a1 + CReFF + head
 
 
@@ -322,7 +332,7 @@ def alter_res_batch_fast(lr_net, ref_ps, imgs, mv_qs, scale=0.5):
         outs = [alter_res_batch_fast(lr_net, ref_ps[i:i + sub], imgs[i:i + sub], mv_qs[i:i + sub], scale) for i in range(0, B, sub)]
         return torch.cat([o[0] for o in outs]), torch.cat([o[1] for o in outs])
     h, w = _downscale_hw(H, W, scale)
-    feat = lr_net.phase1_nhwc4(ops.frame_ingest(imgs, h, w, lr_net.storage_dtype), aux=ops.config.aux_outputs)[-1]     # a3 + phase 1, batched
+    feat = lr_net.phase1_nhwc4(ops.ingest_input(imgs, h, w, lr_net.storage_dtype), aux=ops.config.aux_outputs)[-1]     # a3 + phase 1, batched
     return lr_net.phase2_warp(feat, list(ref_ps), mv_qs)               # a2 + a1 (each frame has its own MV map) + CReFF + head
 
 
@@ -332,7 +342,7 @@ def alter_res_phase1(lr_net, imgs, scale=0.5):
     lr_net = _unwrap(lr_net)
     B, _, H, W = imgs.shape
     h, w = _downscale_hw(H, W, scale)
-    return lr_net.phase1_nhwc4(ops.frame_ingest(imgs, h, w, lr_net.storage_dtype), aux=ops.config.aux_outputs)[-1]
+    return lr_net.phase1_nhwc4(ops.ingest_input(imgs, h, w, lr_net.storage_dtype), aux=ops.config.aux_outputs)[-1]
 
 
 def alter_res_phase2(lr_net, feat, ref_ps, mv_qs):
@@ -352,7 +362,7 @@ def alter_res_batch_pred(lr_net, ref_ps, imgs, mv_qs, scale=0.5, labels=None, hi
     lr_net = _unwrap(lr_net)
     B, _, H, W = imgs.shape
     h, w = _downscale_hw(H, W, scale)
-    feat = lr_net.phase1_nhwc4(ops.frame_ingest(imgs, h, w, lr_net.storage_dtype), aux=ops.config.aux_outputs)[-1]
+    feat = lr_net.phase1_nhwc4(ops.ingest_input(imgs, h, w, lr_net.storage_dtype), aux=ops.config.aux_outputs)[-1]
     fused_up = hasattr(lr_net, "out_upsample")                       # BiSeNetOutput: head -> nn.Upsample(x8, align_corners=False)
     if fused_up:
         lo, _ = lr_net.phase2_warp(feat, list(ref_ps), mv_qs, upsample=False)

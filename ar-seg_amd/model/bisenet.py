@@ -240,7 +240,7 @@ class _BiSeBase(HipModule):
     def _trunk_nhwc(self, x):
         """NCHW frame -> (feat_cp8, feat_cp16, middle_feat), all NHWC."""
         N, C, H, W = x.shape
-        return self._trunk_nhwc4(ops.frame_ingest(x, H, W, self.storage_dtype))
+        return self._trunk_nhwc4(ops.ingest_input(x, H, W, self.storage_dtype))
 
     def phase1_nhwc4(self, x4, aux=True):
         """forward_phase1 on an NHWC4 frame: same outputs as the reference (aux heads included in 'train'

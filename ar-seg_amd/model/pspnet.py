@@ -112,7 +112,7 @@ class _PSPBase(HipModule):
     def _trunk_nhwc(self, x):
         """NCHW frame -> (aux logits [N,n_cls], p NHWC [N,H',W',64])."""
         N, C, H, W = x.shape
-        return self.phase1_nhwc4(ops.frame_ingest(x, H, W, self.storage_dtype))
+        return self.phase1_nhwc4(ops.ingest_input(x, H, W, self.storage_dtype))
 
     def phase1_nhwc4(self, x4, aux=True):
         """The backbone on an NHWC4 frame (pspnet.py:198-217): -> (aux logits [N,n_cls], p NHWC).  ``aux=False`` (the build's fast paths, which
@@ -150,7 +150,7 @@ class _PSPBase(HipModule):
         -> (log-probs NCHW, p NHWC).  Same arithmetic as ``forward``; the training-only auxiliary classifier output is not evaluated."""
         self._check_inference()
         N, C, H, W = x.shape
-        _, p = self.phase1_nhwc4(ops.frame_ingest(x, H, W, self.storage_dtype), aux=False)
+        _, p = self.phase1_nhwc4(ops.ingest_input(x, H, W, self.storage_dtype), aux=False)
         return self._final(p, H, W), p
 
 

@@ -168,7 +168,7 @@ class PSPNetWithFuse(_SemsegBase):
         training-only aux head (pspnet_semseg.py:196-199) is not evaluated."""
         self._check_inference()
         N, C, H, W = x.shape
-        _, p = self.phase1_nhwc4(ops.frame_to_nhwc4(x, H, W))
+        _, p = self.phase1_nhwc4(ops.ingest_input(x, H, W))
         return self._logits_up(p, self.packed()["head"], H, W), p
 
     @staticmethod

@@ -37,6 +37,63 @@ def frame_ingest(img: torch.Tensor, h: int, w: int, dtype: torch.dtype = torch.f
     return out
 
 
+def _plane_layout(t: torch.Tensor, inner, what: str):
+    """(pitch, image stride) in bytes of a uint8 plane [N,H,...inner]: rows of ``inner`` contiguous bytes, any row pitch / image stride."""
+    want, row = [], 1
+    for d in reversed(inner):
+        want.insert(0, row)
+        row *= d
+    N, H = t.shape[0], t.shape[1]
+    if tuple(t.shape[2:]) != tuple(inner) or tuple(t.stride()[2:]) != tuple(want):
+        raise _lib.ArsegError(f"{what}: expected rows of {tuple(inner)} contiguous bytes, got shape {tuple(t.shape)} strides {t.stride()}")
+    pitch = t.stride(1) if H > 1 else row
+    n_stride = t.stride(0) if N > 1 else 0
+    if pitch < row or n_stride < 0:
+        raise _lib.ArsegError(f"{what}: row pitch {pitch} is smaller than a row of {row} bytes (or a negative image stride)")
+    return pitch, n_stride
+
+
+def frame_ingest8(plane0: torch.Tensor, plane1: Optional[torch.Tensor], src_format: int, h: int, w: int, mean, std,
+                  dtype: torch.dtype = torch.float32, colour: int = _lib.COLOUR_BT709_LIMITED) -> torch.Tensor:
+    """8-bit decoder frames -> the conv engine's input at (h,w) in one kernel: NHWC4 fp32, or NHWC8 fp16 / bf16 (csrc/ingest.hip).
+    ``src_format`` _lib.SRC_RGB8: plane0 uint8 [N,H,W,3], plane1 None;  _lib.SRC_NV12: plane0 luma uint8 [N,H,W], plane1 chroma uint8
+    [N,H/2,W/2,2] (Cb, Cr), ``colour`` one of _lib.COLOUR_*.  Planes may be views with a row pitch and an image stride.  Colour conversion,
+    bilinear align_corners=True downscale, ToTensor + Normalize(mean, std): include/arseg_hip.h, arseg_frame_ingest_fwd."""
+    nv12 = src_format == _lib.SRC_NV12
+    if src_format not in (_lib.SRC_RGB8, _lib.SRC_NV12):
+        raise _lib.ArsegError(f"frame_ingest8: unknown source format {src_format}")
+    if dtype != torch.float32 and dtype not in _DT16:
+        raise _lib.ArsegError(f"frame_ingest8: unsupported output dtype {dtype}")
+    _need_gpu(plane0, plane1 if nv12 else None, dtype=torch.uint8)
+    if plane0.dim() != (3 if nv12 else 4) or (nv12 and (plane1 is None or plane1.dim() != 4 or plane1.device != plane0.device)):
+        raise _lib.ArsegError("frame_ingest8 expects uint8 [N,H,W,3] (RGB8) or luma [N,H,W] + chroma [N,H/2,W/2,2] on one device (NV12)")
+    N, H, W = plane0.shape[:3]
+    pitch0, ns0 = _plane_layout(plane0, (W, 3) if not nv12 else (W,), "frame_ingest8 plane 0")
+    pitch1 = ns1 = 0
+    if nv12:
+        if H % 2 or W % 2 or tuple(plane1.shape) != (N, H // 2, W // 2, 2):
+            raise _lib.ArsegError(f"frame_ingest8: NV12 needs even H, W and a chroma plane [N,H/2,W/2,2]; luma {tuple(plane0.shape)}, chroma {tuple(plane1.shape)}")
+        pitch1, ns1 = _plane_layout(plane1, (W // 2, 2), "frame_ingest8 plane 1")
+    out = torch.empty((N, h, w, 4 if dtype == torch.float32 else 8), dtype=dtype, device=plane0.device)
+    m3, s3 = (ctypes.c_float * 3)(*[float(v) for v in mean]), (ctypes.c_float * 3)(*[float(v) for v in std])
+    src_bytes = N * H * W * 3 // (2 if nv12 else 1)
+    launch("frame_ingest8", _lib.load().arseg_frame_ingest_fwd, _ptr(plane0), _ptr(plane1 if nv12 else None), src_format, pitch0, pitch1, ns0, ns1,
+           int(colour), _ptr(out), _lib.DT_F32 if dtype == torch.float32 else _DT16[dtype], N, H, W, h, w, m3, s3, _stream(),
+           nbytes=src_bytes + out.numel() * out.element_size())
+    return out
+
+
+def ingest_input(frames, h: int, w: int, dtype: torch.dtype = torch.float32) -> torch.Tensor:
+    """The one door through which the fast paths take frames: a float NCHW tensor (``frame_ingest``, unchanged) or 8-bit decoder output
+    (``arseg_amd.ingest.DecodedFrames``: its ``to_input`` runs ``frame_ingest8``) -> the conv engine's input at (h,w)."""
+    if torch.is_tensor(frames):
+        return frame_ingest(frames, h, w, dtype)
+    to_input = getattr(frames, "to_input", None)
+    if to_input is None:
+        raise _lib.ArsegError(f"expected a float NCHW tensor or arseg_amd.ingest.DecodedFrames, got {type(frames).__name__}")
+    return to_input(h, w, dtype)
+
+
 # ----------------------------------------------------------------------------------------------
 # layout helpers
 # ----------------------------------------------------------------------------------------------

@@ -414,6 +414,39 @@ int arseg_frame_to_nhwc4_fwd(const float *img, float *out, int N, int H, int W, 
  * (evaluation.py:186-188) in one pass.  mean3 / std3: host pointers to 3 floats. */
 int arseg_frame_u8_to_nhwc4_fwd(const uint8_t *img_hwc, float *out, int N, int H, int W, int h, int w, const float *mean3,
                                 const float *std3, arseg_stream_t stream);
+/* 8-bit decoder frames -> the conv engine's input in one pass, no intermediate tensor (csrc/ingest.hip).
+ *   src_format  ARSEG_SRC_RGB8: plane0 = uint8 [N][H][W][3] interleaved (the layout arseg_frame_u8_to_nhwc4_fwd takes); plane1, pitch1,
+ *                               n_stride1 and colour are ignored
+ *               ARSEG_SRC_NV12: plane0 = luma uint8 [N][H][W], plane1 = chroma uint8 [N][H/2][W/2][2] (Cb, Cr interleaved); H and W even
+ *   pitch0/1    bytes from one row of the plane to the next (>= 3 W for RGB8, >= W for either NV12 plane); n_stride0/1: bytes from one
+ *               image to the next (>= 0; 0 = every image reads the same plane).  Rows may be padded; nothing past a row's last pixel is read.
+ *   out         out_dtype ARSEG_DT_F32: NHWC4 fp32 [N][h][w][4], channel 3 = 0;  ARSEG_DT_F16 | ARSEG_DT_BF16: NHWC8 [N][h][w][8],
+ *               channels 3..7 = 0.  16-byte aligned.
+ *   mean3/std3  host pointers to 3 floats (dataset/camvid.py:503-506).
+ * Per output pixel, all in fp32: (1) the taps of F.interpolate(..., (h, w), mode='bilinear', align_corners=True) on the H x W frame
+ * (evaluation.py:117,188), as the other ingest kernels compute them; (h, w) == (H, W) reads one tap and blends nothing; h > H or w > W
+ * upscales with the same formula.  (2) RGB in the 0-255 scale at each tap -- RGB8: the stored bytes.  NV12: Y = the stored byte; (Cb, Cr)
+ * sampled bilinearly from the half-resolution plane at the luma pixel's position under the H.26x default chroma siting (co-sited with
+ * even luma columns, midway between two luma rows): cx = x / 2, cy = y / 2 - 0.25, both clamped to the plane; then
+ *       R = ky (Y - y0) + rv (Cr - 128),   G = ky (Y - y0) - gu (Cb - 128) - gv (Cr - 128),   B = ky (Y - y0) + bu (Cb - 128)
+ *       rv = 2 (1 - Kr) s,  bu = 2 (1 - Kb) s,  gu = 2 Kb (1 - Kb) / Kg s,  gv = 2 Kr (1 - Kr) / Kg s,  Kg = 1 - Kr - Kb
+ *       BT.601: Kr = 0.299, Kb = 0.114;  BT.709: Kr = 0.2126, Kb = 0.0722
+ *       limited range (Y 16-235, C 16-240): y0 = 16, ky = 255 / 219, s = 255 / 224;   full range: y0 = 0, ky = 1, s = 1
+ *         colour                        ky        rv        gu        gv        bu
+ *         ARSEG_COLOUR_BT601_LIMITED    1.164384  1.596027  0.391762  0.812968  2.017232
+ *         ARSEG_COLOUR_BT601_FULL       1         1.402     0.344136  0.714136  1.772
+ *         ARSEG_COLOUR_BT709_LIMITED    1.164384  1.792741  0.213249  0.532909  2.112402
+ *         ARSEG_COLOUR_BT709_FULL       1         1.5748    0.187324  0.468124  1.8556
+ *     each component clipped to [0, 255], not rounded to an integer.  (3) the taps are blended, then (v / 255 - mean[c]) / std[c]
+ * (evaluated as one fma with 1 / (255 std) and -mean / std formed in double; within 2 ulp of the two divisions).  16-bit outputs are
+ * rounded once, at the store (to nearest even).
+ * ARSEG_EINVAL: a null pointer (plane1 only with NV12), a non-positive size, a zero std, odd H or W with NV12, a pitch smaller than a
+ * row, a negative image stride, an unknown src_format / out_dtype / colour (colour with NV12 only), `out` not 16-byte aligned. */
+enum arseg_src_format { ARSEG_SRC_RGB8 = 0, ARSEG_SRC_NV12 = 1 };
+enum arseg_colour { ARSEG_COLOUR_BT601_LIMITED = 0, ARSEG_COLOUR_BT601_FULL = 1, ARSEG_COLOUR_BT709_LIMITED = 2, ARSEG_COLOUR_BT709_FULL = 3 };
+int arseg_frame_ingest_fwd(const void *plane0, const void *plane1, int src_format, int64_t pitch0, int64_t pitch1, int64_t n_stride0,
+                           int64_t n_stride1, int colour, void *out, int out_dtype, int N, int H, int W, int h, int w, const float *mean3,
+                           const float *std3, arseg_stream_t stream);
 
 /* mergeMotion (pre-process/generate_compressed_dataset_camvid.py:6-56): chains the codec's per-frame motion fields back to
  * the keyframe.  flows: int16 [n_frames+1][H][W][3] = (mv_x, mv_y quarter-pel, reference index), entries <= frame_start unused;
