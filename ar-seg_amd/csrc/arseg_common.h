@@ -20,6 +20,18 @@ static inline hipStream_t arseg_stream(arseg_stream_t s) {
     return reinterpret_cast<hipStream_t>(s);
 }
 static inline int arseg_cdiv(long long a, long long b) { return (int)((a + b - 1) / b); }
+// Compute units of the current device (256 where it cannot be asked), asked on every call: a process may drive several GPUs.
+// max_wgs > 0 caps the answer: persistent kernels leave the other compute units to the kernels of other streams.
+static inline int arseg_cu_count(int max_wgs = 0) {
+    int dev = 0, cus = 256;
+    if (hipGetDevice(&dev) != hipSuccess || hipDeviceGetAttribute(&cus, hipDeviceAttributeMultiprocessorCount, dev) != hipSuccess) cus = 256;
+    return max_wgs > 0 && max_wgs < cus ? max_wgs : cus;
+}
+// Workgroups of 256 threads for a grid-stride loop over `total` items: at least one, at most `cap`
+static inline int arseg_grid_for(long long total, int cap = 8192) {
+    long long b = (total + 255) / 256;
+    return (int)(b > cap ? cap : (b < 1 ? 1 : b));
+}
 
 // hipFuncAttributeMaxDynamicSharedMemorySize is a PER-DEVICE function attribute: remember, per device, the largest request that has
 // been granted (a process may drive several GPUs, e.g. under nn.DataParallel).  Grow-only; a race only repeats the same call.

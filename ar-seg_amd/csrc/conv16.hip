@@ -13,14 +13,11 @@
 //     ingested as NHWC8;
 //   * epilogue through LDS: the fp32 accumulators are transposed into [pixel][co] rows so that scale / bias / residual / activation
 //     run on 8 consecutive channels and the store is a coalesced 16-byte vector of a full NHWC row.
-#include "arseg_common.h"
+#include "arseg_device.h"
 
 namespace {
 
-typedef _Float16 h16x8 __attribute__((ext_vector_type(8)));
 typedef __bf16 bf16x8 __attribute__((ext_vector_type(8)));
-typedef unsigned u32x4 __attribute__((ext_vector_type(4)));
-typedef unsigned u32x2 __attribute__((ext_vector_type(2)));
 
 struct Conv16Params {
     const uint16_t *in, *w, *res;
@@ -630,8 +627,7 @@ int launch_stem16(const Conv16Params &p, hipStream_t st) {
     const size_t smem = (size_t)(64 * 51 + 21 * 70 + 32) * 16;
     static ArsegSmemAttr attr;
     if (int e = arseg_allow_smem(attr, reinterpret_cast<const void *>(conv16_stem_kernel<BF>), smem)) return e;
-    int dev = 0, cus = 256;
-    if (hipGetDevice(&dev) != hipSuccess || hipDeviceGetAttribute(&cus, hipDeviceAttributeMultiprocessorCount, dev) != hipSuccess) cus = 256;
+    const int cus = arseg_cu_count();
     const long long ntiles = (long long)p.N * arseg_cdiv(p.Ho, 8) * arseg_cdiv(p.Wo, 32);
     const int grid = (int)(ntiles < 2 * cus ? ntiles : 2 * cus);
     hipLaunchKernelGGL((conv16_stem_kernel<BF>), dim3(grid), dim3(256), smem, st, p);

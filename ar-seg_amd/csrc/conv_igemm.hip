@@ -32,16 +32,14 @@
 //                     16x the MFMA rate for 3x the instructions.  Weights are split (and scaled per output channel by a
 //                     power of two so that lo stays a normal fp16) once at pack time; activations stay fp32 in HBM and
 //                     are split on their way into LDS, whose row layout becomes [32 hi halves | 32 lo halves | pad].
-#include "arseg_common.h"
+#include "arseg_device.h"
 #include <type_traits>
 #include <cmath>
 #include <cstring>
 
 namespace {
 
-typedef _Float16 h16x8 __attribute__((ext_vector_type(8)));
 typedef __fp16 fp16x2 __attribute__((ext_vector_type(2)));
-typedef unsigned u32x4 __attribute__((ext_vector_type(4)));
 
 constexpr int KALIGN = 32;       // packed K is padded to a multiple of this (one f16x3 weight tile)
 

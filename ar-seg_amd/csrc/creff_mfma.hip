@@ -19,14 +19,11 @@
 // value convolution runs on the VALU and writes its result as split fp16 records ([group of 4 ch][px]{4 hi | 4 lo}, zero outside the
 // image = the unfold's padding, model/attention.py:56-58), the query convolution is lane-local (each lane convolves the
 // 4 channels of its own query that its B operand needs).
+#include "arseg_device.h"
 #include "creff_params.h"
 
 namespace {
 
-typedef _Float16 h16x8 __attribute__((ext_vector_type(8)));
-typedef short s16x4 __attribute__((ext_vector_type(4)));
-typedef unsigned u32x2 __attribute__((ext_vector_type(2)));
-typedef unsigned u32x4 __attribute__((ext_vector_type(4)));
 typedef unsigned u32x6 __attribute__((ext_vector_type(6)));
 
 constexpr int TX = 16;
@@ -43,65 +40,11 @@ template <int TY> struct Geo {
                                                                // (planes on the same banks), values with the transpose read (16 banks apart)
     static constexpr int HPL = HH * HWD, LPL = LH * LWD + 4;
 };
-constexpr unsigned OOB = 0xFFFFFFF0u;
-constexpr float LOG2E = 1.44269504088896340736f;
 
-__device__ __forceinline__ void split4(const f32x4 v, u32x2 &hi, u32x2 &lo) {
-    unsigned h01, h23, l01, l23;
-    arseg_split_f16(v, h01, h23, l01, l23);
-    hi = u32x2{h01, h23}; lo = u32x2{l01, l23};
-}
 // {hi, lo, hi}: dwords 0..3 are the operand {hi,lo}, dwords 2..5 the swapped operand {lo,hi} -- no register copies
-// reductions over the 4 DPP rows of a wave on the VALU (see creff_rr.hip): __shfl_xor is a ds_bpermute (LDS round trip + an address VGPR)
-__device__ __forceinline__ float rows_max(float x) {
-    auto a = __builtin_amdgcn_permlane16_swap(__float_as_uint(x), __float_as_uint(x), false, false);
-    x = fmaxf(__uint_as_float(a[0]), __uint_as_float(a[1]));
-    auto b = __builtin_amdgcn_permlane32_swap(__float_as_uint(x), __float_as_uint(x), false, false);
-    return fmaxf(__uint_as_float(b[0]), __uint_as_float(b[1]));
-}
-__device__ __forceinline__ float rows_sum(float x) {
-    auto a = __builtin_amdgcn_permlane16_swap(__float_as_uint(x), __float_as_uint(x), false, false);
-    x = __uint_as_float(a[0]) + __uint_as_float(a[1]);
-    auto b = __builtin_amdgcn_permlane32_swap(__float_as_uint(x), __float_as_uint(x), false, false);
-    return __uint_as_float(b[0]) + __uint_as_float(b[1]);
-}
 __device__ __forceinline__ u32x6 pack6(const u32x2 hi, const u32x2 lo) { return u32x6{hi.x, hi.y, lo.x, lo.y, hi.x, hi.y}; }
 __device__ __forceinline__ h16x8 op_a(const u32x6 v) { return __builtin_bit_cast(h16x8, __builtin_shufflevector(v, v, 0, 1, 2, 3)); }
 __device__ __forceinline__ h16x8 op_b(const u32x6 v) { return __builtin_bit_cast(h16x8, __builtin_shufflevector(v, v, 2, 3, 4, 5)); }
-__device__ __forceinline__ h16x8 pack8(const u32x2 a, const u32x2 b) { return __builtin_bit_cast(h16x8, u32x4{a.x, a.y, b.x, b.y}); }
-__device__ __forceinline__ u32x2 lds_tr16(const unsigned char *p) {
-    return __builtin_bit_cast(u32x2, __builtin_amdgcn_ds_read_tr16_b64_v4i16((s16x4 __attribute__((address_space(3))) *)p));
-}
-
-// Asynchronous memory traffic is issued through inline asm on purpose.  hipcc (ROCm 7.2) serialises the LDS-DMA builtins
-// (a waterfall loop over the M0 base with an s_waitcnt vmcnt(0) in front of every load) and, on gfx9, drains every counter it
-// knows about in front of each s_barrier -- so builtin stores would expose the full write latency at the next barrier.
-// Loads: waited for explicitly (s_waitcnt vmcnt(0)) before the barrier that publishes their LDS image.  Stores: fire and
-// forget (their data registers are read at issue).
-__device__ __forceinline__ u32x4 make_rsrc(const void *base, unsigned bytes) {
-    const unsigned long long a = (unsigned long long)base;      // wave uniform: pin the descriptor to SGPRs
-    return u32x4{(unsigned)__builtin_amdgcn_readfirstlane((int)(unsigned)a), (unsigned)__builtin_amdgcn_readfirstlane((int)((unsigned)(a >> 32) & 0xffffu)),
-                 (unsigned)__builtin_amdgcn_readfirstlane((int)bytes), 0x00020000u};
-}
-__device__ __forceinline__ void dma16_buf(const u32x4 rsrc, unsigned voff, unsigned lds_base) {   // LDS[lds_base + lane*16] <- buffer
-    unsigned keep;
-    asm volatile("s_mov_b32 %0, m0\n\ts_mov_b32 m0, %1\n\ts_nop 0\n\tbuffer_load_dwordx4 %2, %3, 0 offen lds\n\ts_mov_b32 m0, %0"
-                 : "=&s"(keep) : "s"(lds_base), "v"(voff), "s"(rsrc) : "memory");
-}
-__device__ __forceinline__ void dma16_glb(const void *g, unsigned lds_base) {
-    unsigned keep;
-    asm volatile("s_mov_b32 %0, m0\n\ts_mov_b32 m0, %1\n\ts_nop 0\n\tglobal_load_lds_dwordx4 %2, off\n\ts_mov_b32 m0, %0"
-                 : "=&s"(keep) : "s"(lds_base), "v"(g) : "memory");
-}
-__device__ __forceinline__ void store16_buf(const u32x4 v, const u32x4 rsrc, unsigned voff) {
-    // s_nop: a VMEM store of more than 64 bits needs two wait states (gfx940+) before its data VGPRs may be overwritten (the
-    // compiler pads this hazard for its own stores, not inside asm)
-    asm volatile("buffer_store_dwordx4 %0, %1, %2, 0 offen\n\ts_nop 1" ::"v"(v), "v"(voff), "s"(rsrc) : "memory");
-}
-__device__ __forceinline__ void store4_buf(unsigned v, const u32x4 rsrc, unsigned voff) {
-    asm volatile("buffer_store_dword %0, %1, %2, 0 offen" ::"v"(v), "v"(voff), "s"(rsrc) : "memory");
-}
-__device__ __forceinline__ unsigned lds_addr(const void *p) { return (unsigned)(size_t)(__attribute__((address_space(3))) const void *)p; }
 
 template <int NB, int TY>      // NB: classifier row blocks of 16 classes (0: no head)
 __global__ __launch_bounds__(64 * TY, 4) void creff_mfma_kernel(const CreffParams p) {
@@ -441,7 +384,7 @@ __global__ __launch_bounds__(64 * TY, 4) void creff_mfma_kernel(const CreffParam
         }
         const f32x4 o = lrc + acc * inv;              // p[query][16k + 4g .. +3]
         const unsigned off = p_off0 + (unsigned)k * p_kstep;       // 32-bit: the 64-bit form kept three hoisted partial products in spilled registers
-        store16_buf(__builtin_bit_cast(u32x4, o), p_rsrc, inq ? off : OOB);
+        store16_buf(__builtin_bit_cast(u32x4, o), p_rsrc, inq ? off : OOB_TOP16);
         if (NB > 0) {
             u32x2 oh, ol;
             split4(o, oh, ol);
@@ -485,7 +428,7 @@ __global__ __launch_bounds__(64 * TY, 4) void creff_mfma_kernel(const CreffParam
             for (int i = 0; i < 4; ++i) {
                 const int cls = nb * 16 + 4 * g + i;
                 const unsigned off = (unsigned)(((((size_t)n * p.n_cls + cls) * p.Hp + gyq) * p.Wp + gxq) * sizeof(float));
-                store4_buf(__float_as_uint(lg[nb][i]), l_rsrc, (inq && cls < p.n_cls) ? off : OOB);
+                store4_buf(__float_as_uint(lg[nb][i]), l_rsrc, (inq && cls < p.n_cls) ? off : OOB_TOP16);
             }
     }
 }

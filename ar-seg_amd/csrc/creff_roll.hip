@@ -29,17 +29,13 @@
 // arithmetic (hi/lo split-fp16 operands on v_mfma_f32_16x16x32_f16, softmax over all 49 taps incl. padding taps) is that of creff_rr.hip.
 //
 // Arithmetic contract: as creff.hip (zero-padded unfold: keys / values outside the image are 0 and still take softmax mass).
+#include "arseg_device.h"
 #include "creff_params.h"
 #include "warp_math.h"
 
 namespace {
 
-typedef _Float16 h16x8 __attribute__((ext_vector_type(8)));
 typedef _Float16 h16x4 __attribute__((ext_vector_type(4)));
-typedef short s16x4 __attribute__((ext_vector_type(4)));
-typedef unsigned u32x2 __attribute__((ext_vector_type(2)));
-typedef unsigned u32x4 __attribute__((ext_vector_type(4)));
-typedef float f32x2 __attribute__((ext_vector_type(2)));
 
 constexpr int CH = 64, NT = 1024, NCONS = 4;         // 16 waves: 4 consumers + 768 producer lanes, one gather unit (pixel, channel group) each
 constexpr int SW = 16;                               // query columns of a strip (two 8-column patches)
@@ -76,8 +72,6 @@ constexpr int SC_OFF = BF_OFF + 32 * 4;              //          this workgroup'
 constexpr int SMEM_BYTES = SC_OFF + 16 + 64 * 16;    // 158,896 <= 163,840
 constexpr int T_FIRST = -3;                         // first iteration of a segment (MV request of gather 0); the last is S + 5
 constexpr int MAXN = 32;
-constexpr unsigned OOB = 0xFFFFFFF0u;
-constexpr float LOG2E = 1.44269504088896340736f;
 
 // Ring slot of key row r.  A consumer's ds_read_b128 of one key block wraps from window row b to row b + 1 and conflicts 2-way on up to
 // half of its lanes (profiles/r04_v1_pmc_creff_roll.json).  Rows 5 slots apart remove those conflicts but measured 0.4 % slower (r6,
@@ -136,37 +130,6 @@ __device__ __forceinline__ u32x4 split4r(const f32x4 v) {
     unsigned h01, h23, l01, l23;
     arseg_split_f16(v, h01, h23, l01, l23);
     return u32x4{h01, h23, l01, l23};
-}
-__device__ __forceinline__ h16x8 pack8(const u32x2 a, const u32x2 b) { return __builtin_bit_cast(h16x8, u32x4{a.x, a.y, b.x, b.y}); }
-__device__ __forceinline__ u32x2 lds_tr16(const unsigned char *p) {
-    return __builtin_bit_cast(u32x2, __builtin_amdgcn_ds_read_tr16_b64_v4i16((s16x4 __attribute__((address_space(3))) *)p));
-}
-// a * b + c on packed pairs (v_pk_fma_f32: 2 FMAs per issue slot)
-__device__ __forceinline__ f32x4 fma4(const f32x4 a, const f32x4 b, const f32x4 c) {
-    const f32x2 lo = __builtin_elementwise_fma(__builtin_shufflevector(a, a, 0, 1), __builtin_shufflevector(b, b, 0, 1), __builtin_shufflevector(c, c, 0, 1));
-    const f32x2 hi = __builtin_elementwise_fma(__builtin_shufflevector(a, a, 2, 3), __builtin_shufflevector(b, b, 2, 3), __builtin_shufflevector(c, c, 2, 3));
-    return __builtin_shufflevector(lo, hi, 0, 1, 2, 3);
-}
-// reductions over the 4 DPP rows of a wave (lanes l, l^16, l^32, l^48) on the VALU (see creff_rr.hip)
-__device__ __forceinline__ float rows_max(float x) {
-    auto a = __builtin_amdgcn_permlane16_swap(__float_as_uint(x), __float_as_uint(x), false, false);
-    x = fmaxf(__uint_as_float(a[0]), __uint_as_float(a[1]));
-    auto b = __builtin_amdgcn_permlane32_swap(__float_as_uint(x), __float_as_uint(x), false, false);
-    return fmaxf(__uint_as_float(b[0]), __uint_as_float(b[1]));
-}
-__device__ __forceinline__ float rows_sum(float x) {
-    auto a = __builtin_amdgcn_permlane16_swap(__float_as_uint(x), __float_as_uint(x), false, false);
-    x = __uint_as_float(a[0]) + __uint_as_float(a[1]);
-    auto b = __builtin_amdgcn_permlane32_swap(__float_as_uint(x), __float_as_uint(x), false, false);
-    return __uint_as_float(b[0]) + __uint_as_float(b[1]);
-}
-// a wave-uniform double pinned to scalar registers (left to the compiler, uniform fp64 values live in VGPR pairs across the whole
-// kernel and are spilled; asm: the builtin is folded back into the vector value)
-__device__ __forceinline__ double uniform_f64(double x) {
-    const unsigned long long u = __builtin_bit_cast(unsigned long long, x);
-    unsigned lo, hi;
-    asm volatile("s_nop 1\n\tv_readfirstlane_b32 %0, %2\n\tv_readfirstlane_b32 %1, %3" : "=s"(lo), "=s"(hi) : "v"((unsigned)u), "v"((unsigned)(u >> 32)));
-    return __builtin_bit_cast(double, ((unsigned long long)hi << 32) | lo);
 }
 // Workgroup barrier that orders LDS traffic only: global loads requested before it stay in flight across it (the gather of the next
 // row pair travels under the convolutions of this one).
@@ -286,12 +249,12 @@ __device__ __forceinline__ void consumer(const RollParams &p, const Smem &sm, co
         // one descriptor PER FRAME (scalar arithmetic per piece): the 32-bit buffer offsets then only have to span a frame, not the batch
         const __amdgpu_buffer_rsrc_t p_rsrc = __builtin_amdgcn_make_buffer_rsrc(p.p_out + (size_t)n * (size_t)(CH * Hp) * Wp, 0, (int)p.p_bytes, 0x00020000);
         const __amdgpu_buffer_rsrc_t l_rsrc = __builtin_amdgcn_make_buffer_rsrc(p.logits + (size_t)n * (size_t)(p.n_cls * Hp) * Wp, 0, (int)p.l_bytes, 0x00020000);
-        // Store offsets of this lane's query pixel, split into a per-lane part that is constant down the strip (voffset; OOB for lanes
+        // Store offsets of this lane's query pixel, split into a per-lane part that is constant down the strip (voffset; OOB_TOP16 for lanes
         // whose column or class lies outside) and a wave-uniform part that moves with the step (soffset: scalar arithmetic only).
         const int qy = q >> 3, gxq = x0 + 8 * pc + (q & 7);
         const bool col_ok = gxq < Wp, c8 = p.p_layout == ARSEG_C8;
         const unsigned plane = (unsigned)(Hp * Wp);
-        const unsigned vp = !col_ok ? OOB : c8 ? ((unsigned)(g >> 1) * plane + (unsigned)(qy * Wp + gxq)) * 32u + (unsigned)(g & 1) * 16u
+        const unsigned vp = !col_ok ? OOB_TOP16 : c8 ? ((unsigned)(g >> 1) * plane + (unsigned)(qy * Wp + gxq)) * 32u + (unsigned)(g & 1) * 16u
                                                : (unsigned)(qy * Wp + gxq) * (CH * 4u) + 16u * g;
         const unsigned p_cstep = c8 ? 2u * plane * 32u : 64u;                                    // chunk c: + c * p_cstep
         const unsigned p_unit = (unsigned)(ys * Wp) * (c8 ? 32u : CH * 4u);
@@ -302,7 +265,7 @@ __device__ __forceinline__ void consumer(const RollParams &p, const Smem &sm, co
 #pragma unroll
             for (int i = 0; i < 4; ++i) {
                 const int cls = nb * 16 + 4 * g + i;
-                vl[nb][i] = col_ok && cls < p.n_cls ? ((unsigned)cls * plane + (unsigned)(qy * Wp + gxq)) * 4u : OOB;
+                vl[nb][i] = col_ok && cls < p.n_cls ? ((unsigned)cls * plane + (unsigned)(qy * Wp + gxq)) * 4u : OOB_TOP16;
             }
         const unsigned l_unit = (unsigned)(ys * Wp) * 4u, l_rstep = (unsigned)(2 * Wp) * 4u;
         f32x4 Oh[4];                                 // this half's un-normalised P.V (KH 0: carried to the merge in the next H1)
@@ -531,7 +494,7 @@ __device__ __forceinline__ void producer(const RollParams &p, const Smem &sm, co
             const float inx = (unsigned)gx < (unsigned)Wp ? 1.f : 0.f;
             lwx0[i] = (1.f - m) * inx; lwx1[i] = m * inx;
             lx0[i] = (unsigned)j0 * PXB; lx1[i] = (unsigned)j1 * PXB;
-            if (!l_lane[i]) { lx0[i] = OOB - lr_img; lx1[i] = OOB - lr_img; }      // (wave 13: no unit -- with the row offset still beyond the buffer)
+            if (!l_lane[i]) { lx0[i] = OOB_TOP16 - lr_img; lx1[i] = OOB_TOP16 - lr_img; }      // (wave 13: no unit -- with the row offset still beyond the buffer)
         }
         // ROLE_KV: the four warp rows under the two record rows being produced (rows 0, 1: the window; 2, 3: staged this iteration);
         // ROLE_Q: rows 0, 1 = the window of lr_up rows
@@ -731,9 +694,9 @@ __device__ __forceinline__ void producer(const RollParams &p, const Smem &sm, co
                     arseg_src_index(p.sx, min(max(x0 - 1, 0), Wp - 1), true, p.wp, j0, j1, l);
                     arseg_src_index(p.sx, min(max(x0 + SW, 0), Wp - 1), true, p.wp, je0, je1, l);
                     const int r = i0 + (tq >> 4), c = j0 + (tq & 15);
-                    const unsigned off = r <= ie1 && c <= je1 ? (unsigned)(r * p.wp + c) * PXB : OOB;
+                    const unsigned off = r <= ie1 && c <= je1 ? (unsigned)(r * p.wp + c) * PXB : OOB_TOP16;
                     pft[0] = __builtin_amdgcn_raw_buffer_load_b32(lr_rsrc, off, 0, 0);
-                    if constexpr (PXB == 256u) pft[1] = __builtin_amdgcn_raw_buffer_load_b32(lr_rsrc, off == OOB ? OOB : off + 128u, 0, 0);
+                    if constexpr (PXB == 256u) pft[1] = __builtin_amdgcn_raw_buffer_load_b32(lr_rsrc, off == OOB_TOP16 ? OOB_TOP16 : off + 128u, 0, 0);
                 }
             }
             wg_sync();
@@ -800,11 +763,9 @@ template <int NB, int DT>
 int launch(const RollParams &p, int max_wgs, hipStream_t st) {
     static ArsegSmemAttr attr;
     if (int e = arseg_allow_smem(attr, reinterpret_cast<const void *>(creff_roll_kernel<NB, DT>), SMEM_BYTES)) return e;
-    int dev = 0, cus = 256;
-    if (hipGetDevice(&dev) != hipSuccess || hipDeviceGetAttribute(&cus, hipDeviceAttributeMultiprocessorCount, dev) != hipSuccess) cus = 256;
     // workgroups: one per CU; fewer when the launch is small -- mode 0: one per unit, mode 1: at least 16 steps each (a piece costs 9 iterations of fill)
     const long long nunits = p.balanced ? ((long long)p.nstrips * p.N * ((p.Hp + 1) >> 1) + 15) / 16 : (long long)p.nstrips * p.nseg * p.N;
-    if (max_wgs > 0 && max_wgs < cus) cus = max_wgs;      // leave compute units to the kernels of other streams (the workgroups are persistent)
+    const int cus = arseg_cu_count(max_wgs);      // leave compute units to the kernels of other streams (the workgroups are persistent)
     const int grid = (int)(nunits < cus ? nunits : cus);
     hipLaunchKernelGGL((creff_roll_kernel<NB, DT>), dim3(grid), dim3(NT), SMEM_BYTES, st, p);
     return arseg_launch_status();
@@ -834,9 +795,7 @@ int arseg_creff_roll_launch(const void *const *ref_nhwc_host, const int16_t *mv_
     if (seg_rows <= 0) seg_rows = Hp;
     seg_rows = (seg_rows + 1) & ~1;
     if (!p.balanced) {                                        // a workgroup's list holds MAXPIECES pieces: longer segments if the launch has more
-        int dev = 0, cus = 256;
-        if (hipGetDevice(&dev) != hipSuccess || hipDeviceGetAttribute(&cus, hipDeviceAttributeMultiprocessorCount, dev) != hipSuccess) cus = 256;
-        if (max_wgs > 0 && max_wgs < cus) cus = max_wgs;
+        const int cus = arseg_cu_count(max_wgs);
         for (;;) {
             const long long units = (long long)p.nstrips * arseg_cdiv(Hp, seg_rows) * N, wgs = units < cus ? units : cus;
             // (an XCD's share of the units over its share of the workgroups, both rounded against us)
@@ -853,9 +812,7 @@ int arseg_creff_roll_launch(const void *const *ref_nhwc_host, const int16_t *mv_
     p.ref_bytes = (unsigned)((size_t)CH * Hp * Wp * esz);
     p.sy = arseg_resize_scale(hp, Hp, true); p.sx = arseg_resize_scale(wp, Wp, true);
     if (p.balanced) {      // a workgroup's list of pieces must hold its whole-strip passes + the pieces of its remainder run
-        int dev = 0, cus = 256;
-        if (hipGetDevice(&dev) != hipSuccess || hipDeviceGetAttribute(&cus, hipDeviceAttributeMultiprocessorCount, dev) != hipSuccess) cus = 256;
-        if (max_wgs > 0 && max_wgs < cus) cus = max_wgs;
+        const int cus = arseg_cu_count(max_wgs);
         const long long T = (long long)p.nstrips * N, nunits = (T * ((Hp + 1) >> 1) + 15) / 16, wgs = nunits < cus ? nunits : cus;
         const long long nx = wgs < 8 ? wgs : 8, share = (T + nx - 1) / nx, g = wgs / nx;
         if (share / g + 3 > MAXPIECES) return ARSEG_EUNSUPPORTED;

@@ -21,15 +21,11 @@
 // (registers) -> key records -> Q.K^T + softmax -> value records -> P.V + residual + classifier + stores.
 //
 // Arithmetic contract: as creff.hip (zero-padded unfold: keys / values outside the image are 0 and still take softmax mass).
+#include "arseg_device.h"
 #include "creff_params.h"
 #include "warp_math.h"
 
 namespace {
-
-typedef _Float16 h16x8 __attribute__((ext_vector_type(8)));
-typedef short s16x4 __attribute__((ext_vector_type(4)));
-typedef unsigned u32x2 __attribute__((ext_vector_type(2)));
-typedef unsigned u32x4 __attribute__((ext_vector_type(4)));
 
 constexpr int TX = 16, TY = 16, NT = 1024, CH = 64;
 constexpr int LW = 18, LN = 324, LPL = 329;          // lr_up tile (+1 halo) per channel group
@@ -47,8 +43,6 @@ constexpr int WDQ_OFF = TAPO_OFF + R4N * 4;          // [4 chunks][9 taps + bias
 constexpr int LRT_OFF = WDQ_OFF + 4 * 10 * 4 * 16;      // [18 rows | 18 columns] of the lr_up tile: {tap offset 0, tap offset 1, weight 0, weight 1}
 constexpr int SMEM_BYTES = LRT_OFF + 2 * LW * 16;       // 162,368 <= 163,840
 constexpr int MAXN = 32;
-constexpr unsigned OOB = 0xFFFFFFF0u;
-constexpr float LOG2E = 1.44269504088896340736f;
 // cache policy of the p / logits stores: 2 = nontemporal (1.7 GB per 11-frame launch that nobody re-reads soon; keeps the XCD's L2 for the
 // overlapping gather of the keyframe feature: 242.4-243.9 -> 241.4 us per frame)
 constexpr int PNT = 2;
@@ -63,29 +57,11 @@ struct RRParams {
     float sy, sx;
 };
 
-__device__ __forceinline__ void split4(const f32x4 v, u32x2 &hi, u32x2 &lo) {
-    unsigned h01, h23, l01, l23;
-    arseg_split_f16(v, h01, h23, l01, l23);
-    hi = u32x2{h01, h23}; lo = u32x2{l01, l23};
-}
-__device__ __forceinline__ h16x8 pack8(const u32x2 a, const u32x2 b) { return __builtin_bit_cast(h16x8, u32x4{a.x, a.y, b.x, b.y}); }
-__device__ __forceinline__ u32x2 lds_tr16(const unsigned char *p) {
-    return __builtin_bit_cast(u32x2, __builtin_amdgcn_ds_read_tr16_b64_v4i16((s16x4 __attribute__((address_space(3))) *)p));
-}
-// LDS[lds_base + lane * 16] <- 16 bytes at g (LDS-DMA: no staging registers).  Inline asm: hipcc serialises the builtin (waterfall loop
-// over M0 with a vmcnt(0) per load); the loads are invisible to its s_waitcnt bookkeeping, so the publishing barrier is preceded
-// by an explicit s_waitcnt vmcnt(0).
-__device__ __forceinline__ void dma16_glb(const void *g, unsigned lds_base) {
-    unsigned keep;
-    asm volatile("s_mov_b32 %0, m0\n\ts_mov_b32 m0, %1\n\ts_nop 0\n\tglobal_load_lds_dwordx4 %2, off\n\ts_mov_b32 m0, %0"
-                 : "=&s"(keep) : "s"(lds_base), "v"(g) : "memory");
-}
 __device__ __forceinline__ void dma4_glb(const void *g, unsigned lds_base) {        // LDS[lds_base + lane * 4] <- 4 bytes at g
     unsigned keep;
     asm volatile("s_mov_b32 %0, m0\n\ts_mov_b32 m0, %1\n\ts_nop 0\n\tglobal_load_lds_dword %2, off\n\ts_mov_b32 m0, %0"
                  : "=&s"(keep) : "s"(lds_base), "v"(g) : "memory");
 }
-__device__ __forceinline__ unsigned lds_addr(const void *p) { return (unsigned)(size_t)(__attribute__((address_space(3))) const void *)p; }
 template <int CTRL>
 __device__ __forceinline__ f32x4 dpp4(const f32x4 v) {     // row_shr:1 = 0x111 (lane i <- lane i-1), row_shl:1 = 0x101 (lane i <- lane i+1)
     f32x4 r;
@@ -93,41 +69,9 @@ __device__ __forceinline__ f32x4 dpp4(const f32x4 v) {     // row_shr:1 = 0x111 
     for (int j = 0; j < 4; ++j) r[j] = __int_as_float(__builtin_amdgcn_update_dpp(0, __float_as_int(v[j]), CTRL, 0xF, 0xF, true));
     return r;
 }
-// a * b + c on packed pairs: v_pk_fma_f32 issues 2 FMAs in 4.2 cycles per wave, v_fmac_f32 one in 3.0 (measured on MI355X, 4 waves
-// per SIMD) -- the depthwise convolutions are bound by exactly this
-typedef float f32x2 __attribute__((ext_vector_type(2)));
-__device__ __forceinline__ f32x4 fma4(const f32x4 a, const f32x4 b, const f32x4 c) {
-    const f32x2 lo = __builtin_elementwise_fma(__builtin_shufflevector(a, a, 0, 1), __builtin_shufflevector(b, b, 0, 1), __builtin_shufflevector(c, c, 0, 1));
-    const f32x2 hi = __builtin_elementwise_fma(__builtin_shufflevector(a, a, 2, 3), __builtin_shufflevector(b, b, 2, 3), __builtin_shufflevector(c, c, 2, 3));
-    return __builtin_shufflevector(lo, hi, 0, 1, 2, 3);
-}
 // Record index (row-major in the 22 x 22 record region) of flat window key f = 16b + k0 (k0 in 0..15) of the patch at (pc, pr).
 // The window is 8 rows x 14 columns: f = 14 ky + kx.  With e = 2b + k0 (< 28): ky = b + (e >= 14), kx = e - 14 (e >= 14), so
 // rec = (2pr + ky) * 22 + 8pc + kx = [44 pr + 8 pc + k0] + 24 b + 8 (k0 >= 14 - 2b): one compare-select per block.
-// reductions over the 4 DPP rows of a wave (lanes l, l^16, l^32, l^48) on the VALU: v_permlane16_swap exchanges the odd rows of its
-// first operand with the even rows of the second, v_permlane32_swap the upper half of the first with the lower half of the second --
-// fed two copies of x they return the pair (x, partner's x) in every lane.  (__shfl_xor is a ds_bpermute: an LDS round trip that all
-// 16 lock-stepped waves of the workgroup wait for.)
-__device__ __forceinline__ float rows_max(float x) {
-    auto a = __builtin_amdgcn_permlane16_swap(__float_as_uint(x), __float_as_uint(x), false, false);
-    x = fmaxf(__uint_as_float(a[0]), __uint_as_float(a[1]));
-    auto b = __builtin_amdgcn_permlane32_swap(__float_as_uint(x), __float_as_uint(x), false, false);
-    return fmaxf(__uint_as_float(b[0]), __uint_as_float(b[1]));
-}
-__device__ __forceinline__ float rows_sum(float x) {
-    auto a = __builtin_amdgcn_permlane16_swap(__float_as_uint(x), __float_as_uint(x), false, false);
-    x = __uint_as_float(a[0]) + __uint_as_float(a[1]);
-    auto b = __builtin_amdgcn_permlane32_swap(__float_as_uint(x), __float_as_uint(x), false, false);
-    return __uint_as_float(b[0]) + __uint_as_float(b[1]);
-}
-// a wave-uniform double pinned to scalar registers (uniform fp64 values are computed on the VALU; left in VGPRs across the tile loop
-// they are spilled to scratch and reloaded -- a memory round trip -- in the phase that uses them)
-__device__ __forceinline__ double uniform_f64(double x) {
-    const unsigned long long u = __builtin_bit_cast(unsigned long long, x);
-    unsigned lo, hi;                                 // (asm: the builtin is sunk to the use and the VGPR pair stays live)
-    asm volatile("s_nop 1\n\tv_readfirstlane_b32 %0, %2\n\tv_readfirstlane_b32 %1, %3" : "=s"(lo), "=s"(hi) : "v"((unsigned)u), "v"((unsigned)(u >> 32)));
-    return __builtin_bit_cast(double, ((unsigned long long)hi << 32) | lo);
-}
 __device__ __forceinline__ int key_rec(int b, int k0, int base0) { return base0 + 24 * b + (k0 >= 14 - 2 * b ? 8 : 0); }
 
 template <int NB>      // NB: classifier row blocks of 16 classes (0: no head)
@@ -613,7 +557,7 @@ __global__ __launch_bounds__(NT) void creff_rr_kernel(const RRParams p) {
             auto vrec = [&](int b) { return vbase + 384u * b + (((vsel >> b) & 1u) << 7); };
             auto epilogue = [&](int c, const f32x4 o) {       // o = p[query][16c + 4g .. +3]: store, then this chunk's share of the classifier
                 const unsigned off = p_off0 + (unsigned)c * p_step;
-                __builtin_amdgcn_raw_buffer_store_b128(__builtin_bit_cast(u32x4, o), p_rsrc, inq ? off : OOB, 0, PNT);
+                __builtin_amdgcn_raw_buffer_store_b128(__builtin_bit_cast(u32x4, o), p_rsrc, inq ? off : OOB_TOP16, 0, PNT);
                 if (NB > 0) {
                     u32x2 oh, ol;
                     split4(o, oh, ol);
@@ -675,7 +619,7 @@ __global__ __launch_bounds__(NT) void creff_rr_kernel(const RRParams p) {
                 for (int i = 0; i < 4; ++i) {
                     const int cls = nb * 16 + 4 * g + i;
                     const unsigned off = l_off0 + (unsigned)cls * plane * 4u;
-                    __builtin_amdgcn_raw_buffer_store_b32(__float_as_uint(lg[nb][i]), l_rsrc, (inq && cls < p.n_cls) ? off : OOB, 0, PNT);
+                    __builtin_amdgcn_raw_buffer_store_b32(__float_as_uint(lg[nb][i]), l_rsrc, (inq && cls < p.n_cls) ? off : OOB_TOP16, 0, PNT);
                 }
         }
     }
@@ -687,8 +631,7 @@ template <int NB>
 int launch(const RRParams &p, hipStream_t st) {
     static ArsegSmemAttr attr;
     if (int e = arseg_allow_smem(attr, reinterpret_cast<const void *>(creff_rr_kernel<NB>), SMEM_BYTES)) return e;
-    int dev = 0, cus = 256;
-    if (hipGetDevice(&dev) != hipSuccess || hipDeviceGetAttribute(&cus, hipDeviceAttributeMultiprocessorCount, dev) != hipSuccess) cus = 256;
+    const int cus = arseg_cu_count();
     const long long ntiles = (long long)p.tiles_x * p.tiles_y * p.N;
     const int grid = (int)(ntiles < cus ? ntiles : cus);
     hipLaunchKernelGGL((creff_rr_kernel<NB>), dim3(grid), dim3(NT), SMEM_BYTES, st, p);
@@ -697,33 +640,47 @@ int launch(const RRParams &p, hipStream_t st) {
 
 }  // namespace
 
-extern "C" int arseg_creff_warp_fwd_ex(const float *const *ref_nhwc_host, const int16_t *mv_q, int H, int W, const float *lr,
-                                       const float *wq, const float *bq, const float *wk, const float *bk, const float *wv,
-                                       const float *bv, float *p_out, int p_layout, const float *wf, const float *bf, int n_cls,
-                                       float *logits, int log_softmax, int N, int C, int Hp, int Wp, int hp, int wp, int kH, int kW,
-                                       int impl, int seg_rows, int max_wgs, arseg_stream_t stream) {
+// Argument check of the two fused warp entry points; dtype = element type of ref / lr, max_cls = the largest head that form serves.
+// The order of the checks decides what an argument list that is both invalid and unsupported reports: callers see it.
+static int check_warp_args(const void *const *ref_nhwc_host, const int16_t *mv_q, int H, int W, const void *lr, int dtype, const float *wq,
+                           const float *bq, const float *wk, const float *bk, const float *wv, const float *bv, const float *p_out,
+                           int p_layout, const float *wf, const float *bf, int n_cls, bool head, int max_cls, int N, int C, int Hp, int Wp,
+                           int hp, int wp, int kH, int kW, int seg_rows, int max_wgs) {
     ARSEG_CHECK_PTR(ref_nhwc_host); ARSEG_CHECK_PTR(mv_q); ARSEG_CHECK_PTR(lr); ARSEG_CHECK_PTR(wq); ARSEG_CHECK_PTR(bq); ARSEG_CHECK_PTR(wk);
     ARSEG_CHECK_PTR(bk); ARSEG_CHECK_PTR(wv); ARSEG_CHECK_PTR(bv); ARSEG_CHECK_PTR(p_out);
     ARSEG_CHECK_POS(N); ARSEG_CHECK_POS(C); ARSEG_CHECK_POS(Hp); ARSEG_CHECK_POS(Wp); ARSEG_CHECK_POS(hp); ARSEG_CHECK_POS(wp);
     ARSEG_CHECK_POS(H); ARSEG_CHECK_POS(W);
     if (C != CH || kH != 7 || kW != 7 || N > MAXN) return ARSEG_EUNSUPPORTED;
     if (p_layout != ARSEG_C8 && p_layout != ARSEG_NHWC) return ARSEG_EINVAL;
-    if ((size_t)C * Hp * Wp * sizeof(float) >= (1ull << 31) || (size_t)C * hp * wp * sizeof(float) >= (1ull << 31))
-        return ARSEG_EUNSUPPORTED;                                                             // 32-bit buffer offsets within a frame
+    // 32-bit buffer offsets within a frame: of p_out and of an fp32 lr (a 16-bit lr is half the size and is not bounded here)
+    if ((size_t)C * Hp * Wp * sizeof(float) >= (1ull << 31) || (dtype == ARSEG_DT_F32 && (size_t)C * hp * wp * sizeof(float) >= (1ull << 31)))
+        return ARSEG_EUNSUPPORTED;
     if ((size_t)Hp * Wp >= (1u << 30)) return ARSEG_EUNSUPPORTED;                              // tap index packing
     if (!ARSEG_ALIGNED16(lr) || !ARSEG_ALIGNED16(p_out) || !ARSEG_ALIGNED16(wq) || !ARSEG_ALIGNED16(wk) || !ARSEG_ALIGNED16(wv) ||
         !ARSEG_ALIGNED16(bq) || !ARSEG_ALIGNED16(bk) || !ARSEG_ALIGNED16(bv))
         return ARSEG_EINVAL;
-    const bool head = logits != nullptr;
     if (head) {
         if (!wf || !bf || n_cls <= 0) return ARSEG_EINVAL;
-        if (n_cls > 32) return ARSEG_EUNSUPPORTED;
+        if (n_cls > max_cls) return ARSEG_EUNSUPPORTED;
         if (!ARSEG_ALIGNED16(wf)) return ARSEG_EINVAL;
     }
-    if (impl != ARSEG_CREFF_WARP_AUTO && impl != ARSEG_CREFF_WARP_TILES && impl != ARSEG_CREFF_WARP_ROLL) return ARSEG_EINVAL;
     if (seg_rows < 0 || max_wgs < 0) return ARSEG_EINVAL;
     for (int i = 0; i < N; ++i)
         if (!ref_nhwc_host[i] || !ARSEG_ALIGNED16(ref_nhwc_host[i])) return ARSEG_EINVAL;
+    return ARSEG_OK;
+}
+
+extern "C" int arseg_creff_warp_fwd_ex(const float *const *ref_nhwc_host, const int16_t *mv_q, int H, int W, const float *lr,
+                                       const float *wq, const float *bq, const float *wk, const float *bk, const float *wv,
+                                       const float *bv, float *p_out, int p_layout, const float *wf, const float *bf, int n_cls,
+                                       float *logits, int log_softmax, int N, int C, int Hp, int Wp, int hp, int wp, int kH, int kW,
+                                       int impl, int seg_rows, int max_wgs, arseg_stream_t stream) {
+    const bool head = logits != nullptr;
+    if (int e = check_warp_args(reinterpret_cast<const void *const *>(ref_nhwc_host), mv_q, H, W, lr, ARSEG_DT_F32, wq, bq, wk, bk, wv, bv, p_out, p_layout,
+                                wf, bf, n_cls, head, 32, N, C, Hp, Wp, hp, wp, kH, kW, seg_rows, max_wgs))
+        return e;
+    // (behind the shared check or among its last checks makes no difference: all of those report EINVAL)
+    if (impl != ARSEG_CREFF_WARP_AUTO && impl != ARSEG_CREFF_WARP_TILES && impl != ARSEG_CREFF_WARP_ROLL) return ARSEG_EINVAL;
     // ONE dispatch rule (arseg_creff_warp_select states it, tests/test_gpu_ops.py::test_creff_dispatch_table enforces it): the rolling kernel
     // (creff_roll.hip) serves every launch it admits -- no head or a head of <= 16 classes, a schedule that fits its piece table -- the
     // 16 x 16 tile kernel below the rest (17-32 classes, oversized schedules) and impl = TILES
@@ -754,27 +711,12 @@ extern "C" int arseg_creff_warp16_fwd_ex(const void *const *ref_nhwc_host, const
                                          const float *bv, float *p_out, int p_layout, const float *wf, const float *bf, int n_cls,
                                          float *logits, int log_softmax, int N, int C, int Hp, int Wp, int hp, int wp, int kH, int kW,
                                          int seg_rows, int max_wgs, arseg_stream_t stream) {
-    ARSEG_CHECK_PTR(ref_nhwc_host); ARSEG_CHECK_PTR(mv_q); ARSEG_CHECK_PTR(lr); ARSEG_CHECK_PTR(wq); ARSEG_CHECK_PTR(bq); ARSEG_CHECK_PTR(wk);
-    ARSEG_CHECK_PTR(bk); ARSEG_CHECK_PTR(wv); ARSEG_CHECK_PTR(bv); ARSEG_CHECK_PTR(p_out);
-    ARSEG_CHECK_POS(N); ARSEG_CHECK_POS(C); ARSEG_CHECK_POS(Hp); ARSEG_CHECK_POS(Wp); ARSEG_CHECK_POS(hp); ARSEG_CHECK_POS(wp);
-    ARSEG_CHECK_POS(H); ARSEG_CHECK_POS(W);
+    // (in front of the shared check or behind its pointer / extent checks makes no difference: all of those report EINVAL)
     if (dtype != ARSEG_DT_F16 && dtype != ARSEG_DT_BF16) return ARSEG_EINVAL;
-    if (C != CH || kH != 7 || kW != 7 || N > MAXN) return ARSEG_EUNSUPPORTED;
-    if (p_layout != ARSEG_C8 && p_layout != ARSEG_NHWC) return ARSEG_EINVAL;
-    if ((size_t)C * Hp * Wp * sizeof(float) >= (1ull << 31)) return ARSEG_EUNSUPPORTED;       // 32-bit buffer offsets within a frame of p_out
-    if ((size_t)Hp * Wp >= (1u << 30)) return ARSEG_EUNSUPPORTED;
-    if (!ARSEG_ALIGNED16(lr) || !ARSEG_ALIGNED16(p_out) || !ARSEG_ALIGNED16(wq) || !ARSEG_ALIGNED16(wk) || !ARSEG_ALIGNED16(wv) ||
-        !ARSEG_ALIGNED16(bq) || !ARSEG_ALIGNED16(bk) || !ARSEG_ALIGNED16(bv))
-        return ARSEG_EINVAL;
-    const bool head = logits != nullptr;
-    if (head) {
-        if (!wf || !bf || n_cls <= 0) return ARSEG_EINVAL;
-        if (n_cls > 16) return ARSEG_EUNSUPPORTED;                                               // 17-32 classes: the tile kernel, fp32 inputs only
-        if (!ARSEG_ALIGNED16(wf)) return ARSEG_EINVAL;
-    }
-    if (seg_rows < 0 || max_wgs < 0) return ARSEG_EINVAL;
-    for (int i = 0; i < N; ++i)
-        if (!ref_nhwc_host[i] || !ARSEG_ALIGNED16(ref_nhwc_host[i])) return ARSEG_EINVAL;
+    // a head of up to 16 classes: 17-32 run on the tile kernel, fp32 inputs only
+    if (int e = check_warp_args(ref_nhwc_host, mv_q, H, W, lr, dtype, wq, bq, wk, bk, wv, bv, p_out, p_layout, wf, bf, n_cls, logits != nullptr, 16,
+                                N, C, Hp, Wp, hp, wp, kH, kW, seg_rows, max_wgs))
+        return e;
     // the rolling kernel or nothing: a launch it does not admit (a schedule beyond its piece table) is refused before anything runs
     return arseg_creff_roll_launch(ref_nhwc_host, mv_q, H, W, lr, dtype, wq, bq, wk, bk, wv, bv, p_out, p_layout, wf, bf, n_cls, logits,
                                    log_softmax, N, Hp, Wp, hp, wp, seg_rows, max_wgs, false, arseg_stream(stream));

@@ -29,13 +29,11 @@
 //   * 16-BIT ROWS (FMT 1 = fp16, 2 = bf16): a row is K values of 2 bytes, a K step is still 128 bytes = 64 values = two v_mfma_f32_16x16x32 per
 //     fragment pair instead of the three of the hi/lo emulation; the same DMA image, the same swizzle, the same fragment reads (slot kq = k 8kq..,
 //     slot 4 + kq = k 32 + 8kq..).  The 16-bit storage path's 1x1 and 3x3 stride-1 convs (BASELINE configs[2] / [4]) run on it.
-#include "arseg_common.h"
+#include "arseg_device.h"
 
 namespace {
 
-typedef _Float16 h16x8 __attribute__((ext_vector_type(8)));
 typedef _Float16 h16x2 __attribute__((ext_vector_type(2)));
-typedef unsigned u32x4 __attribute__((ext_vector_type(4)));
 
 struct GX3Params {
     const unsigned char *X, *W;
@@ -60,19 +58,6 @@ struct GX3Params {
     const unsigned char *res_rows;    // residual in the ACTIVATION's row format at the same row index m (out_mode 2 chains: the block input); else p.res (plain, at the output row)
     unsigned ldx;                     // bytes per activation row (K / taps values)
 };
-
-__device__ __forceinline__ unsigned lds_addr(const void *p) { return (unsigned)(size_t)(__attribute__((address_space(3))) const void *)p; }
-__device__ __forceinline__ u32x4 make_rsrc(const void *base, unsigned bytes) {
-    const unsigned long long a = (unsigned long long)base;
-    return u32x4{(unsigned)__builtin_amdgcn_readfirstlane((int)(unsigned)a), (unsigned)__builtin_amdgcn_readfirstlane((int)((unsigned)(a >> 32) & 0xffffu)),
-                 (unsigned)__builtin_amdgcn_readfirstlane((int)bytes), 0x00020000u};
-}
-// LDS[lds_base + lane*16 .. +15] <- buffer[voff .. +15]
-__device__ __forceinline__ void dma16_buf(const u32x4 rsrc, unsigned voff, unsigned lds_base) {
-    unsigned keep;
-    asm volatile("s_mov_b32 %0, m0\n\ts_mov_b32 m0, %1\n\ts_nop 0\n\tbuffer_load_dwordx4 %2, %3, 0 offen lds\n\ts_mov_b32 m0, %0"
-                 : "=&s"(keep) : "s"(lds_base), "v"(voff), "s"(rsrc) : "memory");
-}
 
 typedef __bf16 b16x8 __attribute__((ext_vector_type(8)));
 template <int FMT>
@@ -516,8 +501,8 @@ static int gemm_x3(const void *x_split, const void *w_split, const void *x2_spli
     return launch_cfg<0>(p, tile_cfg, hs);
 }
 
-// Implicit 3x3 conv / plain GEMM on rows of any of the three formats (fmt = enum arseg_rows_fmt); see arseg_conv3x3_rows_fwd in the header.
-// (round 6) The implicit-3x3 entry points arseg_conv3x3_rows_fwd / arseg_pad_rows_fwd of round 5 are gone from the ABI: the route measured parity with
+// Implicit 3x3 conv / plain GEMM on rows of any of the three formats (fmt = the ARSEG_ROWS_* enum below; the row formats and the zero-bordered
+// geometry are described at the top of this file).  The implicit-3x3 entry points arseg_conv3x3_rows_fwd / arseg_pad_rows_fwd of round 5 are gone from the ABI: the route measured parity with
 // the patch-resident kernels and was never selected.  conv_rows keeps its generality (taps = 9 on zero-bordered rows) because the kernel's K-step
 // addressing is shared with the plain GEMMs; the only caller left is arseg_gemm_rows16_fwd (taps = 1).
 enum { ARSEG_ROWS_X3 = 0, ARSEG_ROWS_F16 = 1, ARSEG_ROWS_BF16 = 2 };

@@ -8,11 +8,9 @@
 // with the operation order of the other ingest kernels; then v * na[c] + nb[c] with na = 1 / (255 std), nb = -mean / std formed in
 // double on the host ((v / 255 - mean) / std in one fma: within 2 ulp of the two-division form).  16-bit outputs round once, at the
 // store (arseg_f2h: v_cvt_pk_bf16_f32 for bf16).
-#include "arseg_common.h"
+#include "arseg_device.h"
 
 namespace {
-
-typedef unsigned u32x4 __attribute__((ext_vector_type(4)));
 
 // ------------------------------------------------------------------ the colour contract (documented in include/arseg_hip.h)
 // R = ky (Y - y0) + rv (Cr - 128);  G = ky (Y - y0) - gu (Cb - 128) - gv (Cr - 128);  B = ky (Y - y0) + bu (Cb - 128), with
@@ -210,15 +208,10 @@ __global__ __launch_bounds__(256) void frame_ingest_rows_kernel(const IngestP p)
     }
 }
 
-inline int grid_for(long long total, int cap = 8192) {
-    long long b = (total + 255) / 256;
-    return (int)(b > cap ? cap : (b < 1 ? 1 : b));
-}
-
 template <bool NV12, int OUT>
 int launch_ingest(const IngestP &p, bool staged, hipStream_t st) {
     if (staged) hipLaunchKernelGGL((frame_ingest_rows_kernel<NV12, OUT>), dim3((unsigned)(p.N * p.h * p.segs)), dim3(256), 0, st, p);
-    else hipLaunchKernelGGL((frame_ingest_kernel<NV12, OUT>), dim3(grid_for((long long)p.N * p.h * p.w)), dim3(256), 0, st, p);
+    else hipLaunchKernelGGL((frame_ingest_kernel<NV12, OUT>), dim3(arseg_grid_for((long long)p.N * p.h * p.w)), dim3(256), 0, st, p);
     return arseg_launch_status();
 }
 template <bool NV12>

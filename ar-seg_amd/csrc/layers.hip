@@ -7,11 +7,6 @@
 
 namespace {
 
-inline int grid_for(long long total, int cap = 8192) {
-    long long b = (total + 255) / 256;
-    return (int)(b > cap ? cap : (b < 1 ? 1 : b));
-}
-
 // ------------------------------------------------------------------ MaxPool2d(3, 2, 1)
 __global__ __launch_bounds__(256) void maxpool3x3s2_kernel(const float *__restrict__ in, float *__restrict__ out, int N,
                                                            int H, int W, int C, int Ho, int Wo) {
@@ -1042,7 +1037,7 @@ extern "C" int arseg_maxpool3x3s2_fwd(const float *in, float *out, int N, int H,
     ARSEG_CHECK_PTR(in); ARSEG_CHECK_PTR(out); ARSEG_CHECK_POS(N); ARSEG_CHECK_POS(H); ARSEG_CHECK_POS(W); ARSEG_CHECK_POS(C);
     if (C & 3) return ARSEG_EINVAL;
     const int Ho = (H - 1) / 2 + 1, Wo = (W - 1) / 2 + 1;
-    hipLaunchKernelGGL(maxpool3x3s2_kernel, dim3(grid_for((long long)N * Ho * Wo * (C >> 2))), dim3(256), 0, arseg_stream(stream),
+    hipLaunchKernelGGL(maxpool3x3s2_kernel, dim3(arseg_grid_for((long long)N * Ho * Wo * (C >> 2))), dim3(256), 0, arseg_stream(stream),
                        in, out, N, H, W, C, Ho, Wo);
     return arseg_launch_status();
 }
@@ -1159,7 +1154,7 @@ extern "C" int arseg_psp_prior_sum_fwd(const float *t, float *out, int N, int H,
         hipLaunchKernelGGL(psp_prior_sum_kernel, dim3(arseg_cdiv((long long)N * H * (C >> 2), 256)), dim3(256), 0, arseg_stream(stream), t, out, N,
                            H, W, C, ps);
     else
-        hipLaunchKernelGGL(psp_prior_sum_px_kernel, dim3(grid_for((long long)N * H * W * (C >> 2))), dim3(256), 0, arseg_stream(stream), t, out, N,
+        hipLaunchKernelGGL(psp_prior_sum_px_kernel, dim3(arseg_grid_for((long long)N * H * W * (C >> 2))), dim3(256), 0, arseg_stream(stream), t, out, N,
                            H, W, C, ps);
     return arseg_launch_status();
 }
@@ -1203,7 +1198,7 @@ extern "C" int arseg_psp_prior_sum16_fwd(const void *t, void *out, int dtype, in
         if (sizes[i] <= 0) return ARSEG_EINVAL;
         ps.size[i] = sizes[i]; ps.off[i] = ps.rows; ps.rows += sizes[i] * sizes[i];
     }
-    const dim3 grid(grid_for((long long)N * H * W * (C >> 3)));
+    const dim3 grid(arseg_grid_for((long long)N * H * W * (C >> 3)));
     hipStream_t hs = arseg_stream(stream);
     if (dtype == ARSEG_DT_BF16) hipLaunchKernelGGL(psp_prior_sum16_kernel<true>, grid, dim3(256), 0, hs, (const uint16_t *)t, (uint16_t *)out, N, H, W, C, ps);
     else hipLaunchKernelGGL(psp_prior_sum16_kernel<false>, grid, dim3(256), 0, hs, (const uint16_t *)t, (uint16_t *)out, N, H, W, C, ps);
@@ -1273,20 +1268,20 @@ extern "C" int arseg_resize_fwd(const float *in, float *out, int N, int C, int H
                                in, out, C, Hin, Win, in_ld, out_ld);
             return arseg_launch_status();
         }
-        hipLaunchKernelGGL(resize_nhwc_kernel, dim3(grid_for((long long)N * Hout * Wout * (C >> 2))), dim3(256), 0,
+        hipLaunchKernelGGL(resize_nhwc_kernel, dim3(arseg_grid_for((long long)N * Hout * Wout * (C >> 2))), dim3(256), 0,
                            arseg_stream(stream), in, out, N, C, Hin, Win, Hout, Wout, mode, align_corners ? 1 : 0, in_ld, out_ld);
     } else if (layout == ARSEG_NCHW) {
         if (mode == ARSEG_BILINEAR && !align_corners && (Wout == 8 * Win || Wout == 16 * Win) && ARSEG_ALIGNED16(out)) {
-            const int g = grid_for((long long)N * C * Hout * (Win + 1), 65536);
+            const int g = arseg_grid_for((long long)N * C * Hout * (Win + 1), 65536);
             if (Wout == 8 * Win)
                 hipLaunchKernelGGL(resize_nchw_bilinear_runs_kernel<8>, dim3(g), dim3(256), 0, arseg_stream(stream), in, out, N * C, Hin, Win, Hout);
             else
                 hipLaunchKernelGGL(resize_nchw_bilinear_runs_kernel<16>, dim3(g), dim3(256), 0, arseg_stream(stream), in, out, N * C, Hin, Win, Hout);
         } else if (mode == ARSEG_BILINEAR && (Wout & 3) == 0 && ARSEG_ALIGNED16(out))
-            hipLaunchKernelGGL(resize_nchw_bilinear_x4_kernel, dim3(grid_for((long long)N * C * Hout * (Wout >> 2), 16384)), dim3(256), 0,
+            hipLaunchKernelGGL(resize_nchw_bilinear_x4_kernel, dim3(arseg_grid_for((long long)N * C * Hout * (Wout >> 2), 16384)), dim3(256), 0,
                                arseg_stream(stream), in, out, N * C, Hin, Win, Hout, Wout, align_corners ? 1 : 0);
         else
-            hipLaunchKernelGGL(resize_nchw_kernel, dim3(grid_for((long long)N * C * Hout * Wout, 16384)), dim3(256), 0,
+            hipLaunchKernelGGL(resize_nchw_kernel, dim3(arseg_grid_for((long long)N * C * Hout * Wout, 16384)), dim3(256), 0,
                                arseg_stream(stream), in, out, N * C, Hin, Win, Hout, Wout, mode, align_corners ? 1 : 0);
     } else return ARSEG_EINVAL;
     return arseg_launch_status();
@@ -1296,7 +1291,7 @@ extern "C" int arseg_scale_add_fwd(const float *x, const float *scale, const flo
                                    int N, int HW, int C, arseg_stream_t stream) {
     ARSEG_CHECK_PTR(x); ARSEG_CHECK_PTR(scale); ARSEG_CHECK_PTR(out); ARSEG_CHECK_POS(N); ARSEG_CHECK_POS(HW); ARSEG_CHECK_POS(C);
     if (C & 3) return ARSEG_EINVAL;
-    hipLaunchKernelGGL(scale_add_kernel, dim3(grid_for((long long)N * HW * (C >> 2))), dim3(256), 0, arseg_stream(stream), x, scale,
+    hipLaunchKernelGGL(scale_add_kernel, dim3(arseg_grid_for((long long)N * HW * (C >> 2))), dim3(256), 0, arseg_stream(stream), x, scale,
                        add_full, add_vec, out, N, HW, C);
     return arseg_launch_status();
 }
@@ -1325,7 +1320,7 @@ extern "C" int arseg_head_fwd(const float *p, int p_ld, const float *wf, const f
         return arseg_launch_status();
     }
     const size_t smem = (size_t)n_cls * C * sizeof(float);
-    const int g = grid_for((long long)N * HW, 2048);
+    const int g = arseg_grid_for((long long)N * HW, 2048);
     if (n_cls <= 12) hipLaunchKernelGGL(head_kernel<12>, dim3(g), dim3(256), smem, st, p, p_ld, wf, bf, logits, N, HW, C, n_cls, log_softmax);
     else if (n_cls <= 19) hipLaunchKernelGGL(head_kernel<19>, dim3(g), dim3(256), smem, st, p, p_ld, wf, bf, logits, N, HW, C, n_cls, log_softmax);
     else hipLaunchKernelGGL(head_kernel<32>, dim3(g), dim3(256), smem, st, p, p_ld, wf, bf, logits, N, HW, C, n_cls, log_softmax);
@@ -1340,7 +1335,7 @@ extern "C" int arseg_frame_to_nhwc4_fwd(const float *img, float *out, int N, int
         hipLaunchKernelGGL(frame_to_nhwc4_rows_kernel, dim3((unsigned)(N * h * segs)), dim3(256), 0, arseg_stream(stream), img, out, N, H, W, h, w, segs);
         return arseg_launch_status();
     }
-    hipLaunchKernelGGL(frame_to_nhwc4_kernel, dim3(grid_for((long long)N * h * w)), dim3(256), 0, arseg_stream(stream), img, out, N, H, W, h, w);
+    hipLaunchKernelGGL(frame_to_nhwc4_kernel, dim3(arseg_grid_for((long long)N * h * w)), dim3(256), 0, arseg_stream(stream), img, out, N, H, W, h, w);
     return arseg_launch_status();
 }
 
@@ -1349,7 +1344,7 @@ extern "C" int arseg_frame_u8_to_nhwc4_fwd(const uint8_t *img_hwc, float *out, i
     ARSEG_CHECK_PTR(img_hwc); ARSEG_CHECK_PTR(out); ARSEG_CHECK_PTR(mean3); ARSEG_CHECK_PTR(std3);
     ARSEG_CHECK_POS(N); ARSEG_CHECK_POS(H); ARSEG_CHECK_POS(W); ARSEG_CHECK_POS(h); ARSEG_CHECK_POS(w);
     if (std3[0] == 0.f || std3[1] == 0.f || std3[2] == 0.f) return ARSEG_EINVAL;
-    hipLaunchKernelGGL(frame_u8_to_nhwc4_kernel, dim3(grid_for((long long)N * h * w)), dim3(256), 0, arseg_stream(stream), img_hwc, out, N, H,
+    hipLaunchKernelGGL(frame_u8_to_nhwc4_kernel, dim3(arseg_grid_for((long long)N * h * w)), dim3(256), 0, arseg_stream(stream), img_hwc, out, N, H,
                        W, h, w, mean3[0], mean3[1], mean3[2], std3[0], std3[1], std3[2]);
     return arseg_launch_status();
 }
@@ -1367,10 +1362,10 @@ extern "C" int arseg_merge_motion_fwd(const int16_t *flows, int16_t *out, void *
     hipStream_t st = arseg_stream(stream);
     int4 *dp = reinterpret_cast<int4 *>(workspace);
     const long long n = (long long)(n_frames + 1) * H * W;
-    hipLaunchKernelGGL(fill_int4_kernel, dim3(grid_for(n)), dim3(256), 0, st, dp, n, -1);
+    hipLaunchKernelGGL(fill_int4_kernel, dim3(arseg_grid_for(n)), dim3(256), 0, st, dp, n, -1);
     for (int f1 = frame_start + 1; f1 <= n_frames; ++f1)
-        hipLaunchKernelGGL(merge_motion_step_kernel, dim3(grid_for((long long)H * W)), dim3(256), 0, st, flows + (size_t)f1 * H * W * 3, dp, f1, H, W);
-    hipLaunchKernelGGL(merge_motion_out_kernel, dim3(grid_for(n)), dim3(256), 0, st, dp, out, n_frames + 1, H, W);
+        hipLaunchKernelGGL(merge_motion_step_kernel, dim3(arseg_grid_for((long long)H * W)), dim3(256), 0, st, flows + (size_t)f1 * H * W * 3, dp, f1, H, W);
+    hipLaunchKernelGGL(merge_motion_out_kernel, dim3(arseg_grid_for(n)), dim3(256), 0, st, dp, out, n_frames + 1, H, W);
     return arseg_launch_status();
 }
 
@@ -1396,14 +1391,14 @@ extern "C" int arseg_argmax_confusion_fwd(const float *logits, const int64_t *la
     unsigned long long *hh = reinterpret_cast<unsigned long long *>(hist);
     const int S = H / h;
     if (!align_corners && S * h == H && S * w == W && (S == 2 || S == 4 || S == 8)) {          // exact power-of-two upsample: one thread per run of S pixels
-        const int g = grid_for((long long)N * H * (w + 1), 4096);
+        const int g = arseg_grid_for((long long)N * H * (w + 1), 4096);
         hipStream_t st = arseg_stream(stream);
         if (S == 8) hipLaunchKernelGGL(argmax_confusion_up_kernel<8>, dim3(g), dim3(256), 0, st, logits, label, pred, hh, N, n_cls, h, w, ignore_label);
         else if (S == 4) hipLaunchKernelGGL(argmax_confusion_up_kernel<4>, dim3(g), dim3(256), 0, st, logits, label, pred, hh, N, n_cls, h, w, ignore_label);
         else hipLaunchKernelGGL(argmax_confusion_up_kernel<2>, dim3(g), dim3(256), 0, st, logits, label, pred, hh, N, n_cls, h, w, ignore_label);
         return arseg_launch_status();
     }
-    hipLaunchKernelGGL(argmax_confusion_kernel, dim3(grid_for((long long)N * H * W, 1024)), dim3(256), 0, arseg_stream(stream), logits,
+    hipLaunchKernelGGL(argmax_confusion_kernel, dim3(arseg_grid_for((long long)N * H * W, 1024)), dim3(256), 0, arseg_stream(stream), logits,
                        label, pred, hh, N, n_cls, h, w, H, W, ignore_label, align_corners);
     return arseg_launch_status();
 }
@@ -1421,14 +1416,14 @@ extern "C" int arseg_argmax_confusion_grouped_fwd(const float *logits, const int
     hipStream_t st = arseg_stream(stream);
     const int gy = N < 65535 ? N : 65535, S = H / h;
     if (!align_corners && S * h == H && S * w == W && (S == 2 || S == 4 || S == 8)) {
-        const int per = grid_for((long long)H * (w + 1), 4096), share = 4096 / gy;
+        const int per = arseg_grid_for((long long)H * (w + 1), 4096), share = 4096 / gy;
         const dim3 g(per < share ? per : (share < 1 ? 1 : share), gy);
         if (S == 8) hipLaunchKernelGGL(argmax_confusion_up_grouped_kernel<8>, g, dim3(256), 0, st, logits, label, group, pred, hh, N, n_groups, n_cls, h, w, ignore_label);
         else if (S == 4) hipLaunchKernelGGL(argmax_confusion_up_grouped_kernel<4>, g, dim3(256), 0, st, logits, label, group, pred, hh, N, n_groups, n_cls, h, w, ignore_label);
         else hipLaunchKernelGGL(argmax_confusion_up_grouped_kernel<2>, g, dim3(256), 0, st, logits, label, group, pred, hh, N, n_groups, n_cls, h, w, ignore_label);
         return arseg_launch_status();
     }
-    const int per = grid_for((long long)H * W, 1024), share = 1024 / gy;
+    const int per = arseg_grid_for((long long)H * W, 1024), share = 1024 / gy;
     hipLaunchKernelGGL(argmax_confusion_grouped_kernel, dim3(per < share ? per : (share < 1 ? 1 : share), gy), dim3(256), 0, st, logits, label, group,
                        pred, hh, N, n_groups, n_cls, h, w, H, W, ignore_label, align_corners);
     return arseg_launch_status();

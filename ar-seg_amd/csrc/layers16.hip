@@ -2,12 +2,10 @@
 // model/bisenet.py:77,215,252-258,284-298,390-398 and the frame ingest of evaluation.py:186-188).  Same arithmetic as layers.hip with
 // 16-bit loads / stores: every kernel reads 8 channels (16 bytes) per thread, computes in fp32 and rounds once (to nearest even) at the
 // store.  dtype = ARSEG_DT_F16 | ARSEG_DT_BF16.
-#include "arseg_common.h"
+#include "arseg_device.h"
 #include "warp_math.h"
 
 namespace {
-
-typedef unsigned u32x4 __attribute__((ext_vector_type(4)));
 
 template <bool BF>
 __device__ __forceinline__ void unpack8(const u32x4 v, float (&f)[8]) {
@@ -23,11 +21,6 @@ __device__ __forceinline__ u32x4 pack8(const float (&f)[8]) {
 }
 __device__ __forceinline__ u32x4 ld8(const uint16_t *p) { return *reinterpret_cast<const u32x4 *>(p); }
 __device__ __forceinline__ void st8(uint16_t *p, const u32x4 v) { *reinterpret_cast<u32x4 *>(p) = v; }
-
-inline int grid_for(long long total, int cap = 8192) {
-    long long b = (total + 255) / 256;
-    return (int)(b > cap ? cap : (b < 1 ? 1 : b));
-}
 
 // ------------------------------------------------------------------ frame ingest: NCHW fp32 RGB -> NHWC8 16-bit (+ bilinear align_corners=True downscale)
 template <bool BF>
@@ -443,7 +436,7 @@ extern "C" int arseg_frame_to_nhwc8_16_fwd(const float *img, void *out, int dtyp
                     hipLaunchKernelGGL(frame_to_nhwc8_rows_kernel<false>, dim3(gr), dim3(256), 0, arseg_stream(stream), img, (uint16_t *)out, N, H, W, h, w, segs));
         return arseg_launch_status();
     }
-    const int g = grid_for((long long)N * h * w);
+    const int g = arseg_grid_for((long long)N * h * w);
     DISPATCH_BF(dtype, hipLaunchKernelGGL(frame_to_nhwc8_kernel<true>, dim3(g), dim3(256), 0, arseg_stream(stream), img, (uint16_t *)out, N, H, W, h, w),
                 hipLaunchKernelGGL(frame_to_nhwc8_kernel<false>, dim3(g), dim3(256), 0, arseg_stream(stream), img, (uint16_t *)out, N, H, W, h, w));
     return arseg_launch_status();
@@ -453,7 +446,7 @@ extern "C" int arseg_maxpool3x3s2_16_fwd(const void *in, void *out, int dtype, i
     ARSEG_CHECK_PTR(in); ARSEG_CHECK_PTR(out); ARSEG_CHECK_POS(N); ARSEG_CHECK_POS(H); ARSEG_CHECK_POS(W); ARSEG_CHECK_POS(C);
     if ((C & 7) || !ARSEG_ALIGNED16(in) || !ARSEG_ALIGNED16(out)) return ARSEG_EINVAL;
     const int Ho = (H - 1) / 2 + 1, Wo = (W - 1) / 2 + 1;
-    const int g = grid_for((long long)N * Ho * Wo * (C >> 3));
+    const int g = arseg_grid_for((long long)N * Ho * Wo * (C >> 3));
     DISPATCH_BF(dtype, hipLaunchKernelGGL(maxpool16_kernel<true>, dim3(g), dim3(256), 0, arseg_stream(stream), (const uint16_t *)in, (uint16_t *)out, N, H, W, C, Ho, Wo),
                 hipLaunchKernelGGL(maxpool16_kernel<false>, dim3(g), dim3(256), 0, arseg_stream(stream), (const uint16_t *)in, (uint16_t *)out, N, H, W, C, Ho, Wo));
     return arseg_launch_status();
@@ -576,7 +569,7 @@ extern "C" int arseg_resize16_fwd(const void *in, void *out, int dtype, int N, i
     ARSEG_CHECK_POS(Hout); ARSEG_CHECK_POS(Wout);
     if (mode != ARSEG_NEAREST && mode != ARSEG_BILINEAR) return ARSEG_EINVAL;
     if ((C & 7) || (in_ld & 7) || (out_ld & 7) || in_ld < C || out_ld < C || !ARSEG_ALIGNED16(in) || !ARSEG_ALIGNED16(out)) return ARSEG_EINVAL;
-    const int g = grid_for((long long)N * Hout * Wout * (C >> 3));
+    const int g = arseg_grid_for((long long)N * Hout * Wout * (C >> 3));
     DISPATCH_BF(dtype, hipLaunchKernelGGL(resize16_kernel<true>, dim3(g), dim3(256), 0, arseg_stream(stream), (const uint16_t *)in, (uint16_t *)out, N, C, Hin, Win, Hout, Wout, mode, align_corners, in_ld, out_ld),
                 hipLaunchKernelGGL(resize16_kernel<false>, dim3(g), dim3(256), 0, arseg_stream(stream), (const uint16_t *)in, (uint16_t *)out, N, C, Hin, Win, Hout, Wout, mode, align_corners, in_ld, out_ld));
     return arseg_launch_status();
@@ -587,7 +580,7 @@ extern "C" int arseg_scale_add16_fwd(const void *x, const void *scale, const voi
     ARSEG_CHECK_PTR(x); ARSEG_CHECK_PTR(scale); ARSEG_CHECK_PTR(out); ARSEG_CHECK_POS(N); ARSEG_CHECK_POS(HW); ARSEG_CHECK_POS(C);
     if ((C & 7) || !ARSEG_ALIGNED16(x) || !ARSEG_ALIGNED16(scale) || !ARSEG_ALIGNED16(out) || (add_full && !ARSEG_ALIGNED16(add_full)) || (add_vec && !ARSEG_ALIGNED16(add_vec)))
         return ARSEG_EINVAL;
-    const int g = grid_for((long long)N * HW * (C >> 3));
+    const int g = arseg_grid_for((long long)N * HW * (C >> 3));
     DISPATCH_BF(dtype, hipLaunchKernelGGL(scale_add16_kernel<true>, dim3(g), dim3(256), 0, arseg_stream(stream), (const uint16_t *)x, (const uint16_t *)scale, (const uint16_t *)add_full, (const uint16_t *)add_vec, (uint16_t *)out, N, HW, C),
                 hipLaunchKernelGGL(scale_add16_kernel<false>, dim3(g), dim3(256), 0, arseg_stream(stream), (const uint16_t *)x, (const uint16_t *)scale, (const uint16_t *)add_full, (const uint16_t *)add_vec, (uint16_t *)out, N, HW, C));
     return arseg_launch_status();
@@ -617,7 +610,7 @@ extern "C" int arseg_head16_fwd(const void *p, int p_ld, int dtype, const float 
     }
     const size_t smem = (size_t)n_cls * C * sizeof(float);
     if (smem > 64 * 1024) return ARSEG_EUNSUPPORTED;
-    const int g = grid_for((long long)N * HW, 2048);
+    const int g = arseg_grid_for((long long)N * HW, 2048);
 #define HEAD(BF_) do { if (n_cls <= 12) hipLaunchKernelGGL((head16_kernel<BF_, 12>), dim3(g), dim3(256), smem, st, pp, p_ld, wf, bf, logits, N, HW, C, n_cls, log_softmax); \
                        else if (n_cls <= 19) hipLaunchKernelGGL((head16_kernel<BF_, 19>), dim3(g), dim3(256), smem, st, pp, p_ld, wf, bf, logits, N, HW, C, n_cls, log_softmax); \
                        else hipLaunchKernelGGL((head16_kernel<BF_, 32>), dim3(g), dim3(256), smem, st, pp, p_ld, wf, bf, logits, N, HW, C, n_cls, log_softmax); } while (0)
@@ -629,7 +622,7 @@ extern "C" int arseg_head16_fwd(const void *p, int p_ld, int dtype, const float 
 extern "C" int arseg_cast_fwd(const void *in, int in_dtype, void *out, int out_dtype, long long count, arseg_stream_t stream) {
     ARSEG_CHECK_PTR(in); ARSEG_CHECK_PTR(out);
     if (count <= 0 || (count & 7) || !ARSEG_ALIGNED16(in) || !ARSEG_ALIGNED16(out)) return ARSEG_EINVAL;
-    const int g = grid_for(count / 8);
+    const int g = arseg_grid_for(count / 8);
     hipStream_t st = arseg_stream(stream);
     if (out_dtype == ARSEG_DT_F32) {
         DISPATCH_BF(in_dtype, hipLaunchKernelGGL(cast_to32_kernel<true>, dim3(g), dim3(256), 0, st, (const uint16_t *)in, (float *)out, count / 8),

@@ -3,12 +3,9 @@
 //   arseg_peak_stream_copy : HBM -> HBM copy of n_bytes with 16-byte accesses (read + write = 2 n_bytes of traffic per launch)
 //   arseg_peak_mfma_f16    : every wave of a full-chip launch issues `iters` x 8 independent v_mfma_f32_32x32x16_f16 (no memory traffic)
 // bench.py times each with HIP events once per run and prints `peaks_measured`.
-#include "arseg_common.h"
+#include "arseg_device.h"
 
 namespace {
-
-typedef _Float16 h16x8 __attribute__((ext_vector_type(8)));
-typedef unsigned u32x4 __attribute__((ext_vector_type(4)));
 
 __global__ __launch_bounds__(256) void peak_copy_kernel(const u32x4 *__restrict__ src, u32x4 *__restrict__ dst, size_t n16) {
     // grid-stride, four 16-byte loads in flight per thread, consecutive lanes on consecutive addresses
@@ -46,8 +43,7 @@ extern "C" int arseg_peak_stream_copy(const void *src, void *dst, size_t n_bytes
     ARSEG_CHECK_PTR(src); ARSEG_CHECK_PTR(dst);
     if (n_bytes < 16 || (n_bytes & 15) || !ARSEG_ALIGNED16(src) || !ARSEG_ALIGNED16(dst)) return ARSEG_EINVAL;
     hipStream_t st = arseg_stream(stream);
-    int dev = 0, cus = 256;
-    if (hipGetDevice(&dev) != hipSuccess || hipDeviceGetAttribute(&cus, hipDeviceAttributeMultiprocessorCount, dev) != hipSuccess) cus = 256;
+    const int cus = arseg_cu_count();
     hipLaunchKernelGGL(peak_copy_kernel, dim3(cus * 16), dim3(256), 0, st, (const u32x4 *)src, (u32x4 *)dst, n_bytes / 16);
     return arseg_launch_status();
 }
@@ -56,8 +52,7 @@ extern "C" int arseg_peak_stream_copy(const void *src, void *dst, size_t n_bytes
 extern "C" int arseg_peak_mfma_f16(float *scratch, int iters, double *flops_out, arseg_stream_t stream) {
     ARSEG_CHECK_PTR(scratch); ARSEG_CHECK_POS(iters);
     hipStream_t st = arseg_stream(stream);
-    int dev = 0, cus = 256;
-    if (hipGetDevice(&dev) != hipSuccess || hipDeviceGetAttribute(&cus, hipDeviceAttributeMultiprocessorCount, dev) != hipSuccess) cus = 256;
+    const int cus = arseg_cu_count();
     const int wgs = cus * 4;                     // 4 workgroups x 4 waves per CU: four waves per SIMD
     if (flops_out) *flops_out = (double)wgs * 4.0 * (double)iters * 8.0 * (2.0 * 32 * 32 * 16);
     hipLaunchKernelGGL(peak_mfma_kernel, dim3(wgs), dim3(256), 0, st, scratch, iters);

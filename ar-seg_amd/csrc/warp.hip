@@ -150,11 +150,6 @@ __global__ __launch_bounds__(256) void warp_mvq_nhwc_kernel(const float *__restr
     }
 }
 
-inline int grid_for(long long total) {
-    long long b = (total + 255) / 256;
-    return (int)(b > 8192 ? 8192 : (b < 1 ? 1 : b));
-}
-
 }  // namespace
 
 extern "C" int arseg_warp_fwd(const float *feature, const void *flow, int flow_dtype, float *out, int N, int C, int H,
@@ -168,14 +163,14 @@ extern "C" int arseg_warp_fwd(const float *feature, const void *flow, int flow_d
         if (out_layout != ARSEG_NHWC && out_layout != ARSEG_C8) return ARSEG_EINVAL;
         const int c8 = out_layout == ARSEG_C8;
         if (c8 && (C & 7)) return ARSEG_EINVAL;
-        const int g = grid_for((long long)N * H * W * (C >> 2));
+        const int g = arseg_grid_for((long long)N * H * W * (C >> 2));
         if (flow_dtype == ARSEG_FLOW_F64)
             hipLaunchKernelGGL(warp_nhwc_kernel<double>, dim3(g), dim3(256), 0, st, feature, (const double *)flow, out, N, C, H, W, c8);
         else
             hipLaunchKernelGGL(warp_nhwc_kernel<float>, dim3(g), dim3(256), 0, st, feature, (const float *)flow, out, N, C, H, W, c8);
     } else if (layout == ARSEG_NCHW) {
         if (out_layout != ARSEG_NCHW) return ARSEG_EINVAL;
-        const int g = grid_for((long long)N * H * W);
+        const int g = arseg_grid_for((long long)N * H * W);
         if (flow_dtype == ARSEG_FLOW_F64)
             hipLaunchKernelGGL(warp_nchw_kernel<double>, dim3(g), dim3(256), 0, st, feature, (const double *)flow, out, N, C, H, W);
         else
@@ -188,7 +183,7 @@ extern "C" int arseg_mv_resize_fwd(const int16_t *mv_q, double *out, int N, int 
                                    arseg_stream_t stream) {
     ARSEG_CHECK_PTR(mv_q); ARSEG_CHECK_PTR(out);
     ARSEG_CHECK_POS(N); ARSEG_CHECK_POS(H); ARSEG_CHECK_POS(W); ARSEG_CHECK_POS(Hp); ARSEG_CHECK_POS(Wp);
-    hipLaunchKernelGGL(mv_resize_kernel, dim3(grid_for((long long)N * Hp * Wp)), dim3(256), 0, arseg_stream(stream), mv_q,
+    hipLaunchKernelGGL(mv_resize_kernel, dim3(arseg_grid_for((long long)N * Hp * Wp)), dim3(256), 0, arseg_stream(stream), mv_q,
                        out, N, H, W, Hp, Wp);
     return arseg_launch_status();
 }
@@ -197,7 +192,7 @@ extern "C" int arseg_flow_resize_fwd(const void *flow, int flow_dtype, double *o
                                      arseg_stream_t stream) {
     ARSEG_CHECK_PTR(flow); ARSEG_CHECK_PTR(out);
     ARSEG_CHECK_POS(N); ARSEG_CHECK_POS(H); ARSEG_CHECK_POS(W); ARSEG_CHECK_POS(Hp); ARSEG_CHECK_POS(Wp);
-    const int g = grid_for((long long)N * Hp * Wp);
+    const int g = arseg_grid_for((long long)N * Hp * Wp);
     if (flow_dtype == ARSEG_FLOW_F64)
         hipLaunchKernelGGL(flow_resize_kernel<double>, dim3(g), dim3(256), 0, arseg_stream(stream), (const double *)flow, out, N, H, W, Hp, Wp);
     else if (flow_dtype == ARSEG_FLOW_F32)

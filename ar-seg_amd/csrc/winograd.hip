@@ -11,7 +11,7 @@
 // Layouts: V = [36][T][C], M = [36][T][Cout], T = N*d*d*tilesY*tilesX, tile t = (((n*d+sy)*d+sx)*tilesY+ty)*tilesX+tx,
 // tilesY = ceil(ceil(H/d)/4).  Threads run along channels (coalesced 4-byte accesses, 36 registers of patch per thread).
 // fp32 throughout; the transform constants grow the rounding error to ~1e-5 relative (vs 1e-6 for the direct form).
-#include "arseg_common.h"
+#include "arseg_device.h"
 
 namespace {
 
@@ -53,8 +53,6 @@ __device__ __forceinline__ void tile_origin(const WinoGeom &g, int t, int &n, in
     y0 = sy + g.d * 4 * ty;     // image row of the tile's first output
     x0 = sx + g.d * 4 * tx;
 }
-
-typedef float f32x2 __attribute__((ext_vector_type(2)));
 
 // One transformed value (pair) of frequency k, tile t, channel c.  SPLIT: V is written in the "split rows" operand format of
 // arseg_gemm_x3_fwd (csrc/gemm_x3.hip: per 32 channels 32 hi halves then 32 lo halves, the same 4 bytes per value) so that the batched
@@ -244,11 +242,6 @@ __global__ __launch_bounds__(256) void wino43_output_kernel(const float *__restr
     }
 }
 
-inline int grid_for(long long total) {
-    long long b = (total + 255) / 256;
-    return (int)(b > 16384 ? 16384 : (b < 1 ? 1 : b));
-}
-
 }  // namespace
 
 extern "C" long long arseg_wino43_tiles(int N, int H, int W, int dil) {
@@ -272,19 +265,19 @@ static int wino43_input(const float *in, int in_ld, float *V, int N, int H, int 
     hipStream_t hs = arseg_stream(stream);
     if (split) {
         if (!vec2 || (C & 31) || !ARSEG_ALIGNED16(V) || (reinterpret_cast<uintptr_t>(range_flag) & 3)) return ARSEG_EINVAL;
-        if (upsample2x) hipLaunchKernelGGL((wino43_input_up2_kernel<f32x2, true>), dim3(grid_for((long long)g.T * C / 2)), dim3(256), 0, hs, in, in_ld, V, C, g, v_scale, rf, rl);
-        else hipLaunchKernelGGL((wino43_input_kernel<f32x2, true>), dim3(grid_for((long long)g.T * C / 2)), dim3(256), 0, hs, in, in_ld, V, C, g, v_scale, rf, rl);
+        if (upsample2x) hipLaunchKernelGGL((wino43_input_up2_kernel<f32x2, true>), dim3(arseg_grid_for((long long)g.T * C / 2, 16384)), dim3(256), 0, hs, in, in_ld, V, C, g, v_scale, rf, rl);
+        else hipLaunchKernelGGL((wino43_input_kernel<f32x2, true>), dim3(arseg_grid_for((long long)g.T * C / 2, 16384)), dim3(256), 0, hs, in, in_ld, V, C, g, v_scale, rf, rl);
         return arseg_launch_status();
     }
     if (upsample2x) {
-        if (vec2) hipLaunchKernelGGL((wino43_input_up2_kernel<f32x2>), dim3(grid_for((long long)g.T * C / 2)), dim3(256), 0, hs, in, in_ld, V, C, g, v_scale, rf, rl);
-        else hipLaunchKernelGGL((wino43_input_up2_kernel<float>), dim3(grid_for((long long)g.T * C)), dim3(256), 0, hs, in, in_ld, V, C, g, v_scale, rf, rl);
+        if (vec2) hipLaunchKernelGGL((wino43_input_up2_kernel<f32x2>), dim3(arseg_grid_for((long long)g.T * C / 2, 16384)), dim3(256), 0, hs, in, in_ld, V, C, g, v_scale, rf, rl);
+        else hipLaunchKernelGGL((wino43_input_up2_kernel<float>), dim3(arseg_grid_for((long long)g.T * C, 16384)), dim3(256), 0, hs, in, in_ld, V, C, g, v_scale, rf, rl);
         return arseg_launch_status();
     }
     if (vec2)
-        hipLaunchKernelGGL((wino43_input_kernel<f32x2>), dim3(grid_for((long long)g.T * C / 2)), dim3(256), 0, hs, in, in_ld, V, C, g, v_scale, rf, rl);
+        hipLaunchKernelGGL((wino43_input_kernel<f32x2>), dim3(arseg_grid_for((long long)g.T * C / 2, 16384)), dim3(256), 0, hs, in, in_ld, V, C, g, v_scale, rf, rl);
     else
-        hipLaunchKernelGGL((wino43_input_kernel<float>), dim3(grid_for((long long)g.T * C)), dim3(256), 0, hs, in, in_ld, V, C, g, v_scale, rf, rl);
+        hipLaunchKernelGGL((wino43_input_kernel<float>), dim3(arseg_grid_for((long long)g.T * C, 16384)), dim3(256), 0, hs, in, in_ld, V, C, g, v_scale, rf, rl);
     return arseg_launch_status();
 }
 
@@ -307,10 +300,10 @@ extern "C" int arseg_wino43_output_fwd(const float *M, const float *scale, const
     const WinoGeom g = make_geom(N, H, W, dil);
     auto al8 = [](const void *p) { return !(reinterpret_cast<uintptr_t>(p) & 7); };
     if (!(Cout & 1) && !(out_ld & 1) && !(res_ld & 1) && al8(M) && al8(out) && al8(scale) && al8(bias) && al8(residual))
-        hipLaunchKernelGGL(wino43_output_kernel<f32x2>, dim3(grid_for((long long)g.T * Cout / 2)), dim3(256), 0, arseg_stream(stream), M, scale,
+        hipLaunchKernelGGL(wino43_output_kernel<f32x2>, dim3(arseg_grid_for((long long)g.T * Cout / 2, 16384)), dim3(256), 0, arseg_stream(stream), M, scale,
                            bias, residual, res_ld, out, out_ld, Cout, act, prelu_slope, g, m_scale);
     else
-        hipLaunchKernelGGL(wino43_output_kernel<float>, dim3(grid_for((long long)g.T * Cout)), dim3(256), 0, arseg_stream(stream), M, scale,
+        hipLaunchKernelGGL(wino43_output_kernel<float>, dim3(arseg_grid_for((long long)g.T * Cout, 16384)), dim3(256), 0, arseg_stream(stream), M, scale,
                            bias, residual, res_ld, out, out_ld, Cout, act, prelu_slope, g, m_scale);
     return arseg_launch_status();
 }

@@ -130,16 +130,15 @@ def creff_warp(refs_nhwc, mv_q: torch.Tensor, lr_nhwc: torch.Tensor, attn, head=
     if is16(lr_nhwc) or any(is16(r) for r in refs_nhwc):
         dt = _need_gpu16(lr_nhwc, *refs_nhwc)
         _need_gpu(mv_q, dtype=torch.int16)
-        B, hp, wp, C = lr_nhwc.shape
-        Hp, Wp, C2 = refs_nhwc[0].shape
-        if len(refs_nhwc) != B or mv_q.shape[0] != B or C2 != C or any(tuple(r.shape) != (Hp, Wp, C) for r in refs_nhwc):
-            raise _lib.ArsegError("creff_warp: refs / mv_q / lr batch or channel mismatch")
+        B, C, Hp, Wp, hp, wp = _check_warp_shapes(refs_nhwc, mv_q, lr_nhwc)
         if not (C == 64 and kH == 7 and kW == 7):
             return _creff_warp16_two_kernel(dt, refs_nhwc, mv_q, lr_nhwc, attn, head, log_softmax, kH, kW, p_layout)
         n_cls = 0 if head is None else head[0].shape[0]
         direct = (config.creff_warp16 or WARP16_DEFAULT) == "direct"
         if direct and n_cls <= 32 and C * Hp * Wp * 4 < (1 << 31) and creff_warp_kernel(B, C, Hp, Wp, hp, wp, n_cls, kH, kW) == "roll":
-            return _creff_warp16_direct(dt, refs_nhwc, mv_q, lr_nhwc, attn, head, log_softmax, p_layout)
+            # the rolling kernel on the 16-bit tensors as they are; it addresses every frame through its own descriptors: only the
+            # pointer table caps a launch
+            return _launch_creff_warp(dt, min(B, 32), refs_nhwc, mv_q, lr_nhwc, attn, head, log_softmax, kH, kW, p_layout)
         # cast once: every distinct keyframe feature of THIS call (the frames of a GOP batch share one) and the LR batch, then the fp32 routes below
         once = {}
         for r in refs_nhwc:
@@ -150,43 +149,36 @@ def creff_warp(refs_nhwc, mv_q: torch.Tensor, lr_nhwc: torch.Tensor, attn, head=
         lr_nhwc = cast(lr_nhwc, torch.float32)
     _need_gpu(lr_nhwc, *refs_nhwc)
     _need_gpu(mv_q, dtype=torch.int16)
-    lr_nhwc, mv_q = lr_nhwc.contiguous(), mv_q.contiguous()
-    B, hp, wp, C = lr_nhwc.shape
-    refs = [r.contiguous() for r in refs_nhwc]
-    Hp, Wp, C2 = refs[0].shape
-    _, H, W, _ = mv_q.shape
-    if len(refs) != B or mv_q.shape[0] != B or C2 != C or any(tuple(r.shape) != (Hp, Wp, C) for r in refs):
-        raise _lib.ArsegError("creff_warp: refs / mv_q / lr batch or channel mismatch")
-    fused_ok = C == 64 and kH == 7 and kW == 7 and (head is None or head[0].shape[0] <= 32) and C * Hp * Wp * 4 < (1 << 31)
+    B, C, Hp, Wp, hp, wp = _check_warp_shapes(refs_nhwc, mv_q, lr_nhwc)
+    n_cls = 0 if head is None else head[0].shape[0]
+    fused_ok = C == 64 and kH == 7 and kW == 7 and n_cls <= 32 and C * Hp * Wp * 4 < (1 << 31)
     if not fused_ok:
         ref_c8 = torch.empty((B, C // 8, Hp, Wp, 8), dtype=torch.float32, device=lr_nhwc.device)
         for b in range(B):
-            warp_mvq(refs[b].unsqueeze(0), mv_q[b:b + 1], _lib.C8, out=ref_c8[b:b + 1])
+            warp_mvq(refs_nhwc[b].unsqueeze(0), mv_q[b:b + 1], _lib.C8, out=ref_c8[b:b + 1])
         p_c8, logits = creff(ref_c8, lr_nhwc, attn, head, log_softmax, kH, kW)
         return (p_c8 if p_layout == _lib.C8 else from_c8(p_c8, _lib.NHWC)), logits
-    n_cls = 0 if head is None else head[0].shape[0]
     per = _warp_frames_per_launch(B, C, Hp, Wp, hp, wp, n_cls, kH, kW)
-    shape = (B, C // 8, Hp, Wp, 8) if p_layout == _lib.C8 else (B, Hp, Wp, C)
-    p_out = torch.empty(shape, dtype=torch.float32, device=lr_nhwc.device)
-    logits, wf, bf = None, None, None
-    if head is not None:
-        wf, bf = head
-        logits = torch.empty((B, n_cls, Hp, Wp), dtype=torch.float32, device=lr_nhwc.device)
-    impl = {"tiles": 1, "roll": 2}.get(config.creff_warp_impl, 0)
-    for i in range(0, B, per):          # one launch unless the kernel's addressing caps it; every launch writes its slice of the one output
-        b = min(per, B - i)
-        ptrs = (ctypes.c_void_p * b)(*[r.data_ptr() for r in refs[i:i + b]])
-        launch("creff_warp", _lib.load().arseg_creff_warp_fwd_ex, ptrs, _ptr(mv_q[i:i + b]), H, W, _ptr(lr_nhwc[i:i + b]), _ptr(attn.wq), _ptr(attn.bq),
-                _ptr(attn.wk), _ptr(attn.bk), _ptr(attn.wv), _ptr(attn.bv), _ptr(p_out[i:i + b]), p_layout, _ptr(wf), _ptr(bf), n_cls,
-                _ptr(None if logits is None else logits[i:i + b]), 1 if log_softmax else 0, b, C, Hp, Wp, hp, wp, kH, kW, impl,
-                max(0, int(config.creff_seg_rows)), max(0, int(config.creff_max_wgs)), _stream(),
-                flops=b * Hp * Wp * C * (250 + 2 * n_cls),
-                nbytes=b * (4 * (2 * C * Hp * Wp + C * hp * wp + n_cls * Hp * Wp) + 4 * H * W))
-    return p_out, logits
+    return _launch_creff_warp(None, per, refs_nhwc, mv_q, lr_nhwc, attn, head, log_softmax, kH, kW, p_layout)
 
 
-def _creff_warp16_direct(dt, refs_nhwc, mv_q, lr_nhwc, attn, head, log_softmax, p_layout):
-    """The rolling kernel on the 16-bit tensors as they are (C = 64, 7 x 7, a launch it admits: the caller has asked creff_warp_kernel)."""
+def _warp_knobs() -> Tuple[int, int, int]:
+    """(impl, seg_rows, max_wgs) as the fused entry points and arseg_creff_warp_select take them, from ops.config."""
+    return {"tiles": 1, "roll": 2}.get(config.creff_warp_impl, 0), max(0, int(config.creff_seg_rows)), max(0, int(config.creff_max_wgs))
+
+
+def _check_warp_shapes(refs_nhwc, mv_q, lr_nhwc) -> Tuple[int, int, int, int, int, int]:
+    """(B, C, Hp, Wp, hp, wp) of a creff_warp call whose refs / mv_q / lr agree in batch, extent and channels; raises otherwise."""
+    B, hp, wp, C = lr_nhwc.shape
+    Hp, Wp, C2 = refs_nhwc[0].shape
+    if len(refs_nhwc) != B or mv_q.shape[0] != B or C2 != C or any(tuple(r.shape) != (Hp, Wp, C) for r in refs_nhwc):
+        raise _lib.ArsegError("creff_warp: refs / mv_q / lr batch or channel mismatch")
+    return B, C, Hp, Wp, hp, wp
+
+
+def _launch_creff_warp(dt, per, refs_nhwc, mv_q, lr_nhwc, attn, head, log_softmax, kH, kW, p_layout):
+    """The fused kernel on checked tensors, ``per`` frames a launch; every launch writes its slice of the one output.  dt None: fp32 features
+    (arseg_creff_warp_fwd_ex); dt = the features' 16-bit arseg_dtype: read as they are (arseg_creff_warp16_fwd_ex)."""
     lr_nhwc, mv_q = lr_nhwc.contiguous(), mv_q.contiguous()
     refs = [r.contiguous() for r in refs_nhwc]
     B, hp, wp, C = lr_nhwc.shape
@@ -199,16 +191,19 @@ def _creff_warp16_direct(dt, refs_nhwc, mv_q, lr_nhwc, attn, head, log_softmax, 
     if head is not None:
         wf, bf = head
         logits = torch.empty((B, n_cls, Hp, Wp), dtype=torch.float32, device=lr_nhwc.device)
-    per = min(B, 32)          # (the rolling kernel addresses every frame through its own descriptors: only the pointer table caps a launch)
+    fn = _lib.load().arseg_creff_warp_fwd_ex if dt is None else _lib.load().arseg_creff_warp16_fwd_ex
+    knobs = _warp_knobs()[0 if dt is None else 1:]          # (the 16-bit form has one kernel: no impl)
+    esz = 4 if dt is None else 2          # bytes per feature element read; p and the logits are written as fp32
     for i in range(0, B, per):
         b = min(per, B - i)
         ptrs = (ctypes.c_void_p * b)(*[r.data_ptr() for r in refs[i:i + b]])
-        launch("creff_warp", _lib.load().arseg_creff_warp16_fwd_ex, ptrs, _ptr(lr_nhwc[i:i + b]), dt, _ptr(mv_q[i:i + b]), H, W, _ptr(attn.wq),
-                _ptr(attn.bq), _ptr(attn.wk), _ptr(attn.bk), _ptr(attn.wv), _ptr(attn.bv), _ptr(p_out[i:i + b]), p_layout, _ptr(wf), _ptr(bf), n_cls,
-                _ptr(None if logits is None else logits[i:i + b]), 1 if log_softmax else 0, b, C, Hp, Wp, hp, wp, 7, 7,
-                max(0, int(config.creff_seg_rows)), max(0, int(config.creff_max_wgs)), _stream(),
-                flops=b * Hp * Wp * C * (250 + 2 * n_cls),
-                nbytes=b * (2 * (C * Hp * Wp + C * hp * wp) + 4 * (C * Hp * Wp + n_cls * Hp * Wp) + 4 * H * W))
+        lr_i, mv_i = _ptr(lr_nhwc[i:i + b]), _ptr(mv_q[i:i + b])
+        lead = (ptrs, mv_i, H, W, lr_i) if dt is None else (ptrs, lr_i, dt, mv_i, H, W)
+        launch("creff_warp", fn, *lead, _ptr(attn.wq), _ptr(attn.bq), _ptr(attn.wk), _ptr(attn.bk), _ptr(attn.wv), _ptr(attn.bv),
+               _ptr(p_out[i:i + b]), p_layout, _ptr(wf), _ptr(bf), n_cls, _ptr(None if logits is None else logits[i:i + b]),
+               1 if log_softmax else 0, b, C, Hp, Wp, hp, wp, kH, kW, *knobs, _stream(),
+               flops=b * Hp * Wp * C * (250 + 2 * n_cls),
+               nbytes=b * (esz * (C * Hp * Wp + C * hp * wp) + 4 * (C * Hp * Wp + n_cls * Hp * Wp) + 4 * H * W))
     return p_out, logits
 
 
@@ -237,9 +232,8 @@ def _warp_frames_per_launch(B, C, Hp, Wp, hp, wp, n_cls, kH=7, kW=7) -> int:
     """Frames one arseg_creff_warp_fwd_ex launch takes for this shape under the current knobs: 32 pointers; the rolling kernel addresses every
     frame through its own buffer descriptor (any batch), the tile kernel the whole batch through one (N x C x Hp x Wp x 4 < 2 GiB) -- asked of
     the library's own dispatch query, not restated here."""
-    impl = {"tiles": 1, "roll": 2}.get(config.creff_warp_impl, 0)
     sel = _lib.load().arseg_creff_warp_select
-    args = (C, Hp, Wp, hp, wp, kH, kW, n_cls, impl, max(0, int(config.creff_seg_rows)), max(0, int(config.creff_max_wgs)))
+    args = (C, Hp, Wp, hp, wp, kH, kW, n_cls, *_warp_knobs())
     per = min(B, 32)
     if per > 1 and sel(per, *args) == _lib.ARSEG_EUNSUPPORTED:          # not as one launch: what the batch-wide descriptors admit
         per = max(1, min(per, ((1 << 31) - 1) // (C * Hp * Wp * 4)))
@@ -250,10 +244,9 @@ def creff_warp_kernel(B: int, C: int, Hp: int, Wp: int, hp: int, wp: int, n_cls:
     """Which kernel ``creff_warp`` runs for this launch under the current knobs: "roll" (csrc/creff_roll.hip), "tiles" (csrc/creff_rr.hip) or
     "two-kernel" (arseg_warp_mvq_fwd + arseg_creff_fwd: shapes the fused entry point does not cover).  A pure query of the library's own
     dispatch rule (arseg_creff_warp_select) -- bench.py labels its roofline line with it instead of restating the rule."""
-    impl = {"tiles": 1, "roll": 2}.get(config.creff_warp_impl, 0)
+    impl, seg_rows, max_wgs = _warp_knobs()
     per = _warp_frames_per_launch(B, C, Hp, Wp, hp, wp, n_cls, kH, kW)
-    st = _lib.load().arseg_creff_warp_select(min(B, per), C, Hp, Wp, hp, wp, kH, kW, n_cls, impl, max(0, int(config.creff_seg_rows)),
-                                             max(0, int(config.creff_max_wgs)))
+    st = _lib.load().arseg_creff_warp_select(min(B, per), C, Hp, Wp, hp, wp, kH, kW, n_cls, impl, seg_rows, max_wgs)
     if st == _lib.ARSEG_EUNSUPPORTED and impl != 2:
         return "two-kernel"
     _lib.check(st if st < 0 else 0, "creff_warp_select")
