@@ -21,7 +21,7 @@ NEAREST, BILINEAR = 0, 1
 REDUCE_MEAN, REDUCE_MAX = 0, 1
 MATH_F32, MATH_F16X3, MATH_F16 = 0, 1, 2
 DT_F32, DT_F16, DT_BF16 = 0, 1, 2
-SRC_RGB8, SRC_NV12 = 0, 1
+SRC_RGB8, SRC_NV12, SRC_I420, SRC_P010, SRC_I010 = 0, 1, 2, 3, 4
 COLOUR_BT601_LIMITED, COLOUR_BT601_FULL, COLOUR_BT709_LIMITED, COLOUR_BT709_FULL = 0, 1, 2, 3
 
 
@@ -116,6 +116,7 @@ PROTOTYPES = {
     "arseg_frame_to_nhwc4_fwd": (c_int, [_P, _P, c_int, c_int, c_int, c_int, c_int, _STREAM]),
     "arseg_frame_u8_to_nhwc4_fwd": (c_int, [_P, _P, c_int, c_int, c_int, c_int, c_int, POINTER(c_float), POINTER(c_float), _STREAM]),
     "arseg_frame_ingest_fwd": (c_int, [_P, _P, c_int, c_int64, c_int64, c_int64, c_int64, c_int, _P, c_int] + [c_int] * 5 + [POINTER(c_float), POINTER(c_float), _STREAM]),
+    "arseg_frame_ingest_yuv_fwd": (c_int, [_P, _P, _P, c_int] + [c_int64] * 6 + [c_int, _P, c_int] + [c_int] * 5 + [POINTER(c_float), POINTER(c_float), _STREAM]),
     "arseg_merge_motion_workspace_bytes": (c_size_t, [c_int, c_int, c_int]),
     "arseg_merge_motion_fwd": (c_int, [_P, _P, _P, c_size_t, c_int, c_int, c_int, c_int, _STREAM]),
     "arseg_nchw_to_nhwc_fwd": (c_int, [_P, _P, c_int, c_int, c_int, c_int, _STREAM]),

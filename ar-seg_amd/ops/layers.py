@@ -38,19 +38,19 @@ def frame_ingest(img: torch.Tensor, h: int, w: int, dtype: torch.dtype = torch.f
 
 
 def _plane_layout(t: torch.Tensor, inner, what: str):
-    """(pitch, image stride) in bytes of a uint8 plane [N,H,...inner]: rows of ``inner`` contiguous bytes, any row pitch / image stride."""
+    """(pitch, image stride) in bytes of a uint8 / uint16 plane [N,H,...inner]: rows of ``inner`` contiguous samples, any row pitch / image stride."""
     want, row = [], 1
     for d in reversed(inner):
         want.insert(0, row)
         row *= d
     N, H = t.shape[0], t.shape[1]
     if tuple(t.shape[2:]) != tuple(inner) or tuple(t.stride()[2:]) != tuple(want):
-        raise _lib.ArsegError(f"{what}: expected rows of {tuple(inner)} contiguous bytes, got shape {tuple(t.shape)} strides {t.stride()}")
+        raise _lib.ArsegError(f"{what}: expected rows of {tuple(inner)} contiguous samples, got shape {tuple(t.shape)} strides {t.stride()}")
     pitch = t.stride(1) if H > 1 else row
     n_stride = t.stride(0) if N > 1 else 0
     if pitch < row or n_stride < 0:
-        raise _lib.ArsegError(f"{what}: row pitch {pitch} is smaller than a row of {row} bytes (or a negative image stride)")
-    return pitch, n_stride
+        raise _lib.ArsegError(f"{what}: row pitch {pitch} is smaller than a row of {row} samples (or a negative image stride)")
+    return pitch * t.element_size(), n_stride * t.element_size()
 
 
 def frame_ingest8(plane0: torch.Tensor, plane1: Optional[torch.Tensor], src_format: int, h: int, w: int, mean, std,
@@ -83,9 +83,42 @@ def frame_ingest8(plane0: torch.Tensor, plane1: Optional[torch.Tensor], src_form
     return out
 
 
+def frame_ingest_yuv(planes, src_format: int, h: int, w: int, mean, std, dtype: torch.dtype = torch.float32,
+                     colour: int = _lib.COLOUR_BT709_LIMITED) -> torch.Tensor:
+    """Planar 4:2:0 / 10-bit decoder frames -> the conv engine's input at (h,w) in one kernel, like ``frame_ingest8`` (csrc/ingest.hip).
+    ``src_format`` _lib.SRC_I420: planes = (Y [N,H,W], Cb [N,H/2,W/2], Cr [N,H/2,W/2]) uint8;  _lib.SRC_I010: the same planes, uint16, code in
+    the low 10 bits;  _lib.SRC_P010: planes = (Y [N,H,W], (Cb, Cr) [N,H/2,W/2,2]) uint16, code in the high 10 bits.  Planes may be views with a
+    row pitch and an image stride.  include/arseg_hip.h, arseg_frame_ingest_yuv_fwd."""
+    if src_format not in (_lib.SRC_I420, _lib.SRC_P010, _lib.SRC_I010):
+        raise _lib.ArsegError(f"frame_ingest_yuv: unknown source format {src_format}")
+    if dtype != torch.float32 and dtype not in _DT16:
+        raise _lib.ArsegError(f"frame_ingest_yuv: unsupported output dtype {dtype}")
+    planar = src_format != _lib.SRC_P010
+    planes = tuple(planes)
+    if len(planes) != (3 if planar else 2) or any(not torch.is_tensor(t) for t in planes):
+        raise _lib.ArsegError(f"frame_ingest_yuv: expected {3 if planar else 2} plane tensors, got {len(planes)}")
+    _need_gpu(*planes, dtype=torch.uint8 if src_format == _lib.SRC_I420 else torch.uint16)
+    y = planes[0]
+    if y.dim() != 3 or any(t.device != y.device for t in planes):
+        raise _lib.ArsegError("frame_ingest_yuv expects a luma plane [N,H,W] and its chroma planes on one device")
+    N, H, W = y.shape
+    inner = (W // 2,) if planar else (W // 2, 2)
+    if H % 2 or W % 2 or any(tuple(t.shape) != (N, H // 2) + inner for t in planes[1:]):
+        raise _lib.ArsegError(f"frame_ingest_yuv: needs even H, W and chroma planes {(N, H // 2) + inner}; got {[tuple(t.shape) for t in planes]}")
+    lay = [_plane_layout(y, (W,), "frame_ingest_yuv plane 0")] + [_plane_layout(t, inner, f"frame_ingest_yuv plane {i + 1}") for i, t in enumerate(planes[1:])]
+    lay += [(0, 0)] * (3 - len(lay))
+    out = torch.empty((N, h, w, 4 if dtype == torch.float32 else 8), dtype=dtype, device=y.device)
+    m3, s3 = (ctypes.c_float * 3)(*[float(v) for v in mean]), (ctypes.c_float * 3)(*[float(v) for v in std])
+    src_bytes = N * H * W * 3 // 2 * y.element_size()
+    launch("frame_ingest_yuv", _lib.load().arseg_frame_ingest_yuv_fwd, _ptr(y), _ptr(planes[1]), _ptr(planes[2] if planar else None), src_format,
+           lay[0][0], lay[1][0], lay[2][0], lay[0][1], lay[1][1], lay[2][1], int(colour), _ptr(out),
+           _lib.DT_F32 if dtype == torch.float32 else _DT16[dtype], N, H, W, h, w, m3, s3, _stream(), nbytes=src_bytes + out.numel() * out.element_size())
+    return out
+
+
 def ingest_input(frames, h: int, w: int, dtype: torch.dtype = torch.float32) -> torch.Tensor:
     """The one door through which the fast paths take frames: a float NCHW tensor (``frame_ingest``, unchanged) or 8-bit decoder output
-    (``arseg_amd.ingest.DecodedFrames``: its ``to_input`` runs ``frame_ingest8``) -> the conv engine's input at (h,w)."""
+    (``arseg_amd.ingest.DecodedFrames``: its ``to_input`` runs ``frame_ingest8`` / ``frame_ingest_yuv``) -> the conv engine's input at (h,w)."""
     if torch.is_tensor(frames):
         return frame_ingest(frames, h, w, dtype)
     to_input = getattr(frames, "to_input", None)

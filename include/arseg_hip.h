@@ -442,11 +442,37 @@ int arseg_frame_u8_to_nhwc4_fwd(const uint8_t *img_hwc, float *out, int N, int H
  * rounded once, at the store (to nearest even).
  * ARSEG_EINVAL: a null pointer (plane1 only with NV12), a non-positive size, a zero std, odd H or W with NV12, a pitch smaller than a
  * row, a negative image stride, an unknown src_format / out_dtype / colour (colour with NV12 only), `out` not 16-byte aligned. */
-enum arseg_src_format { ARSEG_SRC_RGB8 = 0, ARSEG_SRC_NV12 = 1 };
+enum arseg_src_format { ARSEG_SRC_RGB8 = 0, ARSEG_SRC_NV12 = 1, ARSEG_SRC_I420 = 2, ARSEG_SRC_P010 = 3, ARSEG_SRC_I010 = 4 };     /* 2..4: arseg_frame_ingest_yuv_fwd */
 enum arseg_colour { ARSEG_COLOUR_BT601_LIMITED = 0, ARSEG_COLOUR_BT601_FULL = 1, ARSEG_COLOUR_BT709_LIMITED = 2, ARSEG_COLOUR_BT709_FULL = 3 };
 int arseg_frame_ingest_fwd(const void *plane0, const void *plane1, int src_format, int64_t pitch0, int64_t pitch1, int64_t n_stride0,
                            int64_t n_stride1, int colour, void *out, int out_dtype, int N, int H, int W, int h, int w, const float *mean3,
                            const float *std3, arseg_stream_t stream);
+/* Planar 4:2:0 and 10-bit decoder frames -> the conv engine's input, the same pass as arseg_frame_ingest_fwd (csrc/ingest.hip).
+ *   src_format  ARSEG_SRC_I420: plane0 = Y uint8 [N][H][W], plane1 = Cb uint8 [N][H/2][W/2], plane2 = Cr uint8 [N][H/2][W/2]
+ *                               (what a software HEVC decoder hands over for a yuv420p stream)
+ *               ARSEG_SRC_P010: plane0 = Y uint16 [N][H][W], plane1 = (Cb, Cr) interleaved uint16 [N][H/2][W/2][2], plane2 / pitch2 /
+ *                               n_stride2 ignored; little-endian words, code = word >> 6 (the low 6 bits are ignored)
+ *               ARSEG_SRC_I010: planes as I420 with uint16 little-endian samples (yuv420p10le), code = word & 0x3ff (the high 6 bits
+ *                               are ignored)
+ *               ARSEG_SRC_RGB8 and ARSEG_SRC_NV12 are unknown to this entry point: they keep arseg_frame_ingest_fwd.
+ *   pitch0/1/2, n_stride0/1/2   bytes, per plane, as above; a row holds W (I420 Y), 2 W (16-bit Y, P010 chroma), W / 2 (I420 chroma) or
+ *               W (I010 chroma) bytes.  Rows may be padded; nothing past a row's last sample is read.  H and W even.  Pointer, pitch and
+ *               image stride of a 16-bit plane are even.
+ *   colour, out, out_dtype, mean3 / std3: as arseg_frame_ingest_fwd.
+ * Contract: steps (1) and (3) of arseg_frame_ingest_fwd unchanged, and so is the chroma siting (cx = x / 2, cy = y / 2 - 0.25, clamped to
+ * the plane, bilinear on the stored codes).  Step (2) gains the bit depth n = 8 (I420) or 10 (P010, I010): with C = the interpolated
+ * chroma code,
+ *       limited range:  Y8 = code_Y 2^-(n-8),          C8 - 128 = (C - 2^(n-1)) 2^-(n-8)          (10-bit: Y 64-940, C 64-960; exact in fp32)
+ *       full range (H.273):  Y8 = code_Y 255 / (2^n - 1),   C8 - 128 = (C - 2^(n-1)) 255 / (2^n - 1)   (the factor formed in double, rounded
+ *                                                                                                     to fp32 once; 1 for n = 8)
+ * then the matrix of `colour` on (Y8 - y0, C8b - 128, C8r - 128) as above, each component clipped to [0, 255], not rounded.  For equal
+ * sample values the three formats give the same fp32 bits.  BT.2020, 12-bit, 4:2:2 and 4:4:4 sources are not covered.
+ * ARSEG_EINVAL: a null pointer (plane2 with the planar formats only), a non-positive size, odd H or W, a pitch smaller than a row, a
+ * negative image stride, an odd pointer / pitch / image stride of a 16-bit plane, a zero std, an unknown src_format / out_dtype / colour,
+ * `out` not 16-byte aligned. */
+int arseg_frame_ingest_yuv_fwd(const void *plane0, const void *plane1, const void *plane2, int src_format, int64_t pitch0, int64_t pitch1,
+                               int64_t pitch2, int64_t n_stride0, int64_t n_stride1, int64_t n_stride2, int colour, void *out, int out_dtype,
+                               int N, int H, int W, int h, int w, const float *mean3, const float *std3, arseg_stream_t stream);
 
 /* mergeMotion (pre-process/generate_compressed_dataset_camvid.py:6-56): chains the codec's per-frame motion fields back to
  * the keyframe.  flows: int16 [n_frames+1][H][W][3] = (mv_x, mv_y quarter-pel, reference index), entries <= frame_start unused;

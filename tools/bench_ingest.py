@@ -9,6 +9,10 @@ Shapes: the 11 non-keyframes of a GOP at 512x1024 -> 256x512 and at 1024x2048 ->
   torch_then_f32 what a caller had to do before for the same uint8 RGB frames: torch ops to a normalised fp32 NCHW tensor
                  (permute, float, /255, -mean, /std), then ops.frame_ingest
   f32            ops.frame_ingest alone from a ready fp32 NCHW tensor
+--yuv: the planar 4:2:0 / 10-bit routes instead, same protocol, written to profiles/ingest_yuv.json:
+  i420 / p010 / i010   ops.frame_ingest_yuv from I420 / P010 / I010 planes   (one kernel)
+  nv12                 the NV12 route above, run again in the same process: the yardstick of that table
+and the GOP step from I420 and P010 frames next to NV12.
 GB/s = the bytes the route MUST move (its source once + its output once) over the time; beside the stream-copy figure of a bench.py --full
 run if one is on file (--peaks).  Then one bise_bf16-shaped GOP step (keyframe 1024x2048 + 11 non-keyframes at 0.5x) end to end from
 DecodedFrames (RGB8, NV12) and from fp32 frames.  One JSON line on stdout, the same written to --out."""
@@ -81,7 +85,33 @@ def shape_cost(N, H, W, h, w, repeats, window, dev, copy_gbps):
     return rows
 
 
-def gop_step(repeats, window, dev, H=1024, W=2048, gop=12):
+def shape_cost_yuv(N, H, W, h, w, repeats, window, dev, copy_gbps):
+    g = np.random.Generator(np.random.PCG64(1))
+    u8 = lambda *s: torch.from_numpy(g.integers(0, 256, s, dtype=np.uint8)).to(dev)
+    u16 = lambda shift, *s: torch.from_numpy(g.integers(0, 1024, s, dtype=np.uint16) << shift).to(dev)
+    D = ingest.DecodedFrames
+    src = {"nv12": D.nv12(u8(N, H, W), u8(N, H // 2, W // 2, 2), MEAN, STD),
+           "i420": D.i420(u8(N, H, W), u8(N, H // 2, W // 2), u8(N, H // 2, W // 2), MEAN, STD),
+           "p010": D.p010(u16(6, N, H, W), u16(6, N, H // 2, W // 2, 2), MEAN, STD),
+           "i010": D.i010(u16(0, N, H, W), u16(0, N, H // 2, W // 2), u16(0, N, H // 2, W // 2), MEAN, STD)}
+    rows = []
+    for name, dt in DT.items():
+        out_b = N * h * w * 16                                           # NHWC4 fp32 and NHWC8 16-bit are both 16 bytes per pixel
+        need = {k: N * H * W * 3 // 2 * (2 if k in ("p010", "i010") else 1) + out_b for k in src}
+        res = alternate({k: (lambda d=d: d.to_input(h, w, dt)) for k, d in src.items()}, repeats, window)
+        for k, r in res.items():
+            r["bytes_needed"] = need[k]
+            r["GBps_of_needed_bytes"] = need[k] / (r["ms_median"] * 1e-3) / 1e9
+            r["time_over_nv12"] = r["ms_median"] / res["nv12"]["ms_median"]
+            if copy_gbps:
+                r["share_of_stream_copy"] = r["GBps_of_needed_bytes"] / copy_gbps
+        rows.append({"frames": N, "source": [H, W], "output": [h, w], "dtype": name, "routes": res})
+        print(f"{N} x {H}x{W} -> {h}x{w} {name}: " + ", ".join(f"{k} {r['ms_median'] * 1e3:.1f} us ({r['ms_min'] * 1e3:.1f}-{r['ms_max'] * 1e3:.1f}; {r['GBps_of_needed_bytes']:.0f} GB/s)"
+                                                                 for k, r in res.items()), file=sys.stderr)
+    return rows
+
+
+def gop_step(repeats, window, dev, H=1024, W=2048, gop=12, yuv=False):
     hr, lr = BiSeNetV1(n_classes=19, backend="resnet18"), BiSeNetV1WithFuse(n_classes=19, backend="resnet18")
     synth.load_synth_weights(hr, 0)
     synth.load_synth_weights(lr, 1)
@@ -92,6 +122,10 @@ def gop_step(repeats, window, dev, H=1024, W=2048, gop=12):
     y, uv = ingest.rgb_to_nv12(u8)
     src = {"fp32_frames": torch.from_numpy(clip["frames"]).to(dev), "rgb8": ingest.DecodedFrames.rgb8(torch.from_numpy(u8).to(dev), MEAN, STD),
            "nv12": ingest.DecodedFrames.nv12(torch.from_numpy(y).to(dev), torch.from_numpy(uv).to(dev), MEAN, STD)}
+    if yuv:
+        del src["rgb8"]
+        src["i420"] = ingest.DecodedFrames.i420(*[torch.from_numpy(p).to(dev) for p in ingest.rgb_to_yuv420(u8, "i420")], MEAN, STD)
+        src["p010"] = ingest.DecodedFrames.p010(*[torch.from_numpy(p).to(dev) for p in ingest.rgb_to_yuv420(u8, "p010")], MEAN, STD)
 
     def step(f):
         _, ref = hr.forward_keyframe(f[0:1])
@@ -112,8 +146,10 @@ def main():
     ap.add_argument("--window", type=float, default=0.5)
     ap.add_argument("--only", choices=["ingest", "gop"], default=None)
     ap.add_argument("--peaks", default=os.path.join(root, "profiles", "r06_bise_bf16_bench.json"), help="a bench.py --full result holding the on-box stream-copy rate")
-    ap.add_argument("--out", default=os.path.join(root, "profiles", "ingest_formats.json"))
+    ap.add_argument("--yuv", action="store_true", help="the I420 / P010 / I010 routes beside NV12 -> profiles/ingest_yuv.json")
+    ap.add_argument("--out", default=None, help="default: profiles/ingest_formats.json, or profiles/ingest_yuv.json with --yuv")
     a = ap.parse_args()
+    a.out = a.out or os.path.join(root, "profiles", "ingest_yuv.json" if a.yuv else "ingest_formats.json")
     dev = torch.device("cuda:0")
     _lib.load()
     copy_gbps = None
@@ -134,9 +170,9 @@ def main():
         if a.only != "gop":
             res["ingest"] = []
             for (N, H, W, h, w) in ((11, 512, 1024, 256, 512), (11, 1024, 2048, 512, 1024), (1, 512, 1024, 512, 1024), (1, 1024, 2048, 1024, 2048)):
-                res["ingest"] += shape_cost(N, H, W, h, w, a.repeats, a.window, dev, copy_gbps)
+                res["ingest"] += (shape_cost_yuv if a.yuv else shape_cost)(N, H, W, h, w, a.repeats, a.window, dev, copy_gbps)
         if a.only != "ingest":
-            res["gop_step"] = gop_step(a.repeats, a.window, dev)
+            res["gop_step"] = gop_step(a.repeats, a.window, dev, yuv=a.yuv)
     text = json.dumps(res)
     with open(a.out, "w") as f:
         f.write(text + "\n")
