@@ -119,6 +119,10 @@ PROTOTYPES = {
     "arseg_frame_ingest_yuv_fwd": (c_int, [_P, _P, _P, c_int] + [c_int64] * 6 + [c_int, _P, c_int] + [c_int] * 5 + [POINTER(c_float), POINTER(c_float), _STREAM]),
     "arseg_merge_motion_workspace_bytes": (c_size_t, [c_int, c_int, c_int]),
     "arseg_merge_motion_fwd": (c_int, [_P, _P, _P, c_size_t, c_int, c_int, c_int, c_int, _STREAM]),
+    "arseg_mv_records_workspace_bytes": (c_size_t, [c_int, c_int]),
+    "arseg_mv_records_reset": (c_int, [_P, _P, c_size_t, c_int, c_int, _STREAM]),
+    "arseg_mv_records_step_fwd": (c_int, [_P, c_int, _P, c_int, c_int, _P, c_size_t, c_int, c_int, c_int, _STREAM]),
+    "arseg_mv_records_rasterize_fwd": (c_int, [_P, c_int, _P, _P, c_size_t, c_int, c_int, _STREAM]),
     "arseg_nchw_to_nhwc_fwd": (c_int, [_P, _P, c_int, c_int, c_int, c_int, _STREAM]),
     "arseg_nhwc_to_nchw_fwd": (c_int, [_P, c_int, _P, c_int, c_int, c_int, _STREAM]),
     "arseg_argmax_confusion_fwd": (c_int, [_P, _P, _P, _P] + [c_int] * 8 + [_STREAM]),

@@ -86,6 +86,11 @@ __device__ __forceinline__ void arseg_split_f16_pair(float a, float b, unsigned 
         : "=&v"(h), "=&v"(l0), "=&v"(l1) : "v"(a), "v"(b));
     l = __builtin_bit_cast(unsigned, __builtin_amdgcn_cvt_pkrtz(l0, l1));
 }
+// np.round(v / 4) for integer v: the quarter-pel -> pixel step of mergeMotion (layers.hip) and of the record chain (mv_records.hip)
+__device__ __forceinline__ int round_half_even_div4(int v) {
+    const int b = v >> 2, r = v & 3;                                  // v = 4b + r, floor division
+    return r < 2 ? b : (r > 2 ? b + 1 : b + (b & 1));                 // .5 -> the even neighbour
+}
 #endif
 
 // Bilinear source coordinate exactly as ATen computes it for fp32 tensors

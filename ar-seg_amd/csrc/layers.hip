@@ -759,10 +759,7 @@ __global__ __launch_bounds__(256) void frame_u8_to_nhwc4_kernel(const uint8_t *_
 // (pre-process/generate_compressed_dataset_camvid.py:6-56).  Frames are sequential (a pixel links to the parent of its
 // target in an earlier frame), pixels independent: one launch per frame, an integer gather from the earlier frames' links.
 // dp[f][y][x] = int4 (x, y, frame, -) of the linked position, frame == -1: no link yet (the keyframe).
-__device__ __forceinline__ int round_half_even_div4(int v) {        // np.round(v / 4) for integer v
-    const int b = v >> 2, r = v & 3;                                  // v = 4b + r, floor division
-    return r < 2 ? b : (r > 2 ? b + 1 : b + (b & 1));                 // .5 -> the even neighbour
-}
+// (round_half_even_div4: arseg_common.h, shared with csrc/mv_records.hip)
 __global__ __launch_bounds__(256) void merge_motion_step_kernel(const int16_t *__restrict__ flow, int4 *__restrict__ dp, int f1, int H, int W) {
     const int hw = H * W;
     for (int pix = blockIdx.x * blockDim.x + threadIdx.x; pix < hw; pix += gridDim.x * blockDim.x) {

@@ -1,0 +1,169 @@
+// Decoder motion-vector block records -> mv_q, chained to the keyframe frame by frame (contract: include/arseg_hip.h,
+// arseg_mv_records_*).  A decoder exports motion as prediction-block records (position, size, vector, reference index); the fast
+// paths read a dense int16 [H,W,2] field accumulated back to the keyframe.  One P-frame is two kernels:
+//   scatter : a wave per record, its lanes over the record's clipped pixels, atomicMax of the record index into an int32 index map
+//             (-1 = uncovered) -- the highest index wins wherever records overlap, in any arrival order
+//   compose : four pixels per lane; index -> 16-byte record (neighbours share it through L1 / L2) -> intra rule, rounding, clamp ->
+//             4 bytes gathered from merged[f2] -> 16-byte store into merged[f]; the index map is set back to -1 on the way, so the
+//             next frame needs no fill pass
+// The merged tensor is the chain state: within H, W <= 8192 every accumulated value fits int16, so the link of a pixel is
+// out[f][y,x] = 4 (k2 - x, j2 - y) + (f2 > 0 ? out[f2][j2,k2] : 0) and mergeMotion's int4 link table (layers.hip) is not needed.
+#include "arseg_device.h"
+
+constexpr int MVR_MAX_DIM = 8192;      // 4 * 8191 = 32764: the largest accumulated displacement still fits int16
+constexpr int MVR_BAND = 256;          // frame rows per scatter band (blockIdx.y): bounds the pixels one wave covers of a frame-sized record
+
+// record = int16 x, y, w, h, mvx, mvy, ref, reserved, read as one int4 (little endian)
+__device__ __forceinline__ int rec_lo(int v) { return (int)(short)v; }
+__device__ __forceinline__ int rec_hi(int v) { return v >> 16; }
+
+__global__ __launch_bounds__(256) void mv_records_scatter_kernel(const int4 *__restrict__ rec, int n, int *__restrict__ idx, int H, int W) {
+    const int lane = threadIdx.x & 63;
+    const int wave = blockIdx.x * 4 + __builtin_amdgcn_readfirstlane((int)(threadIdx.x >> 6)), n_waves = gridDim.x * 4;
+    const int band0 = blockIdx.y * MVR_BAND, band1 = min(band0 + MVR_BAND, H);
+    for (int r = wave; r < n; r += n_waves) {
+        const int4 q = rec[r];                                        // wave uniform
+        const int x = rec_lo(q.x), y = rec_hi(q.x), w = rec_lo(q.y), h = rec_hi(q.y);
+        if (w <= 0 || h <= 0) continue;                               // padding of a fixed-capacity buffer
+        const int x0 = max(x, 0), x1 = min(x + w, W), y0 = max(y, band0), y1 = min(y + h, band1);
+        if (x0 >= x1 || y0 >= y1) continue;
+        const int cw = x1 - x0;
+        const int sh = cw > 32 ? 6 : (cw <= 1 ? 0 : 32 - __clz(cw - 1));      // lanes along x: the power of two that covers min(cw, 64)
+        const int lx = lane & ((1 << sh) - 1), ly = lane >> sh, lxn = 1 << sh, lyn = 64 >> sh;
+        for (int yy = y0 + ly; yy < y1; yy += lyn)
+            for (int xx = x0 + lx; xx < x1; xx += lxn) atomicMax(idx + yy * W + xx, r);      // 0 <= yy < H, 0 <= xx < W
+    }
+}
+
+// one pixel of frame f: packed (dx, dy) int16 pair.  id outside [0, n): no record (intra).
+__device__ __forceinline__ unsigned mvr_compose(const int4 *__restrict__ rec, int n, int id, const unsigned *merged, int f, int x, int y, int H, int W,
+                                                int max_ref) {
+    int mx = 0, my = 0, ref = 0;                                      // intra: zero motion, previous frame
+    if (id >= 0 && id < n) {
+        const int4 q = rec[id];
+        const int r = rec_lo(q.w);
+        if (r >= 0 && r < max_ref) { mx = rec_lo(q.z); my = rec_hi(q.z); ref = r; }
+    }
+    const int k2 = min(max(x + round_half_even_div4(mx), 0), W - 1), j2 = min(max(y + round_half_even_div4(my), 0), H - 1);
+    const int f2 = max(0, f - ref - 1);
+    int dx = 4 * (k2 - x), dy = 4 * (j2 - y);
+    if (f2 > 0) {                                                     // the target's own link, from the output of frame f2 < f
+        const unsigned p = merged[((size_t)f2 * H + j2) * W + k2];
+        dx += rec_lo((int)p); dy += rec_hi((int)p);
+    }
+    return ((unsigned)dx & 0xffffu) | ((unsigned)dy << 16);
+}
+
+// merged / out: the same tensor (frames < f are read, frame f is written): no __restrict__
+template <bool VEC>
+__global__ __launch_bounds__(256) void mv_records_compose_kernel(const int4 *__restrict__ rec, int n, int *__restrict__ idx, const unsigned *merged, unsigned *out,
+                                                                 int f, int H, int W, int max_ref) {
+    const int hw = H * W;
+    if constexpr (VEC) {                                              // hw % 4 == 0, 16-byte aligned frames
+        const int n4 = hw >> 2;
+        for (int t = blockIdx.x * blockDim.x + threadIdx.x; t < n4; t += gridDim.x * blockDim.x) {
+            const int4 id = reinterpret_cast<const int4 *>(idx)[t];
+            int y = (t * 4) / W, x = t * 4 - y * W;
+            const int ids[4] = {id.x, id.y, id.z, id.w};
+            u32x4 o;
+#pragma unroll
+            for (int k = 0; k < 4; ++k) {
+                o[k] = mvr_compose(rec, n, ids[k], merged, f, x, y, H, W, max_ref);
+                if (++x == W) { x = 0; ++y; }
+            }
+            reinterpret_cast<u32x4 *>(out)[t] = o;
+            reinterpret_cast<int4 *>(idx)[t] = make_int4(-1, -1, -1, -1);
+        }
+    } else {
+        for (int pix = blockIdx.x * blockDim.x + threadIdx.x; pix < hw; pix += gridDim.x * blockDim.x) {
+            const int y = pix / W, x = pix - y * W;
+            out[pix] = mvr_compose(rec, n, idx[pix], merged, f, x, y, H, W, max_ref);
+            idx[pix] = -1;
+        }
+    }
+}
+
+// the dense field of one frame as the reference's decoder dumps it: (mvx, mvy, ref) of the winning record, (0, 0, -1) where there is none
+__global__ __launch_bounds__(256) void mv_records_dense_kernel(const int4 *__restrict__ rec, int n, int *__restrict__ idx, int16_t *__restrict__ dense, int hw) {
+    for (int pix = blockIdx.x * blockDim.x + threadIdx.x; pix < hw; pix += gridDim.x * blockDim.x) {
+        const int id = idx[pix];
+        int mx = 0, my = 0, ref = -1;
+        if (id >= 0 && id < n) {
+            const int4 q = rec[id];
+            mx = rec_lo(q.z); my = rec_hi(q.z); ref = rec_lo(q.w);
+        }
+        dense[(size_t)pix * 3] = (int16_t)mx; dense[(size_t)pix * 3 + 1] = (int16_t)my; dense[(size_t)pix * 3 + 2] = (int16_t)ref;
+        idx[pix] = -1;
+    }
+}
+
+// a[i] = b[i] = -1 (all bits set) for i < n; b may be null
+__global__ __launch_bounds__(256) void mv_records_fill_kernel(unsigned *__restrict__ a, unsigned *__restrict__ b, int n) {
+    for (int i = blockIdx.x * blockDim.x + threadIdx.x; i < n; i += gridDim.x * blockDim.x) {
+        a[i] = 0xffffffffu;
+        if (b != nullptr) b[i] = 0xffffffffu;
+    }
+}
+
+static int mvr_check_frame(const void *records, int n_records, const void *workspace, size_t workspace_bytes, int H, int W) {
+    if (n_records < 0 || (n_records > 0 && records == nullptr) || workspace == nullptr) return ARSEG_EINVAL;
+    if (H <= 0 || W <= 0 || H > MVR_MAX_DIM || W > MVR_MAX_DIM) return ARSEG_EINVAL;
+    if (workspace_bytes < arseg_mv_records_workspace_bytes(H, W)) return ARSEG_EWORKSPACE;
+    if (!ARSEG_ALIGNED16(workspace) || !ARSEG_ALIGNED16(records)) return ARSEG_EINVAL;
+    return ARSEG_OK;
+}
+
+static void mvr_scatter(const int16_t *records, int n_records, int *idx, int H, int W, hipStream_t st) {
+    if (n_records == 0) return;
+    const int gx = (int)(((long long)n_records + 3) / 4 > 65536 ? 65536 : ((long long)n_records + 3) / 4);
+    hipLaunchKernelGGL(mv_records_scatter_kernel, dim3(gx, arseg_cdiv(H, MVR_BAND)), dim3(256), 0, st, reinterpret_cast<const int4 *>(records), n_records, idx, H, W);
+}
+
+extern "C" size_t arseg_mv_records_workspace_bytes(int H, int W) {
+    return H <= 0 || W <= 0 || H > MVR_MAX_DIM || W > MVR_MAX_DIM ? 0 : (size_t)H * W * sizeof(int32_t);
+}
+
+extern "C" int arseg_mv_records_reset(int16_t *merged, void *workspace, size_t workspace_bytes, int H, int W, arseg_stream_t stream) {
+    ARSEG_CHECK_PTR(merged);
+    const int bad = mvr_check_frame(nullptr, 0, workspace, workspace_bytes, H, W);
+    if (bad) return bad;
+    if (reinterpret_cast<uintptr_t>(merged) & 3u) return ARSEG_EINVAL;
+    hipStream_t st = arseg_stream(stream);
+    hipLaunchKernelGGL(mv_records_fill_kernel, dim3(arseg_grid_for((long long)H * W)), dim3(256), 0, st, reinterpret_cast<unsigned *>(workspace),
+                       reinterpret_cast<unsigned *>(merged), H * W);
+    return arseg_launch_status();
+}
+
+extern "C" int arseg_mv_records_step_fwd(const int16_t *records, int n_records, int16_t *merged, int f, int gop, void *workspace, size_t workspace_bytes,
+                                         int H, int W, int max_ref, arseg_stream_t stream) {
+    ARSEG_CHECK_PTR(merged);
+    const int bad = mvr_check_frame(records, n_records, workspace, workspace_bytes, H, W);
+    if (bad) return bad;
+    if (max_ref < 1 || max_ref > 16 || f < 1 || f >= gop || (reinterpret_cast<uintptr_t>(merged) & 3u)) return ARSEG_EINVAL;
+    hipStream_t st = arseg_stream(stream);
+    int *idx = reinterpret_cast<int *>(workspace);
+    const int hw = H * W;
+    const unsigned *m = reinterpret_cast<const unsigned *>(merged);
+    unsigned *out = reinterpret_cast<unsigned *>(merged) + (size_t)f * hw;
+    mvr_scatter(records, n_records, idx, H, W, st);
+    const int4 *rec = reinterpret_cast<const int4 *>(records);
+    if (hw % 4 == 0 && ARSEG_ALIGNED16(merged))
+        hipLaunchKernelGGL(mv_records_compose_kernel<true>, dim3(arseg_grid_for(hw / 4)), dim3(256), 0, st, rec, n_records, idx, m, out, f, H, W, max_ref);
+    else
+        hipLaunchKernelGGL(mv_records_compose_kernel<false>, dim3(arseg_grid_for(hw)), dim3(256), 0, st, rec, n_records, idx, m, out, f, H, W, max_ref);
+    return arseg_launch_status();
+}
+
+extern "C" int arseg_mv_records_rasterize_fwd(const int16_t *records, int n_records, int16_t *dense_out, void *workspace, size_t workspace_bytes, int H, int W,
+                                              arseg_stream_t stream) {
+    ARSEG_CHECK_PTR(dense_out);
+    const int bad = mvr_check_frame(records, n_records, workspace, workspace_bytes, H, W);
+    if (bad) return bad;
+    hipStream_t st = arseg_stream(stream);
+    int *idx = reinterpret_cast<int *>(workspace);
+    const int hw = H * W;
+    hipLaunchKernelGGL(mv_records_fill_kernel, dim3(arseg_grid_for(hw)), dim3(256), 0, st, reinterpret_cast<unsigned *>(idx), (unsigned *)nullptr, hw);
+    mvr_scatter(records, n_records, idx, H, W, st);
+    hipLaunchKernelGGL(mv_records_dense_kernel, dim3(arseg_grid_for(hw)), dim3(256), 0, st, reinterpret_cast<const int4 *>(records), n_records, idx, dense_out, hw);
+    return arseg_launch_status();
+}

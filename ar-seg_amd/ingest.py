@@ -8,6 +8,10 @@
 * decoder output as the fast paths take it: ``DecodedFrames`` (uint8 RGB, NV12 or I420 planes, 10-bit P010 or I010 planes + normalisation +
   colour matrix); every fast path that accepts float NCHW frames accepts one of these instead and ingests it with ``ops.frame_ingest8`` /
   ``ops.frame_ingest_yuv`` (csrc/ingest.hip).
+* decoder motion as a decoder holds it: block records ``int16 [n,8]`` per P-frame (x, y, w, h, mvx, mvy, ref, reserved; the contract is in
+  include/arseg_hip.h, arseg_mv_records_*).  ``MotionChain`` rasterises and chains them to the keyframe frame by frame on the GPU
+  (csrc/mv_records.hip) into the ``mv_qs`` tensor the fast paths read; ``mv_to_records`` / ``records_to_dense`` convert the reference's
+  dense per-frame dumps to records and back on the host.
 """
 from __future__ import annotations
 
@@ -272,3 +276,127 @@ class DecodedFrames(object):
             return ops.frame_ingest_yuv(self.planes, self.src_format, h, w, self.mean, self.std, dtype, self.colour)
         return ops.frame_ingest8(self.planes[0], self.planes[1] if self.src_format == _lib.SRC_NV12 else None, self.src_format, h, w,
                                  self.mean, self.std, dtype, self.colour)
+
+
+# ----------------------------------------------------------------------------------------------
+# decoder motion: block records -> mv_q
+# ----------------------------------------------------------------------------------------------
+RECORD_FIELDS = ("x", "y", "w", "h", "mvx", "mvy", "ref", "reserved")          # one record: eight int16, 16 bytes
+
+
+def mv_to_records(dense) -> np.ndarray:
+    """A dense per-frame motion field int16 [H,W,3] = (mvx, mvy, ref), as the reference's decoder dumps it, -> block records int16 [n,8]:
+    greedily the largest aligned squares (64, 32, ... 1 pixels, inside the frame) on which all three channels are constant, listed in raster
+    order of their top-left corners.  The squares do not overlap and cover the frame, so ``records_to_dense`` gives ``dense`` back.  Host,
+    numpy; for tests, tools and callers who hold the reference's dumps."""
+    d = np.asarray(dense)
+    if d.dtype != np.int16 or d.ndim != 3 or d.shape[2] != 3:
+        raise ValueError(f"mv_to_records expects int16 [H,W,3], got {d.dtype} {d.shape}")
+    H, W, _ = d.shape
+    covered = np.zeros((H, W), dtype=bool)
+    found = []
+    s = 64
+    while s >= 1:
+        hb, wb = H // s, W // s
+        if hb and wb:
+            blk = d[:hb * s, :wb * s].reshape(hb, s, wb, s, 3)
+            const = (blk.max(axis=(1, 3)) == blk.min(axis=(1, 3))).all(axis=-1)
+            const &= ~covered[:hb * s, :wb * s].reshape(hb, s, wb, s).any(axis=(1, 3))
+            by, bx = np.nonzero(const)
+            if by.size:
+                rec = np.zeros((by.size, 8), dtype=np.int16)
+                rec[:, 0], rec[:, 1], rec[:, 2], rec[:, 3] = bx * s, by * s, s, s
+                rec[:, 4:7] = d[by * s, bx * s]
+                found.append(rec)
+                covered[:hb * s, :wb * s] |= np.repeat(np.repeat(const, s, axis=0), s, axis=1)
+        s //= 2
+    rec = np.concatenate(found) if found else np.zeros((0, 8), dtype=np.int16)
+    return np.ascontiguousarray(rec[np.lexsort((rec[:, 0], rec[:, 1]))])
+
+
+def records_to_dense(records, H: int, W: int) -> np.ndarray:
+    """Block records int16 [n,8] -> the dense field int16 [H,W,3] they rasterise to, by the rules of include/arseg_hip.h: records in index
+    order, each assigned to its rectangle clipped to the frame (so the highest index wins an overlap), w <= 0 or h <= 0 covers nothing,
+    uncovered pixels read (0, 0, -1).  The host restatement of ``ops.mv_records_rasterize``, for callers without a GPU at hand."""
+    r = np.asarray(records)
+    if r.dtype != np.int16 or r.ndim != 2 or r.shape[1] != 8:
+        raise ValueError(f"records_to_dense expects int16 [n,8], got {r.dtype} {r.shape}")
+    out = np.zeros((H, W, 3), dtype=np.int16)
+    out[..., 2] = -1
+    for x, y, w, h, mvx, mvy, ref, _ in r.astype(np.int64):
+        if w <= 0 or h <= 0:
+            continue
+        x0, x1, y0, y1 = max(x, 0), min(x + w, W), max(y, 0), min(y + h, H)
+        if x0 < x1 and y0 < y1:
+            out[y0:y1, x0:x1] = (mvx, mvy, ref)
+    return out
+
+
+def pad_records(records, capacity: int) -> np.ndarray:
+    """int16 [n,8] -> int16 [capacity,8], the tail filled with zero records (w = h = 0: they cover nothing) -- the fixed-size buffer a
+    captured graph reads."""
+    r = np.asarray(records, dtype=np.int16)
+    if r.ndim != 2 or r.shape[1] != 8 or r.shape[0] > capacity:
+        raise ValueError(f"pad_records: {r.shape} does not fit a buffer of {capacity} records")
+    out = np.zeros((capacity, 8), dtype=np.int16)
+    out[:r.shape[0]] = r
+    return out
+
+
+class MotionChain(object):
+    """The motion half of a decoder's output on the GPU: block records of one P-frame at a time -> ``mv_q``, the int16 quarter-pel field
+    accumulated back to the keyframe (what mergeMotion writes into the datasets' .bin files).  Owns ``merged`` int16 [gop,H,W,2] and the
+    int32 index map, both allocated once; ``push`` is two kernel launches and neither synchronises nor allocates, so a closure over a
+    MotionChain and static (padded) record buffers can be captured in a HIP graph (``executor.GopGraph``).
+
+        chain = MotionChain(H, W, gop=12)
+        for each GOP:   chain.reset();  for each P-frame:  mv_q = chain.push(records)          # [H,W,2], a view of chain.merged[f]
+        chain.mv_q()[1:]                       # [f,H,W,2]: the ``mv_qs`` of alter_res_batch_fast / alter_res_batch_pred / GopRunner
+
+    H, W <= 8192; max_ref as mergeMotion's constant 3 (reference indices >= max_ref are intra), 1..16."""
+
+    def __init__(self, H: int, W: int, gop: int = 12, max_ref: int = 3, device="cuda"):
+        H, W, gop, max_ref = int(H), int(W), int(gop), int(max_ref)
+        if not (1 <= H <= 8192 and 1 <= W <= 8192) or gop < 2 or not 1 <= max_ref <= 16:
+            raise _lib.ArsegError(f"MotionChain: H, W in 1..8192, gop >= 2, max_ref in 1..16; got {H}x{W}, gop {gop}, max_ref {max_ref}")
+        self.H, self.W, self.gop, self.max_ref = H, W, gop, max_ref
+        self.device = torch.device(device)
+        if self.device.type != "cuda":
+            raise _lib.ArsegError("MotionChain runs on the GPU only; there is no CPU fallback (records_to_dense is the host restatement)")
+        self.merged = torch.empty((gop, H, W, 2), dtype=torch.int16, device=self.device)
+        self.index_map = torch.empty(H * W, dtype=torch.int32, device=self.device)
+        self.f = 0
+        self.reset()
+
+    def reset(self) -> None:
+        """Starts a GOP: frame 0 of ``merged`` = -1 (as ``ops.merge_motion`` leaves it), index map clean, no frame pushed."""
+        ops.mv_records_reset(self.merged, self.index_map)
+        self.f = 0
+
+    def _records(self, records) -> torch.Tensor:
+        if not torch.is_tensor(records):                      # host records: uploaded here (allocates; a graph wants device buffers)
+            r = np.ascontiguousarray(records)
+            if r.dtype != np.int16 or r.ndim != 2 or r.shape[1] != 8:
+                raise _lib.ArsegError(f"MotionChain: records must be int16 [n,8], got {r.dtype} {r.shape}")
+            records = torch.from_numpy(r).to(self.device)
+        return records
+
+    def push(self, records) -> torch.Tensor:
+        """The next P-frame's records (int16 [n,8] on the chain's device; n is the buffer's capacity, zero records are padding) -> its
+        mv_q int16 [H,W,2], the view ``merged[f]``.  Raises once gop - 1 frames have been pushed."""
+        if self.f >= self.gop - 1:
+            raise _lib.ArsegError(f"MotionChain: the GOP holds {self.gop - 1} P-frames and all were pushed; reset() starts the next one")
+        out = ops.mv_records_step(self._records(records), self.merged, self.f + 1, self.index_map, self.max_ref)
+        self.f += 1
+        return out
+
+    def push_gop(self, list_of_records) -> torch.Tensor:
+        """reset() + one push per entry; returns ``mv_q()``."""
+        self.reset()
+        for r in list_of_records:
+            self.push(r)
+        return self.mv_q()
+
+    def mv_q(self) -> torch.Tensor:
+        """int16 [f+1,H,W,2], a view: frame 0 = -1 (the keyframe has no motion field), frames 1..f as pushed."""
+        return self.merged[:self.f + 1]

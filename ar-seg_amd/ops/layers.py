@@ -454,6 +454,59 @@ def merge_motion(flows: torch.Tensor, frame_start: int = 0) -> torch.Tensor:
     return out
 
 
+def _mv_records(records: torch.Tensor, what: str) -> int:
+    """Checks a record buffer (int16 [n,8], contiguous, on the GPU; include/arseg_hip.h, arseg_mv_records_*) and returns its capacity n."""
+    if not torch.is_tensor(records) or records.dtype != torch.int16 or not records.is_cuda or records.dim() != 2 or records.shape[1] != 8 \
+            or not records.is_contiguous():
+        raise _lib.ArsegError(f"{what} expects records as a contiguous CUDA int16 tensor [n,8] (x, y, w, h, mvx, mvy, ref, reserved)")
+    return int(records.shape[0])
+
+
+def _mv_chain_state(merged: torch.Tensor, index_map: torch.Tensor, what: str):
+    if not torch.is_tensor(merged) or merged.dtype != torch.int16 or not merged.is_cuda or merged.dim() != 4 or merged.shape[-1] != 2 \
+            or not merged.is_contiguous():
+        raise _lib.ArsegError(f"{what} expects merged as a contiguous CUDA int16 tensor [gop,H,W,2]")
+    gop, H, W, _ = merged.shape
+    if not torch.is_tensor(index_map) or index_map.dtype != torch.int32 or index_map.device != merged.device or not index_map.is_contiguous() \
+            or index_map.numel() < H * W:
+        raise _lib.ArsegError(f"{what} expects the index map as a contiguous int32 tensor of at least H*W = {H * W} elements on merged's device")
+    return gop, H, W
+
+
+def mv_records_reset(merged: torch.Tensor, index_map: torch.Tensor) -> None:
+    """Starts a GOP of the record chain: index map = -1, merged[0] = -1 (what merge_motion leaves in frame 0).  merged int16 [gop,H,W,2],
+    index_map int32 [H*W] (or [H,W]), both caller-owned on one GPU."""
+    _, H, W = _mv_chain_state(merged, index_map, "mv_records_reset")
+    launch("mv_records_reset", _lib.load().arseg_mv_records_reset, _ptr(merged), _ptr(index_map), index_map.numel() * 4, H, W, _stream())
+
+
+def mv_records_step(records: torch.Tensor, merged: torch.Tensor, f: int, index_map: torch.Tensor, max_ref: int = 3) -> torch.Tensor:
+    """One P-frame of the record chain: rasterises the frame's block records (highest index wins) and chains them to the keyframe through
+    merged[f2], f2 < f; writes and returns the view merged[f] (int16 [H,W,2] quarter-pel, the mv_q of frame f).  Two kernels, no
+    synchronisation, no allocation; frames go in order 1, 2, ... after mv_records_reset."""
+    n = _mv_records(records, "mv_records_step")
+    gop, H, W = _mv_chain_state(merged, index_map, "mv_records_step")
+    if records.device != merged.device:
+        raise _lib.ArsegError(f"mv_records_step: records are on {records.device}, merged on {merged.device}")
+    launch("mv_records_step", _lib.load().arseg_mv_records_step_fwd, _ptr(records), n, _ptr(merged), int(f), gop, _ptr(index_map), index_map.numel() * 4,
+           H, W, int(max_ref), _stream())
+    return merged[f]
+
+
+def mv_records_rasterize(records: torch.Tensor, H: int, W: int) -> torch.Tensor:
+    """Block records int16 [n,8] -> the dense field int16 [H,W,3] = (mvx, mvy, ref) the reference's decoder dumps per frame ((0, 0, -1)
+    where no record covers a pixel): the rasterisation of mv_records_step alone."""
+    n = _mv_records(records, "mv_records_rasterize")
+    lib = _lib.load()
+    nbytes = lib.arseg_mv_records_workspace_bytes(int(H), int(W))
+    if nbytes == 0:
+        raise _lib.ArsegError(f"mv_records_rasterize: H and W must be in 1..8192, got {H}x{W}")
+    ws = workspace(nbytes, records.device)
+    out = torch.empty((H, W, 3), dtype=torch.int16, device=records.device)
+    launch("mv_records_rasterize", lib.arseg_mv_records_rasterize_fwd, _ptr(records), n, _ptr(out), _ptr(ws), nbytes, int(H), int(W), _stream())
+    return out
+
+
 def argmax_confusion(logits: torch.Tensor, label: Optional[torch.Tensor], H: int, W: int, hist: Optional[torch.Tensor] = None,
                      ignore_label: int = 255, want_pred: bool = True, align_corners: bool = True):
     """Evaluator tail (evaluation.py:201-209): returns (pred int32 [N,H,W] or None, hist int64 [n_cls,n_cls] or None).

@@ -193,3 +193,12 @@ def make_mv_chain(seed: int, H: int, W: int, n_frames: int) -> np.ndarray:
         blk = np.concatenate([mv, ref[..., None]], axis=-1).astype(np.int16)
         out[f] = np.repeat(np.repeat(blk, bs, axis=0), bs, axis=1)[:H, :W]
     return out
+
+
+def make_record_chain(seed: int, H: int, W: int, n_frames: int):
+    """The fields of ``make_mv_chain(seed, H, W, n_frames)`` as a decoder would export them: a list of n_frames block-record arrays
+    int16 [n,8] (frames 1..n_frames; ingest.mv_to_records)."""
+    from .ingest import mv_to_records
+
+    flows = make_mv_chain(seed, H, W, n_frames)
+    return [mv_to_records(flows[f]) for f in range(1, n_frames + 1)]

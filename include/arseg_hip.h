@@ -481,6 +481,53 @@ int arseg_frame_ingest_yuv_fwd(const void *plane0, const void *plane1, const voi
 size_t arseg_merge_motion_workspace_bytes(int n_frames, int H, int W);
 int arseg_merge_motion_fwd(const int16_t *flows, int16_t *out, void *workspace, size_t workspace_bytes, int n_frames, int frame_start,
                            int H, int W, arseg_stream_t stream);
+
+/* ---------------------------------------------------------------------------------------------
+ * Decoder motion-vector block records -> mv_q, chained to the keyframe frame by frame (csrc/mv_records.hip).
+ * The motion half of a decoder's output as a decoder holds it (libde265's prediction-unit table, FFmpeg's motion-vector side data): a
+ * list of block records per P-frame instead of mergeMotion's dense per-frame dumps, consumed one frame at a time.
+ *   record      16 bytes, 16-byte aligned, eight int16:  x, y, w, h, mvx, mvy, ref, reserved
+ *                 x, y      top-left luma pixel of the block
+ *                 w, h      its size in pixels
+ *                 mvx, mvy  quarter-pel displacement from the block to its reference position, mergeMotion's sign: k2 = k1 + round(mvx / 4)
+ *                 ref       reference index as mergeMotion reads channel 2: 0 = the previous frame, r = r + 1 frames back;
+ *                           ref < 0 or ref >= max_ref = intra
+ *                 reserved  ignored, whatever it holds
+ *   records     int16 [n_records][8] on the device; n_records is a host integer, the CAPACITY of the buffer (may be 0, then records may
+ *               be NULL)
+ * Rasterisation (one frame's records -> one dense field):
+ *   - a record covers the integer rectangle [x, x + w) x [y, y + h) clipped to the frame; any position and size, on or off the frame
+ *   - w <= 0 or h <= 0 covers nothing: a fixed-capacity buffer padded with zero records is valid, and a HIP graph captured over such a
+ *     buffer can be replayed on refilled contents
+ *   - where records overlap the HIGHEST record index wins (deterministic: an atomic maximum of the index, not the arrival order)
+ *   - a pixel no record covers reads (0, 0, -1): intra
+ * Chaining = mergeMotion with frame_start = 0 (pre-process/generate_compressed_dataset_camvid.py:6-56), per pixel (x, y) of frame f >= 1:
+ *       intra -> (mvx, mvy, ref) = (0, 0, 0)                                    (:20-22, with max_ref in place of the constant 3)
+ *       k2 = clamp(x + round(mvx / 4), 0, W - 1),  j2 = clamp(y + round(mvy / 4), 0, H - 1)      round = np.round: half to even (:26-34)
+ *       f2 = max(0, f - ref - 1)                                                                                               (:28)
+ *       merged[f][y][x] = 4 (k2 - x, j2 - y) + (f2 > 0 ? merged[f2][j2][k2] : (0, 0))       (a pixel links to its target's link, :37-54)
+ *   H, W <= 8192: every accumulated value is then at most 4 * 8191 in magnitude and fits int16 without wrapping, which is what lets the
+ *   merged tensor itself be the chain state (mergeMotion's per-pixel link table, 16 bytes per pixel and frame, is not needed).
+ *   merged: int16 [gop][H][W][2], caller-owned, 4-byte aligned; frames 1 .. f of it are the mv_q the warp entry points above take.
+ * Entry points (enqueue only: no host synchronisation, no allocation):
+ *   arseg_mv_records_workspace_bytes  one int32 index map: 4 H W bytes (0 for a size outside 1 .. 8192)
+ *   arseg_mv_records_reset            starts a GOP: index map = -1, merged[0] = -1 (what arseg_merge_motion_fwd leaves in frame 0, so the
+ *                                     whole tensor compares bit for bit)
+ *   arseg_mv_records_step_fwd         one P-frame f in [1, gop): reads merged[f2] for f2 < f, writes merged[f]; leaves the index map at -1.
+ *                                     Frames must be pushed in order 1, 2, ... after a reset.  max_ref in 1 .. 16 (the reference's constant: 3)
+ *   arseg_mv_records_rasterize_fwd    the dense field alone, dense_out int16 [H][W][3] = (mvx, mvy, ref) of the winning record as stored
+ *                                     (no intra rule), for cross-checks and for writing the reference's dumps; the workspace needs no
+ *                                     reset before it and is left at -1
+ * workspace: 16-byte aligned, >= arseg_mv_records_workspace_bytes(H, W) bytes (else ARSEG_EWORKSPACE).
+ * ARSEG_EINVAL: a null pointer, n_records < 0, H or W outside 1 .. 8192, max_ref outside 1 .. 16, f outside [1, gop), records or workspace
+ * not 16-byte aligned, merged not 4-byte aligned.  B-frames (two records per block) are not covered: mergeMotion has no rule for them.
+ * ------------------------------------------------------------------------------------------- */
+size_t arseg_mv_records_workspace_bytes(int H, int W);
+int arseg_mv_records_reset(int16_t *merged, void *workspace, size_t workspace_bytes, int H, int W, arseg_stream_t stream);
+int arseg_mv_records_step_fwd(const int16_t *records, int n_records, int16_t *merged, int f, int gop, void *workspace, size_t workspace_bytes,
+                              int H, int W, int max_ref, arseg_stream_t stream);
+int arseg_mv_records_rasterize_fwd(const int16_t *records, int n_records, int16_t *dense_out, void *workspace, size_t workspace_bytes, int H,
+                                   int W, arseg_stream_t stream);
 /* layout changes at the API boundary */
 int arseg_nchw_to_nhwc_fwd(const float *in, float *out, int N, int C, int HW, int out_ld, arseg_stream_t stream);
 int arseg_nhwc_to_nchw_fwd(const float *in, int in_ld, float *out, int N, int C, int HW, arseg_stream_t stream);
