@@ -127,6 +127,8 @@ PROTOTYPES = {
     "arseg_nhwc_to_nchw_fwd": (c_int, [_P, c_int, _P, c_int, c_int, c_int, _STREAM]),
     "arseg_argmax_confusion_fwd": (c_int, [_P, _P, _P, _P] + [c_int] * 8 + [_STREAM]),
     "arseg_argmax_confusion_grouped_fwd": (c_int, [_P, _P, _P, _P, _P] + [c_int] * 9 + [_STREAM]),
+    "arseg_segment_egress_fwd": (c_int, [_P] + [c_int] * 7 + [_P, _P, c_int64, c_int64, c_int, _P, _P, _P] + [c_int64] * 6 + [_P, _P, _P] + [c_int64] * 6
+                                 + [_P, _P, _STREAM]),
 }
 
 # the SURVEY.md section 8(b) names: aliases with the prototypes of their targets

@@ -1,5 +1,5 @@
 // Device-side primitives shared by the gfx950 kernels: vector types, buffer descriptors, LDS-DMA and store instructions issued through
-// inline asm, split-fp16 operand packing and wave reductions.  Each exists once, here; the kernels keep what is theirs alone.
+// inline asm, split-fp16 operand packing, wave reductions and the label rule of the evaluator tail.  Each exists once, here; the kernels keep what is theirs alone.
 #pragma once
 #include "arseg_common.h"
 
@@ -90,4 +90,92 @@ __device__ __forceinline__ double uniform_f64(double x) {
     unsigned lo, hi;                                 // (asm: the builtin is sunk to the use and the VGPR pair stays live)
     asm volatile("s_nop 1\n\tv_readfirstlane_b32 %0, %2\n\tv_readfirstlane_b32 %1, %3" : "=s"(lo), "=s"(hi) : "v"((unsigned)u), "v"((unsigned)(u >> 32)));
     return __builtin_bit_cast(double, ((unsigned long long)hi << 32) | lo);
+}
+
+// ------------------------------------------------------------------ the label rule of the evaluator tail and of the egress kernels
+// logits NCHW [N,n_cls,h,w] -> the class of one output pixel after the bilinear resize to H x W.  THE one definition: the evaluator tail
+// (layers.hip: argmax_pixel / argmax_run, ungrouped and grouped) and the egress kernels (egress.hip) call these, so their labels agree bit for
+// bit.  torch.argmax semantics: the first maximum wins, a NaN counts as the maximum (the first NaN wins).  Branch free (the short-circuit
+// form compiles to a divergent branch per pixel and class).
+
+// One output pixel (ox, oy) of frame n on the per-pixel route: `same` (h == H && w == W) reads the logit itself, otherwise the four bilinear
+// taps of arseg_src_index (sy / sx = arseg_resize_scale of the two axes, either align_corners).
+__device__ __forceinline__ int arseg_label_pixel(const float *__restrict__ logits, int n, int oy, int ox, int n_cls, int h, int w, int align, bool same,
+                                                 float sy, float sx) {
+    int y0 = oy, y1 = oy, x0 = ox, x1 = ox; float ly = 0.f, lx = 0.f;
+    if (!same) {
+        arseg_src_index(sy, oy, align != 0, h, y0, y1, ly);
+        arseg_src_index(sx, ox, align != 0, w, x0, x1, lx);
+        ly = fminf(fmaxf(ly, 0.f), 1.f); lx = fminf(fmaxf(lx, 0.f), 1.f);
+    }
+    float best = -INFINITY; int bi = 0; bool best_nan = false;
+    for (int k = 0; k < n_cls; ++k) {
+        const float *b = logits + ((size_t)n * n_cls + k) * h * w;
+        float v;
+        if (same) v = b[(size_t)oy * w + ox];
+        else v = (1.f - ly) * ((1.f - lx) * b[(size_t)y0 * w + x0] + lx * b[(size_t)y0 * w + x1]) +
+                 ly * ((1.f - lx) * b[(size_t)y1 * w + x0] + lx * b[(size_t)y1 * w + x1]);
+        const bool isn = v != v, take = !best_nan & ((v > best) | isn);
+        best = take ? v : best; bi = take ? k : bi; best_nan = best_nan | (take & isn);
+    }
+    return bi;
+}
+
+// One run of an exact x S bilinear upsample with align_corners=False, S a power of two: the S output pixels x = S*j + S/2 .. S*j + 3S/2 - 1
+// of output row oy all interpolate between the low-resolution columns j and j+1 (src = j + (r + 0.5) / S), j = -1 .. w-1 (the first and the
+// last run reach S/2 pixels off the frame: those entries of bi are computed on clamped columns and belong to no pixel).  The 4 taps are
+// loaded once per class and the S pixels evaluated from registers -- 4 loads per class and run instead of 4 S.  Same taps and weights as
+// arseg_label_pixel (arseg_src_index, sc = 1 / S); the blend is regrouped (see below), so a label may differ from the per-pixel form where
+// the top two logits are within fp32 rounding of each other: a caller picks the route by shape, never per pixel.
+template <int S>
+__device__ __forceinline__ void arseg_label_run(const float *__restrict__ logits, float sc, int n, int oy, int j, int n_cls, int h, int w, int (&bi)[S]) {
+    const int W = S * w;
+    int y0, y1; float ly;
+    arseg_src_index(sc, oy, false, h, y0, y1, ly);
+    ly = fminf(fmaxf(ly, 0.f), 1.f);
+    const int x0 = max(j, 0), x1 = min(x0 + 1, w - 1), xs = S * j + S / 2;       // first output column of the run (may be negative for j = -1)
+    float lx[S];
+#pragma unroll
+    for (int r = 0; r < S; ++r) {
+        int a, b;
+        arseg_src_index(sc, min(max(xs + r, 0), W - 1), false, w, a, b, lx[r]);
+        lx[r] = fminf(fmaxf(lx[r], 0.f), 1.f);
+    }
+    float best[S]; bool bn[S];
+#pragma unroll
+    for (int r = 0; r < S; ++r) { best[r] = -INFINITY; bi[r] = 0; bn[r] = false; }
+    const float *b = logits + (size_t)n * n_cls * h * w;
+    const size_t o00 = (size_t)y0 * w + x0, o01 = (size_t)y0 * w + x1, o10 = (size_t)y1 * w + x0, o11 = (size_t)y1 * w + x1, cs = (size_t)h * w;
+    for (int k0 = 0; k0 < n_cls; k0 += 4) {          // four classes' taps in flight (a class at a time is bound by the load latency)
+        float t[4][4];
+#pragma unroll
+        for (int u = 0; u < 4; ++u) {
+            const float *bk = b + (size_t)min(k0 + u, n_cls - 1) * cs;
+            if (x1 > x0) {          // the two taps of a row are neighbours: one 8-byte load (the kernel is bound by the number of load instructions)
+                // (a 4-byte aligned pair type: the address is odd in floats for every other run -- gfx950 global loads take any dword
+                // address, and the reduced alignment makes that a defined access instead of a misaligned float2)
+                typedef float f32x2_a4 __attribute__((ext_vector_type(2), aligned(4)));
+                const f32x2_a4 a01 = *reinterpret_cast<const f32x2_a4 *>(bk + o00), a11 = *reinterpret_cast<const f32x2_a4 *>(bk + o10);
+                t[u][0] = a01.x; t[u][1] = a01.y; t[u][2] = a11.x; t[u][3] = a11.y;
+            } else {
+                t[u][0] = bk[o00]; t[u][1] = bk[o01]; t[u][2] = bk[o10]; t[u][3] = bk[o11];
+            }
+        }
+#pragma unroll
+        for (int u = 0; u < 4; ++u) {
+            if (k0 + u >= n_cls) break;
+            // the bilinear blend is linear in lx along the run: v(r) = a + lx[r] * b -- one FMA per pixel and class (the expanded form,
+            // 6 operations, made this kernel VALU bound); same value up to fp32 rounding of the regrouped sum
+            const float a = (1.f - ly) * t[u][0] + ly * t[u][2];
+            const float b = (1.f - ly) * (t[u][1] - t[u][0]) + ly * (t[u][3] - t[u][2]);
+#pragma unroll
+            for (int r = 0; r < S; ++r) {
+                const float v = fmaf(lx[r], b, a);
+                const bool isn = v != v, take = !bn[r] & ((v > best[r]) | isn);
+                best[r] = take ? v : best[r];
+                bi[r] = take ? k0 + u : bi[r];
+                bn[r] = bn[r] | (take & isn);
+            }
+        }
+    }
 }

@@ -3,7 +3,7 @@
 // head, frame ingest (downscale + NCHW -> NHWC4), layout changes and the evaluator tail.
 // All of them are HBM/L2-bound element-wise or small-window kernels: 16-byte channel vectors per
 // lane (coalesced along C), grid-stride loops, no MFMA.
-#include "arseg_common.h"
+#include "arseg_device.h"
 
 namespace {
 
@@ -832,29 +832,13 @@ __device__ __forceinline__ void lds_hist_flush(const unsigned int *lh, unsigned 
         if (lh[i]) atomicAdd(&hist[i], (unsigned long long)lh[i]);
 }
 
-// One output pixel (ox, oy) of frame n: bilinear taps, argmax over the classes, pred store and the LDS count.  Shared by the ungrouped
-// and the grouped kernel, so the two give the same labels bit for bit.
+// One output pixel (ox, oy) of frame n: its class (arseg_label_pixel, arseg_device.h: bilinear taps, argmax over the classes), the pred
+// store and the LDS count.  Shared by the ungrouped and the grouped kernel, so the two give the same labels bit for bit.
 __device__ __forceinline__ void argmax_pixel(const float *__restrict__ logits, const int64_t *__restrict__ label, int32_t *__restrict__ pred,
                                              unsigned int *lh, bool count, int n, int oy, int ox, int n_cls, int h, int w, int H, int W,
                                              int ignore_label, int align, bool same, float sy, float sx) {
     const long long pix = ((long long)n * H + oy) * W + ox;
-    int y0 = oy, y1 = oy, x0 = ox, x1 = ox; float ly = 0.f, lx = 0.f;
-    if (!same) {
-        arseg_src_index(sy, oy, align != 0, h, y0, y1, ly);
-        arseg_src_index(sx, ox, align != 0, w, x0, x1, lx);
-        ly = fminf(fmaxf(ly, 0.f), 1.f); lx = fminf(fmaxf(lx, 0.f), 1.f);
-    }
-    // torch.argmax semantics: the first maximum wins, a NaN counts as the maximum (the first NaN wins)
-    float best = -INFINITY; int bi = 0; bool best_nan = false;
-    for (int k = 0; k < n_cls; ++k) {
-        const float *b = logits + ((size_t)n * n_cls + k) * h * w;
-        float v;
-        if (same) v = b[(size_t)oy * w + ox];
-        else v = (1.f - ly) * ((1.f - lx) * b[(size_t)y0 * w + x0] + lx * b[(size_t)y0 * w + x1]) +
-                 ly * ((1.f - lx) * b[(size_t)y1 * w + x0] + lx * b[(size_t)y1 * w + x1]);
-        const bool isn = v != v, take = !best_nan & ((v > best) | isn);          // branch free
-        best = take ? v : best; bi = take ? k : bi; best_nan = best_nan | (take & isn);
-    }
+    const int bi = arseg_label_pixel(logits, n, oy, ox, n_cls, h, w, align, same, sy, sx);
     if (pred) pred[pix] = bi;
     if (count) {
         const long long lab = label[pix];
@@ -907,61 +891,15 @@ __global__ __launch_bounds__(256) void argmax_confusion_grouped_kernel(const flo
 // columns j and j+1 (src = j + (r + 0.5) / S), so one thread takes such a run, loads its 4 taps once per class and evaluates the S
 // pixels from registers -- 4 loads per class and run instead of 4 S; the per-pixel kernel above issues 76 scattered loads per output
 // pixel at 19 classes and is bound by the texture path's instruction rate (77 us per 1024x2048 frame; this one: memory-side trivial).
-// Same taps and weights (arseg_src_index) and the same argmax semantics; the blend is regrouped (see below).
+// Same taps and weights (arseg_src_index) and the same argmax semantics; the blend is regrouped (arseg_label_run, arseg_device.h).
 // One run of frame n: output row oy, low-resolution column j (-1 .. w-1).  Shared by the ungrouped and the grouped kernel.
 template <int S>
 __device__ __forceinline__ void argmax_run(const float *__restrict__ logits, const int64_t *__restrict__ label, int32_t *__restrict__ pred,
                                            unsigned int *lh, bool count, bool pred_vec, float sc, int n, int oy, int j, int n_cls, int h, int w,
                                            int ignore_label) {
-    const int H = S * h, W = S * w;
-    int y0, y1; float ly;
-    arseg_src_index(sc, oy, false, h, y0, y1, ly);
-    ly = fminf(fmaxf(ly, 0.f), 1.f);
-    const int x0 = max(j, 0), x1 = min(x0 + 1, w - 1), xs = S * j + S / 2;       // first output column of the run (may be negative for j = -1)
-    float lx[S];
-#pragma unroll
-    for (int r = 0; r < S; ++r) {
-        int a, b;
-        arseg_src_index(sc, min(max(xs + r, 0), W - 1), false, w, a, b, lx[r]);
-        lx[r] = fminf(fmaxf(lx[r], 0.f), 1.f);
-    }
-    float best[S]; int bi[S]; bool bn[S];
-#pragma unroll
-    for (int r = 0; r < S; ++r) { best[r] = -INFINITY; bi[r] = 0; bn[r] = false; }
-    const float *b = logits + (size_t)n * n_cls * h * w;
-    const size_t o00 = (size_t)y0 * w + x0, o01 = (size_t)y0 * w + x1, o10 = (size_t)y1 * w + x0, o11 = (size_t)y1 * w + x1, cs = (size_t)h * w;
-    for (int k0 = 0; k0 < n_cls; k0 += 4) {          // four classes' taps in flight (a class at a time is bound by the load latency)
-        float t[4][4];
-#pragma unroll
-        for (int u = 0; u < 4; ++u) {
-            const float *bk = b + (size_t)min(k0 + u, n_cls - 1) * cs;
-            if (x1 > x0) {          // the two taps of a row are neighbours: one 8-byte load (the kernel is bound by the number of load instructions)
-                // (a 4-byte aligned pair type: the address is odd in floats for every other run -- gfx950 global loads take any dword
-                // address, and the reduced alignment makes that a defined access instead of a misaligned float2)
-                typedef float f32x2_a4 __attribute__((ext_vector_type(2), aligned(4)));
-                const f32x2_a4 a01 = *reinterpret_cast<const f32x2_a4 *>(bk + o00), a11 = *reinterpret_cast<const f32x2_a4 *>(bk + o10);
-                t[u][0] = a01.x; t[u][1] = a01.y; t[u][2] = a11.x; t[u][3] = a11.y;
-            } else {
-                t[u][0] = bk[o00]; t[u][1] = bk[o01]; t[u][2] = bk[o10]; t[u][3] = bk[o11];
-            }
-        }
-#pragma unroll
-        for (int u = 0; u < 4; ++u) {
-            if (k0 + u >= n_cls) break;
-            // the bilinear blend is linear in lx along the run: v(r) = a + lx[r] * b -- one FMA per pixel and class (the expanded form,
-            // 6 operations, made this kernel VALU bound); same value up to fp32 rounding of the regrouped sum
-            const float a = (1.f - ly) * t[u][0] + ly * t[u][2];
-            const float b = (1.f - ly) * (t[u][1] - t[u][0]) + ly * (t[u][3] - t[u][2]);
-#pragma unroll
-            for (int r = 0; r < S; ++r) {          // branch free (the short-circuit form compiles to a divergent branch per pixel and class)
-                const float v = fmaf(lx[r], b, a);
-                const bool isn = v != v, take = !bn[r] & ((v > best[r]) | isn);
-                best[r] = take ? v : best[r];
-                bi[r] = take ? k0 + u : bi[r];
-                bn[r] = bn[r] | (take & isn);
-            }
-        }
-    }
+    const int H = S * h, W = S * w, xs = S * j + S / 2;       // first output column of the run (may be negative for j = -1)
+    int bi[S];
+    arseg_label_run<S>(logits, sc, n, oy, j, n_cls, h, w, bi);
     const long long row = ((long long)n * H + oy) * W;
     const bool whole = xs >= 0 && xs + S <= W;              // interior run: S consecutive labels, S/2 * 4 bytes aligned (W = S w, xs = S j + S/2)
     if (pred && whole && S >= 4 && pred_vec) {               // vector stores (scalar ones: 4 bytes per lane at a 4 S byte stride)

@@ -1,0 +1,103 @@
+"""What a deployed segmenter hands on, straight from the head logits (the mirror of ``ingest`` on the way out).
+
+* ``labels8``: the 8-bit mask plane, optionally mapped from train ids to the dataset's label ids.
+* ``overlay``: the frame with the classes painted over it, in the plane format the decoder delivered (``ingest.DecodedFrames``: RGB8, NV12 or
+  I420) -- the input of a display or a hardware encoder.  ``out=frames`` paints in place.
+
+Both are one launch of ``ops.segment_egress`` (csrc/egress.hip): the bilinear resize and the argmax are the evaluator tail's own, so the
+labels equal ``ops.argmax_confusion``'s ``pred`` bit for bit, and neither int32 labels nor a float frame are ever written.  The painting is
+integer arithmetic, written out in include/arseg_hip.h (arseg_segment_egress_fwd).  Not covered: 10-bit, 4:2:2 or 4:4:4 destinations, text,
+legends or contours, the encoder itself.
+"""
+from __future__ import annotations
+
+import numpy as np
+import torch
+
+from . import _lib, ingest, ops
+
+# Presentation colours (RGB), one per train id; any [n_cls,3] uint8 table serves.
+CAMVID_PALETTE = ((135, 206, 235), (128, 0, 0), (192, 192, 128), (128, 64, 128), (0, 0, 192), (0, 160, 0), (192, 128, 128), (64, 64, 128),
+                  (64, 0, 128), (255, 160, 0), (0, 128, 192), (0, 0, 0))
+CITYSCAPES_PALETTE = ((120, 60, 130), (240, 40, 230), (72, 72, 72), (100, 100, 160), (190, 150, 150), (150, 150, 150), (255, 170, 30),
+                      (220, 220, 0), (100, 140, 40), (150, 250, 150), (70, 130, 180), (220, 20, 60), (255, 0, 0), (0, 0, 140), (0, 0, 70),
+                      (0, 60, 100), (0, 80, 100), (0, 0, 230), (120, 10, 30))
+
+_MATRIX = {enum: key for key, enum in ingest._COLOUR.items()}          # enum arseg_colour -> ("bt601" | "bt709", full_range)
+
+
+class Palette(object):
+    """Colours and blend weights of an overlay: ``colours_u8`` [n_cls,3] RGB, ``alpha`` one float or n_cls floats in 0..1 (0 leaves the frame,
+    1 replaces it).  The kernel's weights are ``a_k = clip(rint(alpha_k * 256), 0, 256)``."""
+
+    def __init__(self, colours_u8, alpha=0.5):
+        c = np.asarray(colours_u8)
+        if c.ndim != 2 or c.shape[1] != 3 or c.shape[0] < 1 or not np.issubdtype(c.dtype, np.integer) or c.min() < 0 or c.max() > 255:
+            raise ValueError(f"Palette: colours must be [n_cls,3] integers in 0..255, got {c.dtype} {c.shape}")
+        self.colours = np.ascontiguousarray(c.astype(np.uint8))
+        a = np.asarray(alpha, dtype=np.float64)
+        if a.ndim == 0:
+            a = np.full(len(self.colours), float(a))
+        if a.shape != (len(self.colours),) or np.isnan(a).any():
+            raise ValueError(f"Palette: alpha must be one float or {len(self.colours)} floats, got shape {a.shape}")
+        self.weights = np.clip(np.rint(a * 256.0), 0, 256).astype(np.uint16)
+
+    def __len__(self):
+        return len(self.colours)
+
+    def codes(self, src_format, colour=_lib.COLOUR_BT709_LIMITED) -> np.ndarray:
+        """The [n_cls,3] uint8 table in the destination's codes: RGB8 -> the colours; NV12 / I420 -> (Y, Cb, Cr) of each colour under the
+        frame's ``colour`` enum, by ``ingest.rgb_to_nv12``'s arithmetic (a 2x2 image of one colour: the box average of equal values)."""
+        if src_format == _lib.SRC_RGB8:
+            return self.colours.copy()
+        if src_format not in (_lib.SRC_NV12, _lib.SRC_I420):
+            raise ValueError(f"Palette.codes: RGB8, NV12 or I420 destinations only (10-bit formats are not covered), got format {src_format!r}")
+        if colour not in _MATRIX:
+            raise ValueError(f"Palette.codes: unknown colour enum {colour!r}")
+        matrix, full = _MATRIX[colour]
+        y, uv = ingest.rgb_to_nv12(np.broadcast_to(self.colours[:, None, None, :], (len(self.colours), 2, 2, 3)), matrix, full)
+        return np.ascontiguousarray(np.concatenate([y[:, :1, 0], uv[:, 0, 0, :]], axis=1))
+
+
+def _check_logits(logits):
+    if not torch.is_tensor(logits) or logits.dim() != 4:
+        raise ValueError("expected head logits as an fp32 tensor [N,n_cls,h,w]")
+    return logits.contiguous()
+
+
+def labels8(logits, H, W, lut=None, out=None, align_corners=True) -> torch.Tensor:
+    """Head logits [N,n_cls,h,w] -> uint8 labels [N,H,W]: ``ops.argmax_confusion``'s pred (same resize, same argmax), as bytes, through
+    ``lut`` (n_cls integers 0..255, e.g. train id -> label id; a list or an array) when given.  ``out``: the caller's buffer (nothing is allocated then)."""
+    logits = _check_logits(logits)
+    if out is None:
+        out = torch.empty((logits.shape[0], int(H), int(W)), dtype=torch.uint8, device=logits.device)
+    ops.segment_egress(logits, H, W, align_corners=align_corners, lut=lut, labels_out=out)
+    return out
+
+
+def overlay(logits, frames, palette, out=None, labels_out=None, lut=None, align_corners=True):
+    """Head logits [N,n_cls,h,w] + the decoder's frames -> (the painted frames, labels8 | None), one launch.  ``frames``: an 8-bit
+    ``ingest.DecodedFrames`` (RGB8, NV12, I420); the labels have its H x W.  The result has the format, colour, mean and std of ``frames``;
+    ``out``: a DecodedFrames of the same format and size to write into (``out=frames`` paints in place), default freshly allocated.
+    ``labels_out``: a uint8 [N,H,W] buffer, or True to have one allocated; None = no label plane."""
+    if not isinstance(frames, ingest.DecodedFrames):
+        raise ValueError(f"overlay paints over ingest.DecodedFrames (8-bit RGB8 / NV12 / I420), got {type(frames).__name__}")
+    if frames.src_format not in (_lib.SRC_RGB8, _lib.SRC_NV12, _lib.SRC_I420):
+        raise ValueError("overlay: 10-bit sources (P010, I010) are not covered; RGB8, NV12 and I420 are")
+    if not isinstance(palette, Palette):
+        palette = Palette(palette)
+    logits = _check_logits(logits)
+    n_cls = logits.shape[1]
+    if len(palette) < n_cls:
+        raise ValueError(f"overlay: the palette holds {len(palette)} colours, the logits {n_cls} classes")
+    if out is None:
+        out = frames._with([torch.empty(p.shape, dtype=p.dtype, device=p.device) for p in frames.planes])
+    elif not isinstance(out, ingest.DecodedFrames) or out.src_format != frames.src_format or out.shape != frames.shape:
+        raise ValueError("overlay: out must be DecodedFrames of the source's format and size")
+    if labels_out is True:
+        labels_out = torch.empty((frames.N, frames.H, frames.W), dtype=torch.uint8, device=logits.device)
+    ops.segment_egress(logits, frames.H, frames.W, align_corners=align_corners, lut=lut, labels_out=labels_out, src=frames, dst=out,
+                       palette=palette.codes(frames.src_format, frames.colour)[:n_cls], weights=palette.weights[:n_cls])
+    if out is not frames and (out.colour, out.mean, out.std) != (frames.colour, frames.mean, frames.std):
+        out = frames._with(out.planes)
+    return out, labels_out

@@ -373,3 +373,33 @@ def alter_res_batch_pred(lr_net, ref_ps, imgs, mv_qs, scale=0.5, labels=None, hi
     if groups is not None:
         return ops.argmax_confusion_grouped(lo, labels, groups, n_groups, H, W, hist, ignore_label, align_corners=not fused_up)
     return ops.argmax_confusion(lo, labels, H, W, hist, ignore_label, align_corners=not fused_up)
+
+
+def alter_res_batch_render(lr_net, ref_ps, imgs, mv_qs, scale=0.5, palette=None, lut=None, labels_out=None, out=None):
+    """The deployment sibling of ``alter_res_batch_pred``: the same phase 1 and phase 2, then the egress launch instead of the evaluator
+    tail -> (labels uint8 [B,H,W], painted frames | None).  The labels equal ``alter_res_batch_pred``'s pred (the same route decision:
+    BiSeNet's 1/8-resolution head logits with align_corners=False when the frame is exactly 8x the head, align_corners=True otherwise),
+    as bytes and through ``lut`` (n_cls integers 0..255) when given.  ``palette`` (``egress.Palette`` or an [n_cls,3] colour table): also paint the classes over
+    ``imgs``, which must then be 8-bit ``ingest.DecodedFrames`` (RGB8, NV12, I420); ``out`` the frames to write into (``out=imgs``: in
+    place).  ``labels_out`` / ``out``: the caller's buffers; with both given nothing frame-sized is allocated.  A GOP's keyframe goes
+    through ``egress.overlay(net.forward_keyframe(key)[0], key, palette)``.  ``out`` without ``palette`` is a ValueError (nothing would be
+    painted into it)."""
+    from . import egress
+    if palette is None and out is not None:
+        raise ValueError("alter_res_batch_render: out= needs a palette (without one only the labels are written)")
+    lr_net = _unwrap(lr_net)
+    B, _, H, W = imgs.shape
+    h, w = _downscale_hw(H, W, scale)
+    feat = lr_net.phase1_nhwc4(ops.ingest_input(imgs, h, w, lr_net.storage_dtype), aux=ops.config.aux_outputs)[-1]
+    fused_up = hasattr(lr_net, "out_upsample")
+    if fused_up:
+        lo, _ = lr_net.phase2_warp(feat, list(ref_ps), mv_qs, upsample=False)
+        if (8 * lo.shape[-2], 8 * lo.shape[-1]) != (H, W):
+            lo, fused_up = ops.resize_nchw(lo, 8 * lo.shape[-2], 8 * lo.shape[-1], _lib.BILINEAR, False), False
+    else:
+        lo, _ = lr_net.phase2_warp(feat, list(ref_ps), mv_qs)
+    if palette is None:
+        return egress.labels8(lo, H, W, lut=lut, out=labels_out, align_corners=not fused_up), None
+    painted, labels = egress.overlay(lo, imgs, palette, out=out, labels_out=True if labels_out is None else labels_out, lut=lut,
+                                     align_corners=not fused_up)
+    return labels, painted

@@ -1,0 +1,93 @@
+"""The output half of the pipeline: head logits -> an 8-bit label plane and / or the frame with the classes painted over it, one ABI call
+(include/arseg_hip.h, arseg_segment_egress_fwd; csrc/egress.hip)."""
+from __future__ import annotations
+
+import ctypes
+from typing import Optional
+
+import numpy as np
+import torch
+
+from .. import _lib
+from ._base import _need_gpu, _ptr, _stream
+from ._profile import launch
+from .layers import _plane_layout
+
+_INNER = {_lib.SRC_RGB8: lambda W: ((W, 3),), _lib.SRC_NV12: lambda W: ((W,), (W // 2, 2)), _lib.SRC_I420: lambda W: ((W,), (W // 2,), (W // 2,))}
+
+
+def _host_u8(v, n, what):
+    """n host values in 0..255 (any integer sequence or array) -> a ctypes uint8 array."""
+    a = np.asarray(v)
+    if a.size != n or not (np.issubdtype(a.dtype, np.integer) or a.dtype == np.bool_) or (a.size and (a.min() < 0 or a.max() > 255)):
+        raise ValueError(f"{what}: expected {n} integers in 0..255, got {a.dtype} {a.shape}")
+    return (ctypes.c_uint8 * n).from_buffer_copy(np.ascontiguousarray(a, dtype=np.uint8).tobytes())
+
+
+def _planes(frames, N, H, W, what):
+    """(src_format, [(tensor, pitch, image stride)] * planes) of a DecodedFrames-like object (``src_format``, ``planes``)."""
+    fmt = getattr(frames, "src_format", None)
+    if fmt not in _INNER:
+        raise ValueError(f"{what}: an overlay takes 8-bit RGB8, NV12 or I420 frames; 10-bit and other sources are not covered (format {fmt!r})")
+    planes = tuple(frames.planes)
+    inner = _INNER[fmt](W)
+    if len(planes) != len(inner) or any(not torch.is_tensor(t) or t.dtype != torch.uint8 for t in planes):
+        raise ValueError(f"{what}: expected {len(inner)} uint8 plane tensors")
+    if fmt != _lib.SRC_RGB8 and (H % 2 or W % 2):
+        raise ValueError(f"{what}: 4:2:0 needs even H and W, got {H}x{W}")
+    _need_gpu(*planes, dtype=torch.uint8)
+    out = []
+    for i, (t, inn) in enumerate(zip(planes, inner)):
+        want = (N, H if i == 0 else H // 2) + tuple(inn)
+        if tuple(t.shape) != want:
+            raise ValueError(f"{what}: plane {i} must be {want}, got {tuple(t.shape)}")
+        out.append((t,) + _plane_layout(t, inn, f"{what} plane {i}"))
+    return fmt, out
+
+
+def segment_egress(logits: torch.Tensor, H: int, W: int, *, align_corners: bool = True, lut=None, labels_out: Optional[torch.Tensor] = None,
+                   src=None, dst=None, palette=None, weights=None):
+    """Head logits fp32 [N,n_cls,h,w] -> the label plane ``labels_out`` (uint8 [N,H,W], rows contiguous, any row pitch / image stride; value
+    ``lut[k]`` or ``k``) and / or the overlay ``dst`` of ``src`` (both ``ingest.DecodedFrames`` of one 8-bit format, RGB8 / NV12 / I420, [N,.,H,W];
+    ``dst`` may be ``src``: painted in place), in one launch.  ``k`` is ``argmax_confusion``'s pred for the same ``H, W, align_corners``, bit for
+    bit.  ``palette`` [n_cls,3] integers 0..255 in the destination's codes, ``weights`` n_cls integers 0..256, ``lut`` n_cls integers 0..255 (host
+    values: lists or arrays of any integer type).
+    Allocates nothing: every output is the caller's, so the call can be captured in a HIP graph.  Returns (labels_out, dst)."""
+    _need_gpu(logits)
+    if logits.dim() != 4 or not logits.is_contiguous():
+        raise _lib.ArsegError(f"segment_egress expects contiguous fp32 logits [N,n_cls,h,w], got {tuple(logits.shape)}")
+    N, n_cls, h, w = logits.shape
+    H, W = int(H), int(W)
+    if labels_out is None and dst is None:
+        raise ValueError("segment_egress: nothing to write (labels_out and dst are both None)")
+    if not 1 <= n_cls <= 32:
+        raise ValueError(f"segment_egress: 1..32 classes, got {n_cls}")
+    lab_pitch = lab_ns = 0
+    if labels_out is not None:
+        _need_gpu(labels_out, dtype=torch.uint8)
+        if tuple(labels_out.shape) != (N, H, W) or labels_out.device != logits.device:
+            raise ValueError(f"labels_out must be uint8 {(N, H, W)} on {logits.device}, got {tuple(labels_out.shape)} on {labels_out.device}")
+        lab_pitch, lab_ns = _plane_layout(labels_out, (W,), "segment_egress labels_out")
+    lut_c = None if lut is None else _host_u8(lut, n_cls, "lut")
+    fmt, sp, dp, pal_c, wt_c = 0, [], [], None, None
+    if dst is not None:
+        if src is None or palette is None or weights is None:
+            raise ValueError("segment_egress: an overlay needs src, palette and weights")
+        fmt, sp = _planes(src, N, H, W, "segment_egress src")
+        fmt_d, dp = _planes(dst, N, H, W, "segment_egress dst")
+        if fmt_d != fmt or any(t.device != logits.device for t, _, _ in sp + dp):
+            raise ValueError("segment_egress: src and dst must hold the same format on the logits' device")
+        pal_c = _host_u8(palette, 3 * n_cls, "palette")
+        wts = np.asarray(weights)
+        if wts.size != n_cls or not np.issubdtype(wts.dtype, np.integer) or wts.min() < 0 or wts.max() > 256:
+            raise ValueError(f"weights: expected {n_cls} integers in 0..256")
+        wt_c = (ctypes.c_uint16 * n_cls).from_buffer_copy(np.ascontiguousarray(wts, dtype=np.uint16).tobytes())
+    none = (None, 0, 0)
+    sp3, dp3 = (sp + [none] * 3)[:3], (dp + [none] * 3)[:3]
+    plane_bytes = sum(t.shape[0] * t.shape[1] * int(np.prod(t.shape[2:])) for t, _, _ in sp + dp)
+    launch("segment_egress", _lib.load().arseg_segment_egress_fwd, _ptr(logits), N, n_cls, h, w, H, W, 1 if align_corners else 0, lut_c,
+           _ptr(labels_out), lab_pitch, lab_ns, fmt,
+           _ptr(sp3[0][0]), _ptr(sp3[1][0]), _ptr(sp3[2][0]), sp3[0][1], sp3[1][1], sp3[2][1], sp3[0][2], sp3[1][2], sp3[2][2],
+           _ptr(dp3[0][0]), _ptr(dp3[1][0]), _ptr(dp3[2][0]), dp3[0][1], dp3[1][1], dp3[2][1], dp3[0][2], dp3[1][2], dp3[2][2],
+           pal_c, wt_c, _stream(), nbytes=logits.numel() * 4 + plane_bytes + (N * H * W if labels_out is not None else 0))
+    return labels_out, dst

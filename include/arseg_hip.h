@@ -624,6 +624,44 @@ int arseg_argmax_confusion_grouped_fwd(const float *logits, const int64_t *label
                                        arseg_stream_t stream);
 
 /* ---------------------------------------------------------------------------------------------
+ * Segmentation egress (csrc/egress.hip): head logits -> what a deployed segmenter hands on, in one launch for N frames, without an int32
+ * or float frame-sized tensor in between.
+ *   logits, N, n_cls, h, w, H, W, align_corners: as arseg_argmax_confusion_fwd.  Per output pixel the class k is EXACTLY what that entry point
+ *               writes into pred for the same arguments (one device function serves both, csrc/arseg_device.h): the h == H && w == W route, the
+ *               per-pixel bilinear route (either align_corners) and the x2 / x4 / x8 align_corners == 0 run route with its regrouped blend;
+ *               first maximum wins, NaN counts as maximum.
+ *   labels8     uint8 [N][H][W], labels_pitch bytes from row to row (>= W), labels_n_stride bytes from image to image (>= 0); value =
+ *               lut ? lut[k] : k.  lut: HOST pointer to n_cls bytes (e.g. train id -> dataset label id), NULL = identity.  May be NULL.
+ *   overlay     src0..2 -> dst0..2: the frame with the classes painted over it, source and destination in the same 8-bit `format`:
+ *               ARSEG_SRC_RGB8 (plane 0), ARSEG_SRC_NV12 (planes 0, 1) or ARSEG_SRC_I420 (planes 0, 1, 2), planes, pitches and image strides
+ *               as arseg_frame_ingest_fwd / arseg_frame_ingest_yuv_fwd take them, each side with its own.  Rows may be padded; nothing past a
+ *               row's last sample is read or written.  dst0 NULL = no overlay (format and the plane arguments are then ignored).
+ *   palette     HOST uint8 [n_cls][3], codes of the destination format: (R, G, B), or (Y, Cb, Cr) of the frame's colour matrix and range
+ *   weights     HOST uint16 [n_cls], a_k in 0 .. 256: 0 leaves the frame's sample, 256 replaces it
+ * Integer arithmetic, exact:
+ *   RGB8, per channel c:     dst = (src (256 - a_k) + P[k][c] a_k + 128) >> 8
+ *   4:2:0 luma, per pixel:   Y'  = (Y (256 - a_k) + P[k][0] a_k + 128) >> 8
+ *   4:2:0 chroma, per sample, over the four luma pixels i of its 2 x 2 block with classes k_i:  A = sum a_{k_i},
+ *                            C'  = (C (1024 - A) + sum a_{k_i} P[k_i][c] + 512) >> 10          c = 1 (Cb), 2 (Cr)
+ *   (equal weights: the 2 x 2 box average of the painted colour, the chroma model of a 4:2:0 encoder's input)
+ * In place: every destination sample is read from the source and written by the same thread exactly once, so a destination plane may BE its
+ * source plane (same pointer, pitch and image stride), or be entirely distinct from every source plane.  Partial overlap is undefined.
+ * labels8 must not overlap any other buffer.
+ * Enqueue only: no allocation, no synchronisation.  ARSEG_EINVAL, before any launch: null logits; labels8 and dst0 both null; dst0 without
+ * src0, palette or weights (or without the format's further planes on either side); n_cls < 1 or > 32; a weight above 256; a non-positive
+ * size; odd H or W with NV12 / I420; a pitch smaller than a row; a negative image stride; a format other than the three above (P010 / I010
+ * are rejected).
+ * Not covered: 10-bit, 4:2:2 or 4:4:4 destinations; text, legends or contours; the encoder; the confusion histogram (evaluation keeps
+ * arseg_argmax_confusion_fwd).
+ * ------------------------------------------------------------------------------------------- */
+int arseg_segment_egress_fwd(const float *logits, int N, int n_cls, int h, int w, int H, int W, int align_corners, const uint8_t *lut,
+                             uint8_t *labels8, int64_t labels_pitch, int64_t labels_n_stride, int format, const void *src0, const void *src1,
+                             const void *src2, int64_t src_pitch0, int64_t src_pitch1, int64_t src_pitch2, int64_t src_n_stride0,
+                             int64_t src_n_stride1, int64_t src_n_stride2, void *dst0, void *dst1, void *dst2, int64_t dst_pitch0,
+                             int64_t dst_pitch1, int64_t dst_pitch2, int64_t dst_n_stride0, int64_t dst_n_stride1, int64_t dst_n_stride2,
+                             const uint8_t *palette, const uint16_t *weights, arseg_stream_t stream);
+
+/* ---------------------------------------------------------------------------------------------
  * Measurement aids (no reference counterpart; BASELINE.md section 3: roofline fractions are reported against the datasheet peaks AND
  * against on-box micro-benchmarks).  bench.py times each with HIP events and prints `peaks_measured`.
  *   arseg_peak_stream_copy: dst[0 .. n_bytes) = src[0 .. n_bytes) with 16-byte accesses (n_bytes % 16 == 0, both 16-byte aligned):
