@@ -6,8 +6,8 @@
 * decoded frames: uint8 HWC; ``ToTensor`` + ``Normalize`` (dataset/camvid.py:503-506) and the evaluator's downscale
   (evaluation.py:186-188) run in one kernel, ``ops.frame_u8_to_nhwc4``.
 * decoder output as the fast paths take it: ``DecodedFrames`` (uint8 RGB, NV12 or I420 planes, 10-bit P010 or I010 planes + normalisation +
-  colour matrix); every fast path that accepts float NCHW frames accepts one of these instead and ingests it with ``ops.frame_ingest8`` /
-  ``ops.frame_ingest_yuv`` (csrc/ingest.hip).
+  colour matrix); every fast path that accepts float NCHW frames accepts one of these instead and ingests it with the one implementation
+  behind ``ops.frame_ingest8`` / ``ops.frame_ingest_yuv`` (csrc/ingest.hip).
 * decoder motion as a decoder holds it: block records ``int16 [n,8]`` per P-frame (x, y, w, h, mvx, mvy, ref, reserved; the contract is in
   include/arseg_hip.h, arseg_mv_records_*).  ``MotionChain`` rasterises and chains them to the keyframe frame by frame on the GPU
   (csrc/mv_records.hip) into the ``mv_qs`` tensor the fast paths read; ``mv_to_records`` / ``records_to_dense`` convert the reference's
@@ -63,26 +63,33 @@ def colour_enum(matrix: str = "bt709", full_range: bool = False) -> int:
         raise ValueError(f"matrix must be 'bt601' or 'bt709', got {matrix!r}") from None
 
 
+def _rgb_to_yuv(rgb_u8, who, what, bits, matrix, full_range):
+    """The fp64 core of ``rgb_to_nv12`` / ``rgb_to_yuv420``: -> (Y [..,H,W], Cb, Cr [..,H/2,W/2]) codes of depth ``bits``, rounded to nearest once."""
+    colour_enum(matrix, full_range)
+    rgb = np.asarray(rgb_u8)
+    if rgb.dtype != np.uint8 or rgb.ndim not in (3, 4) or rgb.shape[-1] != 3:
+        raise ValueError(f"{who} expects uint8 [H,W,3] or [N,H,W,3], got {rgb.dtype} {rgb.shape}")
+    H, W = rgb.shape[-3], rgb.shape[-2]
+    if H % 2 or W % 2:
+        raise ValueError(f"{what} needs even H and W, got {H}x{W}")
+    kr, kb = _LUMA[str(matrix).lower()]
+    r, g, b = (rgb[..., c].astype(np.float64) for c in range(3))
+    yl = kr * r + (1.0 - kr - kb) * g + kb * b
+    cb, cr = (b - yl) / (2.0 * (1.0 - kb)), (r - yl) / (2.0 * (1.0 - kr))
+    top, k = (1 << bits) - 1, 1 << (bits - 8)
+    sy, sc, y0 = (top / 255.0, top / 255.0, 0.0) if full_range else (219.0 * k / 255.0, 224.0 * k / 255.0, 16.0 * k)
+    box = lambda c: c.reshape(c.shape[:-2] + (H // 2, 2, W // 2, 2)).mean(axis=(-3, -1))
+    q = lambda v: np.clip(np.rint(v), 0, top).astype(np.uint8 if bits == 8 else np.uint16)
+    return q(y0 + sy * yl), q(128.0 * k + sc * box(cb)), q(128.0 * k + sc * box(cr))
+
+
 def rgb_to_nv12(rgb_u8, matrix: str = "bt709", full_range: bool = False):
     """uint8 RGB [H,W,3] / [N,H,W,3] (numpy) -> (luma uint8 [..,H,W], chroma uint8 [..,H/2,W/2,2] = (Cb, Cr)), H and W even: what a decoder
     would hand over for these frames.  Y' = Kr R + Kg G + Kb B, Cb = (B - Y') / (2 (1 - Kb)), Cr = (R - Y') / (2 (1 - Kr)); limited range
     Y = 16 + 219/255 Y', C = 128 + 224/255 C', full range Y = Y', C = 128 + C'; chroma is the 2x2 box average (the sample between two luma
     rows), everything rounded to nearest once.  For tests, tools and callers without a decoder; runs on the host."""
-    colour_enum(matrix, full_range)
-    rgb = np.asarray(rgb_u8)
-    if rgb.dtype != np.uint8 or rgb.ndim not in (3, 4) or rgb.shape[-1] != 3:
-        raise ValueError(f"rgb_to_nv12 expects uint8 [H,W,3] or [N,H,W,3], got {rgb.dtype} {rgb.shape}")
-    H, W = rgb.shape[-3], rgb.shape[-2]
-    if H % 2 or W % 2:
-        raise ValueError(f"NV12 needs even H and W, got {H}x{W}")
-    kr, kb = _LUMA[str(matrix).lower()]
-    r, g, b = (rgb[..., c].astype(np.float64) for c in range(3))
-    yl = kr * r + (1.0 - kr - kb) * g + kb * b
-    cb, cr = (b - yl) / (2.0 * (1.0 - kb)), (r - yl) / (2.0 * (1.0 - kr))
-    sy, sc, y0 = (1.0, 1.0, 0.0) if full_range else (219.0 / 255.0, 224.0 / 255.0, 16.0)
-    box = lambda c: c.reshape(c.shape[:-2] + (H // 2, 2, W // 2, 2)).mean(axis=(-3, -1))
-    q = lambda v: np.clip(np.rint(v), 0, 255).astype(np.uint8)
-    return q(y0 + sy * yl), np.stack([q(128.0 + sc * box(cb)), q(128.0 + sc * box(cr))], axis=-1)
+    y, u, v = _rgb_to_yuv(rgb_u8, "rgb_to_nv12", "NV12", 8, matrix, full_range)
+    return y, np.stack([u, v], axis=-1)
 
 
 _LAYOUTS = ("nv12", "i420", "p010", "i010")
@@ -97,40 +104,19 @@ def rgb_to_yuv420(rgb_u8, layout: str = "nv12", matrix: str = "bt709", full_rang
     if layout not in _LAYOUTS:
         raise ValueError(f"layout must be one of {_LAYOUTS}, got {layout!r}")
     if layout in ("nv12", "i420"):
-        y, uv = rgb_to_nv12(rgb_u8, matrix, full_range)
-        return (y, uv) if layout == "nv12" else (y, np.ascontiguousarray(uv[..., 0]), np.ascontiguousarray(uv[..., 1]))
-    colour_enum(matrix, full_range)
-    rgb = np.asarray(rgb_u8)
-    if rgb.dtype != np.uint8 or rgb.ndim not in (3, 4) or rgb.shape[-1] != 3:
-        raise ValueError(f"rgb_to_yuv420 expects uint8 [H,W,3] or [N,H,W,3], got {rgb.dtype} {rgb.shape}")
-    H, W = rgb.shape[-3], rgb.shape[-2]
-    if H % 2 or W % 2:
-        raise ValueError(f"4:2:0 needs even H and W, got {H}x{W}")
-    kr, kb = _LUMA[str(matrix).lower()]
-    r, g, b = (rgb[..., c].astype(np.float64) for c in range(3))
-    yl = kr * r + (1.0 - kr - kb) * g + kb * b
-    cb, cr = (b - yl) / (2.0 * (1.0 - kb)), (r - yl) / (2.0 * (1.0 - kr))
-    sy, sc, y0 = (1023.0 / 255.0, 1023.0 / 255.0, 0.0) if full_range else (876.0 / 255.0, 896.0 / 255.0, 64.0)
-    box = lambda c: c.reshape(c.shape[:-2] + (H // 2, 2, W // 2, 2)).mean(axis=(-3, -1))
-    q = lambda v: np.clip(np.rint(v), 0, 1023).astype(np.uint16)
-    y, u, v = q(y0 + sy * yl), q(512.0 + sc * box(cb)), q(512.0 + sc * box(cr))
+        y, u, v = _rgb_to_yuv(rgb_u8, "rgb_to_nv12", "NV12", 8, matrix, full_range)
+        return (y, np.stack([u, v], axis=-1)) if layout == "nv12" else (y, u, v)
+    y, u, v = _rgb_to_yuv(rgb_u8, "rgb_to_yuv420", "4:2:0", 10, matrix, full_range)
     return (y, u, v) if layout == "i010" else (y << 6, np.stack([u, v], axis=-1) << 6)
 
 
-def _plane(t, what):
+def _plane(t, what, dtype=torch.uint8):
+    """Samples as they are (a view, not a copy); where uint16 is wanted, torch.int16 is taken as the same bit pattern."""
     t = torch.as_tensor(np.ascontiguousarray(t)) if not torch.is_tensor(t) else t
-    if t.dtype != torch.uint8:
-        raise ValueError(f"{what}: expected uint8, got {t.dtype}")
-    return t
-
-
-def _plane16(t, what):
-    """16-bit samples: torch.uint16 or numpy uint16; torch.int16 is taken as the same bit pattern (a view, not a copy)."""
-    t = torch.as_tensor(np.ascontiguousarray(t)) if not torch.is_tensor(t) else t
-    if t.dtype == torch.int16:
+    if dtype == torch.uint16 and t.dtype == torch.int16:
         t = t.view(torch.uint16)
-    if t.dtype != torch.uint16:
-        raise ValueError(f"{what}: expected uint16 (or int16 holding the same bits), got {t.dtype}")
+    if t.dtype != dtype:
+        raise ValueError(f"{what}: expected {'uint8' if dtype == torch.uint8 else 'uint16 (or int16 holding the same bits)'}, got {t.dtype}")
     return t
 
 
@@ -170,26 +156,30 @@ class DecodedFrames(object):
         return cls(_lib.SRC_RGB8, (_rows(t, (t.shape[2], 3)),), mean, std)
 
     @classmethod
-    def nv12(cls, y, uv, mean=CAMVID_MEAN, std=CAMVID_STD, matrix="bt709", full_range=False):
-        """luma uint8 [H,W] / [N,H,W] and chroma uint8 [H/2,W/2,2] / [N,H/2,W/2,2] (Cb, Cr interleaved), H and W even, both on one device."""
+    def _semi_planar(cls, src_format, name, dtype, y, uv, mean, std, matrix, full_range):
         colour = colour_enum(matrix, full_range)
-        y, uv = _plane(y, "DecodedFrames.nv12 luma"), _plane(uv, "DecodedFrames.nv12 chroma")
+        y, uv = _plane(y, f"DecodedFrames.{name} luma", dtype), _plane(uv, f"DecodedFrames.{name} chroma", dtype)
         y, uv = (y.unsqueeze(0) if y.dim() == 2 else y), (uv.unsqueeze(0) if uv.dim() == 3 else uv)
         if y.dim() != 3 or uv.dim() != 4 or 0 in y.shape:
-            raise ValueError(f"DecodedFrames.nv12 expects luma [N,H,W] and chroma [N,H/2,W/2,2], got {tuple(y.shape)} and {tuple(uv.shape)}")
+            raise ValueError(f"DecodedFrames.{name} expects luma [N,H,W] and chroma [N,H/2,W/2,2], got {tuple(y.shape)} and {tuple(uv.shape)}")
         N, H, W = y.shape
         if H % 2 or W % 2:
-            raise ValueError(f"NV12 needs even H and W, got {H}x{W}")
+            raise ValueError(f"{name.upper()} needs even H and W, got {H}x{W}")
         if tuple(uv.shape) != (N, H // 2, W // 2, 2):
             raise ValueError(f"chroma plane of {N} frames {H}x{W} must be {(N, H // 2, W // 2, 2)}, got {tuple(uv.shape)}")
         if y.device != uv.device:
             raise ValueError(f"luma is on {y.device}, chroma on {uv.device}: both planes must be on one device")
-        return cls(_lib.SRC_NV12, (_rows(y, (W,)), _rows(uv, (W // 2, 2))), mean, std, colour)
+        return cls(src_format, (_rows(y, (W,)), _rows(uv, (W // 2, 2))), mean, std, colour)
 
     @classmethod
-    def _planar(cls, src_format, name, plane, y, u, v, mean, std, matrix, full_range):
+    def nv12(cls, y, uv, mean=CAMVID_MEAN, std=CAMVID_STD, matrix="bt709", full_range=False):
+        """luma uint8 [H,W] / [N,H,W] and chroma uint8 [H/2,W/2,2] / [N,H/2,W/2,2] (Cb, Cr interleaved), H and W even, both on one device."""
+        return cls._semi_planar(_lib.SRC_NV12, "nv12", torch.uint8, y, uv, mean, std, matrix, full_range)
+
+    @classmethod
+    def _planar(cls, src_format, name, dtype, y, u, v, mean, std, matrix, full_range):
         colour = colour_enum(matrix, full_range)
-        y, u, v = plane(y, f"DecodedFrames.{name} luma"), plane(u, f"DecodedFrames.{name} Cb"), plane(v, f"DecodedFrames.{name} Cr")
+        y, u, v = _plane(y, f"DecodedFrames.{name} luma", dtype), _plane(u, f"DecodedFrames.{name} Cb", dtype), _plane(v, f"DecodedFrames.{name} Cr", dtype)
         y, u, v = (t.unsqueeze(0) if t.dim() == 2 else t for t in (y, u, v))
         if y.dim() != 3 or u.dim() != 3 or v.dim() != 3 or 0 in y.shape:
             raise ValueError(f"DecodedFrames.{name} expects luma [N,H,W] and Cb, Cr [N,H/2,W/2], got {tuple(y.shape)}, {tuple(u.shape)} and {tuple(v.shape)}")
@@ -207,31 +197,19 @@ class DecodedFrames(object):
     def i420(cls, y, u, v, mean=CAMVID_MEAN, std=CAMVID_STD, matrix="bt709", full_range=False):
         """Planar 8-bit 4:2:0 (yuv420p, what a software HEVC decoder hands over): luma uint8 [H,W] / [N,H,W], Cb and Cr uint8 [H/2,W/2] /
         [N,H/2,W/2], H and W even, all on one device."""
-        return cls._planar(_lib.SRC_I420, "i420", _plane, y, u, v, mean, std, matrix, full_range)
+        return cls._planar(_lib.SRC_I420, "i420", torch.uint8, y, u, v, mean, std, matrix, full_range)
 
     @classmethod
     def i010(cls, y, u, v, mean=CAMVID_MEAN, std=CAMVID_STD, matrix="bt709", full_range=False):
         """Planar 10-bit 4:2:0 (yuv420p10le): the planes of ``i420`` as uint16 (torch.uint16, numpy uint16, or torch.int16 holding the same
         bits), the code in the low 10 bits; the high 6 bits are ignored."""
-        return cls._planar(_lib.SRC_I010, "i010", _plane16, y, u, v, mean, std, matrix, full_range)
+        return cls._planar(_lib.SRC_I010, "i010", torch.uint16, y, u, v, mean, std, matrix, full_range)
 
     @classmethod
     def p010(cls, y, uv, mean=CAMVID_MEAN, std=CAMVID_STD, matrix="bt709", full_range=False):
         """P010 (a hardware decoder's 10-bit output): luma uint16 [H,W] / [N,H,W] and chroma uint16 [H/2,W/2,2] / [N,H/2,W/2,2] (Cb, Cr
         interleaved), the code in the high 10 bits of each word; the low 6 bits are ignored.  uint16 as for ``i010``."""
-        colour = colour_enum(matrix, full_range)
-        y, uv = _plane16(y, "DecodedFrames.p010 luma"), _plane16(uv, "DecodedFrames.p010 chroma")
-        y, uv = (y.unsqueeze(0) if y.dim() == 2 else y), (uv.unsqueeze(0) if uv.dim() == 3 else uv)
-        if y.dim() != 3 or uv.dim() != 4 or 0 in y.shape:
-            raise ValueError(f"DecodedFrames.p010 expects luma [N,H,W] and chroma [N,H/2,W/2,2], got {tuple(y.shape)} and {tuple(uv.shape)}")
-        N, H, W = y.shape
-        if H % 2 or W % 2:
-            raise ValueError(f"P010 needs even H and W, got {H}x{W}")
-        if tuple(uv.shape) != (N, H // 2, W // 2, 2):
-            raise ValueError(f"chroma plane of {N} frames {H}x{W} must be {(N, H // 2, W // 2, 2)}, got {tuple(uv.shape)}")
-        if y.device != uv.device:
-            raise ValueError(f"luma is on {y.device}, chroma on {uv.device}: both planes must be on one device")
-        return cls(_lib.SRC_P010, (_rows(y, (W,)), _rows(uv, (W // 2, 2))), mean, std, colour)
+        return cls._semi_planar(_lib.SRC_P010, "p010", torch.uint16, y, uv, mean, std, matrix, full_range)
 
     # ---- what callers of the float tensor ask of it
     @property
@@ -272,10 +250,7 @@ class DecodedFrames(object):
 
     def to_input(self, h, w, dtype=torch.float32):
         """-> NHWC4 fp32 [N,h,w,4] or NHWC8 fp16 / bf16 [N,h,w,8] on the planes' (GPU) device: one kernel."""
-        if self.src_format in (_lib.SRC_I420, _lib.SRC_P010, _lib.SRC_I010):
-            return ops.frame_ingest_yuv(self.planes, self.src_format, h, w, self.mean, self.std, dtype, self.colour)
-        return ops.frame_ingest8(self.planes[0], self.planes[1] if self.src_format == _lib.SRC_NV12 else None, self.src_format, h, w,
-                                 self.mean, self.std, dtype, self.colour)
+        return ops._frame_ingest_planes(self.planes, self.src_format, h, w, self.mean, self.std, dtype, self.colour)
 
 
 # ----------------------------------------------------------------------------------------------

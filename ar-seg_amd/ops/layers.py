@@ -53,34 +53,60 @@ def _plane_layout(t: torch.Tensor, inner, what: str):
     return pitch * t.element_size(), n_stride * t.element_size()
 
 
+# source format -> (public name = launch label, sample dtype, inner shape of each plane at width W): plane 0 is [N,H,...], the chroma planes [N,H/2,...]
+_SRC_PLANES = {
+    _lib.SRC_RGB8: ("frame_ingest8", torch.uint8, lambda W: ((W, 3),)),
+    _lib.SRC_NV12: ("frame_ingest8", torch.uint8, lambda W: ((W,), (W // 2, 2))),
+    _lib.SRC_I420: ("frame_ingest_yuv", torch.uint8, lambda W: ((W,), (W // 2,), (W // 2,))),
+    _lib.SRC_P010: ("frame_ingest_yuv", torch.uint16, lambda W: ((W,), (W // 2, 2))),
+    _lib.SRC_I010: ("frame_ingest_yuv", torch.uint16, lambda W: ((W,), (W // 2,), (W // 2,))),
+}
+# launch label -> (C entry point, plane arguments it has, what it expects in words)
+_INGEST_ENTRY = {
+    "frame_ingest8": ("arseg_frame_ingest_fwd", 2, "expects uint8 [N,H,W,3] (RGB8) or luma [N,H,W] + chroma [N,H/2,W/2,2] on one device (NV12)"),
+    "frame_ingest_yuv": ("arseg_frame_ingest_yuv_fwd", 3, "expects a luma plane [N,H,W] and its chroma planes on one device"),
+}
+
+
+def _frame_ingest_planes(planes, src_format: int, h: int, w: int, mean, std, dtype: torch.dtype = torch.float32,
+                         colour: int = _lib.COLOUR_BT709_LIMITED, only: Optional[str] = None) -> torch.Tensor:
+    """The planes of any ``src_format`` -> the conv engine's input at (h,w): checks them against _SRC_PLANES and makes the format's one ABI
+    call.  ``only``: the public name asked for, which takes its own formats and no others."""
+    name, sample, inner_at = _SRC_PLANES.get(src_format, (None, None, None))
+    if name is None or only not in (None, name):
+        raise _lib.ArsegError(f"{only or 'frame_ingest'}: unknown source format {src_format}")
+    if dtype != torch.float32 and dtype not in _DT16:
+        raise _lib.ArsegError(f"{name}: unsupported output dtype {dtype}")
+    entry, slots, expects = _INGEST_ENTRY[name]
+    planes, n = tuple(planes), len(inner_at(0))
+    if len(planes) != n or any(not torch.is_tensor(t) for t in planes):
+        raise _lib.ArsegError(f"{name}: expected {n} plane tensors, got {sum(torch.is_tensor(t) for t in planes)}")
+    _need_gpu(*planes, dtype=sample)
+    p0 = planes[0]
+    if p0.dim() != 2 + len(inner_at(0)[0]) or any(t.device != p0.device for t in planes):
+        raise _lib.ArsegError(f"{name} {expects}")
+    N, H, W = p0.shape[:3]
+    inner = inner_at(W)
+    if n > 1 and (H % 2 or W % 2 or any(tuple(t.shape) != (N, H // 2) + i for t, i in zip(planes[1:], inner[1:]))):
+        raise _lib.ArsegError(f"{name}: needs even H, W and chroma planes {[(N, H // 2) + i for i in inner[1:]]}; got {[tuple(t.shape) for t in planes]}")
+    lay = [_plane_layout(t, i, f"{name} plane {k}") for k, (t, i) in enumerate(zip(planes, inner))] + [(0, 0)] * (slots - n)
+    ptrs = [_ptr(t) for t in planes] + [_ptr(None)] * (slots - n)
+    out = torch.empty((N, h, w, 4 if dtype == torch.float32 else 8), dtype=dtype, device=p0.device)
+    m3, s3 = (ctypes.c_float * 3)(*[float(v) for v in mean]), (ctypes.c_float * 3)(*[float(v) for v in std])
+    src_bytes = N * H * W * 3 * p0.element_size() // (1 if n == 1 else 2)
+    launch(name, getattr(_lib.load(), entry), *ptrs, src_format, *[p for p, _ in lay], *[s for _, s in lay], int(colour), _ptr(out),
+           _lib.DT_F32 if dtype == torch.float32 else _DT16[dtype], N, H, W, h, w, m3, s3, _stream(), nbytes=src_bytes + out.numel() * out.element_size())
+    return out
+
+
 def frame_ingest8(plane0: torch.Tensor, plane1: Optional[torch.Tensor], src_format: int, h: int, w: int, mean, std,
                   dtype: torch.dtype = torch.float32, colour: int = _lib.COLOUR_BT709_LIMITED) -> torch.Tensor:
     """8-bit decoder frames -> the conv engine's input at (h,w) in one kernel: NHWC4 fp32, or NHWC8 fp16 / bf16 (csrc/ingest.hip).
     ``src_format`` _lib.SRC_RGB8: plane0 uint8 [N,H,W,3], plane1 None;  _lib.SRC_NV12: plane0 luma uint8 [N,H,W], plane1 chroma uint8
     [N,H/2,W/2,2] (Cb, Cr), ``colour`` one of _lib.COLOUR_*.  Planes may be views with a row pitch and an image stride.  Colour conversion,
     bilinear align_corners=True downscale, ToTensor + Normalize(mean, std): include/arseg_hip.h, arseg_frame_ingest_fwd."""
-    nv12 = src_format == _lib.SRC_NV12
-    if src_format not in (_lib.SRC_RGB8, _lib.SRC_NV12):
-        raise _lib.ArsegError(f"frame_ingest8: unknown source format {src_format}")
-    if dtype != torch.float32 and dtype not in _DT16:
-        raise _lib.ArsegError(f"frame_ingest8: unsupported output dtype {dtype}")
-    _need_gpu(plane0, plane1 if nv12 else None, dtype=torch.uint8)
-    if plane0.dim() != (3 if nv12 else 4) or (nv12 and (plane1 is None or plane1.dim() != 4 or plane1.device != plane0.device)):
-        raise _lib.ArsegError("frame_ingest8 expects uint8 [N,H,W,3] (RGB8) or luma [N,H,W] + chroma [N,H/2,W/2,2] on one device (NV12)")
-    N, H, W = plane0.shape[:3]
-    pitch0, ns0 = _plane_layout(plane0, (W, 3) if not nv12 else (W,), "frame_ingest8 plane 0")
-    pitch1 = ns1 = 0
-    if nv12:
-        if H % 2 or W % 2 or tuple(plane1.shape) != (N, H // 2, W // 2, 2):
-            raise _lib.ArsegError(f"frame_ingest8: NV12 needs even H, W and a chroma plane [N,H/2,W/2,2]; luma {tuple(plane0.shape)}, chroma {tuple(plane1.shape)}")
-        pitch1, ns1 = _plane_layout(plane1, (W // 2, 2), "frame_ingest8 plane 1")
-    out = torch.empty((N, h, w, 4 if dtype == torch.float32 else 8), dtype=dtype, device=plane0.device)
-    m3, s3 = (ctypes.c_float * 3)(*[float(v) for v in mean]), (ctypes.c_float * 3)(*[float(v) for v in std])
-    src_bytes = N * H * W * 3 // (2 if nv12 else 1)
-    launch("frame_ingest8", _lib.load().arseg_frame_ingest_fwd, _ptr(plane0), _ptr(plane1 if nv12 else None), src_format, pitch0, pitch1, ns0, ns1,
-           int(colour), _ptr(out), _lib.DT_F32 if dtype == torch.float32 else _DT16[dtype], N, H, W, h, w, m3, s3, _stream(),
-           nbytes=src_bytes + out.numel() * out.element_size())
-    return out
+    planes = (plane0, plane1) if src_format == _lib.SRC_NV12 else (plane0,)
+    return _frame_ingest_planes(planes, src_format, h, w, mean, std, dtype, colour, only="frame_ingest8")
 
 
 def frame_ingest_yuv(planes, src_format: int, h: int, w: int, mean, std, dtype: torch.dtype = torch.float32,
@@ -89,36 +115,12 @@ def frame_ingest_yuv(planes, src_format: int, h: int, w: int, mean, std, dtype: 
     ``src_format`` _lib.SRC_I420: planes = (Y [N,H,W], Cb [N,H/2,W/2], Cr [N,H/2,W/2]) uint8;  _lib.SRC_I010: the same planes, uint16, code in
     the low 10 bits;  _lib.SRC_P010: planes = (Y [N,H,W], (Cb, Cr) [N,H/2,W/2,2]) uint16, code in the high 10 bits.  Planes may be views with a
     row pitch and an image stride.  include/arseg_hip.h, arseg_frame_ingest_yuv_fwd."""
-    if src_format not in (_lib.SRC_I420, _lib.SRC_P010, _lib.SRC_I010):
-        raise _lib.ArsegError(f"frame_ingest_yuv: unknown source format {src_format}")
-    if dtype != torch.float32 and dtype not in _DT16:
-        raise _lib.ArsegError(f"frame_ingest_yuv: unsupported output dtype {dtype}")
-    planar = src_format != _lib.SRC_P010
-    planes = tuple(planes)
-    if len(planes) != (3 if planar else 2) or any(not torch.is_tensor(t) for t in planes):
-        raise _lib.ArsegError(f"frame_ingest_yuv: expected {3 if planar else 2} plane tensors, got {len(planes)}")
-    _need_gpu(*planes, dtype=torch.uint8 if src_format == _lib.SRC_I420 else torch.uint16)
-    y = planes[0]
-    if y.dim() != 3 or any(t.device != y.device for t in planes):
-        raise _lib.ArsegError("frame_ingest_yuv expects a luma plane [N,H,W] and its chroma planes on one device")
-    N, H, W = y.shape
-    inner = (W // 2,) if planar else (W // 2, 2)
-    if H % 2 or W % 2 or any(tuple(t.shape) != (N, H // 2) + inner for t in planes[1:]):
-        raise _lib.ArsegError(f"frame_ingest_yuv: needs even H, W and chroma planes {(N, H // 2) + inner}; got {[tuple(t.shape) for t in planes]}")
-    lay = [_plane_layout(y, (W,), "frame_ingest_yuv plane 0")] + [_plane_layout(t, inner, f"frame_ingest_yuv plane {i + 1}") for i, t in enumerate(planes[1:])]
-    lay += [(0, 0)] * (3 - len(lay))
-    out = torch.empty((N, h, w, 4 if dtype == torch.float32 else 8), dtype=dtype, device=y.device)
-    m3, s3 = (ctypes.c_float * 3)(*[float(v) for v in mean]), (ctypes.c_float * 3)(*[float(v) for v in std])
-    src_bytes = N * H * W * 3 // 2 * y.element_size()
-    launch("frame_ingest_yuv", _lib.load().arseg_frame_ingest_yuv_fwd, _ptr(y), _ptr(planes[1]), _ptr(planes[2] if planar else None), src_format,
-           lay[0][0], lay[1][0], lay[2][0], lay[0][1], lay[1][1], lay[2][1], int(colour), _ptr(out),
-           _lib.DT_F32 if dtype == torch.float32 else _DT16[dtype], N, H, W, h, w, m3, s3, _stream(), nbytes=src_bytes + out.numel() * out.element_size())
-    return out
+    return _frame_ingest_planes(planes, src_format, h, w, mean, std, dtype, colour, only="frame_ingest_yuv")
 
 
 def ingest_input(frames, h: int, w: int, dtype: torch.dtype = torch.float32) -> torch.Tensor:
     """The one door through which the fast paths take frames: a float NCHW tensor (``frame_ingest``, unchanged) or 8-bit decoder output
-    (``arseg_amd.ingest.DecodedFrames``: its ``to_input`` runs ``frame_ingest8`` / ``frame_ingest_yuv``) -> the conv engine's input at (h,w)."""
+    (``arseg_amd.ingest.DecodedFrames``: its ``to_input`` runs ``_frame_ingest_planes``) -> the conv engine's input at (h,w)."""
     if torch.is_tensor(frames):
         return frame_ingest(frames, h, w, dtype)
     to_input = getattr(frames, "to_input", None)

@@ -439,7 +439,8 @@ int arseg_frame_u8_to_nhwc4_fwd(const uint8_t *img_hwc, float *out, int N, int H
  *         ARSEG_COLOUR_BT709_FULL       1         1.5748    0.187324  0.468124  1.8556
  *     each component clipped to [0, 255], not rounded to an integer.  (3) the taps are blended, then (v / 255 - mean[c]) / std[c]
  * (evaluated as one fma with 1 / (255 std) and -mean / std formed in double; within 2 ulp of the two divisions).  16-bit outputs are
- * rounded once, at the store (to nearest even).
+ * rounded once, at the store (to nearest even).  One kernel family serves this entry point and arseg_frame_ingest_yuv_fwd; apart from that
+ * fma and the tap weight's, no multiply is fused with an add, so the fp32 result does not depend on the format, the route or the output type.
  * ARSEG_EINVAL: a null pointer (plane1 only with NV12), a non-positive size, a zero std, odd H or W with NV12, a pitch smaller than a
  * row, a negative image stride, an unknown src_format / out_dtype / colour (colour with NV12 only), `out` not 16-byte aligned. */
 enum arseg_src_format { ARSEG_SRC_RGB8 = 0, ARSEG_SRC_NV12 = 1, ARSEG_SRC_I420 = 2, ARSEG_SRC_P010 = 3, ARSEG_SRC_I010 = 4 };     /* 2..4: arseg_frame_ingest_yuv_fwd */
@@ -466,7 +467,7 @@ int arseg_frame_ingest_fwd(const void *plane0, const void *plane1, int src_forma
  *       full range (H.273):  Y8 = code_Y 255 / (2^n - 1),   C8 - 128 = (C - 2^(n-1)) 255 / (2^n - 1)   (the factor formed in double, rounded
  *                                                                                                     to fp32 once; 1 for n = 8)
  * then the matrix of `colour` on (Y8 - y0, C8b - 128, C8r - 128) as above, each component clipped to [0, 255], not rounded.  For equal
- * sample values the three formats give the same fp32 bits.  BT.2020, 12-bit, 4:2:2 and 4:4:4 sources are not covered.
+ * sample values the three formats, and NV12 through arseg_frame_ingest_fwd, give the same fp32 bits.  BT.2020, 12-bit, 4:2:2 and 4:4:4 sources are not covered.
  * ARSEG_EINVAL: a null pointer (plane2 with the planar formats only), a non-positive size, odd H or W, a pitch smaller than a row, a
  * negative image stride, an odd pointer / pitch / image stride of a 16-bit plane, a zero std, an unknown src_format / out_dtype / colour,
  * `out` not 16-byte aligned. */

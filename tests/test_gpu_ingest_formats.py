@@ -57,7 +57,7 @@ def test_rgb8_fp32_equals_existing_u8_ingest(dev, H, W, h, w, pad):
 @pytest.mark.parametrize("H,W,h,w", [(64, 1200, 32, 600), (36, 48, 18, 24), (35, 47, 17, 23), (20, 32, 20, 32)])
 def test_16bit_equals_rounded_fp32(dev, dtype, src, H, W, h, w):
     """fp16 / bf16 NHWC8 output == the fp32 output rounded to the storage type, by the rule of test_frame_ingest_16bit_equals_rounded_fp32
-    (tests/test_gpu_16bit.py): within one unit of the storage type everywhere (hipcc contracts the blend per kernel instantiation), the same
+    (tests/test_gpu_16bit.py): within one unit of the storage type everywhere (contraction is off in csrc/ingest.hip: the output types share their arithmetic up to the store), the same
     rounding nearly always (< 1e-3 of the elements differ), padding channels exactly 0."""
     from arseg_amd import ingest
 
