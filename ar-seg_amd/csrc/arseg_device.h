@@ -92,16 +92,108 @@ __device__ __forceinline__ double uniform_f64(double x) {
     return __builtin_bit_cast(double, ((unsigned long long)hi << 32) | lo);
 }
 
+// ------------------------------------------------------------------ byte spans of the 8-bit output planes (egress.hip, confidence.hip)
+typedef unsigned u32x2_a4 __attribute__((ext_vector_type(2), aligned(4)));
+
+// NB consecutive bytes <-> NB values, with the widest accesses the address allows: 8 / 4 bytes on a 4-byte aligned address, 2 bytes on an
+// even one, single bytes otherwise.  Exactly the NB bytes are touched: nothing past a row's last sample is read or written.
+template <int NB>
+__device__ __forceinline__ void span_load(const uint8_t *g, unsigned (&v)[NB]) {
+    const unsigned al = (unsigned)reinterpret_cast<uintptr_t>(g);
+    if (NB % 4 == 0 && !(al & 3u)) {
+#pragma unroll
+        for (int q = 0; q < NB / 4; q += 2) {
+            unsigned x0, x1 = 0;
+            if (q + 1 < NB / 4) { const u32x2_a4 x = *reinterpret_cast<const u32x2_a4 *>(g + 4 * q); x0 = x.x; x1 = x.y; }
+            else x0 = *reinterpret_cast<const unsigned *>(g + 4 * q);
+#pragma unroll
+            for (int b = 0; b < 4; ++b) {
+                v[4 * q + b] = (x0 >> (8 * b)) & 0xffu;
+                if (q + 1 < NB / 4) v[(4 * q + 4 < NB ? 4 * q + 4 : 0) + b] = (x1 >> (8 * b)) & 0xffu;
+            }
+        }
+    } else if (NB % 2 == 0 && !(al & 1u)) {
+#pragma unroll
+        for (int q = 0; q < NB / 2; ++q) {
+            const unsigned x = *reinterpret_cast<const uint16_t *>(g + 2 * q);
+            v[2 * q] = x & 0xffu; v[2 * q + 1] = x >> 8;
+        }
+    } else {
+#pragma unroll
+        for (int q = 0; q < NB; ++q) v[q] = g[q];
+    }
+}
+template <int NB>
+__device__ __forceinline__ void span_store(uint8_t *g, const unsigned (&v)[NB]) {
+    const unsigned al = (unsigned)reinterpret_cast<uintptr_t>(g);
+    if (NB % 4 == 0 && !(al & 3u)) {
+#pragma unroll
+        for (int q = 0; q < NB / 4; q += 2) {
+            const unsigned x0 = v[4 * q] | (v[4 * q + 1] << 8) | (v[4 * q + 2] << 16) | (v[4 * q + 3] << 24);
+            if (q + 1 < NB / 4) {
+                const int o = 4 * q + 4 < NB ? 4 * q + 4 : 0;
+                const unsigned x1 = v[o] | (v[o + 1] << 8) | (v[o + 2] << 16) | (v[o + 3] << 24);
+                *reinterpret_cast<u32x2_a4 *>(g + 4 * q) = u32x2_a4{x0, x1};
+            } else {
+                *reinterpret_cast<unsigned *>(g + 4 * q) = x0;
+            }
+        }
+    } else if (NB % 2 == 0 && !(al & 1u)) {
+#pragma unroll
+        for (int q = 0; q < NB / 2; ++q) *reinterpret_cast<uint16_t *>(g + 2 * q) = (uint16_t)(v[2 * q] | (v[2 * q + 1] << 8));
+    } else {
+#pragma unroll
+        for (int q = 0; q < NB; ++q) g[q] = (uint8_t)v[q];
+    }
+}
+
 // ------------------------------------------------------------------ the label rule of the evaluator tail and of the egress kernels
 // logits NCHW [N,n_cls,h,w] -> the class of one output pixel after the bilinear resize to H x W.  THE one definition: the evaluator tail
 // (layers.hip: argmax_pixel / argmax_run, ungrouped and grouped) and the egress kernels (egress.hip) call these, so their labels agree bit for
 // bit.  torch.argmax semantics: the first maximum wins, a NaN counts as the maximum (the first NaN wins).  Branch free (the short-circuit
 // form compiles to a divergent branch per pixel and class).
+//
+// Accumulators.  With an accumulator type other than ArsegNoAcc (the default: the tail and egress, nothing is instantiated for it) the rule
+// hands every blended class value v_k to *acc, together with the running best before it and the rule's decision: acc->step(r, v, best,
+// take) for pixel r of the thread, in class order, BEFORE best / bi are updated.  The accumulator only looks on: the operations that decide
+// k* are the same with or without it.
+
+struct ArsegNoAcc {};
+template <class Acc> constexpr bool arseg_has_acc = !__is_same(Acc, ArsegNoAcc);
+
+// The softmax of a pixel's blended class values in one pass over the classes (include/arseg_hip.h, arseg_segment_confidence_fwd): running
+// maximum m (the rule's own best), Z = sum_k exp(v_k - m) rescaled whenever the maximum moves -- one exp per class either way, since
+// exp(-|v - m|) is the rescale factor when v is the new maximum and the new term when it is not -- and the largest value over k != k*.
+// A NaN value makes Z NaN for good; infinite maxima are caught in code().  S pixels per thread, no per-class array.
+template <int S>
+struct ArsegSoftmaxAcc {
+    float m[S], Z[S], sec[S];
+    __device__ __forceinline__ ArsegSoftmaxAcc() {
+#pragma unroll
+        for (int r = 0; r < S; ++r) { m[r] = -INFINITY; Z[r] = 0.f; sec[r] = -INFINITY; }
+    }
+    __device__ __forceinline__ void step(int r, float v, float best, bool take) {
+        const float e = v == best ? 1.f : __expf(-fabsf(v - best));          // (equal infinities: their difference would be NaN)
+        Z[r] = take ? fmaf(Z[r], e, 1.f) : Z[r] + e;
+        sec[r] = take ? best : fmaxf(sec[r], v);
+        m[r] = take ? v : m[r];
+    }
+    // the 8-bit code of pixel r: q = floor(255 c + 0.5), c = p1 = 1 / Z or the margin p1 - p2 = (1 - exp(v_second - m)) / Z; a NaN c
+    // (NaN value, +inf maximum, all -inf) -> 0
+    __device__ __forceinline__ unsigned code(int r, bool margin) const {
+        float c = __builtin_amdgcn_rcpf(Z[r]);
+        if (margin) c *= 1.f - __expf(sec[r] - m[r]);
+        c = fabsf(m[r]) == INFINITY ? NAN : c;
+        const float q = floorf(fmaf(255.f, c, 0.5f));
+        return q == q ? (unsigned)fminf(q, 255.f) : 0u;
+    }
+};
 
 // One output pixel (ox, oy) of frame n on the per-pixel route: `same` (h == H && w == W) reads the logit itself, otherwise the four bilinear
 // taps of arseg_src_index (sy / sx = arseg_resize_scale of the two axes, either align_corners).
+template <class Acc = ArsegNoAcc>
 __device__ __forceinline__ int arseg_label_pixel(const float *__restrict__ logits, int n, int oy, int ox, int n_cls, int h, int w, int align, bool same,
-                                                 float sy, float sx) {
+                                                 float sy, float sx, Acc *acc = nullptr) {
     int y0 = oy, y1 = oy, x0 = ox, x1 = ox; float ly = 0.f, lx = 0.f;
     if (!same) {
         arseg_src_index(sy, oy, align != 0, h, y0, y1, ly);
@@ -116,6 +208,7 @@ __device__ __forceinline__ int arseg_label_pixel(const float *__restrict__ logit
         else v = (1.f - ly) * ((1.f - lx) * b[(size_t)y0 * w + x0] + lx * b[(size_t)y0 * w + x1]) +
                  ly * ((1.f - lx) * b[(size_t)y1 * w + x0] + lx * b[(size_t)y1 * w + x1]);
         const bool isn = v != v, take = !best_nan & ((v > best) | isn);
+        if constexpr (arseg_has_acc<Acc>) acc->step(0, v, best, take);
         best = take ? v : best; bi = take ? k : bi; best_nan = best_nan | (take & isn);
     }
     return bi;
@@ -127,8 +220,9 @@ __device__ __forceinline__ int arseg_label_pixel(const float *__restrict__ logit
 // loaded once per class and the S pixels evaluated from registers -- 4 loads per class and run instead of 4 S.  Same taps and weights as
 // arseg_label_pixel (arseg_src_index, sc = 1 / S); the blend is regrouped (see below), so a label may differ from the per-pixel form where
 // the top two logits are within fp32 rounding of each other: a caller picks the route by shape, never per pixel.
-template <int S>
-__device__ __forceinline__ void arseg_label_run(const float *__restrict__ logits, float sc, int n, int oy, int j, int n_cls, int h, int w, int (&bi)[S]) {
+template <int S, class Acc = ArsegNoAcc>
+__device__ __forceinline__ void arseg_label_run(const float *__restrict__ logits, float sc, int n, int oy, int j, int n_cls, int h, int w, int (&bi)[S],
+                                                Acc *acc = nullptr) {
     const int W = S * w;
     int y0, y1; float ly;
     arseg_src_index(sc, oy, false, h, y0, y1, ly);
@@ -172,6 +266,7 @@ __device__ __forceinline__ void arseg_label_run(const float *__restrict__ logits
             for (int r = 0; r < S; ++r) {
                 const float v = fmaf(lx[r], b, a);
                 const bool isn = v != v, take = !bn[r] & ((v > best[r]) | isn);
+                if constexpr (arseg_has_acc<Acc>) acc->step(r, v, best[r], take);
                 best[r] = take ? v : best[r];
                 bi[r] = take ? k0 + u : bi[r];
                 bn[r] = bn[r] | (take & isn);

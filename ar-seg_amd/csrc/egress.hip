@@ -9,7 +9,7 @@
 // whole 2 x 2 luma blocks with their chroma sample -- one block (per-pixel routes), the S/2 blocks under a run on two rows (x4, x8: a run
 // starts at S j + S/2, an even column), or for x2, whose runs start at odd columns, the aligned block [2c, 2c+2) with each pixel evaluated
 // by its own run (c-1 for the left column, c for the right one: the formula is arseg_label_run's, unchanged).
-// Stores are assembled per thread into 2- to 8-byte accesses where the address allows it (span_store); a byte per lane only on planes whose
+// Stores are assembled per thread into 2- to 8-byte accesses where the address allows it (span_store, arseg_device.h); a byte per lane only on planes whose
 // pointers or pitches are odd, or where a lane owns a single sample.
 #include "arseg_device.h"
 
@@ -27,60 +27,6 @@ struct EgressP {
     unsigned tab[32];                 // per class: P[k][0] | P[k][1] << 8 | P[k][2] << 16 | (lut ? lut[k] : k) << 24
     unsigned short wt[32];            // per class: a_k, 0 .. 256
 };
-
-typedef unsigned u32x2_a4 __attribute__((ext_vector_type(2), aligned(4)));
-
-// NB consecutive bytes <-> NB values, with the widest accesses the address allows: 8 / 4 bytes on a 4-byte aligned address, 2 bytes on an
-// even one, single bytes otherwise.  Exactly the NB bytes are touched: nothing past a row's last sample is read or written.
-template <int NB>
-__device__ __forceinline__ void span_load(const uint8_t *g, unsigned (&v)[NB]) {
-    const unsigned al = (unsigned)reinterpret_cast<uintptr_t>(g);
-    if (NB % 4 == 0 && !(al & 3u)) {
-#pragma unroll
-        for (int q = 0; q < NB / 4; q += 2) {
-            unsigned x0, x1 = 0;
-            if (q + 1 < NB / 4) { const u32x2_a4 x = *reinterpret_cast<const u32x2_a4 *>(g + 4 * q); x0 = x.x; x1 = x.y; }
-            else x0 = *reinterpret_cast<const unsigned *>(g + 4 * q);
-#pragma unroll
-            for (int b = 0; b < 4; ++b) {
-                v[4 * q + b] = (x0 >> (8 * b)) & 0xffu;
-                if (q + 1 < NB / 4) v[(4 * q + 4 < NB ? 4 * q + 4 : 0) + b] = (x1 >> (8 * b)) & 0xffu;
-            }
-        }
-    } else if (NB % 2 == 0 && !(al & 1u)) {
-#pragma unroll
-        for (int q = 0; q < NB / 2; ++q) {
-            const unsigned x = *reinterpret_cast<const uint16_t *>(g + 2 * q);
-            v[2 * q] = x & 0xffu; v[2 * q + 1] = x >> 8;
-        }
-    } else {
-#pragma unroll
-        for (int q = 0; q < NB; ++q) v[q] = g[q];
-    }
-}
-template <int NB>
-__device__ __forceinline__ void span_store(uint8_t *g, const unsigned (&v)[NB]) {
-    const unsigned al = (unsigned)reinterpret_cast<uintptr_t>(g);
-    if (NB % 4 == 0 && !(al & 3u)) {
-#pragma unroll
-        for (int q = 0; q < NB / 4; q += 2) {
-            const unsigned x0 = v[4 * q] | (v[4 * q + 1] << 8) | (v[4 * q + 2] << 16) | (v[4 * q + 3] << 24);
-            if (q + 1 < NB / 4) {
-                const int o = 4 * q + 4 < NB ? 4 * q + 4 : 0;
-                const unsigned x1 = v[o] | (v[o + 1] << 8) | (v[o + 2] << 16) | (v[o + 3] << 24);
-                *reinterpret_cast<u32x2_a4 *>(g + 4 * q) = u32x2_a4{x0, x1};
-            } else {
-                *reinterpret_cast<unsigned *>(g + 4 * q) = x0;
-            }
-        }
-    } else if (NB % 2 == 0 && !(al & 1u)) {
-#pragma unroll
-        for (int q = 0; q < NB / 2; ++q) *reinterpret_cast<uint16_t *>(g + 2 * q) = (uint16_t)(v[2 * q] | (v[2 * q + 1] << 8));
-    } else {
-#pragma unroll
-        for (int q = 0; q < NB; ++q) g[q] = (uint8_t)v[q];
-    }
-}
 
 __device__ __forceinline__ unsigned blend8(unsigned src, unsigned code, unsigned a) { return (src * (256u - a) + code * a + 128u) >> 8; }
 

@@ -4,7 +4,12 @@
 * ``overlay``: the frame with the classes painted over it, in the plane format the decoder delivered (``ingest.DecodedFrames``: RGB8, NV12 or
   I420) -- the input of a display or a hardware encoder.  ``out=frames`` paints in place.
 
-Both are one launch of ``ops.segment_egress`` (csrc/egress.hip): the bilinear resize and the argmax are the evaluator tail's own, so the
+* ``confidence``: how much to trust the mask -- an 8-bit plane of the softmax's top-1 probability (or its margin over the runner-up) per
+  pixel, the label plane next to it and per-frame statistics (sum of the codes, uncertain pixels, pixels per class), one launch of
+  ``ops.segment_confidence`` (csrc/confidence.hip) and one pass over the logits; ``DriftMonitor`` turns the statistics into "refresh the
+  keyframe" reports on a stream without ground truth.
+
+``labels8`` and ``overlay`` are one launch of ``ops.segment_egress`` (csrc/egress.hip): the bilinear resize and the argmax are the evaluator tail's own, so the
 labels equal ``ops.argmax_confusion``'s ``pred`` bit for bit, and neither int32 labels nor a float frame are ever written.  The painting is
 integer arithmetic, written out in include/arseg_hip.h (arseg_segment_egress_fwd).  Not covered: 10-bit, 4:2:2 or 4:4:4 destinations, text,
 legends or contours, the encoder itself.
@@ -101,3 +106,56 @@ def overlay(logits, frames, palette, out=None, labels_out=None, lut=None, align_
     if out is not frames and (out.colour, out.mean, out.std) != (frames.colour, frames.mean, frames.std):
         out = frames._with(out.planes)
     return out, labels_out
+
+
+def confidence(logits, H, W, kind="top1", low=128, out=None, labels_out=None, lut=None, stats=None, align_corners=True):
+    """Head logits [N,n_cls,h,w] -> (conf8 uint8 [N,H,W], labels8 | None, stats | None), one launch and one pass over the logits.
+
+    ``conf8`` = ``floor(255 c + 0.5)`` per output pixel, c from the fp32 softmax over the classes of the resized logits (the resize and the
+    class k* are ``ops.argmax_confusion``'s): ``kind="top1"`` the probability of k*, ``kind="margin"`` that minus the runner-up's; 0 where c
+    is NaN (a NaN logit, a +inf maximum, all classes -inf).  Log-probability outputs give the same codes (softmax of a log-softmax).
+    ``out``: the caller's plane (default freshly allocated).  ``labels_out``: a uint8 [N,H,W] buffer, or True to have one allocated; None =
+    no label plane; values as ``labels8`` (through ``lut`` when given).  ``stats``: an int64 [N, _lib.CONF_NSTATS] tensor to accumulate
+    into, or True for a zeroed one; None = no statistics.  Row n: [0] += sum of the frame's codes, [1] += pixels with a code below ``low``
+    (0..256), [2 + k] += pixels of class k (not mapped through ``lut``) -- integers, so two runs are bit-equal; ``DriftMonitor`` reads rows
+    of it.  Everything is included in the one launch; with ``out``, ``labels_out`` and ``stats`` given nothing is allocated."""
+    logits = _check_logits(logits)
+    N = logits.shape[0]
+    if out is None:
+        out = torch.empty((N, int(H), int(W)), dtype=torch.uint8, device=logits.device)
+    if labels_out is True:
+        labels_out = torch.empty((N, int(H), int(W)), dtype=torch.uint8, device=logits.device)
+    if stats is True:
+        stats = torch.zeros((N, _lib.CONF_NSTATS), dtype=torch.int64, device=logits.device)
+    ops.segment_confidence(logits, H, W, kind=kind, low=low, align_corners=align_corners, lut=lut, conf_out=out, labels_out=labels_out, stats=stats)
+    return out, labels_out, stats
+
+
+class DriftMonitor(object):
+    """Reports when a stream's confidence says the keyframe should be refreshed early (after a scene cut, or when the motion chain has
+    drifted).  Pure Python on rows of ``confidence``'s ``stats`` (a tensor row, an array or a list: [sum of codes, low pixels, ...]); it only
+    reports -- acting on the report (the keyframe schedule) is the caller's.
+
+    ``rel_drop``: report when a frame's mean code has fallen below ``rel_drop`` x the mean code of the last keyframe (0 < rel_drop <= 1).
+    ``low_share``: report when more than this share of the frame's pixels has a code below the ``low`` the statistics were taken with
+    (0 <= low_share <= 1).  Both are required: neither has a value that is right for every network, dataset and ``kind``; they are the
+    caller's to calibrate on its own streams (e.g. against ``EvalByDistance``'s table where labels exist)."""
+
+    def __init__(self, rel_drop, low_share):
+        self.rel_drop, self.low_share = float(rel_drop), float(low_share)
+        if not 0.0 < self.rel_drop <= 1.0 or not 0.0 <= self.low_share <= 1.0:
+            raise ValueError(f"DriftMonitor: rel_drop in (0, 1] and low_share in [0, 1], got {rel_drop!r}, {low_share!r}")
+        self.key_mean = None          # mean code of the last keyframe
+
+    def update(self, stats_row, n_pixels, is_keyframe) -> bool:
+        """One frame: ``stats_row`` its row of statistics, ``n_pixels`` = H x W.  A keyframe resets the baseline first (and is itself only
+        held to ``low_share``).  True = refresh the keyframe.  Before the first keyframe only ``low_share`` is applied."""
+        n_pixels = int(n_pixels)
+        if n_pixels <= 0:
+            raise ValueError(f"DriftMonitor.update: n_pixels must be positive, got {n_pixels}")
+        total, low = int(stats_row[0]), int(stats_row[1])
+        mean = total / n_pixels
+        if is_keyframe:
+            self.key_mean = mean
+        dropped = self.key_mean is not None and mean < self.rel_drop * self.key_mean
+        return bool(dropped or low / n_pixels > self.low_share)

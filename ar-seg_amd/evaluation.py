@@ -403,3 +403,25 @@ def alter_res_batch_render(lr_net, ref_ps, imgs, mv_qs, scale=0.5, palette=None,
     painted, labels = egress.overlay(lo, imgs, palette, out=out, labels_out=True if labels_out is None else labels_out, lut=lut,
                                      align_corners=not fused_up)
     return labels, painted
+
+
+def alter_res_batch_confidence(lr_net, ref_ps, imgs, mv_qs, scale=0.5, kind="top1", low=128, lut=None, out=None, labels_out=True, stats=True):
+    """``alter_res_batch_render``'s sibling for the online quality signal: the same phase 1 and phase 2 and the same route decision
+    (BiSeNet's 1/8-resolution head logits with align_corners=False when the frame is exactly 8x the head, align_corners=True otherwise),
+    then ``egress.confidence`` instead of the egress launch -> (conf8 uint8 [B,H,W], labels uint8 [B,H,W] | None, stats int64
+    [B, CONF_NSTATS] | None).  The labels equal ``alter_res_batch_render``'s; ``kind``, ``low``, ``lut``, ``out``, ``labels_out`` and
+    ``stats`` as ``egress.confidence`` takes them (True: allocated here, a tensor: the caller's, None: not wanted).  Feed the rows of
+    ``stats`` to an ``egress.DriftMonitor``."""
+    from . import egress
+    lr_net = _unwrap(lr_net)
+    B, _, H, W = imgs.shape
+    h, w = _downscale_hw(H, W, scale)
+    feat = lr_net.phase1_nhwc4(ops.ingest_input(imgs, h, w, lr_net.storage_dtype), aux=ops.config.aux_outputs)[-1]
+    fused_up = hasattr(lr_net, "out_upsample")
+    if fused_up:
+        lo, _ = lr_net.phase2_warp(feat, list(ref_ps), mv_qs, upsample=False)
+        if (8 * lo.shape[-2], 8 * lo.shape[-1]) != (H, W):
+            lo, fused_up = ops.resize_nchw(lo, 8 * lo.shape[-2], 8 * lo.shape[-1], _lib.BILINEAR, False), False
+    else:
+        lo, _ = lr_net.phase2_warp(feat, list(ref_ps), mv_qs)
+    return egress.confidence(lo, H, W, kind=kind, low=low, out=out, labels_out=labels_out, lut=lut, stats=stats, align_corners=not fused_up)

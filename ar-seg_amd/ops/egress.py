@@ -1,5 +1,6 @@
 """The output half of the pipeline: head logits -> an 8-bit label plane and / or the frame with the classes painted over it, one ABI call
-(include/arseg_hip.h, arseg_segment_egress_fwd; csrc/egress.hip)."""
+(include/arseg_hip.h, arseg_segment_egress_fwd; csrc/egress.hip); head logits -> an 8-bit confidence plane, the label plane and per-frame
+statistics, one ABI call (arseg_segment_confidence_fwd; csrc/confidence.hip)."""
 from __future__ import annotations
 
 import ctypes
@@ -91,3 +92,50 @@ def segment_egress(logits: torch.Tensor, H: int, W: int, *, align_corners: bool 
            _ptr(dp3[0][0]), _ptr(dp3[1][0]), _ptr(dp3[2][0]), dp3[0][1], dp3[1][1], dp3[2][1], dp3[0][2], dp3[1][2], dp3[2][2],
            pal_c, wt_c, _stream(), nbytes=logits.numel() * 4 + plane_bytes + (N * H * W if labels_out is not None else 0))
     return labels_out, dst
+
+
+_CONF_KINDS = {"top1": _lib.CONF_TOP1, "margin": _lib.CONF_MARGIN}
+
+
+def segment_confidence(logits: torch.Tensor, H: int, W: int, *, kind: str = "top1", low: int = 128, align_corners: bool = True, lut=None,
+                       conf_out: Optional[torch.Tensor] = None, labels_out: Optional[torch.Tensor] = None, stats: Optional[torch.Tensor] = None):
+    """Head logits fp32 [N,n_cls,h,w] -> any non-empty subset of: the confidence plane ``conf_out`` (uint8 [N,H,W], rows contiguous, any row
+    pitch / image stride; ``floor(255 c + 0.5)`` with c the softmax's top-1 probability of the resized logits, ``kind="top1"``, or its margin
+    over the runner-up, ``kind="margin"``; 0 where c is NaN), the label plane ``labels_out`` (as ``segment_egress``: ``lut[k]`` or ``k``, ``k``
+    = ``argmax_confusion``'s pred bit for bit) and ``stats`` (int64 [N, CONF_NSTATS], contiguous, ACCUMULATED INTO: per frame the sum of the
+    codes, the number of pixels with a code below ``low`` (0..256), and the pixels per class from column 2 on), in one launch and one pass
+    over the logits.  Allocates nothing: every output is the caller's, so the call can be captured in a HIP graph.
+    Returns (conf_out, labels_out, stats)."""
+    _need_gpu(logits)
+    if logits.dim() != 4 or not logits.is_contiguous():
+        raise _lib.ArsegError(f"segment_confidence expects contiguous fp32 logits [N,n_cls,h,w], got {tuple(logits.shape)}")
+    N, n_cls, h, w = logits.shape
+    H, W = int(H), int(W)
+    if conf_out is None and labels_out is None and stats is None:
+        raise ValueError("segment_confidence: nothing to write (conf_out, labels_out and stats are all None)")
+    if not 1 <= n_cls <= 32:
+        raise ValueError(f"segment_confidence: 1..32 classes, got {n_cls}")
+    if kind not in _CONF_KINDS:
+        raise ValueError(f"segment_confidence: kind is 'top1' or 'margin', got {kind!r}")
+    low = int(low)
+    if not 0 <= low <= 256:
+        raise ValueError(f"segment_confidence: low is a code threshold in 0..256, got {low}")
+    layout = {}
+    for name, t in (("conf_out", conf_out), ("labels_out", labels_out)):
+        layout[name] = (0, 0)
+        if t is not None:
+            _need_gpu(t, dtype=torch.uint8)
+            if tuple(t.shape) != (N, H, W) or t.device != logits.device:
+                raise ValueError(f"{name} must be uint8 {(N, H, W)} on {logits.device}, got {tuple(t.shape)} on {t.device}")
+            layout[name] = _plane_layout(t, (W,), f"segment_confidence {name}")
+    if stats is not None:
+        _need_gpu(stats, dtype=torch.int64)
+        if tuple(stats.shape) != (N, _lib.CONF_NSTATS) or not stats.is_contiguous() or stats.device != logits.device:
+            raise _lib.ArsegError(f"stats must be a contiguous int64 {(N, _lib.CONF_NSTATS)} tensor on {logits.device}, got {tuple(stats.shape)} "
+                                  f"strides {stats.stride()} on {stats.device}")
+    lut_c = None if lut is None else _host_u8(lut, n_cls, "lut")
+    planes = (conf_out is not None) + (labels_out is not None)
+    launch("segment_confidence", _lib.load().arseg_segment_confidence_fwd, _ptr(logits), N, n_cls, h, w, H, W, 1 if align_corners else 0,
+           _CONF_KINDS[kind], low, lut_c, _ptr(conf_out), layout["conf_out"][0], layout["conf_out"][1], _ptr(labels_out), layout["labels_out"][0],
+           layout["labels_out"][1], _ptr(stats), _stream(), nbytes=logits.numel() * 4 + planes * N * H * W)
+    return conf_out, labels_out, stats

@@ -663,6 +663,42 @@ int arseg_segment_egress_fwd(const float *logits, int N, int n_cls, int h, int w
                              const uint8_t *palette, const uint16_t *weights, arseg_stream_t stream);
 
 /* ---------------------------------------------------------------------------------------------
+ * Segmentation confidence (csrc/confidence.hip): head logits -> how much to trust each pixel and each frame, in one launch for N frames and
+ * one pass over the logits, without probabilities or any other float frame-sized tensor in between.  The online signal of a stream without
+ * ground truth: the softmax's top-1 probability per output pixel, its sum over the frame and the number of uncertain pixels.
+ *   logits, N, n_cls, h, w, H, W, align_corners: as arseg_argmax_confusion_fwd and arseg_segment_egress_fwd, with their route choice (h == H
+ *               && w == W; per-pixel bilinear, either align_corners; the x2 / x4 / x8 align_corners == 0 run route with its regrouped blend).
+ *               The blended class values v_k of an output pixel and its class k* are those of the one label rule (csrc/arseg_device.h): k* is
+ *               EXACTLY what arseg_argmax_confusion_fwd writes into pred for the same arguments (first maximum wins, NaN counts as maximum).
+ *   per pixel   m = max_k v_k, Z = sum_k exp(v_k - m) in fp32 (one pass over the classes: running maximum, rescaled sum);
+ *               p1 = 1 / Z;  p2 = exp(v_second - m) / Z, v_second the largest value over k != k* (p2 = 0 for n_cls == 1).
+ *               softmax(log_softmax(x)) = softmax(x): log-probability outputs need no special case.
+ *   kind        enum arseg_conf_kind: ARSEG_CONF_TOP1 c = p1;  ARSEG_CONF_MARGIN c = p1 - p2
+ *   code        q = (uint8) floor(255 c + 0.5), never above 255; a pixel whose c is NaN (a NaN logit, a +inf maximum, all classes -inf)
+ *               gets q = 0
+ * Outputs, any non-empty subset (NULL = not wanted):
+ *   conf8       uint8 [N][H][W] of q, conf_pitch bytes from row to row (>= W), conf_n_stride bytes from image to image (>= 0); nothing past
+ *               a row's last sample is written
+ *   labels8     uint8 [N][H][W], labels_pitch / labels_n_stride alike; value = lut ? lut[k*] : k*.  lut: HOST pointer to n_cls bytes, NULL =
+ *               identity (as in arseg_segment_egress_fwd)
+ *   stats       int64 [N][ARSEG_CONF_NSTATS] on the device, ACCUMULATED INTO (like hist); for frame n
+ *                 stats[n][0]     += sum of q over the frame
+ *                 stats[n][1]     += number of pixels with q < low (low: 0 .. 256)
+ *                 stats[n][2 + k] += number of pixels with k* == k (not mapped through lut), k < n_cls; entries from 2 + n_cls on are untouched
+ *               Integer sums: independent of the order of the atomic adds, so two runs are bit-equal.  stats alone equals the stats of the
+ *               same call with planes.
+ * The output buffers must not overlap each other or the logits.
+ * Enqueue only: no allocation, no synchronisation.  ARSEG_EINVAL, before any launch: null logits; conf8, labels8 and stats all null;
+ * n_cls < 1 or > 32; a non-positive size; a pitch smaller than W; a negative image stride; an unknown kind; low outside 0 .. 256.
+ * Not covered: entropy or calibrated confidences, per-class confidence, confidence painted into overlays, 10-bit planes.
+ * ------------------------------------------------------------------------------------------- */
+enum arseg_conf_kind { ARSEG_CONF_TOP1 = 0, ARSEG_CONF_MARGIN = 1 };
+#define ARSEG_CONF_NSTATS (2 + 32)
+int arseg_segment_confidence_fwd(const float *logits, int N, int n_cls, int h, int w, int H, int W, int align_corners, int kind, int low,
+                                 const uint8_t *lut, uint8_t *conf8, int64_t conf_pitch, int64_t conf_n_stride, uint8_t *labels8,
+                                 int64_t labels_pitch, int64_t labels_n_stride, int64_t *stats, arseg_stream_t stream);
+
+/* ---------------------------------------------------------------------------------------------
  * Measurement aids (no reference counterpart; BASELINE.md section 3: roofline fractions are reported against the datasheet peaks AND
  * against on-box micro-benchmarks).  bench.py times each with HIP events and prints `peaks_measured`.
  *   arseg_peak_stream_copy: dst[0 .. n_bytes) = src[0 .. n_bytes) with 16-byte accesses (n_bytes % 16 == 0, both 16-byte aligned):
