@@ -25,6 +25,7 @@ SRC_RGB8, SRC_NV12, SRC_I420, SRC_P010, SRC_I010 = 0, 1, 2, 3, 4
 COLOUR_BT601_LIMITED, COLOUR_BT601_FULL, COLOUR_BT709_LIMITED, COLOUR_BT709_FULL = 0, 1, 2, 3
 CONF_TOP1, CONF_MARGIN = 0, 1
 CONF_NSTATS = 2 + 32      # ARSEG_CONF_NSTATS: sum of codes, low count, 32 class areas
+TC_NSTATS = 3 + 3 * 32    # ARSEG_TC_NSTATS: compared, outside, void, then 32 each of cur_k, ref_k, inter_k
 
 
 class ConvDesc(Structure):
@@ -132,6 +133,8 @@ PROTOTYPES = {
     "arseg_segment_egress_fwd": (c_int, [_P] + [c_int] * 7 + [_P, _P, c_int64, c_int64, c_int, _P, _P, _P] + [c_int64] * 6 + [_P, _P, _P] + [c_int64] * 6
                                  + [_P, _P, _STREAM]),
     "arseg_segment_confidence_fwd": (c_int, [_P] + [c_int] * 9 + [_P, _P, c_int64, c_int64, _P, c_int64, c_int64, _P, _STREAM]),
+    "arseg_segment_consistency_fwd": (c_int, [_P] + [c_int] * 7 + [_P, c_int64, c_int64, _P, _P, _P, c_int64, c_int64, _P, c_int64, c_int64, _P, _STREAM]),
+    "arseg_labels_consistency_fwd": (c_int, [_P, c_int64, c_int64] + [c_int] * 4 + [_P, c_int64, c_int64, _P, _P, c_int64, c_int64, _P, _STREAM]),
 }
 
 # the SURVEY.md section 8(b) names: aliases with the prototypes of their targets

@@ -8,6 +8,10 @@
   pixel, the label plane next to it and per-frame statistics (sum of the codes, uncertain pixels, pixels per class), one launch of
   ``ops.segment_confidence`` (csrc/confidence.hip) and one pass over the logits; ``DriftMonitor`` turns the statistics into "refresh the
   keyframe" reports on a stream without ground truth.
+* ``consistency``: whether the mask agrees with the keyframe's mask fetched through the accumulated motion ``mv_q`` -- an 8-bit change plane
+  (0 agree / 255 differ / 128 not compared), the label plane and per-frame counters (compared / outside / void, per-class areas and
+  intersections), one launch of ``ops.segment_consistency`` (csrc/consistency.hip); ``consistency_of_planes`` takes label planes instead
+  of logits, ``tc_table`` turns the counters into agreement and temporal-consistency mIoU, ``ConsistencyMonitor`` into refresh reports.
 
 ``labels8`` and ``overlay`` are one launch of ``ops.segment_egress`` (csrc/egress.hip): the bilinear resize and the argmax are the evaluator tail's own, so the
 labels equal ``ops.argmax_confusion``'s ``pred`` bit for bit, and neither int32 labels nor a float frame are ever written.  The painting is
@@ -159,3 +163,105 @@ class DriftMonitor(object):
             self.key_mean = mean
         dropped = self.key_mean is not None and mean < self.rel_drop * self.key_mean
         return bool(dropped or low / n_pixels > self.low_share)
+
+
+def _ref_planes(ref_labels, N):
+    """[H,W] | [1,H,W] (one plane shared by the N frames) | [N,H,W] -> a 3-d uint8 tensor."""
+    if not torch.is_tensor(ref_labels) or ref_labels.dim() not in (2, 3):
+        raise ValueError("expected the reference's train-id plane as a uint8 tensor [H,W], [1,H,W] or [N,H,W]")
+    return ref_labels[None] if ref_labels.dim() == 2 else ref_labels
+
+
+def consistency(logits, ref_labels, mv_q, H, W, change_out=None, labels_out=None, lut=None, stats=True, align_corners=True):
+    """Head logits [N,n_cls,h,w] + a reference mask + the motion back to it -> (change8 | None, labels8 | None, stats | None), one launch and
+    one pass over the logits (``ops.segment_consistency``, csrc/consistency.hip).
+
+    ``ref_labels``: uint8 TRAIN IDS (not mapped through ``lut``), [H,W] or [1,H,W] (one plane shared by the N frames: the GOP's keyframe,
+    ``labels8(forward_keyframe(...)[0], H, W)``) or [N,H,W]; a value >= n_cls is void.  ``mv_q``: int16 [N,H,W,2], quarter pels accumulated
+    back to the reference frame (``ingest.MotionChain.mv_q()``, ``ops.merge_motion``).  Pixel (x, y) with class k* (``ops.argmax_confusion``'s
+    pred) is compared with ``ref[y + round(mvy / 4), x + round(mvx / 4)]`` (halves to even, no clamp): ``change8`` is 0 where they agree, 255
+    where they differ, 128 where the target lies off the frame or either side is void.
+    ``change_out`` / ``labels_out``: a uint8 [N,H,W] buffer, or True to have one allocated; None = not wanted; labels as ``labels8``
+    (through ``lut`` when given).  ``stats``: an int64 [N, _lib.TC_NSTATS] tensor to accumulate into, or True for a zeroed one; None = no
+    statistics.  Row n: [0] += compared pixels, [1] += outside, [2] += void, [3 + k] / [35 + k] / [67 + k] += compared pixels of class k in
+    the frame / in the reference / in both -- integers, so two runs are bit-equal; ``tc_table`` and ``ConsistencyMonitor`` read rows of it."""
+    logits = _check_logits(logits)
+    N = logits.shape[0]
+    ref_labels = _ref_planes(ref_labels, N)
+    if change_out is True:
+        change_out = torch.empty((N, int(H), int(W)), dtype=torch.uint8, device=logits.device)
+    if labels_out is True:
+        labels_out = torch.empty((N, int(H), int(W)), dtype=torch.uint8, device=logits.device)
+    if stats is True:
+        stats = torch.zeros((N, _lib.TC_NSTATS), dtype=torch.int64, device=logits.device)
+    ops.segment_consistency(logits, ref_labels, mv_q, H, W, align_corners=align_corners, lut=lut, labels_out=labels_out, change_out=change_out,
+                            stats=stats)
+    return change_out, labels_out, stats
+
+
+def consistency_of_planes(labels, ref_labels, mv_q, n_cls, change_out=None, stats=True):
+    """The plane form of ``consistency``: ``labels`` uint8 [N,H,W] in train ids (e.g. earlier ``labels8`` planes; a value >= n_cls is void)
+    instead of logits -> (change8 | None, stats | None), one launch of ``ops.labels_consistency``.  With ``ref_labels`` [N,H,W] and a
+    per-frame field it serves consecutive-frame consistency."""
+    if not torch.is_tensor(labels) or labels.dim() != 3:
+        raise ValueError("expected the label planes as a uint8 tensor [N,H,W]")
+    N, H, W = labels.shape
+    ref_labels = _ref_planes(ref_labels, N)
+    if change_out is True:
+        change_out = torch.empty((N, H, W), dtype=torch.uint8, device=labels.device)
+    if stats is True:
+        stats = torch.zeros((N, _lib.TC_NSTATS), dtype=torch.int64, device=labels.device)
+    ops.labels_consistency(labels, ref_labels, mv_q, n_cls, change_out=change_out, stats=stats)
+    return change_out, stats
+
+
+def tc_table(stats, n_cls):
+    """Rows of ``consistency``'s statistics (a tensor, an array or lists, [N, _lib.TC_NSTATS]) -> {"agreement": [N], "tc_miou": [N],
+    "compared_share": [N]} as float64 numpy arrays.  agreement = sum_k inter_k / compared; tc_miou = the mean over the classes with a
+    non-zero union of inter_k / (cur_k + ref_k - inter_k); compared_share = compared / (compared + outside + void).  A frame with
+    compared == 0 yields NaN for agreement and tc_miou (and a compared_share of 0; NaN there only for a row that counted no pixel)."""
+    s = np.asarray(stats.cpu() if torch.is_tensor(stats) else stats, dtype=np.int64)
+    if s.ndim == 1:
+        s = s[None]
+    n_cls = int(n_cls)
+    if s.ndim != 2 or s.shape[1] != _lib.TC_NSTATS or not 1 <= n_cls <= 32:
+        raise ValueError(f"tc_table: expected rows of {_lib.TC_NSTATS} counters and 1..32 classes, got {s.shape}, {n_cls}")
+    compared, total = s[:, 0].astype(np.float64), s[:, :3].sum(axis=1).astype(np.float64)
+    cur, ref, inter = (s[:, o:o + n_cls].astype(np.float64) for o in (3, 35, 67))
+    union = cur + ref - inter
+    with np.errstate(divide="ignore", invalid="ignore"):
+        agreement = np.where(compared > 0, inter.sum(axis=1) / compared, np.nan)
+        iou = np.where(union > 0, inter / union, np.nan)
+        seen = (union > 0).sum(axis=1)
+        tc = np.where(seen > 0, np.nansum(iou, axis=1) / np.maximum(seen, 1), np.nan)
+        share = np.where(total > 0, compared / total, np.nan)
+    return {"agreement": agreement, "tc_miou": tc, "compared_share": share}
+
+
+class ConsistencyMonitor(object):
+    """Reports when a frame's mask no longer agrees with the keyframe's mask along the motion chain -- the label-free signal that stays
+    informative when the softmax is sharp but wrong (a drifted chain, a scene cut inside a GOP); the sibling of ``DriftMonitor``.  Pure
+    Python on rows of ``consistency``'s ``stats``; it only reports -- acting on the report (the keyframe schedule) is the caller's.
+
+    ``min_agreement``: report when the agreement rate sum_k inter_k / compared falls below it (0 <= min_agreement <= 1).
+    ``min_compared_share``: report when less than this share of the frame's pixels could be compared at all (the targets lie off the frame
+    or on void: the chain has left the picture; 0 <= min_compared_share <= 1).  Both are required: neither has a value that is right for
+    every network, dataset and motion source; they are the caller's to calibrate on its own streams (e.g. against ``EvalByDistance``'s
+    table where labels exist)."""
+
+    def __init__(self, min_agreement, min_compared_share):
+        self.min_agreement, self.min_compared_share = float(min_agreement), float(min_compared_share)
+        if not 0.0 <= self.min_agreement <= 1.0 or not 0.0 <= self.min_compared_share <= 1.0:
+            raise ValueError(f"ConsistencyMonitor: both thresholds in [0, 1], got {min_agreement!r}, {min_compared_share!r}")
+
+    def update(self, stats_row, n_pixels) -> bool:
+        """One non-keyframe: ``stats_row`` its row of statistics, ``n_pixels`` = H x W.  True = refresh the keyframe.  A frame of which
+        nothing could be compared is reported whenever ``min_compared_share`` > 0, and never for its (undefined) agreement."""
+        n_pixels = int(n_pixels)
+        if n_pixels <= 0:
+            raise ValueError(f"ConsistencyMonitor.update: n_pixels must be positive, got {n_pixels}")
+        compared = int(stats_row[0])
+        agree = sum(int(stats_row[67 + k]) for k in range(32))
+        too_little = compared / n_pixels < self.min_compared_share
+        disagrees = compared > 0 and agree / compared < self.min_agreement
+        return bool(too_little or disagrees)

@@ -425,3 +425,28 @@ def alter_res_batch_confidence(lr_net, ref_ps, imgs, mv_qs, scale=0.5, kind="top
     else:
         lo, _ = lr_net.phase2_warp(feat, list(ref_ps), mv_qs)
     return egress.confidence(lo, H, W, kind=kind, low=low, out=out, labels_out=labels_out, lut=lut, stats=stats, align_corners=not fused_up)
+
+
+def alter_res_batch_consistency(lr_net, ref_ps, imgs, mv_qs, key_labels, scale=0.5, lut=None, change_out=True, labels_out=True, stats=True):
+    """``alter_res_batch_confidence``'s sibling for temporal consistency: the same phase 1 and phase 2 and the same route decision
+    (BiSeNet's 1/8-resolution head logits with align_corners=False when the frame is exactly 8x the head, align_corners=True otherwise),
+    then ``egress.consistency`` against ``key_labels``, the keyframe's TRAIN-ID plane (uint8 [H,W] or [1,H,W]:
+    ``egress.labels8(net.forward_keyframe(key)[0], H, W)`` without a lut; [B,H,W] for a reference per frame), through ``mv_qs`` -- the
+    int16 field [B,H,W,2] accumulated back to the keyframe that phase 2 warps with -> (change8 uint8 [B,H,W] | None, labels uint8
+    [B,H,W] | None, stats int64 [B, TC_NSTATS] | None).  The labels equal ``alter_res_batch_render``'s; ``lut``, ``change_out``,
+    ``labels_out`` and ``stats`` as ``egress.consistency`` takes them (True: allocated here, a tensor: the caller's, None: not wanted).
+    Feed the rows of ``stats`` to an ``egress.ConsistencyMonitor`` or to ``egress.tc_table``."""
+    from . import egress
+    lr_net = _unwrap(lr_net)
+    B, _, H, W = imgs.shape
+    h, w = _downscale_hw(H, W, scale)
+    feat = lr_net.phase1_nhwc4(ops.ingest_input(imgs, h, w, lr_net.storage_dtype), aux=ops.config.aux_outputs)[-1]
+    fused_up = hasattr(lr_net, "out_upsample")
+    if fused_up:
+        lo, _ = lr_net.phase2_warp(feat, list(ref_ps), mv_qs, upsample=False)
+        if (8 * lo.shape[-2], 8 * lo.shape[-1]) != (H, W):
+            lo, fused_up = ops.resize_nchw(lo, 8 * lo.shape[-2], 8 * lo.shape[-1], _lib.BILINEAR, False), False
+    else:
+        lo, _ = lr_net.phase2_warp(feat, list(ref_ps), mv_qs)
+    return egress.consistency(lo, key_labels, mv_qs, H, W, change_out=change_out, labels_out=labels_out, lut=lut, stats=stats,
+                              align_corners=not fused_up)

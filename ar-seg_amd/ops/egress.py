@@ -139,3 +139,84 @@ def segment_confidence(logits: torch.Tensor, H: int, W: int, *, kind: str = "top
            _CONF_KINDS[kind], low, lut_c, _ptr(conf_out), layout["conf_out"][0], layout["conf_out"][1], _ptr(labels_out), layout["labels_out"][0],
            layout["labels_out"][1], _ptr(stats), _stream(), nbytes=logits.numel() * 4 + planes * N * H * W)
     return conf_out, labels_out, stats
+
+
+def _tc_common(what, N, H, W, n_cls, device, ref_labels, mv_q, change_out, stats):
+    """The arguments the two consistency forms share -> (ref pitch, ref image stride, change pitch, change image stride)."""
+    if not 1 <= n_cls <= 32:
+        raise ValueError(f"{what}: 1..32 classes, got {n_cls}")
+    _need_gpu(ref_labels, dtype=torch.uint8)
+    if ref_labels.dim() != 3 or tuple(ref_labels.shape[1:]) != (H, W) or ref_labels.shape[0] not in (1, N) or ref_labels.device != device:
+        raise ValueError(f"ref_labels must be uint8 {(1, H, W)} (shared) or {(N, H, W)} on {device}, got {tuple(ref_labels.shape)} on "
+                         f"{ref_labels.device}")
+    ref_pitch, ref_ns = _plane_layout(ref_labels, (W,), f"{what} ref_labels")
+    if ref_labels.shape[0] == 1 and N > 1:
+        ref_ns = 0                                        # one plane for all N frames
+    _need_gpu(mv_q, dtype=torch.int16)
+    if tuple(mv_q.shape) != (N, H, W, 2) or not mv_q.is_contiguous() or mv_q.device != device or mv_q.data_ptr() % 4:
+        raise _lib.ArsegError(f"mv_q must be a contiguous, 4-byte aligned int16 {(N, H, W, 2)} tensor on {device}, got {tuple(mv_q.shape)} "
+                              f"strides {mv_q.stride()} on {mv_q.device}")
+    chg = (0, 0)
+    if change_out is not None:
+        _need_gpu(change_out, dtype=torch.uint8)
+        if tuple(change_out.shape) != (N, H, W) or change_out.device != device:
+            raise ValueError(f"change_out must be uint8 {(N, H, W)} on {device}, got {tuple(change_out.shape)} on {change_out.device}")
+        chg = _plane_layout(change_out, (W,), f"{what} change_out")
+    if stats is not None:
+        _need_gpu(stats, dtype=torch.int64)
+        if tuple(stats.shape) != (N, _lib.TC_NSTATS) or not stats.is_contiguous() or stats.device != device:
+            raise _lib.ArsegError(f"stats must be a contiguous int64 {(N, _lib.TC_NSTATS)} tensor on {device}, got {tuple(stats.shape)} "
+                                  f"strides {stats.stride()} on {stats.device}")
+    return ref_pitch, ref_ns, chg[0], chg[1]
+
+
+def segment_consistency(logits: torch.Tensor, ref_labels: torch.Tensor, mv_q: torch.Tensor, H: int, W: int, *, align_corners: bool = True,
+                        lut=None, labels_out: Optional[torch.Tensor] = None, change_out: Optional[torch.Tensor] = None,
+                        stats: Optional[torch.Tensor] = None):
+    """Head logits fp32 [N,n_cls,h,w] + the reference's train-id plane(s) ``ref_labels`` (uint8 [1,H,W]: shared by the N frames, or [N,H,W];
+    rows contiguous, any pitch; a value >= n_cls is void) + ``mv_q`` (int16 [N,H,W,2], contiguous: quarter pels back to the reference frame)
+    -> any non-empty subset of: the label plane ``labels_out`` (as ``segment_egress``: ``lut[k]`` or ``k``, ``k`` = ``argmax_confusion``'s
+    pred bit for bit), the change plane ``change_out`` (uint8 [N,H,W]: 0 where ``ref[y + round(mvy / 4), x + round(mvx / 4)] == k``, 255
+    where it differs, 128 where the target is off the frame or void) and ``stats`` (int64 [N, TC_NSTATS], contiguous, ACCUMULATED INTO:
+    compared, outside, void, then 32 each of cur_k, ref_k, inter_k over the compared pixels), in one launch and one pass over the logits.
+    Allocates nothing: every output is the caller's, so the call can be captured in a HIP graph.
+    Returns (change_out, labels_out, stats)."""
+    _need_gpu(logits)
+    if logits.dim() != 4 or not logits.is_contiguous():
+        raise _lib.ArsegError(f"segment_consistency expects contiguous fp32 logits [N,n_cls,h,w], got {tuple(logits.shape)}")
+    N, n_cls, h, w = logits.shape
+    H, W = int(H), int(W)
+    if labels_out is None and change_out is None and stats is None:
+        raise ValueError("segment_consistency: nothing to write (labels_out, change_out and stats are all None)")
+    ref_pitch, ref_ns, chg_pitch, chg_ns = _tc_common("segment_consistency", N, H, W, n_cls, logits.device, ref_labels, mv_q, change_out, stats)
+    lab_pitch = lab_ns = 0
+    if labels_out is not None:
+        _need_gpu(labels_out, dtype=torch.uint8)
+        if tuple(labels_out.shape) != (N, H, W) or labels_out.device != logits.device:
+            raise ValueError(f"labels_out must be uint8 {(N, H, W)} on {logits.device}, got {tuple(labels_out.shape)} on {labels_out.device}")
+        lab_pitch, lab_ns = _plane_layout(labels_out, (W,), "segment_consistency labels_out")
+    lut_c = None if lut is None else _host_u8(lut, n_cls, "lut")
+    planes = (change_out is not None) + (labels_out is not None)
+    launch("segment_consistency", _lib.load().arseg_segment_consistency_fwd, _ptr(logits), N, n_cls, h, w, H, W, 1 if align_corners else 0,
+           _ptr(ref_labels), ref_pitch, ref_ns, _ptr(mv_q), lut_c, _ptr(labels_out), lab_pitch, lab_ns, _ptr(change_out), chg_pitch, chg_ns,
+           _ptr(stats), _stream(), nbytes=logits.numel() * 4 + (5 + planes) * N * H * W)
+    return change_out, labels_out, stats
+
+
+def labels_consistency(labels: torch.Tensor, ref_labels: torch.Tensor, mv_q: torch.Tensor, n_cls: int, *,
+                       change_out: Optional[torch.Tensor] = None, stats: Optional[torch.Tensor] = None):
+    """The plane form of ``segment_consistency``: ``labels`` uint8 [N,H,W] in train ids (rows contiguous, any pitch / image stride; a value
+    >= n_cls is void) instead of logits; the same comparison, change plane and counters.  Returns (change_out, stats)."""
+    _need_gpu(labels, dtype=torch.uint8)
+    if labels.dim() != 3:
+        raise _lib.ArsegError(f"labels_consistency expects a uint8 label plane [N,H,W], got {tuple(labels.shape)}")
+    N, H, W = labels.shape
+    n_cls = int(n_cls)
+    if change_out is None and stats is None:
+        raise ValueError("labels_consistency: nothing to write (change_out and stats are both None)")
+    ref_pitch, ref_ns, chg_pitch, chg_ns = _tc_common("labels_consistency", N, H, W, n_cls, labels.device, ref_labels, mv_q, change_out, stats)
+    in_pitch, in_ns = _plane_layout(labels, (W,), "labels_consistency labels")
+    launch("labels_consistency", _lib.load().arseg_labels_consistency_fwd, _ptr(labels), in_pitch, in_ns, N, n_cls, H, W, _ptr(ref_labels),
+           ref_pitch, ref_ns, _ptr(mv_q), _ptr(change_out), chg_pitch, chg_ns, _ptr(stats), _stream(),
+           nbytes=(6 + (change_out is not None)) * N * H * W)
+    return change_out, stats

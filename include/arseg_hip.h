@@ -699,6 +699,60 @@ int arseg_segment_confidence_fwd(const float *logits, int N, int n_cls, int h, i
                                  int64_t labels_pitch, int64_t labels_n_stride, int64_t *stats, arseg_stream_t stream);
 
 /* ---------------------------------------------------------------------------------------------
+ * Temporal consistency (csrc/consistency.hip): does the mask of a frame agree with the mask of a reference frame -- the GOP's keyframe --
+ * fetched through the motion between them?  The label-free signal the confidence cannot give: a drifted chain or a scene cut inside a GOP
+ * can still produce sharp softmaxes.  One launch for N frames and one pass over the logits; no int32 labels and no resized logits exist.
+ *   logits, N, n_cls, h, w, H, W, align_corners, lut, pitches and image strides: exactly as arseg_segment_confidence_fwd takes them, with its
+ *               route choice (h == H && w == W; per-pixel bilinear, either align_corners; the x2 / x4 / x8 align_corners == 0 run route).
+ *               The class k* of a pixel is the one label rule (csrc/arseg_device.h): EXACTLY what arseg_argmax_confusion_fwd writes into pred.
+ *   ref_labels  uint8 [R][H][W] on the device, TRAIN IDS (not mapped through lut), ref_pitch bytes from row to row (>= W), ref_image_stride
+ *               bytes from image to image; ref_image_stride == 0: one plane shared by all N frames (the keyframe).  A value >= n_cls is void
+ *               (e.g. 255).
+ *   mv_q        int16 [N][H][W][2] on the device, contiguous, 4-byte aligned: (mvx, mvy) in quarter pels accumulated back to the reference
+ *               frame, sign and units of arseg_merge_motion_fwd's output.  Target of pixel (x, y):
+ *                 tx = x + round_half_even_div4(mvx)      ty = y + round_half_even_div4(mvy)
+ *               (np.round(v / 4): halves go to the even neighbour, the rounding of mergeMotion).  NO clamp.
+ *   per pixel   exactly one of four outcomes, decided in this order:
+ *                 outside  (tx, ty) is not in [0, W) x [0, H); the reference plane is not read
+ *                 void     ref_labels[ty][tx] >= n_cls (plane form: or the source label >= n_cls)
+ *                 agree    ref_labels[ty][tx] == k*
+ *                 differ   otherwise
+ * Outputs, any non-empty subset (NULL = not wanted):
+ *   labels_out  uint8 [N][H][W], labels_pitch / labels_image_stride in bytes; value = lut ? lut[k*] : k* (lut: HOST pointer to n_cls bytes)
+ *   change_out  uint8 [N][H][W], change_pitch / change_image_stride alike: 0 agree, 255 differ, 128 not compared (outside or void); nothing
+ *               past a row's last sample is written
+ *   stats       int64 [N][ARSEG_TC_NSTATS] on the device, ACCUMULATED INTO (like hist and the confidence statistics); for frame n
+ *                 stats[n][0]      += compared pixels (agree + differ)
+ *                 stats[n][1]      += outside pixels
+ *                 stats[n][2]      += void pixels
+ *                 stats[n][3 + k]  += compared pixels with k* == k            (cur_k)
+ *                 stats[n][35 + k] += compared pixels with ref == k           (ref_k)
+ *                 stats[n][67 + k] += compared pixels with k* == ref == k     (inter_k)         k < n_cls; the other entries are untouched
+ *               Integers: independent of the order of the atomic adds, so two runs are bit-equal; stats alone equals the stats of the same
+ *               call with planes.  Agreement rate of a frame = sum_k inter_k / compared; temporal consistency in the mIoU form = the mean
+ *               over the classes with cur_k + ref_k - inter_k > 0 of inter_k / (cur_k + ref_k - inter_k).
+ * arseg_labels_consistency_fwd is the plane form: the same comparison and the same counters with an 8-bit TRAIN-ID plane labels_in (uint8
+ * [N][H][W], in_pitch / in_image_stride in bytes) as the source instead of logits; a source label >= n_cls makes an inside pixel void.  For
+ * callers that hold labels8 planes already, or that compare consecutive frames with a per-frame field of their own (R = N).
+ * The output buffers must not overlap each other or any input.
+ * Enqueue only: no allocation, no synchronisation.  ARSEG_EINVAL, before any launch: null logits / labels_in; null ref_labels or mv_q; an
+ * mv_q that is not 4-byte aligned; no output at all; n_cls < 1 or > 32; a non-positive size; a pitch smaller than W; a negative image
+ * stride.  (The tail refuses no shape on the run route -- a shape that is not an exact x2 / x4 / x8 takes the per-pixel route -- so neither
+ * does this.)
+ * Not covered: sub-pixel comparison of label probabilities, occlusion reasoning, consecutive-frame fields (the plane form takes one).
+ * ------------------------------------------------------------------------------------------- */
+#define ARSEG_TC_NSTATS (3 + 3 * 32)
+int arseg_segment_consistency_fwd(const float *logits, int N, int n_cls, int h, int w, int H, int W, int align_corners,
+                                  const uint8_t *ref_labels, int64_t ref_pitch, int64_t ref_image_stride, const int16_t *mv_q,
+                                  const uint8_t *lut, uint8_t *labels_out, int64_t labels_pitch, int64_t labels_image_stride,
+                                  uint8_t *change_out, int64_t change_pitch, int64_t change_image_stride, int64_t *stats,
+                                  arseg_stream_t stream);
+int arseg_labels_consistency_fwd(const uint8_t *labels_in, int64_t in_pitch, int64_t in_image_stride, int N, int n_cls, int H, int W,
+                                 const uint8_t *ref_labels, int64_t ref_pitch, int64_t ref_image_stride, const int16_t *mv_q,
+                                 uint8_t *change_out, int64_t change_pitch, int64_t change_image_stride, int64_t *stats,
+                                 arseg_stream_t stream);
+
+/* ---------------------------------------------------------------------------------------------
  * Measurement aids (no reference counterpart; BASELINE.md section 3: roofline fractions are reported against the datasheet peaks AND
  * against on-box micro-benchmarks).  bench.py times each with HIP events and prints `peaks_measured`.
  *   arseg_peak_stream_copy: dst[0 .. n_bytes) = src[0 .. n_bytes) with 16-byte accesses (n_bytes % 16 == 0, both 16-byte aligned):
