@@ -135,6 +135,8 @@ PROTOTYPES = {
     "arseg_segment_confidence_fwd": (c_int, [_P] + [c_int] * 9 + [_P, _P, c_int64, c_int64, _P, c_int64, c_int64, _P, _STREAM]),
     "arseg_segment_consistency_fwd": (c_int, [_P] + [c_int] * 7 + [_P, c_int64, c_int64, _P, _P, _P, c_int64, c_int64, _P, c_int64, c_int64, _P, _STREAM]),
     "arseg_labels_consistency_fwd": (c_int, [_P, c_int64, c_int64] + [c_int] * 4 + [_P, c_int64, c_int64, _P, _P, c_int64, c_int64, _P, _STREAM]),
+    "arseg_labels_rle_fwd": (c_int, [_P, c_int64, c_int64, c_int, c_int, c_int, _P, _P, c_int64, _STREAM]),
+    "arseg_rle_decode_fwd": (c_int, [_P, _P, c_int64, c_int, c_int, c_int, _P, c_int64, c_int64, _STREAM]),
 }
 
 # the SURVEY.md section 8(b) names: aliases with the prototypes of their targets

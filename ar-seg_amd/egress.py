@@ -13,6 +13,10 @@
   intersections), one launch of ``ops.segment_consistency`` (csrc/consistency.hip); ``consistency_of_planes`` takes label planes instead
   of logits, ``tc_table`` turns the counters into agreement and temporal-consistency mIoU, ``ConsistencyMonitor`` into refresh reports.
 
+* ``rle`` / ``rle_of_planes``: the mask as run-length codes -- per frame the rows' run offsets and one 32-bit word ``(x_first << 8) | value``
+  per run, counted, scanned and compacted on the GPU (``ops.labels_rle``, csrc/rle.hip) without a host synchronisation, so a few KB per
+  frame cross the host link instead of a byte per pixel; ``RleFrames.decode`` is the inverse on the GPU, ``rle_decode_numpy`` on a host.
+
 ``labels8`` and ``overlay`` are one launch of ``ops.segment_egress`` (csrc/egress.hip): the bilinear resize and the argmax are the evaluator tail's own, so the
 labels equal ``ops.argmax_confusion``'s ``pred`` bit for bit, and neither int32 labels nor a float frame are ever written.  The painting is
 integer arithmetic, written out in include/arseg_hip.h (arseg_segment_egress_fwd).  Not covered: 10-bit, 4:2:2 or 4:4:4 destinations, text,
@@ -265,3 +269,93 @@ class ConsistencyMonitor(object):
         too_little = compared / n_pixels < self.min_compared_share
         disagrees = compared > 0 and agree / compared < self.min_agreement
         return bool(too_little or disagrees)
+
+
+class RleFrames(object):
+    """The row-run code of N planes of H x W (include/arseg_hip.h, arseg_labels_rle_fwd): ``row_start`` int32 [N,H+1] (the exclusive prefix of
+    the rows' run counts) and ``runs`` 32-bit [N,capacity] (run i of a frame in (y, x) order: ``(x_first << 8) | value``), both on the device.
+    ``labels``: the plane the runs were taken from, where ``rle`` allocated it (else None)."""
+
+    def __init__(self, row_start, runs, H, W, labels=None):
+        self.row_start, self.runs, self.H, self.W, self.labels = row_start, runs, int(H), int(W), labels
+        if row_start.dim() != 2 or row_start.shape[1] != self.H + 1 or runs.dim() != 2 or runs.shape[0] != row_start.shape[0]:
+            raise ValueError(f"RleFrames: row_start [N,{self.H + 1}] and runs [N,capacity], got {tuple(row_start.shape)} and {tuple(runs.shape)}")
+
+    @property
+    def N(self):
+        return self.row_start.shape[0]
+
+    @property
+    def capacity(self):
+        return self.runs.shape[1]
+
+    def needed(self) -> torch.Tensor:
+        """The runs each frame needs (a device view, int32 [N]): exact whatever the capacity; ``needed() > capacity`` is an overflow."""
+        return self.row_start[:, self.H]
+
+    def decode(self, out=None) -> torch.Tensor:
+        """The planes back, on the GPU (``ops.rle_decode``): uint8 [N,H,W] into ``out`` (default: a zeroed plane).  The pixels of runs
+        beyond the capacity keep what ``out`` held."""
+        if out is None:
+            out = torch.zeros((self.N, self.H, self.W), dtype=torch.uint8, device=self.runs.device)
+        return ops.rle_decode(self.row_start, self.runs, out)
+
+    def to_host(self):
+        """[(row_start int32 [H+1], runs uint32 [needed])] per frame as numpy arrays, in two copies: the offsets (with the needed counts),
+        then ``runs[:, :max(needed)]`` -- the bytes that cross the link follow the runs, not the capacity.  Raises ``ArsegError`` naming
+        the frame, the runs it needs and the capacity when a frame has overflowed."""
+        offsets = self.row_start.cpu().numpy()
+        needed = offsets[:, self.H]
+        for n, k in enumerate(needed):
+            if k > self.capacity:
+                raise _lib.ArsegError(f"RleFrames.to_host: frame {n} needs {int(k)} runs, the capacity is {self.capacity}")
+        words = self.runs[:, :int(needed.max())].cpu().numpy().view(np.uint32)
+        return [(offsets[n], words[n, :needed[n]]) for n in range(self.N)]
+
+
+def rle_of_planes(labels, capacity, out=None) -> RleFrames:
+    """uint8 planes [N,H,W] on the GPU (``labels8``, change or confidence planes, any byte values; rows contiguous, any pitch) ->
+    ``RleFrames`` with room for ``capacity`` runs per frame, one call of ``ops.labels_rle``.  ``out``: an ``RleFrames`` of the same N, H, W
+    to write into (nothing is allocated then; its capacity holds)."""
+    if not torch.is_tensor(labels) or labels.dim() != 3:
+        raise ValueError("expected the planes as a uint8 tensor [N,H,W]")
+    N, H, W = labels.shape
+    if out is None:
+        capacity = int(capacity)
+        if capacity < 0:
+            raise ValueError(f"rle_of_planes: capacity must not be negative, got {capacity}")
+        out = RleFrames(torch.empty((N, H + 1), dtype=torch.int32, device=labels.device),
+                        torch.empty((N, capacity), dtype=torch.int32, device=labels.device), H, W)
+    elif not isinstance(out, RleFrames) or (out.N, out.H, out.W) != (N, H, W):
+        raise ValueError(f"rle_of_planes: out must be RleFrames of {N} frames of {H}x{W}")
+    ops.labels_rle(labels, out.row_start, out.runs)
+    return out
+
+
+def rle(logits, H, W, capacity, lut=None, labels_out=None, out=None, align_corners=True) -> RleFrames:
+    """Head logits [N,n_cls,h,w] -> the row-run code of their ``labels8`` plane: ``labels8`` into ``labels_out`` (default: a plane the
+    returned object keeps as ``.labels``), then the encoder -- two ABI calls, nothing in between comes to the host.  With ``out`` (an
+    ``RleFrames``) and ``labels_out`` given nothing is allocated and the pair can be captured in a HIP graph."""
+    logits = _check_logits(logits)
+    kept = labels_out is None
+    plane = labels8(logits, H, W, lut=lut, out=labels_out, align_corners=align_corners)
+    frames = rle_of_planes(plane, capacity, out=out)
+    frames.labels = plane if kept else frames.labels
+    return frames
+
+
+def rle_decode_numpy(row_start, runs, H, W) -> np.ndarray:
+    """The receiving side without a GPU: one frame's ``row_start`` [H+1] and ``runs`` [>= row_start[H]] (as ``RleFrames.to_host`` returns
+    them) -> the uint8 plane [H,W]."""
+    H, W = int(H), int(W)
+    rs = np.asarray(row_start).astype(np.int64)
+    words = np.asarray(runs).astype(np.int64) & 0xFFFFFFFF
+    if rs.shape != (H + 1,) or rs[0] != 0 or (np.diff(rs) < 1).any() or words.ndim != 1 or len(words) < rs[H]:
+        raise ValueError(f"rle_decode_numpy: expected row_start [{H + 1}], rising from 0 by at least one run per row, and the row_start[{H}] runs it counts")
+    words = words[:rs[H]]
+    x0 = words >> 8
+    x1 = np.append(x0[1:], W)
+    x1[rs[1:] - 1] = W                                # the last run of a row ends at W
+    if (x0[rs[:-1]] != 0).any() or (x1 <= x0).any() or (x1 > W).any():
+        raise ValueError("rle_decode_numpy: the runs of a row do not start at 0 and increase below W")
+    return np.repeat((words & 0xFF).astype(np.uint8), x1 - x0).reshape(H, W)

@@ -450,3 +450,28 @@ def alter_res_batch_consistency(lr_net, ref_ps, imgs, mv_qs, key_labels, scale=0
         lo, _ = lr_net.phase2_warp(feat, list(ref_ps), mv_qs)
     return egress.consistency(lo, key_labels, mv_qs, H, W, change_out=change_out, labels_out=labels_out, lut=lut, stats=stats,
                               align_corners=not fused_up)
+
+
+def alter_res_batch_rle(lr_net, ref_ps, imgs, mv_qs, capacity, scale=0.5, lut=None, labels_out=True):
+    """``alter_res_batch_render``'s sibling for run-length coded masks: the same phase 1 and phase 2 and the same route decision
+    (BiSeNet's 1/8-resolution head logits with align_corners=False when the frame is exactly 8x the head, align_corners=True otherwise),
+    then ``egress.rle`` -> (``egress.RleFrames`` with room for ``capacity`` runs per frame, labels uint8 [B,H,W]).  The labels equal
+    ``alter_res_batch_render``'s (through ``lut`` when given) and are the plane the runs were taken from; ``labels_out``: True -- allocated
+    here -- or the caller's buffer.  ``RleFrames.to_host()`` brings the runs over the host link, ``RleFrames.decode()`` gives the planes
+    back on a GPU."""
+    from . import egress
+    lr_net = _unwrap(lr_net)
+    B, _, H, W = imgs.shape
+    h, w = _downscale_hw(H, W, scale)
+    feat = lr_net.phase1_nhwc4(ops.ingest_input(imgs, h, w, lr_net.storage_dtype), aux=ops.config.aux_outputs)[-1]
+    fused_up = hasattr(lr_net, "out_upsample")
+    if fused_up:
+        lo, _ = lr_net.phase2_warp(feat, list(ref_ps), mv_qs, upsample=False)
+        if (8 * lo.shape[-2], 8 * lo.shape[-1]) != (H, W):
+            lo, fused_up = ops.resize_nchw(lo, 8 * lo.shape[-2], 8 * lo.shape[-1], _lib.BILINEAR, False), False
+    else:
+        lo, _ = lr_net.phase2_warp(feat, list(ref_ps), mv_qs)
+    if labels_out is True or labels_out is None:
+        labels_out = torch.empty((B, H, W), dtype=torch.uint8, device=lo.device)
+    frames = egress.rle(lo, H, W, capacity, lut=lut, labels_out=labels_out, align_corners=not fused_up)
+    return frames, labels_out

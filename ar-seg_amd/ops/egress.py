@@ -1,6 +1,7 @@
 """The output half of the pipeline: head logits -> an 8-bit label plane and / or the frame with the classes painted over it, one ABI call
 (include/arseg_hip.h, arseg_segment_egress_fwd; csrc/egress.hip); head logits -> an 8-bit confidence plane, the label plane and per-frame
-statistics, one ABI call (arseg_segment_confidence_fwd; csrc/confidence.hip)."""
+statistics, one ABI call (arseg_segment_confidence_fwd; csrc/confidence.hip); an 8-bit plane <-> its row-run code, one ABI call each
+(arseg_labels_rle_fwd / arseg_rle_decode_fwd; csrc/rle.hip)."""
 from __future__ import annotations
 
 import ctypes
@@ -220,3 +221,65 @@ def labels_consistency(labels: torch.Tensor, ref_labels: torch.Tensor, mv_q: tor
            ref_pitch, ref_ns, _ptr(mv_q), _ptr(change_out), chg_pitch, chg_ns, _ptr(stats), _stream(),
            nbytes=(6 + (change_out is not None)) * N * H * W)
     return change_out, stats
+
+
+_RUN_DTYPES = tuple(d for d in (torch.int32, getattr(torch, "uint32", None)) if d is not None)          # one 32-bit word per run, either sign
+
+
+def _rle_common(what, N, H, device, row_start, runs, need_runs):
+    """The arguments the encoder and the decoder share -> cap (0 without runs)."""
+    _need_gpu(row_start, dtype=torch.int32)
+    if tuple(row_start.shape) != (N, H + 1) or not row_start.is_contiguous() or row_start.device != device or row_start.data_ptr() % 4:
+        raise _lib.ArsegError(f"{what}: row_start must be a contiguous int32 {(N, H + 1)} tensor on {device}, got {tuple(row_start.shape)} "
+                              f"strides {row_start.stride()} on {row_start.device}")
+    if runs is None:
+        if need_runs:
+            raise ValueError(f"{what}: runs is required")
+        return 0
+    _need_gpu(runs, dtype=None)
+    if runs.dtype not in _RUN_DTYPES:
+        raise _lib.ArsegError(f"{what}: runs holds one 32-bit word per run (torch.int32 or torch.uint32), got {runs.dtype}")
+    if runs.dim() != 2 or runs.shape[0] != N or not runs.is_contiguous() or runs.device != device or runs.data_ptr() % 4:
+        raise _lib.ArsegError(f"{what}: runs must be a contiguous 32-bit [{N}, cap] tensor on {device}, got {tuple(runs.shape)} strides "
+                              f"{runs.stride()} on {runs.device}")
+    return int(runs.shape[1])
+
+
+def labels_rle(labels: torch.Tensor, row_start: torch.Tensor, runs: Optional[torch.Tensor] = None):
+    """An 8-bit plane uint8 [N,H,W] (rows contiguous, any pitch / image stride; any byte values) -> its row-run code (include/arseg_hip.h,
+    arseg_labels_rle_fwd): ``row_start`` int32 [N,H+1], contiguous, OVERWRITTEN with the exclusive prefix of the rows' run counts
+    (``row_start[n, H]`` = the runs frame n needs, exact whatever the capacity), and ``runs`` 32-bit [N,cap], contiguous: run i of frame n in
+    (y, x) order as ``(x_first << 8) | value``; words with an index >= cap are not written, nothing from ``runs[n, cap]`` on is touched.
+    ``runs=None``: the sizing pass, ``row_start`` only.  Allocates nothing and synchronises nothing: capturable in a HIP graph.
+    Returns (row_start, runs)."""
+    _need_gpu(labels, dtype=torch.uint8)
+    if labels.dim() != 3:
+        raise _lib.ArsegError(f"labels_rle expects a uint8 plane [N,H,W], got {tuple(labels.shape)}")
+    N, H, W = labels.shape
+    if W > 1 << 24 or H * W > 2 ** 31 - 1:
+        raise ValueError(f"labels_rle: W <= 2^24 and H * W < 2^31, got {H}x{W}")
+    cap = _rle_common("labels_rle", N, H, labels.device, row_start, runs, False)
+    pitch, ns = _plane_layout(labels, (W,), "labels_rle labels")
+    launch("labels_rle", _lib.load().arseg_labels_rle_fwd, _ptr(labels), pitch, ns, N, H, W, _ptr(row_start), _ptr(runs), cap, _stream(),
+           nbytes=(2 if runs is not None else 1) * N * H * W + 12 * N * (H + 1))          # (+ 4 bytes per run, known on the device only)
+    return row_start, runs
+
+
+def rle_decode(row_start: torch.Tensor, runs: torch.Tensor, labels_out: torch.Tensor):
+    """The inverse of ``labels_rle`` (arseg_rle_decode_fwd): ``row_start`` int32 [N,H+1] and ``runs`` 32-bit [N,cap] -> ``labels_out`` uint8
+    [N,H,W] (rows contiguous, any pitch / image stride).  Every pixel of a stored run is written; the pixels of runs with an index >= cap
+    keep what they held (of a run whose successor in the row was cut off, the first pixel is written); nothing past a row is written.
+    Allocates nothing.  Returns labels_out."""
+    _need_gpu(labels_out, dtype=torch.uint8)
+    if labels_out.dim() != 3:
+        raise _lib.ArsegError(f"rle_decode expects a uint8 plane [N,H,W] to write into, got {tuple(labels_out.shape)}")
+    N, H, W = labels_out.shape
+    if W > 1 << 24 or H * W > 2 ** 31 - 1:
+        raise ValueError(f"rle_decode: W <= 2^24 and H * W < 2^31, got {H}x{W}")
+    cap = _rle_common("rle_decode", N, H, labels_out.device, row_start, runs, True)
+    pitch, ns = _plane_layout(labels_out, (W,), "rle_decode labels_out")
+    if cap == 0:          # no run is stored (an empty tensor has no address to hand over): every pixel keeps what it held
+        return labels_out
+    launch("rle_decode", _lib.load().arseg_rle_decode_fwd, _ptr(row_start), _ptr(runs), cap, N, H, W, _ptr(labels_out), pitch, ns, _stream(),
+           nbytes=N * H * W + 4 * N * (H + 1))
+    return labels_out

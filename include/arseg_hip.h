@@ -753,6 +753,38 @@ int arseg_labels_consistency_fwd(const uint8_t *labels_in, int64_t in_pitch, int
                                  arseg_stream_t stream);
 
 /* ---------------------------------------------------------------------------------------------
+ * Run-length coded label planes (csrc/rle.hip): the 8-bit planes above (labels8, change8, conf8) are a few thousand constant runs per
+ * frame, and what leaves the GPU for a bus, a database or a browser is run-length codes.  Encoded and decoded on the device, without a host
+ * synchronisation, so both calls can be captured in a HIP graph.
+ * Row-run format.  Runs never cross a row.  In row y of frame n a run begins at x = 0 and at every x >= 1 with plane[y][x] != plane[y][x-1].
+ *   row_start   int32 [N][H+1] on the device, contiguous, 4-byte aligned, OVERWRITTEN (not accumulated into):
+ *                 row_start[n][y] = number of runs in rows 0 .. y-1 of frame n;  row_start[n][0] = 0;
+ *                 row_start[n][H] = the number of runs the frame needs -- always exact, whatever cap is.
+ *   runs        uint32 [N][cap] on the device, 4-byte aligned.  Run i of frame n, in (y, x) order, is the word (x_first << 8) | value; value
+ *               is the plane's byte: any byte 0 .. 255 is legal, there is no n_cls.  A run ends where the next run of its row starts, or at W.
+ *               Overflow: a word whose index is >= cap is not written; every word below cap is written and exact; nothing at or past
+ *               runs[n][cap] is touched.  The caller detects overflow as row_start[n][H] > cap.
+ *               runs == NULL: cap is ignored and row_start alone is produced (the sizing pass).
+ * arseg_labels_rle_fwd: labels uint8 [N][H][W] on the device, pitch bytes from row to row (>= W, any parity), image_stride bytes from image
+ *   to image (>= 0).  Three launches (count per row, a prefix per frame, emit; the per-row counts live in row_start[n][y+1] in between); no
+ *   workgroup waits for another.  Enqueue only: no allocation, no synchronisation, no workspace.
+ * arseg_rle_decode_fwd: the inverse, for a receiving GPU and for round trips.  Every pixel covered by a stored run gets that run's value;
+ *   the pixels of runs with an index >= cap are left untouched; nothing past a row's last sample is written.  The last stored run of an
+ *   overflowed frame, when the next run of its row was cut off, has no stored end: its first pixel is written and no more.
+ *   Undefined results if row_start is not non-decreasing with row_start[n][0] == 0; even then nothing outside runs[n][0 .. cap) is read and
+ *   nothing outside the rows is written.
+ * The buffers must not overlap.
+ * ARSEG_EINVAL, before any launch: null labels / labels_out or row_start (decode: null runs); a row_start or runs that is not 4-byte aligned;
+ * cap < 0 with non-null runs; non-positive N, H or W; pitch < W; a negative image stride; W > 1 << 24 (x_first has 24 bits); H * W > INT32_MAX.
+ * Not covered: COCO's column-major per-class RLE; entropy coding; runs across rows; the run count fused into the tail kernels (the tail
+ * writes labels8 as before and the encoder reads that plane).
+ * ------------------------------------------------------------------------------------------- */
+int arseg_labels_rle_fwd(const uint8_t *labels, int64_t pitch, int64_t image_stride, int N, int H, int W, int32_t *row_start, uint32_t *runs,
+                         int64_t cap, arseg_stream_t stream);
+int arseg_rle_decode_fwd(const int32_t *row_start, const uint32_t *runs, int64_t cap, int N, int H, int W, uint8_t *labels_out, int64_t pitch,
+                         int64_t image_stride, arseg_stream_t stream);
+
+/* ---------------------------------------------------------------------------------------------
  * Measurement aids (no reference counterpart; BASELINE.md section 3: roofline fractions are reported against the datasheet peaks AND
  * against on-box micro-benchmarks).  bench.py times each with HIP events and prints `peaks_measured`.
  *   arseg_peak_stream_copy: dst[0 .. n_bytes) = src[0 .. n_bytes) with 16-byte accesses (n_bytes % 16 == 0, both 16-byte aligned):
