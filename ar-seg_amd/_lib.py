@@ -137,6 +137,8 @@ PROTOTYPES = {
     "arseg_labels_consistency_fwd": (c_int, [_P, c_int64, c_int64] + [c_int] * 4 + [_P, c_int64, c_int64, _P, _P, c_int64, c_int64, _P, _STREAM]),
     "arseg_labels_rle_fwd": (c_int, [_P, c_int64, c_int64, c_int, c_int, c_int, _P, _P, c_int64, _STREAM]),
     "arseg_rle_decode_fwd": (c_int, [_P, _P, c_int64, c_int, c_int, c_int, _P, c_int64, c_int64, _STREAM]),
+    "arseg_rle_regions_workspace_bytes": (c_size_t, [c_int, c_int64]),
+    "arseg_rle_regions_fwd": (c_int, [_P, _P, c_int64, c_int, c_int, c_int, c_int, _P, _P, _P, c_int64, _P, c_size_t, _STREAM]),
 }
 
 # the SURVEY.md section 8(b) names: aliases with the prototypes of their targets

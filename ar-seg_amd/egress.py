@@ -16,6 +16,9 @@
 * ``rle`` / ``rle_of_planes``: the mask as run-length codes -- per frame the rows' run offsets and one 32-bit word ``(x_first << 8) | value``
   per run, counted, scanned and compacted on the GPU (``ops.labels_rle``, csrc/rle.hip) without a host synchronisation, so a few KB per
   frame cross the host link instead of a byte per pixel; ``RleFrames.decode`` is the inverse on the GPU, ``rle_decode_numpy`` on a host.
+* ``regions``: the objects of each frame -- for every connected region of one value its value, area, bounding box and centroid, labelled on the
+  GPU from the run code alone (``ops.rle_regions``, csrc/regions.hip: a lock-free union-find over the runs), numbered in the raster order of
+  their first pixel; ``RegionFrames.to_host`` brings the records over, ``regions_numpy`` computes the same records from a run code on a host.
 
 ``labels8`` and ``overlay`` are one launch of ``ops.segment_egress`` (csrc/egress.hip): the bilinear resize and the argmax are the evaluator tail's own, so the
 labels equal ``ops.argmax_confusion``'s ``pred`` bit for bit, and neither int32 labels nor a float frame are ever written.  The painting is
@@ -359,3 +362,159 @@ def rle_decode_numpy(row_start, runs, H, W) -> np.ndarray:
     if (x0[rs[:-1]] != 0).any() or (x1 <= x0).any() or (x1 > W).any():
         raise ValueError("rle_decode_numpy: the runs of a row do not start at 0 and increase below W")
     return np.repeat((words & 0xFF).astype(np.uint8), x1 - x0).reshape(H, W)
+
+
+REGION_DTYPE = np.dtype([("value", np.int64), ("area", np.int64), ("x_min", np.int64), ("y_min", np.int64), ("x_max", np.int64),
+                         ("y_max", np.int64), ("cx", np.float64), ("cy", np.float64)])
+
+
+def _region_records(rows, min_area=None, values=None) -> np.ndarray:
+    """int64 [R,8] rows {value, area, x_min, y_min, x_max, y_max, sum_x, sum_y} -> the structured records (centroids = sums / area),
+    filtered on the host; the order (raster order of the regions' first pixels) stays."""
+    rows = np.asarray(rows, dtype=np.int64).reshape(-1, 8)
+    rec = np.empty(len(rows), dtype=REGION_DTYPE)
+    for k, name in enumerate(REGION_DTYPE.names[:6]):
+        rec[name] = rows[:, k]
+    area = np.maximum(rows[:, 1], 1).astype(np.float64)
+    rec["cx"], rec["cy"] = rows[:, 6] / area, rows[:, 7] / area
+    keep = np.ones(len(rec), dtype=bool)
+    if min_area is not None:
+        keep &= rec["area"] >= min_area
+    if values is not None:
+        keep &= np.isin(rec["value"], np.asarray(list(values) if not np.isscalar(values) else [values]))
+    return rec[keep]
+
+
+class RegionFrames(object):
+    """The connected regions of ``frames`` (an ``RleFrames``; include/arseg_hip.h, arseg_rle_regions_fwd), on the device: ``n_regions`` int32
+    [N] (-1: the frame's run code overflowed), ``run_region`` int32 [N,frames.capacity] (the region number of every stored run) and
+    ``records`` int64 [N,capacity,8]: ``value, area, x_min, y_min, x_max, y_max, sum_x, sum_y`` per region.  ``workspace``: the scratch tensor
+    the labelling uses, kept so that a repeated call allocates nothing."""
+
+    def __init__(self, n_regions, run_region, records, frames, connectivity=8, workspace=None):
+        self.n_regions, self.run_region, self.records, self.frames = n_regions, run_region, records, frames
+        self.connectivity, self.workspace = int(connectivity), workspace
+        if not isinstance(frames, RleFrames):
+            raise ValueError("RegionFrames: frames must be the RleFrames the regions were taken from")
+        N = frames.N
+        if tuple(n_regions.shape) != (N,) or tuple(run_region.shape) != (N, frames.capacity) or records.dim() != 3 or \
+                records.shape[0] != N or records.shape[2] != 8:
+            raise ValueError(f"RegionFrames: n_regions [{N}], run_region [{N},{frames.capacity}] and records [{N},capacity,8], got "
+                             f"{tuple(n_regions.shape)}, {tuple(run_region.shape)} and {tuple(records.shape)}")
+
+    @property
+    def N(self):
+        return self.frames.N
+
+    @property
+    def capacity(self):
+        return self.records.shape[1]
+
+    def needed(self) -> torch.Tensor:
+        """The regions of each frame (a device view, int32 [N]): exact whatever the capacity; ``needed() > capacity`` is an overflow of the
+        records, -1 an overflow of the frame's run code."""
+        return self.n_regions
+
+    def to_host(self, min_area=None, values=None):
+        """Per frame a numpy structured array with the fields ``value, area, x_min, y_min, x_max, y_max, cx, cy`` (bounds inclusive, the
+        centroid float64 from the integer sums), in two copies: ``n_regions``, then ``records[:, :max needed]``.  ``min_area`` and
+        ``values`` (one value or several) filter on the host.  Raises ``ArsegError`` naming the frame, what it needs and the capacity when
+        a frame has more regions than the capacity, or when its run code had overflowed (no regions exist for it)."""
+        need = self.n_regions.cpu().numpy()
+        for n, k in enumerate(need):
+            if k < 0:
+                raise _lib.ArsegError(f"RegionFrames.to_host: the run code of frame {n} overflowed (it needs {int(self.frames.needed()[n])} "
+                                      f"runs, the capacity is {self.frames.capacity}): it has no regions")
+            if k > self.capacity:
+                raise _lib.ArsegError(f"RegionFrames.to_host: frame {n} needs {int(k)} regions, the capacity is {self.capacity}")
+        rows = self.records[:, :int(need.max())].cpu().numpy()
+        return [_region_records(rows[n, :need[n]], min_area, values) for n in range(self.N)]
+
+
+def regions(frames: RleFrames, region_capacity, connectivity=8, out=None) -> RegionFrames:
+    """The connected regions of run-coded frames, on the GPU: one call of ``ops.rle_regions`` -> ``RegionFrames`` with room for
+    ``region_capacity`` records per frame.  ``out``: a ``RegionFrames`` of these frames' N and run capacity to write into (its capacity and
+    workspace hold; nothing is allocated then, and ``labels8 -> labels_rle -> rle_regions`` can be captured in one HIP graph)."""
+    if not isinstance(frames, RleFrames):
+        raise ValueError("regions: expected the RleFrames of egress.rle / egress.rle_of_planes")
+    if connectivity not in (4, 8):
+        raise ValueError(f"regions: connectivity is 4 or 8, got {connectivity!r}")
+    N, cap, dev = frames.N, frames.capacity, frames.runs.device
+    if out is None:
+        region_capacity = int(region_capacity)
+        if region_capacity < 0:
+            raise ValueError(f"regions: region_capacity must not be negative, got {region_capacity}")
+        out = RegionFrames(torch.empty((N,), dtype=torch.int32, device=dev), torch.empty((N, cap), dtype=torch.int32, device=dev),
+                           torch.empty((N, region_capacity, 8), dtype=torch.int64, device=dev), frames, connectivity,
+                           torch.empty((N, max(cap, 1)), dtype=torch.int32, device=dev))
+    elif not isinstance(out, RegionFrames) or out.N != N or out.run_region.shape[1] != cap:
+        raise ValueError(f"regions: out must be RegionFrames of {N} frames with room for {cap} runs")
+    else:
+        out.frames, out.connectivity = frames, int(connectivity)
+    ops.rle_regions(frames.row_start, frames.runs, frames.H, frames.W, out.n_regions, out.run_region,
+                    out.records if out.capacity else None, connectivity=connectivity, workspace=out.workspace)
+    return out
+
+
+def regions_numpy(row_start, runs, H, W, connectivity=8, return_run_region=False):
+    """The receiving side without a GPU, and what a CPU consumer of the run code calls: one frame's ``row_start`` [H+1] and ``runs``
+    [>= row_start[H]] (as ``RleFrames.to_host`` returns them) -> the records ``RegionFrames.to_host`` gives for that frame (same order, same
+    integers); with ``return_run_region`` also the region number of every run, int32 [row_start[H]].  Vectorised: the neighbours of all runs
+    by two searches over the whole frame, components by minimum-label propagation with pointer jumping."""
+    H, W = int(H), int(W)
+    if connectivity not in (4, 8):
+        raise ValueError(f"regions_numpy: connectivity is 4 or 8, got {connectivity!r}")
+    d = 1 if connectivity == 8 else 0
+    rs = np.asarray(row_start).astype(np.int64)
+    words = np.asarray(runs).astype(np.int64) & 0xFFFFFFFF
+    if rs.shape != (H + 1,) or rs[0] != 0 or (np.diff(rs) < 1).any() or words.ndim != 1 or len(words) < rs[H]:
+        raise ValueError(f"regions_numpy: expected row_start [{H + 1}], rising from 0 by at least one run per row, and the row_start[{H}] runs it counts")
+    words = words[:rs[H]]
+    n = len(words)
+    x0, val = words >> 8, words & 0xFF
+    x1 = np.append(x0[1:], W)
+    x1[rs[1:] - 1] = W
+    if (x0[rs[:-1]] != 0).any() or (x1 <= x0).any() or (x1 > W).any():
+        raise ValueError("regions_numpy: the runs of a row do not start at 0 and increase below W")
+    row = np.repeat(np.arange(H, dtype=np.int64), np.diff(rs))
+    # keys that order (row, x) globally: a search for a column of row y - 1 cannot leave that row
+    K = W + 2
+    cur = np.flatnonzero(row > 0)
+    first = np.searchsorted(row * K + x1, (row[cur] - 1) * K + x0[cur] - d, side="right")           # the first run above with b1 + d > a0
+    last = np.searchsorted(row * K + x0, (row[cur] - 1) * K + x1[cur] + d, side="left") - 1          # the last run above with b0 < a1 + d
+    count = last - first + 1
+    u = np.repeat(cur, count)
+    v = np.repeat(first, count) + np.arange(count.sum()) - np.repeat(np.cumsum(count) - count, count)
+    same = val[u] == val[v]
+    u, v = u[same], v[same]
+    lab = np.arange(n, dtype=np.int64)
+    while True:
+        m = np.minimum(lab[u], lab[v])
+        nxt = lab.copy()
+        np.minimum.at(nxt, u, m)
+        np.minimum.at(nxt, v, m)
+        nxt = np.minimum(nxt, nxt[nxt])
+        while True:
+            j = nxt[nxt]
+            if np.array_equal(j, nxt):
+                break
+            nxt = j
+        if np.array_equal(nxt, lab):
+            break
+        lab = nxt
+    roots, run_region = np.unique(lab, return_inverse=True)
+    length = x1 - x0
+    R = len(roots)
+    rows = np.zeros((R, 8), dtype=np.int64)
+    rows[:, 0] = val[roots]
+    np.add.at(rows[:, 1], run_region, length)
+    rows[:, 2], rows[:, 3] = W, H
+    np.minimum.at(rows[:, 2], run_region, x0)
+    np.minimum.at(rows[:, 3], run_region, row)
+    rows[:, 4] = rows[:, 5] = -1
+    np.maximum.at(rows[:, 4], run_region, x1 - 1)
+    np.maximum.at(rows[:, 5], run_region, row)
+    np.add.at(rows[:, 6], run_region, (x0 + x1 - 1) * length // 2)
+    np.add.at(rows[:, 7], run_region, row * length)
+    rec = _region_records(rows)
+    return (rec, run_region.astype(np.int32)) if return_run_region else rec

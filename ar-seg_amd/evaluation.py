@@ -475,3 +475,13 @@ def alter_res_batch_rle(lr_net, ref_ps, imgs, mv_qs, capacity, scale=0.5, lut=No
         labels_out = torch.empty((B, H, W), dtype=torch.uint8, device=lo.device)
     frames = egress.rle(lo, H, W, capacity, lut=lut, labels_out=labels_out, align_corners=not fused_up)
     return frames, labels_out
+
+
+def alter_res_batch_regions(lr_net, ref_ps, imgs, mv_qs, capacity, region_capacity, scale=0.5, lut=None, labels_out=True, connectivity=8):
+    """``alter_res_batch_rle``'s sibling for the objects of each frame: the same phases, route decision and run code (room for ``capacity``
+    runs per frame), then ``egress.regions`` on it -> (``egress.RegionFrames`` with room for ``region_capacity`` regions per frame, whose
+    ``.frames`` is the ``RleFrames``; labels uint8 [B,H,W]).  Nothing comes to the host in between; ``RegionFrames.to_host()`` brings the
+    records (value, area, bounding box, centroid) over."""
+    from . import egress
+    frames, labels = alter_res_batch_rle(lr_net, ref_ps, imgs, mv_qs, capacity, scale=scale, lut=lut, labels_out=labels_out)
+    return egress.regions(frames, region_capacity, connectivity=connectivity), labels

@@ -1,7 +1,8 @@
 """The output half of the pipeline: head logits -> an 8-bit label plane and / or the frame with the classes painted over it, one ABI call
 (include/arseg_hip.h, arseg_segment_egress_fwd; csrc/egress.hip); head logits -> an 8-bit confidence plane, the label plane and per-frame
 statistics, one ABI call (arseg_segment_confidence_fwd; csrc/confidence.hip); an 8-bit plane <-> its row-run code, one ABI call each
-(arseg_labels_rle_fwd / arseg_rle_decode_fwd; csrc/rle.hip)."""
+(arseg_labels_rle_fwd / arseg_rle_decode_fwd; csrc/rle.hip); a row-run code -> its connected regions, one ABI call (arseg_rle_regions_fwd;
+csrc/regions.hip)."""
 from __future__ import annotations
 
 import ctypes
@@ -11,7 +12,7 @@ import numpy as np
 import torch
 
 from .. import _lib
-from ._base import _need_gpu, _ptr, _stream
+from ._base import _need_gpu, _ptr, _stream, workspace as _workspace
 from ._profile import launch
 from .layers import _plane_layout
 
@@ -283,3 +284,47 @@ def rle_decode(row_start: torch.Tensor, runs: torch.Tensor, labels_out: torch.Te
     launch("rle_decode", _lib.load().arseg_rle_decode_fwd, _ptr(row_start), _ptr(runs), cap, N, H, W, _ptr(labels_out), pitch, ns, _stream(),
            nbytes=N * H * W + 4 * N * (H + 1))
     return labels_out
+
+
+def rle_regions(row_start: torch.Tensor, runs: torch.Tensor, H: int, W: int, n_regions: torch.Tensor, run_region: torch.Tensor,
+                regions: Optional[torch.Tensor] = None, connectivity: int = 8, workspace: Optional[torch.Tensor] = None):
+    """The connected regions of a row-run code (include/arseg_hip.h, arseg_rle_regions_fwd): ``row_start`` int32 [N,H+1] and ``runs`` 32-bit
+    [N,cap] as ``labels_rle`` wrote them -> ``n_regions`` int32 [N] (R per frame, -1 for a frame whose run code overflowed), ``run_region``
+    int32 [N,cap] (the region number of every stored run) and, when given, ``regions`` int64 [N,rcap,8]: per region ``value, area, x_min,
+    y_min, x_max, y_max, sum_x, sum_y``, exact below ``min(R, rcap)``, untouched from there on.  Regions are numbered in the raster order of
+    their first pixel.  ``connectivity`` 4 or 8.  ``workspace``: a device tensor of at least ``arseg_rle_regions_workspace_bytes(N, cap)``
+    bytes (default: the stream's shared workspace).  With every buffer given nothing is allocated and nothing synchronises: capturable in a
+    HIP graph.  Returns (n_regions, run_region, regions)."""
+    H, W = int(H), int(W)
+    if H <= 0 or W <= 0 or W > 1 << 24 or H * W > 2 ** 31 - 1:
+        raise ValueError(f"rle_regions: 0 < W <= 2^24 and 0 < H * W < 2^31, got {H}x{W}")
+    if connectivity not in (4, 8):
+        raise ValueError(f"rle_regions: connectivity is 4 or 8, got {connectivity!r}")
+    _need_gpu(row_start, dtype=torch.int32)
+    if row_start.dim() != 2 or row_start.shape[1] != H + 1:
+        raise _lib.ArsegError(f"rle_regions: row_start must be int32 [N,{H + 1}], got {tuple(row_start.shape)}")
+    N, dev = row_start.shape[0], row_start.device
+    cap = _rle_common("rle_regions", N, H, dev, row_start, runs, True)
+    if cap == 0:
+        raise ValueError("rle_regions: the run buffer holds no run (capacity 0)")
+    _need_gpu(n_regions, run_region, dtype=torch.int32)
+    if tuple(n_regions.shape) != (N,) or not n_regions.is_contiguous() or n_regions.device != dev:
+        raise _lib.ArsegError(f"rle_regions: n_regions must be a contiguous int32 [{N}] tensor on {dev}, got {tuple(n_regions.shape)}")
+    if tuple(run_region.shape) != (N, cap) or not run_region.is_contiguous() or run_region.device != dev:
+        raise _lib.ArsegError(f"rle_regions: run_region must be a contiguous int32 {(N, cap)} tensor on {dev}, got {tuple(run_region.shape)}")
+    rcap = 0
+    if regions is not None:
+        _need_gpu(regions, dtype=torch.int64)
+        if regions.dim() != 3 or regions.shape[0] != N or regions.shape[2] != 8 or not regions.is_contiguous() or regions.device != dev:
+            raise _lib.ArsegError(f"rle_regions: regions must be a contiguous int64 [{N}, rcap, 8] tensor on {dev}, got {tuple(regions.shape)}")
+        rcap = int(regions.shape[1])
+    lib = _lib.load()
+    nbytes = lib.arseg_rle_regions_workspace_bytes(N, cap)
+    if workspace is None:
+        workspace = _workspace(nbytes, dev)
+    elif not workspace.is_cuda or workspace.device != dev or not workspace.is_contiguous() or workspace.numel() * workspace.element_size() < nbytes:
+        raise _lib.ArsegError(f"rle_regions: workspace must be a contiguous tensor of at least {nbytes} bytes on {dev}")
+    launch("rle_regions", lib.arseg_rle_regions_fwd, _ptr(row_start), _ptr(runs), cap, N, H, W, int(connectivity), _ptr(n_regions),
+           _ptr(run_region), _ptr(regions if rcap else None), rcap, _ptr(workspace), workspace.numel() * workspace.element_size(), _stream(),
+           nbytes=4 * N * (H + 1))          # (+ about 50 bytes per run, known on the device only)
+    return n_regions, run_region, regions

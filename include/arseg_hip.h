@@ -785,6 +785,48 @@ int arseg_rle_decode_fwd(const int32_t *row_start, const uint32_t *runs, int64_t
                          int64_t image_stride, arseg_stream_t stream);
 
 /* ---------------------------------------------------------------------------------------------
+ * Connected regions of a run code (csrc/regions.hip): for every connected region of one value its value, area, bounding box and the sums
+ * that give its centroid -- what a tracker, an alerting rule or a click target starts from -- labelled on the device from the runs alone
+ * (a union-find over a few thousand runs; the plane is not read), without a host synchronisation: capturable in a HIP graph behind
+ * arseg_labels_rle_fwd.
+ * Input: row_start int32 [N][H+1] and runs uint32 [N][cap] exactly as arseg_labels_rle_fwd writes them, the same N, H, W and cap;
+ *   connectivity 4 or 8.
+ * Adjacency.  Run i of row y covers [a0, a1) (a1: the start of the next run of its row, or W) and has value v; run j of row y-1 covers
+ *   [b0, b1) and has the same value.  4-connectivity: adjacent iff a0 < b1 && b0 < a1.  8-connectivity: adjacent iff a0 < b1 + 1 &&
+ *   b0 < a1 + 1.  Runs of one row are never adjacent (neighbours in a row differ by construction).  A region is a connected component of
+ *   this graph.  Every byte value forms regions: there is no background class and no n_cls.
+ * Order.  A region's root is its run with the smallest index in the frame's (y, x) order; regions are numbered 0 .. R-1 by rising root
+ *   index (the raster order of each region's first pixel).  Every output is a pure function of the input, whatever the order of the merges.
+ * Outputs, all integers, all OVERWRITTEN:
+ *   n_regions   int32 [N]: R of the frame, exact whatever cap and rcap are.
+ *   run_region  int32 [N][cap]: the region number of each stored run; the words from row_start[n][H] up to cap are untouched.  Exact also
+ *               when R > rcap.
+ *   regions     int64 [N][rcap][8], 8-byte aligned: per region {value, area, x_min, y_min, x_max, y_max, sum_x, sum_y}; the bounds are
+ *               inclusive pixel coordinates, sum_x and sum_y sums over the region's pixels (centroid = sum / area).  A run [a0, a1) of row y
+ *               gives area += a1 - a0, sum_x += (a0 + a1 - 1)(a1 - a0) / 2, sum_y += y (a1 - a0).  The rows below min(R, rcap) are exact,
+ *               the rows from min(R, rcap) on are untouched; the caller detects the overflow as R > rcap.  regions == NULL with rcap == 0:
+ *               the sizing and labelling pass.
+ * A frame whose run code overflowed (row_start[n][H] > cap) has an incomplete graph: n_regions[n] = -1, and neither run_region[n] nor
+ *   regions[n] is touched.  Decided on the device; nothing comes to the host.
+ * workspace: the caller's, 4-byte aligned, >= arseg_rle_regions_workspace_bytes(N, cap) bytes (else ARSEG_EWORKSPACE): the forest, one
+ *   int32 parent per run slot.  Its contents are scratch.
+ * Five launches (init, link, flatten, number, relabel + accumulate); no workgroup waits for another.  Enqueue only: no allocation, no
+ *   synchronisation.  The buffers must not overlap.
+ * A malformed run code (a row_start that does not rise, x_first out of order or >= W) gives undefined regions, but nothing outside the
+ *   caller's buffers is read or written: indices and columns are clamped, and every loop that follows a parent pointer is bounded, since
+ *   parents only ever point to smaller indices.
+ * ARSEG_EINVAL, before any launch: null row_start, runs, n_regions or run_region; one of them or the workspace not 4-byte aligned, regions
+ *   not 8-byte aligned; non-positive N, H or W; cap <= 0; rcap < 0; regions == NULL with rcap > 0; connectivity other than 4 or 8;
+ *   W > 1 << 24; H * W > INT32_MAX; a null workspace.
+ * Not covered: a dense 32-bit instance-id plane; removing or merging small regions; contours or polygons; tracking regions from frame to
+ *   frame; regions across frames; the labelling fused into the run coder.
+ * ------------------------------------------------------------------------------------------- */
+size_t arseg_rle_regions_workspace_bytes(int N, int64_t cap);
+int arseg_rle_regions_fwd(const int32_t *row_start, const uint32_t *runs, int64_t cap, int N, int H, int W, int connectivity,
+                          int32_t *n_regions, int32_t *run_region, int64_t *regions, int64_t rcap, void *workspace, size_t workspace_bytes,
+                          arseg_stream_t stream);
+
+/* ---------------------------------------------------------------------------------------------
  * Measurement aids (no reference counterpart; BASELINE.md section 3: roofline fractions are reported against the datasheet peaks AND
  * against on-box micro-benchmarks).  bench.py times each with HIP events and prints `peaks_measured`.
  *   arseg_peak_stream_copy: dst[0 .. n_bytes) = src[0 .. n_bytes) with 16-byte accesses (n_bytes % 16 == 0, both 16-byte aligned):
