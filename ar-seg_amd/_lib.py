@@ -139,6 +139,9 @@ PROTOTYPES = {
     "arseg_rle_decode_fwd": (c_int, [_P, _P, c_int64, c_int, c_int, c_int, _P, c_int64, c_int64, _STREAM]),
     "arseg_rle_regions_workspace_bytes": (c_size_t, [c_int, c_int64]),
     "arseg_rle_regions_fwd": (c_int, [_P, _P, c_int64, c_int, c_int, c_int, c_int, _P, _P, _P, c_int64, _P, c_size_t, _STREAM]),
+    "arseg_region_links_workspace_bytes": (c_size_t, [c_int, c_int64]),
+    "arseg_region_links_fwd": (c_int, [_P, _P, _P, _P, c_int64, _P, _P, _P, _P, c_int64, c_int, _P, c_int, c_int, c_int, _P, _P, c_int64, _P, c_int64,
+                                       c_int64, _P, c_size_t, _STREAM]),
 }
 
 # the SURVEY.md section 8(b) names: aliases with the prototypes of their targets

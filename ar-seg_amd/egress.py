@@ -19,6 +19,9 @@
 * ``regions``: the objects of each frame -- for every connected region of one value its value, area, bounding box and centroid, labelled on the
   GPU from the run code alone (``ops.rle_regions``, csrc/regions.hip: a lock-free union-find over the runs), numbered in the raster order of
   their first pixel; ``RegionFrames.to_host`` brings the records over, ``regions_numpy`` computes the same records from a run code on a host.
+* ``links``: which region of the keyframe every region of a frame came from, and how much of it, through the accumulated motion ``mv_q``
+  (``ops.region_links``, csrc/links.hip: one pass over the field, the pairs counted in a hash table on the GPU); ``LinkFrames.to_host`` brings
+  the links over, ``links_numpy`` computes them on a host, ``TrackIds`` turns them into ids that last over a stream.
 
 ``labels8`` and ``overlay`` are one launch of ``ops.segment_egress`` (csrc/egress.hip): the bilinear resize and the argmax are the evaluator tail's own, so the
 labels equal ``ops.argmax_confusion``'s ``pred`` bit for bit, and neither int32 labels nor a float frame are ever written.  The painting is
@@ -518,3 +521,218 @@ def regions_numpy(row_start, runs, H, W, connectivity=8, return_run_region=False
     np.add.at(rows[:, 7], run_region, row * length)
     rec = _region_records(rows)
     return (rec, run_region.astype(np.int32)) if return_run_region else rec
+
+
+LINK_DTYPE = np.dtype([(name, np.int64) for name in ("ref_region", "overlap", "same", "outside", "mutual", "n_ref")])
+BACK_DTYPE = np.dtype([(name, np.int64) for name in ("cur_region", "overlap", "covered", "n_cur")])
+
+
+def _records_of(rows, dtype) -> np.ndarray:
+    """int64 [R, fields] rows -> the structured records."""
+    rows = np.asarray(rows, dtype=np.int64).reshape(-1, len(dtype.names))
+    rec = np.empty(len(rows), dtype=dtype)
+    for k, name in enumerate(dtype.names):
+        rec[name] = rows[:, k]
+    return rec
+
+
+class LinkFrames(object):
+    """The links of the regions of ``cur`` (a ``RegionFrames`` of N frames) to the regions of ``ref`` (a ``RegionFrames`` of one frame, shared,
+    or of N) along the motion (include/arseg_hip.h, arseg_region_links_fwd), on the device: ``n_pairs`` int32 [N] (-1: a side of the frame has
+    no regions, -2: more distinct pairs than ``pair_capacity``), ``links`` int64 [N,cur.capacity,6] (``ref_region, overlap, same, outside,
+    mutual, n_ref`` per region) and ``back`` int64 [N,ref.capacity,4] (``cur_region, overlap, covered, n_cur`` per reference region).
+    ``workspace``: the tables the linking uses, kept so that a repeated call allocates nothing."""
+
+    def __init__(self, n_pairs, links, back, cur, ref, pair_capacity, workspace=None):
+        self.n_pairs, self.links, self.back, self.cur, self.ref = n_pairs, links, back, cur, ref
+        self.pair_capacity, self.workspace = int(pair_capacity), workspace
+        if not isinstance(cur, RegionFrames) or not isinstance(ref, RegionFrames):
+            raise ValueError("LinkFrames: cur and ref must be the RegionFrames the links were taken from")
+        N = cur.N
+        if ref.N not in (1, N) or (ref.frames.H, ref.frames.W) != (cur.frames.H, cur.frames.W):
+            raise ValueError(f"LinkFrames: ref must hold one frame or {N} of {cur.frames.H}x{cur.frames.W}, got {ref.N} of "
+                             f"{ref.frames.H}x{ref.frames.W}")
+        if tuple(n_pairs.shape) != (N,) or tuple(links.shape) != (N, cur.capacity, 6) or tuple(back.shape) != (N, ref.capacity, 4):
+            raise ValueError(f"LinkFrames: n_pairs [{N}], links [{N},{cur.capacity},6] and back [{N},{ref.capacity},4], got "
+                             f"{tuple(n_pairs.shape)}, {tuple(links.shape)} and {tuple(back.shape)}")
+        if self.pair_capacity < 1:
+            raise ValueError(f"LinkFrames: pair_capacity must be at least 1, got {pair_capacity!r}")
+
+    @property
+    def N(self):
+        return self.cur.N
+
+    def needed(self) -> torch.Tensor:
+        """The distinct pairs of each frame (a device view, int32 [N]); -1: the frame could not be linked, -2: more than ``pair_capacity``."""
+        return self.n_pairs
+
+    def to_host(self):
+        """Per frame ``(links, back)``: two numpy structured arrays with the fields ``ref_region, overlap, same, outside, mutual, n_ref`` (one
+        row per region of the frame) and ``cur_region, overlap, covered, n_cur`` (one row per region of its reference).  ``n_pairs`` and the
+        region counts come over first, then only the rows in use.  Raises ``ArsegError`` naming the frame when it could not be linked (a run
+        code overflowed), when it has more pairs than ``pair_capacity``, or when a side has more regions than its capacity."""
+        pairs = self.n_pairs.cpu().numpy()
+        R, K = self.cur.n_regions.cpu().numpy(), self.ref.n_regions.cpu().numpy()
+        K = np.broadcast_to(K, (self.N,)) if len(K) == 1 else K
+        for n in range(self.N):
+            if pairs[n] == -1:
+                raise _lib.ArsegError(f"LinkFrames.to_host: frame {n} could not be linked: its run code or its reference's overflowed "
+                                      f"(regions {int(R[n])}, reference regions {int(K[n])})")
+            if pairs[n] == -2:
+                raise _lib.ArsegError(f"LinkFrames.to_host: frame {n} has more distinct pairs than the pair capacity {self.pair_capacity}")
+            if R[n] > self.cur.capacity:
+                raise _lib.ArsegError(f"LinkFrames.to_host: frame {n} needs {int(R[n])} regions, the capacity is {self.cur.capacity}")
+            if K[n] > self.ref.capacity:
+                raise _lib.ArsegError(f"LinkFrames.to_host: the reference of frame {n} needs {int(K[n])} regions, the capacity is "
+                                      f"{self.ref.capacity}")
+        links = self.links[:, :int(R.max())].cpu().numpy()
+        back = self.back[:, :int(K.max())].cpu().numpy()
+        return [(_records_of(links[n, :R[n]], LINK_DTYPE), _records_of(back[n, :K[n]], BACK_DTYPE)) for n in range(self.N)]
+
+
+def links(cur: RegionFrames, ref: RegionFrames, mv_q=None, pair_capacity=None, out=None) -> LinkFrames:
+    """Which region of ``ref`` every region of ``cur`` came from, on the GPU: one call of ``ops.region_links`` -> ``LinkFrames``.  ``ref``: the
+    ``RegionFrames`` of one frame (the GOP's keyframe, shared by the N frames) or of N frames; ``mv_q``: int16 [N,H,W,2], quarter pels
+    accumulated back to the reference (``ingest.MotionChain.mv_q()``), None: zero motion.  A pixel of region r whose target
+    ``(x + round(mvx / 4), y + round(mvy / 4))`` (halves to even, no clamp) lies in a reference run of the same value, of region k, counts
+    into the pair (r, k).  ``pair_capacity``: the slots of the pair table, default ``4 * cur.frames.capacity``.  ``out``: a ``LinkFrames``
+    of the same N and capacities to write into (its pair capacity and workspace hold; nothing is allocated then, and ``labels8 ->
+    labels_rle -> rle_regions -> region_links`` can be captured in one HIP graph)."""
+    if not isinstance(cur, RegionFrames) or not isinstance(ref, RegionFrames):
+        raise ValueError("links: expected the RegionFrames of egress.regions for both sides")
+    N, H, W, dev = cur.N, cur.frames.H, cur.frames.W, cur.frames.runs.device
+    if ref.N not in (1, N) or (ref.frames.H, ref.frames.W) != (H, W):
+        raise ValueError(f"links: ref must hold one frame (shared) or {N} of {H}x{W}, got {ref.N} of {ref.frames.H}x{ref.frames.W}")
+    if out is None:
+        pair_capacity = 4 * cur.frames.capacity if pair_capacity is None else int(pair_capacity)
+        if pair_capacity < 1:
+            raise ValueError(f"links: pair_capacity must be at least 1, got {pair_capacity}")
+        _need = _lib.load().arseg_region_links_workspace_bytes(N, pair_capacity)
+        if not cur.frames.runs.is_cuda:
+            raise _lib.ArsegError("links runs on the GPU only (got CPU tensors); links_numpy is the host form")
+        out = LinkFrames(torch.empty((N,), dtype=torch.int32, device=dev), torch.empty((N, cur.capacity, 6), dtype=torch.int64, device=dev),
+                         torch.empty((N, ref.capacity, 4), dtype=torch.int64, device=dev), cur, ref, pair_capacity,
+                         torch.empty((_need // 8,), dtype=torch.int64, device=dev))
+    elif not isinstance(out, LinkFrames) or out.N != N or out.links.shape[1] != cur.capacity or out.back.shape[1] != ref.capacity:
+        raise ValueError(f"links: out must be LinkFrames of {N} frames with room for {cur.capacity} and {ref.capacity} regions")
+    else:
+        out.cur, out.ref = cur, ref
+    ops.region_links(cur.frames.row_start, cur.frames.runs, cur.n_regions, cur.run_region, ref.frames.row_start, ref.frames.runs,
+                     ref.n_regions, ref.run_region, H, W, out.n_pairs, out.links if cur.capacity else None,
+                     out.back if ref.capacity else None, mv_q=mv_q, pair_capacity=out.pair_capacity, workspace=out.workspace)
+    return out
+
+
+def _region_planes(what, row_start, runs, run_region, H, W):
+    """One frame's run code and run_region -> (value plane, region-id plane), int64 [H,W] each, and the number of regions."""
+    rs = np.asarray(row_start).astype(np.int64)
+    words = np.asarray(runs).astype(np.int64) & 0xFFFFFFFF
+    rr = np.asarray(run_region).astype(np.int64)
+    if rs.shape != (H + 1,) or rs[0] != 0 or (np.diff(rs) < 1).any() or words.ndim != 1 or len(words) < rs[H] or rr.ndim != 1 or len(rr) < rs[H]:
+        raise ValueError(f"{what}: expected row_start [{H + 1}], rising from 0 by at least one run per row, and the row_start[{H}] runs and "
+                         f"region numbers it counts")
+    words, rr = words[:rs[H]], rr[:rs[H]]
+    x0 = words >> 8
+    x1 = np.append(x0[1:], W)
+    x1[rs[1:] - 1] = W
+    if (x0[rs[:-1]] != 0).any() or (x1 <= x0).any() or (x1 > W).any() or (rr < 0).any():
+        raise ValueError(f"{what}: the runs of a row do not start at 0 and increase below W, or a region number is negative")
+    return np.repeat(words & 0xFF, x1 - x0).reshape(H, W), np.repeat(rr, x1 - x0).reshape(H, W), int(rr.max()) + 1
+
+
+def links_numpy(cur_row_start, cur_runs, cur_run_region, ref_row_start, ref_runs, ref_run_region, H, W, mv_q=None):
+    """The same links on a host without a GPU: one frame's run code and ``run_region`` (as ``RleFrames.to_host`` and ``regions_numpy(...,
+    return_run_region=True)`` give them), its reference's, and ``mv_q`` int16 [H,W,2] (None: zero motion) -> the ``(links, back)`` pair of
+    structured arrays ``LinkFrames.to_host`` returns for that frame.  Vectorised: both sides decoded to region-id planes, one gather, then
+    ``np.unique`` over the pairs."""
+    H, W = int(H), int(W)
+    val, reg, R = _region_planes("links_numpy", cur_row_start, cur_runs, cur_run_region, H, W)
+    rval, rreg, K = _region_planes("links_numpy", ref_row_start, ref_runs, ref_run_region, H, W)
+    ys, xs = np.mgrid[0:H, 0:W]
+    if mv_q is None:
+        tx, ty = xs, ys
+    else:
+        mv = np.asarray(mv_q)
+        if mv.shape != (H, W, 2) or not np.issubdtype(mv.dtype, np.integer):
+            raise ValueError(f"links_numpy: mv_q must be integers [{H},{W},2], got {mv.dtype} {mv.shape}")
+        mv = mv.astype(np.int64)
+        b, r = mv >> 2, mv & 3                           # v = 4 b + r: halves go to the even neighbour
+        step = np.where(r < 2, b, np.where(r > 2, b + 1, b + (b & 1)))
+        tx, ty = xs + step[..., 0], ys + step[..., 1]
+    inside = (tx >= 0) & (tx < W) & (ty >= 0) & (ty < H)
+    cx, cy = np.where(inside, tx, 0), np.where(inside, ty, 0)
+    hit = inside & (rval[cy, cx] == val)
+    key, count = np.unique(reg[hit] * K + rreg[cy, cx][hit], return_counts=True)
+    pr, pk = key // K, key % K
+    rows = np.zeros((R, 6), dtype=np.int64)
+    rows[:, 0] = -1
+    back = np.zeros((K, 4), dtype=np.int64)
+    back[:, 0] = -1
+    rows[:, 3] = np.bincount(reg[~inside], minlength=R)
+    if len(key):
+        rows[:, 2], rows[:, 5] = np.bincount(pr, weights=count, minlength=R).astype(np.int64), np.bincount(pr, minlength=R)
+        back[:, 2], back[:, 3] = np.bincount(pk, weights=count, minlength=K).astype(np.int64), np.bincount(pk, minlength=K)
+        # the largest count first, then the smaller partner: the first entry of each group wins
+        order = np.lexsort((pk, -count, pr))
+        first = order[np.r_[True, np.diff(pr[order]) != 0]]
+        rows[pr[first], 0], rows[pr[first], 1] = pk[first], count[first]
+        order = np.lexsort((pr, -count, pk))
+        first = order[np.r_[True, np.diff(pk[order]) != 0]]
+        back[pk[first], 0], back[pk[first], 1] = pr[first], count[first]
+        linked = rows[:, 0] >= 0
+        rows[linked, 4] = back[rows[linked, 0], 0] == np.flatnonzero(linked)
+    return _records_of(rows, LINK_DTYPE), _records_of(back, BACK_DTYPE)
+
+
+class TrackIds(object):
+    """Persistent ids for the regions of a stream, from the links alone.  Pure Python on the ``links`` arrays of ``LinkFrames.to_host`` /
+    ``links_numpy``; it has no thresholds -- what to do with a short-lived id is the caller's business.
+
+    A region whose link is mutual (it is the largest part of the reference region it mostly came from) inherits that region's id.  Every
+    other region gets the next fresh id, and its parent is the id of the reference region it mostly came from (a split or a merge), or -1."""
+
+    def __init__(self):
+        self.next_id = 0
+        self.key_ids = None          # ids of the current keyframe's regions
+        self.last_ids = None         # ids of the most recent frame's regions (a keyframe included)
+
+    def _fresh(self, count):
+        ids = np.arange(self.next_id, self.next_id + count, dtype=np.int64)
+        self.next_id += count
+        return ids
+
+    def _assign(self, links, ref_ids, what):
+        ref = np.asarray(links["ref_region"], dtype=np.int64)
+        mutual = np.asarray(links["mutual"], dtype=np.int64) == 1
+        if len(ref) and ref.max() >= len(ref_ids):
+            raise ValueError(f"{what}: the links name reference region {int(ref.max())}, the reference has {len(ref_ids)} regions")
+        ids = np.full(len(ref), -1, dtype=np.int64)
+        ids[mutual] = ref_ids[ref[mutual]]
+        ids[~mutual] = self._fresh(int((~mutual).sum()))
+        parents = np.full(len(ref), -1, dtype=np.int64)
+        born = ~mutual & (ref >= 0)
+        parents[born] = ref_ids[ref[born]]
+        return ids, parents
+
+    def keyframe(self, n_regions, links=None):
+        """A keyframe with ``n_regions`` regions -> their ids, int64 [n_regions].  ``links``: the links of this keyframe's regions against the
+        previous frame's regions, made with ``mv_q=None`` (zero motion): ids survive the GOP boundary through them.  Without: all fresh."""
+        n_regions = int(n_regions)
+        if links is None:
+            ids = self._fresh(n_regions)
+        else:
+            if self.last_ids is None:
+                raise ValueError("TrackIds.keyframe: links given, but there is no previous frame")
+            if len(links) != n_regions:
+                raise ValueError(f"TrackIds.keyframe: {n_regions} regions, {len(links)} links")
+            ids, _ = self._assign(links, self.last_ids, "TrackIds.keyframe")
+        self.key_ids = self.last_ids = ids
+        return ids
+
+    def frame(self, links):
+        """A non-keyframe's links against the current keyframe -> (ids, parents), int64 [regions] each."""
+        if self.key_ids is None:
+            raise ValueError("TrackIds.frame: no keyframe yet")
+        ids, parents = self._assign(links, self.key_ids, "TrackIds.frame")
+        self.last_ids = ids
+        return ids, parents

@@ -485,3 +485,16 @@ def alter_res_batch_regions(lr_net, ref_ps, imgs, mv_qs, capacity, region_capaci
     from . import egress
     frames, labels = alter_res_batch_rle(lr_net, ref_ps, imgs, mv_qs, capacity, scale=scale, lut=lut, labels_out=labels_out)
     return egress.regions(frames, region_capacity, connectivity=connectivity), labels
+
+
+def alter_res_batch_links(lr_net, ref_ps, imgs, mv_qs, key_regions, capacity, region_capacity, scale=0.5, lut=None, labels_out=True,
+                          connectivity=8, pair_capacity=None):
+    """``alter_res_batch_regions``'s sibling for object association: the same phases, run code and regions, then ``egress.links`` of every
+    frame's regions to ``key_regions`` -- the ``egress.RegionFrames`` of the keyframe's mask (one frame, made with the same ``lut`` and
+    ``connectivity``) -- through ``mv_qs``, the int16 field [B,H,W,2] accumulated back to the keyframe that phase 2 warps with ->
+    (``egress.LinkFrames``, ``egress.RegionFrames``, labels uint8 [B,H,W]).  Nothing comes to the host in between;
+    ``LinkFrames.to_host()`` brings the links over, ``egress.TrackIds`` turns them into ids that last over the stream."""
+    from . import egress
+    found, labels = alter_res_batch_regions(lr_net, ref_ps, imgs, mv_qs, capacity, region_capacity, scale=scale, lut=lut, labels_out=labels_out,
+                                            connectivity=connectivity)
+    return egress.links(found, key_regions, mv_qs, pair_capacity=pair_capacity), found, labels

@@ -2,7 +2,7 @@
 (include/arseg_hip.h, arseg_segment_egress_fwd; csrc/egress.hip); head logits -> an 8-bit confidence plane, the label plane and per-frame
 statistics, one ABI call (arseg_segment_confidence_fwd; csrc/confidence.hip); an 8-bit plane <-> its row-run code, one ABI call each
 (arseg_labels_rle_fwd / arseg_rle_decode_fwd; csrc/rle.hip); a row-run code -> its connected regions, one ABI call (arseg_rle_regions_fwd;
-csrc/regions.hip)."""
+csrc/regions.hip); the regions of two frames -> their links along the motion, one ABI call (arseg_region_links_fwd; csrc/links.hip)."""
 from __future__ import annotations
 
 import ctypes
@@ -328,3 +328,80 @@ def rle_regions(row_start: torch.Tensor, runs: torch.Tensor, H: int, W: int, n_r
            _ptr(run_region), _ptr(regions if rcap else None), rcap, _ptr(workspace), workspace.numel() * workspace.element_size(), _stream(),
            nbytes=4 * N * (H + 1))          # (+ about 50 bytes per run, known on the device only)
     return n_regions, run_region, regions
+
+
+def _links_side(what, side, H, row_start, runs, n_regions, run_region, device=None):
+    """One side's four arrays of ``region_links`` -> (frames, cap)."""
+    _need_gpu(row_start, dtype=torch.int32)
+    if row_start.dim() != 2 or row_start.shape[1] != H + 1:
+        raise _lib.ArsegError(f"{what}: {side}row_start must be int32 [N,{H + 1}], got {tuple(row_start.shape)}")
+    F, dev = row_start.shape[0], row_start.device
+    if device is not None and dev != device:
+        raise _lib.ArsegError(f"{what}: {side}row_start must be on {device}, got {dev}")
+    cap = _rle_common(what, F, H, dev, row_start, runs, True)
+    if cap == 0:
+        raise ValueError(f"{what}: the {side}run buffer holds no run (capacity 0)")
+    _need_gpu(n_regions, run_region, dtype=torch.int32)
+    if tuple(n_regions.shape) != (F,) or not n_regions.is_contiguous() or n_regions.device != dev:
+        raise _lib.ArsegError(f"{what}: {side}n_regions must be a contiguous int32 [{F}] tensor on {dev}, got {tuple(n_regions.shape)}")
+    if tuple(run_region.shape) != (F, cap) or not run_region.is_contiguous() or run_region.device != dev:
+        raise _lib.ArsegError(f"{what}: {side}run_region must be a contiguous int32 {(F, cap)} tensor on {dev}, got {tuple(run_region.shape)}")
+    return F, cap
+
+
+def region_links(row_start: torch.Tensor, runs: torch.Tensor, n_regions: torch.Tensor, run_region: torch.Tensor, ref_row_start: torch.Tensor,
+                 ref_runs: torch.Tensor, ref_n_regions: torch.Tensor, ref_run_region: torch.Tensor, H: int, W: int, n_pairs: torch.Tensor,
+                 links: Optional[torch.Tensor] = None, back: Optional[torch.Tensor] = None, mv_q: Optional[torch.Tensor] = None,
+                 pair_capacity: Optional[int] = None, workspace: Optional[torch.Tensor] = None):
+    """Which region of a reference frame every region of a frame came from, along the motion (include/arseg_hip.h, arseg_region_links_fwd):
+    the current frames' ``row_start`` int32 [N,H+1], ``runs`` 32-bit [N,cap], ``n_regions`` int32 [N] and ``run_region`` int32 [N,cap] as
+    ``labels_rle`` + ``rle_regions`` wrote them, the reference's four alike ([1,...]: one reference shared by the N frames, or [N,...]) and
+    ``mv_q`` (int16 [N,H,W,2], contiguous: quarter pels back to the reference; None: zero motion) -> ``n_pairs`` int32 [N] (the distinct
+    pairs of a frame; -1: a run code overflowed or a side has no regions; -2: more than ``pair_capacity`` pairs) and, when given, ``links``
+    int64 [N,rcap,6] (``ref_region, overlap, same, outside, mutual, n_ref`` per region) and ``back`` int64 [N,kcap,4] (``cur_region,
+    overlap, covered, n_cur`` per reference region), exact below the region counts and untouched from there on.  ``pair_capacity``: the
+    slots of the pair table (default ``4 * cap``).  ``workspace``: a device tensor of at least
+    ``arseg_region_links_workspace_bytes(N, pair_capacity)`` bytes, 8-byte aligned (default: the stream's shared workspace).  With every
+    buffer given nothing is allocated and nothing synchronises: capturable in a HIP graph.  Returns (n_pairs, links, back)."""
+    what = "region_links"
+    H, W = int(H), int(W)
+    if H <= 0 or W <= 0 or W > 1 << 24 or H * W > 2 ** 31 - 1:
+        raise ValueError(f"{what}: 0 < W <= 2^24 and 0 < H * W < 2^31, got {H}x{W}")
+    N, cap = _links_side(what, "", H, row_start, runs, n_regions, run_region)
+    dev = row_start.device
+    R, ref_cap = _links_side(what, "ref_", H, ref_row_start, ref_runs, ref_n_regions, ref_run_region, dev)
+    if R not in (1, N):
+        raise ValueError(f"{what}: one reference frame (shared) or {N}, got {R}")
+    pcap = 4 * cap if pair_capacity is None else int(pair_capacity)
+    if pcap < 1:
+        raise ValueError(f"{what}: pair_capacity must be at least 1, got {pair_capacity!r}")
+    _need_gpu(n_pairs, dtype=torch.int32)
+    if tuple(n_pairs.shape) != (N,) or not n_pairs.is_contiguous() or n_pairs.device != dev:
+        raise _lib.ArsegError(f"{what}: n_pairs must be a contiguous int32 [{N}] tensor on {dev}, got {tuple(n_pairs.shape)}")
+    caps = []
+    for name, t, width in (("links", links, 6), ("back", back, 4)):
+        caps.append(0)
+        if t is not None:
+            _need_gpu(t, dtype=torch.int64)
+            if t.dim() != 3 or t.shape[0] != N or t.shape[2] != width or not t.is_contiguous() or t.device != dev:
+                raise _lib.ArsegError(f"{what}: {name} must be a contiguous int64 [{N}, capacity, {width}] tensor on {dev}, got {tuple(t.shape)}")
+            caps[-1] = int(t.shape[1])
+    rcap, kcap = caps
+    if mv_q is not None:
+        _need_gpu(mv_q, dtype=torch.int16)
+        if tuple(mv_q.shape) != (N, H, W, 2) or not mv_q.is_contiguous() or mv_q.device != dev or mv_q.data_ptr() % 4:
+            raise _lib.ArsegError(f"{what}: mv_q must be a contiguous, 4-byte aligned int16 {(N, H, W, 2)} tensor on {dev}, got "
+                                  f"{tuple(mv_q.shape)} strides {mv_q.stride()} on {mv_q.device}")
+    lib = _lib.load()
+    nbytes = lib.arseg_region_links_workspace_bytes(N, pcap)
+    if workspace is None:
+        workspace = _workspace(nbytes, dev)
+    elif not workspace.is_cuda or workspace.device != dev or not workspace.is_contiguous() or workspace.data_ptr() % 8 or \
+            workspace.numel() * workspace.element_size() < nbytes:
+        raise _lib.ArsegError(f"{what}: workspace must be a contiguous, 8-byte aligned tensor of at least {nbytes} bytes on {dev}")
+    launch(what, lib.arseg_region_links_fwd, _ptr(row_start), _ptr(runs), _ptr(n_regions), _ptr(run_region), cap, _ptr(ref_row_start),
+           _ptr(ref_runs), _ptr(ref_n_regions), _ptr(ref_run_region), ref_cap, 1 if R == 1 else 0, _ptr(mv_q), N, H, W, _ptr(n_pairs),
+           _ptr(links if rcap else None), rcap, _ptr(back if kcap else None), kcap, pcap, _ptr(workspace),
+           workspace.numel() * workspace.element_size(), _stream(),
+           nbytes=(4 * N * H * W if mv_q is not None else 0) + 64 * N * pcap)          # the field once from HBM; the tables cleared and read
+    return n_pairs, links, back

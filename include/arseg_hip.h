@@ -818,13 +818,65 @@ int arseg_rle_decode_fwd(const int32_t *row_start, const uint32_t *runs, int64_t
  * ARSEG_EINVAL, before any launch: null row_start, runs, n_regions or run_region; one of them or the workspace not 4-byte aligned, regions
  *   not 8-byte aligned; non-positive N, H or W; cap <= 0; rcap < 0; regions == NULL with rcap > 0; connectivity other than 4 or 8;
  *   W > 1 << 24; H * W > INT32_MAX; a null workspace.
- * Not covered: a dense 32-bit instance-id plane; removing or merging small regions; contours or polygons; tracking regions from frame to
- *   frame; regions across frames; the labelling fused into the run coder.
+ * Not covered: a dense 32-bit instance-id plane; removing or merging small regions; contours or polygons; regions across frames; the
+ *   labelling fused into the run coder.  (Which region of another frame a region came from: arseg_region_links_fwd, below.)
  * ------------------------------------------------------------------------------------------- */
 size_t arseg_rle_regions_workspace_bytes(int N, int64_t cap);
 int arseg_rle_regions_fwd(const int32_t *row_start, const uint32_t *runs, int64_t cap, int N, int H, int W, int connectivity,
                           int32_t *n_regions, int32_t *run_region, int64_t *regions, int64_t rcap, void *workspace, size_t workspace_bytes,
                           arseg_stream_t stream);
+
+/* ---------------------------------------------------------------------------------------------
+ * Links between the regions of two frames along the motion chain (csrc/links.hip): for every region of a frame, which region of a
+ * reference frame -- the GOP's keyframe -- it came from, and how much of it; the object-level form of arseg_segment_consistency_fwd.
+ * Computed on the device from the two run codes, their run_region and the motion field, without a host synchronisation: capturable in a
+ * HIP graph behind arseg_rle_regions_fwd.  mv_q is the only input of the size of a frame.
+ * Input.  The CURRENT frames: row_start int32 [N][H+1], runs uint32 [N][cap], n_regions int32 [N] and run_region int32 [N][cap] exactly as
+ *   arseg_labels_rle_fwd + arseg_rle_regions_fwd leave them.  The REFERENCE frames: the same four arrays with their own ref_cap;
+ *   ref_shared = 1: one reference frame for all N (the keyframe), ref_shared = 0: one per current frame (consecutive-frame use with a field
+ *   of the caller's own).  mv_q int16 [N][H][W][2], contiguous, 4-byte aligned, sign and units of arseg_segment_consistency_fwd; NULL = zero
+ *   motion.
+ * Per pixel.  Pixel (x, y) of current frame n lies in run i with value v and region r = run_region[n][i].  Its target is
+ *     tx = x + round_half_even_div4(mvx)      ty = y + round_half_even_div4(mvy)          (no clamp, as arseg_segment_consistency_fwd)
+ *   (tx, ty) not in [0, W) x [0, H): the pixel is OUTSIDE.  Otherwise the reference run j that covers tx in row ty has value u and region k:
+ *   u == v: the pixel counts 1 into the pair (r, k); u != v: it counts nothing (per region: area - outside - same such pixels).
+ * Outputs, all integers, all OVERWRITTEN, every one a pure function of the inputs whatever the order of the atomics:
+ *   n_pairs     int32 [N]: the number of distinct pairs (r, k) with a count > 0; or
+ *                 -1  the frame cannot be linked: its run code or its reference's overflowed (row_start[.][H] > cap), or either n_regions
+ *                     entry is negative.  Nothing else of that frame is touched.
+ *                 -2  more than pcap distinct pairs.  Nothing else of that frame is touched; the caller retries with a larger table.
+ *   links       int64 [N][rcap][6], 8-byte aligned: per current region r {ref_region, overlap, same, outside, mutual, n_ref}.
+ *                 ref_region  the k with the largest pair count, ties to the smaller k; -1 if none
+ *                 overlap     that pair's count                    same     the sum of r's pair counts
+ *                 outside     as defined above                     n_ref    the number of distinct k
+ *                 mutual      1 iff back[ref_region].cur_region == r (exact whatever kcap is, also with back == NULL)
+ *               The rows below min(R, rcap) are exact, the rows from there on are untouched.  links == NULL with rcap == 0: not wanted.
+ *   back        int64 [N][kcap][4], 8-byte aligned: per reference region k and current frame {cur_region, overlap, covered, n_cur}:
+ *               cur_region the r with the largest count (ties to the smaller r, -1 if none), overlap that count, covered the sum over r of
+ *               the pair counts, n_cur the number of distinct r.  Exact below min(R_ref, kcap), untouched above.  back == NULL with
+ *               kcap == 0: not wanted.
+ * workspace: the caller's, 8-byte aligned, >= arseg_region_links_workspace_bytes(N, pcap) bytes (else ARSEG_EWORKSPACE): per frame an open
+ *   addressed table of pcap slots for the pairs (a 64-bit key and a 64-bit count), one of pcap slots for the best current region of every
+ *   reference region, and a flag.  pcap: any value >= 1.  Probing visits every slot before it gives up, so an insert fails if and only if
+ *   the frame has more than pcap distinct pairs: -2 does not depend on timing.  Its contents are scratch.
+ * Six launches (clear, vote, rows, outside -- not without mv_q or links --, resolve, finish); no workgroup waits for another.  Enqueue only:
+ *   no allocation, no synchronisation.  The buffers must not overlap.
+ * Malformed input (a run_region outside [0, R), a row_start that does not rise, x_first out of order) gives meaningless links, but nothing
+ *   outside the caller's buffers is read or written: indices and columns are clamped as arseg_rle_regions_fwd clamps them, and every loop
+ *   is bounded.
+ * ARSEG_EINVAL, before any launch: a null row_start, runs, n_regions or run_region of either side, or a null n_pairs; one of them or mv_q
+ *   not 4-byte aligned; links, back or the workspace not 8-byte aligned; non-positive N, H, W, cap, ref_cap or pcap; negative rcap or kcap;
+ *   links == NULL with rcap > 0, back == NULL with kcap > 0; ref_shared other than 0 or 1; W > 1 << 24; H * W > INT32_MAX; a null
+ *   workspace.
+ * Not covered: frame-to-frame motion fields (the caller supplies one with ref_shared = 0); occlusion reasoning; appearance features;
+ *   many-to-many assignment; thresholds of any kind (what counts as the same object is the caller's decision).
+ * ------------------------------------------------------------------------------------------- */
+size_t arseg_region_links_workspace_bytes(int N, int64_t pcap);
+int arseg_region_links_fwd(const int32_t *row_start, const uint32_t *runs, const int32_t *n_regions, const int32_t *run_region, int64_t cap,
+                           const int32_t *ref_row_start, const uint32_t *ref_runs, const int32_t *ref_n_regions,
+                           const int32_t *ref_run_region, int64_t ref_cap, int ref_shared, const int16_t *mv_q, int N, int H, int W,
+                           int32_t *n_pairs, int64_t *links, int64_t rcap, int64_t *back, int64_t kcap, int64_t pcap, void *workspace,
+                           size_t workspace_bytes, arseg_stream_t stream);
 
 /* ---------------------------------------------------------------------------------------------
  * Measurement aids (no reference counterpart; BASELINE.md section 3: roofline fractions are reported against the datasheet peaks AND
