@@ -22,6 +22,9 @@
 * ``links``: which region of the keyframe every region of a frame came from, and how much of it, through the accumulated motion ``mv_q``
   (``ops.region_links``, csrc/links.hip: one pass over the field, the pairs counted in a hash table on the GPU); ``LinkFrames.to_host`` brings
   the links over, ``links_numpy`` computes them on a host, ``TrackIds`` turns them into ids that last over a stream.
+* ``absorb``: the specks of a mask removed where it is cheap -- every region below ``min_area`` pixels takes the value of the neighbour it
+  shares the longest border with, on the run code and on the GPU (``ops.rle_absorb``, csrc/absorb.hip) -> a new ``RleFrames`` for the bus,
+  the overlay and the next ``regions`` / ``links``; ``absorb_numpy`` is the same pass on a host.
 
 ``labels8`` and ``overlay`` are one launch of ``ops.segment_egress`` (csrc/egress.hip): the bilinear resize and the argmax are the evaluator tail's own, so the
 labels equal ``ops.argmax_confusion``'s ``pred`` bit for bit, and neither int32 labels nor a float frame are ever written.  The painting is
@@ -682,6 +685,135 @@ def links_numpy(cur_row_start, cur_runs, cur_run_region, ref_row_start, ref_runs
         linked = rows[:, 0] >= 0
         rows[linked, 4] = back[rows[linked, 0], 0] == np.flatnonzero(linked)
     return _records_of(rows, LINK_DTYPE), _records_of(back, BACK_DTYPE)
+
+
+class AbsorbedFrames(RleFrames):
+    """The run code of ``source.frames`` (``source``: a ``RegionFrames``) with the small regions absorbed into their neighbours
+    (include/arseg_hip.h, arseg_rle_absorb_fwd), on the device: an ``RleFrames`` with ``target`` int32 [N,source.capacity] (per region of the
+    source -1: stable, -2: small and left alone, else the region it went into) and ``n_absorbed`` int32 [N] (-1: the frame could not be
+    processed, -2: more neighbour pairs than ``pair_capacity``; the frame's code is not written then).  It carries no regions: ``regions``
+    labels it.  ``workspace``: the tables the pass uses, kept so that a repeated call allocates nothing."""
+
+    def __init__(self, row_start, runs, H, W, target, n_absorbed, source, pair_capacity, workspace=None):
+        super().__init__(row_start, runs, H, W)
+        self.target, self.n_absorbed, self.source = target, n_absorbed, source
+        self.pair_capacity, self.workspace = int(pair_capacity), workspace
+        if not isinstance(source, RegionFrames) or (source.N, source.frames.H, source.frames.W) != (self.N, self.H, self.W):
+            raise ValueError(f"AbsorbedFrames: source must be the RegionFrames of {self.N} frames of {self.H}x{self.W} the code was made from")
+        if tuple(n_absorbed.shape) != (self.N,) or target.dim() != 2 or target.shape[0] != self.N:
+            raise ValueError(f"AbsorbedFrames: n_absorbed [{self.N}] and target [{self.N},capacity], got {tuple(n_absorbed.shape)} and "
+                             f"{tuple(target.shape)}")
+        if self.pair_capacity < 1:
+            raise ValueError(f"AbsorbedFrames: pair_capacity must be at least 1, got {pair_capacity!r}")
+
+    def _absorbed(self, what):
+        """n_absorbed on the host, after raising ``ArsegError`` for a frame that was not written."""
+        done = self.n_absorbed.cpu().numpy()
+        for n, k in enumerate(done):
+            if k == -1:
+                raise _lib.ArsegError(f"AbsorbedFrames.{what}: frame {n} could not be processed: its run code overflowed, or its regions are "
+                                      f"missing or more than the capacity {self.source.capacity} (regions {int(self.source.n_regions[n])})")
+            if k == -2:
+                raise _lib.ArsegError(f"AbsorbedFrames.{what}: frame {n} has more neighbour pairs than the pair capacity {self.pair_capacity}")
+        return done
+
+    def to_host(self):
+        """``RleFrames.to_host`` of the new code; raises ``ArsegError`` naming the frame when it could not be processed (-1) or had more
+        neighbour pairs than ``pair_capacity`` (-2)."""
+        self._absorbed("to_host")
+        return super().to_host()
+
+    def targets_to_host(self):
+        """Per frame the target of every region of the source, int32 [R]; the same errors as ``to_host``, and one for a target capacity
+        below a frame's regions."""
+        self._absorbed("targets_to_host")
+        R = self.source.n_regions.cpu().numpy()
+        for n, k in enumerate(R):
+            if k > self.target.shape[1]:
+                raise _lib.ArsegError(f"AbsorbedFrames.targets_to_host: frame {n} has {int(k)} regions, the target capacity is {self.target.shape[1]}")
+        rows = self.target[:, :int(R.max())].cpu().numpy()
+        return [rows[n, :R[n]] for n in range(self.N)]
+
+
+def absorb(regions: RegionFrames, min_area, protect=None, pair_capacity=None, out=None) -> AbsorbedFrames:
+    """The run code of ``regions.frames`` with every region below ``min_area`` pixels absorbed into the neighbour it shares the longest
+    border with, on the GPU: one call of ``ops.rle_absorb`` -> ``AbsorbedFrames`` (an ``RleFrames`` with ``.target`` and ``.n_absorbed``).
+    ``protect``: values (0..255) whose regions are never absorbed, whatever their area.  A small region goes into the STABLE neighbour
+    (``area >= min_area`` or protected) with the most 4-neighbour pixel pairs along their border, ties to the smaller region number; one
+    without a stable neighbour stays.  One pass: a second one is ``absorb(regions(result, ...), ...)``.  ``pair_capacity``: the slots of the
+    pair table, default ``3 * regions.frames.capacity`` (which cannot overflow).  ``out``: an ``AbsorbedFrames`` of the same N, H, W to write
+    into (its capacities, pair capacity and workspace hold; nothing is allocated then, and ``labels8 -> labels_rle -> rle_regions ->
+    rle_absorb -> rle_regions`` can be captured in one HIP graph)."""
+    if not isinstance(regions, RegionFrames):
+        raise ValueError("absorb: expected the RegionFrames of egress.regions")
+    src = regions.frames
+    N, H, W, cap, dev = src.N, src.H, src.W, src.capacity, src.runs.device
+    if out is None:
+        pair_capacity = 3 * cap if pair_capacity is None else int(pair_capacity)
+        if pair_capacity < 1:
+            raise ValueError(f"absorb: pair_capacity must be at least 1, got {pair_capacity}")
+        if not src.runs.is_cuda:
+            raise _lib.ArsegError("absorb runs on the GPU only (got CPU tensors); absorb_numpy is the host form")
+        _need = _lib.load().arseg_rle_absorb_workspace_bytes(N, cap, regions.capacity, H, pair_capacity)
+        out = AbsorbedFrames(torch.zeros((N, H + 1), dtype=torch.int32, device=dev), torch.empty((N, cap), dtype=torch.int32, device=dev), H, W,
+                             torch.empty((N, regions.capacity), dtype=torch.int32, device=dev), torch.empty((N,), dtype=torch.int32, device=dev),
+                             regions, pair_capacity, torch.empty((max(_need // 8, 1),), dtype=torch.int64, device=dev))
+    elif not isinstance(out, AbsorbedFrames) or (out.N, out.H, out.W) != (N, H, W):
+        raise ValueError(f"absorb: out must be AbsorbedFrames of {N} frames of {H}x{W}")
+    else:
+        out.source = regions
+    ops.rle_absorb(src.row_start, src.runs, regions.n_regions, regions.run_region, regions.records, H, W, min_area, out.row_start, out.runs,
+                   out.n_absorbed, target=out.target if out.target.shape[1] else None, protect=protect, pair_capacity=out.pair_capacity,
+                   workspace=out.workspace)
+    return out
+
+
+def absorb_numpy(row_start, runs, H, W, min_area, protect=None, connectivity=8):
+    """The same pass on a host without a GPU: one frame's ``row_start`` [H+1] and ``runs`` [>= row_start[H]] (as ``RleFrames.to_host``
+    returns them) -> ``(row_start int32 [H+1], runs uint32, target int32 [R])`` as ``AbsorbedFrames.to_host`` and ``targets_to_host`` give
+    them for that frame, the regions being those of ``regions_numpy`` at ``connectivity``.  Vectorised over the runs: the borders from the
+    neighbouring run pairs (one search over the frame for the row above), summed per pair of regions with ``np.unique``."""
+    H, W, min_area = int(H), int(W), int(min_area)
+    if min_area < 1:
+        raise ValueError(f"absorb_numpy: min_area must be at least 1, got {min_area}")
+    rec, rr = regions_numpy(row_start, runs, H, W, connectivity, return_run_region=True)
+    rr = rr.astype(np.int64)
+    R = len(rec)
+    rs = np.asarray(row_start).astype(np.int64)
+    words = (np.asarray(runs).astype(np.int64) & 0xFFFFFFFF)[:rs[H]]
+    x0, val = words >> 8, words & 0xFF
+    x1 = np.append(x0[1:], W)
+    x1[rs[1:] - 1] = W
+    row = np.repeat(np.arange(H, dtype=np.int64), np.diff(rs))
+    stable = rec["area"] >= min_area
+    if protect is not None:
+        stable |= ops.egress.protect_table(protect, "absorb_numpy")[rec["value"]]
+    # neighbouring runs: (i, i + 1) of one row with one pixel pair; a run and the runs above it that overlap it, with the overlap's length
+    left = np.flatnonzero(row[:-1] == row[1:])
+    K = W + 2
+    cur = np.flatnonzero(row > 0)
+    first = np.searchsorted(row * K + x1, (row[cur] - 1) * K + x0[cur], side="right")
+    last = np.searchsorted(row * K + x0, (row[cur] - 1) * K + x1[cur], side="left") - 1
+    count = last - first + 1
+    u = np.repeat(cur, count)
+    v = np.repeat(first, count) + np.arange(count.sum()) - np.repeat(np.cumsum(count) - count, count)
+    a = np.concatenate([rr[left], rr[left + 1], rr[u], rr[v]])
+    b = np.concatenate([rr[left + 1], rr[left], rr[v], rr[u]])
+    w = np.concatenate([np.ones(2 * len(left), dtype=np.int64), np.tile(np.minimum(x1[u], x1[v]) - np.maximum(x0[u], x0[v]), 2)])
+    voting = (a != b) & ~stable[a] & stable[b]
+    key, inverse = np.unique(a[voting] * R + b[voting], return_inverse=True)
+    border = np.bincount(inverse.reshape(-1), weights=w[voting], minlength=len(key)).astype(np.int64)
+    pa, pb = key // R, key % R
+    target = np.where(stable, -1, -2).astype(np.int32)
+    if len(key):
+        order = np.lexsort((pb, -border, pa))                # the longest border first, then the smaller region: the first of each group wins
+        best = order[np.r_[True, np.diff(pa[order]) != 0]]
+        target[pa[best]] = pb[best]
+    goes = target[rr]
+    new = np.where(goes >= 0, rec["value"][np.maximum(goes, 0)], val)
+    keep = np.r_[True, (new[1:] != new[:-1]) | (row[1:] != row[:-1])]
+    out_start = np.concatenate(([0], np.cumsum(np.bincount(row[keep], minlength=H)))).astype(np.int32)
+    return out_start, ((x0[keep] << 8) | new[keep]).astype(np.uint32), target
 
 
 class TrackIds(object):

@@ -487,6 +487,20 @@ def alter_res_batch_regions(lr_net, ref_ps, imgs, mv_qs, capacity, region_capaci
     return egress.regions(frames, region_capacity, connectivity=connectivity), labels
 
 
+def alter_res_batch_absorb(lr_net, ref_ps, imgs, mv_qs, capacity, region_capacity, min_area, scale=0.5, lut=None, labels_out=True,
+                           connectivity=8, protect=None, pair_capacity=None):
+    """``alter_res_batch_regions``'s sibling for masks without specks: the same phases, run code and regions, then ``egress.absorb`` (every
+    region below ``min_area`` pixels whose value is not in ``protect`` goes into the neighbour it shares the longest border with) and
+    ``egress.regions`` on the new code -> (``egress.RegionFrames`` of the cleaned masks, whose ``.frames`` is the ``egress.AbsorbedFrames``
+    and its ``.source`` the regions before the pass; labels uint8 [B,H,W]: the plane before the pass).  Nothing comes to the host in
+    between."""
+    from . import egress
+    found, labels = alter_res_batch_regions(lr_net, ref_ps, imgs, mv_qs, capacity, region_capacity, scale=scale, lut=lut, labels_out=labels_out,
+                                            connectivity=connectivity)
+    cleaned = egress.absorb(found, min_area, protect=protect, pair_capacity=pair_capacity)
+    return egress.regions(cleaned, region_capacity, connectivity=connectivity), labels
+
+
 def alter_res_batch_links(lr_net, ref_ps, imgs, mv_qs, key_regions, capacity, region_capacity, scale=0.5, lut=None, labels_out=True,
                           connectivity=8, pair_capacity=None):
     """``alter_res_batch_regions``'s sibling for object association: the same phases, run code and regions, then ``egress.links`` of every

@@ -2,7 +2,8 @@
 (include/arseg_hip.h, arseg_segment_egress_fwd; csrc/egress.hip); head logits -> an 8-bit confidence plane, the label plane and per-frame
 statistics, one ABI call (arseg_segment_confidence_fwd; csrc/confidence.hip); an 8-bit plane <-> its row-run code, one ABI call each
 (arseg_labels_rle_fwd / arseg_rle_decode_fwd; csrc/rle.hip); a row-run code -> its connected regions, one ABI call (arseg_rle_regions_fwd;
-csrc/regions.hip); the regions of two frames -> their links along the motion, one ABI call (arseg_region_links_fwd; csrc/links.hip)."""
+csrc/regions.hip); the regions of two frames -> their links along the motion, one ABI call (arseg_region_links_fwd; csrc/links.hip); a row-run
+code and its regions -> the code with the small regions absorbed into their neighbours, one ABI call (arseg_rle_absorb_fwd; csrc/absorb.hip)."""
 from __future__ import annotations
 
 import ctypes
@@ -405,3 +406,76 @@ def region_links(row_start: torch.Tensor, runs: torch.Tensor, n_regions: torch.T
            workspace.numel() * workspace.element_size(), _stream(),
            nbytes=(4 * N * H * W if mv_q is not None else 0) + 64 * N * pcap)          # the field once from HBM; the tables cleared and read
     return n_pairs, links, back
+
+
+def protect_table(protect, what="protect"):
+    """The protected values of ``rle_absorb`` -- any collection of integers 0..255, or a table of 256 boolean flags -> the 256 flags."""
+    flags = np.asarray(sorted(protect) if isinstance(protect, (set, frozenset)) else protect)
+    if flags.dtype == np.bool_ and flags.shape == (256,):
+        return flags.copy()
+    values = flags.reshape(-1)
+    if values.size and (not np.issubdtype(values.dtype, np.integer) or values.min() < 0 or values.max() > 255):
+        raise ValueError(f"{what}: protect holds values 0..255 (or 256 boolean flags), got {values.dtype} {values.shape}")
+    table = np.zeros(256, dtype=bool)
+    table[values.astype(np.int64)] = True
+    return table
+
+
+def rle_absorb(row_start: torch.Tensor, runs: torch.Tensor, n_regions: torch.Tensor, run_region: torch.Tensor, regions: torch.Tensor, H: int,
+               W: int, min_area: int, out_row_start: torch.Tensor, out_runs: torch.Tensor, n_absorbed: torch.Tensor,
+               target: Optional[torch.Tensor] = None, protect=None, pair_capacity: Optional[int] = None,
+               workspace: Optional[torch.Tensor] = None):
+    """The small regions of a row-run code absorbed into their neighbours (include/arseg_hip.h, arseg_rle_absorb_fwd): ``row_start`` int32
+    [N,H+1], ``runs`` 32-bit [N,cap], ``n_regions`` int32 [N], ``run_region`` int32 [N,cap] and ``regions`` int64 [N,rcap,8] as
+    ``labels_rle`` + ``rle_regions`` wrote them -> ``out_row_start`` int32 [N,H+1] and ``out_runs`` 32-bit [N,out_cap]: the run code of the
+    plane in which every region below ``min_area`` pixels whose value is not in ``protect`` (host values 0..255, or a table of 256 flags) has
+    taken the value of the stable neighbour it shares the longest 4-neighbour border with (ties to the smaller region number; none: it
+    stays); ``n_absorbed`` int32 [N] (the regions absorbed; -1: the run code overflowed, or the regions are missing or more than rcap;
+    -2: more than ``pair_capacity`` neighbour pairs; either way nothing else of the frame is touched) and, when given, ``target`` int32
+    [N,tcap] (-1 stable, -2 small and left alone, else the region it went into).  ``pair_capacity``: the slots of the pair table (default
+    ``3 * cap``, which cannot overflow).  ``workspace``: a device tensor of at least ``arseg_rle_absorb_workspace_bytes(N, cap, rcap, H,
+    pair_capacity)`` bytes, 8-byte aligned (default: the stream's shared workspace).  With every buffer given nothing is allocated and
+    nothing synchronises: capturable in a HIP graph.  Returns (out_row_start, out_runs, target, n_absorbed)."""
+    what = "rle_absorb"
+    H, W = int(H), int(W)
+    if H <= 0 or W <= 0 or W > 1 << 24 or H * W > 2 ** 31 - 1:
+        raise ValueError(f"{what}: 0 < W <= 2^24 and 0 < H * W < 2^31, got {H}x{W}")
+    min_area = int(min_area)
+    if min_area < 1:
+        raise ValueError(f"{what}: min_area must be at least 1, got {min_area}")
+    N, cap = _links_side(what, "", H, row_start, runs, n_regions, run_region)
+    dev = row_start.device
+    _need_gpu(regions, dtype=torch.int64)
+    if regions.dim() != 3 or regions.shape[0] != N or regions.shape[2] != 8 or not regions.is_contiguous() or regions.device != dev:
+        raise _lib.ArsegError(f"{what}: regions must be a contiguous int64 [{N}, rcap, 8] tensor on {dev}, got {tuple(regions.shape)}")
+    rcap = int(regions.shape[1])
+    if rcap == 0:
+        raise ValueError(f"{what}: the record buffer holds no region (capacity 0)")
+    out_cap = _rle_common(what, N, H, dev, out_row_start, out_runs, True)
+    if out_cap == 0:
+        raise ValueError(f"{what}: the output run buffer holds no run (capacity 0)")
+    _need_gpu(n_absorbed, dtype=torch.int32)
+    if tuple(n_absorbed.shape) != (N,) or not n_absorbed.is_contiguous() or n_absorbed.device != dev:
+        raise _lib.ArsegError(f"{what}: n_absorbed must be a contiguous int32 [{N}] tensor on {dev}, got {tuple(n_absorbed.shape)}")
+    tcap = 0
+    if target is not None:
+        _need_gpu(target, dtype=torch.int32)
+        if target.dim() != 2 or target.shape[0] != N or not target.is_contiguous() or target.device != dev:
+            raise _lib.ArsegError(f"{what}: target must be a contiguous int32 [{N}, capacity] tensor on {dev}, got {tuple(target.shape)}")
+        tcap = int(target.shape[1])
+    protect_c = None if protect is None else _host_u8(protect_table(protect, what), 256, "protect")
+    pcap = 3 * cap if pair_capacity is None else int(pair_capacity)
+    if pcap < 1:
+        raise ValueError(f"{what}: pair_capacity must be at least 1, got {pair_capacity!r}")
+    lib = _lib.load()
+    nbytes = lib.arseg_rle_absorb_workspace_bytes(N, cap, rcap, H, pcap)
+    if workspace is None:
+        workspace = _workspace(nbytes, dev)
+    elif not workspace.is_cuda or workspace.device != dev or not workspace.is_contiguous() or workspace.data_ptr() % 8 or \
+            workspace.numel() * workspace.element_size() < nbytes:
+        raise _lib.ArsegError(f"{what}: workspace must be a contiguous, 8-byte aligned tensor of at least {nbytes} bytes on {dev}")
+    launch(what, lib.arseg_rle_absorb_fwd, _ptr(row_start), _ptr(runs), _ptr(n_regions), _ptr(run_region), cap, _ptr(regions), rcap, N, H, W,
+           min_area, protect_c, _ptr(out_row_start), _ptr(out_runs), out_cap, _ptr(target if tcap else None), tcap, _ptr(n_absorbed), pcap,
+           _ptr(workspace), workspace.numel() * workspace.element_size(), _stream(),
+           nbytes=32 * N * pcap + 12 * N * (H + 1))          # the table cleared and read (+ about 40 bytes per run, known on the device only)
+    return out_row_start, out_runs, target, n_absorbed

@@ -818,8 +818,9 @@ int arseg_rle_decode_fwd(const int32_t *row_start, const uint32_t *runs, int64_t
  * ARSEG_EINVAL, before any launch: null row_start, runs, n_regions or run_region; one of them or the workspace not 4-byte aligned, regions
  *   not 8-byte aligned; non-positive N, H or W; cap <= 0; rcap < 0; regions == NULL with rcap > 0; connectivity other than 4 or 8;
  *   W > 1 << 24; H * W > INT32_MAX; a null workspace.
- * Not covered: a dense 32-bit instance-id plane; removing or merging small regions; contours or polygons; regions across frames; the
- *   labelling fused into the run coder.  (Which region of another frame a region came from: arseg_region_links_fwd, below.)
+ * Not covered: a dense 32-bit instance-id plane; contours or polygons; regions across frames; the labelling fused into the run coder.
+ *   (Which region of another frame a region came from: arseg_region_links_fwd, below.  Removing or merging small regions:
+ *   arseg_rle_absorb_fwd, below.)
  * ------------------------------------------------------------------------------------------- */
 size_t arseg_rle_regions_workspace_bytes(int N, int64_t cap);
 int arseg_rle_regions_fwd(const int32_t *row_start, const uint32_t *runs, int64_t cap, int N, int H, int W, int connectivity,
@@ -877,6 +878,58 @@ int arseg_region_links_fwd(const int32_t *row_start, const uint32_t *runs, const
                            const int32_t *ref_run_region, int64_t ref_cap, int ref_shared, const int16_t *mv_q, int N, int H, int W,
                            int32_t *n_pairs, int64_t *links, int64_t rcap, int64_t *back, int64_t kcap, int64_t pcap, void *workspace,
                            size_t workspace_bytes, arseg_stream_t stream);
+
+/* ---------------------------------------------------------------------------------------------
+ * Small regions absorbed into their neighbours (csrc/absorb.hip): the specks of a mask -- few-pixel islands of another class along object
+ * borders and where the motion field tears -- take the value of the neighbour they share the longest border with, on the run code (a few
+ * thousand words per frame, not the plane) and on the device, without a host synchronisation: capturable in a HIP graph behind
+ * arseg_rle_regions_fwd.
+ * Input: row_start int32 [N][H+1], runs uint32 [N][cap], n_regions int32 [N], run_region int32 [N][cap] and regions int64 [N][rcap][8]
+ *   exactly as arseg_labels_rle_fwd + arseg_rle_regions_fwd leave them (either connectivity); the same N, H, W; min_area >= 1; protect: a
+ *   host table of 256 bytes or NULL, read during the call and handed to the kernels by value, as lut is.
+ * Definitions, all integer.  Region r is PROTECTED iff protect && protect[value_r]; STABLE iff area_r >= min_area or it is protected; SMALL
+ *   otherwise.  border(r, s), r != s: the number of 4-neighbour pixel pairs (p, q) with p in r and q in s, whatever connectivity the
+ *   regions were labelled with.  In runs: two consecutive runs of one row add 1 to the pair of their regions; run i of row y over [a0, a1)
+ *   and run j of row y-1 over [b0, b1) of different regions add min(a1, b1) - max(a0, b0) when that is positive.
+ *   target(r) of a small r: the stable s with the largest border(r, s), ties to the smaller s.  A small region without a stable neighbour
+ *   has no target and stays as it is.  One pass, no cascade: every decision reads the input only, so the result does not depend on timing;
+ *   a caller who wants a second pass labels the output and calls again.
+ *   The new value of a run: value_target(r) if its region r is small and has a target, its own value otherwise.
+ * Outputs, all integers, all OVERWRITTEN:
+ *   out_row_start int32 [N][H+1], out_runs uint32 [N][out_cap]: the row-run code of the resulting plane, word for word what
+ *               arseg_labels_rle_fwd writes for the decoded, re-valued plane: neighbouring runs of a row whose new values are equal are
+ *               one run.  The encoder's overflow rule: out_row_start[n][H] is always exact, a word whose index is >= out_cap is not
+ *               written, nothing at or past out_runs[n][out_cap] is touched.  The output never needs more runs than the input:
+ *               out_cap = cap cannot overflow.
+ *   target      int32 [N][tcap]: per region below min(R, tcap) -1: stable, -2: small and left alone, else the s it was absorbed into; the
+ *               rows from there on are untouched.  target == NULL with tcap == 0: not wanted.
+ *   n_absorbed  int32 [N]: the number of regions with a target; or
+ *                 -1  the frame cannot be processed: row_start[n][H] > cap, n_regions[n] < 0, or n_regions[n] > rcap (the area of every
+ *                     region is needed).  Nothing else of that frame is touched, out_row_start[n] included.
+ *                 -2  more than pcap distinct (small, stable) neighbour pairs.  Nothing else of that frame is touched either.
+ *   The output carries no run_region: merged runs can join what were two regions.  The caller labels it with arseg_rle_regions_fwd.
+ *   min_area == 1: every region is stable, the output code equals the input code, target is all -1 and n_absorbed 0.
+ * workspace: the caller's, 8-byte aligned, >= arseg_rle_absorb_workspace_bytes(N, cap, rcap, H, pcap) bytes (else ARSEG_EWORKSPACE): per
+ *   frame an open addressed table of pcap slots for the pairs (a 64-bit key and a 64-bit border), one 64-bit word per region record and a
+ *   flag.  Probing visits every slot before it gives up, so an insert fails if and only if the frame has more than pcap distinct pairs: -2
+ *   does not depend on timing.  A frame's distinct neighbouring run pairs are at most 3 x row_start[n][H] (runs - H in the rows, fewer
+ *   than 2 x runs between rows), so pcap = 3 x cap can never give -2.  Its contents are scratch.
+ * Six launches (clear + classify, vote, resolve, count, scan, emit); nothing is written into an output before the vote is known to have
+ *   fitted; no workgroup waits for another.  Enqueue only: no allocation, no synchronisation.  The buffers must not overlap.
+ * Malformed input (a run_region outside [0, R), a row_start that does not rise, x_first out of order) gives a meaningless code, but nothing
+ *   outside the caller's buffers is read or written: indices and columns are clamped as arseg_rle_regions_fwd clamps them, and every loop
+ *   is bounded.
+ * ARSEG_EINVAL, before any launch: a null row_start, runs, n_regions, run_region, regions, out_row_start, out_runs or n_absorbed; one of
+ *   them (regions apart) or target not 4-byte aligned; regions or the workspace not 8-byte aligned; non-positive N, H, W, cap, pcap or
+ *   out_cap; min_area < 1; negative rcap or tcap; target == NULL with tcap > 0; W > 1 << 24; H * W > INT32_MAX; a null workspace.
+ * Not covered: cascaded absorption inside one call; criteria other than the area (confidence, shape); filling holes only; morphological
+ *   opening or closing; region or track ids carried across the rewrite; the pass fused into the run coder.
+ * ------------------------------------------------------------------------------------------- */
+size_t arseg_rle_absorb_workspace_bytes(int N, int64_t cap, int64_t rcap, int H, int64_t pcap);
+int arseg_rle_absorb_fwd(const int32_t *row_start, const uint32_t *runs, const int32_t *n_regions, const int32_t *run_region, int64_t cap,
+                         const int64_t *regions, int64_t rcap, int N, int H, int W, int64_t min_area, const uint8_t *protect,
+                         int32_t *out_row_start, uint32_t *out_runs, int64_t out_cap, int32_t *target, int64_t tcap, int32_t *n_absorbed,
+                         int64_t pcap, void *workspace, size_t workspace_bytes, arseg_stream_t stream);
 
 /* ---------------------------------------------------------------------------------------------
  * Measurement aids (no reference counterpart; BASELINE.md section 3: roofline fractions are reported against the datasheet peaks AND
