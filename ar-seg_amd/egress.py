@@ -816,6 +816,184 @@ def absorb_numpy(row_start, runs, H, W, min_area, protect=None, connectivity=8):
     return out_start, ((x0[keep] << 8) | new[keep]).astype(np.uint32), target
 
 
+class ContourFrames(object):
+    """The outlines of the regions of ``source`` (a ``RegionFrames``; include/arseg_hip.h, arseg_rle_contours_fwd), on the device: ``counts``
+    int32 [N,2] (the loops and the vertices of each frame, exact whatever the capacities; -1, -1: the frame could not be processed),
+    ``loops`` int32 [N,loop_capacity,4] (``region, first, count, hole`` per loop) and ``verts`` 32-bit [N,vertex_capacity] (the corners of
+    the loops one after the other, ``y << 16 | x``).  ``workspace``: the scratch the pass uses, kept so that a repeated call allocates
+    nothing."""
+
+    def __init__(self, counts, loops, verts, source, workspace=None):
+        self.counts, self.loops, self.verts, self.source, self.workspace = counts, loops, verts, source, workspace
+        if not isinstance(source, RegionFrames):
+            raise ValueError("ContourFrames: source must be the RegionFrames the outlines were traced from")
+        N = source.N
+        if tuple(counts.shape) != (N, 2) or loops.dim() != 3 or loops.shape[0] != N or loops.shape[2] != 4 or verts.dim() != 2 or \
+                verts.shape[0] != N:
+            raise ValueError(f"ContourFrames: counts [{N},2], loops [{N},capacity,4] and verts [{N},capacity], got {tuple(counts.shape)}, "
+                             f"{tuple(loops.shape)} and {tuple(verts.shape)}")
+
+    @property
+    def N(self):
+        return self.source.N
+
+    @property
+    def loop_capacity(self):
+        return self.loops.shape[1]
+
+    @property
+    def vertex_capacity(self):
+        return self.verts.shape[1]
+
+    def needed(self) -> torch.Tensor:
+        """The loops and vertices each frame needs (a device view, int32 [N,2]): exact whatever the capacities; a value above its capacity
+        is an overflow, -1 a frame that could not be processed."""
+        return self.counts
+
+    def to_host(self):
+        """Per frame a list of ``(region, hole, int32 [k,2] array of (x, y))``, one entry per loop in the contract's order (outer loops
+        clockwise on the screen, holes counter-clockwise), in three copies: the counts, then the loops and vertices up to the largest
+        need.  Raises ``ArsegError`` naming the frame when it could not be processed or needs more loops or vertices than the capacity."""
+        need = self.counts.cpu().numpy()
+        for n, (L, V) in enumerate(need):
+            if L < 0:
+                raise _lib.ArsegError(f"ContourFrames.to_host: frame {n} could not be processed: its run code overflowed or it has no regions "
+                                      f"(regions {int(self.source.n_regions[n])})")
+            if L > self.loop_capacity or V > self.vertex_capacity:
+                raise _lib.ArsegError(f"ContourFrames.to_host: frame {n} needs {int(L)} loops and {int(V)} vertices, the capacities are "
+                                      f"{self.loop_capacity} and {self.vertex_capacity}")
+        rows = self.loops[:, :int(need[:, 0].max())].cpu().numpy()
+        words = self.verts[:, :int(need[:, 1].max())].cpu().numpy().view(np.uint32)
+        return [_polygons(rows[n, :need[n, 0]], words[n, :need[n, 1]]) for n in range(self.N)]
+
+
+def _polygons(loops, verts):
+    """One frame's loop records and vertex words -> [(region, hole, int32 [k,2] of (x, y))]."""
+    return [(int(r), int(hole), np.stack([verts[first:first + count] & 0xFFFF, verts[first:first + count] >> 16], axis=1).astype(np.int32))
+            for r, first, count, hole in loops]
+
+
+def contours(regions: RegionFrames, loop_capacity=None, vertex_capacity=None, out=None) -> ContourFrames:
+    """The outlines of the regions as closed polygon loops, traced on the GPU from the run code: one call of ``ops.rle_contours`` ->
+    ``ContourFrames``.  A vertex is a corner of the pixel grid; every loop has its region on the right hand (outer loops clockwise on the
+    screen, holes counter-clockwise), holds corners only and begins at its smallest vertex in (y, x) order; where a region touches itself
+    across a corner the loop joins the two pixels at ``regions.connectivity`` 8 and parts them at 4.  The capacities default to the bounds
+    that cannot overflow: one loop and four vertices per run.  ``out``: a ``ContourFrames`` of the same N to write into (its capacities
+    and workspace hold; nothing is allocated then, and ``labels8 -> labels_rle -> rle_regions -> rle_contours`` can be captured in one HIP
+    graph)."""
+    if not isinstance(regions, RegionFrames):
+        raise ValueError("contours: expected the RegionFrames of egress.regions")
+    src = regions.frames
+    N, H, W, cap, dev = src.N, src.H, src.W, src.capacity, src.runs.device
+    if out is None:
+        loop_capacity = cap if loop_capacity is None else int(loop_capacity)
+        vertex_capacity = 4 * cap if vertex_capacity is None else int(vertex_capacity)
+        if loop_capacity < 0 or vertex_capacity < 0:
+            raise ValueError(f"contours: the capacities must not be negative, got {loop_capacity} and {vertex_capacity}")
+        if not src.runs.is_cuda:
+            raise _lib.ArsegError("contours runs on the GPU only (got CPU tensors); contours_numpy is the host form")
+        _need = _lib.load().arseg_rle_contours_workspace_bytes(N, cap)
+        out = ContourFrames(torch.empty((N, 2), dtype=torch.int32, device=dev), torch.empty((N, loop_capacity, 4), dtype=torch.int32, device=dev),
+                            torch.empty((N, vertex_capacity), dtype=torch.int32, device=dev), regions,
+                            torch.empty((max(_need // 16, 1), 4), dtype=torch.int32, device=dev))
+    elif not isinstance(out, ContourFrames) or out.N != N:
+        raise ValueError(f"contours: out must be ContourFrames of {N} frames")
+    else:
+        out.source = regions
+    ops.rle_contours(src.row_start, src.runs, regions.n_regions, regions.run_region, H, W, out.counts,
+                     loops=out.loops if out.loop_capacity else None, verts=out.verts if out.vertex_capacity else None,
+                     connectivity=regions.connectivity, workspace=out.workspace)
+    return out
+
+
+def contours_numpy(row_start, runs, H, W, connectivity=8):
+    """The same pass on a host without a GPU: one frame's ``row_start`` [H+1] and ``runs`` [>= row_start[H]] (as ``RleFrames.to_host``
+    returns them) -> ``(counts int32 [2], loops int32 [L,4], verts uint32 [V])`` as arseg_rle_contours_fwd leaves them with room for
+    everything, the regions being those of ``regions_numpy`` at ``connectivity``.  Every run gives two vertical edges (its left end
+    travelled upwards, its right end downwards); the edge that follows an edge along its loop is found from the neighbouring row, and the
+    cycles of that permutation are the loops."""
+    H, W = int(H), int(W)
+    if H > 65535 or W > 65535:
+        raise ValueError(f"contours_numpy: H and W at most 65535 (a vertex is y << 16 | x), got {H}x{W}")
+    _, rr = regions_numpy(row_start, runs, H, W, connectivity, return_run_region=True)
+    eight = connectivity == 8
+    rs = np.asarray(row_start).astype(np.int64)
+    words = (np.asarray(runs).astype(np.int64) & 0xFFFFFFFF)[:rs[H]]
+    n = len(words)
+    x0, val = (words >> 8).tolist(), (words & 0xFF).tolist()
+    x1 = np.append(words[1:] >> 8, W)
+    x1[rs[1:] - 1] = W
+    x1 = x1.tolist()
+    rs = rs.tolist()
+    starts = np.asarray(x0)
+    succ, end = [0] * (2 * n), [0] * (2 * n)                  # the edge after edge e = 2 * run + side, and the corner where it starts
+
+    def cover(y, x):                                          # the run of row y that covers column x
+        return rs[y] + int(np.searchsorted(starts[rs[y]:rs[y + 1]], x, side="right")) - 1
+
+    def east(t, Y, v, j, stop):                               # along the top of run t (row Y) to the first run >= j above with value v
+        while j < stop and (x0[j] <= x1[t] if eight else x0[j] < x1[t]):
+            if val[j] == v:
+                return 2 * j, (Y << 16) | x0[j]
+            j += 1
+        return 2 * t + 1, (Y << 16) | x1[t]
+
+    def west(t, Y, v, k, stop):                               # along the bottom of run t (row Y - 1) to the last run <= k below with value v
+        while k >= stop and (x1[k] >= x0[t] if eight else x1[k] > x0[t]):
+            if val[k] == v:
+                return 2 * k + 1, (Y << 16) | x1[k]
+            k -= 1
+        return 2 * t, (Y << 16) | x0[t]
+
+    for y in range(H):
+        for i in range(rs[y], rs[y + 1]):
+            a0, a1, v = x0[i], x1[i], val[i]
+            if y == 0:                                        # the left end, arriving at (a0, y)
+                succ[2 * i], end[2 * i] = east(i, y, v, 0, 0)
+            else:
+                p = cover(y - 1, a0)
+                ur = val[p] == v
+                ul = a0 > 0 and (ur if x0[p] < a0 else val[p - 1] == v)
+                if ur and not ul:
+                    succ[2 * i], end[2 * i] = 2 * p, (y << 16) | a0
+                elif ur or (eight and ul):
+                    succ[2 * i], end[2 * i] = west(p if ur else p - 1, y, v, i - 1, rs[y])
+                else:
+                    succ[2 * i], end[2 * i] = east(i, y, v, p + 1, rs[y])
+            e = 2 * i + 1
+            if y == H - 1:                                    # the right end, arriving at (a1, y + 1)
+                succ[e], end[e] = west(i, y + 1, v, -1, 0)
+            else:
+                p = cover(y + 1, a1 - 1)
+                bl = val[p] == v
+                br = a1 < W and (bl if x1[p] > a1 else val[p + 1] == v)
+                if bl and not br:
+                    succ[e], end[e] = 2 * p + 1, ((y + 1) << 16) | a1
+                elif bl or (eight and br):
+                    succ[e], end[e] = east(p if bl else p + 1, y + 1, v, i + 1, rs[y + 1])
+                else:
+                    succ[e], end[e] = west(i, y + 1, v, p, rs[y + 1])
+    loops, verts, seen = [], [], [False] * (2 * n)
+    row = np.repeat(np.arange(H), np.diff(rs)).tolist()
+    for lead in range(2 * n):                                 # the smallest edge of every cycle, in rising order
+        if seen[lead]:
+            continue
+        pts, e = [], lead
+        while not seen[e]:
+            seen[e] = True
+            i = e >> 1
+            own = ((row[i] + 1) << 16 | x1[i]) if e & 1 else (row[i] << 16 | x0[i])
+            if end[e] != own:
+                pts += [own, end[e]]
+            e = succ[e]
+        if lead & 1:                                          # a hole begins where its smallest edge starts
+            pts = pts[-1:] + pts[:-1]
+        loops.append((rr[lead >> 1], len(verts), len(pts), lead & 1))
+        verts += pts
+    return (np.array([len(loops), len(verts)], dtype=np.int32), np.array(loops, dtype=np.int32).reshape(-1, 4),
+            np.array(verts, dtype=np.uint32))
+
+
 class TrackIds(object):
     """Persistent ids for the regions of a stream, from the links alone.  Pure Python on the ``links`` arrays of ``LinkFrames.to_host`` /
     ``links_numpy``; it has no thresholds -- what to do with a short-lived id is the caller's business.

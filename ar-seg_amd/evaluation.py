@@ -501,6 +501,23 @@ def alter_res_batch_absorb(lr_net, ref_ps, imgs, mv_qs, capacity, region_capacit
     return egress.regions(cleaned, region_capacity, connectivity=connectivity), labels
 
 
+def alter_res_batch_contours(lr_net, ref_ps, imgs, mv_qs, capacity, region_capacity, scale=0.5, lut=None, labels_out=True, connectivity=8,
+                             min_area=None, protect=None, pair_capacity=None, loop_capacity=None, vertex_capacity=None):
+    """``alter_res_batch_regions``'s sibling for vector outlines: the same phases, run code and regions, then ``egress.contours`` ->
+    (``egress.ContourFrames``, whose ``.source`` is the ``egress.RegionFrames`` the outlines belong to; labels uint8 [B,H,W]).  With
+    ``min_area`` the specks are absorbed first (``alter_res_batch_absorb``: ``egress.absorb`` + ``egress.regions``) and the outlines are
+    those of the cleaned masks; labels stay the plane before the pass.  Nothing comes to the host in between;
+    ``ContourFrames.to_host()`` brings the polygons over."""
+    from . import egress
+    if min_area is None:
+        found, labels = alter_res_batch_regions(lr_net, ref_ps, imgs, mv_qs, capacity, region_capacity, scale=scale, lut=lut,
+                                                labels_out=labels_out, connectivity=connectivity)
+    else:
+        found, labels = alter_res_batch_absorb(lr_net, ref_ps, imgs, mv_qs, capacity, region_capacity, min_area, scale=scale, lut=lut,
+                                               labels_out=labels_out, connectivity=connectivity, protect=protect, pair_capacity=pair_capacity)
+    return egress.contours(found, loop_capacity=loop_capacity, vertex_capacity=vertex_capacity), labels
+
+
 def alter_res_batch_links(lr_net, ref_ps, imgs, mv_qs, key_regions, capacity, region_capacity, scale=0.5, lut=None, labels_out=True,
                           connectivity=8, pair_capacity=None):
     """``alter_res_batch_regions``'s sibling for object association: the same phases, run code and regions, then ``egress.links`` of every

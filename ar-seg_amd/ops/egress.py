@@ -479,3 +479,53 @@ def rle_absorb(row_start: torch.Tensor, runs: torch.Tensor, n_regions: torch.Ten
            _ptr(workspace), workspace.numel() * workspace.element_size(), _stream(),
            nbytes=32 * N * pcap + 12 * N * (H + 1))          # the table cleared and read (+ about 40 bytes per run, known on the device only)
     return out_row_start, out_runs, target, n_absorbed
+
+
+def rle_contours(row_start: torch.Tensor, runs: torch.Tensor, n_regions: torch.Tensor, run_region: torch.Tensor, H: int, W: int,
+                 counts: torch.Tensor, loops: Optional[torch.Tensor] = None, verts: Optional[torch.Tensor] = None, connectivity: int = 8,
+                 workspace: Optional[torch.Tensor] = None):
+    """The outlines of the regions of a row-run code as closed polygon loops (include/arseg_hip.h, arseg_rle_contours_fwd): ``row_start``
+    int32 [N,H+1], ``runs`` 32-bit [N,cap], ``n_regions`` int32 [N] and ``run_region`` int32 [N,cap] as ``labels_rle`` + ``rle_regions``
+    wrote them, ``connectivity`` the value the regions were labelled with -> ``counts`` int32 [N,2] (the loops and vertices of each frame,
+    exact whatever the capacities; -1, -1: the run code overflowed or the regions are missing, nothing else of the frame is touched) and,
+    when given, ``loops`` int32 [N,lcap,4] (``region, first, count, hole`` per loop) and ``verts`` 32-bit [N,vcap] (the corners, ``y << 16 |
+    x``), exact below the counts and untouched from there on.  ``lcap = cap`` and ``vcap = 4 * cap`` cannot overflow.  ``workspace``: a
+    device tensor of at least ``arseg_rle_contours_workspace_bytes(N, cap)`` bytes (default: the stream's shared workspace).  With every
+    buffer given nothing is allocated and nothing synchronises: capturable in a HIP graph.  Returns (counts, loops, verts)."""
+    what = "rle_contours"
+    H, W = int(H), int(W)
+    if H <= 0 or W <= 0 or H > 65535 or W > 65535:
+        raise ValueError(f"{what}: 0 < H <= 65535 and 0 < W <= 65535 (a vertex is y << 16 | x), got {H}x{W}")
+    if connectivity not in (4, 8):
+        raise ValueError(f"{what}: connectivity is 4 or 8, got {connectivity!r}")
+    N, cap = _links_side(what, "", H, row_start, runs, n_regions, run_region)
+    if cap > 1 << 29:
+        raise ValueError(f"{what}: at most 2^29 runs per frame, got a capacity of {cap}")
+    dev = row_start.device
+    _need_gpu(counts, dtype=torch.int32)
+    if tuple(counts.shape) != (N, 2) or not counts.is_contiguous() or counts.device != dev:
+        raise _lib.ArsegError(f"{what}: counts must be a contiguous int32 {(N, 2)} tensor on {dev}, got {tuple(counts.shape)}")
+    lcap = vcap = 0
+    if loops is not None:
+        _need_gpu(loops, dtype=torch.int32)
+        if loops.dim() != 3 or loops.shape[0] != N or loops.shape[2] != 4 or not loops.is_contiguous() or loops.device != dev:
+            raise _lib.ArsegError(f"{what}: loops must be a contiguous int32 [{N}, capacity, 4] tensor on {dev}, got {tuple(loops.shape)}")
+        lcap = int(loops.shape[1])
+    if verts is not None:
+        _need_gpu(verts, dtype=None)
+        if verts.dtype not in _RUN_DTYPES or verts.dim() != 2 or verts.shape[0] != N or not verts.is_contiguous() or verts.device != dev:
+            raise _lib.ArsegError(f"{what}: verts must be a contiguous 32-bit [{N}, capacity] tensor on {dev}, got {verts.dtype} "
+                                  f"{tuple(verts.shape)}")
+        vcap = int(verts.shape[1])
+    lib = _lib.load()
+    nbytes = lib.arseg_rle_contours_workspace_bytes(N, cap)
+    if workspace is None:
+        workspace = _workspace(nbytes, dev)
+    elif not workspace.is_cuda or workspace.device != dev or not workspace.is_contiguous() or workspace.data_ptr() % 4 or \
+            workspace.numel() * workspace.element_size() < nbytes:
+        raise _lib.ArsegError(f"{what}: workspace must be a contiguous, 4-byte aligned tensor of at least {nbytes} bytes on {dev}")
+    launch(what, lib.arseg_rle_contours_fwd, _ptr(row_start), _ptr(runs), _ptr(n_regions), _ptr(run_region), cap, N, H, W, int(connectivity),
+           _ptr(counts), _ptr(loops if lcap else None), lcap, _ptr(verts if vcap else None), vcap, _ptr(workspace),
+           workspace.numel() * workspace.element_size(), _stream(),
+           nbytes=4 * N * (H + 1))          # (+ about 80 bytes per run and round of jumping, known on the device only)
+    return counts, loops, verts

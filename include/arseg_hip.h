@@ -652,8 +652,8 @@ int arseg_argmax_confusion_grouped_fwd(const float *logits, const int64_t *label
  * src0, palette or weights (or without the format's further planes on either side); n_cls < 1 or > 32; a weight above 256; a non-positive
  * size; odd H or W with NV12 / I420; a pitch smaller than a row; a negative image stride; a format other than the three above (P010 / I010
  * are rejected).
- * Not covered: 10-bit, 4:2:2 or 4:4:4 destinations; text, legends or contours; the encoder; the confusion histogram (evaluation keeps
- * arseg_argmax_confusion_fwd).
+ * Not covered: 10-bit, 4:2:2 or 4:4:4 destinations; text or legends; the encoder; the confusion histogram (evaluation keeps
+ * arseg_argmax_confusion_fwd).  (The outlines of the mask's regions as polygons, for a vector overlay: arseg_rle_contours_fwd, below.)
  * ------------------------------------------------------------------------------------------- */
 int arseg_segment_egress_fwd(const float *logits, int N, int n_cls, int h, int w, int H, int W, int align_corners, const uint8_t *lut,
                              uint8_t *labels8, int64_t labels_pitch, int64_t labels_n_stride, int format, const void *src0, const void *src1,
@@ -818,9 +818,9 @@ int arseg_rle_decode_fwd(const int32_t *row_start, const uint32_t *runs, int64_t
  * ARSEG_EINVAL, before any launch: null row_start, runs, n_regions or run_region; one of them or the workspace not 4-byte aligned, regions
  *   not 8-byte aligned; non-positive N, H or W; cap <= 0; rcap < 0; regions == NULL with rcap > 0; connectivity other than 4 or 8;
  *   W > 1 << 24; H * W > INT32_MAX; a null workspace.
- * Not covered: a dense 32-bit instance-id plane; contours or polygons; regions across frames; the labelling fused into the run coder.
+ * Not covered: a dense 32-bit instance-id plane; regions across frames; the labelling fused into the run coder.
  *   (Which region of another frame a region came from: arseg_region_links_fwd, below.  Removing or merging small regions:
- *   arseg_rle_absorb_fwd, below.)
+ *   arseg_rle_absorb_fwd, below.  The regions' outlines as polygons: arseg_rle_contours_fwd, below.)
  * ------------------------------------------------------------------------------------------- */
 size_t arseg_rle_regions_workspace_bytes(int N, int64_t cap);
 int arseg_rle_regions_fwd(const int32_t *row_start, const uint32_t *runs, int64_t cap, int N, int H, int W, int connectivity,
@@ -930,6 +930,56 @@ int arseg_rle_absorb_fwd(const int32_t *row_start, const uint32_t *runs, const i
                          const int64_t *regions, int64_t rcap, int N, int H, int W, int64_t min_area, const uint8_t *protect,
                          int32_t *out_row_start, uint32_t *out_runs, int64_t out_cap, int32_t *target, int64_t tcap, int32_t *n_absorbed,
                          int64_t pcap, void *workspace, size_t workspace_bytes, arseg_stream_t stream);
+
+/* ---------------------------------------------------------------------------------------------
+ * Region outlines as polygon loops (csrc/contours.hip): the shape of every region as closed loops of grid corners -- what an annotation
+ * tool, a geo or CAD layer, a browser overlay or a shape matcher takes -- traced on the device from the run code alone (its run ends are
+ * the vertical boundary segments of the mask; the plane is not read), without a host synchronisation: capturable in a HIP graph behind
+ * arseg_rle_regions_fwd.
+ * Input: row_start int32 [N][H+1], runs uint32 [N][cap], n_regions int32 [N] and run_region int32 [N][cap] exactly as
+ *   arseg_labels_rle_fwd + arseg_rle_regions_fwd leave them; the same N, H, W and cap; connectivity: the value the regions were labelled
+ *   with (4 or 8).
+ * Geometry.  Pixel (x, y) is the unit square [x, x+1] x [y, y+1].  A vertex is a grid corner (x, y), 0 <= x <= W, 0 <= y <= H, stored as
+ *   the word y << 16 | x.  The boundary of region r is the set of unit edges between a pixel of r and a pixel that is not of r; the image
+ *   border counts as a boundary.  Each edge is directed so that r lies on its right hand on the screen (y down): heading (hx, hy) has its
+ *   right at (-hy, hx).  Outer loops therefore run clockwise on the screen and holes counter-clockwise.  At a vertex where r holds exactly
+ *   two diagonal pixels (a saddle) the walk turns left when connectivity == 8 (the diagonal pixels are joined) and right when
+ *   connectivity == 4; everywhere else the continuation is unique.  The edges of r fall into closed loops.  A loop is stored as its
+ *   corners only: collinear vertices are dropped, so consecutive vertices differ in exactly one coordinate and the axes alternate.  A loop
+ *   may pass through one vertex twice (a saddle).
+ * Canonical form: the output is a pure function of the input.  A loop starts at its smallest vertex in (y, x) order (it is visited once).
+ *   The loops of a frame are ordered by rising first vertex in (y, x) order; where two loops start at one vertex -- a hole and the outer
+ *   loop of the region inside it -- the hole comes first.  In runs: every run has two vertical edges, 2 run + side with left end = 0 and
+ *   right end = 1; the loops are ordered by their smallest edge, and a loop whose smallest edge is a right end is a hole.
+ * Outputs, all integers, all OVERWRITTEN:
+ *   counts      int32 [N][2] = {L, V}: the frame's loops and vertices, exact whatever lcap and vcap are (V below 2^31); or {-1, -1}: the
+ *               frame cannot be processed -- row_start[n][H] > cap or n_regions[n] < 0 -- and nothing else of it is touched.  Decided on
+ *               the device; nothing comes to the host.
+ *   loops       int32 [N][lcap][4] = {region, first, count, hole}: first is the index of the loop's first vertex in the frame's list (the
+ *               vertex counts of the loops before it), exact also when V > vcap.  The rows below min(L, lcap) are exact, the rows from
+ *               there on untouched.  loops == NULL with lcap == 0: not wanted.
+ *   verts       uint32 [N][vcap]: the vertices of the loops one after the other.  The words below min(V, vcap) are exact, the words from
+ *               there on untouched.  verts == NULL with vcap == 0: not wanted (both: the sizing pass).
+ *   The caller detects an overflow as L > lcap or V > vcap.  L <= row_start[n][H] (a loop has a smallest run end) and
+ *   V <= 4 x row_start[n][H] (a run end gives at most two corners), so lcap = cap and vcap = 4 x cap never overflow.
+ * workspace: the caller's, 4-byte aligned, >= arseg_rle_contours_workspace_bytes(N, cap) bytes (else ARSEG_EWORKSPACE): 80 bytes per run
+ *   slot -- per run end its successor, the corner of its move and two states of the pointer jumping.  Its contents are scratch.
+ * 4 + ceil(log2(2 cap)) launches (clear, successors, the jumps, scan, emit -- no emit without verts); the number is fixed by cap, so
+ *   nothing comes back to the host; no workgroup waits for another.  Enqueue only: no allocation, no synchronisation.  The buffers must
+ *   not overlap.
+ * Malformed input (a row_start that does not rise, x_first out of order) gives meaningless loops, but nothing outside the caller's buffers
+ *   is read or written: indices and columns are clamped as arseg_rle_regions_fwd clamps them, and every loop is bounded.
+ * ARSEG_EINVAL, before any launch: a null row_start, runs, n_regions, run_region or counts; one of them, loops, verts or the workspace not
+ *   4-byte aligned; non-positive N, H, W or cap; negative lcap or vcap; loops == NULL with lcap > 0, verts == NULL with vcap > 0;
+ *   connectivity other than 4 or 8; H > 65535 or W > 65535 (the vertex word); cap > 1 << 29; a null workspace.
+ * Not covered: simplified or smoothed polygons (Douglas-Peucker, splines); sub-pixel outlines from the logits; the nesting tree of holes
+ *   and islands (a hole's region is given, the region inside it is the loop that follows it at the same vertex); outlines of absorbed
+ *   masks in one call (label the output of arseg_rle_absorb_fwd and call again).
+ * ------------------------------------------------------------------------------------------- */
+size_t arseg_rle_contours_workspace_bytes(int N, int64_t cap);
+int arseg_rle_contours_fwd(const int32_t *row_start, const uint32_t *runs, const int32_t *n_regions, const int32_t *run_region,
+                           int64_t cap, int N, int H, int W, int connectivity, int32_t *counts, int32_t *loops, int64_t lcap,
+                           uint32_t *verts, int64_t vcap, void *workspace, size_t workspace_bytes, arseg_stream_t stream);
 
 /* ---------------------------------------------------------------------------------------------
  * Measurement aids (no reference counterpart; BASELINE.md section 3: roofline fractions are reported against the datasheet peaks AND
