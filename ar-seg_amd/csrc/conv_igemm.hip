@@ -471,6 +471,8 @@ __global__ __launch_bounds__(128 * WM, (BN == 64 ? (WM == 2 ? 3 : 4) : 2)) void 
     // UP2 items: block (by, bx) of the patch = upsampled rows 2*iy+1, 2*iy+2 and columns 2*ix+1, 2*ix+2; quad = low-res rows
     // clamp(iy), clamp(iy+1) x columns clamp(ix), clamp(ix+1).  uflag: bit 0/1 row 0/1 inside the image, bit 2/3 column 0/1 inside,
     // bit 4: iy < 0 (row 1 is the image's first row = the low-res row itself), bit 5: ix < 0.
+    // TWIN: conv_up2_c64.hip (load_quads / stage) restates the quad addressing, uflag and the blend of store_patch below, operation for
+    // operation, so that tile_cfg 23 rounds as these plans do.  Change one and change the other (tests/test_gpu_up2_c64.py compares them).
     unsigned uoff[MAXU][4];
     int upx[MAXU], uflag[MAXU];
     if constexpr (UP2) {
@@ -706,7 +708,7 @@ __global__ __launch_bounds__(256) void conv_splitk_reduce_kernel(const ConvParam
     }
 }
 
-struct Plan { int bm, bn, bk, nbuf, nsplit, ktiles, ktiles_per_split, tiles_m, tiles_n, Ho, Wo, M, K, Kpad, patch_tw; };
+struct Plan { int bm, bn, bk, nbuf, nsplit, ktiles, ktiles_per_split, tiles_m, tiles_n, Ho, Wo, M, K, Kpad, patch_tw, up2_c64; };
 
 int make_plan(const arseg_conv_desc *d, Plan *pl) {
     if (!d) return ARSEG_EINVAL;
@@ -724,8 +726,22 @@ int make_plan(const arseg_conv_desc *d, Plan *pl) {
     pl->M = (int)M;
     pl->K = d->R * d->S * d->Cin;
     pl->Kpad = arseg_packed_k(d->Cin, d->R, d->S);
-    if (d->tile_cfg < 0 || d->tile_cfg > 22) return ARSEG_EINVAL;
-    pl->patch_tw = 0;
+    if (d->tile_cfg < 0 || d->tile_cfg > 23) return ARSEG_EINVAL;
+    pl->patch_tw = 0; pl->up2_c64 = 0;
+    if (d->tile_cfg == 23) {      // the persistent kernel of up_3 (conv_up2_c64.hip): the shape class of arseg_conv_up2_c64_fwd, which checks it again
+        if (!d->upsample2x) return ARSEG_EINVAL;                  // the id exists for convs on an upsampled input only
+        if (d->math != ARSEG_MATH_F16X3 || d->Cin != 64 || d->Cout != 64 || d->R != 3 || d->S != 3 || d->stride != 1 || d->pad != 1 || d->dil != 1 ||
+            (d->H & 1) || (d->W & 1) || (d->out_ld & 3) || d->batch > 1 || d->split_k > 1)
+            return ARSEG_EUNSUPPORTED;
+        // 32-bit buffer offsets (in = [N, H/2, W/2, in_ld])
+        if ((((long long)d->N * (d->H >> 1) * (d->W >> 1) - 1) * d->in_ld + 64) * 4 >= (1ll << 31) || ((M - 1) * d->out_ld + 64) * 4 >= (1ll << 31))
+            return ARSEG_EUNSUPPORTED;
+        pl->up2_c64 = 1;
+        pl->bm = 128; pl->bn = 64; pl->bk = 32; pl->nbuf = 2;
+        pl->ktiles = pl->Kpad / 32; pl->ktiles_per_split = pl->ktiles; pl->nsplit = 1;
+        pl->tiles_m = d->N * arseg_cdiv(pl->Ho, 8) * arseg_cdiv(pl->Wo, 16); pl->tiles_n = 1;
+        return ARSEG_OK;
+    }
     if (d->tile_cfg >= 17 && d->math != ARSEG_MATH_F16X3) return ARSEG_EUNSUPPORTED;      // the large tiles are built for f16x3 only
     // patch-resident 3x3 kernel: 128 (13, 14) / 256 (15, 16) pixel tiles TH x TW of one image, BN = 64 / 128; (r6) 20 / 21 / 22 = BN 64 on squarer
     // tiles -- 20: 256 pixels as 8 x 32, 21: 256 as 16 x 16, 22: 128 as 8 x 16 -- whose patch has less halo than the default 4 x 64 / 2 x 64 of a
@@ -879,6 +895,7 @@ extern "C" int arseg_conv2d_fwd(const arseg_conv_desc *d, const float *in, const
     ARSEG_CHECK_PTR(in); ARSEG_CHECK_PTR(w_packed); ARSEG_CHECK_PTR(out);
     if (!ARSEG_ALIGNED16(in) || !ARSEG_ALIGNED16(w_packed)) return ARSEG_EINVAL;
     if (residual && d->res_ld < d->Cout) return ARSEG_EINVAL;
+    if (pl.up2_c64) return residual ? ARSEG_EUNSUPPORTED : arseg_conv_up2_c64_fwd(d, in, w_packed, scale, bias, out, 0, stream);
     if (pl.nsplit > 1) {
         if (!workspace || workspace_bytes < (size_t)pl.nsplit * pl.M * d->Cout * sizeof(float)) return ARSEG_EWORKSPACE;
         if (!ARSEG_ALIGNED16(workspace)) return ARSEG_EINVAL;
@@ -1026,7 +1043,7 @@ extern "C" int arseg_pack_dw3x3_host(const float *w, int C, float *out) {
 
 // ---------------------------------------------------------------------------------------------------------------------------
 // "find": times the launch plans a conv shape admits on the device it will run on and returns the fastest.  The candidate set is
-// every tile_cfg the shape supports (5..12 GEMM tiles, 13..16 patch-resident, 17..19 large f16x3 tiles) x split-K {1,2,3,4,6,8}
+// every tile_cfg the shape supports (5..12 GEMM tiles, 13..16 / 20..22 patch-resident, 17..19 large f16x3 tiles, 23 with a fused upsample) x split-K {1,2,3,4,6,8}
 // (K long enough, Cout % 4 == 0, not in batched mode) plus the built-in heuristic (0, 0).  Unlike every other entry point this one
 // SYNCHRONISES the stream (hipEvent timing); it writes `out` (and the workspace) with real results of each candidate.
 namespace {
@@ -1036,7 +1053,7 @@ int find_candidates(const arseg_conv_desc *d, FindCand *c, int cap) {
     c[n++] = FindCand{0, 0};
     if (d->upsample2x) {                       // only the patch-resident plans upsample while they stage
         for (int cfg = 13; cfg <= 16 && n < cap; ++cfg) c[n++] = FindCand{cfg, 1};
-        for (int cfg = 20; cfg <= 22 && n < cap; ++cfg) c[n++] = FindCand{cfg, 1};
+        for (int cfg = 20; cfg <= 23 && n < cap; ++cfg) c[n++] = FindCand{cfg, 1};      // 23: up_3's persistent kernel (refuses other shapes)
         return n;
     }
     const int ktiles = (d->R * d->S * d->Cin + 31) / 32;

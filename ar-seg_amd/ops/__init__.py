@@ -22,7 +22,7 @@ from ._base import _DT16, _need_gpu, _need_gpu16, _nhwc_ld, _ptr, _range_word, _
 from ._config import Config, config, configure, set_conv_math
 from ._plans import _conv_plans, _time
 from ._profile import profile
-from .conv import (SplitRows, _conv1x1_x3, _conv2d16, _conv_up2_taps, _conv_wino, conv2d, gemm_rows16, gemm_x3_enabled, psp_bottleneck_x3,
+from .conv import (SplitRows, _conv1x1_x3, _conv2d16, _conv_up2_taps, _conv_wino, conv2d, conv_up2_c64, gemm_rows16, gemm_x3_enabled, psp_bottleneck_x3,
                    psp_x3_foldable, split_rows)
 from .creff import creff, creff_warp, creff_warp_kernel, flow_resize, mv_resize, warp, warp_mvq
 from .egress import labels_consistency, labels_rle, region_links, rle_absorb, rle_contours, rle_decode, rle_regions, segment_confidence, segment_consistency, segment_egress

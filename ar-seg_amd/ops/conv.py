@@ -181,7 +181,8 @@ def conv2d(x: torch.Tensor, pc, residual: Optional[torch.Tensor] = None, out: Op
         raise _lib.ArsegError(f"conv expects {pc.cin_pad} input channels (padded), got {Cin}")
     in_ld_hi = Cin if x_low is not None else _nhwc_ld(x)
     math = sw.math
-    d, out, Ho, Wo = _conv_desc(pc, N, H, W, Cin, in_ld_hi, tile_cfg, split_k, residual, out, torch.float32, dev, math)
+    d, out, Ho, Wo = _conv_desc(pc, N, H, W, Cin, in_ld_hi, tile_cfg, split_k, residual, out, torch.float32, dev, math,
+                                up2=x_low is not None and tile_cfg in _PATCH_CFGS)
     w_dev, scale_dev = (pc.w_h3, pc.scale_h3) if math != _lib.MATH_F32 else (pc.w, pc.scale)
     lib = _lib.load()
     flops = 2 * N * Ho * Wo * pc.cout * pc.R * pc.S * pc.cin
@@ -275,9 +276,24 @@ def conv2d(x: torch.Tensor, pc, residual: Optional[torch.Tensor] = None, out: Op
     return out
 
 
-def _conv_desc(pc, N, H, W, Cin, in_ld, tile_cfg, split_k, residual, out, dtype, device, math=_lib.MATH_F32):
+def conv_up2_c64(x_low: torch.Tensor, pc, out: Optional[torch.Tensor] = None, max_wgs: int = 0):
+    """up_3's persistent kernel by itself (arseg_conv_up2_c64_fwd = tile_cfg 23 of ``conv2d(..., up2=True)``): 3x3 stride-1 pad-1, 64 -> 64
+    channels, on the x2 bilinear upsample of ``x_low`` [N,h,w,64], split-fp16 arithmetic whatever the configured conv math.  max_wgs > 0 caps
+    the persistent grid (0: one workgroup per compute unit)."""
+    _need_gpu(x_low, out)
+    n, h, w, c = x_low.shape
+    d, out, Ho, Wo = _conv_desc(pc, n, 2 * h, 2 * w, c, _nhwc_ld(x_low), 23, 1, None, out, torch.float32, x_low.device, _lib.MATH_F16X3, up2=True)
+    flops = 2 * n * Ho * Wo * pc.cout * 9 * pc.cin
+    with tagged((n, Ho, Wo, pc.cin, pc.cout, 3, 1, 1, True, "up2_c64", flops)):
+        launch("conv2d", _lib.load().arseg_conv_up2_c64_fwd, ctypes.byref(d), _ptr(x_low), _ptr(pc.w_h3), _ptr(pc.scale_h3), _ptr(pc.bias), _ptr(out),
+               max_wgs, _stream(), flops=flops)
+    return out
+
+
+def _conv_desc(pc, N, H, W, Cin, in_ld, tile_cfg, split_k, residual, out, dtype, device, math=_lib.MATH_F32, up2=False):
     """arseg_conv_desc of ``pc`` on an [N, H, W, Cin] input of row pitch ``in_ld``, and its output tensor: ``out`` (shape checked) or a new one
-    of ``dtype`` (16-bit: row pitch padded to 8 channels) -> (desc, out, Ho, Wo)."""
+    of ``dtype`` (16-bit: row pitch padded to 8 channels) -> (desc, out, Ho, Wo).  up2: ``tile_cfg`` is a plan that upsamples its
+    half-resolution input itself (upsample2x; H, W are the upsampled size)."""
     d = ConvDesc()
     d.N, d.H, d.W, d.Cin, d.in_ld = N, H, W, Cin, in_ld
     d.Cout = pc.cout
@@ -288,6 +304,7 @@ def _conv_desc(pc, N, H, W, Cin, in_ld, tile_cfg, split_k, residual, out, dtype,
     _arm_range_watch(d, device)
     d.out_ld, d.res_ld = pc.cout, pc.cout     # provisional, for the shape query
     ho, wo = ctypes.c_int(), ctypes.c_int()
+    d.upsample2x = 1 if up2 else 0
     check(_lib.load().arseg_conv_out_hw(ctypes.byref(d), ctypes.byref(ho), ctypes.byref(wo)), "conv_out_hw")
     Ho, Wo = ho.value, wo.value
     if out is None:

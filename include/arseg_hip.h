@@ -203,7 +203,10 @@ typedef struct arseg_conv_desc {
                           ARSEG_EUNSUPPORTED for other shapes; 17..19 = 256x128, 128x256, 256x256 tiles on 8 / 16 waves (F16X3 only):
                           more MFMA work per byte fetched from L2 / Infinity Cache, for wide GEMMs that fill the chip; 20..22 (r6) = the
                           patch-resident kernel with BN = 64 on squarer pixel tiles (20: 256 pixels as 8 x 32, 21: 16 x 16, 22: 128 pixels as
-                          8 x 16: less halo per output than the 4 x 64 / 2 x 64 tiles 13..16 take on a wide map); refused on narrower maps */
+                          8 x 16: less halo per output than the 4 x 64 / 2 x 64 tiles 13..16 take on a wide map); refused on narrower maps;
+                          23 = the persistent kernel of arseg_conv_up2_c64_fwd (below): upsample2x, 3x3 stride 1 pad 1, Cin = Cout = 64,
+                          F16X3, no residual, out_ld % 4 == 0, `out` 16-byte aligned; ARSEG_EUNSUPPORTED for anything else (ARSEG_EINVAL without
+                          upsample2x: the id is defined for convs on an upsampled input only) */
     int split_k;       /* 0 auto, >= 1 explicit */
     /* batched mode (used by the Winograd path): `batch` independent problems of identical shape, problem b reads
        in + b*in_batch_stride, w_packed + b*w_batch_stride and writes out + b*out_batch_stride (strides in floats);
@@ -239,6 +242,14 @@ size_t arseg_conv2d_workspace_bytes(const arseg_conv_desc *d);
 int arseg_conv2d_fwd(const arseg_conv_desc *d, const float *in, const float *w_packed, const float *scale,
                      const float *bias, const float *residual, float *out, void *workspace, size_t workspace_bytes,
                      arseg_stream_t stream);
+
+/* tile_cfg 23 of arseg_conv2d_fwd by itself: the 64 -> 64 channel 3x3 stride-1 pad-1 conv on the x2 bilinear upsample of `in`
+ * (d->upsample2x = 1, ARSEG_MATH_F16X3; PSPNet's up_3) with the folded scale / bias / activation epilogue, no residual.  One persistent
+ * workgroup per compute unit walks a run of 8 x 16 pixel tiles: four waves keep the layer's split weights in registers and multiply,
+ * four stage the next tile's upsampled patch (csrc/conv_up2_c64.hip).  d->tile_cfg is ignored; no workspace.  max_wgs > 0 caps the
+ * number of workgroups (0: one per compute unit, at most one per tile); results do not depend on it.  range_flag as in arseg_conv_desc. */
+int arseg_conv_up2_c64_fwd(const arseg_conv_desc *d, const float *in, const float *w_packed, const float *scale, const float *bias,
+                           float *out, int max_wgs, arseg_stream_t stream);
 
 /* Plan selection ("find", what MIOpen calls miopenFindConvolutionForwardAlgorithm; the reference gets it implicitly from
  * torch.backends.cudnn.benchmark, train.py / evaluation.py): runs every launch plan the shape admits -- all tile_cfg it supports x
