@@ -994,6 +994,95 @@ def contours_numpy(row_start, runs, H, W, connectivity=8):
             np.array(verts, dtype=np.uint32))
 
 
+class SimplifiedContours(ContourFrames):
+    """``contours`` (a ``ContourFrames``) simplified to ``tolerance`` pixels (include/arseg_hip.h, arseg_contours_simplify_fwd), on the
+    device: a ``ContourFrames`` itself -- ``counts``, ``loops``, ``verts``, ``needed()`` and ``to_host()`` mean what they mean there, the
+    vertices being the kept ones -- whose ``source`` is the input's."""
+
+    def __init__(self, counts, loops, verts, contours, tolerance, workspace=None):
+        if not isinstance(contours, ContourFrames):
+            raise ValueError("SimplifiedContours: contours must be the ContourFrames that were simplified")
+        super().__init__(counts, loops, verts, contours.source, workspace)
+        self.contours, self.tolerance = contours, tolerance
+        if loops.shape[1] != contours.loop_capacity:
+            raise ValueError(f"SimplifiedContours: loops must have the input's capacity {contours.loop_capacity}, got {loops.shape[1]}")
+
+
+def simplify(contours: ContourFrames, tolerance, vertex_capacity=None, out=None) -> SimplifiedContours:
+    """The outlines with the vertices dropped that lie within ``tolerance`` pixels (a non-negative multiple of 0.25) of the polygon that
+    remains, on the GPU: one call of ``ops.contours_simplify`` -> ``SimplifiedContours``.  Per loop Douglas-Peucker on the two chains
+    between its first vertex and the vertex farthest from it; a loop that would keep fewer than 3 vertices is left whole; loops, their
+    order, first vertices, regions and hole marks stay.  ``vertex_capacity`` defaults to the input's, which cannot overflow.  ``out``: a
+    ``SimplifiedContours`` of the same N and loop capacity to write into (its vertex capacity and workspace hold; nothing is allocated
+    then, and the call can be captured in one HIP graph behind ``rle_contours``).  Each loop is simplified on its own: a border shared by
+    two regions is simplified twice, and the two results may differ by up to the tolerance."""
+    if not isinstance(contours, ContourFrames):
+        raise ValueError("simplify: expected the ContourFrames of egress.contours")
+    ops.tolerance_q(tolerance, "simplify")
+    N, lcap, vcap, dev = contours.N, contours.loop_capacity, contours.vertex_capacity, contours.counts.device
+    if out is None:
+        vertex_capacity = vcap if vertex_capacity is None else int(vertex_capacity)
+        if vertex_capacity < 0:
+            raise ValueError(f"simplify: the capacity must not be negative, got {vertex_capacity}")
+        if not contours.counts.is_cuda:
+            raise _lib.ArsegError("simplify runs on the GPU only (got CPU tensors); simplify_numpy is the host form")
+        _need = _lib.load().arseg_contours_simplify_workspace_bytes(N, lcap, vcap)
+        out = SimplifiedContours(torch.empty((N, 2), dtype=torch.int32, device=dev), torch.empty((N, lcap, 4), dtype=torch.int32, device=dev),
+                                 torch.empty((N, vertex_capacity), dtype=torch.int32, device=dev), contours, tolerance,
+                                 torch.empty((max(_need // 16, 1), 4), dtype=torch.int32, device=dev))
+    elif not isinstance(out, SimplifiedContours) or out.N != N or out.loop_capacity != lcap or out is contours:
+        raise ValueError(f"simplify: out must be SimplifiedContours of {N} frames with a loop capacity of {lcap}")
+    else:
+        out.contours, out.source, out.tolerance = contours, contours.source, tolerance
+    frame = contours.source.frames
+    ops.contours_simplify(contours.counts, contours.loops if lcap else None, contours.verts if vcap else None, frame.H, frame.W, tolerance,
+                          out.counts, loops_out=out.loops if lcap else None, verts_out=out.verts if out.vertex_capacity else None,
+                          workspace=out.workspace)
+    return out
+
+
+def simplify_numpy(counts, loops, verts, tolerance):
+    """The same pass on a host without a GPU: one frame's ``(counts [2], loops [>= L,4], verts [>= V])`` (as ``contours_numpy`` returns
+    them) -> the same three arrays of the simplified outlines, as arseg_contours_simplify_fwd leaves them with room for everything.  The
+    recursion runs on an explicit stack of segments, the distances of a segment's interior in one vectorised step."""
+    tol = ops.tolerance_q(tolerance, "simplify_numpy")
+    L, V = int(counts[0]), int(counts[1])
+    if L < 0 or V < 0 or L > len(loops) or V > len(verts):
+        raise ValueError(f"simplify_numpy: the frame holds {len(loops)} loops and {len(verts)} vertices, its counts say {L} and {V}")
+    words = np.asarray(verts)[:V].astype(np.int64) & 0xFFFFFFFF
+    xs, ys = words & 0xFFFF, words >> 16
+    if V and (xs.max() > 16384 or ys.max() > 16384):
+        raise ValueError("simplify_numpy: H and W at most 16384")
+    records, kept_words = np.array(np.asarray(loops)[:L], dtype=np.int32).reshape(-1, 4), []
+    at = 0
+    for k, (_, first, count, _) in enumerate(records.tolist()):
+        if first < 0 or count < 0 or first + count > V:
+            raise ValueError(f"simplify_numpy: loop {k} lies outside the frame's {V} vertices")
+        x, y = np.append(xs[first:first + count], xs[first:first + 1]), np.append(ys[first:first + count], ys[first:first + 1])
+        keep = np.zeros(count, dtype=bool)
+        if count:
+            far = int(np.argmax((x[:count] - x[0]) ** 2 + (y[:count] - y[0]) ** 2))          # argmax: the first of a tie
+            keep[[0, far]] = True
+            todo = [(0, far), (far, count)]
+            while todo:
+                a, b = todo.pop()
+                if b - a < 2:
+                    continue
+                ex, ey = int(x[b] - x[a]), int(y[b] - y[a])
+                c = np.abs(ex * (y[a + 1:b] - y[a]) - ey * (x[a + 1:b] - x[a]))
+                i = int(np.argmax(c))
+                if 16 * int(c[i]) ** 2 > tol * (ex * ex + ey * ey):
+                    keep[a + 1 + i] = True
+                    todo += [(a, a + 1 + i), (a + 1 + i, b)]
+            if keep.sum() < 3:
+                keep[:] = True
+        records[k, 1:3] = (at, int(keep.sum()))
+        at += int(keep.sum())
+        kept_words.append(words[first:first + count][keep])
+    out = np.concatenate(kept_words).astype(np.uint32) if kept_words else np.zeros(0, dtype=np.uint32)
+    return np.array([L, at], dtype=np.int32), records, out
+
+
 class TrackIds(object):
     """Persistent ids for the regions of a stream, from the links alone.  Pure Python on the ``links`` arrays of ``LinkFrames.to_host`` /
     ``links_numpy``; it has no thresholds -- what to do with a short-lived id is the caller's business.

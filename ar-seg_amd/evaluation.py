@@ -518,6 +518,18 @@ def alter_res_batch_contours(lr_net, ref_ps, imgs, mv_qs, capacity, region_capac
     return egress.contours(found, loop_capacity=loop_capacity, vertex_capacity=vertex_capacity), labels
 
 
+def alter_res_batch_polygons(lr_net, ref_ps, imgs, mv_qs, capacity, region_capacity, tolerance, scale=0.5, lut=None, labels_out=True,
+                             connectivity=8, min_area=None, protect=None, pair_capacity=None, loop_capacity=None, vertex_capacity=None):
+    """``alter_res_batch_contours`` + ``egress.simplify``: the outlines within ``tolerance`` pixels (a non-negative multiple of 0.25) ->
+    (``egress.SimplifiedContours``, whose ``.contours`` are the exact outlines and ``.source`` the regions; labels uint8 [B,H,W]).  With
+    ``min_area`` the specks are absorbed first.  Nothing comes to the host in between; ``to_host()`` brings the polygons over."""
+    from . import egress
+    outlines, labels = alter_res_batch_contours(lr_net, ref_ps, imgs, mv_qs, capacity, region_capacity, scale=scale, lut=lut, labels_out=labels_out,
+                                                connectivity=connectivity, min_area=min_area, protect=protect, pair_capacity=pair_capacity,
+                                                loop_capacity=loop_capacity, vertex_capacity=vertex_capacity)
+    return egress.simplify(outlines, tolerance), labels
+
+
 def alter_res_batch_links(lr_net, ref_ps, imgs, mv_qs, key_regions, capacity, region_capacity, scale=0.5, lut=None, labels_out=True,
                           connectivity=8, pair_capacity=None):
     """``alter_res_batch_regions``'s sibling for object association: the same phases, run code and regions, then ``egress.links`` of every

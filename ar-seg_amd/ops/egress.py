@@ -3,7 +3,9 @@
 statistics, one ABI call (arseg_segment_confidence_fwd; csrc/confidence.hip); an 8-bit plane <-> its row-run code, one ABI call each
 (arseg_labels_rle_fwd / arseg_rle_decode_fwd; csrc/rle.hip); a row-run code -> its connected regions, one ABI call (arseg_rle_regions_fwd;
 csrc/regions.hip); the regions of two frames -> their links along the motion, one ABI call (arseg_region_links_fwd; csrc/links.hip); a row-run
-code and its regions -> the code with the small regions absorbed into their neighbours, one ABI call (arseg_rle_absorb_fwd; csrc/absorb.hip)."""
+code and its regions -> the code with the small regions absorbed into their neighbours, one ABI call (arseg_rle_absorb_fwd; csrc/absorb.hip);
+the regions' outlines as polygon loops (arseg_rle_contours_fwd; csrc/contours.hip) and those simplified to a pixel tolerance
+(arseg_contours_simplify_fwd; csrc/simplify.hip), one ABI call each."""
 from __future__ import annotations
 
 import ctypes
@@ -529,3 +531,63 @@ def rle_contours(row_start: torch.Tensor, runs: torch.Tensor, n_regions: torch.T
            workspace.numel() * workspace.element_size(), _stream(),
            nbytes=4 * N * (H + 1))          # (+ about 80 bytes per run and round of jumping, known on the device only)
     return counts, loops, verts
+
+
+def tolerance_q(tolerance, what="contours_simplify"):
+    """A tolerance in pixels, a non-negative multiple of 0.25 -> ``tol2_q``: sixteen times its square (an integer)."""
+    quarters = float(tolerance) * 4.0
+    if not (0.0 <= quarters <= 32768.0) or quarters != int(quarters):          # 32768 quarters: tol2_q = 1 << 30, the entry point's limit
+        raise ValueError(f"{what}: tolerance must be a non-negative multiple of 0.25 pixels (at most 8192), got {tolerance!r}")
+    return int(quarters) ** 2
+
+
+def contours_simplify(counts: torch.Tensor, loops: Optional[torch.Tensor], verts: Optional[torch.Tensor], H: int, W: int, tolerance,
+                      counts_out: torch.Tensor, loops_out: Optional[torch.Tensor] = None, verts_out: Optional[torch.Tensor] = None,
+                      workspace: Optional[torch.Tensor] = None):
+    """Region outlines simplified to ``tolerance`` pixels (include/arseg_hip.h, arseg_contours_simplify_fwd): ``counts`` int32 [N,2],
+    ``loops`` int32 [N,lcap,4] and ``verts`` 32-bit [N,vcap] as ``rle_contours`` wrote them -> ``counts_out`` int32 [N,2] (the loops and
+    the kept vertices of each frame, exact whatever the capacity; -1, -1: the source frame was refused or overflowed, nothing else of the
+    frame is touched), ``loops_out`` int32 [N,lcap,4] (``region, first', count', hole``; required with loops) and, when given,
+    ``verts_out`` 32-bit [N,vcap_out], exact below the counts and untouched from there on.  ``tolerance``: a non-negative multiple of
+    0.25.  Per loop Douglas-Peucker on the two chains between its first vertex and the vertex farthest from it; a loop that would keep
+    fewer than 3 vertices is left whole.  ``workspace``: a device tensor of at least ``arseg_contours_simplify_workspace_bytes(N, lcap,
+    vcap)`` bytes (default: the stream's shared workspace).  With every buffer given nothing is allocated and nothing synchronises:
+    capturable in a HIP graph.  Returns (counts_out, loops_out, verts_out)."""
+    what = "contours_simplify"
+    H, W = int(H), int(W)
+    if H <= 0 or W <= 0 or H > 16384 or W > 16384:
+        raise ValueError(f"{what}: 0 < H <= 16384 and 0 < W <= 16384, got {H}x{W}")
+    tol2_q = tolerance_q(tolerance, what)
+    _need_gpu(counts, counts_out, dtype=torch.int32)
+    if counts.dim() != 2 or counts.shape[1] != 2 or counts.shape[0] < 1 or not counts.is_contiguous():
+        raise _lib.ArsegError(f"{what}: counts must be a contiguous int32 [N,2] tensor, got {tuple(counts.shape)}")
+    N, dev = int(counts.shape[0]), counts.device
+    if tuple(counts_out.shape) != (N, 2) or not counts_out.is_contiguous() or counts_out.device != dev:
+        raise _lib.ArsegError(f"{what}: counts_out must be a contiguous int32 {(N, 2)} tensor on {dev}, got {tuple(counts_out.shape)}")
+    lcap = vcap = vcap_out = 0
+    if loops is not None:
+        _need_gpu(loops, loops_out, dtype=torch.int32)
+        if loops.dim() != 3 or loops.shape[0] != N or loops.shape[2] != 4 or not loops.is_contiguous() or loops.device != dev:
+            raise _lib.ArsegError(f"{what}: loops must be a contiguous int32 [{N}, capacity, 4] tensor on {dev}, got {tuple(loops.shape)}")
+        if loops_out is None or tuple(loops_out.shape) != tuple(loops.shape) or not loops_out.is_contiguous() or loops_out.device != dev:
+            raise _lib.ArsegError(f"{what}: loops_out must be a contiguous int32 {tuple(loops.shape)} tensor on {dev}")
+        lcap = int(loops.shape[1])
+    for name, t in (("verts", verts), ("verts_out", verts_out)):
+        if t is not None:
+            _need_gpu(t, dtype=None)
+            if t.dtype not in _RUN_DTYPES or t.dim() != 2 or t.shape[0] != N or not t.is_contiguous() or t.device != dev:
+                raise _lib.ArsegError(f"{what}: {name} must be a contiguous 32-bit [{N}, capacity] tensor on {dev}, got {t.dtype} {tuple(t.shape)}")
+    vcap = int(verts.shape[1]) if verts is not None else 0
+    vcap_out = int(verts_out.shape[1]) if verts_out is not None else 0
+    lib = _lib.load()
+    nbytes = lib.arseg_contours_simplify_workspace_bytes(N, lcap, vcap)
+    if workspace is None:
+        workspace = _workspace(max(nbytes, 16), dev)
+    elif not workspace.is_cuda or workspace.device != dev or not workspace.is_contiguous() or workspace.data_ptr() % 4 or \
+            workspace.numel() * workspace.element_size() < nbytes:
+        raise _lib.ArsegError(f"{what}: workspace must be a contiguous, 4-byte aligned tensor of at least {nbytes} bytes on {dev}")
+    launch(what, lib.arseg_contours_simplify_fwd, _ptr(counts), _ptr(loops if lcap else None), lcap, _ptr(verts if vcap else None), vcap, N, H, W,
+           tol2_q, _ptr(counts_out), _ptr(loops_out if lcap else None), _ptr(verts_out if vcap_out else None), vcap_out, _ptr(workspace),
+           workspace.numel() * workspace.element_size(), _stream(),
+           nbytes=16 * N)          # (+ about 16 bytes per loop and some 30 per vertex, known on the device only)
+    return counts_out, loops_out, verts_out

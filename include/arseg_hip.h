@@ -983,14 +983,62 @@ int arseg_rle_absorb_fwd(const int32_t *row_start, const uint32_t *runs, const i
  * ARSEG_EINVAL, before any launch: a null row_start, runs, n_regions, run_region or counts; one of them, loops, verts or the workspace not
  *   4-byte aligned; non-positive N, H, W or cap; negative lcap or vcap; loops == NULL with lcap > 0, verts == NULL with vcap > 0;
  *   connectivity other than 4 or 8; H > 65535 or W > 65535 (the vertex word); cap > 1 << 29; a null workspace.
- * Not covered: simplified or smoothed polygons (Douglas-Peucker, splines); sub-pixel outlines from the logits; the nesting tree of holes
- *   and islands (a hole's region is given, the region inside it is the loop that follows it at the same vertex); outlines of absorbed
- *   masks in one call (label the output of arseg_rle_absorb_fwd and call again).
+ * Not covered: smoothed polygons (splines; simplified ones: arseg_contours_simplify_fwd, further down); sub-pixel outlines from the
+ *   logits; the nesting tree of holes and islands (a hole's region is given, the region inside it is the loop that follows it at the
+ *   same vertex); outlines of absorbed masks in one call (label the output of arseg_rle_absorb_fwd and call again).
  * ------------------------------------------------------------------------------------------- */
 size_t arseg_rle_contours_workspace_bytes(int N, int64_t cap);
 int arseg_rle_contours_fwd(const int32_t *row_start, const uint32_t *runs, const int32_t *n_regions, const int32_t *run_region,
                            int64_t cap, int N, int H, int W, int connectivity, int32_t *counts, int32_t *loops, int64_t lcap,
                            uint32_t *verts, int64_t vcap, void *workspace, size_t workspace_bytes, arseg_stream_t stream);
+
+/* ---------------------------------------------------------------------------------------------
+ * Region outlines simplified to a pixel tolerance (csrc/simplify.hip): the loops of arseg_rle_contours_fwd with the vertices dropped that
+ * lie within a stated distance of the polygon that remains (Douglas-Peucker) -- what an overlay, an annotation tool or a tracker draws
+ * instead of a vertex at every pixel step -- on the device, one more pass behind the outlines, without a host synchronisation:
+ * capturable in the same HIP graph.  Integers only: every result is exact.  (A backward-compatible addition: ARSEG_ABI_VERSION stays.)
+ * Input: counts int32 [N][2], loops int32 [N][lcap][4] and verts uint32 [N][vcap] exactly as arseg_rle_contours_fwd leaves them, with
+ *   their capacities; H and W of the frames; tol2_q = 16 x the squared tolerance in pixels (0.5 px -> 4, 1 px -> 16, 1.5 px -> 36,
+ *   2 px -> 64).
+ * Rule per loop, on integer coordinates; the vertices are P[0 .. n) with P[n] = P[0]:
+ *   1. Anchors.  a0 = 0 (the loop's smallest vertex: it is on the loop's hull); a1 = the position with the largest squared Euclidean
+ *      distance from P[0], the smallest position of a tie.
+ *   2. Chains.  Douglas-Peucker on the two open chains [a0, a1] and [a1, n].  For a segment (a, b) and its interior positions a < i < b,
+ *      c_i = |(P[b] - P[a]) x (P[i] - P[a])|; the i with the largest c_i is picked, the smallest position of a tie.  If
+ *      16 c_i^2 > tol2_q |P[b] - P[a]|^2 the vertex is kept and both halves are treated the same way; otherwise every interior vertex is
+ *      dropped.  The distance is to the line through the two ends (as cv2.approxPolyDP measures it).  The ends of a segment never
+ *      coincide: a1 is at positive distance from a0, and a kept vertex is strictly off its chord.
+ *   3. No collapse.  If fewer than 3 vertices would be kept the loop is emitted unchanged, with all n vertices (a unit square stays a
+ *      unit square).  Three kept vertices are never collinear, so every emitted loop is a proper polygon.
+ *   4. Order.  Kept vertices keep their order, the loop still starts at the same first vertex; region and hole are copied; the loops keep
+ *      their order.
+ *   tol2_q = 0 gives the input back: an interior vertex of a corner loop is never on its chord.
+ * Range: H, W <= 16384 keeps c_i <= 2^29 (32-bit products) and, with tol2_q <= 2^30, both sides of the comparison below 2^63.
+ * Outputs, all integers, all OVERWRITTEN:
+ *   counts_out  int32 [N][2] = {L, V'}: exact whatever vcap_out is; or {-1, -1}: the frame is refused -- its source counts are negative,
+ *               or L > lcap or V > vcap (an overflowed source) -- and nothing else of it is touched.  Decided on the device.
+ *   loops_out   int32 [N][lcap][4] = {region, first', count', hole}: first' is the prefix sum of count', exact also when V' > vcap_out.
+ *               The rows below L are exact, the rows from there on untouched.
+ *   verts_out   uint32 [N][vcap_out]: the words below min(V', vcap_out) are exact, the words from there on untouched.  verts_out == NULL
+ *               with vcap_out == 0: the sizing pass.  V' <= V, so vcap_out = vcap never overflows.
+ * workspace: the caller's, 4-byte aligned, >= arseg_contours_simplify_workspace_bytes(N, lcap, vcap) bytes (else ARSEG_EWORKSPACE): per
+ *   frame 4 bytes per loop slot (the kept count) and a byte per vertex slot (the keep flag); capacities whose size does not fit size_t
+ *   give SIZE_MAX and ARSEG_EWORKSPACE.  Its contents are scratch.
+ * 4 launches (clear, keep, scan, emit -- no emit without verts_out), sized on the host from the capacities; no workgroup waits for
+ *   another.  Enqueue only: no allocation, no synchronisation.  The buffers must not overlap.
+ * Malformed input (a loop record whose first or count lies outside the frame's vertices) gives meaningless output, but nothing outside
+ *   the caller's buffers is read or written: first and count are clamped into [0, min(V, vcap)], and every loop is bounded.
+ * ARSEG_EINVAL, before any launch: a null counts or counts_out; loops or loops_out NULL with lcap > 0, verts NULL with vcap > 0,
+ *   verts_out NULL with vcap_out > 0; one of the arrays or the workspace not 4-byte aligned; non-positive N, H or W; a negative
+ *   capacity; H > 16384 or W > 16384; tol2_q < 0 or > 1 << 30; verts_out == verts, loops_out == loops or counts_out == counts; a null
+ *   workspace.
+ * Not covered: a border shared by two regions is simplified once per loop, so the two results may differ by up to the tolerance
+ *   (splitting the loops where three regions meet and simplifying each arc once is a later item); smoothing; area-preserving rules.
+ * ------------------------------------------------------------------------------------------- */
+size_t arseg_contours_simplify_workspace_bytes(int N, int64_t lcap, int64_t vcap);
+int arseg_contours_simplify_fwd(const int32_t *counts, const int32_t *loops, int64_t lcap, const uint32_t *verts, int64_t vcap, int N, int H,
+                                int W, int64_t tol2_q, int32_t *counts_out, int32_t *loops_out, uint32_t *verts_out, int64_t vcap_out,
+                                void *workspace, size_t workspace_bytes, arseg_stream_t stream);
 
 /* ---------------------------------------------------------------------------------------------
  * Measurement aids (no reference counterpart; BASELINE.md section 3: roofline fractions are reported against the datasheet peaks AND
