@@ -733,8 +733,10 @@ extern "C" int arseg_conv2d16_fwd(const arseg_conv_desc *d, int dtype, const voi
     if (d->batch > 1) return ARSEG_EUNSUPPORTED;
     int Ho, Wo;
     {
-        arseg_conv_desc d0 = *d;                 // (the fp32 plan check of arseg_conv_out_hw refuses upsample2x on plans that are not its own)
-        d0.upsample2x = 0;
+        // the size query goes through the fp32 engine's plan check: it refuses upsample2x on plans that are not its own, and its tile_cfg 13
+        // is an f16x3-only patch plan -- this kernel's plan 13 was refused right here, for every shape, before it was looked at
+        arseg_conv_desc d0 = *d;
+        d0.upsample2x = 0; d0.tile_cfg = 0;
         if (int e = arseg_conv_out_hw(&d0, &Ho, &Wo)) return e;
     }
     // upsample2x: `in` is [N, H/2, W/2, in_ld]; only the patch-resident plans (5..8, 10..13; 0 = 7) stage its x2 upsample, for a 3x3 stride-1
