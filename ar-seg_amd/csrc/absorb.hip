@@ -22,30 +22,25 @@
 //   count    the first launch that writes an output, and the first that knows whether the vote fitted.  A wave per row: the new value of
 //            every run (its target's value, else its own), a run survives if it is the first of its row or its new value differs from its
 //            predecessor's; the survivors of the row into out_row_start[n][y + 1].
-//   scan     one workgroup per frame: rle.hip's prefix over out_row_start; target and n_absorbed (or -2) from the regions' words.
+//   scan     one workgroup per frame: the prefix over out_row_start (rc_block_scan); target and n_absorbed (or -2) from the regions' words.
 //   emit     the walk of count; a survivor's index is the row's base plus the survivors before it in the wave; words below out_cap only.
 // Integers throughout: every output is a pure function of the inputs.
 //
 // Bounds of the loops (nothing else loops):
 //   grid-stride loops      over frames, rows, runs of a row, slots and regions: counted.
-//   the binary search      over (first, last] of the row above: at most 31 rounds.
+//   rc_cover               a binary search over (first, last] of the row above: at most 31 rounds.
 //   the walk               advances one run of the row above per round and ends at that row's last run at the latest.
-//   ab_insert              advances one slot per round and ends after pcap rounds at the latest.
+//   rc_pair_insert         advances one slot per round and ends after pcap rounds at the latest.
 //   the shuffles           6 rounds.
-// Indices are clamped as regions.hip clamps them: a row's runs into [0, stored runs) of its frame, columns into [0, W]; a region number is
+// Indices are clamped by runcode.h: a row's runs into [0, stored runs) of its frame, columns into [0, W]; a region number is
 // used as an index only below the frame's region count, which is at most rcap in a frame that is not refused.  A malformed run code or
 // run_region gives a meaningless code and nothing outside the caller's buffers.
-#include "arseg_device.h"
-
-#include <limits.h>
+#include "runcode.h"
 
 namespace {
 
-typedef unsigned long long ab_u64;
-
 constexpr int AB_WAVES = 4;                             // waves (= rows in flight) per workgroup
-constexpr ab_u64 AB_EMPTY = ~0ull;                      // no key: region numbers are never negative in a key
-constexpr ab_u64 AB_STABLE = ~0ull;                     // a stable region's word; a packed best holds a border < 2^32 - 1 (at most 2 H W - 2)
+constexpr rc_u64 AB_STABLE = ~0ull;                     // a stable region's word; a packed best holds a border < 2^32 - 1 (at most 2 H W - 2)
 
 struct AbP {
     const int *rs;                                      // [N][H + 1]
@@ -57,72 +52,43 @@ struct AbP {
     unsigned *out_runs;                                 // [N][out_cap]
     int *target;                                        // [N][tcap] (may be null: tcap == 0)
     int *nabs;                                          // [N]
-    ab_u64 *pairs;                                      // [N][pcap][2]: key, border
-    ab_u64 *best;                                       // [N][rcap]
+    rc_u64 *pairs;                                      // [N][pcap][2]: key, border
+    rc_u64 *best;                                       // [N][rcap]
     unsigned *flag;                                     // [N][2]: the first word is used
-    ab_u64 protect[4];                                  // bit v: value v is protected
+    rc_u64 protect[4];                                  // bit v: value v is protected
     long long cap_stride, out_stride, rcap, tcap, pcap, min_area;
     int cap, out_cap;                                   // min(., INT32_MAX): an index is below 2^31
     int N, H, W;
 };
 
-__device__ __forceinline__ int ab_clamp(int v, int lo, int hi) { return min(max(v, lo), hi); }
-
 // The stored runs of a frame, or -1 for a frame that is refused: its run code overflowed, or its regions are missing or more than the records.
 __device__ __forceinline__ int ab_total(const AbP &p, int n) {
-    const int need = p.rs[(size_t)n * (p.H + 1) + p.H], R = p.nreg[n];
-    return (need > p.cap || R < 0 || (long long)R > p.rcap) ? -1 : max(need, 0);
+    const int stored = rc_stored(p.rs[(size_t)n * (p.H + 1) + p.H], p.cap), R = p.nreg[n];
+    return (R < 0 || (long long)R > p.rcap) ? -1 : stored;
 }
 
 __device__ __forceinline__ bool ab_protected(const AbP &p, unsigned v) {
-    const ab_u64 w = v < 64 ? p.protect[0] : v < 128 ? p.protect[1] : v < 192 ? p.protect[2] : p.protect[3];
+    const rc_u64 w = v < 64 ? p.protect[0] : v < 128 ? p.protect[1] : v < 192 ? p.protect[2] : p.protect[3];
     return (w >> (v & 63u)) & 1ull;
 }
 
-__device__ __forceinline__ long long ab_slot(ab_u64 key, long long pcap) {
-    const ab_u64 h = (key * 0x9E3779B97F4A7C15ull) >> 32;
-    return pcap < (1ll << 32) ? (long long)((h * (ab_u64)pcap) >> 32) : (long long)h;
-}
-
-// The slot of key in a table of pcap slots of two words, taken when the key is new; -1 when all pcap slots hold other keys.
-__device__ __forceinline__ long long ab_insert(ab_u64 *tab, long long pcap, ab_u64 key) {
-    long long s = ab_slot(key, pcap);
-    for (long long t = 0; t < pcap; ++t) {
-        ab_u64 old = __hip_atomic_load(tab + 2 * s, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
-        if (old == AB_EMPTY) old = atomicCAS(tab + 2 * s, AB_EMPTY, key);
-        if (old == AB_EMPTY || old == key) return s;
-        s = s + 1 == pcap ? 0 : s + 1;
-    }
-    return -1;
-}
-
-__device__ __forceinline__ void ab_add(const AbP &p, int n, ab_u64 *pairs, ab_u64 key, ab_u64 border) {
-    const long long s = ab_insert(pairs, p.pcap, key);
+__device__ __forceinline__ void ab_add(const AbP &p, int n, rc_u64 *pairs, rc_u64 key, rc_u64 border) {
+    const long long s = rc_pair_insert(pairs, p.pcap, key);
     if (s >= 0) atomicAdd(pairs + 2 * s + 1, border);
     else atomicOr(p.flag + 2 * (size_t)n, 1u);
 }
 
-// The key of two neighbouring regions a != b with the words wa and wb: (small, stable) in that order, AB_EMPTY for every other combination.
-__device__ __forceinline__ ab_u64 ab_key(int a, ab_u64 wa, int b, ab_u64 wb) {
-    if (a == b || (wa == AB_STABLE) == (wb == AB_STABLE)) return AB_EMPTY;
-    return wa == AB_STABLE ? ((ab_u64)(unsigned)b << 32) | (unsigned)a : ((ab_u64)(unsigned)a << 32) | (unsigned)b;
-}
-
-// Lanes next to each other that hold one key: true on the first lane of each stretch, with the stretch's length.  Every lane of the wave calls.
-__device__ __forceinline__ bool ab_segment(ab_u64 key, int lane, int &len) {
-    const ab_u64 left = __shfl_up(key, 1, 64);
-    const bool head = lane == 0 || left != key;
-    const ab_u64 heads = __ballot(head);
-    const ab_u64 after = lane == 63 ? 0ull : heads >> (lane + 1);
-    len = after ? __ffsll((long long)after) : 64 - lane;
-    return head;
+// The key of two neighbouring regions a != b with the words wa and wb: (small, stable) in that order, RC_EMPTY for every other combination.
+__device__ __forceinline__ rc_u64 ab_key(int a, rc_u64 wa, int b, rc_u64 wb) {
+    if (a == b || (wa == AB_STABLE) == (wb == AB_STABLE)) return RC_EMPTY;
+    return wa == AB_STABLE ? ((rc_u64)(unsigned)b << 32) | (unsigned)a : ((rc_u64)(unsigned)a << 32) | (unsigned)b;
 }
 
 // The value run i takes: its target's where its region has one, its own otherwise.  R: the frame's regions (<= rcap).
-__device__ __forceinline__ unsigned ab_value(const unsigned *runs, const int *rr, const ab_u64 *best, const long long *reg, int R, int i) {
+__device__ __forceinline__ unsigned ab_value(const unsigned *runs, const int *rr, const rc_u64 *best, const long long *reg, int R, int i) {
     const int r = rr[i];
     if ((unsigned)r < (unsigned)R) {
-        const ab_u64 w = best[r];
+        const rc_u64 w = best[r];
         if (w != 0 && w != AB_STABLE) {
             const unsigned s = 0xffffffffu - (unsigned)(w & 0xffffffffull);
             if (s < (unsigned)R) return (unsigned)reg[(size_t)s * 8] & 0xffu;
@@ -137,10 +103,10 @@ __global__ __launch_bounds__(256) void absorb_clear_kernel(const AbP p) {
         if (blockIdx.x == 0 && threadIdx.x == 0) { p.nabs[n] = ok ? 0 : -1; p.flag[2 * (size_t)n] = 0; p.flag[2 * (size_t)n + 1] = 0; }
         if (!ok) continue;
         const long long R = p.nreg[n];
-        ab_u64 *pairs = p.pairs + (size_t)n * p.pcap * 2, *best = p.best + (size_t)n * p.rcap;
+        rc_u64 *pairs = p.pairs + (size_t)n * p.pcap * 2, *best = p.best + (size_t)n * p.rcap;
         const long long *reg = p.reg + (size_t)n * p.rcap * 8;
         for (long long i = (long long)blockIdx.x * blockDim.x + threadIdx.x; i < max(p.pcap, R); i += (long long)gridDim.x * blockDim.x) {
-            if (i < p.pcap) { pairs[2 * i] = AB_EMPTY; pairs[2 * i + 1] = 0; }
+            if (i < p.pcap) { pairs[2 * i] = RC_EMPTY; pairs[2 * i + 1] = 0; }
             if (i < R) best[i] = (reg[i * 8 + 1] >= p.min_area || ab_protected(p, (unsigned)reg[i * 8] & 0xffu)) ? AB_STABLE : 0ull;
         }
     }
@@ -155,20 +121,20 @@ __global__ __launch_bounds__(64 * AB_WAVES) void absorb_vote_kernel(const AbP p)
         const int *rs = p.rs + (size_t)n * (p.H + 1);
         const unsigned *runs = p.runs + (size_t)n * p.cap_stride;
         const int *rr = p.rr + (size_t)n * p.cap_stride;
-        const ab_u64 *best = p.best + (size_t)n * p.rcap;
-        ab_u64 *pairs = p.pairs + (size_t)n * p.pcap * 2;
+        const rc_u64 *best = p.best + (size_t)n * p.rcap;
+        rc_u64 *pairs = p.pairs + (size_t)n * p.pcap * 2;
         for (int y = blockIdx.x * AB_WAVES + wave; y < p.H; y += gridDim.x * AB_WAVES) {
             // a malformed row_start may not lead outside [0, total): both rows are clamped into it
-            const int first = ab_clamp(rs[y], 0, total), last = ab_clamp(rs[y + 1], first, total);
-            const int pf = y > 0 ? ab_clamp(rs[y - 1], 0, first) : first, pl = first;          // the row above: [pf, pl), empty for y == 0
+            int first, last;
+            rc_row(rs, y, total, first, last);
+            const int pf = y > 0 ? rc_clamp(rs[y - 1], 0, first) : first, pl = first;          // the row above: [pf, pl), empty for y == 0
             for (int i0 = first; i0 < last; i0 += 64) {                     // i0 is wave uniform: every lane makes every pass
                 const int i = i0 + lane;
                 const bool live = i < last;
                 int r = -1, a0 = 0, a1 = 0;
-                ab_u64 wr = 0, key = AB_EMPTY;
+                rc_u64 wr = 0, key = RC_EMPTY;
                 if (live) {
-                    a0 = min((int)(runs[i] >> 8), p.W);
-                    a1 = i + 1 < last ? ab_clamp((int)(runs[i + 1] >> 8), a0, p.W) : p.W;
+                    a0 = rc_x0(runs, i, p.W); a1 = rc_x1(runs, i, last, p.W);
                     r = rr[i];
                     if ((unsigned)r >= (unsigned)R) r = -1;
                     else wr = best[r];
@@ -178,31 +144,26 @@ __global__ __launch_bounds__(64 * AB_WAVES) void absorb_vote_kernel(const AbP p)
                     }
                 }
                 int len;
-                const bool head = ab_segment(key, lane, len);
-                if (head && key != AB_EMPTY) ab_add(p, n, pairs, key, (ab_u64)len);
+                const bool head = rc_segment(key, lane, len);
+                if (head && key != RC_EMPTY) ab_add(p, n, pairs, key, (rc_u64)len);
                 if (r < 0 || pl <= pf || a1 <= a0) continue;                // no shuffle follows in this pass
-                // the first run j of the row above with b1 > a0: b1 is the start of run j + 1, or W behind the row's last run
-                int lo = pf + 1, hi = pl;
-                while (lo < hi) {
-                    const int mid = (lo + hi) >> 1;
-                    if ((int)(runs[mid] >> 8) > a0) hi = mid; else lo = mid + 1;
-                }
-                ab_u64 open = AB_EMPTY, sum = 0;                            // the key of the last runs above and their overlap so far
-                for (int j = lo - 1; j < pl; ++j) {
-                    const int b0 = min((int)(runs[j] >> 8), p.W);
+                rc_u64 open = RC_EMPTY, sum = 0;                            // the key of the last runs above and their overlap so far
+                // from the first run j of the row above with b1 > a0 on: b1 is the start of run j + 1, or W behind the row's last run
+                for (int j = rc_cover(runs, pf, pl, a0); j < pl; ++j) {
+                    const int b0 = rc_x0(runs, j, p.W);
                     if (b0 >= a1) break;                                    // the row is sorted: no later run overlaps
-                    const int b1 = j + 1 < pl ? min((int)(runs[j + 1] >> 8), p.W) : p.W;
+                    const int b1 = rc_x1(runs, j, pl, p.W);
                     const int overlap = min(a1, b1) - max(a0, b0);
                     const int q = rr[j];
                     if (overlap <= 0 || (unsigned)q >= (unsigned)R) continue;
-                    const ab_u64 k = ab_key(r, wr, q, best[q]);
+                    const rc_u64 k = ab_key(r, wr, q, best[q]);
                     if (k != open) {
-                        if (open != AB_EMPTY) ab_add(p, n, pairs, open, sum);
+                        if (open != RC_EMPTY) ab_add(p, n, pairs, open, sum);
                         open = k; sum = 0;
                     }
-                    sum += (ab_u64)overlap;
+                    sum += (rc_u64)overlap;
                 }
-                if (open != AB_EMPTY) ab_add(p, n, pairs, open, sum);
+                if (open != RC_EMPTY) ab_add(p, n, pairs, open, sum);
             }
         }
     }
@@ -212,11 +173,11 @@ __global__ __launch_bounds__(256) void absorb_resolve_kernel(const AbP p) {
     for (int n = blockIdx.y; n < p.N; n += gridDim.y) {
         if (ab_total(p, n) < 0 || p.flag[2 * (size_t)n] != 0) continue;
         const long long R = p.nreg[n];
-        const ab_u64 *pairs = p.pairs + (size_t)n * p.pcap * 2;
-        ab_u64 *best = p.best + (size_t)n * p.rcap;
+        const rc_u64 *pairs = p.pairs + (size_t)n * p.pcap * 2;
+        rc_u64 *best = p.best + (size_t)n * p.rcap;
         for (long long i = (long long)blockIdx.x * blockDim.x + threadIdx.x; i < p.pcap; i += (long long)gridDim.x * blockDim.x) {
-            const ab_u64 key = pairs[2 * i];
-            if (key == AB_EMPTY) continue;
+            const rc_u64 key = pairs[2 * i];
+            if (key == RC_EMPTY) continue;
             const long long r = (long long)(key >> 32);
             if (r < R) atomicMax(best + r, (pairs[2 * i + 1] << 32) | (0xffffffffull - (key & 0xffffffffull)));          // the longest border, then the smaller index
         }
@@ -234,12 +195,13 @@ __global__ __launch_bounds__(64 * AB_WAVES) void absorb_rows_kernel(const AbP p)
         const int *rs = p.rs + (size_t)n * (p.H + 1);
         const unsigned *runs = p.runs + (size_t)n * p.cap_stride;
         const int *rr = p.rr + (size_t)n * p.cap_stride;
-        const ab_u64 *best = p.best + (size_t)n * p.rcap;
+        const rc_u64 *best = p.best + (size_t)n * p.rcap;
         const long long *reg = p.reg + (size_t)n * p.rcap * 8;
         int *out_rs = p.out_rs + (size_t)n * (p.H + 1);
         unsigned *out_runs = p.out_runs + (size_t)n * p.out_stride;
         for (int y = blockIdx.x * AB_WAVES + wave; y < p.H; y += gridDim.x * AB_WAVES) {
-            const int first = ab_clamp(rs[y], 0, total), last = ab_clamp(rs[y + 1], first, total);
+            int first, last;
+            rc_row(rs, y, total, first, last);
             int base = EMIT ? out_rs[y] : 0;
             for (int i0 = first; i0 < last; i0 += 64) {                     // i0 is wave uniform: every lane makes every pass
                 const int i = i0 + lane;
@@ -248,7 +210,7 @@ __global__ __launch_bounds__(64 * AB_WAVES) void absorb_rows_kernel(const AbP p)
                 unsigned left = __shfl_up(v, 1, 64);
                 if (lane == 0) left = i0 > first ? ab_value(runs, rr, best, reg, R, i0 - 1) : 0x100u;          // 0x100: no value, the row's first run survives
                 const bool survives = live && v != left;
-                const ab_u64 found = __ballot(survives);
+                const rc_u64 found = __ballot(survives);
                 if constexpr (EMIT) {
                     const int idx = base + __popcll(found & ((1ull << lane) - 1ull));
                     if (survives && idx >= 0 && idx < p.out_cap) out_runs[idx] = (runs[i] & ~0xffu) | v;
@@ -262,10 +224,10 @@ __global__ __launch_bounds__(64 * AB_WAVES) void absorb_rows_kernel(const AbP p)
     }
 }
 
-// out_row_start[n][1 .. H]: counts -> their inclusive prefix, in place (rle_scan_kernel's scheme); target and n_absorbed from the regions' words
+// out_row_start[n][1 .. H]: counts -> their inclusive prefix, in place (rc_block_scan); target and n_absorbed from the regions' words
 __global__ __launch_bounds__(256) void absorb_scan_kernel(const AbP p) {
     __shared__ int part[4];
-    const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
+    const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;          // (for the count of the absorbed regions)
     for (int n = blockIdx.x; n < p.N; n += gridDim.x) {
         if (ab_total(p, n) < 0) continue;
         if (p.flag[2 * (size_t)n] != 0) {
@@ -277,30 +239,19 @@ __global__ __launch_bounds__(256) void absorb_scan_kernel(const AbP p) {
         for (int i0 = 1; i0 <= p.H; i0 += 256) {
             const int i = i0 + (int)threadIdx.x;
             int inc = i <= p.H ? rs[i] : 0;
-#pragma unroll
-            for (int o = 1; o < 64; o <<= 1) {
-                const int t = __shfl_up(inc, o, 64);
-                inc += lane >= o ? t : 0;
-            }
-            if (lane == 63) part[wave] = inc;
-            __syncthreads();
-            int before = carry;
-#pragma unroll
-            for (int k = 0; k < 4; ++k) before += k < wave ? part[k] : 0;
-            carry += part[0] + part[1] + part[2] + part[3];
-            if (i <= p.H) rs[i] = before + inc;
-            __syncthreads();
+            rc_block_scan<1>(&inc, &carry, part);
+            if (i <= p.H) rs[i] = inc;
         }
         if (threadIdx.x == 0) rs[0] = 0;
         const int R = p.nreg[n];
-        const ab_u64 *best = p.best + (size_t)n * p.rcap;
+        const rc_u64 *best = p.best + (size_t)n * p.rcap;
         int *target = p.target ? p.target + (size_t)n * p.tcap : nullptr;
         int absorbed = 0;
         for (int r0 = 0; r0 < R; r0 += 256) {                              // r0 is uniform: every thread makes every pass
             const int r = r0 + (int)threadIdx.x;
             int t = -1;
             if (r < R) {
-                const ab_u64 w = best[r];
+                const rc_u64 w = best[r];
                 if (w != AB_STABLE) t = w == 0 ? -2 : (int)(0xffffffffu - (unsigned)(w & 0xffffffffull));
                 if (r < p.tcap) target[r] = t;
             }
@@ -311,13 +262,6 @@ __global__ __launch_bounds__(256) void absorb_scan_kernel(const AbP p) {
         if (threadIdx.x == 0) p.nabs[n] = part[0] + part[1] + part[2] + part[3];
         __syncthreads();
     }
-}
-
-// workgroups per frame x frames for `items` items of work a workgroup takes `per` of, capped for the grid-stride loops
-dim3 ab_grid(int N, long long items, int per) {
-    const int gy = N < 65535 ? N : 65535;
-    const long long share = 16384 / gy > 0 ? 16384 / gy : 1, need = (items + per - 1) / per;
-    return dim3((unsigned)(need < share ? (need > 0 ? need : 1) : share), (unsigned)gy);
 }
 
 }  // namespace
@@ -339,35 +283,33 @@ extern "C" int arseg_rle_absorb_fwd(const int32_t *row_start, const uint32_t *ru
     ARSEG_CHECK_POS(N); ARSEG_CHECK_POS(H); ARSEG_CHECK_POS(W);
     if (cap <= 0 || pcap <= 0 || out_cap <= 0 || min_area < 1 || rcap < 0 || tcap < 0 || (target == nullptr && tcap > 0)) return ARSEG_EINVAL;
     if (W > (1 << 24) || (int64_t)H * W > (int64_t)INT32_MAX) return ARSEG_EINVAL;
-    if (((reinterpret_cast<uintptr_t>(row_start) | reinterpret_cast<uintptr_t>(runs) | reinterpret_cast<uintptr_t>(n_regions) |
-          reinterpret_cast<uintptr_t>(run_region) | reinterpret_cast<uintptr_t>(out_row_start) | reinterpret_cast<uintptr_t>(out_runs) |
-          reinterpret_cast<uintptr_t>(target) | reinterpret_cast<uintptr_t>(n_absorbed)) & 3u) ||
-        ((reinterpret_cast<uintptr_t>(regions) | reinterpret_cast<uintptr_t>(workspace)) & 7u))
+    if (rc_misaligned(4, row_start, runs, n_regions, run_region, out_row_start, out_runs, target, n_absorbed) ||
+        rc_misaligned(8, regions, workspace))
         return ARSEG_EINVAL;
     if (workspace_bytes < arseg_rle_absorb_workspace_bytes(N, cap, rcap, H, pcap)) return ARSEG_EWORKSPACE;
     ARSEG_CHECK_PTR(workspace);
     AbP p = {};
     p.rs = row_start; p.runs = runs; p.nreg = n_regions; p.rr = run_region; p.reg = reinterpret_cast<const long long *>(regions);
     p.out_rs = out_row_start; p.out_runs = out_runs; p.target = target; p.nabs = n_absorbed;
-    p.pairs = static_cast<ab_u64 *>(workspace);
+    p.pairs = static_cast<rc_u64 *>(workspace);
     p.best = p.pairs + (size_t)N * (size_t)pcap * 2;
     p.flag = reinterpret_cast<unsigned *>(p.best + (size_t)N * (size_t)rcap);
     if (protect)
         for (int v = 0; v < 256; ++v)
             if (protect[v]) p.protect[v >> 6] |= 1ull << (v & 63);
     p.cap_stride = cap; p.out_stride = out_cap; p.rcap = rcap; p.tcap = target ? tcap : 0; p.pcap = pcap; p.min_area = min_area;
-    p.cap = (int)(cap < (int64_t)INT32_MAX ? cap : (int64_t)INT32_MAX);
-    p.out_cap = (int)(out_cap < (int64_t)INT32_MAX ? out_cap : (int64_t)INT32_MAX);
+    p.cap = rc_cap(cap); p.out_cap = rc_cap(out_cap);
     p.N = N; p.H = H; p.W = W;
     hipStream_t st = arseg_stream(stream);
     // a frame that is not refused has at most min(rcap, H * W) regions
     const long long regions_most = rcap < (long long)H * W ? rcap : (long long)H * W;
-    const dim3 per_item = ab_grid(N, pcap > regions_most ? pcap : regions_most, 256), per_slot = ab_grid(N, pcap, 256), per_row = ab_grid(N, H, AB_WAVES);
+    const dim3 per_item = rc_grid(N, pcap > regions_most ? pcap : regions_most, 256, 16384), per_slot = rc_grid(N, pcap, 256, 16384);
+    const dim3 per_row = rc_grid(N, H, AB_WAVES, 16384);
     hipLaunchKernelGGL(absorb_clear_kernel, per_item, dim3(256), 0, st, p);
     hipLaunchKernelGGL(absorb_vote_kernel, per_row, dim3(64 * AB_WAVES), 0, st, p);
     hipLaunchKernelGGL(absorb_resolve_kernel, per_slot, dim3(256), 0, st, p);
     hipLaunchKernelGGL((absorb_rows_kernel<false>), per_row, dim3(64 * AB_WAVES), 0, st, p);
-    hipLaunchKernelGGL(absorb_scan_kernel, dim3((unsigned)(N < 65535 ? N : 65535)), dim3(256), 0, st, p);
+    hipLaunchKernelGGL(absorb_scan_kernel, rc_frames(N), dim3(256), 0, st, p);
     hipLaunchKernelGGL((absorb_rows_kernel<true>), per_row, dim3(64 * AB_WAVES), 0, st, p);
     return arseg_launch_status();
 }

@@ -21,7 +21,7 @@
 //            end of a run of its value.  Touching runs of one value are one region, so values and the connectivity decide everything.
 //   jump     K times: a lane per edge combines its window with the window its pointer names; the first minimum is kept.  Once the window
 //            covers the cycle every edge knows its leader and the weight from itself forward to the leader; further rounds change nothing.
-//   scan     one workgroup per frame: rle.hip's prefix over the edges, of the leaders (a loop's index) and of their vertex totals (a loop's
+//   scan     one workgroup per frame: the prefix (rc_block_scan) over the edges, of the leaders (a loop's index) and of their vertex totals (a loop's
 //            first); counts and the loop records.
 //   emit     the walk of succ over rows and runs: an edge with a move writes its two corners at first + position, the position turned by
 //            one for a hole (which begins where its leader starts, not where it ends); words below vcap only.
@@ -29,16 +29,14 @@
 //
 // Bounds of the loops (nothing else loops):
 //   grid-stride loops      over frames, rows, runs of a row and edges: counted.
-//   the binary search      over (first, last] of the neighbouring row: at most 31 rounds.
+//   rc_cover               a binary search over (first, last] of the neighbouring row: at most 31 rounds.
 //   the walks              advance one run of one row per round and end at that row's first or last run at the latest.
 //   the shuffles           6 rounds.
-// Indices are clamped as regions.hip clamps them: a row's runs into [0, stored runs) of its frame, columns into [0, W].  Every successor
+// Indices are clamped by runcode.h: a row's runs into [0, stored runs) of its frame, columns into [0, W].  Every successor
 // is made from such a run index, so every pointer the jumps follow stays below twice the stored runs; a loop index or a vertex position
 // is used only below lcap or vcap; a division is made only by a positive total.  A malformed run code gives meaningless loops and nothing
 // outside the caller's buffers.
-#include "arseg_device.h"
-
-#include <limits.h>
+#include "runcode.h"
 
 namespace {
 
@@ -63,26 +61,10 @@ struct CtP {
     int N, H, W, eight;
 };
 
-__device__ __forceinline__ int ct_clamp(int v, int lo, int hi) { return min(max(v, lo), hi); }
-
 // The stored runs of a frame, or -1 for a frame that is refused: its run code overflowed or its regions are missing.
 __device__ __forceinline__ int ct_total(const CtP &p, int n) {
-    const int need = p.rs[(size_t)n * (p.H + 1) + p.H];
-    return (need > p.cap || p.nreg[n] < 0) ? -1 : max(need, 0);
-}
-
-__device__ __forceinline__ int ct_x0(const unsigned *runs, int i, int W) { return min((int)(runs[i] >> 8), W); }
-// l: the end of run i's row
-__device__ __forceinline__ int ct_x1(const unsigned *runs, int i, int l, int W) { return i + 1 < l ? min((int)(runs[i + 1] >> 8), W) : W; }
-
-// The run of the row [f, l), f < l, that covers column x: the last one that starts at or before x.
-__device__ __forceinline__ int ct_cover(const unsigned *runs, int f, int l, int x) {
-    int lo = f + 1, hi = l;
-    while (lo < hi) {
-        const int mid = (lo + hi) >> 1;
-        if ((int)(runs[mid] >> 8) > x) hi = mid; else lo = mid + 1;
-    }
-    return lo - 1;
+    const int stored = rc_stored(p.rs[(size_t)n * (p.H + 1) + p.H], p.cap);
+    return (stored < 0 || p.nreg[n] < 0) ? -1 : stored;          // (n_regions is not read for an overflowed frame)
 }
 
 // Eastwards along line Y, the top of run t (tl: the end of its row), the region below: the first run in [j, stop) of the row above with
@@ -90,9 +72,9 @@ __device__ __forceinline__ int ct_cover(const unsigned *runs, int f, int l, int 
 // right end of t.
 __device__ __forceinline__ void ct_east(const unsigned *runs, int W, bool eight, int t, int tl, int Y, unsigned v, int j, int stop, unsigned &next,
                                         unsigned &corner) {
-    const int t1 = ct_x1(runs, t, tl, W);
+    const int t1 = rc_x1(runs, t, tl, W);
     for (; j < stop; ++j) {
-        const int b0 = ct_x0(runs, j, W);
+        const int b0 = rc_x0(runs, j, W);
         if (eight ? b0 > t1 : b0 >= t1) break;
         if ((runs[j] & 0xffu) == v) { next = 2u * (unsigned)j; corner = ((unsigned)Y << 16) | (unsigned)b0; return; }
     }
@@ -103,9 +85,9 @@ __device__ __forceinline__ void ct_east(const unsigned *runs, int W, bool eight,
 // that ends behind the start of t (at it too with 8-connectivity) -> its right end; else the left end of t.
 __device__ __forceinline__ void ct_west(const unsigned *runs, int W, bool eight, int t, int Y, unsigned v, int k, int stop, int kl, unsigned &next,
                                         unsigned &corner) {
-    const int t0 = ct_x0(runs, t, W);
+    const int t0 = rc_x0(runs, t, W);
     for (; k >= stop; --k) {
-        const int k1 = ct_x1(runs, k, kl, W);
+        const int k1 = rc_x1(runs, k, kl, W);
         if (eight ? k1 < t0 : k1 <= t0) break;
         if ((runs[k] & 0xffu) == v) { next = 2u * (unsigned)k + 1u; corner = ((unsigned)Y << 16) | (unsigned)k1; return; }
     }
@@ -130,21 +112,22 @@ __global__ __launch_bounds__(64 * CT_WAVES) void contours_succ_kernel(const CtP 
         const size_t edge0 = (size_t)n * 2 * p.cap_stride;
         for (int y = blockIdx.x * CT_WAVES + wave; y < p.H; y += gridDim.x * CT_WAVES) {
             // a malformed row_start may not lead outside [0, total): the three rows are clamped into it
-            const int first = ct_clamp(rs[y], 0, total), last = ct_clamp(rs[y + 1], first, total);
-            const int pf = y > 0 ? ct_clamp(rs[y - 1], 0, first) : first, pl = first;              // the row above: [pf, pl), empty for y == 0
-            const int nf = last, nl = y + 1 < p.H ? ct_clamp(rs[y + 2], last, total) : last;      // the row below: [nf, nl)
+            int first, last;
+            rc_row(rs, y, total, first, last);
+            const int pf = y > 0 ? rc_clamp(rs[y - 1], 0, first) : first, pl = first;              // the row above: [pf, pl), empty for y == 0
+            const int nf = last, nl = y + 1 < p.H ? rc_clamp(rs[y + 2], last, total) : last;      // the row below: [nf, nl)
             for (int i = first + lane; i < last; i += 64) {                  // no lane needs another: nothing is shuffled here
                 const unsigned v = runs[i] & 0xffu;
-                const int a0 = ct_x0(runs, i, p.W), a1 = ct_x1(runs, i, last, p.W);
+                const int a0 = rc_x0(runs, i, p.W), a1 = rc_x1(runs, i, last, p.W);
                 for (int side = 0; side < 2; ++side) {
                     unsigned next, corner;
                     const unsigned own = side ? ((unsigned)(y + 1) << 16) | (unsigned)a1 : ((unsigned)y << 16) | (unsigned)a0;
                     if (side == 0) {                                        // arriving at (a0, y), heading up
                         if (pl <= pf) ct_east(runs, p.W, eight, i, last, y, v, 0, 0, next, corner);
                         else {
-                            const int q = ct_cover(runs, pf, pl, a0);
+                            const int q = rc_cover(runs, pf, pl, a0);
                             const bool ur = (runs[q] & 0xffu) == v;
-                            const bool ul = a0 > 0 && (ct_x0(runs, q, p.W) < a0 ? ur : (q > pf && (runs[q - 1] & 0xffu) == v));
+                            const bool ul = a0 > 0 && (rc_x0(runs, q, p.W) < a0 ? ur : (q > pf && (runs[q - 1] & 0xffu) == v));
                             if (ur && !ul) { next = 2u * (unsigned)q; corner = own; }
                             else if (ur || (eight && ul)) ct_west(runs, p.W, eight, ur ? q : q - 1, y, v, i - 1, first, last, next, corner);
                             else ct_east(runs, p.W, eight, i, last, y, v, q + 1, pl, next, corner);
@@ -152,9 +135,9 @@ __global__ __launch_bounds__(64 * CT_WAVES) void contours_succ_kernel(const CtP 
                     } else {                                                // arriving at (a1, y + 1), heading down
                         if (nl <= nf) ct_west(runs, p.W, eight, i, y + 1, v, -1, 0, last, next, corner);
                         else {
-                            const int q = ct_cover(runs, nf, nl, a1 - 1);
+                            const int q = rc_cover(runs, nf, nl, a1 - 1);
                             const bool bl = (runs[q] & 0xffu) == v;
-                            const bool br = a1 < p.W && (ct_x1(runs, q, nl, p.W) > a1 ? bl : (q + 1 < nl && (runs[q + 1] & 0xffu) == v));
+                            const bool br = a1 < p.W && (rc_x1(runs, q, nl, p.W) > a1 ? bl : (q + 1 < nl && (runs[q + 1] & 0xffu) == v));
                             if (bl && !br) { next = 2u * (unsigned)q + 1u; corner = own; }
                             else if (bl || (eight && br)) ct_east(runs, p.W, eight, bl ? q : q + 1, nl, y + 1, v, i + 1, last, next, corner);
                             else ct_west(runs, p.W, eight, i, y + 1, v, q, nf, nl, next, corner);
@@ -189,10 +172,9 @@ __global__ __launch_bounds__(256) void contours_jump_kernel(const CtP p, int fro
 }
 
 // Per frame: the leaders (the edges that are their window's smallest) counted and their totals summed over the edge array, 256 at a time
-// with a carry (rle_scan_kernel's scheme) -> the loop records, {first, count, index} at the leader in st[1 - fin], and counts.
+// with a carry (rc_block_scan) -> the loop records, {first, count, index} at the leader in st[1 - fin], and counts.
 __global__ __launch_bounds__(256) void contours_scan_kernel(const CtP p, int fin) {
-    __shared__ unsigned part[2][4];
-    const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
+    __shared__ unsigned part[2 * 4];
     for (int n = blockIdx.x; n < p.N; n += gridDim.x) {
         const int total = ct_total(p, n);
         if (total < 0) continue;
@@ -202,7 +184,7 @@ __global__ __launch_bounds__(256) void contours_scan_kernel(const CtP p, int fin
         const unsigned *succ = p.succ + edge0;
         const int *rr = p.rr + (size_t)n * p.cap_stride;
         const unsigned edges = 2u * (unsigned)total;
-        unsigned carry_l = 0, carry_v = 0;
+        unsigned carry[2] = {0, 0};                                         // loops, vertices
         for (unsigned e0 = 0; e0 < edges; e0 += 256) {                      // e0 is uniform: every thread makes every pass
             const unsigned e = e0 + threadIdx.x;
             bool lead = false;
@@ -212,29 +194,17 @@ __global__ __launch_bounds__(256) void contours_scan_kernel(const CtP p, int fin
                 lead = true;
                 count = 2u * (s & 1u) + st[min(s >> 1, edges - 1u)].z;       // its own move and the weight from its successor back to it
             }
-            unsigned inc_l = lead ? 1u : 0u, inc_v = count;
-#pragma unroll
-            for (int o = 1; o < 64; o <<= 1) {
-                const unsigned tl = __shfl_up(inc_l, o, 64), tv = __shfl_up(inc_v, o, 64);
-                inc_l += lane >= o ? tl : 0u; inc_v += lane >= o ? tv : 0u;
-            }
-            if (lane == 63) { part[0][wave] = inc_l; part[1][wave] = inc_v; }
-            __syncthreads();
-            unsigned before_l = carry_l, before_v = carry_v;
-#pragma unroll
-            for (int k = 0; k < 4; ++k) { before_l += k < wave ? part[0][k] : 0u; before_v += k < wave ? part[1][k] : 0u; }
-            carry_l += part[0][0] + part[0][1] + part[0][2] + part[0][3];
-            carry_v += part[1][0] + part[1][1] + part[1][2] + part[1][3];
+            unsigned inc[2] = {lead ? 1u : 0u, count};
+            rc_block_scan<2>(inc, carry, part);                             // both in one pass
             if (lead) {
-                const unsigned index = before_l + inc_l - 1u, firstv = before_v + inc_v - count;
+                const unsigned index = inc[0] - 1u, firstv = inc[1] - count;
                 info[e] = ct_u32x4{firstv, count, index, 0u};
                 if ((long long)index < p.lcap)
                     *reinterpret_cast<ct_i32x4 *>(p.loops + ((size_t)n * p.lcap + index) * 4) =
                         ct_i32x4{rr[e >> 1], (int)firstv, (int)count, (int)(e & 1u)};
             }
-            __syncthreads();
         }
-        if (threadIdx.x == 0) { p.counts[2 * (size_t)n] = (int)carry_l; p.counts[2 * (size_t)n + 1] = (int)carry_v; }
+        if (threadIdx.x == 0) { p.counts[2 * (size_t)n] = (int)carry[0]; p.counts[2 * (size_t)n + 1] = (int)carry[1]; }
     }
 }
 
@@ -250,9 +220,10 @@ __global__ __launch_bounds__(64 * CT_WAVES) void contours_emit_kernel(const CtP 
         unsigned *verts = p.verts + (size_t)n * p.vcap;
         const unsigned edges = 2u * (unsigned)total;
         for (int y = blockIdx.x * CT_WAVES + wave; y < p.H; y += gridDim.x * CT_WAVES) {
-            const int first = ct_clamp(rs[y], 0, total), last = ct_clamp(rs[y + 1], first, total);
+            int first, last;
+            rc_row(rs, y, total, first, last);
             for (int i = first + lane; i < last; i += 64) {
-                const int a0 = ct_x0(runs, i, p.W), a1 = ct_x1(runs, i, last, p.W);
+                const int a0 = rc_x0(runs, i, p.W), a1 = rc_x1(runs, i, last, p.W);
                 for (int side = 0; side < 2; ++side) {
                     const unsigned e = 2u * (unsigned)i + (unsigned)side;
                     if (!(p.succ[edge0 + e] & 1u)) continue;                // it goes straight on: no corner
@@ -272,13 +243,6 @@ __global__ __launch_bounds__(64 * CT_WAVES) void contours_emit_kernel(const CtP 
             }
         }
     }
-}
-
-// workgroups per frame x frames for `items` items of work a workgroup takes `per` of, capped for the grid-stride loops
-dim3 ct_grid(int N, long long items, int per) {
-    const int gy = N < 65535 ? N : 65535;
-    const long long share = 4096 / gy > 0 ? 4096 / gy : 1, need = (items + per - 1) / per;
-    return dim3((unsigned)(need < share ? (need > 0 ? need : 1) : share), (unsigned)gy);
 }
 
 // the rounds of pointer jumping that cover a cycle of 2 cap edges: the smallest K with 2^K >= 2 cap
@@ -304,10 +268,7 @@ extern "C" int arseg_rle_contours_fwd(const int32_t *row_start, const uint32_t *
     if (cap <= 0 || cap > ((int64_t)1 << 29) || lcap < 0 || vcap < 0 || (loops == nullptr && lcap > 0) || (verts == nullptr && vcap > 0))
         return ARSEG_EINVAL;
     if ((connectivity != 4 && connectivity != 8) || H > 65535 || W > 65535) return ARSEG_EINVAL;
-    if ((reinterpret_cast<uintptr_t>(row_start) | reinterpret_cast<uintptr_t>(runs) | reinterpret_cast<uintptr_t>(n_regions) |
-         reinterpret_cast<uintptr_t>(run_region) | reinterpret_cast<uintptr_t>(counts) | reinterpret_cast<uintptr_t>(loops) |
-         reinterpret_cast<uintptr_t>(verts) | reinterpret_cast<uintptr_t>(workspace)) & 3u)
-        return ARSEG_EINVAL;
+    if (rc_misaligned(4, row_start, runs, n_regions, run_region, counts, loops, verts, workspace)) return ARSEG_EINVAL;
     if (workspace_bytes < arseg_rle_contours_workspace_bytes(N, cap)) return ARSEG_EWORKSPACE;
     ARSEG_CHECK_PTR(workspace);
     CtP p = {};
@@ -321,12 +282,12 @@ extern "C" int arseg_rle_contours_fwd(const int32_t *row_start, const uint32_t *
     p.cap_stride = cap; p.lcap = p.loops ? lcap : 0; p.vcap = p.verts ? vcap : 0;
     p.cap = (int)cap; p.N = N; p.H = H; p.W = W; p.eight = connectivity == 8;
     hipStream_t st = arseg_stream(stream);
-    const dim3 per_row = ct_grid(N, H, CT_WAVES), per_edge = ct_grid(N, 2 * cap, 256);
+    const dim3 per_row = rc_grid(N, H, CT_WAVES, 4096), per_edge = rc_grid(N, 2 * cap, 256, 4096);
     const int rounds = ct_rounds(cap), fin = rounds & 1;
     hipLaunchKernelGGL(contours_clear_kernel, dim3((unsigned)((N + 255) / 256 < 4096 ? (N + 255) / 256 : 4096)), dim3(256), 0, st, p);
     hipLaunchKernelGGL(contours_succ_kernel, per_row, dim3(64 * CT_WAVES), 0, st, p);
     for (int k = 0; k < rounds; ++k) hipLaunchKernelGGL(contours_jump_kernel, per_edge, dim3(256), 0, st, p, k & 1);
-    hipLaunchKernelGGL(contours_scan_kernel, dim3((unsigned)(N < 65535 ? N : 65535)), dim3(256), 0, st, p, fin);
+    hipLaunchKernelGGL(contours_scan_kernel, rc_frames(N), dim3(256), 0, st, p, fin);
     if (p.vcap > 0) hipLaunchKernelGGL(contours_emit_kernel, per_row, dim3(64 * CT_WAVES), 0, st, p, fin);          // not in a sizing pass
     return arseg_launch_status();
 }

@@ -30,22 +30,17 @@
 //
 // Bounds of the loops (nothing else loops):
 //   grid-stride loops      over frames, rows, pixels of a row, slots and records: counted.
-//   lk_run_at              a binary search over [first, last) with first < last <= stored runs: at most 31 rounds.
-//   lk_insert / lk_lookup  advance one slot per round and end after pcap rounds at the latest.
+//   rc_cover               a binary search over [first, last) with first < last <= stored runs: at most 31 rounds.
+//   rc_pair_insert / rc_pair_lookup  advance one slot per round and end after pcap rounds at the latest.
 //   the shuffles           6 rounds.
-// Indices are clamped as regions.hip clamps them: a row's runs into [0, stored runs) of its frame, a region number is used as an index only
+// Indices are clamped by runcode.h: a row's runs into [0, stored runs) of its frame, a region number is used as an index only
 // below the stored region count and the capacity, a target row only inside [0, H).  A malformed run code or run_region gives meaningless
 // links and nothing outside the caller's buffers.
-#include "arseg_device.h"
-
-#include <limits.h>
+#include "runcode.h"
 
 namespace {
 
-typedef unsigned long long lk_u64;
-
 constexpr int LK_WAVES = 4;                             // waves (= rows in flight) per workgroup
-constexpr lk_u64 LK_EMPTY = ~0ull;                      // no key: r and k are never negative in a key
 
 struct LkSide {
     const int *rs;                                      // [.][H + 1]
@@ -62,79 +57,29 @@ struct LkP {
     int *npairs;                                        // [N]
     long long *links;                                   // [N][rcap][6] (may be null: rcap == 0)
     long long *back;                                    // [N][kcap][4] (may be null: kcap == 0)
-    lk_u64 *pairs;                                      // [N][pcap][2]: key, count
-    lk_u64 *bests;                                      // [N][pcap][2]: k, count << 32 | ~r
+    rc_u64 *pairs;                                      // [N][pcap][2]: key, count
+    rc_u64 *bests;                                      // [N][pcap][2]: k, count << 32 | ~r
     unsigned *flag;                                     // [N][2]: the first word is used
     long long rcap, kcap, pcap;
     int N, H, W, shared;
 };
 
-__device__ __forceinline__ int lk_clamp(int v, int lo, int hi) { return min(max(v, lo), hi); }
-
 // The stored runs of a side's frame, or -1 where the frame has no regions: its run code overflowed or n_regions says so.
 __device__ __forceinline__ int lk_total(const LkSide &s, int f, int H) {
-    const int need = s.rs[(size_t)f * (H + 1) + H];
-    return (need > s.cap || s.nreg[f] < 0) ? -1 : max(need, 0);
+    const int stored = rc_stored(s.rs[(size_t)f * (H + 1) + H], s.cap);
+    return (stored < 0 || s.nreg[f] < 0) ? -1 : stored;          // (n_regions is not read for an overflowed frame)
 }
 __device__ __forceinline__ long long lk_rows(const LkSide &s, int f, long long capacity) { return min((long long)s.nreg[f], capacity); }
-
-// The last run of [first, last) that begins at or before x (the first one when none does); first < last.
-__device__ __forceinline__ int lk_run_at(const unsigned *runs, int first, int last, int x) {
-    int lo = first, hi = last - 1;
-    while (lo < hi) {
-        const int mid = (lo + hi + 1) >> 1;
-        if ((int)(runs[mid] >> 8) <= x) lo = mid; else hi = mid - 1;
-    }
-    return lo;
-}
-
-__device__ __forceinline__ long long lk_slot(lk_u64 key, long long pcap) {
-    const lk_u64 h = (key * 0x9E3779B97F4A7C15ull) >> 32;
-    return pcap < (1ll << 32) ? (long long)((h * (lk_u64)pcap) >> 32) : (long long)h;
-}
-
-// The slot of key in a table of pcap slots of two words, taken when the key is new; -1 when all pcap slots hold other keys.
-__device__ __forceinline__ long long lk_insert(lk_u64 *tab, long long pcap, lk_u64 key) {
-    long long s = lk_slot(key, pcap);
-    for (long long t = 0; t < pcap; ++t) {
-        lk_u64 old = __hip_atomic_load(tab + 2 * s, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
-        if (old == LK_EMPTY) old = atomicCAS(tab + 2 * s, LK_EMPTY, key);
-        if (old == LK_EMPTY || old == key) return s;
-        s = s + 1 == pcap ? 0 : s + 1;
-    }
-    return -1;
-}
-// The slot of key in a finished table, -1 when it is not there.
-__device__ __forceinline__ long long lk_lookup(const lk_u64 *tab, long long pcap, lk_u64 key) {
-    long long s = lk_slot(key, pcap);
-    for (long long t = 0; t < pcap; ++t) {
-        const lk_u64 old = tab[2 * s];
-        if (old == key) return s;
-        if (old == LK_EMPTY) return -1;
-        s = s + 1 == pcap ? 0 : s + 1;
-    }
-    return -1;
-}
-
-// Lanes next to each other that hold one key: true on the first lane of each stretch, with the stretch's length.  Every lane of the wave calls.
-__device__ __forceinline__ bool lk_segment(lk_u64 key, int lane, int &len) {
-    const lk_u64 left = __shfl_up(key, 1, 64);
-    const bool head = lane == 0 || left != key;
-    const lk_u64 heads = __ballot(head);
-    const lk_u64 after = lane == 63 ? 0ull : heads >> (lane + 1);
-    len = after ? __ffsll((long long)after) : 64 - lane;
-    return head;
-}
 
 __global__ __launch_bounds__(256) void links_clear_kernel(const LkP p) {
     for (int n = blockIdx.y; n < p.N; n += gridDim.y) {
         const bool ok = lk_total(p.cur, n, p.H) >= 0 && lk_total(p.ref, p.shared ? 0 : n, p.H) >= 0;
         if (blockIdx.x == 0 && threadIdx.x == 0) { p.npairs[n] = ok ? 0 : -1; p.flag[2 * (size_t)n] = 0; p.flag[2 * (size_t)n + 1] = 0; }
         if (!ok) continue;
-        lk_u64 *pairs = p.pairs + (size_t)n * p.pcap * 2, *bests = p.bests + (size_t)n * p.pcap * 2;
+        rc_u64 *pairs = p.pairs + (size_t)n * p.pcap * 2, *bests = p.bests + (size_t)n * p.pcap * 2;
         for (long long i = (long long)blockIdx.x * blockDim.x + threadIdx.x; i < p.pcap; i += (long long)gridDim.x * blockDim.x) {
-            pairs[2 * i] = LK_EMPTY; pairs[2 * i + 1] = 0;
-            bests[2 * i] = LK_EMPTY; bests[2 * i + 1] = 0;
+            pairs[2 * i] = RC_EMPTY; pairs[2 * i + 1] = 0;
+            bests[2 * i] = RC_EMPTY; bests[2 * i + 1] = 0;
         }
     }
 }
@@ -155,10 +100,11 @@ __global__ __launch_bounds__(64 * LK_WAVES) void links_vote_kernel(const LkP p) 
         const int *rs = p.cur.rs + (size_t)n * (p.H + 1), *qrs = p.ref.rs + (size_t)m * (p.H + 1);
         const unsigned *runs = p.cur.runs + (size_t)n * p.cur.cap_stride, *qruns = p.ref.runs + (size_t)m * p.ref.cap_stride;
         const int *rr = p.cur.rr + (size_t)n * p.cur.cap_stride, *qrr = p.ref.rr + (size_t)m * p.ref.cap_stride;
-        lk_u64 *pairs = p.pairs + (size_t)n * p.pcap * 2;
+        rc_u64 *pairs = p.pairs + (size_t)n * p.pcap * 2;
         for (int y = blockIdx.x * LK_WAVES + wave; y < p.H; y += gridDim.x * LK_WAVES) {
             // a malformed row_start may not lead outside [0, total)
-            const int first = lk_clamp(rs[y], 0, total), last = lk_clamp(rs[y + 1], first, total);
+            int first, last;
+            rc_row(rs, y, total, first, last);
             if (last <= first) continue;                                    // wave uniform
             const unsigned *mv = p.mv ? p.mv + ((size_t)n * p.H + y) * p.W : nullptr;
             for (int x0 = 0; x0 < p.W; x0 += 64) {                          // x0 is wave uniform: every lane makes every pass
@@ -167,31 +113,32 @@ __global__ __launch_bounds__(64 * LK_WAVES) void links_vote_kernel(const LkP p) 
                 const unsigned mq = (live && mv) ? mv[x] : 0u;
                 const int tx = x + round_half_even_div4((int)(short)(mq & 0xffffu)), ty = y + round_half_even_div4((int)(short)(mq >> 16));
                 const bool inside = (unsigned)tx < (unsigned)p.W && (unsigned)ty < (unsigned)p.H;          // no clamp: a target off the frame is never read
-                lk_u64 key = LK_EMPTY;
+                rc_u64 key = RC_EMPTY;
                 if constexpr (OUTSIDE) {
                     if (__ballot(live && !inside) == 0ull) continue;
                     if (live && !inside) {
-                        const int r = rr[lk_run_at(runs, first, last, x)];
-                        if (r >= 0 && r < rlim) key = (lk_u64)(unsigned)r;
+                        const int r = rr[rc_cover(runs, first, last, x)];
+                        if (r >= 0 && r < rlim) key = (rc_u64)(unsigned)r;
                     }
                 } else if (live && inside) {
-                    const int i = lk_run_at(runs, first, last, x);
+                    const int i = rc_cover(runs, first, last, x);
                     const int r = rr[i];
-                    const int qf = lk_clamp(qrs[ty], 0, qtotal), ql = lk_clamp(qrs[ty + 1], qf, qtotal);
+                    int qf, ql;
+                    rc_row(qrs, ty, qtotal, qf, ql);
                     if (r >= 0 && ql > qf) {
-                        const int j = lk_run_at(qruns, qf, ql, tx);
+                        const int j = rc_cover(qruns, qf, ql, tx);
                         const int k = qrr[j];
-                        if (k >= 0 && ((qruns[j] ^ runs[i]) & 0xffu) == 0) key = ((lk_u64)(unsigned)r << 32) | (unsigned)k;
+                        if (k >= 0 && ((qruns[j] ^ runs[i]) & 0xffu) == 0) key = ((rc_u64)(unsigned)r << 32) | (unsigned)k;
                     }
                 }
                 int len;
-                const bool head = lk_segment(key, lane, len);
-                if (!head || key == LK_EMPTY) continue;                     // no shuffle follows in this pass
+                const bool head = rc_segment(key, lane, len);
+                if (!head || key == RC_EMPTY) continue;                     // no shuffle follows in this pass
                 if constexpr (OUTSIDE) {
-                    atomicAdd(reinterpret_cast<lk_u64 *>(p.links + ((size_t)n * p.rcap + key) * 6 + 3), (lk_u64)len);
+                    atomicAdd(reinterpret_cast<rc_u64 *>(p.links + ((size_t)n * p.rcap + key) * 6 + 3), (rc_u64)len);
                 } else {
-                    const long long s = lk_insert(pairs, p.pcap, key);
-                    if (s >= 0) atomicAdd(pairs + 2 * s + 1, (lk_u64)len);
+                    const long long s = rc_pair_insert(pairs, p.pcap, key);
+                    if (s >= 0) atomicAdd(pairs + 2 * s + 1, (rc_u64)len);
                     else atomicOr(p.flag + 2 * (size_t)n, 1u);
                 }
             }
@@ -226,31 +173,31 @@ __global__ __launch_bounds__(256) void links_resolve_kernel(const LkP p) {
         const int m = p.shared ? 0 : n;
         if (lk_total(p.cur, n, p.H) < 0 || lk_total(p.ref, m, p.H) < 0 || p.flag[2 * (size_t)n] != 0) continue;
         const long long rlim = lk_rows(p.cur, n, p.rcap), klim = lk_rows(p.ref, m, p.kcap);
-        const lk_u64 *pairs = p.pairs + (size_t)n * p.pcap * 2;
-        lk_u64 *bests = p.bests + (size_t)n * p.pcap * 2;
+        const rc_u64 *pairs = p.pairs + (size_t)n * p.pcap * 2;
+        rc_u64 *bests = p.bests + (size_t)n * p.pcap * 2;
         // the bound is rounded up to whole waves: every lane of a wave reaches the ballot
         const long long padded = (p.pcap + 63) / 64 * 64;
         for (long long i = (long long)blockIdx.x * blockDim.x + threadIdx.x; i < padded; i += (long long)gridDim.x * blockDim.x) {
-            const lk_u64 key = i < p.pcap ? pairs[2 * i] : LK_EMPTY;
-            const bool taken = key != LK_EMPTY;
+            const rc_u64 key = i < p.pcap ? pairs[2 * i] : RC_EMPTY;
+            const bool taken = key != RC_EMPTY;
             if (taken) {
-                const lk_u64 count = pairs[2 * i + 1];
+                const rc_u64 count = pairs[2 * i + 1];
                 const long long r = (long long)(key >> 32), k = (long long)(key & 0xffffffffu);
                 if (r < rlim) {
-                    lk_u64 *row = reinterpret_cast<lk_u64 *>(p.links + ((size_t)n * p.rcap + r) * 6);
-                    atomicMax(row + 1, (count << 32) | (0xffffffffull - (lk_u64)k));           // the largest count, then the smaller k
+                    rc_u64 *row = reinterpret_cast<rc_u64 *>(p.links + ((size_t)n * p.rcap + r) * 6);
+                    atomicMax(row + 1, (count << 32) | (0xffffffffull - (rc_u64)k));           // the largest count, then the smaller k
                     atomicAdd(row + 2, count);
                     atomicAdd(row + 5, 1ull);
                 }
-                const long long s = lk_insert(bests, p.pcap, (lk_u64)k);           // cannot fail: no more reference regions than pairs
-                if (s >= 0) atomicMax(bests + 2 * s + 1, (count << 32) | (0xffffffffull - (lk_u64)r));
+                const long long s = rc_pair_insert(bests, p.pcap, (rc_u64)k);           // cannot fail: no more reference regions than pairs
+                if (s >= 0) atomicMax(bests + 2 * s + 1, (count << 32) | (0xffffffffull - (rc_u64)r));
                 if (k < klim) {
-                    lk_u64 *row = reinterpret_cast<lk_u64 *>(p.back + ((size_t)n * p.kcap + k) * 4);
+                    rc_u64 *row = reinterpret_cast<rc_u64 *>(p.back + ((size_t)n * p.kcap + k) * 4);
                     atomicAdd(row + 2, count);
                     atomicAdd(row + 3, 1ull);
                 }
             }
-            const lk_u64 found = __ballot(taken);
+            const rc_u64 found = __ballot(taken);
             if (found && (threadIdx.x & 63) == 0) atomicAdd(p.npairs + n, __popcll(found));
         }
     }
@@ -261,23 +208,23 @@ __global__ __launch_bounds__(256) void links_finish_kernel(const LkP p) {
         const int m = p.shared ? 0 : n;
         if (lk_total(p.cur, n, p.H) < 0 || lk_total(p.ref, m, p.H) < 0 || p.flag[2 * (size_t)n] != 0) continue;
         const long long rlim = lk_rows(p.cur, n, p.rcap), klim = lk_rows(p.ref, m, p.kcap);
-        const lk_u64 *bests = p.bests + (size_t)n * p.pcap * 2;
+        const rc_u64 *bests = p.bests + (size_t)n * p.pcap * 2;
         for (long long i = (long long)blockIdx.x * blockDim.x + threadIdx.x; i < max(rlim, klim); i += (long long)gridDim.x * blockDim.x) {
             if (i < rlim) {
                 long long *row = p.links + ((size_t)n * p.rcap + i) * 6;
-                const lk_u64 best = (lk_u64)row[1];
+                const rc_u64 best = (rc_u64)row[1];
                 if (best) {
-                    const lk_u64 k = 0xffffffffull - (best & 0xffffffffull);
-                    const long long s = lk_lookup(bests, p.pcap, k);
+                    const rc_u64 k = 0xffffffffull - (best & 0xffffffffull);
+                    const long long s = rc_pair_lookup(bests, p.pcap, k);
                     row[0] = (long long)k; row[1] = (long long)(best >> 32);
-                    row[4] = (s >= 0 && 0xffffffffull - (bests[2 * s + 1] & 0xffffffffull) == (lk_u64)i) ? 1 : 0;
+                    row[4] = (s >= 0 && 0xffffffffull - (bests[2 * s + 1] & 0xffffffffull) == (rc_u64)i) ? 1 : 0;
                 }
             }
             if (i < klim) {
-                const long long s = lk_lookup(bests, p.pcap, (lk_u64)i);
+                const long long s = rc_pair_lookup(bests, p.pcap, (rc_u64)i);
                 if (s >= 0) {
                     long long *row = p.back + ((size_t)n * p.kcap + i) * 4;
-                    const lk_u64 best = bests[2 * s + 1];
+                    const rc_u64 best = bests[2 * s + 1];
                     row[0] = (long long)(0xffffffffull - (best & 0xffffffffull)); row[1] = (long long)(best >> 32);
                 }
             }
@@ -285,21 +232,12 @@ __global__ __launch_bounds__(256) void links_finish_kernel(const LkP p) {
     }
 }
 
-// workgroups per frame x frames for `items` items of work a workgroup takes `per` of, capped for the grid-stride loops
-dim3 lk_grid(int N, long long items, int per) {
-    const int gy = N < 65535 ? N : 65535;
-    const long long share = 16384 / gy > 0 ? 16384 / gy : 1, need = (items + per - 1) / per;
-    return dim3((unsigned)(need < share ? (need > 0 ? need : 1) : share), (unsigned)gy);
-}
-
 int lk_side(LkSide &s, const int32_t *row_start, const uint32_t *runs, const int32_t *n_regions, const int32_t *run_region, int64_t cap) {
     ARSEG_CHECK_PTR(row_start); ARSEG_CHECK_PTR(runs); ARSEG_CHECK_PTR(n_regions); ARSEG_CHECK_PTR(run_region);
     if (cap <= 0) return ARSEG_EINVAL;
-    if ((reinterpret_cast<uintptr_t>(row_start) | reinterpret_cast<uintptr_t>(runs) | reinterpret_cast<uintptr_t>(n_regions) |
-         reinterpret_cast<uintptr_t>(run_region)) & 3u)
-        return ARSEG_EINVAL;
+    if (rc_misaligned(4, row_start, runs, n_regions, run_region)) return ARSEG_EINVAL;
     s.rs = row_start; s.runs = runs; s.nreg = n_regions; s.rr = run_region;
-    s.cap_stride = cap; s.cap = (int)(cap < (int64_t)INT32_MAX ? cap : (int64_t)INT32_MAX);
+    s.cap_stride = cap; s.cap = rc_cap(cap);
     return ARSEG_OK;
 }
 
@@ -326,9 +264,7 @@ extern "C" int arseg_region_links_fwd(const int32_t *row_start, const uint32_t *
     if (pcap <= 0 || rcap < 0 || kcap < 0 || (links == nullptr && rcap > 0) || (back == nullptr && kcap > 0)) return ARSEG_EINVAL;
     if (ref_shared != 0 && ref_shared != 1) return ARSEG_EINVAL;
     if (W > (1 << 24) || (int64_t)H * W > (int64_t)INT32_MAX) return ARSEG_EINVAL;
-    if (((reinterpret_cast<uintptr_t>(n_pairs) | reinterpret_cast<uintptr_t>(mv_q)) & 3u) ||
-        ((reinterpret_cast<uintptr_t>(links) | reinterpret_cast<uintptr_t>(back) | reinterpret_cast<uintptr_t>(workspace)) & 7u))
-        return ARSEG_EINVAL;
+    if (rc_misaligned(4, n_pairs, mv_q) || rc_misaligned(8, links, back, workspace)) return ARSEG_EINVAL;
     if (workspace_bytes < arseg_region_links_workspace_bytes(N, pcap)) return ARSEG_EWORKSPACE;
     ARSEG_CHECK_PTR(workspace);
     p.mv = reinterpret_cast<const unsigned *>(mv_q);
@@ -336,14 +272,15 @@ extern "C" int arseg_region_links_fwd(const int32_t *row_start, const uint32_t *
     p.links = links ? reinterpret_cast<long long *>(links) : nullptr; p.rcap = links ? rcap : 0;
     p.back = back ? reinterpret_cast<long long *>(back) : nullptr; p.kcap = back ? kcap : 0;
     p.pcap = pcap;
-    p.pairs = static_cast<lk_u64 *>(workspace);
+    p.pairs = static_cast<rc_u64 *>(workspace);
     p.bests = p.pairs + (size_t)N * (size_t)pcap * 2;
     p.flag = reinterpret_cast<unsigned *>(p.bests + (size_t)N * (size_t)pcap * 2);
     p.N = N; p.H = H; p.W = W; p.shared = ref_shared;
     hipStream_t st = arseg_stream(stream);
     // a frame has at most min(cap, H * W) regions: the records beyond cannot be in use
     const long long most = p.rcap > p.kcap ? p.rcap : p.kcap, regions_most = p.cur.cap > p.ref.cap ? p.cur.cap : p.ref.cap;
-    const dim3 per_slot = lk_grid(N, pcap, 256), per_row = lk_grid(N, H, LK_WAVES), per_rec = lk_grid(N, most < regions_most ? most : regions_most, 256);
+    const dim3 per_slot = rc_grid(N, pcap, 256, 16384), per_row = rc_grid(N, H, LK_WAVES, 16384);
+    const dim3 per_rec = rc_grid(N, most < regions_most ? most : regions_most, 256, 16384);
     hipLaunchKernelGGL(links_clear_kernel, per_slot, dim3(256), 0, st, p);
     hipLaunchKernelGGL((links_vote_kernel<false>), per_row, dim3(64 * LK_WAVES), 0, st, p);
     hipLaunchKernelGGL(links_rows_kernel, per_rec, dim3(256), 0, st, p);

@@ -19,7 +19,7 @@
 //            the result: only what atomicMin returns decides.
 //   flatten  parent[i] <- parent[parent[i]] until parent[i] is a root (pointer jumping, in place: a slot only moves to a higher ancestor, so
 //            a reader meets an ancestor whichever value it sees).  Afterwards every slot holds its root, and i is a root iff parent[i] == i.
-//   number   one workgroup per frame: the root flags of the stored runs scanned 256 at a time with a carry (rle_scan_kernel's scheme).  A root
+//   number   one workgroup per frame: the root flags of the stored runs scanned 256 at a time with a carry (rc_block_scan).  A root
 //            gets its dense number into run_region and, below rcap, its record initialised (value; area = sums = 0; min = INT64_MAX;
 //            max = -1); n_regions[n] = R, or -1 for a frame whose run code overflowed.
 //   relabel  a wave takes 64 consecutive runs: run_region[i] = run_region[parent[i]]; the row of a run by binary search in row_start; the
@@ -27,9 +27,7 @@
 //            first (a background region holds hundreds of runs): the lanes of the first region still open are balloted, their values reduced,
 //            and the first of them issues the 7 atomics.  Integers throughout: two runs of the program are bit-equal.
 // A frame with row_start[n][H] > cap is skipped by every kernel (decided on the device, from row_start alone).
-#include "arseg_device.h"
-
-#include <limits.h>
+#include "runcode.h"
 
 namespace {
 
@@ -49,11 +47,7 @@ struct RegP {
 };
 
 // The stored runs of a frame: row_start[n][H], never below 0; -1 for a frame whose run code overflowed.  At most cap either way.
-__device__ __forceinline__ int reg_total(const RegP &p, const int *rs) {
-    const int need = rs[p.H];
-    return need > p.cap ? -1 : max(need, 0);
-}
-__device__ __forceinline__ int reg_clamp(int v, int lo, int hi) { return min(max(v, lo), hi); }
+__device__ __forceinline__ int reg_total(const RegP &p, const int *rs) { return rc_stored(rs[p.H], p.cap); }
 
 __device__ __forceinline__ int reg_load(const int *q) { return __hip_atomic_load(q, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT); }
 
@@ -96,19 +90,15 @@ __global__ __launch_bounds__(64 * REG_WAVES) void regions_link_kernel(const RegP
         int *par = p.par + (size_t)n * p.cap_stride;
         for (int y = 1 + blockIdx.x * REG_WAVES + wave; y < p.H; y += gridDim.x * REG_WAVES) {
             // a malformed row_start may not lead outside [0, total): both rows are clamped into it
-            const int pf = reg_clamp(rs[y - 1], 0, total), first = reg_clamp(rs[y], 0, total);
-            const int pl = max(first, pf), last = reg_clamp(rs[y + 1], first, total);
+            int pf, pl, first, last;
+            rc_row(rs, y - 1, total, pf, pl);
+            rc_row(rs, y, total, first, last);
             if (pl <= pf) continue;
             for (int i = first + lane; i < last; i += 64) {
                 const unsigned word = runs[i];
-                const int a0 = min((int)(word >> 8), p.W), a1 = i + 1 < last ? min((int)(runs[i + 1] >> 8), p.W) : p.W;
-                // the first run j of row y - 1 with b1 + d > a0: b1 is the start of run j + 1, or W behind the row's last run
-                int lo = pf + 1, hi = pl;
-                while (lo < hi) {
-                    const int mid = (lo + hi) >> 1;
-                    if ((int)(runs[mid] >> 8) > a0 - p.d) hi = mid; else lo = mid + 1;
-                }
-                for (int j = lo - 1; j < pl; ++j) {
+                const int a0 = rc_x0(runs, i, p.W), a1 = rc_x1(runs, i, last, p.W);
+                // from the first run j of row y - 1 with b1 + d > a0 on: b1 is the start of run j + 1, or W behind the row's last run
+                for (int j = rc_cover(runs, pf, pl, a0 - p.d); j < pl; ++j) {
                     const unsigned other = runs[j];
                     if ((int)(other >> 8) >= a1 + p.d) break;              // b0 < a1 + d ends here: the row is sorted
                     if (((other ^ word) & 0xffu) == 0) reg_unite(par, i, j);
@@ -136,7 +126,6 @@ __global__ __launch_bounds__(64 * REG_WAVES) void regions_flatten_kernel(const R
 
 __global__ __launch_bounds__(256) void regions_number_kernel(const RegP p) {
     __shared__ int part[4];
-    const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
     for (int n = blockIdx.x; n < p.N; n += gridDim.x) {
         const int total = reg_total(p, p.rs + (size_t)n * (p.H + 1));
         if (total < 0) {
@@ -151,19 +140,9 @@ __global__ __launch_bounds__(256) void regions_number_kernel(const RegP p) {
             const int i = i0 + (int)threadIdx.x;
             const bool root = i < total && par[i] == i;
             int inc = root ? 1 : 0;
-#pragma unroll
-            for (int o = 1; o < 64; o <<= 1) {
-                const int t = __shfl_up(inc, o, 64);
-                inc += lane >= o ? t : 0;
-            }
-            if (lane == 63) part[wave] = inc;
-            __syncthreads();
-            int before = carry;
-#pragma unroll
-            for (int k = 0; k < 4; ++k) before += k < wave ? part[k] : 0;
-            carry += part[0] + part[1] + part[2] + part[3];
+            rc_block_scan<1>(&inc, &carry, part);
             if (root) {
-                const int k = before + inc - 1;
+                const int k = inc - 1;
                 rr[i] = k;
                 if (k < p.rcap) {
                     long long *row = p.reg + ((size_t)n * p.rcap_stride + k) * 8;
@@ -173,7 +152,6 @@ __global__ __launch_bounds__(256) void regions_number_kernel(const RegP p) {
                     row[6] = 0; row[7] = 0;
                 }
             }
-            __syncthreads();
         }
         if (threadIdx.x == 0) p.nreg[n] = carry;
     }
@@ -202,8 +180,7 @@ __global__ __launch_bounds__(64 * REG_WAVES) void regions_relabel_kernel(const R
                         const int mid = (y + top + 1) >> 1;
                         if (rs[mid] <= i) y = mid; else top = mid - 1;
                     }
-                    const int a0 = min((int)(runs[i] >> 8), p.W);
-                    const int a1 = i + 1 < min(rs[y + 1], total) ? reg_clamp((int)(runs[i + 1] >> 8), a0, p.W) : p.W;
+                    const int a0 = rc_x0(runs, i, p.W), a1 = rc_x1(runs, i, min(rs[y + 1], total), p.W);
                     const long long len = a1 - a0;
                     area = len; sx = (long long)(a0 + a1 - 1) * len / 2; sy = (long long)y * len;
                     x_lo = a0; x_hi = a1 - 1; y_lo = y_hi = y;
@@ -241,13 +218,6 @@ __global__ __launch_bounds__(64 * REG_WAVES) void regions_relabel_kernel(const R
     }
 }
 
-// workgroups per frame x frames for `items` items of work a workgroup takes `per` of, capped for the grid-stride loops
-dim3 reg_grid(int N, long long items, int per) {
-    const int gy = N < 65535 ? N : 65535;
-    const long long share = 16384 / gy > 0 ? 16384 / gy : 1, need = (items + per - 1) / per;
-    return dim3((unsigned)(need < share ? (need > 0 ? need : 1) : share), (unsigned)gy);
-}
-
 }  // namespace
 
 extern "C" size_t arseg_rle_regions_workspace_bytes(int N, int64_t cap) {
@@ -263,24 +233,21 @@ extern "C" int arseg_rle_regions_fwd(const int32_t *row_start, const uint32_t *r
     if (cap <= 0 || rcap < 0 || (regions == nullptr && rcap > 0)) return ARSEG_EINVAL;
     if (connectivity != 4 && connectivity != 8) return ARSEG_EINVAL;
     if (W > (1 << 24) || (int64_t)H * W > (int64_t)INT32_MAX) return ARSEG_EINVAL;
-    if (((reinterpret_cast<uintptr_t>(row_start) | reinterpret_cast<uintptr_t>(runs) | reinterpret_cast<uintptr_t>(n_regions) |
-          reinterpret_cast<uintptr_t>(run_region) | reinterpret_cast<uintptr_t>(workspace)) & 3u) || (reinterpret_cast<uintptr_t>(regions) & 7u))
-        return ARSEG_EINVAL;
+    if (rc_misaligned(4, row_start, runs, n_regions, run_region, workspace) || rc_misaligned(8, regions)) return ARSEG_EINVAL;
     if (workspace_bytes < arseg_rle_regions_workspace_bytes(N, cap)) return ARSEG_EWORKSPACE;
     ARSEG_CHECK_PTR(workspace);
     RegP p = {};
     p.rs = row_start; p.runs = runs; p.par = static_cast<int *>(workspace); p.rr = run_region;
     p.reg = regions ? reinterpret_cast<long long *>(regions) : nullptr; p.nreg = n_regions;
     p.cap_stride = cap; p.rcap_stride = regions ? rcap : 0;
-    p.cap = (int)(cap < (int64_t)INT32_MAX ? cap : (int64_t)INT32_MAX);
-    p.rcap = regions ? (int)(rcap < (int64_t)INT32_MAX ? rcap : (int64_t)INT32_MAX) : 0;
+    p.cap = rc_cap(cap); p.rcap = regions ? rc_cap(rcap) : 0;
     p.N = N; p.H = H; p.W = W; p.d = connectivity == 8 ? 1 : 0;
     hipStream_t st = arseg_stream(stream);
-    const dim3 per_run = reg_grid(N, p.cap, 64 * REG_WAVES), per_row = reg_grid(N, H, REG_WAVES), block(64 * REG_WAVES);
+    const dim3 per_run = rc_grid(N, p.cap, 64 * REG_WAVES, 16384), per_row = rc_grid(N, H, REG_WAVES, 16384), block(64 * REG_WAVES);
     hipLaunchKernelGGL(regions_init_kernel, per_run, block, 0, st, p);
     if (H > 1) hipLaunchKernelGGL(regions_link_kernel, per_row, block, 0, st, p);
     hipLaunchKernelGGL(regions_flatten_kernel, per_run, block, 0, st, p);
-    hipLaunchKernelGGL(regions_number_kernel, dim3((unsigned)(N < 65535 ? N : 65535)), dim3(256), 0, st, p);
+    hipLaunchKernelGGL(regions_number_kernel, rc_frames(N), dim3(256), 0, st, p);
     hipLaunchKernelGGL(regions_relabel_kernel, per_run, block, 0, st, p);
     return arseg_launch_status();
 }

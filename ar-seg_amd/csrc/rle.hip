@@ -14,7 +14,7 @@
 //          base, which begins at row_start[n][y]; a lane writes the words of its piece whose index is < cap.
 // Decoder: a wave per row; a lane takes the runs row_start[n][y] + lane, + 64, ..., reads its word and the next one of the same row (or W) and
 // fills [x_first, x_next): bytes up to a 4-byte boundary, dwords up to a 16-byte boundary, 16-byte stores, dwords, bytes.
-#include "arseg_device.h"
+#include "runcode.h"
 
 namespace {
 
@@ -125,26 +125,14 @@ __global__ __launch_bounds__(64 * RLE_WAVES) void rle_encode_kernel(const RleP p
 // row_start[n][1 .. H]: counts -> their inclusive prefix, in place; row_start[n][0] = 0
 __global__ __launch_bounds__(256) void rle_scan_kernel(const RleP p) {
     __shared__ int part[4];
-    const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
     for (int n = blockIdx.x; n < p.N; n += gridDim.x) {
         int *rs = p.rs + (size_t)n * (p.H + 1);
         int carry = 0;
         for (int i0 = 1; i0 <= p.H; i0 += 256) {
             const int i = i0 + (int)threadIdx.x;
             int inc = i <= p.H ? rs[i] : 0;
-#pragma unroll
-            for (int o = 1; o < 64; o <<= 1) {
-                const int t = __shfl_up(inc, o, 64);
-                inc += lane >= o ? t : 0;
-            }
-            if (lane == 63) part[wave] = inc;
-            __syncthreads();
-            int before = carry;
-#pragma unroll
-            for (int k = 0; k < 4; ++k) before += k < wave ? part[k] : 0;
-            carry += part[0] + part[1] + part[2] + part[3];
-            if (i <= p.H) rs[i] = before + inc;
-            __syncthreads();
+            rc_block_scan<1>(&inc, &carry, part);
+            if (i <= p.H) rs[i] = inc;
         }
         if (threadIdx.x == 0) rs[0] = 0;
     }
@@ -171,7 +159,7 @@ __global__ __launch_bounds__(64 * RLE_WAVES) void rle_decode_kernel(const RleP p
             const int stored = min(last, p.cap);
             for (int i = first + lane; i < stored; i += 64) {
                 const unsigned word = runs[i];
-                const int xa = min((int)(word >> 8), p.W);
+                const int xa = rc_x0(runs, i, p.W);
                 // the run ends where the next one of its row begins, or at W; a stored run whose successor in the row was cut off by cap
                 // is known to hold its first pixel only
                 const int xb = i + 1 >= last ? p.W : (i + 1 < p.cap ? (int)(runs[i + 1] >> 8) : xa + 1);
@@ -182,26 +170,19 @@ __global__ __launch_bounds__(64 * RLE_WAVES) void rle_decode_kernel(const RleP p
     }
 }
 
-// rows / RLE_WAVES workgroups per frame x frames, capped for the grid-stride loops
-dim3 rle_grid(int N, int H) {
-    const int gy = N < 65535 ? N : 65535;
-    const long long share = 16384 / gy > 0 ? 16384 / gy : 1, need = ((long long)H + RLE_WAVES - 1) / RLE_WAVES;
-    return dim3((unsigned)(need < share ? need : share), (unsigned)gy);
-}
-
 // what the two entry points share: the plane, row_start, runs and cap
 int rle_common(RleP &p, const void *plane, int64_t pitch, int64_t image_stride, int N, int H, int W, const int32_t *row_start, const uint32_t *runs,
                int64_t cap) {
     ARSEG_CHECK_PTR(plane); ARSEG_CHECK_PTR(row_start);
     ARSEG_CHECK_POS(N); ARSEG_CHECK_POS(H); ARSEG_CHECK_POS(W);
-    if ((reinterpret_cast<uintptr_t>(row_start) & 3u) || (reinterpret_cast<uintptr_t>(runs) & 3u)) return ARSEG_EINVAL;
+    if (rc_misaligned(4, row_start, runs)) return ARSEG_EINVAL;
     if (runs && cap < 0) return ARSEG_EINVAL;
     if (pitch < (int64_t)W || image_stride < 0) return ARSEG_EINVAL;
     if (W > (1 << 24) || (int64_t)H * W > (int64_t)INT32_MAX) return ARSEG_EINVAL;
     p.rs = const_cast<int *>(row_start); p.runs = const_cast<unsigned *>(runs);
     p.pitch = pitch; p.ns = image_stride;
     p.cap_stride = runs ? cap : 0;
-    p.cap = runs ? (int)(cap < (int64_t)INT32_MAX ? cap : (int64_t)INT32_MAX) : 0;
+    p.cap = runs ? rc_cap(cap) : 0;
     p.N = N; p.H = H; p.W = W;
     return ARSEG_OK;
 }
@@ -215,9 +196,9 @@ extern "C" int arseg_labels_rle_fwd(const uint8_t *labels, int64_t pitch, int64_
     if (rc != ARSEG_OK) return rc;
     p.lab = labels;
     hipStream_t st = arseg_stream(stream);
-    const dim3 g = rle_grid(N, H);
+    const dim3 g = rc_grid(N, H, RLE_WAVES, 16384);
     hipLaunchKernelGGL((rle_encode_kernel<false>), g, dim3(64 * RLE_WAVES), 0, st, p);
-    hipLaunchKernelGGL(rle_scan_kernel, dim3((unsigned)(N < 65535 ? N : 65535)), dim3(256), 0, st, p);
+    hipLaunchKernelGGL(rle_scan_kernel, rc_frames(N), dim3(256), 0, st, p);
     if (runs && p.cap > 0) hipLaunchKernelGGL((rle_encode_kernel<true>), g, dim3(64 * RLE_WAVES), 0, st, p);
     return arseg_launch_status();
 }
@@ -230,6 +211,6 @@ extern "C" int arseg_rle_decode_fwd(const int32_t *row_start, const uint32_t *ru
     if (rc != ARSEG_OK) return rc;
     p.out = labels_out;
     if (p.cap == 0) return ARSEG_OK;          // no run is stored: every pixel stays
-    hipLaunchKernelGGL(rle_decode_kernel, rle_grid(N, H), dim3(64 * RLE_WAVES), 0, arseg_stream(stream), p);
+    hipLaunchKernelGGL(rle_decode_kernel, rc_grid(N, H, RLE_WAVES, 16384), dim3(64 * RLE_WAVES), 0, arseg_stream(stream), p);
     return arseg_launch_status();
 }

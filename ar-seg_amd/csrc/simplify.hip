@@ -16,7 +16,7 @@
 //            launch zeroed: program order alone makes the flags visible, no fence is needed.  A loop of at most SP_STAGE = 2048 vertices
 //            is first copied into the wave's own LDS with its flags, walked there and its flags copied out: a round then waits for
 //            LDS, not for L2.  Longer loops are walked in place.  The kept count after the fewer-than-3 rule.
-//   scan     one workgroup per frame: rle.hip's prefix with a carry over the loops' kept counts -> counts_out and the loop records.
+//   scan     one workgroup per frame: the prefix with a carry (rc_block_scan) over the loops' kept counts -> counts_out and the loop records.
 //   emit     a wave owns a loop: the kept vertices (all of them for a loop kept whole) compacted in order with a ballot prefix to first';
 //            words below vcap_out only.  Not launched without verts_out.
 //
@@ -31,7 +31,7 @@
 // it was found in; an output index is used only below vcap_out, a loop index only below L <= lcap.  Coordinates are taken as 16-bit
 // fields and multiplied as unsigned words: a malformed vertex gives a meaningless product, never a trap.  No division is made.  A
 // malformed loop record gives meaningless output and touches nothing outside the caller's buffers.
-#include "arseg_device.h"
+#include "runcode.h"
 
 namespace {
 
@@ -56,8 +56,6 @@ struct SpP {
     int N;
 };
 
-__device__ __forceinline__ int sp_clamp(int v, int lo, int hi) { return min(max(v, lo), hi); }
-
 // The loops and vertices of a frame; false for a frame that is refused: its source was refused or overflowed.
 __device__ __forceinline__ bool sp_frame(const SpP &p, int n, int &L, int &V) {
     L = p.counts[2 * (size_t)n]; V = p.counts[2 * (size_t)n + 1];
@@ -67,8 +65,8 @@ __device__ __forceinline__ bool sp_frame(const SpP &p, int n, int &L, int &V) {
 // A loop's record -> its first vertex and its count, clamped into the frame's V vertices.
 __device__ __forceinline__ void sp_loop(const SpP &p, int n, int l, int V, int &first, int &cnt) {
     const int *rec = p.loops + ((size_t)n * p.lcap + l) * 4;
-    first = sp_clamp(rec[1], 0, V);
-    cnt = sp_clamp(rec[2], 0, V - first);
+    first = rc_clamp(rec[1], 0, V);
+    cnt = rc_clamp(rec[2], 0, V - first);
 }
 
 template <int CTRL>
@@ -142,7 +140,7 @@ __device__ __forceinline__ int sp_walk(const unsigned *P, unsigned char *F, int 
         }
     }
     key = sp_wave_max(key);                                                  // (lane 0 holds position 0: the key is never empty)
-    const int a1 = sp_clamp(sp_key_pos(key), 0, cnt - 1);
+    const int a1 = rc_clamp(sp_key_pos(key), 0, cnt - 1);
     F[0] = 1; F[a1] = 1;                                                      // every lane stores: see the head of the file
     int kept = a1 > 0 ? 2 : 1;
     // ---- the walk: a is final, b the next kept position after it (cnt stands for the closing P[0])
@@ -168,7 +166,7 @@ __device__ __forceinline__ int sp_walk(const unsigned *P, unsigned char *F, int 
             key = sp_wave_max(key);
             const unsigned long long c = key >> 32, len2 = (unsigned long long)(ex * ex + ey * ey);
             if (16ull * c * c > tol * len2) {                                // uniform: the one 64-bit comparison of the segment
-                const int i = sp_clamp(sp_key_pos(key), a + 1, b - 1);
+                const int i = rc_clamp(sp_key_pos(key), a + 1, b - 1);
                 F[i] = 1;
                 ++kept; b = i; marked = true;
             }
@@ -222,10 +220,9 @@ __global__ __launch_bounds__(64 * SP_WAVES) void simplify_keep_kernel(const SpP 
     }
 }
 
-// Per frame: the kept counts summed over the loops, 256 at a time with a carry (rle_scan_kernel's scheme) -> the loop records and counts_out.
+// Per frame: the kept counts summed over the loops, 256 at a time with a carry (rc_block_scan) -> the loop records and counts_out.
 __global__ __launch_bounds__(256) void simplify_scan_kernel(const SpP p) {
     __shared__ unsigned part[4];
-    const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
     for (int n = blockIdx.x; n < p.N; n += gridDim.x) {
         int L, V;
         if (!sp_frame(p, n, L, V)) continue;
@@ -234,22 +231,11 @@ __global__ __launch_bounds__(256) void simplify_scan_kernel(const SpP p) {
             const int l = l0 + (int)threadIdx.x;
             const unsigned count = l < L ? (unsigned)p.kept[(size_t)n * p.lcap + l] : 0u;
             unsigned inc = count;
-#pragma unroll
-            for (int o = 1; o < 64; o <<= 1) {
-                const unsigned t = __shfl_up(inc, o, 64);
-                inc += lane >= o ? t : 0u;
-            }
-            if (lane == 63) part[wave] = inc;
-            __syncthreads();
-            unsigned before = carry;
-#pragma unroll
-            for (int k = 0; k < 4; ++k) before += k < wave ? part[k] : 0u;
-            carry += part[0] + part[1] + part[2] + part[3];
+            rc_block_scan<1>(&inc, &carry, part);
             if (l < L) {
                 const sp_i32x4 rec = *reinterpret_cast<const sp_i32x4 *>(p.loops + ((size_t)n * p.lcap + l) * 4);
-                *reinterpret_cast<sp_i32x4 *>(p.loops_out + ((size_t)n * p.lcap + l) * 4) = sp_i32x4{rec.x, (int)(before + inc - count), (int)count, rec.w};
+                *reinterpret_cast<sp_i32x4 *>(p.loops_out + ((size_t)n * p.lcap + l) * 4) = sp_i32x4{rec.x, (int)(inc - count), (int)count, rec.w};
             }
-            __syncthreads();
         }
         if (threadIdx.x == 0) { p.counts_out[2 * (size_t)n] = L; p.counts_out[2 * (size_t)n + 1] = (int)carry; }
     }
@@ -280,13 +266,6 @@ __global__ __launch_bounds__(64 * SP_WAVES) void simplify_emit_kernel(const SpP 
     }
 }
 
-// workgroups per frame x frames for `items` items of work a workgroup takes `per` of, capped for the grid-stride loops
-dim3 sp_grid(int N, long long items, int per) {
-    const int gy = N < 65535 ? N : 65535;
-    const long long share = 4096 / gy > 0 ? 4096 / gy : 1, need = (items + per - 1) / per;
-    return dim3((unsigned)(need < share ? (need > 0 ? need : 1) : share), (unsigned)gy);
-}
-
 long long sp_flag_stride(int64_t vcap) { return (long long)((vcap + 3) & ~(int64_t)3); }
 
 }  // namespace
@@ -312,10 +291,7 @@ extern "C" int arseg_contours_simplify_fwd(const int32_t *counts, const int32_t 
         (verts_out == nullptr && vcap_out > 0))
         return ARSEG_EINVAL;
     if (H > 16384 || W > 16384 || tol2_q < 0 || tol2_q > ((int64_t)1 << 30)) return ARSEG_EINVAL;
-    if ((reinterpret_cast<uintptr_t>(counts) | reinterpret_cast<uintptr_t>(loops) | reinterpret_cast<uintptr_t>(verts) |
-         reinterpret_cast<uintptr_t>(counts_out) | reinterpret_cast<uintptr_t>(loops_out) | reinterpret_cast<uintptr_t>(verts_out) |
-         reinterpret_cast<uintptr_t>(workspace)) & 3u)
-        return ARSEG_EINVAL;
+    if (rc_misaligned(4, counts, loops, verts, counts_out, loops_out, verts_out, workspace)) return ARSEG_EINVAL;
     if ((verts != nullptr && verts_out == verts) || (loops != nullptr && loops_out == loops) || counts_out == counts) return ARSEG_EINVAL;
     const size_t need = arseg_contours_simplify_workspace_bytes(N, lcap, vcap);
     if (need == ~(size_t)0 || workspace_bytes < need) return ARSEG_EWORKSPACE;
@@ -328,10 +304,10 @@ extern "C" int arseg_contours_simplify_fwd(const int32_t *counts, const int32_t 
     p.flags = reinterpret_cast<unsigned char *>(p.kept + (size_t)N * (size_t)lcap);
     p.tol = (unsigned long long)tol2_q; p.N = N;
     hipStream_t st = arseg_stream(stream);
-    const dim3 per_loop = sp_grid(N, lcap, SP_WAVES);
-    hipLaunchKernelGGL(simplify_clear_kernel, sp_grid(N, p.fstride / 4, 256), dim3(256), 0, st, p);
+    const dim3 per_loop = rc_grid(N, lcap, SP_WAVES, 4096);
+    hipLaunchKernelGGL(simplify_clear_kernel, rc_grid(N, p.fstride / 4, 256, 4096), dim3(256), 0, st, p);
     hipLaunchKernelGGL(simplify_keep_kernel, per_loop, dim3(64 * SP_WAVES), 0, st, p);
-    hipLaunchKernelGGL(simplify_scan_kernel, dim3((unsigned)(N < 65535 ? N : 65535)), dim3(256), 0, st, p);
+    hipLaunchKernelGGL(simplify_scan_kernel, rc_frames(N), dim3(256), 0, st, p);
     if (p.vcap_out > 0) hipLaunchKernelGGL(simplify_emit_kernel, per_loop, dim3(64 * SP_WAVES), 0, st, p);          // not in a sizing pass
     return arseg_launch_status();
 }

@@ -87,6 +87,11 @@ def _check_logits(logits):
     return logits.contiguous()
 
 
+def _plane_if_true(x, N, H, W, device):
+    """True -> a fresh uint8 [N,H,W] plane on ``device``; the caller's buffer or None stays what it is."""
+    return torch.empty((N, int(H), int(W)), dtype=torch.uint8, device=device) if x is True else x
+
+
 def labels8(logits, H, W, lut=None, out=None, align_corners=True) -> torch.Tensor:
     """Head logits [N,n_cls,h,w] -> uint8 labels [N,H,W]: ``ops.argmax_confusion``'s pred (same resize, same argmax), as bytes, through
     ``lut`` (n_cls integers 0..255, e.g. train id -> label id; a list or an array) when given.  ``out``: the caller's buffer (nothing is allocated then)."""
@@ -116,8 +121,7 @@ def overlay(logits, frames, palette, out=None, labels_out=None, lut=None, align_
         out = frames._with([torch.empty(p.shape, dtype=p.dtype, device=p.device) for p in frames.planes])
     elif not isinstance(out, ingest.DecodedFrames) or out.src_format != frames.src_format or out.shape != frames.shape:
         raise ValueError("overlay: out must be DecodedFrames of the source's format and size")
-    if labels_out is True:
-        labels_out = torch.empty((frames.N, frames.H, frames.W), dtype=torch.uint8, device=logits.device)
+    labels_out = _plane_if_true(labels_out, frames.N, frames.H, frames.W, logits.device)
     ops.segment_egress(logits, frames.H, frames.W, align_corners=align_corners, lut=lut, labels_out=labels_out, src=frames, dst=out,
                        palette=palette.codes(frames.src_format, frames.colour)[:n_cls], weights=palette.weights[:n_cls])
     if out is not frames and (out.colour, out.mean, out.std) != (frames.colour, frames.mean, frames.std):
@@ -138,10 +142,8 @@ def confidence(logits, H, W, kind="top1", low=128, out=None, labels_out=None, lu
     of it.  Everything is included in the one launch; with ``out``, ``labels_out`` and ``stats`` given nothing is allocated."""
     logits = _check_logits(logits)
     N = logits.shape[0]
-    if out is None:
-        out = torch.empty((N, int(H), int(W)), dtype=torch.uint8, device=logits.device)
-    if labels_out is True:
-        labels_out = torch.empty((N, int(H), int(W)), dtype=torch.uint8, device=logits.device)
+    out = _plane_if_true(True if out is None else out, N, H, W, logits.device)
+    labels_out = _plane_if_true(labels_out, N, H, W, logits.device)
     if stats is True:
         stats = torch.zeros((N, _lib.CONF_NSTATS), dtype=torch.int64, device=logits.device)
     ops.segment_confidence(logits, H, W, kind=kind, low=low, align_corners=align_corners, lut=lut, conf_out=out, labels_out=labels_out, stats=stats)
@@ -201,10 +203,8 @@ def consistency(logits, ref_labels, mv_q, H, W, change_out=None, labels_out=None
     logits = _check_logits(logits)
     N = logits.shape[0]
     ref_labels = _ref_planes(ref_labels, N)
-    if change_out is True:
-        change_out = torch.empty((N, int(H), int(W)), dtype=torch.uint8, device=logits.device)
-    if labels_out is True:
-        labels_out = torch.empty((N, int(H), int(W)), dtype=torch.uint8, device=logits.device)
+    change_out = _plane_if_true(change_out, N, H, W, logits.device)
+    labels_out = _plane_if_true(labels_out, N, H, W, logits.device)
     if stats is True:
         stats = torch.zeros((N, _lib.TC_NSTATS), dtype=torch.int64, device=logits.device)
     ops.segment_consistency(logits, ref_labels, mv_q, H, W, align_corners=align_corners, lut=lut, labels_out=labels_out, change_out=change_out,
@@ -220,8 +220,7 @@ def consistency_of_planes(labels, ref_labels, mv_q, n_cls, change_out=None, stat
         raise ValueError("expected the label planes as a uint8 tensor [N,H,W]")
     N, H, W = labels.shape
     ref_labels = _ref_planes(ref_labels, N)
-    if change_out is True:
-        change_out = torch.empty((N, H, W), dtype=torch.uint8, device=labels.device)
+    change_out = _plane_if_true(change_out, N, H, W, labels.device)
     if stats is True:
         stats = torch.zeros((N, _lib.TC_NSTATS), dtype=torch.int64, device=labels.device)
     ops.labels_consistency(labels, ref_labels, mv_q, n_cls, change_out=change_out, stats=stats)
@@ -353,21 +352,39 @@ def rle(logits, H, W, capacity, lut=None, labels_out=None, out=None, align_corne
     return frames
 
 
-def rle_decode_numpy(row_start, runs, H, W) -> np.ndarray:
-    """The receiving side without a GPU: one frame's ``row_start`` [H+1] and ``runs`` [>= row_start[H]] (as ``RleFrames.to_host`` returns
-    them) -> the uint8 plane [H,W]."""
-    H, W = int(H), int(W)
+def _parse_runs(what, row_start, runs, H, W):
+    """One frame's run code, checked -> ``rs`` int64 [H+1] and, per counted run, ``x0``, ``x1`` (its columns [x0, x1)), ``val`` and ``row``,
+    int64 each.  THE host-side definition of the format: a run ends where the next one of its row begins, or at W."""
     rs = np.asarray(row_start).astype(np.int64)
     words = np.asarray(runs).astype(np.int64) & 0xFFFFFFFF
     if rs.shape != (H + 1,) or rs[0] != 0 or (np.diff(rs) < 1).any() or words.ndim != 1 or len(words) < rs[H]:
-        raise ValueError(f"rle_decode_numpy: expected row_start [{H + 1}], rising from 0 by at least one run per row, and the row_start[{H}] runs it counts")
+        raise ValueError(f"{what}: expected row_start [{H + 1}], rising from 0 by at least one run per row, and the row_start[{H}] runs it counts")
     words = words[:rs[H]]
     x0 = words >> 8
     x1 = np.append(x0[1:], W)
     x1[rs[1:] - 1] = W                                # the last run of a row ends at W
     if (x0[rs[:-1]] != 0).any() or (x1 <= x0).any() or (x1 > W).any():
-        raise ValueError("rle_decode_numpy: the runs of a row do not start at 0 and increase below W")
-    return np.repeat((words & 0xFF).astype(np.uint8), x1 - x0).reshape(H, W)
+        raise ValueError(f"{what}: the runs of a row do not start at 0 and increase below W")
+    return rs, x0, x1, words & 0xFF, np.repeat(np.arange(H, dtype=np.int64), np.diff(rs))
+
+
+def _runs_above(row, x0, x1, W, d):
+    """The pairs (u, v) of a run u and a run v of the row above that overlaps it, or with ``d`` = 1 touches it across a corner: two searches
+    over the whole frame, on keys that order (row, x) globally so that a search for a column of row y - 1 cannot leave that row."""
+    K = W + 2
+    cur = np.flatnonzero(row > 0)
+    first = np.searchsorted(row * K + x1, (row[cur] - 1) * K + x0[cur] - d, side="right")           # the first run above with b1 + d > a0
+    last = np.searchsorted(row * K + x0, (row[cur] - 1) * K + x1[cur] + d, side="left") - 1          # the last run above with b0 < a1 + d
+    count = last - first + 1
+    return np.repeat(cur, count), np.repeat(first, count) + np.arange(count.sum()) - np.repeat(np.cumsum(count) - count, count)
+
+
+def rle_decode_numpy(row_start, runs, H, W) -> np.ndarray:
+    """The receiving side without a GPU: one frame's ``row_start`` [H+1] and ``runs`` [>= row_start[H]] (as ``RleFrames.to_host`` returns
+    them) -> the uint8 plane [H,W]."""
+    H, W = int(H), int(W)
+    _, x0, x1, val, _ = _parse_runs("rle_decode_numpy", row_start, runs, H, W)
+    return np.repeat(val.astype(np.uint8), x1 - x0).reshape(H, W)
 
 
 REGION_DTYPE = np.dtype([("value", np.int64), ("area", np.int64), ("x_min", np.int64), ("y_min", np.int64), ("x_max", np.int64),
@@ -470,30 +487,18 @@ def regions_numpy(row_start, runs, H, W, connectivity=8, return_run_region=False
     H, W = int(H), int(W)
     if connectivity not in (4, 8):
         raise ValueError(f"regions_numpy: connectivity is 4 or 8, got {connectivity!r}")
-    d = 1 if connectivity == 8 else 0
-    rs = np.asarray(row_start).astype(np.int64)
-    words = np.asarray(runs).astype(np.int64) & 0xFFFFFFFF
-    if rs.shape != (H + 1,) or rs[0] != 0 or (np.diff(rs) < 1).any() or words.ndim != 1 or len(words) < rs[H]:
-        raise ValueError(f"regions_numpy: expected row_start [{H + 1}], rising from 0 by at least one run per row, and the row_start[{H}] runs it counts")
-    words = words[:rs[H]]
-    n = len(words)
-    x0, val = words >> 8, words & 0xFF
-    x1 = np.append(x0[1:], W)
-    x1[rs[1:] - 1] = W
-    if (x0[rs[:-1]] != 0).any() or (x1 <= x0).any() or (x1 > W).any():
-        raise ValueError("regions_numpy: the runs of a row do not start at 0 and increase below W")
-    row = np.repeat(np.arange(H, dtype=np.int64), np.diff(rs))
-    # keys that order (row, x) globally: a search for a column of row y - 1 cannot leave that row
-    K = W + 2
-    cur = np.flatnonzero(row > 0)
-    first = np.searchsorted(row * K + x1, (row[cur] - 1) * K + x0[cur] - d, side="right")           # the first run above with b1 + d > a0
-    last = np.searchsorted(row * K + x0, (row[cur] - 1) * K + x1[cur] + d, side="left") - 1          # the last run above with b0 < a1 + d
-    count = last - first + 1
-    u = np.repeat(cur, count)
-    v = np.repeat(first, count) + np.arange(count.sum()) - np.repeat(np.cumsum(count) - count, count)
+    _, x0, x1, val, row = _parse_runs("regions_numpy", row_start, runs, H, W)
+    rows, run_region = _regions_of(x0, x1, val, row, H, W, connectivity)
+    rec = _region_records(rows)
+    return (rec, run_region.astype(np.int32)) if return_run_region else rec
+
+
+def _regions_of(x0, x1, val, row, H, W, connectivity):
+    """The parsed runs of a frame -> (the int64 [R,8] rows of its regions, the region number of every run)."""
+    u, v = _runs_above(row, x0, x1, W, 1 if connectivity == 8 else 0)
     same = val[u] == val[v]
     u, v = u[same], v[same]
-    lab = np.arange(n, dtype=np.int64)
+    lab = np.arange(len(x0), dtype=np.int64)
     while True:
         m = np.minimum(lab[u], lab[v])
         nxt = lab.copy()
@@ -522,8 +527,7 @@ def regions_numpy(row_start, runs, H, W, connectivity=8, return_run_region=False
     np.maximum.at(rows[:, 5], run_region, row)
     np.add.at(rows[:, 6], run_region, (x0 + x1 - 1) * length // 2)
     np.add.at(rows[:, 7], run_region, row * length)
-    rec = _region_records(rows)
-    return (rec, run_region.astype(np.int32)) if return_run_region else rec
+    return rows, run_region
 
 
 LINK_DTYPE = np.dtype([(name, np.int64) for name in ("ref_region", "overlap", "same", "outside", "mutual", "n_ref")])
@@ -628,19 +632,12 @@ def links(cur: RegionFrames, ref: RegionFrames, mv_q=None, pair_capacity=None, o
 
 def _region_planes(what, row_start, runs, run_region, H, W):
     """One frame's run code and run_region -> (value plane, region-id plane), int64 [H,W] each, and the number of regions."""
-    rs = np.asarray(row_start).astype(np.int64)
-    words = np.asarray(runs).astype(np.int64) & 0xFFFFFFFF
+    rs, x0, x1, val, _ = _parse_runs(what, row_start, runs, H, W)
     rr = np.asarray(run_region).astype(np.int64)
-    if rs.shape != (H + 1,) or rs[0] != 0 or (np.diff(rs) < 1).any() or words.ndim != 1 or len(words) < rs[H] or rr.ndim != 1 or len(rr) < rs[H]:
-        raise ValueError(f"{what}: expected row_start [{H + 1}], rising from 0 by at least one run per row, and the row_start[{H}] runs and "
-                         f"region numbers it counts")
-    words, rr = words[:rs[H]], rr[:rs[H]]
-    x0 = words >> 8
-    x1 = np.append(x0[1:], W)
-    x1[rs[1:] - 1] = W
-    if (x0[rs[:-1]] != 0).any() or (x1 <= x0).any() or (x1 > W).any() or (rr < 0).any():
-        raise ValueError(f"{what}: the runs of a row do not start at 0 and increase below W, or a region number is negative")
-    return np.repeat(words & 0xFF, x1 - x0).reshape(H, W), np.repeat(rr, x1 - x0).reshape(H, W), int(rr.max()) + 1
+    if rr.ndim != 1 or len(rr) < rs[H] or (rr[:rs[H]] < 0).any():
+        raise ValueError(f"{what}: expected the row_start[{H}] region numbers of the runs, none of them negative")
+    rr = rr[:rs[H]]
+    return np.repeat(val, x1 - x0).reshape(H, W), np.repeat(rr, x1 - x0).reshape(H, W), int(rr.max()) + 1
 
 
 def links_numpy(cur_row_start, cur_runs, cur_run_region, ref_row_start, ref_runs, ref_run_region, H, W, mv_q=None):
@@ -776,27 +773,17 @@ def absorb_numpy(row_start, runs, H, W, min_area, protect=None, connectivity=8):
     H, W, min_area = int(H), int(W), int(min_area)
     if min_area < 1:
         raise ValueError(f"absorb_numpy: min_area must be at least 1, got {min_area}")
-    rec, rr = regions_numpy(row_start, runs, H, W, connectivity, return_run_region=True)
-    rr = rr.astype(np.int64)
-    R = len(rec)
-    rs = np.asarray(row_start).astype(np.int64)
-    words = (np.asarray(runs).astype(np.int64) & 0xFFFFFFFF)[:rs[H]]
-    x0, val = words >> 8, words & 0xFF
-    x1 = np.append(x0[1:], W)
-    x1[rs[1:] - 1] = W
-    row = np.repeat(np.arange(H, dtype=np.int64), np.diff(rs))
+    if connectivity not in (4, 8):
+        raise ValueError(f"absorb_numpy: connectivity is 4 or 8, got {connectivity!r}")
+    _, x0, x1, val, row = _parse_runs("absorb_numpy", row_start, runs, H, W)
+    rows, rr = _regions_of(x0, x1, val, row, H, W, connectivity)
+    rec, R = _region_records(rows), len(rows)
     stable = rec["area"] >= min_area
     if protect is not None:
         stable |= ops.egress.protect_table(protect, "absorb_numpy")[rec["value"]]
     # neighbouring runs: (i, i + 1) of one row with one pixel pair; a run and the runs above it that overlap it, with the overlap's length
     left = np.flatnonzero(row[:-1] == row[1:])
-    K = W + 2
-    cur = np.flatnonzero(row > 0)
-    first = np.searchsorted(row * K + x1, (row[cur] - 1) * K + x0[cur], side="right")
-    last = np.searchsorted(row * K + x0, (row[cur] - 1) * K + x1[cur], side="left") - 1
-    count = last - first + 1
-    u = np.repeat(cur, count)
-    v = np.repeat(first, count) + np.arange(count.sum()) - np.repeat(np.cumsum(count) - count, count)
+    u, v = _runs_above(row, x0, x1, W, 0)
     a = np.concatenate([rr[left], rr[left + 1], rr[u], rr[v]])
     b = np.concatenate([rr[left + 1], rr[left], rr[v], rr[u]])
     w = np.concatenate([np.ones(2 * len(left), dtype=np.int64), np.tile(np.minimum(x1[u], x1[v]) - np.maximum(x0[u], x0[v]), 2)])
@@ -915,17 +902,13 @@ def contours_numpy(row_start, runs, H, W, connectivity=8):
     H, W = int(H), int(W)
     if H > 65535 or W > 65535:
         raise ValueError(f"contours_numpy: H and W at most 65535 (a vertex is y << 16 | x), got {H}x{W}")
-    _, rr = regions_numpy(row_start, runs, H, W, connectivity, return_run_region=True)
+    if connectivity not in (4, 8):
+        raise ValueError(f"contours_numpy: connectivity is 4 or 8, got {connectivity!r}")
+    rs, starts, x1, val, row = _parse_runs("contours_numpy", row_start, runs, H, W)
+    _, rr = _regions_of(starts, x1, val, row, H, W, connectivity)
     eight = connectivity == 8
-    rs = np.asarray(row_start).astype(np.int64)
-    words = (np.asarray(runs).astype(np.int64) & 0xFFFFFFFF)[:rs[H]]
-    n = len(words)
-    x0, val = (words >> 8).tolist(), (words & 0xFF).tolist()
-    x1 = np.append(words[1:] >> 8, W)
-    x1[rs[1:] - 1] = W
-    x1 = x1.tolist()
-    rs = rs.tolist()
-    starts = np.asarray(x0)
+    n = len(starts)
+    rs, x0, x1, val, row = rs.tolist(), starts.tolist(), x1.tolist(), val.tolist(), row.tolist()
     succ, end = [0] * (2 * n), [0] * (2 * n)                  # the edge after edge e = 2 * run + side, and the corner where it starts
 
     def cover(y, x):                                          # the run of row y that covers column x
@@ -974,7 +957,6 @@ def contours_numpy(row_start, runs, H, W, connectivity=8):
                 else:
                     succ[e], end[e] = west(i, y + 1, v, p, rs[y + 1])
     loops, verts, seen = [], [], [False] * (2 * n)
-    row = np.repeat(np.arange(H), np.diff(rs)).tolist()
     for lead in range(2 * n):                                 # the smallest edge of every cycle, in rising order
         if seen[lead]:
             continue

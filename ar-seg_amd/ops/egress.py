@@ -51,6 +51,62 @@ def _planes(frames, N, H, W, what):
     return fmt, out
 
 
+def _frame_dims(what, H, W, limit=None, positive=True):
+    """H and W as ints, or ValueError.  ``limit``: the most either may be (they share a vertex word); None: the run code's own limits, a column
+    in 24 bits and a pixel index in 31."""
+    H, W = int(H), int(W)
+    over = (W > 1 << 24 or H * W > 2 ** 31 - 1) if limit is None else (H > limit or W > limit)
+    if over or (positive and (H <= 0 or W <= 0)):
+        bounds = "W <= 2^24 and H * W < 2^31" if limit is None else f"H <= {limit} and W <= {limit}"
+        raise ValueError(f"{what}: H and W {'positive, ' if positive else ''}{bounds}, got {H}x{W}")
+    return H, W
+
+
+def _dense(what, name, t, dtype, shape, dev=None):
+    """``t`` is a contiguous, aligned ``dtype`` tensor of ``shape`` on ``dev`` (None: wherever it lies), or ArsegError.  A None entry of
+    ``shape`` stands for any size, and that size is returned: a capacity, or the number of frames.  ``dtype``: one dtype, or those allowed."""
+    if t is None:
+        raise ValueError(f"{what}: {name} is required")
+    kinds = dtype if isinstance(dtype, tuple) else (dtype,)
+    _need_gpu(t, dtype=None)
+    if t.dtype not in kinds:
+        raise _lib.ArsegError(f"{what}: {name} holds {' or '.join(str(k) for k in kinds)}, got {t.dtype}")
+    fits = t.dim() == len(shape) and all(want is None or have == want for have, want in zip(t.shape, shape))
+    if not fits or not t.is_contiguous() or (dev is not None and t.device != dev) or t.data_ptr() % t.element_size():
+        want = ", ".join("capacity" if s is None else str(s) for s in shape)
+        raise _lib.ArsegError(f"{what}: {name} must be a contiguous {kinds[0]} [{want}] tensor on {t.device if dev is None else dev}, got "
+                              f"{tuple(t.shape)} strides {t.stride()} on {t.device}")
+    return next((int(have) for have, want in zip(t.shape, shape) if want is None), None)
+
+
+def _out_plane(what, name, t, N, H, W, dev):
+    """An 8-bit plane ``t`` [N,H,W] on ``dev`` (rows contiguous, any pitch) -> (pitch, image stride); (0, 0) for None."""
+    if t is None:
+        return 0, 0
+    _need_gpu(t, dtype=torch.uint8)
+    if tuple(t.shape) != (N, H, W) or t.device != dev:
+        raise ValueError(f"{name} must be uint8 {(N, H, W)} on {dev}, got {tuple(t.shape)} on {t.device}")
+    return _plane_layout(t, (W,), f"{what} {name}")
+
+
+def _mv_field(what, mv_q, N, H, W, dev):
+    """The dense quarter-pel field: int16 [N,H,W,2], contiguous and 4-byte aligned (a vector is read as one word)."""
+    _need_gpu(mv_q, dtype=torch.int16)
+    if tuple(mv_q.shape) != (N, H, W, 2) or not mv_q.is_contiguous() or mv_q.device != dev or mv_q.data_ptr() % 4:
+        raise _lib.ArsegError(f"{what}: mv_q must be a contiguous, 4-byte aligned int16 {(N, H, W, 2)} tensor on {dev}, got {tuple(mv_q.shape)} "
+                              f"strides {mv_q.stride()} on {mv_q.device}")
+
+
+def _own_workspace(what, workspace, nbytes, dev, align=1):
+    """The caller's workspace after its check, or the stream's shared one -> (the tensor, its size in bytes)."""
+    if workspace is None:
+        workspace = _workspace(nbytes, dev)
+    elif not workspace.is_cuda or workspace.device != dev or not workspace.is_contiguous() or workspace.data_ptr() % align or \
+            workspace.numel() * workspace.element_size() < nbytes:
+        raise _lib.ArsegError(f"{what}: workspace must be a contiguous, {align}-byte aligned tensor of at least {nbytes} bytes on {dev}")
+    return workspace, workspace.numel() * workspace.element_size()
+
+
 def segment_egress(logits: torch.Tensor, H: int, W: int, *, align_corners: bool = True, lut=None, labels_out: Optional[torch.Tensor] = None,
                    src=None, dst=None, palette=None, weights=None):
     """Head logits fp32 [N,n_cls,h,w] -> the label plane ``labels_out`` (uint8 [N,H,W], rows contiguous, any row pitch / image stride; value
@@ -68,12 +124,7 @@ def segment_egress(logits: torch.Tensor, H: int, W: int, *, align_corners: bool 
         raise ValueError("segment_egress: nothing to write (labels_out and dst are both None)")
     if not 1 <= n_cls <= 32:
         raise ValueError(f"segment_egress: 1..32 classes, got {n_cls}")
-    lab_pitch = lab_ns = 0
-    if labels_out is not None:
-        _need_gpu(labels_out, dtype=torch.uint8)
-        if tuple(labels_out.shape) != (N, H, W) or labels_out.device != logits.device:
-            raise ValueError(f"labels_out must be uint8 {(N, H, W)} on {logits.device}, got {tuple(labels_out.shape)} on {labels_out.device}")
-        lab_pitch, lab_ns = _plane_layout(labels_out, (W,), "segment_egress labels_out")
+    lab_pitch, lab_ns = _out_plane("segment_egress", "labels_out", labels_out, N, H, W, logits.device)
     lut_c = None if lut is None else _host_u8(lut, n_cls, "lut")
     fmt, sp, dp, pal_c, wt_c = 0, [], [], None, None
     if dst is not None:
@@ -125,24 +176,15 @@ def segment_confidence(logits: torch.Tensor, H: int, W: int, *, kind: str = "top
     low = int(low)
     if not 0 <= low <= 256:
         raise ValueError(f"segment_confidence: low is a code threshold in 0..256, got {low}")
-    layout = {}
-    for name, t in (("conf_out", conf_out), ("labels_out", labels_out)):
-        layout[name] = (0, 0)
-        if t is not None:
-            _need_gpu(t, dtype=torch.uint8)
-            if tuple(t.shape) != (N, H, W) or t.device != logits.device:
-                raise ValueError(f"{name} must be uint8 {(N, H, W)} on {logits.device}, got {tuple(t.shape)} on {t.device}")
-            layout[name] = _plane_layout(t, (W,), f"segment_confidence {name}")
+    conf = _out_plane("segment_confidence", "conf_out", conf_out, N, H, W, logits.device)
+    lab = _out_plane("segment_confidence", "labels_out", labels_out, N, H, W, logits.device)
     if stats is not None:
-        _need_gpu(stats, dtype=torch.int64)
-        if tuple(stats.shape) != (N, _lib.CONF_NSTATS) or not stats.is_contiguous() or stats.device != logits.device:
-            raise _lib.ArsegError(f"stats must be a contiguous int64 {(N, _lib.CONF_NSTATS)} tensor on {logits.device}, got {tuple(stats.shape)} "
-                                  f"strides {stats.stride()} on {stats.device}")
+        _dense("segment_confidence", "stats", stats, torch.int64, (N, _lib.CONF_NSTATS), logits.device)
     lut_c = None if lut is None else _host_u8(lut, n_cls, "lut")
     planes = (conf_out is not None) + (labels_out is not None)
     launch("segment_confidence", _lib.load().arseg_segment_confidence_fwd, _ptr(logits), N, n_cls, h, w, H, W, 1 if align_corners else 0,
-           _CONF_KINDS[kind], low, lut_c, _ptr(conf_out), layout["conf_out"][0], layout["conf_out"][1], _ptr(labels_out), layout["labels_out"][0],
-           layout["labels_out"][1], _ptr(stats), _stream(), nbytes=logits.numel() * 4 + planes * N * H * W)
+           _CONF_KINDS[kind], low, lut_c, _ptr(conf_out), conf[0], conf[1], _ptr(labels_out), lab[0], lab[1], _ptr(stats), _stream(),
+           nbytes=logits.numel() * 4 + planes * N * H * W)
     return conf_out, labels_out, stats
 
 
@@ -157,21 +199,10 @@ def _tc_common(what, N, H, W, n_cls, device, ref_labels, mv_q, change_out, stats
     ref_pitch, ref_ns = _plane_layout(ref_labels, (W,), f"{what} ref_labels")
     if ref_labels.shape[0] == 1 and N > 1:
         ref_ns = 0                                        # one plane for all N frames
-    _need_gpu(mv_q, dtype=torch.int16)
-    if tuple(mv_q.shape) != (N, H, W, 2) or not mv_q.is_contiguous() or mv_q.device != device or mv_q.data_ptr() % 4:
-        raise _lib.ArsegError(f"mv_q must be a contiguous, 4-byte aligned int16 {(N, H, W, 2)} tensor on {device}, got {tuple(mv_q.shape)} "
-                              f"strides {mv_q.stride()} on {mv_q.device}")
-    chg = (0, 0)
-    if change_out is not None:
-        _need_gpu(change_out, dtype=torch.uint8)
-        if tuple(change_out.shape) != (N, H, W) or change_out.device != device:
-            raise ValueError(f"change_out must be uint8 {(N, H, W)} on {device}, got {tuple(change_out.shape)} on {change_out.device}")
-        chg = _plane_layout(change_out, (W,), f"{what} change_out")
+    _mv_field(what, mv_q, N, H, W, device)
+    chg = _out_plane(what, "change_out", change_out, N, H, W, device)
     if stats is not None:
-        _need_gpu(stats, dtype=torch.int64)
-        if tuple(stats.shape) != (N, _lib.TC_NSTATS) or not stats.is_contiguous() or stats.device != device:
-            raise _lib.ArsegError(f"stats must be a contiguous int64 {(N, _lib.TC_NSTATS)} tensor on {device}, got {tuple(stats.shape)} "
-                                  f"strides {stats.stride()} on {stats.device}")
+        _dense(what, "stats", stats, torch.int64, (N, _lib.TC_NSTATS), device)
     return ref_pitch, ref_ns, chg[0], chg[1]
 
 
@@ -194,12 +225,7 @@ def segment_consistency(logits: torch.Tensor, ref_labels: torch.Tensor, mv_q: to
     if labels_out is None and change_out is None and stats is None:
         raise ValueError("segment_consistency: nothing to write (labels_out, change_out and stats are all None)")
     ref_pitch, ref_ns, chg_pitch, chg_ns = _tc_common("segment_consistency", N, H, W, n_cls, logits.device, ref_labels, mv_q, change_out, stats)
-    lab_pitch = lab_ns = 0
-    if labels_out is not None:
-        _need_gpu(labels_out, dtype=torch.uint8)
-        if tuple(labels_out.shape) != (N, H, W) or labels_out.device != logits.device:
-            raise ValueError(f"labels_out must be uint8 {(N, H, W)} on {logits.device}, got {tuple(labels_out.shape)} on {labels_out.device}")
-        lab_pitch, lab_ns = _plane_layout(labels_out, (W,), "segment_consistency labels_out")
+    lab_pitch, lab_ns = _out_plane("segment_consistency", "labels_out", labels_out, N, H, W, logits.device)
     lut_c = None if lut is None else _host_u8(lut, n_cls, "lut")
     planes = (change_out is not None) + (labels_out is not None)
     launch("segment_consistency", _lib.load().arseg_segment_consistency_fwd, _ptr(logits), N, n_cls, h, w, H, W, 1 if align_corners else 0,
@@ -230,25 +256,6 @@ def labels_consistency(labels: torch.Tensor, ref_labels: torch.Tensor, mv_q: tor
 _RUN_DTYPES = tuple(d for d in (torch.int32, getattr(torch, "uint32", None)) if d is not None)          # one 32-bit word per run, either sign
 
 
-def _rle_common(what, N, H, device, row_start, runs, need_runs):
-    """The arguments the encoder and the decoder share -> cap (0 without runs)."""
-    _need_gpu(row_start, dtype=torch.int32)
-    if tuple(row_start.shape) != (N, H + 1) or not row_start.is_contiguous() or row_start.device != device or row_start.data_ptr() % 4:
-        raise _lib.ArsegError(f"{what}: row_start must be a contiguous int32 {(N, H + 1)} tensor on {device}, got {tuple(row_start.shape)} "
-                              f"strides {row_start.stride()} on {row_start.device}")
-    if runs is None:
-        if need_runs:
-            raise ValueError(f"{what}: runs is required")
-        return 0
-    _need_gpu(runs, dtype=None)
-    if runs.dtype not in _RUN_DTYPES:
-        raise _lib.ArsegError(f"{what}: runs holds one 32-bit word per run (torch.int32 or torch.uint32), got {runs.dtype}")
-    if runs.dim() != 2 or runs.shape[0] != N or not runs.is_contiguous() or runs.device != device or runs.data_ptr() % 4:
-        raise _lib.ArsegError(f"{what}: runs must be a contiguous 32-bit [{N}, cap] tensor on {device}, got {tuple(runs.shape)} strides "
-                              f"{runs.stride()} on {runs.device}")
-    return int(runs.shape[1])
-
-
 def labels_rle(labels: torch.Tensor, row_start: torch.Tensor, runs: Optional[torch.Tensor] = None):
     """An 8-bit plane uint8 [N,H,W] (rows contiguous, any pitch / image stride; any byte values) -> its row-run code (include/arseg_hip.h,
     arseg_labels_rle_fwd): ``row_start`` int32 [N,H+1], contiguous, OVERWRITTEN with the exclusive prefix of the rows' run counts
@@ -260,9 +267,9 @@ def labels_rle(labels: torch.Tensor, row_start: torch.Tensor, runs: Optional[tor
     if labels.dim() != 3:
         raise _lib.ArsegError(f"labels_rle expects a uint8 plane [N,H,W], got {tuple(labels.shape)}")
     N, H, W = labels.shape
-    if W > 1 << 24 or H * W > 2 ** 31 - 1:
-        raise ValueError(f"labels_rle: W <= 2^24 and H * W < 2^31, got {H}x{W}")
-    cap = _rle_common("labels_rle", N, H, labels.device, row_start, runs, False)
+    _frame_dims("labels_rle", H, W, positive=False)
+    _dense("labels_rle", "row_start", row_start, torch.int32, (N, H + 1), labels.device)
+    cap = 0 if runs is None else _dense("labels_rle", "runs", runs, _RUN_DTYPES, (N, None), labels.device)
     pitch, ns = _plane_layout(labels, (W,), "labels_rle labels")
     launch("labels_rle", _lib.load().arseg_labels_rle_fwd, _ptr(labels), pitch, ns, N, H, W, _ptr(row_start), _ptr(runs), cap, _stream(),
            nbytes=(2 if runs is not None else 1) * N * H * W + 12 * N * (H + 1))          # (+ 4 bytes per run, known on the device only)
@@ -278,15 +285,27 @@ def rle_decode(row_start: torch.Tensor, runs: torch.Tensor, labels_out: torch.Te
     if labels_out.dim() != 3:
         raise _lib.ArsegError(f"rle_decode expects a uint8 plane [N,H,W] to write into, got {tuple(labels_out.shape)}")
     N, H, W = labels_out.shape
-    if W > 1 << 24 or H * W > 2 ** 31 - 1:
-        raise ValueError(f"rle_decode: W <= 2^24 and H * W < 2^31, got {H}x{W}")
-    cap = _rle_common("rle_decode", N, H, labels_out.device, row_start, runs, True)
+    _frame_dims("rle_decode", H, W, positive=False)
+    _dense("rle_decode", "row_start", row_start, torch.int32, (N, H + 1), labels_out.device)
+    cap = _dense("rle_decode", "runs", runs, _RUN_DTYPES, (N, None), labels_out.device)
     pitch, ns = _plane_layout(labels_out, (W,), "rle_decode labels_out")
     if cap == 0:          # no run is stored (an empty tensor has no address to hand over): every pixel keeps what it held
         return labels_out
     launch("rle_decode", _lib.load().arseg_rle_decode_fwd, _ptr(row_start), _ptr(runs), cap, N, H, W, _ptr(labels_out), pitch, ns, _stream(),
            nbytes=N * H * W + 4 * N * (H + 1))
     return labels_out
+
+
+def _run_side(what, side, H, row_start, runs, n_regions, run_region, dev=None):
+    """A run code with its regions, the four arrays of one side (``side``: the prefix of their names) -> (frames, cap, device)."""
+    N = _dense(what, side + "row_start", row_start, torch.int32, (None, H + 1), dev)
+    dev = row_start.device
+    cap = _dense(what, side + "runs", runs, _RUN_DTYPES, (N, None), dev)
+    if cap == 0:
+        raise ValueError(f"{what}: the {side}run buffer holds no run (capacity 0)")
+    _dense(what, side + "n_regions", n_regions, torch.int32, (N,), dev)
+    _dense(what, side + "run_region", run_region, torch.int32, (N, cap), dev)
+    return N, cap, dev
 
 
 def rle_regions(row_start: torch.Tensor, runs: torch.Tensor, H: int, W: int, n_regions: torch.Tensor, run_region: torch.Tensor,
@@ -298,58 +317,18 @@ def rle_regions(row_start: torch.Tensor, runs: torch.Tensor, H: int, W: int, n_r
     their first pixel.  ``connectivity`` 4 or 8.  ``workspace``: a device tensor of at least ``arseg_rle_regions_workspace_bytes(N, cap)``
     bytes (default: the stream's shared workspace).  With every buffer given nothing is allocated and nothing synchronises: capturable in a
     HIP graph.  Returns (n_regions, run_region, regions)."""
-    H, W = int(H), int(W)
-    if H <= 0 or W <= 0 or W > 1 << 24 or H * W > 2 ** 31 - 1:
-        raise ValueError(f"rle_regions: 0 < W <= 2^24 and 0 < H * W < 2^31, got {H}x{W}")
+    what = "rle_regions"
+    H, W = _frame_dims(what, H, W)
     if connectivity not in (4, 8):
-        raise ValueError(f"rle_regions: connectivity is 4 or 8, got {connectivity!r}")
-    _need_gpu(row_start, dtype=torch.int32)
-    if row_start.dim() != 2 or row_start.shape[1] != H + 1:
-        raise _lib.ArsegError(f"rle_regions: row_start must be int32 [N,{H + 1}], got {tuple(row_start.shape)}")
-    N, dev = row_start.shape[0], row_start.device
-    cap = _rle_common("rle_regions", N, H, dev, row_start, runs, True)
-    if cap == 0:
-        raise ValueError("rle_regions: the run buffer holds no run (capacity 0)")
-    _need_gpu(n_regions, run_region, dtype=torch.int32)
-    if tuple(n_regions.shape) != (N,) or not n_regions.is_contiguous() or n_regions.device != dev:
-        raise _lib.ArsegError(f"rle_regions: n_regions must be a contiguous int32 [{N}] tensor on {dev}, got {tuple(n_regions.shape)}")
-    if tuple(run_region.shape) != (N, cap) or not run_region.is_contiguous() or run_region.device != dev:
-        raise _lib.ArsegError(f"rle_regions: run_region must be a contiguous int32 {(N, cap)} tensor on {dev}, got {tuple(run_region.shape)}")
-    rcap = 0
-    if regions is not None:
-        _need_gpu(regions, dtype=torch.int64)
-        if regions.dim() != 3 or regions.shape[0] != N or regions.shape[2] != 8 or not regions.is_contiguous() or regions.device != dev:
-            raise _lib.ArsegError(f"rle_regions: regions must be a contiguous int64 [{N}, rcap, 8] tensor on {dev}, got {tuple(regions.shape)}")
-        rcap = int(regions.shape[1])
+        raise ValueError(f"{what}: connectivity is 4 or 8, got {connectivity!r}")
+    N, cap, dev = _run_side(what, "", H, row_start, runs, n_regions, run_region)
+    rcap = 0 if regions is None else _dense(what, "regions", regions, torch.int64, (N, None, 8), dev)
     lib = _lib.load()
-    nbytes = lib.arseg_rle_regions_workspace_bytes(N, cap)
-    if workspace is None:
-        workspace = _workspace(nbytes, dev)
-    elif not workspace.is_cuda or workspace.device != dev or not workspace.is_contiguous() or workspace.numel() * workspace.element_size() < nbytes:
-        raise _lib.ArsegError(f"rle_regions: workspace must be a contiguous tensor of at least {nbytes} bytes on {dev}")
-    launch("rle_regions", lib.arseg_rle_regions_fwd, _ptr(row_start), _ptr(runs), cap, N, H, W, int(connectivity), _ptr(n_regions),
-           _ptr(run_region), _ptr(regions if rcap else None), rcap, _ptr(workspace), workspace.numel() * workspace.element_size(), _stream(),
+    workspace, ws_bytes = _own_workspace(what, workspace, lib.arseg_rle_regions_workspace_bytes(N, cap), dev)
+    launch(what, lib.arseg_rle_regions_fwd, _ptr(row_start), _ptr(runs), cap, N, H, W, int(connectivity), _ptr(n_regions),
+           _ptr(run_region), _ptr(regions if rcap else None), rcap, _ptr(workspace), ws_bytes, _stream(),
            nbytes=4 * N * (H + 1))          # (+ about 50 bytes per run, known on the device only)
     return n_regions, run_region, regions
-
-
-def _links_side(what, side, H, row_start, runs, n_regions, run_region, device=None):
-    """One side's four arrays of ``region_links`` -> (frames, cap)."""
-    _need_gpu(row_start, dtype=torch.int32)
-    if row_start.dim() != 2 or row_start.shape[1] != H + 1:
-        raise _lib.ArsegError(f"{what}: {side}row_start must be int32 [N,{H + 1}], got {tuple(row_start.shape)}")
-    F, dev = row_start.shape[0], row_start.device
-    if device is not None and dev != device:
-        raise _lib.ArsegError(f"{what}: {side}row_start must be on {device}, got {dev}")
-    cap = _rle_common(what, F, H, dev, row_start, runs, True)
-    if cap == 0:
-        raise ValueError(f"{what}: the {side}run buffer holds no run (capacity 0)")
-    _need_gpu(n_regions, run_region, dtype=torch.int32)
-    if tuple(n_regions.shape) != (F,) or not n_regions.is_contiguous() or n_regions.device != dev:
-        raise _lib.ArsegError(f"{what}: {side}n_regions must be a contiguous int32 [{F}] tensor on {dev}, got {tuple(n_regions.shape)}")
-    if tuple(run_region.shape) != (F, cap) or not run_region.is_contiguous() or run_region.device != dev:
-        raise _lib.ArsegError(f"{what}: {side}run_region must be a contiguous int32 {(F, cap)} tensor on {dev}, got {tuple(run_region.shape)}")
-    return F, cap
 
 
 def region_links(row_start: torch.Tensor, runs: torch.Tensor, n_regions: torch.Tensor, run_region: torch.Tensor, ref_row_start: torch.Tensor,
@@ -367,45 +346,24 @@ def region_links(row_start: torch.Tensor, runs: torch.Tensor, n_regions: torch.T
     ``arseg_region_links_workspace_bytes(N, pair_capacity)`` bytes, 8-byte aligned (default: the stream's shared workspace).  With every
     buffer given nothing is allocated and nothing synchronises: capturable in a HIP graph.  Returns (n_pairs, links, back)."""
     what = "region_links"
-    H, W = int(H), int(W)
-    if H <= 0 or W <= 0 or W > 1 << 24 or H * W > 2 ** 31 - 1:
-        raise ValueError(f"{what}: 0 < W <= 2^24 and 0 < H * W < 2^31, got {H}x{W}")
-    N, cap = _links_side(what, "", H, row_start, runs, n_regions, run_region)
-    dev = row_start.device
-    R, ref_cap = _links_side(what, "ref_", H, ref_row_start, ref_runs, ref_n_regions, ref_run_region, dev)
+    H, W = _frame_dims(what, H, W)
+    N, cap, dev = _run_side(what, "", H, row_start, runs, n_regions, run_region)
+    R, ref_cap, _ = _run_side(what, "ref_", H, ref_row_start, ref_runs, ref_n_regions, ref_run_region, dev)
     if R not in (1, N):
         raise ValueError(f"{what}: one reference frame (shared) or {N}, got {R}")
     pcap = 4 * cap if pair_capacity is None else int(pair_capacity)
     if pcap < 1:
         raise ValueError(f"{what}: pair_capacity must be at least 1, got {pair_capacity!r}")
-    _need_gpu(n_pairs, dtype=torch.int32)
-    if tuple(n_pairs.shape) != (N,) or not n_pairs.is_contiguous() or n_pairs.device != dev:
-        raise _lib.ArsegError(f"{what}: n_pairs must be a contiguous int32 [{N}] tensor on {dev}, got {tuple(n_pairs.shape)}")
-    caps = []
-    for name, t, width in (("links", links, 6), ("back", back, 4)):
-        caps.append(0)
-        if t is not None:
-            _need_gpu(t, dtype=torch.int64)
-            if t.dim() != 3 or t.shape[0] != N or t.shape[2] != width or not t.is_contiguous() or t.device != dev:
-                raise _lib.ArsegError(f"{what}: {name} must be a contiguous int64 [{N}, capacity, {width}] tensor on {dev}, got {tuple(t.shape)}")
-            caps[-1] = int(t.shape[1])
-    rcap, kcap = caps
+    _dense(what, "n_pairs", n_pairs, torch.int32, (N,), dev)
+    rcap = 0 if links is None else _dense(what, "links", links, torch.int64, (N, None, 6), dev)
+    kcap = 0 if back is None else _dense(what, "back", back, torch.int64, (N, None, 4), dev)
     if mv_q is not None:
-        _need_gpu(mv_q, dtype=torch.int16)
-        if tuple(mv_q.shape) != (N, H, W, 2) or not mv_q.is_contiguous() or mv_q.device != dev or mv_q.data_ptr() % 4:
-            raise _lib.ArsegError(f"{what}: mv_q must be a contiguous, 4-byte aligned int16 {(N, H, W, 2)} tensor on {dev}, got "
-                                  f"{tuple(mv_q.shape)} strides {mv_q.stride()} on {mv_q.device}")
+        _mv_field(what, mv_q, N, H, W, dev)
     lib = _lib.load()
-    nbytes = lib.arseg_region_links_workspace_bytes(N, pcap)
-    if workspace is None:
-        workspace = _workspace(nbytes, dev)
-    elif not workspace.is_cuda or workspace.device != dev or not workspace.is_contiguous() or workspace.data_ptr() % 8 or \
-            workspace.numel() * workspace.element_size() < nbytes:
-        raise _lib.ArsegError(f"{what}: workspace must be a contiguous, 8-byte aligned tensor of at least {nbytes} bytes on {dev}")
+    workspace, ws_bytes = _own_workspace(what, workspace, lib.arseg_region_links_workspace_bytes(N, pcap), dev, 8)
     launch(what, lib.arseg_region_links_fwd, _ptr(row_start), _ptr(runs), _ptr(n_regions), _ptr(run_region), cap, _ptr(ref_row_start),
            _ptr(ref_runs), _ptr(ref_n_regions), _ptr(ref_run_region), ref_cap, 1 if R == 1 else 0, _ptr(mv_q), N, H, W, _ptr(n_pairs),
-           _ptr(links if rcap else None), rcap, _ptr(back if kcap else None), kcap, pcap, _ptr(workspace),
-           workspace.numel() * workspace.element_size(), _stream(),
+           _ptr(links if rcap else None), rcap, _ptr(back if kcap else None), kcap, pcap, _ptr(workspace), ws_bytes, _stream(),
            nbytes=(4 * N * H * W if mv_q is not None else 0) + 64 * N * pcap)          # the field once from HBM; the tables cleared and read
     return n_pairs, links, back
 
@@ -439,46 +397,29 @@ def rle_absorb(row_start: torch.Tensor, runs: torch.Tensor, n_regions: torch.Ten
     pair_capacity)`` bytes, 8-byte aligned (default: the stream's shared workspace).  With every buffer given nothing is allocated and
     nothing synchronises: capturable in a HIP graph.  Returns (out_row_start, out_runs, target, n_absorbed)."""
     what = "rle_absorb"
-    H, W = int(H), int(W)
-    if H <= 0 or W <= 0 or W > 1 << 24 or H * W > 2 ** 31 - 1:
-        raise ValueError(f"{what}: 0 < W <= 2^24 and 0 < H * W < 2^31, got {H}x{W}")
+    H, W = _frame_dims(what, H, W)
     min_area = int(min_area)
     if min_area < 1:
         raise ValueError(f"{what}: min_area must be at least 1, got {min_area}")
-    N, cap = _links_side(what, "", H, row_start, runs, n_regions, run_region)
-    dev = row_start.device
-    _need_gpu(regions, dtype=torch.int64)
-    if regions.dim() != 3 or regions.shape[0] != N or regions.shape[2] != 8 or not regions.is_contiguous() or regions.device != dev:
-        raise _lib.ArsegError(f"{what}: regions must be a contiguous int64 [{N}, rcap, 8] tensor on {dev}, got {tuple(regions.shape)}")
-    rcap = int(regions.shape[1])
+    N, cap, dev = _run_side(what, "", H, row_start, runs, n_regions, run_region)
+    rcap = _dense(what, "regions", regions, torch.int64, (N, None, 8), dev)
     if rcap == 0:
         raise ValueError(f"{what}: the record buffer holds no region (capacity 0)")
-    out_cap = _rle_common(what, N, H, dev, out_row_start, out_runs, True)
+    _dense(what, "out_row_start", out_row_start, torch.int32, (N, H + 1), dev)
+    out_cap = _dense(what, "out_runs", out_runs, _RUN_DTYPES, (N, None), dev)
     if out_cap == 0:
         raise ValueError(f"{what}: the output run buffer holds no run (capacity 0)")
-    _need_gpu(n_absorbed, dtype=torch.int32)
-    if tuple(n_absorbed.shape) != (N,) or not n_absorbed.is_contiguous() or n_absorbed.device != dev:
-        raise _lib.ArsegError(f"{what}: n_absorbed must be a contiguous int32 [{N}] tensor on {dev}, got {tuple(n_absorbed.shape)}")
-    tcap = 0
-    if target is not None:
-        _need_gpu(target, dtype=torch.int32)
-        if target.dim() != 2 or target.shape[0] != N or not target.is_contiguous() or target.device != dev:
-            raise _lib.ArsegError(f"{what}: target must be a contiguous int32 [{N}, capacity] tensor on {dev}, got {tuple(target.shape)}")
-        tcap = int(target.shape[1])
+    _dense(what, "n_absorbed", n_absorbed, torch.int32, (N,), dev)
+    tcap = 0 if target is None else _dense(what, "target", target, torch.int32, (N, None), dev)
     protect_c = None if protect is None else _host_u8(protect_table(protect, what), 256, "protect")
     pcap = 3 * cap if pair_capacity is None else int(pair_capacity)
     if pcap < 1:
         raise ValueError(f"{what}: pair_capacity must be at least 1, got {pair_capacity!r}")
     lib = _lib.load()
-    nbytes = lib.arseg_rle_absorb_workspace_bytes(N, cap, rcap, H, pcap)
-    if workspace is None:
-        workspace = _workspace(nbytes, dev)
-    elif not workspace.is_cuda or workspace.device != dev or not workspace.is_contiguous() or workspace.data_ptr() % 8 or \
-            workspace.numel() * workspace.element_size() < nbytes:
-        raise _lib.ArsegError(f"{what}: workspace must be a contiguous, 8-byte aligned tensor of at least {nbytes} bytes on {dev}")
+    workspace, ws_bytes = _own_workspace(what, workspace, lib.arseg_rle_absorb_workspace_bytes(N, cap, rcap, H, pcap), dev, 8)
     launch(what, lib.arseg_rle_absorb_fwd, _ptr(row_start), _ptr(runs), _ptr(n_regions), _ptr(run_region), cap, _ptr(regions), rcap, N, H, W,
            min_area, protect_c, _ptr(out_row_start), _ptr(out_runs), out_cap, _ptr(target if tcap else None), tcap, _ptr(n_absorbed), pcap,
-           _ptr(workspace), workspace.numel() * workspace.element_size(), _stream(),
+           _ptr(workspace), ws_bytes, _stream(),
            nbytes=32 * N * pcap + 12 * N * (H + 1))          # the table cleared and read (+ about 40 bytes per run, known on the device only)
     return out_row_start, out_runs, target, n_absorbed
 
@@ -495,40 +436,19 @@ def rle_contours(row_start: torch.Tensor, runs: torch.Tensor, n_regions: torch.T
     device tensor of at least ``arseg_rle_contours_workspace_bytes(N, cap)`` bytes (default: the stream's shared workspace).  With every
     buffer given nothing is allocated and nothing synchronises: capturable in a HIP graph.  Returns (counts, loops, verts)."""
     what = "rle_contours"
-    H, W = int(H), int(W)
-    if H <= 0 or W <= 0 or H > 65535 or W > 65535:
-        raise ValueError(f"{what}: 0 < H <= 65535 and 0 < W <= 65535 (a vertex is y << 16 | x), got {H}x{W}")
+    H, W = _frame_dims(what, H, W, 65535)          # a vertex is y << 16 | x
     if connectivity not in (4, 8):
         raise ValueError(f"{what}: connectivity is 4 or 8, got {connectivity!r}")
-    N, cap = _links_side(what, "", H, row_start, runs, n_regions, run_region)
+    N, cap, dev = _run_side(what, "", H, row_start, runs, n_regions, run_region)
     if cap > 1 << 29:
         raise ValueError(f"{what}: at most 2^29 runs per frame, got a capacity of {cap}")
-    dev = row_start.device
-    _need_gpu(counts, dtype=torch.int32)
-    if tuple(counts.shape) != (N, 2) or not counts.is_contiguous() or counts.device != dev:
-        raise _lib.ArsegError(f"{what}: counts must be a contiguous int32 {(N, 2)} tensor on {dev}, got {tuple(counts.shape)}")
-    lcap = vcap = 0
-    if loops is not None:
-        _need_gpu(loops, dtype=torch.int32)
-        if loops.dim() != 3 or loops.shape[0] != N or loops.shape[2] != 4 or not loops.is_contiguous() or loops.device != dev:
-            raise _lib.ArsegError(f"{what}: loops must be a contiguous int32 [{N}, capacity, 4] tensor on {dev}, got {tuple(loops.shape)}")
-        lcap = int(loops.shape[1])
-    if verts is not None:
-        _need_gpu(verts, dtype=None)
-        if verts.dtype not in _RUN_DTYPES or verts.dim() != 2 or verts.shape[0] != N or not verts.is_contiguous() or verts.device != dev:
-            raise _lib.ArsegError(f"{what}: verts must be a contiguous 32-bit [{N}, capacity] tensor on {dev}, got {verts.dtype} "
-                                  f"{tuple(verts.shape)}")
-        vcap = int(verts.shape[1])
+    _dense(what, "counts", counts, torch.int32, (N, 2), dev)
+    lcap = 0 if loops is None else _dense(what, "loops", loops, torch.int32, (N, None, 4), dev)
+    vcap = 0 if verts is None else _dense(what, "verts", verts, _RUN_DTYPES, (N, None), dev)
     lib = _lib.load()
-    nbytes = lib.arseg_rle_contours_workspace_bytes(N, cap)
-    if workspace is None:
-        workspace = _workspace(nbytes, dev)
-    elif not workspace.is_cuda or workspace.device != dev or not workspace.is_contiguous() or workspace.data_ptr() % 4 or \
-            workspace.numel() * workspace.element_size() < nbytes:
-        raise _lib.ArsegError(f"{what}: workspace must be a contiguous, 4-byte aligned tensor of at least {nbytes} bytes on {dev}")
+    workspace, ws_bytes = _own_workspace(what, workspace, lib.arseg_rle_contours_workspace_bytes(N, cap), dev, 4)
     launch(what, lib.arseg_rle_contours_fwd, _ptr(row_start), _ptr(runs), _ptr(n_regions), _ptr(run_region), cap, N, H, W, int(connectivity),
-           _ptr(counts), _ptr(loops if lcap else None), lcap, _ptr(verts if vcap else None), vcap, _ptr(workspace),
-           workspace.numel() * workspace.element_size(), _stream(),
+           _ptr(counts), _ptr(loops if lcap else None), lcap, _ptr(verts if vcap else None), vcap, _ptr(workspace), ws_bytes, _stream(),
            nbytes=4 * N * (H + 1))          # (+ about 80 bytes per run and round of jumping, known on the device only)
     return counts, loops, verts
 
@@ -554,40 +474,26 @@ def contours_simplify(counts: torch.Tensor, loops: Optional[torch.Tensor], verts
     vcap)`` bytes (default: the stream's shared workspace).  With every buffer given nothing is allocated and nothing synchronises:
     capturable in a HIP graph.  Returns (counts_out, loops_out, verts_out)."""
     what = "contours_simplify"
-    H, W = int(H), int(W)
-    if H <= 0 or W <= 0 or H > 16384 or W > 16384:
-        raise ValueError(f"{what}: 0 < H <= 16384 and 0 < W <= 16384, got {H}x{W}")
+    H, W = _frame_dims(what, H, W, 16384)
     tol2_q = tolerance_q(tolerance, what)
-    _need_gpu(counts, counts_out, dtype=torch.int32)
-    if counts.dim() != 2 or counts.shape[1] != 2 or counts.shape[0] < 1 or not counts.is_contiguous():
-        raise _lib.ArsegError(f"{what}: counts must be a contiguous int32 [N,2] tensor, got {tuple(counts.shape)}")
-    N, dev = int(counts.shape[0]), counts.device
-    if tuple(counts_out.shape) != (N, 2) or not counts_out.is_contiguous() or counts_out.device != dev:
-        raise _lib.ArsegError(f"{what}: counts_out must be a contiguous int32 {(N, 2)} tensor on {dev}, got {tuple(counts_out.shape)}")
-    lcap = vcap = vcap_out = 0
+    N = _dense(what, "counts", counts, torch.int32, (None, 2))
+    dev = counts.device
+    if N < 1:
+        raise _lib.ArsegError(f"{what}: counts must hold at least one frame, got {tuple(counts.shape)}")
+    _dense(what, "counts_out", counts_out, torch.int32, (N, 2), dev)
+    lcap = 0
     if loops is not None:
-        _need_gpu(loops, loops_out, dtype=torch.int32)
-        if loops.dim() != 3 or loops.shape[0] != N or loops.shape[2] != 4 or not loops.is_contiguous() or loops.device != dev:
-            raise _lib.ArsegError(f"{what}: loops must be a contiguous int32 [{N}, capacity, 4] tensor on {dev}, got {tuple(loops.shape)}")
-        if loops_out is None or tuple(loops_out.shape) != tuple(loops.shape) or not loops_out.is_contiguous() or loops_out.device != dev:
-            raise _lib.ArsegError(f"{what}: loops_out must be a contiguous int32 {tuple(loops.shape)} tensor on {dev}")
-        lcap = int(loops.shape[1])
-    for name, t in (("verts", verts), ("verts_out", verts_out)):
-        if t is not None:
-            _need_gpu(t, dtype=None)
-            if t.dtype not in _RUN_DTYPES or t.dim() != 2 or t.shape[0] != N or not t.is_contiguous() or t.device != dev:
-                raise _lib.ArsegError(f"{what}: {name} must be a contiguous 32-bit [{N}, capacity] tensor on {dev}, got {t.dtype} {tuple(t.shape)}")
-    vcap = int(verts.shape[1]) if verts is not None else 0
-    vcap_out = int(verts_out.shape[1]) if verts_out is not None else 0
+        lcap = _dense(what, "loops", loops, torch.int32, (N, None, 4), dev)
+        if loops_out is None:
+            raise _lib.ArsegError(f"{what}: loops_out is required with loops")
+        _dense(what, "loops_out", loops_out, torch.int32, (N, lcap, 4), dev)
+    vcap = 0 if verts is None else _dense(what, "verts", verts, _RUN_DTYPES, (N, None), dev)
+    vcap_out = 0 if verts_out is None else _dense(what, "verts_out", verts_out, _RUN_DTYPES, (N, None), dev)
     lib = _lib.load()
     nbytes = lib.arseg_contours_simplify_workspace_bytes(N, lcap, vcap)
-    if workspace is None:
-        workspace = _workspace(max(nbytes, 16), dev)
-    elif not workspace.is_cuda or workspace.device != dev or not workspace.is_contiguous() or workspace.data_ptr() % 4 or \
-            workspace.numel() * workspace.element_size() < nbytes:
-        raise _lib.ArsegError(f"{what}: workspace must be a contiguous, 4-byte aligned tensor of at least {nbytes} bytes on {dev}")
+    workspace, ws_bytes = _own_workspace(what, workspace, max(nbytes, 16) if workspace is None else nbytes, dev, 4)
     launch(what, lib.arseg_contours_simplify_fwd, _ptr(counts), _ptr(loops if lcap else None), lcap, _ptr(verts if vcap else None), vcap, N, H, W,
            tol2_q, _ptr(counts_out), _ptr(loops_out if lcap else None), _ptr(verts_out if vcap_out else None), vcap_out, _ptr(workspace),
-           workspace.numel() * workspace.element_size(), _stream(),
+           ws_bytes, _stream(),
            nbytes=16 * N)          # (+ about 16 bytes per loop and some 30 per vertex, known on the device only)
     return counts_out, loops_out, verts_out

@@ -114,6 +114,14 @@ def test_run_and_region_counts(dev, count):
 
 
 @pytest.mark.parametrize("connectivity", [4, 8])
+@pytest.mark.parametrize("H", [256, 257, 513])
+def test_tall_planes(dev, H, connectivity):
+    """More rows than one 256-entry pass of the scan over out_row_start: exactly one pass, one row into the second, one into the third.
+    Narrow dense noise, so that every row has runs and specks; two unlike frames per call."""
+    _run(dev, regions_oracle.dense_noise(1000 + H, 2, H, 5), 3, connectivity=connectivity)
+
+
+@pytest.mark.parametrize("connectivity", [4, 8])
 def test_seeded_planes_and_unlike_frames(dev, connectivity):
     """The seeded noise, and N = 2 with frames of different sizes of problem in both orders: a frame's result is the one it has alone."""
     noise = regions_oracle.noise_planes(*regions_oracle.NOISE)
