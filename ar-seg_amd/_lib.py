@@ -7,7 +7,7 @@ from __future__ import annotations
 
 import ctypes
 import os
-from ctypes import POINTER, Structure, c_char_p, c_double, c_float, c_int, c_int16, c_int32, c_int64, c_size_t, c_void_p
+from ctypes import POINTER, Structure, c_char_p, c_double, c_float, c_int, c_int16, c_int32, c_int64, c_size_t, c_uint64, c_void_p
 
 _HERE = os.path.dirname(os.path.abspath(__file__))
 LIB_PATH = os.environ.get("ARSEG_HIP_LIB", os.path.join(_HERE, "lib", "libarseg_hip.so"))   # env override: kernel experiments
@@ -23,6 +23,7 @@ MATH_F32, MATH_F16X3, MATH_F16 = 0, 1, 2
 DT_F32, DT_F16, DT_BF16 = 0, 1, 2
 SRC_RGB8, SRC_NV12, SRC_I420, SRC_P010, SRC_I010 = 0, 1, 2, 3, 4
 COLOUR_BT601_LIMITED, COLOUR_BT601_FULL, COLOUR_BT709_LIMITED, COLOUR_BT709_FULL = 0, 1, 2, 3
+MVR_BI_LIST0, MVR_BI_NEAR, MVR_BI_MEAN = 0, 1, 2
 CONF_TOP1, CONF_MARGIN = 0, 1
 CONF_NSTATS = 2 + 32      # ARSEG_CONF_NSTATS: sum of codes, low count, 32 class areas
 TC_NSTATS = 3 + 3 * 32    # ARSEG_TC_NSTATS: compared, outside, void, then 32 each of cur_k, ref_k, inter_k
@@ -127,6 +128,9 @@ PROTOTYPES = {
     "arseg_mv_records_reset": (c_int, [_P, _P, c_size_t, c_int, c_int, _STREAM]),
     "arseg_mv_records_step_fwd": (c_int, [_P, c_int, _P, c_int, c_int, _P, c_size_t, c_int, c_int, c_int, _STREAM]),
     "arseg_mv_records_rasterize_fwd": (c_int, [_P, c_int, _P, _P, c_size_t, c_int, c_int, _STREAM]),
+    "arseg_mv_records_bi_workspace_bytes": (c_size_t, [c_int, c_int]),
+    "arseg_mv_records_bi_reset": (c_int, [_P, _P, c_size_t, c_int, c_int, _STREAM]),
+    "arseg_mv_records_bi_step_fwd": (c_int, [_P, c_int, _P, c_int, c_int, c_uint64, c_int, _P, c_size_t, c_int, c_int, c_int, _STREAM]),
     "arseg_nchw_to_nhwc_fwd": (c_int, [_P, _P, c_int, c_int, c_int, c_int, _STREAM]),
     "arseg_nhwc_to_nchw_fwd": (c_int, [_P, c_int, _P, c_int, c_int, c_int, _STREAM]),
     "arseg_argmax_confusion_fwd": (c_int, [_P, _P, _P, _P] + [c_int] * 8 + [_STREAM]),

@@ -8,6 +8,8 @@
 //             next frame needs no fill pass
 // The merged tensor is the chain state: within H, W <= 8192 every accumulated value fits int16, so the link of a pixel is
 // out[f][y,x] = 4 (k2 - x, j2 - y) + (f2 > 0 ? out[f2][j2,k2] : 0) and mergeMotion's int4 link table (layers.hip) is not needed.
+// B-frames (arseg_mv_records_bi_*): two index maps, one per prediction list (reserved & 1), the same two kernels per frame; a frame links to
+// any frame already chained in this GOP (done_mask), before or after it in display order, and frames arrive in decode order.
 #include "arseg_device.h"
 
 constexpr int MVR_MAX_DIM = 8192;      // 4 * 8191 = 32764: the largest accumulated displacement still fits int16
@@ -17,6 +19,8 @@ constexpr int MVR_BAND = 256;          // frame rows per scatter band (blockIdx.
 __device__ __forceinline__ int rec_lo(int v) { return (int)(short)v; }
 __device__ __forceinline__ int rec_hi(int v) { return v >> 16; }
 
+// BI: idx is two maps of H * W words, the record's list bit (reserved & 1) picks one
+template <bool BI>
 __global__ __launch_bounds__(256) void mv_records_scatter_kernel(const int4 *__restrict__ rec, int n, int *__restrict__ idx, int H, int W) {
     const int lane = threadIdx.x & 63;
     const int wave = blockIdx.x * 4 + __builtin_amdgcn_readfirstlane((int)(threadIdx.x >> 6)), n_waves = gridDim.x * 4;
@@ -30,8 +34,10 @@ __global__ __launch_bounds__(256) void mv_records_scatter_kernel(const int4 *__r
         const int cw = x1 - x0;
         const int sh = cw > 32 ? 6 : (cw <= 1 ? 0 : 32 - __clz(cw - 1));      // lanes along x: the power of two that covers min(cw, 64)
         const int lx = lane & ((1 << sh) - 1), ly = lane >> sh, lxn = 1 << sh, lyn = 64 >> sh;
+        int *map = idx;
+        if constexpr (BI) map += (size_t)(rec_hi(q.w) & 1) * H * W;
         for (int yy = y0 + ly; yy < y1; yy += lyn)
-            for (int xx = x0 + lx; xx < x1; xx += lxn) atomicMax(idx + yy * W + xx, r);      // 0 <= yy < H, 0 <= xx < W
+            for (int xx = x0 + lx; xx < x1; xx += lxn) atomicMax(map + yy * W + xx, r);      // 0 <= yy < H, 0 <= xx < W
     }
 }
 
@@ -83,6 +89,97 @@ __global__ __launch_bounds__(256) void mv_records_compose_kernel(const int4 *__r
     }
 }
 
+// ---- B-frames: two lists, decode order ----
+// display-order target of reference code `ref` from frame f: ref >= 0 counts back from f - 1 (clamped to the keyframe), ref < 0 forward from f + 1
+__device__ __forceinline__ int mvb_target(int f, int ref) { return ref >= 0 ? max(0, f - ref - 1) : f - ref; }
+
+// bit (ref + 16) set where a winner with that ref is usable: ref in [-max_ref, max_ref) and its target already chained.  Wave uniform (kernel
+// arguments only); max_ref <= 16 keeps the 32 codes in one word.
+__device__ __forceinline__ unsigned mvb_usable_refs(int f, unsigned long long done, int max_ref) {
+    unsigned m = 0;
+    for (int ref = -max_ref; ref < max_ref; ++ref) {
+        const int t = mvb_target(f, ref);
+        if (t < 64 && ((done >> t) & 1ull)) m |= 1u << (ref + 16);
+    }
+    return m;
+}
+
+// link of one list: packed 4 (k2 - x, j2 - y) + (t > 0 ? merged[t][j2][k2] : 0)
+__device__ __forceinline__ unsigned mvb_link(int4 q, int t, const unsigned *merged, int x, int y, int H, int W) {
+    const int k2 = min(max(x + round_half_even_div4(rec_lo(q.z)), 0), W - 1), j2 = min(max(y + round_half_even_div4(rec_hi(q.z)), 0), H - 1);
+    int dx = 4 * (k2 - x), dy = 4 * (j2 - y);
+    if (t > 0) {
+        const unsigned m = merged[((size_t)t * H + j2) * W + k2];
+        dx += rec_lo((int)m); dy += rec_hi((int)m);
+    }
+    return ((unsigned)dx & 0xffffu) | ((unsigned)dy << 16);
+}
+
+__device__ __forceinline__ int mvb_mean(int a, int b) {               // (a + b) / 2, half to even
+    const int s = a + b, m = s >> 1;
+    return m + (s & 1 & m);
+}
+
+// one pixel of frame f.  id0 / id1: the winners of list 0 / 1, outside [0, n) = none.  p: the nearest chained frame before f (intra target).
+__device__ __forceinline__ unsigned mvb_compose(const int4 *__restrict__ rec, int n, int id0, int id1, const unsigned *merged, int f, int p, unsigned usable,
+                                                int policy, int pix, int x, int y, int H, int W) {
+    int4 q0 = make_int4(0, 0, 0, 0), q1 = q0;
+    bool u0 = false, u1 = false;
+    if ((unsigned)id0 < (unsigned)n) {
+        q0 = rec[id0];
+        const unsigned c = (unsigned)(rec_lo(q0.w) + 16);
+        u0 = c < 32u && ((usable >> c) & 1u);
+    }
+    if ((unsigned)id1 < (unsigned)n) {
+        q1 = rec[id1];
+        const unsigned c = (unsigned)(rec_lo(q1.w) + 16);
+        u1 = c < 32u && ((usable >> c) & 1u);
+    }
+    const int t0 = mvb_target(f, rec_lo(q0.w)), t1 = mvb_target(f, rec_lo(q1.w));
+    if (u0 && u1 && policy != ARSEG_MVR_BI_MEAN) {                    // one list: one gather
+        if (policy == ARSEG_MVR_BI_NEAR && abs(t1 - f) < abs(t0 - f)) u0 = false;
+        else u1 = false;
+    }
+    if (!u0 && !u1) return p > 0 ? merged[(size_t)p * H * W + pix] : 0u;      // intra: zero motion to frame p
+    const unsigned l0 = u0 ? mvb_link(q0, t0, merged, x, y, H, W) : 0u, l1 = u1 ? mvb_link(q1, t1, merged, x, y, H, W) : 0u;
+    if (u0 && u1) return ((unsigned)mvb_mean(rec_lo((int)l0), rec_lo((int)l1)) & 0xffffu) | ((unsigned)mvb_mean(rec_hi((int)l0), rec_hi((int)l1)) << 16);
+    return u0 ? l0 : l1;
+}
+
+// idx: two maps of hw words (list 0, list 1).  merged / out: the same tensor (frames in `done` are read, frame f, not in `done`, is written)
+template <bool VEC>
+__global__ __launch_bounds__(256) void mv_records_bi_compose_kernel(const int4 *__restrict__ rec, int n, int *__restrict__ idx, const unsigned *merged, unsigned *out,
+                                                                    int f, unsigned long long done, int policy, int H, int W, int max_ref) {
+    const int hw = H * W;
+    const unsigned usable = mvb_usable_refs(f, done, max_ref);
+    const int p = 63 - __clzll((long long)(done & ((1ull << f) - 1ull)));     // bit 0 of done is set, 1 <= f < 64
+    int *idx1 = idx + hw;
+    if constexpr (VEC) {                                              // hw % 4 == 0, 16-byte aligned frames
+        const int n4 = hw >> 2;
+        for (int t = blockIdx.x * blockDim.x + threadIdx.x; t < n4; t += gridDim.x * blockDim.x) {
+            const int4 a = reinterpret_cast<const int4 *>(idx)[t], b = reinterpret_cast<const int4 *>(idx1)[t];
+            int y = (t * 4) / W, x = t * 4 - y * W;
+            const int ia[4] = {a.x, a.y, a.z, a.w}, ib[4] = {b.x, b.y, b.z, b.w};
+            u32x4 o;
+#pragma unroll
+            for (int k = 0; k < 4; ++k) {
+                o[k] = mvb_compose(rec, n, ia[k], ib[k], merged, f, p, usable, policy, t * 4 + k, x, y, H, W);
+                if (++x == W) { x = 0; ++y; }
+            }
+            reinterpret_cast<u32x4 *>(out)[t] = o;
+            reinterpret_cast<int4 *>(idx)[t] = make_int4(-1, -1, -1, -1);
+            reinterpret_cast<int4 *>(idx1)[t] = make_int4(-1, -1, -1, -1);
+        }
+    } else {
+        for (int pix = blockIdx.x * blockDim.x + threadIdx.x; pix < hw; pix += gridDim.x * blockDim.x) {
+            const int y = pix / W, x = pix - y * W;
+            out[pix] = mvb_compose(rec, n, idx[pix], idx1[pix], merged, f, p, usable, policy, pix, x, y, H, W);
+            idx[pix] = -1;
+            idx1[pix] = -1;
+        }
+    }
+}
+
 // the dense field of one frame as the reference's decoder dumps it: (mvx, mvy, ref) of the winning record, (0, 0, -1) where there is none
 __global__ __launch_bounds__(256) void mv_records_dense_kernel(const int4 *__restrict__ rec, int n, int *__restrict__ idx, int16_t *__restrict__ dense, int hw) {
     for (int pix = blockIdx.x * blockDim.x + threadIdx.x; pix < hw; pix += gridDim.x * blockDim.x) {
@@ -105,18 +202,20 @@ __global__ __launch_bounds__(256) void mv_records_fill_kernel(unsigned *__restri
     }
 }
 
-static int mvr_check_frame(const void *records, int n_records, const void *workspace, size_t workspace_bytes, int H, int W) {
+// maps: index maps in the workspace (1: P-frames, 2: B-frames)
+static int mvr_check_frame(const void *records, int n_records, const void *workspace, size_t workspace_bytes, int H, int W, int maps = 1) {
     if (n_records < 0 || (n_records > 0 && records == nullptr) || workspace == nullptr) return ARSEG_EINVAL;
     if (H <= 0 || W <= 0 || H > MVR_MAX_DIM || W > MVR_MAX_DIM) return ARSEG_EINVAL;
-    if (workspace_bytes < arseg_mv_records_workspace_bytes(H, W)) return ARSEG_EWORKSPACE;
+    if (workspace_bytes < maps * arseg_mv_records_workspace_bytes(H, W)) return ARSEG_EWORKSPACE;
     if (!ARSEG_ALIGNED16(workspace) || !ARSEG_ALIGNED16(records)) return ARSEG_EINVAL;
     return ARSEG_OK;
 }
 
+template <bool BI = false>
 static void mvr_scatter(const int16_t *records, int n_records, int *idx, int H, int W, hipStream_t st) {
     if (n_records == 0) return;
     const int gx = (int)(((long long)n_records + 3) / 4 > 65536 ? 65536 : ((long long)n_records + 3) / 4);
-    hipLaunchKernelGGL(mv_records_scatter_kernel, dim3(gx, arseg_cdiv(H, MVR_BAND)), dim3(256), 0, st, reinterpret_cast<const int4 *>(records), n_records, idx, H, W);
+    hipLaunchKernelGGL(mv_records_scatter_kernel<BI>, dim3(gx, arseg_cdiv(H, MVR_BAND)), dim3(256), 0, st, reinterpret_cast<const int4 *>(records), n_records, idx, H, W);
 }
 
 extern "C" size_t arseg_mv_records_workspace_bytes(int H, int W) {
@@ -165,5 +264,45 @@ extern "C" int arseg_mv_records_rasterize_fwd(const int16_t *records, int n_reco
     hipLaunchKernelGGL(mv_records_fill_kernel, dim3(arseg_grid_for(hw)), dim3(256), 0, st, reinterpret_cast<unsigned *>(idx), (unsigned *)nullptr, hw);
     mvr_scatter(records, n_records, idx, H, W, st);
     hipLaunchKernelGGL(mv_records_dense_kernel, dim3(arseg_grid_for(hw)), dim3(256), 0, st, reinterpret_cast<const int4 *>(records), n_records, idx, dense_out, hw);
+    return arseg_launch_status();
+}
+
+extern "C" size_t arseg_mv_records_bi_workspace_bytes(int H, int W) { return 2 * arseg_mv_records_workspace_bytes(H, W); }
+
+extern "C" int arseg_mv_records_bi_reset(int16_t *merged, void *workspace, size_t workspace_bytes, int H, int W, arseg_stream_t stream) {
+    ARSEG_CHECK_PTR(merged);
+    const int bad = mvr_check_frame(nullptr, 0, workspace, workspace_bytes, H, W, 2);
+    if (bad) return bad;
+    if (reinterpret_cast<uintptr_t>(merged) & 3u) return ARSEG_EINVAL;
+    hipStream_t st = arseg_stream(stream);
+    const int hw = H * W;
+    unsigned *ws = reinterpret_cast<unsigned *>(workspace);
+    hipLaunchKernelGGL(mv_records_fill_kernel, dim3(arseg_grid_for(hw)), dim3(256), 0, st, ws, reinterpret_cast<unsigned *>(merged), hw);
+    hipLaunchKernelGGL(mv_records_fill_kernel, dim3(arseg_grid_for(hw)), dim3(256), 0, st, ws + hw, (unsigned *)nullptr, hw);
+    return arseg_launch_status();
+}
+
+extern "C" int arseg_mv_records_bi_step_fwd(const int16_t *records, int n_records, int16_t *merged, int f, int gop, uint64_t done_mask, int policy,
+                                            void *workspace, size_t workspace_bytes, int H, int W, int max_ref, arseg_stream_t stream) {
+    ARSEG_CHECK_PTR(merged);
+    const int bad = mvr_check_frame(records, n_records, workspace, workspace_bytes, H, W, 2);
+    if (bad) return bad;
+    if (max_ref < 1 || max_ref > 16 || f < 1 || f >= gop || gop > 64 || (reinterpret_cast<uintptr_t>(merged) & 3u)) return ARSEG_EINVAL;
+    if (!(done_mask & 1u) || ((done_mask >> f) & 1u) || (gop < 64 && (done_mask >> gop) != 0)) return ARSEG_EINVAL;
+    if (policy < ARSEG_MVR_BI_LIST0 || policy > ARSEG_MVR_BI_MEAN) return ARSEG_EINVAL;
+    hipStream_t st = arseg_stream(stream);
+    int *idx = reinterpret_cast<int *>(workspace);
+    const int hw = H * W;
+    const unsigned *m = reinterpret_cast<const unsigned *>(merged);
+    unsigned *out = reinterpret_cast<unsigned *>(merged) + (size_t)f * hw;
+    const unsigned long long done = done_mask;
+    mvr_scatter<true>(records, n_records, idx, H, W, st);
+    const int4 *rec = reinterpret_cast<const int4 *>(records);
+    if (hw % 4 == 0 && ARSEG_ALIGNED16(merged))
+        hipLaunchKernelGGL(mv_records_bi_compose_kernel<true>, dim3(arseg_grid_for(hw / 4)), dim3(256), 0, st, rec, n_records, idx, m, out, f, done, policy, H, W,
+                           max_ref);
+    else
+        hipLaunchKernelGGL(mv_records_bi_compose_kernel<false>, dim3(arseg_grid_for(hw)), dim3(256), 0, st, rec, n_records, idx, m, out, f, done, policy, H, W,
+                           max_ref);
     return arseg_launch_status();
 }

@@ -11,7 +11,9 @@
 * decoder motion as a decoder holds it: block records ``int16 [n,8]`` per P-frame (x, y, w, h, mvx, mvy, ref, reserved; the contract is in
   include/arseg_hip.h, arseg_mv_records_*).  ``MotionChain`` rasterises and chains them to the keyframe frame by frame on the GPU
   (csrc/mv_records.hip) into the ``mv_qs`` tensor the fast paths read; ``mv_to_records`` / ``records_to_dense`` convert the reference's
-  dense per-frame dumps to records and back on the host.
+  dense per-frame dumps to records and back on the host.  ``MotionChain(bidirectional=True)`` takes B-frames as well: two prediction lists
+  per frame, forward references, frames in decode order (arseg_mv_records_bi_*); ``chain_records_numpy`` is that rule on the host,
+  ``motion_vectors_to_records`` the mapping from ``AVMotionVector``-style arrays.
 """
 from __future__ import annotations
 
@@ -318,8 +320,123 @@ def pad_records(records, capacity: int) -> np.ndarray:
     return out
 
 
+def _as_int_array(v, name: str, n=None) -> np.ndarray:
+    a = np.asarray(v)
+    if a.dtype.kind not in "iu" and a.size:
+        raise ValueError(f"motion_vectors_to_records: {name} must hold integers, got {a.dtype}")
+    a = a.astype(np.int64)
+    if n is not None:
+        if a.ndim > 1 or (a.ndim == 1 and a.shape[0] != n):
+            raise ValueError(f"motion_vectors_to_records: {name} must be a scalar or hold {n} values, got shape {a.shape}")
+        a = np.broadcast_to(a, (n,))
+    return a
+
+
+def motion_vectors_to_records(dst_x, dst_y, w, h, motion_x, motion_y, motion_scale, offset, list_=0) -> np.ndarray:
+    """Motion vectors as FFmpeg's ``AVMotionVector`` side data holds them (centre of the block in the current frame, block size, displacement
+    to the reference in units of 1 / motion_scale pixel) -> block records int16 [n,8], integer arithmetic throughout:
+    ``x = dst_x - w // 2``, ``y = dst_y - h // 2``, ``mvx = 4 * motion_x / motion_scale`` rounded half to even (likewise mvy).  ``offset`` is the
+    signed display-order distance of the reference frame, negative = past: -k -> ``ref = k - 1``, +k -> ``ref = -k`` (the codes of
+    arseg_mv_records_bi_*; a P-only stream has only negative offsets and gives the records ``MotionChain`` always took).  ``list_`` (0 or 1) goes
+    into bit 0 of ``reserved``.  The first six arguments are integer arrays of one length n; motion_scale, offset and list_ are arrays of that
+    length or scalars.  ValueError: offset == 0, motion_scale <= 0, list_ outside {0, 1}, any resulting field outside int16."""
+    dst_x = _as_int_array(dst_x, "dst_x")
+    if dst_x.ndim != 1:
+        raise ValueError(f"motion_vectors_to_records: dst_x must be one-dimensional, got shape {dst_x.shape}")
+    n = dst_x.shape[0]
+    dst_y, w, h, motion_x, motion_y, motion_scale, offset, list_ = (_as_int_array(v, k, n) for k, v in (
+        ("dst_y", dst_y), ("w", w), ("h", h), ("motion_x", motion_x), ("motion_y", motion_y), ("motion_scale", motion_scale), ("offset", offset),
+        ("list_", list_)))
+    if (offset == 0).any():
+        raise ValueError("motion_vectors_to_records: offset 0 (a frame predicted from itself) has no record")
+    if (motion_scale <= 0).any():
+        raise ValueError("motion_vectors_to_records: motion_scale must be positive")
+    if ((list_ != 0) & (list_ != 1)).any():
+        raise ValueError("motion_vectors_to_records: list_ is 0 or 1")
+
+    def quarter(m):                                                      # 4 m / scale, half to even
+        q, r = np.divmod(4 * m, motion_scale)
+        return q + ((2 * r > motion_scale) | ((2 * r == motion_scale) & (q & 1 == 1)))
+
+    rec = np.stack([dst_x - w // 2, dst_y - h // 2, w, h, quarter(motion_x), quarter(motion_y), np.where(offset < 0, -offset - 1, -offset), list_], axis=1)
+    if rec.size and (rec.min() < -32768 or rec.max() > 32767):
+        raise ValueError("motion_vectors_to_records: a field does not fit int16")
+    return np.ascontiguousarray(rec.astype(np.int16))
+
+
+BIPRED = ("list0", "near", "mean")          # what a pixel reads when both of its lists are usable: ARSEG_MVR_BI_LIST0 / _NEAR / _MEAN
+
+
+def _round_half_even_div4(v):
+    b, r = v >> 2, v & 3
+    return b + ((r > 2) | ((r == 2) & (b & 1 == 1)))
+
+
+def chain_records_numpy(pushes, H: int, W: int, gop: int, max_ref: int = 3, bipred: str = "list0") -> np.ndarray:
+    """The two-list chain rule of include/arseg_hip.h (arseg_mv_records_bi_*) on the host, for callers without a GPU at hand: ``pushes`` is a
+    list of ``(f, records int16 [n,8])`` in decode order; returns ``merged`` int16 [gop,H,W,2] with frame 0 = -1 and frames never pushed = 0.
+    What ``MotionChain(bidirectional=True, bipred=bipred)`` leaves in ``merged`` after the same pushes."""
+    H, W, gop, max_ref = int(H), int(W), int(gop), int(max_ref)
+    if not (1 <= H <= 8192 and 1 <= W <= 8192) or not 2 <= gop <= 64 or not 1 <= max_ref <= 16 or bipred not in BIPRED:
+        raise ValueError(f"chain_records_numpy: H, W in 1..8192, gop in 2..64, max_ref in 1..16, bipred in {BIPRED}; got {H}x{W}, gop {gop}, "
+                         f"max_ref {max_ref}, bipred {bipred!r}")
+    merged = np.zeros((gop, H, W, 2), dtype=np.int64)
+    merged[0] = -1
+    done = np.zeros(gop + 17, dtype=bool)                               # a forward target reaches at most f + 16
+    done[0] = True
+    ys, xs = np.mgrid[0:H, 0:W]
+    for f, records in pushes:
+        r = np.asarray(records)
+        if r.dtype != np.int16 or r.ndim != 2 or r.shape[1] != 8:
+            raise ValueError(f"chain_records_numpy expects records as int16 [n,8], got {r.dtype} {r.shape}")
+        if not 1 <= f < gop or done[f]:
+            raise ValueError(f"chain_records_numpy: frame {f} is outside [1, {gop}) or was pushed twice")
+        r = r.astype(np.int64)
+        winner = np.full((2, H, W), -1, dtype=np.int64)
+        for i, (x, y, w, h) in enumerate(r[:, :4]):
+            if w <= 0 or h <= 0:
+                continue
+            x0, x1, y0, y1 = max(x, 0), min(x + w, W), max(y, 0), min(y + h, H)
+            if x0 < x1 and y0 < y1:
+                winner[r[i, 7] & 1, y0:y1, x0:x1] = i
+        usable, target, link = [], [], []
+        for l in (0, 1):
+            q = r[np.maximum(winner[l], 0)] if r.shape[0] else np.zeros((H, W, 8), dtype=np.int64)
+            ref = q[..., 6]
+            t = np.where(ref >= 0, np.maximum(0, f - ref - 1), f - ref)
+            ok = (winner[l] >= 0) & (ref >= -max_ref) & (ref < max_ref)
+            t = np.where(ok, t, 0)
+            k2 = np.clip(xs + _round_half_even_div4(q[..., 4]), 0, W - 1)
+            j2 = np.clip(ys + _round_half_even_div4(q[..., 5]), 0, H - 1)
+            d = 4 * np.stack([k2 - xs, j2 - ys], axis=-1)
+            ok &= done[t]
+            t = np.where(ok, t, 0)                                       # a target outside the GOP is never read
+            usable.append(ok)
+            target.append(t)
+            link.append(d + np.where((t > 0)[..., None], merged[t, j2, k2], 0))
+        p = int(np.nonzero(done[:f])[0].max())
+        out = np.broadcast_to(merged[p] if p > 0 else 0, (H, W, 2)).copy()
+        both = usable[0] & usable[1]
+        if bipred == "near":
+            first = ~both | (np.abs(target[0] - f) <= np.abs(target[1] - f))
+        else:
+            first = np.ones((H, W), dtype=bool)
+        use0 = usable[0] & first
+        use1 = usable[1] & ~use0
+        out[use1] = link[1][use1]
+        out[use0] = link[0][use0]
+        if bipred == "mean":
+            s = link[0] + link[1]
+            m = s >> 1
+            out[both] = (m + (s & 1 & m))[both]
+        merged[f] = out
+        done[f] = True
+    assert merged.min() >= -32768 and merged.max() <= 32767
+    return merged.astype(np.int16)
+
+
 class MotionChain(object):
-    """The motion half of a decoder's output on the GPU: block records of one P-frame at a time -> ``mv_q``, the int16 quarter-pel field
+    """The motion half of a decoder's output on the GPU: block records of one frame at a time -> ``mv_q``, the int16 quarter-pel field
     accumulated back to the keyframe (what mergeMotion writes into the datasets' .bin files).  Owns ``merged`` int16 [gop,H,W,2] and the
     int32 index map, both allocated once; ``push`` is two kernel launches and neither synchronises nor allocates, so a closure over a
     MotionChain and static (padded) record buffers can be captured in a HIP graph (``executor.GopGraph``).
@@ -328,25 +445,45 @@ class MotionChain(object):
         for each GOP:   chain.reset();  for each P-frame:  mv_q = chain.push(records)          # [H,W,2], a view of chain.merged[f]
         chain.mv_q()[1:]                       # [f,H,W,2]: the ``mv_qs`` of alter_res_batch_fast / alter_res_batch_pred / GopRunner
 
-    H, W <= 8192; max_ref as mergeMotion's constant 3 (reference indices >= max_ref are intra), 1..16."""
+    H, W <= 8192; max_ref as mergeMotion's constant 3 (reference indices >= max_ref are intra), 1..16.
 
-    def __init__(self, H: int, W: int, gop: int = 12, max_ref: int = 3, device="cuda"):
+    ``bidirectional=False``: P-frames only, one record per block, pushed in display order (arseg_mv_records_*).  ``bidirectional=True``: streams
+    with B-frames (arseg_mv_records_bi_*; gop <= 64, two index maps).  A record's ``reserved & 1`` is its prediction list, ``ref < 0`` points
+    forward in display order, and frames are pushed in DECODE order with their display index: ``push(records, at=f)``.  A reference to a frame
+    not pushed yet is unusable (the pixel falls to its other list, or to zero motion from the nearest pushed frame before it); ``bipred`` =
+    "list0" | "near" | "mean" decides a pixel both of whose lists are usable.  P-only records pushed in order give the same ``merged`` either way.
+
+        chain = MotionChain(H, W, gop=8, bidirectional=True, bipred="near")
+        chain.reset();  for f, records in decode_order:  chain.push(records, at=f)
+        chain.mv_q()[1:]                       # once frames 1..k are all in
+    """
+
+    def __init__(self, H: int, W: int, gop: int = 12, max_ref: int = 3, device="cuda", bidirectional: bool = False, bipred: str = "list0"):
         H, W, gop, max_ref = int(H), int(W), int(gop), int(max_ref)
         if not (1 <= H <= 8192 and 1 <= W <= 8192) or gop < 2 or not 1 <= max_ref <= 16:
             raise _lib.ArsegError(f"MotionChain: H, W in 1..8192, gop >= 2, max_ref in 1..16; got {H}x{W}, gop {gop}, max_ref {max_ref}")
+        if bipred not in BIPRED:
+            raise _lib.ArsegError(f"MotionChain: bipred is one of {BIPRED}, got {bipred!r}")
+        if bidirectional and gop > 64:
+            raise _lib.ArsegError(f"MotionChain: a bidirectional chain holds at most 64 frames (the done set is one 64-bit mask), got gop {gop}")
         self.H, self.W, self.gop, self.max_ref = H, W, gop, max_ref
+        self.bidirectional, self.bipred = bool(bidirectional), bipred
         self.device = torch.device(device)
         if self.device.type != "cuda":
             raise _lib.ArsegError("MotionChain runs on the GPU only; there is no CPU fallback (records_to_dense is the host restatement)")
         self.merged = torch.empty((gop, H, W, 2), dtype=torch.int16, device=self.device)
-        self.index_map = torch.empty(H * W, dtype=torch.int32, device=self.device)
-        self.f = 0
+        self.index_map = torch.empty((2 if self.bidirectional else 1) * H * W, dtype=torch.int32, device=self.device)
+        self.f = 0                      # in-order chain: the last frame pushed
+        self.done_mask = 1              # bidirectional chain: bit g = frame g is chained
         self.reset()
 
     def reset(self) -> None:
-        """Starts a GOP: frame 0 of ``merged`` = -1 (as ``ops.merge_motion`` leaves it), index map clean, no frame pushed."""
-        ops.mv_records_reset(self.merged, self.index_map)
-        self.f = 0
+        """Starts a GOP: frame 0 of ``merged`` = -1 (as ``ops.merge_motion`` leaves it), index map(s) clean, no frame pushed."""
+        if self.bidirectional:
+            ops.mv_records_bi_reset(self.merged, self.index_map)
+        else:
+            ops.mv_records_reset(self.merged, self.index_map)
+        self.f, self.done_mask = 0, 1
 
     def _records(self, records) -> torch.Tensor:
         if not torch.is_tensor(records):                      # host records: uploaded here (allocates; a graph wants device buffers)
@@ -356,22 +493,51 @@ class MotionChain(object):
             records = torch.from_numpy(r).to(self.device)
         return records
 
-    def push(self, records) -> torch.Tensor:
-        """The next P-frame's records (int16 [n,8] on the chain's device; n is the buffer's capacity, zero records are padding) -> its
-        mv_q int16 [H,W,2], the view ``merged[f]``.  Raises once gop - 1 frames have been pushed."""
-        if self.f >= self.gop - 1:
-            raise _lib.ArsegError(f"MotionChain: the GOP holds {self.gop - 1} P-frames and all were pushed; reset() starts the next one")
-        out = ops.mv_records_step(self._records(records), self.merged, self.f + 1, self.index_map, self.max_ref)
-        self.f += 1
+    def frames_done(self) -> tuple:
+        """The display indices chained so far in this GOP, sorted, the keyframe 0 included."""
+        if not self.bidirectional:
+            return tuple(range(self.f + 1))
+        return tuple(g for g in range(self.gop) if (self.done_mask >> g) & 1)
+
+    def push(self, records, at=None) -> torch.Tensor:
+        """One frame's records (int16 [n,8] on the chain's device; n is the buffer's capacity, zero records are padding) -> its mv_q int16
+        [H,W,2], the view ``merged[at]``.  ``at`` is the frame's display index in [1, gop); None = the lowest index not pushed yet (the next
+        frame of an in-order stream).  An in-order chain takes only that one.  Raises for an index outside the GOP or pushed before."""
+        if not self.bidirectional:
+            if self.f >= self.gop - 1:
+                raise _lib.ArsegError(f"MotionChain: the GOP holds {self.gop - 1} P-frames and all were pushed; reset() starts the next one")
+            if at is not None and int(at) != self.f + 1:
+                raise _lib.ArsegError(f"MotionChain: an in-order chain takes frame {self.f + 1} next, not {at}; bidirectional=True takes decode order")
+            out = ops.mv_records_step(self._records(records), self.merged, self.f + 1, self.index_map, self.max_ref)
+            self.f += 1
+            return out
+        if at is None:
+            at = next((g for g in range(1, self.gop) if not (self.done_mask >> g) & 1), self.gop)
+        at = int(at)
+        if not 1 <= at < self.gop:
+            raise _lib.ArsegError(f"MotionChain: frame {at} is outside [1, {self.gop}) (or every frame of the GOP was pushed); reset() starts the next GOP")
+        if (self.done_mask >> at) & 1:
+            raise _lib.ArsegError(f"MotionChain: frame {at} was pushed before in this GOP")
+        out = ops.mv_records_bi_step(self._records(records), self.merged, at, self.done_mask, self.index_map, self.max_ref, self.bipred)
+        self.done_mask |= 1 << at
         return out
 
-    def push_gop(self, list_of_records) -> torch.Tensor:
-        """reset() + one push per entry; returns ``mv_q()``."""
+    def push_gop(self, list_of_records, order=None) -> torch.Tensor:
+        """reset() + one push per entry; ``order`` = the display index of each entry (decode order; None: 1, 2, ...).  Returns ``mv_q()``."""
+        list_of_records = list(list_of_records)
+        if order is not None and len(order) != len(list_of_records):
+            raise _lib.ArsegError(f"MotionChain: {len(list_of_records)} record lists but {len(order)} display indices")
         self.reset()
-        for r in list_of_records:
-            self.push(r)
+        for i, r in enumerate(list_of_records):
+            self.push(r, None if order is None else order[i])
         return self.mv_q()
 
     def mv_q(self) -> torch.Tensor:
-        """int16 [f+1,H,W,2], a view: frame 0 = -1 (the keyframe has no motion field), frames 1..f as pushed."""
-        return self.merged[:self.f + 1]
+        """int16 [k+1,H,W,2], a view: frame 0 = -1 (the keyframe has no motion field), frames 1..k as pushed.  A bidirectional chain raises
+        while the frames pushed are not 1..k without a gap (``merged[g]`` of a frame not pushed is not motion); a complete GOP never is."""
+        if not self.bidirectional:
+            return self.merged[:self.f + 1]
+        k = bin(self.done_mask).count("1") - 1
+        if self.done_mask != (1 << (k + 1)) - 1:
+            raise _lib.ArsegError(f"MotionChain: frames {self.frames_done()} are chained, which is not 0..{k} without a gap; mv_q() is whole prefixes only")
+        return self.merged[:k + 1]

@@ -464,14 +464,15 @@ def _mv_records(records: torch.Tensor, what: str) -> int:
     return int(records.shape[0])
 
 
-def _mv_chain_state(merged: torch.Tensor, index_map: torch.Tensor, what: str):
+def _mv_chain_state(merged: torch.Tensor, index_map: torch.Tensor, what: str, maps: int = 1):
     if not torch.is_tensor(merged) or merged.dtype != torch.int16 or not merged.is_cuda or merged.dim() != 4 or merged.shape[-1] != 2 \
             or not merged.is_contiguous():
         raise _lib.ArsegError(f"{what} expects merged as a contiguous CUDA int16 tensor [gop,H,W,2]")
     gop, H, W, _ = merged.shape
     if not torch.is_tensor(index_map) or index_map.dtype != torch.int32 or index_map.device != merged.device or not index_map.is_contiguous() \
-            or index_map.numel() < H * W:
-        raise _lib.ArsegError(f"{what} expects the index map as a contiguous int32 tensor of at least H*W = {H * W} elements on merged's device")
+            or index_map.numel() < maps * H * W:
+        raise _lib.ArsegError(f"{what} expects the index map as a contiguous int32 tensor of at least {maps if maps > 1 else ''}H*W = {maps * H * W} elements on "
+                              f"merged's device")
     return gop, H, W
 
 
@@ -492,6 +493,37 @@ def mv_records_step(records: torch.Tensor, merged: torch.Tensor, f: int, index_m
         raise _lib.ArsegError(f"mv_records_step: records are on {records.device}, merged on {merged.device}")
     launch("mv_records_step", _lib.load().arseg_mv_records_step_fwd, _ptr(records), n, _ptr(merged), int(f), gop, _ptr(index_map), index_map.numel() * 4,
            H, W, int(max_ref), _stream())
+    return merged[f]
+
+
+MV_BI_POLICIES = {"list0": _lib.MVR_BI_LIST0, "near": _lib.MVR_BI_NEAR, "mean": _lib.MVR_BI_MEAN}
+
+
+def mv_records_bi_reset(merged: torch.Tensor, index_maps: torch.Tensor) -> None:
+    """Starts a GOP of the two-list (B-frame) record chain: both index maps = -1, merged[0] = -1.  merged int16 [gop,H,W,2], index_maps int32
+    of at least 2*H*W elements (list 0's map, then list 1's), both caller-owned on one GPU."""
+    _, H, W = _mv_chain_state(merged, index_maps, "mv_records_bi_reset", maps=2)
+    launch("mv_records_bi_reset", _lib.load().arseg_mv_records_bi_reset, _ptr(merged), _ptr(index_maps), index_maps.numel() * 4, H, W, _stream())
+
+
+def mv_records_bi_step(records: torch.Tensor, merged: torch.Tensor, f: int, done_mask: int, index_maps: torch.Tensor, max_ref: int = 3,
+                       policy="list0") -> torch.Tensor:
+    """One frame of the two-list record chain (include/arseg_hip.h, arseg_mv_records_bi_*): frame f of a GOP pushed in decode order, with
+    done_mask = the frames already chained (bit g = frame g; bit 0, the keyframe, always; bit f never).  A record's `reserved & 1` is its
+    prediction list, `ref < 0` points forward in display order; policy "list0" | "near" | "mean" decides a pixel both of whose lists are
+    usable.  Writes and returns the view merged[f]; two kernels, no synchronisation, no allocation."""
+    n = _mv_records(records, "mv_records_bi_step")
+    gop, H, W = _mv_chain_state(merged, index_maps, "mv_records_bi_step", maps=2)
+    if records.device != merged.device:
+        raise _lib.ArsegError(f"mv_records_bi_step: records are on {records.device}, merged on {merged.device}")
+    if policy not in MV_BI_POLICIES:
+        raise _lib.ArsegError(f"mv_records_bi_step: policy is one of {sorted(MV_BI_POLICIES)}, got {policy!r}")
+    f, done_mask = int(f), int(done_mask)
+    if gop > 64 or not 1 <= f < gop or not done_mask & 1 or (done_mask >> f) & 1 or done_mask < 0 or done_mask >> gop:
+        raise _lib.ArsegError(f"mv_records_bi_step: gop <= 64, f in [1, gop), done_mask with bit 0 set, bit f clear and no bit >= gop; got gop {gop}, "
+                              f"f {f}, done_mask {done_mask:#x}")
+    launch("mv_records_bi_step", _lib.load().arseg_mv_records_bi_step_fwd, _ptr(records), n, _ptr(merged), f, gop, done_mask,
+           MV_BI_POLICIES[policy], _ptr(index_maps), index_maps.numel() * 4, H, W, int(max_ref), _stream())
     return merged[f]
 
 

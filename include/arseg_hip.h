@@ -532,7 +532,8 @@ int arseg_merge_motion_fwd(const int16_t *flows, int16_t *out, void *workspace, 
  *                                     reset before it and is left at -1
  * workspace: 16-byte aligned, >= arseg_mv_records_workspace_bytes(H, W) bytes (else ARSEG_EWORKSPACE).
  * ARSEG_EINVAL: a null pointer, n_records < 0, H or W outside 1 .. 8192, max_ref outside 1 .. 16, f outside [1, gop), records or workspace
- * not 16-byte aligned, merged not 4-byte aligned.  B-frames (two records per block) are not covered: mergeMotion has no rule for them.
+ * not 16-byte aligned, merged not 4-byte aligned.  B-frames (two records per block, forward references, decode order) are outside these
+ * entry points: arseg_mv_records_bi_* below take them.
  * ------------------------------------------------------------------------------------------- */
 size_t arseg_mv_records_workspace_bytes(int H, int W);
 int arseg_mv_records_reset(int16_t *merged, void *workspace, size_t workspace_bytes, int H, int W, arseg_stream_t stream);
@@ -540,6 +541,45 @@ int arseg_mv_records_step_fwd(const int16_t *records, int n_records, int16_t *me
                               int H, int W, int max_ref, arseg_stream_t stream);
 int arseg_mv_records_rasterize_fwd(const int16_t *records, int n_records, int16_t *dense_out, void *workspace, size_t workspace_bytes, int H,
                                    int W, arseg_stream_t stream);
+
+/* ---------------------------------------------------------------------------------------------
+ * B-frame motion records: two prediction lists per frame, references before and after the frame, frames pushed in DECODE order
+ * (csrc/mv_records.hip).  mergeMotion has no rule for this case; the rule below is this library's, written so that a P-only stream pushed
+ * in display order gives arseg_mv_records_step_fwd's result bit for bit under every policy.
+ *   record      the same 16 bytes; two fields read differently:
+ *                 ref       signed display-order offset code from frame f: 0 <= ref < max_ref -> target t = max(0, f - ref - 1) as above;
+ *                           -max_ref <= ref < 0 -> t = f - ref (-1 = the next frame in display order); any other value: the record is UNUSABLE
+ *                 reserved  bit 0 = the prediction list (0 or 1), every other bit ignored.  A list is not a direction: list 0 may point
+ *                           forward, list 1 backward, both the same way (low-delay B)
+ * Per frame f, pushed with the set D of frames already chained in this GOP (done_mask: bit g set = g in D; 0 in D always, f not in D):
+ *   - per list l the winner at a pixel is the HIGHEST record index among the records of that list covering it; clipping, w <= 0 or h <= 0
+ *     padding and off-frame positions exactly as in the rasterisation rules above
+ *   - a winner is USABLE if its ref is in range and its target t_l is in D.  An unusable winner does not fall back to a lower index (as an
+ *     intra record covers pixels above)
+ *   - link_l = 4 (k2 - x, j2 - y) + (t_l > 0 ? merged[t_l][j2][k2] : (0, 0)),  k2 = clamp(x + round(mvx / 4), 0, W - 1), j2 likewise, round = half to even
+ *   - exactly one list usable: merged[f][y][x] = that list's link
+ *   - neither usable (intra): p = max{g in D : g < f}, merged[f][y][x] = p > 0 ? merged[p][y][x] : (0, 0) -- zero motion to the nearest chained
+ *     frame before f; with in-order pushes the intra rule above
+ *   - both usable, by `policy`:
+ *       ARSEG_MVR_BI_LIST0  link_0
+ *       ARSEG_MVR_BI_NEAR   the list with the smaller |t_l - f|, a tie goes to list 0
+ *       ARSEG_MVR_BI_MEAN   per component (link_0 + link_1) / 2 rounded half to even (int16 and inside the frame because both ends are)
+ * Entry points (enqueue only: no host synchronisation, no allocation):
+ *   arseg_mv_records_bi_workspace_bytes  two int32 index maps, one per list: 8 H W bytes (0 for a size outside 1 .. 8192)
+ *   arseg_mv_records_bi_reset            starts a GOP: both maps = -1, merged[0] = -1
+ *   arseg_mv_records_bi_step_fwd         one frame f in [1, gop): reads merged[t] for t in D, writes merged[f], leaves both maps at -1.  Two
+ *                                        launches.  done_mask is a kernel argument: a captured HIP graph replays one fixed decode order, which
+ *                                        is what a GOP structure is.  merged, records, workspace alignment and n_records as above
+ * ARSEG_EINVAL before any launch: everything arseg_mv_records_step_fwd refuses; gop > 64; bit 0 of done_mask clear; bit f of done_mask set; a
+ * bit >= gop of done_mask set; policy outside 0 .. 2.  ARSEG_EWORKSPACE: workspace_bytes below arseg_mv_records_bi_workspace_bytes(H, W).
+ * Not covered: open GOPs (references across a keyframe), choosing the path with the fewest hops to the keyframe, weighted prediction, more
+ * than one keyframe per chain.
+ * ------------------------------------------------------------------------------------------- */
+enum arseg_mvr_bi_policy { ARSEG_MVR_BI_LIST0 = 0, ARSEG_MVR_BI_NEAR = 1, ARSEG_MVR_BI_MEAN = 2 };
+size_t arseg_mv_records_bi_workspace_bytes(int H, int W);
+int arseg_mv_records_bi_reset(int16_t *merged, void *workspace, size_t workspace_bytes, int H, int W, arseg_stream_t stream);
+int arseg_mv_records_bi_step_fwd(const int16_t *records, int n_records, int16_t *merged, int f, int gop, uint64_t done_mask, int policy,
+                                 void *workspace, size_t workspace_bytes, int H, int W, int max_ref, arseg_stream_t stream);
 /* layout changes at the API boundary */
 int arseg_nchw_to_nhwc_fwd(const float *in, float *out, int N, int C, int HW, int out_ld, arseg_stream_t stream);
 int arseg_nhwc_to_nchw_fwd(const float *in, int in_ld, float *out, int N, int C, int HW, arseg_stream_t stream);
