@@ -2,6 +2,7 @@
 #pragma once
 #include <hip/hip_runtime.h>
 #include <stdint.h>
+#include <type_traits>
 #include "arseg_hip.h"
 
 #define ARSEG_CHECK_PTR(p) do { if ((p) == nullptr) return ARSEG_EINVAL; } while (0)
@@ -44,6 +45,14 @@ static inline int arseg_allow_smem(ArsegSmemAttr &a, const void *kernel, size_t 
     if (e != hipSuccess) return (int)e;
     if (known) a.granted[dev] = smem;
     return ARSEG_OK;
+}
+
+// A runtime 16-bit storage dtype as a template argument: launch(std::integral_constant<int, DT>) -> status, ARSEG_EINVAL for any other dtype
+template <class F>
+static inline int arseg_dispatch16(int dtype, F &&launch) {
+    if (dtype == ARSEG_DT_BF16) return launch(std::integral_constant<int, ARSEG_DT_BF16>{});
+    if (dtype == ARSEG_DT_F16) return launch(std::integral_constant<int, ARSEG_DT_F16>{});
+    return ARSEG_EINVAL;
 }
 
 typedef float f32x4 __attribute__((ext_vector_type(4)));

@@ -92,6 +92,49 @@ __device__ __forceinline__ double uniform_f64(double x) {
     return __builtin_bit_cast(double, ((unsigned long long)hi << 32) | lo);
 }
 
+// ------------------------------------------------------------------ NHWC element storage of the small layers (layers.hip, warp.hip)
+// One lane moves a 16-byte channel vector: V = 4 fp32 or 8 fp16 / bf16 channels.  Arithmetic is fp32 in both storages; a 16-bit store rounds
+// once, to nearest even.  The pyramid cells and bins take 4 channels per lane in both storages (ld4 / st4: 16 or 8 bytes).
+template <int DT>           // enum arseg_dtype: ARSEG_DT_F16 | ARSEG_DT_BF16 (fp32: the specialisation below)
+struct ArsegStore {
+    static constexpr bool BF = DT == ARSEG_DT_BF16;
+    using T = uint16_t;
+    static constexpr int V = 8, SH = 3;          // channels per lane, log2 V
+    static __device__ __forceinline__ void ld(const T *p, float (&f)[8]) {
+        const u32x4 v = *reinterpret_cast<const u32x4 *>(p);
+#pragma unroll
+        for (int e = 0; e < 4; ++e) { f[2 * e] = arseg_h2f<BF>((uint16_t)(v[e] & 0xffffu)); f[2 * e + 1] = arseg_h2f<BF>((uint16_t)(v[e] >> 16)); }
+    }
+    static __device__ __forceinline__ void st(T *p, const float (&f)[8]) {
+        u32x4 v;
+#pragma unroll
+        for (int e = 0; e < 4; ++e) v[e] = (unsigned)arseg_f2h<BF>(f[2 * e]) | ((unsigned)arseg_f2h<BF>(f[2 * e + 1]) << 16);
+        *reinterpret_cast<u32x4 *>(p) = v;
+    }
+    static __device__ __forceinline__ void cp(T *dst, const T *src) { *reinterpret_cast<u32x4 *>(dst) = *reinterpret_cast<const u32x4 *>(src); }     // bits, unconverted
+    static __device__ __forceinline__ f32x4 ld4(const T *p) {
+        const u32x2 v = *reinterpret_cast<const u32x2 *>(p);
+        return f32x4{arseg_h2f<BF>((uint16_t)(v.x & 0xffffu)), arseg_h2f<BF>((uint16_t)(v.x >> 16)), arseg_h2f<BF>((uint16_t)(v.y & 0xffffu)),
+                     arseg_h2f<BF>((uint16_t)(v.y >> 16))};
+    }
+    static __device__ __forceinline__ void st4(T *p, const f32x4 f) {
+        *reinterpret_cast<u32x2 *>(p) = u32x2{arseg_f2h<BF>(f[0]) | ((unsigned)arseg_f2h<BF>(f[1]) << 16), arseg_f2h<BF>(f[2]) | ((unsigned)arseg_f2h<BF>(f[3]) << 16)};
+    }
+};
+template <>
+struct ArsegStore<ARSEG_DT_F32> {
+    using T = float;
+    static constexpr int V = 4, SH = 2;
+    static __device__ __forceinline__ void ld(const T *p, float (&f)[4]) {
+        const f32x4 v = *reinterpret_cast<const f32x4 *>(p);
+        f[0] = v[0]; f[1] = v[1]; f[2] = v[2]; f[3] = v[3];
+    }
+    static __device__ __forceinline__ void st(T *p, const float (&f)[4]) { *reinterpret_cast<f32x4 *>(p) = f32x4{f[0], f[1], f[2], f[3]}; }
+    static __device__ __forceinline__ void cp(T *dst, const T *src) { *reinterpret_cast<f32x4 *>(dst) = *reinterpret_cast<const f32x4 *>(src); }
+    static __device__ __forceinline__ f32x4 ld4(const T *p) { return *reinterpret_cast<const f32x4 *>(p); }
+    static __device__ __forceinline__ void st4(T *p, const f32x4 f) { *reinterpret_cast<f32x4 *>(p) = f; }
+};
+
 // ------------------------------------------------------------------ byte spans of the 8-bit output planes (egress.hip, confidence.hip)
 typedef unsigned u32x2_a4 __attribute__((ext_vector_type(2), aligned(4)));
 

@@ -253,8 +253,8 @@ __global__ __launch_bounds__(256) void conv16_kernel(const Conv16Params p) {
 //
 // UP2: the conv input is the x2 bilinear (align_corners=False) upsample of `p.in` [N, H/2, W/2, in_ld] (PSPUpsample, model/pspnet.py:43-46),
 // never materialised.  Per chunk the low-resolution window of the tile ((TH/2+2) x (TW/2+2) pixels, a quarter of the patch's bytes) is
-// fetched into registers, stored to LDS, and every patch pixel is interpolated from it with resize16_kernel's source-index helper, fp32
-// expression and single rounding (layers16.hip), so the staged values -- and the conv -- equal resize16 -> conv2d16 bit for bit.  Dilation 1.
+// fetched into registers, stored to LDS, and every patch pixel is interpolated from it with resize_nhwc_kernel's source-index helper, fp32
+// expression and single rounding (layers.hip), so the staged values -- and the conv -- equal resize16 -> conv2d16 bit for bit.  Dilation 1.
 template <bool BF, int BN, int WM, bool UP2>      // WM wave rows of 64 output pixels each: BM = 64*WM pixels, 2*WM waves
 __global__ __launch_bounds__(128 * WM, (BN == 64 ? 4 : 2)) void conv16_patch_kernel(const Conv16Params p) {
     constexpr int ROWB = 144;                          // bytes per LDS row: 64 halves + pad (conflict-free b128 reads)
@@ -345,7 +345,7 @@ __global__ __launch_bounds__(128 * WM, (BN == 64 ? 4 : 2)) void conv16_patch_ker
                 const int gy = ty0 - 1 + py, gx = tx0 - 1 + pxx;
                 u32x4 o = {0u, 0u, 0u, 0u};                                   // conv padding outside the upsampled image
                 if ((unsigned)gy < (unsigned)p.H && (unsigned)gx < (unsigned)p.W) {
-                    // resize16_kernel (layers16.hip), bilinear, align_corners = 0: the same index helper, clamps, expression and rounding
+                    // resize_nhwc_kernel (layers.hip), bilinear, align_corners = 0: the same index helper, clamps, expression and rounding
                     int y0, y1, x0, x1; float ly, lx;
                     arseg_src_index(sy, gy, false, h, y0, y1, ly);
                     arseg_src_index(sx, gx, false, w, x0, x1, lx);

@@ -193,7 +193,7 @@ __global__ __launch_bounds__(256) void ingest_kernel(const IngestP p) {
     }
 }
 
-// ------------------------------------------------------------------ row-staged form (the twin of frame_to_nhwc8_rows_kernel, csrc/layers16.hip)
+// ------------------------------------------------------------------ row-staged form (the twin of frame_to_nhwc_rows_kernel, csrc/layers.hip)
 // One workgroup = 256 consecutive output pixels of one output row.  Per source row under it (two; one at identity size) LDS holds the
 // plane-0 row over the pixels' x span and, for YUV, its NC chroma rows over columns xa / 2 .. xe1 / 2 + 1, staged with coalesced 4-byte loads
 // (a per-pixel gather of 3-byte pixels / chroma samples is not); the taps come from there, every lane stores 16 bytes.  Needs 4-byte aligned

@@ -3,33 +3,39 @@
 // head, frame ingest (downscale + NCHW -> NHWC4), layout changes and the evaluator tail.
 // All of them are HBM/L2-bound element-wise or small-window kernels: 16-byte channel vectors per
 // lane (coalesced along C), grid-stride loops, no MFMA.
+// The kernels that exist in both storages (fp32, and fp16 / bf16 of BASELINE configs[2] / configs[4]) are written once over ArsegStore<DT>
+// (arseg_device.h): 4 or 8 channels per lane, fp32 arithmetic, one rounding at a 16-bit store.
 #include "arseg_device.h"
 
 namespace {
 
 // ------------------------------------------------------------------ MaxPool2d(3, 2, 1)
-__global__ __launch_bounds__(256) void maxpool3x3s2_kernel(const float *__restrict__ in, float *__restrict__ out, int N,
-                                                           int H, int W, int C, int Ho, int Wo) {
-    const int c4n = C >> 2;
-    const long long total = (long long)N * Ho * Wo * c4n;
+template <int DT>
+__global__ __launch_bounds__(256) void maxpool3x3s2_kernel(const typename ArsegStore<DT>::T *__restrict__ in, typename ArsegStore<DT>::T *__restrict__ out,
+                                                           int N, int H, int W, int C, int Ho, int Wo) {
+    using S = ArsegStore<DT>;
+    const int cvn = C >> S::SH;
+    const long long total = (long long)N * Ho * Wo * cvn;
     for (long long idx = (long long)blockIdx.x * blockDim.x + threadIdx.x; idx < total; idx += (long long)gridDim.x * blockDim.x) {
-        const int c = (int)(idx % c4n) * 4;
-        const long long pix = idx / c4n;
+        const int c = (int)(idx % cvn) * S::V;
+        const long long pix = idx / cvn;
         const int ox = (int)(pix % Wo), oy = (int)((pix / Wo) % Ho), n = (int)(pix / ((long long)Wo * Ho));
-        f32x4 m = {-INFINITY, -INFINITY, -INFINITY, -INFINITY};
+        float m[S::V];
 #pragma unroll
+        for (int e = 0; e < S::V; ++e) m[e] = -INFINITY;
         for (int dy = 0; dy < 3; ++dy) {
             const int iy = oy * 2 - 1 + dy;
             if ((unsigned)iy >= (unsigned)H) continue;
-#pragma unroll
             for (int dx = 0; dx < 3; ++dx) {
                 const int ix = ox * 2 - 1 + dx;
                 if ((unsigned)ix >= (unsigned)W) continue;
-                const f32x4 v = *reinterpret_cast<const f32x4 *>(in + (((size_t)n * H + iy) * W + ix) * C + c);
-                m[0] = fmaxf(m[0], v[0]); m[1] = fmaxf(m[1], v[1]); m[2] = fmaxf(m[2], v[2]); m[3] = fmaxf(m[3], v[3]);
+                float f[S::V];
+                S::ld(in + (((size_t)n * H + iy) * W + ix) * C + c, f);
+#pragma unroll
+                for (int e = 0; e < S::V; ++e) m[e] = fmaxf(m[e], f[e]);
             }
         }
-        *reinterpret_cast<f32x4 *>(out + pix * C + c) = m;
+        S::st(out + pix * C + c, m);
     }
 }
 
@@ -127,14 +133,95 @@ __global__ __launch_bounds__(256) void global_combine_kernel(const float *__rest
     *reinterpret_cast<f32x4 *>(out + (size_t)n * C + c) = acc;
 }
 
-// ------------------------------------------------------------------ pyramid pooling in one pass over the map (PSPModule, model/pspnet.py:14-31)
+// ------------------------------------------------------------------ global mean / max of 16-bit maps: fp32 partials of pixel slices, then the result
+// (a different algorithm from the fp32 kernels above: slices of pixels and a final pass over the slices.)  The max widens to fp32 exactly and
+// narrows back exactly -- it is one of the inputs -- and a NaN wins (fmaxf would drop it): max_nan keeps the first NaN met.
+__device__ __forceinline__ float max_nan(float m, float f) { return (f > m || f != f) ? f : m; }
+template <bool IS_MAX> __device__ __forceinline__ float slice_op(float a, float f) { return IS_MAX ? max_nan(a, f) : a + f; }
+
+// step 1: grid (C/256 blocks of 32 channel vectors, N, S slices); block = 32 channel vectors x 8 pixel lanes; part[n][s][c] fp32
+template <int DT, bool IS_MAX>
+__global__ __launch_bounds__(256) void global_slices16_kernel(const uint16_t *__restrict__ in, int in_ld, float *__restrict__ part, int HW, int C, int S) {
+    __shared__ float red[8][32][8];
+    const int n = blockIdx.y, sl = blockIdx.z, cv = blockIdx.x * 32 + (threadIdx.x & 31), pl = threadIdx.x >> 5;
+    const int per = (HW + S - 1) / S, p0 = sl * per, p1 = min(p0 + per, HW);
+    const float e0 = IS_MAX ? -INFINITY : 0.f;
+    float acc[8] = {e0, e0, e0, e0, e0, e0, e0, e0};
+    if (cv * 8 < C) {
+        const uint16_t *base = in + (size_t)n * HW * in_ld + cv * 8;
+        for (int px = p0 + pl; px < p1; px += 8) {
+            float f[8];
+            ArsegStore<DT>::ld(base + (size_t)px * in_ld, f);
+#pragma unroll
+            for (int e = 0; e < 8; ++e) acc[e] = slice_op<IS_MAX>(acc[e], f[e]);
+        }
+    }
+#pragma unroll
+    for (int e = 0; e < 8; ++e) red[pl][threadIdx.x & 31][e] = acc[e];
+    __syncthreads();
+    if (pl == 0 && cv * 8 < C) {
+        float *o = part + ((size_t)n * S + sl) * C + cv * 8;
+#pragma unroll
+        for (int e = 0; e < 8; ++e) {
+            float t = e0;
+#pragma unroll
+            for (int k = 0; k < 8; ++k) t = slice_op<IS_MAX>(t, red[k][threadIdx.x & 31][e]);
+            o[e] = t;
+        }
+    }
+}
+// step 2: out[n][c] = sum_s part[n][s][c] * inv (or the max over s).  8 lanes per (n, c) take every 8th slice, their results are combined in
+// lane order (a fixed order: deterministic); one thread per (n, c) walking all S slices was a chain of S dependent-latency loads (60 us at S = 1024).
+template <int DT, bool IS_MAX>
+__global__ __launch_bounds__(256) void global_fin16_kernel(const float *__restrict__ part, uint16_t *__restrict__ out, int N, int C, int S, float inv) {
+    __shared__ float red[8][32];
+    const int i = blockIdx.x * 32 + (threadIdx.x & 31), k = threadIdx.x >> 5;
+    float t = IS_MAX ? -INFINITY : 0.f;
+    if (i < N * C) {
+        const int n = i / C, c = i - n * C;
+        for (int s = k; s < S; s += 8) t = slice_op<IS_MAX>(t, part[((size_t)n * S + s) * C + c]);
+    }
+    red[k][threadIdx.x & 31] = t;
+    __syncthreads();
+    if (k == 0 && i < N * C) {
+        float a = IS_MAX ? -INFINITY : 0.f;
+#pragma unroll
+        for (int j = 0; j < 8; ++j) a = slice_op<IS_MAX>(a, red[j][threadIdx.x]);
+        out[i] = arseg_f2h<DT == ARSEG_DT_BF16>(IS_MAX ? a : a * inv);
+    }
+}
+
+// ------------------------------------------------------------------ element type conversion (fp32 <-> 16-bit), 8 elements per thread
+template <int DT>
+__global__ __launch_bounds__(256) void cast_to32_kernel(const uint16_t *__restrict__ in, float *__restrict__ out, long long n8) {
+    for (long long i = (long long)blockIdx.x * blockDim.x + threadIdx.x; i < n8; i += (long long)gridDim.x * blockDim.x) {
+        float f[8];
+        ArsegStore<DT>::ld(in + i * 8, f);
+        *reinterpret_cast<f32x4 *>(out + i * 8) = f32x4{f[0], f[1], f[2], f[3]};
+        *reinterpret_cast<f32x4 *>(out + i * 8 + 4) = f32x4{f[4], f[5], f[6], f[7]};
+    }
+}
+template <int DT>
+__global__ __launch_bounds__(256) void cast_to16_kernel(const float *__restrict__ in, uint16_t *__restrict__ out, long long n8) {
+    for (long long i = (long long)blockIdx.x * blockDim.x + threadIdx.x; i < n8; i += (long long)gridDim.x * blockDim.x) {
+        const f32x4 a = *reinterpret_cast<const f32x4 *>(in + i * 8), b = *reinterpret_cast<const f32x4 *>(in + i * 8 + 4);
+        const float f[8] = {a[0], a[1], a[2], a[3], b[0], b[1], b[2], b[3]};
+        ArsegStore<DT>::st(out + i * 8, f);
+    }
+}
+
+// ------------------------------------------------------------------ pyramid pooling in one pass over the map// ------------------------------------------------------------------ pyramid pooling in one pass over the map (PSPModule, model/pspnet.py:14-31)
 // The adaptive-average bins of the pyramid levels overlap within a level (H not divisible by s) and across levels, but every bin is a union of
 // cells of the grid spanned by ALL bin edges of all levels (<= 25 edges per axis).  Stage 1 sums every cell (each pixel is read exactly once: the
 // four per-level launches read the map four times, 184 MB instead of 46 MB for the 11-frame LR batch), stage 2 adds the cells of a bin, divides
 // by its pixel count and writes the block-structured row (its level's column block, zeros in the sibling blocks).
 struct PoolGrid { int ny, nx, nlev, rows; int ey[26], ex[26]; int size[4], off[4]; };
 
-__global__ __launch_bounds__(256) void psp_cells_kernel(const float *__restrict__ in, int in_ld, float *__restrict__ cells, int H, int W, int C, PoolGrid g) {
+// (16-bit storage, model/pspnet.py: the same cells and bins, 4 channels = 8 bytes per lane, fp32 cell sums in the workspace, one rounding per
+// element of the pooled matrix, zeros of the sibling blocks included)
+template <int DT>
+__global__ __launch_bounds__(256) void psp_cells_kernel(const typename ArsegStore<DT>::T *__restrict__ in, int in_ld, float *__restrict__ cells, int H, int W, int C,
+                                                        PoolGrid g) {
     __shared__ f32x4 red[16][17];
     const int cell = blockIdx.x, cy = cell / g.nx, cx = cell - cy * g.nx, n = blockIdx.z;
     const int y0 = g.ey[cy], y1 = g.ey[cy + 1], x0 = g.ex[cx], x1 = g.ex[cx + 1];
@@ -144,7 +231,7 @@ __global__ __launch_bounds__(256) void psp_cells_kernel(const float *__restrict_
     if (c < C)
         for (int i = pl; i < cnt; i += 16) {
             const int yy = y0 + i / ww, xx = x0 + i % ww;
-            acc += *reinterpret_cast<const f32x4 *>(in + (((size_t)n * H + yy) * W + xx) * in_ld + c);
+            acc += ArsegStore<DT>::ld4(in + (((size_t)n * H + yy) * W + xx) * in_ld + c);
         }
     red[pl][cv] = acc;
     __syncthreads();
@@ -156,7 +243,8 @@ __global__ __launch_bounds__(256) void psp_cells_kernel(const float *__restrict_
     if (pl == 0 && c < C) *reinterpret_cast<f32x4 *>(cells + ((size_t)n * g.ny * g.nx + cell) * C + c) = red[0][cv];
 }
 
-__global__ __launch_bounds__(256) void psp_bins_kernel(const float *__restrict__ cells, float *__restrict__ out, int H, int W, int C, PoolGrid g) {
+template <int DT>
+__global__ __launch_bounds__(256) void psp_bins_kernel(const float *__restrict__ cells, typename ArsegStore<DT>::T *__restrict__ out, int H, int W, int C, PoolGrid g) {
     const int row = blockIdx.x, n = blockIdx.y;
     int lev = 0;
     while (lev + 1 < g.nlev && row >= g.off[lev + 1]) ++lev;
@@ -164,7 +252,7 @@ __global__ __launch_bounds__(256) void psp_bins_kernel(const float *__restrict__
     const int y0 = (by * H) / s, y1 = ((by + 1) * H + s - 1) / s, x0 = (bx * W) / s, x1 = ((bx + 1) * W + s - 1) / s;
     const float inv = 1.0f / (float)((y1 - y0) * (x1 - x0));
     const float *cn = cells + (size_t)n * g.ny * g.nx * C;
-    float *o = out + ((size_t)n * g.rows + row) * ((size_t)g.nlev * C);
+    typename ArsegStore<DT>::T *o = out + ((size_t)n * g.rows + row) * ((size_t)g.nlev * C);
     // the cells of a bin are a rectangle of the cell grid (both are cut at the same edges): no tests inside the loops, four loads in flight
     int cy0 = 0, cy1 = g.ny, cx0 = 0, cx1 = g.nx;
     while (g.ey[cy0] < y0) ++cy0;
@@ -181,98 +269,56 @@ __global__ __launch_bounds__(256) void psp_bins_kernel(const float *__restrict__
             a0 += v0; a1 += v1; a2 += v2; a3 += v3;
         }
         for (; i < nc; ++i) a0 += cell(i);
-        const f32x4 acc = (a0 + a1) + (a2 + a3);
-        for (int j = 0; j < g.nlev; ++j) *reinterpret_cast<f32x4 *>(o + (size_t)j * C + c) = j == lev ? acc * inv : f32x4{0.f, 0.f, 0.f, 0.f};
-    }
-}
-
-// 16-bit twins (the storage path of model/pspnet.py): the same cells and bins, 16-bit input read 4 channels (8 bytes) per lane, fp32 cell sums in
-// the workspace, one rounding per element of the pooled matrix (zeros of the sibling blocks included).
-template <bool BF>
-__global__ __launch_bounds__(256) void psp_cells16_kernel(const uint16_t *__restrict__ in, int in_ld, float *__restrict__ cells, int H, int W, int C, PoolGrid g) {
-    __shared__ f32x4 red[16][17];
-    const int cell = blockIdx.x, cy = cell / g.nx, cx = cell - cy * g.nx, n = blockIdx.z;
-    const int y0 = g.ey[cy], y1 = g.ey[cy + 1], x0 = g.ex[cx], x1 = g.ex[cx + 1];
-    const int cv = threadIdx.x & 15, pl = threadIdx.x >> 4, c = blockIdx.y * 64 + cv * 4;
-    const int ww = x1 - x0, cnt = (y1 - y0) * ww;
-    f32x4 acc = {0.f, 0.f, 0.f, 0.f};
-    if (c < C)
-        for (int i = pl; i < cnt; i += 16) {
-            const int yy = y0 + i / ww, xx = x0 + i % ww;
-            const uint2 v = *reinterpret_cast<const uint2 *>(in + (((size_t)n * H + yy) * W + xx) * in_ld + c);
-            acc += f32x4{arseg_h2f<BF>((uint16_t)(v.x & 0xffffu)), arseg_h2f<BF>((uint16_t)(v.x >> 16)), arseg_h2f<BF>((uint16_t)(v.y & 0xffffu)),
-                         arseg_h2f<BF>((uint16_t)(v.y >> 16))};
-        }
-    red[pl][cv] = acc;
-    __syncthreads();
-#pragma unroll
-    for (int s = 8; s >= 1; s >>= 1) {
-        if (pl < s) red[pl][cv] += red[pl + s][cv];
-        __syncthreads();
-    }
-    if (pl == 0 && c < C) *reinterpret_cast<f32x4 *>(cells + ((size_t)n * g.ny * g.nx + cell) * C + c) = red[0][cv];
-}
-
-template <bool BF>
-__global__ __launch_bounds__(256) void psp_bins16_kernel(const float *__restrict__ cells, uint16_t *__restrict__ out, int H, int W, int C, PoolGrid g) {
-    const int row = blockIdx.x, n = blockIdx.y;
-    int lev = 0;
-    while (lev + 1 < g.nlev && row >= g.off[lev + 1]) ++lev;
-    const int s = g.size[lev], b = row - g.off[lev], by = b / s, bx = b - by * s;
-    const int y0 = (by * H) / s, y1 = ((by + 1) * H + s - 1) / s, x0 = (bx * W) / s, x1 = ((bx + 1) * W + s - 1) / s;
-    const float inv = 1.0f / (float)((y1 - y0) * (x1 - x0));
-    const float *cn = cells + (size_t)n * g.ny * g.nx * C;
-    uint16_t *o = out + ((size_t)n * g.rows + row) * ((size_t)g.nlev * C);
-    int cy0 = 0, cy1 = g.ny, cx0 = 0, cx1 = g.nx;
-    while (g.ey[cy0] < y0) ++cy0;
-    while (g.ey[cy1] > y1) --cy1;
-    while (g.ex[cx0] < x0) ++cx0;
-    while (g.ex[cx1] > x1) --cx1;
-    const int nc = (cy1 - cy0) * (cx1 - cx0), cw = cx1 - cx0;
-    for (int c = threadIdx.x * 4; c < C; c += 1024) {
-        f32x4 a0 = {0.f, 0.f, 0.f, 0.f}, a1 = a0, a2 = a0, a3 = a0;
-        auto cell = [&](int i) { return *reinterpret_cast<const f32x4 *>(cn + (size_t)((cy0 + i / cw) * g.nx + cx0 + i % cw) * C + c); };
-        int i = 0;
-        for (; i + 4 <= nc; i += 4) {
-            const f32x4 v0 = cell(i), v1 = cell(i + 1), v2 = cell(i + 2), v3 = cell(i + 3);
-            a0 += v0; a1 += v1; a2 += v2; a3 += v3;
-        }
-        for (; i < nc; ++i) a0 += cell(i);
         const f32x4 acc = ((a0 + a1) + (a2 + a3)) * inv;
-        const uint2 v = {arseg_f2h<BF>(acc[0]) | ((unsigned)arseg_f2h<BF>(acc[1]) << 16), arseg_f2h<BF>(acc[2]) | ((unsigned)arseg_f2h<BF>(acc[3]) << 16)};
-        for (int j = 0; j < g.nlev; ++j) *reinterpret_cast<uint2 *>(o + (size_t)j * C + c) = j == lev ? v : uint2{0u, 0u};
+        for (int j = 0; j < g.nlev; ++j) ArsegStore<DT>::st4(o + (size_t)j * C + c, j == lev ? acc : f32x4{0.f, 0.f, 0.f, 0.f});
     }
 }
 
 // ------------------------------------------------------------------ resize
-__global__ __launch_bounds__(256) void resize_nhwc_kernel(const float *__restrict__ in, float *__restrict__ out, int N, int C,
-                                                          int Hin, int Win, int Hout, int Wout, int mode, int align, int in_ld,
-                                                          int out_ld) {
-    const int c4n = C >> 2;
-    const long long total = (long long)N * Hout * Wout * c4n;
+// The bilinear blend of a lane's channel vector keeps the form it has always had in each storage: one vector expression in fp32 storage
+// (bilerp4: v = or += the blend of the four taps), a loop over the eight converted elements in 16-bit storage.  hipcc contracts the two forms
+// into different FMA chains, which differ in the last bit for some inputs with align_corners = 0 -- one form for both would move results.
+template <bool ACC>
+__device__ __forceinline__ void bilerp4(const float (&a)[4], const float (&b)[4], const float (&cc)[4], const float (&d)[4], float ly, float lx, float (&v)[4]) {
+    const f32x4 a4 = {a[0], a[1], a[2], a[3]}, b4 = {b[0], b[1], b[2], b[3]}, c4 = {cc[0], cc[1], cc[2], cc[3]}, d4 = {d[0], d[1], d[2], d[3]};
+    f32x4 r = {v[0], v[1], v[2], v[3]};
+    if constexpr (ACC) r += (1.f - ly) * ((1.f - lx) * a4 + lx * b4) + ly * ((1.f - lx) * c4 + lx * d4);
+    else r = (1.f - ly) * ((1.f - lx) * a4 + lx * b4) + ly * ((1.f - lx) * c4 + lx * d4);
+    v[0] = r[0]; v[1] = r[1]; v[2] = r[2]; v[3] = r[3];
+}
+
+template <int DT>
+__global__ __launch_bounds__(256) void resize_nhwc_kernel(const typename ArsegStore<DT>::T *__restrict__ in, typename ArsegStore<DT>::T *__restrict__ out, int N,
+                                                          int C, int Hin, int Win, int Hout, int Wout, int mode, int align, int in_ld, int out_ld) {
+    using S = ArsegStore<DT>;
+    const int cvn = C >> S::SH;
+    const long long total = (long long)N * Hout * Wout * cvn;
     const float sy = arseg_resize_scale(Hin, Hout, align), sx = arseg_resize_scale(Win, Wout, align);
     for (long long idx = (long long)blockIdx.x * blockDim.x + threadIdx.x; idx < total; idx += (long long)gridDim.x * blockDim.x) {
-        const int c = (int)(idx % c4n) * 4;
-        const long long pix = idx / c4n;
+        const int c = (int)(idx % cvn) * S::V;
+        const long long pix = idx / cvn;
         const int ox = (int)(pix % Wout), oy = (int)((pix / Wout) % Hout), n = (int)(pix / ((long long)Wout * Hout));
-        const float *base = in + (size_t)n * Hin * Win * in_ld + c;
-        f32x4 v;
-        if (mode == ARSEG_NEAREST) {
+        const typename S::T *base = in + (size_t)n * Hin * Win * in_ld + c;
+        if (mode == ARSEG_NEAREST) {          // moves bits: nothing is converted
             const int iy = min((int)floorf((float)oy * ((float)Hin / (float)Hout)), Hin - 1);
             const int ix = min((int)floorf((float)ox * ((float)Win / (float)Wout)), Win - 1);
-            v = *reinterpret_cast<const f32x4 *>(base + ((size_t)iy * Win + ix) * in_ld);
+            S::cp(out + pix * out_ld + c, base + ((size_t)iy * Win + ix) * in_ld);
         } else {
             int y0, y1, x0, x1; float ly, lx;
             arseg_src_index(sy, oy, align, Hin, y0, y1, ly);
             arseg_src_index(sx, ox, align, Win, x0, x1, lx);
             ly = fminf(fmaxf(ly, 0.f), 1.f); lx = fminf(fmaxf(lx, 0.f), 1.f);
-            const f32x4 a = *reinterpret_cast<const f32x4 *>(base + ((size_t)y0 * Win + x0) * in_ld);
-            const f32x4 b = *reinterpret_cast<const f32x4 *>(base + ((size_t)y0 * Win + x1) * in_ld);
-            const f32x4 cc = *reinterpret_cast<const f32x4 *>(base + ((size_t)y1 * Win + x0) * in_ld);
-            const f32x4 d = *reinterpret_cast<const f32x4 *>(base + ((size_t)y1 * Win + x1) * in_ld);
-            v = (1.f - ly) * ((1.f - lx) * a + lx * b) + ly * ((1.f - lx) * cc + lx * d);
+            float a[S::V], b[S::V], cc[S::V], d[S::V], v[S::V];
+            S::ld(base + ((size_t)y0 * Win + x0) * in_ld, a);
+            S::ld(base + ((size_t)y0 * Win + x1) * in_ld, b);
+            S::ld(base + ((size_t)y1 * Win + x0) * in_ld, cc);
+            S::ld(base + ((size_t)y1 * Win + x1) * in_ld, d);
+            if constexpr (S::V == 4) bilerp4<false>(a, b, cc, d, ly, lx, v);
+            else
+#pragma unroll
+                for (int e = 0; e < S::V; ++e) v[e] = (1.f - ly) * ((1.f - lx) * a[e] + lx * b[e]) + ly * ((1.f - lx) * cc[e] + lx * d[e]);
+            S::st(out + pix * out_ld + c, v);
         }
-        *reinterpret_cast<f32x4 *>(out + pix * out_ld + c) = v;
     }
 }
 
@@ -448,94 +494,82 @@ __global__ __launch_bounds__(256) void psp_prior_sum_kernel(const float *__restr
     }
 }
 
-// per-pixel form (one thread per output vector): used when there are too few (row, channel quad) pairs to fill the chip (single images)
-__global__ __launch_bounds__(256) void psp_prior_sum_px_kernel(const float *__restrict__ t, float *__restrict__ out, int N, int H, int W,
-                                                               int C, PriorSizes ps) {
-    const int c4n = C >> 2;
-    const long long total = (long long)N * H * W * c4n;
+// per-pixel form (one thread per output vector): used when there are too few (row, channel quad) pairs to fill the chip (single images), and
+// for 16-bit maps (the sum over levels in fp32, one rounding at the store: the result is the residual of the bottleneck conv2d16, which
+// applies the ReLU after the add)
+template <int DT>
+__global__ __launch_bounds__(256) void psp_prior_sum_px_kernel(const typename ArsegStore<DT>::T *__restrict__ t, typename ArsegStore<DT>::T *__restrict__ out, int N,
+                                                               int H, int W, int C, PriorSizes ps) {
+    using S = ArsegStore<DT>;
+    const int cvn = C >> S::SH;
+    const long long total = (long long)N * H * W * cvn;
     for (long long idx = (long long)blockIdx.x * blockDim.x + threadIdx.x; idx < total; idx += (long long)gridDim.x * blockDim.x) {
-        const int c = (int)(idx % c4n) * 4;
-        const long long pix = idx / c4n;
+        const int c = (int)(idx % cvn) * S::V;
+        const long long pix = idx / cvn;
         const int x = (int)(pix % W), y = (int)((pix / W) % H), n = (int)(pix / ((long long)W * H));
-        f32x4 acc = {0.f, 0.f, 0.f, 0.f};
+        float acc[S::V];
+#pragma unroll
+        for (int e = 0; e < S::V; ++e) acc[e] = 0.f;
         for (int s = 0; s < ps.n; ++s) {
             const int sz = ps.size[s];
-            const float *base = t + ((size_t)n * ps.rows + ps.off[s]) * C + c;
+            const typename S::T *base = t + ((size_t)n * ps.rows + ps.off[s]) * C + c;
             int y0, y1, x0, x1; float ly, lx;
             arseg_src_index(arseg_resize_scale(sz, H, false), y, false, sz, y0, y1, ly);
             arseg_src_index(arseg_resize_scale(sz, W, false), x, false, sz, x0, x1, lx);
             ly = fminf(fmaxf(ly, 0.f), 1.f); lx = fminf(fmaxf(lx, 0.f), 1.f);
-            const f32x4 a = *reinterpret_cast<const f32x4 *>(base + (size_t)(y0 * sz + x0) * C);
-            const f32x4 b = *reinterpret_cast<const f32x4 *>(base + (size_t)(y0 * sz + x1) * C);
-            const f32x4 cc = *reinterpret_cast<const f32x4 *>(base + (size_t)(y1 * sz + x0) * C);
-            const f32x4 d = *reinterpret_cast<const f32x4 *>(base + (size_t)(y1 * sz + x1) * C);
-            acc += (1.f - ly) * ((1.f - lx) * a + lx * b) + ly * ((1.f - lx) * cc + lx * d);
-        }
-        *reinterpret_cast<f32x4 *>(out + pix * C + c) = acc;
-    }
-}
-
-// 16-bit pyramid priors: psp_prior_sum_px_kernel with 16-bit maps (8 channels per thread), the same blend per level, the sum over levels in fp32,
-// one rounding at the store (the result is the residual of the bottleneck conv2d16, which applies the ReLU after the add).
-template <bool BF>
-__global__ __launch_bounds__(256) void psp_prior_sum16_kernel(const uint16_t *__restrict__ t, uint16_t *__restrict__ out, int N, int H, int W,
-                                                              int C, PriorSizes ps) {
-    const int c8n = C >> 3;
-    const long long total = (long long)N * H * W * c8n;
-    for (long long idx = (long long)blockIdx.x * blockDim.x + threadIdx.x; idx < total; idx += (long long)gridDim.x * blockDim.x) {
-        const int c = (int)(idx % c8n) * 8;
-        const long long pix = idx / c8n;
-        const int x = (int)(pix % W), y = (int)((pix / W) % H), n = (int)(pix / ((long long)W * H));
-        float acc[8] = {0.f, 0.f, 0.f, 0.f, 0.f, 0.f, 0.f, 0.f};
-        for (int s = 0; s < ps.n; ++s) {
-            const int sz = ps.size[s];
-            const uint16_t *base = t + ((size_t)n * ps.rows + ps.off[s]) * C + c;
-            int y0, y1, x0, x1; float ly, lx;
-            arseg_src_index(arseg_resize_scale(sz, H, false), y, false, sz, y0, y1, ly);
-            arseg_src_index(arseg_resize_scale(sz, W, false), x, false, sz, x0, x1, lx);
-            ly = fminf(fmaxf(ly, 0.f), 1.f); lx = fminf(fmaxf(lx, 0.f), 1.f);
-            const uint4 a = *reinterpret_cast<const uint4 *>(base + (size_t)(y0 * sz + x0) * C);
-            const uint4 b = *reinterpret_cast<const uint4 *>(base + (size_t)(y0 * sz + x1) * C);
-            const uint4 cc = *reinterpret_cast<const uint4 *>(base + (size_t)(y1 * sz + x0) * C);
-            const uint4 d = *reinterpret_cast<const uint4 *>(base + (size_t)(y1 * sz + x1) * C);
-            const unsigned av[4] = {a.x, a.y, a.z, a.w}, bv[4] = {b.x, b.y, b.z, b.w}, cv[4] = {cc.x, cc.y, cc.z, cc.w}, dv[4] = {d.x, d.y, d.z, d.w};
+            float a[S::V], b[S::V], cc[S::V], d[S::V];
+            S::ld(base + (size_t)(y0 * sz + x0) * C, a);
+            S::ld(base + (size_t)(y0 * sz + x1) * C, b);
+            S::ld(base + (size_t)(y1 * sz + x0) * C, cc);
+            S::ld(base + (size_t)(y1 * sz + x1) * C, d);
+            if constexpr (S::V == 4) bilerp4<true>(a, b, cc, d, ly, lx, acc);
+            else
 #pragma unroll
-            for (int e = 0; e < 8; ++e) {
-                const int sh = (e & 1) * 16;
-                const float fa = arseg_h2f<BF>((uint16_t)(av[e >> 1] >> sh)), fb = arseg_h2f<BF>((uint16_t)(bv[e >> 1] >> sh));
-                const float fc = arseg_h2f<BF>((uint16_t)(cv[e >> 1] >> sh)), fd = arseg_h2f<BF>((uint16_t)(dv[e >> 1] >> sh));
-                acc[e] += (1.f - ly) * ((1.f - lx) * fa + lx * fb) + ly * ((1.f - lx) * fc + lx * fd);
-            }
+                for (int e = 0; e < S::V; ++e) acc[e] += (1.f - ly) * ((1.f - lx) * a[e] + lx * b[e]) + ly * ((1.f - lx) * cc[e] + lx * d[e]);
         }
-        unsigned o[4];
-#pragma unroll
-        for (int e = 0; e < 4; ++e) o[e] = arseg_f2h<BF>(acc[2 * e]) | ((unsigned)arseg_f2h<BF>(acc[2 * e + 1]) << 16);
-        *reinterpret_cast<uint4 *>(out + pix * C + c) = uint4{o[0], o[1], o[2], o[3]};
+        S::st(out + pix * C + c, acc);
     }
 }
 
 // ------------------------------------------------------------------ ARM / FFM channel scaling
-__global__ __launch_bounds__(256) void scale_add_kernel(const float *__restrict__ x, const float *__restrict__ scale,
-                                                        const float *__restrict__ add_full, const float *__restrict__ add_vec,
-                                                        float *__restrict__ out, int N, int HW, int C) {
-    const int c4n = C >> 2;
-    const long long total = (long long)N * HW * c4n;
+template <int DT>
+__global__ __launch_bounds__(256) void scale_add_kernel(const typename ArsegStore<DT>::T *__restrict__ x, const typename ArsegStore<DT>::T *__restrict__ scale,
+                                                        const typename ArsegStore<DT>::T *__restrict__ add_full, const typename ArsegStore<DT>::T *__restrict__ add_vec,
+                                                        typename ArsegStore<DT>::T *__restrict__ out, int N, int HW, int C) {
+    using S = ArsegStore<DT>;
+    const int cvn = C >> S::SH;
+    const long long total = (long long)N * HW * cvn;
     for (long long idx = (long long)blockIdx.x * blockDim.x + threadIdx.x; idx < total; idx += (long long)gridDim.x * blockDim.x) {
-        const int c = (int)(idx % c4n) * 4;
-        const long long pix = idx / c4n;
+        const int c = (int)(idx % cvn) * S::V;
+        const long long pix = idx / cvn;
         const int n = (int)(pix / HW);
-        f32x4 v = *reinterpret_cast<const f32x4 *>(x + pix * C + c) * *reinterpret_cast<const f32x4 *>(scale + (size_t)n * C + c);
-        if (add_full) v += *reinterpret_cast<const f32x4 *>(add_full + pix * C + c);
-        if (add_vec) v += *reinterpret_cast<const f32x4 *>(add_vec + (size_t)n * C + c);
-        *reinterpret_cast<f32x4 *>(out + pix * C + c) = v;
+        float v[S::V], s[S::V], t[S::V];
+        S::ld(x + pix * C + c, v);
+        S::ld(scale + (size_t)n * C + c, s);
+#pragma unroll
+        for (int e = 0; e < S::V; ++e) v[e] *= s[e];
+        if (add_full) {
+            S::ld(add_full + pix * C + c, t);
+#pragma unroll
+            for (int e = 0; e < S::V; ++e) v[e] += t[e];
+        }
+        if (add_vec) {
+            S::ld(add_vec + (size_t)n * C + c, t);
+#pragma unroll
+            for (int e = 0; e < S::V; ++e) v[e] += t[e];
+        }
+        S::st(out + pix * C + c, v);
     }
 }
 
 // ------------------------------------------------------------------ 1x1 classifier head (NHWC in, NCHW out)
-template <int NC>
-__global__ __launch_bounds__(256) void head_kernel(const float *__restrict__ p, int p_ld, const float *__restrict__ wf,
+// (fp32 weights and logits in both storages.  The dot product of a step is the left-to-right sum of the V products of the lane's channel
+// vector, then added to the accumulator: 4 terms per step in fp32 storage, 8 in 16-bit storage -- each keeps its association.)
+template <int DT, int NC>
+__global__ __launch_bounds__(256) void head_kernel(const typename ArsegStore<DT>::T *__restrict__ p, int p_ld, const float *__restrict__ wf,
                                                    const float *__restrict__ bf, float *__restrict__ logits, int N, int HW, int C,
                                                    int n_cls, int log_softmax) {
+    using S = ArsegStore<DT>;
     extern __shared__ __attribute__((aligned(16))) float wsm[];   // [n_cls][C]
     for (int i = threadIdx.x; i < n_cls * C; i += blockDim.x) wsm[i] = wf[i];
     __syncthreads();
@@ -544,14 +578,23 @@ __global__ __launch_bounds__(256) void head_kernel(const float *__restrict__ p, 
         float acc[NC];
 #pragma unroll
         for (int k = 0; k < NC; ++k) acc[k] = (k < n_cls) ? bf[k] : 0.f;
-        const float *pp = p + pix * p_ld;
-        for (int c = 0; c < C; c += 4) {
-            const f32x4 v = *reinterpret_cast<const f32x4 *>(pp + c);
+        const typename S::T *pp = p + pix * p_ld;
+        for (int c = 0; c < C; c += S::V) {
+            float v[S::V];
+            S::ld(pp + c, v);
 #pragma unroll
             for (int k = 0; k < NC; ++k)
                 if (k < n_cls) {
-                    const f32x4 w = *reinterpret_cast<const f32x4 *>(wsm + k * C + c);
-                    acc[k] += v[0] * w[0] + v[1] * w[1] + v[2] * w[2] + v[3] * w[3];
+                    float w[S::V];
+#pragma unroll
+                    for (int q = 0; q < S::V; q += 4) {
+                        const f32x4 w4 = *reinterpret_cast<const f32x4 *>(wsm + k * C + c + q);
+                        w[q] = w4[0]; w[q + 1] = w4[1]; w[q + 2] = w4[2]; w[q + 3] = w4[3];
+                    }
+                    float dot = v[0] * w[0];
+#pragma unroll
+                    for (int e = 1; e < S::V; ++e) dot += v[e] * w[e];
+                    acc[k] += dot;
                 }
         }
         if (log_softmax) {
@@ -570,6 +613,40 @@ __global__ __launch_bounds__(256) void head_kernel(const float *__restrict__ p, 
 #pragma unroll
         for (int k = 0; k < NC; ++k)
             if (k < n_cls) logits[((size_t)n * n_cls + k) * HW + hw] = acc[k];
+    }
+}
+
+// The classifier epilogue of the two matrix-core heads below: lane = pixel px0 + li, acc[r] = class (r&3) + 8*(r>>2) + 4*lh of it.  Bias, class
+// mask, LogSoftmax (one exchange between the lane halves, which hold the two halves of a pixel's classes) and the NCHW store.
+__device__ __forceinline__ void head_mfma_epilogue(f32x16 acc, const float *Bl, float *__restrict__ logits, long long px0, long long total, int HW, int n_cls,
+                                                   int log_softmax, int li, int lh) {
+    float m = -INFINITY;
+#pragma unroll
+    for (int r = 0; r < 16; ++r) {
+        const int cls = (r & 3) + 8 * (r >> 2) + 4 * lh;
+        acc[r] += Bl[cls];
+        m = fmaxf(m, cls < n_cls ? acc[r] : -INFINITY);
+    }
+    if (log_softmax) {
+        auto sw = __builtin_amdgcn_permlane32_swap(__float_as_uint(m), __float_as_uint(m), false, false);
+        m = fmaxf(__uint_as_float(sw[0]), __uint_as_float(sw[1]));
+        float z = 0.f;
+#pragma unroll
+        for (int r = 0; r < 16; ++r) z += (r & 3) + 8 * (r >> 2) + 4 * lh < n_cls ? expf(acc[r] - m) : 0.f;
+        auto sz = __builtin_amdgcn_permlane32_swap(__float_as_uint(z), __float_as_uint(z), false, false);
+        const float lse = m + logf(__uint_as_float(sz[0]) + __uint_as_float(sz[1]));
+#pragma unroll
+        for (int r = 0; r < 16; ++r) acc[r] -= lse;
+    }
+    const long long pix = px0 + li;
+    if (pix < total) {
+        const int n = (int)(pix / HW);
+        const long long hw = pix - (long long)n * HW;
+#pragma unroll
+        for (int r = 0; r < 16; ++r) {
+            const int cls = (r & 3) + 8 * (r >> 2) + 4 * lh;
+            if (cls < n_cls) logits[((size_t)n * n_cls + cls) * HW + hw] = acc[r];
+        }
     }
 }
 
@@ -628,47 +705,69 @@ __global__ __launch_bounds__(256, NPC == 8 ? 3 : 2) void head_mfma_kernel(const 
 #pragma unroll
             for (int e = 0; e < 4; ++e) acc = __builtin_amdgcn_mfma_f32_32x32x2f32(a[e], b[e], acc, 0, 0, 0);
         }
-        // lane = pixel li; acc[r] = class (r&3) + 8*(r>>2) + 4*lh
-        float m = -INFINITY;
-#pragma unroll
-        for (int r = 0; r < 16; ++r) {
-            const int cls = (r & 3) + 8 * (r >> 2) + 4 * lh;
-            acc[r] += Bl[cls];
-            m = fmaxf(m, cls < n_cls ? acc[r] : -INFINITY);
-        }
-        if (log_softmax) {
-            auto sw = __builtin_amdgcn_permlane32_swap(__float_as_uint(m), __float_as_uint(m), false, false);
-            m = fmaxf(__uint_as_float(sw[0]), __uint_as_float(sw[1]));
-            float z = 0.f;
-#pragma unroll
-            for (int r = 0; r < 16; ++r) z += (r & 3) + 8 * (r >> 2) + 4 * lh < n_cls ? expf(acc[r] - m) : 0.f;
-            auto sz = __builtin_amdgcn_permlane32_swap(__float_as_uint(z), __float_as_uint(z), false, false);
-            const float lse = m + logf(__uint_as_float(sz[0]) + __uint_as_float(sz[1]));
-#pragma unroll
-            for (int r = 0; r < 16; ++r) acc[r] -= lse;
-        }
-        const long long pix = px0 + li;
-        if (pix < total) {
-            const int n = (int)(pix / HW);
-            const long long hw = pix - (long long)n * HW;
-#pragma unroll
-            for (int r = 0; r < 16; ++r) {
-                const int cls = (r & 3) + 8 * (r >> 2) + 4 * lh;
-                if (cls < n_cls) logits[((size_t)n * n_cls + cls) * HW + hw] = acc[r];
-            }
-        }
+        head_mfma_epilogue(acc, Bl, logits, px0, total, HW, n_cls, log_softmax, li, lh);
     }
 }
 
-// ------------------------------------------------------------------ frame ingest: NCHW RGB -> NHWC4 (+ downscale)
-__global__ __launch_bounds__(256) void frame_to_nhwc4_kernel(const float *__restrict__ img, float *__restrict__ out, int N, int H,
-                                                             int W, int h, int w) {
+// The matrix-core head on 16-bit features: the pixel tile is converted to fp32 while it is staged through LDS in 64-channel chunks
+// (C % 64 == 0), fp32 weights resident in LDS.  (The one-thread-per-pixel kernel re-reads every weight from LDS per pixel: 1200
+// ds_read_b128 per pixel at C = 256, 19 classes.)
+template <int DT>
+__global__ __launch_bounds__(256) void head16_mfma_kernel(const uint16_t *__restrict__ p, int p_ld, const float *__restrict__ wf, const float *__restrict__ bf,
+                                                          float *__restrict__ logits, int N, int HW, int C, int n_cls, int log_softmax) {
+    constexpr int KC = 64, PS = KC + 4;
+    extern __shared__ __attribute__((aligned(16))) float hsm[];
+    const int WS = C + 4;
+    float *Wl = hsm;                                        // [32][WS] (rows >= n_cls zero)
+    float *Bl = Wl + 32 * WS;                               // [32] bias
+    float *Pl = Bl + 32 + (threadIdx.x >> 6) * 32 * PS;     // this wave's pixel tile chunk [32][PS]
+    const int tid = threadIdx.x, lane = tid & 63, li = lane & 31, lh = lane >> 5, c4n = C >> 2;
+    for (int i = tid; i < 32 * c4n; i += 256) {
+        const int r = i / c4n, c = (i - r * c4n) * 4;
+        *reinterpret_cast<f32x4 *>(Wl + r * WS + c) = r < n_cls ? *reinterpret_cast<const f32x4 *>(wf + (size_t)r * C + c) : f32x4{0.f, 0.f, 0.f, 0.f};
+    }
+    if (tid < 32) Bl[tid] = tid < n_cls ? bf[tid] : 0.f;
+    __syncthreads();
+    const long long total = (long long)N * HW, ntile = (total + 31) / 32;
+    for (long long tile = (long long)blockIdx.x * 4 + (tid >> 6); tile < ntile; tile += (long long)gridDim.x * 4) {
+        const long long px0 = tile * 32;
+        f32x16 acc;
+#pragma unroll
+        for (int e = 0; e < 16; ++e) acc[e] = 0.f;
+        for (int kc = 0; kc < C; kc += KC) {
+#pragma unroll
+            for (int j = 0; j < 4; ++j) {                   // 32 pixels x 8 pieces of 8 halves: consecutive lanes, consecutive 16-byte pieces
+                const int i = lane + 64 * j, r = i >> 3, c = (i & 7) * 8;
+                float f[8] = {0.f, 0.f, 0.f, 0.f, 0.f, 0.f, 0.f, 0.f};
+                if (px0 + r < total) ArsegStore<DT>::ld(p + (size_t)(px0 + r) * p_ld + kc + c, f);
+                *reinterpret_cast<f32x4 *>(Pl + r * PS + c) = f32x4{f[0], f[1], f[2], f[3]};
+                *reinterpret_cast<f32x4 *>(Pl + r * PS + c + 4) = f32x4{f[4], f[5], f[6], f[7]};
+            }
+            const float *wa = Wl + li * WS + kc + lh * (KC / 2), *pb = Pl + li * PS + lh * (KC / 2);
+#pragma unroll
+            for (int k = 0; k < KC / 2; k += 4) {
+                const f32x4 a = *reinterpret_cast<const f32x4 *>(wa + k), b = *reinterpret_cast<const f32x4 *>(pb + k);
+#pragma unroll
+                for (int e = 0; e < 4; ++e) acc = __builtin_amdgcn_mfma_f32_32x32x2f32(a[e], b[e], acc, 0, 0, 0);
+            }
+        }
+        head_mfma_epilogue(acc, Bl, logits, px0, total, HW, n_cls, log_softmax, li, lh);
+    }
+}
+
+// ------------------------------------------------------------------ frame ingest: NCHW fp32 RGB -> NHWC4 fp32 / NHWC8 16-bit (+ bilinear align_corners=True downscale)
+template <int DT>
+__global__ __launch_bounds__(256) void frame_to_nhwc_kernel(const float *__restrict__ img, typename ArsegStore<DT>::T *__restrict__ out, int N, int H, int W, int h,
+                                                            int w) {
+    using S = ArsegStore<DT>;
     const long long total = (long long)N * h * w;
     const float sy = arseg_resize_scale(H, h, true), sx = arseg_resize_scale(W, w, true);
     const bool same = (h == H && w == W);
     for (long long pix = (long long)blockIdx.x * blockDim.x + threadIdx.x; pix < total; pix += (long long)gridDim.x * blockDim.x) {
         const int ox = (int)(pix % w), oy = (int)((pix / w) % h), n = (int)(pix / ((long long)w * h));
-        f32x4 v = {0.f, 0.f, 0.f, 0.f};
+        float v[S::V];
+#pragma unroll
+        for (int e = 0; e < S::V; ++e) v[e] = 0.f;
         const float *base = img + (size_t)n * 3 * H * W;
         if (same) {
 #pragma unroll
@@ -685,17 +784,19 @@ __global__ __launch_bounds__(256) void frame_to_nhwc4_kernel(const float *__rest
                        ly * ((1.f - lx) * b[(size_t)y1 * W + x0] + lx * b[(size_t)y1 * W + x1]);
             }
         }
-        *reinterpret_cast<f32x4 *>(out + pix * 4) = v;
+        S::st(out + pix * S::V, v);
     }
 }
 
 // The same for the downscaling case with coalesced reads: one workgroup = 256 consecutive output pixels of one output row.  The two source
 // rows under it (x span of the 256 pixels, three planes) are staged in LDS with 16-byte loads, the four taps of a pixel come from there
 // (the kernel above reads 12 strided scalars per pixel: 0.4 TB/s).  Same blend, same operation order: bit-identical results.
-constexpr int F4_SPAN = 1056;                    // staged floats per row and plane: 255 * sx + 4 (+3 alignment) <= F4_SPAN  <=>  sx <= 4.1
-__global__ __launch_bounds__(256) void frame_to_nhwc4_rows_kernel(const float *__restrict__ img, float *__restrict__ out, int N, int H, int W, int h, int w,
-                                                                  int segs) {
-    __shared__ __attribute__((aligned(16))) float st[6][F4_SPAN];
+constexpr int FRAME_SPAN = 1056;                 // staged floats per row and plane: 255 * sx + 4 (+3 alignment) <= FRAME_SPAN  <=>  sx <= 4.1
+template <int DT>
+__global__ __launch_bounds__(256) void frame_to_nhwc_rows_kernel(const float *__restrict__ img, typename ArsegStore<DT>::T *__restrict__ out, int N, int H, int W,
+                                                                 int h, int w, int segs) {
+    using S = ArsegStore<DT>;
+    __shared__ __attribute__((aligned(16))) float st[6][FRAME_SPAN];
     const float sy = arseg_resize_scale(H, h, true), sx = arseg_resize_scale(W, w, true);
     const int seg = blockIdx.x % segs, oy = (blockIdx.x / segs) % h, n = blockIdx.x / (segs * h);
     const int ox0 = seg * 256, ox1 = min(ox0 + 255, w - 1);
@@ -717,11 +818,13 @@ __global__ __launch_bounds__(256) void frame_to_nhwc4_rows_kernel(const float *_
         arseg_src_index(sx, ox, true, W, x0, x1, lx);
         lx = fminf(fmaxf(lx, 0.f), 1.f);
         x0 -= xs4; x1 -= xs4;
-        f32x4 v = {0.f, 0.f, 0.f, 0.f};
+        float v[S::V];
+#pragma unroll
+        for (int e = 0; e < S::V; ++e) v[e] = 0.f;
 #pragma unroll
         for (int c = 0; c < 3; ++c)
             v[c] = (1.f - ly) * ((1.f - lx) * st[2 * c][x0] + lx * st[2 * c][x1]) + ly * ((1.f - lx) * st[2 * c + 1][x0] + lx * st[2 * c + 1][x1]);
-        *reinterpret_cast<f32x4 *>(out + (((size_t)n * h + oy) * w + ox) * 4) = v;
+        S::st(out + (((size_t)n * h + oy) * w + ox) * S::V, v);
     }
 }
 
@@ -972,7 +1075,7 @@ extern "C" int arseg_maxpool3x3s2_fwd(const float *in, float *out, int N, int H,
     ARSEG_CHECK_PTR(in); ARSEG_CHECK_PTR(out); ARSEG_CHECK_POS(N); ARSEG_CHECK_POS(H); ARSEG_CHECK_POS(W); ARSEG_CHECK_POS(C);
     if (C & 3) return ARSEG_EINVAL;
     const int Ho = (H - 1) / 2 + 1, Wo = (W - 1) / 2 + 1;
-    hipLaunchKernelGGL(maxpool3x3s2_kernel, dim3(arseg_grid_for((long long)N * Ho * Wo * (C >> 2))), dim3(256), 0, arseg_stream(stream),
+    hipLaunchKernelGGL(maxpool3x3s2_kernel<ARSEG_DT_F32>, dim3(arseg_grid_for((long long)N * Ho * Wo * (C >> 2))), dim3(256), 0, arseg_stream(stream),
                        in, out, N, H, W, C, Ho, Wo);
     return arseg_launch_status();
 }
@@ -1052,80 +1155,49 @@ static int pool_grid(int H, int W, int n_sizes, const int *sizes, PoolGrid *g) {
 }
 
 // The folded pyramid's pooled matrix [N][rows][n_sizes * C] (rows = sum s^2: level i's adaptive average pool in columns [i*C, (i+1)*C) of its
-// rows, zeros elsewhere) in one pass over the map; workspace = the cell sums.
+// rows, zeros elsewhere) in one pass over the map; workspace = the cell sums (fp32 in both storages).
 extern "C" size_t arseg_psp_pool_matrix_workspace_bytes(int N, int H, int W, int C, int n_sizes, const int *sizes) {
     PoolGrid g;
     if (N <= 0 || H <= 0 || W <= 0 || C <= 0 || !sizes || pool_grid(H, W, n_sizes, sizes, &g) != ARSEG_OK) return 0;
     return (size_t)N * g.ny * g.nx * C * sizeof(float);
 }
-
-extern "C" int arseg_psp_pool_matrix_fwd(const float *in, int in_ld, float *out, void *workspace, size_t workspace_bytes, int N, int H, int W, int C,
-                                         int n_sizes, const int *sizes, arseg_stream_t stream) {
-    ARSEG_CHECK_PTR(in); ARSEG_CHECK_PTR(out); ARSEG_CHECK_PTR(workspace); ARSEG_CHECK_PTR(sizes);
-    ARSEG_CHECK_POS(N); ARSEG_CHECK_POS(H); ARSEG_CHECK_POS(W); ARSEG_CHECK_POS(C);
-    if ((C & 3) || (in_ld & 3) || in_ld < C || !ARSEG_ALIGNED16(in) || !ARSEG_ALIGNED16(out) || !ARSEG_ALIGNED16(workspace) || N > 65535) return ARSEG_EINVAL;
-    PoolGrid g;
-    if (int e = pool_grid(H, W, n_sizes, sizes, &g)) return e;
-    if (workspace_bytes < (size_t)N * g.ny * g.nx * C * sizeof(float)) return ARSEG_EWORKSPACE;
-    hipStream_t hs = arseg_stream(stream);
-    hipLaunchKernelGGL(psp_cells_kernel, dim3(g.ny * g.nx, arseg_cdiv(C, 64), N), dim3(256), 0, hs, in, in_ld, reinterpret_cast<float *>(workspace), H, W, C, g);
-    hipLaunchKernelGGL(psp_bins_kernel, dim3(g.rows, N), dim3(256), 0, hs, reinterpret_cast<const float *>(workspace), out, H, W, C, g);
-    return arseg_launch_status();
-}
-
-extern "C" int arseg_psp_prior_sum_fwd(const float *t, float *out, int N, int H, int W, int C, int n_sizes, const int *sizes,
-                                       arseg_stream_t stream) {
-    ARSEG_CHECK_PTR(t); ARSEG_CHECK_PTR(out); ARSEG_CHECK_PTR(sizes);
-    ARSEG_CHECK_POS(N); ARSEG_CHECK_POS(H); ARSEG_CHECK_POS(W); ARSEG_CHECK_POS(C);
-    if (n_sizes < 1 || n_sizes > 4 || (C & 3) || !ARSEG_ALIGNED16(t) || !ARSEG_ALIGNED16(out)) return ARSEG_EINVAL;
-    PriorSizes ps;
-    ps.n = n_sizes; ps.rows = 0;
-    for (int i = 0; i < 4; ++i) { ps.size[i] = 1; ps.off[i] = 0; }
-    for (int i = 0; i < n_sizes; ++i) {
-        if (sizes[i] <= 0) return ARSEG_EINVAL;
-        ps.size[i] = sizes[i]; ps.off[i] = ps.rows; ps.rows += sizes[i] * sizes[i];
-    }
-    if ((long long)N * H * (C >> 2) >= 49152)
-        hipLaunchKernelGGL(psp_prior_sum_kernel, dim3(arseg_cdiv((long long)N * H * (C >> 2), 256)), dim3(256), 0, arseg_stream(stream), t, out, N,
-                           H, W, C, ps);
-    else
-        hipLaunchKernelGGL(psp_prior_sum_px_kernel, dim3(arseg_grid_for((long long)N * H * W * (C >> 2))), dim3(256), 0, arseg_stream(stream), t, out, N,
-                           H, W, C, ps);
-    return arseg_launch_status();
-}
-
 extern "C" size_t arseg_psp_pool_matrix16_workspace_bytes(int N, int H, int W, int C, int n_sizes, const int *sizes) {
     return arseg_psp_pool_matrix_workspace_bytes(N, H, W, C, n_sizes, sizes);
 }
 
-extern "C" int arseg_psp_pool_matrix16_fwd(const void *in, int in_ld, void *out, int dtype, void *workspace, size_t workspace_bytes, int N, int H,
-                                           int W, int C, int n_sizes, const int *sizes, arseg_stream_t stream) {
+template <int DT>
+static int psp_pool_matrix(const void *in, int in_ld, void *out, void *workspace, size_t workspace_bytes, int N, int H, int W, int C, int n_sizes,
+                           const int *sizes, arseg_stream_t stream) {
+    using T = typename ArsegStore<DT>::T;
+    constexpr int M = ArsegStore<DT>::V - 1;
     ARSEG_CHECK_PTR(in); ARSEG_CHECK_PTR(out); ARSEG_CHECK_PTR(workspace); ARSEG_CHECK_PTR(sizes);
     ARSEG_CHECK_POS(N); ARSEG_CHECK_POS(H); ARSEG_CHECK_POS(W); ARSEG_CHECK_POS(C);
-    if (dtype != ARSEG_DT_F16 && dtype != ARSEG_DT_BF16) return ARSEG_EINVAL;
-    if ((C & 7) || (in_ld & 7) || in_ld < C || !ARSEG_ALIGNED16(in) || !ARSEG_ALIGNED16(out) || !ARSEG_ALIGNED16(workspace) || N > 65535) return ARSEG_EINVAL;
+    if ((C & M) || (in_ld & M) || in_ld < C || !ARSEG_ALIGNED16(in) || !ARSEG_ALIGNED16(out) || !ARSEG_ALIGNED16(workspace) || N > 65535) return ARSEG_EINVAL;
     PoolGrid g;
     if (int e = pool_grid(H, W, n_sizes, sizes, &g)) return e;
     if (workspace_bytes < (size_t)N * g.ny * g.nx * C * sizeof(float)) return ARSEG_EWORKSPACE;
     hipStream_t hs = arseg_stream(stream);
     float *cells = reinterpret_cast<float *>(workspace);
-    const dim3 g1(g.ny * g.nx, arseg_cdiv(C, 64), N), g2(g.rows, N);
-    if (dtype == ARSEG_DT_BF16) {
-        hipLaunchKernelGGL(psp_cells16_kernel<true>, g1, dim3(256), 0, hs, (const uint16_t *)in, in_ld, cells, H, W, C, g);
-        hipLaunchKernelGGL(psp_bins16_kernel<true>, g2, dim3(256), 0, hs, cells, (uint16_t *)out, H, W, C, g);
-    } else {
-        hipLaunchKernelGGL(psp_cells16_kernel<false>, g1, dim3(256), 0, hs, (const uint16_t *)in, in_ld, cells, H, W, C, g);
-        hipLaunchKernelGGL(psp_bins16_kernel<false>, g2, dim3(256), 0, hs, cells, (uint16_t *)out, H, W, C, g);
-    }
+    hipLaunchKernelGGL(psp_cells_kernel<DT>, dim3(g.ny * g.nx, arseg_cdiv(C, 64), N), dim3(256), 0, hs, (const T *)in, in_ld, cells, H, W, C, g);
+    hipLaunchKernelGGL(psp_bins_kernel<DT>, dim3(g.rows, N), dim3(256), 0, hs, cells, (T *)out, H, W, C, g);
     return arseg_launch_status();
 }
+extern "C" int arseg_psp_pool_matrix_fwd(const float *in, int in_ld, float *out, void *workspace, size_t workspace_bytes, int N, int H, int W, int C,
+                                         int n_sizes, const int *sizes, arseg_stream_t stream) {
+    return psp_pool_matrix<ARSEG_DT_F32>(in, in_ld, out, workspace, workspace_bytes, N, H, W, C, n_sizes, sizes, stream);
+}
+extern "C" int arseg_psp_pool_matrix16_fwd(const void *in, int in_ld, void *out, int dtype, void *workspace, size_t workspace_bytes, int N, int H,
+                                           int W, int C, int n_sizes, const int *sizes, arseg_stream_t stream) {
+    return arseg_dispatch16(dtype, [&](auto dt) { return psp_pool_matrix<dt()>(in, in_ld, out, workspace, workspace_bytes, N, H, W, C, n_sizes, sizes, stream); });
+}
 
-extern "C" int arseg_psp_prior_sum16_fwd(const void *t, void *out, int dtype, int N, int H, int W, int C, int n_sizes, const int *sizes,
-                                         arseg_stream_t stream) {
+template <int DT>
+static int psp_prior_sum(const void *t, void *out, int N, int H, int W, int C, int n_sizes, const int *sizes, arseg_stream_t stream) {
+    using S = ArsegStore<DT>;
+    using T = typename S::T;
     ARSEG_CHECK_PTR(t); ARSEG_CHECK_PTR(out); ARSEG_CHECK_PTR(sizes);
     ARSEG_CHECK_POS(N); ARSEG_CHECK_POS(H); ARSEG_CHECK_POS(W); ARSEG_CHECK_POS(C);
-    if (dtype != ARSEG_DT_F16 && dtype != ARSEG_DT_BF16) return ARSEG_EINVAL;
-    if (n_sizes < 1 || n_sizes > 4 || (C & 7) || !ARSEG_ALIGNED16(t) || !ARSEG_ALIGNED16(out)) return ARSEG_EINVAL;
+    if (n_sizes < 1 || n_sizes > 4 || (C & (S::V - 1)) || !ARSEG_ALIGNED16(t) || !ARSEG_ALIGNED16(out)) return ARSEG_EINVAL;
     PriorSizes ps;
     ps.n = n_sizes; ps.rows = 0;
     for (int i = 0; i < 4; ++i) { ps.size[i] = 1; ps.off[i] = 0; }
@@ -1133,11 +1205,23 @@ extern "C" int arseg_psp_prior_sum16_fwd(const void *t, void *out, int dtype, in
         if (sizes[i] <= 0) return ARSEG_EINVAL;
         ps.size[i] = sizes[i]; ps.off[i] = ps.rows; ps.rows += sizes[i] * sizes[i];
     }
-    const dim3 grid(arseg_grid_for((long long)N * H * W * (C >> 3)));
     hipStream_t hs = arseg_stream(stream);
-    if (dtype == ARSEG_DT_BF16) hipLaunchKernelGGL(psp_prior_sum16_kernel<true>, grid, dim3(256), 0, hs, (const uint16_t *)t, (uint16_t *)out, N, H, W, C, ps);
-    else hipLaunchKernelGGL(psp_prior_sum16_kernel<false>, grid, dim3(256), 0, hs, (const uint16_t *)t, (uint16_t *)out, N, H, W, C, ps);
+    if constexpr (DT == ARSEG_DT_F32) {          // (the row-walk form exists in fp32 only)
+        if ((long long)N * H * (C >> 2) >= 49152) {
+            hipLaunchKernelGGL(psp_prior_sum_kernel, dim3(arseg_cdiv((long long)N * H * (C >> 2), 256)), dim3(256), 0, hs, (const float *)t, (float *)out, N, H, W, C, ps);
+            return arseg_launch_status();
+        }
+    }
+    hipLaunchKernelGGL(psp_prior_sum_px_kernel<DT>, dim3(arseg_grid_for((long long)N * H * W * (C >> S::SH))), dim3(256), 0, hs, (const T *)t, (T *)out, N, H, W, C, ps);
     return arseg_launch_status();
+}
+extern "C" int arseg_psp_prior_sum_fwd(const float *t, float *out, int N, int H, int W, int C, int n_sizes, const int *sizes,
+                                       arseg_stream_t stream) {
+    return psp_prior_sum<ARSEG_DT_F32>(t, out, N, H, W, C, n_sizes, sizes, stream);
+}
+extern "C" int arseg_psp_prior_sum16_fwd(const void *t, void *out, int dtype, int N, int H, int W, int C, int n_sizes, const int *sizes,
+                                         arseg_stream_t stream) {
+    return arseg_dispatch16(dtype, [&](auto dt) { return psp_prior_sum<dt()>(t, out, N, H, W, C, n_sizes, sizes, stream); });
 }
 
 extern "C" int arseg_global_reduce_fwd(const float *in, int in_ld, float *out, int N, int H, int W, int C, int op,
@@ -1203,7 +1287,7 @@ extern "C" int arseg_resize_fwd(const float *in, float *out, int N, int C, int H
                                in, out, C, Hin, Win, in_ld, out_ld);
             return arseg_launch_status();
         }
-        hipLaunchKernelGGL(resize_nhwc_kernel, dim3(arseg_grid_for((long long)N * Hout * Wout * (C >> 2))), dim3(256), 0,
+        hipLaunchKernelGGL(resize_nhwc_kernel<ARSEG_DT_F32>, dim3(arseg_grid_for((long long)N * Hout * Wout * (C >> 2))), dim3(256), 0,
                            arseg_stream(stream), in, out, N, C, Hin, Win, Hout, Wout, mode, align_corners ? 1 : 0, in_ld, out_ld);
     } else if (layout == ARSEG_NCHW) {
         if (mode == ARSEG_BILINEAR && !align_corners && (Wout == 8 * Win || Wout == 16 * Win) && ARSEG_ALIGNED16(out)) {
@@ -1226,7 +1310,7 @@ extern "C" int arseg_scale_add_fwd(const float *x, const float *scale, const flo
                                    int N, int HW, int C, arseg_stream_t stream) {
     ARSEG_CHECK_PTR(x); ARSEG_CHECK_PTR(scale); ARSEG_CHECK_PTR(out); ARSEG_CHECK_POS(N); ARSEG_CHECK_POS(HW); ARSEG_CHECK_POS(C);
     if (C & 3) return ARSEG_EINVAL;
-    hipLaunchKernelGGL(scale_add_kernel, dim3(arseg_grid_for((long long)N * HW * (C >> 2))), dim3(256), 0, arseg_stream(stream), x, scale,
+    hipLaunchKernelGGL(scale_add_kernel<ARSEG_DT_F32>, dim3(arseg_grid_for((long long)N * HW * (C >> 2))), dim3(256), 0, arseg_stream(stream), x, scale,
                        add_full, add_vec, out, N, HW, C);
     return arseg_launch_status();
 }
@@ -1256,9 +1340,9 @@ extern "C" int arseg_head_fwd(const float *p, int p_ld, const float *wf, const f
     }
     const size_t smem = (size_t)n_cls * C * sizeof(float);
     const int g = arseg_grid_for((long long)N * HW, 2048);
-    if (n_cls <= 12) hipLaunchKernelGGL(head_kernel<12>, dim3(g), dim3(256), smem, st, p, p_ld, wf, bf, logits, N, HW, C, n_cls, log_softmax);
-    else if (n_cls <= 19) hipLaunchKernelGGL(head_kernel<19>, dim3(g), dim3(256), smem, st, p, p_ld, wf, bf, logits, N, HW, C, n_cls, log_softmax);
-    else hipLaunchKernelGGL(head_kernel<32>, dim3(g), dim3(256), smem, st, p, p_ld, wf, bf, logits, N, HW, C, n_cls, log_softmax);
+    if (n_cls <= 12) hipLaunchKernelGGL((head_kernel<ARSEG_DT_F32, 12>), dim3(g), dim3(256), smem, st, p, p_ld, wf, bf, logits, N, HW, C, n_cls, log_softmax);
+    else if (n_cls <= 19) hipLaunchKernelGGL((head_kernel<ARSEG_DT_F32, 19>), dim3(g), dim3(256), smem, st, p, p_ld, wf, bf, logits, N, HW, C, n_cls, log_softmax);
+    else hipLaunchKernelGGL((head_kernel<ARSEG_DT_F32, 32>), dim3(g), dim3(256), smem, st, p, p_ld, wf, bf, logits, N, HW, C, n_cls, log_softmax);
     return arseg_launch_status();
 }
 
@@ -1266,11 +1350,11 @@ extern "C" int arseg_frame_to_nhwc4_fwd(const float *img, float *out, int N, int
     ARSEG_CHECK_PTR(img); ARSEG_CHECK_PTR(out); ARSEG_CHECK_POS(N); ARSEG_CHECK_POS(H); ARSEG_CHECK_POS(W); ARSEG_CHECK_POS(h); ARSEG_CHECK_POS(w);
     const float sx = arseg_resize_scale(W, w, true);
     const int segs = arseg_cdiv(w, 256);
-    if (!(h == H && w == W) && W % 4 == 0 && ARSEG_ALIGNED16(img) && 255.f * sx + 8.f <= (float)F4_SPAN && (long long)N * h * segs < (1ll << 31)) {
-        hipLaunchKernelGGL(frame_to_nhwc4_rows_kernel, dim3((unsigned)(N * h * segs)), dim3(256), 0, arseg_stream(stream), img, out, N, H, W, h, w, segs);
+    if (!(h == H && w == W) && W % 4 == 0 && ARSEG_ALIGNED16(img) && 255.f * sx + 8.f <= (float)FRAME_SPAN && (long long)N * h * segs < (1ll << 31)) {
+        hipLaunchKernelGGL(frame_to_nhwc_rows_kernel<ARSEG_DT_F32>, dim3((unsigned)(N * h * segs)), dim3(256), 0, arseg_stream(stream), img, out, N, H, W, h, w, segs);
         return arseg_launch_status();
     }
-    hipLaunchKernelGGL(frame_to_nhwc4_kernel, dim3(arseg_grid_for((long long)N * h * w)), dim3(256), 0, arseg_stream(stream), img, out, N, H, W, h, w);
+    hipLaunchKernelGGL(frame_to_nhwc_kernel<ARSEG_DT_F32>, dim3(arseg_grid_for((long long)N * h * w)), dim3(256), 0, arseg_stream(stream), img, out, N, H, W, h, w);
     return arseg_launch_status();
 }
 
@@ -1362,4 +1446,140 @@ extern "C" int arseg_argmax_confusion_grouped_fwd(const float *logits, const int
     hipLaunchKernelGGL(argmax_confusion_grouped_kernel, dim3(per < share ? per : (share < 1 ? 1 : share), gy), dim3(256), 0, st, logits, label, group,
                        pred, hh, N, n_groups, n_cls, h, w, H, W, ignore_label, align_corners);
     return arseg_launch_status();
+}
+
+// ------------------------------------------------------------------ entry points of the 16-bit storage path (dtype = ARSEG_DT_F16 | ARSEG_DT_BF16)
+extern "C" int arseg_frame_to_nhwc8_16_fwd(const float *img, void *out, int dtype, int N, int H, int W, int h, int w, arseg_stream_t stream) {
+    ARSEG_CHECK_PTR(img); ARSEG_CHECK_PTR(out); ARSEG_CHECK_POS(N); ARSEG_CHECK_POS(H); ARSEG_CHECK_POS(W); ARSEG_CHECK_POS(h); ARSEG_CHECK_POS(w);
+    if (!ARSEG_ALIGNED16(out)) return ARSEG_EINVAL;
+    const int segs = arseg_cdiv(w, 256);
+    const float sx = arseg_resize_scale(W, w, true);
+    const bool rows = !(h == H && w == W) && W % 4 == 0 && ARSEG_ALIGNED16(img) && 255.f * sx + 8.f <= (float)FRAME_SPAN && (long long)N * h * segs < (1ll << 31);
+    return arseg_dispatch16(dtype, [&](auto dt) {
+        if (rows) hipLaunchKernelGGL(frame_to_nhwc_rows_kernel<dt()>, dim3((unsigned)(N * h * segs)), dim3(256), 0, arseg_stream(stream), img, (uint16_t *)out, N, H, W, h, w, segs);
+        else hipLaunchKernelGGL(frame_to_nhwc_kernel<dt()>, dim3(arseg_grid_for((long long)N * h * w)), dim3(256), 0, arseg_stream(stream), img, (uint16_t *)out, N, H, W, h, w);
+        return arseg_launch_status();
+    });
+}
+
+extern "C" int arseg_maxpool3x3s2_16_fwd(const void *in, void *out, int dtype, int N, int H, int W, int C, arseg_stream_t stream) {
+    ARSEG_CHECK_PTR(in); ARSEG_CHECK_PTR(out); ARSEG_CHECK_POS(N); ARSEG_CHECK_POS(H); ARSEG_CHECK_POS(W); ARSEG_CHECK_POS(C);
+    if ((C & 7) || !ARSEG_ALIGNED16(in) || !ARSEG_ALIGNED16(out)) return ARSEG_EINVAL;
+    const int Ho = (H - 1) / 2 + 1, Wo = (W - 1) / 2 + 1;
+    return arseg_dispatch16(dtype, [&](auto dt) {
+        hipLaunchKernelGGL(maxpool3x3s2_kernel<dt()>, dim3(arseg_grid_for((long long)N * Ho * Wo * (C >> 3))), dim3(256), 0, arseg_stream(stream),
+                           (const uint16_t *)in, (uint16_t *)out, N, H, W, C, Ho, Wo);
+        return arseg_launch_status();
+    });
+}
+
+static int mean16_slices(int N, int HW, int C) {
+    long long blocks = (long long)arseg_cdiv(C, 256) * N;
+    int S = (int)(512 / (blocks < 1 ? 1 : blocks));           // aim for ~512 workgroups
+    S = S < 1 ? 1 : S;
+    const int maxS = (HW + 63) / 64;                           // at least 64 pixels per slice
+    return S > maxS ? maxS : S;
+}
+extern "C" size_t arseg_global_mean16_workspace_bytes(int N, int H, int W, int C) {
+    if (N <= 0 || H <= 0 || W <= 0 || C <= 0) return 0;
+    return (size_t)N * mean16_slices(N, H * W, C) * C * sizeof(float);
+}
+
+// torch.mean / torch.amax (x, (2,3)) on 16-bit NHWC (the max: the PSPNet auxiliary classifier input, model/pspnet.py:92-93): the same two
+// steps, slices and workspace for both
+template <bool IS_MAX>
+static int global_reduce16(const void *in, int in_ld, void *out, int dtype, int N, int H, int W, int C, void *workspace, size_t workspace_bytes,
+                           arseg_stream_t stream) {
+    ARSEG_CHECK_PTR(in); ARSEG_CHECK_PTR(out); ARSEG_CHECK_POS(N); ARSEG_CHECK_POS(H); ARSEG_CHECK_POS(W); ARSEG_CHECK_POS(C);
+    if ((C & 7) || (in_ld & 7) || in_ld < C || !ARSEG_ALIGNED16(in) || N > 65535) return ARSEG_EINVAL;
+    if (IS_MAX && dtype != ARSEG_DT_F16 && dtype != ARSEG_DT_BF16) return ARSEG_EINVAL;          // (the max refuses a dtype before a workspace, the mean after it)
+    const int S = mean16_slices(N, H * W, C);
+    if (!workspace || workspace_bytes < (size_t)N * S * C * sizeof(float)) return ARSEG_EWORKSPACE;
+    return arseg_dispatch16(dtype, [&](auto dt) {
+        hipStream_t st = arseg_stream(stream);
+        float *part = (float *)workspace;
+        hipLaunchKernelGGL((global_slices16_kernel<dt(), IS_MAX>), dim3(arseg_cdiv(C, 256), N, S), dim3(256), 0, st, (const uint16_t *)in, in_ld, part, H * W, C, S);
+        hipLaunchKernelGGL((global_fin16_kernel<dt(), IS_MAX>), dim3(arseg_cdiv((long long)N * C, 32)), dim3(256), 0, st, part, (uint16_t *)out, N, C, S,
+                           1.0f / (float)(H * W));
+        return arseg_launch_status();
+    });
+}
+extern "C" int arseg_global_mean16_fwd(const void *in, int in_ld, void *out, int dtype, int N, int H, int W, int C, void *workspace,
+                                       size_t workspace_bytes, arseg_stream_t stream) {
+    return global_reduce16<false>(in, in_ld, out, dtype, N, H, W, C, workspace, workspace_bytes, stream);
+}
+extern "C" int arseg_global_max16_fwd(const void *in, int in_ld, void *out, int dtype, int N, int H, int W, int C, void *workspace,
+                                      size_t workspace_bytes, arseg_stream_t stream) {
+    return global_reduce16<true>(in, in_ld, out, dtype, N, H, W, C, workspace, workspace_bytes, stream);
+}
+
+extern "C" int arseg_resize16_fwd(const void *in, void *out, int dtype, int N, int C, int Hin, int Win, int Hout, int Wout, int mode, int align_corners,
+                                  int in_ld, int out_ld, arseg_stream_t stream) {
+    ARSEG_CHECK_PTR(in); ARSEG_CHECK_PTR(out); ARSEG_CHECK_POS(N); ARSEG_CHECK_POS(C); ARSEG_CHECK_POS(Hin); ARSEG_CHECK_POS(Win);
+    ARSEG_CHECK_POS(Hout); ARSEG_CHECK_POS(Wout);
+    if (mode != ARSEG_NEAREST && mode != ARSEG_BILINEAR) return ARSEG_EINVAL;
+    if ((C & 7) || (in_ld & 7) || (out_ld & 7) || in_ld < C || out_ld < C || !ARSEG_ALIGNED16(in) || !ARSEG_ALIGNED16(out)) return ARSEG_EINVAL;
+    return arseg_dispatch16(dtype, [&](auto dt) {
+        hipLaunchKernelGGL(resize_nhwc_kernel<dt()>, dim3(arseg_grid_for((long long)N * Hout * Wout * (C >> 3))), dim3(256), 0, arseg_stream(stream),
+                           (const uint16_t *)in, (uint16_t *)out, N, C, Hin, Win, Hout, Wout, mode, align_corners, in_ld, out_ld);
+        return arseg_launch_status();
+    });
+}
+
+extern "C" int arseg_scale_add16_fwd(const void *x, const void *scale, const void *add_full, const void *add_vec, void *out, int dtype, int N, int HW, int C,
+                                     arseg_stream_t stream) {
+    ARSEG_CHECK_PTR(x); ARSEG_CHECK_PTR(scale); ARSEG_CHECK_PTR(out); ARSEG_CHECK_POS(N); ARSEG_CHECK_POS(HW); ARSEG_CHECK_POS(C);
+    if ((C & 7) || !ARSEG_ALIGNED16(x) || !ARSEG_ALIGNED16(scale) || !ARSEG_ALIGNED16(out) || (add_full && !ARSEG_ALIGNED16(add_full)) || (add_vec && !ARSEG_ALIGNED16(add_vec)))
+        return ARSEG_EINVAL;
+    return arseg_dispatch16(dtype, [&](auto dt) {
+        hipLaunchKernelGGL(scale_add_kernel<dt()>, dim3(arseg_grid_for((long long)N * HW * (C >> 3))), dim3(256), 0, arseg_stream(stream), (const uint16_t *)x,
+                           (const uint16_t *)scale, (const uint16_t *)add_full, (const uint16_t *)add_vec, (uint16_t *)out, N, HW, C);
+        return arseg_launch_status();
+    });
+}
+
+extern "C" int arseg_head16_fwd(const void *p, int p_ld, int dtype, const float *wf, const float *bf, float *logits, int N, int HW, int C, int n_cls,
+                                int log_softmax, arseg_stream_t stream) {
+    ARSEG_CHECK_PTR(p); ARSEG_CHECK_PTR(wf); ARSEG_CHECK_PTR(bf); ARSEG_CHECK_PTR(logits); ARSEG_CHECK_POS(N); ARSEG_CHECK_POS(HW); ARSEG_CHECK_POS(C); ARSEG_CHECK_POS(n_cls);
+    if ((C & 7) || (p_ld & 7) || p_ld < C || !ARSEG_ALIGNED16(p)) return ARSEG_EINVAL;
+    if (n_cls > 32) return ARSEG_EUNSUPPORTED;
+    const bool mfma = !(C & 63) && C <= 512 && ARSEG_ALIGNED16(wf);          // fp32 matrix-core kernel, 64-channel chunks
+    const size_t smem = (size_t)n_cls * C * sizeof(float);
+    if (!mfma && smem > 64 * 1024) return ARSEG_EUNSUPPORTED;
+    return arseg_dispatch16(dtype, [&](auto dt) {
+        hipStream_t st = arseg_stream(stream);
+        const uint16_t *pp = (const uint16_t *)p;
+        if (mfma) {
+            const size_t sm = (size_t)(32 * (C + 4) + 32 + 4 * 32 * 68) * sizeof(float);
+            static ArsegSmemAttr attr;          // (one per instantiation of this lambda: one per dtype)
+            const long long ntile = ((long long)N * HW + 31) / 32;
+            const long long gb = (ntile + 3) / 4;
+            if (int e = arseg_allow_smem(attr, reinterpret_cast<const void *>(head16_mfma_kernel<dt()>), sm)) return e;
+            hipLaunchKernelGGL(head16_mfma_kernel<dt()>, dim3((unsigned)(gb > 2048 ? 2048 : gb)), dim3(256), sm, st, pp, p_ld, wf, bf, logits, N, HW, C, n_cls, log_softmax);
+            return arseg_launch_status();
+        }
+        const int g = arseg_grid_for((long long)N * HW, 2048);
+        if (n_cls <= 12) hipLaunchKernelGGL((head_kernel<dt(), 12>), dim3(g), dim3(256), smem, st, pp, p_ld, wf, bf, logits, N, HW, C, n_cls, log_softmax);
+        else if (n_cls <= 19) hipLaunchKernelGGL((head_kernel<dt(), 19>), dim3(g), dim3(256), smem, st, pp, p_ld, wf, bf, logits, N, HW, C, n_cls, log_softmax);
+        else hipLaunchKernelGGL((head_kernel<dt(), 32>), dim3(g), dim3(256), smem, st, pp, p_ld, wf, bf, logits, N, HW, C, n_cls, log_softmax);
+        return arseg_launch_status();
+    });
+}
+
+extern "C" int arseg_cast_fwd(const void *in, int in_dtype, void *out, int out_dtype, long long count, arseg_stream_t stream) {
+    ARSEG_CHECK_PTR(in); ARSEG_CHECK_PTR(out);
+    if (count <= 0 || (count & 7) || !ARSEG_ALIGNED16(in) || !ARSEG_ALIGNED16(out)) return ARSEG_EINVAL;
+    const int g = arseg_grid_for(count / 8);
+    hipStream_t st = arseg_stream(stream);
+    if (out_dtype == ARSEG_DT_F32)
+        return arseg_dispatch16(in_dtype, [&](auto dt) {
+            hipLaunchKernelGGL(cast_to32_kernel<dt()>, dim3(g), dim3(256), 0, st, (const uint16_t *)in, (float *)out, count / 8);
+            return arseg_launch_status();
+        });
+    if (in_dtype == ARSEG_DT_F32)
+        return arseg_dispatch16(out_dtype, [&](auto dt) {
+            hipLaunchKernelGGL(cast_to16_kernel<dt()>, dim3(g), dim3(256), 0, st, (const float *)in, (uint16_t *)out, count / 8);
+            return arseg_launch_status();
+        });
+    return ARSEG_EINVAL;
 }

@@ -8,6 +8,7 @@
 //   ix    = ((g + 1) * W - 1) / 2          (grid_sample, align_corners=False default, fp32)
 //   4-tap bilinear, taps outside the image contribute zero (padding_mode='zeros').
 // Note zero motion is NOT the identity: ix = x*W/(W-1) - 0.5.
+#include "arseg_device.h"
 #include "warp_math.h"
 
 namespace {
@@ -110,24 +111,7 @@ __global__ __launch_bounds__(256) void warp_mvq_nhwc_kernel(const float *__restr
     __shared__ int s_off[4][64];
     __shared__ float s_w[4][64];
     const int tid = threadIdx.x, y = blockIdx.y, n = blockIdx.z, xb = blockIdx.x * 64;
-    if (tid < 64) {
-        const int x = min(xb + tid, Wp - 1);                                  // clamped: surplus lanes redo the last pixel
-        double fx, fy;
-        if (Hp == H && Wp == W) {              // identity resize (PSPNet): (q/4 * Hp) / H == q/4 exactly
-            const int16_t *m = mv + ((size_t)n * H * W + (size_t)y * W + x) * 2;
-            fx = (double)m[0] / 4.0; fy = (double)m[1] / 4.0;
-        } else {
-            mv_at(mv + (size_t)n * H * W * 2, H, W, Hp, Wp, y, x, fx, fy);
-        }
-        float gx, gy;
-        norm_grid<double>(x, y, fx, fy, Hp, Wp, gx, gy);
-        const Taps t = make_taps(gx, gy, Hp, Wp);
-        const int xa = min(max(t.x0, 0), Wp - 1), xc = min(max(t.x0 + 1, 0), Wp - 1);
-        const int ya = min(max(t.y0, 0), Hp - 1), yc = min(max(t.y0 + 1, 0), Hp - 1);
-        s_off[0][tid] = ya * Wp + xa; s_off[1][tid] = ya * Wp + xc; s_off[2][tid] = yc * Wp + xa; s_off[3][tid] = yc * Wp + xc;
-        s_w[0][tid] = t.vy0 && t.vx0 ? t.wnw : 0.f; s_w[1][tid] = t.vy0 && t.vx1 ? t.wne : 0.f;
-        s_w[2][tid] = t.vy1 && t.vx0 ? t.wsw : 0.f; s_w[3][tid] = t.vy1 && t.vx1 ? t.wse : 0.f;
-    }
+    if (tid < 64) warp_mvq_taps(mv, n, y, min(xb + tid, Wp - 1), Hp, Wp, H, W, tid, s_off, s_w);          // clamped: surplus lanes redo the last pixel
     __syncthreads();
     const int sub = tid & 15;
     const float *img = feat + (size_t)n * Hp * Wp * C;
@@ -146,6 +130,44 @@ __global__ __launch_bounds__(256) void warp_mvq_nhwc_kernel(const float *__restr
             acc += *reinterpret_cast<const f32x4 *>(img + (size_t)o3 * C + c) * w3;
             const size_t o = c8 ? ((((size_t)n * (C >> 3) + (c >> 3)) * hw + pix) * 8 + (c & 4)) : (((size_t)n * hw + pix) * C + c);
             *reinterpret_cast<f32x4 *>(out + o) = acc;      // (duplicate lanes of a clamped pixel store identical values)
+        }
+    }
+}
+
+// The same for a 16-bit NHWC keyframe feature -> fp32 C8 (the CReFF kernels' input): 8 lanes per pixel move 8-channel vectors; the blend
+// is fp32 on the converted taps, in its own order (a*w0 + b*w1 + ..., where the fp32 kernel above starts from 0).
+template <int DT>
+__global__ __launch_bounds__(256) void warp_mvq16_kernel(const uint16_t *__restrict__ feat, const int16_t *__restrict__ mv, float *__restrict__ out, int N, int C,
+                                                         int Hp, int Wp, int H, int W, long long feat_n_stride) {
+    __shared__ int s_off[4][64];
+    __shared__ float s_w[4][64];
+    const int tid = threadIdx.x, y = blockIdx.y, n = blockIdx.z, xb = blockIdx.x * 64;
+    if (tid < 64) warp_mvq_taps(mv, n, y, min(xb + tid, Wp - 1), Hp, Wp, H, W, tid, s_off, s_w);
+    __syncthreads();
+    const int sub = tid & 7;
+    const uint16_t *img = feat + (size_t)n * feat_n_stride;       // (stride 0: the frames of a GOP sample one keyframe feature)
+    const int hw = Hp * Wp;
+#pragma unroll
+    for (int it = 0; it < 2; ++it) {
+        const int pl = it * 32 + (tid >> 3);
+        const int x = min(xb + pl, Wp - 1), pix = y * Wp + x;
+        const int o0 = s_off[0][pl], o1 = s_off[1][pl], o2 = s_off[2][pl], o3 = s_off[3][pl];
+        const float w0 = s_w[0][pl], w1 = s_w[1][pl], w2 = s_w[2][pl], w3 = s_w[3][pl];
+        for (int c = sub * 8; c < C; c += 64) {
+            float a[8], b[8], cc[8], d[8];
+            ArsegStore<DT>::ld(img + (size_t)o0 * C + c, a);
+            ArsegStore<DT>::ld(img + (size_t)o1 * C + c, b);
+            ArsegStore<DT>::ld(img + (size_t)o2 * C + c, cc);
+            ArsegStore<DT>::ld(img + (size_t)o3 * C + c, d);
+            f32x4 r0, r1;
+#pragma unroll
+            for (int e = 0; e < 4; ++e) {
+                r0[e] = a[e] * w0 + b[e] * w1 + cc[e] * w2 + d[e] * w3;
+                r1[e] = a[4 + e] * w0 + b[4 + e] * w1 + cc[4 + e] * w2 + d[4 + e] * w3;
+            }
+            float *o = out + (((size_t)n * (C >> 3) + (c >> 3)) * hw + pix) * 8;      // C8: [N][C/8][H][W][8]
+            *reinterpret_cast<f32x4 *>(o) = r0;
+            *reinterpret_cast<f32x4 *>(o + 4) = r1;
         }
     }
 }
@@ -212,4 +234,23 @@ extern "C" int arseg_warp_mvq_fwd(const float *feature, const int16_t *mv_q, flo
     hipLaunchKernelGGL(warp_mvq_nhwc_kernel, dim3(arseg_cdiv(Wp, 64), Hp, N), dim3(256), 0, arseg_stream(stream), feature, mv_q, out, N, C,
                        Hp, Wp, H, W, out_layout == ARSEG_C8 ? 1 : 0);
     return arseg_launch_status();
+}
+
+extern "C" int arseg_warp_mvq16_fwd(const void *feature, int dtype, const int16_t *mv_q, float *out_c8, int N, int C, int Hp, int Wp, int H, int W,
+                                    arseg_stream_t stream) {
+    return arseg_warp_mvq16_shared_fwd(feature, (long long)Hp * Wp * C, dtype, mv_q, out_c8, N, C, Hp, Wp, H, W, stream);
+}
+
+extern "C" int arseg_warp_mvq16_shared_fwd(const void *feature, long long feat_n_stride, int dtype, const int16_t *mv_q, float *out_c8, int N, int C,
+                                           int Hp, int Wp, int H, int W, arseg_stream_t stream) {
+    if (feat_n_stride < 0 || (feat_n_stride & 7)) return ARSEG_EINVAL;
+    ARSEG_CHECK_PTR(feature); ARSEG_CHECK_PTR(mv_q); ARSEG_CHECK_PTR(out_c8);
+    ARSEG_CHECK_POS(N); ARSEG_CHECK_POS(C); ARSEG_CHECK_POS(H); ARSEG_CHECK_POS(W); ARSEG_CHECK_POS(Hp); ARSEG_CHECK_POS(Wp);
+    if ((C & 7) || !ARSEG_ALIGNED16(feature) || !ARSEG_ALIGNED16(out_c8)) return ARSEG_EINVAL;
+    if (Hp > 65535 || N > 65535) return ARSEG_EUNSUPPORTED;
+    return arseg_dispatch16(dtype, [&](auto dt) {
+        hipLaunchKernelGGL(warp_mvq16_kernel<dt()>, dim3(arseg_cdiv(Wp, 64), Hp, N), dim3(256), 0, arseg_stream(stream), (const uint16_t *)feature, mv_q, out_c8, N, C,
+                           Hp, Wp, H, W, feat_n_stride);
+        return arseg_launch_status();
+    });
 }

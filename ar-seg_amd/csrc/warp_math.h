@@ -66,3 +66,25 @@ __device__ __forceinline__ void mv_at(const int16_t *__restrict__ mv, int H, int
     }
     fx = v[0]; fy = v[1];
 }
+
+// The tap table of the MV-guided warps (warp_mvq_nhwc_kernel, warp_mvq16_kernel: warp.hip): lane `slot` does the fp64 coordinate arithmetic
+// of pixel (x, y) of frame n on the Hp x Wp map and parks the four tap offsets and weights in LDS.  Branch-free taps: one outside the
+// image gets weight 0 and a clamped (in-range) offset.
+__device__ __forceinline__ void warp_mvq_taps(const int16_t *__restrict__ mv, int n, int y, int x, int Hp, int Wp, int H, int W, int slot,
+                                              int (&s_off)[4][64], float (&s_w)[4][64]) {
+    double fx, fy;
+    if (Hp == H && Wp == W) {              // identity resize (PSPNet): (q/4 * Hp) / H == q/4 exactly
+        const int16_t *m = mv + ((size_t)n * H * W + (size_t)y * W + x) * 2;
+        fx = (double)m[0] / 4.0; fy = (double)m[1] / 4.0;
+    } else {
+        mv_at(mv + (size_t)n * H * W * 2, H, W, Hp, Wp, y, x, fx, fy);
+    }
+    float gx, gy;
+    norm_grid<double>(x, y, fx, fy, Hp, Wp, gx, gy);
+    const Taps t = make_taps(gx, gy, Hp, Wp);
+    const int xa = min(max(t.x0, 0), Wp - 1), xc = min(max(t.x0 + 1, 0), Wp - 1);
+    const int ya = min(max(t.y0, 0), Hp - 1), yc = min(max(t.y0 + 1, 0), Hp - 1);
+    s_off[0][slot] = ya * Wp + xa; s_off[1][slot] = ya * Wp + xc; s_off[2][slot] = yc * Wp + xa; s_off[3][slot] = yc * Wp + xc;
+    s_w[0][slot] = t.vy0 && t.vx0 ? t.wnw : 0.f; s_w[1][slot] = t.vy0 && t.vx1 ? t.wne : 0.f;
+    s_w[2][slot] = t.vy1 && t.vx0 ? t.wsw : 0.f; s_w[3][slot] = t.vy1 && t.vx1 ? t.wse : 0.f;
+}

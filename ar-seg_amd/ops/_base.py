@@ -46,6 +46,15 @@ def _need_gpu16(*tensors):
     return _DT16[dt]
 
 
+def _storage(*tensors) -> Optional[int]:
+    """Checks the tensors of a small layer (on the GPU, all of one storage dtype) and returns the ABI dtype code of 16-bit storage
+    (fp16 / bf16), or None for fp32.  The first tensor decides which of the two it is."""
+    if is16(next(t for t in tensors if t is not None)):
+        return _need_gpu16(*tensors)
+    _need_gpu(*tensors)
+    return None
+
+
 def _ptr(t: Optional[torch.Tensor]):
     return ctypes.c_void_p(0 if t is None else t.data_ptr())
 

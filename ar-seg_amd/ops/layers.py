@@ -8,7 +8,7 @@ from typing import Optional
 import torch
 
 from .. import _lib
-from ._base import _DT16, _need_gpu, _need_gpu16, _nhwc_ld, _ptr, _stream, is16, workspace
+from ._base import _DT16, _need_gpu, _need_gpu16, _nhwc_ld, _ptr, _storage, _stream, is16, workspace
 from ._profile import launch
 
 
@@ -230,19 +230,19 @@ def local_weighting(v: torch.Tensor, w: torch.Tensor, kH: int, kW: int) -> torch
 # ----------------------------------------------------------------------------------------------
 # small layers
 # ----------------------------------------------------------------------------------------------
+# A layer that exists in both storages makes one call: `dt = _storage(...)` is the 16-bit dtype code or None (fp32); the 16-bit entry point
+# takes the code as an extra argument (``*_dt(dt)``) and the result has the input's dtype.
+def _dt(dt):
+    return () if dt is None else (dt,)
+
+
 def maxpool3x3s2(x: torch.Tensor) -> torch.Tensor:
-    if is16(x):
-        dt = _need_gpu16(x)
-        x = x.contiguous()
-        N, H, W, C = x.shape
-        out = torch.empty((N, (H - 1) // 2 + 1, (W - 1) // 2 + 1, C), dtype=x.dtype, device=x.device)
-        launch("maxpool", _lib.load().arseg_maxpool3x3s2_16_fwd, _ptr(x), _ptr(out), dt, N, H, W, C, _stream())
-        return out
-    _need_gpu(x)
+    dt = _storage(x)
     x = x.contiguous()
     N, H, W, C = x.shape
-    out = torch.empty((N, (H - 1) // 2 + 1, (W - 1) // 2 + 1, C), dtype=torch.float32, device=x.device)
-    launch("maxpool", _lib.load().arseg_maxpool3x3s2_fwd, _ptr(x), _ptr(out), N, H, W, C, _stream())
+    out = torch.empty((N, (H - 1) // 2 + 1, (W - 1) // 2 + 1, C), dtype=x.dtype, device=x.device)
+    lib = _lib.load()
+    launch("maxpool", lib.arseg_maxpool3x3s2_fwd if dt is None else lib.arseg_maxpool3x3s2_16_fwd, _ptr(x), _ptr(out), *_dt(dt), N, H, W, C, _stream())
     return out
 
 
@@ -263,104 +263,76 @@ def psp_pool_matrix(x: torch.Tensor, sizes) -> torch.Tensor:
     """The folded pyramid's block-structured pooled matrix [N, sum(s^2), 1, len(sizes)*C]: level i's adaptive average pool in columns
     [i*C, (i+1)*C) of its s_i^2 rows, zeros elsewhere -- written entirely by the pooling launches (no fill).
     16-bit input: arseg_psp_pool_matrix16_fwd, the matrix in the storage dtype."""
-    if is16(x):
-        return _psp_pool_matrix16(x, sizes)
-    _need_gpu(x)
-    N, H, W, C = x.shape
-    n, rows = len(sizes), sum(s * s for s in sizes)
-    out = torch.empty((N, rows, 1, n * C), dtype=torch.float32, device=x.device)
-    lib = _lib.load()
-    arr = (ctypes.c_int * n)(*[int(s) for s in sizes])
-    nb = lib.arseg_psp_pool_matrix_workspace_bytes(N, H, W, C, n, arr) if (n <= 4 and C % 4 == 0 and N <= 65535) else 0
-    if nb:          # one pass over the map: the cells of the grid spanned by all bin edges are summed once, then combined per bin
-        ws = torch.empty((nb // 4,), dtype=torch.float32, device=x.device)
-        launch("adaptive_avgpool", lib.arseg_psp_pool_matrix_fwd, _ptr(x), _nhwc_ld(x), _ptr(out), _ptr(ws), nb, N, H, W, C, n, arr, _stream())
-        return out
-    off = 0
-    for i, s in enumerate(sizes):
-        launch("adaptive_avgpool", _lib.load().arseg_adaptive_avgpool_blockrow_fwd, _ptr(x), _nhwc_ld(x), _ptr(out[0, off]), rows * n * C,
-                N, H, W, C, s, s, n, i, _stream())
-        off += s * s
-    return out
-
-
-def _psp_pool_matrix16(x, sizes):
-    dt = _need_gpu16(x)
+    dt = _storage(x)
     N, H, W, C = x.shape
     n, rows = len(sizes), sum(s * s for s in sizes)
     out = torch.empty((N, rows, 1, n * C), dtype=x.dtype, device=x.device)
     lib = _lib.load()
     arr = (ctypes.c_int * n)(*[int(s) for s in sizes])
-    nb = lib.arseg_psp_pool_matrix16_workspace_bytes(N, H, W, C, n, arr)
-    if not nb:
-        raise _lib.ArsegError(f"psp_pool_matrix (16-bit): pyramid sizes {tuple(sizes)} are not supported (at most 4 levels of size <= 6)")
-    ws = workspace(nb, x.device)
-    launch("adaptive_avgpool", lib.arseg_psp_pool_matrix16_fwd, _ptr(x), _nhwc_ld(x), _ptr(out), dt, _ptr(ws), nb, N, H, W, C, n, arr, _stream())
+    if dt is not None:
+        nb = lib.arseg_psp_pool_matrix16_workspace_bytes(N, H, W, C, n, arr)
+        if not nb:
+            raise _lib.ArsegError(f"psp_pool_matrix (16-bit): pyramid sizes {tuple(sizes)} are not supported (at most 4 levels of size <= 6)")
+        ws = workspace(nb, x.device)
+    else:
+        nb = lib.arseg_psp_pool_matrix_workspace_bytes(N, H, W, C, n, arr) if (n <= 4 and C % 4 == 0 and N <= 65535) else 0
+        ws = torch.empty((nb // 4,), dtype=torch.float32, device=x.device) if nb else None
+    if nb:          # one pass over the map: the cells of the grid spanned by all bin edges are summed once, then combined per bin
+        launch("adaptive_avgpool", lib.arseg_psp_pool_matrix_fwd if dt is None else lib.arseg_psp_pool_matrix16_fwd, _ptr(x), _nhwc_ld(x), _ptr(out), *_dt(dt),
+               _ptr(ws), nb, N, H, W, C, n, arr, _stream())
+        return out
+    off = 0
+    for i, s in enumerate(sizes):          # (fp32 only: a pyramid the one-pass form does not take, level by level)
+        launch("adaptive_avgpool", lib.arseg_adaptive_avgpool_blockrow_fwd, _ptr(x), _nhwc_ld(x), _ptr(out[0, off]), rows * n * C,
+                N, H, W, C, s, s, n, i, _stream())
+        off += s * s
     return out
 
 
 def psp_prior_sum(t: torch.Tensor, sizes, H: int, W: int) -> torch.Tensor:
     """t [N, sum(s^2), C] (per-level maps after the folded 1x1 convs) -> [N,H,W,C] sum of bilinear upsamples (16-bit t: in the storage dtype,
     summed in fp32 and rounded once)."""
-    if is16(t):
-        dt = _need_gpu16(t)
-        t = t.contiguous()
-        N, rows, C = t.shape
-        if rows != sum(s * s for s in sizes):
-            raise _lib.ArsegError("psp_prior_sum: row count does not match the pyramid sizes")
-        out = torch.empty((N, H, W, C), dtype=t.dtype, device=t.device)
-        arr = (ctypes.c_int * len(sizes))(*[int(s) for s in sizes])
-        launch("psp_prior_sum", _lib.load().arseg_psp_prior_sum16_fwd, _ptr(t), _ptr(out), dt, N, H, W, C, len(sizes), arr, _stream())
-        return out
-    _need_gpu(t)
+    dt = _storage(t)
     t = t.contiguous()
     N, rows, C = t.shape
     if rows != sum(s * s for s in sizes):
         raise _lib.ArsegError("psp_prior_sum: row count does not match the pyramid sizes")
-    out = torch.empty((N, H, W, C), dtype=torch.float32, device=t.device)
+    out = torch.empty((N, H, W, C), dtype=t.dtype, device=t.device)
     arr = (ctypes.c_int * len(sizes))(*[int(s) for s in sizes])
-    launch("psp_prior_sum", _lib.load().arseg_psp_prior_sum_fwd, _ptr(t), _ptr(out), N, H, W, C, len(sizes), arr, _stream())
+    lib = _lib.load()
+    launch("psp_prior_sum", lib.arseg_psp_prior_sum_fwd if dt is None else lib.arseg_psp_prior_sum16_fwd, _ptr(t), _ptr(out), *_dt(dt), N, H, W, C, len(sizes),
+           arr, _stream())
     return out
 
 
 def global_reduce(x: torch.Tensor, op: int) -> torch.Tensor:
     """NHWC -> [N,1,1,C] mean or max over (H,W)."""
-    if is16(x):
-        dt = _need_gpu16(x)
-        if op not in (_lib.REDUCE_MEAN, _lib.REDUCE_MAX):
-            raise _lib.ArsegError(f"global_reduce: unknown op {op}")
-        N, H, W, C = x.shape
-        out = torch.empty((N, 1, 1, C), dtype=x.dtype, device=x.device)
-        nb = _lib.load().arseg_global_mean16_workspace_bytes(N, H, W, C)
-        ws = workspace(nb, x.device)
-        fn = _lib.load().arseg_global_mean16_fwd if op == _lib.REDUCE_MEAN else _lib.load().arseg_global_max16_fwd
-        launch("global_reduce", fn, _ptr(x), _nhwc_ld(x), _ptr(out), dt, N, H, W, C, _ptr(ws), nb, _stream())
-        return out
-    _need_gpu(x)
+    dt = _storage(x)
     N, H, W, C = x.shape
-    out = torch.empty((N, 1, 1, C), dtype=torch.float32, device=x.device)
+    out = torch.empty((N, 1, 1, C), dtype=x.dtype, device=x.device)
     lib = _lib.load()
-    nb = lib.arseg_global_reduce_workspace_bytes(N, H, W, C)
-    ws = torch.empty((nb // 4,), dtype=torch.float32, device=x.device) if nb else None       # (large map, few images: two-stage reduce)
-    launch("global_reduce", lib.arseg_global_reduce_ws_fwd, _ptr(x), _nhwc_ld(x), _ptr(out), _ptr(ws), nb, N, H, W, C, op, _stream())
+    if dt is None:
+        nb = lib.arseg_global_reduce_workspace_bytes(N, H, W, C)
+        ws = torch.empty((nb // 4,), dtype=torch.float32, device=x.device) if nb else None       # (large map, few images: two-stage reduce)
+        launch("global_reduce", lib.arseg_global_reduce_ws_fwd, _ptr(x), _nhwc_ld(x), _ptr(out), _ptr(ws), nb, N, H, W, C, op, _stream())
+        return out
+    if op not in (_lib.REDUCE_MEAN, _lib.REDUCE_MAX):          # (16-bit storage: one entry point per op, slices and a final pass)
+        raise _lib.ArsegError(f"global_reduce: unknown op {op}")
+    nb = lib.arseg_global_mean16_workspace_bytes(N, H, W, C)
+    ws = workspace(nb, x.device)
+    launch("global_reduce", lib.arseg_global_mean16_fwd if op == _lib.REDUCE_MEAN else lib.arseg_global_max16_fwd, _ptr(x), _nhwc_ld(x), _ptr(out), dt,
+           N, H, W, C, _ptr(ws), nb, _stream())
     return out
 
 
 def resize_nhwc(x: torch.Tensor, Hout: int, Wout: int, mode: int, align_corners: bool, out: Optional[torch.Tensor] = None) -> torch.Tensor:
-    if is16(x):
-        dt = _need_gpu16(x, out)
-        N, H, W, C = x.shape
-        if out is None:
-            out = torch.empty((N, Hout, Wout, C), dtype=x.dtype, device=x.device)
-        launch("resize_nhwc", _lib.load().arseg_resize16_fwd, _ptr(x), _ptr(out), dt, N, C, H, W, Hout, Wout, mode, 1 if align_corners else 0,
-                _nhwc_ld(x), _nhwc_ld(out), _stream())
-        return out
-    _need_gpu(x, out)
+    dt = _storage(x, out)
     N, H, W, C = x.shape
     if out is None:
-        out = torch.empty((N, Hout, Wout, C), dtype=torch.float32, device=x.device)
-    launch("resize_nhwc", _lib.load().arseg_resize_fwd, _ptr(x), _ptr(out), N, C, H, W, Hout, Wout, mode, 1 if align_corners else 0, _lib.NHWC,
-                                       _nhwc_ld(x), _nhwc_ld(out), _stream())
+        out = torch.empty((N, Hout, Wout, C), dtype=x.dtype, device=x.device)
+    lib = _lib.load()
+    launch("resize_nhwc", lib.arseg_resize_fwd if dt is None else lib.arseg_resize16_fwd, _ptr(x), _ptr(out), *_dt(dt), N, C, H, W, Hout, Wout, mode,
+           1 if align_corners else 0, *((_lib.NHWC,) if dt is None else ()), _nhwc_ld(x), _nhwc_ld(out), _stream())
     return out
 
 
@@ -377,42 +349,27 @@ def resize_nchw(x: torch.Tensor, Hout: int, Wout: int, mode: int, align_corners:
 def scale_add(x: torch.Tensor, scale: torch.Tensor, add_full: Optional[torch.Tensor] = None, add_vec: Optional[torch.Tensor] = None
               ) -> torch.Tensor:
     """out = x * scale[n,c] (+ add_full[n,h,w,c]) (+ add_vec[n,c]); x NHWC contiguous, scale/add_vec [N,1,1,C]."""
-    if is16(x):
-        dt = _need_gpu16(x, scale, add_full, add_vec)
-        x = x.contiguous()
-        N, H, W, C = x.shape
-        out = torch.empty_like(x)
-        launch("scale_add", _lib.load().arseg_scale_add16_fwd, _ptr(x), _ptr(scale.contiguous()), _ptr(None if add_full is None else add_full.contiguous()),
-                _ptr(None if add_vec is None else add_vec.contiguous()), _ptr(out), dt, N, H * W, C, _stream())
-        return out
-    _need_gpu(x, scale, add_full, add_vec)
+    dt = _storage(x, scale, add_full, add_vec)
     x = x.contiguous()
     N, H, W, C = x.shape
     out = torch.empty_like(x)
-    if add_full is not None:
-        add_full = add_full.contiguous()
-    launch("scale_add", _lib.load().arseg_scale_add_fwd, _ptr(x), _ptr(scale.contiguous()), _ptr(add_full),
-                                          _ptr(None if add_vec is None else add_vec.contiguous()), _ptr(out), N, H * W, C, _stream())
+    lib = _lib.load()
+    launch("scale_add", lib.arseg_scale_add_fwd if dt is None else lib.arseg_scale_add16_fwd, _ptr(x), _ptr(scale.contiguous()),
+           _ptr(None if add_full is None else add_full.contiguous()), _ptr(None if add_vec is None else add_vec.contiguous()), _ptr(out), *_dt(dt), N, H * W, C,
+           _stream())
     return out
 
 
 def head(p_nhwc: torch.Tensor, wf: torch.Tensor, bf: torch.Tensor, log_softmax: bool) -> torch.Tensor:
-    """1x1 classifier on an NHWC feature -> NCHW logits (optionally LogSoftmax over classes)."""
-    if is16(p_nhwc):
-        dt = _need_gpu16(p_nhwc)
-        _need_gpu(wf, bf)
-        N, H, W, C = p_nhwc.shape
-        n_cls = wf.shape[0]
-        out = torch.empty((N, n_cls, H, W), dtype=torch.float32, device=p_nhwc.device)
-        launch("head", _lib.load().arseg_head16_fwd, _ptr(p_nhwc), _nhwc_ld(p_nhwc), dt, _ptr(wf), _ptr(bf), _ptr(out), N, H * W, C, n_cls,
-                1 if log_softmax else 0, _stream())
-        return out
-    _need_gpu(p_nhwc, wf, bf)
+    """1x1 classifier on an NHWC feature (fp32 or 16-bit; fp32 weights) -> NCHW fp32 logits (optionally LogSoftmax over classes)."""
+    dt = _storage(p_nhwc)
+    _need_gpu(wf, bf)
     N, H, W, C = p_nhwc.shape
     n_cls = wf.shape[0]
     out = torch.empty((N, n_cls, H, W), dtype=torch.float32, device=p_nhwc.device)
-    launch("head", _lib.load().arseg_head_fwd, _ptr(p_nhwc), _nhwc_ld(p_nhwc), _ptr(wf), _ptr(bf), _ptr(out), N, H * W, C, n_cls,
-                                     1 if log_softmax else 0, _stream())
+    lib = _lib.load()
+    launch("head", lib.arseg_head_fwd if dt is None else lib.arseg_head16_fwd, _ptr(p_nhwc), _nhwc_ld(p_nhwc), *_dt(dt), _ptr(wf), _ptr(bf), _ptr(out), N, H * W,
+           C, n_cls, 1 if log_softmax else 0, _stream())
     return out
 
 

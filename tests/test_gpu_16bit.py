@@ -154,6 +154,98 @@ def test_small_layers16(dev, dtype):
     assert torch.equal(ops.cast(rnd(17, 4, 40).to(dev), dtype).cpu(), rnd(17, 4, 40).to(dtype))
 
 
+def _bits(x):
+    return x.contiguous().view(torch.int32 if x.dtype == torch.float32 else torch.int16)
+
+
+@pytest.mark.parametrize("k", [1, 3])
+@pytest.mark.parametrize("dtype", [torch.float32] + DTYPES)
+def test_vector_width_edges(dev, dtype, k):
+    """The small layers written once over the storage trait at C == V and C == 3 V (V = channels per 16-byte lane vector: 4 in fp32, 8 in
+    16-bit storage), against the torch expressions and tolerances of test_small_layers16 / tests/test_gpu_ops.py."""
+    from arseg_amd import _lib, ops
+
+    f32 = dtype == torch.float32
+    C = (4 if f32 else 8) * k
+
+    def close(got, want, extra, tol32):
+        if f32:
+            assert maxdiff(got, want) <= tol32
+        else:
+            close16(got, want, dtype, extra=extra)
+
+    x = rnd(70, 2, 5, 7, C).to(dtype)
+    xd, xc = x.to(dev), x.double().permute(0, 3, 1, 2)
+    got = ops.maxpool3x3s2(xd)
+    assert got.dtype == dtype and torch.equal(got.cpu(), F.max_pool2d(x.float().permute(0, 3, 1, 2), 3, 2, 1).permute(0, 2, 3, 1).to(dtype))
+    assert torch.equal(ops.resize_nhwc(xd, 11, 13, _lib.NEAREST, False).cpu(), F.interpolate(x.float().permute(0, 3, 1, 2), (11, 13)).permute(0, 2, 3, 1).to(dtype))
+    for al in (False, True):
+        want = F.interpolate(xc, (11, 13), mode="bilinear", align_corners=al)
+        close(ops.resize_nhwc(xd, 11, 13, _lib.BILINEAR, al).permute(0, 3, 1, 2), want, 1e-5, 1e-5)
+    sc, av, af = rnd(71, 2, 1, 1, C).to(dtype), rnd(72, 2, 1, 1, C).to(dtype), rnd(73, 2, 5, 7, C).to(dtype)
+    close(ops.scale_add(xd, sc.to(dev), add_full=af.to(dev), add_vec=av.to(dev)), x.double() * sc.double() + af.double() + av.double(), 1e-6, 1e-6)
+    close(ops.scale_add(xd, sc.to(dev), add_vec=av.to(dev)), x.double() * sc.double() + av.double(), 1e-6, 1e-6)
+    close(ops.scale_add(xd, sc.to(dev), add_full=af.to(dev)), x.double() * sc.double() + af.double(), 1e-6, 1e-6)
+    for n_cls, lsm in ((5, True), (19, False)):
+        wf, bf = rnd(74, n_cls, C, scale=0.2), rnd(75, n_cls, scale=0.1)
+        want = F.conv2d(xc, wf.double()[:, :, None, None], bf.double())
+        want = F.log_softmax(want, dim=1) if lsm else want
+        lg = ops.head(xd, wf.to(dev), bf.to(dev), log_softmax=lsm)
+        assert lg.dtype == torch.float32 and maxdiff(lg, want) <= (1e-4 if f32 else 2e-4)
+
+
+@pytest.mark.parametrize("dtype", DTYPES)
+def test_channel_slices16(dev, dtype):
+    """16-bit small layers on channel-slice views [..., 8:8+C] of wider NHWC buffers: bit-equal to the contiguous call, and a sliced output
+    leaves the channels around it alone."""
+    from arseg_amd import _lib, ops
+
+    C = 16
+    x = rnd(80, 2, 9, 6, C).to(dtype).to(dev)
+    wide = rnd(81, 2, 9, 6, C + 16).to(dtype).to(dev)
+    wide[..., 8:8 + C] = x
+    xs = wide[..., 8:8 + C]
+    for mode, al in ((_lib.NEAREST, False), (_lib.BILINEAR, False), (_lib.BILINEAR, True)):
+        want = ops.resize_nhwc(x, 18, 12, mode, al)
+        fill = rnd(82, 2, 18, 12, C + 16).to(dtype).to(dev)
+        ow = fill.clone()
+        got = ops.resize_nhwc(xs, 18, 12, mode, al, out=ow[..., 8:8 + C])
+        assert torch.equal(_bits(got), _bits(want))
+        assert torch.equal(_bits(ow[..., :8]), _bits(fill[..., :8])) and torch.equal(_bits(ow[..., 8 + C:]), _bits(fill[..., 8 + C:]))
+    for op in (_lib.REDUCE_MEAN, _lib.REDUCE_MAX):
+        assert torch.equal(_bits(ops.global_reduce(xs, op)), _bits(ops.global_reduce(x, op)))
+    for n_cls, lsm in ((5, True), (19, False)):
+        wf, bf = rnd(83, n_cls, C, scale=0.2).to(dev), rnd(84, n_cls, scale=0.1).to(dev)
+        assert torch.equal(_bits(ops.head(xs, wf, bf, lsm)), _bits(ops.head(x, wf, bf, lsm)))
+
+
+def _two_storage_cases():
+    from arseg_amd import _lib, ops
+
+    return {
+        "maxpool": ((2, 9, 13, 16), lambda x, r: ops.maxpool3x3s2(x)),
+        "psp_pool_matrix": ((2, 9, 13, 16), lambda x, r: ops.psp_pool_matrix(x, (1, 2, 3, 6))),
+        "resize_bilinear_aligned": ((2, 5, 7, 16), lambda x, r: ops.resize_nhwc(x, 11, 13, _lib.BILINEAR, True)),
+        "scale_add": ((2, 5, 7, 16), lambda x, r: ops.scale_add(x, r(91, 2, 1, 1, 16), add_full=r(92, 2, 5, 7, 16), add_vec=r(93, 2, 1, 1, 16))),
+    }
+
+
+@pytest.mark.parametrize("case", ["maxpool", "psp_pool_matrix", "resize_bilinear_aligned", "scale_add"])
+@pytest.mark.parametrize("dtype", DTYPES)
+def test_one_body_two_storages(dev, dtype, case):
+    """One kernel body serves both storages, so on inputs drawn in the 16-bit dtype the 16-bit result is the fp32 result rounded once:
+    op(x16) == op(x16.float()).to(dtype), bit for bit.  Left out on purpose: the bilinear blends with align_corners = 0 (resize_nhwc 5x7 -> 11x13
+    and psp_prior_sum to 9x13), whose vector form in fp32 storage and per-element form in 16-bit storage are contracted into different FMA chains
+    (csrc/layers.hip, bilerp) and have always differed in the last bit; and the generic head, whose dot product adds 4 terms per step in fp32
+    storage and 8 in 16-bit storage."""
+    shape, op = _two_storage_cases()[case]
+    x16 = rnd(90, *shape).to(dtype).to(dev)
+    got = op(x16, lambda seed, *s: rnd(seed, *s).to(dtype).to(dev))
+    want = op(x16.float(), lambda seed, *s: rnd(seed, *s).to(dtype).to(dev).float())
+    assert got.dtype == dtype and want.dtype == torch.float32
+    assert torch.equal(_bits(got), _bits(want.to(dtype)))
+
+
 @pytest.mark.parametrize("dtype", DTYPES)
 def test_warp_mvq16(dev, dtype):
     """MV resize + warp of a 16-bit keyframe feature (fp32 C8 out) against the oracle's warp of the same rounded feature."""
