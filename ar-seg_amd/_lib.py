@@ -6,6 +6,7 @@ is no Python / PyTorch fallback for any op.
 from __future__ import annotations
 
 import ctypes
+import functools
 import os
 from ctypes import POINTER, Structure, c_char_p, c_double, c_float, c_int, c_int16, c_int32, c_int64, c_size_t, c_uint64, c_void_p
 
@@ -21,6 +22,8 @@ NEAREST, BILINEAR = 0, 1
 REDUCE_MEAN, REDUCE_MAX = 0, 1
 MATH_F32, MATH_F16X3, MATH_F16 = 0, 1, 2
 DT_F32, DT_F16, DT_BF16 = 0, 1, 2
+CONV_ENGINE_F32, CONV_ENGINE_16 = 0, 1
+PLAN_NONE, PLAN_AUTO, PLAN_TILE, PLAN_TILE_WIDE, PLAN_PATCH, PLAN_STEM, PLAN_UP2_C64 = range(7)
 SRC_RGB8, SRC_NV12, SRC_I420, SRC_P010, SRC_I010 = 0, 1, 2, 3, 4
 COLOUR_BT601_LIMITED, COLOUR_BT601_FULL, COLOUR_BT709_LIMITED, COLOUR_BT709_FULL = 0, 1, 2, 3
 MVR_BI_LIST0, MVR_BI_NEAR, MVR_BI_MEAN = 0, 1, 2
@@ -37,6 +40,12 @@ class ConvDesc(Structure):
                 ("act", c_int), ("prelu_slope", c_float), ("tile_cfg", c_int), ("split_k", c_int),
                 ("batch", c_int), ("in_batch_stride", c_int64), ("w_batch_stride", c_int64), ("out_batch_stride", c_int64),
                 ("math", c_int), ("upsample2x", c_int), ("range_flag", c_void_p), ("range_limit", c_float)]
+
+
+class ConvPlanInfo(Structure):
+    """struct arseg_conv_plan_info (include/arseg_hip.h)."""
+    _fields_ = [("kind", c_int), ("bm", c_int), ("bn", c_int), ("bk", c_int), ("nbuf", c_int), ("fuses_upsample", c_int), ("split_k_allowed", c_int),
+                ("nsplit", c_int), ("patch_tw", c_int), ("patch_th", c_int), ("Ho", c_int), ("Wo", c_int), ("workspace_bytes", c_size_t)]
 
 
 _P = c_void_p  # device or host pointer passed as integer
@@ -62,6 +71,7 @@ PROTOTYPES = {
     "arseg_to_c8_fwd": (c_int, [_P, c_int, c_int, _P, c_int, c_int, c_int, _STREAM]),
     "arseg_from_c8_fwd": (c_int, [_P, _P, c_int, c_int, c_int, c_int, c_int, _STREAM]),
     "arseg_conv_out_hw": (c_int, [POINTER(ConvDesc), POINTER(c_int), POINTER(c_int)]),
+    "arseg_conv_plan_query": (c_int, [c_int, POINTER(ConvDesc), POINTER(ConvPlanInfo)]),
     "arseg_conv2d_workspace_bytes": (c_size_t, [POINTER(ConvDesc)]),
     "arseg_conv2d_fwd": (c_int, [POINTER(ConvDesc), _P, _P, _P, _P, _P, _P, _P, c_size_t, _STREAM]),
     "arseg_conv_up2_c64_fwd": (c_int, [POINTER(ConvDesc), _P, _P, _P, _P, _P, c_int, _STREAM]),
@@ -191,6 +201,23 @@ def load() -> ctypes.CDLL:
         raise ArsegError(f"ABI version mismatch: library reports {lib.arseg_version()}, binding expects {ABI_VERSION}")
     _lib = lib
     return lib
+
+
+@functools.lru_cache(maxsize=None)
+def conv_plan_row(engine: int, tile_cfg: int) -> ConvPlanInfo:
+    """What the id ``tile_cfg`` of a conv engine is (kind, bm, bn, bk, nbuf, fuses_upsample, split_k_allowed): the library's plan table, read
+    through arseg_conv_plan_query once per id.  kind == PLAN_NONE for a number that is no id."""
+    d, info = ConvDesc(), ConvPlanInfo()
+    d.tile_cfg = tile_cfg
+    load().arseg_conv_plan_query(engine, ctypes.byref(d), ctypes.byref(info))      # (the verdict on the empty descriptor is not asked for)
+    return info
+
+
+def conv_plan(engine: int, d: ConvDesc) -> ConvPlanInfo:
+    """arseg_conv_plan_query: what descriptor ``d`` launches on ``engine``; raises the verdict the launch would give."""
+    info = ConvPlanInfo()
+    check(load().arseg_conv_plan_query(engine, ctypes.byref(d), ctypes.byref(info)), "conv_plan_query")
+    return info
 
 
 def check(status: int, what: str) -> None:

@@ -14,6 +14,7 @@
 //   * epilogue through LDS: the fp32 accumulators are transposed into [pixel][co] rows so that scale / bias / residual / activation
 //     run on 8 consecutive channels and the store is a coalesced 16-byte vector of a full NHWC row.
 #include "arseg_device.h"
+#include "conv_plans.h"
 
 namespace {
 
@@ -511,18 +512,9 @@ int launch_patch16(const Conv16Params &p, hipStream_t st) {
     return arseg_launch_status();
 }
 template <bool BF, bool UP2>
-int launch_patch16_cfg(const Conv16Params &p, int cfg, hipStream_t st) {
-    switch (cfg) {
-        case 5: return launch_patch16<BF, 64, 2, UP2>(p, st);
-        case 6: return launch_patch16<BF, 128, 2, UP2>(p, st);
-        case 7: case 10: case 11: return launch_patch16<BF, 64, 4, UP2>(p, st);
-        case 13: return launch_patch16<BF, 64, 2, UP2>(p, st);
-        default: return launch_patch16<BF, 128, 4, UP2>(p, st);      // 8, 12
-    }
-}
-template <bool BF>
-int launch_patch16_any(const Conv16Params &p, int cfg, bool up2, hipStream_t st) {
-    return up2 ? launch_patch16_cfg<BF, true>(p, cfg, st) : launch_patch16_cfg<BF, false>(p, cfg, st);
+int launch_patch16_tile(const Conv16Params &p, const ConvPlan &pl, hipStream_t st) {
+    if (pl.bm == 128) return pl.bn == 64 ? launch_patch16<BF, 64, 2, UP2>(p, st) : launch_patch16<BF, 128, 2, UP2>(p, st);
+    return pl.bn == 64 ? launch_patch16<BF, 64, 4, UP2>(p, st) : launch_patch16<BF, 128, 4, UP2>(p, st);
 }
 
 // ------------------------------------------------------------------------------------------------------------------------------
@@ -686,37 +678,60 @@ int launch_cfg(const Conv16Params &p, bool wide, bool deep, hipStream_t st) {
     return deep ? launch<BF, 64, 64>(p, st) : launch<BF, 64, 32>(p, st);
 }
 
-}  // namespace
-
-namespace {
-// split-K slices of a launch: explicit (desc.split_k >= 1) or, with 0, chosen so that a launch whose tiles do not fill the chip and
-// whose K loop is long gets ~2 workgroups per CU (the 16x32-map layers of BiSeNet-18: 176 tiles, K = 4608)
-int conv16_nsplit(const arseg_conv_desc *d, long long M, int Kpad, int co_t) {
-    if ((d->Cout & 7) || d->tile_cfg >= 5) return 1;          // (the patch-resident and stem plans have no split-K)
-    const int kt64 = Kpad / 64;
-    int ns = d->split_k;
-    if (ns <= 0) {
-        const long long tiles = (long long)arseg_cdiv(d->Cout, co_t) * arseg_cdiv(M, PIX_T);
-        ns = 1;
-        while (tiles * ns < 384 && ns < 8 && kt64 / (ns * 2) >= 6) ns *= 2;
-    }
+// The GEMM tile of a row on this shape (fills bn, bk, nsplit, tiles).  The auto plan takes 128-channel tiles when they still give every CU a few
+// workgroups, and K step 64 (half the barriers, 74 KB of LDS) for long K loops.  Split-K slices: explicit (desc.split_k >= 1) or, with 0, chosen
+// so that a launch whose tiles do not fill the chip and whose K loop is long gets ~2 workgroups per CU (the 16x32-map layers of BiSeNet-18:
+// 176 tiles, K = 4608); one slice where Cout % 8 (the reduce kernel is 8-wide)
+void conv16_gemm_tile(const arseg_conv_desc *d, const ConvPlanRow &row, ConvPlan *pl) {
+    pl->bn = row.bn ? row.bn : (d->Cout > 64 && (long long)arseg_cdiv(d->Cout, 128) * arseg_cdiv(pl->M, PIX_T) >= 512 ? 128 : 64);
+    pl->bk = row.bk ? row.bk : (pl->K >= 512 ? 64 : 32);
+    pl->tiles_n = arseg_cdiv(d->Cout, pl->bn); pl->tiles_m = arseg_cdiv(pl->M, PIX_T);
+    int ns = d->split_k, kt64 = pl->Kpad / 64;
+    if (ns <= 0)
+        for (ns = 1; (long long)pl->tiles_n * pl->tiles_m * ns < 384 && ns < 8 && kt64 / (ns * 2) >= 6;) ns *= 2;
     if (ns > kt64) ns = kt64;
-    return ns < 1 ? 1 : ns;
-}
-bool conv16_wide(const arseg_conv_desc *d, long long M) {
-    const int cfg = d->tile_cfg;
-    if (cfg == 0) return d->Cout > 64 && (long long)arseg_cdiv(d->Cout, 128) * arseg_cdiv(M, PIX_T) >= 512;
-    return cfg == 2 || cfg == 4;
+    pl->split((d->Cout & 7) || ns < 1 ? 1 : ns, d->Cout);
 }
 }  // namespace
 
+int conv16_plan(const arseg_conv_desc *d, ConvPlan *pl) {
+    if (!d) return ARSEG_EINVAL;
+    ARSEG_CHECK_POS(d->N); ARSEG_CHECK_POS(d->H); ARSEG_CHECK_POS(d->W); ARSEG_CHECK_POS(d->Cin); ARSEG_CHECK_POS(d->Cout);
+    ARSEG_CHECK_POS(d->R); ARSEG_CHECK_POS(d->S); ARSEG_CHECK_POS(d->stride); ARSEG_CHECK_POS(d->dil);
+    if ((d->Cin & 7) || (d->in_ld & 7) || d->in_ld < d->Cin || (d->out_ld & 7) || d->out_ld < d->Cout) return ARSEG_EINVAL;
+    if (d->batch > 1) return ARSEG_EUNSUPPORTED;
+    if (int e = conv_geometry(d, pl)) return e;
+    // (these extents also cover this engine's own 32-bit offsets: M < 2^31, in and w below 2^31 bytes)
+    if (!conv_fits_32bit(d, arseg_packed_k(d->Cin, d->R, d->S))) return ARSEG_EUNSUPPORTED;
+    pl->Kpad = (pl->K + KPAD - 1) / KPAD * KPAD;
+    // upsample2x: `in` is [N, H/2, W/2, in_ld]; only the patch-resident plans (auto = the 256-pixel, 64-channel one) stage its x2 upsample, for a 3x3
+    // stride-1 pad-1 conv with dil 1 on an even H x W.  Everything else is refused (a plan that ignored the flag would read the small tensor as H x W)
+    const bool up2 = d->upsample2x != 0;
+    const ConvPlanRow *row = conv_plan_row(kConvPlans16, d->tile_cfg);
+    if (up2 && row && row->kind == ARSEG_PLAN_AUTO) row = &kConvPlans16[kConv16AutoUp2];
+    if (up2 && ((d->H & 1) || (d->W & 1) || d->dil != 1 || d->R != 3 || d->S != 3 || d->stride != 1 || d->pad != 1 || (d->Cin & 63) || d->split_k > 1 ||
+                d->tile_cfg < 0 || (row && !row->fuses_up2)))
+        return row ? ARSEG_EUNSUPPORTED : ARSEG_EINVAL;
+    if (d->R * d->S > 64) return ARSEG_EUNSUPPORTED;          // (the multiply-high filter-row decode is exact for taps < 64: up to 7 x 7 and 8 x 8)
+    if (!row) return ARSEG_EINVAL;
+    pl->take(*row); pl->patch_tw = pl->patch_th = 0; pl->tiles_m = 0; pl->tiles_n = 1; pl->split(1, d->Cout); pl->ktiles = pl->ktiles_per_split = 0;
+    if (row->kind == ARSEG_PLAN_STEM)          // 7x7 stride-2 pad-3, NHWC8 -> 64 channels (and no residual: arseg_conv2d16_fwd)
+        return d->R == 7 && d->S == 7 && d->stride == 2 && d->pad == 3 && d->dil == 1 && d->Cin == 8 && d->Cout == 64 && d->split_k <= 1 ? ARSEG_OK : ARSEG_EUNSUPPORTED;
+    if (row->kind == ARSEG_PLAN_PATCH) return conv_patch_plan(d, *row, 63, pl);
+    if (d->split_k < 0) return ARSEG_EINVAL;
+    conv16_gemm_tile(d, *row, pl);
+    return ARSEG_OK;
+}
+
+// (0 for every descriptor the FP32 engine's arseg_conv_out_hw refuses, and with upsample2x, whose plans have no split-K: the gate this query
+// has always had.  arseg_conv_plan_query(ARSEG_CONV_ENGINE_16) gives this engine's own verdict and the same bytes wherever it accepts.)
 extern "C" size_t arseg_conv2d16_workspace_bytes(const arseg_conv_desc *d) {
-    int Ho, Wo;
-    if (!d || d->upsample2x || arseg_conv_out_hw(d, &Ho, &Wo) != ARSEG_OK) return 0;          // (the fused-upsample plans have no split-K)
-    const long long M = (long long)d->N * Ho * Wo;
-    const int Kpad = (d->R * d->S * d->Cin + KPAD - 1) / KPAD * KPAD;
-    const int ns = conv16_nsplit(d, M, Kpad, conv16_wide(d, M) ? 128 : 64);
-    return ns > 1 ? (size_t)ns * M * d->Cout * sizeof(float) : 0;
+    ConvPlan pl;
+    const ConvPlanRow *row = d ? conv_plan_row(kConvPlans16, d->tile_cfg) : nullptr;
+    if (!row || !row->split_k || d->upsample2x || arseg_conv_out_hw(d, &pl.Ho, &pl.Wo) != ARSEG_OK) return 0;
+    pl.M = d->N * pl.Ho * pl.Wo; pl.K = d->R * d->S * d->Cin; pl.Kpad = (pl.K + KPAD - 1) / KPAD * KPAD;
+    conv16_gemm_tile(d, *row, &pl);
+    return pl.workspace_bytes;
 }
 
 extern "C" int arseg_conv2d16_fwd(const arseg_conv_desc *d, int dtype, const void *in, const void *w_packed16, const float *scale,
@@ -724,80 +739,33 @@ extern "C" int arseg_conv2d16_fwd(const arseg_conv_desc *d, int dtype, const voi
                                   arseg_stream_t stream) {
     if (!d) return ARSEG_EINVAL;
     ARSEG_CHECK_PTR(in); ARSEG_CHECK_PTR(w_packed16); ARSEG_CHECK_PTR(out);
-    ARSEG_CHECK_POS(d->N); ARSEG_CHECK_POS(d->H); ARSEG_CHECK_POS(d->W); ARSEG_CHECK_POS(d->Cin); ARSEG_CHECK_POS(d->Cout);
-    ARSEG_CHECK_POS(d->R); ARSEG_CHECK_POS(d->S); ARSEG_CHECK_POS(d->stride); ARSEG_CHECK_POS(d->dil);
     if (dtype != ARSEG_DT_F16 && dtype != ARSEG_DT_BF16) return ARSEG_EINVAL;
-    if ((d->Cin & 7) || (d->in_ld & 7) || d->in_ld < d->Cin) return ARSEG_EINVAL;
-    if ((d->out_ld & 7) || d->out_ld < d->Cout || (residual && ((d->res_ld & 7) || d->res_ld < d->Cout))) return ARSEG_EINVAL;
+    if (residual && ((d->res_ld & 7) || d->res_ld < d->Cout)) return ARSEG_EINVAL;
     if (!ARSEG_ALIGNED16(in) || !ARSEG_ALIGNED16(w_packed16) || !ARSEG_ALIGNED16(out) || (residual && !ARSEG_ALIGNED16(residual))) return ARSEG_EINVAL;
-    if (d->batch > 1) return ARSEG_EUNSUPPORTED;
-    int Ho, Wo;
-    {
-        // the size query goes through the fp32 engine's plan check: it refuses upsample2x on plans that are not its own, and its tile_cfg 13
-        // is an f16x3-only patch plan -- this kernel's plan 13 was refused right here, for every shape, before it was looked at
-        arseg_conv_desc d0 = *d;
-        d0.upsample2x = 0; d0.tile_cfg = 0;
-        if (int e = arseg_conv_out_hw(&d0, &Ho, &Wo)) return e;
-    }
-    // upsample2x: `in` is [N, H/2, W/2, in_ld]; only the patch-resident plans (5..8, 10..13; 0 = 7) stage its x2 upsample, for a 3x3 stride-1
-    // pad-1 conv with dil 1 on an even H x W.  Everything else is refused (a plan that ignored the flag would read the small tensor as H x W)
+    ConvPlan pl;
+    if (int e = conv16_plan(d, &pl)) return e;
     const bool up2 = d->upsample2x != 0;
-    if (up2 && ((d->H & 1) || (d->W & 1) || d->dil != 1 || d->R != 3 || d->S != 3 || d->stride != 1 || d->pad != 1 || (d->Cin & 63) ||
-                d->split_k > 1 || d->tile_cfg < 0 || (d->tile_cfg >= 1 && d->tile_cfg <= 4) || d->tile_cfg == 9))
-        return d->tile_cfg < 0 || d->tile_cfg > 13 ? ARSEG_EINVAL : ARSEG_EUNSUPPORTED;
     Conv16Params p;
-    p.in = (const uint16_t *)in; p.w = (const uint16_t *)w_packed16; p.res = (const uint16_t *)residual; p.scale = scale; p.bias = bias;
-    p.out = (uint16_t *)out;
-    p.N = d->N; p.H = d->H; p.W = d->W; p.Cin = d->Cin; p.in_ld = d->in_ld; p.Ho = Ho; p.Wo = Wo; p.Cout = d->Cout; p.out_ld = d->out_ld;
+    p.in = (const uint16_t *)in; p.w = (const uint16_t *)w_packed16; p.res = (const uint16_t *)residual; p.scale = scale; p.bias = bias; p.out = (uint16_t *)out;
+    p.N = d->N; p.H = d->H; p.W = d->W; p.Cin = d->Cin; p.in_ld = d->in_ld; p.Ho = pl.Ho; p.Wo = pl.Wo; p.Cout = d->Cout; p.out_ld = d->out_ld;
     p.res_ld = d->res_ld; p.R = d->R; p.S = d->S; p.stride = d->stride; p.pad = d->pad; p.dil = d->dil;
-    p.K = d->R * d->S * d->Cin; p.Kpad = (p.K + KPAD - 1) / KPAD * KPAD; p.act = d->act; p.slope = d->prelu_slope;
+    p.K = pl.K; p.Kpad = pl.Kpad; p.act = d->act; p.slope = d->prelu_slope;
     p.log2Cin = -1;
     for (int b = 3; b < 16; ++b) if (d->Cin == (1 << b)) p.log2Cin = b;
-    p.inv_S = 65536 / d->S + 1;
-    if (d->R * d->S > 64) return ARSEG_EUNSUPPORTED;          // (the multiply-high filter-row decode is exact for taps < 64: up to 7 x 7 and 8 x 8)
-    const long long M = (long long)d->N * Ho * Wo;
-    const size_t in_bytes = (size_t)d->N * (up2 ? (d->H >> 1) * (d->W >> 1) : d->H * d->W) * d->in_ld * 2, w_bytes = (size_t)d->Cout * p.Kpad * 2;
-    if (M >= (1ll << 31) || in_bytes >= (1ull << 31) || w_bytes >= (1ull << 31)) return ARSEG_EUNSUPPORTED;       // 32-bit buffer offsets
-    p.M = (int)M; p.in_bytes = (unsigned)in_bytes; p.w_bytes = (unsigned)w_bytes;
-    // tile_cfg: 0 auto; 1 / 2 = 64- / 128-channel tile with K step 32; 3 / 4 = the same with K step 64
-    const int cfg = up2 && d->tile_cfg == 0 ? 7 : d->tile_cfg;
-    if (cfg < 0 || cfg > 13) return ARSEG_EINVAL;
-    if (cfg == 9) {          // stem kernel: 7x7 stride-2 pad-3, NHWC8 -> 64 channels, no residual
-        if (d->R != 7 || d->S != 7 || d->stride != 2 || d->pad != 3 || d->dil != 1 || d->Cin != 8 || d->Cout != 64 || residual || d->split_k > 1)
-            return ARSEG_EUNSUPPORTED;
-        p.patch_tw = 0; p.patch_l2tw = 0; p.tiles_m = 0; p.tiles_co = 1; p.tiles_px = 0; p.nsplit = 1; p.kt_per_split = 0; p.ws = nullptr;
-        hipStream_t st = arseg_stream(stream);
-        return dtype == ARSEG_DT_BF16 ? launch_stem16<true>(p, st) : launch_stem16<false>(p, st);
-    }
-    if (cfg >= 5) {          // patch-resident 3x3 kernel: 5 / 6 = 128-pixel tiles with 64 / 128 output channels, 7 / 8 = 256-pixel tiles;
-        // (r6) 10 / 11 / 12 / 13 = squarer tiles (less halo: 8 x 32 = 340 patch pixels, 16 x 16 = 324, against 4 x 64 = 396 for the same 256 outputs):
-        // 10 = 256 pixels as 8 x 32, 64 channels; 11 = 16 x 16, 64 channels; 12 = 8 x 32, 128 channels; 13 = 128 pixels as 8 x 16, 64 channels
-        if (d->R != 3 || d->S != 3 || d->stride != 1 || d->pad != d->dil || (d->Cin & 63) || d->split_k > 1) return ARSEG_EUNSUPPORTED;
-        const int bm = (cfg == 5 || cfg == 6 || cfg == 13) ? 128 : 256;
-        int tw = Wo >= 48 ? 64 : (Wo >= 24 ? 32 : 16);
-        if (cfg == 10 || cfg == 12) { if (tw <= 32) return ARSEG_EUNSUPPORTED; tw = 32; }        // (the same tile as 7 / 8 on a narrower map: not a new plan)
-        if (cfg == 11 || cfg == 13) { if (tw <= 16) return ARSEG_EUNSUPPORTED; tw = 16; }
-        const int th = bm / tw;
-        if ((th + 2 * d->dil) * (tw + 2 * d->dil) > (bm == 128 ? 288 : 448)) return ARSEG_EUNSUPPORTED;
-        p.patch_tw = tw; p.patch_l2tw = tw == 64 ? 6 : (tw == 32 ? 5 : 4);
-        p.tiles_m = d->N * arseg_cdiv(Ho, th) * arseg_cdiv(Wo, tw);
-        p.tiles_co = arseg_cdiv(d->Cout, (cfg == 6 || cfg == 8 || cfg == 12) ? 128 : 64); p.tiles_px = 0;
-        p.nsplit = 1; p.kt_per_split = 0; p.ws = nullptr;
-        hipStream_t st = arseg_stream(stream);
-        return dtype == ARSEG_DT_BF16 ? launch_patch16_any<true>(p, cfg, up2, st) : launch_patch16_any<false>(p, cfg, up2, st);
-    }
-    p.patch_tw = 0; p.patch_l2tw = 0; p.tiles_m = 0;
-    // 128-channel tiles when they still give every CU a few workgroups, K step 64 (half the barriers, 74 KB of LDS) for long K loops
-    const bool wide = conv16_wide(d, M), deep = cfg == 0 ? p.K >= 512 : cfg >= 3;
-    const int co_t = wide ? 128 : 64;
-    if (d->split_k < 0) return ARSEG_EINVAL;
-    p.nsplit = conv16_nsplit(d, M, p.Kpad, co_t);
-    p.kt_per_split = 0; p.ws = reinterpret_cast<float *>(workspace);
+    p.inv_S = 65536 / d->S + 1; p.M = pl.M;
+    p.in_bytes = (unsigned)((size_t)d->N * (up2 ? (d->H >> 1) * (d->W >> 1) : d->H * d->W) * d->in_ld * 2); p.w_bytes = (unsigned)((size_t)d->Cout * p.Kpad * 2);
+    p.patch_tw = pl.patch_tw; p.patch_l2tw = pl.patch_tw == 64 ? 6 : (pl.patch_tw == 32 ? 5 : (pl.patch_tw == 16 ? 4 : 0));
+    p.tiles_m = pl.kind == ARSEG_PLAN_PATCH ? pl.tiles_m : 0; p.tiles_co = pl.tiles_n; p.tiles_px = pl.kind == ARSEG_PLAN_PATCH ? 0 : pl.tiles_m;
+    p.nsplit = pl.nsplit; p.kt_per_split = 0; p.ws = nullptr;
+    hipStream_t hs = arseg_stream(stream);
+    if (pl.kind == ARSEG_PLAN_STEM) return residual ? ARSEG_EUNSUPPORTED : (dtype == ARSEG_DT_BF16 ? launch_stem16<true>(p, hs) : launch_stem16<false>(p, hs));
+    if (pl.kind == ARSEG_PLAN_PATCH)
+        return dtype == ARSEG_DT_BF16 ? (up2 ? launch_patch16_tile<true, true>(p, pl, hs) : launch_patch16_tile<true, false>(p, pl, hs))
+                                      : (up2 ? launch_patch16_tile<false, true>(p, pl, hs) : launch_patch16_tile<false, false>(p, pl, hs));
+    p.ws = reinterpret_cast<float *>(workspace);
     if (p.nsplit > 1) {
-        if (!workspace || workspace_bytes < (size_t)p.nsplit * M * d->Cout * sizeof(float)) return ARSEG_EWORKSPACE;
+        if (!workspace || workspace_bytes < pl.workspace_bytes) return ARSEG_EWORKSPACE;
         if (!ARSEG_ALIGNED16(workspace)) return ARSEG_EINVAL;
     }
-    p.tiles_co = arseg_cdiv(d->Cout, co_t); p.tiles_px = arseg_cdiv(M, PIX_T);
-    hipStream_t st = arseg_stream(stream);
-    return dtype == ARSEG_DT_BF16 ? launch_cfg<true>(p, wide, deep, st) : launch_cfg<false>(p, wide, deep, st);
+    return dtype == ARSEG_DT_BF16 ? launch_cfg<true>(p, pl.bn == 128, pl.bk == 64, hs) : launch_cfg<false>(p, pl.bn == 128, pl.bk == 64, hs);
 }

@@ -33,6 +33,7 @@
 //                     power of two so that lo stays a normal fp16) once at pack time; activations stay fp32 in HBM and
 //                     are split on their way into LDS, whose row layout becomes [32 hi halves | 32 lo halves | pad].
 #include "arseg_device.h"
+#include "conv_plans.h"
 #include <type_traits>
 #include <cmath>
 #include <cstring>
@@ -708,119 +709,64 @@ __global__ __launch_bounds__(256) void conv_splitk_reduce_kernel(const ConvParam
     }
 }
 
-struct Plan { int bm, bn, bk, nbuf, nsplit, ktiles, ktiles_per_split, tiles_m, tiles_n, Ho, Wo, M, K, Kpad, patch_tw, up2_c64; };
-
-int make_plan(const arseg_conv_desc *d, Plan *pl) {
-    if (!d) return ARSEG_EINVAL;
-    if (d->N <= 0 || d->H <= 0 || d->W <= 0 || d->Cin <= 0 || d->Cout <= 0 || d->R <= 0 || d->S <= 0 || d->stride <= 0 ||
-        d->dil <= 0 || d->pad < 0)
-        return ARSEG_EINVAL;
-    if ((d->Cin & 3) || (d->in_ld & 3) || d->in_ld < d->Cin || d->out_ld < d->Cout) return ARSEG_EINVAL;
-    if (d->R * d->S > 1 && (d->Cin & (d->Cin - 1))) return ARSEG_EUNSUPPORTED;
-    if (d->math != ARSEG_MATH_F32 && d->math != ARSEG_MATH_F16X3 && d->math != ARSEG_MATH_F16) return ARSEG_EINVAL;
-    pl->Ho = (d->H + 2 * d->pad - d->dil * (d->R - 1) - 1) / d->stride + 1;
-    pl->Wo = (d->W + 2 * d->pad - d->dil * (d->S - 1) - 1) / d->stride + 1;
-    if (pl->Ho <= 0 || pl->Wo <= 0) return ARSEG_EINVAL;
-    const long long M = (long long)d->N * pl->Ho * pl->Wo;
-    if (M > (1ll << 30) || (long long)d->N * d->H * d->W > (1ll << 30)) return ARSEG_EUNSUPPORTED;
-    pl->M = (int)M;
-    pl->K = d->R * d->S * d->Cin;
+int make_plan(const arseg_conv_desc *d, ConvPlan *pl) {
+    if (int e = conv_geometry(d, pl)) return e;
     pl->Kpad = arseg_packed_k(d->Cin, d->R, d->S);
-    if (d->tile_cfg < 0 || d->tile_cfg > 23) return ARSEG_EINVAL;
-    pl->patch_tw = 0; pl->up2_c64 = 0;
-    if (d->tile_cfg == 23) {      // the persistent kernel of up_3 (conv_up2_c64.hip): the shape class of arseg_conv_up2_c64_fwd, which checks it again
+    const ConvPlanRow *row = conv_plan_row(kConvPlans32, d->tile_cfg);
+    if (!row) return ARSEG_EINVAL;
+    pl->take(*row);
+    pl->patch_tw = pl->patch_th = 0; pl->ktiles = (pl->Kpad + pl->bk - 1) / pl->bk; pl->ktiles_per_split = pl->ktiles; pl->split(1, d->Cout);
+    if (row->kind == ARSEG_PLAN_UP2_C64) {
         if (!d->upsample2x) return ARSEG_EINVAL;                  // the id exists for convs on an upsampled input only
-        if (d->math != ARSEG_MATH_F16X3 || d->Cin != 64 || d->Cout != 64 || d->R != 3 || d->S != 3 || d->stride != 1 || d->pad != 1 || d->dil != 1 ||
-            (d->H & 1) || (d->W & 1) || (d->out_ld & 3) || d->batch > 1 || d->split_k > 1)
-            return ARSEG_EUNSUPPORTED;
-        // 32-bit buffer offsets (in = [N, H/2, W/2, in_ld])
-        if ((((long long)d->N * (d->H >> 1) * (d->W >> 1) - 1) * d->in_ld + 64) * 4 >= (1ll << 31) || ((M - 1) * d->out_ld + 64) * 4 >= (1ll << 31))
-            return ARSEG_EUNSUPPORTED;
-        pl->up2_c64 = 1;
-        pl->bm = 128; pl->bn = 64; pl->bk = 32; pl->nbuf = 2;
-        pl->ktiles = pl->Kpad / 32; pl->ktiles_per_split = pl->ktiles; pl->nsplit = 1;
+        if (!conv_up2_c64_shape(d) || (d->out_ld & 3) || conv_up2_c64_in_bytes(d) >= (1ll << 31) || conv_up2_c64_out_bytes(d) >= (1ll << 31)) return ARSEG_EUNSUPPORTED;
         pl->tiles_m = d->N * arseg_cdiv(pl->Ho, 8) * arseg_cdiv(pl->Wo, 16); pl->tiles_n = 1;
         return ARSEG_OK;
     }
-    if (d->tile_cfg >= 17 && d->math != ARSEG_MATH_F16X3) return ARSEG_EUNSUPPORTED;      // the large tiles are built for f16x3 only
-    // patch-resident 3x3 kernel: 128 (13, 14) / 256 (15, 16) pixel tiles TH x TW of one image, BN = 64 / 128; (r6) 20 / 21 / 22 = BN 64 on squarer
-    // tiles -- 20: 256 pixels as 8 x 32, 21: 256 as 16 x 16, 22: 128 as 8 x 16 -- whose patch has less halo than the default 4 x 64 / 2 x 64 of a
-    // wide map (340 / 324 staged pixels against 396 per 256 outputs); refused where the default tile is already that narrow
-    if ((d->tile_cfg >= 13 && d->tile_cfg <= 16) || d->tile_cfg >= 20) {
-        if (d->R != 3 || d->S != 3 || d->stride != 1 || d->pad != d->dil || d->math != ARSEG_MATH_F16X3 || (d->Cin & 31) || d->batch > 1 ||
-            d->split_k > 1)
-            return ARSEG_EUNSUPPORTED;
-        if (d->upsample2x && (d->dil != 1 || (d->H & 1) || (d->W & 1))) return ARSEG_EUNSUPPORTED;
-        const int bm = (d->tile_cfg == 13 || d->tile_cfg == 14 || d->tile_cfg == 22) ? 128 : 256;
-        int tw = pl->Wo >= 48 ? 64 : (pl->Wo >= 24 ? 32 : 16);
-        if (d->tile_cfg == 20) { if (tw <= 32) return ARSEG_EUNSUPPORTED; tw = 32; }
-        if (d->tile_cfg >= 21) { if (tw <= 16) return ARSEG_EUNSUPPORTED; tw = 16; }
-        const int th = bm / tw;
-        if ((th + 2 * d->dil) * (tw + 2 * d->dil) > (bm == 128 ? 288 : 448)) return ARSEG_EUNSUPPORTED;
-        if (((long long)d->N * d->H * d->W * d->in_ld + d->Cin) * 4 >= (1ll << 31) || (long long)d->Cout * pl->Kpad * 4 >= (1ll << 31))
-            return ARSEG_EUNSUPPORTED;
-        pl->patch_tw = tw;
-        pl->bm = bm; pl->bn = (d->tile_cfg >= 20 || (d->tile_cfg & 1)) ? 64 : 128; pl->bk = 32; pl->nbuf = 2;
-        pl->ktiles = pl->Kpad / 32; pl->ktiles_per_split = pl->ktiles; pl->nsplit = 1;
-        pl->tiles_m = d->N * arseg_cdiv(pl->Ho, th) * arseg_cdiv(pl->Wo, tw);
-        pl->tiles_n = arseg_cdiv(d->Cout, pl->bn);
-        return ARSEG_OK;
-    }
-    if (d->upsample2x) return ARSEG_EUNSUPPORTED;          // only the patch-resident plans (tile_cfg 13..16) apply the upsample
-    pl->bk = (d->tile_cfg >= 9 && d->tile_cfg <= 12) ? 64 : 32;
-    pl->ktiles = (pl->Kpad + pl->bk - 1) / pl->bk;
-    // operands are addressed through 32-bit buffer offsets
-    if (((long long)d->N * d->H * d->W * d->in_ld + d->Cin) * 4 >= (1ll << 31) || (long long)d->Cout * pl->Kpad * 4 >= (1ll << 31))
-        return ARSEG_EUNSUPPORTED;
-
-    static const int cfg[20][2] = {{0, 0}, {128, 128}, {128, 64}, {64, 64}, {64, 128}, {128, 128}, {128, 64}, {64, 64}, {64, 128},
-                                   {128, 128}, {128, 64}, {64, 64}, {64, 128}, {0, 0}, {0, 0}, {0, 0}, {0, 0},
-                                   {256, 128}, {128, 256}, {256, 256}};       // 17..19: 8- / 16-wave tiles (more reuse per byte from L2 / MALL)
+    if (row->f16x3_only && d->math != ARSEG_MATH_F16X3) return ARSEG_EUNSUPPORTED;
+    if (d->upsample2x && !row->fuses_up2) return ARSEG_EUNSUPPORTED;
+    if (!conv_fits_32bit(d, pl->Kpad)) return ARSEG_EUNSUPPORTED;
+    if (row->kind == ARSEG_PLAN_PATCH) return conv_patch_plan(d, *row, 31, pl);
     // Tile / split-K choice, fitted to a brute-force sweep of this model family's layer shapes on MI355X
     // (scratch sweep recorded in DESIGN.md): aim for ~512 workgroups (2 per CU); take the largest tile that gets
     // there with a split-K factor that still leaves >= 8 K-steps per slice; shallow GEMMs (< 64 K-steps) are best
     // served by 64x64 tiles.
+    const long long M = pl->M;
     const int target = d->batch > 1 ? (512 + d->batch - 1) / d->batch : 512;
     const int max_split = pl->ktiles / 8 > 0 ? (pl->ktiles / 8 > 16 ? 16 : pl->ktiles / 8) : 1;
-    int bm = 64, bn = 64, nsplit = 1;
-    pl->nbuf = (d->tile_cfg >= 1 && d->tile_cfg <= 4) ? 2 : 1;     // single LDS buffer (more blocks per CU) measured faster
-    if (d->tile_cfg >= 1) { bm = cfg[d->tile_cfg][0]; bn = cfg[d->tile_cfg][1]; }
-    else {
+    int nsplit = 1;
+    if (row->kind == ARSEG_PLAN_AUTO) {      // (its K step and single LDS buffer -- more blocks per CU, measured faster -- are the row's)
         const int order_deep[4] = {1, 4, 2, 3}, order_shallow[4] = {3, 3, 3, 3};
         const int *order = pl->ktiles >= 64 ? order_deep : order_shallow;
+        pl->bm = pl->bn = 64;
         bool found = false;
         for (int t = 0; t < 4 && !found; ++t) {
-            const int tb_m = cfg[order[t]][0], tb_n = cfg[order[t]][1];
+            const int tb_m = kConvPlans32[order[t]].bm, tb_n = kConvPlans32[order[t]].bn;
             if (tb_n == 128 && d->Cout <= 64) continue;
             if (tb_m == 128 && M <= 64) continue;
-            const long long tiles = (long long)arseg_cdiv(M, tb_m) * arseg_cdiv(d->Cout, tb_n);
-            const long long need = (target + tiles - 1) / tiles;
+            const long long tiles = (long long)arseg_cdiv(M, tb_m) * arseg_cdiv(d->Cout, tb_n), need = (target + tiles - 1) / tiles;
             if (need <= max_split || order[t] == 3) {
-                bm = tb_m; bn = tb_n;
+                pl->bm = tb_m; pl->bn = tb_n;
                 nsplit = (int)(need < 1 ? 1 : (need > max_split ? max_split : need));
                 found = true;
             }
         }
     }
-    pl->bm = bm; pl->bn = bn;
-    pl->tiles_m = arseg_cdiv(M, bm);
-    pl->tiles_n = arseg_cdiv(d->Cout, bn);
+    pl->tiles_m = arseg_cdiv(M, pl->bm); pl->tiles_n = arseg_cdiv(d->Cout, pl->bn);
     if (d->split_k > 0) nsplit = d->split_k;
-    else if (d->tile_cfg >= 1) {
-        const long long tiles = (long long)pl->tiles_m * pl->tiles_n;
-        const long long need = (target + tiles - 1) / tiles;
+    else if (row->kind != ARSEG_PLAN_AUTO) {
+        const long long tiles = (long long)pl->tiles_m * pl->tiles_n, need = (target + tiles - 1) / tiles;
         nsplit = (int)(need < 1 ? 1 : (need > max_split ? max_split : need));
     }
     if (nsplit > pl->ktiles) nsplit = pl->ktiles;
     if (nsplit > 1 && (d->Cout & 3)) nsplit = 1;   // the reduce kernel is 4-wide
     if (d->batch > 1) nsplit = 1;                   // batched GEMMs bring their own parallelism
     pl->ktiles_per_split = arseg_cdiv(pl->ktiles, nsplit);
-    pl->nsplit = arseg_cdiv(pl->ktiles, pl->ktiles_per_split);
+    pl->split(arseg_cdiv(pl->ktiles, pl->ktiles_per_split), d->Cout);
     return ARSEG_OK;
 }
 
 template <int BM, int BN, int BK, int NBUF, int MATH, int NWM = 2, int NWN = 2>
-int launch(const ConvParams &p, const Plan &pl, hipStream_t st) {
+int launch(const ConvParams &p, const ConvPlan &pl, hipStream_t st) {
     const size_t smem = (size_t)NBUF * (BM + BN) * (BK + 4) * sizeof(float);
     static ArsegSmemAttr attr;
     if (int e = arseg_allow_smem(attr, reinterpret_cast<const void *>(conv_igemm_kernel<BM, BN, BK, NBUF, MATH, NWM, NWN>), smem)) return e;
@@ -830,7 +776,7 @@ int launch(const ConvParams &p, const Plan &pl, hipStream_t st) {
 }
 
 template <int BK, int NBUF, int MATH>
-int launch_tile(const ConvParams &p, const Plan &pl, hipStream_t hs) {
+int launch_tile(const ConvParams &p, const ConvPlan &pl, hipStream_t hs) {
     if (pl.bm == 128 && pl.bn == 128) return launch<128, 128, BK, NBUF, MATH>(p, pl, hs);
     if (pl.bm == 128 && pl.bn == 64) return launch<128, 64, BK, NBUF, MATH>(p, pl, hs);
     if (pl.bm == 64 && pl.bn == 128) return launch<64, 128, BK, NBUF, MATH>(p, pl, hs);
@@ -838,8 +784,8 @@ int launch_tile(const ConvParams &p, const Plan &pl, hipStream_t hs) {
 }
 
 template <int BN, int WM, bool UP2>
-int launch_patch_up(const ConvParams &p, const Plan &pl, int dil, hipStream_t st) {
-    const int tw = pl.patch_tw, th = 64 * WM / tw, npx = (th + 2 * dil) * (tw + 2 * dil);
+int launch_patch_up(const ConvParams &p, const ConvPlan &pl, int dil, hipStream_t st) {
+    const int tw = pl.patch_tw, npx = (pl.patch_th + 2 * dil) * (tw + 2 * dil);
     const size_t smem = (size_t)((npx * 144 + 255) & ~255) + (size_t)2 * BN * 144;
     static ArsegSmemAttr attr;
     if (int e = arseg_allow_smem(attr, reinterpret_cast<const void *>(conv3x3_patch_kernel<BN, WM, UP2>), smem)) return e;
@@ -849,13 +795,13 @@ int launch_patch_up(const ConvParams &p, const Plan &pl, int dil, hipStream_t st
     return arseg_launch_status();
 }
 template <int BN, int WM>
-int launch_patch(const ConvParams &p, const Plan &pl, int dil, hipStream_t st) {
+int launch_patch(const ConvParams &p, const ConvPlan &pl, int dil, hipStream_t st) {
     return p.up2 ? launch_patch_up<BN, WM, true>(p, pl, dil, st) : launch_patch_up<BN, WM, false>(p, pl, dil, st);
 }
 
 template <int MATH>
-int launch_math(const ConvParams &p, const Plan &pl, hipStream_t hs) {
-    if (MATH == ARSEG_MATH_F16X3 && (pl.bm == 256 || pl.bn == 256)) {
+int launch_math(const ConvParams &p, const ConvPlan &pl, hipStream_t hs) {
+    if (pl.kind == ARSEG_PLAN_TILE_WIDE) {      // (f16x3 only: make_plan)
         if (pl.bm == 256 && pl.bn == 128) return launch<256, 128, 32, 1, ARSEG_MATH_F16X3, 4, 2>(p, pl, hs);
         if (pl.bm == 128 && pl.bn == 256) return launch<128, 256, 32, 1, ARSEG_MATH_F16X3, 2, 4>(p, pl, hs);
         return launch<256, 256, 32, 1, ARSEG_MATH_F16X3, 4, 4>(p, pl, hs);
@@ -872,32 +818,40 @@ extern "C" int arseg_packed_k(int Cin_pad, int R, int S) {
 }
 
 extern "C" int arseg_conv_out_hw(const arseg_conv_desc *d, int *Ho, int *Wo) {
-    Plan pl;
-    int st = make_plan(d, &pl);
-    if (st != ARSEG_OK) return st;
+    ConvPlan pl;
+    if (int e = make_plan(d, &pl)) return e;
     if (Ho) *Ho = pl.Ho;
     if (Wo) *Wo = pl.Wo;
     return ARSEG_OK;
 }
 
+extern "C" int arseg_conv_plan_query(int engine, const arseg_conv_desc *d, arseg_conv_plan_info *info) {
+    if (!d || !info || (engine != ARSEG_CONV_ENGINE_F32 && engine != ARSEG_CONV_ENGINE_16)) return ARSEG_EINVAL;
+    const bool e16 = engine == ARSEG_CONV_ENGINE_16;
+    ConvPlan pl{};
+    if (const ConvPlanRow *row = e16 ? conv_plan_row(kConvPlans16, d->tile_cfg) : conv_plan_row(kConvPlans32, d->tile_cfg)) pl.take(*row);
+    const int st = e16 ? conv16_plan(d, &pl) : make_plan(d, &pl);
+    *info = pl;          // (refused: what the id is; the shape's fields are then without meaning)
+    return st;
+}
+
 extern "C" size_t arseg_conv2d_workspace_bytes(const arseg_conv_desc *d) {
-    Plan pl;
-    if (make_plan(d, &pl) != ARSEG_OK) return 0;
-    return pl.nsplit > 1 ? (size_t)pl.nsplit * pl.M * d->Cout * sizeof(float) : 0;
+    arseg_conv_plan_info info;
+    return arseg_conv_plan_query(ARSEG_CONV_ENGINE_F32, d, &info) == ARSEG_OK ? info.workspace_bytes : 0;
 }
 
 extern "C" int arseg_conv2d_fwd(const arseg_conv_desc *d, const float *in, const float *w_packed, const float *scale,
                                 const float *bias, const float *residual, float *out, void *workspace,
                                 size_t workspace_bytes, arseg_stream_t stream) {
-    Plan pl;
+    ConvPlan pl;
     int st = make_plan(d, &pl);
     if (st != ARSEG_OK) return st;
     ARSEG_CHECK_PTR(in); ARSEG_CHECK_PTR(w_packed); ARSEG_CHECK_PTR(out);
     if (!ARSEG_ALIGNED16(in) || !ARSEG_ALIGNED16(w_packed)) return ARSEG_EINVAL;
     if (residual && d->res_ld < d->Cout) return ARSEG_EINVAL;
-    if (pl.up2_c64) return residual ? ARSEG_EUNSUPPORTED : arseg_conv_up2_c64_fwd(d, in, w_packed, scale, bias, out, 0, stream);
+    if (pl.kind == ARSEG_PLAN_UP2_C64) return residual ? ARSEG_EUNSUPPORTED : arseg_conv_up2_c64_fwd(d, in, w_packed, scale, bias, out, 0, stream);
     if (pl.nsplit > 1) {
-        if (!workspace || workspace_bytes < (size_t)pl.nsplit * pl.M * d->Cout * sizeof(float)) return ARSEG_EWORKSPACE;
+        if (!workspace || workspace_bytes < pl.workspace_bytes) return ARSEG_EWORKSPACE;
         if (!ARSEG_ALIGNED16(workspace)) return ARSEG_EINVAL;
     }
     ConvParams p;
@@ -930,7 +884,7 @@ extern "C" int arseg_conv2d_fwd(const arseg_conv_desc *d, const float *in, const
     p.range_flag = d->math == ARSEG_MATH_F16X3 ? reinterpret_cast<unsigned *>(d->range_flag) : nullptr;
     p.range_limit = d->range_limit > 0.0f ? d->range_limit : 65504.0f;
     if (p.range_flag && (reinterpret_cast<uintptr_t>(p.range_flag) & 3)) return ARSEG_EINVAL;
-    if (pl.patch_tw) {
+    if (pl.kind == ARSEG_PLAN_PATCH) {
         p.in_bytes = d->upsample2x ? (unsigned)((((long long)d->N * (d->H >> 1) * (d->W >> 1) - 1) * d->in_ld + d->Cin) * 4)
                                    : (unsigned)((((long long)d->N * d->H * d->W - 1) * d->in_ld + d->Cin) * 4);
         if (pl.bm == 256) return pl.bn == 64 ? launch_patch<64, 4>(p, pl, d->dil, hs) : launch_patch<128, 4>(p, pl, d->dil, hs);
@@ -1049,22 +1003,17 @@ extern "C" int arseg_pack_dw3x3_host(const float *w, int C, float *out) {
 namespace {
 struct FindCand { int cfg, sk; };
 int find_candidates(const arseg_conv_desc *d, FindCand *c, int cap) {
-    int n = 0;
+    int n = 0, ktiles = (d->R * d->S * d->Cin + 31) / 32;
     c[n++] = FindCand{0, 0};
-    if (d->upsample2x) {                       // only the patch-resident plans upsample while they stage
-        for (int cfg = 13; cfg <= 16 && n < cap; ++cfg) c[n++] = FindCand{cfg, 1};
-        for (int cfg = 20; cfg <= 23 && n < cap; ++cfg) c[n++] = FindCand{cfg, 1};      // 23: up_3's persistent kernel (refuses other shapes)
-        return n;
-    }
-    const int ktiles = (d->R * d->S * d->Cin + 31) / 32;
-    for (int cfg = 5; cfg <= 22 && n < cap; ++cfg) {
-        if ((cfg >= 13 && cfg <= 16) || cfg >= 20) { c[n++] = FindCand{cfg, 1}; continue; }
+    for (int cfg = 1; cfg < (int)(sizeof(kConvPlans32) / sizeof(kConvPlans32[0])) && n < cap; ++cfg) {
+        const ConvPlanRow &row = kConvPlans32[cfg];
+        // with a fused upsample only the plans that upsample while they stage; without, not up_3's kernel (it refuses every other shape) and not
+        // the double-buffered GEMM tiles (their single-buffered twins measured faster)
+        if (d->upsample2x ? !row.fuses_up2 : (row.kind == ARSEG_PLAN_NONE || row.kind == ARSEG_PLAN_UP2_C64 || (row.kind == ARSEG_PLAN_TILE && row.nbuf == 2)))
+            continue;
         static const int sks[6] = {1, 2, 3, 4, 6, 8};
-        for (int i = 0; i < 6 && n < cap; ++i) {
-            const int sk = sks[i];
-            if (sk > 1 && (d->batch > 1 || ktiles / sk < 4 || (d->Cout & 3))) continue;
-            c[n++] = FindCand{cfg, sk};
-        }
+        for (int i = 0; i < 6 && n < cap; ++i)
+            if (sks[i] == 1 || (row.split_k && d->batch <= 1 && ktiles / sks[i] >= 4 && !(d->Cout & 3))) c[n++] = FindCand{cfg, sks[i]};
     }
     return n;
 }

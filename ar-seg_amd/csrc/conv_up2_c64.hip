@@ -21,6 +21,7 @@
 // of patch pixel px sits in slot g ^ ((px >> 1) & 2) of its row.  A ds_read_b128 lane group holds 8 pixels on group g and 8 on g ^ 1; pixel
 // rows are consecutive, so with the swizzle the 16 lanes fall on 16 different 16-byte slots of the 256-byte bank row whatever the tap offset.
 #include "arseg_device.h"
+#include "conv_plans.h"
 #include <cmath>
 
 namespace {
@@ -245,9 +246,7 @@ extern "C" int arseg_conv_up2_c64_fwd(const arseg_conv_desc *d, const float *in,
                                       int max_wgs, arseg_stream_t stream) {
     if (!d) return ARSEG_EINVAL;
     if (d->N <= 0 || d->H <= 0 || d->W <= 0 || max_wgs < 0) return ARSEG_EINVAL;
-    if (d->R != 3 || d->S != 3 || d->stride != 1 || d->pad != 1 || d->dil != 1 || d->Cin != 64 || d->Cout != 64 || d->math != ARSEG_MATH_F16X3 ||
-        !d->upsample2x || (d->H & 1) || (d->W & 1) || d->batch > 1 || d->split_k > 1)
-        return ARSEG_EUNSUPPORTED;
+    if (!conv_up2_c64_shape(d)) return ARSEG_EUNSUPPORTED;
     if (d->in_ld < 64 || (d->in_ld & 3) || d->out_ld < 64) return ARSEG_EINVAL;
     if (d->out_ld & 3) return ARSEG_EUNSUPPORTED;                // a lane stores its 4 channels as one 16-byte piece
     if (d->act != ARSEG_ACT_NONE && d->act != ARSEG_ACT_RELU && d->act != ARSEG_ACT_PRELU && d->act != ARSEG_ACT_SIGMOID) return ARSEG_EINVAL;
@@ -256,9 +255,8 @@ extern "C" int arseg_conv_up2_c64_fwd(const arseg_conv_desc *d, const float *in,
     if (!ARSEG_ALIGNED16(out)) return ARSEG_EUNSUPPORTED;
     void *rf = d->range_flag;
     if (rf && (reinterpret_cast<uintptr_t>(rf) & 3)) return ARSEG_EINVAL;
-    const long long M = (long long)d->N * d->H * d->W;
-    const long long ib = (((long long)d->N * (d->H >> 1) * (d->W >> 1) - 1) * d->in_ld + 64) * 4, ob = ((M - 1) * d->out_ld + 64) * 4;
-    if (M > (1ll << 30) || ib >= (1ll << 31) || ob >= (1ll << 31)) return ARSEG_EUNSUPPORTED;      // 32-bit buffer offsets
+    const long long ib = conv_up2_c64_in_bytes(d), ob = conv_up2_c64_out_bytes(d);
+    if ((long long)d->N * d->H * d->W > (1ll << 30) || ib >= (1ll << 31) || ob >= (1ll << 31)) return ARSEG_EUNSUPPORTED;      // 32-bit buffer offsets
     Up2Params p;
     p.in = in; p.w = w_packed; p.scale = scale; p.bias = bias; p.out = out;
     p.H = d->H; p.W = d->W; p.in_ld = d->in_ld; p.out_ld = d->out_ld;

@@ -40,8 +40,11 @@ class _PlanCache(dict):
 
 _conv_plans = _PlanCache()
 _config._plan_file_listeners.append(_conv_plans.load)
-# arseg_conv_desc.tile_cfg of the direct plans with a fused x2 upsample: the patch-resident 3x3 kernel and (23) the persistent kernel of up_3
-_PATCH_CFGS = (13, 14, 15, 16, 20, 21, 22, 23)
+
+
+def fuses_up2(tile_cfg: int, engine: int = _lib.CONV_ENGINE_F32) -> bool:
+    """Does plan ``tile_cfg`` of the engine apply desc.upsample2x itself (the patch-resident 3x3 plans, up_3's kernel)?  The library's plan table says."""
+    return bool(_lib.conv_plan_row(engine, tile_cfg).fuses_upsample)
 
 
 def _conv_candidates(ktiles: int, cout: int, m: int, patch_ok: bool = False):
@@ -51,13 +54,8 @@ def _conv_candidates(ktiles: int, cout: int, m: int, patch_ok: bool = False):
         if cout == 64 and ktiles == 18:            # up_3's persistent kernel: 64 -> 64; the library refuses it (skipped) without a fused upsample
             cands.append((23, 1))
     for cfg in (5, 6, 7, 8, 9, 10, 11, 12) + ((17, 18, 19) if sw.math == _lib.MATH_F16X3 else ()):
-        bn = {17: 128, 18: 256, 19: 256}.get(cfg, 128 if cfg in (5, 8, 9, 12) else 64)
-        bm = {17: 256, 18: 128, 19: 256}.get(cfg, 128 if cfg in (5, 6, 9, 10) else 64)
-        if bn >= 128 and cfg >= 17 and cout < bn:
-            continue
-        if bn == 128 and cout <= 64:
-            continue
-        if bm == 128 and m <= 64:
+        row = _lib.conv_plan_row(_lib.CONV_ENGINE_F32, cfg)
+        if (row.kind == _lib.PLAN_TILE_WIDE and cout < row.bn) or (row.bn == 128 and cout <= 64) or (row.bm == 128 and m <= 64):
             continue
         for sk in (1, 2, 3, 4, 6, 8):
             if sk > 1 and (ktiles // sk < 4 or cout % 4):

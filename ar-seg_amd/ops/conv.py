@@ -11,7 +11,7 @@ from .. import _lib
 from .._lib import ConvDesc, check
 from ._base import RANGE_LIMIT, _arm_range_watch, _need_gpu, _need_gpu16, _nhwc_ld, _ptr, _range_word, _stream, is16, workspace
 from ._config import config, set_conv_math, sw
-from ._plans import _PATCH_CFGS, _tune_conv, tuned
+from ._plans import _tune_conv, fuses_up2, tuned
 from ._profile import launch, tagged
 from .layers import psp_prior_sum, resize_nhwc
 
@@ -169,7 +169,7 @@ def conv2d(x: torch.Tensor, pc, residual: Optional[torch.Tensor] = None, out: Op
     if up2:
         x_low = x
         n_, h_, w_, c_ = x.shape
-        if (tile_cfg and tile_cfg not in _PATCH_CFGS) or (not tile_cfg and (split_k or not sw.AUTOTUNE)):
+        if (tile_cfg and not fuses_up2(tile_cfg)) or (not tile_cfg and (split_k or not sw.AUTOTUNE)):
             x, x_low = resize_nhwc(x, 2 * h_, 2 * w_, _lib.BILINEAR, False), None          # explicit GEMM tile / heuristic plan: materialise
         else:
             # shape carrier; filled only if a plan without a fused upsample is chosen (the patch-resident plans and the Winograd
@@ -182,7 +182,7 @@ def conv2d(x: torch.Tensor, pc, residual: Optional[torch.Tensor] = None, out: Op
     in_ld_hi = Cin if x_low is not None else _nhwc_ld(x)
     math = sw.math
     d, out, Ho, Wo = _conv_desc(pc, N, H, W, Cin, in_ld_hi, tile_cfg, split_k, residual, out, torch.float32, dev, math,
-                                up2=x_low is not None and tile_cfg in _PATCH_CFGS)
+                                up2=x_low is not None and fuses_up2(tile_cfg))
     w_dev, scale_dev = (pc.w_h3, pc.scale_h3) if math != _lib.MATH_F32 else (pc.w, pc.scale)
     lib = _lib.load()
     flops = 2 * N * Ho * Wo * pc.cout * pc.R * pc.S * pc.cin
@@ -201,7 +201,7 @@ def conv2d(x: torch.Tensor, pc, residual: Optional[torch.Tensor] = None, out: Op
         xin = x
         d.upsample2x, d.in_ld = 0, in_ld_hi
         if x_low is not None:
-            if cfg in _PATCH_CFGS:                              # the patch-resident kernel upsamples while it stages its patch
+            if fuses_up2(cfg):                                  # the patch-resident kernel upsamples while it stages its patch
                 xin, d.upsample2x, d.in_ld = x_low, 1, _nhwc_ld(x_low)
             else:                                               # GEMM kernel on an upsampled input: materialise it
                 if not up_buf:
@@ -280,7 +280,7 @@ def conv2d(x: torch.Tensor, pc, residual: Optional[torch.Tensor] = None, out: Op
     except _lib.ArsegError:
         # the plan key holds the shape, not the alignment / row pitch of `out` and `residual`: a cached route or patch-resident plan that
         # refuses this call's channel-slice view (16-byte stores) gives way to the library's heuristic for this call; the cached plan stays
-        if not (isinstance(plan, str) or plan[0] in _PATCH_CFGS):
+        if not (isinstance(plan, str) or fuses_up2(plan[0])):
             raise
         go((0, 0))
     return out
@@ -303,7 +303,7 @@ def conv_up2_c64(x_low: torch.Tensor, pc, out: Optional[torch.Tensor] = None, ma
 def _conv_desc(pc, N, H, W, Cin, in_ld, tile_cfg, split_k, residual, out, dtype, device, math=_lib.MATH_F32, up2=False):
     """arseg_conv_desc of ``pc`` on an [N, H, W, Cin] input of row pitch ``in_ld``, and its output tensor: ``out`` (shape checked) or a new one
     of ``dtype`` (16-bit: row pitch padded to 8 channels) -> (desc, out, Ho, Wo).  up2: ``tile_cfg`` is a plan that upsamples its
-    half-resolution input itself (upsample2x; H, W are the upsampled size)."""
+    half-resolution input itself (upsample2x; H, W are the upsampled size).  The engine that stores ``dtype`` gives the size (or its refusal)."""
     d = ConvDesc()
     d.N, d.H, d.W, d.Cin, d.in_ld = N, H, W, Cin, in_ld
     d.Cout = pc.cout
@@ -312,13 +312,12 @@ def _conv_desc(pc, N, H, W, Cin, in_ld, tile_cfg, split_k, residual, out, dtype,
     d.tile_cfg, d.split_k = tile_cfg, split_k
     d.math = math
     _arm_range_watch(d, device)
-    d.out_ld, d.res_ld = pc.cout, pc.cout     # provisional, for the shape query
-    ho, wo = ctypes.c_int(), ctypes.c_int()
+    ld = pc.cout if dtype == torch.float32 else (pc.cout + 7) // 8 * 8
+    d.out_ld, d.res_ld = ld, ld               # provisional, for the shape query
     d.upsample2x = 1 if up2 else 0
-    check(_lib.load().arseg_conv_out_hw(ctypes.byref(d), ctypes.byref(ho), ctypes.byref(wo)), "conv_out_hw")
-    Ho, Wo = ho.value, wo.value
+    info = _lib.conv_plan(_lib.CONV_ENGINE_F32 if dtype == torch.float32 else _lib.CONV_ENGINE_16, d)
+    Ho, Wo = info.Ho, info.Wo
     if out is None:
-        ld = pc.cout if dtype == torch.float32 else (pc.cout + 7) // 8 * 8
         out = torch.empty((N, Ho, Wo, ld), dtype=dtype, device=device)[..., :pc.cout]
     elif tuple(out.shape) != (N, Ho, Wo, pc.cout):
         raise _lib.ArsegError(f"conv out has shape {tuple(out.shape)}, expected {(N, Ho, Wo, pc.cout)}")
@@ -338,15 +337,28 @@ def _desc16(x, pc, residual, out, tile_cfg, split_k, up2=False):
     w16, cin_pad = pc.weights16(x.dtype)
     if Cin != cin_pad:
         raise _lib.ArsegError(f"conv (16-bit) expects {cin_pad} input channels (padded to 8), got {Cin}")
-    d, out, Ho, Wo = _conv_desc(pc, N, H, W, Cin, _nhwc_ld(x), 0, 0, residual, out, x.dtype, x.device)
-    # set after the size query: arseg_conv_out_hw checks the fp32 engine's plans (its tile_cfg 13 is an f16x3-only plan: a pinned 16-bit plan 13
-    # was refused there, before arseg_conv2d16_fwd saw it)
-    d.tile_cfg, d.upsample2x, d.split_k = tile_cfg, (1 if up2 else 0), split_k
+    d, out, Ho, Wo = _conv_desc(pc, N, H, W, Cin, _nhwc_ld(x), tile_cfg, split_k, residual, out, x.dtype, x.device, up2=up2)
     return d, out, N, H, W, Ho, Wo
 
 
-# arseg_conv2d16_fwd's patch-resident plans: the only ones that stage a x2 upsample of their input (upsample2x)
-_PATCH16_CFGS = (5, 6, 7, 8, 10, 11, 12, 13)
+def _conv16_candidates(ktiles: int, cout: int):
+    """The (tile_cfg, split_k) the 16-bit tuner times, in its order: every plan x split-K where the plan takes it and K (``ktiles`` steps of 64) is long enough."""
+    for cfg in (0, 1, 2, 3, 4, 5, 6, 7, 8, 9, 10, 11, 12, 13):
+        row = _lib.conv_plan_row(_lib.CONV_ENGINE_16, cfg)
+        # (a plan without split-K -- patch-resident, stem -- enters once, its 128-channel tiles only for more than 64 channels)
+        yield from ((cfg, sk) for sk in (0, 1, 2, 4, 8) if not ((sk > 1 and (ktiles // sk < 3 or cout % 8 or not row.split_k_allowed))
+                                                                or (not row.split_k_allowed and (sk == 1 or (row.bn == 128 and cout <= 64)))))
+
+
+def _conv16_up2_candidates(cout: int):
+    """The fused-upsample plans the 16-bit tuner times, in its order (128-channel tiles only where there are more than 64 channels)."""
+    return [(cfg, 0) for cfg in range(14) if fuses_up2(cfg, _lib.CONV_ENGINE_16) and not (_lib.conv_plan_row(_lib.CONV_ENGINE_16, cfg).bn == 128 and cout <= 64)]
+
+
+def _wino_gemm_candidates(math: int, cout: int):
+    """The tile_cfg of the batched GEMM the Winograd route times, in its order: tiles of 128 or more channels only where they are more than half used."""
+    return [cfg for cfg in (0, 5, 6, 7, 8, 9, 10, 11, 12) + ((17, 18, 19) if math == _lib.MATH_F16X3 else ())
+            for bn in [_lib.conv_plan_row(_lib.CONV_ENGINE_F32, cfg).bn] if not (bn >= 128 and cout <= bn // 2)]
 
 
 def _up2_fusable(x_low, pc) -> bool:
@@ -364,7 +376,7 @@ def _conv2d16_up2(x_low, pc, residual, out, tile_cfg, split_k):
     def materialised(o=out, cfg=tile_cfg, sk=split_k):
         return _conv2d16(resize_nhwc(x_low, 2 * h_, 2 * w_, _lib.BILINEAR, False), pc, residual, o, False, cfg, sk)
 
-    if split_k or (tile_cfg and tile_cfg not in _PATCH16_CFGS) or not _up2_fusable(x_low, pc):
+    if split_k or (tile_cfg and not fuses_up2(tile_cfg, _lib.CONV_ENGINE_16)) or not _up2_fusable(x_low, pc):
         return materialised()
     lib = _lib.load()
     d, out, N, H, W, Ho, Wo = _desc16(x_low, pc, residual, out, tile_cfg, 0, up2=True)
@@ -381,7 +393,7 @@ def _conv2d16_up2(x_low, pc, residual, out, tile_cfg, split_k):
             check(lib.arseg_conv2d16_fwd(*args()), "conv2d16")
 
         def candidates():
-            yield from ((cfg, 0) for cfg in _PATCH16_CFGS if not (cfg in (6, 8, 12) and pc.cout <= 64))
+            yield from _conv16_up2_candidates(pc.cout)
             materialised(out)                                                  # (tunes the materialised conv's own plan first)
             yield "resize"
 
@@ -420,15 +432,7 @@ def _conv2d16(x, pc, residual, out, up2, tile_cfg=0, split_k=0):
             check(lib.arseg_conv2d16_fwd(*args()), "conv2d16")
 
         def candidates():
-            ktiles = (pc.R * pc.S * Cin + 63) // 64
-            # 5..8, 10..13: patch-resident 3x3 plans (10..13: squarer pixel tiles, r6), 9: the 7x7 stem kernel (EUNSUPPORTED for other shapes)
-            for cfg in (0, 1, 2, 3, 4, 5, 6, 7, 8, 9, 10, 11, 12, 13):
-                for sk in (0, 1, 2, 4, 8):
-                    if sk > 1 and (ktiles // sk < 3 or pc.cout % 8 or cfg >= 5):
-                        continue
-                    if cfg >= 5 and (sk == 1 or (cfg in (6, 8, 12) and pc.cout <= 64)):
-                        continue
-                    yield cfg, sk
+            yield from _conv16_candidates((pc.R * pc.S * Cin + 63) // 64, pc.cout)
             if sw.IGEMM3 and pc.R == 1 and pc.S == 1 and pc.stride == 1 and pc.pad == 0 and Cin % 64 == 0 and pc.cout % 4 == 0 and d.in_ld == Cin:
                 try:                                                                       # 1x1: the plain GEMM of the LDS-DMA kernel
                     gemm_rows16(x, pc, residual, out, record=False)                         # (tunes its tile shape first)
@@ -497,9 +501,7 @@ def _conv_wino(x, pc, residual, out, N, H, W, record=True, up2=False):
 
     def candidates():
         transform(False, record=False)
-        for cfg in (0, 5, 6, 7, 8, 9, 10, 11, 12) + ((17, 18, 19) if math == _lib.MATH_F16X3 else ()):
-            if not ((cfg in (5, 8, 9, 12, 17, 18, 19) and Cout <= 64) or (cfg in (18, 19) and Cout <= 128)):
-                yield cfg
+        yield from _wino_gemm_candidates(math, Cout)
         if x3_ok:
             transform(True, record=False)
             yield from range(100, 107)

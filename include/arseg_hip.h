@@ -243,6 +243,26 @@ int arseg_conv2d_fwd(const arseg_conv_desc *d, const float *in, const float *w_p
                      const float *bias, const float *residual, float *out, void *workspace, size_t workspace_bytes,
                      arseg_stream_t stream);
 
+/* What a descriptor would launch, asked without a device: the verdict arseg_conv2d_fwd (engine = ARSEG_CONV_ENGINE_F32) or arseg_conv2d16_fwd
+ * (ARSEG_CONV_ENGINE_16) gives before it looks at its pointers -- ARSEG_OK, ARSEG_EINVAL or ARSEG_EUNSUPPORTED -- and the plan behind it.  kind ..
+ * split_k_allowed describe the id d->tile_cfg alone (the table of csrc/conv_plans.h; kind = ARSEG_PLAN_NONE for a number that is no id of the
+ * engine) and are filled whatever the verdict, so a descriptor with nothing but tile_cfg set reads the table; on ARSEG_OK bm / bn / bk hold the
+ * tile of this shape (the auto plans choose one) and the remaining fields are filled.  The 16-bit engine's bn is its channel tile, bk its K
+ * step in halves, bm its pixel tile.  arseg_conv2d_workspace_bytes is workspace_bytes of the fp32 engine (0 on any other verdict). */
+enum arseg_conv_engine { ARSEG_CONV_ENGINE_F32 = 0, ARSEG_CONV_ENGINE_16 = 1 };
+enum arseg_conv_plan_kind { ARSEG_PLAN_NONE = 0, ARSEG_PLAN_AUTO, ARSEG_PLAN_TILE, ARSEG_PLAN_TILE_WIDE /* 8 / 16 waves */, ARSEG_PLAN_PATCH,
+                            ARSEG_PLAN_STEM, ARSEG_PLAN_UP2_C64 };
+typedef struct arseg_conv_plan_info {
+    int kind;                            /* enum arseg_conv_plan_kind */
+    int bm, bn, bk, nbuf;                /* tile: output pixels x output channels, K step, LDS stages (0: chosen per shape) */
+    int fuses_upsample, split_k_allowed; /* the plan applies upsample2x itself | may take split-K */
+    int nsplit;                          /* K slices of this launch */
+    int patch_tw, patch_th;              /* patch-resident plans: the pixel tile (0 otherwise) */
+    int Ho, Wo;
+    size_t workspace_bytes;
+} arseg_conv_plan_info;
+int arseg_conv_plan_query(int engine, const arseg_conv_desc *d, arseg_conv_plan_info *info);
+
 /* tile_cfg 23 of arseg_conv2d_fwd by itself: the 64 -> 64 channel 3x3 stride-1 pad-1 conv on the x2 bilinear upsample of `in`
  * (d->upsample2x = 1, ARSEG_MATH_F16X3; PSPNet's up_3) with the folded scale / bias / activation epilogue, no residual.  One persistent
  * workgroup per compute unit walks a run of 8 x 16 pixel tiles: four waves keep the layer's split weights in registers and multiply,
