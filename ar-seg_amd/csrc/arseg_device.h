@@ -83,6 +83,25 @@ __device__ __forceinline__ float rows_sum(float x) {
     auto b = __builtin_amdgcn_permlane32_swap(__float_as_uint(x), __float_as_uint(x), false, false);
     return __uint_as_float(b[0]) + __uint_as_float(b[1]);
 }
+// ------------------------------------------------------------------ non-finite values: the activation of every conv epilogue, the max of the pools
+// A NaN or an infinity that reaches an epilogue or a pool leaves it as torch's ReLU / PReLU / identity / max would leave it (DESIGN.md section 2,
+// "Non-finite values").  fmaxf / v_max_f32 return the operand that is NOT NaN, so neither a ReLU nor a pool may be written with them: the
+// forms below are compares and selects on uniform parameters (v_cmp + v_cndmask, no branch per element; the sigmoid keeps its uniform branch).
+struct ArsegAct { float slope; bool relu, sigmoid; };
+__device__ __forceinline__ ArsegAct arseg_act(int act, float slope) {
+    return ArsegAct{act == ARSEG_ACT_PRELU ? slope : 1.0f, act == ARSEG_ACT_RELU, act == ARSEG_ACT_SIGMOID};      // (NONE / RELU: slope 1)
+}
+__device__ __forceinline__ float arseg_act_apply(float v, const ArsegAct a) {
+    if (a.sigmoid) return 1.0f / (1.0f + __expf(-v));
+    const float t = v >= 0.0f ? v : v * a.slope;          // a NaN fails the compare and stays NaN through the product
+    return (a.relu && v < 0.0f) ? 0.0f : t;               // a NaN fails this one too: it is not clipped
+}
+// max that keeps a NaN: the first NaN met wins and stays (m NaN: both compares fail)
+__device__ __forceinline__ float max_nan(float m, float f) { return (f > m || f != f) ? f : m; }
+__device__ __forceinline__ f32x4 max_nan(const f32x4 m, const f32x4 f) {
+    return f32x4{max_nan(m[0], f[0]), max_nan(m[1], f[1]), max_nan(m[2], f[2]), max_nan(m[3], f[3])};
+}
+
 // a wave-uniform double pinned to scalar registers (uniform fp64 values are computed on the VALU; left in VGPRs across a kernel's main
 // loop they are spilled to scratch and reloaded -- a memory round trip -- in the phase that uses them)
 __device__ __forceinline__ double uniform_f64(double x) {

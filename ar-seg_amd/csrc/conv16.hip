@@ -45,14 +45,8 @@ __device__ __forceinline__ f32x16 mfma16(const u32x4 a, const u32x4 b, const f32
     else return __builtin_amdgcn_mfma_f32_32x32x16_f16(__builtin_bit_cast(h16x8, a), __builtin_bit_cast(h16x8, b), c, 0, 0, 0);
 }
 
-// activation as arithmetic on two uniform parameters (no switch per element: the epilogues apply it to 32-64 values per lane, and the four-way
-// branch per value made them as long as the MFMAs of a short-K tile): none / relu / prelu = max(v >= 0 ? v : v * s, lo) with (s, lo) = (1, -inf) /
-// (1, 0) / (slope, -inf); sigmoid keeps its (uniform) branch
-__device__ __forceinline__ float act_apply(float v, int act, float slope) {
-    if (act == ARSEG_ACT_SIGMOID) return 1.0f / (1.0f + __expf(-v));
-    const float s = act == ARSEG_ACT_PRELU ? slope : 1.0f, lo = act == ARSEG_ACT_RELU ? 0.0f : -INFINITY;
-    return fmaxf(v >= 0.0f ? v : v * s, lo);
-}
+// (the activation of the epilogues is arseg_act_apply: selects on uniform parameters, no switch per element -- they apply it to 32-64 values per
+// lane, and the four-way branch per value made them as long as the MFMAs of a short-K tile)
 
 template <bool BF, int CO_T, int BK>      // BK: K step (32 | 64 halves); LDS rows carry 8 halves of padding (ds_read_b128 of 32 rows conflict free)
 __global__ __launch_bounds__(256) void conv16_kernel(const Conv16Params p) {
@@ -232,7 +226,7 @@ __global__ __launch_bounds__(256) void conv16_kernel(const Conv16Params p) {
                         const uint16_t rb = nco == 8 ? (uint16_t)((e & 1) ? rres[e >> 1] >> 16 : rres[e >> 1] & 0xffffu) : p.res[(size_t)m * p.res_ld + min(co + e, p.Cout - 1)];
                         x += arseg_h2f<BF>(rb);
                     }
-                    o[e] = arseg_f2h<BF>(act_apply(x, p.act, p.slope));
+                    o[e] = arseg_f2h<BF>(arseg_act_apply(x, arseg_act(p.act, p.slope)));
                 }
                 uint16_t *dst = p.out + (size_t)m * p.out_ld + co;
                 if (nco == 8) *reinterpret_cast<u32x4 *>(dst) = u32x4{o[0] | ((unsigned)o[1] << 16), o[2] | ((unsigned)o[3] << 16), o[4] | ((unsigned)o[5] << 16), o[6] | ((unsigned)o[7] << 16)};
@@ -484,7 +478,7 @@ __global__ __launch_bounds__(128 * WM, (BN == 64 ? 4 : 2)) void conv16_patch_ker
                 for (int e = 0; e < 8; ++e) {
                     float x = (e < 4 ? v0[e] : v1[e - 4]) * (e < 4 ? s0[e] : s1[e - 4]) + (e < 4 ? b0[e] : b1[e - 4]);
                     if (p.res) x += arseg_h2f<BF>((uint16_t)((e & 1) ? rres[e >> 1] >> 16 : rres[e >> 1] & 0xffffu));
-                    o[e] = arseg_f2h<BF>(act_apply(x, p.act, p.slope));
+                    o[e] = arseg_f2h<BF>(arseg_act_apply(x, arseg_act(p.act, p.slope)));
                 }
                 *reinterpret_cast<u32x4 *>(p.out + m * p.out_ld + co) =
                     u32x4{o[0] | ((unsigned)o[1] << 16), o[2] | ((unsigned)o[3] << 16), o[4] | ((unsigned)o[5] << 16), o[6] | ((unsigned)o[7] << 16)};
@@ -492,7 +486,7 @@ __global__ __launch_bounds__(128 * WM, (BN == 64 ? 4 : 2)) void conv16_patch_ker
                 for (int e = 0; e < nco; ++e) {
                     float x = (e < 4 ? v0[e] : v1[e - 4]) * (p.scale ? p.scale[co + e] : 1.0f) + (p.bias ? p.bias[co + e] : 0.0f);
                     if (p.res) x += arseg_h2f<BF>(p.res[m * p.res_ld + co + e]);
-                    p.out[m * p.out_ld + co + e] = arseg_f2h<BF>(act_apply(x, p.act, p.slope));
+                    p.out[m * p.out_ld + co + e] = arseg_f2h<BF>(arseg_act_apply(x, arseg_act(p.act, p.slope)));
                 }
             }
         }
@@ -607,7 +601,7 @@ __global__ __launch_bounds__(256, 2) void conv16_stem_kernel(const Conv16Params 
                     const f32x4 sc = SBl[co >> 2], bi = SBl[16 + (co >> 2)];
                     uint16_t o[4];
 #pragma unroll
-                    for (int e = 0; e < 4; ++e) o[e] = arseg_f2h<BF>(act_apply(acc[i][k][4 * q4 + e] * sc[e] + bi[e], p.act, p.slope));
+                    for (int e = 0; e < 4; ++e) o[e] = arseg_f2h<BF>(arseg_act_apply(acc[i][k][4 * q4 + e] * sc[e] + bi[e], arseg_act(p.act, p.slope)));
                     *reinterpret_cast<u32x2 *>(dst + co) = u32x2{o[0] | ((unsigned)o[1] << 16), o[2] | ((unsigned)o[3] << 16)};
                 }
         }
@@ -647,7 +641,7 @@ __global__ __launch_bounds__(256) void conv16_splitk_reduce_kernel(const Conv16P
         for (int e = 0; e < 8; ++e) {
             float x = (e < 4 ? a[e] : b[e - 4]) * (p.scale ? p.scale[co + e] : 1.0f) + (p.bias ? p.bias[co + e] : 0.0f);
             if (p.res) x += arseg_h2f<BF>((uint16_t)((e & 1) ? rres[e >> 1] >> 16 : rres[e >> 1] & 0xffffu));
-            o[e] = arseg_f2h<BF>(act_apply(x, p.act, p.slope));
+            o[e] = arseg_f2h<BF>(arseg_act_apply(x, arseg_act(p.act, p.slope)));
         }
         *reinterpret_cast<u32x4 *>(p.out + (size_t)m * p.out_ld + co) =
             u32x4{o[0] | ((unsigned)o[1] << 16), o[2] | ((unsigned)o[3] << 16), o[4] | ((unsigned)o[5] << 16), o[6] | ((unsigned)o[7] << 16)};

@@ -64,15 +64,6 @@ struct ConvParams {
     long long in_bs, w_bs, out_bs;   // batched GEMM mode (blockIdx.y = batch index): element strides between problems
 };
 
-__device__ __forceinline__ float apply_act(float v, int act, float slope) {
-    switch (act) {
-        case ARSEG_ACT_RELU: return fmaxf(v, 0.0f);
-        case ARSEG_ACT_PRELU: return v >= 0.0f ? v : v * slope;
-        case ARSEG_ACT_SIGMOID: return 1.0f / (1.0f + __expf(-v));
-        default: return v;
-    }
-}
-
 // fp32 x4 -> (hi, lo) fp16 x4 each (arseg_common.h: hi = RTZ fp16 of x, lo = fp16 of x - hi; representable range |x| <= 131008)
 __device__ __forceinline__ void split_f16x3(const f32x4 v, uint2 &hi, uint2 &lo) {
     unsigned h01, h23, l01, l23;
@@ -91,24 +82,14 @@ __device__ __forceinline__ void range_report(const ConvParams &p, bool watch, fl
 }
 
 // Branch-free epilogue of one accumulator element: scale, bias, residual, activation, store.  The bounds tests become out-of-range
-// buffer offsets (loads return 0, stores are dropped), the activation is arithmetic on two uniform parameters -- the per-element
+// buffer offsets (loads return 0, stores are dropped), the activation is selects on uniform parameters (arseg_act_apply) -- the per-element
 // `continue` / `if (res)` / switch form compiled to ~3 branches and a 64-bit multiply per element (a fifth of a short-K tile's time).
-struct EpiAct { float slope, lo; bool sigmoid; };
-__device__ __forceinline__ EpiAct epi_act(int act, float slope) {
-    EpiAct a;
-    a.slope = act == ARSEG_ACT_PRELU ? slope : 1.0f;               // v >= 0 ? v : v * slope   (NONE / RELU: slope 1)
-    a.lo = act == ARSEG_ACT_RELU ? 0.0f : -INFINITY;                // then max(v, lo)
-    a.sigmoid = act == ARSEG_ACT_SIGMOID;
-    return a;
-}
 template <bool RES>
-__device__ __forceinline__ void epi_store(float v, float sc, float bi, const EpiAct a, const __amdgpu_buffer_rsrc_t o_rsrc,
+__device__ __forceinline__ void epi_store(float v, float sc, float bi, const ArsegAct a, const __amdgpu_buffer_rsrc_t o_rsrc,
                                           const __amdgpu_buffer_rsrc_t r_rsrc, unsigned o_off, unsigned r_off) {
     v = v * sc + bi;
     if constexpr (RES) v += __builtin_bit_cast(float, __builtin_amdgcn_raw_buffer_load_b32(r_rsrc, r_off, 0, 0));
-    if (a.sigmoid) v = 1.0f / (1.0f + __expf(-v));                  // (uniform)
-    else v = fmaxf(v >= 0.0f ? v : v * a.slope, a.lo);
-    __builtin_amdgcn_raw_buffer_store_b32(__builtin_bit_cast(unsigned, v), o_rsrc, o_off, 0, 0);
+    __builtin_amdgcn_raw_buffer_store_b32(__builtin_bit_cast(unsigned, arseg_act_apply(v, a)), o_rsrc, o_off, 0, 0);
 }
 
 template <int BM, int BN, int BK, int NBUF, int MATH, int NWM = 2, int NWN = 2>      // NWM x NWN waves, wave tile BM/NWM x BN/NWN
@@ -364,7 +345,7 @@ __global__ __launch_bounds__(64 * NWM * NWN) void conv_igemm_kernel(const ConvPa
         constexpr unsigned OOBS = 0x80000000u;
         const __amdgpu_buffer_rsrc_t o_rsrc = __builtin_amdgcn_make_buffer_rsrc(gout, 0, (int)p.out_bytes, 0x00020000);
         const __amdgpu_buffer_rsrc_t r_rsrc = __builtin_amdgcn_make_buffer_rsrc(const_cast<float *>(p.res ? p.res : gout), 0, (int)p.res_bytes, 0x00020000);
-        const EpiAct ea = epi_act(p.act, p.slope);
+        const ArsegAct ea = arseg_act(p.act, p.slope);
         auto run = [&](auto res_tag) {
             constexpr bool RES = decltype(res_tag)::value;
 #pragma unroll
@@ -405,7 +386,7 @@ __global__ __launch_bounds__(64 * NWM * NWN) void conv_igemm_kernel(const ConvPa
                 if (p.nsplit == 1) {
                     v = v * sc + bi;
                     if (p.res) v += p.res[(size_t)m * p.res_ld + n];
-                    gout[(size_t)m * p.out_ld + n] = apply_act(v, p.act, p.slope);
+                    gout[(size_t)m * p.out_ld + n] = arseg_act_apply(v, arseg_act(p.act, p.slope));
                 } else {
                     p.ws[((size_t)blockIdx.z * p.M + m) * p.Cout + n] = v;
                 }
@@ -649,7 +630,7 @@ __global__ __launch_bounds__(128 * WM, (BN == 64 ? (WM == 2 ? 3 : 4) : 2)) void 
         constexpr unsigned OOBS = 0x80000000u;
         const __amdgpu_buffer_rsrc_t o_rsrc = __builtin_amdgcn_make_buffer_rsrc(p.out, 0, (int)p.out_bytes, 0x00020000);
         const __amdgpu_buffer_rsrc_t r_rsrc = __builtin_amdgcn_make_buffer_rsrc(const_cast<float *>(p.res ? p.res : p.out), 0, (int)p.res_bytes, 0x00020000);
-        const EpiAct ea = epi_act(p.act, p.slope);
+        const ArsegAct ea = arseg_act(p.act, p.slope);
         auto run = [&](auto res_tag) {
             constexpr bool RES = decltype(res_tag)::value;
 #pragma unroll
@@ -687,7 +668,7 @@ __global__ __launch_bounds__(128 * WM, (BN == 64 ? (WM == 2 ? 3 : 4) : 2)) void 
                 const size_t m = ((size_t)img * p.Ho + oy) * p.Wo + ox;
                 float v = acc[tm][tn][r] * sc + bi;
                 if (p.res) v += p.res[m * p.res_ld + n];
-                p.out[m * p.out_ld + n] = apply_act(v, p.act, p.slope);
+                p.out[m * p.out_ld + n] = arseg_act_apply(v, arseg_act(p.act, p.slope));
             }
         }
 }
@@ -704,7 +685,7 @@ __global__ __launch_bounds__(256) void conv_splitk_reduce_kernel(const ConvParam
         for (int j = 0; j < 4; ++j) {
             float x = v[j] * (p.scale ? p.scale[n + j] : 1.0f) + (p.bias ? p.bias[n + j] : 0.0f);
             if (p.res) x += p.res[(size_t)m * p.res_ld + n + j];
-            p.out[(size_t)m * p.out_ld + n + j] = apply_act(x, p.act, p.slope);
+            p.out[(size_t)m * p.out_ld + n + j] = arseg_act_apply(x, arseg_act(p.act, p.slope));
         }
     }
 }

@@ -166,8 +166,7 @@ __device__ __forceinline__ void up2_role(const Up2Params &p, unsigned char *lds)
         float sc[4], bi[4];
 #pragma unroll
         for (int r = 0; r < 4; ++r) { sc[r] = p.scale ? p.scale[c0 + r] : 1.0f; bi[r] = p.bias ? p.bias[c0 + r] : 0.0f; }
-        const float a_slope = p.act == ARSEG_ACT_PRELU ? p.slope : 1.0f, a_lo = p.act == ARSEG_ACT_RELU ? 0.0f : -INFINITY;
-        const bool a_sigmoid = p.act == ARSEG_ACT_SIGMOID;
+        const ArsegAct ea = arseg_act(p.act, p.slope);
         const u32x4 o_rsrc = make_rsrc(p.out, p.out_bytes);
         // byte offset of this lane's fragment in a plane for patch pixel l15 + C, without the 64 C term: by C & 7 (the swizzle looks at bit 2 of the pixel)
         unsigned swz[8];
@@ -220,12 +219,7 @@ __device__ __forceinline__ void up2_role(const Up2Params &p, unsigned char *lds)
                 const int oy = tp.ty0 + mf;
                 f32x4 v;
 #pragma unroll
-                for (int r = 0; r < 4; ++r) {
-                    float x = acc[mf][r] * sc[r] + bi[r];
-                    if (a_sigmoid) x = 1.0f / (1.0f + __expf(-x));                  // (uniform)
-                    else x = fmaxf(x >= 0.0f ? x : x * a_slope, a_lo);
-                    v[r] = x;
-                }
+                for (int r = 0; r < 4; ++r) v[r] = arseg_act_apply(acc[mf][r] * sc[r] + bi[r], ea);
                 const unsigned m = ((unsigned)tp.img * (unsigned)p.H + (unsigned)oy) * (unsigned)p.W + (unsigned)ox;
                 store16_buf(__builtin_bit_cast(u32x4, v), o_rsrc, (oy < p.H && ox < p.W) ? (m * (unsigned)p.out_ld + (unsigned)c0) * 4u : OOB);
             }

@@ -63,7 +63,7 @@ constexpr int Q_OFF = LS_OFF + 2 * 16 * LPL * 16;    // 112,640  query records [
 constexpr int R_OFF = Q_OFF + 2 * 16 * 16 * 16;      // 120,832  residual records lr_up(query) [2 patches][16 groups][16 queries] fp32 x 4
 constexpr int XB_OFF = R_OFF + 2 * 16 * 16 * 16;     // 129,024  partials of the kh-1 waves [2 patches][4 chunks + {m, z}][64 lanes]
 constexpr int TW_OFF = XB_OFF + 2 * 5 * 64 * 16;     // 139,264  [48] {ex, wx, ey, wy} with the tap validity folded in
-constexpr int TO_OFF = TW_OFF + NGP * 16;            //          [48] byte offsets of the four (clamped) taps of a pixel: NW, NE, SW, SE
+constexpr int TO_OFF = TW_OFF + NGP * 16;            //          [48] byte offsets of the four (clamped) taps of a pixel: NW, NE, SW, SE (beyond the buffer: nothing to sample)
 constexpr int WD_OFF = TO_OFF + NGP * 16 + 2 * 16;   //          depthwise weights [key | value | query][16 groups][9 taps + bias]
                                                      //          (32 bytes of padding in front: the offsets below stay as measured)
 constexpr int WF_OFF = WD_OFF + 3 * 160 * 16;        // 147,904  classifier records [4 chunks][4 groups][32] {4 hi | 4 lo}
@@ -660,13 +660,19 @@ __device__ __forceinline__ void producer(const RollParams &p, const Smem &sm, co
                 // ---- tap table of gather t + 2 from the sampling positions of H1(t)
                 if (tap_lane && t >= -2 && t <= S + 1) {
                     const int gy = ys + 2 * t + trr, gx = x0 - 4 + tcc;
+                    // A pixel with nothing to sample -- outside the image (conv padding), or a sample wholly off the image in x or in y -- gets
+                    // offsets beyond ref_bytes (a frame stays below 2 GiB; still beyond it with the gather lane's channel offset added): its loads
+                    // return zeros.  A clamped pixel times weight 0 would hand a NaN of that pixel to an output grid_sample gives nothing.  (One tap
+                    // of a pair off the image clamps onto its in-image partner, which the sample reads anyway.)
+                    constexpr unsigned OOB_TAP = 0x80000000u;
                     f32x4 w = {0.f, 0.f, 0.f, 0.f};
-                    u32x4 o = {0u, 0u, 0u, 0u};
+                    u32x4 o = {OOB_TAP, OOB_TAP, OOB_TAP, OOB_TAP};
                     if ((unsigned)gy < (unsigned)Hp && (unsigned)gx < (unsigned)Wp) {      // outside the image the warped feature is zero (conv padding)
                         const Taps tp = make_taps(ngx, ngy, Hp, Wp);
                         const int xa = min(max(tp.x0, 0), Wp - 1), xc = min(max(tp.x0 + 1, 0), Wp - 1);
                         const int ya = min(max(tp.y0, 0), Hp - 1), yc = min(max(tp.y0 + 1, 0), Hp - 1);
-                        o = u32x4{(unsigned)(ya * Wp + xa), (unsigned)(ya * Wp + xc), (unsigned)(yc * Wp + xa), (unsigned)(yc * Wp + xc)} * PXB;
+                        if ((tp.vx0 || tp.vx1) && (tp.vy0 || tp.vy1))
+                            o = u32x4{(unsigned)(ya * Wp + xa), (unsigned)(ya * Wp + xc), (unsigned)(yc * Wp + xa), (unsigned)(yc * Wp + xc)} * PXB;
                         w = f32x4{tp.vx0 ? tp.ex : 0.f, tp.vx1 ? tp.wx : 0.f, tp.vy0 ? tp.ey : 0.f, tp.vy1 ? tp.wy : 0.f};
                     }
                     sm.TapW[tl] = w; sm.TapO[tl] = o;

@@ -37,7 +37,7 @@ constexpr int KPLK = 496, KPLV = 500;                // record plane strides: ke
                                                      // (transpose read) 16 banks apart
 constexpr int BIG_BYTES = 16 * HPL * 16;             // 147,712: staged region / lr_up tile / key records / value records
 constexpr int TAPW_OFF = BIG_BYTES;                  // [576] {ex, wx, ey, wy} with the tap validity folded in (0 = tap outside)
-constexpr int TAPO_OFF = TAPW_OFF + R4N * 16;        // [576] pixel index of the NW tap | dx << 30 | dy << 31 (clamped taps)
+constexpr int TAPO_OFF = TAPW_OFF + R4N * 16;        // [576] pixel index of the NW tap | dx << 30 | dy << 31 (clamped taps), or TAP_NONE
 constexpr int WFS_OFF = 16 * KPLV * 16;              // classifier records: behind the value records, inside BIG (128,000 + 8 KB <= 147,712)
 constexpr int WDQ_OFF = TAPO_OFF + R4N * 4;          // [4 chunks][9 taps + bias][4 groups] query conv weights
 constexpr int LRT_OFF = WDQ_OFF + 4 * 10 * 4 * 16;      // [18 rows | 18 columns] of the lr_up tile: {tap offset 0, tap offset 1, weight 0, weight 1}
@@ -56,6 +56,15 @@ struct RRParams {
     unsigned p_bytes, l_bytes, lr_bytes;
     float sy, sx;
 };
+
+// A region pixel with nothing to sample (outside the image, or a sample wholly off it): its four taps read one pixel of zeros -- the image's
+// pixel count stays below 2^30 (arseg_creff_warp_select), dx = dy = 0.
+constexpr unsigned TAP_NONE = 0x3FFFFFFFu;
+__device__ __attribute__((aligned(16))) const float rr_zero_pixel[CH] = {};
+__device__ __forceinline__ const float *tap_src(const float *img, unsigned o) {          // (a select of the address: no branch around the loads)
+    const unsigned pix = o & 0x3FFFFFFFu;
+    return pix == TAP_NONE ? rr_zero_pixel : img + (size_t)pix * CH;
+}
 
 __device__ __forceinline__ void dma4_glb(const void *g, unsigned lds_base) {        // LDS[lds_base + lane * 4] <- 4 bytes at g
     unsigned keep;
@@ -172,7 +181,7 @@ __global__ __launch_bounds__(NT) void creff_rr_kernel(const RRParams p) {
             const int yr = t / R4W, xr = t - yr * R4W;
             const int gy = ty0 - 4 + yr, gx = tx0 - 4 + xr;
             f32x4 w = {0.f, 0.f, 0.f, 0.f};
-            unsigned o = 0;
+            unsigned o = TAP_NONE;                 // nothing to sample: the gather reads zeros (tap_src), not a clamped pixel times weight 0
             if ((unsigned)gy < (unsigned)Hp && (unsigned)gx < (unsigned)Wp) {      // outside the image the region is zero (conv padding)
                 double fx, fy;
                 if (mv_ident) {                        // identity resize (PSPNet): (q/4 * Hp) / H == q/4 exactly
@@ -189,7 +198,8 @@ __global__ __launch_bounds__(NT) void creff_rr_kernel(const RRParams p) {
                 const Taps tp = make_taps(ngx, ngy, Hq, Wq);
                 const int xa = min(max(tp.x0, 0), Wp - 1), xc = min(max(tp.x0 + 1, 0), Wp - 1);
                 const int ya = min(max(tp.y0, 0), Hp - 1), yc = min(max(tp.y0 + 1, 0), Hp - 1);
-                o = (unsigned)(ya * Wp + xa) | ((unsigned)(xc - xa) << 30) | ((unsigned)(yc - ya) << 31);
+                // (a sample wholly off the image in x or in y keeps TAP_NONE; one tap of a pair off the image clamps onto its in-image partner)
+                if ((tp.vx0 || tp.vx1) && (tp.vy0 || tp.vy1)) o = (unsigned)(ya * Wp + xa) | ((unsigned)(xc - xa) << 30) | ((unsigned)(yc - ya) << 31);
                 w = f32x4{tp.vx0 ? tp.ex : 0.f, tp.vx1 ? tp.wx : 0.f, tp.vy0 ? tp.ey : 0.f, tp.vy1 ? tp.wy : 0.f};
             }
             TapW[t] = w; TapO[t] = o;
@@ -264,7 +274,7 @@ __global__ __launch_bounds__(NT) void creff_rr_kernel(const RRParams p) {
             for (int q = 0; q < 4; ++q) {                    // rare: one pixel at a time keeps the register footprint of the common path
                 const int pq = p00 + (q >> 1) * R4W + (q & 1);
                 const unsigned o = TapO[pq];
-                const float *a = g_img + (size_t)(o & 0x3FFFFFFFu) * CH + g16 * 4;
+                const float *a = tap_src(g_img, o) + g16 * 4;
                 const unsigned dxo = (o & 0x40000000u) ? CH : 0u, dyo = (o & 0x80000000u) ? g_row_off : 0u;
                 const f32x4 x0 = *reinterpret_cast<const f32x4 *>(a), x1 = *reinterpret_cast<const f32x4 *>(a + dxo);
                 const f32x4 x2 = *reinterpret_cast<const f32x4 *>(a + dyo), x3 = *reinterpret_cast<const f32x4 *>(a + dyo + dxo);
@@ -278,7 +288,7 @@ __global__ __launch_bounds__(NT) void creff_rr_kernel(const RRParams p) {
     auto p_issue = [&](f32x4 (&x)[4]) {
         RR_TID(t);
         const unsigned o = TapO[p_pix()];
-        const float *a = g_img + (size_t)(o & 0x3FFFFFFFu) * CH + (t & 15) * 4;
+        const float *a = tap_src(g_img, o) + (t & 15) * 4;
         const unsigned dxo = (o & 0x40000000u) ? CH : 0u, dyo = (o & 0x80000000u) ? g_row_off : 0u;
         x[0] = *reinterpret_cast<const f32x4 *>(a); x[1] = *reinterpret_cast<const f32x4 *>(a + dxo);
         x[2] = *reinterpret_cast<const f32x4 *>(a + dyo); x[3] = *reinterpret_cast<const f32x4 *>(a + dyo + dxo);

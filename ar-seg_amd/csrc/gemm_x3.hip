@@ -284,7 +284,7 @@ __global__ __launch_bounds__(64 * NWM * NWN) void gemm_x3_kernel(const GX3Params
     }
 
     // epilogue: D[n][m]: lane (i16, kq) of fragment (a, c) holds channels n..n+3 (n = 16c + 4kq) of row m = 16a + i16
-    const bool prelu = p.act == ARSEG_ACT_PRELU, relu = p.act == ARSEG_ACT_RELU, sigm = p.act == ARSEG_ACT_SIGMOID;
+    const ArsegAct ea = arseg_act(p.act, p.slope);
     float vmax = 0.f;
     // this lane's rows: where each goes (orow < 0: nowhere) and whether it is a pixel of the image (implicit 3x3: border rows of the padded
     // geometry are computed like any other and then dropped or zeroed)
@@ -335,11 +335,7 @@ __global__ __launch_bounds__(64 * NWM * NWN) void gemm_x3_kernel(const GX3Params
                 }
             }
 #pragma unroll
-            for (int e = 0; e < 4; ++e) {
-                if (relu) v[e] = fmaxf(v[e], 0.f);
-                else if (prelu) v[e] = v[e] >= 0.f ? v[e] : v[e] * p.slope;
-                else if (sigm) v[e] = 1.0f / (1.0f + __expf(-v[e]));
-            }
+            for (int e = 0; e < 4; ++e) v[e] = arseg_act_apply(v[e], ea);
             if ((border >> a) & 1u) v = f32x4{0.f, 0.f, 0.f, 0.f};          // (out_mode 2) the zero border of the next conv's operand
             if constexpr (FMT != 0) {
                 const uint2 o = {(unsigned)arseg_f2h<FMT == 2>(v[0]) | ((unsigned)arseg_f2h<FMT == 2>(v[1]) << 16),

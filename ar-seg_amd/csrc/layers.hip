@@ -32,7 +32,7 @@ __global__ __launch_bounds__(256) void maxpool3x3s2_kernel(const typename ArsegS
                 float f[S::V];
                 S::ld(in + (((size_t)n * H + iy) * W + ix) * C + c, f);
 #pragma unroll
-                for (int e = 0; e < S::V; ++e) m[e] = fmaxf(m[e], f[e]);
+                for (int e = 0; e < S::V; ++e) m[e] = max_nan(m[e], f[e]);          // (fmaxf would drop a NaN)
             }
         }
         S::st(out + pix * C + c, m);
@@ -59,7 +59,7 @@ __global__ __launch_bounds__(CV * PL) void window_reduce_kernel(const float *__r
         for (int i = pl; i < cnt; i += PL) {
             const int yy = y0 + i / ww, xx = x0 + i % ww;
             const f32x4 v = *reinterpret_cast<const f32x4 *>(in + (((size_t)n * H + yy) * W + xx) * in_ld + c);
-            if (IS_MAX) { acc[0] = fmaxf(acc[0], v[0]); acc[1] = fmaxf(acc[1], v[1]); acc[2] = fmaxf(acc[2], v[2]); acc[3] = fmaxf(acc[3], v[3]); }
+            if (IS_MAX) acc = max_nan(acc, v);
             else acc += v;
         }
     }
@@ -70,7 +70,7 @@ __global__ __launch_bounds__(CV * PL) void window_reduce_kernel(const float *__r
         if (pl < s) {
             const f32x4 o = red[pl + s][cv];
             f32x4 t = red[pl][cv];
-            if (IS_MAX) { t[0] = fmaxf(t[0], o[0]); t[1] = fmaxf(t[1], o[1]); t[2] = fmaxf(t[2], o[2]); t[3] = fmaxf(t[3], o[3]); }
+            if (IS_MAX) t = max_nan(t, o);
             else t += o;
             red[pl][cv] = t;
         }
@@ -101,7 +101,7 @@ __global__ __launch_bounds__(256) void global_parts_kernel(const float *__restri
     if (c < C)
         for (int i = p0 + pl; i < p1; i += 16) {
             const f32x4 v = *reinterpret_cast<const f32x4 *>(in + ((size_t)n * HW + i) * in_ld + c);
-            if (IS_MAX) { acc[0] = fmaxf(acc[0], v[0]); acc[1] = fmaxf(acc[1], v[1]); acc[2] = fmaxf(acc[2], v[2]); acc[3] = fmaxf(acc[3], v[3]); }
+            if (IS_MAX) acc = max_nan(acc, v);
             else acc += v;
         }
     red[pl][cv] = acc;
@@ -111,7 +111,7 @@ __global__ __launch_bounds__(256) void global_parts_kernel(const float *__restri
         if (pl < s) {
             const f32x4 o = red[pl + s][cv];
             f32x4 t = red[pl][cv];
-            if (IS_MAX) { t[0] = fmaxf(t[0], o[0]); t[1] = fmaxf(t[1], o[1]); t[2] = fmaxf(t[2], o[2]); t[3] = fmaxf(t[3], o[3]); }
+            if (IS_MAX) t = max_nan(t, o);
             else t += o;
             red[pl][cv] = t;
         }
@@ -126,7 +126,7 @@ __global__ __launch_bounds__(256) void global_combine_kernel(const float *__rest
     f32x4 acc = *reinterpret_cast<const f32x4 *>(ws + (size_t)n * parts * C + c);
     for (int q = 1; q < parts; ++q) {
         const f32x4 v = *reinterpret_cast<const f32x4 *>(ws + ((size_t)n * parts + q) * C + c);
-        if (IS_MAX) { acc[0] = fmaxf(acc[0], v[0]); acc[1] = fmaxf(acc[1], v[1]); acc[2] = fmaxf(acc[2], v[2]); acc[3] = fmaxf(acc[3], v[3]); }
+        if (IS_MAX) acc = max_nan(acc, v);
         else acc += v;
     }
     if (!IS_MAX) acc = acc / (float)HW;
@@ -135,8 +135,7 @@ __global__ __launch_bounds__(256) void global_combine_kernel(const float *__rest
 
 // ------------------------------------------------------------------ global mean / max of 16-bit maps: fp32 partials of pixel slices, then the result
 // (a different algorithm from the fp32 kernels above: slices of pixels and a final pass over the slices.)  The max widens to fp32 exactly and
-// narrows back exactly -- it is one of the inputs -- and a NaN wins (fmaxf would drop it): max_nan keeps the first NaN met.
-__device__ __forceinline__ float max_nan(float m, float f) { return (f > m || f != f) ? f : m; }
+// narrows back exactly -- it is one of the inputs -- and a NaN wins, as in the fp32 kernels above (max_nan, arseg_device.h).
 template <bool IS_MAX> __device__ __forceinline__ float slice_op(float a, float f) { return IS_MAX ? max_nan(a, f) : a + f; }
 
 // step 1: grid (C/256 blocks of 32 channel vectors, N, S slices); block = 32 channel vectors x 8 pixel lanes; part[n][s][c] fp32

@@ -16,18 +16,9 @@
 //   out(Y, X)  = sum_ky UpY(H_ky(., X))(Y + ky - 1)             both Y = 2y, 2y+1
 // A thread owns a low-resolution column x and four channels and walks a strip of rows keeping H of three rows in registers: 27 16-byte
 // loads per low-resolution pixel, the 3x column re-use is left to L1/L2.  Memory-bound: z is read once from HBM, out written once.
-#include "arseg_common.h"
+#include "arseg_device.h"
 
 namespace {
-
-__device__ __forceinline__ float up_act(float v, int act, float slope) {
-    switch (act) {
-        case ARSEG_ACT_RELU: return fmaxf(v, 0.0f);
-        case ARSEG_ACT_PRELU: return v >= 0.0f ? v : v * slope;
-        case ARSEG_ACT_SIGMOID: return 1.0f / (1.0f + __expf(-v));
-        default: return v;
-    }
-}
 
 // SPLIT: `out` is written as split rows (the operand format of arseg_gemm_x3_fwd, csrc/gemm_x3.hip; out_ld == C, C % 32 == 0) -- the output is
 // the next tap GEMM's activation operand (up_1 -> up_2) -- and the running |out| maximum feeds the operand range word.
@@ -77,6 +68,7 @@ __global__ __launch_bounds__(256) void up2_tap_gather_kernel(const float *__rest
     hrow(y0, H0);
     float *on = out + (size_t)n * (2 * h) * (2 * w) * out_ld + (SPLIT ? 0 : c);
     float vmax = 0.f;
+    const ArsegAct ea = arseg_act(act, slope);
     auto put = [&](size_t pix, const f32x4 v) {
         if constexpr (SPLIT) {
             unsigned h01, h23, l01, l23;
@@ -104,7 +96,7 @@ __global__ __launch_bounds__(256) void up2_tap_gather_kernel(const float *__rest
             o0 = o0 * sc + bi;
             o1 = o1 * sc + bi;
 #pragma unroll
-            for (int e = 0; e < 4; ++e) { o0[e] = up_act(o0[e], act, slope); o1[e] = up_act(o1[e], act, slope); }
+            for (int e = 0; e < 4; ++e) { o0[e] = arseg_act_apply(o0[e], ea); o1[e] = arseg_act_apply(o1[e], ea); }
             put((size_t)(2 * y) * (2 * w) + 2 * x + b, o0);
             put((size_t)(2 * y + 1) * (2 * w) + 2 * x + b, o1);
         }

@@ -13,6 +13,8 @@
 
 namespace {
 
+__device__ __attribute__((aligned(16))) const unsigned warp_zeros[4] = {0u, 0u, 0u, 0u};      // what a tap outside the image reads (warp_tap_ptr)
+
 __device__ __forceinline__ f32x4 gather4(const float *img, const Taps &t, int W, int ld, int c) {
     f32x4 acc = {0.f, 0.f, 0.f, 0.f};
     const float *p = img + ((long long)t.y0 * W + t.x0) * ld + c;
@@ -105,7 +107,7 @@ __global__ __launch_bounds__(256) void mv_resize_kernel(const int16_t *__restric
 // arithmetic (two divisions) and the tap setup and parks the result in LDS -- done by 16 lanes per pixel it would occupy
 // whole waves with 4 useful lanes.  Phase 2: 16 lanes per pixel walk the channel vectors, four pixels groups per thread;
 // the four taps of a pixel are read as whole contiguous pixels (C*4 bytes each), branch-free: taps outside the image get
-// weight 0 and a clamped (in-range) address.
+// weight 0 and the address of 16 zero bytes.
 __global__ __launch_bounds__(256) void warp_mvq_nhwc_kernel(const float *__restrict__ feat, const int16_t *__restrict__ mv,
                                                             float *__restrict__ out, int N, int C, int Hp, int Wp, int H, int W, int c8) {
     __shared__ int s_off[4][64];
@@ -124,10 +126,10 @@ __global__ __launch_bounds__(256) void warp_mvq_nhwc_kernel(const float *__restr
         const float w0 = s_w[0][pl], w1 = s_w[1][pl], w2 = s_w[2][pl], w3 = s_w[3][pl];
         for (int c = sub * 4; c < C; c += 64) {
             f32x4 acc = {0.f, 0.f, 0.f, 0.f};
-            acc += *reinterpret_cast<const f32x4 *>(img + (size_t)o0 * C + c) * w0;
-            acc += *reinterpret_cast<const f32x4 *>(img + (size_t)o1 * C + c) * w1;
-            acc += *reinterpret_cast<const f32x4 *>(img + (size_t)o2 * C + c) * w2;
-            acc += *reinterpret_cast<const f32x4 *>(img + (size_t)o3 * C + c) * w3;
+            acc += *reinterpret_cast<const f32x4 *>(warp_tap_ptr(img, o0, C, c, warp_zeros)) * w0;
+            acc += *reinterpret_cast<const f32x4 *>(warp_tap_ptr(img, o1, C, c, warp_zeros)) * w1;
+            acc += *reinterpret_cast<const f32x4 *>(warp_tap_ptr(img, o2, C, c, warp_zeros)) * w2;
+            acc += *reinterpret_cast<const f32x4 *>(warp_tap_ptr(img, o3, C, c, warp_zeros)) * w3;
             const size_t o = c8 ? ((((size_t)n * (C >> 3) + (c >> 3)) * hw + pix) * 8 + (c & 4)) : (((size_t)n * hw + pix) * C + c);
             *reinterpret_cast<f32x4 *>(out + o) = acc;      // (duplicate lanes of a clamped pixel store identical values)
         }
@@ -155,10 +157,10 @@ __global__ __launch_bounds__(256) void warp_mvq16_kernel(const uint16_t *__restr
         const float w0 = s_w[0][pl], w1 = s_w[1][pl], w2 = s_w[2][pl], w3 = s_w[3][pl];
         for (int c = sub * 8; c < C; c += 64) {
             float a[8], b[8], cc[8], d[8];
-            ArsegStore<DT>::ld(img + (size_t)o0 * C + c, a);
-            ArsegStore<DT>::ld(img + (size_t)o1 * C + c, b);
-            ArsegStore<DT>::ld(img + (size_t)o2 * C + c, cc);
-            ArsegStore<DT>::ld(img + (size_t)o3 * C + c, d);
+            ArsegStore<DT>::ld(warp_tap_ptr(img, o0, C, c, warp_zeros), a);
+            ArsegStore<DT>::ld(warp_tap_ptr(img, o1, C, c, warp_zeros), b);
+            ArsegStore<DT>::ld(warp_tap_ptr(img, o2, C, c, warp_zeros), cc);
+            ArsegStore<DT>::ld(warp_tap_ptr(img, o3, C, c, warp_zeros), d);
             f32x4 r0, r1;
 #pragma unroll
             for (int e = 0; e < 4; ++e) {

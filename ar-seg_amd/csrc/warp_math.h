@@ -69,7 +69,8 @@ __device__ __forceinline__ void mv_at(const int16_t *__restrict__ mv, int H, int
 
 // The tap table of the MV-guided warps (warp_mvq_nhwc_kernel, warp_mvq16_kernel: warp.hip): lane `slot` does the fp64 coordinate arithmetic
 // of pixel (x, y) of frame n on the Hp x Wp map and parks the four tap offsets and weights in LDS.  Branch-free taps: one outside the
-// image gets weight 0 and a clamped (in-range) offset.
+// image gets weight 0 and the offset -1, for which the kernels read zeros (warp_tap_ptr) -- a clamped pixel times weight 0 would hand a NaN or
+// an infinity of the border to samples grid_sample(padding_mode='zeros') gives nothing.
 __device__ __forceinline__ void warp_mvq_taps(const int16_t *__restrict__ mv, int n, int y, int x, int Hp, int Wp, int H, int W, int slot,
                                               int (&s_off)[4][64], float (&s_w)[4][64]) {
     double fx, fy;
@@ -84,7 +85,13 @@ __device__ __forceinline__ void warp_mvq_taps(const int16_t *__restrict__ mv, in
     const Taps t = make_taps(gx, gy, Hp, Wp);
     const int xa = min(max(t.x0, 0), Wp - 1), xc = min(max(t.x0 + 1, 0), Wp - 1);
     const int ya = min(max(t.y0, 0), Hp - 1), yc = min(max(t.y0 + 1, 0), Hp - 1);
-    s_off[0][slot] = ya * Wp + xa; s_off[1][slot] = ya * Wp + xc; s_off[2][slot] = yc * Wp + xa; s_off[3][slot] = yc * Wp + xc;
-    s_w[0][slot] = t.vy0 && t.vx0 ? t.wnw : 0.f; s_w[1][slot] = t.vy0 && t.vx1 ? t.wne : 0.f;
-    s_w[2][slot] = t.vy1 && t.vx0 ? t.wsw : 0.f; s_w[3][slot] = t.vy1 && t.vx1 ? t.wse : 0.f;
+    const bool v0 = t.vy0 && t.vx0, v1 = t.vy0 && t.vx1, v2 = t.vy1 && t.vx0, v3 = t.vy1 && t.vx1;
+    s_off[0][slot] = v0 ? ya * Wp + xa : -1; s_off[1][slot] = v1 ? ya * Wp + xc : -1; s_off[2][slot] = v2 ? yc * Wp + xa : -1; s_off[3][slot] = v3 ? yc * Wp + xc : -1;
+    s_w[0][slot] = v0 ? t.wnw : 0.f; s_w[1][slot] = v1 ? t.wne : 0.f;
+    s_w[2][slot] = v2 ? t.wsw : 0.f; s_w[3][slot] = v3 ? t.wse : 0.f;
+}
+// the 16 bytes of channels [c, c + V) of tap `off` of warp_mvq_taps: the pixel's, or zeros for a tap outside the image (a select of the address, no branch)
+template <typename T>
+__device__ __forceinline__ const T *warp_tap_ptr(const T *img, int off, int C, int c, const void *zeros) {
+    return off >= 0 ? img + (size_t)off * C + c : static_cast<const T *>(zeros);
 }

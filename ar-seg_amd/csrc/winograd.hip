@@ -182,15 +182,6 @@ __global__ __launch_bounds__(256) void wino43_input_up2_kernel(const float *__re
     if (SPLIT && range_flag && vmax > range_limit) atomicOr(range_flag, 1u);
 }
 
-__device__ __forceinline__ float wino_act(float v, int act, float slope) {
-    switch (act) {
-        case ARSEG_ACT_RELU: return fmaxf(v, 0.0f);
-        case ARSEG_ACT_PRELU: return v >= 0.0f ? v : v * slope;
-        case ARSEG_ACT_SIGMOID: return 1.0f / (1.0f + __expf(-v));
-        default: return v;
-    }
-}
-
 template <typename F>
 __global__ __launch_bounds__(256) void wino43_output_kernel(const float *__restrict__ M, const float *__restrict__ scale,
                                                             const float *__restrict__ bias, const float *__restrict__ res, int res_ld,
@@ -235,7 +226,7 @@ __global__ __launch_bounds__(256) void wino43_output_kernel(const float *__restr
                 if (res) v += *reinterpret_cast<const F *>(res + pix * res_ld + c);
                 float *vp = reinterpret_cast<float *>(&v);
 #pragma unroll
-                for (int e = 0; e < VW; ++e) vp[e] = wino_act(vp[e], act, slope);
+                for (int e = 0; e < VW; ++e) vp[e] = arseg_act_apply(vp[e], arseg_act(act, slope));
                 *reinterpret_cast<F *>(out + pix * out_ld + c) = v;
             }
         }

@@ -14,6 +14,17 @@
  *   - "NHWC" tensors are [N][H][W][ld] floats with `ld >= C` the per-pixel channel stride, so a
  *     channel slice of a wider tensor can be read or written in place (concat without copies).
  *   - No hidden global state; the library is thread-compatible (one stream per caller thread).
+ *   - Non-finite values.  A NaN or an infinity in a float input reaches the output as it does in the torch expression an entry point
+ *     restates (tests/test_gpu_nonfinite.py): (a) every output that depends on the element with non-zero weight is non-finite; (b) every
+ *     output the fp64 reference keeps finite is finite and within the entry point's tolerance; (c) a NaN stays a NaN, and for the convs
+ *     (every plan), scale_add, the pools, the global mean / max and the heads the non-finite outputs under a NaN are exactly the
+ *     reference's.  The activations (ReLU / PReLU / none), the max pools, the global max, the nearest resize and the casts are selects,
+ *     not v_max: NaN, +Inf and -Inf come out as torch's (ReLU: NaN -> NaN, -Inf -> 0).  Two kernels compute in tiles wider than an
+ *     output's receptive field, and what they may make non-finite is the reference's set grown to whole tiles: Winograd F(4,3) (4 x 4
+ *     output tiles on the dilation lattice: the 6 x 6 input transform mixes the tile) and the matrix-core CReFF kernels (2-row x 8-column
+ *     query patches: P.V runs over all keys under a patch, with probability 0 outside a query's own window).  In ARSEG_MATH_F16X3 and in
+ *     16-bit storage an infinity may come out as NaN (hi = Inf, lo = Inf - Inf): (a)-(c) hold, the Inf / NaN class is not kept.  A warp
+ *     tap outside the image reads zeros (never a clamped pixel times weight 0): grid_sample(padding_mode='zeros').
  */
 #ifndef ARSEG_HIP_H
 #define ARSEG_HIP_H
