@@ -243,7 +243,9 @@ typedef struct arseg_conv_desc {
  * ARSEG_MATH_F16X3: fp32 emulated on the fp16 matrix cores: x = hi + lo (two fp16, 22 significant bits),
  *                   a.b = a_hi.b_hi + a_hi.b_lo + a_lo.b_hi with fp32 accumulation (error ~2^-21 relative per product,
  *                   activations must satisfy |x| <= 131008 = 2 x 65504: the hi/lo pair clamps beyond, full 22-bit precision below 65504; |x| below the fp16 normal range carries an absolute error <= 6e-8).  w_packed from arseg_split_weight_f16x3_host, and `scale` must
- *                   carry that function's per-channel chan_mul_inv factor.
+ *                   carry that function's per-channel chan_mul_inv factor.  The bound is tested for every plan and route that computes
+ *                   this way (every tile_cfg, split-K, the Winograd, LDS-DMA GEMM, tap and PSP routes): max|err| / max|out| against fp64
+ *                   within 4x (8x on two K = 64 cases) the error of the plain fp32 loop (tests/test_gpu_split_accuracy.py).
  * ARSEG_MATH_F16:   reduced precision: plain fp16 operands (activations rounded to nearest, the hi halves of the same split
  *                   weights), one fp16 MFMA per product, fp32 accumulation; ~1e-3 relative error per conv.  Not used by default. */
 enum arseg_math { ARSEG_MATH_F32 = 0, ARSEG_MATH_F16X3 = 1, ARSEG_MATH_F16 = 2 };
