@@ -164,6 +164,9 @@ PROTOTYPES = {
     "arseg_rle_contours_fwd": (c_int, [_P, _P, _P, _P, c_int64, c_int, c_int, c_int, c_int, _P, _P, c_int64, _P, c_int64, _P, c_size_t, _STREAM]),
     "arseg_contours_simplify_workspace_bytes": (c_size_t, [c_int, c_int64, c_int64]),
     "arseg_contours_simplify_fwd": (c_int, [_P, _P, c_int64, _P, c_int64, c_int, c_int, c_int, c_int64, _P, _P, _P, c_int64, _P, c_size_t, _STREAM]),
+    "arseg_contours_simplify_shared_workspace_bytes": (c_size_t, [c_int, c_int64, c_int64, c_int64]),
+    "arseg_contours_simplify_shared_fwd": (c_int, [_P, _P, c_int64, _P, _P, c_int64, _P, c_int64, c_int, c_int, c_int, c_int64, _P, _P, _P, c_int64, _P,
+                                           c_size_t, _STREAM]),
 }
 
 # the SURVEY.md section 8(b) names: aliases with the prototypes of their targets

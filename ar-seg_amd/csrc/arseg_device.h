@@ -83,6 +83,40 @@ __device__ __forceinline__ float rows_sum(float x) {
     auto b = __builtin_amdgcn_permlane32_swap(__float_as_uint(x), __float_as_uint(x), false, false);
     return __uint_as_float(b[0]) + __uint_as_float(b[1]);
 }
+// The largest 64-bit key of a wave (simplify.hip, simplify_shared.hip: {value, tie-break} packed into one word).
+template <int CTRL>
+__device__ __forceinline__ unsigned long long dpp_max_u64(unsigned long long k) {
+    const unsigned lo = (unsigned)__builtin_amdgcn_update_dpp(0, (int)(unsigned)k, CTRL, 0xf, 0xf, false);
+    const unsigned hi = (unsigned)__builtin_amdgcn_update_dpp(0, (int)(unsigned)(k >> 32), CTRL, 0xf, 0xf, false);
+    const unsigned long long o = ((unsigned long long)hi << 32) | lo;
+    return o > k ? o : k;
+}
+// The largest key of the wave in every lane: within a row of 16 lanes by DPP (each step pairs every lane with one partner, so all lanes
+// end with the row's maximum; quad_perm [1,0,3,2] and [2,3,0,1], row_half_mirror, row_mirror), across the rows by the lane swaps above
+// (fed two copies they return {own, partner's} or the reverse -- the same order for both halves of the key).
+__device__ __forceinline__ unsigned long long wave_max_u64(unsigned long long k) {
+    k = dpp_max_u64<0xB1>(k);
+    k = dpp_max_u64<0x4E>(k);
+    k = dpp_max_u64<0x141>(k);
+    k = dpp_max_u64<0x140>(k);
+#pragma unroll
+    for (int step = 0; step < 2; ++step) {
+        const unsigned lo = (unsigned)k, hi = (unsigned)(k >> 32);
+        unsigned l0, l1, h0, h1;
+        if (step == 0) {
+            auto a = __builtin_amdgcn_permlane16_swap(lo, lo, false, false); l0 = a[0]; l1 = a[1];
+            auto b = __builtin_amdgcn_permlane16_swap(hi, hi, false, false); h0 = b[0]; h1 = b[1];
+        } else {
+            auto a = __builtin_amdgcn_permlane32_swap(lo, lo, false, false); l0 = a[0]; l1 = a[1];
+            auto b = __builtin_amdgcn_permlane32_swap(hi, hi, false, false); h0 = b[0]; h1 = b[1];
+        }
+        const unsigned long long k0 = ((unsigned long long)h0 << 32) | l0, k1 = ((unsigned long long)h1 << 32) | l1;
+        k = k0 > k1 ? k0 : k1;
+    }
+    // uniform from here on: what is decided from the key is decided on the scalar unit
+    return ((unsigned long long)(unsigned)__builtin_amdgcn_readfirstlane((int)(unsigned)(k >> 32)) << 32) | (unsigned)__builtin_amdgcn_readfirstlane((int)(unsigned)k);
+}
+
 // ------------------------------------------------------------------ non-finite values: the activation of every conv epilogue, the max of the pools
 // A NaN or an infinity that reaches an epilogue or a pool leaves it as torch's ReLU / PReLU / identity / max would leave it (DESIGN.md section 2,
 // "Non-finite values").  fmaxf / v_max_f32 return the operand that is NOT NaN, so neither a ReLU nor a pool may be written with them: the

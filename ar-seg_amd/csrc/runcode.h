@@ -1,5 +1,5 @@
 // The row-run code of a label plane, defined once for the passes that work on it (rle.hip, regions.hip, links.hip, absorb.hip, contours.hip,
-// simplify.hip): row_start int32 [N][H + 1] is the exclusive prefix of the rows' run counts, runs uint32 [N][cap] holds one word
+// simplify.hip, simplify_shared.hip): row_start int32 [N][H + 1] is the exclusive prefix of the rows' run counts, runs uint32 [N][cap] holds one word
 // (x_first << 8) | value per run in (y, x) order, and a run ends where the next run of its row begins, or at W.  A frame whose
 // row_start[n][H] exceeds cap overflowed: its runs are not all stored and every pass refuses it.
 //

@@ -25,7 +25,7 @@
 //   the walk               every round either keeps a vertex (at most count - 2 times) or advances a to the next kept position (at most
 //                          count times): it ends within 2 count rounds, and the loop is given 2 count + 2 explicitly.
 //   the search for b       64 flags per round from a + 1 to the loop's end: counted.
-//   the reductions         4 DPP steps and 2 lane swaps.
+//   the reductions         4 DPP steps and 2 lane swaps (arseg_device.h, wave_max_u64).
 // Clamps: a frame is processed only with 0 <= L <= lcap and 0 <= V <= vcap; a loop's first is clamped into [0, V] and its count into
 // [0, V - first], so every vertex and flag index stays below V <= vcap, and an index into the LDS stage below count <= SP_STAGE; a position taken from a reduced key is clamped into the segment
 // it was found in; an output index is used only below vcap_out, a loop index only below L <= lcap.  Coordinates are taken as 16-bit
@@ -39,8 +39,6 @@ typedef int sp_i32x4 __attribute__((ext_vector_type(4), aligned(4)));
 
 constexpr int SP_WAVES = 4;                             // waves (= loops in flight) per workgroup
 constexpr int SP_STAGE = 2048;                          // the longest loop a wave stages in LDS: 10 KiB per wave, 40 per workgroup
-constexpr int SP_DPP_XOR1 = 0xB1, SP_DPP_XOR2 = 0x4E;   // quad_perm [1,0,3,2] and [2,3,0,1]
-constexpr int SP_DPP_HALF_MIRROR = 0x141, SP_DPP_MIRROR = 0x140;
 
 struct SpP {
     const int *counts;                                  // [N][2]
@@ -67,40 +65,6 @@ __device__ __forceinline__ void sp_loop(const SpP &p, int n, int l, int V, int &
     const int *rec = p.loops + ((size_t)n * p.lcap + l) * 4;
     first = rc_clamp(rec[1], 0, V);
     cnt = rc_clamp(rec[2], 0, V - first);
-}
-
-template <int CTRL>
-__device__ __forceinline__ unsigned long long sp_dpp_max(unsigned long long k) {
-    const unsigned lo = (unsigned)__builtin_amdgcn_update_dpp(0, (int)(unsigned)k, CTRL, 0xf, 0xf, false);
-    const unsigned hi = (unsigned)__builtin_amdgcn_update_dpp(0, (int)(unsigned)(k >> 32), CTRL, 0xf, 0xf, false);
-    const unsigned long long o = ((unsigned long long)hi << 32) | lo;
-    return o > k ? o : k;
-}
-
-// The largest key of the wave in every lane: within a row of 16 lanes by DPP (each step pairs every lane with one partner, so all lanes
-// end with the row's maximum), across the rows by arseg_device.h's lane swaps (fed two copies they return {own, partner's} or the
-// reverse -- the same order for both halves of the key).
-__device__ __forceinline__ unsigned long long sp_wave_max(unsigned long long k) {
-    k = sp_dpp_max<SP_DPP_XOR1>(k);
-    k = sp_dpp_max<SP_DPP_XOR2>(k);
-    k = sp_dpp_max<SP_DPP_HALF_MIRROR>(k);
-    k = sp_dpp_max<SP_DPP_MIRROR>(k);
-#pragma unroll
-    for (int step = 0; step < 2; ++step) {
-        const unsigned lo = (unsigned)k, hi = (unsigned)(k >> 32);
-        unsigned l0, l1, h0, h1;
-        if (step == 0) {
-            auto a = __builtin_amdgcn_permlane16_swap(lo, lo, false, false); l0 = a[0]; l1 = a[1];
-            auto b = __builtin_amdgcn_permlane16_swap(hi, hi, false, false); h0 = b[0]; h1 = b[1];
-        } else {
-            auto a = __builtin_amdgcn_permlane32_swap(lo, lo, false, false); l0 = a[0]; l1 = a[1];
-            auto b = __builtin_amdgcn_permlane32_swap(hi, hi, false, false); h0 = b[0]; h1 = b[1];
-        }
-        const unsigned long long k0 = ((unsigned long long)h0 << 32) | l0, k1 = ((unsigned long long)h1 << 32) | l1;
-        k = k0 > k1 ? k0 : k1;
-    }
-    // uniform from here on: what is decided from the key is decided on the scalar unit
-    return ((unsigned long long)(unsigned)__builtin_amdgcn_readfirstlane((int)(unsigned)(k >> 32)) << 32) | (unsigned)__builtin_amdgcn_readfirstlane((int)(unsigned)k);
 }
 
 // {value, smallest position} as one key: the larger value wins, then the smaller position.
@@ -139,7 +103,7 @@ __device__ __forceinline__ int sp_walk(const unsigned *P, unsigned char *F, int 
             key = i < cnt && k > key ? k : key;
         }
     }
-    key = sp_wave_max(key);                                                  // (lane 0 holds position 0: the key is never empty)
+    key = wave_max_u64(key);                                                  // (lane 0 holds position 0: the key is never empty)
     const int a1 = rc_clamp(sp_key_pos(key), 0, cnt - 1);
     F[0] = 1; F[a1] = 1;                                                      // every lane stores: see the head of the file
     int kept = a1 > 0 ? 2 : 1;
@@ -163,7 +127,7 @@ __device__ __forceinline__ int sp_walk(const unsigned *P, unsigned char *F, int 
                     key = i < b && k > key ? k : key;
                 }
             }
-            key = sp_wave_max(key);
+            key = wave_max_u64(key);
             const unsigned long long c = key >> 32, len2 = (unsigned long long)(ex * ex + ey * ey);
             if (16ull * c * c > tol * len2) {                                // uniform: the one 64-bit comparison of the segment
                 const int i = rc_clamp(sp_key_pos(key), a + 1, b - 1);

@@ -997,7 +997,7 @@ def simplify(contours: ContourFrames, tolerance, vertex_capacity=None, out=None)
     order, first vertices, regions and hole marks stay.  ``vertex_capacity`` defaults to the input's, which cannot overflow.  ``out``: a
     ``SimplifiedContours`` of the same N and loop capacity to write into (its vertex capacity and workspace hold; nothing is allocated
     then, and the call can be captured in one HIP graph behind ``rle_contours``).  Each loop is simplified on its own: a border shared by
-    two regions is simplified twice, and the two results may differ by up to the tolerance."""
+    two regions is simplified twice, and the two results may differ by up to the tolerance (``simplify_shared`` simplifies it once)."""
     if not isinstance(contours, ContourFrames):
         raise ValueError("simplify: expected the ContourFrames of egress.contours")
     ops.tolerance_q(tolerance, "simplify")
@@ -1061,6 +1061,148 @@ def simplify_numpy(counts, loops, verts, tolerance):
         records[k, 1:3] = (at, int(keep.sum()))
         at += int(keep.sum())
         kept_words.append(words[first:first + count][keep])
+    out = np.concatenate(kept_words).astype(np.uint32) if kept_words else np.zeros(0, dtype=np.uint32)
+    return np.array([L, at], dtype=np.int32), records, out
+
+
+class SharedContours(SimplifiedContours):
+    """``contours`` simplified to ``tolerance`` pixels with shared borders (include/arseg_hip.h, arseg_contours_simplify_shared_fwd), on
+    the device: a ``SimplifiedContours`` whose loops were cut where three regions meet and simplified arc by arc, so that two
+    neighbouring polygons keep the same vertices of their common border and leave no gap or overlap between them.  A loop may hold more
+    vertices than its source (the junctions inside its straight edges are vertices now), and a region thinner than the tolerance may
+    come out degenerate -- two vertices, or all of them on one line: its neighbours close over it."""
+
+    def to_host(self, drop_degenerate=False):
+        """``ContourFrames.to_host``; with ``drop_degenerate`` the loops whose kept vertices span no area are left out (their neighbours
+        cover them)."""
+        frames = super().to_host()
+        if not drop_degenerate:
+            return frames
+        return [[loop for loop in frame if _area2(loop[2]) != 0] for frame in frames]
+
+
+def _area2(pts):
+    """Twice the signed area of a closed polygon int [k,2]."""
+    p = np.asarray(pts, dtype=np.int64)
+    q = np.roll(p, -1, axis=0)
+    return int((p[:, 0] * q[:, 1] - q[:, 0] * p[:, 1]).sum())
+
+
+def simplify_shared(contours: ContourFrames, tolerance, vertex_capacity=None, out=None) -> SharedContours:
+    """``simplify`` for neighbours that must fit: the outlines within ``tolerance`` pixels (a non-negative multiple of 0.25), every border
+    between two regions simplified once, on the GPU: one call of ``ops.contours_simplify_shared`` -> ``SharedContours``.  The run code is
+    ``contours.source.frames``'.  Every loop gets the junctions inside its straight edges as vertices, is cut at every junction (a grid
+    corner where three or four regions, or the frame's corner, meet) and each arc goes through Douglas-Peucker with ties decided by the
+    vertex, not by the direction of travel; a closed arc that would keep fewer than 3 vertices stays whole; loops, their order, regions
+    and hole marks stay.  ``vertex_capacity`` defaults to the input's plus twice the run code's capacity, which cannot overflow.
+    ``out``: a ``SharedContours`` of the same N and loop capacity to write into (its vertex capacity and workspace hold; nothing is
+    allocated then, and the call can be captured in one HIP graph behind ``rle_contours``).  Raises as ``simplify`` does."""
+    if not isinstance(contours, ContourFrames):
+        raise ValueError("simplify_shared: expected the ContourFrames of egress.contours")
+    ops.tolerance_q(tolerance, "simplify_shared")
+    frame = contours.source.frames
+    N, lcap, vcap, dev = contours.N, contours.loop_capacity, contours.vertex_capacity, contours.counts.device
+    if out is None:
+        vertex_capacity = vcap + 2 * frame.capacity if vertex_capacity is None else int(vertex_capacity)
+        if vertex_capacity < 0:
+            raise ValueError(f"simplify_shared: the capacity must not be negative, got {vertex_capacity}")
+        if not contours.counts.is_cuda:
+            raise _lib.ArsegError("simplify_shared runs on the GPU only (got CPU tensors); simplify_shared_numpy is the host form")
+        _need = _lib.load().arseg_contours_simplify_shared_workspace_bytes(N, frame.capacity, lcap, vcap)
+        out = SharedContours(torch.empty((N, 2), dtype=torch.int32, device=dev), torch.empty((N, lcap, 4), dtype=torch.int32, device=dev),
+                             torch.empty((N, vertex_capacity), dtype=torch.int32, device=dev), contours, tolerance,
+                             torch.empty((max(_need // 16, 1), 4), dtype=torch.int32, device=dev))
+    elif not isinstance(out, SharedContours) or out.N != N or out.loop_capacity != lcap or out is contours:
+        raise ValueError(f"simplify_shared: out must be SharedContours of {N} frames with a loop capacity of {lcap}")
+    else:
+        out.contours, out.source, out.tolerance = contours, contours.source, tolerance
+    ops.contours_simplify_shared(frame.row_start, frame.runs, contours.counts, contours.loops if lcap else None,
+                                 contours.verts if vcap else None, frame.H, frame.W, tolerance, out.counts,
+                                 loops_out=out.loops if lcap else None, verts_out=out.verts if out.vertex_capacity else None,
+                                 workspace=out.workspace)
+    return out
+
+
+def simplify_shared_numpy(row_start, runs, H, W, counts, loops, verts, tolerance):
+    """The same pass on a host without a GPU: one frame's run code (as ``RleFrames.to_host`` returns it) and its ``(counts [2], loops
+    [>= L,4], verts [>= V])`` (as ``contours_numpy`` returns them) -> the three arrays of the outlines simplified with shared borders, as
+    arseg_contours_simplify_shared_fwd leaves them with room for everything.  The junctions are a map of the grid corners computed from
+    the decoded plane in one vectorised step; an edge takes its inside junctions from a slice of that map; the recursion of an arc runs
+    on an explicit stack of segments."""
+    tol = ops.tolerance_q(tolerance, "simplify_shared_numpy")
+    H, W = int(H), int(W)
+    if not (0 < H <= 16384 and 0 < W <= 16384):
+        raise ValueError(f"simplify_shared_numpy: H and W positive and at most 16384, got {H}x{W}")
+    L, V = int(counts[0]), int(counts[1])
+    if L < 0 or V < 0 or L > len(loops) or V > len(verts):
+        raise ValueError(f"simplify_shared_numpy: the frame holds {len(loops)} loops and {len(verts)} vertices, its counts say {L} and {V}")
+    padded = np.full((H + 2, W + 2), -1, dtype=np.int16)                     # -1: outside the frame
+    padded[1:-1, 1:-1] = rle_decode_numpy(row_start, runs, H, W)
+    a, b, c, d = padded[:-1, :-1], padded[:-1, 1:], padded[1:, :-1], padded[1:, 1:]          # the four pixels of corner (x, y) at [y, x]
+    junction = ((a != b).astype(np.int8) + (c != d) + (a != c) + (b != d)) >= 3
+    junction[[0, 0, H, H], [0, W, 0, W]] = True
+    words = np.asarray(verts)[:V].astype(np.int64) & 0xFFFFFFFF
+    if V and ((words & 0xFFFF).max() > W or (words >> 16).max() > H):
+        raise ValueError(f"simplify_shared_numpy: a vertex lies outside the {H}x{W} frame")
+    records, kept_words = np.array(np.asarray(loops)[:L], dtype=np.int32).reshape(-1, 4), []
+    at = 0
+    for k, (_, first, count, _) in enumerate(records.tolist()):
+        if first < 0 or count < 0 or first + count > V:
+            raise ValueError(f"simplify_shared_numpy: loop {k} lies outside the frame's {V} vertices")
+        w = words[first:first + count]
+        pieces = []
+        for w0, w1 in zip(w.tolist(), np.roll(w, -1).tolist()):             # the expanded loop: each corner and the junctions inside its edge
+            x0, y0, x1, y1 = w0 & 0xFFFF, w0 >> 16, w1 & 0xFFFF, w1 >> 16
+            pieces.append(np.array([w0], dtype=np.int64))
+            if y0 == y1:
+                xs = np.flatnonzero(junction[y0, min(x0, x1) + 1:max(x0, x1)]) + min(x0, x1) + 1
+                pieces.append((y0 << 16) | (xs if x1 > x0 else xs[::-1]))
+            elif x0 == x1:
+                ys = np.flatnonzero(junction[min(y0, y1) + 1:max(y0, y1), x0]) + min(y0, y1) + 1
+                pieces.append(((ys if y1 > y0 else ys[::-1]) << 16) | x0)
+            else:
+                raise ValueError(f"simplify_shared_numpy: loop {k} has an edge along neither axis")
+        e = np.concatenate(pieces) if pieces else np.zeros(0, dtype=np.int64)
+        n = len(e)
+        keep = junction[e >> 16, e & 0xFFFF].copy() if n else np.zeros(0, dtype=bool)
+        cuts = np.flatnonzero(keep)
+        rot = int(cuts[0]) if len(cuts) else 0
+        e2 = np.concatenate([e[rot:], e[:rot + 1]]) if n else e                 # from the first junction passage, closed
+        x, y = e2 & 0xFFFF, e2 >> 16
+        ends = np.append(cuts - rot, n) if len(cuts) else np.array([0, n])
+        stay = np.zeros(n + 1, dtype=bool)
+
+        def chain(lo, hi):
+            todo = [(lo, hi)]
+            while todo:
+                p, q = todo.pop()
+                if q - p < 2:
+                    continue
+                ex, ey = int(x[q] - x[p]), int(y[q] - y[p])
+                c = np.abs(ex * (y[p + 1:q] - y[p]) - ey * (x[p + 1:q] - x[p]))
+                tie = np.flatnonzero(c == c.max())
+                i = p + 1 + int(tie[np.argmin(e2[p + 1:q][tie])])           # the smallest vertex word of a tie
+                if 16 * int(c.max()) ** 2 > tol * (ex * ex + ey * ey):
+                    stay[i] = True
+                    todo += [(p, i), (i, q)]
+
+        for lo, hi in zip(ends[:-1].tolist(), ends[1:].tolist()):
+            stay[lo] = True
+            if e2[lo] != e2[hi]:
+                chain(lo, hi)
+                continue
+            far = (x[lo:hi] - x[lo]) ** 2 + (y[lo:hi] - y[lo]) ** 2
+            tie = np.flatnonzero(far == far.max())
+            a1 = lo + int(tie[np.argmin(e2[lo:hi][tie])])
+            stay[a1] = True
+            chain(lo, a1)
+            chain(a1, hi)
+            if stay[lo:hi].sum() < 3:
+                stay[lo:hi] = True
+        keep = np.roll(stay[:n], rot)
+        records[k, 1:3] = (at, int(keep.sum()))
+        at += int(keep.sum())
+        kept_words.append(e[keep])
     out = np.concatenate(kept_words).astype(np.uint32) if kept_words else np.zeros(0, dtype=np.uint32)
     return np.array([L, at], dtype=np.int32), records, out
 

@@ -519,15 +519,18 @@ def alter_res_batch_contours(lr_net, ref_ps, imgs, mv_qs, capacity, region_capac
 
 
 def alter_res_batch_polygons(lr_net, ref_ps, imgs, mv_qs, capacity, region_capacity, tolerance, scale=0.5, lut=None, labels_out=True,
-                             connectivity=8, min_area=None, protect=None, pair_capacity=None, loop_capacity=None, vertex_capacity=None):
+                             connectivity=8, min_area=None, protect=None, pair_capacity=None, loop_capacity=None, vertex_capacity=None,
+                             shared_borders=False):
     """``alter_res_batch_contours`` + ``egress.simplify``: the outlines within ``tolerance`` pixels (a non-negative multiple of 0.25) ->
     (``egress.SimplifiedContours``, whose ``.contours`` are the exact outlines and ``.source`` the regions; labels uint8 [B,H,W]).  With
-    ``min_area`` the specks are absorbed first.  Nothing comes to the host in between; ``to_host()`` brings the polygons over."""
+    ``min_area`` the specks are absorbed first.  With ``shared_borders`` the last step is ``egress.simplify_shared`` (->
+    ``egress.SharedContours``): a border between two regions is simplified once, so neighbouring polygons leave no gap between them.
+    Nothing comes to the host in between; ``to_host()`` brings the polygons over."""
     from . import egress
     outlines, labels = alter_res_batch_contours(lr_net, ref_ps, imgs, mv_qs, capacity, region_capacity, scale=scale, lut=lut, labels_out=labels_out,
                                                 connectivity=connectivity, min_area=min_area, protect=protect, pair_capacity=pair_capacity,
                                                 loop_capacity=loop_capacity, vertex_capacity=vertex_capacity)
-    return egress.simplify(outlines, tolerance), labels
+    return (egress.simplify_shared if shared_borders else egress.simplify)(outlines, tolerance), labels
 
 
 def alter_res_batch_links(lr_net, ref_ps, imgs, mv_qs, key_regions, capacity, region_capacity, scale=0.5, lut=None, labels_out=True,

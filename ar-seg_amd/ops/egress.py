@@ -5,7 +5,8 @@ statistics, one ABI call (arseg_segment_confidence_fwd; csrc/confidence.hip); an
 csrc/regions.hip); the regions of two frames -> their links along the motion, one ABI call (arseg_region_links_fwd; csrc/links.hip); a row-run
 code and its regions -> the code with the small regions absorbed into their neighbours, one ABI call (arseg_rle_absorb_fwd; csrc/absorb.hip);
 the regions' outlines as polygon loops (arseg_rle_contours_fwd; csrc/contours.hip) and those simplified to a pixel tolerance
-(arseg_contours_simplify_fwd; csrc/simplify.hip), one ABI call each."""
+(arseg_contours_simplify_fwd; csrc/simplify.hip) or, with the borders between neighbours simplified once,
+(arseg_contours_simplify_shared_fwd; csrc/simplify_shared.hip), one ABI call each."""
 from __future__ import annotations
 
 import ctypes
@@ -496,4 +497,46 @@ def contours_simplify(counts: torch.Tensor, loops: Optional[torch.Tensor], verts
            tol2_q, _ptr(counts_out), _ptr(loops_out if lcap else None), _ptr(verts_out if vcap_out else None), vcap_out, _ptr(workspace),
            ws_bytes, _stream(),
            nbytes=16 * N)          # (+ about 16 bytes per loop and some 30 per vertex, known on the device only)
+    return counts_out, loops_out, verts_out
+
+
+def contours_simplify_shared(row_start: torch.Tensor, runs: torch.Tensor, counts: torch.Tensor, loops: Optional[torch.Tensor],
+                             verts: Optional[torch.Tensor], H: int, W: int, tolerance, counts_out: torch.Tensor,
+                             loops_out: Optional[torch.Tensor] = None, verts_out: Optional[torch.Tensor] = None,
+                             workspace: Optional[torch.Tensor] = None):
+    """Region outlines simplified to ``tolerance`` pixels with shared borders (include/arseg_hip.h, arseg_contours_simplify_shared_fwd):
+    ``row_start`` int32 [N,H+1] and ``runs`` 32-bit [N,cap] (the run code the outlines were traced from), ``counts`` int32 [N,2], ``loops``
+    int32 [N,lcap,4] and ``verts`` 32-bit [N,vcap] as ``rle_contours`` wrote them -> ``counts_out`` int32 [N,2] (the loops and the kept
+    vertices of each frame, exact whatever the capacity; -1, -1: the source frame was refused or overflowed, or its run code overflowed,
+    nothing else of the frame is touched), ``loops_out`` int32 [N,lcap,4] (``region, first', count', hole``; required with loops) and,
+    when given, ``verts_out`` 32-bit [N,vcap_out], exact below the counts and untouched from there on; ``vcap_out = vcap + 2 * cap``
+    cannot overflow.  ``tolerance``: a non-negative multiple of 0.25.  The loops are cut at every junction of three or more regions (and
+    at the frame's corners) and every arc is simplified by a rule that is the same in both directions of travel, so neighbours keep the
+    same vertices of their common border.  ``workspace``: a device tensor of at least
+    ``arseg_contours_simplify_shared_workspace_bytes(N, cap, lcap, vcap)`` bytes (default: the stream's shared workspace).  With every
+    buffer given nothing is allocated and nothing synchronises: capturable in a HIP graph.  Returns (counts_out, loops_out, verts_out)."""
+    what = "contours_simplify_shared"
+    H, W = _frame_dims(what, H, W, 16384)
+    tol2_q = tolerance_q(tolerance, what)
+    N = _dense(what, "row_start", row_start, torch.int32, (None, H + 1))
+    dev = row_start.device
+    cap = _dense(what, "runs", runs, _RUN_DTYPES, (N, None), dev)
+    if cap == 0 or cap > 1 << 29:
+        raise ValueError(f"{what}: between 1 and 2^29 runs per frame, got a capacity of {cap}")
+    _dense(what, "counts", counts, torch.int32, (N, 2), dev)
+    _dense(what, "counts_out", counts_out, torch.int32, (N, 2), dev)
+    lcap = 0
+    if loops is not None:
+        lcap = _dense(what, "loops", loops, torch.int32, (N, None, 4), dev)
+        if loops_out is None:
+            raise _lib.ArsegError(f"{what}: loops_out is required with loops")
+        _dense(what, "loops_out", loops_out, torch.int32, (N, lcap, 4), dev)
+    vcap = 0 if verts is None else _dense(what, "verts", verts, _RUN_DTYPES, (N, None), dev)
+    vcap_out = 0 if verts_out is None else _dense(what, "verts_out", verts_out, _RUN_DTYPES, (N, None), dev)
+    lib = _lib.load()
+    workspace, ws_bytes = _own_workspace(what, workspace, lib.arseg_contours_simplify_shared_workspace_bytes(N, cap, lcap, vcap), dev, 4)
+    launch(what, lib.arseg_contours_simplify_shared_fwd, _ptr(row_start), _ptr(runs), cap, _ptr(counts), _ptr(loops if lcap else None), lcap,
+           _ptr(verts if vcap else None), vcap, N, H, W, tol2_q, _ptr(counts_out), _ptr(loops_out if lcap else None),
+           _ptr(verts_out if vcap_out else None), vcap_out, _ptr(workspace), ws_bytes, _stream(),
+           nbytes=16 * N)          # (+ about 36 bytes per loop and some 60 per vertex, known on the device only)
     return counts_out, loops_out, verts_out

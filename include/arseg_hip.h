@@ -1106,12 +1106,78 @@ int arseg_rle_contours_fwd(const int32_t *row_start, const uint32_t *runs, const
  *   capacity; H > 16384 or W > 16384; tol2_q < 0 or > 1 << 30; verts_out == verts, loops_out == loops or counts_out == counts; a null
  *   workspace.
  * Not covered: a border shared by two regions is simplified once per loop, so the two results may differ by up to the tolerance
- *   (splitting the loops where three regions meet and simplifying each arc once is a later item); smoothing; area-preserving rules.
+ *   (arseg_contours_simplify_shared_fwd, below, cuts the loops where three regions meet and simplifies each arc once); smoothing;
+ *   area-preserving rules.
  * ------------------------------------------------------------------------------------------- */
 size_t arseg_contours_simplify_workspace_bytes(int N, int64_t lcap, int64_t vcap);
 int arseg_contours_simplify_fwd(const int32_t *counts, const int32_t *loops, int64_t lcap, const uint32_t *verts, int64_t vcap, int N, int H,
                                 int W, int64_t tol2_q, int32_t *counts_out, int32_t *loops_out, uint32_t *verts_out, int64_t vcap_out,
                                 void *workspace, size_t workspace_bytes, arseg_stream_t stream);
+
+/* ---------------------------------------------------------------------------------------------
+ * Region outlines simplified with shared borders (csrc/simplify_shared.hip): arseg_contours_simplify_fwd's output for consumers that lay
+ * neighbouring polygons side by side -- a vector overlay, a GIS layer, an annotation tool --: a border between two regions is cut out of
+ * both loops at the same points and simplified by a rule that does not depend on the direction of travel, so the two neighbours keep
+ * the same vertices of it and no sliver or overlap opens between them.  On the device, behind arseg_rle_contours_fwd, without a host
+ * synchronisation: capturable in the same HIP graph.  Integers only: every result is exact.  (A backward-compatible addition:
+ * ARSEG_ABI_VERSION stays.)
+ * Input: row_start int32 [N][H+1] and runs uint32 [N][cap] (the run code the outlines were traced from, as arseg_labels_rle_fwd or
+ *   arseg_rle_absorb_fwd leaves it); counts int32 [N][2], loops int32 [N][lcap][4] and verts uint32 [N][vcap] exactly as
+ *   arseg_rle_contours_fwd leaves them, with their capacities; H and W of the frames; tol2_q = 16 x the squared tolerance in pixels.
+ * Junctions.  Four unit grid edges meet at a grid corner (x, y), each between two of its four pixels.  A grid edge is a border edge if
+ *   its two pixels differ in value, or if exactly one of them lies outside the frame (side-adjacent pixels of one value are one region
+ *   at either connectivity, so the values decide).  The degree of a corner is its number of border edges: 0, 2, 3 or 4.  A corner is a
+ *   junction if its degree is at least 3, or if it is one of the four corners of the frame (else the corners of the picture would be
+ *   cut off).  A saddle has degree 4: a junction at either connectivity.
+ * Expanded loop.  The source loop (corners only) plus, on each of its straight edges, every junction strictly inside that edge, in
+ *   travel order: the T-junctions whose straight side is this loop -- the two regions on the other side have a corner there.  Every
+ *   vertex of the expanded loop is a junction passage or an ordinary corner; a loop may pass one junction twice (a saddle), and each
+ *   passage counts.
+ * Arcs.  The expanded loop is cut at every junction passage; an arc runs from one passage to the next, cyclically.  A loop without a
+ *   junction is one closed arc from the source loop's first vertex; a loop with one passage is one closed arc from that passage round to
+ *   itself; two different passages may be the same point (a one-pixel appendage on a saddle), and the arc between them is closed too.
+ *   Inside an arc every vertex has degree 2: an arc never visits a point twice and has the same two regions on its two sides all along.
+ * Rule per arc, on integer coordinates; the arc's points are P[0 .. m]:
+ *   open (P[0] != P[m]): both ends are kept; Douglas-Peucker on (0, m) as in arseg_contours_simplify_fwd's rule 2 -- c_i = |(P[b] - P[a])
+ *     x (P[i] - P[a])|, the largest c_i picked, kept with both halves treated the same way iff 16 c_i^2 > tol2_q |P[b] - P[a]|^2 -- with
+ *     one change: among ties the SMALLEST VERTEX WORD is picked, not the smallest position.  That makes the rule the same in both
+ *     directions of travel.
+ *   closed (P[0] == P[m]): P[0] is kept; a1 = the position in [0, m) with the largest squared distance from P[0], the smallest vertex
+ *     word of a tie, is kept; Douglas-Peucker on (0, a1) and (a1, m).  If fewer than 3 vertices would be kept all m are kept (the arc's
+ *     other side decides the same: a one-pixel island and its hole both stay squares).
+ * Outputs, all integers, all OVERWRITTEN, in the format and order of arseg_contours_simplify_fwd:
+ *   counts_out  int32 [N][2] = {L, V'}: exact whatever vcap_out is; or {-1, -1}: the frame is refused -- its source counts are negative,
+ *               L > lcap, V > vcap or row_start[n][H] > cap -- and nothing else of it is touched.  Decided on the device.
+ *   loops_out   int32 [N][lcap][4] = {region, first', count', hole}: first' is the prefix sum of count', exact also when V' > vcap_out;
+ *               region and hole are copied, the loops keep their order.  The rows below L are exact, the rows from there on untouched.
+ *   verts_out   uint32 [N][vcap_out]: a loop's kept vertices in source order, from the first kept position at or after the source
+ *               loop's first vertex.  The words below min(V', vcap_out) are exact, the words from there on untouched.  verts_out ==
+ *               NULL with vcap_out == 0: the sizing pass.
+ *   tol2_q = 0 gives the expanded loops: the source corners plus the inserted junctions.
+ *   V' can exceed V: at most one vertex is inserted per end of an interior vertical unit border edge whose junction has a straight
+ *   side, and there are row_start[n][H] - H such edges, so V' <= V + 2 x row_start[n][H] and vcap_out = vcap + 2 x cap never overflows.
+ *   Degenerate loops are emitted as they are: a loop made of open arcs that all collapse onto their chords comes out with count' = 2
+ *   or with collinear vertices -- its region is thinner than the tolerance, its neighbours close over it without a gap, and restoring it
+ *   would break the match with them.  count' >= 2 always.
+ * workspace: the caller's, 4-byte aligned, >= arseg_contours_simplify_shared_workspace_bytes(N, cap, lcap, vcap) bytes (else
+ *   ARSEG_EWORKSPACE): per frame 12 bytes per loop slot, 4 per vertex slot and 5 per slot of the expanded loops (vcap + 2 cap of
+ *   them); capacities whose size does not fit size_t give SIZE_MAX and ARSEG_EWORKSPACE.  Its contents are scratch.
+ * 7 launches (mark, place, scan, expand, keep, scan, emit -- no emit without verts_out), sized on the host from the capacities; no workgroup
+ *   waits for another.  Enqueue only: no allocation, no synchronisation.  The buffers must not overlap.
+ * Malformed input (a run code or loop records that do not belong together) gives meaningless output, but nothing outside the caller's
+ *   buffers is read or written: rows, run indices, loop records and expanded slots are clamped, and every loop is bounded.
+ * ARSEG_EINVAL, before any launch: a null row_start, runs, counts or counts_out; loops or loops_out NULL with lcap > 0, verts NULL with
+ *   vcap > 0, verts_out NULL with vcap_out > 0; one of the arrays or the workspace not 4-byte aligned; non-positive N, H, W or cap; a
+ *   negative lcap, vcap or vcap_out; H > 16384 or W > 16384; tol2_q < 0 or > 1 << 30; cap > 1 << 29; an output that is one of the
+ *   inputs; a null workspace.
+ * Not covered: the arcs themselves as output (shared arcs with per-loop arc lists); self-intersection repair; smoothing and
+ *   area-preserving rules; more than one wave per long loop.
+ * ------------------------------------------------------------------------------------------- */
+size_t arseg_contours_simplify_shared_workspace_bytes(int N, int64_t cap, int64_t lcap, int64_t vcap);
+int arseg_contours_simplify_shared_fwd(const int32_t *row_start, const uint32_t *runs, int64_t cap, const int32_t *counts,
+                                       const int32_t *loops, int64_t lcap, const uint32_t *verts, int64_t vcap, int N, int H, int W,
+                                       int64_t tol2_q, int32_t *counts_out, int32_t *loops_out, uint32_t *verts_out, int64_t vcap_out,
+                                       void *workspace, size_t workspace_bytes, arseg_stream_t stream);
 
 /* ---------------------------------------------------------------------------------------------
  * Measurement aids (no reference counterpart; BASELINE.md section 3: roofline fractions are reported against the datasheet peaks AND
