@@ -30,6 +30,7 @@ MVR_BI_LIST0, MVR_BI_NEAR, MVR_BI_MEAN = 0, 1, 2
 CONF_TOP1, CONF_MARGIN = 0, 1
 CONF_NSTATS = 2 + 32      # ARSEG_CONF_NSTATS: sum of codes, low count, 32 class areas
 TC_NSTATS = 3 + 3 * 32    # ARSEG_TC_NSTATS: compared, outside, void, then 32 each of cur_k, ref_k, inter_k
+FILL_NSTATS = 3 + 3 * 256  # ARSEG_FILL_NSTATS: gaps, excess, changed, then 256 each of ref_area, fill_area, both
 
 
 class ConvDesc(Structure):
@@ -167,6 +168,9 @@ PROTOTYPES = {
     "arseg_contours_simplify_shared_workspace_bytes": (c_size_t, [c_int, c_int64, c_int64, c_int64]),
     "arseg_contours_simplify_shared_fwd": (c_int, [_P, _P, c_int64, _P, _P, c_int64, _P, c_int64, c_int, c_int, c_int, c_int64, _P, _P, _P, c_int64, _P,
                                            c_size_t, _STREAM]),
+    "arseg_contours_fill_workspace_bytes": (c_size_t, [c_int, c_int, c_int, c_int64, c_int64, c_int64]),
+    "arseg_contours_fill_fwd": (c_int, [_P, _P, c_int64, _P, c_int64, _P, _P, c_int64, c_int, c_int, c_int, c_int, _P, c_int64, c_int64, _P, c_int64,
+                                c_int64, _P, _P, c_int64, _P, c_size_t, _STREAM]),
 }
 
 # the SURVEY.md section 8(b) names: aliases with the prototypes of their targets

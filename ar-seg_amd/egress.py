@@ -26,6 +26,11 @@
   shares the longest border with, on the run code and on the GPU (``ops.rle_absorb``, csrc/absorb.hip) -> a new ``RleFrames`` for the bus,
   the overlay and the next ``regions`` / ``links``; ``absorb_numpy`` is the same pass on a host.
 
+* ``fill``: the polygons back to a mask -- every region's loops (``contours``, ``simplify`` or ``simplify_shared``) filled on the GPU by the
+  even-odd rule on the pixel centres, the larger region number on top (``ops.contours_fill``, csrc/fill.hip) -> ``FilledFrames``: the plane
+  a consumer of the polygons draws, and per frame what the simplification did to the mask (``fidelity()``: uncovered and doubly covered
+  pixels, changed pixels, IoU per value); ``fill_numpy`` is the same fill on a host.
+
 ``labels8`` and ``overlay`` are one launch of ``ops.segment_egress`` (csrc/egress.hip): the bilinear resize and the argmax are the evaluator tail's own, so the
 labels equal ``ops.argmax_confusion``'s ``pred`` bit for bit, and neither int32 labels nor a float frame are ever written.  The painting is
 integer arithmetic, written out in include/arseg_hip.h (arseg_segment_egress_fwd).  Not covered: 10-bit, 4:2:2 or 4:4:4 destinations, text,
@@ -1205,6 +1210,146 @@ def simplify_shared_numpy(row_start, runs, H, W, counts, loops, verts, tolerance
         kept_words.append(e[keep])
     out = np.concatenate(kept_words).astype(np.uint32) if kept_words else np.zeros(0, dtype=np.uint32)
     return np.array([L, at], dtype=np.int32), records, out
+
+
+class FilledFrames(object):
+    """``contours`` (any ``ContourFrames``) filled back into label planes (include/arseg_hip.h, arseg_contours_fill_fwd), on the device:
+    ``labels`` uint8 [N,H,W] (every region's loops filled by the even-odd rule on the pixel centres, the larger region number on top, the
+    background value where no region covers), ``counts`` int32 [N] (the edge-row crossings each frame needs; -1: the frame could not be
+    processed) and ``stats`` int64 [N,3 + 3 * 256] (``gaps, excess, changed, ref_area[256], fill_area[256], both[256]`` against the
+    reference plane the call was given).  ``workspace``: the scratch the pass uses, kept so that a repeated call allocates nothing."""
+
+    def __init__(self, labels, counts, stats, contours, event_capacity, background=255, workspace=None):
+        self.labels, self.counts, self.stats, self.contours, self.workspace = labels, counts, stats, contours, workspace
+        self.event_capacity, self.background = int(event_capacity), int(background)
+        if not isinstance(contours, ContourFrames):
+            raise ValueError("FilledFrames: contours must be the ContourFrames that were filled")
+        N = contours.N
+        if labels.dim() != 3 or labels.shape[0] != N or tuple(counts.shape) != (N,) or tuple(stats.shape) != (N, _lib.FILL_NSTATS):
+            raise ValueError(f"FilledFrames: labels [{N},H,W], counts [{N}] and stats [{N},{_lib.FILL_NSTATS}], got {tuple(labels.shape)}, "
+                             f"{tuple(counts.shape)} and {tuple(stats.shape)}")
+
+    @property
+    def N(self):
+        return self.contours.N
+
+    def needed(self) -> torch.Tensor:
+        """The crossings each frame needs (a device view, int32 [N]): exact whatever the capacity; a value above ``event_capacity`` is an
+        overflow (the frame's plane and stats were not written), -1 a frame that could not be processed."""
+        return self.counts
+
+    def rle(self, capacity, out=None) -> RleFrames:
+        """The filled planes as run codes (``rle_of_planes``): the mask re-enters the chain -- ``regions``, ``links``, ``absorb``."""
+        frames = rle_of_planes(self.labels, capacity, out=out)
+        frames.labels = self.labels
+        return frames
+
+    def fidelity(self):
+        """What the polygons did to the mask, per frame a dict: ``gaps`` (pixels no polygon covers), ``excess`` (coverings beyond the first,
+        summed over the pixels), ``changed`` (pixels whose value differs from the reference; gaps count), ``iou`` (value -> both / (ref_area
+        + fill_area - both) for the values present on either side) and ``miou`` (their mean; None without any), in one copy of ``counts``
+        and ``stats``.  Without a reference ``changed`` is 0 and the areas are those of the fill alone.  Raises ``ArsegError`` naming a
+        frame that was refused or needs more crossings than the capacity."""
+        both = torch.cat([self.counts.to(torch.int64)[:, None], self.stats], dim=1).cpu().numpy()
+        out = []
+        for n, row in enumerate(both):
+            if row[0] < 0:
+                raise _lib.ArsegError(f"FilledFrames.fidelity: frame {n} could not be processed: its outlines were refused or overflowed, or "
+                                      f"its regions are missing")
+            if row[0] > self.event_capacity:
+                raise _lib.ArsegError(f"FilledFrames.fidelity: frame {n} needs {int(row[0])} crossings, the capacity is {self.event_capacity}")
+            ref_area, fill_area, inter = row[4:260], row[260:516], row[516:772]
+            union = ref_area + fill_area - inter
+            iou = {int(v): float(inter[v]) / float(union[v]) for v in np.flatnonzero(union)}
+            out.append({"gaps": int(row[1]), "excess": int(row[2]), "changed": int(row[3]), "iou": iou,
+                        "miou": float(np.mean(list(iou.values()))) if iou else None})
+        return out
+
+
+def fill(contours: ContourFrames, background=255, ref=None, event_capacity=None, out=None) -> FilledFrames:
+    """The polygons back to masks, on the GPU: one call of ``ops.contours_fill`` -> ``FilledFrames``.  ``contours``: any
+    ``ContourFrames`` -- exact outlines, ``SimplifiedContours`` or ``SharedContours``; a region's value comes from
+    ``contours.source.records``.  A pixel belongs to a region when its centre lies inside the region's loops by the even-odd rule (a centre
+    on an edge goes to the polygon on the right of the edge); where several regions cover it the largest region number wins, where none
+    does it gets ``background``.  ``ref``: the mask to compare with -- None, a uint8 [N,H,W] device plane, or True: the plane the run code
+    was taken from (``contours.source.frames.labels``) when it is kept, else that run code decoded.  ``event_capacity`` defaults to twice
+    the run code's capacity, which cannot overflow for outlines that come from it.  ``out``: a ``FilledFrames`` of the same N, H, W to
+    write into (its capacity and workspace hold; nothing is allocated then, and the call can be captured in one HIP graph behind
+    ``rle_contours`` and the simplify passes)."""
+    if not isinstance(contours, ContourFrames):
+        raise ValueError("fill: expected the ContourFrames of egress.contours, egress.simplify or egress.simplify_shared")
+    background = int(background)
+    if not 0 <= background <= 255:
+        raise ValueError(f"fill: background is a byte, got {background}")
+    found = contours.source
+    frame = found.frames
+    N, H, W, lcap, vcap, dev = contours.N, frame.H, frame.W, contours.loop_capacity, contours.vertex_capacity, contours.counts.device
+    if out is None:
+        event_capacity = 2 * frame.capacity if event_capacity is None else int(event_capacity)
+        if event_capacity < 0:
+            raise ValueError(f"fill: the capacity must not be negative, got {event_capacity}")
+        if not contours.counts.is_cuda:
+            raise _lib.ArsegError("fill runs on the GPU only (got CPU tensors); fill_numpy is the host form")
+        _need = _lib.load().arseg_contours_fill_workspace_bytes(N, H, W, lcap, vcap, event_capacity)
+        out = FilledFrames(torch.empty((N, H, W), dtype=torch.uint8, device=dev), torch.empty((N,), dtype=torch.int32, device=dev),
+                           torch.zeros((N, _lib.FILL_NSTATS), dtype=torch.int64, device=dev), contours, event_capacity, background,
+                           torch.empty((max(_need // 16, 1), 2), dtype=torch.int64, device=dev))
+    elif not isinstance(out, FilledFrames) or out.N != N or tuple(out.labels.shape) != (N, H, W):
+        raise ValueError(f"fill: out must be FilledFrames of {N} frames of {H}x{W}")
+    else:
+        out.contours, out.background = contours, background
+    if ref is True:
+        ref = frame.labels if frame.labels is not None else frame.decode()
+    ops.contours_fill(contours.counts, contours.loops if lcap else None, contours.verts if vcap else None, found.n_regions,
+                      found.records if found.capacity else None, H, W, out.labels, out.counts, background=background, ref_labels=ref,
+                      stats=out.stats, event_capacity=out.event_capacity, workspace=out.workspace)
+    return out
+
+
+def fill_numpy(counts, loops, verts, values, H, W, background=255):
+    """The same fill on a host without a GPU: one frame's ``(counts [2], loops [>= L,4], verts [>= V])`` (as ``contours_numpy``,
+    ``simplify_numpy`` or ``simplify_shared_numpy`` return them) and ``values`` (the value of every region, e.g. ``regions_numpy``'s
+    ``value`` field) -> ``(plane uint8 [H,W], gaps, excess)``.  All edges at once: the rows an edge crosses are laid out by ``np.repeat``,
+    the crossing columns come from the contract's formula, one sort by (region, row, column) pairs them into spans, and the spans are
+    painted in rising region number."""
+    H, W, background = int(H), int(W), int(background)
+    if not (0 < H <= 16384 and 0 < W <= 16384) or not 0 <= background <= 255:
+        raise ValueError(f"fill_numpy: H and W positive and at most 16384 and background a byte, got {H}x{W} and {background}")
+    L, V = int(counts[0]), int(counts[1])
+    if L < 0 or V < 0 or L > len(loops) or V > len(verts):
+        raise ValueError(f"fill_numpy: the frame holds {len(loops)} loops and {len(verts)} vertices, its counts say {L} and {V}")
+    values = np.asarray(values).astype(np.int64).reshape(-1)
+    rec = np.asarray(loops)[:L].astype(np.int64).reshape(-1, 4)
+    region, first, count = rec[:, 0], rec[:, 1], rec[:, 2]
+    if L and (first.min() < 0 or count.min() < 0 or (first + count).max() > V):
+        raise ValueError(f"fill_numpy: a loop lies outside the frame's {V} vertices")
+    if L and (region.min() < 0 or region.max() >= len(values)):
+        raise ValueError(f"fill_numpy: a loop names a region outside the {len(values)} values")
+    words = np.asarray(verts)[:V].astype(np.int64) & 0xFFFFFFFF
+    if V and ((words & 0xFFFF).max() > W or (words >> 16).max() > H):
+        raise ValueError(f"fill_numpy: a vertex lies outside the {H}x{W} frame")
+    plane = np.full((H, W), background, dtype=np.uint8)
+    # every vertex with its successor along its loop
+    start = np.repeat(first, count)
+    at = start + np.arange(count.sum()) - np.repeat(np.cumsum(count) - count, count)
+    nxt = np.where(at + 1 < start + np.repeat(count, count), at + 1, start)
+    xa, ya, xb, yb, r = words[at] & 0xFFFF, words[at] >> 16, words[nxt] & 0xFFFF, words[nxt] >> 16, np.repeat(region, count)
+    swap = ya > yb
+    xa, xb, ya, yb = np.where(swap, xb, xa), np.where(swap, xa, xb), np.minimum(ya, yb), np.maximum(ya, yb)
+    dy = yb - ya                                                   # 0: a horizontal edge crosses no row
+    e = np.repeat(np.arange(len(dy)), dy)
+    y = ya[e] + np.arange(dy.sum()) - np.repeat(np.cumsum(dy) - dy, dy)
+    num = 2 * xa[e] * dy[e] + (2 * y + 1 - 2 * ya[e]) * (xb[e] - xa[e]) - dy[e]
+    xs = np.clip(-((-num) // (2 * dy[e])), 0, W)                   # the ceiling, for either sign
+    order = np.lexsort((xs, y, r[e]))
+    c0, c1, row, owner = xs[order][0::2], xs[order][1::2], y[order][0::2], r[e][order][0::2]
+    if len(xs) % 2 or (row != y[order][1::2]).any() or (owner != r[e][order][1::2]).any():
+        raise ValueError("fill_numpy: a region crosses a row an odd number of times: its loops are not closed")
+    length = c1 - c0
+    where = np.repeat(row * W + c0, length) + np.arange(length.sum()) - np.repeat(np.cumsum(length) - length, length)
+    plane.reshape(-1)[where] = np.repeat(values[owner] & 0xFF, length).astype(np.uint8)          # in rising region number: the last one stays
+    covered = np.bincount(where, minlength=H * W)
+    return plane, int((covered == 0).sum()), int((covered - np.minimum(covered, 1)).sum())
 
 
 class TrackIds(object):

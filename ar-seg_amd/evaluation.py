@@ -533,6 +533,22 @@ def alter_res_batch_polygons(lr_net, ref_ps, imgs, mv_qs, capacity, region_capac
     return (egress.simplify_shared if shared_borders else egress.simplify)(outlines, tolerance), labels
 
 
+def alter_res_batch_polygon_fidelity(lr_net, ref_ps, imgs, mv_qs, capacity, region_capacity, tolerance, scale=0.5, lut=None, connectivity=8,
+                                     min_area=None, protect=None, pair_capacity=None, loop_capacity=None, vertex_capacity=None,
+                                     shared_borders=False, background=255):
+    """``alter_res_batch_polygons`` + ``egress.fill``: the polygons filled back into masks and compared with the masks they were traced
+    from -> (the polygons, ``egress.FilledFrames``, labels uint8 [B,H,W]).  ``FilledFrames.fidelity()`` tells per frame what
+    ``tolerance`` did: uncovered and doubly covered pixels (both 0 with ``shared_borders``), changed pixels and the IoU per value.  The
+    reference is ``labels``, the mask before any absorption: with ``min_area`` the absorbed specks count as changed.  Nothing comes to the
+    host in between."""
+    from . import egress
+    polygons, labels = alter_res_batch_polygons(lr_net, ref_ps, imgs, mv_qs, capacity, region_capacity, tolerance, scale=scale, lut=lut,
+                                                labels_out=True, connectivity=connectivity, min_area=min_area, protect=protect,
+                                                pair_capacity=pair_capacity, loop_capacity=loop_capacity, vertex_capacity=vertex_capacity,
+                                                shared_borders=shared_borders)
+    return polygons, egress.fill(polygons, background=background, ref=labels), labels
+
+
 def alter_res_batch_links(lr_net, ref_ps, imgs, mv_qs, key_regions, capacity, region_capacity, scale=0.5, lut=None, labels_out=True,
                           connectivity=8, pair_capacity=None):
     """``alter_res_batch_regions``'s sibling for object association: the same phases, run code and regions, then ``egress.links`` of every

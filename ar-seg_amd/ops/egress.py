@@ -6,7 +6,8 @@ csrc/regions.hip); the regions of two frames -> their links along the motion, on
 code and its regions -> the code with the small regions absorbed into their neighbours, one ABI call (arseg_rle_absorb_fwd; csrc/absorb.hip);
 the regions' outlines as polygon loops (arseg_rle_contours_fwd; csrc/contours.hip) and those simplified to a pixel tolerance
 (arseg_contours_simplify_fwd; csrc/simplify.hip) or, with the borders between neighbours simplified once,
-(arseg_contours_simplify_shared_fwd; csrc/simplify_shared.hip), one ABI call each."""
+(arseg_contours_simplify_shared_fwd; csrc/simplify_shared.hip), one ABI call each; the polygons filled back into a label plane with the
+fidelity counters (arseg_contours_fill_fwd; csrc/fill.hip), one ABI call."""
 from __future__ import annotations
 
 import ctypes
@@ -540,3 +541,53 @@ def contours_simplify_shared(row_start: torch.Tensor, runs: torch.Tensor, counts
            _ptr(verts_out if vcap_out else None), vcap_out, _ptr(workspace), ws_bytes, _stream(),
            nbytes=16 * N)          # (+ about 36 bytes per loop and some 60 per vertex, known on the device only)
     return counts_out, loops_out, verts_out
+
+
+def contours_fill(counts: torch.Tensor, loops: Optional[torch.Tensor], verts: Optional[torch.Tensor], n_regions: torch.Tensor,
+                  records: Optional[torch.Tensor], H: int, W: int, labels_out: Optional[torch.Tensor], counts_out: torch.Tensor,
+                  background: int = 255, ref_labels: Optional[torch.Tensor] = None, stats: Optional[torch.Tensor] = None,
+                  event_capacity: Optional[int] = None, workspace: Optional[torch.Tensor] = None):
+    """Region polygons rasterised back to a label plane (include/arseg_hip.h, arseg_contours_fill_fwd): ``counts`` int32 [N,2], ``loops``
+    int32 [N,lcap,4] and ``verts`` 32-bit [N,vcap] as ``rle_contours``, ``contours_simplify`` or ``contours_simplify_shared`` wrote them,
+    ``n_regions`` int32 [N] and ``records`` int64 [N,rcap,8] of ``rle_regions`` (a region's value is read) -> ``labels_out`` uint8 [N,H,W]
+    (rows contiguous, any pitch / image stride): every region's loops filled by the even-odd rule on the pixel centres, the larger region
+    number on top, ``background`` where no region covers; ``counts_out`` int32 [N] (the edge-row crossings the frame needs, exact whatever
+    the capacity; -1: the source frame was refused or overflowed, or its regions are missing or more than rcap -- nothing else of it is
+    touched; above ``event_capacity``: nothing else of it is written) and, when given, ``stats`` int64 [N,FILL_NSTATS]: ``gaps, excess,
+    changed`` and 256 each of ``ref_area, fill_area, both`` against ``ref_labels`` (uint8 [N,H,W], rows contiguous; None: ``changed``,
+    ``ref_area`` and ``both`` stay 0).  ``event_capacity``: the crossing slots per frame; twice the run code's capacity cannot overflow
+    for outlines that come from it (default: half the vertex capacity, which is that with ``rle_contours``' default of 4 vertices per
+    run).  ``labels_out=None`` with ``event_capacity=0``: the sizing pass.
+    ``workspace``: a device tensor of at least ``arseg_contours_fill_workspace_bytes(N, H, W, lcap, vcap, event_capacity)`` bytes, 8-byte
+    aligned (default: the stream's shared workspace).  With every buffer given nothing is allocated and nothing synchronises: capturable
+    in a HIP graph.  Returns (labels_out, counts_out, stats)."""
+    what = "contours_fill"
+    H, W = _frame_dims(what, H, W, 16384)
+    background = int(background)
+    if not 0 <= background <= 255:
+        raise ValueError(f"{what}: background is a byte, got {background}")
+    if event_capacity is not None and int(event_capacity) < 0:
+        raise ValueError(f"{what}: event_capacity must not be negative, got {event_capacity!r}")
+    if labels_out is None and (event_capacity is None or int(event_capacity) > 0):
+        raise ValueError(f"{what}: labels_out is required (None with event_capacity=0 is the sizing pass)")
+    N = _dense(what, "counts", counts, torch.int32, (None, 2))
+    dev = counts.device
+    if N < 1:
+        raise _lib.ArsegError(f"{what}: counts must hold at least one frame, got {tuple(counts.shape)}")
+    _dense(what, "counts_out", counts_out, torch.int32, (N,), dev)
+    _dense(what, "n_regions", n_regions, torch.int32, (N,), dev)
+    lcap = 0 if loops is None else _dense(what, "loops", loops, torch.int32, (N, None, 4), dev)
+    vcap = 0 if verts is None else _dense(what, "verts", verts, _RUN_DTYPES, (N, None), dev)
+    rcap = 0 if records is None else _dense(what, "records", records, torch.int64, (N, None, 8), dev)
+    ecap = vcap // 2 if event_capacity is None else int(event_capacity)
+    pitch, ns = _out_plane(what, "labels_out", labels_out, N, H, W, dev)
+    ref_pitch, ref_ns = _out_plane(what, "ref_labels", ref_labels, N, H, W, dev)
+    if stats is not None:
+        _dense(what, "stats", stats, torch.int64, (N, _lib.FILL_NSTATS), dev)
+    lib = _lib.load()
+    workspace, ws_bytes = _own_workspace(what, workspace, lib.arseg_contours_fill_workspace_bytes(N, H, W, lcap, vcap, ecap), dev, 8)
+    launch(what, lib.arseg_contours_fill_fwd, _ptr(counts), _ptr(loops if lcap else None), lcap, _ptr(verts if vcap else None), vcap,
+           _ptr(n_regions), _ptr(records if rcap else None), rcap, N, H, W, background, _ptr(ref_labels), ref_pitch, ref_ns, _ptr(labels_out),
+           pitch, ns, _ptr(counts_out), _ptr(stats), ecap, _ptr(workspace), ws_bytes, _stream(),
+           nbytes=(0 if labels_out is None else N * H * W) + (0 if ref_labels is None else N * H * W) + 16 * N * (H + 1))          # (+ 16 bytes per crossing)
+    return labels_out, counts_out, stats

@@ -1180,6 +1180,66 @@ int arseg_contours_simplify_shared_fwd(const int32_t *row_start, const uint32_t 
                                        void *workspace, size_t workspace_bytes, arseg_stream_t stream);
 
 /* ---------------------------------------------------------------------------------------------
+ * Region polygons rasterised back to a label plane, with the fidelity counters (csrc/fill.hip): the inverse and the check of the three
+ * passes above -- the mask a consumer of the polygons draws, and what the simplification did to it: uncovered pixels, doubly covered
+ * pixels, pixels that changed value, and per value the areas and the intersection with the mask the outlines were traced from.  On the
+ * device, behind the passes above, without a host synchronisation: capturable in the same HIP graph.  Integers only: every result is
+ * exact and reproducible.  (A backward-compatible addition: ARSEG_ABI_VERSION stays.)
+ * Input, per frame: counts int32 [N][2], loops int32 [N][lcap][4] and verts uint32 [N][vcap] exactly as arseg_rle_contours_fwd,
+ *   arseg_contours_simplify_fwd or arseg_contours_simplify_shared_fwd leave them, with their capacities; n_regions int32 [N] and records
+ *   int64 [N][rcap][8] of arseg_rle_regions_fwd, of which only records[n][r][0], the region's value (its low byte), is read; H and W of
+ *   the frames, at most 16384; background, a byte; optionally ref_labels uint8 with ref_pitch and ref_image_stride (bytes): the mask the
+ *   outlines were traced from.
+ * Crossing.  Vertices are grid corners; the centre of pixel (x, y) is (x + 1/2, y + 1/2), so a pixel row never passes through a vertex.
+ *   An edge A -> B with ya != yb crosses the rows min(ya, yb) <= y < max(ya, yb); horizontal edges cross nothing.  Order the edge so that
+ *   ya < yb, whatever its direction of travel; with dy = yb - ya and t = 2 y + 1 - 2 ya the crossing column is
+ *       xs = ceil((2 xa dy + t (xb - xa) - dy) / (2 dy)),
+ *   the first column whose centre lies at or to the right of the edge, clamped into [0, W]; floor and ceiling are those of a negative
+ *   numerator too; all terms stay below 2^31 for H, W <= 16384.  A centre exactly on an edge therefore belongs to the polygon on the
+ *   right of the edge, and two loops that share an edge compute the same xs: the formula does not depend on the direction of travel.
+ * Coverage (even-odd per region).  For region r and row y sort the crossings of all edges of all loops whose record names r:
+ *   c0 <= c1 <= ... -- always an even number --; r covers the columns [c0, c1) u [c2, c3) u ...  The orientation of the loops and their
+ *   hole flag are not read.  A two-vertex loop, which arseg_contours_simplify_shared_fwd can emit, cancels itself.
+ * Composition (painter's rule).  A pixel covered by k regions takes the value of the covering region with the largest region number; a
+ *   pixel with k = 0 takes background.  That equals filling each region's loops in rising region number over a plane of background --
+ *   what a consumer does with fillPoly-style calls.
+ * Outputs, all OVERWRITTEN:
+ *   labels_out  uint8, row y of frame n at labels_out + n * image_stride + y * pitch.
+ *   counts_out  int32 [N]: E, the number of crossings the frame needs, exact whatever ecap is (INT32_MAX from there on); or -1: the frame
+ *               is refused -- its source counts are negative, L > lcap, V > vcap, n_regions[n] < 0 or n_regions[n] > rcap -- and nothing
+ *               else of it is touched.  A frame with E > ecap gets its counts_out and nothing else.  Decided on the device.
+ *   stats       int64 [N][ARSEG_FILL_NSTATS] = {gaps, excess, changed, ref_area[256], fill_area[256], both[256]} (may be NULL): gaps the
+ *               pixels with k = 0; excess the sum of max(k - 1, 0) over the pixels; changed the pixels whose output differs from
+ *               ref_labels, gap pixels counting as changed; ref_area[v] the pixels of value v in the reference; fill_area[v] the covered
+ *               pixels that received v; both[v] the covered pixels with v in both.  Without a reference changed, ref_area and both are 0.
+ *   labels_out == NULL with ecap == 0: the sizing pass, counts_out only.
+ * Capacity.  The loops of arseg_rle_contours_fwd, arseg_contours_simplify_fwd and arseg_contours_simplify_shared_fwd that come from a
+ *   run code of capacity cap need E <= 2 x cap: the exact outlines have 2 x runs unit crossings (a run's two ends), and a Douglas-Peucker
+ *   chord never spans more rows than the chain it replaces.  ecap = 2 x cap therefore never overflows for them.
+ * workspace: the caller's, 8-byte aligned, >= arseg_contours_fill_workspace_bytes(N, H, W, lcap, vcap, ecap) bytes (else
+ *   ARSEG_EWORKSPACE): per frame 8 bytes per crossing slot and 8 per row and one more, and for W > 8192 one owner line of 4 W bytes per
+ *   workgroup of the row launch (at most 256); sizes that do not fit size_t give SIZE_MAX and ARSEG_EWORKSPACE.  Its contents are scratch.
+ * 5 launches (clear, count, scan, scatter, rows -- the first three in a sizing pass), sized on the host from the capacities; no workgroup
+ *   waits for another.  Enqueue only: no allocation, no synchronisation.  The buffers must not overlap.  A row with m crossings costs
+ *   m x m comparisons (a rank by counting), on chip up to 1024 crossings and from L2 beyond.
+ * Malformed input (a loop outside the frame's vertices, a region number outside [0, n_regions), a vertex beyond W or H) gives
+ *   meaningless output, but nothing outside the caller's buffers is read or written: loop records, region numbers, vertices, bucket
+ *   bounds and slots are clamped, and every loop is bounded.
+ * ARSEG_EINVAL, before any launch: a null counts, n_regions or counts_out; loops NULL with lcap > 0, verts NULL with vcap > 0, records
+ *   NULL with rcap > 0, labels_out NULL with ecap > 0; counts, loops, verts, n_regions or counts_out not 4-byte aligned, records, stats
+ *   or the workspace not 8-byte aligned; non-positive N, H or W; H > 16384 or W > 16384; a negative capacity; background outside
+ *   0..255; pitch < W or ref_pitch < W, a negative image stride; an output that is one of the inputs or another output; a null workspace.
+ * Not covered: anti-aliased (fractional) coverage; non-integer vertices; winding-rule fills; frames of more than 16384 rows or columns.
+ * ------------------------------------------------------------------------------------------- */
+#define ARSEG_FILL_NSTATS (3 + 3 * 256)
+size_t arseg_contours_fill_workspace_bytes(int N, int H, int W, int64_t lcap, int64_t vcap, int64_t ecap);
+int arseg_contours_fill_fwd(const int32_t *counts, const int32_t *loops, int64_t lcap, const uint32_t *verts, int64_t vcap,
+                            const int32_t *n_regions, const int64_t *records, int64_t rcap, int N, int H, int W, int background,
+                            const uint8_t *ref_labels, int64_t ref_pitch, int64_t ref_image_stride, uint8_t *labels_out, int64_t pitch,
+                            int64_t image_stride, int32_t *counts_out, int64_t *stats, int64_t ecap, void *workspace,
+                            size_t workspace_bytes, arseg_stream_t stream);
+
+/* ---------------------------------------------------------------------------------------------
  * Measurement aids (no reference counterpart; BASELINE.md section 3: roofline fractions are reported against the datasheet peaks AND
  * against on-box micro-benchmarks).  bench.py times each with HIP events and prints `peaks_measured`.
  *   arseg_peak_stream_copy: dst[0 .. n_bytes) = src[0 .. n_bytes) with 16-byte accesses (n_bytes % 16 == 0, both 16-byte aligned):
