@@ -7,6 +7,8 @@
   wrapped in ``nn.DataParallel`` (the reference addresses ``net.module`` on the hot path).
 * ``EvalByDistance`` / ``EvalTable`` / ``table_filename`` -- the reference's result table (mIoU at keyframe distance
   0 .. GOP-1 and their mean, evaluation.py:272-303, 308-386, 406-439) from ONE pass: one confusion matrix per distance.
+* ``EvalByBand`` / ``BandTable`` / ``label_bands_numpy`` -- the same table split by the distance to the ground truth's label boundaries
+  (trimap bands; no reference counterpart), from the same one pass.
 * ``alter_res_step_fast`` -- the same non-keyframe step on the kernel-native layouts (int16 MVs in,
   MV resize + warp + CReFF + head fused), used by the GOP runner and bench.py.
 
@@ -302,6 +304,151 @@ class EvalTable(object):
         t = cls.__new__(cls)
         t.hist, t.iou, t.miou = None, None, [float(v) for v in vals[:-1]]
         return t
+
+
+def label_bands_numpy(label, radii, n_cls, ignore_label=255):
+    """The host form of ``ops.label_bands``' band plane (include/arseg_hip.h, arseg_label_bands_fwd), numpy only: ``label`` an integer
+    array [..., H, W] -> uint8 of the same shape, the band of every pixel (``len(radii)``: interior).  A 3 x 3 minimum and a 3 x 3 maximum
+    filter with edge replication, iterated: after r rounds they are the extremes of the clipped (2r+1) x (2r+1) window, and the distance
+    of a pixel is the first r at which the two differ."""
+    rad = ops.band_radii(radii)
+    lab = np.asarray(label)
+    if lab.ndim < 2 or not np.issubdtype(lab.dtype, np.integer):
+        raise ValueError(f"label_bands_numpy takes an integer array [..., H, W], got {lab.dtype} {lab.shape}")
+    lab = lab.astype(np.int64)
+    lo = np.where((lab >= 0) & (lab < n_cls) & (lab != ignore_label), lab, 255).astype(np.uint8)
+    hi = lo
+
+    def spread(a, pick):
+        for axis in (-2, -1):
+            p = np.concatenate([np.take(a, [0], axis), a, np.take(a, [-1], axis)], axis)
+            n = a.shape[axis]
+            a = pick(pick(np.take(p, range(0, n), axis), np.take(p, range(1, n + 1), axis)), np.take(p, range(2, n + 2), axis))
+        return a
+
+    dist = np.full(lab.shape, rad[-1] + 1, np.int64)
+    for r in range(1, rad[-1] + 1):
+        lo, hi = spread(lo, np.minimum), spread(hi, np.maximum)
+        dist = np.where((dist > r) & (lo != hi), r, dist)
+    return np.searchsorted(np.asarray(rad), dist, side="left").astype(np.uint8)
+
+
+def alter_res_batch_bands(lr_net, ref_ps, imgs, mv_qs, labels, radii, scale=0.5, hist=None, ignore_label=255, groups=None, n_groups=1):
+    """``alter_res_batch_pred``'s sibling for the errors' place: the same phases and tail (its pred, without a label), then
+    ``ops.label_bands`` of that pred against ``labels`` (int64 [B,H,W]) -> (pred int32 [B,H,W], hist int64
+    [n_groups, len(radii) + 1, n_cls, n_cls], accumulated when given).  ``groups`` / ``n_groups`` as ``ops.label_bands`` takes them.
+    Nothing comes to the host in between."""
+    pred, _ = alter_res_batch_pred(lr_net, ref_ps, imgs, mv_qs, scale=scale)
+    n_cls = hist.shape[-1] if hist is not None else _unwrap(lr_net).final_conv.out_channels
+    _, hist = ops.label_bands(labels, radii, pred=pred, groups=groups, n_groups=n_groups, n_cls=n_cls, hist=hist, ignore_label=ignore_label)
+    return pred, hist
+
+
+class BandTable(object):
+    """mIoU per keyframe distance and boundary band from a [G, n_bands + 1, n_cls, n_cls] histogram (``EvalByBand``): ``hist`` and
+    ``radii``; ``band(k)`` the pixels whose distance to a label boundary is in (radii[k-1], radii[k]], ``trimap(k)`` those within
+    radii[k] (the bands 0 .. k summed), ``interior()`` those beyond the last radius and ``total()`` all of them -- ``EvalByDistance``'s
+    histogram on the same samples --, each an ``EvalTable``.  Plain torch / numpy; works on CPU tensors."""
+
+    def __init__(self, hist, radii):
+        hist = torch.as_tensor(hist)
+        self.radii = ops.band_radii(radii)
+        if hist.dim() != 4 or hist.shape[1] != len(self.radii) + 1 or hist.shape[2] != hist.shape[3]:
+            raise ValueError(f"BandTable takes a [G, {len(self.radii) + 1}, n_cls, n_cls] histogram, got {tuple(hist.shape)}")
+        self.hist = hist
+
+    def _need_hist(self):
+        if self.hist is None:
+            raise ValueError("a table read from a file holds the mIoU values only, not the histogram")
+
+    def band(self, k):
+        self._need_hist()
+        if not 0 <= k < len(self.radii):
+            raise IndexError(f"band {k} of {len(self.radii)}")
+        return EvalTable(self.hist[:, k])
+
+    def trimap(self, k):
+        self._need_hist()
+        if not 0 <= k < len(self.radii):
+            raise IndexError(f"trimap {k} of {len(self.radii)}")
+        return EvalTable(self.hist[:, :k + 1].sum(dim=1))
+
+    def interior(self):
+        self._need_hist()
+        return EvalTable(self.hist[:, -1])
+
+    def total(self):
+        self._need_hist()
+        return EvalTable(self.hist.sum(dim=1))
+
+    def as_array(self):
+        """[n_bands + 2, G + 1]: the trimaps of width radii[0], radii[1], ..., the interior, the total; each row the G values and their
+        mean, as ``EvalTable.as_array``."""
+        if self.hist is None:
+            return self._array
+        rows = [self.trimap(k) for k in range(len(self.radii))] + [self.interior(), self.total()]
+        return np.stack([t.as_array() for t in rows])
+
+    def save(self, path):
+        np.savetxt(path, self.as_array(), header="radii " + " ".join(str(r) for r in self.radii))
+
+    @classmethod
+    def load(cls, path):
+        """A table written by ``save``: the radii and the floats only (``hist`` is None; ``as_array`` gives them back)."""
+        with open(path) as f:
+            head = f.readline().split()
+        if head[:2] != ["#", "radii"]:
+            raise ValueError(f"{path}: not a BandTable file (no radii line)")
+        t = cls.__new__(cls)
+        t.radii = ops.band_radii(head[2:])
+        vals = np.atleast_2d(np.loadtxt(path))
+        if vals.shape[0] != len(t.radii) + 2 or vals.shape[1] < 2:
+            raise ValueError(f"{path}: expected {len(t.radii) + 2} rows of G mIoU values and their mean, got {vals.shape}")
+        t.hist, t._array = None, vals
+        return t
+
+
+class EvalByBand(EvalByDistance):
+    """``EvalByDistance`` with the place of the errors: the same samples, keyframe handling (d = 0 through the HR net) and operand-range
+    fallback, one pass, and per keyframe distance one confusion matrix per band of distance to the ground truth's label boundaries
+    (``radii``, in pixels; include/arseg_hip.h, arseg_label_bands_fwd).  One [gop, len(radii) + 1, n_cls, n_cls] histogram, all-reduced
+    once under torch.distributed.  Returns a ``BandTable``, whose ``total()`` is ``EvalByDistance``'s table on the same samples."""
+
+    def __init__(self, scale=0.5, ignore_label=255, gop=12, cache_keyframe=False, radii=(1, 2, 4, 8)):
+        super().__init__(scale, ignore_label, gop, cache_keyframe)
+        self.radii = ops.band_radii(radii)
+
+    def __call__(self, highres_net, net, dl, n_classes):
+        first = self.hr_forwards
+
+        def reset():
+            self.hr_forwards = first
+
+        hist = _range_safe_hist(lambda: self._run(highres_net, net, dl, n_classes), dl, reset)
+        if dist.is_available() and dist.is_initialized():
+            dist.all_reduce(hist, dist.ReduceOp.SUM)                 # integer counts: exact
+        return BandTable(hist, self.radii)
+
+    def _run(self, highres_net, net, dl, n_classes):
+        hist = torch.zeros((self.gop, len(self.radii) + 1, n_classes, n_classes), dtype=torch.int64, device="cuda")
+        lr_net = _unwrap(net)
+        cache = [None, None]
+        for sample in dl:
+            label = sample[1].cuda()
+            N = label.shape[0]
+            if len(sample) == 3:
+                out = highres_net(sample[0].cuda())[0]
+                groups = [0] * N
+            elif len(sample) == 6:
+                imgs, _, _, ref_imgs, flow, d = sample
+                out = self._logits(highres_net, lr_net, imgs, ref_imgs, flow, cache)
+                groups = self._groups(d, N)
+            else:
+                raise ValueError(f"EvalByBand takes (imgs, label, _) or (imgs, label, _, ref_imgs, flow, dist) samples, got {len(sample)} elements")
+            pred, _ = ops.argmax_confusion_grouped(out, None, groups, self.gop, label.shape[-2], label.shape[-1])
+            ops.label_bands(label, self.radii, pred=pred, groups=groups, n_groups=self.gop, n_cls=n_classes, hist=hist,
+                            ignore_label=self.ignore_label)
+        return hist
 
 
 def alter_res_step_fast(lr_net, ref_p_nhwc, img, mv_q, scale=0.5):

@@ -572,3 +572,79 @@ def argmax_confusion_grouped(logits: torch.Tensor, label: Optional[torch.Tensor]
     launch("argmax_confusion_grouped", _lib.load().arseg_argmax_confusion_grouped_fwd, _ptr(logits), _ptr(label), _ptr(grp), _ptr(pred),
            _ptr(hist if label is not None else None), N, n_groups, n_cls, h, w, H, W, ignore_label, 1 if align_corners else 0, _stream())
     return pred, hist
+
+
+_stream_workspace = workspace          # (label_bands takes a ``workspace`` argument of its own)
+
+
+def band_radii(radii) -> tuple:
+    """The radii of ``label_bands`` as a tuple of ints after their check: 1 .. 8 of them, each in 1 .. 32, strictly ascending."""
+    r = tuple(int(v) for v in radii)
+    if not 1 <= len(r) <= 8 or any(not 1 <= v <= 32 for v in r) or any(b <= a for a, b in zip(r, r[1:])):
+        raise ValueError(f"radii: 1 to 8 strictly ascending integers in 1..32, got {r}")
+    return r
+
+
+def label_bands(label: torch.Tensor, radii, pred: Optional[torch.Tensor] = None, groups=None, n_groups: int = 1, n_cls: Optional[int] = None,
+                hist: Optional[torch.Tensor] = None, ignore_label: int = 255, band_out=None, workspace: Optional[torch.Tensor] = None):
+    """Confusion counts in bands around the label boundaries (include/arseg_hip.h, arseg_label_bands_fwd): ``label`` int64 [N,H,W] and
+    ``pred`` int32 [N,H,W] (``argmax_confusion*``'s) -> ``hist`` int64 [n_groups, len(radii) + 1, n_cls, n_cls], accumulated: frame n counts
+    into hist[groups[n]][band], the band of a pixel being the first radius its Chebyshev distance to a pixel of another label (void is
+    one label) does not exceed, ``len(radii)`` for the interior.  The sum over the bands is ``argmax_confusion_grouped``'s hist.
+    ``groups`` as ``argmax_confusion_grouped`` takes them, or None with ``n_groups == 1``.  ``n_cls``: default ``hist.shape[-1]``.
+    ``band_out``: a uint8 [N,H,W] plane (rows contiguous, any pitch / image stride) for the band of every pixel, True to have it
+    allocated, None for no plane -- except without ``pred``, where the plane is all the call gives (``hist`` must then be None too).
+    ``workspace``: a device tensor of at least ``arseg_label_bands_workspace_bytes(N, H, W)`` bytes (default: the stream's shared one).
+    One ABI call; with every buffer given nothing is allocated and nothing synchronises.  Returns (bands or None, hist or None)."""
+    what = "label_bands"
+    rad = band_radii(radii)
+    ids = None if groups is None else _group_ids(groups, n_groups)
+    if groups is None and n_groups != 1:
+        raise ValueError(f"{what}: groups=None needs n_groups == 1, got {n_groups}")
+    if pred is None and hist is not None:
+        raise ValueError(f"{what}: hist needs pred")
+    _need_gpu(label, dtype=torch.int64)
+    if label.dim() != 3 or not label.is_contiguous():
+        raise _lib.ArsegError(f"{what}: label must be a contiguous int64 [N,H,W] tensor, got {tuple(label.shape)} strides {label.stride()}")
+    N, H, W = label.shape
+    dev = label.device
+    if n_cls is None:
+        if hist is None:
+            raise ValueError(f"{what}: n_cls is required without hist")
+        n_cls = hist.shape[-1]
+    n_cls = int(n_cls)
+    if not 1 <= n_cls <= 32:
+        raise ValueError(f"{what}: 1..32 classes, got {n_cls}")
+    grp = None
+    if pred is not None:
+        _need_gpu(pred, dtype=torch.int32)
+        if tuple(pred.shape) != (N, H, W) or not pred.is_contiguous() or pred.device != dev:
+            raise _lib.ArsegError(f"{what}: pred must be a contiguous int32 {(N, H, W)} tensor on {dev}, got {tuple(pred.shape)} on {pred.device}")
+        if groups is not None:
+            grp = _groups_tensor(groups, ids, N, dev)
+        shape = (n_groups, len(rad) + 1, n_cls, n_cls)
+        if hist is None:
+            hist = torch.zeros(shape, dtype=torch.int64, device=dev)
+        elif tuple(hist.shape) != shape or hist.dtype != torch.int64 or hist.device != dev or not hist.is_contiguous():
+            raise _lib.ArsegError(f"{what}: hist must be a contiguous int64 GPU tensor {list(shape)}, got {hist.dtype} {tuple(hist.shape)}")
+    if band_out is True or (band_out is None and pred is None):
+        band_out = torch.empty((N, H, W), dtype=torch.uint8, device=dev)
+    pitch, ns = 0, 0
+    if band_out is not None:
+        _need_gpu(band_out, dtype=torch.uint8)
+        if tuple(band_out.shape) != (N, H, W) or band_out.device != dev:
+            raise ValueError(f"{what}: band_out must be uint8 {(N, H, W)} on {dev}, got {tuple(band_out.shape)} on {band_out.device}")
+        pitch, ns = _plane_layout(band_out, (W,), f"{what} band_out")
+    lib = _lib.load()
+    need = lib.arseg_label_bands_workspace_bytes(N, H, W)
+    if need == 0:
+        raise ValueError(f"{what}: frames of 1..16384 rows and columns, got {H}x{W}")
+    if workspace is None:
+        workspace = _stream_workspace(need, dev)
+    elif not workspace.is_cuda or workspace.device != dev or not workspace.is_contiguous() or workspace.data_ptr() % 2 or \
+            workspace.numel() * workspace.element_size() < need:
+        raise _lib.ArsegError(f"{what}: workspace must be a contiguous, 2-byte aligned tensor of at least {need} bytes on {dev}")
+    launch(what, lib.arseg_label_bands_fwd, _ptr(label), _ptr(pred), _ptr(grp), (ctypes.c_int * len(rad))(*rad), len(rad), _ptr(band_out), pitch, ns,
+           _ptr(hist), N, n_groups, n_cls, H, W, int(ignore_label), _ptr(workspace), workspace.numel() * workspace.element_size(), _stream(),
+           nbytes=N * H * W * (8 + 4 + (4 if pred is not None else 0) + (1 if band_out is not None else 0)))
+    return band_out, hist

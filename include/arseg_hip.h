@@ -1240,6 +1240,47 @@ int arseg_contours_fill_fwd(const int32_t *counts, const int32_t *loops, int64_t
                             size_t workspace_bytes, arseg_stream_t stream);
 
 /* ---------------------------------------------------------------------------------------------
+ * Confusion counts in bands around the label boundaries (csrc/bands.hip): where the errors are, next to the evaluator tail's how many --
+ * the "trimap" accuracy of DeepLab, the band Boundary IoU is built on.  No reference counterpart.
+ * Void.      label is int64 [N][H][W], contiguous, as the evaluator tail takes it.  Every pixel becomes a byte: v = label if
+ *            0 <= label < n_cls and label != ignore_label, else 255 ("void").  All void pixels are one value.
+ * Distance.  D(p) is the smallest r >= 1 such that the (2r+1) x (2r+1) window centred at p, CLIPPED to the image, holds a pixel whose
+ *            byte differs from p's: a Chebyshev distance, what r iterations of a 3 x 3 erosion remove.  The image border is not a
+ *            boundary; a frame of one value has none.
+ * Bands.     radii is a HOST array of n_bands ints, strictly ascending, 1 <= radii[k] <= 32, 1 <= n_bands <= 8.  band(p) is the smallest
+ *            k with D(p) <= radii[k], and n_bands ("interior") if D(p) > radii[n_bands - 1].  The bands are disjoint; cumulating them
+ *            (a trimap of width radii[k] is the bands 0 .. k) is the host's business.
+ * Tally.     pred is int32 [N][H][W], what arseg_argmax_confusion*_fwd write; group is int32 [N] on the device and may be NULL only
+ *            when n_groups == 1: every frame is then group 0.  Every non-void pixel with 0 <= pred < n_cls, in a frame whose group id is
+ *            in [0, n_groups), adds 1 to hist[group[n]][band(p)][label][pred]; hist is int64 [n_groups][n_bands + 1][n_cls][n_cls],
+ *            ACCUMULATED.  Void pixels count nowhere; they still get a band and still are a boundary for their neighbours, as the void
+ *            ring of a VOC-style annotation is.  The sum of hist[g] over the bands is bit-equal to the hist[g] that
+ *            arseg_argmax_confusion_grouped_fwd gives on the same labels and the logits the predictions come from.
+ * band_out   uint8, band(p) of row y of frame n at band_out + n * band_n_stride + y * band_pitch (bytes; band_pitch >= W,
+ *            band_n_stride >= 0); OVERWRITTEN, for every frame and pixel, void ones included.  May be NULL.
+ * pred and hist may be NULL together (the bands of a plane only); pred without hist is not read.  With band_out and hist both NULL only
+ *            the first launch runs, which leaves the workspace's words (tools/bench_bands.py times the launches apart that way).
+ * workspace: the caller's, 2-byte aligned, >= arseg_label_bands_workspace_bytes(N, H, W) bytes (else ARSEG_EWORKSPACE): one 16-bit word
+ *            per pixel, rounded up to 16 bytes in all (0 for dimensions the entry point refuses; a size that does not fit size_t gives
+ *            SIZE_MAX).  Its contents are scratch.
+ * 2 launches (rows: label -> byte and in-row distance; columns: the distance, the band, the tally), sized on the host; no workgroup
+ *            waits for another.  Enqueue only: no allocation, no synchronisation; capturable in a HIP graph.  The buffers must not
+ *            overlap.
+ * Malformed labels only ever give void, predictions outside [0, n_cls) and group ids outside [0, n_groups) count nowhere; nothing
+ *            outside the caller's buffers is read or written, and every loop is bounded.
+ * ARSEG_EINVAL, before any launch: a null label, radii or workspace; non-positive N, H or W; H > 16384 or W > 16384; n_bands outside
+ *            1..8, a radius outside 1..32 or radii that do not ascend strictly; n_cls outside 1..32; n_groups < 1; a null group with
+ *            n_groups > 1; hist without pred; with band_out, band_pitch < W or a negative band_n_stride; label or hist not 8-byte
+ *            aligned, pred or group not 4-byte aligned, the workspace not 2-byte aligned.
+ * Not covered: Boundary IoU proper (it needs the band of the prediction too, and a joint tally; band_out is what it would start from);
+ *            Euclidean distance; radii above 32; the image border as a boundary.
+ * ------------------------------------------------------------------------------------------- */
+size_t arseg_label_bands_workspace_bytes(int N, int H, int W);
+int arseg_label_bands_fwd(const int64_t *label, const int32_t *pred, const int32_t *group, const int *radii, int n_bands, uint8_t *band_out,
+                          int64_t band_pitch, int64_t band_n_stride, int64_t *hist, int N, int n_groups, int n_cls, int H, int W,
+                          int ignore_label, void *workspace, size_t workspace_bytes, arseg_stream_t stream);
+
+/* ---------------------------------------------------------------------------------------------
  * Measurement aids (no reference counterpart; BASELINE.md section 3: roofline fractions are reported against the datasheet peaks AND
  * against on-box micro-benchmarks).  bench.py times each with HIP events and prints `peaks_measured`.
  *   arseg_peak_stream_copy: dst[0 .. n_bytes) = src[0 .. n_bytes) with 16-byte accesses (n_bytes % 16 == 0, both 16-byte aligned):
