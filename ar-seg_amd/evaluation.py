@@ -9,6 +9,8 @@
   0 .. GOP-1 and their mean, evaluation.py:272-303, 308-386, 406-439) from ONE pass: one confusion matrix per distance.
 * ``EvalByBand`` / ``BandTable`` / ``label_bands_numpy`` -- the same table split by the distance to the ground truth's label boundaries
   (trimap bands; no reference counterpart), from the same one pass.
+* ``EvalByBoundary`` / ``BoundaryTable`` / ``boundary_iou_numpy`` -- Boundary IoU per keyframe distance (the ground truth's band
+  intersected with the prediction's; no reference counterpart), from the same one pass.
 * ``alter_res_step_fast`` -- the same non-keyframe step on the kernel-native layouts (int16 MVs in,
   MV resize + warp + CReFF + head fused), used by the GOP runner and bench.py.
 
@@ -449,6 +451,183 @@ class EvalByBand(EvalByDistance):
             ops.label_bands(label, self.radii, pred=pred, groups=groups, n_groups=self.gop, n_cls=n_classes, hist=hist,
                             ignore_label=self.ignore_label)
         return hist
+
+
+def boundary_iou_numpy(label, pred, radii, n_cls, ignore_label=255, border=True):
+    """The host form of ``ops.boundary_iou``'s counts (include/arseg_hip.h, arseg_boundary_iou_fwd), numpy only and written the paper's
+    way: ``label`` and ``pred`` integer arrays [..., H, W] -> int64 [3, len(radii) + 1, n_cls], the frames summed.  Per class the mask
+    of the ground truth and that of the prediction, each minus its d-fold 3 x 3 erosion (zero-padded with ``border``, edge-replicated
+    without), restricted to the pixels that count, give the inner bands of width d = radii[k] and their intersection; differences of
+    consecutive widths give the disjoint bands, the whole masks the last one."""
+    rad = ops.boundary_radii(radii)
+    lab, prd = np.asarray(label), np.asarray(pred)
+    if lab.ndim < 2 or lab.shape != prd.shape or not np.issubdtype(lab.dtype, np.integer) or not np.issubdtype(prd.dtype, np.integer):
+        raise ValueError(f"boundary_iou_numpy takes two integer arrays [..., H, W] of one shape, got {lab.dtype} {lab.shape} and {prd.dtype} {prd.shape}")
+    lab, prd = lab.astype(np.int64), prd.astype(np.int64)
+    lab = np.where((lab >= 0) & (lab < n_cls) & (lab != ignore_label), lab, 255)
+    prd = np.where((prd >= 0) & (prd < n_cls), prd, 255)
+    counting = (lab != 255) & (prd != 255)
+
+    def erode(m):
+        for axis in (-2, -1):
+            n = m.shape[axis]
+            first, last = np.take(m, [0], axis), np.take(m, [-1], axis)
+            if border:
+                first, last = np.zeros_like(first), np.zeros_like(last)
+            p = np.concatenate([first, m, last], axis)
+            m = np.take(p, range(0, n), axis) & np.take(p, range(1, n + 1), axis) & np.take(p, range(2, n + 2), axis)
+        return m
+
+    def sizes(g, p):
+        g, p = g & counting, p & counting
+        return np.array([g.sum(), p.sum(), (g & p).sum()], np.int64)
+
+    out = np.zeros((3, len(rad) + 1, n_cls), np.int64)
+    for c in range(n_cls):
+        g, p = lab == c, prd == c
+        eg, ep, d, before = g, p, 0, np.zeros(3, np.int64)
+        for k, r in enumerate(rad):
+            while d < r:
+                eg, ep, d = erode(eg), erode(ep), d + 1
+            within = sizes(g & ~eg, p & ~ep)
+            out[:, k, c], before = within - before, within
+        out[:, len(rad), c] = sizes(g, p) - before
+    return out
+
+
+def alter_res_batch_boundary(lr_net, ref_ps, imgs, mv_qs, labels, radii, scale=0.5, counts=None, ignore_label=255, groups=None, n_groups=1,
+                             border=True):
+    """``alter_res_batch_pred``'s sibling for Boundary IoU: the same phases and tail (its pred, without a label), then
+    ``ops.boundary_iou`` of that pred against ``labels`` (int64 [B,H,W]) -> (pred int32 [B,H,W], counts int64
+    [n_groups, 3, len(radii) + 1, n_cls], accumulated when given).  ``groups`` / ``n_groups`` as ``ops.boundary_iou`` takes them.
+    Nothing comes to the host in between."""
+    pred, _ = alter_res_batch_pred(lr_net, ref_ps, imgs, mv_qs, scale=scale)
+    n_cls = counts.shape[-1] if counts is not None else _unwrap(lr_net).final_conv.out_channels
+    counts, _, _ = ops.boundary_iou(labels, pred, radii, groups=groups, n_groups=n_groups, n_cls=n_cls, counts=counts, ignore_label=ignore_label,
+                                    border=border)
+    return pred, counts
+
+
+class BoundaryTable(object):
+    """Boundary IoU per keyframe distance from a [G, 3, n_bands + 1, n_cls] tensor of counts (``EvalByBoundary``, ``ops.boundary_iou``):
+    ``counts``, ``radii`` and ``border``.  ``boundary_iou(k)`` float32 [G, n_cls], the Boundary IoU at width radii[k] (the bands 0 .. k
+    summed; I / (G + P - I) in ``EvalTable``'s float32 arithmetic, 0 / 0 = NaN); ``iou()`` all bands summed -- ``EvalByDistance``'s
+    ``EvalTable.iou`` on the same samples; ``miou(k)`` the G class means as Python floats (``k=None``: of ``iou()``) and ``mean(k)`` their
+    float64 mean as ``EvalTable`` takes it.  Plain torch / numpy; works on CPU tensors."""
+
+    def __init__(self, counts, radii, border=True):
+        counts = torch.as_tensor(counts)
+        self.radii = ops.boundary_radii(radii)
+        self.border = bool(border)
+        if counts.dim() != 4 or counts.shape[1] != 3 or counts.shape[2] != len(self.radii) + 1:
+            raise ValueError(f"BoundaryTable takes [G, 3, {len(self.radii) + 1}, n_cls] counts, got {tuple(counts.shape)}")
+        self.counts = counts
+
+    def _need_counts(self):
+        if self.counts is None:
+            raise ValueError("a table read from a file holds the mean values only, not the counts")
+
+    def _ratio(self, upto):
+        c = self.counts[:, :, :upto].sum(dim=2).float()
+        return c[:, 2] / (c[:, 0] + c[:, 1] - c[:, 2])
+
+    def boundary_iou(self, k):
+        self._need_counts()
+        if not 0 <= k < len(self.radii):
+            raise IndexError(f"radius {k} of {len(self.radii)}")
+        return self._ratio(k + 1).cpu()
+
+    def iou(self):
+        self._need_counts()
+        return self._ratio(len(self.radii) + 1).cpu()
+
+    def miou(self, k=None):
+        self._need_counts()
+        if k is not None and not 0 <= k < len(self.radii):
+            raise IndexError(f"radius {k} of {len(self.radii)}")
+        ious = self._ratio(len(self.radii) + 1 if k is None else k + 1)
+        return [i.mean().item() for i in ious]               # on the counts' device, as EvalTable does
+
+    def mean(self, k=None):
+        return np.array(self.miou(k)).mean()
+
+    def as_array(self):
+        """[n_bands + 1, G + 1]: the mean Boundary IoU at radii[0], radii[1], ..., then the plain mIoU; each row the G values and their
+        mean, as ``EvalTable.as_array``."""
+        if self.counts is None:
+            return self._array
+        rows = [self.miou(k) for k in range(len(self.radii))] + [self.miou()]
+        return np.stack([np.array(list(r) + [np.array(r).mean()]) for r in rows])
+
+    def save(self, path):
+        np.savetxt(path, self.as_array(), header="radii " + " ".join(str(r) for r in self.radii) + f" border {int(self.border)}")
+
+    @classmethod
+    def load(cls, path):
+        """A table written by ``save``: the radii, the border flag and the floats only (``counts`` is None; ``as_array`` gives them back)."""
+        with open(path) as f:
+            head = f.readline().split()
+        if head[:2] != ["#", "radii"] or len(head) < 5 or head[-2] != "border" or head[-1] not in ("0", "1"):
+            raise ValueError(f"{path}: not a BoundaryTable file (no radii ... border line)")
+        t = cls.__new__(cls)
+        t.radii, t.border = ops.boundary_radii(head[2:-2]), head[-1] == "1"
+        vals = np.atleast_2d(np.loadtxt(path))
+        if vals.shape[0] != len(t.radii) + 1 or vals.shape[1] < 2:
+            raise ValueError(f"{path}: expected {len(t.radii) + 1} rows of G mean values and their mean, got {vals.shape}")
+        t.counts, t._array = None, vals
+        return t
+
+
+class EvalByBoundary(EvalByDistance):
+    """``EvalByDistance`` with Boundary IoU (Cheng et al., CVPR 2021): the same samples, keyframe handling (d = 0 through the HR net) and
+    operand-range fallback, one pass, and per keyframe distance the counts of ``ops.boundary_iou`` (include/arseg_hip.h,
+    arseg_boundary_iou_fwd).  ``radii`` in pixels; None takes ``ops.boundary_radius`` of the first label's size, the paper's 2 % of the
+    diagonal.  One [gop, 3, len(radii) + 1, n_cls] tensor, all-reduced once under torch.distributed.  Returns a ``BoundaryTable``, whose
+    ``iou()`` is ``EvalByDistance``'s table on the same samples."""
+
+    def __init__(self, scale=0.5, ignore_label=255, gop=12, cache_keyframe=False, radii=None, border=True):
+        super().__init__(scale, ignore_label, gop, cache_keyframe)
+        self.radii = None if radii is None else ops.boundary_radii(radii)
+        self.border = bool(border)
+
+    def __call__(self, highres_net, net, dl, n_classes):
+        first = self.hr_forwards
+        used = [self.radii]
+
+        def reset():
+            self.hr_forwards = first
+
+        counts = _range_safe_hist(lambda: self._run(highres_net, net, dl, n_classes, used), dl, reset)
+        if dist.is_available() and dist.is_initialized():
+            dist.all_reduce(counts, dist.ReduceOp.SUM)               # integer counts: exact
+        return BoundaryTable(counts, used[0], self.border)
+
+    def _run(self, highres_net, net, dl, n_classes, used):
+        counts = None
+        lr_net = _unwrap(net)
+        cache = [None, None]
+        for sample in dl:
+            label = sample[1].cuda()
+            N = label.shape[0]
+            if counts is None:
+                if used[0] is None:
+                    used[0] = ops.boundary_radii((ops.boundary_radius(label.shape[-2], label.shape[-1]),))    # above 64: refused
+                counts = torch.zeros((self.gop, 3, len(used[0]) + 1, n_classes), dtype=torch.int64, device="cuda")
+            if len(sample) == 3:
+                out = highres_net(sample[0].cuda())[0]
+                groups = [0] * N
+            elif len(sample) == 6:
+                imgs, _, _, ref_imgs, flow, d = sample
+                out = self._logits(highres_net, lr_net, imgs, ref_imgs, flow, cache)
+                groups = self._groups(d, N)
+            else:
+                raise ValueError(f"EvalByBoundary takes (imgs, label, _) or (imgs, label, _, ref_imgs, flow, dist) samples, got {len(sample)} elements")
+            pred, _ = ops.argmax_confusion_grouped(out, None, groups, self.gop, label.shape[-2], label.shape[-1])
+            ops.boundary_iou(label, pred, used[0], groups=groups, n_groups=self.gop, n_cls=n_classes, counts=counts,
+                             ignore_label=self.ignore_label, border=self.border)
+        if counts is None:
+            raise ValueError("EvalByBoundary: the loader gave no sample")
+        return counts
 
 
 def alter_res_step_fast(lr_net, ref_p_nhwc, img, mv_q, scale=0.5):

@@ -3,6 +3,7 @@ mergeMotion): thin wrappers, one ABI call each."""
 from __future__ import annotations
 
 import ctypes
+import math
 from typing import Optional
 
 import torch
@@ -648,3 +649,85 @@ def label_bands(label: torch.Tensor, radii, pred: Optional[torch.Tensor] = None,
            _ptr(hist), N, n_groups, n_cls, H, W, int(ignore_label), _ptr(workspace), workspace.numel() * workspace.element_size(), _stream(),
            nbytes=N * H * W * (8 + 4 + (4 if pred is not None else 0) + (1 if band_out is not None else 0)))
     return band_out, hist
+
+
+def boundary_radii(radii) -> tuple:
+    """The radii of ``boundary_iou`` as a tuple of ints after their check: 1 .. 8 of them, each in 1 .. 64, strictly ascending."""
+    r = tuple(int(v) for v in radii)
+    if not 1 <= len(r) <= 8 or any(not 1 <= v <= 64 for v in r) or any(b <= a for a, b in zip(r, r[1:])):
+        raise ValueError(f"radii: 1 to 8 strictly ascending integers in 1..64, got {r}")
+    return r
+
+
+def boundary_radius(H: int, W: int, ratio: float = 0.02) -> int:
+    """The band width of Boundary IoU (Cheng et al., CVPR 2021) in pixels: ``ratio`` of the image diagonal, at least 1."""
+    return max(1, int(round(ratio * math.sqrt(H * H + W * W))))
+
+
+def _band_plane(what, name, plane, N, H, W, dev):
+    """A band plane argument (None / True / a uint8 [N,H,W] tensor) -> (tensor or None, row pitch, image stride)."""
+    if plane is None:
+        return None, 0, 0
+    if plane is True:
+        plane = torch.empty((N, H, W), dtype=torch.uint8, device=dev)
+    _need_gpu(plane, dtype=torch.uint8)
+    if tuple(plane.shape) != (N, H, W) or plane.device != dev:
+        raise ValueError(f"{what}: {name} must be uint8 {(N, H, W)} on {dev}, got {tuple(plane.shape)} on {plane.device}")
+    pitch, ns = _plane_layout(plane, (W,), f"{what} {name}")
+    return plane, pitch, ns
+
+
+def boundary_iou(label: torch.Tensor, pred: torch.Tensor, radii, groups=None, n_groups: int = 1, n_cls: Optional[int] = None,
+                 counts: Optional[torch.Tensor] = None, ignore_label: int = 255, border: bool = True, label_band_out=None, pred_band_out=None,
+                 workspace: Optional[torch.Tensor] = None):
+    """Boundary IoU counts from joint label / prediction bands (include/arseg_hip.h, arseg_boundary_iou_fwd): ``label`` int64 [N,H,W] and
+    ``pred`` int32 [N,H,W] -> ``counts`` int64 [n_groups, 3, len(radii) + 1, n_cls], accumulated: per band of Chebyshev distance to the
+    nearest other byte of the label plane / of the prediction plane (and, with ``border``, to the image border) the pixels of the
+    ground-truth mask (row 0), of the predicted mask (row 1) and of both (row 2, at the larger of the two bands).  Summed over the bands
+    the rows are the row sums, column sums and diagonal of ``argmax_confusion_grouped``'s hist.  ``groups`` as ``argmax_confusion_grouped``
+    takes them, or None with ``n_groups == 1``.  ``n_cls``: default ``counts.shape[-1]``.  ``label_band_out`` / ``pred_band_out``: a
+    uint8 [N,H,W] plane (rows contiguous, any pitch / image stride), True to have it allocated, None for no plane.  ``workspace``: a
+    device tensor of at least ``arseg_boundary_iou_workspace_bytes(N, H, W)`` bytes (default: the stream's shared one).  One ABI call;
+    with every buffer given nothing is allocated and nothing synchronises.  Returns (counts, label bands or None, pred bands or None)."""
+    what = "boundary_iou"
+    rad = boundary_radii(radii)
+    ids = None if groups is None else _group_ids(groups, n_groups)
+    if groups is None and n_groups != 1:
+        raise ValueError(f"{what}: groups=None needs n_groups == 1, got {n_groups}")
+    _need_gpu(label, dtype=torch.int64)
+    if label.dim() != 3 or not label.is_contiguous():
+        raise _lib.ArsegError(f"{what}: label must be a contiguous int64 [N,H,W] tensor, got {tuple(label.shape)} strides {label.stride()}")
+    N, H, W = label.shape
+    dev = label.device
+    _need_gpu(pred, dtype=torch.int32)
+    if tuple(pred.shape) != (N, H, W) or not pred.is_contiguous() or pred.device != dev:
+        raise _lib.ArsegError(f"{what}: pred must be a contiguous int32 {(N, H, W)} tensor on {dev}, got {tuple(pred.shape)} on {pred.device}")
+    if n_cls is None:
+        if counts is None:
+            raise ValueError(f"{what}: n_cls is required without counts")
+        n_cls = counts.shape[-1]
+    n_cls = int(n_cls)
+    if not 1 <= n_cls <= 32:
+        raise ValueError(f"{what}: 1..32 classes, got {n_cls}")
+    grp = None if groups is None else _groups_tensor(groups, ids, N, dev)
+    shape = (n_groups, 3, len(rad) + 1, n_cls)
+    if counts is None:
+        counts = torch.zeros(shape, dtype=torch.int64, device=dev)
+    elif tuple(counts.shape) != shape or counts.dtype != torch.int64 or counts.device != dev or not counts.is_contiguous():
+        raise _lib.ArsegError(f"{what}: counts must be a contiguous int64 GPU tensor {list(shape)}, got {counts.dtype} {tuple(counts.shape)}")
+    label_band_out, lpitch, lns = _band_plane(what, "label_band_out", label_band_out, N, H, W, dev)
+    pred_band_out, ppitch, pns = _band_plane(what, "pred_band_out", pred_band_out, N, H, W, dev)
+    lib = _lib.load()
+    need = lib.arseg_boundary_iou_workspace_bytes(N, H, W)
+    if need == 0:
+        raise ValueError(f"{what}: frames of 1..16384 rows and columns, got {H}x{W}")
+    if workspace is None:
+        workspace = _stream_workspace(need, dev)
+    elif not workspace.is_cuda or workspace.device != dev or not workspace.is_contiguous() or workspace.data_ptr() % 2 or \
+            workspace.numel() * workspace.element_size() < need:
+        raise _lib.ArsegError(f"{what}: workspace must be a contiguous, 2-byte aligned tensor of at least {need} bytes on {dev}")
+    launch(what, lib.arseg_boundary_iou_fwd, _ptr(label), _ptr(pred), _ptr(grp), (ctypes.c_int * len(rad))(*rad), len(rad), 1 if border else 0,
+           _ptr(label_band_out), lpitch, lns, _ptr(pred_band_out), ppitch, pns, _ptr(counts), N, n_groups, n_cls, H, W, int(ignore_label),
+           _ptr(workspace), workspace.numel() * workspace.element_size(), _stream(),
+           nbytes=N * H * W * (12 + 8 + (1 if label_band_out is not None else 0) + (1 if pred_band_out is not None else 0)))
+    return counts, label_band_out, pred_band_out

@@ -1272,13 +1272,55 @@ int arseg_contours_fill_fwd(const int32_t *counts, const int32_t *loops, int64_t
  *            1..8, a radius outside 1..32 or radii that do not ascend strictly; n_cls outside 1..32; n_groups < 1; a null group with
  *            n_groups > 1; hist without pred; with band_out, band_pitch < W or a negative band_n_stride; label or hist not 8-byte
  *            aligned, pred or group not 4-byte aligned, the workspace not 2-byte aligned.
- * Not covered: Boundary IoU proper (it needs the band of the prediction too, and a joint tally; band_out is what it would start from);
- *            Euclidean distance; radii above 32; the image border as a boundary.
+ * Not covered: Euclidean distance.  Boundary IoU proper, radii above 32 and the image border as a boundary are the next entry point's.
  * ------------------------------------------------------------------------------------------- */
 size_t arseg_label_bands_workspace_bytes(int N, int H, int W);
 int arseg_label_bands_fwd(const int64_t *label, const int32_t *pred, const int32_t *group, const int *radii, int n_bands, uint8_t *band_out,
                           int64_t band_pitch, int64_t band_n_stride, int64_t *hist, int N, int n_groups, int n_cls, int H, int W,
                           int ignore_label, void *workspace, size_t workspace_bytes, arseg_stream_t stream);
+
+/* ---------------------------------------------------------------------------------------------
+ * Boundary IoU counts from joint label / prediction bands (csrc/bands.hip; Cheng et al., "Boundary IoU", CVPR 2021): per class the
+ * inner boundary band of the ground-truth mask, that of the predicted mask, and their intersection, in disjoint bands of width.  No
+ * reference counterpart.
+ * Bytes.     label is int64 [N][H][W], pred int32 [N][H][W], both contiguous and both required.  A label becomes a byte exactly as in
+ *            arseg_label_bands_fwd (itself if 0 <= label < n_cls and label != ignore_label, else 255); a prediction becomes a byte:
+ *            itself if 0 <= pred < n_cls, else 255.  Each plane's bytes alone decide that plane's distances.
+ * Distance.  D(p) on a byte plane is arseg_label_bands_fwd's Chebyshev distance: the smallest r >= 1 whose (2r+1) x (2r+1) window at
+ *            p, clipped to the image, holds another byte.  With border != 0, D(p) is also at most min(x + 1, y + 1, W - x, H - y), the
+ *            smallest r whose window leaves the image: the image border is a boundary, as under the zero-padded erosion of the
+ *            published implementation.  With border == 0, D on the label plane is arseg_label_bands_fwd's, bit for bit.
+ * Bands.     radii is a HOST array of n_bands ints, strictly ascending, 1 <= radii[k] <= 64, 1 <= n_bands <= 8.  band(p) is the smallest
+ *            k with D(p) <= radii[k], and n_bands for the interior; bg is the band on the label plane, bp that on the prediction plane.
+ * Counts.    group as in arseg_label_bands_fwd (int32 [N] on the device; NULL only with n_groups == 1).  A pixel counts if its label
+ *            byte is not 255, its prediction byte is not 255 and its frame's group id g is in [0, n_groups).  counts is int64
+ *            [n_groups][3][n_bands + 1][n_cls], ACCUMULATED; a counting pixel adds 1 to counts[g][0][bg][label] and to
+ *            counts[g][1][bp][pred], and, if label == pred, to counts[g][2][max(bg, bp)][label].  Void-labelled pixels count nowhere
+ *            and are a boundary for their neighbours on the label plane, as predictions outside the classes are on theirs.  The bands
+ *            are disjoint; cumulating them is the host's business: at radii[k], with I, G and P the sums over the bands 0 .. k of rows
+ *            2, 0 and 1, the Boundary IoU of class c is I / (G + P - I).  Summed over all n_bands + 1 bands, rows 0, 1 and 2 are the
+ *            row sums, column sums and diagonal of arseg_argmax_confusion_grouped_fwd's hist on the same inputs, exactly.
+ * label_band_out, pred_band_out: uint8, bg and bp of row y of frame n at out + n * n_stride + y * pitch (bytes; pitch >= W,
+ *            n_stride >= 0); OVERWRITTEN, for every frame and pixel.  Each may be NULL; counts may be NULL if a plane is given.
+ * workspace: the caller's, 2-byte aligned, >= arseg_boundary_iou_workspace_bytes(N, H, W) bytes (else ARSEG_EWORKSPACE): two 16-bit
+ *            words per pixel, 4 N H W bytes rounded up to 16 (0 for dimensions the entry point refuses; a size that does not fit
+ *            size_t gives SIZE_MAX).  Its contents are scratch.
+ * 2 launches (rows: both planes' bytes and in-row distances; columns: the distances, the bands, the tally), sized on the host; no
+ *            workgroup waits for another.  Enqueue only: no allocation, no synchronisation; capturable in a HIP graph.  The buffers
+ *            must not overlap.  Malformed labels and predictions only ever give the byte 255; nothing outside the caller's buffers is
+ *            read or written, and every loop is bounded.
+ * ARSEG_EINVAL, before any launch and before ARSEG_EWORKSPACE: a null label, pred, radii or workspace; non-positive N, H or W; H > 16384
+ *            or W > 16384; n_bands outside 1..8, a radius outside 1..64 or radii that do not ascend strictly; n_cls outside 1..32;
+ *            n_groups < 1; a null group with n_groups > 1; border outside {0, 1}; all three outputs null; with a plane, its pitch < W
+ *            or a negative n_stride; label or counts not 8-byte aligned, pred or group not 4-byte aligned, the workspace not 2-byte
+ *            aligned.
+ * Not covered: Euclidean distance; radii above 64; Boundary AP / PQ; min(IoU, Boundary IoU); fusion into the argmax launch.
+ * ------------------------------------------------------------------------------------------- */
+size_t arseg_boundary_iou_workspace_bytes(int N, int H, int W);
+int arseg_boundary_iou_fwd(const int64_t *label, const int32_t *pred, const int32_t *group, const int *radii, int n_bands, int border,
+                           uint8_t *label_band_out, int64_t label_band_pitch, int64_t label_band_n_stride, uint8_t *pred_band_out,
+                           int64_t pred_band_pitch, int64_t pred_band_n_stride, int64_t *counts, int N, int n_groups, int n_cls, int H,
+                           int W, int ignore_label, void *workspace, size_t workspace_bytes, arseg_stream_t stream);
 
 /* ---------------------------------------------------------------------------------------------
  * Measurement aids (no reference counterpart; BASELINE.md section 3: roofline fractions are reported against the datasheet peaks AND
