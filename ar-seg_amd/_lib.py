@@ -8,7 +8,7 @@ from __future__ import annotations
 import ctypes
 import functools
 import os
-from ctypes import POINTER, Structure, c_char_p, c_double, c_float, c_int, c_int16, c_int32, c_int64, c_size_t, c_uint64, c_void_p
+from ctypes import POINTER, Structure, c_char_p, c_double, c_float, c_int, c_int16, c_int32, c_int64, c_size_t, c_uint8, c_uint64, c_void_p
 
 _HERE = os.path.dirname(os.path.abspath(__file__))
 LIB_PATH = os.environ.get("ARSEG_HIP_LIB", os.path.join(_HERE, "lib", "libarseg_hip.so"))   # env override: kernel experiments
@@ -30,6 +30,8 @@ MVR_BI_LIST0, MVR_BI_NEAR, MVR_BI_MEAN = 0, 1, 2
 CONF_TOP1, CONF_MARGIN = 0, 1
 CONF_NSTATS = 2 + 32      # ARSEG_CONF_NSTATS: sum of codes, low count, 32 class areas
 TC_NSTATS = 3 + 3 * 32    # ARSEG_TC_NSTATS: compared, outside, void, then 32 each of cur_k, ref_k, inter_k
+LINK_INTRA, LINK_UNCOVERED, LINK_CLAMPED = 1, 2, 4      # ARSEG_LINK_*: flag bits of a link byte; bits 4..7 = hops to the keyframe
+LINK_NSTATS = 4 + 16      # ARSEG_LINK_NSTATS: pixels with INTRA, UNCOVERED, CLAMPED, any flag, then 16 hop bins
 FILL_NSTATS = 3 + 3 * 256  # ARSEG_FILL_NSTATS: gaps, excess, changed, then 256 each of ref_area, fill_area, both
 
 
@@ -142,6 +144,9 @@ PROTOTYPES = {
     "arseg_mv_records_bi_workspace_bytes": (c_size_t, [c_int, c_int]),
     "arseg_mv_records_bi_reset": (c_int, [_P, _P, c_size_t, c_int, c_int, _STREAM]),
     "arseg_mv_records_bi_step_fwd": (c_int, [_P, c_int, _P, c_int, c_int, c_uint64, c_int, _P, c_size_t, c_int, c_int, c_int, _STREAM]),
+    "arseg_mv_link_reset": (c_int, [_P, _P, c_int, c_int, c_int, _STREAM]),
+    "arseg_mv_records_step_link_fwd": (c_int, [_P, c_int, _P, c_int, c_int, _P, c_size_t, c_int, c_int, c_int, _P, _P, _STREAM]),
+    "arseg_mv_records_bi_step_link_fwd": (c_int, [_P, c_int, _P, c_int, c_int, c_uint64, c_int, _P, c_size_t, c_int, c_int, c_int, _P, _P, _STREAM]),
     "arseg_nchw_to_nhwc_fwd": (c_int, [_P, _P, c_int, c_int, c_int, c_int, _STREAM]),
     "arseg_nhwc_to_nchw_fwd": (c_int, [_P, c_int, _P, c_int, c_int, c_int, _STREAM]),
     "arseg_argmax_confusion_fwd": (c_int, [_P, _P, _P, _P] + [c_int] * 8 + [_STREAM]),
@@ -151,6 +156,8 @@ PROTOTYPES = {
     "arseg_segment_confidence_fwd": (c_int, [_P] + [c_int] * 9 + [_P, _P, c_int64, c_int64, _P, c_int64, c_int64, _P, _STREAM]),
     "arseg_segment_consistency_fwd": (c_int, [_P] + [c_int] * 7 + [_P, c_int64, c_int64, _P, _P, _P, c_int64, c_int64, _P, c_int64, c_int64, _P, _STREAM]),
     "arseg_labels_consistency_fwd": (c_int, [_P, c_int64, c_int64] + [c_int] * 4 + [_P, c_int64, c_int64, _P, _P, c_int64, c_int64, _P, _STREAM]),
+    "arseg_labels_consistency_linked_fwd": (c_int, [_P, c_int64, c_int64] + [c_int] * 4 + [_P, c_int64, c_int64, _P, _P, c_int64, c_int64, _P,
+                                                    _P, c_int64, c_int64, c_uint8, _P, _STREAM]),
     "arseg_labels_rle_fwd": (c_int, [_P, c_int64, c_int64, c_int, c_int, c_int, _P, _P, c_int64, _STREAM]),
     "arseg_rle_decode_fwd": (c_int, [_P, _P, c_int64, c_int, c_int, c_int, _P, c_int64, c_int64, _STREAM]),
     "arseg_rle_regions_workspace_bytes": (c_size_t, [c_int, c_int64]),

@@ -12,6 +12,8 @@
 // its counters belong to one row of `stats`: compared / outside / void live in registers and are added up across the wave once per frame,
 // the 3 x 32 class counters are counted in LDS, and a workgroup issues one 64-bit vector atomic add per non-zero counter and frame.  All
 // counters are integers: the result does not depend on the order of the atomics.
+// arseg_labels_consistency_linked_fwd: one more instantiation of the plane kernel, which reads the chain's link byte of a pixel first and leaves
+// a flagged pixel out of the comparison (change 128, no counter of stats, its own count per frame).
 #include "arseg_device.h"
 
 namespace {
@@ -26,6 +28,11 @@ struct TcP {
     long long src_pitch, src_ns, ref_pitch, ref_ns, lab_pitch, lab_ns, chg_pitch, chg_ns;          // bytes per row / per image
     int N, n_cls, h, w, H, W, align;
     uint8_t lut[32];                                    // lut ? lut[k] : k
+    // the linked plane form only (behind everything the other instantiations read):
+    const uint8_t *link;                                // a link plane per frame (csrc/mv_records.hip)
+    long long link_pitch, link_ns;
+    unsigned long long *unlinked;                       // [N]
+    unsigned link_mask;
 };
 
 struct TcLds {
@@ -124,7 +131,8 @@ __device__ __forceinline__ void tc_flush(TcLds &s, unsigned long long *row, unsi
 }
 
 // ------------------------------------------------------------------ per-pixel routes: h == H && w == W, any bilinear resize, or (PLANE) a byte load
-template <bool PLANE>
+// LINKED (plane form): a pixel whose link byte has a bit of link_mask is unlinked -- decided first, nothing else of it is read
+template <bool PLANE, bool LINKED = false>
 __global__ __launch_bounds__(256) void consistency_pixel_kernel(const TcP p) {
     __shared__ TcLds s;
     tc_stage(p, s);
@@ -133,14 +141,35 @@ __global__ __launch_bounds__(256) void consistency_pixel_kernel(const TcP p) {
     const bool same = (p.h == p.H && p.w == p.W);
     for (int n = blockIdx.y; n < p.N; n += gridDim.y) {
         unsigned long long cmp = 0, out = 0, vd = 0;
+        [[maybe_unused]] unsigned long long unl = 0;
         for (long long idx = (long long)blockIdx.x * blockDim.x + threadIdx.x; idx < total; idx += (long long)gridDim.x * blockDim.x) {
             const int ox = (int)(idx % p.W), oy = (int)(idx / p.W);
+            if constexpr (LINKED) {
+                if (p.link[(size_t)n * p.link_ns + (size_t)oy * p.link_pitch + ox] & p.link_mask) {
+                    if (p.chg) p.chg[(size_t)n * p.chg_ns + (size_t)oy * p.chg_pitch + ox] = 128;
+                    ++unl;
+                    continue;
+                }
+            }
             int k;
             if constexpr (PLANE) k = p.src[(size_t)n * p.src_ns + (size_t)oy * p.src_pitch + ox];
             else k = arseg_label_pixel(p.logits, n, oy, ox, p.n_cls, p.h, p.w, p.align, same, sy, sx);
             tc_emit<1>(p, s, n, oy, ox, &k, cmp, out, vd);
         }
         if (p.stats) tc_flush(s, p.stats + (size_t)n * ARSEG_TC_NSTATS, cmp, out, vd);
+        if constexpr (LINKED) {
+            if (p.unlinked) {                                        // registers -> wave -> LDS -> one atomic per workgroup and frame
+                __shared__ unsigned long long s_unl;
+                if (threadIdx.x == 0) s_unl = 0;
+                __syncthreads();
+#pragma unroll
+                for (int o = 32; o > 0; o >>= 1) unl += __shfl_xor(unl, o, 64);
+                if ((threadIdx.x & 63) == 0 && unl) atomicAdd(&s_unl, unl);
+                __syncthreads();
+                if (threadIdx.x == 0 && s_unl) atomicAdd(&p.unlinked[n], s_unl);
+                __syncthreads();                                     // s_unl is cleared again for the next frame
+            }
+        }
     }
 }
 
@@ -235,5 +264,25 @@ extern "C" int arseg_labels_consistency_fwd(const uint8_t *labels_in, int64_t in
     p.src = labels_in; p.src_pitch = in_pitch; p.src_ns = in_image_stride;
     p.h = H; p.w = W;
     hipLaunchKernelGGL((consistency_pixel_kernel<true>), tc_grid((long long)H * W, N, 1024), dim3(256), 0, arseg_stream(stream), p);
+    return arseg_launch_status();
+}
+
+extern "C" int arseg_labels_consistency_linked_fwd(const uint8_t *labels_in, int64_t in_pitch, int64_t in_image_stride, int N, int n_cls, int H, int W,
+                                                   const uint8_t *ref_labels, int64_t ref_pitch, int64_t ref_image_stride, const int16_t *mv_q,
+                                                   uint8_t *change_out, int64_t change_pitch, int64_t change_image_stride, int64_t *stats,
+                                                   const uint8_t *link, int64_t link_pitch, int64_t link_image_stride, uint8_t link_mask,
+                                                   int64_t *unlinked, arseg_stream_t stream) {
+    ARSEG_CHECK_PTR(labels_in); ARSEG_CHECK_PTR(link);
+    if (!change_out && !stats) return ARSEG_EINVAL;
+    if (in_pitch < (int64_t)W || in_image_stride < 0 || link_pitch < (int64_t)W || link_image_stride < 0) return ARSEG_EINVAL;
+    if (reinterpret_cast<uintptr_t>(unlinked) & 7u) return ARSEG_EINVAL;
+    TcP p = {};
+    const int rc = tc_common(p, N, n_cls, H, W, ref_labels, ref_pitch, ref_image_stride, mv_q, change_out, change_pitch, change_image_stride, stats);
+    if (rc != ARSEG_OK) return rc;
+    p.src = labels_in; p.src_pitch = in_pitch; p.src_ns = in_image_stride;
+    p.h = H; p.w = W;
+    p.link = link; p.link_pitch = link_pitch; p.link_ns = link_image_stride; p.link_mask = link_mask;
+    p.unlinked = reinterpret_cast<unsigned long long *>(unlinked);
+    hipLaunchKernelGGL((consistency_pixel_kernel<true, true>), tc_grid((long long)H * W, N, 1024), dim3(256), 0, arseg_stream(stream), p);
     return arseg_launch_status();
 }

@@ -10,9 +10,16 @@
 // out[f][y,x] = 4 (k2 - x, j2 - y) + (f2 > 0 ? out[f2][j2,k2] : 0) and mergeMotion's int4 link table (layers.hip) is not needed.
 // B-frames (arseg_mv_records_bi_*): two index maps, one per prediction list (reserved & 1), the same two kernels per frame; a frame links to
 // any frame already chained in this GOP (done_mask), before or after it in display order, and frames arrive in decode order.
+// Link bytes (arseg_mv_*_link_*): the compose kernels' LINK = true instantiations also write one byte per pixel -- intra / uncovered / clamped
+// at this hop or at any hop towards the keyframe, and the number of hops -- gathered from link[t] at the pixel merged[t] is gathered from, and
+// count them per frame: flag counts in registers, hop bins in LDS, one 64-bit atomic per non-zero counter and workgroup (consistency.hip's scheme).
 #include "arseg_device.h"
 
 constexpr int MVR_MAX_DIM = 8192;      // 4 * 8191 = 32764: the largest accumulated displacement still fits int16
+// The counted LINK launches: every workgroup ends with one 64-bit atomic per non-zero counter, all on the 160 bytes of one row of link_stats, and
+// those serialise in L2 (measured: ~20 000 of them, 2048 workgroups of 256 threads at 1024x2048, cost more than the rest of the kernel).  So few and
+// large workgroups: at most one of 1024 threads per CU of an MI355X.
+constexpr int MVL_THREADS = 1024, MVL_GRID_CAP = 256;
 constexpr int MVR_BAND = 256;          // frame rows per scatter band (blockIdx.y): bounds the pixels one wave covers of a frame-sized record
 
 // record = int16 x, y, w, h, mvx, mvy, ref, reserved, read as one int4 (little endian)
@@ -41,30 +48,88 @@ __global__ __launch_bounds__(256) void mv_records_scatter_kernel(const int4 *__r
     }
 }
 
-// one pixel of frame f: packed (dx, dy) int16 pair.  id outside [0, n): no record (intra).
+// link byte of a pixel from its own flags and the byte of its target (0 where the target is the keyframe): flags accumulate, hops count up to 15
+__device__ __forceinline__ unsigned mvl_byte(unsigned own, unsigned gathered) {
+    return ((own | gathered) & 7u) | (min(15u, 1u + (gathered >> 4)) << 4);
+}
+
+// this workgroup's share of one row of link_stats
+struct MvlCount {
+    unsigned *bins;                                                   // LDS [ARSEG_LINK_NSTATS], null: no statistics wanted
+    unsigned intra = 0, uncovered = 0, clamped = 0, any = 0;          // this lane's
+    unsigned hop = 0, len = 0;                                        // a stretch of equal hop counts not yet added
+    __device__ __forceinline__ void add(unsigned lk) {
+        intra += lk & 1u; uncovered += (lk >> 1) & 1u; clamped += (lk >> 2) & 1u; any += (lk & 7u) ? 1u : 0u;
+        if (len && hop != (lk >> 4)) flush();
+        hop = lk >> 4; ++len;
+    }
+    __device__ __forceinline__ void flush() {
+        if (len) atomicAdd(&bins[4 + hop], len);
+        len = 0;
+    }
+};
+
+__device__ __forceinline__ void mvl_count_begin(unsigned *bins) {
+    if (threadIdx.x < ARSEG_LINK_NSTATS) bins[threadIdx.x] = 0;
+    __syncthreads();
+}
+
+// registers -> wave -> LDS -> one 64-bit atomic per non-zero counter.  Every thread of the workgroup comes here.
+__device__ __forceinline__ void mvl_count_end(MvlCount &c, unsigned long long *row) {
+    c.flush();
+    unsigned v[4] = {c.intra, c.uncovered, c.clamped, c.any};
+#pragma unroll
+    for (int i = 0; i < 4; ++i) {
+#pragma unroll
+        for (int o = 32; o > 0; o >>= 1) v[i] += __shfl_xor(v[i], o, 64);
+        if ((threadIdx.x & 63) == 0 && v[i]) atomicAdd(&c.bins[i], v[i]);
+    }
+    __syncthreads();
+    if (threadIdx.x < ARSEG_LINK_NSTATS) {
+        const unsigned n = c.bins[threadIdx.x];
+        if (n) atomicAdd(&row[threadIdx.x], (unsigned long long)n);
+    }
+}
+
+// one pixel of frame f: packed (dx, dy) int16 pair.  id outside [0, n): no record (intra).  LINK: lk = the pixel's link byte.
+template <bool LINK>
 __device__ __forceinline__ unsigned mvr_compose(const int4 *__restrict__ rec, int n, int id, const unsigned *merged, int f, int x, int y, int H, int W,
-                                                int max_ref) {
+                                                int max_ref, const uint8_t *link, unsigned &lk) {
     int mx = 0, my = 0, ref = 0;                                      // intra: zero motion, previous frame
+    unsigned own = ARSEG_LINK_UNCOVERED;
     if (id >= 0 && id < n) {
         const int4 q = rec[id];
         const int r = rec_lo(q.w);
-        if (r >= 0 && r < max_ref) { mx = rec_lo(q.z); my = rec_hi(q.z); ref = r; }
+        own = ARSEG_LINK_INTRA;
+        if (r >= 0 && r < max_ref) { mx = rec_lo(q.z); my = rec_hi(q.z); ref = r; own = 0; }
     }
-    const int k2 = min(max(x + round_half_even_div4(mx), 0), W - 1), j2 = min(max(y + round_half_even_div4(my), 0), H - 1);
+    const int tx = x + round_half_even_div4(mx), ty = y + round_half_even_div4(my);
+    const int k2 = min(max(tx, 0), W - 1), j2 = min(max(ty, 0), H - 1);
     const int f2 = max(0, f - ref - 1);
     int dx = 4 * (k2 - x), dy = 4 * (j2 - y);
+    unsigned g = 0;
     if (f2 > 0) {                                                     // the target's own link, from the output of frame f2 < f
-        const unsigned p = merged[((size_t)f2 * H + j2) * W + k2];
+        const size_t at = ((size_t)f2 * H + j2) * W + k2;
+        const unsigned p = merged[at];
         dx += rec_lo((int)p); dy += rec_hi((int)p);
+        if constexpr (LINK) g = link[at];
     }
+    if constexpr (LINK) lk = mvl_byte(own | ((k2 != tx || j2 != ty) ? (unsigned)ARSEG_LINK_CLAMPED : 0u), g);
     return ((unsigned)dx & 0xffffu) | ((unsigned)dy << 16);
 }
 
-// merged / out: the same tensor (frames < f are read, frame f is written): no __restrict__
-template <bool VEC>
-__global__ __launch_bounds__(256) void mv_records_compose_kernel(const int4 *__restrict__ rec, int n, int *__restrict__ idx, const unsigned *merged, unsigned *out,
-                                                                 int f, int H, int W, int max_ref) {
+// merged / out: the same tensor (frames < f are read, frame f is written): no __restrict__.  LINK: link / link_out likewise (link_out = frame f of
+// link), stats = row f of link_stats or null; the 4-pixel form needs link_out 4-byte aligned.
+template <bool VEC, bool LINK>
+__global__ __launch_bounds__(LINK ? MVL_THREADS : 256) void mv_records_compose_kernel(const int4 *__restrict__ rec, int n, int *__restrict__ idx, const unsigned *merged, unsigned *out,
+                                                                 int f, int H, int W, int max_ref, const uint8_t *link, uint8_t *link_out,
+                                                                 unsigned long long *stats) {
     const int hw = H * W;
+    MvlCount cnt = {};
+    if constexpr (LINK) {
+        __shared__ unsigned bins[ARSEG_LINK_NSTATS];
+        if (stats) { cnt.bins = bins; mvl_count_begin(bins); }
+    }
     if constexpr (VEC) {                                              // hw % 4 == 0, 16-byte aligned frames
         const int n4 = hw >> 2;
         for (int t = blockIdx.x * blockDim.x + threadIdx.x; t < n4; t += gridDim.x * blockDim.x) {
@@ -72,20 +137,35 @@ __global__ __launch_bounds__(256) void mv_records_compose_kernel(const int4 *__r
             int y = (t * 4) / W, x = t * 4 - y * W;
             const int ids[4] = {id.x, id.y, id.z, id.w};
             u32x4 o;
+            unsigned lw = 0;
 #pragma unroll
             for (int k = 0; k < 4; ++k) {
-                o[k] = mvr_compose(rec, n, ids[k], merged, f, x, y, H, W, max_ref);
+                unsigned lk = 0;
+                o[k] = mvr_compose<LINK>(rec, n, ids[k], merged, f, x, y, H, W, max_ref, link, lk);
+                if constexpr (LINK) {
+                    lw |= lk << (8 * k);
+                    if (cnt.bins) cnt.add(lk);
+                }
                 if (++x == W) { x = 0; ++y; }
             }
             reinterpret_cast<u32x4 *>(out)[t] = o;
+            if constexpr (LINK) reinterpret_cast<unsigned *>(link_out)[t] = lw;
             reinterpret_cast<int4 *>(idx)[t] = make_int4(-1, -1, -1, -1);
         }
     } else {
         for (int pix = blockIdx.x * blockDim.x + threadIdx.x; pix < hw; pix += gridDim.x * blockDim.x) {
             const int y = pix / W, x = pix - y * W;
-            out[pix] = mvr_compose(rec, n, idx[pix], merged, f, x, y, H, W, max_ref);
+            unsigned lk = 0;
+            out[pix] = mvr_compose<LINK>(rec, n, idx[pix], merged, f, x, y, H, W, max_ref, link, lk);
+            if constexpr (LINK) {
+                link_out[pix] = (uint8_t)lk;
+                if (cnt.bins) cnt.add(lk);
+            }
             idx[pix] = -1;
         }
+    }
+    if constexpr (LINK) {
+        if (stats) mvl_count_end(cnt, stats);
     }
 }
 
@@ -104,14 +184,20 @@ __device__ __forceinline__ unsigned mvb_usable_refs(int f, unsigned long long do
     return m;
 }
 
-// link of one list: packed 4 (k2 - x, j2 - y) + (t > 0 ? merged[t][j2][k2] : 0)
-__device__ __forceinline__ unsigned mvb_link(int4 q, int t, const unsigned *merged, int x, int y, int H, int W) {
-    const int k2 = min(max(x + round_half_even_div4(rec_lo(q.z)), 0), W - 1), j2 = min(max(y + round_half_even_div4(rec_hi(q.z)), 0), H - 1);
+// link of one list: packed 4 (k2 - x, j2 - y) + (t > 0 ? merged[t][j2][k2] : 0).  LINK: lk = the list's link byte.
+template <bool LINK>
+__device__ __forceinline__ unsigned mvb_link(int4 q, int t, const unsigned *merged, int x, int y, int H, int W, const uint8_t *link, unsigned &lk) {
+    const int tx = x + round_half_even_div4(rec_lo(q.z)), ty = y + round_half_even_div4(rec_hi(q.z));
+    const int k2 = min(max(tx, 0), W - 1), j2 = min(max(ty, 0), H - 1);
     int dx = 4 * (k2 - x), dy = 4 * (j2 - y);
+    unsigned g = 0;
     if (t > 0) {
-        const unsigned m = merged[((size_t)t * H + j2) * W + k2];
+        const size_t at = ((size_t)t * H + j2) * W + k2;
+        const unsigned m = merged[at];
         dx += rec_lo((int)m); dy += rec_hi((int)m);
+        if constexpr (LINK) g = link[at];
     }
+    if constexpr (LINK) lk = mvl_byte((k2 != tx || j2 != ty) ? (unsigned)ARSEG_LINK_CLAMPED : 0u, g);
     return ((unsigned)dx & 0xffffu) | ((unsigned)dy << 16);
 }
 
@@ -121,8 +207,10 @@ __device__ __forceinline__ int mvb_mean(int a, int b) {               // (a + b)
 }
 
 // one pixel of frame f.  id0 / id1: the winners of list 0 / 1, outside [0, n) = none.  p: the nearest chained frame before f (intra target).
+// LINK: lk = the pixel's link byte (both lists under MEAN: the flags of both, the larger hop count).
+template <bool LINK>
 __device__ __forceinline__ unsigned mvb_compose(const int4 *__restrict__ rec, int n, int id0, int id1, const unsigned *merged, int f, int p, unsigned usable,
-                                                int policy, int pix, int x, int y, int H, int W) {
+                                                int policy, int pix, int x, int y, int H, int W, const uint8_t *link, unsigned &lk) {
     int4 q0 = make_int4(0, 0, 0, 0), q1 = q0;
     bool u0 = false, u1 = false;
     if ((unsigned)id0 < (unsigned)n) {
@@ -140,20 +228,35 @@ __device__ __forceinline__ unsigned mvb_compose(const int4 *__restrict__ rec, in
         if (policy == ARSEG_MVR_BI_NEAR && abs(t1 - f) < abs(t0 - f)) u0 = false;
         else u1 = false;
     }
-    if (!u0 && !u1) return p > 0 ? merged[(size_t)p * H * W + pix] : 0u;      // intra: zero motion to frame p
-    const unsigned l0 = u0 ? mvb_link(q0, t0, merged, x, y, H, W) : 0u, l1 = u1 ? mvb_link(q1, t1, merged, x, y, H, W) : 0u;
+    if (!u0 && !u1) {                                                 // intra: zero motion to frame p
+        if constexpr (LINK) {
+            const bool won = (unsigned)id0 < (unsigned)n || (unsigned)id1 < (unsigned)n;
+            lk = mvl_byte(won ? ARSEG_LINK_INTRA : ARSEG_LINK_UNCOVERED, p > 0 ? (unsigned)link[(size_t)p * H * W + pix] : 0u);
+        }
+        return p > 0 ? merged[(size_t)p * H * W + pix] : 0u;
+    }
+    unsigned k0 = 0, k1 = 0;
+    const unsigned l0 = u0 ? mvb_link<LINK>(q0, t0, merged, x, y, H, W, link, k0) : 0u, l1 = u1 ? mvb_link<LINK>(q1, t1, merged, x, y, H, W, link, k1) : 0u;
+    if constexpr (LINK) lk = ((k0 | k1) & 7u) | (max(k0 >> 4, k1 >> 4) << 4);          // an unused list left its byte at 0
     if (u0 && u1) return ((unsigned)mvb_mean(rec_lo((int)l0), rec_lo((int)l1)) & 0xffffu) | ((unsigned)mvb_mean(rec_hi((int)l0), rec_hi((int)l1)) << 16);
     return u0 ? l0 : l1;
 }
 
-// idx: two maps of hw words (list 0, list 1).  merged / out: the same tensor (frames in `done` are read, frame f, not in `done`, is written)
-template <bool VEC>
-__global__ __launch_bounds__(256) void mv_records_bi_compose_kernel(const int4 *__restrict__ rec, int n, int *__restrict__ idx, const unsigned *merged, unsigned *out,
-                                                                    int f, unsigned long long done, int policy, int H, int W, int max_ref) {
+// idx: two maps of hw words (list 0, list 1).  merged / out: the same tensor (frames in `done` are read, frame f, not in `done`, is written).
+// LINK: as in mv_records_compose_kernel.
+template <bool VEC, bool LINK>
+__global__ __launch_bounds__(LINK ? MVL_THREADS : 256) void mv_records_bi_compose_kernel(const int4 *__restrict__ rec, int n, int *__restrict__ idx, const unsigned *merged, unsigned *out,
+                                                                    int f, unsigned long long done, int policy, int H, int W, int max_ref,
+                                                                    const uint8_t *link, uint8_t *link_out, unsigned long long *stats) {
     const int hw = H * W;
     const unsigned usable = mvb_usable_refs(f, done, max_ref);
     const int p = 63 - __clzll((long long)(done & ((1ull << f) - 1ull)));     // bit 0 of done is set, 1 <= f < 64
     int *idx1 = idx + hw;
+    MvlCount cnt = {};
+    if constexpr (LINK) {
+        __shared__ unsigned bins[ARSEG_LINK_NSTATS];
+        if (stats) { cnt.bins = bins; mvl_count_begin(bins); }
+    }
     if constexpr (VEC) {                                              // hw % 4 == 0, 16-byte aligned frames
         const int n4 = hw >> 2;
         for (int t = blockIdx.x * blockDim.x + threadIdx.x; t < n4; t += gridDim.x * blockDim.x) {
@@ -161,22 +264,37 @@ __global__ __launch_bounds__(256) void mv_records_bi_compose_kernel(const int4 *
             int y = (t * 4) / W, x = t * 4 - y * W;
             const int ia[4] = {a.x, a.y, a.z, a.w}, ib[4] = {b.x, b.y, b.z, b.w};
             u32x4 o;
+            unsigned lw = 0;
 #pragma unroll
             for (int k = 0; k < 4; ++k) {
-                o[k] = mvb_compose(rec, n, ia[k], ib[k], merged, f, p, usable, policy, t * 4 + k, x, y, H, W);
+                unsigned lk = 0;
+                o[k] = mvb_compose<LINK>(rec, n, ia[k], ib[k], merged, f, p, usable, policy, t * 4 + k, x, y, H, W, link, lk);
+                if constexpr (LINK) {
+                    lw |= lk << (8 * k);
+                    if (cnt.bins) cnt.add(lk);
+                }
                 if (++x == W) { x = 0; ++y; }
             }
             reinterpret_cast<u32x4 *>(out)[t] = o;
+            if constexpr (LINK) reinterpret_cast<unsigned *>(link_out)[t] = lw;
             reinterpret_cast<int4 *>(idx)[t] = make_int4(-1, -1, -1, -1);
             reinterpret_cast<int4 *>(idx1)[t] = make_int4(-1, -1, -1, -1);
         }
     } else {
         for (int pix = blockIdx.x * blockDim.x + threadIdx.x; pix < hw; pix += gridDim.x * blockDim.x) {
             const int y = pix / W, x = pix - y * W;
-            out[pix] = mvb_compose(rec, n, idx[pix], idx1[pix], merged, f, p, usable, policy, pix, x, y, H, W);
+            unsigned lk = 0;
+            out[pix] = mvb_compose<LINK>(rec, n, idx[pix], idx1[pix], merged, f, p, usable, policy, pix, x, y, H, W, link, lk);
+            if constexpr (LINK) {
+                link_out[pix] = (uint8_t)lk;
+                if (cnt.bins) cnt.add(lk);
+            }
             idx[pix] = -1;
             idx1[pix] = -1;
         }
+    }
+    if constexpr (LINK) {
+        if (stats) mvl_count_end(cnt, stats);
     }
 }
 
@@ -233,23 +351,67 @@ extern "C" int arseg_mv_records_reset(int16_t *merged, void *workspace, size_t w
     return arseg_launch_status();
 }
 
-extern "C" int arseg_mv_records_step_fwd(const int16_t *records, int n_records, int16_t *merged, int f, int gop, void *workspace, size_t workspace_bytes,
-                                         int H, int W, int max_ref, arseg_stream_t stream) {
+// launch geometry of a compose pass over `total` items: the plain one, or the counted one (see MVL_THREADS)
+static void mvl_geometry(long long total, bool counted, dim3 &grid, dim3 &block) {
+    block = dim3(counted ? MVL_THREADS : 256);
+    grid = dim3(counted ? arseg_grid_for((total + 3) / 4, MVL_GRID_CAP) : arseg_grid_for(total));          // (total + 3) / 4 items of 256 = total of 1024
+}
+
+// link == null: the plain step; else the LINK instantiations, which also write frame f of link and add to row f of link_stats (may be null)
+static int mvr_step(const int16_t *records, int n_records, int16_t *merged, int f, int gop, void *workspace, size_t workspace_bytes, int H, int W, int max_ref,
+                    uint8_t *link, int64_t *link_stats, arseg_stream_t stream) {
     ARSEG_CHECK_PTR(merged);
     const int bad = mvr_check_frame(records, n_records, workspace, workspace_bytes, H, W);
     if (bad) return bad;
     if (max_ref < 1 || max_ref > 16 || f < 1 || f >= gop || (reinterpret_cast<uintptr_t>(merged) & 3u)) return ARSEG_EINVAL;
+    if (reinterpret_cast<uintptr_t>(link_stats) & 7u) return ARSEG_EINVAL;
     hipStream_t st = arseg_stream(stream);
     int *idx = reinterpret_cast<int *>(workspace);
     const int hw = H * W;
     const unsigned *m = reinterpret_cast<const unsigned *>(merged);
     unsigned *out = reinterpret_cast<unsigned *>(merged) + (size_t)f * hw;
+    uint8_t *lout = link ? link + (size_t)f * hw : nullptr;
+    unsigned long long *row = link_stats ? reinterpret_cast<unsigned long long *>(link_stats) + (size_t)f * ARSEG_LINK_NSTATS : nullptr;
     mvr_scatter(records, n_records, idx, H, W, st);
     const int4 *rec = reinterpret_cast<const int4 *>(records);
-    if (hw % 4 == 0 && ARSEG_ALIGNED16(merged))
-        hipLaunchKernelGGL(mv_records_compose_kernel<true>, dim3(arseg_grid_for(hw / 4)), dim3(256), 0, st, rec, n_records, idx, m, out, f, H, W, max_ref);
+    const bool vec = hw % 4 == 0 && ARSEG_ALIGNED16(merged) && !(reinterpret_cast<uintptr_t>(link) & 3u);
+    dim3 grid, block;
+    mvl_geometry(vec ? hw / 4 : hw, link_stats != nullptr, grid, block);
+    if (vec && link)
+        hipLaunchKernelGGL((mv_records_compose_kernel<true, true>), grid, block, 0, st, rec, n_records, idx, m, out, f, H, W, max_ref, link, lout, row);
+    else if (link)
+        hipLaunchKernelGGL((mv_records_compose_kernel<false, true>), grid, block, 0, st, rec, n_records, idx, m, out, f, H, W, max_ref, link, lout, row);
+    else if (vec)
+        hipLaunchKernelGGL((mv_records_compose_kernel<true, false>), grid, block, 0, st, rec, n_records, idx, m, out, f, H, W, max_ref, link, lout, row);
     else
-        hipLaunchKernelGGL(mv_records_compose_kernel<false>, dim3(arseg_grid_for(hw)), dim3(256), 0, st, rec, n_records, idx, m, out, f, H, W, max_ref);
+        hipLaunchKernelGGL((mv_records_compose_kernel<false, false>), grid, block, 0, st, rec, n_records, idx, m, out, f, H, W, max_ref, link, lout, row);
+    return arseg_launch_status();
+}
+
+extern "C" int arseg_mv_records_step_fwd(const int16_t *records, int n_records, int16_t *merged, int f, int gop, void *workspace, size_t workspace_bytes,
+                                         int H, int W, int max_ref, arseg_stream_t stream) {
+    return mvr_step(records, n_records, merged, f, gop, workspace, workspace_bytes, H, W, max_ref, nullptr, nullptr, stream);
+}
+
+extern "C" int arseg_mv_records_step_link_fwd(const int16_t *records, int n_records, int16_t *merged, int f, int gop, void *workspace, size_t workspace_bytes,
+                                              int H, int W, int max_ref, uint8_t *link, int64_t *link_stats, arseg_stream_t stream) {
+    ARSEG_CHECK_PTR(link);
+    return mvr_step(records, n_records, merged, f, gop, workspace, workspace_bytes, H, W, max_ref, link, link_stats, stream);
+}
+
+// link[0] = 0 (the keyframe links to itself: no flag, no hop), every row of link_stats = 0
+__global__ __launch_bounds__(256) void mv_link_reset_kernel(uint8_t *__restrict__ link, int hw, unsigned long long *__restrict__ stats, int n_stats) {
+    for (int i = blockIdx.x * blockDim.x + threadIdx.x; i < hw; i += gridDim.x * blockDim.x) link[i] = 0;
+    if (stats != nullptr)
+        for (int i = blockIdx.x * blockDim.x + threadIdx.x; i < n_stats; i += gridDim.x * blockDim.x) stats[i] = 0;
+}
+
+extern "C" int arseg_mv_link_reset(uint8_t *link, int64_t *link_stats, int gop, int H, int W, arseg_stream_t stream) {
+    ARSEG_CHECK_PTR(link);
+    if (gop < 1 || gop > (1 << 20) || H <= 0 || W <= 0 || H > MVR_MAX_DIM || W > MVR_MAX_DIM) return ARSEG_EINVAL;
+    if (reinterpret_cast<uintptr_t>(link_stats) & 7u) return ARSEG_EINVAL;
+    hipLaunchKernelGGL(mv_link_reset_kernel, dim3(arseg_grid_for((long long)H * W)), dim3(256), 0, arseg_stream(stream), link, H * W,
+                       reinterpret_cast<unsigned long long *>(link_stats), gop * ARSEG_LINK_NSTATS);
     return arseg_launch_status();
 }
 
@@ -282,27 +444,50 @@ extern "C" int arseg_mv_records_bi_reset(int16_t *merged, void *workspace, size_
     return arseg_launch_status();
 }
 
-extern "C" int arseg_mv_records_bi_step_fwd(const int16_t *records, int n_records, int16_t *merged, int f, int gop, uint64_t done_mask, int policy,
-                                            void *workspace, size_t workspace_bytes, int H, int W, int max_ref, arseg_stream_t stream) {
+static int mvb_step(const int16_t *records, int n_records, int16_t *merged, int f, int gop, uint64_t done_mask, int policy, void *workspace,
+                    size_t workspace_bytes, int H, int W, int max_ref, uint8_t *link, int64_t *link_stats, arseg_stream_t stream) {
     ARSEG_CHECK_PTR(merged);
     const int bad = mvr_check_frame(records, n_records, workspace, workspace_bytes, H, W, 2);
     if (bad) return bad;
     if (max_ref < 1 || max_ref > 16 || f < 1 || f >= gop || gop > 64 || (reinterpret_cast<uintptr_t>(merged) & 3u)) return ARSEG_EINVAL;
     if (!(done_mask & 1u) || ((done_mask >> f) & 1u) || (gop < 64 && (done_mask >> gop) != 0)) return ARSEG_EINVAL;
-    if (policy < ARSEG_MVR_BI_LIST0 || policy > ARSEG_MVR_BI_MEAN) return ARSEG_EINVAL;
+    if (policy < ARSEG_MVR_BI_LIST0 || policy > ARSEG_MVR_BI_MEAN || (reinterpret_cast<uintptr_t>(link_stats) & 7u)) return ARSEG_EINVAL;
     hipStream_t st = arseg_stream(stream);
     int *idx = reinterpret_cast<int *>(workspace);
     const int hw = H * W;
     const unsigned *m = reinterpret_cast<const unsigned *>(merged);
     unsigned *out = reinterpret_cast<unsigned *>(merged) + (size_t)f * hw;
+    uint8_t *lout = link ? link + (size_t)f * hw : nullptr;
+    unsigned long long *row = link_stats ? reinterpret_cast<unsigned long long *>(link_stats) + (size_t)f * ARSEG_LINK_NSTATS : nullptr;
     const unsigned long long done = done_mask;
     mvr_scatter<true>(records, n_records, idx, H, W, st);
     const int4 *rec = reinterpret_cast<const int4 *>(records);
-    if (hw % 4 == 0 && ARSEG_ALIGNED16(merged))
-        hipLaunchKernelGGL(mv_records_bi_compose_kernel<true>, dim3(arseg_grid_for(hw / 4)), dim3(256), 0, st, rec, n_records, idx, m, out, f, done, policy, H, W,
-                           max_ref);
+    const bool vec = hw % 4 == 0 && ARSEG_ALIGNED16(merged) && !(reinterpret_cast<uintptr_t>(link) & 3u);
+    dim3 grid, block;
+    mvl_geometry(vec ? hw / 4 : hw, link_stats != nullptr, grid, block);
+    if (vec && link)
+        hipLaunchKernelGGL((mv_records_bi_compose_kernel<true, true>), grid, block, 0, st, rec, n_records, idx, m, out, f, done, policy, H, W, max_ref, link,
+                           lout, row);
+    else if (link)
+        hipLaunchKernelGGL((mv_records_bi_compose_kernel<false, true>), grid, block, 0, st, rec, n_records, idx, m, out, f, done, policy, H, W, max_ref, link,
+                           lout, row);
+    else if (vec)
+        hipLaunchKernelGGL((mv_records_bi_compose_kernel<true, false>), grid, block, 0, st, rec, n_records, idx, m, out, f, done, policy, H, W, max_ref, link,
+                           lout, row);
     else
-        hipLaunchKernelGGL(mv_records_bi_compose_kernel<false>, dim3(arseg_grid_for(hw)), dim3(256), 0, st, rec, n_records, idx, m, out, f, done, policy, H, W,
-                           max_ref);
+        hipLaunchKernelGGL((mv_records_bi_compose_kernel<false, false>), grid, block, 0, st, rec, n_records, idx, m, out, f, done, policy, H, W, max_ref, link,
+                           lout, row);
     return arseg_launch_status();
+}
+
+extern "C" int arseg_mv_records_bi_step_fwd(const int16_t *records, int n_records, int16_t *merged, int f, int gop, uint64_t done_mask, int policy,
+                                            void *workspace, size_t workspace_bytes, int H, int W, int max_ref, arseg_stream_t stream) {
+    return mvb_step(records, n_records, merged, f, gop, done_mask, policy, workspace, workspace_bytes, H, W, max_ref, nullptr, nullptr, stream);
+}
+
+extern "C" int arseg_mv_records_bi_step_link_fwd(const int16_t *records, int n_records, int16_t *merged, int f, int gop, uint64_t done_mask, int policy,
+                                                 void *workspace, size_t workspace_bytes, int H, int W, int max_ref, uint8_t *link, int64_t *link_stats,
+                                                 arseg_stream_t stream) {
+    ARSEG_CHECK_PTR(link);
+    return mvb_step(records, n_records, merged, f, gop, done_mask, policy, workspace, workspace_bytes, H, W, max_ref, link, link_stats, stream);
 }

@@ -217,10 +217,18 @@ def consistency(logits, ref_labels, mv_q, H, W, change_out=None, labels_out=None
     return change_out, labels_out, stats
 
 
-def consistency_of_planes(labels, ref_labels, mv_q, n_cls, change_out=None, stats=True):
+def consistency_of_planes(labels, ref_labels, mv_q, n_cls, change_out=None, stats=True, link=None,
+                          link_mask=_lib.LINK_INTRA | _lib.LINK_UNCOVERED, unlinked=None):
     """The plane form of ``consistency``: ``labels`` uint8 [N,H,W] in train ids (e.g. earlier ``labels8`` planes; a value >= n_cls is void)
     instead of logits -> (change8 | None, stats | None), one launch of ``ops.labels_consistency``.  With ``ref_labels`` [N,H,W] and a
-    per-frame field it serves consecutive-frame consistency."""
+    per-frame field it serves consecutive-frame consistency.
+
+    ``link`` (uint8 [N,H,W]: the frames' planes of ``ingest.MotionChain(track_links=True).link()``) gates the comparison: a pixel whose link
+    byte has a bit of ``link_mask`` (default: an intra block or an uncovered pixel somewhere along its chain, i.e. ``mv_q`` does not lead to
+    its counterpart) is *unlinked* -- change8 128, in no counter of ``stats``, counted per frame in ``unlinked`` (an int64 [N] tensor to
+    accumulate into, True for a zeroed one, None = not wanted) -- so that disocclusion does not read as drift.  One launch of
+    ``ops.labels_consistency_linked``; returns (change8 | None, stats | None, unlinked | None).  ``link=None``: the path and the results
+    above, ``link_mask`` and ``unlinked`` unused."""
     if not torch.is_tensor(labels) or labels.dim() != 3:
         raise ValueError("expected the label planes as a uint8 tensor [N,H,W]")
     N, H, W = labels.shape
@@ -228,8 +236,13 @@ def consistency_of_planes(labels, ref_labels, mv_q, n_cls, change_out=None, stat
     change_out = _plane_if_true(change_out, N, H, W, labels.device)
     if stats is True:
         stats = torch.zeros((N, _lib.TC_NSTATS), dtype=torch.int64, device=labels.device)
-    ops.labels_consistency(labels, ref_labels, mv_q, n_cls, change_out=change_out, stats=stats)
-    return change_out, stats
+    if link is None:
+        ops.labels_consistency(labels, ref_labels, mv_q, n_cls, change_out=change_out, stats=stats)
+        return change_out, stats
+    if unlinked is True:
+        unlinked = torch.zeros((N,), dtype=torch.int64, device=labels.device)
+    ops.labels_consistency_linked(labels, ref_labels, mv_q, n_cls, link, link_mask, change_out=change_out, stats=stats, unlinked=unlinked)
+    return change_out, stats, unlinked
 
 
 def tc_table(stats, n_cls):

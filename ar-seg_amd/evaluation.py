@@ -778,6 +778,43 @@ def alter_res_batch_consistency(lr_net, ref_ps, imgs, mv_qs, key_labels, scale=0
                               align_corners=not fused_up)
 
 
+def alter_res_batch_consistency_linked(lr_net, ref_ps, imgs, mv_qs, key_labels, scale=0.5, lut=None, change_out=True, labels_out=True, stats=True,
+                                       link=None, link_mask=_lib.LINK_INTRA | _lib.LINK_UNCOVERED):
+    """``alter_res_batch_consistency`` gated by the motion chain's link bytes: ``link`` uint8 [B,H,W], the frames' planes of
+    ``ingest.MotionChain(track_links=True).link()[1:]`` (the chain ``mv_qs`` came from), ``link_mask`` the flags that gate.  The same phase 1,
+    phase 2 and route decision; then TWO passes over the label plane instead of one over the logits: the fused tail writes the train-id
+    plane (``egress.labels8``), and ``egress.consistency_of_planes(..., link=link)`` compares it (the logits form has no linked variant).
+    A pixel with ``link & link_mask`` is unlinked: change8 128, in no counter of ``stats``, counted per frame in ``unlinked``.
+    -> (change8 | None, labels uint8 [B,H,W] | None, stats | None, unlinked int64 [B]).  ``labels_out`` True or a buffer: the labels as
+    ``alter_res_batch_consistency`` returns them (through ``lut`` when given, which costs one more tail launch: the comparison needs train
+    ids).  ``link_mask=0`` gives ``alter_res_batch_consistency``'s planes and statistics."""
+    from . import egress
+    if link is None:
+        raise _lib.ArsegError("alter_res_batch_consistency_linked: link is required (alter_res_batch_consistency is the form without)")
+    lr_net = _unwrap(lr_net)
+    B, _, H, W = imgs.shape
+    h, w = _downscale_hw(H, W, scale)
+    feat = lr_net.phase1_nhwc4(ops.ingest_input(imgs, h, w, lr_net.storage_dtype), aux=ops.config.aux_outputs)[-1]
+    fused_up = hasattr(lr_net, "out_upsample")
+    if fused_up:
+        lo, _ = lr_net.phase2_warp(feat, list(ref_ps), mv_qs, upsample=False)
+        if (8 * lo.shape[-2], 8 * lo.shape[-1]) != (H, W):
+            lo, fused_up = ops.resize_nchw(lo, 8 * lo.shape[-2], 8 * lo.shape[-1], _lib.BILINEAR, False), False
+    else:
+        lo, _ = lr_net.phase2_warp(feat, list(ref_ps), mv_qs)
+    keep = labels_out if torch.is_tensor(labels_out) and lut is None else None
+    train_ids = egress.labels8(lo, H, W, out=keep, align_corners=not fused_up)
+    change, stats, unlinked = egress.consistency_of_planes(train_ids, key_labels, mv_qs, lo.shape[1], change_out=change_out, stats=stats, link=link,
+                                                           link_mask=link_mask, unlinked=True)
+    if labels_out is None:
+        labels = None
+    elif lut is None:
+        labels = train_ids
+    else:
+        labels = egress.labels8(lo, H, W, lut=lut, out=labels_out if torch.is_tensor(labels_out) else None, align_corners=not fused_up)
+    return change, labels, stats, unlinked
+
+
 def alter_res_batch_rle(lr_net, ref_ps, imgs, mv_qs, capacity, scale=0.5, lut=None, labels_out=True):
     """``alter_res_batch_render``'s sibling for run-length coded masks: the same phase 1 and phase 2 and the same route decision
     (BiSeNet's 1/8-resolution head logits with align_corners=False when the frame is exactly 8x the head, align_corners=True otherwise),

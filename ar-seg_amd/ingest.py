@@ -364,6 +364,14 @@ def motion_vectors_to_records(dst_x, dst_y, w, h, motion_x, motion_y, motion_sca
     return np.ascontiguousarray(rec.astype(np.int16))
 
 
+LINK_INTRA, LINK_UNCOVERED, LINK_CLAMPED = _lib.LINK_INTRA, _lib.LINK_UNCOVERED, _lib.LINK_CLAMPED       # flag bits of a link byte (ARSEG_LINK_*)
+
+
+def link_hops(plane):
+    """Link bytes (a tensor or an array of uint8) -> the number of links from each pixel to the keyframe, 0..15 (15 = 15 or more)."""
+    return plane >> 4
+
+
 BIPRED = ("list0", "near", "mean")          # what a pixel reads when both of its lists are usable: ARSEG_MVR_BI_LIST0 / _NEAR / _MEAN
 
 
@@ -372,16 +380,19 @@ def _round_half_even_div4(v):
     return b + ((r > 2) | ((r == 2) & (b & 1 == 1)))
 
 
-def chain_records_numpy(pushes, H: int, W: int, gop: int, max_ref: int = 3, bipred: str = "list0") -> np.ndarray:
+def chain_records_numpy(pushes, H: int, W: int, gop: int, max_ref: int = 3, bipred: str = "list0", return_link: bool = False):
     """The two-list chain rule of include/arseg_hip.h (arseg_mv_records_bi_*) on the host, for callers without a GPU at hand: ``pushes`` is a
     list of ``(f, records int16 [n,8])`` in decode order; returns ``merged`` int16 [gop,H,W,2] with frame 0 = -1 and frames never pushed = 0.
-    What ``MotionChain(bidirectional=True, bipred=bipred)`` leaves in ``merged`` after the same pushes."""
+    What ``MotionChain(bidirectional=True, bipred=bipred)`` leaves in ``merged`` after the same pushes.  ``return_link=True``: returns
+    ``(merged, link)`` with ``link`` uint8 [gop,H,W], the link bytes of include/arseg_hip.h (arseg_mv_records_bi_step_link_fwd) -- what
+    ``MotionChain(..., track_links=True)`` leaves in ``link``; frames never pushed = 0."""
     H, W, gop, max_ref = int(H), int(W), int(gop), int(max_ref)
     if not (1 <= H <= 8192 and 1 <= W <= 8192) or not 2 <= gop <= 64 or not 1 <= max_ref <= 16 or bipred not in BIPRED:
         raise ValueError(f"chain_records_numpy: H, W in 1..8192, gop in 2..64, max_ref in 1..16, bipred in {BIPRED}; got {H}x{W}, gop {gop}, "
                          f"max_ref {max_ref}, bipred {bipred!r}")
     merged = np.zeros((gop, H, W, 2), dtype=np.int64)
     merged[0] = -1
+    links = np.zeros((gop, H, W), dtype=np.int64)
     done = np.zeros(gop + 17, dtype=bool)                               # a forward target reaches at most f + 16
     done[0] = True
     ys, xs = np.mgrid[0:H, 0:W]
@@ -399,7 +410,7 @@ def chain_records_numpy(pushes, H: int, W: int, gop: int, max_ref: int = 3, bipr
             x0, x1, y0, y1 = max(x, 0), min(x + w, W), max(y, 0), min(y + h, H)
             if x0 < x1 and y0 < y1:
                 winner[r[i, 7] & 1, y0:y1, x0:x1] = i
-        usable, target, link = [], [], []
+        usable, target, link, byte = [], [], [], []
         for l in (0, 1):
             q = r[np.maximum(winner[l], 0)] if r.shape[0] else np.zeros((H, W, 8), dtype=np.int64)
             ref = q[..., 6]
@@ -414,8 +425,14 @@ def chain_records_numpy(pushes, H: int, W: int, gop: int, max_ref: int = 3, bipr
             usable.append(ok)
             target.append(t)
             link.append(d + np.where((t > 0)[..., None], merged[t, j2, k2], 0))
+            clamped = (k2 != xs + _round_half_even_div4(q[..., 4])) | (j2 != ys + _round_half_even_div4(q[..., 5]))
+            g = np.where(t > 0, links[t, j2, k2], 0)
+            byte.append(((np.where(clamped, LINK_CLAMPED, 0) | g) & 7) | (np.minimum(15, 1 + (g >> 4)) << 4))
         p = int(np.nonzero(done[:f])[0].max())
         out = np.broadcast_to(merged[p] if p > 0 else 0, (H, W, 2)).copy()
+        g = links[p] if p > 0 else np.zeros((H, W), dtype=np.int64)
+        own = np.where((winner[0] >= 0) | (winner[1] >= 0), LINK_INTRA, LINK_UNCOVERED)
+        lk = ((own | g) & 7) | (np.minimum(15, 1 + (g >> 4)) << 4)
         both = usable[0] & usable[1]
         if bipred == "near":
             first = ~both | (np.abs(target[0] - f) <= np.abs(target[1] - f))
@@ -425,14 +442,18 @@ def chain_records_numpy(pushes, H: int, W: int, gop: int, max_ref: int = 3, bipr
         use1 = usable[1] & ~use0
         out[use1] = link[1][use1]
         out[use0] = link[0][use0]
+        lk[use1] = byte[1][use1]
+        lk[use0] = byte[0][use0]
         if bipred == "mean":
             s = link[0] + link[1]
             m = s >> 1
             out[both] = (m + (s & 1 & m))[both]
+            lk[both] = ((((byte[0] | byte[1]) & 7) | (np.maximum(byte[0] >> 4, byte[1] >> 4) << 4)))[both]
         merged[f] = out
+        links[f] = lk
         done[f] = True
     assert merged.min() >= -32768 and merged.max() <= 32767
-    return merged.astype(np.int16)
+    return (merged.astype(np.int16), links.astype(np.uint8)) if return_link else merged.astype(np.int16)
 
 
 class MotionChain(object):
@@ -456,9 +477,16 @@ class MotionChain(object):
         chain = MotionChain(H, W, gop=8, bidirectional=True, bipred="near")
         chain.reset();  for f, records in decode_order:  chain.push(records, at=f)
         chain.mv_q()[1:]                       # once frames 1..k are all in
+
+    ``track_links=True``: the chain also owns ``link_bytes`` uint8 [gop,H,W] and ``link_counts`` int64 [gop, LINK_NSTATS] and ``push`` goes
+    through the link entry points (arseg_mv_records_*_link_fwd: the same launches, ``merged`` bit-equal).  ``link()`` is the [k+1,H,W] view
+    under ``mv_q()``'s prefix rule: per pixel LINK_INTRA / LINK_UNCOVERED / LINK_CLAMPED if that happened at this hop or at any hop towards
+    the keyframe, and ``link_hops``; ``link_stats()`` the per-frame counts [intra, uncovered, clamped, any flag, 16 hop bins] -- rows for a
+    ``LinkMonitor``, planes for ``egress.consistency_of_planes(..., link=)``.  With ``False`` allocations and entry points are as before.
     """
 
-    def __init__(self, H: int, W: int, gop: int = 12, max_ref: int = 3, device="cuda", bidirectional: bool = False, bipred: str = "list0"):
+    def __init__(self, H: int, W: int, gop: int = 12, max_ref: int = 3, device="cuda", bidirectional: bool = False, bipred: str = "list0",
+                 track_links: bool = False):
         H, W, gop, max_ref = int(H), int(W), int(gop), int(max_ref)
         if not (1 <= H <= 8192 and 1 <= W <= 8192) or gop < 2 or not 1 <= max_ref <= 16:
             raise _lib.ArsegError(f"MotionChain: H, W in 1..8192, gop >= 2, max_ref in 1..16; got {H}x{W}, gop {gop}, max_ref {max_ref}")
@@ -473,6 +501,9 @@ class MotionChain(object):
             raise _lib.ArsegError("MotionChain runs on the GPU only; there is no CPU fallback (records_to_dense is the host restatement)")
         self.merged = torch.empty((gop, H, W, 2), dtype=torch.int16, device=self.device)
         self.index_map = torch.empty((2 if self.bidirectional else 1) * H * W, dtype=torch.int32, device=self.device)
+        self.track_links = bool(track_links)
+        self.link_bytes = torch.empty((gop, H, W), dtype=torch.uint8, device=self.device) if self.track_links else None
+        self.link_counts = torch.empty((gop, _lib.LINK_NSTATS), dtype=torch.int64, device=self.device) if self.track_links else None
         self.f = 0                      # in-order chain: the last frame pushed
         self.done_mask = 1              # bidirectional chain: bit g = frame g is chained
         self.reset()
@@ -483,6 +514,8 @@ class MotionChain(object):
             ops.mv_records_bi_reset(self.merged, self.index_map)
         else:
             ops.mv_records_reset(self.merged, self.index_map)
+        if self.track_links:
+            ops.mv_link_reset(self.link_bytes, self.link_counts)
         self.f, self.done_mask = 0, 1
 
     def _records(self, records) -> torch.Tensor:
@@ -508,7 +541,11 @@ class MotionChain(object):
                 raise _lib.ArsegError(f"MotionChain: the GOP holds {self.gop - 1} P-frames and all were pushed; reset() starts the next one")
             if at is not None and int(at) != self.f + 1:
                 raise _lib.ArsegError(f"MotionChain: an in-order chain takes frame {self.f + 1} next, not {at}; bidirectional=True takes decode order")
-            out = ops.mv_records_step(self._records(records), self.merged, self.f + 1, self.index_map, self.max_ref)
+            if self.track_links:
+                out, _ = ops.mv_records_step_link(self._records(records), self.merged, self.f + 1, self.index_map, self.link_bytes, self.link_counts,
+                                                  self.max_ref)
+            else:
+                out = ops.mv_records_step(self._records(records), self.merged, self.f + 1, self.index_map, self.max_ref)
             self.f += 1
             return out
         if at is None:
@@ -518,7 +555,11 @@ class MotionChain(object):
             raise _lib.ArsegError(f"MotionChain: frame {at} is outside [1, {self.gop}) (or every frame of the GOP was pushed); reset() starts the next GOP")
         if (self.done_mask >> at) & 1:
             raise _lib.ArsegError(f"MotionChain: frame {at} was pushed before in this GOP")
-        out = ops.mv_records_bi_step(self._records(records), self.merged, at, self.done_mask, self.index_map, self.max_ref, self.bipred)
+        if self.track_links:
+            out, _ = ops.mv_records_bi_step_link(self._records(records), self.merged, at, self.done_mask, self.index_map, self.link_bytes,
+                                                 self.link_counts, self.max_ref, self.bipred)
+        else:
+            out = ops.mv_records_bi_step(self._records(records), self.merged, at, self.done_mask, self.index_map, self.max_ref, self.bipred)
         self.done_mask |= 1 << at
         return out
 
@@ -535,9 +576,59 @@ class MotionChain(object):
     def mv_q(self) -> torch.Tensor:
         """int16 [k+1,H,W,2], a view: frame 0 = -1 (the keyframe has no motion field), frames 1..k as pushed.  A bidirectional chain raises
         while the frames pushed are not 1..k without a gap (``merged[g]`` of a frame not pushed is not motion); a complete GOP never is."""
+        return self.merged[:self._prefix("mv_q()") + 1]
+
+    def _prefix(self, what) -> int:
         if not self.bidirectional:
-            return self.merged[:self.f + 1]
+            return self.f
         k = bin(self.done_mask).count("1") - 1
         if self.done_mask != (1 << (k + 1)) - 1:
-            raise _lib.ArsegError(f"MotionChain: frames {self.frames_done()} are chained, which is not 0..{k} without a gap; mv_q() is whole prefixes only")
-        return self.merged[:k + 1]
+            raise _lib.ArsegError(f"MotionChain: frames {self.frames_done()} are chained, which is not 0..{k} without a gap; {what} is whole prefixes only")
+        return k
+
+    def link(self) -> torch.Tensor:
+        """uint8 [k+1,H,W], a view: the link bytes of frames 0..k (frame 0 all zero), under ``mv_q()``'s prefix rule.  ``track_links=True`` only."""
+        if not self.track_links:
+            raise _lib.ArsegError("MotionChain: link() needs track_links=True")
+        return self.link_bytes[:self._prefix("link()") + 1]
+
+    def link_stats(self) -> torch.Tensor:
+        """int64 [gop, LINK_NSTATS]: row f = the counts of frame f as pushed in this GOP (rows of frames not pushed are zero).
+        ``track_links=True`` only."""
+        if not self.track_links:
+            raise _lib.ArsegError("MotionChain: link_stats() needs track_links=True")
+        return self.link_counts
+
+
+class LinkMonitor(object):
+    """Reports when too much of a frame has lost its link to the keyframe: an intra block or an uncovered pixel somewhere along its chain
+    means the encoder found no prediction there (occlusion, new content, a scene cut -- inside a GOP every block is intra), the cleanest
+    re-key signal a compressed stream offers, and it is there before any mask disagrees.  Pure Python on rows of
+    ``MotionChain.link_stats()``, in the style of ``egress.DriftMonitor``; it only reports.
+
+    ``max_unlinked``: report when the flagged share of the frame exceeds it (0 <= max_unlinked <= 1).  Required: no value is right for every
+    encoder and content; it is the caller's to calibrate on its own streams.
+    ``mask``: the flags that count.  The row counts each flag and "any flag", not every union, so the share is exact for a single flag and
+    for all three (column 3); for two flags the row gives only bounds and the monitor takes the LOWER one, max(count_a, count_b) <= union:
+    it never reports a frame the exact union would not.  A caller that needs the exact union of two flags counts it on the plane:
+    ``(chain.link()[f] & mask != 0).sum()``, and passes it as ``flagged``."""
+
+    def __init__(self, max_unlinked, mask=LINK_INTRA | LINK_UNCOVERED):
+        self.max_unlinked, self.mask = float(max_unlinked), int(mask)
+        if not 0.0 <= self.max_unlinked <= 1.0 or not 0 < self.mask <= 7:
+            raise ValueError(f"LinkMonitor: max_unlinked in [0, 1] and a mask of LINK_* flags, got {max_unlinked!r}, {mask!r}")
+
+    def flagged(self, stats_row) -> int:
+        """The number of flagged pixels the row vouches for (see ``mask``)."""
+        if self.mask == 7:
+            return int(stats_row[3])
+        return max(int(stats_row[b]) for b in range(3) if (self.mask >> b) & 1)
+
+    def update(self, stats_row, n_pixels, flagged=None) -> bool:
+        """One frame: ``stats_row`` its row of ``link_stats()``, ``n_pixels`` = H x W; ``flagged`` overrides the count taken from the row.
+        True = refresh the keyframe."""
+        n_pixels = int(n_pixels)
+        if n_pixels <= 0:
+            raise ValueError(f"LinkMonitor.update: n_pixels must be positive, got {n_pixels}")
+        n = self.flagged(stats_row) if flagged is None else int(flagged)
+        return bool(n / n_pixels > self.max_unlinked)

@@ -255,6 +255,39 @@ def labels_consistency(labels: torch.Tensor, ref_labels: torch.Tensor, mv_q: tor
     return change_out, stats
 
 
+def labels_consistency_linked(labels: torch.Tensor, ref_labels: torch.Tensor, mv_q: torch.Tensor, n_cls: int, link: torch.Tensor, link_mask: int, *,
+                              change_out: Optional[torch.Tensor] = None, stats: Optional[torch.Tensor] = None,
+                              unlinked: Optional[torch.Tensor] = None):
+    """``labels_consistency`` gated by the chain's link bytes: ``link`` uint8 [N,H,W] (rows contiguous, any pitch / image stride; a frame's
+    plane of ``MotionChain.link()``), ``link_mask`` 0..255 the bits that gate.  A pixel with ``link & link_mask`` is unlinked: decided first,
+    ``change_out`` 128, no counter of ``stats``, one count in ``unlinked`` (int64 [N], contiguous, ACCUMULATED INTO; None: not wanted).
+    ``link_mask=0`` gives ``labels_consistency``'s outputs bit for bit.  Returns (change_out, stats, unlinked)."""
+    _need_gpu(labels, dtype=torch.uint8)
+    if labels.dim() != 3:
+        raise _lib.ArsegError(f"labels_consistency_linked expects a uint8 label plane [N,H,W], got {tuple(labels.shape)}")
+    N, H, W = labels.shape
+    n_cls, link_mask = int(n_cls), int(link_mask)
+    if change_out is None and stats is None:
+        raise ValueError("labels_consistency_linked: nothing to write (change_out and stats are both None)")
+    if not 0 <= link_mask <= 255:
+        raise ValueError(f"labels_consistency_linked: link_mask is a byte, got {link_mask}")
+    what = "labels_consistency_linked"
+    ref_pitch, ref_ns, chg_pitch, chg_ns = _tc_common(what, N, H, W, n_cls, labels.device, ref_labels, mv_q, change_out, stats)
+    in_pitch, in_ns = _plane_layout(labels, (W,), f"{what} labels")
+    if link is None:
+        raise _lib.ArsegError(f"{what}: link is required (labels_consistency is the form without)")
+    _need_gpu(link, dtype=torch.uint8)
+    if tuple(link.shape) != (N, H, W) or link.device != labels.device:
+        raise _lib.ArsegError(f"{what}: link must be uint8 {(N, H, W)} on {labels.device}, got {tuple(link.shape)} on {link.device}")
+    link_pitch, link_ns = _plane_layout(link, (W,), f"{what} link")
+    if unlinked is not None:
+        _dense(what, "unlinked", unlinked, torch.int64, (N,), labels.device)
+    launch(what, _lib.load().arseg_labels_consistency_linked_fwd, _ptr(labels), in_pitch, in_ns, N, n_cls, H, W, _ptr(ref_labels),
+           ref_pitch, ref_ns, _ptr(mv_q), _ptr(change_out), chg_pitch, chg_ns, _ptr(stats), _ptr(link), link_pitch, link_ns, link_mask,
+           _ptr(unlinked), _stream(), nbytes=(7 + (change_out is not None)) * N * H * W)
+    return change_out, stats, unlinked
+
+
 _RUN_DTYPES = tuple(d for d in (torch.int32, getattr(torch, "uint32", None)) if d is not None)          # one 32-bit word per run, either sign
 
 

@@ -454,6 +454,39 @@ def mv_records_step(records: torch.Tensor, merged: torch.Tensor, f: int, index_m
     return merged[f]
 
 
+def _mv_link_state(link: torch.Tensor, link_stats, gop: int, H: int, W: int, dev, what: str) -> None:
+    if not torch.is_tensor(link) or link.dtype != torch.uint8 or link.device != dev or tuple(link.shape) != (gop, H, W) or not link.is_contiguous():
+        raise _lib.ArsegError(f"{what} expects link as a contiguous uint8 tensor {(gop, H, W)} on {dev}")
+    if link_stats is not None and (not torch.is_tensor(link_stats) or link_stats.dtype != torch.int64 or link_stats.device != dev
+                                   or tuple(link_stats.shape) != (gop, _lib.LINK_NSTATS) or not link_stats.is_contiguous()):
+        raise _lib.ArsegError(f"{what} expects link_stats as a contiguous int64 tensor {(gop, _lib.LINK_NSTATS)} on {dev} (or None)")
+
+
+def mv_link_reset(link: torch.Tensor, link_stats: Optional[torch.Tensor] = None) -> None:
+    """Starts a GOP of the link bytes (include/arseg_hip.h, arseg_mv_link_reset): link[0] = 0 and every row of link_stats = 0.  link uint8
+    [gop,H,W], link_stats int64 [gop, LINK_NSTATS] or None, caller-owned on one GPU.  Goes with mv_records_reset / mv_records_bi_reset."""
+    if not torch.is_tensor(link) or not link.is_cuda or link.dim() != 3:
+        raise _lib.ArsegError("mv_link_reset expects link as a contiguous CUDA uint8 tensor [gop,H,W]")
+    gop, H, W = link.shape
+    _mv_link_state(link, link_stats, gop, H, W, link.device, "mv_link_reset")
+    launch("mv_link_reset", _lib.load().arseg_mv_link_reset, _ptr(link), _ptr(link_stats), gop, H, W, _stream())
+
+
+def mv_records_step_link(records: torch.Tensor, merged: torch.Tensor, f: int, index_map: torch.Tensor, link: torch.Tensor,
+                         link_stats: Optional[torch.Tensor] = None, max_ref: int = 3):
+    """mv_records_step that also writes the link bytes of frame f (uint8 [H,W]: bit 0 intra, bit 1 uncovered, bit 2 clamped -- at this hop or at
+    any hop towards the keyframe -- and the hops in bits 4..7) into link[f] and adds the frame's counts to link_stats[f] (None: not wanted).
+    merged[f] is bit-equal to mv_records_step's; the same two kernels.  Returns the views (merged[f], link[f])."""
+    n = _mv_records(records, "mv_records_step_link")
+    gop, H, W = _mv_chain_state(merged, index_map, "mv_records_step_link")
+    if records.device != merged.device:
+        raise _lib.ArsegError(f"mv_records_step_link: records are on {records.device}, merged on {merged.device}")
+    _mv_link_state(link, link_stats, gop, H, W, merged.device, "mv_records_step_link")
+    launch("mv_records_step_link", _lib.load().arseg_mv_records_step_link_fwd, _ptr(records), n, _ptr(merged), int(f), gop, _ptr(index_map),
+           index_map.numel() * 4, H, W, int(max_ref), _ptr(link), _ptr(link_stats), _stream())
+    return merged[f], link[f]
+
+
 MV_BI_POLICIES = {"list0": _lib.MVR_BI_LIST0, "near": _lib.MVR_BI_NEAR, "mean": _lib.MVR_BI_MEAN}
 
 
@@ -483,6 +516,26 @@ def mv_records_bi_step(records: torch.Tensor, merged: torch.Tensor, f: int, done
     launch("mv_records_bi_step", _lib.load().arseg_mv_records_bi_step_fwd, _ptr(records), n, _ptr(merged), f, gop, done_mask,
            MV_BI_POLICIES[policy], _ptr(index_maps), index_maps.numel() * 4, H, W, int(max_ref), _stream())
     return merged[f]
+
+
+def mv_records_bi_step_link(records: torch.Tensor, merged: torch.Tensor, f: int, done_mask: int, index_maps: torch.Tensor, link: torch.Tensor,
+                            link_stats: Optional[torch.Tensor] = None, max_ref: int = 3, policy="list0"):
+    """mv_records_bi_step that also writes link[f] and adds to link_stats[f], as mv_records_step_link does for the P-frame step; under "mean"
+    a pixel with both lists usable carries the flags of both and the larger hop count.  Returns the views (merged[f], link[f])."""
+    n = _mv_records(records, "mv_records_bi_step_link")
+    gop, H, W = _mv_chain_state(merged, index_maps, "mv_records_bi_step_link", maps=2)
+    if records.device != merged.device:
+        raise _lib.ArsegError(f"mv_records_bi_step_link: records are on {records.device}, merged on {merged.device}")
+    if policy not in MV_BI_POLICIES:
+        raise _lib.ArsegError(f"mv_records_bi_step_link: policy is one of {sorted(MV_BI_POLICIES)}, got {policy!r}")
+    f, done_mask = int(f), int(done_mask)
+    if gop > 64 or not 1 <= f < gop or not done_mask & 1 or (done_mask >> f) & 1 or done_mask < 0 or done_mask >> gop:
+        raise _lib.ArsegError(f"mv_records_bi_step_link: gop <= 64, f in [1, gop), done_mask with bit 0 set, bit f clear and no bit >= gop; got gop {gop}, "
+                              f"f {f}, done_mask {done_mask:#x}")
+    _mv_link_state(link, link_stats, gop, H, W, merged.device, "mv_records_bi_step_link")
+    launch("mv_records_bi_step_link", _lib.load().arseg_mv_records_bi_step_link_fwd, _ptr(records), n, _ptr(merged), f, gop, done_mask,
+           MV_BI_POLICIES[policy], _ptr(index_maps), index_maps.numel() * 4, H, W, int(max_ref), _ptr(link), _ptr(link_stats), _stream())
+    return merged[f], link[f]
 
 
 def mv_records_rasterize(records: torch.Tensor, H: int, W: int) -> torch.Tensor:

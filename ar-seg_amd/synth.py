@@ -202,3 +202,25 @@ def make_record_chain(seed: int, H: int, W: int, n_frames: int):
 
     flows = make_mv_chain(seed, H, W, n_frames)
     return [mv_to_records(flows[f]) for f in range(1, n_frames + 1)]
+
+
+def make_link_chain(seed: int, H: int, W: int, n_frames: int, intra: float = 0.04, holes: float = 0.04):
+    """What ``make_record_chain`` cannot produce, for the link bytes (``ingest.MotionChain(track_links=True)``): a list of n_frames block-record
+    arrays int16 [n,8] (frames 1..n_frames, P-only, list 0) on 8- / 16-pixel blocks in raster order where a share ``holes`` of the blocks has
+    no record at all (uncovered pixels), a share ``intra`` carries a reference index out of range (-1 or 5), the rest reference 0..2 frames
+    back with vectors of up to 6 pixels, so that blocks at the border point off the frame (clamped targets)."""
+    g = np.random.Generator(np.random.PCG64([seed, H, W, n_frames]))
+    out = []
+    for f in range(1, n_frames + 1):
+        bs = 8 if f % 2 else 16
+        hb, wb = (H + bs - 1) // bs, (W + bs - 1) // bs
+        by, bx = np.mgrid[0:hb, 0:wb]
+        mv = g.integers(-24, 25, (hb, wb, 2))
+        u = g.random((hb, wb))
+        ref = np.where(u < intra, g.choice(np.array([-1, 5]), (hb, wb)), g.choice(np.array([0, 0, 0, 0, 1, 2]), (hb, wb)))
+        keep = (u >= intra + holes) | (u < intra)
+        rec = np.zeros((hb, wb, 8), dtype=np.int16)
+        rec[..., 0], rec[..., 1], rec[..., 2], rec[..., 3] = bx * bs, by * bs, bs, bs
+        rec[..., 4:6], rec[..., 6] = mv, ref
+        out.append(np.ascontiguousarray(rec[keep]))
+    return out

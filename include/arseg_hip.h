@@ -613,6 +613,53 @@ size_t arseg_mv_records_bi_workspace_bytes(int H, int W);
 int arseg_mv_records_bi_reset(int16_t *merged, void *workspace, size_t workspace_bytes, int H, int W, arseg_stream_t stream);
 int arseg_mv_records_bi_step_fwd(const int16_t *records, int n_records, int16_t *merged, int f, int gop, uint64_t done_mask, int policy,
                                  void *workspace, size_t workspace_bytes, int H, int W, int max_ref, arseg_stream_t stream);
+
+/* ---------------------------------------------------------------------------------------------
+ * Link quality along the chain (csrc/mv_records.hip): merged keeps the accumulated displacement of a pixel and nothing about how good its
+ * links are.  Three things that happen at a hop all end as an ordinary-looking vector: an INTRA block (the encoder found no usable
+ * prediction; the rule substitutes zero motion), an UNCOVERED pixel (no record; the same substitution) and a CLAMPED target (it fell off
+ * the frame and was pulled back to the border).  The link entry points write, next to merged[f], one byte per pixel that keeps them.
+ *   link        uint8 [gop][H][W] on the device, contiguous, caller-owned; frame 0 is all zero.  For frame f and pixel (x, y), flag bits
+ *               mean "at this hop or at any hop between here and the keyframe":
+ *                 bit 0  ARSEG_LINK_INTRA      set at a hop when a record won the pixel but could not be used.  P entry: ref < 0 or ref >= max_ref.
+ *                                              Bi entry: no list is usable and at least one list has a winner (its ref out of range or its
+ *                                              target not in D)
+ *                 bit 1  ARSEG_LINK_UNCOVERED  no record of any list covers the pixel (index outside [0, n_records))
+ *                 bit 2  ARSEG_LINK_CLAMPED    a USED list's rounded target x + round_half_even_div4(mvx) or y + round_half_even_div4(mvy) lay
+ *                                              outside the frame before the clamp
+ *                 bit 3  reserved, written 0
+ *                 bits 4..7  hops: the number of links from this pixel to the keyframe, saturating at 15; a pixel whose target is in frame
+ *                            0 has 1 hop
+ *   Propagation, with (t, j2, k2) EXACTLY the pixel whose merged value the compose step gathers (the intra / uncovered substitution targets
+ *   the same pixel of frame max(0, f - 1), P entry, or of frame p, bi entry, as in the rules above), and g = t > 0 ? link[t][j2][k2] : 0:
+ *       link[f][y][x] = ((own flags | g) & 7) | (min(15, 1 + (g >> 4)) << 4)
+ *   Bi entry under LIST0 / NEAR: only the chosen list contributes.  Under MEAN with both lists usable: the flags are the OR of both lists'
+ *   bytes, the hops their maximum.  With every record in list 0, frames pushed in order and done_mask = (1 << f) - 1 the bi entry's link
+ *   equals the P entry's bit for bit under every policy, as merged does.
+ *   link_stats  int64 [gop][ARSEG_LINK_NSTATS] on the device, 8-byte aligned, may be NULL; row f is ACCUMULATED INTO by the step of frame f:
+ *                 [0] pixels with INTRA   [1] with UNCOVERED   [2] with CLAMPED   [3] with any flag   [4 + h] pixels with h hops (h = 0 .. 15)
+ *               Integers: two runs are bit-equal.
+ * Entry points (enqueue only: no host synchronisation, no allocation; a captured graph replays them):
+ *   arseg_mv_link_reset                zeroes link[0] and every row of link_stats (if not NULL); one launch.  Goes with arseg_mv_records_reset
+ *                                      / _bi_reset, which it does not replace
+ *   arseg_mv_records_step_link_fwd     arseg_mv_records_step_fwd + link, link_stats: writes merged[f] bit-equal to that entry, and link[f].
+ *                                      No further launch: the compose pass writes the byte (a 1-byte gather at the address pattern of the
+ *                                      4-byte one)
+ *   arseg_mv_records_bi_step_link_fwd  the same for arseg_mv_records_bi_step_fwd
+ * ARSEG_EINVAL before any launch: everything the plain entries refuse; a null link; a link_stats that is not 8-byte aligned; reset: gop < 1,
+ * H or W outside 1 .. 8192.
+ * Not covered: which hop set a flag; a per-list byte under MEAN; link bytes for arseg_merge_motion_fwd's dense route.
+ * ------------------------------------------------------------------------------------------- */
+#define ARSEG_LINK_INTRA 1
+#define ARSEG_LINK_UNCOVERED 2
+#define ARSEG_LINK_CLAMPED 4
+#define ARSEG_LINK_NSTATS (4 + 16)
+int arseg_mv_link_reset(uint8_t *link, int64_t *link_stats, int gop, int H, int W, arseg_stream_t stream);
+int arseg_mv_records_step_link_fwd(const int16_t *records, int n_records, int16_t *merged, int f, int gop, void *workspace, size_t workspace_bytes,
+                                   int H, int W, int max_ref, uint8_t *link, int64_t *link_stats, arseg_stream_t stream);
+int arseg_mv_records_bi_step_link_fwd(const int16_t *records, int n_records, int16_t *merged, int f, int gop, uint64_t done_mask, int policy,
+                                      void *workspace, size_t workspace_bytes, int H, int W, int max_ref, uint8_t *link, int64_t *link_stats,
+                                      arseg_stream_t stream);
 /* layout changes at the API boundary */
 int arseg_nchw_to_nhwc_fwd(const float *in, float *out, int N, int C, int HW, int out_ld, arseg_stream_t stream);
 int arseg_nhwc_to_nchw_fwd(const float *in, int in_ld, float *out, int N, int C, int HW, arseg_stream_t stream);
@@ -823,7 +870,19 @@ int arseg_segment_confidence_fwd(const float *logits, int N, int n_cls, int h, i
  * mv_q that is not 4-byte aligned; no output at all; n_cls < 1 or > 32; a non-positive size; a pitch smaller than W; a negative image
  * stride.  (The tail refuses no shape on the run route -- a shape that is not an exact x2 / x4 / x8 takes the per-pixel route -- so neither
  * does this.)
- * Not covered: sub-pixel comparison of label probabilities, occlusion reasoning, consecutive-frame fields (the plane form takes one).
+ * arseg_labels_consistency_linked_fwd is the plane form gated by the chain's link bytes (arseg_mv_records_step_link_fwd above), four more
+ * arguments:
+ *   link        uint8 [N][H][W] on the device, link_pitch bytes from row to row (>= W), link_image_stride bytes from frame to frame: the
+ *               link plane of each frame
+ *   link_mask   the flags that gate (ARSEG_LINK_INTRA | ARSEG_LINK_UNCOVERED | ARSEG_LINK_CLAMPED, any subset; the hop bits may be named too)
+ *   unlinked    int64 [N] on the device, ACCUMULATED INTO, may be NULL
+ * A pixel with link & link_mask != 0 takes a fifth outcome, UNLINKED, decided FIRST: neither mv_q nor the reference is read for it,
+ * change_out is 128, it enters no counter of stats, and unlinked[n] is incremented.  Otherwise the four outcomes above in their order.  The
+ * stats layout is unchanged; for every frame compared + outside + void + unlinked = H W.  link_mask == 0 gives the outputs of
+ * arseg_labels_consistency_fwd bit for bit.  ARSEG_EINVAL additionally: a null link, link_pitch < W, a negative link_image_stride, an unlinked
+ * that is not 8-byte aligned.
+ * Not covered: sub-pixel comparison of label probabilities, occlusion reasoning beyond the link flags (the logits form has no linked
+ * variant), consecutive-frame fields (the plane form takes one).
  * ------------------------------------------------------------------------------------------- */
 #define ARSEG_TC_NSTATS (3 + 3 * 32)
 int arseg_segment_consistency_fwd(const float *logits, int N, int n_cls, int h, int w, int H, int W, int align_corners,
@@ -835,6 +894,11 @@ int arseg_labels_consistency_fwd(const uint8_t *labels_in, int64_t in_pitch, int
                                  const uint8_t *ref_labels, int64_t ref_pitch, int64_t ref_image_stride, const int16_t *mv_q,
                                  uint8_t *change_out, int64_t change_pitch, int64_t change_image_stride, int64_t *stats,
                                  arseg_stream_t stream);
+int arseg_labels_consistency_linked_fwd(const uint8_t *labels_in, int64_t in_pitch, int64_t in_image_stride, int N, int n_cls, int H, int W,
+                                        const uint8_t *ref_labels, int64_t ref_pitch, int64_t ref_image_stride, const int16_t *mv_q,
+                                        uint8_t *change_out, int64_t change_pitch, int64_t change_image_stride, int64_t *stats,
+                                        const uint8_t *link, int64_t link_pitch, int64_t link_image_stride, uint8_t link_mask,
+                                        int64_t *unlinked, arseg_stream_t stream);
 
 /* ---------------------------------------------------------------------------------------------
  * Run-length coded label planes (csrc/rle.hip): the 8-bit planes above (labels8, change8, conf8) are a few thousand constant runs per
