@@ -182,6 +182,8 @@ PROTOTYPES = {
     "arseg_label_bands_fwd": (c_int, [_P, _P, _P, POINTER(c_int), c_int, _P, c_int64, c_int64, _P] + [c_int] * 6 + [_P, c_size_t, _STREAM]),
     "arseg_boundary_iou_workspace_bytes": (c_size_t, [c_int, c_int, c_int]),
     "arseg_boundary_iou_fwd": (c_int, [_P, _P, _P, POINTER(c_int), c_int, c_int, _P, c_int64, c_int64, _P, c_int64, c_int64, _P] + [c_int] * 6 + [_P, c_size_t, _STREAM]),
+    "arseg_contour_f_workspace_bytes": (c_size_t, [c_int, c_int, c_int]),
+    "arseg_contour_f_fwd": (c_int, [_P, _P, _P, POINTER(c_int), c_int, _P, c_int64, c_int64, _P, c_int64, c_int64, _P] + [c_int] * 6 + [_P, c_size_t, _STREAM]),
 }
 
 # the SURVEY.md section 8(b) names: aliases with the prototypes of their targets

@@ -56,6 +56,30 @@
 // Its clamps: both bytes of a counting pixel are below n_cls and both bands at most n_bands, so a counter's index is below
 // 3 (n_bands + 1) n_cls; a staged row is read only where b is in [64 - R, 128 + R), the rows the host sized the tiles for, and only in
 // columns inside the image, which were staged; the planes' rows are written inside [0, W) only.
+//
+// The contour F-measure counts (arseg_contour_f_fwd) take the same two byte planes (bd_byte) and the same tiles, groups, wave tally
+// (bd_tally) and flush, but their distance is Euclidean and between the planes, so nothing of the row and column passes carries over.
+// The scratch is one mark byte per pixel and plane in the caller's workspace ([2][N][H][W]): CF_NONE, or the class of a contour pixel
+// with CF_COUNTS where both planes' bytes are classes.  2 launches, sized on the host.
+//   marks    contour_marks_kernel: a tile of 64 x 64 pixels with a halo of one, both planes' bytes in LDS (255 outside the image, so
+//            the border and void are one rule); the 3 x 3 test is byte compares (cf_mark); rows of 64 marks leave together.
+//   match    contour_match_kernel: both planes' marks of the tile with a halo of R = radii[n_bands - 1] in LDS (CF_NONE outside the
+//            image; at R = 32 two times 128 x 128 bytes), each plane's contour pixels of the tile compacted into a list with ballots and
+//            a count of the lanes below (cf_compact), then a LANE per contour pixel: Chebyshev rings around it on the other plane's
+//            marks, inside a ring outwards from the axes so that the first hit is the ring's least (cf_search, which says when it may
+//            stop).  Two rounds: the first seeks within CF_R1 rings, where what it finds is final; the pixels it leaves -- the
+//            unmatched among them, whose search is the whole disc -- are compacted again, so that long searches fill whole waves
+//            instead of holding one up each.  The staging reads the marks four at a time (cf_load4: rows start at any alignment).
+//            The band is the number of radii whose square is below m2.  A plane gets 255 in rows of 64 bytes wherever the tile has no
+//            contour pixel, and a contour pixel's lane writes its band itself: a tenth of the bytes, and 8 KB of LDS less than staging
+//            them, which at R = 19 is a workgroup more per CU.  Counters and flush as above.  50.3 KB of dynamic LDS at most.
+// Its loops: the same grid-stride loops; the staging 17 rounds in marks and (64 + 2 R) / 8 rows per half wave in match, R <= 32 checked
+// on the host; 16 rows per wave in cf_compact; two rounds of at most 4096 / 256 passes over list entries per plane and tile; rho = 0 .. R
+// and t = 0 .. rho in cf_search; n_bands <= 8 compares; cf_dword's 4 bytes; bd_tally of at most 64 rounds.
+// Its clamps: a contour pixel's class is a byte below n_cls and its band at most n_bands, so a counter's index is below
+// 2 (n_bands + 1) n_cls; a list holds at most the tile's 4096 places; cf_search reads at most R marks from a pixel of the tile in either
+// direction, inside the staged halo; cf_dword reads inside the 2 N H W marks only, whatever the row's alignment; marks and planes are
+// written inside the image only.
 #include "arseg_common.h"
 
 namespace {
@@ -71,6 +95,12 @@ constexpr int BI_PITCH = BD_TW + 2;                     // words per staged row 
                                                         // column, one per lane, spread over the LDS banks
 constexpr int BI_OPITCH = BD_TW + 4;                    // bytes per row of its staged bands: 17 dwords, for the same reason
 constexpr unsigned BD_VOID = 255u;
+constexpr int CF_RMAX = 32;                             // the largest radius of contour_f: a halo of 32 marks round a tile of 64 x 64
+constexpr int CF_MPITCH = BD_TW + 4;                    // bytes per staged row of contour_marks_kernel: the tile and a pixel either side
+constexpr unsigned CF_NONE = 0x80u;                     // the mark of a pixel that is no contour pixel
+constexpr unsigned CF_COUNTS = 0x40u;                   // on a contour pixel's mark (its class, below 32): both planes' bytes are classes here
+constexpr int CF_R1 = 2;                                // the rings of the first round of the search
+constexpr unsigned CF_CLASS = 0xbfu;                    // a mark without CF_COUNTS: the class of a contour pixel, CF_NONE else
 
 struct BdP {
     const long long *label;                             // [N][H][W]
@@ -377,6 +407,272 @@ __global__ __launch_bounds__(256) void boundary_cols_kernel(const BiP p) {
     }
 }
 
+struct CfP {
+    const long long *label;                             // [N][H][W]
+    const int *pred;                                    // [N][H][W]
+    const int *group;                                   // [N] (null: every frame is group 0)
+    unsigned char *lmatch, *pmatch;                     // the match planes of the labels' and of the predictions' contours (each may be null)
+    unsigned long long *counts;                         // [n_groups][2][n_bands + 1][n_cls] (may be null)
+    unsigned char *marks;                               // the workspace: [2][N][H][W], the labels' marks, then the predictions'
+    long long lpitch, lns, ppitch, pns;
+    int radii[BD_NBMAX];
+    int N, H, W, n_groups, n_cls, n_bands, R, ignore_label;
+};
+
+// The mark of the pixel whose byte is at[0] in a staged tile of CF_MPITCH bytes per row (bytes outside the image staged as 255): its class
+// if one of its 8 neighbours holds another class -- a 255 neighbour, void or outside the image, makes no contour --, with CF_COUNTS when
+// the other plane's byte at the pixel, ``other``, is a class too; CF_NONE else.
+__device__ __forceinline__ unsigned cf_mark(const unsigned char *at, unsigned other) {
+    const unsigned c = at[0];
+    bool edge = false;
+#pragma unroll
+    for (int dy = -1; dy <= 1; ++dy)
+#pragma unroll
+        for (int dx = -1; dx <= 1; ++dx) {
+            const unsigned v = at[dy * CF_MPITCH + dx];
+            edge |= v != c && v != BD_VOID;
+        }
+    return c != BD_VOID && edge ? c | (other != BD_VOID ? CF_COUNTS : 0u) : CF_NONE;
+}
+
+__global__ __launch_bounds__(256) void contour_marks_kernel(const CfP p) {
+    __shared__ unsigned char sb[2][(BD_TH + 2) * CF_MPITCH];                  // row r, column c: the pixel (y0 - 1 + r, x0 - 1 + c)
+    const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
+    const int H = p.H, W = p.W;
+    const size_t frame = (size_t)H * (size_t)W, plane = (size_t)p.N * frame;
+    const int tiles_x = (W + BD_TW - 1) / BD_TW, tiles = tiles_x * ((H + BD_TH - 1) / BD_TH);
+    for (int n = blockIdx.y; n < p.N; n += gridDim.y) {
+        const long long *lab = p.label + (size_t)n * frame;
+        const int *prd = p.pred + (size_t)n * frame;
+        unsigned char *ml = p.marks + (size_t)n * frame, *mp = ml + plane;
+        for (int t = blockIdx.x; t < tiles; t += gridDim.x) {                 // uniform: every thread makes every pass
+            const int x0 = (t % tiles_x) * BD_TW, y0 = (t / tiles_x) * BD_TH;
+            for (int i = tid; i < (BD_TH + 2) * (BD_TW + 2); i += 256) {
+                const int r = i / (BD_TW + 2), c = i - r * (BD_TW + 2);
+                const int y = y0 - 1 + r, x = x0 - 1 + c;
+                const bool in = y >= 0 && y < H && x >= 0 && x < W;
+                const size_t at = in ? (size_t)y * (size_t)W + x : 0;
+                sb[0][r * CF_MPITCH + c] = (unsigned char)(in ? bd_byte(lab[at], p.n_cls, p.ignore_label) : BD_VOID);
+                sb[1][r * CF_MPITCH + c] = (unsigned char)(in ? bd_byte((long long)prd[at], p.n_cls, -1) : BD_VOID);       // -1 is no byte's value
+            }
+            __syncthreads();
+            for (int ly = wave; ly < BD_TH; ly += 4) {                        // lane = column: rows of 64 marks leave together
+                const int y = y0 + ly, x = x0 + lane;
+                if (y < H && x < W) {
+                    const unsigned char *a = sb[0] + (ly + 1) * CF_MPITCH + lane + 1, *b = sb[1] + (ly + 1) * CF_MPITCH + lane + 1;
+                    const size_t at = (size_t)y * (size_t)W + x;
+                    ml[at] = (unsigned char)cf_mark(a, b[0]);
+                    mp[at] = (unsigned char)cf_mark(b, a[0]);
+                }
+            }
+            __syncthreads();                                                  // before the next tile's bytes
+        }
+    }
+}
+
+// The lanes of a wave that have a place (ly * 64 + lx) to add to a list in LDS: the wave's ballot and a count of the lanes below give a
+// lane's slot behind the wave's base, which the leading lane takes off the list's counter.  Every lane of the wave calls.
+__device__ __forceinline__ void cf_push(unsigned short *list, unsigned *n_list, bool is, unsigned place, int lane) {
+    const unsigned long long m = __ballot(is);
+    unsigned base = 0;
+    if (lane == 0 && m) base = atomicAdd(n_list, (unsigned)__builtin_popcountll(m));
+    base = (unsigned)__shfl((int)base, 0, 64);
+    if (is) list[base + (unsigned)__builtin_popcountll(m & ((1ull << lane) - 1ull))] = (unsigned short)place;
+}
+
+// The contour pixels of one plane of the tile, compacted: list[0 .. *n_list) their places, in any order.  A wave takes a row of the tile at
+// a time; ``mine`` is the tile's own part of the staged marks (pitch P).  Every thread of the workgroup calls.
+__device__ __forceinline__ void cf_compact(const unsigned char *mine, int P, unsigned short *list, unsigned *n_list, int lane, int wave) {
+    for (int ly = wave; ly < BD_TH; ly += 4) cf_push(list, n_list, mine[ly * P + lane] != CF_NONE, (unsigned)(ly * BD_TW + lane), lane);
+}
+
+// m2 of the contour pixel of class c at ``at`` against the other plane's staged marks (pitch P, a halo of at least R marks on every side,
+// CF_NONE outside the image), as far as the band needs it: R * R + 1 for "none within R".  Chebyshev rings rho = 0, 1, ...: the marks of
+// ring rho are at (+-rho, +-t) and (+-t, +-rho), t = 0 .. rho, squared distance rho^2 + t^2, so within a ring t ascends and the first hit
+// is the ring's least.  A ring can improve on the best only while rho^2 < best -- not merely until the first ring with a hit: (5, 5) is in
+// ring 5 at 50, (0, 6) in ring 6 at 36 --, and nothing below radii[0]^2 changes the band: a HIT within radii[0] ends the search ("none
+// within R" is no hit, whatever radii[0] is: R may be the first round's few rings, below radii[0]).
+__device__ __forceinline__ unsigned cf_search(const unsigned char *at, int P, unsigned c, int R, unsigned r0sq) {
+    unsigned best = (unsigned)(R * R) + 1u;
+    const unsigned enough = min(r0sq, (unsigned)(R * R));
+    for (int rho = 0; rho <= R && (unsigned)(rho * rho) < best && best > enough; ++rho) {
+        const unsigned char *up = at - rho * P, *dn = at + rho * P;
+        for (int t = 0; t <= rho; ++t) {
+            const unsigned d2 = (unsigned)(rho * rho + t * t);
+            if (d2 >= best) break;
+            const int tp = t * P;
+            const unsigned a0 = up[t], a1 = up[-t], a2 = dn[t], a3 = dn[-t], a4 = at[tp - rho], a5 = at[-tp - rho], a6 = at[tp + rho], a7 = at[-tp + rho];
+            const bool hit = (a0 & CF_CLASS) == c | (a1 & CF_CLASS) == c | (a2 & CF_CLASS) == c | (a3 & CF_CLASS) == c | (a4 & CF_CLASS) == c |
+                             (a5 & CF_CLASS) == c | (a6 & CF_CLASS) == c | (a7 & CF_CLASS) == c;
+            if (hit) {
+                best = d2;
+                break;
+            }
+        }
+    }
+    return best;
+}
+
+// The same m2 for the long searches of the second round, by rows: the pixel's own row of the other plane's marks, then the rows dy = 1, 2, ...
+// above and below it while dy^2 < best, in each the columns within w of the pixel's, w the largest with dy^2 + w^2 < best -- inside the
+// disc of R, and shrinking with every hit.  Four marks per aligned 32-bit LDS read: with the class in every byte XORed in, a mark of
+// the class is a zero byte (the usual test), and a word with one is looked at byte by byte.  The bytes a word holds beyond w are marks
+// too, at their true distance, and the minimum may take them.  ``row`` is the pixel's staged row of the other plane (its first byte,
+// 4-byte aligned, pitch P a multiple of 4), ``cx`` its column there: cx - w >= 0 and cx + w < P for every w <= R.
+__device__ __forceinline__ unsigned cf_scan(const unsigned char *row, int cx, int P, unsigned c, int R, unsigned r0sq) {
+    unsigned best = (unsigned)(R * R) + 1u;
+    const unsigned cw = c * 0x01010101u;
+    int w = R;
+    for (int dy = 0; dy <= R && (unsigned)(dy * dy) < best && best > r0sq; ++dy) {
+        const int lim = (int)best - 1 - dy * dy;                              // >= 0: dx^2 may be at most this
+        while (w * w > lim) --w;                                              // (w only ever shrinks: at most R steps in all)
+        const int c0 = (cx - w) & ~3, c1 = cx + w;
+        for (int side = dy == 0 ? 1 : 0; side < 2; ++side) {
+            const unsigned char *r = side ? row + dy * P : row - dy * P;
+            for (int col = c0; col <= c1; col += 4) {
+                const unsigned v = (*reinterpret_cast<const unsigned *>(r + col) & (CF_CLASS * 0x01010101u)) ^ cw;
+                if (((v - 0x01010101u) & ~v & 0x80808080u) == 0u) continue;   // no byte of v is zero
+#pragma unroll
+                for (int b = 0; b < 4; ++b)
+                    if (((v >> (8 * b)) & 0xffu) == 0u) best = min(best, (unsigned)(dy * dy + (col + b - cx) * (col + b - cx)));
+            }
+        }
+    }
+    return best;
+}
+
+// Four bytes of the marks from the 4-byte aligned element ``a`` on (``total`` bytes in all): one 32-bit load where all four are inside, else
+// byte by byte, zeros outside.
+__device__ __forceinline__ unsigned cf_dword(const unsigned char *marks, long long a, long long total) {
+    if (a >= 0 && a + 4 <= total) return *reinterpret_cast<const unsigned *>(marks + a);
+    unsigned w = 0;
+#pragma unroll
+    for (int b = 0; b < 4; ++b)
+        if (a + b >= 0 && a + b < total) w |= (unsigned)marks[a + b] << (8 * b);
+    return w;
+}
+
+// The four marks from element e on, however e is aligned (rows start anywhere: W and R are any): the two aligned words around them, shifted.
+__device__ __forceinline__ unsigned cf_load4(const unsigned char *marks, long long e, long long total) {
+    const unsigned s = (unsigned)((reinterpret_cast<uintptr_t>(marks) + (uintptr_t)e) & 3u);
+    const long long a = e - (long long)s;
+    const unsigned lo = cf_dword(marks, a, total), hi = s ? cf_dword(marks, a + 4, total) : 0u;
+    return (unsigned)(((unsigned long long)hi << 32 | lo) >> (8u * s));
+}
+
+// the number of radii whose square is below m2: the first k with m2 <= radii[k]^2, n_bands for unmatched
+__device__ __forceinline__ unsigned cf_band(unsigned m2, const int *radii, int n_bands) {
+    unsigned band = 0;
+    for (int k = 0; k < n_bands; ++k) band += m2 > (unsigned)(radii[k] * radii[k]) ? 1u : 0u;
+    return band;
+}
+
+__global__ __launch_bounds__(256) void contour_match_kernel(const CfP p) {
+    extern __shared__ unsigned bd_lds[];                                      // the counters (when a frame can count), the two tiles, the lists
+    __shared__ unsigned n_list[4];                                            // per plane: the contour pixels, those left to the second round
+    const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
+    const int H = p.H, W = p.W, R = p.R, n_cls = p.n_cls, nb1 = p.n_bands + 1;
+    const int nh = p.counts != nullptr ? 2 * nb1 * n_cls : 0;
+    const int rows = BD_TH + 2 * R, P = (BD_TW + 2 * R + 3) & ~3;             // a staged plane: row r, column c is the pixel (y0 - R + r, x0 - R + c)
+    const int R1 = R < CF_R1 ? R : CF_R1;
+    const bool planes = p.lmatch != nullptr || p.pmatch != nullptr;
+    unsigned *lh = bd_lds;
+    unsigned char *tile = reinterpret_cast<unsigned char *>(bd_lds + nh);     // [2][rows][P]
+    unsigned short *list = reinterpret_cast<unsigned short *>(tile + 2 * rows * P);          // [BD_TH * BD_TW]: the plane's contour pixels
+    unsigned short *later = list + BD_TH * BD_TW;                             // [BD_TH * BD_TW]: those the first round leaves
+    const unsigned r0sq = (unsigned)(p.radii[0] * p.radii[0]);
+    const size_t frame = (size_t)H * (size_t)W, plane = (size_t)p.N * frame;
+    const long long total = 2ll * (long long)plane;
+    const int tiles_x = (W + BD_TW - 1) / BD_TW, tiles = tiles_x * ((H + BD_TH - 1) / BD_TH);
+    for (int n = blockIdx.y; n < p.N; n += gridDim.y) {
+        const int g = p.counts == nullptr ? -1 : (p.group != nullptr ? p.group[n] : 0);
+        const bool count = g >= 0 && g < p.n_groups;                          // uniform over the workgroup
+        if (!count && !planes) continue;
+        if (count) {
+            for (int i = tid; i < nh; i += 256) lh[i] = 0u;
+            __syncthreads();
+        }
+        unsigned char *lout = p.lmatch != nullptr ? p.lmatch + (size_t)n * (size_t)p.lns : nullptr;
+        unsigned char *pout = p.pmatch != nullptr ? p.pmatch + (size_t)n * (size_t)p.pns : nullptr;
+        for (int t = blockIdx.x; t < tiles; t += gridDim.x) {                 // uniform: every thread makes every pass
+            const int x0 = (t % tiles_x) * BD_TW, y0 = (t / tiles_x) * BD_TH;
+            if (tid < 4) n_list[tid] = 0u;
+            // half a wave per staged row, four marks per lane: lane j of the half takes the columns 4 j .. 4 j + 3
+            for (int r = 2 * wave + (lane >> 5); r < rows; r += 8) {
+                const int j = lane & 31, y = y0 - R + r, x = x0 - R + 4 * j;
+                if (4 * j >= P) continue;
+                unsigned keep = 0;                                            // 0xff per column inside the image
+#pragma unroll
+                for (int b = 0; b < 4; ++b) keep |= y >= 0 && y < H && x + b >= 0 && x + b < W ? 0xffu << (8 * b) : 0u;
+                unsigned wl = 0, wp = 0;
+                if (keep) {
+                    const long long e = (long long)((size_t)n * frame) + (long long)y * W + x;
+                    wl = cf_load4(p.marks, e, total);
+                    wp = cf_load4(p.marks, (long long)plane + e, total);
+                }
+                const unsigned none = (CF_NONE * 0x01010101u) & ~keep;
+                *reinterpret_cast<unsigned *>(tile + r * P + 4 * j) = (wl & keep) | none;
+                *reinterpret_cast<unsigned *>(tile + (rows + r) * P + 4 * j) = (wp & keep) | none;
+            }
+            __syncthreads();
+            if (planes)                                                       // 255 where there is no contour pixel; those get their band below
+                for (int ly = wave; ly < BD_TH; ly += 4) {                    // lane = column: rows of 64 bytes go out together
+                    const int y = y0 + ly, x = x0 + lane;
+                    if (y < H && x < W) {
+                        if (lout != nullptr && tile[(R + ly) * P + R + lane] == CF_NONE) lout[(size_t)y * (size_t)p.lpitch + x] = (unsigned char)BD_VOID;
+                        if (pout != nullptr && tile[(rows + R + ly) * P + R + lane] == CF_NONE) pout[(size_t)y * (size_t)p.ppitch + x] = (unsigned char)BD_VOID;
+                    }
+                }
+#pragma unroll
+            for (int s = 0; s < 2; ++s) {                                     // a lane per contour pixel of plane s, sought on the other plane
+                const unsigned char *mine = tile + (s * rows + R) * P + R, *theirs = tile + ((1 - s) * rows + R) * P + R;
+                unsigned char *out = s == 0 ? lout : pout;
+                const size_t opitch = (size_t)(s == 0 ? p.lpitch : p.ppitch);
+                cf_compact(mine, P, list, n_list + 2 * s, lane, wave);
+                __syncthreads();
+                // Two rounds.  The first seeks within R1 rings only; what it finds there is final (every later ring is farther), and most
+                // contour pixels of a fair prediction end here.  The others -- a few per wave, unmatched ones among them, whose search is
+                // the whole disc -- are compacted again, so that the long searches fill whole waves instead of holding one up each, and
+                // are sought by rows, four marks a read (cf_scan).
+                for (int round = 0; round < 2; ++round) {
+                    const unsigned short *from = round == 0 ? list : later;
+                    const int n_from = (int)n_list[2 * s + round], reach = round == 0 ? R1 : R;
+                    for (int base = 64 * wave; base < n_from; base += 256) {  // uniform over the wave: the ballots and bd_tally need every lane
+                        const bool have = base + lane < n_from;
+                        unsigned band = 0, c = 0, at = 0;
+                        bool done = false, counts = false;
+                        if (have) {
+                            at = from[base + lane];
+                            const int ly = (int)(at >> 6), lx = (int)(at & 63u);
+                            const unsigned m = mine[ly * P + lx];
+                            c = m & 31u;
+                            counts = (m & CF_COUNTS) != 0u;
+                            const unsigned m2 = round == 0 ? cf_search(theirs + ly * P + lx, P, c, reach, r0sq)
+                                                           : cf_scan(theirs + ly * P - R, R + lx, P, c, R, r0sq);
+                            done = reach == R || m2 <= (unsigned)(reach * reach);
+                            band = cf_band(m2, p.radii, p.n_bands);
+                            if (done && out != nullptr) out[(size_t)(y0 + ly) * opitch + (size_t)(x0 + lx)] = (unsigned char)band;
+                        }
+                        if (round == 0 && R1 < R) cf_push(later, n_list + 2 * s + 1, have && !done, at, lane);
+                        if (count) {
+                            const bool active = done && counts;
+                            bd_tally(lh, active ? ((unsigned)(s * nb1) + band) * (unsigned)n_cls + c : 0u, active, lane);
+                        }
+                    }
+                    __syncthreads();                                          // the second round's list is complete; then: before the next plane's lists
+                }
+            }
+        }
+        if (count) {
+            __syncthreads();
+            unsigned long long *counts = p.counts + (size_t)g * (size_t)nh;
+            for (int i = tid; i < nh; i += 256)
+                if (lh[i]) atomicAdd(counts + i, (unsigned long long)lh[i]);
+            __syncthreads();                                                  // before the next frame clears them
+        }
+    }
+}
+
 }  // namespace
 
 // 2 bytes per pixel, rounded up to 16 bytes in all; a size that does not fit size_t comes back as its largest value, which no workspace has
@@ -469,5 +765,51 @@ extern "C" int arseg_boundary_iou_fwd(const int64_t *label, const int32_t *pred,
     const size_t lds = (counts != nullptr ? 4 * (size_t)3 * (n_bands + 1) * n_cls : 0) + 2 * 2 * (size_t)(BD_TH + 2 * p.R) * BI_PITCH +
                        (label_band_out != nullptr || pred_band_out != nullptr ? (size_t)BD_TH * BI_OPITCH : 0);                      // <= 58496
     hipLaunchKernelGGL(boundary_cols_kernel, dim3(gx, gy), dim3(256), lds, st, p);
+    return arseg_launch_status();
+}
+
+// a mark per pixel and plane, 2 N H W bytes rounded up to 16 in all; saturating as arseg_label_bands_workspace_bytes does
+extern "C" size_t arseg_contour_f_workspace_bytes(int N, int H, int W) {
+    if (N <= 0 || H <= 0 || W <= 0 || H > 16384 || W > 16384) return 0;
+    const size_t none = ~(size_t)0;
+    size_t bytes = 2 * (size_t)H * (size_t)W;
+    if (__builtin_mul_overflow(bytes, (size_t)N, &bytes) || bytes > none - 15) return none;
+    return (bytes + 15) & ~(size_t)15;
+}
+
+extern "C" int arseg_contour_f_fwd(const int64_t *label, const int32_t *pred, const int32_t *group, const int *radii, int n_bands,
+                                   uint8_t *label_match_out, int64_t label_match_pitch, int64_t label_match_n_stride, uint8_t *pred_match_out,
+                                   int64_t pred_match_pitch, int64_t pred_match_n_stride, int64_t *counts, int N, int n_groups, int n_cls, int H,
+                                   int W, int ignore_label, void *workspace, size_t workspace_bytes, arseg_stream_t stream) {
+    ARSEG_CHECK_PTR(label); ARSEG_CHECK_PTR(pred); ARSEG_CHECK_PTR(workspace); ARSEG_CHECK_PTR(radii);
+    ARSEG_CHECK_POS(N); ARSEG_CHECK_POS(H); ARSEG_CHECK_POS(W);
+    if (H > 16384 || W > 16384 || n_cls < 1 || n_cls > 32 || n_groups < 1 || n_bands < 1 || n_bands > BD_NBMAX) return ARSEG_EINVAL;
+    for (int k = 0; k < n_bands; ++k)
+        if (radii[k] < 0 || radii[k] > CF_RMAX || (k > 0 && radii[k] <= radii[k - 1])) return ARSEG_EINVAL;
+    if (group == nullptr && n_groups > 1) return ARSEG_EINVAL;
+    if (label_match_out == nullptr && pred_match_out == nullptr && counts == nullptr) return ARSEG_EINVAL;
+    if (label_match_out != nullptr && (label_match_pitch < (int64_t)W || label_match_n_stride < 0)) return ARSEG_EINVAL;
+    if (pred_match_out != nullptr && (pred_match_pitch < (int64_t)W || pred_match_n_stride < 0)) return ARSEG_EINVAL;
+    if ((reinterpret_cast<uintptr_t>(label) & 7u) || (reinterpret_cast<uintptr_t>(counts) & 7u) || (reinterpret_cast<uintptr_t>(pred) & 3u) ||
+        (reinterpret_cast<uintptr_t>(group) & 3u) || (reinterpret_cast<uintptr_t>(workspace) & 1u))
+        return ARSEG_EINVAL;
+    const size_t need = arseg_contour_f_workspace_bytes(N, H, W);
+    if (need == ~(size_t)0 || workspace_bytes < need) return ARSEG_EWORKSPACE;
+    CfP p = {};
+    p.label = reinterpret_cast<const long long *>(label); p.pred = pred; p.group = group;
+    p.lmatch = label_match_out; p.pmatch = pred_match_out; p.counts = reinterpret_cast<unsigned long long *>(counts);
+    p.marks = static_cast<unsigned char *>(workspace);
+    p.lpitch = label_match_pitch; p.lns = label_match_n_stride; p.ppitch = pred_match_pitch; p.pns = pred_match_n_stride;
+    for (int k = 0; k < n_bands; ++k) p.radii[k] = radii[k];
+    p.N = N; p.H = H; p.W = W; p.n_groups = n_groups; p.n_cls = n_cls; p.n_bands = n_bands; p.R = radii[n_bands - 1];
+    p.ignore_label = ignore_label;
+    hipStream_t st = arseg_stream(stream);
+    const int gy = N < 65535 ? N : 65535, share = 4096 / gy;
+    const int tiles = ((W + BD_TW - 1) / BD_TW) * ((H + BD_TH - 1) / BD_TH);
+    const int gx = tiles < share ? tiles : (share < 1 ? 1 : share);
+    hipLaunchKernelGGL(contour_marks_kernel, dim3(gx, gy), dim3(256), 0, st, p);
+    const size_t side = (size_t)(BD_TW + 2 * p.R), pitch = (side + 3) & ~(size_t)3;
+    const size_t lds = (counts != nullptr ? 4 * (size_t)2 * (n_bands + 1) * n_cls : 0) + 2 * side * pitch + 2 * 2 * (size_t)BD_TH * BD_TW;         // <= 51456
+    hipLaunchKernelGGL(contour_match_kernel, dim3(gx, gy), dim3(256), lds, st, p);
     return arseg_launch_status();
 }

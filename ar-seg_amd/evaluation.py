@@ -11,6 +11,8 @@
   (trimap bands; no reference counterpart), from the same one pass.
 * ``EvalByBoundary`` / ``BoundaryTable`` / ``boundary_iou_numpy`` -- Boundary IoU per keyframe distance (the ground truth's band
   intersected with the prediction's; no reference counterpart), from the same one pass.
+* ``EvalByContour`` / ``ContourTable`` / ``contour_f_numpy`` -- the contour F-measure per keyframe distance (precision and recall of
+  the class contours within a pixel tolerance, the F of DAVIS's J & F; no reference counterpart), from the same one pass.
 * ``alter_res_step_fast`` -- the same non-keyframe step on the kernel-native layouts (int16 MVs in,
   MV resize + warp + CReFF + head fused), used by the GOP runner and bench.py.
 
@@ -627,6 +629,189 @@ class EvalByBoundary(EvalByDistance):
                              ignore_label=self.ignore_label, border=self.border)
         if counts is None:
             raise ValueError("EvalByBoundary: the loader gave no sample")
+        return counts
+
+
+def contour_f_numpy(label, pred, radii, n_cls, ignore_label=255):
+    """The host form of ``ops.contour_f``'s counts (include/arseg_hip.h, arseg_contour_f_fwd), numpy only and written the published way
+    (the dilation of DAVIS's F-measure, the distance threshold of bfscore): ``label`` and ``pred`` integer arrays [..., H, W] -> int64
+    [2, len(radii) + 1, n_cls], the frames summed.  Per class the contour map of each plane (the class's pixels with another class among
+    their 8 neighbours), dilated by the disc dx^2 + dy^2 <= r^2 through shifted ORs and ANDed with the other plane's contours, gives the
+    contour pixels matched within r; differences of consecutive radii give the disjoint bands, the whole contour the last one."""
+    rad = ops.contour_radii(radii)
+    lab, prd = np.asarray(label), np.asarray(pred)
+    if lab.ndim < 2 or lab.shape != prd.shape or not np.issubdtype(lab.dtype, np.integer) or not np.issubdtype(prd.dtype, np.integer):
+        raise ValueError(f"contour_f_numpy takes two integer arrays [..., H, W] of one shape, got {lab.dtype} {lab.shape} and {prd.dtype} {prd.shape}")
+    lab, prd = lab.astype(np.int64), prd.astype(np.int64)
+    lab = np.where((lab >= 0) & (lab < n_cls) & (lab != ignore_label), lab, 255)
+    prd = np.where((prd >= 0) & (prd < n_cls), prd, 255)
+    counting = (lab != 255) & (prd != 255)
+    H, W = lab.shape[-2:]
+
+    def shifted(m, dy, dx):
+        """m moved by (dy, dx): out[y, x] = m[y - dy, x - dx], False where that is outside the image."""
+        out = np.zeros_like(m)
+        if abs(dy) < H and abs(dx) < W:
+            out[..., max(dy, 0):H + min(dy, 0), max(dx, 0):W + min(dx, 0)] = m[..., max(-dy, 0):H + min(-dy, 0), max(-dx, 0):W + min(-dx, 0)]
+        return out
+
+    def contour(plane, c):
+        other = (plane != c) & (plane != 255)
+        near = np.zeros_like(other)
+        for dy in (-1, 0, 1):
+            for dx in (-1, 0, 1):
+                near |= shifted(other, dy, dx)
+        return (plane == c) & near
+
+    def dilated(m, r):
+        out = np.zeros_like(m)
+        for dy in range(-r, r + 1):
+            for dx in range(-r, r + 1):
+                if dy * dy + dx * dx <= r * r:
+                    out |= shifted(m, dy, dx)
+        return out
+
+    out = np.zeros((2, len(rad) + 1, n_cls), np.int64)
+    for c in range(n_cls):
+        cg, cp = contour(lab, c), contour(prd, c)
+        if not cg.any() and not cp.any():
+            continue
+        before = np.zeros(2, np.int64)
+        for k, r in enumerate(rad):
+            within = np.array([(cg & dilated(cp, r) & counting).sum(), (cp & dilated(cg, r) & counting).sum()], np.int64)
+            out[:, k, c], before = within - before, within
+        out[:, len(rad), c] = np.array([(cg & counting).sum(), (cp & counting).sum()], np.int64) - before
+    return out
+
+
+def alter_res_batch_contour(lr_net, ref_ps, imgs, mv_qs, labels, radii, scale=0.5, counts=None, ignore_label=255, groups=None, n_groups=1):
+    """``alter_res_batch_pred``'s sibling for the contour F-measure: the same phases and tail (its pred, without a label), then
+    ``ops.contour_f`` of that pred against ``labels`` (int64 [B,H,W]) -> (pred int32 [B,H,W], counts int64
+    [n_groups, 2, len(radii) + 1, n_cls], accumulated when given).  ``groups`` / ``n_groups`` as ``ops.contour_f`` takes them.
+    Nothing comes to the host in between."""
+    pred, _ = alter_res_batch_pred(lr_net, ref_ps, imgs, mv_qs, scale=scale)
+    n_cls = counts.shape[-1] if counts is not None else _unwrap(lr_net).final_conv.out_channels
+    counts, _, _ = ops.contour_f(labels, pred, radii, groups=groups, n_groups=n_groups, n_cls=n_cls, counts=counts, ignore_label=ignore_label)
+    return pred, counts
+
+
+class ContourTable(object):
+    """Contour precision, recall and F per keyframe distance from a [G, 2, n_bands + 1, n_cls] tensor of counts (``EvalByContour``,
+    ``ops.contour_f``): ``counts`` and ``radii``.  ``recall(k)`` / ``precision(k)`` float32 [G, n_cls]: the contour pixels of the ground
+    truth / of the prediction matched within radii[k] (the bands 0 .. k summed) over all of them, in ``EvalTable``'s float32 arithmetic,
+    0 / 0 = NaN (the class has no contour on that plane); ``f(k)`` = 2 P R / (P + R), NaN where P or R is, 0 where P + R == 0;
+    ``mean_f(k)`` the G class means as Python floats and ``mean(k)`` their float64 mean as ``EvalTable`` takes it.  The means are plain
+    means, as the sibling tables': a group's ``mean_f(k)`` is NaN as soon as ONE class has no contour on either plane in that group, and
+    then so are ``mean(k)`` and that entry of every row of ``as_array()`` -- with rare classes at a keyframe distance, read ``f(k)`` and
+    average the classes that are there (``torch.nanmean(table.f(k), dim=1)``).  Plain torch / numpy; works on CPU tensors."""
+
+    def __init__(self, counts, radii):
+        counts = torch.as_tensor(counts)
+        self.radii = ops.contour_radii(radii)
+        if counts.dim() != 4 or counts.shape[1] != 2 or counts.shape[2] != len(self.radii) + 1:
+            raise ValueError(f"ContourTable takes [G, 2, {len(self.radii) + 1}, n_cls] counts, got {tuple(counts.shape)}")
+        self.counts = counts
+
+    def _ratio(self, row, k):
+        if self.counts is None:
+            raise ValueError("a table read from a file holds the mean values only, not the counts")
+        if not 0 <= k < len(self.radii):
+            raise IndexError(f"radius {k} of {len(self.radii)}")
+        c = self.counts[:, row]
+        return c[:, :k + 1].sum(dim=1).float() / c.sum(dim=1).float()
+
+    def _f(self, k):
+        p, r = self._ratio(1, k), self._ratio(0, k)
+        f = 2 * p * r / (p + r)
+        return torch.where((p + r) == 0, torch.zeros_like(f), f)             # 0 / 0 here is "nothing matched", not "no contour"
+
+    def precision(self, k):
+        return self._ratio(1, k).cpu()
+
+    def recall(self, k):
+        return self._ratio(0, k).cpu()
+
+    def f(self, k):
+        return self._f(k).cpu()
+
+    def mean_f(self, k):
+        return [f.mean().item() for f in self._f(k)]                          # on the counts' device, as EvalTable does
+
+    def mean(self, k):
+        return np.array(self.mean_f(k)).mean()
+
+    def as_array(self):
+        """[n_bands, G + 1]: the mean F at radii[0], radii[1], ...; each row the G values and their mean, as ``EvalTable.as_array``."""
+        if self.counts is None:
+            return self._array
+        rows = [self.mean_f(k) for k in range(len(self.radii))]
+        return np.stack([np.array(list(r) + [np.array(r).mean()]) for r in rows])
+
+    def save(self, path):
+        np.savetxt(path, self.as_array(), header="contour radii " + " ".join(str(r) for r in self.radii))
+
+    @classmethod
+    def load(cls, path):
+        """A table written by ``save``: the radii and the floats only (``counts`` is None; ``as_array`` gives them back)."""
+        with open(path) as f:
+            head = f.readline().split()
+        if head[:3] != ["#", "contour", "radii"] or len(head) < 4:
+            raise ValueError(f"{path}: not a ContourTable file (no contour radii line)")
+        t = cls.__new__(cls)
+        t.radii = ops.contour_radii(head[3:])
+        vals = np.atleast_2d(np.loadtxt(path))
+        if vals.shape[0] != len(t.radii) or vals.shape[1] < 2:
+            raise ValueError(f"{path}: expected {len(t.radii)} rows of G mean values and their mean, got {vals.shape}")
+        t.counts, t._array = None, vals
+        return t
+
+
+class EvalByContour(EvalByDistance):
+    """``EvalByDistance`` with the contour F-measure: the same samples, keyframe handling (d = 0 through the HR net) and operand-range
+    fallback, one pass, and per keyframe distance the counts of ``ops.contour_f`` (include/arseg_hip.h, arseg_contour_f_fwd).  ``radii``
+    in pixels; None takes ``ops.contour_radius`` of the first label's size, DAVIS's 0.8 % of the diagonal.  One
+    [gop, 2, len(radii) + 1, n_cls] tensor, all-reduced once under torch.distributed.  Returns a ``ContourTable``."""
+
+    def __init__(self, scale=0.5, ignore_label=255, gop=12, cache_keyframe=False, radii=None):
+        super().__init__(scale, ignore_label, gop, cache_keyframe)
+        self.radii = None if radii is None else ops.contour_radii(radii)
+
+    def __call__(self, highres_net, net, dl, n_classes):
+        first = self.hr_forwards
+        used = [self.radii]
+
+        def reset():
+            self.hr_forwards = first
+
+        counts = _range_safe_hist(lambda: self._run(highres_net, net, dl, n_classes, used), dl, reset)
+        if dist.is_available() and dist.is_initialized():
+            dist.all_reduce(counts, dist.ReduceOp.SUM)               # integer counts: exact
+        return ContourTable(counts, used[0])
+
+    def _run(self, highres_net, net, dl, n_classes, used):
+        counts = None
+        lr_net = _unwrap(net)
+        cache = [None, None]
+        for sample in dl:
+            label = sample[1].cuda()
+            N = label.shape[0]
+            if counts is None:
+                if used[0] is None:
+                    used[0] = ops.contour_radii((ops.contour_radius(label.shape[-2], label.shape[-1]),))      # above 32: refused
+                counts = torch.zeros((self.gop, 2, len(used[0]) + 1, n_classes), dtype=torch.int64, device="cuda")
+            if len(sample) == 3:
+                out = highres_net(sample[0].cuda())[0]
+                groups = [0] * N
+            elif len(sample) == 6:
+                imgs, _, _, ref_imgs, flow, d = sample
+                out = self._logits(highres_net, lr_net, imgs, ref_imgs, flow, cache)
+                groups = self._groups(d, N)
+            else:
+                raise ValueError(f"EvalByContour takes (imgs, label, _) or (imgs, label, _, ref_imgs, flow, dist) samples, got {len(sample)} elements")
+            pred, _ = ops.argmax_confusion_grouped(out, None, groups, self.gop, label.shape[-2], label.shape[-1])
+            ops.contour_f(label, pred, used[0], groups=groups, n_groups=self.gop, n_cls=n_classes, counts=counts, ignore_label=self.ignore_label)
+        if counts is None:
+            raise ValueError("EvalByContour: the loader gave no sample")
         return counts
 
 

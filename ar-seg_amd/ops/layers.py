@@ -784,3 +784,73 @@ def boundary_iou(label: torch.Tensor, pred: torch.Tensor, radii, groups=None, n_
            _ptr(workspace), workspace.numel() * workspace.element_size(), _stream(),
            nbytes=N * H * W * (12 + 8 + (1 if label_band_out is not None else 0) + (1 if pred_band_out is not None else 0)))
     return counts, label_band_out, pred_band_out
+
+
+def contour_radii(radii) -> tuple:
+    """The radii of ``contour_f`` as a tuple of ints after their check: 1 .. 8 of them, each in 0 .. 32, strictly ascending."""
+    r = tuple(int(v) for v in radii)
+    if not 1 <= len(r) <= 8 or any(not 0 <= v <= 32 for v in r) or any(b <= a for a, b in zip(r, r[1:])):
+        raise ValueError(f"radii: 1 to 8 strictly ascending integers in 0..32, got {r}")
+    return r
+
+
+def contour_radius(H: int, W: int, ratio: float = 0.008) -> int:
+    """The contour tolerance of the DAVIS protocol's F-measure in pixels: ``ratio`` of the image diagonal, rounded up."""
+    return int(math.ceil(ratio * math.sqrt(H * H + W * W)))
+
+
+def contour_f(label: torch.Tensor, pred: torch.Tensor, radii, groups=None, n_groups: int = 1, n_cls: Optional[int] = None,
+              counts: Optional[torch.Tensor] = None, ignore_label: int = 255, label_match_out=None, pred_match_out=None,
+              workspace: Optional[torch.Tensor] = None):
+    """Contour F-measure counts from matched class contours (include/arseg_hip.h, arseg_contour_f_fwd): ``label`` int64 [N,H,W] and
+    ``pred`` int32 [N,H,W] -> ``counts`` int64 [n_groups, 2, len(radii) + 1, n_cls], accumulated: the contour pixels of the ground truth
+    (row 0) and of the prediction (row 1) per class and band of Euclidean distance to the nearest contour pixel of the same class on the
+    other plane -- band k: within radii[k] and not within radii[k - 1]; the last band: unmatched.  Recall at radii[k] is row 0 summed over
+    the bands 0 .. k over row 0 summed over all bands, precision the same on row 1 (``evaluation.ContourTable``).  ``groups`` as
+    ``argmax_confusion_grouped`` takes them, or None with ``n_groups == 1``.  ``n_cls``: default ``counts.shape[-1]``.
+    ``label_match_out`` / ``pred_match_out``: a uint8 [N,H,W] plane (rows contiguous, any pitch / image stride) for the band of every
+    contour pixel of that plane (255 elsewhere), True to have it allocated, None for no plane.  ``workspace``: a device tensor of at
+    least ``arseg_contour_f_workspace_bytes(N, H, W)`` bytes (default: the stream's shared one).  One ABI call; with every buffer given
+    nothing is allocated and nothing synchronises.  Returns (counts, label plane or None, pred plane or None)."""
+    what = "contour_f"
+    rad = contour_radii(radii)
+    ids = None if groups is None else _group_ids(groups, n_groups)
+    if groups is None and n_groups != 1:
+        raise ValueError(f"{what}: groups=None needs n_groups == 1, got {n_groups}")
+    _need_gpu(label, dtype=torch.int64)
+    if label.dim() != 3 or not label.is_contiguous():
+        raise _lib.ArsegError(f"{what}: label must be a contiguous int64 [N,H,W] tensor, got {tuple(label.shape)} strides {label.stride()}")
+    N, H, W = label.shape
+    dev = label.device
+    _need_gpu(pred, dtype=torch.int32)
+    if tuple(pred.shape) != (N, H, W) or not pred.is_contiguous() or pred.device != dev:
+        raise _lib.ArsegError(f"{what}: pred must be a contiguous int32 {(N, H, W)} tensor on {dev}, got {tuple(pred.shape)} on {pred.device}")
+    if n_cls is None:
+        if counts is None:
+            raise ValueError(f"{what}: n_cls is required without counts")
+        n_cls = counts.shape[-1]
+    n_cls = int(n_cls)
+    if not 1 <= n_cls <= 32:
+        raise ValueError(f"{what}: 1..32 classes, got {n_cls}")
+    grp = None if groups is None else _groups_tensor(groups, ids, N, dev)
+    shape = (n_groups, 2, len(rad) + 1, n_cls)
+    if counts is None:
+        counts = torch.zeros(shape, dtype=torch.int64, device=dev)
+    elif tuple(counts.shape) != shape or counts.dtype != torch.int64 or counts.device != dev or not counts.is_contiguous():
+        raise _lib.ArsegError(f"{what}: counts must be a contiguous int64 GPU tensor {list(shape)}, got {counts.dtype} {tuple(counts.shape)}")
+    label_match_out, lpitch, lns = _band_plane(what, "label_match_out", label_match_out, N, H, W, dev)
+    pred_match_out, ppitch, pns = _band_plane(what, "pred_match_out", pred_match_out, N, H, W, dev)
+    lib = _lib.load()
+    need = lib.arseg_contour_f_workspace_bytes(N, H, W)
+    if need == 0:
+        raise ValueError(f"{what}: frames of 1..16384 rows and columns, got {H}x{W}")
+    if workspace is None:
+        workspace = _stream_workspace(need, dev)
+    elif not workspace.is_cuda or workspace.device != dev or not workspace.is_contiguous() or workspace.data_ptr() % 2 or \
+            workspace.numel() * workspace.element_size() < need:
+        raise _lib.ArsegError(f"{what}: workspace must be a contiguous, 2-byte aligned tensor of at least {need} bytes on {dev}")
+    launch(what, lib.arseg_contour_f_fwd, _ptr(label), _ptr(pred), _ptr(grp), (ctypes.c_int * len(rad))(*rad), len(rad),
+           _ptr(label_match_out), lpitch, lns, _ptr(pred_match_out), ppitch, pns, _ptr(counts), N, n_groups, n_cls, H, W, int(ignore_label),
+           _ptr(workspace), workspace.numel() * workspace.element_size(), _stream(),
+           nbytes=N * H * W * (12 + 4 + (1 if label_match_out is not None else 0) + (1 if pred_match_out is not None else 0)))
+    return counts, label_match_out, pred_match_out

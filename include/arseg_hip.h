@@ -1387,6 +1387,54 @@ int arseg_boundary_iou_fwd(const int64_t *label, const int32_t *pred, const int3
                            int W, int ignore_label, void *workspace, size_t workspace_bytes, arseg_stream_t stream);
 
 /* ---------------------------------------------------------------------------------------------
+ * Contour F-measure counts from matched class contours (csrc/bands.hip): per class the contour pixels of the ground truth and of the
+ * prediction, by the distance to the nearest contour pixel of the same class on the other plane -- the precision and recall of the
+ * contours within a pixel tolerance, the F of the DAVIS protocol's "J & F" and the BF score of Csurka et al. (Matlab's bfscore).  No
+ * reference counterpart.
+ * Bytes.     label is int64 [N][H][W], pred int32 [N][H][W], both contiguous and both required.  Labels and predictions become bytes
+ *            exactly as in the entry point above: a label is itself if 0 <= label < n_cls and label != ignore_label, else 255; a
+ *            prediction is itself if 0 <= pred < n_cls, else 255.  1 <= n_cls <= 32.
+ * Contours.  On either byte plane a pixel with byte c != 255 is a contour pixel of class c exactly when one of its 8 neighbours INSIDE the
+ *            image has a byte that is neither c nor 255: the inner contour of each class mask.  The image border is no contour, and a
+ *            255 neighbour makes none: void areas hide the true contour, they are not evidence of one.  On a plane without 255 these
+ *            are the pixels with D(p) == 1 of arseg_label_bands_fwd.
+ * Match.     For a contour pixel p of class c on one plane, m2(p) is the smallest dx^2 + dy^2 to a contour pixel of class c on the OTHER
+ *            plane of the same frame: 0 if the other plane has one at p itself, infinite if it has none.  radii is a HOST array of
+ *            n_bands ints, strictly ascending, 0 <= radii[k] <= 32, 1 <= n_bands <= 8.  band(p) is the smallest k with
+ *            m2(p) <= radii[k]^2, and n_bands if there is none ("unmatched").  The tolerance is a disc, as DAVIS's dilation and
+ *            bfscore's distance threshold are, not the square of the two entry points above.  All arithmetic is integer.
+ * Counts.    group as in the entry points above (int32 [N] on the device; NULL only with n_groups == 1).  A pixel counts if neither of
+ *            its two bytes is 255 and its frame's group id g is in [0, n_groups).  counts is int64 [n_groups][2][n_bands + 1][n_cls],
+ *            ACCUMULATED; a counting contour pixel of class c of the label plane adds 1 to counts[g][0][band(p)][c], one of the
+ *            prediction plane to counts[g][1][band(p)][c].  Contour pixels that do not count are still match targets for the other
+ *            plane.  The bands are disjoint; cumulating them is the host's business: at radii[k] the recall of class c is row 0
+ *            summed over the bands 0 .. k divided by row 0 summed over all n_bands + 1 bands, the precision the same on row 1, and
+ *            F = 2 P R / (P + R).
+ * label_match_out, pred_match_out: uint8, row y of frame n at out + n * n_stride + y * pitch (bytes; pitch >= W, n_stride >= 0);
+ *            OVERWRITTEN, for every frame and pixel: band(p) at every contour pixel of that plane, counting or not, 255 elsewhere.
+ *            Each may be NULL; counts may be NULL if a plane is given.
+ * workspace: the caller's, 2-byte aligned, >= arseg_contour_f_workspace_bytes(N, H, W) bytes (else ARSEG_EWORKSPACE): one byte per pixel
+ *            and plane, 2 N H W bytes rounded up to 16 (0 for dimensions the entry point refuses; a size that does not fit size_t
+ *            gives SIZE_MAX).  Its contents are scratch.
+ * 2 launches (marks: both planes' bytes and their 3 x 3 contour test; match: the search, the bands, the tally), sized on the host; no
+ *            workgroup waits for another.  Enqueue only: no allocation, no synchronisation; capturable in a HIP graph.  The buffers
+ *            must not overlap.  Malformed labels and predictions only ever give the byte 255; nothing outside the caller's buffers is
+ *            read or written, and every loop is bounded.
+ * ARSEG_EINVAL, before any launch and before ARSEG_EWORKSPACE: a null label, pred, radii or workspace; non-positive N, H or W; H > 16384
+ *            or W > 16384; n_bands outside 1..8, a radius outside 0..32 or radii that do not ascend strictly; n_cls outside 1..32;
+ *            n_groups < 1; a null group with n_groups > 1; all three outputs null; with a plane, its pitch < W or a negative n_stride;
+ *            label or counts not 8-byte aligned, pred or group not 4-byte aligned, the workspace not 2-byte aligned.
+ * Not covered: the both-sided contour of DAVIS's seg2bmap; one-to-one (bipartite) matching as in BSDS; the mean of per-frame F (the
+ *            counts are pooled per group; one group per frame gives it); a void neighbour or the image border as a contour; radii
+ *            above 32; the Chebyshev tolerance.
+ * ------------------------------------------------------------------------------------------- */
+size_t arseg_contour_f_workspace_bytes(int N, int H, int W);
+int arseg_contour_f_fwd(const int64_t *label, const int32_t *pred, const int32_t *group, const int *radii, int n_bands,
+                        uint8_t *label_match_out, int64_t label_match_pitch, int64_t label_match_n_stride, uint8_t *pred_match_out,
+                        int64_t pred_match_pitch, int64_t pred_match_n_stride, int64_t *counts, int N, int n_groups, int n_cls, int H,
+                        int W, int ignore_label, void *workspace, size_t workspace_bytes, arseg_stream_t stream);
+
+/* ---------------------------------------------------------------------------------------------
  * Measurement aids (no reference counterpart; BASELINE.md section 3: roofline fractions are reported against the datasheet peaks AND
  * against on-box micro-benchmarks).  bench.py times each with HIP events and prints `peaks_measured`.
  *   arseg_peak_stream_copy: dst[0 .. n_bytes) = src[0 .. n_bytes) with 16-byte accesses (n_bytes % 16 == 0, both 16-byte aligned):
