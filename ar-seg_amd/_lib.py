@@ -154,6 +154,7 @@ PROTOTYPES = {
     "arseg_segment_egress_fwd": (c_int, [_P] + [c_int] * 7 + [_P, _P, c_int64, c_int64, c_int, _P, _P, _P] + [c_int64] * 6 + [_P, _P, _P] + [c_int64] * 6
                                  + [_P, _P, _STREAM]),
     "arseg_segment_confidence_fwd": (c_int, [_P] + [c_int] * 9 + [_P, _P, c_int64, c_int64, _P, c_int64, c_int64, _P, _STREAM]),
+    "arseg_calibration_fwd": (c_int, [_P, _P, _P, _P] + [c_int] * 10 + [_STREAM]),
     "arseg_segment_consistency_fwd": (c_int, [_P] + [c_int] * 7 + [_P, c_int64, c_int64, _P, _P, _P, c_int64, c_int64, _P, c_int64, c_int64, _P, _STREAM]),
     "arseg_labels_consistency_fwd": (c_int, [_P, c_int64, c_int64] + [c_int] * 4 + [_P, c_int64, c_int64, _P, _P, c_int64, c_int64, _P, _STREAM]),
     "arseg_labels_consistency_linked_fwd": (c_int, [_P, c_int64, c_int64] + [c_int] * 4 + [_P, c_int64, c_int64, _P, _P, c_int64, c_int64, _P,

@@ -13,6 +13,9 @@
   intersected with the prediction's; no reference counterpart), from the same one pass.
 * ``EvalByContour`` / ``ContourTable`` / ``contour_f_numpy`` -- the contour F-measure per keyframe distance (precision and recall of
   the class contours within a pixel tolerance, the F of DAVIS's J & F; no reference counterpart), from the same one pass.
+* ``EvalByCalibration`` / ``CalibrationTable`` / ``calibration_numpy`` -- the reliability table of the 8-bit confidence code per
+  keyframe distance (pixels and right pixels per predicted class and code: ECE, MCE, risk-coverage, the threshold for a target
+  precision; no reference counterpart), from the same one pass.
 * ``alter_res_step_fast`` -- the same non-keyframe step on the kernel-native layouts (int16 MVs in,
   MV resize + warp + CReFF + head fused), used by the GOP runner and bench.py.
 
@@ -815,6 +818,212 @@ class EvalByContour(EvalByDistance):
         return counts
 
 
+_CAL_KINDS = ("top1", "margin")
+
+
+def calibration_numpy(logits, label, H, W, n_cls, groups=None, n_groups=1, ignore_label=255, kind="top1", align_corners=True):
+    """The host form of ``ops.calibration`` (include/arseg_hip.h, arseg_calibration_fwd), written from the contract in float64 with numpy
+    and torch on the CPU: fp32 ``logits`` [N,n_cls,h,w] -> F.interpolate(bilinear, ``align_corners``) -> per pixel the class k* (the first
+    maximum; a NaN counts as the maximum) and the code q = floor(255 c + 0.5) of the softmax's top-1 probability (``kind="top1"``) or of
+    its margin over the runner-up (``"margin"``), 0 where c is NaN; ``label`` an integer array [N,H,W] -> int64 [n_groups, n_cls, 256, 2]:
+    the pixels with 0 <= label < n_cls and label != ``ignore_label`` of the frames of group g at [g][k*][q][0], those with label == k*
+    at [g][k*][q][1].  ``groups``: one id per frame (a frame whose id is outside [0, n_groups) counts nowhere), None with one group.
+    float64 decides a pixel within fp32 rounding of a tie or of a code boundary its own way: the GPU tests hold the kernel to the
+    confidence launch's planes, and those to this arithmetic under tests/confidence_oracle.py's rule."""
+    import torch.nn.functional as F
+
+    x = np.asarray(logits)
+    lab = np.asarray(label)
+    H, W = int(H), int(W)
+    if kind not in _CAL_KINDS:
+        raise ValueError(f"calibration_numpy: kind is 'top1' or 'margin', got {kind!r}")
+    if x.ndim != 4 or x.shape[1] != n_cls or not 1 <= n_cls <= 32:
+        raise ValueError(f"calibration_numpy takes logits [N, n_cls, h, w] with 1..32 classes, got {x.shape} for n_cls = {n_cls}")
+    if lab.shape != (x.shape[0], H, W) or not np.issubdtype(lab.dtype, np.integer):
+        raise ValueError(f"calibration_numpy takes integer labels {(x.shape[0], H, W)}, got {lab.dtype} {lab.shape}")
+    if n_groups < 1 or (groups is None and n_groups != 1):
+        raise ValueError(f"calibration_numpy: groups=None needs n_groups == 1, got {n_groups}")
+    ids = [0] * x.shape[0] if groups is None else [int(g) for g in groups]
+    if len(ids) != x.shape[0]:
+        raise ValueError(f"groups names {len(ids)} frames, the batch has {x.shape[0]}")
+    v = torch.from_numpy(np.ascontiguousarray(x, dtype=np.float32)).double()
+    if tuple(v.shape[-2:]) != (H, W):
+        v = F.interpolate(v, size=(H, W), mode="bilinear", align_corners=bool(align_corners))
+    v = v.numpy()
+    isn = np.isnan(v)
+    k = np.where(isn.any(axis=1), isn.argmax(axis=1), np.where(isn, -np.inf, v).argmax(axis=1))
+    with np.errstate(all="ignore"):
+        e = np.exp(v - v.max(axis=1, keepdims=True))
+        p = np.sort(e / e.sum(axis=1, keepdims=True), axis=1)                  # a NaN anywhere makes the whole pixel NaN
+        c = p[:, -1] - (p[:, -2] if kind == "margin" and n_cls > 1 else 0.0)
+        q = np.where(np.isnan(c), 0.0, np.floor(255.0 * c + 0.5)).astype(np.int64)
+    lab = lab.astype(np.int64)
+    counting = (lab >= 0) & (lab < n_cls) & (lab != ignore_label)
+    out = np.zeros((n_groups, n_cls * 256 * 2), np.int64)
+    for n, g in enumerate(ids):
+        if 0 <= g < n_groups:
+            m = counting[n]
+            key = (k[n][m] * 256 + q[n][m]) * 2
+            out[g] += np.bincount(key, minlength=n_cls * 512) + np.bincount(key[lab[n][m] == k[n][m]] + 1, minlength=n_cls * 512)
+    return out.reshape(n_groups, n_cls, 256, 2)
+
+
+class CalibrationTable(object):
+    """Calibration of the 8-bit confidence code per keyframe distance from a [G, n_cls, 256, 2] tensor of counts (``EvalByCalibration``,
+    ``ops.calibration``): ``cal[g][k][q]`` = (pixels predicted k with code q, those of them that were right); ``kind`` the confidence the
+    codes stand for ("top1" or "margin").  Everything here is arithmetic on those integers: sums in int64, ratios in ``EvalTable``'s
+    float32, 0 / 0 = NaN (a group, class or bin without pixels).  The confidence of a pixel is its code / 255: the codes are the
+    confidence rounded to 8 bits, so the mean confidence of a bin is within 0.5 / 255 of the fp32 one, and so are ECE and MCE (the bin a
+    pixel falls into is decided by its code: ``bin(q) = q * n_bins // 256``).  Plain torch / numpy; works on CPU tensors.
+
+    ``counts(per_class=False)`` int64 [G, 256, 2] (or the [G, n_cls, 256, 2] tensor itself); ``accuracy()`` / ``confidence()`` float32
+    [G]; ``reliability(n_bins)`` -> (confidence, accuracy, weight), each [G, n_bins]; ``ece`` / ``mce`` / ``classwise_ece`` [G];
+    ``risk_coverage()`` -> (coverage, selective accuracy), each [G, 256], entry t keeping the pixels with q >= t; ``accuracy_below(low)``
+    [G]: the accuracy of the pixels ``egress.DriftMonitor``'s ``low`` flags (q < low); ``threshold_for(accuracy)`` int64 [G]: the
+    smallest t whose kept pixels reach that accuracy, 256 if none does; ``pooled()`` the table of all groups together."""
+
+    def __init__(self, cal, kind="top1"):
+        cal = torch.as_tensor(cal)
+        if cal.dim() != 4 or cal.shape[2] != 256 or cal.shape[3] != 2 or cal.dtype.is_floating_point:
+            raise ValueError(f"CalibrationTable takes integer [G, n_cls, 256, 2] counts, got {cal.dtype} {tuple(cal.shape)}")
+        if kind not in _CAL_KINDS:
+            raise ValueError(f"CalibrationTable: kind is 'top1' or 'margin', got {kind!r}")
+        self.cal = cal.long()
+        self.kind = kind
+
+    def counts(self, per_class=False):
+        return self.cal if per_class else self.cal.sum(dim=1)
+
+    @staticmethod
+    def _codes(c):
+        return torch.arange(256, dtype=torch.int64, device=c.device)
+
+    def accuracy(self):
+        c = self.counts()
+        return (c[..., 1].sum(dim=-1).float() / c[..., 0].sum(dim=-1).float()).cpu()
+
+    def confidence(self):
+        n = self.counts()[..., 0]
+        return ((n * self._codes(n)).sum(dim=-1).float() / (255 * n.sum(dim=-1)).float()).cpu()
+
+    @staticmethod
+    def _n_bins(n_bins):
+        n_bins = int(n_bins)
+        if not 1 <= n_bins <= 256:
+            raise ValueError(f"n_bins must be in 1..256, got {n_bins}")
+        return n_bins
+
+    def _binned(self, c, n_bins):
+        """counts [..., 256, 2] -> (confidence, accuracy, weight) [..., n_bins]"""
+        q = self._codes(c)
+        index = (q * n_bins // 256).expand(c.shape[:-1])
+        zero = torch.zeros(c.shape[:-2] + (n_bins,), dtype=torch.int64, device=c.device)
+        n = zero.scatter_add(-1, index, c[..., 0])
+        right = zero.scatter_add(-1, index, c[..., 1])
+        qn = zero.scatter_add(-1, index, c[..., 0] * q)
+        return qn.float() / (255 * n).float(), right.float() / n.float(), n.float() / n.sum(dim=-1, keepdim=True).float()
+
+    def reliability(self, n_bins=15):
+        return tuple(t.cpu() for t in self._binned(self.counts(), self._n_bins(n_bins)))
+
+    @staticmethod
+    def _ece(conf, acc, weight):
+        gap = torch.where(weight > 0, (acc - conf).abs() * weight, torch.zeros_like(weight))          # an empty bin: NaN x 0
+        return torch.where(weight.isnan().any(dim=-1), torch.full_like(gap[..., 0], float("nan")), gap.sum(dim=-1))
+
+    def ece(self, n_bins=15):
+        return self._ece(*self._binned(self.counts(), self._n_bins(n_bins))).cpu()
+
+    def mce(self, n_bins=15):
+        conf, acc, weight = self._binned(self.counts(), self._n_bins(n_bins))
+        gap = torch.where(weight > 0, (acc - conf).abs(), torch.full_like(weight, -1.0)).max(dim=-1).values
+        return torch.where(gap < 0, torch.full_like(gap, float("nan")), gap).cpu()
+
+    def classwise_ece(self, n_bins=15):
+        """The mean over the predicted classes present in a group of the ECE within the pixels predicted that class."""
+        per = self._ece(*self._binned(self.cal, self._n_bins(n_bins)))                                  # [G, n_cls], NaN: class not predicted
+        there = ~per.isnan()
+        return (torch.where(there, per, torch.zeros_like(per)).sum(dim=1) / there.sum(dim=1).float()).cpu()
+
+    def risk_coverage(self):
+        c = self.counts()
+        kept = c.flip(-2).cumsum(dim=-2).flip(-2)                                                       # [G, 256, 2]: q >= t
+        return (kept[..., 0].float() / c[..., 0].sum(dim=-1, keepdim=True).float()).cpu(), (kept[..., 1].float() / kept[..., 0].float()).cpu()
+
+    def accuracy_below(self, low):
+        low = int(low)
+        if not 0 <= low <= 256:
+            raise ValueError(f"low is a code threshold in 0..256, got {low}")
+        c = self.counts()[:, :low].sum(dim=1)
+        return (c[:, 1].float() / c[:, 0].float()).cpu()
+
+    def threshold_for(self, accuracy):
+        _, sel = self.risk_coverage()
+        ok = sel >= float(accuracy)                                                                     # NaN (nothing kept) compares False
+        first = torch.where(ok, self._codes(ok).expand_as(ok), torch.full_like(ok, 256, dtype=torch.int64))
+        return first.min(dim=-1).values
+
+    def pooled(self):
+        return CalibrationTable(self.cal.sum(dim=0, keepdim=True), self.kind)
+
+    def save(self, path):
+        """The counts and the kind as .npz (the integers, so every figure can be recomputed)."""
+        with open(path, "wb") as f:
+            np.savez_compressed(f, cal=self.cal.cpu().numpy(), kind=np.array(self.kind))
+
+    @classmethod
+    def load(cls, path):
+        with np.load(path) as z:
+            if "cal" not in z or "kind" not in z:
+                raise ValueError(f"{path}: not a CalibrationTable file (no cal / kind arrays)")
+            return cls(torch.from_numpy(z["cal"]), str(z["kind"]))
+
+
+class EvalByCalibration(EvalByDistance):
+    """``EvalByDistance`` with the reliability table of the confidence code: the same samples, keyframe handling (d = 0 through the HR net)
+    and operand-range fallback, one pass, and per keyframe distance the counts of ``ops.calibration`` (include/arseg_hip.h,
+    arseg_calibration_fwd) from the logits the distance evaluator's tail would have taken -- does a code of 200 at distance 9 mean what it
+    means at distance 1?  ``kind``: "top1" or "margin".  One [gop, n_cls, 256, 2] tensor, all-reduced once under torch.distributed.
+    Returns a ``CalibrationTable``."""
+
+    def __init__(self, scale=0.5, ignore_label=255, gop=12, cache_keyframe=False, kind="top1"):
+        super().__init__(scale, ignore_label, gop, cache_keyframe)
+        if kind not in _CAL_KINDS:
+            raise ValueError(f"EvalByCalibration: kind is 'top1' or 'margin', got {kind!r}")
+        self.kind = kind
+
+    def __call__(self, highres_net, net, dl, n_classes):
+        first = self.hr_forwards
+
+        def reset():
+            self.hr_forwards = first
+
+        cal = _range_safe_hist(lambda: self._run(highres_net, net, dl, n_classes), dl, reset)
+        if dist.is_available() and dist.is_initialized():
+            dist.all_reduce(cal, dist.ReduceOp.SUM)                  # integer counts: exact
+        return CalibrationTable(cal, self.kind)
+
+    def _run(self, highres_net, net, dl, n_classes):
+        cal = torch.zeros((self.gop, n_classes, 256, 2), dtype=torch.int64, device="cuda")
+        lr_net = _unwrap(net)
+        cache = [None, None]
+        for sample in dl:
+            label = sample[1].cuda()
+            N = label.shape[0]
+            if len(sample) == 3:
+                out = highres_net(sample[0].cuda())[0]
+                groups = [0] * N
+            elif len(sample) == 6:
+                imgs, _, _, ref_imgs, flow, d = sample
+                out = self._logits(highres_net, lr_net, imgs, ref_imgs, flow, cache)
+                groups = self._groups(d, N)
+            else:
+                raise ValueError(f"EvalByCalibration takes (imgs, label, _) or (imgs, label, _, ref_imgs, flow, dist) samples, got {len(sample)} elements")
+            ops.calibration(out.contiguous(), label, label.shape[-2], label.shape[-1], groups=groups, n_groups=self.gop, cal=cal, ignore_label=self.ignore_label,
+                            kind=self.kind)
+        return cal
+
+
 def alter_res_step_fast(lr_net, ref_p_nhwc, img, mv_q, scale=0.5):
     """One non-keyframe on the kernel-native layouts.
 
@@ -936,6 +1145,33 @@ def alter_res_batch_confidence(lr_net, ref_ps, imgs, mv_qs, scale=0.5, kind="top
     else:
         lo, _ = lr_net.phase2_warp(feat, list(ref_ps), mv_qs)
     return egress.confidence(lo, H, W, kind=kind, low=low, out=out, labels_out=labels_out, lut=lut, stats=stats, align_corners=not fused_up)
+
+
+def alter_res_batch_calibration(lr_net, ref_ps, imgs, mv_qs, labels, scale=0.5, cal=None, hist=None, ignore_label=255, groups=None, n_groups=1,
+                                kind="top1"):
+    """``alter_res_batch_pred``'s sibling for the reliability table: the same phase 1 and phase 2 and the same route decision, then
+    ``ops.calibration`` of the logits against ``labels`` (int64 [B,H,W]) -> (cal int64 [n_groups, n_cls, 256, 2], hist int64
+    [n_groups, n_cls, n_cls] | None), both accumulated when given.  ``hist``: True or a tensor to also run the grouped evaluator tail on
+    the same logits (``ops.argmax_confusion_grouped``, whose column sums and diagonal the table's sums over the codes are), None for the
+    table alone.  ``groups`` / ``n_groups`` as ``ops.calibration`` takes them.  Nothing comes to the host in between."""
+    lr_net = _unwrap(lr_net)
+    B, _, H, W = imgs.shape
+    h, w = _downscale_hw(H, W, scale)
+    feat = lr_net.phase1_nhwc4(ops.ingest_input(imgs, h, w, lr_net.storage_dtype), aux=ops.config.aux_outputs)[-1]
+    fused_up = hasattr(lr_net, "out_upsample")
+    if fused_up:
+        lo, _ = lr_net.phase2_warp(feat, list(ref_ps), mv_qs, upsample=False)
+        if (8 * lo.shape[-2], 8 * lo.shape[-1]) != (H, W):
+            lo, fused_up = ops.resize_nchw(lo, 8 * lo.shape[-2], 8 * lo.shape[-1], _lib.BILINEAR, False), False
+    else:
+        lo, _ = lr_net.phase2_warp(feat, list(ref_ps), mv_qs)
+    lo = lo.contiguous()
+    if hist is not None:
+        _, hist = ops.argmax_confusion_grouped(lo, labels, [0] * B if groups is None else groups, n_groups, H, W, None if hist is True else hist,
+                                               ignore_label, want_pred=False, align_corners=not fused_up)
+    cal = ops.calibration(lo, labels, H, W, groups=groups, n_groups=n_groups, cal=cal, ignore_label=ignore_label, kind=kind,
+                          align_corners=not fused_up)
+    return cal, hist
 
 
 def alter_res_batch_consistency(lr_net, ref_ps, imgs, mv_qs, key_labels, scale=0.5, lut=None, change_out=True, labels_out=True, stats=True):

@@ -854,3 +854,45 @@ def contour_f(label: torch.Tensor, pred: torch.Tensor, radii, groups=None, n_gro
            _ptr(workspace), workspace.numel() * workspace.element_size(), _stream(),
            nbytes=N * H * W * (12 + 4 + (1 if label_match_out is not None else 0) + (1 if pred_match_out is not None else 0)))
     return counts, label_match_out, pred_match_out
+
+
+_CAL_KINDS = {"top1": _lib.CONF_TOP1, "margin": _lib.CONF_MARGIN}
+
+
+def calibration(logits: torch.Tensor, label: torch.Tensor, H: int, W: int, groups=None, n_groups: int = 1, cal: Optional[torch.Tensor] = None,
+                ignore_label: int = 255, kind: str = "top1", align_corners: bool = True):
+    """Calibration counts of the confidence code (include/arseg_hip.h, arseg_calibration_fwd): head logits fp32 [N,n_cls,h,w] and ``label``
+    int64 [N,H,W] -> ``cal`` int64 [n_groups, n_cls, 256, 2], accumulated: per group of frames, predicted class k* and 8-bit code q
+    (``segment_confidence``'s labels and codes, bit for bit, ``kind`` and ``align_corners`` as it takes them) the pixels with a valid
+    label (column 0) and those of them whose label is k* (column 1).  Summed over the codes, column 0 is the column sums and column 1
+    the diagonal of ``argmax_confusion_grouped``'s hist.  ``groups`` as ``argmax_confusion_grouped`` takes them, or None with
+    ``n_groups == 1``.  One ABI call and one pass over the logits; with ``cal`` given nothing is allocated and nothing synchronises.
+    Returns cal (``evaluation.CalibrationTable`` reads it)."""
+    what = "calibration"
+    if kind not in _CAL_KINDS:
+        raise ValueError(f"{what}: kind is 'top1' or 'margin', got {kind!r}")
+    ids = None if groups is None else _group_ids(groups, n_groups)
+    if groups is None and n_groups != 1:
+        raise ValueError(f"{what}: groups=None needs n_groups == 1, got {n_groups}")
+    _need_gpu(logits)
+    if logits.dim() != 4 or not logits.is_contiguous():
+        raise _lib.ArsegError(f"{what}: logits must be a contiguous fp32 [N,n_cls,h,w] tensor, got {tuple(logits.shape)} strides {logits.stride()}")
+    N, n_cls, h, w = logits.shape
+    H, W = int(H), int(W)
+    dev = logits.device
+    if not 1 <= n_cls <= 32:
+        raise ValueError(f"{what}: 1..32 classes, got {n_cls}")
+    if H < 1 or W < 1:
+        raise ValueError(f"{what}: a positive output size, got {H}x{W}")
+    _need_gpu(label, dtype=torch.int64)
+    if tuple(label.shape) != (N, H, W) or not label.is_contiguous() or label.device != dev:
+        raise _lib.ArsegError(f"{what}: label must be a contiguous int64 {(N, H, W)} tensor on {dev}, got {tuple(label.shape)} on {label.device}")
+    grp = None if groups is None else _groups_tensor(groups, ids, N, dev)
+    shape = (n_groups, n_cls, 256, 2)
+    if cal is None:
+        cal = torch.zeros(shape, dtype=torch.int64, device=dev)
+    elif tuple(cal.shape) != shape or cal.dtype != torch.int64 or cal.device != dev or not cal.is_contiguous():
+        raise _lib.ArsegError(f"{what}: cal must be a contiguous int64 GPU tensor {list(shape)}, got {cal.dtype} {tuple(cal.shape)}")
+    launch(what, _lib.load().arseg_calibration_fwd, _ptr(logits), _ptr(label), _ptr(grp), _ptr(cal), N, n_groups, n_cls, h, w, H, W,
+           int(ignore_label), 1 if align_corners else 0, _CAL_KINDS[kind], _stream(), nbytes=logits.numel() * 4 + N * H * W * 8)
+    return cal

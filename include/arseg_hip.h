@@ -1435,6 +1435,36 @@ int arseg_contour_f_fwd(const int64_t *label, const int32_t *pred, const int32_t
                         int W, int ignore_label, void *workspace, size_t workspace_bytes, arseg_stream_t stream);
 
 /* ---------------------------------------------------------------------------------------------
+ * Calibration counts (csrc/calibration.hip): the reliability table of the confidence code -- per group of frames (keyframe distance),
+ * predicted class and 8-bit code how many pixels there were and how many of them were right -- from the logits and the ground truth in
+ * one launch for N frames and one pass over the logits; neither resized logits, probabilities nor the two byte planes exist.  ECE, MCE,
+ * class-wise ECE, risk-coverage and the threshold for a target precision are host arithmetic on these integers
+ * (arseg_amd.evaluation.CalibrationTable).  No reference counterpart.
+ * Logits.    logits, N, n_cls, h, w, H, W, align_corners, kind: exactly as arseg_segment_confidence_fwd takes them, with its route choice
+ *            (h == H && w == W; per-pixel bilinear, either align_corners; the x2 / x4 / x8 align_corners == 0 run route with its first and
+ *            last half runs).  The class k* and the code q of an output pixel come from the one label rule (csrc/arseg_device.h) with the
+ *            softmax accumulator of the confidence launch: they are bit-equal to labels8 (identity lut) and conf8 of
+ *            arseg_segment_confidence_fwd on the same arguments; a pixel whose confidence is NaN has q = 0.  1 <= n_cls <= 32.
+ * Labels.    label is int64 [N][H][W], contiguous.  A pixel counts if 0 <= label < n_cls and label != ignore_label (the tail's rule).
+ * Groups.    group is int32 [N] on the device, NULL only with n_groups == 1 (every frame is then group 0).  A frame whose group id is
+ *            outside [0, n_groups) counts nowhere.
+ * Counts.    cal is int64 [n_groups][n_cls][256][2], ACCUMULATED.  A counting pixel of a frame of group g adds 1 to cal[g][k*][q][0], and 1
+ *            to cal[g][k*][q][1] if label == k*.  Integers only: independent of the order of the atomic adds, so two runs are bit-equal.
+ *            Summing over the classes (the usual reliability diagram) is the host's business.
+ * Link to the tail.  On the same logits, labels and groups, with hist of arseg_argmax_confusion_grouped_fwd (hist[g][label][pred]):
+ *              sum_q cal[g][k][q][0] == sum_l hist[g][l][k]        (column k: the pixels predicted k)
+ *              sum_q cal[g][k][q][1] == hist[g][k][k]              (the diagonal: the pixels predicted k that are k)
+ *            exactly.
+ * Enqueue only: no allocation, no synchronisation, no workspace; capturable in a HIP graph.  cal must not overlap the inputs.
+ * ARSEG_EINVAL, before any launch: null logits, label or cal; a null group with n_groups > 1; n_groups < 1; n_cls outside 1..32; a
+ *            non-positive size; an unknown kind; label or cal not 8-byte aligned; group not 4-byte aligned.
+ * Not covered: NLL / Brier score (float sums); entropy; the confusion matrix from the same launch (arseg_argmax_confusion_grouped_fwd
+ *            keeps it); temperature fitting.
+ * ------------------------------------------------------------------------------------------- */
+int arseg_calibration_fwd(const float *logits, const int64_t *label, const int32_t *group, int64_t *cal, int N, int n_groups, int n_cls,
+                          int h, int w, int H, int W, int ignore_label, int align_corners, int kind, arseg_stream_t stream);
+
+/* ---------------------------------------------------------------------------------------------
  * Measurement aids (no reference counterpart; BASELINE.md section 3: roofline fractions are reported against the datasheet peaks AND
  * against on-box micro-benchmarks).  bench.py times each with HIP events and prints `peaks_measured`.
  *   arseg_peak_stream_copy: dst[0 .. n_bytes) = src[0 .. n_bytes) with 16-byte accesses (n_bytes % 16 == 0, both 16-byte aligned):
