@@ -32,7 +32,9 @@ CONF_NSTATS = 2 + 32      # ARSEG_CONF_NSTATS: sum of codes, low count, 32 class
 TC_NSTATS = 3 + 3 * 32    # ARSEG_TC_NSTATS: compared, outside, void, then 32 each of cur_k, ref_k, inter_k
 LINK_INTRA, LINK_UNCOVERED, LINK_CLAMPED = 1, 2, 4      # ARSEG_LINK_*: flag bits of a link byte; bits 4..7 = hops to the keyframe
 LINK_NSTATS = 4 + 16      # ARSEG_LINK_NSTATS: pixels with INTRA, UNCOVERED, CLAMPED, any flag, then 16 hop bins
-FILL_NSTATS = 3 + 3 * 256  # ARSEG_FILL_NSTATS: gaps, excess, changed, then 256 each of ref_area, fill_area, both
+BM_INTRA_REF = 16         # ARSEG_BM_INTRA_REF: the reference index an estimated intra block carries (unusable for every max_ref <= 16)
+BM_NSTATS = 4             # ARSEG_BM_NSTATS: intra blocks, matched blocks with the zero vector, sum of SAD and pixels of the matched blocks
+FILL_NSTATS = 3 + 3 * 256 # ARSEG_FILL_NSTATS: gaps, excess, changed, then 256 each of ref_area, fill_area, both
 
 
 class ConvDesc(Structure):
@@ -147,6 +149,8 @@ PROTOTYPES = {
     "arseg_mv_link_reset": (c_int, [_P, _P, c_int, c_int, c_int, _STREAM]),
     "arseg_mv_records_step_link_fwd": (c_int, [_P, c_int, _P, c_int, c_int, _P, c_size_t, c_int, c_int, c_int, _P, _P, _STREAM]),
     "arseg_mv_records_bi_step_link_fwd": (c_int, [_P, c_int, _P, c_int, c_int, c_uint64, c_int, _P, c_size_t, c_int, c_int, c_int, _P, _P, _STREAM]),
+    "arseg_block_motion_workspace_bytes": (c_size_t, [c_int, c_int, c_int, c_int]),
+    "arseg_block_motion_fwd": (c_int, [_P, c_int64, _P, c_int64] + [c_int] * 8 + [_P, _P, _P, _P, c_size_t, _STREAM]),
     "arseg_nchw_to_nhwc_fwd": (c_int, [_P, _P, c_int, c_int, c_int, c_int, _STREAM]),
     "arseg_nhwc_to_nchw_fwd": (c_int, [_P, c_int, _P, c_int, c_int, c_int, _STREAM]),
     "arseg_argmax_confusion_fwd": (c_int, [_P, _P, _P, _P] + [c_int] * 8 + [_STREAM]),

@@ -14,6 +14,8 @@
   dense per-frame dumps to records and back on the host.  ``MotionChain(bidirectional=True)`` takes B-frames as well: two prediction lists
   per frame, forward references, frames in decode order (arseg_mv_records_bi_*); ``chain_records_numpy`` is that rule on the host,
   ``motion_vectors_to_records`` the mapping from ``AVMotionVector``-style arrays.
+* no decoder motion at all (a hardware decoder's frames): ``MotionEstimator`` makes the records on the GPU by block matching of a frame's luma
+  against the previous frame's (csrc/block_motion.hip; include/arseg_hip.h, arseg_block_motion_*); ``block_motion_numpy`` is that search on the host.
 """
 from __future__ import annotations
 
@@ -253,6 +255,11 @@ class DecodedFrames(object):
     def to_input(self, h, w, dtype=torch.float32):
         """-> NHWC4 fp32 [N,h,w,4] or NHWC8 fp16 / bf16 [N,h,w,8] on the planes' (GPU) device: one kernel."""
         return ops._frame_ingest_planes(self.planes, self.src_format, h, w, self.mean, self.std, dtype, self.colour)
+
+    def luma_plane(self):
+        """(plane, src_format): what block motion estimation reads of these frames (``ops.block_motion``, ``MotionEstimator``) -- plane 0, a
+        view with its row pitch kept: the luma plane [N,H,W] of the 4:2:0 formats, the interleaved plane [N,H,W,3] of RGB8."""
+        return self.planes[0], self.src_format
 
 
 # ----------------------------------------------------------------------------------------------
@@ -632,3 +639,136 @@ class LinkMonitor(object):
             raise ValueError(f"LinkMonitor.update: n_pixels must be positive, got {n_pixels}")
         n = self.flagged(stats_row) if flagged is None else int(flagged)
         return bool(n / n_pixels > self.max_unlinked)
+
+
+# ----------------------------------------------------------------------------------------------
+# frames without motion vectors: block motion estimation -> records
+# ----------------------------------------------------------------------------------------------
+BM_INTRA_REF, BM_NSTATS = _lib.BM_INTRA_REF, _lib.BM_NSTATS          # ARSEG_BM_*: the ref of an estimated intra block; the length of the stats row
+
+
+def luma8_numpy(plane, src_format: int = _lib.SRC_NV12) -> np.ndarray:
+    """The 8-bit luma the block search compares (include/arseg_hip.h, arseg_block_motion_fwd), uint8 [H,W]: the byte of an NV12 / I420 luma
+    plane, ``(v & 0x3ff) >> 2`` of I010 words, ``v >> 8`` of P010 words, ``(77 R + 150 G + 29 B + 128) >> 8`` of an RGB8 plane [H,W,3].  A
+    leading batch axis of one is dropped; tensors are taken through numpy; int16 stands for the same 16 bits."""
+    p = plane.cpu() if torch.is_tensor(plane) else plane
+    if torch.is_tensor(p):
+        p = (p.view(torch.int16) if p.dtype == torch.uint16 else p).numpy()
+    p = np.asarray(p)
+    rgb = src_format == _lib.SRC_RGB8
+    if p.ndim == (4 if rgb else 3) and p.shape[0] == 1:
+        p = p[0]
+    wide = src_format in (_lib.SRC_P010, _lib.SRC_I010)
+    if src_format not in (_lib.SRC_RGB8, _lib.SRC_NV12, _lib.SRC_I420, _lib.SRC_P010, _lib.SRC_I010):
+        raise ValueError(f"luma8_numpy: unknown source format {src_format!r}")
+    if p.ndim != (3 if rgb else 2) or (rgb and p.shape[2] != 3) or 0 in p.shape or p.dtype not in ((np.uint16, np.int16) if wide else (np.uint8,)):
+        raise ValueError(f"luma8_numpy: format {src_format} expects {'uint16' if wide else 'uint8'} [H,W{',3' if rgb else ''}], got {p.dtype} {p.shape}")
+    if rgb:
+        c = p.astype(np.int64)
+        return ((77 * c[..., 0] + 150 * c[..., 1] + 29 * c[..., 2] + 128) >> 8).astype(np.uint8)
+    if not wide:
+        return np.ascontiguousarray(p)
+    v = p.view(np.uint16).astype(np.int64)
+    return ((v >> 8) if src_format == _lib.SRC_P010 else ((v & 0x3ff) >> 2)).astype(np.uint8)
+
+
+def _bm_args(who, H, W, B, R, lam, intra, ref_index):
+    if not (1 <= H <= 8192 and 1 <= W <= 8192) or B not in (8, 16) or not 1 <= R <= 32 or not 0 <= lam <= 255 or not 0 <= intra <= 255 \
+            or not 0 <= ref_index <= 15:
+        raise ValueError(f"{who}: H, W in 1..8192, block in (8, 16), search in 1..32, lam and intra in 0..255, ref_index in 0..15; got {H}x{W}, "
+                         f"block {B}, search {R}, lam {lam}, intra {intra}, ref_index {ref_index}")
+
+
+def block_motion_numpy(cur, ref, B: int = 16, R: int = 16, lam: int = 2, intra: int = 255, ref_index: int = 0, src_format: int = _lib.SRC_NV12):
+    """The block search of include/arseg_hip.h (arseg_block_motion_fwd) on the host, for callers without a GPU at hand: ``cur`` / ``ref`` are
+    the planes ``luma8_numpy`` takes for ``src_format``.  Returns ``(records int16 [by*bx,8], sad uint32 [by*bx], stats int64 [BM_NSTATS])`` --
+    what ``ops.block_motion`` writes, stats from zero.  numpy only, one pass over the frame per candidate (a 360 x 480 frame at R = 16 takes
+    a couple of seconds)."""
+    a, b = luma8_numpy(cur, src_format).astype(np.int32), luma8_numpy(ref, src_format).astype(np.int32)
+    B, R, lam, intra, ref_index = int(B), int(R), int(lam), int(intra), int(ref_index)
+    H, W = a.shape
+    if b.shape != a.shape:
+        raise ValueError(f"block_motion_numpy: the current frame is {a.shape}, the reference {b.shape}")
+    _bm_args("block_motion_numpy", H, W, B, R, lam, intra, ref_index)
+    by, bx, side = -(-H // B), -(-W // B), 2 * R + 1
+    x0, y0 = np.arange(bx) * B, np.arange(by) * B
+    w, h = np.minimum(B, W - x0), np.minimum(B, H - y0)
+    diff = np.zeros((by * B, bx * B), dtype=np.int32)                   # what lies beyond the frame stays 0
+    best = np.full((by, bx), (1 << 32) - 1, dtype=np.int64)
+    for dy in range(-R, R + 1):
+        oky = (y0 + dy >= 0) & (y0 + h + dy <= H)
+        ya, yb = max(0, -dy), min(H, H - dy)
+        if not oky.any():
+            continue
+        for dx in range(-R, R + 1):
+            okx = (x0 + dx >= 0) & (x0 + w + dx <= W)
+            xa, xb = max(0, -dx), min(W, W - dx)
+            if not okx.any():
+                continue
+            # every pixel of a block that counts is inside [ya, yb) x [xa, xb); what an earlier candidate left elsewhere is in no such block
+            diff[ya:yb, xa:xb] = np.abs(a[ya:yb, xa:xb] - b[ya + dy:yb + dy, xa + dx:xb + dx])
+            sad = diff.reshape(by, B, bx, B).sum(axis=(1, 3), dtype=np.int64)
+            rank = 0 if dx == 0 and dy == 0 else 1 + (dy + R) * side + (dx + R)
+            key = ((sad + lam * (abs(dx) + abs(dy))) << 13) | rank
+            best = np.where(oky[:, None] & okx[None, :], np.minimum(best, key), best)
+    rank, cost = best & 0x1fff, best >> 13
+    dy = np.where(rank > 0, (rank - 1) // side - R, 0)
+    dx = np.where(rank > 0, (rank - 1) % side - R, 0)
+    sad = cost - lam * (np.abs(dx) + np.abs(dy))
+    is_intra = sad > intra * (h[:, None] * w[None, :])
+    rec = np.zeros((by, bx, 8), dtype=np.int64)
+    rec[..., 0], rec[..., 1], rec[..., 2], rec[..., 3] = x0[None, :], y0[:, None], w[None, :], h[:, None]
+    rec[..., 4], rec[..., 5], rec[..., 6] = np.where(is_intra, 0, 4 * dx), np.where(is_intra, 0, 4 * dy), np.where(is_intra, BM_INTRA_REF, ref_index)
+    m = ~is_intra
+    stats = np.array([is_intra.sum(), (m & (dx == 0) & (dy == 0)).sum(), sad[m].sum(), (h[:, None] * w[None, :])[m].sum()], dtype=np.int64)
+    return np.ascontiguousarray(rec.reshape(-1, 8).astype(np.int16)), sad.reshape(-1).astype(np.uint32), stats
+
+
+class MotionEstimator(object):
+    """Motion for streams whose decoder hands over frames and no motion vectors (a hardware decoder's NV12 / P010 output): block matching of
+    a frame's luma against the previous frame's on the GPU (csrc/block_motion.hip), written as the block records ``MotionChain.push`` takes.
+
+        est, chain = MotionEstimator(H, W), MotionChain(H, W, gop=12, max_ref=1, track_links=True)
+        for each GOP:   chain.reset();  for each P-frame:  mv_q = chain.push(est.estimate(cur, prev))          # cur, prev: one-frame DecodedFrames
+
+    Owns ``records`` int16 [ceil(H/block) * ceil(W/block), 8], ``stats`` int64 [BM_NSTATS] and, ``with_sad=True``, ``sad`` (the winner's SAD per
+    block; int32 holding the uint32 bits), all allocated once: ``estimate`` is one launch that neither synchronises nor allocates, so
+    ``chain.push(est.estimate(cur, prev))`` over static frame buffers can be captured in a HIP graph.  ``block`` in (8, 16); ``search``: |dx|, |dy|
+    <= search, 1..32, whole pixels; cost = SAD + ``lam`` (|dx| + |dy|); a block whose best SAD exceeds ``intra`` per pixel is written intra
+    (``BM_INTRA_REF``: the chain flags it ``LINK_INTRA``; 255 never fires); ``ref_index`` goes into every matched record (0 = the reference
+    frame is the previous one).  The definition is include/arseg_hip.h (arseg_block_motion_fwd); ``block_motion_numpy`` is its host form."""
+
+    def __init__(self, H: int, W: int, block: int = 16, search: int = 16, lam: int = 2, intra: int = 255, ref_index: int = 0, device="cuda",
+                 with_sad: bool = False):
+        self.H, self.W, self.block, self.search = int(H), int(W), int(block), int(search)
+        self.lam, self.intra, self.ref_index = int(lam), int(intra), int(ref_index)
+        try:
+            _bm_args("MotionEstimator", self.H, self.W, self.block, self.search, self.lam, self.intra, self.ref_index)
+        except ValueError as e:
+            raise _lib.ArsegError(str(e)) from None
+        self.device = torch.device(device)
+        if self.device.type != "cuda":
+            raise _lib.ArsegError("MotionEstimator runs on the GPU only; there is no CPU fallback (block_motion_numpy is the host form)")
+        self.n_blocks = -(-self.H // self.block) * -(-self.W // self.block)
+        self.records = torch.zeros((self.n_blocks, 8), dtype=torch.int16, device=self.device)
+        self.stats = torch.zeros(BM_NSTATS, dtype=torch.int64, device=self.device)
+        self.sad = torch.zeros(self.n_blocks, dtype=torch.int32, device=self.device) if with_sad else None
+
+    def estimate(self, cur, ref) -> torch.Tensor:
+        """Two one-frame ``DecodedFrames`` of one format and of this estimator's size, on its device -> ``records`` (the same buffer every call)."""
+        for what, f in (("the current frame", cur), ("the reference frame", ref)):
+            if not isinstance(f, DecodedFrames) or f.N != 1 or (f.H, f.W) != (self.H, self.W):
+                raise _lib.ArsegError(f"MotionEstimator.estimate: {what} must be one DecodedFrames frame of {self.H}x{self.W}")
+        if cur.src_format != ref.src_format:
+            raise _lib.ArsegError(f"MotionEstimator.estimate: the frames differ in format ({cur.src_format} and {ref.src_format})")
+        ops.block_motion(cur.luma_plane()[0], ref.luma_plane()[0], cur.src_format, self.block, self.search, self.lam, self.intra, self.ref_index,
+                         records=self.records, sad=self.sad if self.sad is not None else False, stats=self.stats)
+        return self.records
+
+    def reset_stats(self) -> None:
+        self.stats.zero_()
+
+    def stats_row(self) -> torch.Tensor:
+        """int64 [BM_NSTATS], accumulated since ``reset_stats``: intra blocks, matched blocks with the zero vector, the sum of SAD and the
+        number of pixels of the matched blocks.  A device tensor: reading it on the host synchronises."""
+        return self.stats

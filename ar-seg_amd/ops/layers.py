@@ -552,6 +552,66 @@ def mv_records_rasterize(records: torch.Tensor, H: int, W: int) -> torch.Tensor:
     return out
 
 
+def _luma_plane(t: torch.Tensor, src_format: int, what: str):
+    """(H, W, row pitch in bytes) of the plane block_motion reads: [H,W] or [1,H,W] samples (uint8; uint16 or int16 bits for the 10-bit formats), for
+    RGB8 [H,W,3] or [1,H,W,3] bytes; rows contiguous, any row pitch."""
+    if src_format not in _SRC_PLANES:
+        raise _lib.ArsegError(f"{what}: unknown source format {src_format!r}")
+    dtype, tail = _SRC_PLANES[src_format][1], (3,) if src_format == _lib.SRC_RGB8 else ()
+    if not torch.is_tensor(t) or not t.is_cuda:
+        raise _lib.ArsegError(f"{what} runs on the GPU only (expected a CUDA tensor); ingest.block_motion_numpy is the host form")
+    if t.dtype != dtype and not (dtype == torch.uint16 and t.dtype == torch.int16):
+        raise _lib.ArsegError(f"{what}: expected {dtype} samples for source format {src_format}, got {t.dtype}")
+    if t.dim() == 3 + len(tail) and t.shape[0] == 1:
+        t = t[0]
+    if t.dim() != 2 + len(tail) or tuple(t.shape[2:]) != tail or 0 in t.shape:
+        raise _lib.ArsegError(f"{what}: expected one frame [H,W{',3' if tail else ''}], got {tuple(t.shape)}")
+    H, W = int(t.shape[0]), int(t.shape[1])
+    row = W * (3 if tail else 1)
+    if t.stride(1) != (3 if tail else 1) or (tail and t.stride(2) != 1) or (H > 1 and t.stride(0) < row):
+        raise _lib.ArsegError(f"{what}: expected rows of contiguous samples at a pitch of at least a row, got strides {t.stride()}")
+    return H, W, (t.stride(0) if H > 1 else row) * t.element_size()
+
+
+def block_motion(cur_plane: torch.Tensor, ref_plane: torch.Tensor, src_format: int, B: int = 16, R: int = 16, lam: int = 2, intra: int = 255,
+                 ref_index: int = 0, records: Optional[torch.Tensor] = None, sad=None, stats=None):
+    """Block motion of one frame against a reference frame (include/arseg_hip.h, arseg_block_motion_fwd): full search of every B x B block of
+    ``cur_plane``'s luma8 in ``ref_plane``'s, |dx|, |dy| <= R, cost = SAD + lam (|dx| + |dy|) -> the block records ``mv_records_step`` takes,
+    int16 [ceil(H/B) * ceil(W/B), 8]; a block whose best SAD exceeds ``intra`` per pixel is written intra (ref = BM_INTRA_REF).  The planes
+    are what ``DecodedFrames.luma_plane()`` returns.  ``records`` / ``sad`` (uint32 per block: the winner's SAD) / ``stats`` (int64
+    [BM_NSTATS], accumulated into) are allocated when None -- stats zeroed -- and ``sad=False`` / ``stats=False`` leave that output out.
+    One launch, no synchronisation; with all three buffers passed in, no allocation.  Returns (records, sad, stats)."""
+    H, W, cur_pitch = _luma_plane(cur_plane, src_format, "block_motion (current frame)")
+    H2, W2, ref_pitch = _luma_plane(ref_plane, src_format, "block_motion (reference frame)")
+    B, R, lam, intra, ref_index = int(B), int(R), int(lam), int(intra), int(ref_index)
+    if (H2, W2) != (H, W) or ref_plane.device != cur_plane.device:
+        raise _lib.ArsegError(f"block_motion: the current frame is {H}x{W} on {cur_plane.device}, the reference {H2}x{W2} on {ref_plane.device}")
+    if not (1 <= H <= 8192 and 1 <= W <= 8192) or B not in (8, 16) or not 1 <= R <= 32 or not 0 <= lam <= 255 or not 0 <= intra <= 255 \
+            or not 0 <= ref_index <= 15:
+        raise _lib.ArsegError(f"block_motion: H, W in 1..8192, B in (8, 16), R in 1..32, lam and intra in 0..255, ref_index in 0..15; got {H}x{W}, "
+                              f"B {B}, R {R}, lam {lam}, intra {intra}, ref_index {ref_index}")
+    n, dev = -(-H // B) * -(-W // B), cur_plane.device
+    if records is None:
+        records = torch.empty((n, 8), dtype=torch.int16, device=dev)
+    elif _mv_records(records, "block_motion") != n or records.device != dev:
+        raise _lib.ArsegError(f"block_motion: {H}x{W} in blocks of {B} is {n} records on {dev}, got {tuple(records.shape)} on {records.device}")
+    if sad is None:
+        sad = torch.empty(n, dtype=torch.int32, device=dev)
+    elif sad is False:
+        sad = None
+    elif not torch.is_tensor(sad) or sad.dtype not in (torch.int32, torch.uint32) or sad.device != dev or sad.numel() != n or not sad.is_contiguous():
+        raise _lib.ArsegError(f"block_motion expects sad as a contiguous int32 (uint32 bits) tensor of {n} elements on {dev}")
+    if stats is None:
+        stats = torch.zeros(_lib.BM_NSTATS, dtype=torch.int64, device=dev)
+    elif stats is False:
+        stats = None
+    elif not torch.is_tensor(stats) or stats.dtype != torch.int64 or stats.device != dev or stats.numel() != _lib.BM_NSTATS or not stats.is_contiguous():
+        raise _lib.ArsegError(f"block_motion expects stats as a contiguous int64 tensor of {_lib.BM_NSTATS} elements on {dev}")
+    launch("block_motion", _lib.load().arseg_block_motion_fwd, _ptr(cur_plane), cur_pitch, _ptr(ref_plane), ref_pitch, int(src_format), H, W, B, R, lam,
+           intra, ref_index, _ptr(records), _ptr(sad), _ptr(stats), None, 0, _stream())
+    return records, sad, stats
+
+
 def argmax_confusion(logits: torch.Tensor, label: Optional[torch.Tensor], H: int, W: int, hist: Optional[torch.Tensor] = None,
                      ignore_label: int = 255, want_pred: bool = True, align_corners: bool = True):
     """Evaluator tail (evaluation.py:201-209): returns (pred int32 [N,H,W] or None, hist int64 [n_cls,n_cls] or None).

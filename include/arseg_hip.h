@@ -660,6 +660,52 @@ int arseg_mv_records_step_link_fwd(const int16_t *records, int n_records, int16_
 int arseg_mv_records_bi_step_link_fwd(const int16_t *records, int n_records, int16_t *merged, int f, int gop, uint64_t done_mask, int policy,
                                       void *workspace, size_t workspace_bytes, int H, int W, int max_ref, uint8_t *link, int64_t *link_stats,
                                       arseg_stream_t stream);
+
+/* ---------------------------------------------------------------------------------------------
+ * Block motion estimation (csrc/block_motion.hip): the records above for a stream whose decoder hands over frames and no motion vectors
+ * (a hardware decoder's NV12 / P010 output).  Full search of every block of the current frame's luma in a reference frame's, 8-bit integer
+ * arithmetic throughout; the records go to arseg_mv_records_step_fwd / _step_link_fwd as a software decoder's would.
+ *   luma8       of a sample, by src_format (enum arseg_src_format), taken while the planes are read -- there is no conversion pass:
+ *                 ARSEG_SRC_NV12, ARSEG_SRC_I420   the luma byte
+ *                 ARSEG_SRC_I010                   (v & 0x3ff) >> 2       (uint16 little endian, code in the low 10 bits)
+ *                 ARSEG_SRC_P010                   v >> 8                 (code in the high 10 bits)
+ *                 ARSEG_SRC_RGB8                   (77 R + 150 G + 29 B + 128) >> 8
+ *               Chroma is not read.
+ *   cur, ref    the luma plane ([H][W] samples) of the current and of the reference frame -- for ARSEG_SRC_RGB8 the interleaved plane
+ *               ([H][W][3] bytes) -- on the device, rows cur_pitch / ref_pitch BYTES apart; read only
+ *   blocks      H, W in 1 .. 8192, B in {8, 16}: by = ceil(H / B) rows of bx = ceil(W / B) blocks.  Block (bi, bj): x0 = bj B, y0 = bi B,
+ *               w = min(B, W - x0), h = min(B, H - y0); it is record bi * bx + bj.  Always exactly by * bx records.
+ *   candidates  every integer (dx, dy), |dx| <= R and |dy| <= R, R in 1 .. 32, whose displaced block lies inside the reference frame:
+ *               0 <= x0 + dx, x0 + w + dx <= W, 0 <= y0 + dy, y0 + h + dy <= H.  (0, 0) always is one.  No sample is padded or clamped, so
+ *               the chain never sets ARSEG_LINK_CLAMPED for an estimated record.
+ *   cost        SAD(dx, dy) = sum over the block's w h pixels of |luma8(cur[y][x]) - luma8(ref[y + dy][x + dx])|
+ *               cost = SAD + lambda (|dx| + |dy|), lambda in 0 .. 255
+ *   winner      the candidate with the smallest (cost, rank), rank(0, 0) = 0, otherwise rank = 1 + (dy + R)(2 R + 1) + (dx + R)
+ *               (cost < 2^17 and rank < 2^13: one unsigned minimum of cost << 13 | rank decides)
+ *   record      (x0, y0, w, h, 4 dx, 4 dy, ref_index, 0), ref_index in 0 .. 15 (0 = `ref` is the previous frame); if the winner's
+ *               SAD > intra w h (intra in 0 .. 255: a mean absolute difference per pixel; SAD == intra w h is a match, 255 never fires):
+ *               (x0, y0, w, h, 0, 0, ARSEG_BM_INTRA_REF, 0) -- 16 is unusable for every max_ref <= 16, so both chain entries flag the
+ *               block's pixels ARSEG_LINK_INTRA
+ *   records     int16 [by * bx][8] on the device, 16-byte aligned; every record is written
+ *   sad         uint32 [by * bx], may be NULL: the winner's SAD (of intra blocks too)
+ *   stats       int64 [ARSEG_BM_NSTATS], 8-byte aligned, may be NULL; ACCUMULATED INTO: [0] intra blocks, [1] matched blocks with the zero
+ *               vector, [2] sum of SAD over matched blocks, [3] pixels in matched blocks.  Integers: two runs are bit-equal.
+ * Entry points (enqueue only: no host synchronisation, no allocation; one launch, a captured graph replays it):
+ *   arseg_block_motion_workspace_bytes  0: the search lives in LDS and registers.  Kept so that a caller sizes the workspace as elsewhere
+ *   arseg_block_motion_fwd              workspace may be NULL while the function above answers 0
+ * ARSEG_EINVAL before any launch: a null cur, ref or records; H or W outside 1 .. 8192; B outside {8, 16}; R outside 1 .. 32; lambda or
+ * intra outside 0 .. 255; ref_index outside 0 .. 15; an unknown src_format; a pitch below the row's bytes (W, 2 W for the 16-bit formats,
+ * 3 W for RGB8); a pitch or plane pointer that is odd with a 16-bit format; records not 16-byte, sad not 4-byte, stats not 8-byte aligned.
+ * ARSEG_EWORKSPACE: workspace_bytes below arseg_block_motion_workspace_bytes(H, W, B, R).
+ * Not covered: sub-pel refinement (the chain rounds every hop to whole pixels), hierarchical or predictive search, variable block sizes,
+ * two references per block, chroma.
+ * ------------------------------------------------------------------------------------------- */
+#define ARSEG_BM_INTRA_REF 16
+#define ARSEG_BM_NSTATS 4
+size_t arseg_block_motion_workspace_bytes(int H, int W, int B, int R);
+int arseg_block_motion_fwd(const void *cur, int64_t cur_pitch, const void *ref, int64_t ref_pitch, int src_format, int H, int W, int B, int R,
+                           int lambda, int intra, int ref_index, int16_t *records, uint32_t *sad, int64_t *stats, void *workspace,
+                           size_t workspace_bytes, arseg_stream_t stream);
 /* layout changes at the API boundary */
 int arseg_nchw_to_nhwc_fwd(const float *in, float *out, int N, int C, int HW, int out_ld, arseg_stream_t stream);
 int arseg_nhwc_to_nchw_fwd(const float *in, int in_ld, float *out, int N, int C, int HW, arseg_stream_t stream);
