@@ -151,6 +151,10 @@ PROTOTYPES = {
     "arseg_mv_records_bi_step_link_fwd": (c_int, [_P, c_int, _P, c_int, c_int, c_uint64, c_int, _P, c_size_t, c_int, c_int, c_int, _P, _P, _STREAM]),
     "arseg_block_motion_workspace_bytes": (c_size_t, [c_int, c_int, c_int, c_int]),
     "arseg_block_motion_fwd": (c_int, [_P, c_int64, _P, c_int64] + [c_int] * 8 + [_P, _P, _P, _P, c_size_t, _STREAM]),
+    "arseg_luma_pyramid_bytes": (c_size_t, [c_int, c_int, c_int]),
+    "arseg_luma_pyramid_fwd": (c_int, [_P, c_int64, c_int, c_int, c_int, c_int, _P, c_size_t, _STREAM]),
+    "arseg_block_motion_pyr_workspace_bytes": (c_size_t, [c_int, c_int, c_int, c_int]),
+    "arseg_block_motion_pyr_fwd": (c_int, [_P, _P] + [c_int] * 9 + [_P, _P, _P, _P, c_size_t, _STREAM]),
     "arseg_nchw_to_nhwc_fwd": (c_int, [_P, _P, c_int, c_int, c_int, c_int, _STREAM]),
     "arseg_nhwc_to_nchw_fwd": (c_int, [_P, c_int, _P, c_int, c_int, c_int, _STREAM]),
     "arseg_argmax_confusion_fwd": (c_int, [_P, _P, _P, _P] + [c_int] * 8 + [_STREAM]),

@@ -15,46 +15,10 @@
 //             the wave; lane 0 decodes the rank, applies the intra bound and stores the record with one 16-byte vector store
 //   edge    : a block clipped by the right or bottom frame edge (w < B or h < B) takes a per-pixel walk, a lane per candidate
 //   stats   : one LDS partial per counter and workgroup, one 64-bit atomic per non-zero counter
-#include "arseg_device.h"
+#include "block_motion_luma.h"
 
-constexpr int BM_MAX_DIM = 8192, BM_MAX_R = 32;
 constexpr int BM_TW = 64, BM_TH = 32;                                  // tile in pixels
 constexpr int BM_WIN_W = BM_TW + 2 * BM_MAX_R + 4, BM_WIN_H = BM_TH + 2 * BM_MAX_R;      // window at R = 32: 132 x 96 bytes
-enum { BM_U8 = 0, BM_P010 = 1, BM_I010 = 2, BM_RGB8 = 3 };             // how a sample becomes luma8
-
-template <int F> constexpr int bm_sample_bytes = F == BM_U8 ? 1 : (F == BM_RGB8 ? 3 : 2);
-
-// luma8 of the sample whose bytes are s[0 ..]
-template <int F>
-__device__ __forceinline__ unsigned bm_luma8(const unsigned *s) {
-    if constexpr (F == BM_U8) return s[0];
-    else if constexpr (F == BM_P010) return s[1];                                         // v >> 8
-    else if constexpr (F == BM_I010) return ((s[0] | (s[1] << 8)) & 0x3ffu) >> 2;
-    else return (77u * s[0] + 150u * s[1] + 29u * s[2] + 128u) >> 8;
-}
-
-// luma8 of pixels x .. x + 3 of one frame row, packed little endian; a pixel outside [0, W) reads 0.  row = the row's first byte.
-template <int F>
-__device__ __forceinline__ unsigned bm_luma4(const uint8_t *row, int x, int W) {
-    constexpr int S = bm_sample_bytes<F>;
-    unsigned out = 0;
-    if (x >= 0 && x + 4 <= W) {
-        unsigned v[4 * S];
-        span_load<4 * S>(row + (size_t)x * S, v);
-#pragma unroll
-        for (int i = 0; i < 4; ++i) out |= bm_luma8<F>(v + i * S) << (8 * i);
-    } else {
-#pragma unroll
-        for (int i = 0; i < 4; ++i) {
-            if (x + i < 0 || x + i >= W) continue;
-            unsigned v[S];
-#pragma unroll
-            for (int b = 0; b < S; ++b) v[b] = row[(size_t)(x + i) * S + b];
-            out |= bm_luma8<F>(v) << (8 * i);
-        }
-    }
-    return out;
-}
 
 constexpr int BM_WPITCH = BM_WIN_W / 4;                                // window row pitch in dwords (33: odd), the same for every R: row offsets are immediates
 
@@ -198,16 +162,6 @@ __global__ __launch_bounds__(256) void block_motion_kernel(const uint8_t *__rest
     }
 }
 
-static int bm_format(int src_format) {
-    switch (src_format) {
-    case ARSEG_SRC_NV12: case ARSEG_SRC_I420: return BM_U8;
-    case ARSEG_SRC_P010: return BM_P010;
-    case ARSEG_SRC_I010: return BM_I010;
-    case ARSEG_SRC_RGB8: return BM_RGB8;
-    default: return -1;
-    }
-}
-
 extern "C" size_t arseg_block_motion_workspace_bytes(int H, int W, int B, int R) {
     (void)H; (void)W; (void)B; (void)R;
     return 0;                                                          // the search keeps everything in LDS and registers
@@ -230,9 +184,7 @@ extern "C" int arseg_block_motion_fwd(const void *cur, int64_t cur_pitch, const 
     if (lambda < 0 || lambda > 255 || intra < 0 || intra > 255 || ref_index < 0 || ref_index > 15) return ARSEG_EINVAL;
     const int f = bm_format(src_format);
     if (f < 0) return ARSEG_EINVAL;
-    const int64_t sample = f == BM_U8 ? 1 : (f == BM_RGB8 ? 3 : 2), align = f == BM_P010 || f == BM_I010 ? 2 : 1;
-    if (cur_pitch < sample * W || ref_pitch < sample * W || cur_pitch % align || ref_pitch % align) return ARSEG_EINVAL;
-    if (reinterpret_cast<uintptr_t>(cur) % align || reinterpret_cast<uintptr_t>(ref) % align) return ARSEG_EINVAL;
+    if (!bm_plane_ok(f, cur, cur_pitch, W) || !bm_plane_ok(f, ref, ref_pitch, W)) return ARSEG_EINVAL;
     if (!ARSEG_ALIGNED16(records) || (reinterpret_cast<uintptr_t>(sad) & 3u) || (reinterpret_cast<uintptr_t>(stats) & 7u)) return ARSEG_EINVAL;
     if (workspace_bytes < arseg_block_motion_workspace_bytes(H, W, B, R)) return ARSEG_EWORKSPACE;
     const int rpad = (R + 3) & ~3;

@@ -16,6 +16,8 @@
   ``motion_vectors_to_records`` the mapping from ``AVMotionVector``-style arrays.
 * no decoder motion at all (a hardware decoder's frames): ``MotionEstimator`` makes the records on the GPU by block matching of a frame's luma
   against the previous frame's (csrc/block_motion.hip; include/arseg_hip.h, arseg_block_motion_*); ``block_motion_numpy`` is that search on the host.
+  ``MotionEstimator(levels=...)`` searches coarse to fine over a ``LumaPyramid`` and reaches past 32 pixels (csrc/block_motion_pyr.hip;
+  arseg_luma_pyramid_*, arseg_block_motion_pyr_*; ``luma_pyramid_numpy`` and ``block_motion_pyr_numpy`` on the host).
 """
 from __future__ import annotations
 
@@ -724,6 +726,141 @@ def block_motion_numpy(cur, ref, B: int = 16, R: int = 16, lam: int = 2, intra: 
     return np.ascontiguousarray(rec.reshape(-1, 8).astype(np.int16)), sad.reshape(-1).astype(np.uint32), stats
 
 
+def luma_pyramid_layout(H: int, W: int, levels: int):
+    """``([(offset, pitch, H_l, W_l) for l in 0 .. levels], total bytes)`` of a luma pyramid buffer (include/arseg_hip.h, arseg_luma_pyramid_*):
+    H_{l+1} = (H_l + 1) >> 1, rows (W_l + 15) & ~15 bytes apart, the levels back to back."""
+    H, W, levels = int(H), int(W), int(levels)
+    if not (1 <= H <= 8192 and 1 <= W <= 8192 and 1 <= levels <= 3):
+        raise ValueError(f"luma_pyramid_layout: H, W in 1..8192 and levels in 1..3; got {H}x{W}, levels {levels}")
+    out, off = [], 0
+    for _ in range(levels + 1):
+        pitch = (W + 15) & ~15
+        out.append((off, pitch, H, W))
+        off, H, W = off + pitch * H, (H + 1) >> 1, (W + 1) >> 1
+    return out, off
+
+
+def luma_pyramid_numpy(plane, src_format: int = _lib.SRC_NV12, levels: int = 1) -> list:
+    """The luma pyramid of include/arseg_hip.h (arseg_luma_pyramid_fwd) on the host: ``[P_0, .. P_levels]``, uint8 [H_l,W_l] each, P_0 =
+    ``luma8_numpy(plane, src_format)``, every further level the rounded 2 x 2 mean with the last row / column replicated for odd sizes."""
+    out = [luma8_numpy(plane, src_format)]
+    luma_pyramid_layout(out[0].shape[0], out[0].shape[1], levels)
+    for _ in range(int(levels)):
+        a = out[-1].astype(np.int32)
+        H, W = a.shape
+        e = a[np.minimum(np.arange(2 * ((H + 1) >> 1)), H - 1)][:, np.minimum(np.arange(2 * ((W + 1) >> 1)), W - 1)]
+        out.append(((e[0::2, 0::2] + e[0::2, 1::2] + e[1::2, 0::2] + e[1::2, 1::2] + 2) >> 2).astype(np.uint8))
+    return out
+
+
+def _refine_numpy(a, b, pvx, pvy, B, r, lam):
+    """One refinement level: the planes int32 [H_l,W_l], the parents' vectors int64 [by_{l+1},bx_{l+1}] -> (dx, dy, sad) int64 [by_l,bx_l].  One
+    gather of the reference per (centre, offset): every block reads at its own displacement."""
+    H, W = a.shape
+    by, bx = -(-H // B), -(-W // B)
+    pby, pbx = pvx.shape
+    bi, bj = np.arange(by), np.arange(bx)
+    x0, y0 = bj * B, bi * B
+    w, h = np.minimum(B, W - x0), np.minimum(B, H - y0)
+    pi, pj = bi >> 1, bj >> 1
+    ni, nj = pi + np.where(bi & 1, 1, -1), pj + np.where(bj & 1, 1, -1)
+    oki, okj = (ni >= 0) & (ni < pby), (nj >= 0) & (nj < pbx)
+    ni, nj = np.clip(ni, 0, pby - 1), np.clip(nj, 0, pbx - 1)
+    yes = np.ones((by, bx), dtype=bool)
+    centres = [(np.zeros((by, bx), np.int64), np.zeros((by, bx), np.int64), yes),
+               (2 * pvx[pi][:, pj], 2 * pvy[pi][:, pj], yes),
+               (2 * pvx[pi][:, nj], 2 * pvy[pi][:, nj], yes & okj[None, :]),
+               (2 * pvx[ni][:, pj], 2 * pvy[ni][:, pj], yes & oki[:, None])]
+    ap = np.zeros((by * B, bx * B), dtype=np.int32)
+    ap[:H, :W] = a
+    Y, X = np.arange(by * B)[:, None], np.arange(bx * B)[None, :]
+    inside = (Y < H) & (X < W)
+    best = np.full((by, bx), (1 << 62), dtype=np.int64)
+    for cx, cy, ok in centres:
+        for oy in range(-r, r + 1):
+            for ox in range(-r, r + 1):
+                dx, dy = cx + ox, cy + oy
+                valid = ok & (x0[None, :] + dx >= 0) & (x0[None, :] + w[None, :] + dx <= W) & (y0[:, None] + dy >= 0) & (y0[:, None] + h[:, None] + dy <= H)
+                if not valid.any():
+                    continue
+                yy = np.clip(Y + np.repeat(np.repeat(dy, B, axis=0), B, axis=1), 0, H - 1)
+                xx = np.clip(X + np.repeat(np.repeat(dx, B, axis=0), B, axis=1), 0, W - 1)
+                sad = (np.abs(ap - b[yy, xx]) * inside).reshape(by, B, bx, B).sum(axis=(1, 3), dtype=np.int64)
+                rank = np.where((dx == 0) & (dy == 0), 0, 1 + (dy + 511) * 1023 + (dx + 511))
+                key = ((sad + lam * (np.abs(dx) + np.abs(dy))) << 20) | rank
+                best = np.where(valid & (key < best), key, best)
+    rank, cost = best & 0xfffff, best >> 20
+    dy = np.where(rank > 0, (rank - 1) // 1023 - 511, 0)
+    dx = np.where(rank > 0, (rank - 1) % 1023 - 511, 0)
+    return dx, dy, cost - lam * (np.abs(dx) + np.abs(dy))
+
+
+def _bmp_args(who, levels, r):
+    if not 0 <= levels <= 3 or (levels and not 1 <= r <= 3):
+        raise ValueError(f"{who}: levels in 0..3 and refine in 1..3; got levels {levels}, refine {r}")
+
+
+def block_motion_pyr_numpy(cur, ref, B: int = 16, Rt: int = 8, r: int = 1, lam: int = 2, intra: int = 255, ref_index: int = 0, levels: int = 2,
+                           src_format: int = _lib.SRC_NV12):
+    """The hierarchical block search of include/arseg_hip.h (arseg_block_motion_pyr_fwd) on the host: ``block_motion_numpy`` with |dx|, |dy| <=
+    ``Rt`` on level ``levels`` of the two ``luma_pyramid_numpy``, then per level below it the candidates +-``r`` around (0, 0) and around twice
+    the vectors of the parent block and of its neighbours on the block's side.  Returns what ``block_motion_numpy`` returns; ``levels=0`` IS
+    ``block_motion_numpy`` with R = ``Rt``.  numpy only, one gather of the frame per centre and offset (360 x 480 at r = 1: about a second)."""
+    B, Rt, r, lam, intra, ref_index, levels = int(B), int(Rt), int(r), int(lam), int(intra), int(ref_index), int(levels)
+    _bmp_args("block_motion_pyr_numpy", levels, r)
+    if levels == 0:
+        return block_motion_numpy(cur, ref, B, Rt, lam, intra, ref_index, src_format)
+    pc, pr = luma_pyramid_numpy(cur, src_format, levels), luma_pyramid_numpy(ref, src_format, levels)
+    H, W = pc[0].shape
+    if pr[0].shape != pc[0].shape:
+        raise ValueError(f"block_motion_pyr_numpy: the current frame is {pc[0].shape}, the reference {pr[0].shape}")
+    _bm_args("block_motion_pyr_numpy", H, W, B, Rt, lam, intra, ref_index)
+    top = block_motion_numpy(pc[levels], pr[levels], B, Rt, lam, 255, 0)[0].astype(np.int64)
+    shape = (-(-pc[levels].shape[0] // B), -(-pc[levels].shape[1] // B))
+    dx, dy = (top[:, 4] // 4).reshape(shape), (top[:, 5] // 4).reshape(shape)
+    for l in range(levels - 1, -1, -1):
+        dx, dy, sad = _refine_numpy(pc[l].astype(np.int32), pr[l].astype(np.int32), dx, dy, B, r, lam)
+    by, bx = dx.shape
+    x0, y0 = np.arange(bx) * B, np.arange(by) * B
+    w, h = np.minimum(B, W - x0), np.minimum(B, H - y0)
+    is_intra = sad > intra * (h[:, None] * w[None, :])
+    rec = np.zeros((by, bx, 8), dtype=np.int64)
+    rec[..., 0], rec[..., 1], rec[..., 2], rec[..., 3] = x0[None, :], y0[:, None], w[None, :], h[:, None]
+    rec[..., 4], rec[..., 5], rec[..., 6] = np.where(is_intra, 0, 4 * dx), np.where(is_intra, 0, 4 * dy), np.where(is_intra, BM_INTRA_REF, ref_index)
+    m = ~is_intra
+    stats = np.array([is_intra.sum(), (m & (dx == 0) & (dy == 0)).sum(), sad[m].sum(), (h[:, None] * w[None, :])[m].sum()], dtype=np.int64)
+    return np.ascontiguousarray(rec.reshape(-1, 8).astype(np.int16)), sad.reshape(-1).astype(np.uint32), stats
+
+
+class LumaPyramid(object):
+    """The luma8 pyramid of one frame on the GPU (include/arseg_hip.h, arseg_luma_pyramid_fwd; csrc/block_motion_pyr.hip): one uint8 buffer,
+    allocated once.  ``build(frame)`` fills it from a one-frame ``DecodedFrames`` -- one launch, no synchronisation, no allocation -- and
+    returns the pyramid; ``level(l)`` is the [H_l, W_l] view of level l (rows ``pitch`` bytes apart).  A caller of ``MotionEstimator(levels=L)``
+    who keeps two of these and alternates them builds each frame of a stream once."""
+
+    def __init__(self, H: int, W: int, levels: int, device="cuda"):
+        self.H, self.W, self.levels = int(H), int(W), int(levels)
+        try:
+            self.layout, self.nbytes = luma_pyramid_layout(self.H, self.W, self.levels)
+        except ValueError as e:
+            raise _lib.ArsegError(str(e)) from None
+        self.device = torch.device(device)
+        if self.device.type != "cuda":
+            raise _lib.ArsegError("LumaPyramid lives on the GPU; there is no CPU fallback (luma_pyramid_numpy is the host form)")
+        self.buffer = torch.zeros(self.nbytes, dtype=torch.uint8, device=self.device)
+
+    def build(self, frame) -> "LumaPyramid":
+        if not isinstance(frame, DecodedFrames) or frame.N != 1 or (frame.H, frame.W) != (self.H, self.W):
+            raise _lib.ArsegError(f"LumaPyramid.build: expected one DecodedFrames frame of {self.H}x{self.W}")
+        plane, src_format = frame.luma_plane()
+        ops.luma_pyramid(plane, src_format, self.levels, out=self.buffer)
+        return self
+
+    def level(self, l: int) -> torch.Tensor:
+        off, pitch, H, W = self.layout[l]
+        return self.buffer[off:off + pitch * H].view(H, pitch)[:, :W]
+
+
 class MotionEstimator(object):
     """Motion for streams whose decoder hands over frames and no motion vectors (a hardware decoder's NV12 / P010 output): block matching of
     a frame's luma against the previous frame's on the GPU (csrc/block_motion.hip), written as the block records ``MotionChain.push`` takes.
@@ -736,14 +873,23 @@ class MotionEstimator(object):
     ``chain.push(est.estimate(cur, prev))`` over static frame buffers can be captured in a HIP graph.  ``block`` in (8, 16); ``search``: |dx|, |dy|
     <= search, 1..32, whole pixels; cost = SAD + ``lam`` (|dx| + |dy|); a block whose best SAD exceeds ``intra`` per pixel is written intra
     (``BM_INTRA_REF``: the chain flags it ``LINK_INTRA``; 255 never fires); ``ref_index`` goes into every matched record (0 = the reference
-    frame is the previous one).  The definition is include/arseg_hip.h (arseg_block_motion_fwd); ``block_motion_numpy`` is its host form."""
+    frame is the previous one).  The definition is include/arseg_hip.h (arseg_block_motion_fwd); ``block_motion_numpy`` is its host form.
+
+    ``levels`` in 1 .. 3 makes the search hierarchical (csrc/block_motion_pyr.hip; arseg_block_motion_pyr_fwd; host form
+    ``block_motion_pyr_numpy``): ``search`` then counts pixels of pyramid level ``levels``, every level below it looks +-``refine`` (1 .. 3)
+    around its parents' doubled vectors, and ``reach`` = search 2^levels + refine (2^levels - 1) is the largest |dx|, |dy| in frame pixels.
+    ``estimate`` then takes a ``DecodedFrames`` or an already built ``LumaPyramid`` for either argument; a frame is built into one of two
+    pyramids the estimator owns (two more launches), so a caller who alternates two ``LumaPyramid``s of their own builds each frame once.
+    Still no synchronisation and no allocation.  ``levels=0`` is the full search, launch for launch."""
 
     def __init__(self, H: int, W: int, block: int = 16, search: int = 16, lam: int = 2, intra: int = 255, ref_index: int = 0, device="cuda",
-                 with_sad: bool = False):
+                 with_sad: bool = False, levels: int = 0, refine: int = 1):
         self.H, self.W, self.block, self.search = int(H), int(W), int(block), int(search)
         self.lam, self.intra, self.ref_index = int(lam), int(intra), int(ref_index)
+        self.levels, self.refine = int(levels), int(refine)
         try:
             _bm_args("MotionEstimator", self.H, self.W, self.block, self.search, self.lam, self.intra, self.ref_index)
+            _bmp_args("MotionEstimator", self.levels, self.refine)
         except ValueError as e:
             raise _lib.ArsegError(str(e)) from None
         self.device = torch.device(device)
@@ -753,9 +899,37 @@ class MotionEstimator(object):
         self.records = torch.zeros((self.n_blocks, 8), dtype=torch.int16, device=self.device)
         self.stats = torch.zeros(BM_NSTATS, dtype=torch.int64, device=self.device)
         self.sad = torch.zeros(self.n_blocks, dtype=torch.int32, device=self.device) if with_sad else None
+        if self.levels:
+            self._pyramids = (LumaPyramid(self.H, self.W, self.levels, self.device), LumaPyramid(self.H, self.W, self.levels, self.device))
+            nbytes = _lib.load().arseg_block_motion_pyr_workspace_bytes(self.H, self.W, self.block, self.levels)
+            self._workspace = torch.zeros(nbytes, dtype=torch.uint8, device=self.device)
+
+    @property
+    def reach(self) -> int:
+        """The largest |dx|, |dy| a record can carry, in frame pixels."""
+        return self.search * (1 << self.levels) + self.refine * ((1 << self.levels) - 1) if self.levels else self.search
+
+    def _estimate_pyr(self, cur, ref) -> torch.Tensor:
+        pyr = []
+        for what, f, own in (("the current frame", cur, self._pyramids[0]), ("the reference frame", ref, self._pyramids[1])):
+            if isinstance(f, LumaPyramid):
+                if (f.H, f.W, f.levels, f.device) != (self.H, self.W, self.levels, self.device):
+                    raise _lib.ArsegError(f"MotionEstimator.estimate: {what} must be a LumaPyramid of {self.H}x{self.W} with {self.levels} levels on {self.device}")
+                pyr.append(f)
+            elif isinstance(f, DecodedFrames) and f.N == 1 and (f.H, f.W) == (self.H, self.W):
+                pyr.append(own.build(f))
+            else:
+                raise _lib.ArsegError(f"MotionEstimator.estimate: {what} must be one DecodedFrames frame of {self.H}x{self.W} or a built LumaPyramid")
+        ops.block_motion_pyr(pyr[0].buffer, pyr[1].buffer, self.H, self.W, self.levels, self.block, self.search, self.refine, self.lam, self.intra,
+                             self.ref_index, records=self.records, sad=self.sad if self.sad is not None else False, stats=self.stats,
+                             workspace=self._workspace)
+        return self.records
 
     def estimate(self, cur, ref) -> torch.Tensor:
-        """Two one-frame ``DecodedFrames`` of one format and of this estimator's size, on its device -> ``records`` (the same buffer every call)."""
+        """Two one-frame ``DecodedFrames`` of one format and of this estimator's size, on its device -> ``records`` (the same buffer every call).
+        With ``levels`` >= 1 either may be a built ``LumaPyramid`` instead, and the two frames may differ in format."""
+        if self.levels:
+            return self._estimate_pyr(cur, ref)
         for what, f in (("the current frame", cur), ("the reference frame", ref)):
             if not isinstance(f, DecodedFrames) or f.N != 1 or (f.H, f.W) != (self.H, self.W):
                 raise _lib.ArsegError(f"MotionEstimator.estimate: {what} must be one DecodedFrames frame of {self.H}x{self.W}")

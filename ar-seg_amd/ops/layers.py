@@ -9,6 +9,7 @@ from typing import Optional
 import torch
 
 from .. import _lib
+from . import _base
 from ._base import _DT16, _need_gpu, _need_gpu16, _nhwc_ld, _ptr, _storage, _stream, is16, workspace
 from ._profile import launch
 
@@ -573,6 +574,29 @@ def _luma_plane(t: torch.Tensor, src_format: int, what: str):
     return H, W, (t.stride(0) if H > 1 else row) * t.element_size()
 
 
+def _bm_outputs(who: str, H: int, W: int, B: int, dev, records, sad, stats):
+    """The output buffers of a block search over an H x W frame in blocks of B, checked or -- None -- allocated (stats zeroed); False leaves
+    sad or stats out (None is returned for it)."""
+    n = -(-H // B) * -(-W // B)
+    if records is None:
+        records = torch.empty((n, 8), dtype=torch.int16, device=dev)
+    elif _mv_records(records, who) != n or records.device != dev:
+        raise _lib.ArsegError(f"{who}: {H}x{W} in blocks of {B} is {n} records on {dev}, got {tuple(records.shape)} on {records.device}")
+    if sad is None:
+        sad = torch.empty(n, dtype=torch.int32, device=dev)
+    elif sad is False:
+        sad = None
+    elif not torch.is_tensor(sad) or sad.dtype not in (torch.int32, torch.uint32) or sad.device != dev or sad.numel() != n or not sad.is_contiguous():
+        raise _lib.ArsegError(f"{who} expects sad as a contiguous int32 (uint32 bits) tensor of {n} elements on {dev}")
+    if stats is None:
+        stats = torch.zeros(_lib.BM_NSTATS, dtype=torch.int64, device=dev)
+    elif stats is False:
+        stats = None
+    elif not torch.is_tensor(stats) or stats.dtype != torch.int64 or stats.device != dev or stats.numel() != _lib.BM_NSTATS or not stats.is_contiguous():
+        raise _lib.ArsegError(f"{who} expects stats as a contiguous int64 tensor of {_lib.BM_NSTATS} elements on {dev}")
+    return records, sad, stats
+
+
 def block_motion(cur_plane: torch.Tensor, ref_plane: torch.Tensor, src_format: int, B: int = 16, R: int = 16, lam: int = 2, intra: int = 255,
                  ref_index: int = 0, records: Optional[torch.Tensor] = None, sad=None, stats=None):
     """Block motion of one frame against a reference frame (include/arseg_hip.h, arseg_block_motion_fwd): full search of every B x B block of
@@ -590,25 +614,64 @@ def block_motion(cur_plane: torch.Tensor, ref_plane: torch.Tensor, src_format: i
             or not 0 <= ref_index <= 15:
         raise _lib.ArsegError(f"block_motion: H, W in 1..8192, B in (8, 16), R in 1..32, lam and intra in 0..255, ref_index in 0..15; got {H}x{W}, "
                               f"B {B}, R {R}, lam {lam}, intra {intra}, ref_index {ref_index}")
-    n, dev = -(-H // B) * -(-W // B), cur_plane.device
-    if records is None:
-        records = torch.empty((n, 8), dtype=torch.int16, device=dev)
-    elif _mv_records(records, "block_motion") != n or records.device != dev:
-        raise _lib.ArsegError(f"block_motion: {H}x{W} in blocks of {B} is {n} records on {dev}, got {tuple(records.shape)} on {records.device}")
-    if sad is None:
-        sad = torch.empty(n, dtype=torch.int32, device=dev)
-    elif sad is False:
-        sad = None
-    elif not torch.is_tensor(sad) or sad.dtype not in (torch.int32, torch.uint32) or sad.device != dev or sad.numel() != n or not sad.is_contiguous():
-        raise _lib.ArsegError(f"block_motion expects sad as a contiguous int32 (uint32 bits) tensor of {n} elements on {dev}")
-    if stats is None:
-        stats = torch.zeros(_lib.BM_NSTATS, dtype=torch.int64, device=dev)
-    elif stats is False:
-        stats = None
-    elif not torch.is_tensor(stats) or stats.dtype != torch.int64 or stats.device != dev or stats.numel() != _lib.BM_NSTATS or not stats.is_contiguous():
-        raise _lib.ArsegError(f"block_motion expects stats as a contiguous int64 tensor of {_lib.BM_NSTATS} elements on {dev}")
+    records, sad, stats = _bm_outputs("block_motion", H, W, B, cur_plane.device, records, sad, stats)
     launch("block_motion", _lib.load().arseg_block_motion_fwd, _ptr(cur_plane), cur_pitch, _ptr(ref_plane), ref_pitch, int(src_format), H, W, B, R, lam,
            intra, ref_index, _ptr(records), _ptr(sad), _ptr(stats), None, 0, _stream())
+    return records, sad, stats
+
+
+def _pyramid_buffer(t, H: int, W: int, levels: int, what: str) -> int:
+    """Checks a luma pyramid buffer (contiguous CUDA uint8 of at least arseg_luma_pyramid_bytes elements, 16-byte aligned) and returns that size."""
+    if not (1 <= H <= 8192 and 1 <= W <= 8192 and 1 <= levels <= 3):
+        raise _lib.ArsegError(f"{what}: H, W in 1..8192 and levels in 1..3; got {H}x{W}, levels {levels}")
+    nbytes = int(_lib.load().arseg_luma_pyramid_bytes(H, W, levels))
+    if t is not None and (not torch.is_tensor(t) or not t.is_cuda or t.dtype != torch.uint8 or t.dim() != 1 or not t.is_contiguous() or t.numel() < nbytes
+                          or t.data_ptr() % 16):
+        raise _lib.ArsegError(f"{what}: a pyramid of {H}x{W} with {levels} levels is a contiguous, 16-byte aligned CUDA uint8 tensor of {nbytes} bytes")
+    return nbytes
+
+
+def luma_pyramid(plane: torch.Tensor, src_format: int, levels: int, out: Optional[torch.Tensor] = None) -> torch.Tensor:
+    """The luma8 pyramid of one frame (include/arseg_hip.h, arseg_luma_pyramid_fwd): ``plane`` is what ``DecodedFrames.luma_plane()`` returns;
+    level l of the flat uint8 buffer is at the offsets and pitches the header gives (``ingest.LumaPyramid`` holds the views).  One launch,
+    no synchronisation; with ``out`` passed, no allocation."""
+    H, W, pitch = _luma_plane(plane, src_format, "luma_pyramid")
+    levels = int(levels)
+    nbytes = _pyramid_buffer(out, H, W, levels, "luma_pyramid")
+    if out is None:
+        out = torch.empty(nbytes, dtype=torch.uint8, device=plane.device)
+    elif out.device != plane.device:
+        raise _lib.ArsegError(f"luma_pyramid: the plane is on {plane.device}, out on {out.device}")
+    launch("luma_pyramid", _lib.load().arseg_luma_pyramid_fwd, _ptr(plane), pitch, int(src_format), H, W, levels, _ptr(out), out.numel(), _stream())
+    return out
+
+
+def block_motion_pyr(cur_pyr: torch.Tensor, ref_pyr: torch.Tensor, H: int, W: int, levels: int, B: int = 16, Rt: int = 8, r: int = 1, lam: int = 2,
+                     intra: int = 255, ref_index: int = 0, records: Optional[torch.Tensor] = None, sad=None, stats=None,
+                     workspace: Optional[torch.Tensor] = None):
+    """Hierarchical block motion of one frame against a reference frame (include/arseg_hip.h, arseg_block_motion_pyr_fwd) from their luma
+    pyramids (``luma_pyramid``): the full search with |dx|, |dy| <= Rt on level ``levels``, then per level below it +-r around twice the
+    vectors of the parent block and of its two neighbours on the block's side -> the records, sad and stats of ``block_motion``, with its
+    conventions for the three buffers.  ``workspace``: uint8, at least arseg_block_motion_pyr_workspace_bytes; None takes the host layer's.
+    ``levels`` + 1 launches, no synchronisation; with all four buffers passed in, no allocation.  Returns (records, sad, stats)."""
+    H, W, levels, B, Rt, r, lam, intra, ref_index = (int(v) for v in (H, W, levels, B, Rt, r, lam, intra, ref_index))
+    _pyramid_buffer(cur_pyr, H, W, levels, "block_motion_pyr (current frame)")
+    _pyramid_buffer(ref_pyr, H, W, levels, "block_motion_pyr (reference frame)")
+    if cur_pyr is None or ref_pyr is None or cur_pyr.device != ref_pyr.device:
+        raise _lib.ArsegError("block_motion_pyr: two pyramids on one device")
+    if B not in (8, 16) or not 1 <= Rt <= 32 or not 1 <= r <= 3 or not 0 <= lam <= 255 or not 0 <= intra <= 255 or not 0 <= ref_index <= 15:
+        raise _lib.ArsegError(f"block_motion_pyr: B in (8, 16), Rt in 1..32, r in 1..3, lam and intra in 0..255, ref_index in 0..15; got B {B}, Rt {Rt}, "
+                              f"r {r}, lam {lam}, intra {intra}, ref_index {ref_index}")
+    dev = cur_pyr.device
+    records, sad, stats = _bm_outputs("block_motion_pyr", H, W, B, dev, records, sad, stats)
+    nbytes = int(_lib.load().arseg_block_motion_pyr_workspace_bytes(H, W, B, levels))
+    if workspace is None:
+        workspace = _base.workspace(nbytes, dev)
+    elif not torch.is_tensor(workspace) or workspace.device != dev or workspace.dtype != torch.uint8 or not workspace.is_contiguous() \
+            or workspace.numel() < nbytes or workspace.data_ptr() % 16:
+        raise _lib.ArsegError(f"block_motion_pyr expects workspace as a contiguous, 16-byte aligned uint8 tensor of at least {nbytes} bytes on {dev}")
+    launch("block_motion_pyr", _lib.load().arseg_block_motion_pyr_fwd, _ptr(cur_pyr), _ptr(ref_pyr), H, W, levels, B, Rt, r, lam, intra, ref_index,
+           _ptr(records), _ptr(sad), _ptr(stats), _ptr(workspace), workspace.numel(), _stream())
     return records, sad, stats
 
 

@@ -697,8 +697,8 @@ int arseg_mv_records_bi_step_link_fwd(const int16_t *records, int n_records, int
  * intra outside 0 .. 255; ref_index outside 0 .. 15; an unknown src_format; a pitch below the row's bytes (W, 2 W for the 16-bit formats,
  * 3 W for RGB8); a pitch or plane pointer that is odd with a 16-bit format; records not 16-byte, sad not 4-byte, stats not 8-byte aligned.
  * ARSEG_EWORKSPACE: workspace_bytes below arseg_block_motion_workspace_bytes(H, W, B, R).
- * Not covered: sub-pel refinement (the chain rounds every hop to whole pixels), hierarchical or predictive search, variable block sizes,
- * two references per block, chroma.
+ * Not covered: sub-pel refinement (the chain rounds every hop to whole pixels), variable block sizes, two references per block, chroma.
+ * (Reach beyond 32 pixels: the hierarchical search below.)
  * ------------------------------------------------------------------------------------------- */
 #define ARSEG_BM_INTRA_REF 16
 #define ARSEG_BM_NSTATS 4
@@ -706,6 +706,58 @@ size_t arseg_block_motion_workspace_bytes(int H, int W, int B, int R);
 int arseg_block_motion_fwd(const void *cur, int64_t cur_pitch, const void *ref, int64_t ref_pitch, int src_format, int H, int W, int B, int R,
                            int lambda, int intra, int ref_index, int16_t *records, uint32_t *sad, int64_t *stats, void *workspace,
                            size_t workspace_bytes, arseg_stream_t stream);
+
+/* ---------------------------------------------------------------------------------------------
+ * Hierarchical block motion search (csrc/block_motion_pyr.hip): the same records from a coarse-to-fine search over a luma8 pyramid --
+ * a reach of Rt 2^L + r (2^L - 1) pixels for about a hundredth of the full search's SADs.  All integers: two runs are bit-equal.
+ *   pyramid     P_0 = the luma8 plane of the source (formats and luma8 as above), H_0 x W_0 = H x W in 1 .. 8192; for l = 0 .. L - 1,
+ *               L = levels in 1 .. 3:  H_{l+1} = (H_l + 1) >> 1, W_{l+1} = (W_l + 1) >> 1,
+ *               P_{l+1}[y][x] = (a + b + c + d + 2) >> 2 over P_l[min(2 y + i, H_l - 1)][min(2 x + j, W_l - 1)], i, j in {0, 1}
+ *               (the last row / column is replicated where a size is odd)
+ *   buffer      uint8 on the device, 16-byte aligned: level l at byte offset off_l, rows pitch_l = (W_l + 15) & ~15 bytes apart, off_0 = 0,
+ *               off_{l+1} = off_l + pitch_l H_l; arseg_luma_pyramid_bytes = off_{L+1}.  Level 0 is materialised, so the search reads bytes
+ *               whatever the source format was.  The bytes of a row beyond W_l are unspecified and never count as pixels; nothing
+ *               beyond the total is touched.
+ *   block grids level l has by_l = ceil(H_l / B) rows of bx_l = ceil(W_l / B) blocks of B x B level-l pixels, B in {8, 16}, clipped at the
+ *               right and bottom edge as above; the grid of level 0 is the record grid above.  Block (bi, bj) of level l has the parent
+ *               (bi >> 1, bj >> 1) at level l + 1, which always exists.
+ *   top level   exactly arseg_block_motion_fwd's candidates, cost and winner on P_L(cur) against P_L(ref), of size H_L x W_L, with
+ *               R = Rt in 1 .. 32 and lambda; no intra test.  This is v_L per block.
+ *   refinement  for l = L - 1 .. 0, per block (bi, bj) of level l:
+ *     centres     (0, 0); 2 v_{l+1} of the parent; 2 v_{l+1} of the parent's horizontal neighbour on the child's side -- parent column
+ *                 (bj >> 1) + ((bj & 1) ? 1 : -1), if that column is in the grid; 2 v_{l+1} of its vertical neighbour likewise, with bi
+ *     candidates  the union (a vector proposed twice counts once) of centre + (ox, oy), |ox| <= r and |oy| <= r, r in 1 .. 3, whose
+ *                 displaced block lies inside P_l(ref): 0 <= x0 + dx, x0 + w + dx <= W_l, 0 <= y0 + dy, y0 + h + dy <= H_l.  Nothing is
+ *                 padded or clamped.  (0, 0) always is one.
+ *     cost        SAD + lambda (|dx| + |dy|), in level-l pixels
+ *     winner      the smallest (cost, rank): rank(0, 0) = 0, otherwise rank = 1 + (dy + 511) 1023 + (dx + 511) -- (0, 0) first, then the
+ *                 smallest dy, then the smallest dx.  (The reach at level 0 is at most 32 * 8 + 3 * 7 = 277, so rank < 2^20 and
+ *                 cost < 2^19: one 64-bit minimum of cost << 20 | rank decides.)
+ *   level 0     records, sad and stats as arseg_block_motion_fwd writes them: (x0, y0, w, h, 4 dx, 4 dy, ref_index, 0); SAD > intra w h
+ *               -> (x0, y0, w, h, 0, 0, ARSEG_BM_INTRA_REF, 0); sad of intra blocks too; stats ACCUMULATED INTO
+ *   workspace   16-byte aligned: the records of levels 1 .. L in the record format, 16 bytes per block, level 1 first (a parent's vector
+ *               is fields 4 and 5 divided by 4)
+ * Entry points (enqueue only: no host synchronisation, no allocation; a captured graph replays them):
+ *   arseg_luma_pyramid_bytes                the size of the buffer; 0 for H, W or levels out of range
+ *   arseg_luma_pyramid_fwd                  one launch for all levels; plane, pitch (bytes) and src_format as cur / cur_pitch above
+ *   arseg_block_motion_pyr_workspace_bytes  16 (by_1 bx_1 + .. + by_L bx_L); 0 for H, W, B or levels out of range
+ *   arseg_block_motion_pyr_fwd              levels + 1 launches on one stream, the levels top-down; cur_pyr and ref_pyr are pyramids of H x W
+ *                                           frames with `levels` levels; sad and stats may be NULL
+ * ARSEG_EINVAL before any launch: a null plane, pyramid, cur_pyr, ref_pyr, records or workspace; H or W outside 1 .. 8192; levels outside
+ * 1 .. 3; B outside {8, 16}; Rt outside 1 .. 32; r outside 1 .. 3; lambda or intra outside 0 .. 255; ref_index outside 0 .. 15; an unknown
+ * src_format; a pitch below the row's bytes; a pitch or plane pointer that is odd with a 16-bit format; a pyramid or workspace that is not
+ * 16-byte aligned; records not 16-byte, sad not 4-byte, stats not 8-byte aligned; pyramid_bytes below arseg_luma_pyramid_bytes(H, W, levels).
+ * ARSEG_EWORKSPACE: workspace_bytes below arseg_block_motion_pyr_workspace_bytes(H, W, B, levels).
+ * Not covered: sub-pel refinement, predictors from the previous frame's field or from spatial neighbours at the same level, variable block
+ * sizes, two references per block, chroma, more than three levels, caching pyramids across calls (a caller keeps the buffers it built).
+ * ------------------------------------------------------------------------------------------- */
+size_t arseg_luma_pyramid_bytes(int H, int W, int levels);
+int arseg_luma_pyramid_fwd(const void *plane, int64_t pitch, int src_format, int H, int W, int levels, uint8_t *pyramid, size_t pyramid_bytes,
+                           arseg_stream_t stream);
+size_t arseg_block_motion_pyr_workspace_bytes(int H, int W, int B, int levels);
+int arseg_block_motion_pyr_fwd(const uint8_t *cur_pyr, const uint8_t *ref_pyr, int H, int W, int levels, int B, int Rt, int r, int lambda, int intra,
+                               int ref_index, int16_t *records, uint32_t *sad, int64_t *stats, void *workspace, size_t workspace_bytes,
+                               arseg_stream_t stream);
 /* layout changes at the API boundary */
 int arseg_nchw_to_nhwc_fwd(const float *in, float *out, int N, int C, int HW, int out_ld, arseg_stream_t stream);
 int arseg_nhwc_to_nchw_fwd(const float *in, int in_ld, float *out, int N, int C, int HW, arseg_stream_t stream);
