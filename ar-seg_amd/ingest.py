@@ -18,6 +18,8 @@
   against the previous frame's (csrc/block_motion.hip; include/arseg_hip.h, arseg_block_motion_*); ``block_motion_numpy`` is that search on the host.
   ``MotionEstimator(levels=...)`` searches coarse to fine over a ``LumaPyramid`` and reaches past 32 pixels (csrc/block_motion_pyr.hip;
   arseg_luma_pyramid_*, arseg_block_motion_pyr_*; ``luma_pyramid_numpy`` and ``block_motion_pyr_numpy`` on the host).
+  ``MotionEstimator(anchor_refine=...)`` checks every block's composed displacement against the keyframe and re-anchors it there
+  (csrc/block_motion_anchor.hip; arseg_block_motion_anchor_fwd; ``block_motion_anchor_numpy`` on the host).
 """
 from __future__ import annotations
 
@@ -832,6 +834,81 @@ def block_motion_pyr_numpy(cur, ref, B: int = 16, Rt: int = 8, r: int = 1, lam: 
     return np.ascontiguousarray(rec.reshape(-1, 8).astype(np.int16)), sad.reshape(-1).astype(np.uint32), stats
 
 
+BMA_NSTATS = _lib.BMA_NSTATS          # ARSEG_BMA_NSTATS: anchored blocks, healed blocks, blocks kept on their hop, drift corrected in pixels
+
+
+def block_motion_anchor_numpy(cur, key, records, merged_prev, f: int, B: int = 16, r: int = 2, lam: int = 2, intra: int = 255):
+    """Keyframe anchoring of include/arseg_hip.h (arseg_block_motion_anchor_fwd) on the host: ``cur`` / ``key`` are uint8 luma planes [H,W] of
+    frame ``f`` and of the keyframe, ``records`` the hop records int16 [by*bx,8] of the B-grid (``block_motion_numpy``), ``merged_prev`` =
+    merged[f - 1] int16 [H,W,2] of the chain (None at f = 1).  Returns ``(records int16 [by*bx,8], sad_of_anchored int64 [by*bx], stats int64
+    [BMA_NSTATS])``: the records ``ops.block_motion_anchor`` writes, the anchored SAD of every anchored block and -1 for a block kept on its
+    hop (the entries the device form leaves untouched), stats from zero.  numpy only, one gather of the keyframe per centre and offset."""
+    a, k = luma8_numpy(cur).astype(np.int32), luma8_numpy(key).astype(np.int32)
+    f, B, r, lam, intra = int(f), int(B), int(r), int(lam), int(intra)
+    H, W = a.shape
+    if k.shape != a.shape:
+        raise ValueError(f"block_motion_anchor_numpy: the current frame is {a.shape}, the keyframe {k.shape}")
+    if not (1 <= H <= 8192 and 1 <= W <= 8192) or B not in (8, 16) or not 1 <= r <= 3 or not 0 <= lam <= 255 or not 0 <= intra <= 255 or not 1 <= f <= 16:
+        raise ValueError(f"block_motion_anchor_numpy: H, W in 1..8192, B in (8, 16), r in 1..3, lam and intra in 0..255, f in 1..16; got {H}x{W}, B {B}, "
+                         f"r {r}, lam {lam}, intra {intra}, f {f}")
+    by, bx = -(-H // B), -(-W // B)
+    rec = np.asarray(records)
+    if rec.dtype != np.int16 or rec.shape != (by * bx, 8):
+        raise ValueError(f"block_motion_anchor_numpy: {H}x{W} in blocks of {B} is int16 [{by * bx},8] records, got {rec.dtype} {rec.shape}")
+    if f == 1:
+        return rec.copy(), np.full(by * bx, -1, dtype=np.int64), np.zeros(BMA_NSTATS, dtype=np.int64)
+    mp = np.asarray(merged_prev)
+    if mp.dtype != np.int16 or mp.shape != (H, W, 2):
+        raise ValueError(f"block_motion_anchor_numpy: merged_prev is int16 [{H},{W},2], got {mp.dtype} {mp.shape}")
+    mp = mp.astype(np.int64)
+    x0, y0 = np.arange(bx) * B, np.arange(by) * B
+    w, h = np.minimum(B, W - x0), np.minimum(B, H - y0)
+    xc, yc = (x0 + w // 2)[None, :], (y0 + h // 2)[:, None]
+    q = rec.astype(np.int64).reshape(by, bx, 8)
+    usable = q[..., 6] == 0
+    hx, hy = np.where(usable, _round_half_even_div4(q[..., 4]), 0), np.where(usable, _round_half_even_div4(q[..., 5]), 0)
+    at = mp[np.clip(yc + hy, 0, H - 1), np.clip(xc + hx, 0, W - 1)]
+    px, py = hx + (at[..., 0] >> 2), hy + (at[..., 1] >> 2)               # pred(q) of every block
+    co = mp[np.broadcast_to(yc, (by, bx)), np.broadcast_to(xc, (by, bx))] >> 2
+    yes, zero = np.ones((by, bx), dtype=bool), np.zeros((by, bx), dtype=np.int64)
+
+    def neighbour(v, di, dj, fill):                                      # v of block (bi + di, bj + dj); fill where that is off the grid
+        out = np.full((by, bx), fill, dtype=v.dtype)
+        out[max(0, -di):by - max(0, di), max(0, -dj):bx - max(0, dj)] = v[max(0, di):by - max(0, -di), max(0, dj):bx - max(0, -dj)]
+        return out
+
+    centres = [(zero, zero, yes), (px, py, yes), (co[..., 0], co[..., 1], yes)]
+    centres += [(neighbour(px, di, dj, 0), neighbour(py, di, dj, 0), neighbour(usable, di, dj, False)) for di, dj in ((0, -1), (0, 1), (-1, 0), (1, 0))]
+    ap = np.zeros((by * B, bx * B), dtype=np.int32)
+    ap[:H, :W] = a
+    Y, X = np.arange(by * B)[:, None], np.arange(bx * B)[None, :]
+    inside = (Y < H) & (X < W)
+    best = np.full((by, bx), (1 << 62), dtype=np.int64)
+    for cx, cy, ok in centres:
+        for oy in range(-r, r + 1):
+            for ox in range(-r, r + 1):
+                dx, dy = cx + ox, cy + oy
+                valid = ok & (x0[None, :] + dx >= 0) & (x0[None, :] + w[None, :] + dx <= W) & (y0[:, None] + dy >= 0) & (y0[:, None] + h[:, None] + dy <= H)
+                if not valid.any():
+                    continue
+                yy = np.clip(Y + np.repeat(np.repeat(dy, B, axis=0), B, axis=1), 0, H - 1)
+                xx = np.clip(X + np.repeat(np.repeat(dx, B, axis=0), B, axis=1), 0, W - 1)
+                sad = (np.abs(ap - k[yy, xx]) * inside).reshape(by, B, bx, B).sum(axis=(1, 3), dtype=np.int64)
+                cand = ((sad + lam * (np.abs(dx - px) + np.abs(dy - py))) << 28) | (((dy + 8192) << 14) | (dx + 8192))
+                best = np.where(valid & (cand < best), cand, best)
+    dy, dx = ((best >> 14) & 16383) - 8192, (best & 16383) - 8192
+    drift = np.abs(dx - px) + np.abs(dy - py)
+    sad = (best >> 28) - lam * drift
+    anchored = sad <= intra * (h[:, None] * w[None, :])
+    out = q.copy()
+    new = np.zeros((by, bx, 8), dtype=np.int64)
+    new[..., 0], new[..., 1], new[..., 2], new[..., 3] = x0[None, :], y0[:, None], w[None, :], h[:, None]
+    new[..., 4], new[..., 5], new[..., 6] = 4 * dx, 4 * dy, f - 1
+    out[anchored] = new[anchored]
+    stats = np.array([anchored.sum(), (anchored & ~usable).sum(), (~anchored).sum(), drift[anchored].sum()], dtype=np.int64)
+    return np.ascontiguousarray(out.reshape(-1, 8).astype(np.int16)), np.where(anchored, sad, -1).reshape(-1).astype(np.int64), stats
+
+
 class LumaPyramid(object):
     """The luma8 pyramid of one frame on the GPU (include/arseg_hip.h, arseg_luma_pyramid_fwd; csrc/block_motion_pyr.hip): one uint8 buffer,
     allocated once.  ``build(frame)`` fills it from a one-frame ``DecodedFrames`` -- one launch, no synchronisation, no allocation -- and
@@ -880,18 +957,33 @@ class MotionEstimator(object):
     around its parents' doubled vectors, and ``reach`` = search 2^levels + refine (2^levels - 1) is the largest |dx|, |dy| in frame pixels.
     ``estimate`` then takes a ``DecodedFrames`` or an already built ``LumaPyramid`` for either argument; a frame is built into one of two
     pyramids the estimator owns (two more launches), so a caller who alternates two ``LumaPyramid``s of their own builds each frame once.
-    Still no synchronisation and no allocation.  ``levels=0`` is the full search, launch for launch."""
+    Still no synchronisation and no allocation.  ``levels=0`` is the full search, launch for launch.
+
+    ``anchor_refine`` in 1 .. 3 adds keyframe anchoring (csrc/block_motion_anchor.hip; arseg_block_motion_anchor_fwd; host form
+    ``block_motion_anchor_numpy``): hops to the previous frame compound their errors over a GOP, and a block that was intra once stays
+    flagged for the rest of it.  ``set_key(frame)`` once per GOP, then
+
+        chain.push(est.estimate_anchored(cur, prev, chain))
+
+    is ``estimate`` plus one launch that matches every block against the keyframe within +-``anchor_refine`` of the displacement the chain
+    would compose for it (and of its neighbours' and the co-located one), and rewrites a block whose SAD is at most ``anchor_intra`` per
+    pixel with ref = f - 1: target frame 0, one hop, this hop's flags only.  The chain needs ``max_ref`` >= its GOP's last frame index (at
+    most 16).  The result is in ``anchored`` (a second record buffer; ``records`` keeps the hops), the counts in ``anchor_stats``.  With 0
+    nothing of this is allocated and every path above is launch for launch as before."""
 
     def __init__(self, H: int, W: int, block: int = 16, search: int = 16, lam: int = 2, intra: int = 255, ref_index: int = 0, device="cuda",
-                 with_sad: bool = False, levels: int = 0, refine: int = 1):
+                 with_sad: bool = False, levels: int = 0, refine: int = 1, anchor_refine: int = 0, anchor_intra: int = 255):
         self.H, self.W, self.block, self.search = int(H), int(W), int(block), int(search)
         self.lam, self.intra, self.ref_index = int(lam), int(intra), int(ref_index)
         self.levels, self.refine = int(levels), int(refine)
+        self.anchor_refine, self.anchor_intra = int(anchor_refine), int(anchor_intra)
         try:
             _bm_args("MotionEstimator", self.H, self.W, self.block, self.search, self.lam, self.intra, self.ref_index)
             _bmp_args("MotionEstimator", self.levels, self.refine)
         except ValueError as e:
             raise _lib.ArsegError(str(e)) from None
+        if not 0 <= self.anchor_refine <= 3 or not 0 <= self.anchor_intra <= 255:
+            raise _lib.ArsegError(f"MotionEstimator: anchor_refine in 0..3 and anchor_intra in 0..255; got {self.anchor_refine}, {self.anchor_intra}")
         self.device = torch.device(device)
         if self.device.type != "cuda":
             raise _lib.ArsegError("MotionEstimator runs on the GPU only; there is no CPU fallback (block_motion_numpy is the host form)")
@@ -903,6 +995,11 @@ class MotionEstimator(object):
             self._pyramids = (LumaPyramid(self.H, self.W, self.levels, self.device), LumaPyramid(self.H, self.W, self.levels, self.device))
             nbytes = _lib.load().arseg_block_motion_pyr_workspace_bytes(self.H, self.W, self.block, self.levels)
             self._workspace = torch.zeros(nbytes, dtype=torch.uint8, device=self.device)
+        self._key_plane = self._cur_pyramid = None
+        if self.anchor_refine:
+            self.anchored = torch.zeros((self.n_blocks, 8), dtype=torch.int16, device=self.device)
+            self.anchor_stats = torch.zeros(BMA_NSTATS, dtype=torch.int64, device=self.device)
+            self._key_pyramid = LumaPyramid(self.H, self.W, self.levels, self.device) if self.levels else None
 
     @property
     def reach(self) -> int:
@@ -920,6 +1017,7 @@ class MotionEstimator(object):
                 pyr.append(own.build(f))
             else:
                 raise _lib.ArsegError(f"MotionEstimator.estimate: {what} must be one DecodedFrames frame of {self.H}x{self.W} or a built LumaPyramid")
+        self._cur_pyramid = pyr[0]
         ops.block_motion_pyr(pyr[0].buffer, pyr[1].buffer, self.H, self.W, self.levels, self.block, self.search, self.refine, self.lam, self.intra,
                              self.ref_index, records=self.records, sad=self.sad if self.sad is not None else False, stats=self.stats,
                              workspace=self._workspace)
@@ -939,8 +1037,72 @@ class MotionEstimator(object):
                          records=self.records, sad=self.sad if self.sad is not None else False, stats=self.stats)
         return self.records
 
+    def _aligned_luma(self, frame, who):
+        """The uint8 luma plane [H,W] of a one-frame NV12 / I420 ``DecodedFrames`` if it meets the anchor's alignment rule."""
+        if not isinstance(frame, DecodedFrames) or frame.N != 1 or (frame.H, frame.W) != (self.H, self.W):
+            raise _lib.ArsegError(f"MotionEstimator.{who}: expected one DecodedFrames frame of {self.H}x{self.W} or a built LumaPyramid")
+        plane, src_format = frame.luma_plane()
+        p = plane[0]
+        if src_format not in (_lib.SRC_NV12, _lib.SRC_I420) or p.device != self.device or p.stride(1) != 1 or p.data_ptr() % 4 \
+                or (self.H > 1 and (p.stride(0) % 4 or p.stride(0) < ((self.W + 3) & ~3))):
+            raise _lib.ArsegError(f"MotionEstimator.{who}: with levels=0 the anchor reads the frame's own luma plane, which must be an NV12 / I420 byte "
+                                  f"plane on {self.device} with a 4-byte aligned base and a pitch that is a multiple of 4; any other frame needs levels >= 1 "
+                                  f"(level 0 of the luma pyramid is such a plane)")
+        return p
+
+    def set_key(self, frame) -> None:
+        """The keyframe of the GOP that ``estimate_anchored`` anchors on: a one-frame ``DecodedFrames`` (with ``levels`` >= 1 built into a third
+        pyramid the estimator owns: one launch; with ``levels=0`` an NV12 / I420 frame whose luma plane is 4-byte aligned, read in place) or a
+        built ``LumaPyramid`` of this size, whose level 0 is read in place.  No synchronisation, no allocation."""
+        if not self.anchor_refine:
+            raise _lib.ArsegError("MotionEstimator.set_key: this estimator was made with anchor_refine=0")
+        if isinstance(frame, LumaPyramid):
+            if (frame.H, frame.W, frame.device) != (self.H, self.W, self.device):
+                raise _lib.ArsegError(f"MotionEstimator.set_key: the keyframe must be a LumaPyramid of {self.H}x{self.W} on {self.device}")
+            self._key_plane = frame.level(0)
+        elif self.levels:
+            if not isinstance(frame, DecodedFrames) or frame.N != 1 or (frame.H, frame.W) != (self.H, self.W):
+                raise _lib.ArsegError(f"MotionEstimator.set_key: expected one DecodedFrames frame of {self.H}x{self.W} or a built LumaPyramid")
+            self._key_plane = self._key_pyramid.build(frame).level(0)
+        else:
+            self._key_plane = self._aligned_luma(frame, "set_key")
+
+    def estimate_anchored(self, cur, ref, chain) -> torch.Tensor:
+        """``estimate(cur, ref)``, then one anchor launch for frame f = ``chain.f`` + 1 against the keyframe of ``set_key`` with ``chain.merged[f - 1]``
+        -> ``anchored`` (the same buffer every call), which ``chain.push`` takes.  ``chain`` is the in-order ``MotionChain`` the result is pushed
+        to next; it is read, not advanced.  Raises for a bidirectional chain, for ``chain.max_ref`` < f (ref = f - 1 would be unusable), for a
+        size or device mismatch and before ``set_key``.  Neither synchronises nor allocates."""
+        if not self.anchor_refine:
+            raise _lib.ArsegError("MotionEstimator.estimate_anchored: this estimator was made with anchor_refine=0")
+        if self._key_plane is None:
+            raise _lib.ArsegError("MotionEstimator.estimate_anchored: set_key(frame) first, once per GOP")
+        if not isinstance(chain, MotionChain) or chain.bidirectional:
+            raise _lib.ArsegError("MotionEstimator.estimate_anchored: anchoring needs an in-order MotionChain (bidirectional chains are not covered)")
+        if (chain.H, chain.W, chain.device) != (self.H, self.W, self.device):
+            raise _lib.ArsegError(f"MotionEstimator.estimate_anchored: the chain is {chain.H}x{chain.W} on {chain.device}, the estimator {self.H}x{self.W} on {self.device}")
+        f = chain.f + 1
+        if f >= chain.gop or f > 16 or chain.max_ref < f:
+            raise _lib.ArsegError(f"MotionEstimator.estimate_anchored: frame {f} needs a chain with gop > {f} and max_ref >= {f} (at most 16): an anchored "
+                                  f"record carries ref = {f - 1}; the chain has gop {chain.gop}, max_ref {chain.max_ref}")
+        cur_plane = None if self.levels else self._aligned_luma(cur, "estimate_anchored")
+        records = self.estimate(cur, ref)
+        if self.levels:
+            cur_plane = self._cur_pyramid.level(0)
+        ops.block_motion_anchor(cur_plane, self._key_plane, records, chain.merged[f - 1] if f >= 2 else None, f, self.block, self.anchor_refine, self.lam,
+                                self.anchor_intra, out=self.anchored, sad=self.sad if self.sad is not None else False, stats=self.anchor_stats)
+        return self.anchored
+
     def reset_stats(self) -> None:
         self.stats.zero_()
+        if self.anchor_refine:
+            self.anchor_stats.zero_()
+
+    def anchor_stats_row(self) -> torch.Tensor:
+        """int64 [BMA_NSTATS], accumulated since ``reset_stats``: anchored blocks, anchored blocks whose hop was unusable (healed), blocks kept on
+        their hop, and the drift corrected (sum of |anchor - chain's prediction| in pixels).  A device tensor: reading it on the host synchronises."""
+        if not self.anchor_refine:
+            raise _lib.ArsegError("MotionEstimator.anchor_stats_row: this estimator was made with anchor_refine=0")
+        return self.anchor_stats
 
     def stats_row(self) -> torch.Tensor:
         """int64 [BM_NSTATS], accumulated since ``reset_stats``: intra blocks, matched blocks with the zero vector, the sum of SAD and the

@@ -675,6 +675,49 @@ def block_motion_pyr(cur_pyr: torch.Tensor, ref_pyr: torch.Tensor, H: int, W: in
     return records, sad, stats
 
 
+def block_motion_anchor(cur_plane: torch.Tensor, key_plane: torch.Tensor, records: torch.Tensor, merged_prev: Optional[torch.Tensor], f: int, B: int = 16,
+                        r: int = 2, lam: int = 2, intra: int = 255, out: Optional[torch.Tensor] = None, sad=None, stats=None):
+    """Anchors the estimated hop records of frame ``f`` on the keyframe (include/arseg_hip.h, arseg_block_motion_anchor_fwd): every block of
+    ``cur_plane`` is matched in ``key_plane`` within +-r of the displacement the chain would compose for it from ``records`` and
+    ``merged_prev`` (= merged[f - 1], int16 [H,W,2]; None at f = 1) and of its neighbours' and the co-located one; a block whose best SAD
+    is at most ``intra`` per pixel gets a record with ref = f - 1 (target: the keyframe), any other keeps its hop record.  The planes are
+    uint8 luma planes [H,W] with a 4-byte aligned base and pitch (level 0 of a ``LumaPyramid``, an aligned NV12 / I420 luma plane).
+    ``out`` / ``sad`` / ``stats`` with ``block_motion``'s conventions, except that sad is read-modify-write (entries of anchored blocks
+    only; allocated zeroed) and stats is int64 [BMA_NSTATS].  ``out`` must not overlap ``records``.  One launch, no synchronisation; with
+    all three buffers passed in, no allocation.  Returns (out, sad, stats)."""
+    H, W, cur_pitch = _luma_plane(cur_plane, _lib.SRC_NV12, "block_motion_anchor (current frame)")
+    H2, W2, key_pitch = _luma_plane(key_plane, _lib.SRC_NV12, "block_motion_anchor (keyframe)")
+    f, B, r, lam, intra = int(f), int(B), int(r), int(lam), int(intra)
+    dev = cur_plane.device
+    if (H2, W2) != (H, W) or key_plane.device != dev:
+        raise _lib.ArsegError(f"block_motion_anchor: the current frame is {H}x{W} on {dev}, the keyframe {H2}x{W2} on {key_plane.device}")
+    if not (1 <= H <= 8192 and 1 <= W <= 8192) or B not in (8, 16) or not 1 <= r <= 3 or not 0 <= lam <= 255 or not 0 <= intra <= 255 or not 1 <= f <= 16:
+        raise _lib.ArsegError(f"block_motion_anchor: H, W in 1..8192, B in (8, 16), r in 1..3, lam and intra in 0..255, f in 1..16; got {H}x{W}, B {B}, "
+                              f"r {r}, lam {lam}, intra {intra}, f {f}")
+    for what, t, pitch in (("current frame", cur_plane, cur_pitch), ("keyframe", key_plane, key_pitch)):
+        if t.data_ptr() % 4 or pitch % 4 or pitch < ((W + 3) & ~3):
+            raise _lib.ArsegError(f"block_motion_anchor ({what}): the plane's base must be 4-byte aligned and its pitch a multiple of 4 of at least "
+                                  f"{(W + 3) & ~3} bytes, got an offset of {t.data_ptr() % 4} and a pitch of {pitch} (level 0 of a LumaPyramid qualifies)")
+    n = -(-H // B) * -(-W // B)
+    if _mv_records(records, "block_motion_anchor") != n or records.device != dev:
+        raise _lib.ArsegError(f"block_motion_anchor: {H}x{W} in blocks of {B} is {n} records on {dev}, got {tuple(records.shape)} on {records.device}")
+    if merged_prev is None:
+        if f >= 2:
+            raise _lib.ArsegError(f"block_motion_anchor: frame {f} needs merged_prev = merged[{f - 1}]")
+    elif not torch.is_tensor(merged_prev) or merged_prev.dtype != torch.int16 or merged_prev.device != dev or tuple(merged_prev.shape) != (H, W, 2) \
+            or not merged_prev.is_contiguous():
+        raise _lib.ArsegError(f"block_motion_anchor expects merged_prev as a contiguous int16 tensor [{H},{W},2] on {dev}")
+    if sad is None:
+        sad = torch.zeros(n, dtype=torch.int32, device=dev)
+    out, sad, stats = _bm_outputs("block_motion_anchor", H, W, B, dev, out, sad, stats)
+    lo, hi = records.data_ptr(), records.data_ptr() + 16 * n
+    if out.data_ptr() < hi and lo < out.data_ptr() + 16 * n:
+        raise _lib.ArsegError("block_motion_anchor: out must not overlap records (neighbour blocks read the input while the output is written)")
+    launch("block_motion_anchor", _lib.load().arseg_block_motion_anchor_fwd, _ptr(cur_plane), cur_pitch, _ptr(key_plane), key_pitch, H, W, B, r, lam, intra, f,
+           _ptr(records), _ptr(merged_prev), _ptr(out), _ptr(sad), _ptr(stats), _stream())
+    return out, sad, stats
+
+
 def argmax_confusion(logits: torch.Tensor, label: Optional[torch.Tensor], H: int, W: int, hist: Optional[torch.Tensor] = None,
                      ignore_label: int = 255, want_pred: bool = True, align_corners: bool = True):
     """Evaluator tail (evaluation.py:201-209): returns (pred int32 [N,H,W] or None, hist int64 [n_cls,n_cls] or None).

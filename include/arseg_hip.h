@@ -758,6 +758,56 @@ size_t arseg_block_motion_pyr_workspace_bytes(int H, int W, int B, int levels);
 int arseg_block_motion_pyr_fwd(const uint8_t *cur_pyr, const uint8_t *ref_pyr, int H, int W, int levels, int B, int Rt, int r, int lambda, int intra,
                                int ref_index, int16_t *records, uint32_t *sad, int64_t *stats, void *workspace, size_t workspace_bytes,
                                arseg_stream_t stream);
+
+/* ---------------------------------------------------------------------------------------------
+ * Keyframe anchoring of estimated block motion (csrc/block_motion_anchor.hip).  The records above are hops to the previous frame; the chain
+ * composes them into the displacement to the keyframe, so a wrong hop is inherited by every later frame of the GOP, and a block that was
+ * intra once stays flagged ARSEG_LINK_INTRA although its content is visible again.  The keyframe's luma is on the card: this entry checks
+ * the composed displacement of every block of frame f against the keyframe directly and, where a match is found, rewrites the block's
+ * record with ref = f - 1 -- target frame 0, one hop, this hop's flags only.  arseg_mv_records_step_* take the result as they are.
+ *   cur, key    luma8 byte planes [H][W] of frame f and of the keyframe, rows cur_pitch / key_pitch BYTES apart; the base 4-byte aligned,
+ *               the pitch a multiple of 4 and at least (W + 3) & ~3.  Level 0 of a luma pyramid qualifies, and so does an aligned NV12 /
+ *               I420 luma plane.  The bytes of a row beyond W are unspecified and never count.  H, W in 1 .. 8192
+ *   blocks      B in {8, 16}: the grid of arseg_block_motion_fwd; block (bi, bj) is record b = bi bx + bj of records_in and records_out,
+ *               x0 = bj B, y0 = bi B, w = min(B, W - x0), h = min(B, H - y0).  Of records_in[b] only fields 4, 5 and 6 are read
+ *   hop(q)      of a block q: USABLE iff field 6 of records_in[q] is 0 (the previous frame); then (hx, hy) = round_half_even_div4 of
+ *               fields 4 and 5, as the chain rounds.  Otherwise (ARSEG_BM_INTRA_REF, any other index) unusable and (hx, hy) = (0, 0)
+ *   pred(q)     with (xc, yc) = (x0 + w / 2, y0 + h / 2) of q, integer division: p = (clamp(xc + hx, 0, W - 1), clamp(yc + hy, 0, H - 1)),
+ *               pred(q) = (hx, hy) + (merged_prev[p.y][p.x] >> 2), the shift arithmetic (the chain writes multiples of 4)
+ *   merged_prev merged[f - 1] of the chain, int16 [H][W][2], 4-byte aligned
+ *   centres     of block b, in this order: C0 = (0, 0); C1 = pred(b); C2 = merged_prev[yc][xc] >> 2, the co-located vector (what the
+ *               chain's intra rule would assign); C3 .. C6 = pred(q) of the left, right, upper and lower neighbour block, each where it
+ *               is in the grid AND its hop is usable
+ *   candidates  the union (a vector proposed twice counts once) of centre + (ox, oy), |ox| <= r and |oy| <= r, r in 1 .. 3, whose displaced
+ *               block lies inside the keyframe: 0 <= x0 + dx, x0 + w + dx <= W, 0 <= y0 + dy, y0 + h + dy <= H.  Nothing is padded or
+ *               clamped.  (0, 0) always is one
+ *   cost        SAD(cur block, key block at (dx, dy)) + lambda (|dx - C1x| + |dy - C1y|): the distance from the chain's own answer;
+ *               lambda in 0 .. 255
+ *   winner      the smallest cost; among equals the smallest dy, then the smallest dx.  (cost < 2^24 and
+ *               (dy + 8192) 16384 + (dx + 8192) < 2^28: one 64-bit minimum of cost << 28 | that decides.)
+ *   record      winner's SAD <= intra w h (intra in 0 .. 255): the block is ANCHORED, records_out[b] = (x0, y0, w, h, 4 dx, 4 dy, f - 1, 0).
+ *               Otherwise records_out[b] = records_in[b], all eight fields.  f in 1 .. 16 (ref = f - 1 must stay below max_ref <= 16).
+ *               f == 1: the hop already targets the keyframe; records_out = records_in, key and merged_prev are not read (merged_prev
+ *               may be NULL), sad and stats are not touched
+ *   sad         uint32 [by * bx], may be NULL; READ-MODIFY-WRITE: the entries of anchored blocks become the anchored SAD, the others
+ *               are left as they were
+ *   stats       int64 [ARSEG_BMA_NSTATS], 8-byte aligned, may be NULL; ACCUMULATED INTO: [0] anchored blocks, [1] anchored blocks whose
+ *               hop was unusable (healed), [2] blocks kept on their hop, [3] sum over anchored blocks of |dx - C1x| + |dy - C1y| (the drift
+ *               corrected, in pixels).  Integers: two runs are bit-equal
+ *   records_out must not overlap records_in: neighbour centres read other blocks' input records while this block's output is written; in
+ *               place the result would depend on scheduling.  Overlapping buffers are refused.
+ * Enqueue only: one launch, no host synchronisation, no allocation, no workspace; a captured graph replays it.
+ * ARSEG_EINVAL before any launch: a null cur, key, records_in or records_out; a null merged_prev at f >= 2; H or W outside 1 .. 8192; B
+ * outside {8, 16}; r outside 1 .. 3; lambda or intra outside 0 .. 255; f outside 1 .. 16; a plane base that is not 4-byte aligned, a pitch
+ * that is no multiple of 4 or below (W + 3) & ~3; records not 16-byte aligned, merged_prev or sad not 4-byte aligned, stats not 8-byte
+ * aligned; overlapping record buffers.
+ * Not covered: bidirectional chains, anchoring decoder records of arbitrary geometry, anchoring on a frame other than 0, choosing by cost
+ * between hop and anchor (an anchor that passes the intra bound always wins), GOPs above 17 frames.
+ * ------------------------------------------------------------------------------------------- */
+#define ARSEG_BMA_NSTATS 4
+int arseg_block_motion_anchor_fwd(const uint8_t *cur, int64_t cur_pitch, const uint8_t *key, int64_t key_pitch, int H, int W, int B, int r, int lambda,
+                                  int intra, int f, const int16_t *records_in, const int16_t *merged_prev, int16_t *records_out, uint32_t *sad,
+                                  int64_t *stats, arseg_stream_t stream);
 /* layout changes at the API boundary */
 int arseg_nchw_to_nhwc_fwd(const float *in, float *out, int N, int C, int HW, int out_ld, arseg_stream_t stream);
 int arseg_nhwc_to_nchw_fwd(const float *in, int in_ld, float *out, int N, int C, int HW, arseg_stream_t stream);
