@@ -150,7 +150,10 @@ int arseg_creff_warp_fwd(const float *const *ref_nhwc_host, const int16_t *mv_q,
  * consumer waves of different rows overlap); TILES: the 16 x 16 tile kernel of rounds 2-3 (creff_rr.hip).  seg_rows = rows of a strip
  * segment (> 0: the rolling kernel works on fixed segments of that many rows, rounded up to even, and raised if a workgroup would get more
  * than 64 of them; 0 = default: whole strips dealt to the workgroups, the remainder cut into equal runs of row pairs); max_wgs = upper bound on its persistent
- * workgroups (0 = one per compute unit; fewer leave compute units to kernels of other streams).  No environment variables are read. */
+ * workgroups (0 = one per compute unit; fewer leave compute units to kernels of other streams).  No environment variables are read.
+ * Both kernels compute in split fp16: the operand range stated at arseg_creff_fwd_ex (full precision for |Q|, |K|, |V|, |p_out| <= 65504,
+ * 11-bit lo halves up to 131008, a silent clamp beyond, an absolute floor of 2^-24 for small features, no range watch) holds for them as it
+ * stands, the warped keyframe feature taking the place of hr; tests/test_gpu_creff_accuracy.py holds every schedule of both to it. */
 int arseg_creff_warp_fwd_ex(const float *const *ref_nhwc_host, const int16_t *mv_q, int H, int W, const float *lr,
                             const float *wq, const float *bq, const float *wk, const float *bk, const float *wv,
                             const float *bv, float *p_out, int p_layout, const float *wf, const float *bf, int n_cls,
@@ -179,7 +182,22 @@ int arseg_creff_warp16_fwd_ex(const void *const *ref_nhwc_host, const void *lr, 
                               int seg_rows, int max_wgs, arseg_stream_t stream);
 
 /* The same with the kernel choice made explicit (measurements, tests): impl = enum arseg_creff_impl (AUTO: the matrix-core kernel
- * for C >= 128, the VALU kernel otherwise); mfma_tile_rows = 0 (by launch size), 8 or 16.  No environment variables are read. */
+ * for C >= 128, the VALU kernel otherwise); mfma_tile_rows = 0 (by launch size), 8 or 16.  No environment variables are read.
+ * Operand range of the matrix-core kernels (creff_mfma.hip behind this entry point; creff_roll.hip and creff_rr.hip behind
+ * arseg_creff_warp_fwd_ex; the VALU kernel is plain fp32 and has none): fp32 emulated on the fp16 matrix cores.  Five operands are split
+ * into hi + lo fp16 halves rounded toward zero (22 significant bits): the query, key and value conv results Q, K, V, the un-normalised
+ * softmax weights P = exp(s - max) <= 1, and, for the classifier, the fused feature p_out and Wf.  A product is a_hi.b_hi + a_lo.b_lo +
+ * a_hi.b_lo + a_lo.b_hi with fp32 accumulation, error ~2^-21 relative per operand, one-sided.  Full precision needs |x| <= 65504 for
+ * every split operand; up to 131008 = 2 x 65504 the lo half keeps only 11 bits of x - 65504 (error up to 2^-11 of x); beyond, the pair
+ * clamps to +-131008 -- silently: the conversion never produces an infinity from a finite value, and no NaN appears.  Below the fp16 normal
+ * range a lo half is subnormal, an ABSOLUTE step of 2^-24 = 6e-8: uniformly small features (|V|, |p_out| << 1) carry an absolute error of
+ * up to 2^-24 (1 + 49 max|V|) in p_out whatever their magnitude, e.g. 2e-5 relative at |V| ~ 4e-3.  Nothing is scaled (the conv engine
+ * scales its weights per channel; Q, K, V here are split as computed) and there is NO range watch: unlike arseg_conv_desc.range_flag no
+ * device word reports an operand outside the range, so a caller whose features may leave O(1e-2) .. 65504 pins impl = ARSEG_CREFF_VALU
+ * (the fused entry point has no fp32 kernel: there, arseg_warp_mvq_fwd + this one).  Inside the range the result is within 4x (8x for
+ * one saturated-softmax case, where the fp32 loop itself is a single rounding) the error of the plain fp32 loop against fp64, for p_out
+ * and the logits; the statement, the clamp and the floor are tested for every kernel in tests/test_gpu_creff_accuracy.py (bounds and
+ * their CPU proof: tests/creff_accuracy.py, tests/test_creff_accuracy.py). */
 int arseg_creff_fwd_ex(const float *hr, const float *lr, const float *wq, const float *bq, const float *wk,
                        const float *bk, const float *wv, const float *bv, float *p_out, const float *wf, const float *bf,
                        int n_cls, float *logits, int log_softmax, int N, int C, int Hp, int Wp, int hp, int wp, int kH,
