@@ -15,7 +15,8 @@
 //             the wave; lane 0 decodes the rank, applies the intra bound and stores the record with one 16-byte vector store
 //   edge    : a block clipped by the right or bottom frame edge (w < B or h < B) takes a per-pixel walk, a lane per candidate
 //   stats   : one LDS partial per counter and workgroup, one 64-bit atomic per non-zero counter
-#include "block_motion_luma.h"
+// The record, the statistics and the argument checks are block_motion_wave.h's, shared with the refinement and the anchor.
+#include "block_motion_wave.h"
 
 constexpr int BM_TW = 64, BM_TH = 32;                                  // tile in pixels
 constexpr int BM_WIN_W = BM_TW + 2 * BM_MAX_R + 4, BM_WIN_H = BM_TH + 2 * BM_MAX_R;      // window at R = 32: 132 x 96 bytes
@@ -141,25 +142,14 @@ __global__ __launch_bounds__(256) void block_motion_kernel(const uint8_t *__rest
             if (rank) { dy = (rank - 1) / side - s.R; dx = (rank - 1) % side - s.R; }
             const unsigned sad = (key >> 13) - (unsigned)(s.lam * (abs(dx) + abs(dy)));
             const bool is_intra = sad > (unsigned)(intra * w * h);
-            int ref_w = ref_index;
-            if (is_intra) { dx = 0; dy = 0; ref_w = ARSEG_BM_INTRA_REF; }
+            if (is_intra) { dx = 0; dy = 0; }
             const size_t at = (size_t)(y0 / B) * bx_n + x0 / B;
-            records[at] = make_int4(x0 | (y0 << 16), w | (h << 16), ((4 * dx) & 0xffff) | ((4 * dy) << 16), ref_w);
+            records[at] = bm_record(x0, y0, w, h, dx, dy, is_intra ? ARSEG_BM_INTRA_REF : ref_index);
             if (sad_out) sad_out[at] = sad;
-            if (stats) {
-                if (is_intra) atomicAdd(&part[0], 1u);
-                else {
-                    if ((dx | dy) == 0) atomicAdd(&part[1], 1u);
-                    atomicAdd(&part[2], sad);
-                    atomicAdd(&part[3], (unsigned)(w * h));
-                }
-            }
+            if (stats) bm_stats_tally(part, is_intra, dx, dy, sad, w * h);
         }
     }
-    if (stats) {
-        __syncthreads();
-        if (tid < ARSEG_BM_NSTATS && part[tid]) atomicAdd(&stats[tid], (unsigned long long)part[tid]);
-    }
+    if (stats) bm_stats_flush(part, stats, tid);
 }
 
 extern "C" size_t arseg_block_motion_workspace_bytes(int H, int W, int B, int R) {
@@ -180,12 +170,10 @@ extern "C" int arseg_block_motion_fwd(const void *cur, int64_t cur_pitch, const 
                                       arseg_stream_t stream) {
     (void)workspace;
     ARSEG_CHECK_PTR(cur); ARSEG_CHECK_PTR(ref); ARSEG_CHECK_PTR(records);
-    if (H <= 0 || W <= 0 || H > BM_MAX_DIM || W > BM_MAX_DIM || (B != 8 && B != 16) || R < 1 || R > BM_MAX_R) return ARSEG_EINVAL;
-    if (lambda < 0 || lambda > 255 || intra < 0 || intra > 255 || ref_index < 0 || ref_index > 15) return ARSEG_EINVAL;
+    if (!bm_args_ok(H, W, B, lambda, intra, records, sad, stats) || R < 1 || R > BM_MAX_R || ref_index < 0 || ref_index > 15) return ARSEG_EINVAL;
     const int f = bm_format(src_format);
     if (f < 0) return ARSEG_EINVAL;
     if (!bm_plane_ok(f, cur, cur_pitch, W) || !bm_plane_ok(f, ref, ref_pitch, W)) return ARSEG_EINVAL;
-    if (!ARSEG_ALIGNED16(records) || (reinterpret_cast<uintptr_t>(sad) & 3u) || (reinterpret_cast<uintptr_t>(stats) & 7u)) return ARSEG_EINVAL;
     if (workspace_bytes < arseg_block_motion_workspace_bytes(H, W, B, R)) return ARSEG_EWORKSPACE;
     const int rpad = (R + 3) & ~3;
     const BmSearch s = {H, W, R, rpad, lambda, (BM_TW + 2 * rpad + 4) / 4};

@@ -5,20 +5,14 @@
 //             dword).  It converts the source to luma8 while staging (bm_luma4), writes level 0 as dwords, and reduces in LDS to levels
 //             1 .. L (32 x 16, 16 x 8, 8 x 4 bytes), each written as dwords.  The 2 x 2 box reads its source with the row and column clamped to
 //             the level's last: the replication for odd sizes happens in the tile that owns that row or column, and in no other
-//   refine  : a wave per block, 16 waves per workgroup, the grid capped at two workgroups per compute unit and walked with its stride.  The
-//             wave reads the records of the parent and of the two neighbour parents on its side (wave uniform), stages per centre the (B + 2 r)-row window of the reference level into LDS -- from the frame dword at or below the
-//             window's left edge, so that window dwords are frame dwords; what lies outside the level is 0 and is never part of a candidate
-//             that counts -- and holds its own block in one register: lane i has dword i.  A lane owns a candidate (centre, oy, ox): per block
-//             row and dword it realigns two window dwords (v_alignbyte_b32) against the block's dword, read with v_readlane_b32 into a scalar
-//             register, and one v_sad_u8 adds the four differences.  The same candidate from two centres gives the same key twice: the
-//             minimum counts it once
-//   winner  : key = cost << 20 | rank (64 bits, all ones where the level's border cuts the candidate off), minimum over the wave on the
-//             VALU; the record is one 16-byte vector store.  Level 0 applies the intra bound and writes sad and stats as block_motion.hip does
-//   edge    : a block clipped by the right or bottom edge of its level (w < B or h < B) takes the same path: its rows beyond h are skipped and
-//             the bytes of columns beyond w are masked to 0 in both operands of the SAD
-#include "block_motion_luma.h"
+//   refine  : the wave-per-block search of block_motion_wave.h (windows, SAD, clipped blocks).  The wave reads the records of the parent and of
+//             the two neighbour parents on its side (wave uniform): four centres with zero, a window each.  The same candidate from two
+//             centres gives the same key twice: the minimum counts it once
+//   winner  : key = cost << 20 | rank (64 bits), minimum over the wave on the VALU; the record is one 16-byte vector store.  Level 0 applies
+//             the intra bound and writes sad and stats as block_motion.hip does
+#include "block_motion_wave.h"
 
-constexpr int PYR_MAX_LEVELS = 3, PYR_MAX_REFINE = 3;
+constexpr int PYR_MAX_LEVELS = 3, PYR_MAX_REFINE = BMW_MAX_REFINE;
 constexpr int PYR_TW = 64, PYR_TH = 32;                                // tile of the source in pixels
 
 struct PyrGeom {
@@ -116,35 +110,22 @@ struct PyrRefine {
     int final_level, intra, ref_index;
 };
 
-constexpr unsigned long long PYR_NO_KEY = ~0ull;
-
-constexpr int PYR_WAVES = 16;                                          // waves per workgroup of the refinement: a wave per block
-
-// What a wave wrote to its own part of LDS is visible to its other lanes: the writes have landed, and nothing moves across this point.
-__device__ __forceinline__ void pyr_wave_sync() {
-    __builtin_amdgcn_fence(__ATOMIC_RELEASE, "workgroup");
-    __builtin_amdgcn_wave_barrier();
-    __builtin_amdgcn_fence(__ATOMIC_ACQUIRE, "workgroup");
-}
-
 // B: the block; RF: r, a template argument so that every division of the lane index is by a constant and the loops have constant trip counts.
-// A workgroup is 16 independent waves that walk the blocks with the grid's stride and meet only for the statistics: the grid is capped
-// (two workgroups per compute unit fill it), because the 64-bit atomics of all workgroups land on one cache line and are served one after
-// the other -- with a workgroup of four blocks they, not the search, set the time of level 0.
+// The wave-per-block search is block_motion_wave.h's; this kernel's own are its four centres, the cost lam (|dx| + |dy|) and the key's rank
+// (DESIGN.md section 6.21).  Every wave has four windows, each with rows for PYR_MAX_REFINE.
 template <int B, int RF>
-__global__ __launch_bounds__(64 * PYR_WAVES) void block_motion_refine_kernel(const uint8_t *__restrict__ cur, const uint8_t *__restrict__ ref, PyrRefine s,
+__global__ __launch_bounds__(64 * BMW_WAVES) void block_motion_refine_kernel(const uint8_t *__restrict__ cur, const uint8_t *__restrict__ ref, PyrRefine s,
                                                                              const int4 *__restrict__ parents, int4 *__restrict__ records,
                                                                              unsigned *__restrict__ sad_out, unsigned long long *__restrict__ stats) {
-    constexpr int CD = B / 4, ROWS = B + 2 * PYR_MAX_REFINE;
-    constexpr int WD = (B + 2 * PYR_MAX_REFINE + 3 + 3) / 4;           // window dwords per row: 3 bytes of alignment, 2 r + B of candidates; 7 or 5 (odd)
-    constexpr int r = RF, n = 2 * r + 1, n2 = n * n, rows = B + 2 * r;
-    __shared__ unsigned win_all[PYR_WAVES][4 * ROWS * WD];             // per wave: four centres
+    constexpr int SLOT = (B + 2 * PYR_MAX_REFINE) * BMW_WD<B>;         // dwords of one window
+    constexpr int r = RF, n = 2 * r + 1, n2 = n * n;
+    __shared__ unsigned win_all[BMW_WAVES][4 * SLOT];
     __shared__ unsigned part[ARSEG_BM_NSTATS];
     const int tid = threadIdx.x, lane = tid & 63, wave = __builtin_amdgcn_readfirstlane(tid >> 6);
     unsigned *win = win_all[wave];
     if (tid < ARSEG_BM_NSTATS) part[tid] = 0;
     __syncthreads();
-    for (int b = blockIdx.x * PYR_WAVES + wave; b < s.n_blocks; b += gridDim.x * PYR_WAVES) {          // wave uniform
+    for (int b = blockIdx.x * BMW_WAVES + wave; b < s.n_blocks; b += gridDim.x * BMW_WAVES) {          // wave uniform
         const int bi = b / s.bx, bj = b - bi * s.bx, x0 = bj * B, y0 = bi * B;
         const int w = min(B, s.W - x0), h = min(B, s.H - y0);
         // the four centres: zero, twice the parent's vector, twice the vectors of the parent's neighbours on this block's side
@@ -154,32 +135,16 @@ __global__ __launch_bounds__(64 * PYR_WAVES) void block_motion_refine_kernel(con
         const int cx1 = (short)(v1 & 0xffff) / 2, cy1 = (v1 >> 16) / 2;     // fields 4 and 5 are 4 v: twice the vector is half the field
         const int cx2 = (short)(v2 & 0xffff) / 2, cy2 = (v2 >> 16) / 2;
         const int cx3 = (short)(v3 & 0xffff) / 2, cy3 = (v3 >> 16) / 2;
-        // x is a multiple of 4 and x + 3 < pitch wherever x < W.  The window of a neighbour that is not in the grid is not staged: no candidate reads it
-        auto stage = [&](int k, int cx, int cy) {
-            const int ya = y0 + cy - r, xa = (x0 + cx - r) & ~3;
-#pragma unroll
-            for (int i0 = 0; i0 < rows * WD; i0 += 64) {
-                const int i = i0 + lane, wy = i / WD, wx = i - wy * WD, y = ya + wy, x = xa + 4 * wx;
-                if (i < rows * WD)
-                    win[(k * ROWS + wy) * WD + wx] = y >= 0 && y < s.H && x >= 0 && x < s.W ? *reinterpret_cast<const unsigned *>(ref + (size_t)y * s.pitch + x) : 0u;
-            }
-        };
+        // The window of a neighbour that is not in the grid is not staged: no candidate reads it
+        auto stage = [&](int k, int cx, int cy) { bmw_stage<B, r>(win + k * SLOT, ref, s.pitch, s.H, s.W, x0 + cx - r, y0 + cy - r, lane); };
         stage(0, 0, 0);
         stage(1, cx1, cy1);
         if (ok2) stage(2, cx2, cy2);
         if (ok3) stage(3, cx3, cy3);
-        // A block clipped to w x h by the level's edge: rows >= h are skipped, bytes at columns >= w are masked out of both operands
-        auto col_mask = [&](int c) { const int rem = w - 4 * c; return rem >= 4 ? 0xffffffffu : (rem <= 0 ? 0u : (1u << (8 * rem)) - 1u); };
-        unsigned mine = 0;                                             // lane i: dword i of the block
-        if (lane < B * CD) {
-            const int y = y0 + lane / CD, x = x0 + 4 * (lane % CD);
-            if (y < s.H && x < s.W) mine = *reinterpret_cast<const unsigned *>(cur + (size_t)y * s.pitch + x) & col_mask(lane % CD);
-        }
-        unsigned cmask[CD];                                            // wave uniform
-#pragma unroll
-        for (int c = 0; c < CD; ++c) cmask[c] = col_mask(c);
-        pyr_wave_sync();
-        unsigned long long best = PYR_NO_KEY;
+        unsigned cmask[B / 4];
+        const unsigned mine = bmw_load_block<B>(cur, s.pitch, s.H, s.W, x0, y0, lane, cmask);
+        bmw_wave_sync();
+        unsigned long long best = BMW_NO_KEY;
 #pragma unroll 1
         for (int q0 = 0; q0 < 4 * n2; q0 += 64) {                       // wave uniform: the lane reads below are reached by the whole wave
             const int q = min(q0 + lane, 4 * n2 - 1), k = q / n2, t = q - k * n2, oyi = t / n, oxi = t - oyi * n;
@@ -187,53 +152,27 @@ __global__ __launch_bounds__(64 * PYR_WAVES) void block_motion_refine_kernel(con
             const bool okc = k == 2 ? ok2 : (k == 3 ? ok3 : true);
             const int dx = cx + oxi - r, dy = cy + oyi - r;
             const bool valid = okc && q0 + lane < 4 * n2 && x0 + dx >= 0 && x0 + w + dx <= s.W && y0 + dy >= 0 && y0 + h + dy <= s.H;
-            // window byte (sb + c, oyi + rr) of centre k = level pixel (x0 + dx + c, y0 + dy + rr)
-            const int sb = x0 + dx - ((x0 + cx - r) & ~3);              // 0 .. 2 r + 3
-            unsigned sad = 0;
-            const unsigned *p = win + (k * ROWS + oyi) * WD + (sb >> 2);
-            const unsigned sh = (unsigned)sb & 3u;
-#pragma unroll
-            for (int rr = 0; rr < B; ++rr) {
-                if (rr < h) {                                           // wave uniform
-                    unsigned d[CD + 1];
-#pragma unroll
-                    for (int c = 0; c <= CD; ++c) d[c] = p[rr * WD + c];
-#pragma unroll
-                    for (int c = 0; c < CD; ++c)
-                        sad = __builtin_amdgcn_sad_u8(__builtin_amdgcn_alignbyte(d[c + 1], d[c], sh) & cmask[c], (unsigned)__builtin_amdgcn_readlane((int)mine, rr * CD + c), sad);
-                }
-            }
+            const unsigned sad = bmw_sad<B>(win + k * SLOT, oyi, ((x0 + cx - r) & 3) + oxi, h, cmask, mine);
             const unsigned cost = sad + (unsigned)(s.lam * (abs(dx) + abs(dy)));
             const unsigned rank = (dx | dy) == 0 ? 0u : (unsigned)(1 + (dy + 511) * 1023 + (dx + 511));
-            const unsigned long long key = valid ? ((unsigned long long)cost << 20) | rank : PYR_NO_KEY;
+            const unsigned long long key = valid ? ((unsigned long long)cost << 20) | rank : BMW_NO_KEY;
             best = key < best ? key : best;
         }
-        const unsigned long long key = ~wave_max_u64(~best);            // (0, 0) is always a candidate: a real key, uniform
+        const unsigned long long key = bmw_wave_min(best);              // (0, 0) is always a candidate: a real key
         if (lane == 0) {
             const int rank = (int)(key & 0xfffffu);
             int dx = 0, dy = 0;
             if (rank) { dy = (rank - 1) / 1023 - 511; dx = (rank - 1) % 1023 - 511; }
             const unsigned sad = (unsigned)(key >> 20) - (unsigned)(s.lam * (abs(dx) + abs(dy)));
             const bool is_intra = s.final_level && sad > (unsigned)(s.intra * w * h);
-            int ref_w = s.ref_index;
-            if (is_intra) { dx = 0; dy = 0; ref_w = ARSEG_BM_INTRA_REF; }
-            records[b] = make_int4(x0 | (y0 << 16), w | (h << 16), ((4 * dx) & 0xffff) | ((4 * dy) << 16), ref_w);
+            if (is_intra) { dx = 0; dy = 0; }
+            records[b] = bm_record(x0, y0, w, h, dx, dy, is_intra ? ARSEG_BM_INTRA_REF : s.ref_index);
             if (sad_out) sad_out[b] = sad;
-            if (stats) {
-                if (is_intra) atomicAdd(&part[0], 1u);
-                else {
-                    if ((dx | dy) == 0) atomicAdd(&part[1], 1u);
-                    atomicAdd(&part[2], sad);
-                    atomicAdd(&part[3], (unsigned)(w * h));
-                }
-            }
+            if (stats) bm_stats_tally(part, is_intra, dx, dy, sad, w * h);
         }
-        pyr_wave_sync();                                               // the next block's windows go where this one's were read
+        bmw_wave_sync();                                               // the next block's windows go where this one's were read
     }
-    if (stats) {
-        __syncthreads();
-        if (tid < ARSEG_BM_NSTATS && part[tid]) atomicAdd(&stats[tid], (unsigned long long)part[tid]);
-    }
+    if (stats) bm_stats_flush(part, stats, tid);
 }
 
 static int pyr_blocks(const PyrGeom &g, int l, int B) { return arseg_cdiv(g.H[l], B) * arseg_cdiv(g.W[l], B); }
@@ -250,10 +189,9 @@ extern "C" int arseg_block_motion_pyr_fwd(const uint8_t *cur_pyr, const uint8_t 
                                           int ref_index, int16_t *records, uint32_t *sad, int64_t *stats, void *workspace, size_t workspace_bytes,
                                           arseg_stream_t stream) {
     ARSEG_CHECK_PTR(cur_pyr); ARSEG_CHECK_PTR(ref_pyr); ARSEG_CHECK_PTR(records); ARSEG_CHECK_PTR(workspace);
-    if (!pyr_shape_ok(H, W, levels) || (B != 8 && B != 16) || Rt < 1 || Rt > BM_MAX_R || r < 1 || r > PYR_MAX_REFINE) return ARSEG_EINVAL;
-    if (lambda < 0 || lambda > 255 || intra < 0 || intra > 255 || ref_index < 0 || ref_index > 15) return ARSEG_EINVAL;
+    if (!pyr_shape_ok(H, W, levels) || !bm_args_ok(H, W, B, lambda, intra, records, sad, stats)) return ARSEG_EINVAL;
+    if (Rt < 1 || Rt > BM_MAX_R || r < 1 || r > PYR_MAX_REFINE || ref_index < 0 || ref_index > 15) return ARSEG_EINVAL;
     if (!ARSEG_ALIGNED16(cur_pyr) || !ARSEG_ALIGNED16(ref_pyr) || !ARSEG_ALIGNED16(workspace)) return ARSEG_EINVAL;
-    if (!ARSEG_ALIGNED16(records) || (reinterpret_cast<uintptr_t>(sad) & 3u) || (reinterpret_cast<uintptr_t>(stats) & 7u)) return ARSEG_EINVAL;
     if (workspace_bytes < arseg_block_motion_pyr_workspace_bytes(H, W, B, levels)) return ARSEG_EWORKSPACE;
     const PyrGeom g = pyr_geom(H, W, levels);
     int4 *lvl[PYR_MAX_LEVELS + 1] = {reinterpret_cast<int4 *>(records), reinterpret_cast<int4 *>(workspace)};      // the records of level l
@@ -263,18 +201,15 @@ extern "C" int arseg_block_motion_pyr_fwd(const uint8_t *cur_pyr, const uint8_t 
                                         g.W[levels], B, Rt, lambda, 255, 0, reinterpret_cast<int16_t *>(lvl[levels]), nullptr, nullptr, nullptr, 0, stream);
     if (status != ARSEG_OK) return status;
     hipStream_t st = arseg_stream(stream);
-    const int cus = arseg_cu_count();
     for (int l = levels - 1; l >= 0; --l) {
         const PyrRefine s = {g.H[l], g.W[l], g.pitch[l], arseg_cdiv(g.W[l], B), pyr_blocks(g, l, B), arseg_cdiv(g.W[l + 1], B), arseg_cdiv(g.H[l + 1], B),
                              lambda, l == 0, intra, l == 0 ? ref_index : 0};
         uint32_t *sad_l = l == 0 ? sad : nullptr;
         unsigned long long *stats_l = l == 0 ? reinterpret_cast<unsigned long long *>(stats) : nullptr;
-        const dim3 grid(min(arseg_cdiv(s.n_blocks, PYR_WAVES), 2 * cus));
-#define PYR_CASE(BB, RR)                                                                                                                  \
-    if (B == BB && r == RR)                                                                                                               \
-        hipLaunchKernelGGL((block_motion_refine_kernel<BB, RR>), grid, dim3(64 * PYR_WAVES), 0, st, cur_pyr + g.off[l], ref_pyr + g.off[l], s, lvl[l + 1], lvl[l], sad_l, stats_l);
-        PYR_CASE(8, 1) PYR_CASE(8, 2) PYR_CASE(8, 3) PYR_CASE(16, 1) PYR_CASE(16, 2) PYR_CASE(16, 3)
-#undef PYR_CASE
+        bmw_dispatch(B, r, [&](auto bb, auto rr) {
+            hipLaunchKernelGGL((block_motion_refine_kernel<bb(), rr()>), dim3(bmw_grid(s.n_blocks)), dim3(64 * BMW_WAVES), 0, st, cur_pyr + g.off[l], ref_pyr + g.off[l], s,
+                               lvl[l + 1], lvl[l], sad_l, stats_l);
+        });
     }
     return arseg_launch_status();
 }

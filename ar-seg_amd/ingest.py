@@ -683,6 +683,20 @@ def _bm_args(who, H, W, B, R, lam, intra, ref_index):
                          f"block {B}, search {R}, lam {lam}, intra {intra}, ref_index {ref_index}")
 
 
+def _bm_outputs(dx, dy, sad, H, W, B, intra, ref_index):
+    """The winners int64 [by,bx] of a block search as ``(records, sad, stats)``: a block whose SAD exceeds ``intra`` per pixel is written intra."""
+    by, bx = dx.shape
+    x0, y0 = np.arange(bx) * B, np.arange(by) * B
+    w, h = np.minimum(B, W - x0), np.minimum(B, H - y0)
+    is_intra = sad > intra * (h[:, None] * w[None, :])
+    rec = np.zeros((by, bx, 8), dtype=np.int64)
+    rec[..., 0], rec[..., 1], rec[..., 2], rec[..., 3] = x0[None, :], y0[:, None], w[None, :], h[:, None]
+    rec[..., 4], rec[..., 5], rec[..., 6] = np.where(is_intra, 0, 4 * dx), np.where(is_intra, 0, 4 * dy), np.where(is_intra, BM_INTRA_REF, ref_index)
+    m = ~is_intra
+    stats = np.array([is_intra.sum(), (m & (dx == 0) & (dy == 0)).sum(), sad[m].sum(), (h[:, None] * w[None, :])[m].sum()], dtype=np.int64)
+    return np.ascontiguousarray(rec.reshape(-1, 8).astype(np.int16)), sad.reshape(-1).astype(np.uint32), stats
+
+
 def block_motion_numpy(cur, ref, B: int = 16, R: int = 16, lam: int = 2, intra: int = 255, ref_index: int = 0, src_format: int = _lib.SRC_NV12):
     """The block search of include/arseg_hip.h (arseg_block_motion_fwd) on the host, for callers without a GPU at hand: ``cur`` / ``ref`` are
     the planes ``luma8_numpy`` takes for ``src_format``.  Returns ``(records int16 [by*bx,8], sad uint32 [by*bx], stats int64 [BM_NSTATS])`` --
@@ -718,14 +732,7 @@ def block_motion_numpy(cur, ref, B: int = 16, R: int = 16, lam: int = 2, intra: 
     rank, cost = best & 0x1fff, best >> 13
     dy = np.where(rank > 0, (rank - 1) // side - R, 0)
     dx = np.where(rank > 0, (rank - 1) % side - R, 0)
-    sad = cost - lam * (np.abs(dx) + np.abs(dy))
-    is_intra = sad > intra * (h[:, None] * w[None, :])
-    rec = np.zeros((by, bx, 8), dtype=np.int64)
-    rec[..., 0], rec[..., 1], rec[..., 2], rec[..., 3] = x0[None, :], y0[:, None], w[None, :], h[:, None]
-    rec[..., 4], rec[..., 5], rec[..., 6] = np.where(is_intra, 0, 4 * dx), np.where(is_intra, 0, 4 * dy), np.where(is_intra, BM_INTRA_REF, ref_index)
-    m = ~is_intra
-    stats = np.array([is_intra.sum(), (m & (dx == 0) & (dy == 0)).sum(), sad[m].sum(), (h[:, None] * w[None, :])[m].sum()], dtype=np.int64)
-    return np.ascontiguousarray(rec.reshape(-1, 8).astype(np.int16)), sad.reshape(-1).astype(np.uint32), stats
+    return _bm_outputs(dx, dy, cost - lam * (np.abs(dx) + np.abs(dy)), H, W, B, intra, ref_index)
 
 
 def luma_pyramid_layout(H: int, W: int, levels: int):
@@ -755,24 +762,15 @@ def luma_pyramid_numpy(plane, src_format: int = _lib.SRC_NV12, levels: int = 1) 
     return out
 
 
-def _refine_numpy(a, b, pvx, pvy, B, r, lam):
-    """One refinement level: the planes int32 [H_l,W_l], the parents' vectors int64 [by_{l+1},bx_{l+1}] -> (dx, dy, sad) int64 [by_l,bx_l].  One
-    gather of the reference per (centre, offset): every block reads at its own displacement."""
+def _bm_best_key(a, b, B, r, centres, key_of):
+    """The smallest ``key_of(sad, dx, dy)`` per block of plane ``a`` int32 [H,W] over the candidates +-``r`` around every centre ``(cx, cy, ok)``
+    (int64, int64, bool [by,bx]; a centre counts where ok) that leave the block inside plane ``b``; int64 [by,bx], 1 << 62 where there is none.
+    One gather of ``b`` per (centre, offset): every block reads at its own displacement, and what a clipped block lacks counts in neither
+    operand."""
     H, W = a.shape
     by, bx = -(-H // B), -(-W // B)
-    pby, pbx = pvx.shape
-    bi, bj = np.arange(by), np.arange(bx)
-    x0, y0 = bj * B, bi * B
+    x0, y0 = (np.arange(bx) * B)[None, :], (np.arange(by) * B)[:, None]
     w, h = np.minimum(B, W - x0), np.minimum(B, H - y0)
-    pi, pj = bi >> 1, bj >> 1
-    ni, nj = pi + np.where(bi & 1, 1, -1), pj + np.where(bj & 1, 1, -1)
-    oki, okj = (ni >= 0) & (ni < pby), (nj >= 0) & (nj < pbx)
-    ni, nj = np.clip(ni, 0, pby - 1), np.clip(nj, 0, pbx - 1)
-    yes = np.ones((by, bx), dtype=bool)
-    centres = [(np.zeros((by, bx), np.int64), np.zeros((by, bx), np.int64), yes),
-               (2 * pvx[pi][:, pj], 2 * pvy[pi][:, pj], yes),
-               (2 * pvx[pi][:, nj], 2 * pvy[pi][:, nj], yes & okj[None, :]),
-               (2 * pvx[ni][:, pj], 2 * pvy[ni][:, pj], yes & oki[:, None])]
     ap = np.zeros((by * B, bx * B), dtype=np.int32)
     ap[:H, :W] = a
     Y, X = np.arange(by * B)[:, None], np.arange(bx * B)[None, :]
@@ -782,15 +780,37 @@ def _refine_numpy(a, b, pvx, pvy, B, r, lam):
         for oy in range(-r, r + 1):
             for ox in range(-r, r + 1):
                 dx, dy = cx + ox, cy + oy
-                valid = ok & (x0[None, :] + dx >= 0) & (x0[None, :] + w[None, :] + dx <= W) & (y0[:, None] + dy >= 0) & (y0[:, None] + h[:, None] + dy <= H)
+                valid = ok & (x0 + dx >= 0) & (x0 + w + dx <= W) & (y0 + dy >= 0) & (y0 + h + dy <= H)
                 if not valid.any():
                     continue
                 yy = np.clip(Y + np.repeat(np.repeat(dy, B, axis=0), B, axis=1), 0, H - 1)
                 xx = np.clip(X + np.repeat(np.repeat(dx, B, axis=0), B, axis=1), 0, W - 1)
                 sad = (np.abs(ap - b[yy, xx]) * inside).reshape(by, B, bx, B).sum(axis=(1, 3), dtype=np.int64)
-                rank = np.where((dx == 0) & (dy == 0), 0, 1 + (dy + 511) * 1023 + (dx + 511))
-                key = ((sad + lam * (np.abs(dx) + np.abs(dy))) << 20) | rank
+                key = key_of(sad, dx, dy)
                 best = np.where(valid & (key < best), key, best)
+    return best
+
+
+def _refine_numpy(a, b, pvx, pvy, B, r, lam):
+    """One refinement level: the planes int32 [H_l,W_l], the parents' vectors int64 [by_{l+1},bx_{l+1}] -> (dx, dy, sad) int64 [by_l,bx_l]."""
+    H, W = a.shape
+    by, bx = -(-H // B), -(-W // B)
+    pby, pbx = pvx.shape
+    bi, bj = np.arange(by), np.arange(bx)
+    pi, pj = bi >> 1, bj >> 1
+    ni, nj = pi + np.where(bi & 1, 1, -1), pj + np.where(bj & 1, 1, -1)
+    oki, okj = (ni >= 0) & (ni < pby), (nj >= 0) & (nj < pbx)
+    ni, nj = np.clip(ni, 0, pby - 1), np.clip(nj, 0, pbx - 1)
+    yes = np.ones((by, bx), dtype=bool)
+    centres = [(np.zeros((by, bx), np.int64), np.zeros((by, bx), np.int64), yes),
+               (2 * pvx[pi][:, pj], 2 * pvy[pi][:, pj], yes),
+               (2 * pvx[pi][:, nj], 2 * pvy[pi][:, nj], yes & okj[None, :]),
+               (2 * pvx[ni][:, pj], 2 * pvy[ni][:, pj], yes & oki[:, None])]
+
+    def key_of(sad, dx, dy):
+        return ((sad + lam * (np.abs(dx) + np.abs(dy))) << 20) | np.where((dx == 0) & (dy == 0), 0, 1 + (dy + 511) * 1023 + (dx + 511))
+
+    best = _bm_best_key(a, b, B, r, centres, key_of)
     rank, cost = best & 0xfffff, best >> 20
     dy = np.where(rank > 0, (rank - 1) // 1023 - 511, 0)
     dx = np.where(rank > 0, (rank - 1) % 1023 - 511, 0)
@@ -822,16 +842,7 @@ def block_motion_pyr_numpy(cur, ref, B: int = 16, Rt: int = 8, r: int = 1, lam: 
     dx, dy = (top[:, 4] // 4).reshape(shape), (top[:, 5] // 4).reshape(shape)
     for l in range(levels - 1, -1, -1):
         dx, dy, sad = _refine_numpy(pc[l].astype(np.int32), pr[l].astype(np.int32), dx, dy, B, r, lam)
-    by, bx = dx.shape
-    x0, y0 = np.arange(bx) * B, np.arange(by) * B
-    w, h = np.minimum(B, W - x0), np.minimum(B, H - y0)
-    is_intra = sad > intra * (h[:, None] * w[None, :])
-    rec = np.zeros((by, bx, 8), dtype=np.int64)
-    rec[..., 0], rec[..., 1], rec[..., 2], rec[..., 3] = x0[None, :], y0[:, None], w[None, :], h[:, None]
-    rec[..., 4], rec[..., 5], rec[..., 6] = np.where(is_intra, 0, 4 * dx), np.where(is_intra, 0, 4 * dy), np.where(is_intra, BM_INTRA_REF, ref_index)
-    m = ~is_intra
-    stats = np.array([is_intra.sum(), (m & (dx == 0) & (dy == 0)).sum(), sad[m].sum(), (h[:, None] * w[None, :])[m].sum()], dtype=np.int64)
-    return np.ascontiguousarray(rec.reshape(-1, 8).astype(np.int16)), sad.reshape(-1).astype(np.uint32), stats
+    return _bm_outputs(dx, dy, sad, H, W, B, intra, ref_index)
 
 
 BMA_NSTATS = _lib.BMA_NSTATS          # ARSEG_BMA_NSTATS: anchored blocks, healed blocks, blocks kept on their hop, drift corrected in pixels
@@ -879,23 +890,7 @@ def block_motion_anchor_numpy(cur, key, records, merged_prev, f: int, B: int = 1
 
     centres = [(zero, zero, yes), (px, py, yes), (co[..., 0], co[..., 1], yes)]
     centres += [(neighbour(px, di, dj, 0), neighbour(py, di, dj, 0), neighbour(usable, di, dj, False)) for di, dj in ((0, -1), (0, 1), (-1, 0), (1, 0))]
-    ap = np.zeros((by * B, bx * B), dtype=np.int32)
-    ap[:H, :W] = a
-    Y, X = np.arange(by * B)[:, None], np.arange(bx * B)[None, :]
-    inside = (Y < H) & (X < W)
-    best = np.full((by, bx), (1 << 62), dtype=np.int64)
-    for cx, cy, ok in centres:
-        for oy in range(-r, r + 1):
-            for ox in range(-r, r + 1):
-                dx, dy = cx + ox, cy + oy
-                valid = ok & (x0[None, :] + dx >= 0) & (x0[None, :] + w[None, :] + dx <= W) & (y0[:, None] + dy >= 0) & (y0[:, None] + h[:, None] + dy <= H)
-                if not valid.any():
-                    continue
-                yy = np.clip(Y + np.repeat(np.repeat(dy, B, axis=0), B, axis=1), 0, H - 1)
-                xx = np.clip(X + np.repeat(np.repeat(dx, B, axis=0), B, axis=1), 0, W - 1)
-                sad = (np.abs(ap - k[yy, xx]) * inside).reshape(by, B, bx, B).sum(axis=(1, 3), dtype=np.int64)
-                cand = ((sad + lam * (np.abs(dx - px) + np.abs(dy - py))) << 28) | (((dy + 8192) << 14) | (dx + 8192))
-                best = np.where(valid & (cand < best), cand, best)
+    best = _bm_best_key(a, k, B, r, centres, lambda sad, dx, dy: ((sad + lam * (np.abs(dx - px) + np.abs(dy - py))) << 28) | (((dy + 8192) << 14) | (dx + 8192)))
     dy, dx = ((best >> 14) & 16383) - 8192, (best & 16383) - 8192
     drift = np.abs(dx - px) + np.abs(dy - py)
     sad = (best >> 28) - lam * drift

@@ -114,7 +114,7 @@ outputs = bmo.outputs
 
 # ---- cases ----
 SIZES = bmo.SIZES                                                      # 5 x 7: one clipped block, H_3 = 1; 37 x 53: odd at every level (37 -> 19 -> 10 -> 5)
-BLOCKS, LEVELS, REFINES, LAMS, INTRAS = (8, 16), (1, 2, 3), (1, 3), (0, 3), (0, 20, 255)
+BLOCKS, LEVELS, REFINES, LAMS, INTRAS = (8, 16), (1, 2, 3), (1, 2, 3), (0, 3), (0, 20, 255)
 KINDS = ("noise", "constant", "stripes")
 RT = 2                                                                 # the top level's radius in the grid of cases (the full search has its own tests)
 
