@@ -3,6 +3,8 @@
 Op level: every 16-bit kernel against fp64 torch arithmetic on the SAME 16-bit-rounded operands -- what remains is fp32
 accumulation order and the single output rounding (half an ulp: at most 2^-8 relative for bf16, 2^-11 for fp16).
 Model level: the reference-generated fixtures G6 / G7 (fp32) with the measured error and the label agreement stated per dtype."""
+import ctypes
+
 import numpy as np
 import pytest
 import torch
@@ -100,11 +102,17 @@ def test_conv2d16(dev, case, dtype):
             got = ops.conv2d(xn.to(dev), pc, residual=rd, tile_cfg=cfg)
             close16(got.permute(0, 3, 1, 2), y, dtype, extra=2e-5 * float(y.abs().max()))
         for cfg in (10, 11, 12, 13):          # (r6) the squarer pixel tiles; a map too narrow for one is refused, not mis-tiled
-            try:
-                got = ops.conv2d(xn.to(dev), pc, residual=rd, tile_cfg=cfg)
-            except _lib.ArsegError as exc:
-                assert "unsupported" in str(exc).lower() or "-2" in str(exc), exc
+            d, info = _lib.ConvDesc(), _lib.ConvPlanInfo()          # the descriptor of this launch: the device-free query says which it is
+            d.N, d.H, d.W, d.Cin, d.in_ld, d.Cout = N, H, W, cpad, cpad, Cout
+            d.out_ld = d.res_ld = (Cout + 7) // 8 * 8
+            d.R, d.S, d.stride, d.pad, d.dil, d.tile_cfg = k, k, stride, pad, dil, cfg
+            verdict = _lib.load().arseg_conv_plan_query(_lib.CONV_ENGINE_16, ctypes.byref(d), ctypes.byref(info))
+            if verdict != _lib.ARSEG_OK:
+                assert verdict == _lib.ARSEG_EUNSUPPORTED, (cfg, verdict)
+                with pytest.raises(_lib.ArsegError, match="(?i)unsupported|-2"):
+                    ops.conv2d(xn.to(dev), pc, residual=rd, tile_cfg=cfg)
                 continue
+            got = ops.conv2d(xn.to(dev), pc, residual=rd, tile_cfg=cfg)
             close16(got.permute(0, 3, 1, 2), y, dtype, extra=2e-5 * float(y.abs().max()))
     if Cout % 8 == 0 and k * k * Cin >= 256:        # split-K: fp32 partial sums + the epilogue in the reduce kernel; deterministic
         for cfg, sk in ((1, 2), (3, 3), (4, 8)):

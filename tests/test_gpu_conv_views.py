@@ -19,7 +19,6 @@ in 8|8, out 8|16, res 16|0 (multiples of 8 halves, which the library requires). 
 
 The cached-route tests at the end cover the host-side hole: the plan key of ``conv2d`` holds the shape, not the pitch / alignment of ``out``
 and ``residual``, so a plan cached from a dense call ("x3", "taps", tile_cfg 23, "gemm16") meets a later view it refuses."""
-import contextlib
 import functools
 
 import numpy as np
@@ -27,11 +26,10 @@ import pytest
 import torch
 import torch.nn.functional as F
 
-from helpers import maxdiff, t
+from helpers import SENTINEL, bits, boxed, maxdiff, neighbours_intact, pinned, t
 
 pytestmark = pytest.mark.gpu
 NAN = float("nan")
-SENTINEL = -7.0
 DTYPES = [torch.float16, torch.bfloat16]
 ULP = {torch.float16: 2.0 ** -10, torch.bfloat16: 2.0 ** -7}          # as tests/test_gpu_16bit.py
 TOL, TOL_TAPS = 2e-4, 5e-5                                            # tests/test_gpu_ops.py: test_conv2d / test_conv2d_winograd*, the tap route
@@ -73,39 +71,6 @@ def close16(got, want, dtype, extra=0.0):
     tol = ULP[dtype] * 0.51 * want.abs() + extra + 1e-6
     bad = (got - want).abs() > tol
     assert not bool(bad.any()), (float((got - want).abs().max()), int(bad.sum()))
-
-
-def boxed(t_, lead, trail, fill):
-    """(wide, view): ``wide`` [N,H,W,lead+C+trail] filled with ``fill``, ``view`` = wide[..., lead:lead+C] set to ``t_``."""
-    n, h, w, c = t_.shape
-    wide = torch.full((n, h, w, lead + c + trail), fill, dtype=t_.dtype, device=t_.device)
-    view = wide[..., lead:lead + c]
-    view.copy_(t_)
-    return wide, view
-
-
-def bits(wide):
-    return wide.view(torch.int32)
-
-
-def neighbours_intact(wide, lead, c):
-    return bool((wide[..., :lead] == SENTINEL).all()) and bool((wide[..., lead + c:] == SENTINEL).all())
-
-
-@contextlib.contextmanager
-def pinned(key, plan):
-    """``plan`` in the plan cache under ``key`` for the block; the entry found there (or its absence) is restored."""
-    from arseg_amd import ops
-
-    saved = ops._conv_plans.get(key)
-    ops._conv_plans[key] = plan
-    try:
-        yield
-    finally:
-        if saved is None:
-            ops._conv_plans.pop(key, None)
-        else:
-            ops._conv_plans[key] = saved
 
 
 def sweep(plans, x, res, oshape, view, refs=(), refuse=(), loose=()):
