@@ -117,15 +117,13 @@ __global__ __launch_bounds__(256) void block_motion_anchor_copy_kernel(const int
     for (int i = blockIdx.x * 256 + threadIdx.x; i < n; i += gridDim.x * 256) rec_out[i] = rec_in[i];
 }
 
-static bool bma_plane_ok(const void *plane, int64_t pitch, int W) { return !(reinterpret_cast<uintptr_t>(plane) & 3u) && !(pitch & 3) && pitch >= ((W + 3) & ~3); }
-
 extern "C" int arseg_block_motion_anchor_fwd(const uint8_t *cur, int64_t cur_pitch, const uint8_t *key, int64_t key_pitch, int H, int W, int B, int r, int lambda,
                                              int intra, int f, const int16_t *records_in, const int16_t *merged_prev, int16_t *records_out, uint32_t *sad,
                                              int64_t *stats, arseg_stream_t stream) {
     ARSEG_CHECK_PTR(cur); ARSEG_CHECK_PTR(key); ARSEG_CHECK_PTR(records_in); ARSEG_CHECK_PTR(records_out);
     if (!bm_args_ok(H, W, B, lambda, intra, records_out, sad, stats) || r < 1 || r > BMW_MAX_REFINE || f < 1 || f > BMA_MAX_F) return ARSEG_EINVAL;
     if (f >= 2 && merged_prev == nullptr) return ARSEG_EINVAL;
-    if (!bma_plane_ok(cur, cur_pitch, W) || !bma_plane_ok(key, key_pitch, W)) return ARSEG_EINVAL;
+    if (!bmw_plane_ok(cur, cur_pitch, W) || !bmw_plane_ok(key, key_pitch, W)) return ARSEG_EINVAL;
     if (!ARSEG_ALIGNED16(records_in) || (reinterpret_cast<uintptr_t>(merged_prev) & 3u)) return ARSEG_EINVAL;
     const AnchorArgs s = {H, W, arseg_cdiv(W, B), arseg_cdiv(H, B), arseg_cdiv(W, B) * arseg_cdiv(H, B), cur_pitch, key_pitch, lambda, intra, f};
     const uintptr_t in0 = reinterpret_cast<uintptr_t>(records_in), out0 = reinterpret_cast<uintptr_t>(records_out), bytes = (uintptr_t)16 * s.n_blocks;

@@ -113,6 +113,10 @@ static inline bool bm_args_ok(int H, int W, int B, int lambda, int intra, const 
     return ARSEG_ALIGNED16(records) && !(reinterpret_cast<uintptr_t>(sad) & 3u) && !(reinterpret_cast<uintptr_t>(stats) & 7u);
 }
 
+// a byte plane that bmw_stage and bmw_load_block read in dwords (the keyframe anchor, the chain healing): the base 4-byte aligned, the pitch a
+// multiple of 4 and at least (W + 3) & ~3
+static inline bool bmw_plane_ok(const void *plane, int64_t pitch, int W) { return !(reinterpret_cast<uintptr_t>(plane) & 3u) && !(pitch & 3) && pitch >= ((W + 3) & ~3); }
+
 // workgroups of BMW_WAVES blocks: two per compute unit fill the device, the rest of the blocks come with the grid's stride
 static inline int bmw_grid(int n_blocks) { return min(arseg_cdiv(n_blocks, BMW_WAVES), 2 * arseg_cu_count()); }
 

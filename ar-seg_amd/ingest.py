@@ -20,6 +20,8 @@
   arseg_luma_pyramid_*, arseg_block_motion_pyr_*; ``luma_pyramid_numpy`` and ``block_motion_pyr_numpy`` on the host).
   ``MotionEstimator(anchor_refine=...)`` checks every block's composed displacement against the keyframe and re-anchors it there
   (csrc/block_motion_anchor.hip; arseg_block_motion_anchor_fwd; ``block_motion_anchor_numpy`` on the host).
+* intra and uncovered pixels of any chain, whoever made its records: ``ChainHealer`` matches the flagged pixels of a pushed frame against the
+  keyframe and rewrites ``merged`` / ``link`` in place (csrc/mv_chain_heal.hip; arseg_mv_chain_heal_fwd; ``mv_chain_heal_numpy`` on the host).
 """
 from __future__ import annotations
 
@@ -391,12 +393,14 @@ def _round_half_even_div4(v):
     return b + ((r > 2) | ((r == 2) & (b & 1 == 1)))
 
 
-def chain_records_numpy(pushes, H: int, W: int, gop: int, max_ref: int = 3, bipred: str = "list0", return_link: bool = False):
+def chain_records_numpy(pushes, H: int, W: int, gop: int, max_ref: int = 3, bipred: str = "list0", return_link: bool = False, after_push=None):
     """The two-list chain rule of include/arseg_hip.h (arseg_mv_records_bi_*) on the host, for callers without a GPU at hand: ``pushes`` is a
     list of ``(f, records int16 [n,8])`` in decode order; returns ``merged`` int16 [gop,H,W,2] with frame 0 = -1 and frames never pushed = 0.
     What ``MotionChain(bidirectional=True, bipred=bipred)`` leaves in ``merged`` after the same pushes.  ``return_link=True``: returns
     ``(merged, link)`` with ``link`` uint8 [gop,H,W], the link bytes of include/arseg_hip.h (arseg_mv_records_bi_step_link_fwd) -- what
-    ``MotionChain(..., track_links=True)`` leaves in ``link``; frames never pushed = 0."""
+    ``MotionChain(..., track_links=True)`` leaves in ``link``; frames never pushed = 0.  ``after_push``: called as ``after_push(f, merged_f int16
+    [H,W,2], link_f uint8 [H,W])`` once frame f is composed; what it returns, ``(merged_f, link_f)``, replaces the frame in the chain's state
+    before the next push reads it (``mv_chain_heal_numpy`` after every push is ``ChainHealer.heal`` after every ``MotionChain.push``)."""
     H, W, gop, max_ref = int(H), int(W), int(gop), int(max_ref)
     if not (1 <= H <= 8192 and 1 <= W <= 8192) or not 2 <= gop <= 64 or not 1 <= max_ref <= 16 or bipred not in BIPRED:
         raise ValueError(f"chain_records_numpy: H, W in 1..8192, gop in 2..64, max_ref in 1..16, bipred in {BIPRED}; got {H}x{W}, gop {gop}, "
@@ -462,6 +466,8 @@ def chain_records_numpy(pushes, H: int, W: int, gop: int, max_ref: int = 3, bipr
             lk[both] = ((((byte[0] | byte[1]) & 7) | (np.maximum(byte[0] >> 4, byte[1] >> 4) << 4)))[both]
         merged[f] = out
         links[f] = lk
+        if after_push is not None:
+            merged[f], links[f] = after_push(f, merged[f].astype(np.int16), links[f].astype(np.uint8))
         done[f] = True
     assert merged.min() >= -32768 and merged.max() <= 32767
     return (merged.astype(np.int16), links.astype(np.uint8)) if return_link else merged.astype(np.int16)
@@ -517,6 +523,7 @@ class MotionChain(object):
         self.link_counts = torch.empty((gop, _lib.LINK_NSTATS), dtype=torch.int64, device=self.device) if self.track_links else None
         self.f = 0                      # in-order chain: the last frame pushed
         self.done_mask = 1              # bidirectional chain: bit g = frame g is chained
+        self.last = 0                   # either chain: the display index of the last frame pushed (0: none yet)
         self.reset()
 
     def reset(self) -> None:
@@ -527,7 +534,7 @@ class MotionChain(object):
             ops.mv_records_reset(self.merged, self.index_map)
         if self.track_links:
             ops.mv_link_reset(self.link_bytes, self.link_counts)
-        self.f, self.done_mask = 0, 1
+        self.f, self.done_mask, self.last = 0, 1, 0
 
     def _records(self, records) -> torch.Tensor:
         if not torch.is_tensor(records):                      # host records: uploaded here (allocates; a graph wants device buffers)
@@ -558,6 +565,7 @@ class MotionChain(object):
             else:
                 out = ops.mv_records_step(self._records(records), self.merged, self.f + 1, self.index_map, self.max_ref)
             self.f += 1
+            self.last = self.f
             return out
         if at is None:
             at = next((g for g in range(1, self.gop) if not (self.done_mask >> g) & 1), self.gop)
@@ -572,6 +580,7 @@ class MotionChain(object):
         else:
             out = ops.mv_records_bi_step(self._records(records), self.merged, at, self.done_mask, self.index_map, self.max_ref, self.bipred)
         self.done_mask |= 1 << at
+        self.last = at
         return out
 
     def push_gop(self, list_of_records, order=None) -> torch.Tensor:
@@ -904,6 +913,107 @@ def block_motion_anchor_numpy(cur, key, records, merged_prev, f: int, B: int = 1
     return np.ascontiguousarray(out.reshape(-1, 8).astype(np.int16)), np.where(anchored, sad, -1).reshape(-1).astype(np.int64), stats
 
 
+HEAL_NSTATS = _lib.HEAL_NSTATS        # ARSEG_HEAL_NSTATS: examined blocks, healed blocks, flagged pixels examined, pixels healed, flagged pixels skipped, drift
+
+
+def mv_chain_heal_numpy(cur, key, merged_f, link_f, B: int = 16, r: int = 2, lam: int = 2, intra: int = 20, flag_mask: int = LINK_INTRA | LINK_UNCOVERED,
+                        min_flagged: int = 1, link_stats_row=None):
+    """The chain healing of include/arseg_hip.h (arseg_mv_chain_heal_fwd) on the host: ``cur`` / ``key`` are uint8 luma planes [H,W] of frame f and
+    of the keyframe, ``merged_f`` int16 [H,W,2] and ``link_f`` uint8 [H,W] the chain's merged[f] and link[f] (not modified: copies are returned),
+    ``link_stats_row`` int64 [LINK_NSTATS] row f of the chain's counters or None.  Returns ``(merged_f, link_f, decisions int16 [by*bx,8],
+    sad int64 [by*bx] with -1 for a skipped block (the entries the device form leaves untouched), stats int64 [HEAL_NSTATS] from zero,
+    link_stats_row corrected or None)``.  numpy only: the examined blocks are gathered once, then one gather of the keyframe per centre and
+    offset over those blocks alone."""
+    a, k = luma8_numpy(cur).astype(np.int32), luma8_numpy(key).astype(np.int32)
+    B, r, lam, intra, flag_mask, min_flagged = int(B), int(r), int(lam), int(intra), int(flag_mask), int(min_flagged)
+    H, W = a.shape
+    if k.shape != a.shape:
+        raise ValueError(f"mv_chain_heal_numpy: the current frame is {a.shape}, the keyframe {k.shape}")
+    if not (1 <= H <= 8192 and 1 <= W <= 8192) or B not in (8, 16) or not 1 <= r <= 3 or not 0 <= lam <= 255 or not 0 <= intra <= 255 \
+            or not 1 <= flag_mask <= 7 or not 1 <= min_flagged <= 64:
+        raise ValueError(f"mv_chain_heal_numpy: H, W in 1..8192, B in (8, 16), r in 1..3, lam and intra in 0..255, flag_mask in 1..7, min_flagged in 1..64; "
+                         f"got {H}x{W}, B {B}, r {r}, lam {lam}, intra {intra}, flag_mask {flag_mask}, min_flagged {min_flagged}")
+    m, l = np.array(merged_f), np.array(link_f)
+    if m.dtype != np.int16 or m.shape != (H, W, 2) or l.dtype != np.uint8 or l.shape != (H, W):
+        raise ValueError(f"mv_chain_heal_numpy: merged_f is int16 [{H},{W},2] and link_f uint8 [{H},{W}], got {m.dtype} {m.shape} and {l.dtype} {l.shape}")
+    row = None
+    if link_stats_row is not None:
+        row = np.array(link_stats_row, dtype=np.int64)
+        if row.shape != (_lib.LINK_NSTATS,):
+            raise ValueError(f"mv_chain_heal_numpy: link_stats_row is int64 [{_lib.LINK_NSTATS}], got {row.shape}")
+    by, bx = -(-H // B), -(-W // B)
+    flagged = (l & flag_mask) != 0
+    fp = np.zeros((by * B, bx * B), dtype=bool)
+    fp[:H, :W] = flagged
+    n_all = fp.reshape(by, B, bx, B).sum(axis=(1, 3), dtype=np.int64)
+    gx0, gy0 = np.arange(bx) * B, np.arange(by) * B
+    gw, gh = np.minimum(B, W - gx0), np.minimum(B, H - gy0)
+    dec = np.zeros((by, bx, 8), dtype=np.int64)
+    dec[..., 0], dec[..., 1], dec[..., 2], dec[..., 3], dec[..., 6], dec[..., 7] = gx0[None, :], gy0[:, None], gw[None, :], gh[:, None], 2, n_all
+    sad = np.full((by, bx), -1, dtype=np.int64)
+    stats = np.zeros(HEAL_NSTATS, dtype=np.int64)
+    examined = n_all >= min_flagged
+    stats[4] = n_all[~examined].sum()
+    bi, bj = np.nonzero(examined)
+    if bi.size:
+        x0, y0, w, h, nf = gx0[bj], gy0[bi], gw[bj], gh[bi], n_all[bi, bj]
+        Y, X = y0[:, None, None] + np.arange(B)[None, :, None], x0[:, None, None] + np.arange(B)[None, None, :]
+        inside = (Y < H) & (X < W)
+        Yc, Xc = np.minimum(Y, H - 1), np.minimum(X, W - 1)
+        blk = a[Yc, Xc] * inside
+        fl = flagged[Yc, Xc] & inside
+        mq = m.astype(np.int64) >> 2
+        yes, zero = np.ones(bi.size, dtype=bool), np.zeros(bi.size, dtype=np.int64)
+        c1 = mq[y0 + h // 2, x0 + w // 2]
+        centres = [(zero, zero, yes), (c1[:, 0], c1[:, 1], yes)]
+        for di, dj in ((0, -1), (0, 1), (-1, 0), (1, 0)):
+            qi, qj = bi + di, bj + dj
+            ok = (qi >= 0) & (qi < by) & (qj >= 0) & (qj < bx)
+            qi, qj = np.clip(qi, 0, by - 1), np.clip(qj, 0, bx - 1)
+            yc, xc = gy0[qi] + gh[qi] // 2, gx0[qj] + gw[qj] // 2
+            c = mq[yc, xc]
+            centres.append((c[:, 0], c[:, 1], ok & ~flagged[yc, xc]))
+        un = (inside & ~fl).reshape(bi.size, B * B)
+        first = un.argmax(axis=1)                                        # raster order within the block
+        c = mq[np.minimum(y0 + first // B, H - 1), np.minimum(x0 + first % B, W - 1)]
+        centres.append((c[:, 0], c[:, 1], un.any(axis=1)))
+        for j in range(len(centres)):                                  # the union is a set: a centre equal to an earlier one proposes nothing new
+            for cx, cy, ok in centres[:j]:
+                centres[j] = (centres[j][0], centres[j][1], centres[j][2] & ~(ok & (cx == centres[j][0]) & (cy == centres[j][1])))
+        best = np.full(bi.size, 1 << 62, dtype=np.int64)
+        for cx, cy, ok in centres:
+            for oy in range(-r, r + 1):
+                for ox in range(-r, r + 1):
+                    dx, dy = cx + ox, cy + oy
+                    valid = ok & (x0 + dx >= 0) & (x0 + w + dx <= W) & (y0 + dy >= 0) & (y0 + h + dy <= H)
+                    if not valid.any():
+                        continue
+                    ref = k[np.clip(Y + dy[:, None, None], 0, H - 1), np.clip(X + dx[:, None, None], 0, W - 1)]
+                    s_all = (np.abs(blk - ref) * inside).sum(axis=(1, 2), dtype=np.int64)
+                    kq = ((s_all + lam * (np.abs(dx - c1[:, 0]) + np.abs(dy - c1[:, 1]))) << 28) | (((dy + 8192) << 14) | (dx + 8192))
+                    best = np.where(valid & (kq < best), kq, best)
+        dy, dx = ((best >> 14) & 16383) - 8192, (best & 16383) - 8192
+        drift = np.abs(dx - c1[:, 0]) + np.abs(dy - c1[:, 1])
+        ref = k[np.clip(Y + dy[:, None, None], 0, H - 1), np.clip(X + dx[:, None, None], 0, W - 1)]
+        s_fl = (np.abs(blk - ref) * fl).sum(axis=(1, 2), dtype=np.int64)
+        healed = s_fl <= intra * nf
+        dec[bi, bj, 4], dec[bi, bj, 5], dec[bi, bj, 6] = 4 * dx, 4 * dy, np.where(healed, 0, 1)
+        sad[bi, bj] = s_fl
+        stats[:4] = bi.size, healed.sum(), nf.sum(), nf[healed].sum()
+        stats[5] = drift[healed].sum()
+        pix = fl & healed[:, None, None]
+        ys, xs = np.broadcast_to(Y, pix.shape)[pix], np.broadcast_to(X, pix.shape)[pix]
+        if row is not None and ys.size:
+            old = l[ys, xs].astype(np.int64)
+            row[:4] -= np.array([(old & 1).sum(), ((old >> 1) & 1).sum(), ((old >> 2) & 1).sum(), ((old & 7) != 0).sum()])
+            row[4:] -= np.bincount(old >> 4, minlength=16)
+            row[4 + 1] += ys.size
+        m[ys, xs, 0] = np.broadcast_to((4 * dx)[:, None, None], pix.shape)[pix]
+        m[ys, xs, 1] = np.broadcast_to((4 * dy)[:, None, None], pix.shape)[pix]
+        l[ys, xs] = 0x10
+    return m, l, np.ascontiguousarray(dec.reshape(-1, 8).astype(np.int16)), sad.reshape(-1), stats, row
+
+
 class LumaPyramid(object):
     """The luma8 pyramid of one frame on the GPU (include/arseg_hip.h, arseg_luma_pyramid_fwd; csrc/block_motion_pyr.hip): one uint8 buffer,
     allocated once.  ``build(frame)`` fills it from a one-frame ``DecodedFrames`` -- one launch, no synchronisation, no allocation -- and
@@ -931,6 +1041,26 @@ class LumaPyramid(object):
     def level(self, l: int) -> torch.Tensor:
         off, pitch, H, W = self.layout[l]
         return self.buffer[off:off + pitch * H].view(H, pitch)[:, :W]
+
+
+def _luma_in_place(owner: str, who: str, what: str, frame, H: int, W: int, device) -> torch.Tensor:
+    """The uint8 luma plane [H,W] that the keyframe anchor and the chain healing read in place: level 0 of a built ``LumaPyramid`` of this size,
+    or the luma plane of a one-frame NV12 / I420 ``DecodedFrames`` if it meets their alignment rule.  ``MotionEstimator`` and ``ChainHealer``
+    both take their frames through here."""
+    if isinstance(frame, LumaPyramid):
+        if (frame.H, frame.W, frame.device) != (H, W, device):
+            raise _lib.ArsegError(f"{owner}.{who}: {what} must be a LumaPyramid of {H}x{W} on {device}")
+        return frame.level(0)
+    if not isinstance(frame, DecodedFrames) or frame.N != 1 or (frame.H, frame.W) != (H, W):
+        raise _lib.ArsegError(f"{owner}.{who}: expected one DecodedFrames frame of {H}x{W} or a built LumaPyramid")
+    plane, src_format = frame.luma_plane()
+    p = plane[0]
+    if src_format not in (_lib.SRC_NV12, _lib.SRC_I420) or p.device != device or p.stride(1) != 1 or p.data_ptr() % 4 \
+            or (H > 1 and (p.stride(0) % 4 or p.stride(0) < ((W + 3) & ~3))):
+        raise _lib.ArsegError(f"{owner}.{who}: with levels=0 the anchor reads the frame's own luma plane, which must be an NV12 / I420 byte "
+                              f"plane on {device} with a 4-byte aligned base and a pitch that is a multiple of 4; any other frame needs levels >= 1 "
+                              f"(level 0 of the luma pyramid is such a plane)")
+    return p
 
 
 class MotionEstimator(object):
@@ -1034,16 +1164,9 @@ class MotionEstimator(object):
 
     def _aligned_luma(self, frame, who):
         """The uint8 luma plane [H,W] of a one-frame NV12 / I420 ``DecodedFrames`` if it meets the anchor's alignment rule."""
-        if not isinstance(frame, DecodedFrames) or frame.N != 1 or (frame.H, frame.W) != (self.H, self.W):
+        if isinstance(frame, LumaPyramid):                            # with levels=0 a pyramid is a keyframe only
             raise _lib.ArsegError(f"MotionEstimator.{who}: expected one DecodedFrames frame of {self.H}x{self.W} or a built LumaPyramid")
-        plane, src_format = frame.luma_plane()
-        p = plane[0]
-        if src_format not in (_lib.SRC_NV12, _lib.SRC_I420) or p.device != self.device or p.stride(1) != 1 or p.data_ptr() % 4 \
-                or (self.H > 1 and (p.stride(0) % 4 or p.stride(0) < ((self.W + 3) & ~3))):
-            raise _lib.ArsegError(f"MotionEstimator.{who}: with levels=0 the anchor reads the frame's own luma plane, which must be an NV12 / I420 byte "
-                                  f"plane on {self.device} with a 4-byte aligned base and a pitch that is a multiple of 4; any other frame needs levels >= 1 "
-                                  f"(level 0 of the luma pyramid is such a plane)")
-        return p
+        return _luma_in_place("MotionEstimator", who, "the frame", frame, self.H, self.W, self.device)
 
     def set_key(self, frame) -> None:
         """The keyframe of the GOP that ``estimate_anchored`` anchors on: a one-frame ``DecodedFrames`` (with ``levels`` >= 1 built into a third
@@ -1051,16 +1174,12 @@ class MotionEstimator(object):
         built ``LumaPyramid`` of this size, whose level 0 is read in place.  No synchronisation, no allocation."""
         if not self.anchor_refine:
             raise _lib.ArsegError("MotionEstimator.set_key: this estimator was made with anchor_refine=0")
-        if isinstance(frame, LumaPyramid):
-            if (frame.H, frame.W, frame.device) != (self.H, self.W, self.device):
-                raise _lib.ArsegError(f"MotionEstimator.set_key: the keyframe must be a LumaPyramid of {self.H}x{self.W} on {self.device}")
-            self._key_plane = frame.level(0)
-        elif self.levels:
+        if isinstance(frame, LumaPyramid) or not self.levels:
+            self._key_plane = _luma_in_place("MotionEstimator", "set_key", "the keyframe", frame, self.H, self.W, self.device)
+        else:
             if not isinstance(frame, DecodedFrames) or frame.N != 1 or (frame.H, frame.W) != (self.H, self.W):
                 raise _lib.ArsegError(f"MotionEstimator.set_key: expected one DecodedFrames frame of {self.H}x{self.W} or a built LumaPyramid")
             self._key_plane = self._key_pyramid.build(frame).level(0)
-        else:
-            self._key_plane = self._aligned_luma(frame, "set_key")
 
     def estimate_anchored(self, cur, ref, chain) -> torch.Tensor:
         """``estimate(cur, ref)``, then one anchor launch for frame f = ``chain.f`` + 1 against the keyframe of ``set_key`` with ``chain.merged[f - 1]``
@@ -1103,3 +1222,76 @@ class MotionEstimator(object):
         """int64 [BM_NSTATS], accumulated since ``reset_stats``: intra blocks, matched blocks with the zero vector, the sum of SAD and the
         number of pixels of the matched blocks.  A device tensor: reading it on the host synchronises."""
         return self.stats
+
+
+class ChainHealer(object):
+    """Heals the intra / uncovered pixels of ANY ``MotionChain(track_links=True)`` on the keyframe (csrc/mv_chain_heal.hip;
+    arseg_mv_chain_heal_fwd; host form ``mv_chain_heal_numpy``).  A pixel flagged at one hop stays flagged, on zero motion, for the rest of the
+    GOP although its content is usually back one frame later; ``MotionEstimator(anchor_refine=...)`` mends that for its own records only.  This
+    works on the chain's output, so it takes a software decoder's records of any geometry, bidirectional chains in decode order and any GOP
+    length:
+
+        healer, chain = ChainHealer(H, W), MotionChain(H, W, gop=20, bidirectional=True, track_links=True)
+        for each GOP:   chain.reset();  healer.set_key(key_frame)
+                        for f, records in decode_order:  chain.push(records, at=f);  mv_q = healer.heal(chain, frame_f)
+
+    Every ``block`` x ``block`` tile (8 or 16) with at least ``min_flagged`` pixels whose link byte has a bit of ``flags`` is searched in the
+    keyframe within +-``refine`` (1 .. 3) of the chain's own vector at its centre, of its unflagged neighbours and of its own unflagged part;
+    where the winner's SAD over the flagged pixels is at most ``intra`` per flagged pixel they get a one-hop vector to the keyframe and a
+    clean link byte, in place in ``chain.merged`` / ``chain.link_bytes``, and the frame's row of ``chain.link_counts`` is corrected, so every
+    later frame composing through them inherits the healed value and a ``LinkMonitor`` sees the healed counts.  Owns ``decisions`` int16
+    [blocks, 8] (x0, y0, w, h, 4 dx, 4 dy, state, flagged pixels; state 0 healed, 1 kept, 2 skipped), ``heal_stats`` int64 [HEAL_NSTATS] and,
+    ``with_sad=True``, ``sad``: ``heal`` is two launches that neither synchronise nor allocate, so ``chain.push(records); healer.heal(chain, cur)``
+    over static buffers can be captured in a HIP graph."""
+
+    def __init__(self, H: int, W: int, block: int = 16, refine: int = 2, lam: int = 2, intra: int = 20, flags: int = LINK_INTRA | LINK_UNCOVERED,
+                 min_flagged: int = 1, device="cuda", with_sad: bool = False):
+        self.H, self.W, self.block, self.refine = int(H), int(W), int(block), int(refine)
+        self.lam, self.intra, self.flags, self.min_flagged = int(lam), int(intra), int(flags), int(min_flagged)
+        if not (1 <= self.H <= 8192 and 1 <= self.W <= 8192) or self.block not in (8, 16) or not 1 <= self.refine <= 3 or not 0 <= self.lam <= 255 \
+                or not 0 <= self.intra <= 255 or not 1 <= self.flags <= 7 or not 1 <= self.min_flagged <= 64:
+            raise _lib.ArsegError(f"ChainHealer: H, W in 1..8192, block in (8, 16), refine in 1..3, lam and intra in 0..255, flags in 1..7, min_flagged in "
+                                  f"1..64; got {self.H}x{self.W}, block {self.block}, refine {self.refine}, lam {self.lam}, intra {self.intra}, flags "
+                                  f"{self.flags}, min_flagged {self.min_flagged}")
+        self.device = torch.device(device)
+        if self.device.type != "cuda":
+            raise _lib.ArsegError("ChainHealer runs on the GPU only; there is no CPU fallback (mv_chain_heal_numpy is the host form)")
+        self.n_blocks = -(-self.H // self.block) * -(-self.W // self.block)
+        self.decisions = torch.zeros((self.n_blocks, 8), dtype=torch.int16, device=self.device)
+        self.heal_stats = torch.zeros(HEAL_NSTATS, dtype=torch.int64, device=self.device)
+        self.sad = torch.zeros(self.n_blocks, dtype=torch.int32, device=self.device) if with_sad else None
+        self._key_plane = None
+
+    def set_key(self, frame) -> None:
+        """The keyframe of the GOP: what ``MotionEstimator.set_key`` takes with ``levels=0`` -- a one-frame NV12 / I420 ``DecodedFrames`` whose luma
+        plane is 4-byte aligned, or a built ``LumaPyramid`` of this size -- read in place.  No launch, no synchronisation, no allocation."""
+        self._key_plane = _luma_in_place("ChainHealer", "set_key", "the keyframe", frame, self.H, self.W, self.device)
+
+    def heal(self, chain, cur, at=None) -> torch.Tensor:
+        """Heals frame ``at`` of ``chain`` (None: the last one pushed) against the keyframe of ``set_key``; ``cur`` is that frame, as ``set_key``
+        takes the keyframe.  Works in place on ``chain.merged[at]``, ``chain.link_bytes[at]`` and ``chain.link_counts[at]`` and returns the
+        ``mv_q`` view ``chain.merged[at]``.  Raises for a chain without ``track_links``, a frame not pushed, a size or device mismatch and
+        before ``set_key``.  Neither synchronises nor allocates."""
+        if self._key_plane is None:
+            raise _lib.ArsegError("ChainHealer.heal: set_key(frame) first, once per GOP")
+        if not isinstance(chain, MotionChain) or not chain.track_links:
+            raise _lib.ArsegError("ChainHealer.heal: healing needs a MotionChain(track_links=True): the link bytes say which pixels to heal")
+        if (chain.H, chain.W, chain.device) != (self.H, self.W, self.device):
+            raise _lib.ArsegError(f"ChainHealer.heal: the chain is {chain.H}x{chain.W} on {chain.device}, the healer {self.H}x{self.W} on {self.device}")
+        at = chain.last if at is None else int(at)
+        if not 1 <= at < chain.gop or at not in chain.frames_done():
+            raise _lib.ArsegError(f"ChainHealer.heal: frame {at} was not pushed in this GOP (pushed: {chain.frames_done()[1:]})")
+        cur_plane = _luma_in_place("ChainHealer", "heal", "the current frame", cur, self.H, self.W, self.device)
+        ops.mv_chain_heal(cur_plane, self._key_plane, chain.merged[at], chain.link_bytes[at], self.block, self.refine, self.lam, self.intra, self.flags,
+                          self.min_flagged, decisions=self.decisions, sad=self.sad if self.sad is not None else False, stats=self.heal_stats,
+                          link_stats_row=chain.link_counts[at])
+        return chain.merged[at]
+
+    def reset_stats(self) -> None:
+        self.heal_stats.zero_()
+
+    def heal_stats_row(self) -> torch.Tensor:
+        """int64 [HEAL_NSTATS], accumulated since ``reset_stats``: examined blocks, healed blocks, flagged pixels in examined blocks, pixels
+        healed, flagged pixels in skipped blocks, and the sum over healed blocks of |winner - the chain's own vector| in pixels.  A device
+        tensor: reading it on the host synchronises."""
+        return self.heal_stats

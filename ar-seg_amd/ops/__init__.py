@@ -29,7 +29,7 @@ from .egress import contours_fill, contours_simplify, contours_simplify_shared, 
 from .layers import (_frame_ingest_planes, adaptive_avgpool, argmax_confusion, argmax_confusion_grouped, as_nchw, band_radii, block_motion, block_motion_anchor, block_motion_pyr, boundary_iou, boundary_radii, boundary_radius, calibration, cast, contour_f, contour_radii, contour_radius, frame_ingest, frame_ingest8, frame_ingest_yuv, frame_to_nhwc4, frame_u8_to_nhwc4, from_c8, global_reduce, head, ingest_input,
                      is_nhwc_view, label_bands, local_similar, luma_pyramid, local_weighting, maxpool3x3s2, merge_motion, MV_BI_POLICIES, mv_link_reset, mv_records_bi_reset, mv_records_bi_step, mv_records_bi_step_link, mv_records_rasterize, mv_records_reset, mv_records_step,
                      mv_records_step_link, psp_pool_matrix, psp_prior_sum, resize_nchw, resize_nhwc,
-                     scale_add, to_c8, to_nchw_contiguous, to_nhwc)
+                     mv_chain_heal, scale_add, to_c8, to_nchw_contiguous, to_nhwc)
 
 _LEGACY_SWITCHES = {"_AUTOTUNE": "AUTOTUNE", "_math": "math", "_RANGE_MODE": "RANGE_MODE", "_RANGE_GUARD": "RANGE_GUARD", "_WINOGRAD": "WINOGRAD",
                     "_UP2_TAPS": "UP2_TAPS", "_GEMM_X3": "GEMM_X3", "_IGEMM3": "IGEMM3", "_PLAN_FILE": "PLAN_FILE"}

@@ -675,6 +675,23 @@ def block_motion_pyr(cur_pyr: torch.Tensor, ref_pyr: torch.Tensor, H: int, W: in
     return records, sad, stats
 
 
+def _aligned_luma_pair(who: str, cur_plane, key_plane):
+    """The current frame's and the keyframe's uint8 luma planes as the keyframe anchor and the chain healing read them: one size in 1..8192, one
+    device, the base 4-byte aligned and the pitch a multiple of 4 of at least (W + 3) & ~3.  Returns (H, W, device, cur_pitch, key_pitch)."""
+    H, W, cur_pitch = _luma_plane(cur_plane, _lib.SRC_NV12, f"{who} (current frame)")
+    H2, W2, key_pitch = _luma_plane(key_plane, _lib.SRC_NV12, f"{who} (keyframe)")
+    dev = cur_plane.device
+    if (H2, W2) != (H, W) or key_plane.device != dev:
+        raise _lib.ArsegError(f"{who}: the current frame is {H}x{W} on {dev}, the keyframe {H2}x{W2} on {key_plane.device}")
+    if not (1 <= H <= 8192 and 1 <= W <= 8192):
+        raise _lib.ArsegError(f"{who}: H, W in 1..8192; got {H}x{W}")
+    for what, t, pitch in (("current frame", cur_plane, cur_pitch), ("keyframe", key_plane, key_pitch)):
+        if t.data_ptr() % 4 or pitch % 4 or pitch < ((W + 3) & ~3):
+            raise _lib.ArsegError(f"{who} ({what}): the plane's base must be 4-byte aligned and its pitch a multiple of 4 of at least "
+                                  f"{(W + 3) & ~3} bytes, got an offset of {t.data_ptr() % 4} and a pitch of {pitch} (level 0 of a LumaPyramid qualifies)")
+    return H, W, dev, cur_pitch, key_pitch
+
+
 def block_motion_anchor(cur_plane: torch.Tensor, key_plane: torch.Tensor, records: torch.Tensor, merged_prev: Optional[torch.Tensor], f: int, B: int = 16,
                         r: int = 2, lam: int = 2, intra: int = 255, out: Optional[torch.Tensor] = None, sad=None, stats=None):
     """Anchors the estimated hop records of frame ``f`` on the keyframe (include/arseg_hip.h, arseg_block_motion_anchor_fwd): every block of
@@ -685,19 +702,11 @@ def block_motion_anchor(cur_plane: torch.Tensor, key_plane: torch.Tensor, record
     ``out`` / ``sad`` / ``stats`` with ``block_motion``'s conventions, except that sad is read-modify-write (entries of anchored blocks
     only; allocated zeroed) and stats is int64 [BMA_NSTATS].  ``out`` must not overlap ``records``.  One launch, no synchronisation; with
     all three buffers passed in, no allocation.  Returns (out, sad, stats)."""
-    H, W, cur_pitch = _luma_plane(cur_plane, _lib.SRC_NV12, "block_motion_anchor (current frame)")
-    H2, W2, key_pitch = _luma_plane(key_plane, _lib.SRC_NV12, "block_motion_anchor (keyframe)")
+    H, W, dev, cur_pitch, key_pitch = _aligned_luma_pair("block_motion_anchor", cur_plane, key_plane)
     f, B, r, lam, intra = int(f), int(B), int(r), int(lam), int(intra)
-    dev = cur_plane.device
-    if (H2, W2) != (H, W) or key_plane.device != dev:
-        raise _lib.ArsegError(f"block_motion_anchor: the current frame is {H}x{W} on {dev}, the keyframe {H2}x{W2} on {key_plane.device}")
-    if not (1 <= H <= 8192 and 1 <= W <= 8192) or B not in (8, 16) or not 1 <= r <= 3 or not 0 <= lam <= 255 or not 0 <= intra <= 255 or not 1 <= f <= 16:
+    if B not in (8, 16) or not 1 <= r <= 3 or not 0 <= lam <= 255 or not 0 <= intra <= 255 or not 1 <= f <= 16:
         raise _lib.ArsegError(f"block_motion_anchor: H, W in 1..8192, B in (8, 16), r in 1..3, lam and intra in 0..255, f in 1..16; got {H}x{W}, B {B}, "
                               f"r {r}, lam {lam}, intra {intra}, f {f}")
-    for what, t, pitch in (("current frame", cur_plane, cur_pitch), ("keyframe", key_plane, key_pitch)):
-        if t.data_ptr() % 4 or pitch % 4 or pitch < ((W + 3) & ~3):
-            raise _lib.ArsegError(f"block_motion_anchor ({what}): the plane's base must be 4-byte aligned and its pitch a multiple of 4 of at least "
-                                  f"{(W + 3) & ~3} bytes, got an offset of {t.data_ptr() % 4} and a pitch of {pitch} (level 0 of a LumaPyramid qualifies)")
     n = -(-H // B) * -(-W // B)
     if _mv_records(records, "block_motion_anchor") != n or records.device != dev:
         raise _lib.ArsegError(f"block_motion_anchor: {H}x{W} in blocks of {B} is {n} records on {dev}, got {tuple(records.shape)} on {records.device}")
@@ -716,6 +725,48 @@ def block_motion_anchor(cur_plane: torch.Tensor, key_plane: torch.Tensor, record
     launch("block_motion_anchor", _lib.load().arseg_block_motion_anchor_fwd, _ptr(cur_plane), cur_pitch, _ptr(key_plane), key_pitch, H, W, B, r, lam, intra, f,
            _ptr(records), _ptr(merged_prev), _ptr(out), _ptr(sad), _ptr(stats), _stream())
     return out, sad, stats
+
+
+def mv_chain_heal(cur_plane: torch.Tensor, key_plane: torch.Tensor, merged_f: torch.Tensor, link_f: torch.Tensor, B: int = 16, r: int = 2, lam: int = 2,
+                  intra: int = 20, flag_mask: int = _lib.LINK_INTRA | _lib.LINK_UNCOVERED, min_flagged: int = 1, decisions: Optional[torch.Tensor] = None,
+                  sad=None, stats=None, link_stats_row=None):
+    """Heals the flagged pixels of one frame of a motion chain on the keyframe (include/arseg_hip.h, arseg_mv_chain_heal_fwd), IN PLACE:
+    ``merged_f`` int16 [H,W,2] and ``link_f`` uint8 [H,W] are merged[f] and link[f] as the chain's step left them.  Every B x B block with at
+    least ``min_flagged`` pixels whose link byte has a bit of ``flag_mask`` is matched in ``key_plane`` within +-r of the chain's own vector at
+    its centre, of its neighbours' where those are unflagged, of its own first unflagged pixel and of (0, 0); where the winner's SAD over the
+    flagged pixels is at most ``intra`` per flagged pixel they get (4 dx, 4 dy) and the link byte 0x10.  The planes are as
+    ``block_motion_anchor`` takes them.  ``decisions`` (int16 [n,8]: x0, y0, w, h, 4 dx, 4 dy, state, flagged pixels; state 0 healed, 1 kept,
+    2 skipped) / ``sad`` (uint32 per block, examined blocks only; allocated zeroed) / ``stats`` (int64 [HEAL_NSTATS], accumulated into) with
+    ``block_motion``'s conventions; ``link_stats_row`` (int64 [LINK_NSTATS], row f of the chain's counters, corrected to a recount of the new
+    plane) is left out when None or False.  Two launches, no synchronisation; with the buffers passed in, no allocation.  Returns
+    (decisions, sad, stats)."""
+    H, W, dev, cur_pitch, key_pitch = _aligned_luma_pair("mv_chain_heal", cur_plane, key_plane)
+    B, r, lam, intra, flag_mask, min_flagged = int(B), int(r), int(lam), int(intra), int(flag_mask), int(min_flagged)
+    if B not in (8, 16) or not 1 <= r <= 3 or not 0 <= lam <= 255 or not 0 <= intra <= 255 or not 1 <= flag_mask <= 7 or not 1 <= min_flagged <= 64:
+        raise _lib.ArsegError(f"mv_chain_heal: B in (8, 16), r in 1..3, lam and intra in 0..255, flag_mask in 1..7, min_flagged in 1..64; got B {B}, "
+                              f"r {r}, lam {lam}, intra {intra}, flag_mask {flag_mask}, min_flagged {min_flagged}")
+    if not torch.is_tensor(merged_f) or merged_f.dtype != torch.int16 or merged_f.device != dev or tuple(merged_f.shape) != (H, W, 2) or not merged_f.is_contiguous() \
+            or merged_f.data_ptr() % 4:
+        raise _lib.ArsegError(f"mv_chain_heal expects merged_f as a contiguous, 4-byte aligned int16 tensor [{H},{W},2] on {dev}")
+    if not torch.is_tensor(link_f) or link_f.dtype != torch.uint8 or link_f.device != dev or tuple(link_f.shape) != (H, W) or not link_f.is_contiguous():
+        raise _lib.ArsegError(f"mv_chain_heal expects link_f as a contiguous uint8 tensor [{H},{W}] on {dev}")
+    n = -(-H // B) * -(-W // B)
+    if sad is None:
+        sad = torch.zeros(n, dtype=torch.int32, device=dev)
+    decisions, sad, _ = _bm_outputs("mv_chain_heal", H, W, B, dev, decisions, sad, False)
+    for name, t, size in (("stats", stats, _lib.HEAL_NSTATS), ("link_stats_row", link_stats_row, _lib.LINK_NSTATS)):
+        if t is not None and t is not False and (not torch.is_tensor(t) or t.dtype != torch.int64 or t.device != dev or t.numel() != size or not t.is_contiguous()
+                                                 or t.data_ptr() % 8):
+            raise _lib.ArsegError(f"mv_chain_heal expects {name} as a contiguous int64 tensor of {size} elements on {dev}")
+    if stats is None:
+        stats = torch.zeros(_lib.HEAL_NSTATS, dtype=torch.int64, device=dev)
+    elif stats is False:
+        stats = None
+    if link_stats_row is False:
+        link_stats_row = None
+    launch("mv_chain_heal", _lib.load().arseg_mv_chain_heal_fwd, _ptr(cur_plane), cur_pitch, _ptr(key_plane), key_pitch, H, W, B, r, lam, intra, flag_mask,
+           min_flagged, _ptr(merged_f), _ptr(link_f), _ptr(decisions), _ptr(sad), _ptr(stats), _ptr(link_stats_row), _stream())
+    return decisions, sad, stats
 
 
 def argmax_confusion(logits: torch.Tensor, label: Optional[torch.Tensor], H: int, W: int, hist: Optional[torch.Tensor] = None,

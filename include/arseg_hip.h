@@ -820,12 +820,72 @@ int arseg_block_motion_pyr_fwd(const uint8_t *cur_pyr, const uint8_t *ref_pyr, i
  * that is no multiple of 4 or below (W + 3) & ~3; records not 16-byte aligned, merged_prev or sad not 4-byte aligned, stats not 8-byte
  * aligned; overlapping record buffers.
  * Not covered: bidirectional chains, anchoring decoder records of arbitrary geometry, anchoring on a frame other than 0, choosing by cost
- * between hop and anchor (an anchor that passes the intra bound always wins), GOPs above 17 frames.
+ * between hop and anchor (an anchor that passes the intra bound always wins), GOPs above 17 frames.  (The FLAGGED pixels of any chain --
+ * bidirectional, decoder records of any geometry, any GOP length -- are healed by arseg_mv_chain_heal_fwd below.)
  * ------------------------------------------------------------------------------------------- */
 #define ARSEG_BMA_NSTATS 4
 int arseg_block_motion_anchor_fwd(const uint8_t *cur, int64_t cur_pitch, const uint8_t *key, int64_t key_pitch, int H, int W, int B, int r, int lambda,
                                   int intra, int f, const int16_t *records_in, const int16_t *merged_prev, int16_t *records_out, uint32_t *sad,
                                   int64_t *stats, arseg_stream_t stream);
+
+/* ---------------------------------------------------------------------------------------------
+ * Healing the flagged pixels of a motion chain on the keyframe (csrc/mv_chain_heal.hip).  A pixel that was intra or uncovered at one hop
+ * stays flagged for the rest of the GOP and carries the substituted zero motion, although its content is usually visible again one frame
+ * later and in the keyframe.  The anchor above mends that for the estimator's own records, before they are pushed.  This entry works on the
+ * chain's OUTPUT instead: after the step entry of frame f, merged[f] and link[f] are dense planes whoever made the records, however they
+ * were shaped and whichever step entry (P or bi) composed them.  The blocks of a fixed grid that hold flagged pixels are matched against
+ * the keyframe, and where the flagged pixels match they get a direct one-hop vector to frame 0 and a clean link byte.  The chain's state
+ * IS merged / link, so every later frame that composes through a healed pixel inherits the healed value.
+ *   cur, key    luma8 byte planes [H][W] of frame f and of the keyframe; alignment and pitch exactly as arseg_block_motion_anchor_fwd: the
+ *               base 4-byte aligned, the pitch a multiple of 4 and at least (W + 3) & ~3; the bytes of a row beyond W never count.
+ *               H, W in 1 .. 8192
+ *   merged_f    int16 [H][W][2], 4-byte aligned, IN PLACE: merged[f] as the step entry left it
+ *   link_f      uint8 [H][W], IN PLACE: link[f] as the step entry left it
+ *   blocks      B in {8, 16}: the grid of arseg_block_motion_fwd; block b = bi bx + bj, x0 = bj B, y0 = bi B, w = min(B, W - x0),
+ *               h = min(B, H - y0)
+ *   flagged     a pixel is FLAGGED iff (link_f[y][x] & flag_mask) != 0; flag_mask in 1 .. 7: which of ARSEG_LINK_INTRA / _UNCOVERED /
+ *               _CLAMPED count.  n(b) = the number of flagged pixels of block b
+ *   skipped     n(b) < min_flagged, min_flagged in 1 .. 64: nothing of the block is read further or written
+ *   centres     of an examined block, in this order, with (xc, yc) = (x0 + w / 2, y0 + h / 2) by integer division and >> 2 an arithmetic
+ *               shift: C0 = (0, 0); C1 = merged_f[yc][xc] >> 2, the chain's own answer, whether or not that pixel is flagged; C2 .. C5 =
+ *               merged_f >> 2 at the centre pixel of the left, right, upper and lower neighbour block, each where the neighbour is in the
+ *               grid AND that pixel is not flagged; C6 = merged_f >> 2 at the first unflagged pixel of the block itself in raster order, if
+ *               there is one (the motion of the part of a split block the encoder did predict)
+ *   candidates  the union (a vector proposed twice counts once) of centre + (ox, oy), |ox| <= r and |oy| <= r, r in 1 .. 3, whose displaced
+ *               block lies inside the keyframe: 0 <= x0 + dx, x0 + w + dx <= W, 0 <= y0 + dy, y0 + h + dy <= H.  Nothing is padded or
+ *               clamped.  (0, 0) always is one
+ *   cost        SAD_all + lambda (|dx - C1x| + |dy - C1y|), SAD_all over all w h pixels of the block; lambda in 0 .. 255
+ *   winner      the smallest cost; among equals the smallest dy, then the smallest dx (the anchor's 64-bit key,
+ *               cost << 28 | (dy + 8192) << 14 | (dx + 8192))
+ *   acceptance  SAD_flagged(winner) <= intra n(b), intra in 0 .. 255: SAD_flagged is the same sum restricted to the flagged pixels.  A
+ *               cleared flag is a claim about those pixels only; it must not be bought by the unflagged rest of the block matching well.
+ *               Where a whole block is flagged the two sums coincide
+ *   result      every flagged pixel of an accepted (HEALED) block: merged_f[y][x] = (4 dx, 4 dy), link_f[y][x] = 0x10 (one hop, no
+ *               flags).  Unflagged pixels and all pixels of other blocks keep every bit
+ *   decisions   int16 [by * bx][8], 16-byte aligned, required: the hand-over between the two launches, and an output:
+ *               (x0, y0, w, h, 4 dx, 4 dy, state, n(b)), state 0 healed, 1 examined and kept, 2 skipped; the vector is the winner for
+ *               states 0 and 1 and zero for state 2
+ *   sad         uint32 [by * bx], may be NULL: SAD_flagged(winner) of examined blocks; the entries of skipped blocks are untouched
+ *   stats       int64 [ARSEG_HEAL_NSTATS], 8-byte aligned, may be NULL; ACCUMULATED INTO: [0] examined blocks, [1] healed blocks,
+ *               [2] flagged pixels in examined blocks, [3] pixels healed, [4] flagged pixels in skipped blocks, [5] sum over healed blocks
+ *               of |dx - C1x| + |dy - C1y|
+ *   link_stats_row  int64 [ARSEG_LINK_NSTATS], 8-byte aligned, may be NULL: row f of the chain's counters, CORRECTED so that afterwards it
+ *               equals what a recount of the new link_f would give: for every healed pixel its old flags and its old hop bin are
+ *               subtracted and hop bin 1 is added
+ * All integers: two runs are bit-equal.  Two launches on one stream (decide: a wave per block, writes decisions, sad and stats only, so no
+ * block reads what another has healed; apply: rewrites the pixels).  Enqueue only: no workspace, no allocation, no host synchronisation;
+ * a captured graph replays it.
+ * ARSEG_EINVAL before any launch: a null cur, key, merged_f, link_f or decisions; H or W outside 1 .. 8192; B outside {8, 16}; r outside
+ * 1 .. 3; lambda or intra outside 0 .. 255; flag_mask outside 1 .. 7; min_flagged outside 1 .. 64; a plane base that is not 4-byte aligned,
+ * a pitch that is no multiple of 4 or below (W + 3) & ~3; merged_f not 4-byte aligned; decisions not 16-byte aligned; sad not 4-byte
+ * aligned; stats or link_stats_row not 8-byte aligned.
+ * Not covered: drift of UNFLAGGED pixels (the anchor's job, for estimated records), healing on a frame other than 0, blocks other than 8
+ * and 16, chroma, sub-pel vectors.
+ * ------------------------------------------------------------------------------------------- */
+#define ARSEG_HEAL_NSTATS 6
+int arseg_mv_chain_heal_fwd(const uint8_t *cur, int64_t cur_pitch, const uint8_t *key, int64_t key_pitch, int H, int W, int B, int r, int lambda,
+                            int intra, int flag_mask, int min_flagged, int16_t *merged_f, uint8_t *link_f, int16_t *decisions, uint32_t *sad,
+                            int64_t *stats, int64_t *link_stats_row, arseg_stream_t stream);
 /* layout changes at the API boundary */
 int arseg_nchw_to_nhwc_fwd(const float *in, float *out, int N, int C, int HW, int out_ld, arseg_stream_t stream);
 int arseg_nhwc_to_nchw_fwd(const float *in, int in_ld, float *out, int N, int C, int HW, arseg_stream_t stream);
