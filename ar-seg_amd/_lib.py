@@ -30,6 +30,7 @@ MVR_BI_LIST0, MVR_BI_NEAR, MVR_BI_MEAN = 0, 1, 2
 CONF_TOP1, CONF_MARGIN = 0, 1
 CONF_NSTATS = 2 + 32      # ARSEG_CONF_NSTATS: sum of codes, low count, 32 class areas
 TC_NSTATS = 3 + 3 * 32    # ARSEG_TC_NSTATS: compared, outside, void, then 32 each of cur_k, ref_k, inter_k
+ST_NSTATS = 8 + 2 * 32    # ARSEG_ST_NSTATS: unlinked, outside, void, weak, agree, held, own, one reserved word, then 32 each of into_k, from_k
 LINK_INTRA, LINK_UNCOVERED, LINK_CLAMPED = 1, 2, 4      # ARSEG_LINK_*: flag bits of a link byte; bits 4..7 = hops to the keyframe
 LINK_NSTATS = 4 + 16      # ARSEG_LINK_NSTATS: pixels with INTRA, UNCOVERED, CLAMPED, any flag, then 16 hop bins
 BM_INTRA_REF = 16         # ARSEG_BM_INTRA_REF: the reference index an estimated intra block carries (unusable for every max_ref <= 16)
@@ -171,6 +172,8 @@ PROTOTYPES = {
     "arseg_labels_consistency_fwd": (c_int, [_P, c_int64, c_int64] + [c_int] * 4 + [_P, c_int64, c_int64, _P, _P, c_int64, c_int64, _P, _STREAM]),
     "arseg_labels_consistency_linked_fwd": (c_int, [_P, c_int64, c_int64] + [c_int] * 4 + [_P, c_int64, c_int64, _P, _P, c_int64, c_int64, _P,
                                                     _P, c_int64, c_int64, c_uint8, _P, _STREAM]),
+    "arseg_segment_stabilise_fwd": (c_int, [_P] + [c_int] * 7 + [_P, c_int64, c_int64, _P, _P, _P, c_int64, c_int64, c_uint8, _P, c_int64, c_int64,
+                                            c_int, _P, _P, c_int64, c_int64, _P, c_int64, c_int64, _P, _STREAM]),
     "arseg_labels_rle_fwd": (c_int, [_P, c_int64, c_int64, c_int, c_int, c_int, _P, _P, c_int64, _STREAM]),
     "arseg_rle_decode_fwd": (c_int, [_P, _P, c_int64, c_int, c_int, c_int, _P, c_int64, c_int64, _STREAM]),
     "arseg_rle_regions_workspace_bytes": (c_size_t, [c_int, c_int64]),

@@ -12,6 +12,10 @@
   (0 agree / 255 differ / 128 not compared), the label plane and per-frame counters (compared / outside / void, per-class areas and
   intersections), one launch of ``ops.segment_consistency`` (csrc/consistency.hip); ``consistency_of_planes`` takes label planes instead
   of logits, ``tc_table`` turns the counters into agreement and temporal-consistency mIoU, ``ConsistencyMonitor`` into refresh reports.
+* ``stabilise``: the label plane with the keyframe prior applied -- a pixel whose class differs from the keyframe's class at the
+  motion-compensated position keeps the keyframe's where its own margin is below a threshold and the link is trustworthy; the label plane,
+  an 8-bit hold plane (0 agree / 255 held / 192 own / 128 no prior) and per-frame counters, one launch of ``ops.segment_stabilise``
+  (csrc/stabilise.hip); ``hold_bonus`` decays the threshold with the keyframe distance, ``hold_table`` reads the counters.
 
 * ``rle`` / ``rle_of_planes``: the mask as run-length codes -- per frame the rows' run offsets and one 32-bit word ``(x_first << 8) | value``
   per run, counted, scanned and compacted on the GPU (``ops.labels_rle``, csrc/rle.hip) without a host synchronisation, so a few KB per
@@ -295,6 +299,75 @@ class ConsistencyMonitor(object):
         too_little = compared / n_pixels < self.min_compared_share
         disagrees = compared > 0 and agree / compared < self.min_agreement
         return bool(too_little or disagrees)
+
+
+HOLD_OUTCOMES = ("unlinked", "outside", "void", "weak", "agree", "held", "own")          # the order of the contract and of the counters
+
+
+def stabilise(logits, ref_labels, mv_q, H, W, bonus, link=None, link_mask=_lib.LINK_INTRA | _lib.LINK_UNCOVERED, ref_conf=None, ref_low=0,
+              labels_out=True, hold_out=None, stats=True, lut=None, align_corners=True):
+    """Head logits [N,n_cls,h,w] + the keyframe's mask + the motion back to it -> (labels8 | None, hold8 | None, stats | None): the labels of
+    ``labels8`` with the keyframe prior applied, one launch and one pass over the logits (``ops.segment_stabilise``, csrc/stabilise.hip).
+
+    ``ref_labels`` and ``mv_q`` as ``consistency`` takes them.  A pixel whose own class k* differs from the class ``c_ref`` the keyframe had
+    at ``(y + round(mvy / 4), x + round(mvx / 4))`` keeps ``c_ref`` where its decision is marginal: where ``v[k*] - v[c_ref] < bonus`` on the
+    resized logits (strict, fp32; false for a NaN).  ``bonus``: the hold threshold in logit units, one float for all frames or an fp32 [N]
+    tensor on the device (``hold_bonus`` makes one per keyframe distance); 0 or less holds nothing, and the labels are ``labels8``'s.
+    No prior is offered where the target lies off the frame, where the keyframe is void (>= n_cls), where ``link`` (uint8 [N,H,W], the
+    planes of ``ingest.MotionChain(track_links=True).link()``) has a bit of ``link_mask``, or where ``ref_conf`` (uint8 [H,W], [1,H,W] or
+    [N,H,W]: the keyframe's ``confidence`` plane) is below ``ref_low`` (0..256) at the target.
+    ``labels_out`` / ``hold_out``: a uint8 [N,H,W] buffer, or True to have one allocated; None = not wanted.  ``hold8``: 0 agree, 255 held,
+    192 own (differs and is kept), 128 no prior.  ``stats``: an int64 [N, _lib.ST_NSTATS] tensor to accumulate into, or True for a zeroed
+    one; None = no statistics; ``hold_table`` reads its rows.  With a tensor ``bonus`` and the caller's buffers nothing is allocated and
+    nothing synchronises.  The planes feed ``rle_of_planes``, ``regions``, ``links``, ``absorb``, ``contours``, overlays and
+    ``consistency_of_planes`` unchanged; with the same gates the latter's agreeing count is ``agree + held`` of ``stats``."""
+    logits = _check_logits(logits)
+    N = logits.shape[0]
+    ref_labels = _ref_planes(ref_labels, N)
+    if ref_conf is not None:
+        if not torch.is_tensor(ref_conf) or ref_conf.dim() not in (2, 3):
+            raise ValueError("expected the reference's confidence plane as a uint8 tensor [H,W], [1,H,W] or [N,H,W]")
+        ref_conf = ref_conf[None] if ref_conf.dim() == 2 else ref_conf
+    if not torch.is_tensor(bonus):
+        bonus = torch.full((N,), float(bonus), dtype=torch.float32, device=logits.device)
+    labels_out = _plane_if_true(labels_out, N, H, W, logits.device)
+    hold_out = _plane_if_true(hold_out, N, H, W, logits.device)
+    if stats is True:
+        stats = torch.zeros((N, _lib.ST_NSTATS), dtype=torch.int64, device=logits.device)
+    ops.segment_stabilise(logits, ref_labels, mv_q, H, W, bonus, align_corners=align_corners, lut=lut, link=link, link_mask=link_mask,
+                          ref_conf=ref_conf, ref_low=ref_low, labels_out=labels_out, hold_out=hold_out, stats=stats)
+    return labels_out, hold_out, stats
+
+
+def hold_bonus(distances, bonus0, half_life, device=None) -> torch.Tensor:
+    """The usual decay of the hold threshold with the distance to the keyframe: ``bonus0 * 2 ** (-d / half_life)`` per entry of
+    ``distances`` (frames since the keyframe, >= 0), computed in float64 and rounded once -> an fp32 tensor of their shape (on ``device``),
+    ``stabilise``'s ``bonus``.  ``bonus0`` >= 0 in logit units, ``half_life`` > 0 in frames; both finite."""
+    d = np.asarray(distances, dtype=np.float64)
+    bonus0, half_life = float(bonus0), float(half_life)
+    if d.ndim > 1 or not np.isfinite(d).all() or (d < 0).any():
+        raise ValueError(f"hold_bonus: distances must be finite and >= 0 (a number or a list), got {distances!r}")
+    if not np.isfinite(bonus0) or bonus0 < 0 or not np.isfinite(half_life) or half_life <= 0:
+        raise ValueError(f"hold_bonus: bonus0 >= 0 and half_life > 0, both finite, got {bonus0!r}, {half_life!r}")
+    return torch.from_numpy(np.atleast_1d(bonus0 * np.exp2(-d / half_life)).astype(np.float32)).to(device if device is not None else "cpu")
+
+
+def hold_table(stats, n_cls):
+    """Rows of ``stabilise``'s statistics (a tensor, an array or lists, [N, _lib.ST_NSTATS]) -> {"shares": {outcome: [N]} for the seven
+    ``HOLD_OUTCOMES`` (each count over the row's total), "held_of_differing": [N] = held / (held + own), "into": int64 [N, n_cls] (held
+    pixels by the keyframe's class they took), "from": int64 [N, n_cls] (by the class they gave up)}; float64 numpy arrays, NaN for 0 / 0."""
+    s = np.asarray(stats.cpu() if torch.is_tensor(stats) else stats, dtype=np.int64)
+    if s.ndim == 1:
+        s = s[None]
+    n_cls = int(n_cls)
+    if s.ndim != 2 or s.shape[1] != _lib.ST_NSTATS or not 1 <= n_cls <= 32:
+        raise ValueError(f"hold_table: expected rows of {_lib.ST_NSTATS} counters and 1..32 classes, got {s.shape}, {n_cls}")
+    counts = s[:, :7].astype(np.float64)
+    total, differing = counts.sum(axis=1), counts[:, 5] + counts[:, 6]
+    with np.errstate(divide="ignore", invalid="ignore"):
+        shares = {name: np.where(total > 0, counts[:, i] / total, np.nan) for i, name in enumerate(HOLD_OUTCOMES)}
+        held = np.where(differing > 0, counts[:, 5] / differing, np.nan)
+    return {"shares": shares, "held_of_differing": held, "into": s[:, 8:8 + n_cls].copy(), "from": s[:, 40:40 + n_cls].copy()}
 
 
 class RleFrames(object):

@@ -1236,6 +1236,30 @@ def alter_res_batch_consistency_linked(lr_net, ref_ps, imgs, mv_qs, key_labels, 
     return change, labels, stats, unlinked
 
 
+def alter_res_batch_stabilised(lr_net, ref_ps, imgs, mv_qs, key_labels, bonus, scale=0.5, link=None, link_mask=_lib.LINK_INTRA | _lib.LINK_UNCOVERED,
+                               key_conf=None, ref_low=0, lut=None, hold_out=None, stats=True):
+    """``alter_res_batch_consistency``'s sibling that acts on what it measures: the same phase 1 and phase 2 and the same route decision,
+    then ``egress.stabilise`` against ``key_labels`` (the keyframe's TRAIN-ID plane) through ``mv_qs`` with the hold threshold ``bonus``
+    (a float or fp32 [B] on the device; ``egress.hold_bonus``) -> (labels uint8 [B,H,W], hold8 uint8 [B,H,W] | None, stats int64
+    [B, ST_NSTATS] | None).  ``link`` / ``link_mask``: the chain's link planes of the frames and the flags that gate (None: no gate);
+    ``key_conf`` / ``ref_low``: the keyframe's ``egress.confidence`` plane and the code below which it offers no prior (None: no gate);
+    ``lut``, ``hold_out`` and ``stats`` as ``egress.stabilise`` takes them.  With ``bonus <= 0`` the labels equal ``alter_res_batch_render``'s."""
+    from . import egress
+    lr_net = _unwrap(lr_net)
+    B, _, H, W = imgs.shape
+    h, w = _downscale_hw(H, W, scale)
+    feat = lr_net.phase1_nhwc4(ops.ingest_input(imgs, h, w, lr_net.storage_dtype), aux=ops.config.aux_outputs)[-1]
+    fused_up = hasattr(lr_net, "out_upsample")
+    if fused_up:
+        lo, _ = lr_net.phase2_warp(feat, list(ref_ps), mv_qs, upsample=False)
+        if (8 * lo.shape[-2], 8 * lo.shape[-1]) != (H, W):
+            lo, fused_up = ops.resize_nchw(lo, 8 * lo.shape[-2], 8 * lo.shape[-1], _lib.BILINEAR, False), False
+    else:
+        lo, _ = lr_net.phase2_warp(feat, list(ref_ps), mv_qs)
+    return egress.stabilise(lo, key_labels, mv_qs, H, W, bonus, link=link, link_mask=link_mask, ref_conf=key_conf, ref_low=ref_low, labels_out=True,
+                            hold_out=hold_out, stats=stats, lut=lut, align_corners=not fused_up)
+
+
 def alter_res_batch_rle(lr_net, ref_ps, imgs, mv_qs, capacity, scale=0.5, lut=None, labels_out=True):
     """``alter_res_batch_render``'s sibling for run-length coded masks: the same phase 1 and phase 2 and the same route decision
     (BiSeNet's 1/8-resolution head logits with align_corners=False when the frame is exactly 8x the head, align_corners=True otherwise),

@@ -1,6 +1,8 @@
 """The output half of the pipeline: head logits -> an 8-bit label plane and / or the frame with the classes painted over it, one ABI call
 (include/arseg_hip.h, arseg_segment_egress_fwd; csrc/egress.hip); head logits -> an 8-bit confidence plane, the label plane and per-frame
-statistics, one ABI call (arseg_segment_confidence_fwd; csrc/confidence.hip); an 8-bit plane <-> its row-run code, one ABI call each
+statistics, one ABI call (arseg_segment_confidence_fwd; csrc/confidence.hip); head logits, the keyframe's label plane and the motion back to
+it -> the label plane held to the keyframe's where the frame's own decision is marginal, one ABI call (arseg_segment_stabilise_fwd;
+csrc/stabilise.hip); an 8-bit plane <-> its row-run code, one ABI call each
 (arseg_labels_rle_fwd / arseg_rle_decode_fwd; csrc/rle.hip); a row-run code -> its connected regions, one ABI call (arseg_rle_regions_fwd;
 csrc/regions.hip); the regions of two frames -> their links along the motion, one ABI call (arseg_region_links_fwd; csrc/links.hip); a row-run
 code and its regions -> the code with the small regions absorbed into their neighbours, one ABI call (arseg_rle_absorb_fwd; csrc/absorb.hip);
@@ -286,6 +288,59 @@ def labels_consistency_linked(labels: torch.Tensor, ref_labels: torch.Tensor, mv
            ref_pitch, ref_ns, _ptr(mv_q), _ptr(change_out), chg_pitch, chg_ns, _ptr(stats), _ptr(link), link_pitch, link_ns, link_mask,
            _ptr(unlinked), _stream(), nbytes=(7 + (change_out is not None)) * N * H * W)
     return change_out, stats, unlinked
+
+
+def segment_stabilise(logits: torch.Tensor, ref_labels: torch.Tensor, mv_q: torch.Tensor, H: int, W: int, bonus: torch.Tensor, *,
+                      align_corners: bool = True, lut=None, link: Optional[torch.Tensor] = None, link_mask: int = 0,
+                      ref_conf: Optional[torch.Tensor] = None, ref_low: int = 0, labels_out: Optional[torch.Tensor] = None,
+                      hold_out: Optional[torch.Tensor] = None, stats: Optional[torch.Tensor] = None):
+    """The keyframe prior along the motion chain (include/arseg_hip.h, arseg_segment_stabilise_fwd): logits, ``ref_labels`` and ``mv_q`` as
+    ``segment_consistency`` takes them; ``bonus`` fp32 [N] on the device, the hold threshold of each frame in logit units; ``link`` uint8
+    [N,H,W] with ``link_mask`` as ``labels_consistency_linked`` takes them (None or a zero mask: no gate); ``ref_conf`` uint8 [1,H,W] or
+    [N,H,W], the reference's confidence codes, with ``ref_low`` 0..256 (None or 0: no gate) -> any non-empty subset of: ``labels_out``
+    (uint8 [N,H,W]: the reference's class where the pixel is HELD, ``k*`` otherwise, through ``lut``), ``hold_out`` (uint8 [N,H,W]: 0 agree,
+    255 held, 192 own, 128 no prior) and ``stats`` (int64 [N, ST_NSTATS], contiguous, ACCUMULATED INTO: the seven outcome counts, a
+    reserved word, then 32 each of into_k, from_k over the held pixels), in one launch and one pass over the logits.  Allocates nothing:
+    every output is the caller's, so the call can be captured in a HIP graph.  Returns (labels_out, hold_out, stats)."""
+    what = "segment_stabilise"
+    _need_gpu(logits)
+    if logits.dim() != 4 or not logits.is_contiguous():
+        raise _lib.ArsegError(f"{what} expects contiguous fp32 logits [N,n_cls,h,w], got {tuple(logits.shape)}")
+    N, n_cls, h, w = logits.shape
+    H, W, link_mask, ref_low = int(H), int(W), int(link_mask), int(ref_low)
+    dev = logits.device
+    if labels_out is None and hold_out is None and stats is None:
+        raise ValueError(f"{what}: nothing to write (labels_out, hold_out and stats are all None)")
+    if not 0 <= link_mask <= 255:
+        raise ValueError(f"{what}: link_mask is a byte, got {link_mask}")
+    if not 0 <= ref_low <= 256:
+        raise ValueError(f"{what}: ref_low is a code threshold in 0..256, got {ref_low}")
+    ref_pitch, ref_ns, _, _ = _tc_common(what, N, H, W, n_cls, dev, ref_labels, mv_q, None, None)
+    hold_pitch, hold_ns = _out_plane(what, "hold_out", hold_out, N, H, W, dev)
+    lab_pitch, lab_ns = _out_plane(what, "labels_out", labels_out, N, H, W, dev)
+    _dense(what, "bonus", bonus, torch.float32, (N,), dev)
+    if stats is not None:
+        _dense(what, "stats", stats, torch.int64, (N, _lib.ST_NSTATS), dev)
+    link_pitch = link_ns = conf_pitch = conf_ns = 0
+    if link is not None:
+        _need_gpu(link, dtype=torch.uint8)
+        if tuple(link.shape) != (N, H, W) or link.device != dev:
+            raise _lib.ArsegError(f"{what}: link must be uint8 {(N, H, W)} on {dev}, got {tuple(link.shape)} on {link.device}")
+        link_pitch, link_ns = _plane_layout(link, (W,), f"{what} link")
+    if ref_conf is not None:
+        _need_gpu(ref_conf, dtype=torch.uint8)
+        if ref_conf.dim() != 3 or tuple(ref_conf.shape[1:]) != (H, W) or ref_conf.shape[0] not in (1, N) or ref_conf.device != dev:
+            raise ValueError(f"ref_conf must be uint8 {(1, H, W)} (shared) or {(N, H, W)} on {dev}, got {tuple(ref_conf.shape)} on {ref_conf.device}")
+        conf_pitch, conf_ns = _plane_layout(ref_conf, (W,), f"{what} ref_conf")
+        if ref_conf.shape[0] == 1 and N > 1:
+            conf_ns = 0                                       # one plane for all N frames
+    lut_c = None if lut is None else _host_u8(lut, n_cls, "lut")
+    planes = (hold_out is not None) + (labels_out is not None)
+    launch(what, _lib.load().arseg_segment_stabilise_fwd, _ptr(logits), N, n_cls, h, w, H, W, 1 if align_corners else 0, _ptr(ref_labels),
+           ref_pitch, ref_ns, _ptr(mv_q), _ptr(bonus), _ptr(link), link_pitch, link_ns, link_mask, _ptr(ref_conf), conf_pitch, conf_ns, ref_low,
+           lut_c, _ptr(labels_out), lab_pitch, lab_ns, _ptr(hold_out), hold_pitch, hold_ns, _ptr(stats), _stream(),
+           nbytes=logits.numel() * 4 + (5 + (link is not None) + (ref_conf is not None) + planes) * N * H * W)
+    return labels_out, hold_out, stats
 
 
 _RUN_DTYPES = tuple(d for d in (torch.int32, getattr(torch, "uint32", None)) if d is not None)          # one 32-bit word per run, either sign

@@ -1127,6 +1127,56 @@ int arseg_labels_consistency_linked_fwd(const uint8_t *labels_in, int64_t in_pit
                                         int64_t *unlinked, arseg_stream_t stream);
 
 /* ---------------------------------------------------------------------------------------------
+ * The keyframe prior along the motion chain (csrc/stabilise.hip): the actuator for what the consistency counters measure.  Where the motion
+ * link of a pixel is trustworthy and the frame's own decision is marginal, the pixel keeps the class the keyframe had at the
+ * motion-compensated position.  One launch for N frames and one pass over the logits; the output is an ordinary labels8 plane.
+ *   logits, N, n_cls, h, w, H, W, align_corners, lut, pitches and image strides; ref_labels, ref_pitch, ref_image_stride (0: one plane for all
+ *               N frames); mv_q: exactly as arseg_segment_consistency_fwd takes them, with its three routes and its route choice (that of
+ *               arseg_argmax_confusion_fwd).  k*, m = v_{k*} and the blended class values v_k of a pixel are those of the one label rule
+ *               (csrc/arseg_device.h).  Target of pixel (x, y): tx = x + round_half_even_div4(mvx), ty = y + round_half_even_div4(mvy), NO clamp.
+ *   bonus       fp32 [N] ON THE DEVICE, 4-byte aligned: the hold threshold beta_n of frame n in logit units (on the device so that a captured
+ *               graph can be replayed with new values)
+ *   link, link_pitch, link_image_stride, link_mask: as in arseg_labels_consistency_linked_fwd; link == NULL or link_mask == 0 turns the gate off
+ *   ref_conf    uint8 confidence codes of the reference (arseg_segment_confidence_fwd's conf8 of the keyframe), conf_pitch / conf_image_stride
+ *               with the conventions of ref_labels (stride 0: one plane for all N frames); NULL turns the gate off
+ *   ref_low     0 .. 256: a pixel whose reference code, read at the same target, is < ref_low offers no prior (0: no pixel)
+ *   per pixel   exactly one of seven outcomes, decided in this order:
+ *                 0 UNLINKED  link & link_mask != 0; neither mv_q nor the reference is read
+ *                 1 OUTSIDE   (tx, ty) is not in [0, W) x [0, H); the reference planes are not read
+ *                 2 VOID      c_ref = ref_labels[ty][tx] >= n_cls
+ *                 3 WEAK      ref_conf[ty][tx] < ref_low
+ *                 4 AGREE     c_ref == k*
+ *                 5 HELD      m - v_{c_ref} < beta_n: strict, in fp32, false when an operand is NaN (a NaN logit, -inf - -inf, a NaN beta);
+ *                             so beta <= 0 holds nothing, and n_cls == 1 never holds
+ *                 6 OWN       otherwise
+ *               The label of the pixel is c_ref for HELD and k* otherwise.
+ * Outputs, any non-empty subset (NULL = not wanted):
+ *   labels_out  uint8 [N][H][W], labels_pitch / labels_image_stride in bytes; value = lut ? lut[label] : label (lut: HOST pointer to n_cls bytes)
+ *   hold_out    uint8 [N][H][W], hold_pitch / hold_image_stride alike: 0 AGREE, 255 HELD, 192 OWN, 128 for the outcomes 0 .. 3; nothing past
+ *               a row's last sample is written
+ *   stats       int64 [N][ARSEG_ST_NSTATS] on the device, ACCUMULATED INTO; for frame n
+ *                 stats[n][o]      += pixels with outcome o, o = 0 .. 6 (they sum to H W per launch); stats[n][7] is reserved and untouched
+ *                 stats[n][8 + k]  += HELD pixels with c_ref == k     (into_k)
+ *                 stats[n][40 + k] += HELD pixels with k* == k        (from_k)           k < n_cls; the other entries are untouched
+ *               Integers: independent of the order of the atomic adds, so two runs are bit-equal; stats alone equals the stats of the same
+ *               call with planes.  With the same gates, AGREE + HELD is the agreeing count arseg_labels_consistency_linked_fwd finds on
+ *               labels_out: agreement along the chain can only rise.
+ * The output buffers must not overlap each other or any input.
+ * Enqueue only: no allocation, no synchronisation.  ARSEG_EINVAL, before any launch: everything arseg_segment_consistency_fwd refuses (with
+ * hold_out in the place of change_out); a null or misaligned bonus; ref_low outside 0 .. 256; with a link, link_pitch < W or a negative
+ * link_image_stride; with a ref_conf, conf_pitch < W or a negative conf_image_stride.
+ * Not covered: a plane form (without logits there is no margin), consecutive-frame recurrence (the chain holds motion to the keyframe only).
+ * (A backward-compatible addition: ARSEG_ABI_VERSION stays.)
+ * ------------------------------------------------------------------------------------------- */
+#define ARSEG_ST_NSTATS (8 + 2 * 32)
+int arseg_segment_stabilise_fwd(const float *logits, int N, int n_cls, int h, int w, int H, int W, int align_corners,
+                                const uint8_t *ref_labels, int64_t ref_pitch, int64_t ref_image_stride, const int16_t *mv_q,
+                                const float *bonus, const uint8_t *link, int64_t link_pitch, int64_t link_image_stride, uint8_t link_mask,
+                                const uint8_t *ref_conf, int64_t conf_pitch, int64_t conf_image_stride, int ref_low,
+                                const uint8_t *lut, uint8_t *labels_out, int64_t labels_pitch, int64_t labels_image_stride,
+                                uint8_t *hold_out, int64_t hold_pitch, int64_t hold_image_stride, int64_t *stats, arseg_stream_t stream);
+
+/* ---------------------------------------------------------------------------------------------
  * Run-length coded label planes (csrc/rle.hip): the 8-bit planes above (labels8, change8, conf8) are a few thousand constant runs per
  * frame, and what leaves the GPU for a bus, a database or a browser is run-length codes.  Encoded and decoded on the device, without a host
  * synchronisation, so both calls can be captured in a HIP graph.
