@@ -36,6 +36,7 @@ LINK_NSTATS = 4 + 16      # ARSEG_LINK_NSTATS: pixels with INTRA, UNCOVERED, CLA
 BM_INTRA_REF = 16         # ARSEG_BM_INTRA_REF: the reference index an estimated intra block carries (unusable for every max_ref <= 16)
 BM_NSTATS = 4             # ARSEG_BM_NSTATS: intra blocks, matched blocks with the zero vector, sum of SAD and pixels of the matched blocks
 BMA_NSTATS = 4            # ARSEG_BMA_NSTATS: anchored blocks, anchored blocks whose hop was unusable, blocks kept on their hop, drift corrected in pixels
+BMS_NSTATS = 6            # ARSEG_BMS_NSTATS: parents split, unusable parents split, child records matched and intra, summed gain of the split usable parents, matched pixels
 HEAL_NSTATS = 6           # ARSEG_HEAL_NSTATS: examined blocks, healed blocks, flagged pixels examined, pixels healed, flagged pixels skipped, drift of the healed
 FILL_NSTATS = 3 + 3 * 256 # ARSEG_FILL_NSTATS: gaps, excess, changed, then 256 each of ref_area, fill_area, both
 
@@ -159,6 +160,7 @@ PROTOTYPES = {
     "arseg_block_motion_pyr_workspace_bytes": (c_size_t, [c_int, c_int, c_int, c_int]),
     "arseg_block_motion_pyr_fwd": (c_int, [_P, _P] + [c_int] * 9 + [_P, _P, _P, _P, c_size_t, _STREAM]),
     "arseg_block_motion_anchor_fwd": (c_int, [_P, c_int64, _P, c_int64] + [c_int] * 7 + [_P, _P, _P, _P, _P, _STREAM]),
+    "arseg_block_motion_split_fwd": (c_int, [_P, c_int64, _P, c_int64] + [c_int] * 7 + [_P, _P, _P, _P, _STREAM]),
     "arseg_mv_chain_heal_fwd": (c_int, [_P, c_int64, _P, c_int64] + [c_int] * 8 + [_P, _P, _P, _P, _P, _P, _STREAM]),
     "arseg_nchw_to_nhwc_fwd": (c_int, [_P, _P, c_int, c_int, c_int, c_int, _STREAM]),
     "arseg_nhwc_to_nchw_fwd": (c_int, [_P, c_int, _P, c_int, c_int, c_int, _STREAM]),

@@ -20,6 +20,8 @@
   arseg_luma_pyramid_*, arseg_block_motion_pyr_*; ``luma_pyramid_numpy`` and ``block_motion_pyr_numpy`` on the host).
   ``MotionEstimator(anchor_refine=...)`` checks every block's composed displacement against the keyframe and re-anchors it there
   (csrc/block_motion_anchor.hip; arseg_block_motion_anchor_fwd; ``block_motion_anchor_numpy`` on the host).
+  ``MotionEstimator(split_refine=...)`` splits a 16 x 16 block that straddles two motions into 8 x 8 children with vectors of their own
+  (csrc/block_motion_split.hip; arseg_block_motion_split_fwd; ``block_motion_split_numpy`` on the host).
 * intra and uncovered pixels of any chain, whoever made its records: ``ChainHealer`` matches the flagged pixels of a pushed frame against the
   keyframe and rewrites ``merged`` / ``link`` in place (csrc/mv_chain_heal.hip; arseg_mv_chain_heal_fwd; ``mv_chain_heal_numpy`` on the host).
 """
@@ -913,6 +915,80 @@ def block_motion_anchor_numpy(cur, key, records, merged_prev, f: int, B: int = 1
     return np.ascontiguousarray(out.reshape(-1, 8).astype(np.int16)), np.where(anchored, sad, -1).reshape(-1).astype(np.int64), stats
 
 
+BMS_NSTATS = _lib.BMS_NSTATS          # ARSEG_BMS_NSTATS: parents split, unusable parents split, children matched / intra, summed gain, matched pixels
+
+
+def block_motion_split_numpy(cur, ref, records, r: int = 2, lam: int = 2, intra: int = 255, split_gain: int = 32, ref_index: int = 0):
+    """The quad-tree split of include/arseg_hip.h (arseg_block_motion_split_fwd) on the host: ``cur`` / ``ref`` are uint8 luma planes [H,W],
+    ``records`` the int16 [by*bx,8] records of the B = 16 grid (``block_motion_numpy``, ``block_motion_pyr_numpy``).  Returns ``(children int16
+    [4*by*bx,8], child_sad uint32 [4*by*bx], stats int64 [BMS_NSTATS])`` -- what ``ops.block_motion_split`` writes, stats from zero;
+    ``np.concatenate([records, children])`` is the list a chain takes.  numpy only, one gather of the frame per centre and offset."""
+    a, k = luma8_numpy(cur).astype(np.int32), luma8_numpy(ref).astype(np.int32)
+    r, lam, intra, split_gain, ref_index = int(r), int(lam), int(intra), int(split_gain), int(ref_index)
+    H, W = a.shape
+    if k.shape != a.shape:
+        raise ValueError(f"block_motion_split_numpy: the current frame is {a.shape}, the reference {k.shape}")
+    if not (1 <= H <= 8192 and 1 <= W <= 8192) or not 1 <= r <= 3 or not 0 <= lam <= 255 or not 0 <= intra <= 255 or not 0 <= split_gain <= 65535 \
+            or not 0 <= ref_index <= 15:
+        raise ValueError(f"block_motion_split_numpy: H, W in 1..8192, r in 1..3, lam and intra in 0..255, split_gain in 0..65535, ref_index in 0..15; got "
+                         f"{H}x{W}, r {r}, lam {lam}, intra {intra}, split_gain {split_gain}, ref_index {ref_index}")
+    by, bx = -(-H // 16), -(-W // 16)
+    rec = np.asarray(records)
+    if rec.dtype != np.int16 or rec.shape != (by * bx, 8):
+        raise ValueError(f"block_motion_split_numpy: {H}x{W} in blocks of 16 is int16 [{by * bx},8] records, got {rec.dtype} {rec.shape}")
+    q = rec.astype(np.int64).reshape(by, bx, 8)
+    px0, py0 = (np.arange(bx) * 16)[None, :], (np.arange(by) * 16)[:, None]
+    pw, ph = np.minimum(16, W - px0), np.minimum(16, H - py0)
+    Px, Py = _round_half_even_div4(q[..., 4]), _round_half_even_div4(q[..., 5])
+    usable = (q[..., 6] == ref_index) & (np.abs(Px) <= 500) & (np.abs(Py) <= 500) & (px0 + Px >= 0) & (px0 + pw + Px <= W) & (py0 + Py >= 0) \
+        & (py0 + ph + Py <= H)
+    # the children that exist are the blocks of the B = 8 grid: child (ci, cj) is child 2 (ci & 1) + (cj & 1) of parent (ci >> 1, cj >> 1)
+    cby, cbx = -(-H // 8), -(-W // 8)
+    ci, cj = np.arange(cby), np.arange(cbx)
+    pi, pj = ci >> 1, cj >> 1
+    ni, nj = pi + np.where(ci & 1, 1, -1), pj + np.where(cj & 1, 1, -1)
+    oki, okj = (ni >= 0) & (ni < by), (nj >= 0) & (nj < bx)
+    ni, nj = np.clip(ni, 0, by - 1), np.clip(nj, 0, bx - 1)
+    yes, zero = np.ones((cby, cbx), dtype=bool), np.zeros((cby, cbx), dtype=np.int64)
+    own = (Px[pi][:, pj], Py[pi][:, pj], usable[pi][:, pj])
+    centres = [(zero, zero, yes), own,
+               (Px[pi][:, nj], Py[pi][:, nj], usable[pi][:, nj] & okj[None, :]),
+               (Px[ni][:, pj], Py[ni][:, pj], usable[ni][:, pj] & oki[:, None])]
+
+    def key_of(sad, dx, dy):
+        return ((sad + lam * (np.abs(dx) + np.abs(dy))) << 20) | np.where((dx == 0) & (dy == 0), 0, 1 + (dy + 511) * 1023 + (dx + 511))
+
+    best = _bm_best_key(a, k, 8, r, centres, key_of)
+    rank, cost = best & 0xfffff, best >> 20
+    dy = np.where(rank > 0, (rank - 1) // 1023 - 511, 0)
+    dx = np.where(rank > 0, (rank - 1) % 1023 - 511, 0)
+    sad = cost - lam * (np.abs(dx) + np.abs(dy))
+    at_p = np.where(own[2], _bm_best_key(a, k, 8, 0, [own], lambda s, dx, dy: s), 0)      # S_q(P): P is a candidate of every child of a usable parent
+    x0, y0 = (cj * 8)[None, :], (ci * 8)[:, None]
+    w, h = np.minimum(8, W - x0), np.minimum(8, H - y0)
+    matched = sad <= intra * (w * h)
+
+    def per_parent(v):                                                  # [cby,cbx] -> [by,bx,4], child q = 2 qy + qx last; 0 where the child does not exist
+        full = np.zeros((2 * by, 2 * bx), dtype=np.int64)
+        full[:cby, :cbx] = v
+        return full.reshape(by, 2, bx, 2).transpose(0, 2, 1, 3).reshape(by, bx, 4)
+
+    exists = per_parent(yes).astype(bool)
+    lhs = per_parent(at_p).sum(axis=2) + lam * (np.abs(Px) + np.abs(Py)) - per_parent(cost).sum(axis=2)
+    m = per_parent(matched).astype(bool)
+    split = np.where(usable, lhs > split_gain, m.any(axis=2))
+    row = np.zeros((cby, cbx, 8), dtype=np.int64)
+    row[..., 0], row[..., 1], row[..., 2], row[..., 3] = x0, y0, w, h
+    row[..., 4], row[..., 5], row[..., 6] = np.where(matched, 4 * dx, 0), np.where(matched, 4 * dy, 0), np.where(matched, ref_index, BM_INTRA_REF)
+    rows = np.stack([per_parent(row[..., c]) for c in range(8)], axis=-1)               # [by,bx,4,8]
+    write = split[..., None] & exists
+    children = np.where(write[..., None], rows, 0)
+    pixels = per_parent(np.where(matched, w * h, 0))
+    stats = np.array([split.sum(), (split & ~usable).sum(), (write & m).sum(), (write & ~m).sum(), lhs[split & usable].sum(), pixels[write & m].sum()],
+                     dtype=np.int64)
+    return np.ascontiguousarray(children.reshape(-1, 8).astype(np.int16)), per_parent(sad).reshape(-1).astype(np.uint32), stats
+
+
 HEAL_NSTATS = _lib.HEAL_NSTATS        # ARSEG_HEAL_NSTATS: examined blocks, healed blocks, flagged pixels examined, pixels healed, flagged pixels skipped, drift
 
 
@@ -1094,10 +1170,23 @@ class MotionEstimator(object):
     would compose for it (and of its neighbours' and the co-located one), and rewrites a block whose SAD is at most ``anchor_intra`` per
     pixel with ref = f - 1: target frame 0, one hop, this hop's flags only.  The chain needs ``max_ref`` >= its GOP's last frame index (at
     most 16).  The result is in ``anchored`` (a second record buffer; ``records`` keeps the hops), the counts in ``anchor_stats``.  With 0
-    nothing of this is allocated and every path above is launch for launch as before."""
+    nothing of this is allocated and every path above is launch for launch as before.
+
+    ``split_refine`` in 1 .. 3 adds the quad-tree split (csrc/block_motion_split.hip; arseg_block_motion_split_fwd; host form
+    ``block_motion_split_numpy``): one vector per 16 x 16 block warps part of a block that straddles two motions from the wrong place.
+    ``estimate`` then is the search plus one launch that searches the four 8 x 8 children of every block within +-``split_refine`` of the
+    block's and its neighbours' vectors and writes them as records of their own where they undercut the block's cost by more than
+    ``split_gain`` (0 .. 65535), or where an intra block has a child that matches.  It needs ``block=16`` and ``anchor_refine=0``.  One buffer
+    ``records_all`` int16 [5 n_blocks, 8] is allocated once; ``records`` is the view of its first n_blocks rows, where the search writes,
+    ``children`` the view of the rest, and ``estimate`` returns ``records_all``: the children have the higher indices and win their pixels, a
+    child row of a block that was not split is eight zeros and covers nothing, so the count is fixed and ``chain.push(est.estimate(cur,
+    prev))`` stays capturable.  With ``levels`` >= 1 the split reads level 0 of the two pyramids; with ``levels=0`` the frames' own luma
+    planes in place, which must be NV12 / I420 byte planes with a 4-byte aligned base and pitch.  The counts are in ``split_stats``;
+    ``with_sad=True`` also owns ``child_sad``.  With 0 nothing of this is allocated and every path above is launch for launch as before."""
 
     def __init__(self, H: int, W: int, block: int = 16, search: int = 16, lam: int = 2, intra: int = 255, ref_index: int = 0, device="cuda",
-                 with_sad: bool = False, levels: int = 0, refine: int = 1, anchor_refine: int = 0, anchor_intra: int = 255):
+                 with_sad: bool = False, levels: int = 0, refine: int = 1, anchor_refine: int = 0, anchor_intra: int = 255, split_refine: int = 0,
+                 split_gain: int = 32):
         self.H, self.W, self.block, self.search = int(H), int(W), int(block), int(search)
         self.lam, self.intra, self.ref_index = int(lam), int(intra), int(ref_index)
         self.levels, self.refine = int(levels), int(refine)
@@ -1109,11 +1198,24 @@ class MotionEstimator(object):
             raise _lib.ArsegError(str(e)) from None
         if not 0 <= self.anchor_refine <= 3 or not 0 <= self.anchor_intra <= 255:
             raise _lib.ArsegError(f"MotionEstimator: anchor_refine in 0..3 and anchor_intra in 0..255; got {self.anchor_refine}, {self.anchor_intra}")
+        self.split_refine, self.split_gain = int(split_refine), int(split_gain)
+        if not 0 <= self.split_refine <= 3 or not 0 <= self.split_gain <= 65535:
+            raise _lib.ArsegError(f"MotionEstimator: split_refine in 0..3 and split_gain in 0..65535; got {self.split_refine}, {self.split_gain}")
+        if self.split_refine and self.block != 16:
+            raise _lib.ArsegError(f"MotionEstimator: split_refine splits 16 x 16 blocks into 8 x 8 children and needs block=16, got block={self.block}")
+        if self.split_refine and self.anchor_refine:
+            raise _lib.ArsegError("MotionEstimator: split_refine and anchor_refine do not combine (splitting anchored records is not covered)")
         self.device = torch.device(device)
         if self.device.type != "cuda":
             raise _lib.ArsegError("MotionEstimator runs on the GPU only; there is no CPU fallback (block_motion_numpy is the host form)")
         self.n_blocks = -(-self.H // self.block) * -(-self.W // self.block)
-        self.records = torch.zeros((self.n_blocks, 8), dtype=torch.int16, device=self.device)
+        if self.split_refine:
+            self.records_all = torch.zeros((5 * self.n_blocks, 8), dtype=torch.int16, device=self.device)
+            self.records, self.children = self.records_all[:self.n_blocks], self.records_all[self.n_blocks:]
+            self.split_stats = torch.zeros(BMS_NSTATS, dtype=torch.int64, device=self.device)
+            self.child_sad = torch.zeros(4 * self.n_blocks, dtype=torch.int32, device=self.device) if with_sad else None
+        else:
+            self.records = torch.zeros((self.n_blocks, 8), dtype=torch.int16, device=self.device)
         self.stats = torch.zeros(BM_NSTATS, dtype=torch.int64, device=self.device)
         self.sad = torch.zeros(self.n_blocks, dtype=torch.int32, device=self.device) if with_sad else None
         if self.levels:
@@ -1146,11 +1248,18 @@ class MotionEstimator(object):
         ops.block_motion_pyr(pyr[0].buffer, pyr[1].buffer, self.H, self.W, self.levels, self.block, self.search, self.refine, self.lam, self.intra,
                              self.ref_index, records=self.records, sad=self.sad if self.sad is not None else False, stats=self.stats,
                              workspace=self._workspace)
-        return self.records
+        return self._split(pyr[0].level(0), pyr[1].level(0)) if self.split_refine else self.records
+
+    def _split(self, cur_plane, ref_plane) -> torch.Tensor:
+        """The split launch on the records the search has just written -> ``records_all``."""
+        ops.block_motion_split(cur_plane, ref_plane, self.records, self.split_refine, self.lam, self.intra, self.split_gain, self.ref_index,
+                               children=self.children, sad=self.child_sad if self.child_sad is not None else False, stats=self.split_stats)
+        return self.records_all
 
     def estimate(self, cur, ref) -> torch.Tensor:
-        """Two one-frame ``DecodedFrames`` of one format and of this estimator's size, on its device -> ``records`` (the same buffer every call).
-        With ``levels`` >= 1 either may be a built ``LumaPyramid`` instead, and the two frames may differ in format."""
+        """Two one-frame ``DecodedFrames`` of one format and of this estimator's size, on its device -> ``records`` (the same buffer every call);
+        with ``split_refine`` -> ``records_all``.  With ``levels`` >= 1 either may be a built ``LumaPyramid`` instead, and the two frames may
+        differ in format."""
         if self.levels:
             return self._estimate_pyr(cur, ref)
         for what, f in (("the current frame", cur), ("the reference frame", ref)):
@@ -1158,9 +1267,10 @@ class MotionEstimator(object):
                 raise _lib.ArsegError(f"MotionEstimator.estimate: {what} must be one DecodedFrames frame of {self.H}x{self.W}")
         if cur.src_format != ref.src_format:
             raise _lib.ArsegError(f"MotionEstimator.estimate: the frames differ in format ({cur.src_format} and {ref.src_format})")
+        planes = (self._aligned_luma(cur, "estimate"), self._aligned_luma(ref, "estimate")) if self.split_refine else None
         ops.block_motion(cur.luma_plane()[0], ref.luma_plane()[0], cur.src_format, self.block, self.search, self.lam, self.intra, self.ref_index,
                          records=self.records, sad=self.sad if self.sad is not None else False, stats=self.stats)
-        return self.records
+        return self._split(*planes) if self.split_refine else self.records
 
     def _aligned_luma(self, frame, who):
         """The uint8 luma plane [H,W] of a one-frame NV12 / I420 ``DecodedFrames`` if it meets the anchor's alignment rule."""
@@ -1210,6 +1320,16 @@ class MotionEstimator(object):
         self.stats.zero_()
         if self.anchor_refine:
             self.anchor_stats.zero_()
+        if self.split_refine:
+            self.split_stats.zero_()
+
+    def split_stats_row(self) -> torch.Tensor:
+        """int64 [BMS_NSTATS], accumulated since ``reset_stats``: blocks split, of those the intra blocks (healed), child records written matched
+        and intra, the summed gain of the split matched blocks, and the pixels in matched children.  A device tensor: reading it on the host
+        synchronises."""
+        if not self.split_refine:
+            raise _lib.ArsegError("MotionEstimator.split_stats_row: this estimator was made with split_refine=0")
+        return self.split_stats
 
     def anchor_stats_row(self) -> torch.Tensor:
         """int64 [BMA_NSTATS], accumulated since ``reset_stats``: anchored blocks, anchored blocks whose hop was unusable (healed), blocks kept on

@@ -26,7 +26,7 @@ from .conv import (SplitRows, _conv1x1_x3, _conv2d16, _conv_up2_taps, _conv_wino
                    psp_x3_foldable, split_rows)
 from .creff import creff, creff_warp, creff_warp_kernel, flow_resize, mv_resize, warp, warp_mvq
 from .egress import contours_fill, contours_simplify, contours_simplify_shared, tolerance_q, labels_consistency, labels_consistency_linked, labels_rle, region_links, rle_absorb, rle_contours, rle_decode, rle_regions, segment_confidence, segment_consistency, segment_egress, segment_stabilise
-from .layers import (_frame_ingest_planes, adaptive_avgpool, argmax_confusion, argmax_confusion_grouped, as_nchw, band_radii, block_motion, block_motion_anchor, block_motion_pyr, boundary_iou, boundary_radii, boundary_radius, calibration, cast, contour_f, contour_radii, contour_radius, frame_ingest, frame_ingest8, frame_ingest_yuv, frame_to_nhwc4, frame_u8_to_nhwc4, from_c8, global_reduce, head, ingest_input,
+from .layers import (_frame_ingest_planes, adaptive_avgpool, argmax_confusion, argmax_confusion_grouped, as_nchw, band_radii, block_motion, block_motion_anchor, block_motion_pyr, block_motion_split, boundary_iou, boundary_radii, boundary_radius, calibration, cast, contour_f, contour_radii, contour_radius, frame_ingest, frame_ingest8, frame_ingest_yuv, frame_to_nhwc4, frame_u8_to_nhwc4, from_c8, global_reduce, head, ingest_input,
                      is_nhwc_view, label_bands, local_similar, luma_pyramid, local_weighting, maxpool3x3s2, merge_motion, MV_BI_POLICIES, mv_link_reset, mv_records_bi_reset, mv_records_bi_step, mv_records_bi_step_link, mv_records_rasterize, mv_records_reset, mv_records_step,
                      mv_records_step_link, psp_pool_matrix, psp_prior_sum, resize_nchw, resize_nhwc,
                      mv_chain_heal, scale_add, to_c8, to_nchw_contiguous, to_nhwc)

@@ -727,6 +727,48 @@ def block_motion_anchor(cur_plane: torch.Tensor, key_plane: torch.Tensor, record
     return out, sad, stats
 
 
+def block_motion_split(cur_plane: torch.Tensor, ref_plane: torch.Tensor, records_in: torch.Tensor, r: int = 2, lam: int = 2, intra: int = 255,
+                       split_gain: int = 32, ref_index: int = 0, children: Optional[torch.Tensor] = None, sad=None, stats=None):
+    """Splits estimated 16 x 16 block records into 8 x 8 children where that pays (include/arseg_hip.h, arseg_block_motion_split_fwd): the four
+    children of every parent of ``records_in`` (int16 [n,8], the B = 16 grid of ``block_motion``) are searched in ``ref_plane`` within +-r of
+    (0, 0), of the parent's vector and of its neighbours' on the child's side; a parent is split where its children's costs undercut its own
+    by more than ``split_gain``, an intra parent where a child matches.  ``children`` int16 [4 n,8] gets a record per child of a split parent
+    and eight zeros -- a record that covers nothing -- everywhere else, so ``records_in`` followed by ``children`` is one list of 5 n records
+    for ``mv_records_step``.  The planes are as ``block_motion_anchor`` takes them.  ``children`` / ``sad`` (uint32 [4 n]: every existing
+    child's SAD) / ``stats`` (int64 [BMS_NSTATS], accumulated into) with ``block_motion``'s conventions.  ``children`` must not overlap
+    ``records_in``.  One launch, no synchronisation; with all three buffers passed in, no allocation.  Returns (children, sad, stats)."""
+    H, W, dev, cur_pitch, ref_pitch = _aligned_luma_pair("block_motion_split", cur_plane, ref_plane)
+    r, lam, intra, split_gain, ref_index = int(r), int(lam), int(intra), int(split_gain), int(ref_index)
+    if not 1 <= r <= 3 or not 0 <= lam <= 255 or not 0 <= intra <= 255 or not 0 <= split_gain <= 65535 or not 0 <= ref_index <= 15:
+        raise _lib.ArsegError(f"block_motion_split: r in 1..3, lam and intra in 0..255, split_gain in 0..65535, ref_index in 0..15; got r {r}, lam {lam}, "
+                              f"intra {intra}, split_gain {split_gain}, ref_index {ref_index}")
+    n = -(-H // 16) * -(-W // 16)
+    if _mv_records(records_in, "block_motion_split") != n or records_in.device != dev:
+        raise _lib.ArsegError(f"block_motion_split: {H}x{W} in blocks of 16 is {n} records on {dev}, got {tuple(records_in.shape)} on {records_in.device}")
+    if children is None:
+        children = torch.empty((4 * n, 8), dtype=torch.int16, device=dev)
+    elif _mv_records(children, "block_motion_split") != 4 * n or children.device != dev:
+        raise _lib.ArsegError(f"block_motion_split: {n} parents have {4 * n} child records on {dev}, got {tuple(children.shape)} on {children.device}")
+    if sad is None:
+        sad = torch.empty(4 * n, dtype=torch.int32, device=dev)
+    elif sad is False:
+        sad = None
+    elif not torch.is_tensor(sad) or sad.dtype not in (torch.int32, torch.uint32) or sad.device != dev or sad.numel() != 4 * n or not sad.is_contiguous():
+        raise _lib.ArsegError(f"block_motion_split expects sad as a contiguous int32 (uint32 bits) tensor of {4 * n} elements on {dev}")
+    if stats is None:
+        stats = torch.zeros(_lib.BMS_NSTATS, dtype=torch.int64, device=dev)
+    elif stats is False:
+        stats = None
+    elif not torch.is_tensor(stats) or stats.dtype != torch.int64 or stats.device != dev or stats.numel() != _lib.BMS_NSTATS or not stats.is_contiguous():
+        raise _lib.ArsegError(f"block_motion_split expects stats as a contiguous int64 tensor of {_lib.BMS_NSTATS} elements on {dev}")
+    lo, hi = records_in.data_ptr(), records_in.data_ptr() + 16 * n
+    if children.data_ptr() < hi and lo < children.data_ptr() + 64 * n:
+        raise _lib.ArsegError("block_motion_split: children must not overlap records_in (neighbour parents are read while the children are written)")
+    launch("block_motion_split", _lib.load().arseg_block_motion_split_fwd, _ptr(cur_plane), cur_pitch, _ptr(ref_plane), ref_pitch, H, W, r, lam, intra,
+           split_gain, ref_index, _ptr(records_in), _ptr(children), _ptr(sad), _ptr(stats), _stream())
+    return children, sad, stats
+
+
 def mv_chain_heal(cur_plane: torch.Tensor, key_plane: torch.Tensor, merged_f: torch.Tensor, link_f: torch.Tensor, B: int = 16, r: int = 2, lam: int = 2,
                   intra: int = 20, flag_mask: int = _lib.LINK_INTRA | _lib.LINK_UNCOVERED, min_flagged: int = 1, decisions: Optional[torch.Tensor] = None,
                   sad=None, stats=None, link_stats_row=None):

@@ -715,8 +715,8 @@ int arseg_mv_records_bi_step_link_fwd(const int16_t *records, int n_records, int
  * intra outside 0 .. 255; ref_index outside 0 .. 15; an unknown src_format; a pitch below the row's bytes (W, 2 W for the 16-bit formats,
  * 3 W for RGB8); a pitch or plane pointer that is odd with a 16-bit format; records not 16-byte, sad not 4-byte, stats not 8-byte aligned.
  * ARSEG_EWORKSPACE: workspace_bytes below arseg_block_motion_workspace_bytes(H, W, B, R).
- * Not covered: sub-pel refinement (the chain rounds every hop to whole pixels), variable block sizes, two references per block, chroma.
- * (Reach beyond 32 pixels: the hierarchical search below.)
+ * Not covered: sub-pel refinement (the chain rounds every hop to whole pixels), variable block sizes (16 x 16 blocks split into 8 x 8 where
+ * that pays: arseg_block_motion_split_fwd below), two references per block, chroma.  (Reach beyond 32 pixels: the hierarchical search below.)
  * ------------------------------------------------------------------------------------------- */
 #define ARSEG_BM_INTRA_REF 16
 #define ARSEG_BM_NSTATS 4
@@ -767,7 +767,8 @@ int arseg_block_motion_fwd(const void *cur, int64_t cur_pitch, const void *ref, 
  * 16-byte aligned; records not 16-byte, sad not 4-byte, stats not 8-byte aligned; pyramid_bytes below arseg_luma_pyramid_bytes(H, W, levels).
  * ARSEG_EWORKSPACE: workspace_bytes below arseg_block_motion_pyr_workspace_bytes(H, W, B, levels).
  * Not covered: sub-pel refinement, predictors from the previous frame's field or from spatial neighbours at the same level, variable block
- * sizes, two references per block, chroma, more than three levels, caching pyramids across calls (a caller keeps the buffers it built).
+ * sizes (arseg_block_motion_split_fwd below splits the level-0 records), two references per block, chroma, more than three levels, caching
+ * pyramids across calls (a caller keeps the buffers it built).
  * ------------------------------------------------------------------------------------------- */
 size_t arseg_luma_pyramid_bytes(int H, int W, int levels);
 int arseg_luma_pyramid_fwd(const void *plane, int64_t pitch, int src_format, int H, int W, int levels, uint8_t *pyramid, size_t pyramid_bytes,
@@ -886,6 +887,56 @@ int arseg_block_motion_anchor_fwd(const uint8_t *cur, int64_t cur_pitch, const u
 int arseg_mv_chain_heal_fwd(const uint8_t *cur, int64_t cur_pitch, const uint8_t *key, int64_t key_pitch, int H, int W, int B, int r, int lambda,
                             int intra, int flag_mask, int min_flagged, int16_t *merged_f, uint8_t *link_f, int16_t *decisions, uint32_t *sad,
                             int64_t *stats, int64_t *link_stats_row, arseg_stream_t stream);
+
+/* ---------------------------------------------------------------------------------------------
+ * Quad-tree split of estimated block motion (csrc/block_motion_split.hip).  The estimators above give every 16 x 16 block one vector, so a
+ * block that straddles the border of a moving object warps part of its pixels from the wrong place.  This entry searches the four 8 x 8
+ * children of every 16 x 16 parent around the parent's and its neighbours' vectors and, where four vectors explain the block better than
+ * one by more than split_gain, writes them as records of their own.  A caller pushes records_in || children as ONE list of 5 nb records to
+ * arseg_mv_records_step_*: the children have the higher indices, so they win their pixels, and a row that was not split covers nothing.
+ *   cur, ref    luma8 byte planes [H][W] of the current and of the reference frame; alignment and pitch exactly as
+ *               arseg_block_motion_anchor_fwd: the base 4-byte aligned, the pitch a multiple of 4 and at least (W + 3) & ~3; the bytes of a
+ *               row beyond W never count.  Level 0 of a luma pyramid and an aligned NV12 / I420 luma plane qualify.  H, W in 1 .. 8192
+ *   parents     the B = 16 grid of arseg_block_motion_fwd: nb = by bx records in records_in, parent (bi, bj) is record b = bi bx + bj with
+ *               x0 = 16 bj, y0 = 16 bi, w = min(16, W - x0), h = min(16, H - y0).  Of records_in only fields 4, 5 and 6 are read.  Parent
+ *               b is USABLE iff field 6 == ref_index AND P(b) = round_half_even_div4 of fields 4 and 5 has |Px|, |Py| <= 500 AND the
+ *               parent's block displaced by P lies inside the reference frame (0 <= x0 + Px, x0 + w + Px <= W, likewise y).  Every record
+ *               the estimators above write that is not intra meets all three; hand-made records may not
+ *   children    child q = 2 qy + qx of parent (bi, bj): x0 = 16 bj + 8 qx, y0 = 16 bi + 8 qy, w = min(8, W - x0), h = min(8, H - y0); it
+ *               EXISTS iff w > 0 and h > 0
+ *   centres     of an existing child, in this order: C0 = (0, 0); C1 = P(b), if b is usable; C2 = P of parent (bi, bj + (qx ? 1 : -1)), if
+ *               that parent is in the grid and usable; C3 = P of parent (bi + (qy ? 1 : -1), bj), likewise
+ *   candidates  the level-0 refinement's of arseg_block_motion_pyr_fwd: the union (a vector proposed twice counts once) of centre +
+ *               (ox, oy), |ox| <= r and |oy| <= r, r in 1 .. 3, whose displaced child lies inside the reference frame.  Nothing is padded
+ *               or clamped.  (0, 0) always is one, and so is P(b) of a usable parent
+ *   cost        SAD + lambda (|dx| + |dy|), lambda in 0 .. 255
+ *   winner      the smallest (cost, rank): rank(0, 0) = 0, otherwise rank = 1 + (dy + 511) 1023 + (dx + 511).  (|d| <= 503, so rank < 2^20
+ *               and cost < 2^19: the refinement's 64-bit key.)  Per child: the winner (dx_q, dy_q), SAD_q, cost_q; for a usable parent
+ *               also S_q(P), the child's SAD at the parent's vector.  A child is MATCHED iff SAD_q <= intra w h, intra in 0 .. 255
+ *   decision    usable parent: split iff (sum_q S_q(P) + lambda (|Px| + |Py|)) - sum_q cost_q > split_gain, the sums over the existing
+ *               children, the compare signed, split_gain in 0 .. 65535.  Four vectors pay lambda four times: the intended bias against
+ *               splitting.  Unusable parent (intra): split iff at least one existing child is matched
+ *   children    int16 [4 nb][8], 16-byte aligned; EVERY row is written every call, so the count is fixed for a captured graph.  Row
+ *               4 b + q: split parent, existing and matched child: (x0, y0, w, h, 4 dx_q, 4 dy_q, ref_index, 0); split parent, existing
+ *               child, not matched: (x0, y0, w, h, 0, 0, ARSEG_BM_INTRA_REF, 0); otherwise eight zeros (w = 0 covers nothing)
+ *   child_sad   uint32 [4 nb], may be NULL: SAD_q of every existing child of every parent, split or not; 0 for a child that does not exist
+ *   stats       int64 [ARSEG_BMS_NSTATS], 8-byte aligned, may be NULL; ACCUMULATED INTO: [0] parents split, [1] of those the unusable
+ *               parents (healed), [2] child records written matched, [3] child records written intra, [4] sum of the decision's left-hand
+ *               side over split usable parents, [5] pixels covered by matched children
+ *   records_in  read only; children must not overlap it.  Overlapping buffers are refused.
+ * All integers: two runs are bit-equal.  Enqueue only: one launch, no workspace, no allocation, no host synchronisation; a captured graph
+ * replays it.
+ * ARSEG_EINVAL before any launch: a null cur, ref, records_in or children; H or W outside 1 .. 8192; r outside 1 .. 3; lambda or intra
+ * outside 0 .. 255; split_gain outside 0 .. 65535; ref_index outside 0 .. 15; a plane base that is not 4-byte aligned, a pitch that is no
+ * multiple of 4 or below (W + 3) & ~3; records_in or children not 16-byte aligned, child_sad not 4-byte aligned, stats not 8-byte aligned;
+ * overlapping record buffers.
+ * Not covered: splitting below 8 x 8, and 16 x 8 / 8 x 16 partitions; splitting anchored records, or any use together with the keyframe
+ * anchor; a split triggered by one child's error alone while the summed gain stays at or below split_gain; sub-pel vectors, chroma.
+ * ------------------------------------------------------------------------------------------- */
+#define ARSEG_BMS_NSTATS 6
+int arseg_block_motion_split_fwd(const uint8_t *cur, int64_t cur_pitch, const uint8_t *ref, int64_t ref_pitch, int H, int W, int r, int lambda,
+                                 int intra, int split_gain, int ref_index, const int16_t *records_in, int16_t *children, uint32_t *child_sad,
+                                 int64_t *stats, arseg_stream_t stream);
 /* layout changes at the API boundary */
 int arseg_nchw_to_nhwc_fwd(const float *in, float *out, int N, int C, int HW, int out_ld, arseg_stream_t stream);
 int arseg_nhwc_to_nchw_fwd(const float *in, int in_ld, float *out, int N, int C, int HW, arseg_stream_t stream);
